@@ -13,9 +13,15 @@ processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT 
 process imports torch or touches a GPU; the parent only waits and relays rank 0's JSON line.  Under
 torchrun (WORLD_SIZE set) it is a rank.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` (the 3x3 conv family,
-HIP-event timed inside the engine on the launching stream) and `cpu_baseline` (the CPU oracle --
-test infrastructure -- timed on this box's host cores, N=1 only).
+Prints ONE JSON line (rank 0) with the driver's contract.  A plain run does only what that line needs: set-up, W warm-up
+steps, the K timed steps, the outputs (--dump-outputs DIR) and the line.  --full adds everything else: `roofline` (the 3x3
+conv family, HIP-event timed inside the engine on the launching stream during the timed steps), `host_path` (the host-buffer
+rates), `secondary` (the 512x512 row) and `cpu_baseline` (the CPU oracle -- test infrastructure -- timed on the host's CPU
+cores, N=1 only); each of them can still be dropped with its --no-* switch.
+
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32, or float64 where the
+path returns float64), at most DUMP_BUDGET bytes in all: an output larger than its share is a fixed seeded sample of its
+elements.  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Other workloads of the same path (--workload): `fusion` = cfg 3 (3 views restored -- one per rank of a
 fusion group when N >= 3 -- gathered point-to-point, aligned and blended); `classify` = the 7-score
@@ -36,6 +42,7 @@ sys.path.insert(0, ROOT)
 MFMA_BF16_PEAK_TFLOPS = 2500.0  # dense bf16, /opt/skills/guides/MI355X_MICROARCH.md chip table
 MFMA_FP8_PEAK_TFLOPS = 5000.0   # dense fp8 (block-scaled MFMA), same table
 HBM_PEAK_GBS = 8000.0
+DUMP_BUDGET = 48 << 20          # --dump-outputs: bytes of array data per rank, all outputs together
 
 
 def parse_args(argv=None):
@@ -58,8 +65,13 @@ def parse_args(argv=None):
     ap.add_argument("--profile-all", action="store_true", help="time every kernel family (more events, ~5 %% slower)")
     ap.add_argument("--profile-every", type=int, default=4, help="time the dominant family's launches on every N-th timed step (an event record is a packet "
                     "between two kernels: on every step it costs 1.35 %% of the step); 1 = every step")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the in-engine kernel timing "
+                    "(roofline), the host-buffer path, the 512x512 sub-record and the CPU baseline (each can still be dropped with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned in its last step as DIR/<name>.npy")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)   # tests only: gloo + a sleep instead of the GPU step
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.size is None:
         args.size = 2048 if args.workload == "tiled" else 1024
     return args
@@ -240,6 +252,29 @@ def per_level_roofline(groups, steps, counters=None):
                                        "1.0 = every layer on whichever table roofline binds it"}
 
 
+def dump_outputs(dirname, arrays, suffix="", budget=DUMP_BUDGET):
+    """Write each array of `arrays` ({name: torch tensor or numpy array}) as dirname/<name><suffix>.npy: float64 stays float64,
+    everything else becomes float32 (exact for the u8 / i32 outputs here).  Smallest first, each array gets an equal share of the
+    `budget` bytes still left; one that is larger is written as a sample of its elements -- flattened, at positions drawn from a
+    generator seeded by its name and sorted -- so the same arguments give the same positions on every run."""
+    import zlib
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    out = {}
+    for name, t in arrays.items():
+        a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    left = budget
+    for k, name in enumerate(sorted(out, key=lambda n: (out[n].nbytes, n))):
+        a = out[name]
+        cap = left // (len(out) - k) // a.itemsize
+        if a.size > cap:
+            pos = np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, cap, replace=False)
+            a = a.reshape(-1)[np.sort(pos)]
+        left -= a.nbytes
+        np.save(os.path.join(dirname, name + suffix + ".npy"), a)
+
+
 class Ctx:
     """Rank context: distributed state + the timing contract (sharding.timed_region)."""
 
@@ -279,6 +314,11 @@ class Ctx:
         if before is not None:
             before()
         return self.sharding.timed_region(step, self.args.steps, self.sync)
+
+    def dump(self, arrays):
+        """--dump-outputs: this rank's outputs of the last timed step (<name>_rank<r>.npy when N > 1)."""
+        if self.args.dump_outputs:
+            dump_outputs(self.args.dump_outputs, arrays, "_rank%d" % self.rank if self.world > 1 else "")
 
     def close(self):
         if self.world > 1:
@@ -335,6 +375,7 @@ def run_restore(ctx, eng):
     jpeg = torch.ones(hi - lo, dtype=torch.uint8, device=ctx.dev)
     out = torch.empty_like(x)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]    # per-step GPU time, no host sync inside
+    profile = a.full and not a.no_profile      # the extras below are --full only: a plain run is set-up, warm-up, timed steps, line
 
     def step(i):
         if i >= 0:
@@ -344,7 +385,7 @@ def run_restore(ctx, eng):
             marks[a.steps].record()
 
     def start_profile():                       # after the warm-up: the in-engine per-kernel event timing covers the timed steps only
-        if not a.no_profile:
+        if profile:
             eng.profile_reset()
             eng.profile_enable(1 if a.profile_all else 2 | (max(1, a.profile_every) << 8))
 
@@ -352,12 +393,13 @@ def run_restore(ctx, eng):
         a.profile_every = 1          # (with several lanes a step is several passes of the network: every one of them is timed)
     n_prof = a.steps if a.profile_all else len(range(0, a.steps, max(1, a.profile_every)))     # timed steps whose launches carry events
     dt = ctx.timed(step, before=start_profile)
+    ctx.dump({"restored": out})                # every step writes `out` from the same input: it holds the last step's images
     prof = None
-    if not a.no_profile:
+    if profile:
         eng.profile_enable(0)
         prof = {f: eng.profile_query(f) for f in ("conv3x3", "conv1x1", "stem", "head", "classifier", "gn_finalize", "all")}
         report = eng.profile_report()
-    hp_ranks = host_path_ranks(ctx, eng, S, B) if (ctx.world > 1 and not a.no_host_path) else None      # every rank takes part
+    hp_ranks = host_path_ranks(ctx, eng, S, B) if (ctx.world > 1 and a.full and not a.no_host_path) else None      # every rank takes part
     if ctx.rank != 0:
         return
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps))
@@ -399,13 +441,13 @@ def run_restore(ctx, eng):
         }
         res["roofline"].update(per_level_roofline(groups, n_prof, (tr or {}).get("per_group")))
         res["whole_net_mfma_frac"] = (f3 + f1) * B * a.steps / dt / 1e12 / MFMA_BF16_PEAK_TFLOPS
-    if ctx.world == 1 and not a.no_host_path:
+    if ctx.world == 1 and a.full and not a.no_host_path:
         res["host_path"] = host_path(eng, S, B)
     elif hp_ranks is not None:
         res["host_path"] = {"all_ranks_closed_loop": hp_ranks}
-    if ctx.world == 1 and not a.no_secondary and S == 1024:
+    if ctx.world == 1 and a.full and not a.no_secondary and S == 1024:
         res["secondary"] = {"cfg1_512": secondary_512(ctx, eng, B)}
-    if ctx.world == 1 and not a.no_cpu_baseline:
+    if ctx.world == 1 and a.full and not a.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(S)
     print(json.dumps(res))
 
@@ -447,15 +489,17 @@ def run_classify(ctx, eng):
     lo, hi = ctx.sharding.shard_range(B * ctx.world, ctx.rank, ctx.world)
     x = torch.from_numpy(synth.batch(hi - lo, S, S, start=lo)).to(ctx.dev)
     jp = torch.ones(hi - lo, dtype=torch.uint8, device=ctx.dev)
+    last = {}
 
     def step(i):
-        eng.classify_tensor(x, jp)
+        last["scores"], last["labels"] = eng.classify_tensor(x, jp)
 
     def start_profile():
         eng.profile_reset()
         eng.profile_enable(1)
 
     dt = ctx.timed(step, before=start_profile)
+    ctx.dump(last)
     eng.profile_enable(0)
     pf = eng.profile_query("classifier")
     if ctx.rank == 0:
@@ -482,27 +526,31 @@ def run_fusion(ctx, eng):
     views_np = synth.fusion_views(S, S, seed=7 + (groups.index(mine) if mine else 100 + ctx.rank))
     jp1 = torch.ones(1, dtype=torch.uint8, device=ctx.dev)
     jp3 = torch.ones(3, dtype=torch.uint8, device=ctx.dev)
+    last = {}                                   # what the fusing rank (or a lone rank) receives from the last step
     if mine is not None:
         view = torch.from_numpy(np.ascontiguousarray(views_np[mine.index(ctx.rank)])).to(ctx.dev)
 
         def step(i):
-            sh.restore_views_and_fuse(
+            fused = sh.restore_views_and_fuse(
                 view, mine, mine[0],
                 restore=lambda v: eng.restore_tensor(v[None], scores=None, is_jpeg_u8=jp1)[0],
                 fuse=lambda vs: eng.fuse_tensor(torch.stack(vs, 0), noise_score=-1.0)[0])
+            if fused is not None:
+                last["fused"] = fused
     else:
         views = torch.from_numpy(np.ascontiguousarray(views_np)).to(ctx.dev)
         buf = torch.empty_like(views)
 
         def step(i):
             eng.restore_tensor(views, buf, scores=None, is_jpeg_u8=jp3)
-            eng.fuse_tensor(buf, noise_score=-1.0)
+            last["fused"], last["shifts"] = eng.fuse_tensor(buf, noise_score=-1.0)
 
     def start_profile():
         eng.profile_reset()
         eng.profile_enable(1)
 
     dt = ctx.timed(step, before=start_profile)
+    ctx.dump(last)
     eng.profile_enable(0)
     pf = eng.profile_query("fusion")
     jobs = len(groups) + (ctx.world - 3 * len(groups))          # one fused image per group and per lone rank, per step

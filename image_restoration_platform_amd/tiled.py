@@ -96,8 +96,9 @@ def bench(ctx, eng, line, mfma_peak):
     jp = torch.ones(1, dtype=torch.uint8, device=ctx.dev)
     scores, _ = eng.classify_tensor(img[None], jp)
     f3, f1 = weights.conv_flops(S, S)
+    last = {}                       # bench.py --dump-outputs: what the last timed step returned
     if ctx.world == 1:
-        out = torch.empty_like(img)
+        out = last["restored"] = torch.empty_like(img)
 
         def step(i):
             eng.restore_tiled_tensor(img, a.strips, out_u8=out, scores=scores[0])
@@ -109,7 +110,8 @@ def bench(ctx, eng, line, mfma_peak):
         rows = split_rows(img, ctx.rank, ctx.world).contiguous()
 
         def step(i):
-            restore_strips_pipelined(sessions, [rows, rows], [scores[0], scores[0]], ctx.sharding, streams)
+            last["restored_strip_a"], last["restored_strip_b"] = restore_strips_pipelined(sessions, [rows, rows], [scores[0], scores[0]],
+                                                                                          ctx.sharding, streams)
             for st in streams:
                 torch.cuda.current_stream().wait_stream(st)
         par = ("%d row strips, one per GPU, 2 images in flight: one grouped P2P exchange per op (halo rows + GroupNorm partials) on each image's own "
@@ -120,6 +122,7 @@ def bench(ctx, eng, line, mfma_peak):
         eng.profile_enable(2)
 
     dt = ctx.timed(step, before=start_profile)
+    ctx.dump(last)
     eng.profile_enable(0)
     c3 = eng.profile_query("conv3x3")
     if ctx.rank == 0:

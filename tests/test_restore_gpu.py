@@ -283,7 +283,7 @@ def test_capacity_query_and_gauges(engine):
 
 def test_profiler_modes_and_sampled_passes(engine):
     """ire_profile_enable: mode 2 brackets the 3x3 conv family's launches (38 per pass of the network), `2 | N << 8` those of every
-    N-th pass only (what bench.py's default run does: an event record is a packet between two kernels); the per-group report adds
+    N-th pass only (what `bench.py --full` does: an event record is a packet between two kernels); the per-group report adds
     up to the family's totals; profiling changes no pixel."""
     imgs = synth.batch(2, 128, 128, start=7)
     ref = engine.restore(imgs)

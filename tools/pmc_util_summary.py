@@ -33,7 +33,7 @@ for k, c in agg.items():
                  100.0 * c.get("SQ_WAIT_INST_ANY", 0) / max(c.get("SQ_WAVE_CYCLES", 1), 1)))
 with open(dst, "w") as f:
     f.write("# " + title + " — PMC counters per kernel, default bench step (1024x1024 bs 8)\n\n"
-            "four separate `rocprofv3 --pmc` passes of `python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-profile`\n"
+            "four separate `rocprofv3 --pmc` passes of `python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-profile`\n"
             "(2 steps traced; no trace domain combined with `--pmc`).  `MfmaUtil` = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE per XCD x 1024 SIMDs):\n"
             "the counter equals #MFMA x 32 cycles exactly (checked against the launch's FLOPs), so this is the achieved fraction of the MFMA\n"
             "pipe AT THE CLOCK THE KERNEL RAN AT (column GHz; profiled passes run a few % slower than unprofiled ones).\n"

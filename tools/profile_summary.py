@@ -4,7 +4,7 @@
   python tools/profile_summary.py traffic <fetch_counter_collection.csv> <write_counter_collection.csv> <out.json> <steps>
 
 `traffic`: FETCH_SIZE and WRITE_SIZE come from two separate `rocprofv3 --pmc` passes of
-`python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-profile` (2 steps traced).  Units are KiB; on gfx950
+`python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-profile` (2 steps traced).  Units are KiB; on gfx950
 FETCH_SIZE reports half of the bytes of wide coalesced reads and is doubled (MI355X_MICROARCH.md, HBM / rocprofv3 section).
 The conv3x3 family = every 3x3 conv kernel the engine's profiler counts in that family (conv_rb without the HEAD
 instantiation, conv_w4 / conv_f8, conv_up -- which since round 2 carries the composed 1x1 fuse -- conv_down, and the 3x3
@@ -92,7 +92,7 @@ def traffic(fetch_csv, write_csv, dst, steps):
     steps = int(steps)
     fe, wr = _sum(fetch_csv, "FETCH_SIZE"), _sum(write_csv, "WRITE_SIZE")
     out = {
-        "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-profile",
+        "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-profile",
         "unit_note": "counters are KiB; FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 reports 1/2 of wide coalesced reads); WRITE_SIZE as is",
         "family": "conv3x3 (conv_pc_kernel / conv_rb_kernel without their HEAD instantiation, conv_w4_kernel, conv_f8_kernel, conv_up_kernel, conv_upq_kernel, conv_dnq_kernel, conv_down_kernel; the v1 stride-2 conv_mfma_kernel instantiation where a switch selects it)",
         "per_kernel": {},

@@ -3,20 +3,20 @@
 set -e
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r02_v4; mkdir -p $O
 cd $R
-timeout -k 10 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err
-timeout -k 10 200 python bench.py --no-profile --no-cpu-baseline > $O/bench_noprofile.json 2>> $O/bench_default.err
-timeout -k 10 200 python bench.py --size 512 --no-cpu-baseline > $O/bench_512.json 2>> $O/bench_default.err
+timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 200 python bench.py --full --no-profile --no-cpu-baseline > $O/bench_noprofile.json 2>> $O/bench_default.err
+timeout -k 10 200 python bench.py --full --size 512 --no-cpu-baseline > $O/bench_512.json 2>> $O/bench_default.err
 timeout -k 10 200 python bench.py --workload tiled --steps 10 --no-cpu-baseline > $O/bench_tiled_bf16.json 2>> $O/bench_default.err
 timeout -k 10 200 python bench.py --workload tiled --precision fp8 --steps 10 --no-cpu-baseline > $O/bench_tiled_fp8.json 2>> $O/bench_default.err
 timeout -k 10 200 python bench.py --workload fusion --steps 10 --no-cpu-baseline > $O/bench_fusion.json 2>> $O/bench_default.err
 timeout -k 10 200 python bench.py --workload classify --steps 50 --no-cpu-baseline > $O/bench_classify.json 2>> $O/bench_default.err
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats -o r --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/stats.log 2>&1
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o r --output-format csv -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-profile > $O/pmc_fetch.log 2>&1
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write -o r --output-format csv -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-profile > $O/pmc_write.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats -o r --output-format csv -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/stats.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o r --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-profile > $O/pmc_fetch.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write -o r --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-profile > $O/pmc_write.log 2>&1
 i=0
 for set in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VALU" "SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_SALU"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $set -d $O/pmc/p$i -o r --output-format csv -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-profile > $O/pmc_p$i.log 2>&1 || echo "pass $i failed"
+  timeout -k 10 300 rocprofv3 --pmc $set -d $O/pmc/p$i -o r --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-profile > $O/pmc_p$i.log 2>&1 || echo "pass $i failed"
 done
 for f in $O/bench_*.json; do echo $f; cut -c1-200 $f; done

@@ -4,7 +4,7 @@ set -e
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r03_bs; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for b in 1 2 4 8; do
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/b$b -o r --output-format csv -- python3 $R/bench.py --batch $b --steps 10 --warmup 2 --no-cpu-baseline --no-host-path --no-profile > $O/b$b.log 2>&1
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/b$b -o r --output-format csv -- python3 $R/bench.py --full --batch $b --steps 10 --warmup 2 --no-cpu-baseline --no-host-path --no-profile > $O/b$b.log 2>&1
   echo "batch $b"; tail -1 $O/b$b.log | cut -c1-160
   python3 - $O/b$b $b <<'PY'
 import csv, glob, sys

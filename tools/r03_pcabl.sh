@@ -4,7 +4,7 @@ for v in 0 1 2 4 8 16 32 3 7 15; do
   touch image_restoration_platform_amd/csrc/conv_pc.hip
   env C3_ABL=$v python -m image_restoration_platform_amd.build > /dev/null 2>&1 || { echo build failed; exit 1; }
   cd /tmp; export TMPDIR=/tmp; rm -rf $O/abl_$v
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/abl_$v -o r --output-format csv -- python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-host-path --no-profile > $O/abl_$v.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/abl_$v -o r --output-format csv -- python3 $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-host-path --no-profile > $O/abl_$v.log 2>&1
   cd $R
   python3 - <<PY
 import csv, glob

@@ -1,7 +1,7 @@
 # GPU box: the whole -m gpu suite, the default bench, the codec seam rates, then workgroup timelines of conv_pc / conv_pk
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04_check2; mkdir -p $O; cd $R
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; rc=$?; tail -12 $O/pytest.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python - <<PY
 import json
 d=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04_check3; mkdir -p $O; cd $R
 timeout -k 10 900 python -m pytest tests/test_restore_gpu.py tests/test_tiled_gpu.py tests/test_node_adapter.py tests/test_serving.py -m gpu -x -q > $O/pytest.log 2>&1; rc=$?; tail -5 $O/pytest.log; [ $rc -eq 0 ] || exit $rc
 for i in 1 2 3; do
-timeout -k 10 300 python bench.py --no-cpu-baseline --no-host-path > $O/bench_$i.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-host-path > $O/bench_$i.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python - <<PY
 import json
 d=json.loads(open("$O/bench_$i.json").read().strip().splitlines()[-1])

@@ -12,7 +12,7 @@ echo "== host path, default"; timeout -k 10 300 python tools/host_path_rate.py 2
 echo "== host path, IRE_CPU_AFFINITY=off"; IRE_CPU_AFFINITY=off timeout -k 10 300 python tools/host_path_rate.py 2>&1 | grep -v "^$" | head -7 | tee $O/rate_off.txt
 timeout -k 10 900 python -m pytest tests/test_restore_gpu.py tests/test_tiled_gpu.py -x -q > $O/pytest.log 2>&1; rc=$?; tail -8 $O/pytest.log; [ $rc -eq 0 ] || exit $rc
 for pk in 1 0 1 0; do
-  IRE_PK=$pk timeout -k 10 200 python bench.py --no-cpu-baseline > $O/bench_pk$pk.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+  IRE_PK=$pk timeout -k 10 200 python bench.py --full --no-cpu-baseline > $O/bench_pk$pk.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
   python - <<PY
 import json
 d=json.loads(open("$O/bench_pk$pk.json").read().strip().splitlines()[-1])

@@ -5,23 +5,23 @@ set -e
 TAG=${1:-v1}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04_$TAG; mkdir -p $O
 cd $R
-timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err
-timeout -k 10 200 python bench.py --no-profile --no-cpu-baseline --no-host-path > $O/bench_noprofile.json 2>> $O/bench_default.err
-timeout -k 10 200 python bench.py --size 512 --no-cpu-baseline --no-host-path --no-secondary > $O/bench_512.json 2>> $O/bench_default.err
+timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 200 python bench.py --full --no-profile --no-cpu-baseline --no-host-path > $O/bench_noprofile.json 2>> $O/bench_default.err
+timeout -k 10 200 python bench.py --full --size 512 --no-cpu-baseline --no-host-path --no-secondary > $O/bench_512.json 2>> $O/bench_default.err
 timeout -k 10 200 python bench.py --workload tiled --steps 10 --no-cpu-baseline > $O/bench_tiled_bf16.json 2>> $O/bench_default.err
 timeout -k 10 200 python bench.py --workload tiled --precision fp8 --steps 10 --no-cpu-baseline > $O/bench_tiled_fp8.json 2>> $O/bench_default.err
 timeout -k 10 200 python bench.py --workload fusion --steps 10 --no-cpu-baseline > $O/bench_fusion.json 2>> $O/bench_default.err
 timeout -k 10 200 python bench.py --workload classify --steps 50 --no-cpu-baseline > $O/bench_classify.json 2>> $O/bench_default.err
 echo "benches done"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats -o r --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-path --no-secondary > $O/stats.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats -o r --output-format csv -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-host-path --no-secondary > $O/stats.log 2>&1
 echo "stats done"
 # kernel-trace rows of the secondary workloads (classifier, fusion incl. the batched entry, tiled bf16 / fp8, 512^2)
 for wl in "classify --steps 30" "fusion --steps 10" "tiled --steps 6" "tiled --precision fp8 --steps 6"; do
   tag=$(echo $wl | tr -d ' -' | cut -c1-16)
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats_$tag -o r --output-format csv -- python3 $R/bench.py --workload $wl --warmup 2 --no-cpu-baseline > $O/stats_$tag.log 2>&1 || echo "stats $tag failed"
 done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats_512 -o r --output-format csv -- python3 $R/bench.py --size 512 --steps 8 --warmup 2 --no-cpu-baseline --no-host-path > $O/stats_512.log 2>&1 || echo "stats 512 failed"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats_512 -o r --output-format csv -- python3 $R/bench.py --full --size 512 --steps 8 --warmup 2 --no-cpu-baseline --no-host-path > $O/stats_512.log 2>&1 || echo "stats 512 failed"
 echo "secondary stats done"
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o r --output-format csv -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-host-path --no-secondary --no-profile > $O/pmc_fetch.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write -o r --output-format csv -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-host-path --no-secondary --no-profile > $O/pmc_write.log 2>&1

@@ -5,7 +5,7 @@ if [ "$T" != "none" ]; then
 timeout -k 10 800 python -m pytest $T -x -q -m gpu > $O/ab_tests.log 2>&1; tail -8 $O/ab_tests.log
 fi
 for v in 1 0 1 0; do
-  env $VAR=$v timeout -k 10 200 python bench.py --no-cpu-baseline --profile-all > $O/ab_$v.json 2>> $O/ab_err.log || exit 1
+  env $VAR=$v timeout -k 10 200 python bench.py --full --no-cpu-baseline --profile-all > $O/ab_$v.json 2>> $O/ab_err.log || exit 1
   python - <<PY
 import json
 d=json.loads(open("gpurun_out/s2/ab_$v.json").read().strip().splitlines()[-1])

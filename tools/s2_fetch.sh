@@ -4,7 +4,7 @@ for v in ${ABL_VALUES:-0}; do
   cd $R; touch image_restoration_platform_amd/csrc/conv_pc.hip
   C3_ABL=$v python -m image_restoration_platform_amd.build > /dev/null 2>&1 || { echo build failed; exit 1; }
   cd /tmp; export TMPDIR=/tmp; rm -rf $O/fe_$v
-  timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $O/fe_$v -o r --output-format csv -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-profile > $O/fe_$v.log 2>&1
+  timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $O/fe_$v -o r --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-profile > $O/fe_$v.log 2>&1
   python3 - <<PY
 import csv, collections
 per = collections.defaultdict(lambda: [0.0, 0])

@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/s2; mkdir -p $O; cd $R
 timeout -k 10 800 python -m pytest tests/test_restore_gpu.py tests/test_tiled_gpu.py -x -q -m gpu ${1:+-k "$1"} > $O/q_tests.log 2>&1; tail -5 $O/q_tests.log
 for i in 1 2; do
-timeout -k 10 200 python bench.py --no-cpu-baseline --profile-all > $O/q_$i.json 2>> $O/q_err.log || exit 1
+timeout -k 10 200 python bench.py --full --no-cpu-baseline --profile-all > $O/q_$i.json 2>> $O/q_err.log || exit 1
 python - <<PY
 import json
 d=json.loads(open("gpurun_out/s2/q_$i.json").read().strip().splitlines()[-1])

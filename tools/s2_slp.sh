@@ -4,8 +4,8 @@ for v in 0 1 0 1; do
   cd $R; env IRE_SLP=$v python -m image_restoration_platform_amd.build > /dev/null 2>&1 || { echo build failed; exit 1; }
   if [ "$v" = 0 ] && [ ! -f /tmp/slp_tested ]; then timeout -k 10 900 python -m pytest tests/test_restore_gpu.py tests/test_tiled_gpu.py -x -q -m gpu > $O/slp_tests.log 2>&1; tail -3 $O/slp_tests.log; touch /tmp/slp_tested; fi
   cd /tmp; export TMPDIR=/tmp; rm -rf $O/slp_$v
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/slp_$v -o r --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/slp_$v.log 2>&1
-  cd $R; timeout -k 10 200 python bench.py --no-cpu-baseline --no-profile > $O/slp_$v.json 2>> $O/slp_err.log
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/slp_$v -o r --output-format csv -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/slp_$v.log 2>&1
+  cd $R; timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-profile > $O/slp_$v.json 2>> $O/slp_err.log
   python3 - <<PY
 import csv, glob, json
 f = glob.glob("$O/slp_$v/**/r_kernel_stats.csv", recursive=True)[0]

@@ -3,6 +3,6 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/s2; mkdir -p $O; cd $R
 touch image_restoration_platform_amd/csrc/conv_w4.hip image_restoration_platform_amd/csrc/conv_rb.hip
 env IRE_RB_ABLATE=2 python -m image_restoration_platform_amd.build > $O/stamps_build.log 2>&1 || { tail $O/stamps_build.log; exit 1; }
-env IRE_RB_STAMPS=$1 timeout -k 10 200 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-profile > $O/stamps.json 2> $O/stamps.err
+env IRE_RB_STAMPS=$1 timeout -k 10 200 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-profile > $O/stamps.json 2> $O/stamps.err
 awk '/^\[stamps\] wg 0 wave 0/{f=1} /^\[stamps\] wg 1/{f=0} f' $O/stamps.err | grep "stamps\|k-steps\|stage=" | awk '/stamps/{n=0} {if (n++ < 21) print}' 
 touch image_restoration_platform_amd/csrc/conv_w4.hip image_restoration_platform_amd/csrc/conv_rb.hip

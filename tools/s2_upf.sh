@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/s2; mkdir -p $O; cd $R
 timeout -k 10 600 python -m pytest tests/test_restore_gpu.py tests/test_tiled_gpu.py -x -q -m gpu > $O/upf_tests.log 2>&1; tail -15 $O/upf_tests.log
 for v in 1 0 1 0; do
-  IRE_UP_FUSE=$v timeout -k 10 200 python bench.py --no-cpu-baseline --profile-all > $O/upf_$v.json 2>> $O/upf_err.log || exit 1
+  IRE_UP_FUSE=$v timeout -k 10 200 python bench.py --full --no-cpu-baseline --profile-all > $O/upf_$v.json 2>> $O/upf_err.log || exit 1
   python - <<PY
 import json
 d=json.loads(open("gpurun_out/s2/upf_$v.json").read().strip().splitlines()[-1])

@@ -1,6 +1,7 @@
 // conv_pk.hip -- the C >= 128 ResBlock convolutions (16 launches, a third of a step) as a PRODUCER / CONSUMER workgroup with
-// 128-cout items: 12 waves per CU = three per SIMD, gfx950.  Round 4; conv_w4.hip stays as the A/B fallback (IRE_PK=0), for
-// pre-activated inputs, for fp8 and for launches whose workgroups would span more images than the coefficient table holds.
+// 128-cout items: 12 waves per CU = three per SIMD, gfx950.  Both convs of a ResBlock (the residual variant too, since round 5);
+// conv_w4.hip stays as the A/B fallback (IRE_PK=0), for pre-activated inputs, for fp8, for 64-cout items and for launches whose
+// workgroups would span more images than the coefficient table holds.
 //
 // Why (profiles/r04_experiments.md, workgroup timelines + profiles/r03_experiments.md stamps): conv_w4's 16-channel stage takes
 // ~6 400 ticks against 4 608 of matrix-pipe time -- its eight waves are the SAME program, each computing AND staging, and what a
@@ -21,6 +22,11 @@
 // + single-buffered fragments; the two consumer waves of a SIMD cover each other's fragment reads.
 // Same tiles, weight slabs (engine.cpp::make_conv d_w4), accumulation order, epilogue arithmetic and partials layout as conv_w4's
 // 8-wave fused form: bit-identical results (tests/test_restore_gpu.py holds the two schedules to equal bytes), row strips included.
+// Registers: no VGPR spill in the k-loop, the producers' transform or the epilogue (profiles/r05_experiments.md: the roles' prologues
+// are separate branches, per-lane addresses are rebuilt from the lane index, the accumulators are packed before the residual rows
+// are requested).  LDS (bytes): tiles 2 x 19 712 + slabs 2 x 36 864 + patches 8 x 4 096 + partials 2 048 + bias 1 024 + coefficients
+// 4 C x 8 + sink 256 = 151 808 (C = 128) / 155 904 (C = 256) of 163 840; the residual rows take no LDS of their own (pass 0 lands in
+// the idle patches).
 // Roofline: MFMA.  `2*9*C*C` flop per output pixel, `4C` B (+ `2C` residual).
 #include "conv_mfma.hpp"
 #include "gn_fold.hpp"
@@ -61,16 +67,13 @@ typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
                      // for the producers); 0: the producers do (9 pieces each: ~900 of their ~5 000 ticks per stage)
 #endif
 #ifndef PK_TOUCH
-#define PK_TOUCH 0   // residual variant: the producers pull the item's residual rows into L2 three stages before the epilogue
-#endif
-#ifndef PK_RING
-#define PK_RING 2    // residual variant without PK_RDMA: passes of residual rows in flight in the epilogue
+#define PK_TOUCH 0   // residual variant: the producers pull the item's residual rows into L2 PK_TOUCH stages before the epilogue (0: off)
 #endif
 #ifndef PK_RDMA
 #define PK_RDMA 1    // residual variant: the FIRST pass's residual rows (16 pixels x 256 B per wave) travel by LDS-DMA into the wave's own -- still
                      // idle -- transpose patch at the top of the item's last stage: no register waits for them through the k-loop, and the
-                     // epilogue starts with its first residual rows in LDS; passes 1..3 then follow through two register sets, each
-                     // requested a whole pass ahead (pass 1 at the epilogue's start, pass 2 behind pass 0, pass 3 behind pass 1)
+                     // epilogue starts with its first residual rows in LDS; passes 1 and 2 are requested as soon as the accumulators are
+                     // packed, pass 3 behind pass 0
 #endif
 #ifndef PK_ABL
 #define PK_ABL 0     // timing ablations (results wrong by design): 1 no transform, 2 no epilogue, 4 no MFMA loop, 8 no slab DMA, 16 epilogue without its global stores
@@ -147,7 +150,6 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
     PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, NBLK, NKC);
     const int n_items = cursor.my_items, S = cursor.S;
     if (S == 0) return;
-    const bool producer = __builtin_amdgcn_readfirstlane(wave) >= 8;
     // diagnostic build (-DPK_TICKS, tools/r04_pkstamps.sh): s_memtime stamps of consumer wave 0 (role 0) and producer wave 8 (role 1) of
     // the first 8 workgroups, stages 0..31: a.stamps[((wg * 2 + role) * 32 + stage) * 4 + k]
     auto stamp = [&](int role, int stage, int k) {
@@ -176,8 +178,17 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
         (void)stage; (void)k;
 #endif
     };
-    const int tp = tid - PK_CONS;                          // producer thread 0..255
-    const int c8_fixed = tp & 1;                           // this thread always stages the same 8-channel half of a pixel
+    // the lane index read afresh (volatile: the compiler cannot keep one copy of it, or of what derives from it, live across code that
+    // needs every register -- the consumers' k-loop, the residual epilogue -- and spill it there)
+    auto lane_now = [&]() __attribute__((always_inline)) -> int {
+        int l;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+        return l;
+    };
+    const int wv = __builtin_amdgcn_readfirstlane(wave);   // (a scalar)
+    const bool producer = wv >= 8;
+    int tp = tid - PK_CONS;                                // producer thread 0..255 (re-derived behind the prologue: tid dies there)
+    int c8_fixed = tp & 1;                                 // this thread always stages the same 8-channel half of a pixel
 
     // ---- producers' input addressing: a thread's chunk i (idx = tp + 256 i: pixel idx >> 1 of the 18 x 34 halo tile, half c8_fixed)
     // sits at the same tile position in every stage of an item: offsets once per item, a stage's request is base(item, kc) + offset
@@ -222,9 +233,26 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
     };
     PersistStage q1 = cursor.cur, q2 = q1, q3 = q1;         // producers: the next stages to transform (q1) .. to request (q3)
 
-    // ---- before the folded GroupNorm finalize: everything that does not need its result is already on its way -- the first two
-    // stages' raw rows (registers) and the first weight slab (LDS-DMA into slot 0; gn_fold's scratch is the first 8 KB of the tile area)
+    // the GroupNorm finalize folded into the prologue, then the bias and the coefficient table in LDS.  Both roles run it (the same
+    // barriers), each inside its own branch: nothing a role holds in registers is live across the other role's code
+    auto setup = [&]() __attribute__((always_inline)) {
+        tl(0);
+        if (a.gn_stats) gn_fold(a, smem, cursor.first_img, cursor.last_img, 512, reinterpret_cast<float2*>(smem + PK_COEF_BASE));     // the coefficient table, straight into LDS
+        tl(1);
+        if (tid < C) reinterpret_cast<float*>(smem + PK_BIAS_BASE)[tid] = a.bias[tid];
+        // the GroupNorm+FiLM coefficients of the images this workgroup's items belong to (gn_fold just wrote them, or
+        // gn_finalize_kernel did): the producers read them from LDS -- their only vector-memory traffic is the input stream and the slabs
+        const int nim = cursor.last_img - cursor.first_img + 1;                // <= PK_IMGS (conv_pk_fits)
+        const float2* ab = a.ab + (size_t)cursor.first_img * C;
+        float2* cd = reinterpret_cast<float2*>(smem + PK_COEF_BASE);
+        if (!a.gn_stats) for (int i = tid; i < nim * C; i += PK_THREADS) cd[i] = ab[i];      // (gn_finalize_kernel ran: row strips, IRE_GN_FOLD=0)
+        __syncthreads();
+    };
+
     if (producer) {
+        // =============================== producers: waves 8..11 ===============================================================
+        // before the folded GroupNorm finalize: everything that does not need its result is already on its way -- the first two
+        // stages' raw rows (registers) and the first weight slab (LDS-DMA into slot 0; gn_fold's scratch is the first 8 KB of the tile area)
         item_offsets(q1.it);
 #pragma unroll
         for (int i = 0; i < PK_P_ITERS; ++i) load_chunk(RA, q1, i);
@@ -238,23 +266,9 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
             rokB = cok;
         }
         q3 = cursor.next();
-    }
-    tl(0);
-    if (a.gn_stats) gn_fold(a, smem, cursor.first_img, cursor.last_img, 512, reinterpret_cast<float2*>(smem + PK_COEF_BASE));     // the coefficient table, straight into LDS
-    tl(1);
-    {
-        if (tid < C) reinterpret_cast<float*>(smem + PK_BIAS_BASE)[tid] = a.bias[tid];
-        // the GroupNorm+FiLM coefficients of the images this workgroup's items belong to (gn_fold just wrote them, or
-        // gn_finalize_kernel did): the producers read them from LDS -- their only vector-memory traffic is the input stream and the slabs
-        const int nim = cursor.last_img - cursor.first_img + 1;                // <= PK_IMGS (conv_pk_fits)
-        const float2* ab = a.ab + (size_t)cursor.first_img * C;
-        float2* cd = reinterpret_cast<float2*>(smem + PK_COEF_BASE);
-        if (!a.gn_stats) for (int i = tid; i < nim * C; i += PK_THREADS) cd[i] = ab[i];      // (gn_finalize_kernel ran: row strips, IRE_GN_FOLD=0)
-    }
-    __syncthreads();
-
-    if (producer) {
-        // =============================== producers: waves 8..11 ===============================================================
+        setup();
+        tp = (wv - 8) * 64 + lane_now();
+        c8_fixed = tp & 1;
         if (PK_PRIO) asm volatile("s_setprio %0" :: "n"(PK_PRIO));
         unsigned pastbits = 0;                                   // bit i: this thread's chunk i is a slot past the tile (idx >= 1224): its value is never read
 #pragma unroll
@@ -347,11 +361,11 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
         // the consumers run stage t; this is stage t + 1 (for t + 1 == S: the last stage again, into slots nobody reads any more): set
         // (t + 1) & 1 -> tile (t + 1) & 1, the set then takes stage t + 3.  S is even (NKC is): the loop runs stage pairs.
         auto body = [&](int t, u32x4_t (&R)[PK_P_ITERS], unsigned& rok, int slot) __attribute__((always_inline)) {
-            if (wave == 8) stamp(1, t, 0);
+            if (wv == 8) stamp(1, t, 0);
             if constexpr (RESID) {
-                // the residual rows of the item the consumers are in, touched (one dword per 128-B line, 1 024 lines) three stages before
-                // its epilogue (PK_TOUCH; off: measured slower -- 32 CUs x 128 KB is the XCD's whole L2)
-                if (PK_TOUCH && cc.kc == NKC - 3) {
+                // the residual rows of the item the consumers are in, touched (one dword per 128-B line, 1 024 lines) PK_TOUCH stages
+                // before its epilogue (three stages ahead measured slower -- 32 CUs x 128 KB is the XCD's whole L2)
+                if (PK_TOUCH && cc.kc == NKC - PK_TOUCH) {
                     const char* rbase = reinterpret_cast<const char*>(a.resid) + (size_t)cc.it.img * a.Hout * a.Wout * (2 * C) + (size_t)cc.it.nb * NT * 2;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
@@ -361,15 +375,15 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
                     }
                 }
             }
-            if (wave == 8) stamp(1, t, 1);
+            if (wv == 8) stamp(1, t, 1);
             // (PK_CDMA = 0: slot (t + 1) & 1 held slab t - 1: free since the last barrier)
             produce(R, rok, q1, smem + slot * PK_IN_BYTES, PK_DBUF ? q3 : q2, slot);
             cc = q1;
             q1 = q2; q2 = q3; q3 = cursor.next();
-            if (wave == 8) stamp(1, t, 2);
+            if (wv == 8) stamp(1, t, 2);
             // PK_CDMA = 0: the slab must have landed before the barrier; the requests that follow its last DMA piece may stay in flight
             if (!PK_CDMA) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PK_DMA_SPLIT ? 3 : PK_P_ITERS) : "memory");
-            if (wave == 8) stamp(1, t, 3);
+            if (wv == 8) stamp(1, t, 3);
             wstamp(t, 0);
             pk_barrier();
             wstamp(t, 1);
@@ -383,26 +397,28 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
     }
 
     // =================================== consumers: waves 0..7 ======================================================================
-    // Lane (r, h) reads pixel p = (2 wave + m + ky) 34 + r + kx of plane h: ONE address register + immediates; weight fragment
-    // (tap, half h, rows 32 j + r): (2 tap NT + h NT + 32 j + r) x 16 B
-    const int a_base = h * PK_PLANE + (wave * 2 * PK_IW + r) * 16;
-    const int b_off = (h * NT + r) * 16;
+    setup();
+    // The k-loop holds 152 of the 168 registers (128 accumulators + 24 fragment registers), so almost nothing else may stay live
+    // across it: the wave index is a scalar, and every per-lane address is rebuilt from lane_now() where it is used (hipcc used to
+    // keep them live and spill them, each reload a vmcnt(0) that also waited for the residual DMA)
+    const int cw = wv;
     const float* bias_lds = reinterpret_cast<const float*>(smem + PK_BIAS_BASE);
     float* red = reinterpret_cast<float*>(smem + PK_RED_BASE);
-    unsigned char* patch = smem + PK_PATCH_BASE + wave * PK_PATCH_BYTES;
+    unsigned char* patch = smem + PK_PATCH_BASE + cw * PK_PATCH_BYTES;
 
     int st_img = -1, st_tile = 0, st_cout0 = 0, st_par = 0, red_par = 0;
     auto flush_stats = [&]() {          // GroupNorm partials of the item that finished before the last stage barrier: 8 waves x 16 chunk slots -> groups
         if (st_img < 0) return;
         constexpr int G = C / 8, CPG = G >> 3, NGL = NT / G;      // couts per group, chunks of 8 couts per group (2 or 4), groups in the item
-        if (a.stats && tid < NGL) {
+        const int ln = lane_now();
+        if (a.stats && cw == 0 && ln < NGL) {
             const float* rd = red + st_par * (8 * 32);
             float sv = 0.f, qv = 0.f;
 #pragma unroll
             for (int w = 0; w < 8; ++w)
 #pragma unroll
-                for (int k = 0; k < CPG; ++k) { sv += rd[(w * 16 + tid * CPG + k) * 2 + 0]; qv += rd[(w * 16 + tid * CPG + k) * 2 + 1]; }
-            float* st = a.stats + (((size_t)st_img * tiles_per_img + st_tile) * 8 + st_cout0 / G + tid) * 2;
+                for (int k = 0; k < CPG; ++k) { sv += rd[(w * 16 + ln * CPG + k) * 2 + 0]; qv += rd[(w * 16 + ln * CPG + k) * 2 + 1]; }
+            float* st = a.stats + (((size_t)st_img * tiles_per_img + st_tile) * 8 + st_cout0 / G + ln) * 2;
             st[0] = sv; st[1] = qv;
         }
         st_img = -1;
@@ -420,12 +436,12 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
     auto consumer_dma = [&](const PersistStage& st, int slot) __attribute__((always_inline)) {
         if constexpr (!PK_CDMA || (PK_ABL & 8)) return;
         const unsigned char* ws = wslab(st);
-        const int wv = __builtin_amdgcn_readfirstlane(wave);
         const unsigned dst = smem_lds + PK_W_BASE + slot * PK_W_BYTES;
+        const int ln = lane_now();
 #pragma unroll
         for (int d = 0; d < 5; ++d) {
-            const int piece = wv + 8 * d;
-            if (piece < PK_W_CHUNKS / 64) pk_glds16(ws + (size_t)(piece * 64 + lane) * 16, dst + piece * 1024);
+            const int piece = cw + 8 * d;
+            if (piece < PK_W_CHUNKS / 64) pk_glds16(ws + (size_t)(piece * 64 + ln) * 16, dst + piece * 1024);
         }
     };
     pk_barrier();                                                  // tile 0 and slab 0 are staged
@@ -434,7 +450,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
         const PersistItem it = cs.it;
         const int cout0 = it.nb * NT;
         {   // accumulators start at the bias (permuted slab rows: accumulator i of lane-half h is cout 32 j + 16 (i >> 3) + 8 h + (i & 7))
-            const float* bl = bias_lds + cout0 + 8 * h;
+            const float* bl = bias_lds + cout0 + 8 * (lane_now() >> 5);
 #pragma unroll
             for (int j = 0; j < NTL; ++j)
 #pragma unroll
@@ -446,20 +462,22 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
         }
 #pragma unroll 1
         for (int kc = 0; kc < NKC; ++kc) {
-            const unsigned char* ib = smem + par * PK_IN_BYTES + a_base;
-            const unsigned char* wb = smem + PK_W_BASE + par * PK_W_BYTES + b_off;
-            if (wave == 0) stamp(0, stage_no, 0);
+            // lane (r, h) reads pixel p = (2 wave + m + ky) 34 + r + kx of plane h: ONE address register + immediates; weight fragment
+            // (tap, half h, rows 32 j + r): (2 tap NT + h NT + 32 j + r) x 16 B
+            const int ln = lane_now(), r_k = ln & 31, h_k = ln >> 5;
+            const unsigned char* ib = smem + par * PK_IN_BYTES + h_k * PK_PLANE + (cw * 2 * PK_IW + r_k) * 16;
+            const unsigned char* wb = smem + PK_W_BASE + par * PK_W_BYTES + (h_k * NT + r_k) * 16;
+            if (cw == 0) stamp(0, stage_no, 0);
             if (stage_no + 1 < S) consumer_dma(cn, par ^ 1);
             if constexpr (RESID && PK_RDMA) {
                 if (kc == NKC - 1) {
-                    int l_e = lane, w_e = wave;
-                    asm volatile("" : "+v"(l_e), "+v"(w_e));
+                    const int l_e = lane_now(), w_e = cw;
                     const int oy = min(it.ty * PK_TH + w_e * 2, a.Hout - 1);                       // pass 0 = the wave's first row, its first 16 pixels
                     const char* rbase = reinterpret_cast<const char*>(a.resid) + (size_t)it.img * a.Hout * a.Wout * (2 * C) + (size_t)(cout0 + 8 * (l_e & 15)) * 2;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {                                                    // read-back k: pixels 4 k + (lane >> 4), this lane's 8-cout chunk
                         const int ox = min(it.tx * PK_TW + 4 * k + (l_e >> 4), a.Wout - 1);         // (a column past the image: any valid address, the value is never used)
-                        pk_glds16(rbase + ((size_t)oy * a.Wout + ox) * (2 * C), smem_lds + PK_PATCH_BASE + __builtin_amdgcn_readfirstlane(wave) * PK_PATCH_BYTES + k * 1024);
+                        pk_glds16(rbase + ((size_t)oy * a.Wout + ox) * (2 * C), smem_lds + PK_PATCH_BASE + cw * PK_PATCH_BYTES + k * 1024);
                     }
                 }
             }
@@ -503,7 +521,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
             }
             par ^= 1;
             if (PK_CDMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's slab pieces (issued a whole k-loop ago) are in LDS
-            if (wave == 0) stamp(0, stage_no, 1);
+            if (cw == 0) stamp(0, stage_no, 1);
             ++stage_no;
             if (kc + 1 < NKC) { cs = cn; cn = cursor.next(); wstamp(stage_no - 1, 0); pk_barrier(); wstamp(stage_no - 1, 1); }     // the item's next stage: its tile and slab are staged, these are free
         }
@@ -515,8 +533,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
 #pragma unroll
                 for (int j = 0; j < NTL; ++j) asm volatile("" :: "v"(acc[m][j]));
         } else {
-            int l_e = lane, w_e = wave;
-            asm volatile("" : "+v"(l_e), "+v"(w_e));
+            const int l_e = lane_now(), w_e = cw;
             const int oyb = it.ty * PK_TH + w_e * 2;
             const int tcol0 = it.tx * PK_TW + (l_e >> 4);
             unsigned toffs[2];
@@ -530,7 +547,15 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
             char* obase = reinterpret_cast<char*>(a.out) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
             const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, a.Hout * a.Wout * (2 * C), 0x00020000);
             const unsigned cstep = (unsigned)(2 * C) * 4u;                    // bytes per read-back's 4 pixels
-            uint4 rvt[PK_RDMA ? 2 : PK_RING][4];                                            // residual rows of pass (m, q) in slot pass % PK_RING
+            // the global offset of read-back (m, q, k), or 0xffffffff (buffer range check: nothing loaded or stored) for a pixel past
+            // the image.  Recomputed at every use from values the compiler cannot see through: left alone, it keeps all 16 offsets of
+            // the residual loads live until the stores that share them -- and spills them, each reload a vmcnt(0) on the residual rows
+            auto eoff = [&](int m, int q, int k) __attribute__((always_inline)) -> unsigned {
+                unsigned o = toffs[m];
+                int c = tcol0;
+                asm volatile("" : "+v"(o), "+v"(c));
+                return trow[m] && c + 16 * q + 4 * k < a.Wout ? o + (unsigned)(4 * q + k) * cstep : 0xffffffffu;
+            };
             auto load_resid_pass = [&](int pass, uint4 (&dst)[4]) __attribute__((always_inline)) {
                 if constexpr (RESID) {
                     char* rbase = const_cast<char*>(reinterpret_cast<const char*>(a.resid)) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
@@ -538,22 +563,11 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
                     const int m = pass >> 1, q = pass & 1;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const bool ok = trow[m] && tcol0 + 16 * q + 4 * k < a.Wout;
-                        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, ok ? toffs[m] + (unsigned)(4 * q + k) * cstep : 0xffffffffu, 0, 0);
+                        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, eoff(m, q, k), 0, 0);
                         dst[k] = make_uint4(v.x, v.y, v.z, v.w);
                     }
                 }
             };
-            uint4 r0[4];                                                      // PK_RDMA: pass 0's residual rows, from the patch
-            if constexpr (RESID && PK_RDMA) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the DMA of the last stage's top: landed a k-loop ago
-#pragma unroll
-                for (int k = 0; k < 4; ++k) r0[k] = *reinterpret_cast<const uint4*>(patch + k * 1024 + l_e * 16);
-                load_resid_pass(1, rvt[1]);
-            } else if constexpr (RESID) {
-#pragma unroll
-                for (int p0 = 0; p0 < PK_RING; ++p0) load_resid_pass(p0, rvt[p0]);
-            }
             const bf16x2_t ones = __builtin_bit_cast(bf16x2_t, 0x3f803f80u);
             const int r16 = l_e & 15, qh = (l_e >> 4) & 1;                    // writer: pixel r = 16 qh + r16 of the row, half h
             const int h_e = l_e >> 5;
@@ -570,29 +584,47 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
                     const int pp = g & 1;
                     pkd[m][g] = u32x4_t{pk_pack(c[8 * pp + 0], c[8 * pp + 1]), pk_pack(c[8 * pp + 2], c[8 * pp + 3]),
                                         pk_pack(c[8 * pp + 4], c[8 * pp + 5]), pk_pack(c[8 * pp + 6], c[8 * pp + 7])};
-                }
+                    asm volatile("" : "+v"(pkd[m][g]));                       // (packed HERE: left alone, hipcc sinks row 1's packing to
+                }                                                             //  pass 2 and keeps its 64 f32 accumulators live until then)
             __builtin_amdgcn_sched_barrier(0);
+            // the residual rows of the four passes: pass 0 from the patch (PK_RDMA: it landed during the k-loop), passes 1 and 2 requested
+            // together, pass 3 behind pass 0 (into pass 0's registers: 48 of them at the peak, beside the 64 of pkd) -- the epilogue waits
+            // for about one round trip, not one per pass, and nothing waits in scratch
+            uint4 rv[4][4];
+            if constexpr (RESID) {
+                if constexpr (PK_RDMA) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the DMA of the last stage's top: landed a k-loop ago
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) rv[0][k] = *reinterpret_cast<const uint4*>(patch + k * 1024 + l_e * 16);
+                } else {
+                    load_resid_pass(0, rv[0]);
+                }
+#pragma unroll
+                for (int p1 = 1; p1 < 3; ++p1) load_resid_pass(p1, rv[p1]);
+            }
             float ssum = 0.f, qsum = 0.f;
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     __builtin_amdgcn_sched_barrier(0);
+                    int r16_p = r16, h_p = h_e, pq_p = pq, cc_p = cc_r;       // (recomputed patch addresses per pass: no 8 + 4 of them live throughout)
+                    asm volatile("" : "+v"(r16_p), "+v"(h_p), "+v"(pq_p), "+v"(cc_p));
                     if (qh == q) {
 #pragma unroll
                         for (int g = 0; g < NTL * 2; ++g) {
-                            const int cc = 2 * g + h_e;                       // chunk of the pixel's 128-cout run: couts 8 cc .. 8 cc + 7
-                            *reinterpret_cast<u32x4_t*>(patch + r16 * PITCH + ((cc ^ r16) << 4)) = pkd[m][g];
+                            const int cc = 2 * g + h_p;                       // chunk of the pixel's 128-cout run: couts 8 cc .. 8 cc + 7
+                            *reinterpret_cast<u32x4_t*>(patch + r16_p * PITCH + ((cc ^ r16_p) << 4)) = pkd[m][g];
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const int p = 4 * k + pq;
-                        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(patch + p * PITCH + ((cc_r ^ p) << 4));
+                        const int p = 4 * k + pq_p;
+                        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(patch + p * PITCH + ((cc_p ^ p) << 4));
                         unsigned w[4] = {v.x, v.y, v.z, v.w};
                         if constexpr (RESID) {
-                            const uint4 rr = PK_RDMA ? ((2 * m + q) == 0 ? r0[k] : rvt[(2 * m + q) & 1][k]) : rvt[(2 * m + q) % PK_RING][k];
+                            const uint4 rr = rv[2 * m + q][k];
                             const unsigned rw[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
                             for (int d = 0; d < 4; ++d) w[d] = pk_pack(pk_lo(w[d]) + pk_lo(rw[d]), pk_hi(w[d]) + pk_hi(rw[d]));
@@ -604,22 +636,22 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
                             s1 = __builtin_amdgcn_fdot2_f32_bf16(bv, ones, s1, false);
                             q1 = __builtin_amdgcn_fdot2_f32_bf16(bv, bv, q1, false);
                         }
-                        const bool ok = trow[m] && tcol0 + 16 * q + 4 * k < a.Wout;
+                        const unsigned off = eoff(m, q, k);
+                        const bool ok = off != 0xffffffffu;
                         ssum += ok ? s1 : 0.f; qsum += ok ? q1 : 0.f;
                         const u32x4_t o4 = {w[0], w[1], w[2], w[3]};
                         if constexpr (PK_ABL & 16) asm volatile("" :: "v"(o4));
-                        else __builtin_amdgcn_raw_buffer_store_b128(o4, orsrc, ok ? toffs[m] + (unsigned)(4 * q + k) * cstep : 0xffffffffu, 0, IRE_ST_LINE);
+                        else __builtin_amdgcn_raw_buffer_store_b128(o4, orsrc, off, 0, IRE_ST_LINE);
                     }
-                    if constexpr (RESID && PK_RDMA) { if (2 * m + q + 2 < 4) load_resid_pass(2 * m + q + 2, rvt[(2 * m + q) & 1]); }      // pass p + 2 into the set pass p (or nobody) used
-                    else if constexpr (RESID) { if (2 * m + q + PK_RING < 4) load_resid_pass(2 * m + q + PK_RING, rvt[(2 * m + q) % PK_RING]); }
+                    if constexpr (RESID) { if (m == 0 && q == 0) load_resid_pass(3, rv[3]); }
                 }
             // this lane's chunk cc_r over its read-backs; the other lanes with the same chunk sit 16 apart
             ssum = pk_swap16_add(ssum); qsum = pk_swap16_add(qsum);
             ssum = pk_swap32_add(ssum); qsum = pk_swap32_add(qsum);
-            if (l_e < 16) *reinterpret_cast<float2*>(red + red_par * (8 * 32) + (wave * 16 + cc_r) * 2) = make_float2(ssum, qsum);
+            if (l_e < 16) *reinterpret_cast<float2*>(red + red_par * (8 * 32) + (cw * 16 + cc_r) * 2) = make_float2(ssum, qsum);
             st_img = it.img; st_tile = it.tile; st_cout0 = cout0; st_par = red_par; red_par ^= 1;
         }
-        if (wave == 0) stamp(0, stage_no - 1, 2);          // epilogue done
+        if (cw == 0) stamp(0, stage_no - 1, 2);          // epilogue done
         cs = cn; cn = cursor.next();
         wstamp(stage_no - 1, 0);
         pk_barrier();                          // stage barrier: the next item's first tile and slab are staged; every wave's chunk sums are in LDS

@@ -1077,9 +1077,10 @@ void Engine::exec_conv(Run& R, const Op& op, const Geo& g) {
             a.fp8 = 1; a.w = reinterpret_cast<const unsigned short*>(cw.d_w8); a.bias = cw.d_bias8; a.oscale = cw.d_oscale;
         }
         // the producer / consumer form (conv_pk.hip) takes the 128-cout bf16 launches with a fused activation whose workgroups stay
-        // within its coefficient table; same slabs, bit-identical results
-        // (use_pk_ 1: the convs without a residual; 2: all of them -- the residual variant's epilogue fetches its 128 KB of residual rows per item
-        //  in one burst with too few registers to wait in: 208 vs conv_w4's 181 us at C = 128, profiles/r04_experiments.md)
+        // within its coefficient table, with and without the residual; same slabs, bit-identical results.  conv_w4 keeps fp8, the
+        // 64-cout items and the batches conv_pk_fits refuses
+        // (use_pk_ 2: all of them; 1: the convs without a residual -- the residual variant lost to conv_w4 while its epilogue spilled
+        //  and waited for its residual rows one pass at a time: profiles/r05_experiments.md)
         if (use_pk_ && (use_pk_ >= 2 || cw.kind != CONV_RB2) && !a.fp8 && a.ab != nullptr && a.w4_nt != 64 && cw.cin == cw.cout &&
             conv_pk_fits(cw.cout, a.tiles_x * a.tiles_y, g.nimg)) {
             conv_pk_launch(cw.kind == CONV_RB2, a, R.stream); kname = "conv_pk";

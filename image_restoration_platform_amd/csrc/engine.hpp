@@ -226,7 +226,7 @@ private:
     int w4_split_ = 1;            // IRE_W4_SPLIT=0: never use the 64-cout items
     int use_dnq_ = 1;             // the stride-2 convs with cout >= 128 as all-DMA 128-cout items on conv_dnq.hip (IRE_DNQ=0: conv_down.hip)
     int use_upq_ = 1;             // the level-2 `up` + `fuse` (cout = 128) as parity-major 128-cout items on conv_upq.hip (IRE_UPQ=0: conv_up.hip)
-    int use_pk_ = 1;              // C >= 128 ResBlock convs (128-cout items, fused activation) on conv_pk.hip's producer / consumer workgroups: 1 = the convs without a residual, 2 = all (IRE_PK=0: conv_w4.hip)
+    int use_pk_ = 2;              // C >= 128 ResBlock convs (128-cout items, fused activation) on conv_pk.hip's producer / consumer workgroups: 2 = all, 1 = the convs without a residual (IRE_PK=0: conv_w4.hip)
     int use_w4_ = 1;              // C >= 128 ResBlock convs on conv_w4.hip (IRE_W4=0: conv_rb.hip)
     int fp8_mx_ = 1;              // fp8: the block-scaled K = 64 MFMA (conv_f8.hip); IRE_FP8_MX=0: the same-rate 32x32x16 fp8 form in conv_w4.hip
     int down_rb_ = 1;             // stride-2 `down` convs on conv_down.hip's pipelined phase kernel (IRE_DOWN_RB=0: the v1 kernel)

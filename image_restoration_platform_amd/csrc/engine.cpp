@@ -888,6 +888,13 @@ void Engine::capture(const char* name, const unsigned short* d, size_t count, hi
     }
     captured_[name] = std::move(f);
 }
+void Engine::capture_f32(const char* name, const float* d, size_t count, hipStream_t s) {
+    if (!capture_ || !name) return;
+    IRE_HIP(hipStreamSynchronize(s));
+    std::vector<float> f(count);
+    IRE_HIP(hipMemcpy(f.data(), d, count * 4, hipMemcpyDeviceToHost));
+    captured_[name] = std::move(f);
+}
 bool Engine::debug_activation(const std::string& name, float* out, size_t* count) {
     auto it = captured_.find(name);
     if (it == captured_.end()) return false;
@@ -1142,6 +1149,10 @@ void Engine::exec_conv(Run& R, const Op& op, const Geo& g) {
         if (R.stats_alt) std::swap(R.stats, R.stats_alt);          // R.stats = the partials produced last
     }
     if (capture_ && !op.name.empty() && a.out && g.halo == 0) capture(op.name.c_str(), a.out, (size_t)g.nimg * Hout * Wout * cw.cout, R.stream);
+    // the (A, B) of y = x A + B this conv applied while staging, [image][cin][2] floats, as "<layer>.ab" ("head.ab" for the head): what a
+    // per-layer check needs to recompute the activated operand from the very coefficients the kernel used
+    if (capture_ && a.ab != nullptr && g.halo == 0)
+        capture_f32(((op.name.empty() ? std::string("head") : op.name) + ".ab").c_str(), reinterpret_cast<const float*>(R.ab), (size_t)g.nimg * cw.cin * 2, R.stream);
 }
 
 void Engine::flush_gn(Run& R, const Geo& g) {

@@ -212,6 +212,7 @@ private:
     void prof_tag(const std::string& key, const char* kernel, int level, int cin, int cout, double flops_exec);   // after prof_begin: the open record's layer group
     void prof_end(hipStream_t s);
     void capture(const char* name, const unsigned short* d, size_t count, hipStream_t s);
+    void capture_f32(const char* name, const float* d, size_t count, hipStream_t s);
     ConvW make_conv(ConvKind kind, const std::string& wname, const std::string& bname, int cin, int cout);
     void make_up_fused(ConvW& up, const std::string& level);
     GNW make_gn(const std::string& prefix, int C, int level);

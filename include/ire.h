@@ -242,7 +242,9 @@ int ire_debug_classifier_sums(ire_engine* e, int n, uint64_t* sums_out);
 /* Turn per-layer capture on/off (slow: synchronises after every layer; tests only). */
 int ire_debug_capture(ire_engine* e, int on);
 /* Copy one named intermediate activation of the last ire_restore* call to host as float32 NHWC.
- * Returns the element count through *count (call with out==NULL to query). */
+ * Returns the element count through *count (call with out==NULL to query).
+ * "<layer>.ab" ("head.ab" for the head) names the GroupNorm+FiLM coefficients (A, B) of y = x*A + B that the
+ * layer's convolution applied to its input, as [N][C_in][2] float32. */
 int ire_debug_activation(ire_engine* e, const char* name, float* out, size_t* count);
 /* Accumulated HIP-event time (ms) and launch count per kernel family since the last reset:
  * family in {"classifier","conv3x3","conv1x1","stem","head","gn_finalize","fusion","all"}. */

@@ -55,7 +55,7 @@ class _Net:
         if self.cap is not None:
             self.cap[name] = t.permute(0, 2, 3, 1).contiguous().numpy().copy()
 
-    def gn_film_silu(self, x, prefix, level, film):
+    def gn_film_silu(self, x, prefix, level, film, keep=None):
         c = x.shape[1]
         g, b = self.w[prefix + ".g"], self.w[prefix + ".b"]
         n = x.shape[0]
@@ -72,6 +72,8 @@ class _Net:
         rg = rstd * g[None, :]
         a = rg * (1.0 + s)
         bb = (b[None, :] - mean * rg) * (1.0 + s) + t
+        if self.cap is not None and keep:      # the (A, B) of y = x A + B, [N, C, 2]: the engine's capture of the same name
+            self.cap[keep + ".ab"] = torch.stack([a, bb], dim=2).numpy().copy()
         y = x * a[:, :, None, None] + bb[:, :, None, None]
         if self.fp8 and c >= 128:          # the activated operand goes to e4m3 (x16), not to bf16
             return _e4m3(F.silu(y) * FP8_ACT_SCALE) / FP8_ACT_SCALE
@@ -88,9 +90,9 @@ class _Net:
 
     def resblock(self, x, prefix, level, film):
         f8 = self.fp8 and x.shape[1] >= 128
-        h = self.conv(self.gn_film_silu(x, prefix + ".gn1", level, film), prefix + ".conv1", fp8=f8)
+        h = self.conv(self.gn_film_silu(x, prefix + ".gn1", level, film, prefix + ".h"), prefix + ".conv1", fp8=f8)
         self.keep(prefix + ".h", h)
-        y = self.conv(self.gn_film_silu(h, prefix + ".gn2", level, film), prefix + ".conv2", fp8=f8)
+        y = self.conv(self.gn_film_silu(h, prefix + ".gn2", level, film, prefix), prefix + ".conv2", fp8=f8)
         out = self.q(y + x)
         self.keep(prefix, out)
         return out
@@ -121,7 +123,7 @@ class _Net:
             self.keep(f"fuse{l}", x)
             x = self.resblock(x, f"dec{l}.rb0", l, film)
             x = self.resblock(x, f"dec{l}.rb1", l, film)
-        y = self.gn_film_silu(x, "head.gn", 0, film)
+        y = self.gn_film_silu(x, "head.gn", 0, film, "head")
         head = F.conv2d(y, self.w["head.w"], self.w["head.b"], padding=1)
         if self.cap is not None:
             self.cap["head"] = head.permute(0, 2, 3, 1).contiguous().numpy().copy()

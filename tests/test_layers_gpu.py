@@ -1,0 +1,130 @@
+"""Every convolution of RestoreNet, layer by layer and element by element, against a float64 evaluation of THAT layer on the
+engine's own captured input (oracle/layer_check.py: teacher forcing; the bound is derived there, nothing is tuned).  A failure names
+the layer, the image, the pixel, its tile and the failing elements per tile.  The free-running comparison
+(test_restore_gpu.py::test_every_layer_tracks_the_bf16_emulating_oracle) stays as the guard of the drift between engine and oracle."""
+import os
+
+import numpy as np
+import pytest
+
+from image_restoration_platform_amd import synth, weights
+from oracle import classifier as oc
+from oracle import layer_check as lc
+
+pytestmark = pytest.mark.gpu
+
+
+def _scores(imgs):
+    return np.stack([oc.classify(im, True)[0] for im in imgs])
+
+
+def _group(name):
+    if name in ("stem", "pixels") or name[:2] in ("do", "up", "fu"):
+        return name.rstrip("0123")
+    c = lc.WIDTHS[lc._level(name)]
+    return "resblock C=%d %s" % (c, "conv1" if name.endswith(".h") else "conv2")
+
+
+def _check(eng, w, imgs, sc, label, fp8=False, up_mode="fused"):
+    eng.debug_capture(True)
+    try:
+        out = eng.restore(imgs, scores=sc)
+        reports = lc.assert_network(w, imgs, sc, eng.activation, out, fp8=fp8, up_mode=up_mode, label=label)
+    finally:
+        eng.debug_capture(False)
+    assert set(reports) == set(lc.layer_names(up_mode))                     # no layer exempt
+    groups = {}
+    for nm, r in reports.items():
+        g = groups.setdefault(_group(nm), [0.0, 0.0, 0.0])
+        g[0], g[1], g[2] = max(g[0], r.headroom), max(g[1], r.median_ulps), max(g[2], r.uncertain)
+    for g, (hr, med, unc) in sorted(groups.items()):                       # information (pytest -s), not a threshold
+        print("LAYERCHECK %s | %s | share of the accumulation budget used %.3f | median bound %.2f ulp | uncertain %.1e" % (label, g, hr, med, unc))
+    return out
+
+
+@pytest.mark.parametrize("n,h,w", [(2, 64, 96), (1, 72, 136), (3, 200, 328), (1, 16, 16)])
+def test_default_engine_every_layer_within_the_derived_bound(engine, weights0, n, h, w):
+    """(72, 136): ragged at every level; (200, 328): several ragged tiles at C = 128 / 256, workgroups crossing images; (16, 16): 2 x 2
+    pixels at level 3."""
+    imgs = synth.batch(n, h, w, start=21 if h == 200 else 0)
+    _check(engine, weights0, imgs, _scores(imgs), "default %dx%dx%d" % (n, h, w))
+
+
+def test_many_small_images_every_layer(weights0):
+    """(12, 32, 48): the launches that do not fit conv_pc's coefficient table take conv_rb (conv_pc_fits)."""
+    from image_restoration_platform_amd.engine import Engine
+    imgs = synth.batch(12, 32, 48, start=5)
+    eng = Engine(device_index=0, max_batch=32)
+    try:
+        _check(eng, weights0, imgs, _scores(imgs), "12x32x48")
+    finally:
+        eng.close()
+
+
+SWITCHES = [{"IRE_PK": "0"}, {"IRE_PC": "0"}, {"IRE_PC": "1"}, {"IRE_W4": "0"}, {"IRE_UPQ": "0"}, {"IRE_DNQ": "0"}, {"IRE_UP_FUSE": "0"},
+            {"IRE_UP_SUBPIX": "0"}, {"IRE_GN_FOLD": "0"}, {"IRE_DOWN_RB": "0", "IRE_HEAD_RB": "0"}, {"IRE_STEM_RB": "0"}]
+
+
+@pytest.mark.parametrize("env", SWITCHES, ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
+def test_every_kernel_family_behind_its_switch(weights0, env, monkeypatch):
+    from image_restoration_platform_amd.engine import Engine
+    imgs = synth.batch(1, 72, 136, start=11)          # one image: the float64 references are what this file's time goes to
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    up_mode = "plain" if env.get("IRE_UP_SUBPIX") == "0" else "subpix" if env.get("IRE_UP_FUSE") == "0" else "fused"
+    eng = Engine(device_index=0, max_batch=8)
+    try:
+        _check(eng, weights0, imgs, _scores(imgs), " ".join("%s=%s" % kv for kv in env.items()), up_mode=up_mode)
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("mx", ["1", "0"])
+@pytest.mark.parametrize("n,h,w", [(2, 128, 160), (1, 72, 136)])
+def test_fp8_engine_every_layer(weights0, n, h, w, mx, monkeypatch):
+    """IRE_PRECISION_FP8: the C >= 128 ResBlock convs on e4m3 operands -- conv_f8.hip (IRE_FP8_MX=1, the default) and conv_w4.hip's
+    fp8 form (=0); both quantise as the checker states (per-cout weight scale to 448, activated operand x16 to e4m3, unit block scales)."""
+    from image_restoration_platform_amd.engine import Engine
+    monkeypatch.setenv("IRE_FP8_MX", mx)
+    imgs = synth.batch(n, h, w, start=3)
+    eng = Engine(device_index=0, max_batch=8, precision="fp8")
+    try:
+        _check(eng, weights0, imgs, _scores(imgs), "fp8 mx=%s %dx%dx%d" % (mx, n, h, w), fp8=True)
+    finally:
+        eng.close()
+
+
+def _engine_with(w, tmp_path):
+    from image_restoration_platform_amd.engine import Engine
+    path = os.path.join(str(tmp_path), "weights.bin")
+    with open(path, "wb") as f:
+        f.write(weights.serialize(w))
+    return Engine(device_index=0, max_batch=8, weights_path=path)
+
+
+def test_other_seed_every_layer(tmp_path):
+    w = weights.generate(1)
+    imgs = synth.batch(2, 72, 136, start=7)
+    eng = _engine_with(w, tmp_path)
+    try:
+        _check(eng, w, imgs, _scores(imgs), "seed 1")
+    finally:
+        eng.close()
+
+
+def stress_images(h=72, w=136):
+    return np.stack([np.zeros((h, w, 3), np.uint8), np.full((h, w, 3), 255, np.uint8), synth.image(4, h, w)])
+
+
+def test_stress_weights_every_layer(weights0, tmp_path):
+    """Negative 1 + s, GroupNorm gains of both signs and exact zeros, outputs in the coarse bf16 ulps, a convolution whose output is its
+    bias; all-0, all-255 and a synthetic image: the head clamps at both ends (tests/test_layer_check.py checks the set on the CPU first)."""
+    w = lc.stress_weights(weights0)
+    imgs = stress_images()
+    sc = _scores(imgs)
+    eng = _engine_with(w, tmp_path)
+    try:
+        out = _check(eng, w, imgs, sc, "stress")
+    finally:
+        eng.close()
+    assert out.min() == 0 and out.max() == 255

@@ -43,6 +43,8 @@ def test_every_layer_tracks_the_bf16_emulating_oracle(engine, weights0, h, w, n,
     tiles at every level (9x17 at 1/8 scale).  By default `up` and the 1x1 `fuse` run as ONE composed convolution
     (conv_up.hip fused form): the `up` tensor does not exist and `fuse{l}` is that kernel's output; with IRE_UP_FUSE=0 the
     two layers run as two kernels and both tensors are checked."""
+    # This free-running comparison guards the drift between engine and oracle; to LOCALISE a wrong layer (which layer, which pixel, which
+    # tile) see tests/test_layers_gpu.py: each layer from the engine's own captured input, every element under a derived bound.
     from image_restoration_platform_amd.engine import Engine
     imgs = synth.batch(n, h, w)
     sc = _scores(imgs)

@@ -53,6 +53,12 @@ SYMBOLS = {
     "ire_png_base64_bytes": (ctypes.c_size_t, [_i, _i]),
     "ire_encode_png_base64_device": (_i, [_vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
     "ire_encode_png_base64": (_i, [_vp, _u8p, _i, _i, _i, _u8p, ctypes.c_size_t]),
+    "ire_restore_fit": (_i, [_vp, _u8p, _i, _i, _i, _vp, _u8p, _u8p, ctypes.POINTER(IreTimings)]),
+    "ire_restore_fit_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ire_png_base64_bytes_fit": (ctypes.c_size_t, [_i, _i]),
+    "ire_encode_png_base64_fit_device": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
+    "ire_encode_png_base64_fit": (_i, [_vp, _u8p, _i, _i, _i, _u8p, ctypes.c_size_t]),
+    "ire_submit_fit": (_i, [_vp, _u8p, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
     "ire_submit": (_i, [_vp, _u8p, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
     "ire_restore_tiled_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ire_strips_stats_bytes": (ctypes.c_size_t, [_i, _i]),

@@ -189,9 +189,10 @@ struct HipBatchBackend {
         on_stream(E, ms, [&] {
             IRE_HIP(hipStreamWaitEvent(ms, hs.ev_in, 0));
             IRE_HIP(hipEventRecord(hs.ev_c0, ms));
-            E.restore_device_mixed(hs.d_in, n, h, w, b.pin_sc_in, has_sc, hs.d_jp, hs.d_out, ms);   // classifies the jobs that brought no scores
+            // classifies the jobs that brought no scores; a shape the network cannot take as it is (ire_submit_fit) is padded into the
+            // engine's staging and its window comes back; with text() the results leave the device as text
+            E.restore_fit_device_mixed(hs.d_in, n, h, w, b.pin_sc_in, has_sc, hs.d_jp, hs.d_out, text() ? hs.d_txt : nullptr, (out_bytes(h, w) + 255) / 256 * 256, ms);
             IRE_HIP(hipMemcpyAsync(b.pin_sc, E.scores_device(), sizeof(double) * 7 * n, hipMemcpyDeviceToHost, ms));
-            if (text()) E.encode_png_base64_device(hs.d_out, n, h, w, hs.d_txt, (out_bytes(h, w) + 255) / 256 * 256, ms);     // the results leave the device as text
             IRE_HIP(hipEventRecord(hs.ev_c1, ms));
             IRE_HIP(hipEventRecord(hs.ev_cw, ms));
         });
@@ -282,6 +283,14 @@ static int family_id(const char* f) {
 }
 
 }  // namespace ire
+
+// behind ire_submit and ire_submit_fit, after their argument checks: one job into the batcher (keyed by its exact h, w)
+static void queue_job(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg, const double* scores, ire_job** job_out) {
+    *job_out = nullptr;
+    std::unique_ptr<ire_job> hnd(new ire_job{});
+    hnd->j = e->batcher->submit(rgb, h, w, is_jpeg, scores);
+    *job_out = hnd.release();
+}
 
 using namespace ire;
 
@@ -422,6 +431,39 @@ int ire_encode_png_base64(ire_engine* e, const uint8_t* rgb, int n, int h, int w
     });
 }
 
+size_t ire_png_base64_bytes_fit(int h, int w) { return (h >= 1 && w >= 1 && h <= 8192 && w <= 8192) ? png_base64_chars(h, w) : 0; }
+
+int ire_encode_png_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes, size_t image_pitch_bytes,
+                                     uint8_t* d_chars, size_t stride_bytes, void* stream) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, (hipStream_t)stream, [&] { E.encode_png_base64_fit_device(d_rgb, n, h, w, row_pitch_bytes, image_pitch_bytes, d_chars, stride_bytes, (hipStream_t)stream); });
+    });
+}
+
+int ire_encode_png_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, E.main_stream(), [&] { E.encode_png_base64_fit_host(rgb, n, h, w, chars, stride_bytes); });
+    });
+}
+
+int ire_restore_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, const double* scores, const uint8_t* is_jpeg, uint8_t* out_rgb,
+                    ire_timings* t) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, E.main_stream(), [&] { E.restore_fit_host(rgb, n, h, w, scores, is_jpeg, out_rgb, t); });
+    });
+}
+
+int ire_restore_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, const double* d_scores, const uint8_t* d_is_jpeg,
+                           uint8_t* d_out_rgb, void* stream) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, (hipStream_t)stream, [&] { E.restore_fit_device(d_rgb, n, h, w, d_scores, d_is_jpeg, d_out_rgb, (hipStream_t)stream); });
+    });
+}
+
 int ire_restore_tiled_device(ire_engine* e, const uint8_t* d_rgb, int h, int w, int nstrips, const double* d_scores,
                              const uint8_t* d_is_jpeg, uint8_t* d_out_rgb, void* stream) {
     return guarded([&] {
@@ -524,10 +566,16 @@ int ire_submit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg, con
         if (!rgb || !job_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit");
         if (h <= 0 || w <= 0 || h % 8 || w % 8 || h < 16 || w < 16 || h > 8192 || w > 8192)
             fail(IRE_ERR_INVALID_INPUT, "invalid image size for restore: height and width must be multiples of 8, >= 16");
-        *job_out = nullptr;
-        std::unique_ptr<ire_job> hnd(new ire_job{});
-        hnd->j = e->batcher->submit(rgb, h, w, is_jpeg, scores);
-        *job_out = hnd.release();
+        queue_job(e, rgb, h, w, is_jpeg, scores, job_out);
+    });
+}
+
+int ire_submit_fit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg, const double* scores, ire_job** job_out) {
+    return guarded([&] {
+        eng(e);
+        if (!rgb || !job_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_fit");
+        if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size: height and width must be in 1..8192");
+        queue_job(e, rgb, h, w, is_jpeg, scores, job_out);
     });
 }
 

@@ -5,7 +5,7 @@
 // seam JS-thread-bound on exactly that: V8's base64 of a raw 3-MB image is 1.03 ms per job on the one JS thread, and with a real codec
 // (PIL's PNG of a 1024^2 photo: ~0.2 s of zlib per image and core; JPEG q85: ~15 ms) the codec, not the engine, sets the rate of a
 // deployed worker (tools/codec_seam_rate.py).  This file removes the result side's host work altogether: three
-// small kernels behind the restore write, per image, a complete PNG file -- signature, IHDR, ONE IDAT chunk holding a zlib stream of
+// small kernels behind the restore write, for a whole batch (the image is a grid dimension), a complete PNG file per image -- signature, IHDR, ONE IDAT chunk holding a zlib stream of
 // STORED deflate blocks (filter type 0 on every scanline), IEND -- with its Adler-32 and CRC-32 computed on the device, and then its
 // base64 text.  Every PNG decoder reads it (stored blocks are plain deflate); it is 0.2 % larger than the pixels where a compressed
 // PNG of a photograph is 20-30 % smaller -- the trade is host CPU seconds for 1 MB more per result on the wire.  The host receives
@@ -13,7 +13,8 @@
 //
 // Integer / byte work, bit-exact by construction against zlib.adler32, zlib.crc32, base64.b64encode and PIL's decoder
 // (oracle/encode.py; tests/test_encode_gpu.py).  HBM-bound by bytes: ~3 (pixels) + 3 + 3 (file written, read) + 4 (text) = 13 B per
-// pixel-byte triple... ~14 MB per 1024^2 image, a few microseconds; in practice three dependent launches.
+// pixel-byte triple... ~14 MB per 1024^2 image, a few microseconds; in practice three dependent launches per BATCH.  The same file holds
+// the two byte movers of the any-size path: the edge-replicate pad in front of the network and the crop of the window behind it.
 #include "encode.hpp"
 
 #include <cstring>
@@ -75,77 +76,105 @@ PngGeom geom_of(int h, int w) {
 struct PngHead { unsigned char b[41]; };       // signature + IHDR chunk (CRC included) + the IDAT chunk's length and type
 __constant__ unsigned char kIend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xae, 0x42, 0x60, 0x82};
 
-// K1: every byte of the file except the two checksums.  A thread writes one dword (4 file bytes; the file buffer is padded to a
-// multiple of 4).  File regions: [0, 41) head | zlib header 78 01 | nblk x (5-byte stored-block header + <= 65535 raw bytes) |
-// Adler-32 (K2) | IDAT CRC (K2) | IEND chunk.
-__global__ __launch_bounds__(256) void png_frame_kernel(const unsigned char* __restrict__ rgb, PngGeom g, PngHead head, unsigned char* __restrict__ file) {
-    const unsigned long long o0 = ((unsigned long long)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (o0 >= g.file) return;
+// Where the pixels lie: the encoder reads the top-left h x w window of n images whose rows are row_pitch bytes and whose first
+// pixels are image_pitch bytes apart (a tightly packed batch: 3 w and 3 w h).  Nothing about the pitches is assumed: a row may
+// start at any byte, so the pixels are read as bytes.
+struct PngSrc { const unsigned char* rgb; unsigned long long row_pitch, image_pitch; };
+
+// The Adler-32 schedule.  adler = ((N + N S - T) mod 65521) << 16 | (1 + S) mod 65521 with S = sum d_i, T = sum i d_i over the raw
+// stream (i the byte's index in it, N its length).  T is kept small by reducing where it would otherwise grow:
+//   per byte      (i mod 65521) * d                      <= 65520 * 255                     (32 bits)
+//   per thread    kFrameDwords * 4 such terms, then mod  <= 16 * 65520 * 255 = 267 321 600  (32 bits) -> < 65521
+//   per workgroup 256 reduced thread sums                <= 256 * 65520 = 16 773 120        (32 bits)
+//   per image     one 64-bit atomic add per workgroup    <= workgroups * 16 773 120         (64 bits: < 2^42 at 16384 x 16384)
+// S needs no reduction: 255 * N < 2^38.  tests/test_fit_abi.py::test_adler_schedule_bounds redoes this arithmetic in integers.
+constexpr unsigned kAdlerMod = 65521u;
+constexpr int kFrameDwords = 4;                 // dwords of the file a thread of K1 writes (256 apart: a workgroup covers 4 KB)
+constexpr int kFrameThreads = 256;              // threads of a K1 workgroup
+static_assert((unsigned long long)kFrameDwords * 4 * (kAdlerMod - 1) * 255 < (1ull << 32), "a thread's T must fit 32 bits before its mod");
+static_assert((unsigned long long)kFrameThreads * (kAdlerMod - 1) < (1ull << 32), "a workgroup's sum of reduced thread sums must fit 32 bits");
+static_assert((unsigned long long)kFrameThreads * kFrameDwords * 4 * 255 < (1ull << 32), "a workgroup's S must fit 32 bits");
+
+// K1: every byte of the file except the two checksums, and the Adler sums of what it writes.  A thread writes kFrameDwords dwords
+// (the file buffer is padded to a multiple of 4).  File regions: [0, 41) head | zlib header 78 01 | nblk x (5-byte stored-block
+// header + <= 65535 raw bytes) | Adler-32 (K2) | IDAT CRC (K2) | IEND chunk.  blockIdx.y is the image.
+__global__ __launch_bounds__(kFrameThreads) void png_frame_kernel(PngSrc src, PngGeom g, PngHead head, unsigned char* __restrict__ files, unsigned long long file_pitch,
+                                                        unsigned long long* __restrict__ acc) {
+    __shared__ unsigned s_s[kFrameThreads / 64], s_t[kFrameThreads / 64];
+    const unsigned char* __restrict__ rgb = src.rgb + (unsigned long long)blockIdx.y * src.image_pitch;
+    unsigned char* __restrict__ file = files + (unsigned long long)blockIdx.y * file_pitch;
     const unsigned long long z0 = g.idat + 4;                 // first byte of the zlib stream
     const unsigned long long d0 = z0 + 2;                     // first stored block
     const unsigned long long dend = d0 + 5ull * g.nblk + g.raw;
-    unsigned out = 0;
+    unsigned S = 0, T = 0;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const unsigned long long o = o0 + k;
-        unsigned v = 0;
-        if (o < 41) v = head.b[o];
-        else if (o < d0) v = o == z0 ? 0x78u : 0x01u;
-        else if (o < dend) {
-            const unsigned rel = (unsigned)(o - d0);                  // (the largest image's file fits 32 bits: 16384 x (1 + 3 x 16384) = 0.8 G)
-            const unsigned blk = rel / (kStored + 5), r = rel - blk * (kStored + 5);
-            if (r < 5) {
-                const unsigned long long left = g.raw - (unsigned long long)blk * kStored;
-                const unsigned len = left < (unsigned)kStored ? (unsigned)left : (unsigned)kStored;
-                v = r == 0 ? (blk + 1 == g.nblk ? 1u : 0u) : r == 1 ? (len & 0xffu) : r == 2 ? (len >> 8) : r == 3 ? ((~len) & 0xffu) : (((~len) >> 8) & 0xffu);
-            } else {
-                const unsigned i = blk * kStored + (r - 5);          // raw stream index
-                const unsigned y = i / g.row, c = i - y * g.row;
-                v = c == 0 ? 0u : rgb[(size_t)y * (g.row - 1) + (c - 1)];                   // filter type 0 | a pixel byte
-            }
-        } else if (o < dend + 8) v = 0;                           // Adler-32, CRC-32: written by png_sums_kernel
-        else if (o < g.file) v = kIend[o - (dend + 8)];
-        out |= v << (8 * k);
-    }
-    *reinterpret_cast<unsigned*>(file + o0) = out;
-}
-
-// K2a: Adler-32 of the raw stream from the PIXELS (the filter bytes are zeros: they only shift positions) as two exact integer sums --
-// S = sum d_i, T = sum pos_i d_i with pos_i the byte's index in the raw stream -- accumulated per workgroup and added with two 64-bit
-// atomics (integers: any order gives the same result).  adler = ((N + N S - T) mod 65521) << 16 | (1 + S) mod 65521.
-__global__ __launch_bounds__(256) void png_adler_kernel(const unsigned char* __restrict__ rgb, PngGeom g, unsigned long long* __restrict__ acc) {
-    __shared__ unsigned long long s_s[256], s_t[256];
-    const unsigned long long npix_bytes = (unsigned long long)g.h * (g.row - 1);
-    unsigned long long S = 0, T = 0;
-    for (unsigned long long i4 = ((unsigned long long)blockIdx.x * 256 + threadIdx.x) * 4; i4 < npix_bytes; i4 += (unsigned long long)gridDim.x * 1024) {
-        const unsigned wv = *reinterpret_cast<const unsigned*>(rgb + i4);        // (3 w is a multiple of 4: w % 8 == 0 -- a dword never straddles two rows)
-        const unsigned long long y = (unsigned)i4 / (g.row - 1);                 // (the pixel bytes of the largest image fit 32 bits)
+    for (int q = 0; q < kFrameDwords; ++q) {
+        const unsigned long long o0 = (((unsigned long long)blockIdx.x * kFrameDwords + q) * kFrameThreads + threadIdx.x) * 4;
+        if (o0 >= g.file) break;
+        // position inside the stored blocks, kept up byte by byte; the one division by the scanline length happens at the first
+        // raw byte of the dword (the raw index runs on across a block header)
+        unsigned blk = 0, r = 0;
+        if (o0 >= d0) { const unsigned rel = (unsigned)(o0 - d0); blk = rel / (kStored + 5); r = rel - blk * (kStored + 5); }     // (the largest file fits 32 bits)
+        bool have = false;
+        unsigned i = 0, y = 0, c = 0;
+        unsigned out = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const unsigned d = (wv >> (8 * k)) & 0xffu;
-            S += d;
-            T += (i4 + k + y + 1) * d;                                           // raw index = i + (rows before and including this one's filter byte)
+            const unsigned long long o = o0 + k;
+            unsigned v = 0;
+            if (o < 41) v = head.b[o];
+            else if (o < d0) v = o == z0 ? 0x78u : 0x01u;
+            else if (o < dend) {
+                if (r < 5) {
+                    const unsigned long long left = g.raw - (unsigned long long)blk * kStored;
+                    const unsigned len = left < (unsigned)kStored ? (unsigned)left : (unsigned)kStored;
+                    v = r == 0 ? (blk + 1 == g.nblk ? 1u : 0u) : r == 1 ? (len & 0xffu) : r == 2 ? (len >> 8) : r == 3 ? ((~len) & 0xffu) : (((~len) >> 8) & 0xffu);
+                } else {
+                    if (!have) { i = blk * kStored + (r - 5); y = i / g.row; c = i - y * g.row; have = true; }
+                    if (c) {                                                      // (c == 0: the scanline's filter byte, 0)
+                        v = rgb[(unsigned long long)y * src.row_pitch + (c - 1)];
+                        S += v;
+                        T += (i % kAdlerMod) * v;
+                    }
+                    ++i;
+                    if (++c == g.row) { c = 0; ++y; }
+                }
+                if (++r == (unsigned)kStored + 5) { r = 0; ++blk; }
+            } else if (o < dend + 8) v = 0;                           // Adler-32, CRC-32: written by png_crc_kernel
+            else if (o < g.file) v = kIend[o - (dend + 8)];
+            out |= v << (8 * k);
+        }
+        *reinterpret_cast<unsigned*>(file + o0) = out;
+    }
+    T %= kAdlerMod;
+    for (int off = 32; off >= 1; off >>= 1) { S += __shfl_down(S, off, 64); T += __shfl_down(T, off, 64); }
+    if ((threadIdx.x & 63) == 0) { s_s[threadIdx.x >> 6] = S; s_t[threadIdx.x >> 6] = T; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned ws = 0, wt = 0;
+        for (int k = 0; k < kFrameThreads / 64; ++k) { ws += s_s[k]; wt += s_t[k]; }
+        if (ws) {                                            // (integers: any order of the adds gives the same sums)
+            atomicAdd(&acc[2 * blockIdx.y], (unsigned long long)ws);
+            atomicAdd(&acc[2 * blockIdx.y + 1], (unsigned long long)wt);
         }
     }
-    s_s[threadIdx.x] = S; s_t[threadIdx.x] = T;
-    __syncthreads();
-    for (int off = 128; off >= 1; off >>= 1) {
-        if ((int)threadIdx.x < off) { s_s[threadIdx.x] += s_s[threadIdx.x + off]; s_t[threadIdx.x] += s_t[threadIdx.x + off]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { atomicAdd(&acc[0], s_s[0]); atomicAdd(&acc[1], s_t[0]); }
 }
 
-// K2b: the Adler-32 into the file, then the CRC-32 of the IDAT chunk (type + zlib stream, Adler included) in two levels: a thread
+// K2: the Adler-32 into the file, then the CRC-32 of the IDAT chunk (type + zlib stream, Adler included) in two levels: a thread
 // runs the byte-wise CRC over its 256-byte slice from register 0 (the chunk's first slice from 0xffffffff); a workgroup combines its
 // 256 slices by a tree (level l: reg(A || B) = reg(A) x^(8 |B|) + reg(B), |B| = 256 * 2^l bytes: operators from the host); the per-
-// workgroup registers go to `part`, and the LAST workgroup (ticket) folds them left to right with the 64-KB operator and the tail's own.
+// workgroup registers go to `part`, and the LAST workgroup of an image (ticket) folds them left to right with the 64-KB operator and
+// the tail's own.  blockIdx.y is the image.
 struct CrcOps { unsigned lvl[8]; unsigned wg; unsigned last_wg; };     // x^(8 * 256 * 2^l), x^(8 * 65536), x^(8 * bytes of the last workgroup's share)
-__global__ __launch_bounds__(kCrcWG) void png_crc_kernel(unsigned char* __restrict__ file, PngGeom g, CrcOps ops, const unsigned long long* __restrict__ acc,
-                                                          unsigned* __restrict__ part, unsigned* __restrict__ ticket) {
+__global__ __launch_bounds__(kCrcWG) void png_crc_kernel(unsigned char* __restrict__ files, unsigned long long file_pitch, PngGeom g, CrcOps ops,
+                                                          const unsigned long long* __restrict__ acc_all, unsigned* __restrict__ part_all, unsigned* __restrict__ tickets) {
     __shared__ unsigned s_tab[256];
     __shared__ unsigned s_reg[kCrcWG];
     __shared__ unsigned s_last;
+    unsigned char* __restrict__ file = files + (unsigned long long)blockIdx.y * file_pitch;
+    const unsigned long long* acc = acc_all + 2 * blockIdx.y;
+    unsigned* part = part_all + (size_t)blockIdx.y * gridDim.x;
+    unsigned* ticket = tickets + blockIdx.y;
     {   // byte table of the reflected polynomial
         unsigned c = threadIdx.x;
         for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ kCrcPoly : c >> 1;
@@ -154,8 +183,8 @@ __global__ __launch_bounds__(kCrcWG) void png_crc_kernel(unsigned char* __restri
     const unsigned long long adler_off = g.idat + 4 + g.zlen - 4;
     // every workgroup derives the same Adler-32 (two loads); the one whose slices hold it patches the bytes in before reading them
     const unsigned long long S = acc[0], T = acc[1];
-    const unsigned A = (unsigned)((1 + S) % 65521ull);
-    const unsigned B = (unsigned)((g.raw % 65521ull + (g.raw % 65521ull) * (S % 65521ull) + 65521ull - T % 65521ull) % 65521ull);
+    const unsigned A = (unsigned)((1 + S) % kAdlerMod);
+    const unsigned B = (unsigned)((g.raw % kAdlerMod + (g.raw % kAdlerMod) * (S % kAdlerMod) + kAdlerMod - T % kAdlerMod) % kAdlerMod);
     const unsigned adler = (B << 16) | A;
     __syncthreads();
     const unsigned long long lo = (unsigned long long)blockIdx.x * (kCrcWG * kSlice) + (unsigned long long)threadIdx.x * kSlice;     // offset within the CRC'd range
@@ -169,10 +198,8 @@ __global__ __launch_bounds__(kCrcWG) void png_crc_kernel(unsigned char* __restri
             reg = s_tab[(reg ^ v) & 0xffu] ^ (reg >> 8);
         }
     }
-    // a slice shorter than 256 bytes (the chunk's tail) must still count as |B| = 256 in the tree: pad it with zero bytes on the RIGHT?
-    // No -- zeros on the right change the register.  Instead the tree runs over FULL slices only and the host chose the operators so
-    // that the tail is handled exactly: every slice but the chunk's last is full, and a partial / empty slice to the right of it is
-    // combined with its TRUE length (0 .. 255), i.e. operator x^(8 len) computed here (rare: one thread per launch).
+    // Every slice but the chunk's last is full; a partial / empty slice to the right of it is combined with its TRUE length
+    // (0 .. 255 bytes), i.e. the operator x^(8 len) computed here (rare: a few threads per image).
     s_reg[threadIdx.x] = reg;
     __syncthreads();
     // true byte count of the slices [t, t + span) of this workgroup
@@ -215,15 +242,18 @@ __global__ __launch_bounds__(kCrcWG) void png_crc_kernel(unsigned char* __restri
         const unsigned crc = r ^ 0xffffffffu;
         const unsigned long long co = g.idat + g.crc_len;
         file[co] = (unsigned char)(crc >> 24); file[co + 1] = (unsigned char)(crc >> 16); file[co + 2] = (unsigned char)(crc >> 8); file[co + 3] = (unsigned char)crc;
-        *ticket = 0;                                             // the next call finds the ticket at zero: no memset per call
     }
 }
 
-// K3: base64 (RFC 4648, '=' padded): a thread turns 12 file bytes (three dwords) into 16 characters (four dwords).
+// K3: base64 (RFC 4648, '=' padded): a thread turns 12 file bytes (three dwords) into 16 characters (four dwords).  blockIdx.y is
+// the image.
 __device__ __forceinline__ unsigned b64_char(unsigned v) {     // 0..63 -> 'A'..'Z' 'a'..'z' '0'..'9' '+' '/'
     return v < 26 ? v + 65 : v < 52 ? v + 71 : v < 62 ? v - 4 : v == 62 ? 43 : 47;
 }
-__global__ __launch_bounds__(256) void base64_kernel(const unsigned char* __restrict__ in, unsigned long long n, unsigned char* __restrict__ out) {
+__global__ __launch_bounds__(256) void base64_kernel(const unsigned char* __restrict__ files, unsigned long long file_pitch, unsigned long long n,
+                                                      unsigned char* __restrict__ texts, unsigned long long text_pitch) {
+    const unsigned char* __restrict__ in = files + (unsigned long long)blockIdx.y * file_pitch;
+    unsigned char* __restrict__ out = texts + (unsigned long long)blockIdx.y * text_pitch;
     const unsigned long long t = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
     const unsigned long long i0 = t * 12;
     if (i0 >= n) return;
@@ -244,32 +274,90 @@ __global__ __launch_bounds__(256) void base64_kernel(const unsigned char* __rest
         o[q] = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
     }
     const unsigned long long groups = (n + 2) / 3, g0 = t * 4;
-    unsigned* dst = reinterpret_cast<unsigned*>(out + g0 * 4);
+    unsigned char* dst = out + g0 * 4;
+    if ((text_pitch & 3u) == 0 && (reinterpret_cast<unsigned long long>(texts) & 3u) == 0) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) if (g0 + q < groups) dst[q] = o[q];
+        for (int q = 0; q < 4; ++q) if (g0 + q < groups) reinterpret_cast<unsigned*>(dst)[q] = o[q];
+    } else {                                                                  // a caller's stride that is no multiple of 4: bytes
+#pragma unroll
+        for (int q = 0; q < 4; ++q) if (g0 + q < groups) { dst[4 * q] = (unsigned char)o[q]; dst[4 * q + 1] = (unsigned char)(o[q] >> 8); dst[4 * q + 2] = (unsigned char)(o[q] >> 16); dst[4 * q + 3] = (unsigned char)(o[q] >> 24); }
+    }
+}
+
+// ---- any-size jobs: edge-replicate pad in front of the network, crop of the window behind it ---------------------------------------
+// [n][h][w][3] -> [n][H][W][3], pixel (y, x) = source (min(y, h - 1), min(x, w - 1)).  3 W is a multiple of 4 (W % 8 == 0) and the
+// destination is the engine's own staging: a thread stores one dword of a padded row; the source is read as bytes.
+__global__ __launch_bounds__(256) void pad_edge_kernel(const unsigned char* __restrict__ src, int h, int w, unsigned char* __restrict__ dst, int H, int W) {
+    const unsigned dw_row = 3u * (unsigned)W / 4u;
+    const unsigned xd = blockIdx.x * 256 + threadIdx.x;
+    if (xd >= dw_row) return;
+    const unsigned y = blockIdx.y, img = blockIdx.z;
+    const unsigned sy = y < (unsigned)h ? y : (unsigned)h - 1;
+    const unsigned char* __restrict__ srow = src + ((size_t)img * h + sy) * (size_t)w * 3;
+    unsigned out = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned b = xd * 4 + k, x = b / 3, c = b - x * 3;
+        const unsigned sx = x < (unsigned)w ? x : (unsigned)w - 1;
+        out |= (unsigned)srow[sx * 3 + c] << (8 * k);
+    }
+    reinterpret_cast<unsigned*>(dst + ((size_t)img * H + y) * (size_t)W * 3)[xd] = out;
+}
+
+// the top-left h x w window of [n][H][W][3] -> [n][h][w][3] tightly packed.  The packed result is one run of n*h*w*3 bytes; a thread
+// moves the 4 of them that share a dword of the destination (`mis` = the destination's address mod 4), so every thread but the
+// first and the last of the run stores one aligned dword whatever h*w*3 and the caller's pointer are.
+__global__ __launch_bounds__(256) void crop_window_kernel(const unsigned char* __restrict__ src, int H, int W, unsigned char* __restrict__ dst, int n, int h, int w, unsigned mis) {
+    const unsigned long long per = (unsigned long long)h * w * 3, total = per * (unsigned long long)n;
+    const unsigned long long t = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long lo = t * 4 < mis ? 0 : t * 4 - mis, hi = t * 4 + 4 - mis < total ? t * 4 + 4 - mis : total;      // [lo, hi) of the run
+    if (lo >= hi) return;
+    const unsigned row = 3u * (unsigned)w;
+    unsigned long long img = lo / per;
+    const unsigned long long rem = lo - img * per;
+    unsigned y = (unsigned)(rem / row), c = (unsigned)(rem - (unsigned long long)y * row);
+    const unsigned cnt = (unsigned)(hi - lo);
+    unsigned v[4] = {0, 0, 0, 0};
+    for (unsigned k = 0; k < cnt; ++k) {
+        v[k] = src[((size_t)img * H + y) * (size_t)W * 3 + c];
+        if (++c == row) { c = 0; if (++y == (unsigned)h) { y = 0; ++img; } }
+    }
+    if (cnt == 4) *reinterpret_cast<unsigned*>(dst + lo) = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+    else for (unsigned k = 0; k < cnt; ++k) dst[lo + k] = (unsigned char)v[k];
+}
+
+struct ScratchLayout { size_t acc, tickets, parts, files, file_pitch, total; unsigned nwg; };
+ScratchLayout layout_of(int n, const PngGeom& g) {
+    ScratchLayout L;
+    L.nwg = (unsigned)((g.crc_len + (size_t)kCrcWG * kSlice - 1) / ((size_t)kCrcWG * kSlice));
+    L.acc = 0;                                                       // n x (S, T) u64
+    L.tickets = (size_t)n * 16;                                      // n x u32, directly behind the sums: one memset clears both
+    L.parts = (L.tickets + (size_t)n * 4 + 255) / 256 * 256;         // n x nwg CRC registers
+    L.files = (L.parts + (size_t)n * L.nwg * 4 + 255) / 256 * 256;
+    L.file_pitch = (((size_t)g.file + 11) / 12 * 12 + 16 + 255) / 256 * 256;     // (padded so that the 12-byte groups of the last base64 threads stay inside)
+    L.total = L.files + L.file_pitch * (size_t)n;
+    return L;
 }
 
 }  // namespace
 
 size_t png_file_bytes(int h, int w) { return (size_t)geom_of(h, w).file; }
 size_t png_base64_chars(int h, int w) { return (png_file_bytes(h, w) + 2) / 3 * 4; }
-size_t png_scratch_bytes(int h, int w) {       // file (padded so that the 12-byte groups of the last threads stay inside) | 2 x u64 sums | ticket | per-workgroup CRC registers
-    const PngGeom g = geom_of(h, w);
-    const size_t file_pad = ((size_t)g.file + 11) / 12 * 12 + 16;
-    const size_t nwg = ((size_t)g.crc_len + kCrcWG * kSlice - 1) / (kCrcWG * kSlice);
-    return (file_pad + 15) / 16 * 16 + 32 + 16 + nwg * 4 + 16;
-}
+size_t png_scratch_bytes(int n, int h, int w) { return layout_of(n, geom_of(h, w)).total; }
 
-// d_rgb [h][w][3] -> d_chars (png_base64_chars bytes of ASCII); d_scratch: png_scratch_bytes, zero at first use (the kernels reset what
-// they count in).  Three dependent launches on `s`.
-void encode_png_base64_launch(const unsigned char* d_rgb, int h, int w, unsigned char* d_scratch, unsigned char* d_chars, hipStream_t s) {
-    if (h <= 0 || w <= 0 || w % 8 || h > 16384 || w > 16384) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder: width must be a multiple of 8");
+// The top-left h x w window of n images (rows row_pitch, images image_pitch bytes apart) -> n texts text_pitch bytes apart
+// (png_base64_chars(h, w) bytes of ASCII each).  d_scratch: png_scratch_bytes(n, h, w); nothing in it has to be initialised.
+// One memset of the n Adler sums and tickets and three launches on `s`, whatever n is.
+void encode_png_base64_launch(const unsigned char* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, unsigned char* d_scratch,
+                              unsigned char* d_chars, size_t text_pitch, hipStream_t s) {
+    if (n < 1 || n > 65535 || h <= 0 || w <= 0 || h > 16384 || w > 16384) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder (1..16384 per side)");
+    if (row_pitch < (size_t)3 * w) fail(IRE_ERR_INVALID_INPUT, "invalid row pitch for the PNG encoder (< 3*w)");
     const PngGeom g = geom_of(h, w);
-    const size_t file_pad = (((size_t)g.file + 11) / 12 * 12 + 16 + 15) / 16 * 16;
-    unsigned char* file = d_scratch;
-    unsigned long long* acc = reinterpret_cast<unsigned long long*>(d_scratch + file_pad);
-    unsigned* ticket = reinterpret_cast<unsigned*>(d_scratch + file_pad + 32);
-    unsigned* part = reinterpret_cast<unsigned*>(d_scratch + file_pad + 48);
+    const ScratchLayout L = layout_of(n, g);
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(d_scratch + L.acc);
+    unsigned* tickets = reinterpret_cast<unsigned*>(d_scratch + L.tickets);
+    unsigned* parts = reinterpret_cast<unsigned*>(d_scratch + L.parts);
+    unsigned char* files = d_scratch + L.files;
     PngHead head;
     {
         static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
@@ -285,23 +373,37 @@ void encode_png_base64_launch(const unsigned char* d_rgb, int h, int w, unsigned
         d[0] = (unsigned char)(g.zlen >> 24); d[1] = (unsigned char)(g.zlen >> 16); d[2] = (unsigned char)(g.zlen >> 8); d[3] = (unsigned char)g.zlen;
         d[4] = 'I'; d[5] = 'D'; d[6] = 'A'; d[7] = 'T';
     }
-    IRE_HIP(hipMemsetAsync(acc, 0, 16, s));
-    const unsigned nthr = (unsigned)((g.file + 3) / 4);
-    hipLaunchKernelGGL(png_frame_kernel, dim3((nthr + 255) / 256), dim3(256), 0, s, d_rgb, g, head, file);
-    const unsigned long long npb = (unsigned long long)h * w * 3;
-    unsigned agrid = (unsigned)((npb / 4 + 1023) / 1024);
-    if (agrid > 1024) agrid = 1024;
-    if (agrid < 1) agrid = 1;
-    hipLaunchKernelGGL(png_adler_kernel, dim3(agrid), dim3(256), 0, s, d_rgb, g, acc);
+    IRE_HIP(hipMemsetAsync(d_scratch, 0, (size_t)n * 20, s));       // the sums and the tickets
+    const PngSrc src{d_rgb, (unsigned long long)row_pitch, (unsigned long long)image_pitch};
+    const unsigned long long dwords = (g.file + 3) / 4;
+    const unsigned fgrid = (unsigned)((dwords + (unsigned long long)kFrameThreads * kFrameDwords - 1) / ((unsigned long long)kFrameThreads * kFrameDwords));
+    hipLaunchKernelGGL(png_frame_kernel, dim3(fgrid, n), dim3(kFrameThreads), 0, s, src, g, head, files, (unsigned long long)L.file_pitch, acc);
     CrcOps ops;
     for (int l = 0; l < 8; ++l) ops.lvl[l] = gf_x_pow_8n((size_t)kSlice << l);
     const size_t wg_bytes = (size_t)kCrcWG * kSlice;
-    const unsigned nwg = (unsigned)((g.crc_len + wg_bytes - 1) / wg_bytes);
     ops.wg = gf_x_pow_8n(wg_bytes);
-    ops.last_wg = gf_x_pow_8n((size_t)(g.crc_len - (unsigned long long)(nwg - 1) * wg_bytes));
-    hipLaunchKernelGGL(png_crc_kernel, dim3(nwg), dim3(kCrcWG), 0, s, file, g, ops, acc, part, ticket);
+    ops.last_wg = gf_x_pow_8n((size_t)(g.crc_len - (unsigned long long)(L.nwg - 1) * wg_bytes));
+    hipLaunchKernelGGL(png_crc_kernel, dim3(L.nwg, n), dim3(kCrcWG), 0, s, files, (unsigned long long)L.file_pitch, g, ops, acc, parts, tickets);
     const unsigned long long groups12 = (g.file + 11) / 12;
-    hipLaunchKernelGGL(base64_kernel, dim3((unsigned)((groups12 + 255) / 256)), dim3(256), 0, s, file, g.file, d_chars);
+    hipLaunchKernelGGL(base64_kernel, dim3((unsigned)((groups12 + 255) / 256), n), dim3(256), 0, s, files, (unsigned long long)L.file_pitch, g.file, d_chars,
+                       (unsigned long long)text_pitch);
+    IRE_HIP(hipGetLastError());
+}
+
+// d_src [n][h][w][3] -> d_dst [n][H][W][3], edge-replicated (H >= h, W >= w, W % 8 == 0).  One launch.
+void pad_edge_launch(const unsigned char* d_src, int n, int h, int w, unsigned char* d_dst, int H, int W, hipStream_t s) {
+    if (n < 1 || h < 1 || w < 1 || H < h || W < w || W % 8 || H > 65535 || n > 65535) fail(IRE_ERR_INVALID_INPUT, "invalid sizes for the edge pad");
+    const unsigned dw_row = 3u * (unsigned)W / 4u;
+    hipLaunchKernelGGL(pad_edge_kernel, dim3((dw_row + 255) / 256, H, n), dim3(256), 0, s, d_src, h, w, d_dst, H, W);
+    IRE_HIP(hipGetLastError());
+}
+
+// the top-left h x w window of d_src [n][H][W][3] -> d_dst [n][h][w][3].  One launch.
+void crop_window_launch(const unsigned char* d_src, int n, int H, int W, unsigned char* d_dst, int h, int w, hipStream_t s) {
+    if (n < 1 || h < 1 || w < 1 || H < h || W < w || n > 65535) fail(IRE_ERR_INVALID_INPUT, "invalid sizes for the window crop");
+    const unsigned long long total = (unsigned long long)h * w * 3 * n;
+    const unsigned mis = (unsigned)(reinterpret_cast<size_t>(d_dst) & 3u);
+    hipLaunchKernelGGL(crop_window_kernel, dim3((unsigned)((total + mis + 1023) / 1024)), dim3(256), 0, s, d_src, H, W, d_dst, n, h, w, mis);
     IRE_HIP(hipGetLastError());
 }
 

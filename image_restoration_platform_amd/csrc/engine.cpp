@@ -190,7 +190,7 @@ Engine::~Engine() {
     for (void* p : net_.allocs) (void)hipFree(p);
     for (void* p : table_allocs_) (void)hipFree(p);
     for (void* p : {(void*)d_in_, (void*)d_out_, (void*)d_jpeg_, (void*)d_sums_, (void*)d_scores_, (void*)d_label_,
-                    (void*)d_cond_, (void*)d_film_, d_zero_, (void*)d_fL_, (void*)d_fQ_, (void*)d_fsad_, (void*)d_fmisc_, (void*)d_fwlut_, (void*)d_pp_tab_, (void*)d_pp_mid_, (void*)d_pp_in_, (void*)d_pp_out_, (void*)d_enc_scratch_, (void*)d_enc_io_})
+                    (void*)d_cond_, (void*)d_film_, d_zero_, (void*)d_fL_, (void*)d_fQ_, (void*)d_fsad_, (void*)d_fmisc_, (void*)d_fwlut_, (void*)d_pp_tab_, (void*)d_pp_mid_, (void*)d_pp_in_, (void*)d_pp_out_, (void*)d_enc_scratch_, (void*)d_enc_io_, (void*)d_pad_in_, (void*)d_pad_out_})
         if (p) (void)hipFree(p);
     for (auto& L : lanes_) {
         if (L.stream) (void)hipStreamDestroy(L.stream);
@@ -688,29 +688,63 @@ void Engine::leave(hipStream_t s) {
     if (hipEventRecord(busy_ev_, s) == hipSuccess) busy_recorded_ = true;
 }
 
-void Engine::encode_png_base64_device(const uint8_t* d_rgb, int n, int h, int w, uint8_t* d_chars, size_t stride, hipStream_t s) {
-    if (!d_rgb || !d_chars || n < 1 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images)");
-    if (h < 1 || w < 8 || w % 8 || h > 16384 || w > 16384) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder: width must be a multiple of 8");
+void Engine::check_fit(int n, int h, int w) const {
+    if (n <= 0 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid batch size n (1..max_batch)");
+    if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size: height and width must be in 1..8192");
+}
+
+void Engine::ensure_pad(int n, int H, int W) {
+    const size_t need = (size_t)n * H * W * 3;
+    if (need <= pad_cap_) return;
+    IRE_HIP(hipSetDevice(device_));
+    IRE_HIP(hipDeviceSynchronize());
+    if (d_pad_in_) (void)hipFree(d_pad_in_);
+    if (d_pad_out_) (void)hipFree(d_pad_out_);
+    d_pad_in_ = d_pad_out_ = nullptr; pad_cap_ = 0;
+    // small shapes: room for a whole batch at once (the first batch of a shape allocates, the later ones never do)
+    const size_t per = (size_t)H * W * 3;
+    const size_t want = per * (size_t)max_batch_ <= ((size_t)256 << 20) ? per * (size_t)max_batch_ : need;
+    d_pad_in_ = (uint8_t*)dalloc(want);
+    d_pad_out_ = (uint8_t*)dalloc(want);
+    pad_cap_ = want;
+}
+
+// the one encoder behind every entry: the window of n images -> n texts.  Three launches and one small memset per batch.
+void Engine::encode_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, hipStream_t s) {
     if (stride < png_base64_chars(h, w)) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the PNG encoder: smaller than ire_png_base64_bytes(h, w)");
-    const size_t per = (png_scratch_bytes(h, w) + 255) / 256 * 256, need = per * (size_t)n;
+    if (row_pitch < (size_t)3 * w || (n > 1 && image_pitch < row_pitch * (size_t)(h - 1) + (size_t)3 * w))
+        fail(IRE_ERR_INVALID_INPUT, "invalid pitch for the PNG encoder: rows or images overlap");
+    const size_t need = png_scratch_bytes(n, h, w);
     if (need > enc_scratch_cap_) {
         IRE_HIP(hipDeviceSynchronize());
         if (d_enc_scratch_) IRE_HIP(hipFree(d_enc_scratch_));
         d_enc_scratch_ = nullptr; enc_scratch_cap_ = 0;
-        d_enc_scratch_ = (uint8_t*)dalloc(need);
-        enc_scratch_cap_ = need;
+        const size_t full = png_scratch_bytes(max_batch_, h, w);       // a whole batch of this shape when that is small
+        const size_t want = full <= ((size_t)256 << 20) ? full : need;
+        d_enc_scratch_ = (uint8_t*)dalloc(want);
+        enc_scratch_cap_ = want;
     }
-    // (the tickets must start at zero; the kernels leave them at zero: one memset per geometry change would do, one per call is 3 us)
-    IRE_HIP(hipMemsetAsync(d_enc_scratch_, 0, need, s));
-    for (int i = 0; i < n; ++i)
-        encode_png_base64_launch(d_rgb + (size_t)i * h * w * 3, h, w, d_enc_scratch_ + per * i, d_chars + stride * i, s);
+    encode_png_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_enc_scratch_, d_chars, stride, s);
 }
 
-void Engine::encode_png_base64_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride) {
-    if (!rgb || !chars) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder: null buffer");
-    if (n < 1 || n > max_batch_ || h < 1 || w < 8 || w % 8 || h > 16384 || w > 16384) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images, width a multiple of 8)");
+void Engine::encode_png_base64_device(const uint8_t* d_rgb, int n, int h, int w, uint8_t* d_chars, size_t stride, hipStream_t s) {
+    if (!d_rgb || !d_chars || n < 1 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images)");
+    if (h < 1 || w < 8 || w % 8 || h > 16384 || w > 16384) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder: width must be a multiple of 8");
+    encode_window(d_rgb, n, h, w, (size_t)3 * w, (size_t)3 * w * h, d_chars, stride, s);
+}
+
+void Engine::encode_png_base64_fit_device(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride,
+                                          hipStream_t s) {
+    if (!d_rgb || !d_chars || n < 1 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images)");
+    if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder: height and width must be in 1..8192");
+    encode_window(d_rgb, n, h, w, row_pitch, image_pitch, d_chars, stride, s);
+}
+
+void Engine::encode_host_impl(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride) {
     const size_t ib = (size_t)h * w * 3, cb = png_base64_chars(h, w), cpad = (cb + 255) / 256 * 256;
-    const size_t need = (ib + cpad) * (size_t)n;
+    if (stride < cb) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the PNG encoder: smaller than ire_png_base64_bytes(h, w)");
+    const size_t in_pad = (ib * n + 255) / 256 * 256;
+    const size_t need = in_pad + cpad * (size_t)n;
     if (need > enc_io_cap_) {
         IRE_HIP(hipDeviceSynchronize());
         if (d_enc_io_) IRE_HIP(hipFree(d_enc_io_));
@@ -720,10 +754,22 @@ void Engine::encode_png_base64_host(const uint8_t* rgb, int n, int h, int w, uin
     }
     hipStream_t s = main_stream_;
     IRE_HIP(hipMemcpyAsync(d_enc_io_, rgb, ib * n, hipMemcpyHostToDevice, s));
-    uint8_t* d_txt = d_enc_io_ + ib * n;
-    encode_png_base64_device(d_enc_io_, n, h, w, d_txt, cpad, s);
+    uint8_t* d_txt = d_enc_io_ + in_pad;
+    encode_window(d_enc_io_, n, h, w, (size_t)3 * w, ib, d_txt, cpad, s);
     for (int i = 0; i < n; ++i) IRE_HIP(hipMemcpyAsync(chars + stride * i, d_txt + cpad * i, cb, hipMemcpyDeviceToHost, s));
     IRE_HIP(hipStreamSynchronize(s));
+}
+
+void Engine::encode_png_base64_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride) {
+    if (!rgb || !chars) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder: null buffer");
+    if (n < 1 || n > max_batch_ || h < 1 || w < 8 || w % 8 || h > 16384 || w > 16384) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images, width a multiple of 8)");
+    encode_host_impl(rgb, n, h, w, chars, stride);
+}
+
+void Engine::encode_png_base64_fit_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride) {
+    if (!rgb || !chars) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder: null buffer");
+    if (n < 1 || n > max_batch_ || h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images, 1..8192 per side)");
+    encode_host_impl(rgb, n, h, w, chars, stride);
 }
 
 void Engine::free_workspace() {
@@ -1288,14 +1334,55 @@ void Engine::restore_tiled_device(const uint8_t* d_rgb, int h, int w, int nstrip
 void Engine::restore_device_mixed(const uint8_t* d_rgb, int n, int h, int w, const double* host_scores, const uint8_t* has_scores,
                                   const uint8_t* d_is_jpeg, uint8_t* d_out, hipStream_t stream) {
     check_shape(n, h, w, true);
+    restore_fit_device_mixed(d_rgb, n, h, w, host_scores, has_scores, d_is_jpeg, d_out, nullptr, 0, stream);
+}
+
+// pad into d_pad_in_, the network on the padded shape into d_pad_out_ (d_scores: of the original pixels, never null here)
+void Engine::restore_padded(const uint8_t* d_rgb, int n, int h, int w, const double* d_scores, const uint8_t* d_is_jpeg, hipStream_t stream) {
+    if (!net_.loaded) fail(IRE_ERR_UNAVAILABLE, "service unavailable: RestoreNet weights are not loaded");
+    const int H = fit_dim(h), W = fit_dim(w);
+    ensure_pad(n, H, W);
+    pad_edge_launch(d_rgb, n, h, w, d_pad_in_, H, W, stream);
+    restore_device(d_pad_in_, n, H, W, d_scores, d_is_jpeg, d_pad_out_, stream);
+}
+
+void Engine::restore_fit_device(const uint8_t* d_rgb, int n, int h, int w, const double* d_scores, const uint8_t* d_is_jpeg, uint8_t* d_out,
+                                hipStream_t stream) {
+    check_fit(n, h, w);
+    if (fit_is_aligned(h, w)) { restore_device(d_rgb, n, h, w, d_scores, d_is_jpeg, d_out, stream); return; }
+    if (!d_rgb || !d_out) fail(IRE_ERR_INVALID_INPUT, "invalid input: null image pointer");
     ensure_io(n, 1, 1);
+    if (!d_scores) {          // the classifier reads the ORIGINAL pixels, never the padded copy
+        classify_device(d_rgb, n, h, w, d_is_jpeg, d_scores_, d_label_, stream);
+        d_scores = d_scores_;
+    }
+    restore_padded(d_rgb, n, h, w, d_scores, d_is_jpeg, stream);
+    crop_window_launch(d_pad_out_, n, fit_dim(h), fit_dim(w), d_out, h, w, stream);
+}
+
+void Engine::restore_fit_device_mixed(const uint8_t* d_rgb, int n, int h, int w, const double* host_scores, const uint8_t* has_scores,
+                                      const uint8_t* d_is_jpeg, uint8_t* d_out, uint8_t* d_txt, size_t txt_stride, hipStream_t stream) {
+    check_fit(n, h, w);
+    ensure_io(n, 1, 1);
+    const bool aligned = fit_is_aligned(h, w);
     bool any_missing = false, any_given = false;
     for (int i = 0; i < n; ++i) { if (has_scores && has_scores[i]) any_given = true; else any_missing = true; }
-    if (!any_given) { restore_device(d_rgb, n, h, w, nullptr, d_is_jpeg, d_out, stream); return; }
-    if (any_missing) classify_device(d_rgb, n, h, w, d_is_jpeg, d_scores_, d_label_, stream);
-    for (int i = 0; i < n; ++i)
-        if (has_scores[i]) IRE_HIP(hipMemcpyAsync(d_scores_ + 7 * i, host_scores + 7 * i, sizeof(double) * 7, hipMemcpyHostToDevice, stream));
-    restore_device(d_rgb, n, h, w, d_scores_, d_is_jpeg, d_out, stream);
+    const double* d_sc = nullptr;       // null: restore_device classifies inside (its scan also writes the FiLM vector); only an aligned shape may
+    if (any_given || !aligned) {
+        if (any_missing) classify_device(d_rgb, n, h, w, d_is_jpeg, d_scores_, d_label_, stream);      // the ORIGINAL pixels
+        for (int i = 0; i < n; ++i)
+            if (has_scores && has_scores[i]) IRE_HIP(hipMemcpyAsync(d_scores_ + 7 * i, host_scores + 7 * i, sizeof(double) * 7, hipMemcpyHostToDevice, stream));
+        d_sc = d_scores_;
+    }
+    if (aligned) {
+        restore_device(d_rgb, n, h, w, d_sc, d_is_jpeg, d_out, stream);
+        if (d_txt) encode_window(d_out, n, h, w, (size_t)3 * w, (size_t)3 * w * h, d_txt, txt_stride, stream);
+        return;
+    }
+    const int H = fit_dim(h), W = fit_dim(w);
+    restore_padded(d_rgb, n, h, w, d_sc, d_is_jpeg, stream);
+    if (d_txt) encode_window(d_pad_out_, n, h, w, (size_t)3 * W, (size_t)3 * W * H, d_txt, txt_stride, stream);     // the crop costs no pass of its own
+    else crop_window_launch(d_pad_out_, n, H, W, d_out, h, w, stream);
 }
 
 void Engine::get_stats(ire_engine_stats* out) {
@@ -1329,9 +1416,9 @@ void Engine::classify_host(const uint8_t* rgb, int n, int h, int w, int row_stri
     IRE_HIP(hipStreamSynchronize(s));
 }
 
-void Engine::restore_host(const uint8_t* rgb, int n, int h, int w, const double* scores, const uint8_t* is_jpeg,
-                          uint8_t* out, ire_timings* t) {
-    check_shape(n, h, w, true);
+// the synchronous host entry behind ire_restore and ire_restore_fit: upload, classify (unless scores are given), restore, download
+void Engine::restore_host_impl(const uint8_t* rgb, int n, int h, int w, const double* scores, const uint8_t* is_jpeg,
+                               uint8_t* out, ire_timings* t) {
     if (!rgb || !out) fail(IRE_ERR_INVALID_INPUT, "invalid input: null pointer");
     ensure_io(n, h, w);
     hipStream_t s = main_stream_;
@@ -1347,14 +1434,14 @@ void Engine::restore_host(const uint8_t* rgb, int n, int h, int w, const double*
         IRE_HIP(hipMemcpyAsync(d_scores_, scores, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
         d_sc = d_scores_;
     } else {
-        // classify as its own step so classify_ms / restore_ms mirror restorator.js:59-95
+        // classify as its own step so classify_ms / restore_ms mirror restorator.js:59-95 (the pixels as uploaded, never a padded copy)
         prof_begin(FAM_CLASSIFIER, s, 0, (double)n * h * w * 3);
         classifier_launch(tables_, d_in_, n, h, w, d_jpeg_, d_sums_, d_scores_, d_label_, d_cond_, s);
         prof_end(s);
         d_sc = d_scores_;
     }
     IRE_HIP(hipEventRecord(ev_[2], s));
-    restore_device(d_in_, n, h, w, d_sc, d_jpeg_, d_out_, s);
+    restore_fit_device(d_in_, n, h, w, d_sc, d_jpeg_, d_out_, s);       // (an aligned shape: restore_device as it is)
     IRE_HIP(hipEventRecord(ev_[3], s));
     IRE_HIP(hipMemcpyAsync(out, d_out_, bytes, hipMemcpyDeviceToHost, s));
     IRE_HIP(hipStreamSynchronize(s));
@@ -1365,6 +1452,16 @@ void Engine::restore_host(const uint8_t* rgb, int n, int h, int w, const double*
         IRE_HIP(hipEventElapsedTime(&c, ev_[0], ev_[3]));
         t->classify_ms = a; t->restore_ms = b; t->total_ms = c;
     }
+}
+
+void Engine::restore_host(const uint8_t* rgb, int n, int h, int w, const double* scores, const uint8_t* is_jpeg, uint8_t* out, ire_timings* t) {
+    check_shape(n, h, w, true);
+    restore_host_impl(rgb, n, h, w, scores, is_jpeg, out, t);
+}
+
+void Engine::restore_fit_host(const uint8_t* rgb, int n, int h, int w, const double* scores, const uint8_t* is_jpeg, uint8_t* out, ire_timings* t) {
+    check_fit(n, h, w);
+    restore_host_impl(rgb, n, h, w, scores, is_jpeg, out, t);
 }
 
 }  // namespace ire

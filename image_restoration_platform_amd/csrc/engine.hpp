@@ -164,6 +164,24 @@ public:
     // encode.hip: n images [h][w][3] -> n x png_base64_chars(h, w) characters, `stride` bytes apart (device buffers, asynchronous on s)
     void encode_png_base64_device(const uint8_t* d_rgb, int n, int h, int w, uint8_t* d_chars, size_t stride, hipStream_t s);
     void encode_png_base64_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride);
+    // the same encoder without the multiple-of-8 rule (h, w in 1..8192), reading the top-left h x w window of images that lie
+    // row_pitch / image_pitch bytes apart; the two entries above are their own argument checks in front of encode_window
+    void encode_png_base64_fit_device(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride,
+                                      hipStream_t s);
+    void encode_png_base64_fit_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride);
+    // Any-size jobs (h, w in 1..8192): edge-replicate pad to (max(16, ceil8 h), max(16, ceil8 w)) into the engine's padded
+    // staging, the network on the padded shape, the top-left h x w window as the result.  The classifier always sees the
+    // ORIGINAL pixels.  A shape restore_device takes as it is skips the pad and runs exactly as restore_device does.
+    void restore_fit_device(const uint8_t* d_rgb, int n, int h, int w, const double* d_scores, const uint8_t* d_is_jpeg, uint8_t* d_out,
+                            hipStream_t stream);
+    void restore_fit_host(const uint8_t* rgb, int n, int h, int w, const double* scores, const uint8_t* is_jpeg, uint8_t* out, ire_timings* t);
+    // batcher form (restore_device_mixed for any size).  d_txt == null: d_out receives the n*h*w*3 result pixels.  d_txt != null:
+    // the results leave as text (png_base64_chars(h, w) characters each, txt_stride apart), encoded where the network left
+    // them; d_out is then working space of n*h*w*3 bytes.
+    void restore_fit_device_mixed(const uint8_t* d_rgb, int n, int h, int w, const double* host_scores, const uint8_t* has_scores,
+                                  const uint8_t* d_is_jpeg, uint8_t* d_out, uint8_t* d_txt, size_t txt_stride, hipStream_t stream);
+    static bool fit_is_aligned(int h, int w) { return h % 8 == 0 && w % 8 == 0 && h >= 16 && w >= 16; }
+    static int fit_dim(int v) { return v <= 16 ? 16 : (v + 7) / 8 * 8; }
     uint32_t flags() const { return flags_; }
 
     void debug_sums(int n, uint64_t* out);
@@ -199,6 +217,12 @@ public:
 
 private:
     void check_shape(int n, int h, int w, bool for_restore) const;
+    void check_fit(int n, int h, int w) const;
+    void ensure_pad(int n, int H, int W);      // d_pad_in_ / d_pad_out_, grow-only
+    void restore_padded(const uint8_t* d_rgb, int n, int h, int w, const double* d_scores, const uint8_t* d_is_jpeg, hipStream_t stream);
+    void restore_host_impl(const uint8_t* rgb, int n, int h, int w, const double* scores, const uint8_t* is_jpeg, uint8_t* out, ire_timings* t);
+    void encode_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, hipStream_t s);
+    void encode_host_impl(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride);
     void ensure_io(int n, int h, int w);
     void ensure_workspace(int n, int h, int w);
     void free_workspace();
@@ -281,7 +305,10 @@ private:
     uint8_t* d_pp_mid_ = nullptr;
     uint8_t* d_pp_in_ = nullptr;
     uint8_t* d_pp_out_ = nullptr;
-    uint8_t* d_enc_scratch_ = nullptr;    // encode.hip: per image: the PNG file + checksum state
+    uint8_t* d_enc_scratch_ = nullptr;    // encode.hip: per batch: the PNG files + checksum state
+    uint8_t* d_pad_in_ = nullptr;         // any-size jobs: the edge-padded batch in front of the network ...
+    uint8_t* d_pad_out_ = nullptr;        // ... and the network's output on the padded shape
+    size_t pad_cap_ = 0;
     uint8_t* d_enc_io_ = nullptr;         // host entry: pixels in | characters out
     size_t enc_scratch_cap_ = 0, enc_io_cap_ = 0;
 

@@ -12,6 +12,8 @@
 //   fuse_batch(h, views[S,k,H,W,3] u8, noise[S] f64 (cpu))  -> (fused[S,H,W,3] u8, shifts[S,k,2] i32) S <= 16 restoreImage calls, one kernel chain
 //   preprocess(h, rgb[H,W,3] u8, orientation, max_dim)      -> upright, fitted [H',W',3] u8          imagePreprocess.js:24-91 (pixel part)
 //   encode_png_base64(h, rgb[N,H,W,3] u8)                   -> chars[N, ire_png_base64_bytes] u8     restorator.js:108 (the result text, on the device)
+//   restore_fit(h, rgb[N,H,W,3] u8, scores?, is_jpeg?)      -> restored[N,H,W,3] u8                  restoreImage for any H, W in 1..8192
+//   encode_png_base64_fit(h, rgb[N,H,W,3] u8, maybe a [:, :H, :W] view) -> chars[N, ire_png_base64_bytes_fit] u8     any width; strides go in as pitches
 #include <c10/hip/HIPStream.h>
 #include <dlfcn.h>
 #include <torch/extension.h>
@@ -38,6 +40,9 @@ struct Api {
     decltype(&ire_preprocess_device) preprocess_device = nullptr;
     decltype(&ire_png_base64_bytes) png_base64_bytes = nullptr;
     decltype(&ire_encode_png_base64_device) encode_png_base64_device = nullptr;
+    decltype(&ire_restore_fit_device) restore_fit_device = nullptr;
+    decltype(&ire_png_base64_bytes_fit) png_base64_bytes_fit = nullptr;
+    decltype(&ire_encode_png_base64_fit_device) encode_png_base64_fit_device = nullptr;
 } g;
 
 void load(const std::string& path) {
@@ -50,6 +55,8 @@ void load(const std::string& path) {
     SYM(restore_tiled_device, "ire_restore_tiled_device") SYM(fuse_batch_device, "ire_fuse_batch_device")
     SYM(preprocess_plan, "ire_preprocess_plan") SYM(preprocess_device, "ire_preprocess_device")
     SYM(png_base64_bytes, "ire_png_base64_bytes") SYM(encode_png_base64_device, "ire_encode_png_base64_device")
+    SYM(restore_fit_device, "ire_restore_fit_device") SYM(png_base64_bytes_fit, "ire_png_base64_bytes_fit")
+    SYM(encode_png_base64_fit_device, "ire_encode_png_base64_fit_device")
 #undef SYM
     if (g.abi_version() != IRE_ABI_VERSION) throw std::runtime_error("[ire status 3] service unavailable: libire.so ABI version mismatch");
     g.so = so;
@@ -160,6 +167,31 @@ at::Tensor encode_png_base64(int64_t h, const at::Tensor& rgb) {
     return out;
 }
 
+at::Tensor restore_fit(int64_t h, const at::Tensor& rgb, const c10::optional<at::Tensor>& scores, const c10::optional<at::Tensor>& is_jpeg) {
+    want(rgb, at::kByte, 4, "rgb must be a contiguous cuda uint8 [N,H,W,3]");
+    if (scores) want(*scores, at::kDouble, 2, "scores must be a cuda float64 [N,7]");
+    if (is_jpeg) want(*is_jpeg, at::kByte, 1, "is_jpeg must be a cuda uint8 [N]");
+    at::Tensor out = at::empty_like(rgb);
+    check(g.restore_fit_device(eng(h), rgb.data_ptr<uint8_t>(), (int)rgb.size(0), (int)rgb.size(1), (int)rgb.size(2),
+                               scores ? scores->data_ptr<double>() : nullptr, is_jpeg ? is_jpeg->data_ptr<uint8_t>() : nullptr, out.data_ptr<uint8_t>(),
+                               stream_of(rgb)));
+    return out;
+}
+
+at::Tensor encode_png_base64_fit(int64_t h, const at::Tensor& rgb) {
+    TORCH_CHECK(rgb.is_cuda() && rgb.scalar_type() == at::kByte && rgb.dim() == 4 && rgb.size(3) == 3 && rgb.stride(3) == 1 && rgb.stride(2) == 3 &&
+                rgb.stride(1) >= 3 * rgb.size(2), "[ire status 1] invalid input: rgb must be a cuda uint8 [N,H,W,3] with dense RGB pixels (a [:, :H, :W] view is fine)");
+    const int n = (int)rgb.size(0), hh = (int)rgb.size(1), ww = (int)rgb.size(2);
+    const size_t cb = g.png_base64_bytes_fit(hh, ww);
+    TORCH_CHECK(cb != 0, "[ire status 1] invalid image size for the PNG encoder: height and width must be in 1..8192");
+    const int64_t stride = ((int64_t)cb + 3) / 4 * 4;
+    at::Tensor out = at::empty({n, stride}, rgb.options());
+    const size_t row_pitch = (size_t)rgb.stride(1), image_pitch = n > 1 ? (size_t)rgb.stride(0) : row_pitch * (size_t)hh;
+    check(g.encode_png_base64_fit_device(eng(h), rgb.data_ptr<uint8_t>(), n, hh, ww, row_pitch, image_pitch, out.data_ptr<uint8_t>(), (size_t)stride,
+                                         stream_of(rgb)));
+    return out.narrow(1, 0, (int64_t)cb);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -172,6 +204,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fuse_batch", &fuse_batch, py::arg("handle"), py::arg("views"), py::arg("noise"));
     m.def("preprocess", &preprocess, py::arg("handle"), py::arg("rgb"), py::arg("orientation") = 1, py::arg("max_dim") = 2048);
     m.def("encode_png_base64", &encode_png_base64, py::arg("handle"), py::arg("rgb"));
+    m.def("restore_fit", &restore_fit, py::arg("handle"), py::arg("rgb"), py::arg("scores") = py::none(), py::arg("is_jpeg") = py::none());
+    m.def("encode_png_base64_fit", &encode_png_base64_fit, py::arg("handle"), py::arg("rgb"));
     m.def("restore_tiled", &restore_tiled, py::arg("handle"), py::arg("rgb"), py::arg("nstrips"), py::arg("scores") = py::none(),
           py::arg("is_jpeg") = py::none());
 }

@@ -114,6 +114,23 @@ class Engine:
             return out, {"classify_ms": t.classify_ms, "restore_ms": t.restore_ms, "total_ms": t.total_ms}
         return out
 
+    def restore_fit(self, rgb, scores=None, is_jpeg=True, return_timings=False):
+        """restore() for an image of ANY size (1..8192 per side): -> restored [N,H,W,3] uint8 of the input's own shape.  The engine
+        edge-replicates to the next multiple of 8 (>= 16) on the device, restores and returns the window; scores=None classifies the
+        original pixels inside the same call.  Equal, bit for bit, to restore(np.pad(x, edge), scores=classify(x)[0])[:, :H, :W]."""
+        rgb = self._as_batch(rgb)
+        n, h, w, _ = rgb.shape
+        jp = np.ascontiguousarray(np.broadcast_to(np.asarray(is_jpeg, dtype=np.uint8), (n,)))
+        sc = None
+        if scores is not None:
+            sc = np.ascontiguousarray(np.asarray(scores, dtype=np.float64).reshape(n, 7))
+        out = np.empty_like(rgb)
+        t = _lib.IreTimings()
+        self._check(self._lib.ire_restore_fit(self._h, _ptr(rgb), n, h, w, _ptr(sc), _ptr(jp), _ptr(out), ctypes.byref(t)))
+        if return_timings:
+            return out, {"classify_ms": t.classify_ms, "restore_ms": t.restore_ms, "total_ms": t.total_ms}
+        return out
+
     def fuse(self, views, noise_score=-1.0):
         """views [k,H,W,3] uint8, k in 2..3 -> (fused [H,W,3], shifts [k,2] (dy,dx))."""
         views = self._as_batch(views)
@@ -163,6 +180,17 @@ class Engine:
         self._check(self._lib.ire_submit(self._h, _ptr(rgb), h, w, int(bool(is_jpeg)), _ptr(sc), ctypes.byref(job)))
         return (job, h, w)
 
+    def submit_fit(self, rgb, is_jpeg=True, scores=None):
+        """submit() for an image of any size (1..8192 per side); poll() / release() take the job as they take submit()'s."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid input: expected [H,W,3] uint8")
+        h, w, _ = rgb.shape
+        sc = None if scores is None else np.ascontiguousarray(np.asarray(scores, dtype=np.float64).reshape(7))
+        job = ctypes.c_void_p()
+        self._check(self._lib.ire_submit_fit(self._h, _ptr(rgb), h, w, int(bool(is_jpeg)), _ptr(sc), ctypes.byref(job)))
+        return (job, h, w)
+
     def stats(self):
         """Service gauges (f4: getHealthStatus / the /health/ready dependency entry)."""
         st = _lib.IreEngineStats()
@@ -179,7 +207,7 @@ class Engine:
         of its PNG file --, scores[7], timings)"""
         handle, h, w = job
         text = bool(getattr(self, "_flags", 0) & _lib.IRE_FLAG_RESULT_PNG_BASE64)
-        out = np.empty(self.png_base64_bytes(h, w), np.uint8) if text else np.empty((h, w, 3), np.uint8)
+        out = np.empty(self.png_base64_bytes_fit(h, w), np.uint8) if text else np.empty((h, w, 3), np.uint8)     # (the job's own h, w)
         scores = np.zeros(7, np.float64)
         t = _lib.IreTimings()
         self._check(self._lib.ire_poll(self._h, handle, timeout_ms, _ptr(out), _ptr(scores), ctypes.byref(t)))
@@ -214,6 +242,54 @@ class Engine:
         self._check(self._lib.ire_encode_png_base64_device(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), n, h, w, ctypes.c_void_p(out.data_ptr()), cb,
                                                            self._stream_ptr(stream)))
         return out
+
+    def png_base64_bytes_fit(self, h, w):
+        return int(self._lib.ire_png_base64_bytes_fit(int(h), int(w)))
+
+    def encode_png_base64_fit(self, rgb):
+        """encode_png_base64() for any size (1..8192 per side)."""
+        single = np.asarray(rgb).ndim == 3
+        x = self._as_batch(rgb)
+        n, h, w, _ = x.shape
+        cb = self.png_base64_bytes_fit(h, w)
+        if cb == 0:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder: height and width must be in 1..8192")
+        stride = (cb + 15) // 16 * 16
+        out = np.empty((n, stride), np.uint8)
+        self._check(self._lib.ire_encode_png_base64_fit(self._h, _ptr(x), n, h, w, _ptr(out), stride))
+        res = [out[i, :cb].tobytes() for i in range(n)]
+        return res[0] if single else res
+
+    def encode_png_base64_fit_tensor(self, rgb_u8, stream=None):
+        """cuda uint8 [N,h,w,3], possibly a window `t[:, :h, :w]` of a larger tensor (only the pixel and channel axes have to be
+        dense) -> cuda uint8 [N, chars] ASCII; the window is encoded where it lies, its strides go to the engine as pitches."""
+        import torch
+        assert rgb_u8.is_cuda and rgb_u8.dtype == torch.uint8 and rgb_u8.dim() == 4 and rgb_u8.shape[3] == 3
+        n, h, w, _ = rgb_u8.shape
+        si, sr, sp, sc = rgb_u8.stride()
+        if sc != 1 or sp != 3 or sr < 3 * w:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid tensor layout for the PNG encoder: pixels must be dense RGB")
+        cb = self.png_base64_bytes_fit(h, w)
+        if cb == 0:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder: height and width must be in 1..8192")
+        stride = (cb + 3) // 4 * 4
+        out = torch.empty((n, stride), dtype=torch.uint8, device=rgb_u8.device)
+        self._check(self._lib.ire_encode_png_base64_fit_device(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), n, h, w, sr, si if n > 1 else max(si, sr * h),
+                                                               ctypes.c_void_p(out.data_ptr()), stride, self._stream_ptr(stream)))
+        return out[:, :cb]
+
+    def restore_fit_tensor(self, rgb_u8, out_u8=None, scores=None, is_jpeg_u8=None, stream=None):
+        """restore_tensor() for any size (1..8192 per side), asynchronous on the torch stream."""
+        import torch
+        assert rgb_u8.is_cuda and rgb_u8.dtype == torch.uint8 and rgb_u8.is_contiguous() and rgb_u8.dim() == 4
+        n, h, w, _ = rgb_u8.shape
+        if out_u8 is None:
+            out_u8 = torch.empty_like(rgb_u8)
+        sc = ctypes.c_void_p(scores.data_ptr()) if scores is not None else None
+        jp = ctypes.c_void_p(is_jpeg_u8.data_ptr()) if is_jpeg_u8 is not None else None
+        self._check(self._lib.ire_restore_fit_device(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), n, h, w, sc, jp,
+                                                     ctypes.c_void_p(out_u8.data_ptr()), self._stream_ptr(stream)))
+        return out_u8
 
     def release(self, job):
         """Give a submitted job up without fetching it (after a poll() timeout the caller will not repeat): ire_job_release."""

@@ -107,6 +107,21 @@ function createEngineRestorer(opts) {
       }
       const w = decoded[0].width, h = decoded[0].height;
       if (decoded.some((d) => d.width !== w || d.height !== h)) throw new Error('invalid images: fusion views must have identical dimensions');
+      const reply = (base64Image) => {
+        jobCounter += 1;
+        return { base64Image, metadata: { providerRequestId: 'ire-' + process.pid + '-' + jobCounter, billedTokens: null, estimatedCostUsd: 0 } };
+      };
+      if (decoded.length === 1) {
+        // one image of any size is ONE job of the engine's batcher (ire_submit_fit): the engine pads on the device, classifies the
+        // image's own pixels in the same batch when analyze() did not, and hands back the h x w window -- with textResults as the
+        // text of its PNG, which IS the result for every size (a one-byte-per-character string: no transcoding)
+        const d = decoded[0];
+        const flags = Buffer.from([d.format === 'jpeg' ? 1 : 0]);
+        const outBytes = engine.textResults ? engine.addon.pngBase64BytesFit(h, w) : 0;
+        const r = await engine.addon.restoreFitAsync(engine.handle, d.data, 1, h, w, flags, known[0] || null, timeoutMs, outBytes);
+        if (engine.textResults) return reply(r.pixels.latin1Slice(0, r.pixels.length));
+        return reply((await codec.encode({ data: r.pixels, width: w, height: h })).toString('base64'));
+      }
       // every view is queued with the engine's batcher at once (ire_submit on this thread, ire_poll on the libuv pool): the
       // views of one call and the single-image jobs of the other in-flight calls (3 per batch, 5 per worker) share engine batches
       let W = w, H = h;
@@ -126,27 +141,12 @@ function createEngineRestorer(opts) {
       });
       let restored = (await Promise.all(pending)).map((r) => r.pixels);
       if (engine.textResults) {
-        jobCounter += 1;
-        if (restored.length === 1 && W === w && H === h) {
-          // nothing was padded, nothing to fuse: the device's text IS the result (a one-byte-per-character string: no transcoding)
-          return { base64Image: restored[0].latin1Slice(0, restored[0].length),
-                   metadata: { providerRequestId: 'ire-' + process.pid + '-' + jobCounter, billedTokens: null, estimatedCostUsd: 0 } };
-        }
-        // padded or multi-view jobs need pixels again: the stored-block PNG inflates at memcpy speed
+        // fusion needs the views' pixels again: the stored-block PNG inflates at memcpy speed
         restored = await Promise.all(restored.map(async (t) => (await codec.decode(Buffer.from(t.latin1Slice(0, t.length), 'base64'))).data));
       }
-      let pixels = restored[0];
-      if (restored.length > 1) {
-        if (H < 64 || W < 64) throw new Error('invalid images: fusion needs at least 64x64 pixels');
-        const r = await engine.addon.fuseAsync(engine.handle, Buffer.concat(restored), restored.length, H, W, null, -1.0);
-        pixels = r.pixels;
-      }
-      const png = await codec.encode({ data: crop(pixels, W, w, h), width: w, height: h });
-      jobCounter += 1;
-      return {
-        base64Image: png.toString('base64'),
-        metadata: { providerRequestId: 'ire-' + process.pid + '-' + jobCounter, billedTokens: null, estimatedCostUsd: 0 },
-      };
+      if (H < 64 || W < 64) throw new Error('invalid images: fusion needs at least 64x64 pixels');
+      const r = await engine.addon.fuseAsync(engine.handle, Buffer.concat(restored), restored.length, H, W, null, -1.0);
+      return reply((await codec.encode({ data: crop(r.pixels, W, w, h), width: w, height: h })).toString('base64'));
     },
   };
 }

@@ -32,6 +32,12 @@ export function bindIre(libPath) {
     ire_png_base64_bytes: ['size_t', ['int', 'int']],
     ire_encode_png_base64_device: ['int', [P, P, 'int', 'int', 'int', P, 'size_t', P]],
     ire_encode_png_base64: ['int', [P, P, 'int', 'int', 'int', P, 'size_t']],
+    ire_restore_fit: ['int', [P, P, 'int', 'int', 'int', P, P, P, P]],
+    ire_restore_fit_device: ['int', [P, P, 'int', 'int', 'int', P, P, P, P]],
+    ire_png_base64_bytes_fit: ['size_t', ['int', 'int']],
+    ire_encode_png_base64_fit_device: ['int', [P, P, 'int', 'int', 'int', 'size_t', 'size_t', P, 'size_t', P]],
+    ire_encode_png_base64_fit: ['int', [P, P, 'int', 'int', 'int', P, 'size_t']],
+    ire_submit_fit: ['int', [P, P, 'int', 'int', 'int', P, PP]],
     ire_submit: ['int', [P, P, 'int', 'int', 'int', P, PP]],
     ire_poll: ['int', [P, P, 'int', P, P, P]],
     ire_job_release: ['int', [P, P]],

@@ -55,6 +55,9 @@ struct Api {
     decltype(&ire_preprocess) preprocess = nullptr;
     decltype(&ire_get_stats) get_stats = nullptr;
     decltype(&ire_max_batch_for) max_batch_for = nullptr;
+    decltype(&ire_restore_fit) restore_fit = nullptr;
+    decltype(&ire_submit_fit) submit_fit = nullptr;
+    decltype(&ire_png_base64_bytes_fit) png_base64_bytes_fit = nullptr;
 } g;
 
 bool load_api(const char* path, std::string* err) {
@@ -68,6 +71,7 @@ bool load_api(const char* path, std::string* err) {
     SYM(restore, "ire_restore") SYM(fuse, "ire_fuse")
     SYM(submit, "ire_submit") SYM(poll, "ire_poll") SYM(job_release, "ire_job_release") SYM(engine_affinity, "ire_engine_affinity") SYM(png_base64_bytes, "ire_png_base64_bytes") SYM(preprocess_plan, "ire_preprocess_plan") SYM(preprocess, "ire_preprocess")
     SYM(get_stats, "ire_get_stats") SYM(max_batch_for, "ire_max_batch_for")
+    SYM(restore_fit, "ire_restore_fit") SYM(submit_fit, "ire_submit_fit") SYM(png_base64_bytes_fit, "ire_png_base64_bytes_fit")
 #undef SYM
     return true;
 }
@@ -83,6 +87,7 @@ struct Job {
     ire_job* queued = nullptr;     // RESTORE with n == 1: already in the engine's batcher (ire_submit ran on the JS thread)
     int orientation = 1, max_dim = 2048, out_w = 0, out_h = 0, resized = 0;
     bool has_scores = false;
+    bool fit = false;              // RESTORE of any size: ire_restore_fit / ire_submit_fit (the engine pads and crops on the device)
     ire_engine* eng;
     std::vector<uint8_t> in, jpeg, out;
     int n, h, w;
@@ -124,7 +129,7 @@ void execute(napi_env, void* data) {
             break;
         case Job::RESTORE:
             j->out.resize((size_t)j->n * j->h * j->w * 3);      // (n > 1 only: single images go through the batcher + waiter threads)
-            j->status = g.restore(j->eng, j->in.data(), j->n, j->h, j->w, j->has_scores ? j->scores.data() : nullptr, j->jpeg.data(), j->out.data(), &j->t);
+            j->status = (j->fit ? g.restore_fit : g.restore)(j->eng, j->in.data(), j->n, j->h, j->w, j->has_scores ? j->scores.data() : nullptr, j->jpeg.data(), j->out.data(), &j->t);
             break;
         case Job::PREPROCESS:
             j->out.resize((size_t)j->out_h * j->out_w * 3);
@@ -244,7 +249,7 @@ bool waiters_start(napi_env env, ire_engine* eng) {
 }
 
 // submit(kind, engineHandle(external), pixels Buffer, n, h, w, jpegFlags Buffer|null, noise) -> Promise
-napi_value submit(napi_env env, napi_callback_info info, Job::Kind kind) {
+napi_value submit(napi_env env, napi_callback_info info, Job::Kind kind, bool fit = false) {
     size_t argc = 9; napi_value argv[9];
     napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
     if (argc < 5) { throw_err(env, "invalid arguments"); return nullptr; }
@@ -257,7 +262,7 @@ napi_value submit(napi_env env, napi_callback_info info, Job::Kind kind) {
         return nullptr;
     }
     Job* j = new Job();
-    j->kind = kind; j->eng = (ire_engine*)eng;
+    j->kind = kind; j->eng = (ire_engine*)eng; j->fit = fit;
     j->n = (int)get_i64(env, argv[2]); j->h = (int)get_i64(env, argv[3]); j->w = (int)get_i64(env, argv[4]);
     const size_t need = (size_t)(j->n > 0 ? j->n : 0) * (j->h > 0 ? j->h : 0) * (j->w > 0 ? j->w : 0) * 3;
     napi_value promise;
@@ -298,7 +303,7 @@ napi_value submit(napi_env env, napi_callback_info info, Job::Kind kind) {
         if (argc > 7) { const int64_t tmo = get_i64(env, argv[7]); if (tmo > 0) j->timeout_ms = (int)(tmo > 0x7fffffff ? 0x7fffffff : tmo); }
         j->deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(j->timeout_ms);
         int rc = waiters_start(env, j->eng) ? 0 : 4;
-        if (rc == 0) rc = g.submit(j->eng, (const uint8_t*)data, j->h, j->w, j->jpeg[0], j->has_scores ? j->scores.data() : nullptr, &j->queued);
+        if (rc == 0) rc = (fit ? g.submit_fit : g.submit)(j->eng, (const uint8_t*)data, j->h, j->w, j->jpeg[0], j->has_scores ? j->scores.data() : nullptr, &j->queued);
         if (rc != 0) {
             napi_value msg, err, code;
             napi_create_string_utf8(env, W && W->started ? g.last_error() : "internal: cannot create the completion function", NAPI_AUTO_LENGTH, &msg);
@@ -335,6 +340,9 @@ napi_value submit(napi_env env, napi_callback_info info, Job::Kind kind) {
 napi_value classify_async(napi_env e, napi_callback_info i) { return submit(e, i, Job::CLASSIFY); }
 napi_value restore_async(napi_env e, napi_callback_info i) { return submit(e, i, Job::RESTORE); }
 napi_value fuse_async(napi_env e, napi_callback_info i) { return submit(e, i, Job::FUSE); }
+// restoreFitAsync: restoreAsync's arguments for an image of ANY size (1..8192 per side); on a flagged engine the caller passes
+// pngBase64BytesFit(h, w) as the result size
+napi_value restore_fit_async(napi_env e, napi_callback_info i) { return submit(e, i, Job::RESTORE, true); }
 
 // preprocessPlan(width, height, orientation, maxDim) -> {width, height, resized}   (imagePreprocess.js:12-22,46-55; host arithmetic)
 napi_value preprocess_plan_sync(napi_env env, napi_callback_info info) {
@@ -433,6 +441,16 @@ napi_value png_base64_bytes_sync(napi_env env, napi_callback_info info) {
     return v;
 }
 
+// pngBase64BytesFit(h, w) -> the same for any h, w in 1..8192 (ire_submit_fit jobs)
+napi_value png_base64_bytes_fit_sync(napi_env env, napi_callback_info info) {
+    size_t argc = 2; napi_value argv[2];
+    napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+    if (argc < 2 || !g.png_base64_bytes_fit) { throw_err(env, "invalid arguments (or engine library not loaded: call init first)"); return nullptr; }
+    napi_value v;
+    napi_create_int64(env, (int64_t)g.png_base64_bytes_fit((int)get_i64(env, argv[0]), (int)get_i64(env, argv[1])), &v);
+    return v;
+}
+
 // init(libPath, weightsPath|null, deviceIndex, maxBatch, numStreams, flags) -> engine handle (throws with the engine's message)
 napi_value init_engine(napi_env env, napi_callback_info info) {
     size_t argc = 6; napi_value argv[6];
@@ -468,6 +486,8 @@ napi_value module_init(napi_env env, napi_value exports) {
         {"stats", nullptr, stats_sync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"maxBatchFor", nullptr, max_batch_for_sync, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"pngBase64Bytes", nullptr, png_base64_bytes_sync, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"restoreFitAsync", nullptr, restore_fit_async, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"pngBase64BytesFit", nullptr, png_base64_bytes_fit_sync, nullptr, nullptr, nullptr, napi_default, nullptr},
     };
     napi_define_properties(env, exports, sizeof(d) / sizeof(d[0]), d);
     return exports;

@@ -25,6 +25,7 @@ from datetime import datetime, timezone
 
 import numpy as np
 
+from . import _lib
 from .prompt_enhancer import KEYS, PromptEnhancerService
 
 BATCH_REQUEST_DELAY_MS = float(os.environ.get("RESTORATION_BATCH_DELAY_MS", "0") or 0)  # restorator.js:13
@@ -135,9 +136,14 @@ class EngineRestorer:
     def _encode(self, result):
         if self.result_codec == "jpeg":
             return encode_jpeg_base64(result)
-        if self.result_codec == "png-device" and result.shape[1] % 8 == 0:
-            return self.engine.encode_png_base64(result).decode("ascii")
-        return encode_png_base64(result)          # (png-device on a width that is not a multiple of 8: the host encoder)
+        if self.result_codec == "png-device":
+            return self.engine.encode_png_base64_fit(result).decode("ascii")      # any width: the device encoder
+        return encode_png_base64(result)
+
+    @staticmethod
+    def _reply(text):
+        return {"base64Image": text,
+                "metadata": {"providerRequestId": f"ire-{uuid.uuid4()}", "billedTokens": None, "estimatedCostUsd": 0}}
 
     def restore_image(self, prompt, images, user_context=None):
         if not images or len(images) > 3:
@@ -150,6 +156,14 @@ class EngineRestorer:
         shapes = {d[0].shape for d in decoded}
         if len(shapes) != 1:
             raise ValueError("invalid images: fusion views must have identical dimensions")
+        text_engine = bool(getattr(self.engine, "_flags", 0) & _lib.IRE_FLAG_RESULT_PNG_BASE64)      # ire_poll returns the text
+        if len(decoded) == 1:
+            # one image of any size is ONE job of the engine's batcher (ire_submit_fit): the engine pads on the device, classifies
+            # the image's own pixels in the same batch when analyze() did not, and hands back the h x w window -- on a flagged
+            # engine as the text of its PNG, which IS the result for every size
+            rgb, fmt, scores = decoded[0]
+            out, _, _ = self.engine.poll(self.engine.submit_fit(rgb, is_jpeg=(fmt == "jpeg"), scores=scores))
+            return self._reply(out.decode("ascii") if text_engine else self._encode(out))
         # every view goes to the engine's batcher (ire_submit) before the first ire_poll: the views of this call and the
         # single-image jobs of the other in-flight calls (restore_batch keeps 3 in flight) coalesce into engine batches
         jobs = []
@@ -159,28 +173,16 @@ class EngineRestorer:
                 # condition on the image's own scores (what analyze() reports), never on its replicate-padded copy's
                 scores = self.engine.classify(rgb, is_jpeg=(fmt == "jpeg"))[0][0]
             jobs.append((self.engine.submit(padded, is_jpeg=(fmt == "jpeg"), scores=scores), h, w))
-        text_engine = bool(getattr(self.engine, "_flags", 0) & 1)          # IRE_FLAG_RESULT_PNG_BASE64: ire_poll returns the text
-        if text_engine and len(jobs) == 1 and decoded[0][0].shape[0] % 8 == 0 and decoded[0][0].shape[1] % 8 == 0 and decoded[0][0].shape[0] >= 16:
-            text, _, _ = self.engine.poll(jobs[0][0])                     # no padding was cut off: the device's text IS the result
-            return {"base64Image": text.decode("ascii"),
-                    "metadata": {"providerRequestId": f"ire-{uuid.uuid4()}", "billedTokens": None, "estimatedCostUsd": 0}}
         restored = []
         for job, h, w in jobs:
             out, _, _ = self.engine.poll(job)
-            if text_engine:                                               # a flagged engine and an image that needs cropping: decode the stored PNG (a memcpy-speed inflate)
+            if text_engine:                                               # fusion needs the views' pixels: decode the stored PNG (a memcpy-speed inflate)
                 out = decode_image(base64.b64decode(out))[0]
             restored.append(np.ascontiguousarray(out[:h, :w]))
-        if len(restored) == 1:
-            result = restored[0]
-        else:
-            views = np.stack(restored, axis=0)
-            padded = np.stack([pad_to_multiple(v)[0] for v in views], axis=0)
-            fused, _ = self.engine.fuse(padded, noise_score=-1.0)
-            result = np.ascontiguousarray(fused[:views.shape[1], :views.shape[2]])
-        return {
-            "base64Image": self._encode(result),
-            "metadata": {"providerRequestId": f"ire-{uuid.uuid4()}", "billedTokens": None, "estimatedCostUsd": 0},
-        }
+        views = np.stack(restored, axis=0)
+        padded = np.stack([pad_to_multiple(v)[0] for v in views], axis=0)
+        fused, _ = self.engine.fuse(padded, noise_score=-1.0)
+        return self._reply(self._encode(np.ascontiguousarray(fused[:views.shape[1], :views.shape[2]])))
 
 
 class RestoratorService:

@@ -113,7 +113,7 @@ async def restore_batch(request: Request):
     import numpy as np
     import torch
     from ..prompt_enhancer import KEYS, PromptEnhancerService
-    from ..restorator import decode_image, encode_png_base64, pad_to_multiple
+    from ..restorator import decode_image
     try:
         payload = await request.json()
         bufs = [base64.b64decode(b) for b in payload["images"]]
@@ -131,9 +131,8 @@ async def restore_batch(request: Request):
     for i, b in enumerate(bufs):
         try:
             rgb, fmt = decode_image(b)
-            padded, hw = pad_to_multiple(rgb)
-            decoded[i] = (padded, hw, fmt, rgb)
-            groups.setdefault(padded.shape, []).append(i)
+            decoded[i] = (rgb, fmt)
+            groups.setdefault(rgb.shape, []).append(i)          # by the image's own shape: the engine takes any size
         except Exception as e:  # noqa: BLE001 -- the reference's envelope for a failed image (restorator.js:141-167)
             results[i] = {"success": False, "error": {"message": str(e), "code": "RESTORATION_FAILED", "type": "INVALID_INPUT"},
                           "timings": {"total_ms": 0}, "metadata": {"processingTime": 0, "failureStage": "CLASSIFICATION"}}
@@ -143,21 +142,13 @@ async def restore_batch(request: Request):
             t0 = time.time()
             try:
                 x = torch.from_numpy(np.stack([decoded[i][0] for i in chunk])).cuda()
-                jp = torch.tensor([1 if decoded[i][2] == "jpeg" else 0 for i in chunk], dtype=torch.uint8, device="cuda")
-                # condition on each image's own scores (unpadded pixels), as analyze() reports them
-                same = all(decoded[i][0].shape == decoded[i][3].shape for i in chunk)
-                if same:
-                    scores, _ = te.classify(x, jp)
-                else:
-                    scores = torch.cat([te.classify(torch.from_numpy(decoded[i][3][None]).cuda(), jp[k:k + 1])[0] for k, i in enumerate(chunk)])
+                jp = torch.tensor([1 if decoded[i][1] == "jpeg" else 0 for i in chunk], dtype=torch.uint8, device="cuda")
+                scores, _ = te.classify(x, jp)                  # each image's own (unpadded) pixels, as analyze() reports them
                 t1 = time.time()
-                restored = te.restore(x, scores, None)
-                # the result text on the device when the chunk's images need no crop (csrc/encode.hip through the extension):
-                # the D2H copy carries base64 characters, the host encodes nothing
-                texts = None
-                if same and restored.shape[2] % 8 == 0:
-                    texts = te.encode_png_base64(restored).cpu().numpy()
-                out = restored.cpu().numpy() if texts is None else None
+                # one engine call per chunk: pad, network and crop on the device; then the result text on the device for every
+                # size (csrc/encode.hip through the extension): the D2H copy carries base64 characters, the host encodes nothing
+                restored = te.restore_fit(x, scores, None)
+                texts = te.encode_png_base64_fit(restored).cpu().numpy()
                 sc = scores.cpu().numpy()
                 t2 = time.time()
             except EngineError as e:
@@ -166,11 +157,9 @@ async def restore_batch(request: Request):
                                   "timings": {}, "metadata": {"processingTime": 0, "failureStage": "AI_RESTORATION"}}
                 continue
             for k, i in enumerate(chunk):
-                h, w = decoded[i][1]
                 degradation = {key: float(sc[k, j]) for j, key in enumerate(KEYS)}
                 results[i] = {
-                    "success": True, "restoredImage": (texts[k].tobytes().decode("ascii") if texts is not None
-                                                       else encode_png_base64(np.ascontiguousarray(out[k, :h, :w]))),
+                    "success": True, "restoredImage": texts[k].tobytes().decode("ascii"),
                     "degradationAnalysis": degradation,
                     "enhancedPrompt": enhancer.enhance(degradation=degradation, user_prompt=payload.get("prompt"), options={"batchIndex": i, "batchSize": len(bufs)}),
                     "timings": {"classify_ms": int(1e3 * (t1 - t0)), "prompt_ms": 0, "restore_ms": int(1e3 * (t2 - t1)), "total_ms": int(1e3 * (t2 - t0))},

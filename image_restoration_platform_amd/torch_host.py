@@ -92,5 +92,13 @@ class TorchEngine:
         """[N,H,W,3] uint8 cuda -> [N, chars] uint8 cuda: the base64 text of each image's PNG file, written on the device."""
         return self._call(self._ext.encode_png_base64, rgb_u8)
 
+    def restore_fit(self, rgb_u8, scores=None, is_jpeg_u8=None):
+        """restore() for any H, W in 1..8192: pad, network and crop of the window on the device, in one call."""
+        return self._call(self._ext.restore_fit, rgb_u8, scores, is_jpeg_u8)
+
+    def encode_png_base64_fit(self, rgb_u8):
+        """encode_png_base64() for any width; rgb_u8 may be a [:, :H, :W] view of a larger tensor (encoded where it lies)."""
+        return self._call(self._ext.encode_png_base64_fit, rgb_u8)
+
     def restore_tiled(self, rgb_u8, nstrips, scores=None, is_jpeg_u8=None):
         return self._call(self._ext.restore_tiled, rgb_u8, int(nstrips), scores, is_jpeg_u8)

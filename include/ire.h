@@ -76,7 +76,7 @@ typedef struct ire_config {
 } ire_config;
 /* The batcher (ire_submit / ire_poll) delivers every result as the base64 TEXT of a PNG file of the restored image, encoded
  * on the device (ire_encode_png_base64_device below), instead of raw pixels: ire_poll's out_rgb then receives
- * ire_png_base64_bytes(h, w) ASCII characters -- the string restorator.js:108 puts on the wire, with no codec or base64 work
+ * ire_png_base64_bytes_fit(h, w) ASCII characters -- the string restorator.js:108 puts on the wire, with no codec or base64 work
  * left for the host. */
 #define IRE_FLAG_RESULT_PNG_BASE64 1u
 
@@ -158,14 +158,42 @@ int ire_encode_png_base64_device(ire_engine* e, const uint8_t* d_rgb, int n, int
                                  void* stream);
 int ire_encode_png_base64(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes);
 
+/* ---- any-size jobs (imagePreprocess.js:46-55 fits an upload inside 2048 px keeping its aspect ratio: a 3000x2000 photograph
+ * arrives as 2048x1365, never a multiple of 8) ----
+ * h, w in 1..8192.  The engine edge-replicates the image to H = max(16, ceil8(h)), W = max(16, ceil8(w)) on the device
+ * (pixel (y, x) = source (min(y, h-1), min(x, w-1))), restores that and returns the top-left h x w window:
+ * result == crop(ire_restore(edge_pad(x), scores), h, w).  scores == NULL => the classifier runs on the ORIGINAL h x w pixels
+ * (never the padded copy) inside the same call.  A shape ire_restore takes is not padded and gives ire_restore's bytes.
+ * Device staging: the first batch of a ragged shape allocates the padded staging (and, for text results, the encoder's scratch)
+ * for max_batch images of it, so later batches never allocate -- as long as that is <= 256 MB (max_batch * H * W * 3; at
+ * max_batch 8 up to about 3300 x 3300).  Above it the staging is sized for the batch at hand, and a later LARGER batch of the
+ * same shape grows it: one device synchronisation and reallocation inside that call. */
+int ire_restore_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, const double* scores,
+                    const uint8_t* is_jpeg, uint8_t* out_rgb /* n*h*w*3 */, ire_timings* t);
+int ire_restore_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, const double* d_scores,
+                           const uint8_t* d_is_jpeg, uint8_t* d_out_rgb, void* stream);
+/* The PNG + base64 encoder for any width.  ire_png_base64_bytes_fit: characters per image, pure host arithmetic (0 outside
+ * 1..8192); equal to ire_png_base64_bytes wherever that is not 0.  The device entry reads the top-left h x w window of n images
+ * whose rows lie row_pitch_bytes (>= 3*w) and whose first pixels lie image_pitch_bytes apart: a window of a larger tensor is
+ * encoded where it lies.  The number of stream operations per call does not depend on n. */
+size_t ire_png_base64_bytes_fit(int h, int w);
+int ire_encode_png_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes,
+                                     size_t image_pitch_bytes, uint8_t* d_chars, size_t stride_bytes, void* stream);
+int ire_encode_png_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes);
+
 /* ---- async batcher (restoreBatch's in-flight promises) ---------------------------------- */
 typedef struct ire_job ire_job;
 /* Queue one h x w image for restoration; jobs of equal shape are coalesced into batches of up
  * to max_batch.  The input is copied before return.  scores: the 7 doubles a previous ire_classify
  * of this image returned (the job is then not classified again), or NULL => classify inside. */
 int ire_submit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg, const double* scores, ire_job** job_out);
+/* ire_submit without the multiple-of-8 rule (h, w in 1..8192; the result is that of ire_restore_fit); jobs are coalesced by
+ * their exact (h, w), polled with ire_poll and released with ire_job_release.  With IRE_FLAG_RESULT_PNG_BASE64 ire_poll
+ * delivers ire_png_base64_bytes_fit(h, w) characters: the PNG of the h x w result. */
+int ire_submit_fit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg, const double* scores, ire_job** job_out);
 /* Wait up to timeout_ms (<0: forever) for the job; on IRE_OK out_rgb (h*w*3 pixel bytes, or with IRE_FLAG_RESULT_PNG_BASE64
- * ire_png_base64_bytes(h, w) characters), scores_out (7, may
+ * ire_png_base64_bytes_fit(h, w) characters -- for an ire_submit job the same number as ire_png_base64_bytes(h, w), which is 0
+ * for the ragged widths ire_submit_fit takes: size the buffer with the _fit form), scores_out (7, may
  * be NULL) and t (may be NULL) are filled and the job is released; any other status but
  * IRE_ERR_TIMEOUT releases it too.  IRE_ERR_TIMEOUT leaves the job pending and the handle valid:
  * poll again, or give the job up with ire_job_release.  One thread at a time per handle. */

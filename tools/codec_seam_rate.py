@@ -1,4 +1,5 @@
-"""The deployed seam with a REAL codec: FastAPI's POST /restore end to end at 1024x1024 -- JPEG upload decoded by
+"""The deployed seam with a REAL codec: FastAPI's POST /restore end to end at 1024x1024 (or the size given as
+the first argument: `1024`, or `WIDTHxHEIGHT` such as 2048x1365 for a photograph fitted inside 2048 px) -- JPEG upload decoded by
 PIL, classified and restored by the engine's batcher, the result encoded and base64'd as restorator.js:108 requires -- at 1 / 4 / 8
 concurrent requests, per result codec (IRE_RESULT_CODEC): host PNG (PIL, zlib 6), host JPEG q85 4:4:4 (imagePreprocess.js:57-64), and
 the device-side stored PNG + base64 (csrc/encode.hip).  Prints one JSON object; the codec's share of a request's wall time is measured
@@ -15,6 +16,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def _size(arg):
+    """'1024' -> (1024, 1024); 'WxH' -> (H, W)"""
+    if "x" in arg:
+        w, h = arg.lower().split("x")
+        return int(h), int(w)
+    return int(arg), int(arg)
+
+
 def one_codec(codec, size, requests, levels):
     os.environ["IRE_RESULT_CODEC"] = codec
     import numpy as np
@@ -22,7 +31,8 @@ def one_codec(codec, size, requests, levels):
     from fastapi.testclient import TestClient
     from image_restoration_platform_amd import restorator, synth
     from image_restoration_platform_amd.serving import app as appmod
-    imgs = synth.batch(8, size, size)
+    height, width = size
+    imgs = synth.batch(8, height, width)
     uploads = []
     for im in imgs:
         bio = io.BytesIO(); Image.fromarray(im).save(bio, format="JPEG", quality=85, subsampling=0)
@@ -64,23 +74,24 @@ def one_codec(codec, size, requests, levels):
         eng = appmod._state["engine"]
         t0 = time.perf_counter()
         for im in imgs[:4]:
-            eng.encode_png_base64(im)
+            eng.encode_png_base64_fit(im)
         t_enc = (time.perf_counter() - t0) / 4               # host pixels -> device -> text -> host (the flagged batcher skips even that)
     return {"codec": codec, "result_chars": out_chars, "decode_jpeg_ms": 1e3 * t_dec, "encode_ms": 1e3 * t_enc,
             "encode_host_equivalent_ms": 1e3 * t_enc_host, "rates": rows, "cores": len(os.sched_getaffinity(0))}
 
 
 def main():
-    size = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
+    arg = sys.argv[1] if len(sys.argv) > 1 else "1024"
+    size = _size(arg)
     if len(sys.argv) > 2:            # child: one codec per process (the codec is read at import, the engine is created once)
         print(json.dumps(one_codec(sys.argv[2], size, int(sys.argv[3]), [int(x) for x in sys.argv[4].split(",")])))
         return
     out = {}
     for codec, requests in (("png", 16), ("jpeg", 48), ("png-device", 48)):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), str(size), codec, str(requests), "1,4,8"], capture_output=True, text=True, timeout=900)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), arg, codec, str(requests), "1,4,8"], capture_output=True, text=True, timeout=900)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
         out[codec] = json.loads(line[-1]) if line else {"error": (r.stderr or r.stdout)[-600:]}
-    print(json.dumps({"workload": "FastAPI POST /restore @%dx%d, JPEG q85 upload, 1 GPU" % (size, size), "by_result_codec": out}))
+    print(json.dumps({"workload": "FastAPI POST /restore @%dx%d (width x height), JPEG q85 upload, 1 GPU" % (size[1], size[0]), "by_result_codec": out}))
 
 
 if __name__ == "__main__":

@@ -15,7 +15,7 @@
 //   * epilogue: conv_upq.hip's (8-pixel passes through a 2-KB patch, the pieces of the stage after next in front of the stores,
 //     counted wait), plain output tile; GroupNorm partials as conv_down's: one (sum, sumsq) per group per tile.
 // Weights: a.w = [n-block of 128][kc32][the 9 taps in phase order][c8][128 rows, permuted like conv_w4's][8] bf16
-// (engine.cpp::make_conv d_wdq).  Roofline: input staging (every output pixel reads four input pixels), then MFMA.
+// (weight_pack.hpp::pack_conv d_wdq).  Roofline: input staging (every output pixel reads four input pixels), then MFMA.
 #include "conv_mfma.hpp"
 #include "persist.hpp"
 

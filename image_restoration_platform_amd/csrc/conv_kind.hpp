@@ -1,0 +1,32 @@
+// conv_kind.hpp -- the seven convolution kinds and the integers of their v1 weight slabs; no HIP, no device code: shared by the
+// launch interface (conv_mfma.hpp) and by the host-only weight packer (weight_pack.hpp).
+#pragma once
+
+namespace ire {
+
+// The seven ways RestoreNet-v0 uses a convolution (DESIGN.md "RestoreNet-v0").
+enum ConvKind {
+    CONV_STEM,  // u8 RGB (padded to 8 ch) -> 32, 3x3, GroupNorm stats out
+    CONV_RB1,   // C->C 3x3, GN+FiLM+SiLU prologue, stats out
+    CONV_RB2,   // C->C 3x3, GN+FiLM+SiLU prologue, + residual, stats out
+    CONV_DOWN,  // C->2C 3x3 stride 2, stats out
+    CONV_UP,    // nearest x2 then 2C->C 3x3
+    CONV_FUSE,  // concat(up, skip) 2C->C 1x1, stats out
+    CONV_HEAD   // GN+SiLU prologue, 32->3 3x3, out = clamp(round(input + y)) u8
+};
+
+// output channels per workgroup
+inline int conv_nt(ConvKind kind, int cout) {
+    if (kind == CONV_STEM || kind == CONV_HEAD) return 32;
+    return cout >= 64 ? 64 : 32;
+}
+// MFMA k-steps per K-chunk (weight slab = nsteps*2*NT*16 B)
+inline int conv_nsteps(ConvKind kind) {
+    switch (kind) {
+        case CONV_STEM: return 5;   // 9 taps x 1 chunk, padded to 10 kk
+        case CONV_FUSE: return 2;   // 1 tap x 4 chunks
+        default: return 18;         // 9 taps x 4 chunks
+    }
+}
+
+}  // namespace ire

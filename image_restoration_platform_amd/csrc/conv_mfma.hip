@@ -346,17 +346,6 @@ void launch_one(const ConvArgs& a, hipStream_t stream) {
 }  // namespace
 
 int conv_tile_h(ConvKind kind) { return kind == CONV_DOWN ? 4 : 8; }
-int conv_nt(ConvKind kind, int cout) {
-    if (kind == CONV_STEM || kind == CONV_HEAD) return 32;
-    return cout >= 64 ? 64 : 32;
-}
-int conv_nsteps(ConvKind kind) {
-    switch (kind) {
-        case CONV_STEM: return 5;   // 9 taps x 1 chunk, padded to 10 kk
-        case CONV_FUSE: return 2;   // 1 tap x 4 chunks
-        default: return 18;         // 9 taps x 4 chunks
-    }
-}
 
 void conv_launch(ConvKind kind, const ConvArgs& a, hipStream_t stream) {
     const int nt = conv_nt(kind, a.cout);

@@ -1,6 +1,7 @@
 // conv_mfma.hpp -- launch interface of the MFMA convolution template (conv_mfma.hip).
 #pragma once
 #include "common.hpp"
+#include "conv_kind.hpp"
 
 // Cache policy of the activation stores (raw_buffer_store aux: 1 = sc0, 2 = nt, 16 = sc1).  IRE_ST_LINE: the line-coalesced
 // epilogues (a wave-instruction = whole 128-B lines) write THROUGH (sc1): the XCD's L2 keeps no dirty copy, so the kernel
@@ -43,17 +44,6 @@ inline int persistent_grid_cus() {
 }
 
 enum { PRO_NONE = 0, PRO_GN = 1, PRO_U8 = 2 };
-
-// The seven ways RestoreNet-v0 uses a convolution (DESIGN.md "RestoreNet-v0").
-enum ConvKind {
-    CONV_STEM,  // u8 RGB (padded to 8 ch) -> 32, 3x3, GroupNorm stats out
-    CONV_RB1,   // C->C 3x3, GN+FiLM+SiLU prologue, stats out
-    CONV_RB2,   // C->C 3x3, GN+FiLM+SiLU prologue, + residual, stats out
-    CONV_DOWN,  // C->2C 3x3 stride 2, stats out
-    CONV_UP,    // nearest x2 then 2C->C 3x3
-    CONV_FUSE,  // concat(up, skip) 2C->C 1x1, stats out
-    CONV_HEAD   // GN+SiLU prologue, 32->3 3x3, out = clamp(round(input + y)) u8
-};
 
 struct ConvArgs {
     const void* in0;             // bf16 NHWC activations (CONV_STEM: u8 RGB)
@@ -98,13 +88,11 @@ struct ConvArgs {
 };
 
 int conv_tile_h(ConvKind kind);       // output rows per workgroup tile (columns: 32)
-int conv_nt(ConvKind kind, int cout); // output channels per workgroup
-int conv_nsteps(ConvKind kind);       // MFMA k-steps per K-chunk (weight slab = nsteps*2*NT*16 B)
 void conv_launch(ConvKind kind, const ConvArgs& a, hipStream_t stream);
 
 // Persistent software-pipelined variant for CONV_RB1 / CONV_RB2 (conv_rb.hip): 16x32 tiles
 // (a.tiles_y must be ceil(Hout/16)), same ConvArgs; the weight slab rows are in permuted cout order (row n of a 32-row tile =
-// cout n with bits 2 and 3 swapped: engine.cpp::make_conv), so the epilogue stores straight from the accumulators.
+// cout n with bits 2 and 3 swapped: weight_pack.hpp::pack_conv), so the epilogue stores straight from the accumulators.
 constexpr int kRbTileH = 16;
 // fused_act: apply y = silu(x*A+B) while staging (a.ab); otherwise the input is already activated.
 void conv_rb_launch(bool resid, bool fused_act, const ConvArgs& a, hipStream_t stream);

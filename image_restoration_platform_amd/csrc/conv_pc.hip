@@ -831,7 +831,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
 }  // namespace
 
 // C = 32 / 64 ResBlock convs with the activation applied while staging (a.ab required), and the head: a.w = permuted-row slabs
-// [k-chunk][kk = tap*4 + c8][C rows][8] (engine.cpp::make_conv d_wp), 16x32 tiles, a.stats = partials [img][tile][8][2] (not for the
+// [k-chunk][kk = tap*4 + c8][C rows][8] (weight_pack.hpp::pack_conv d_wp), 16x32 tiles, a.stats = partials [img][tile][8][2] (not for the
 // head).  The producers' coefficient table holds 64 / 8 images (C = 32 / 64): conv_pc_fits() tells the engine whether every
 // workgroup of a launch stays within it.  (The C >= 128 form of this kernel -- 64-cout items, weight slabs streamed by the producers,
 // IRE_PC=7 -- lost to conv_w4 in round 2 and was superseded by conv_pk.hip in round 4: removed.)

@@ -20,7 +20,7 @@
 // One workgroup barrier per stage.  An input element is activated once per 128 couts (half of the producers' work per MFMA of
 // conv_pc's C >= 128 trial): ~3 000 producer ticks per 4 608-tick stage.  168 registers per wave (three per SIMD): 128 accumulators
 // + single-buffered fragments; the two consumer waves of a SIMD cover each other's fragment reads.
-// Same tiles, weight slabs (engine.cpp::make_conv d_w4), accumulation order, epilogue arithmetic and partials layout as conv_w4's
+// Same tiles, weight slabs (weight_pack.hpp::pack_conv d_w4), accumulation order, epilogue arithmetic and partials layout as conv_w4's
 // 8-wave fused form: bit-identical results (tests/test_restore_gpu.py holds the two schedules to equal bytes), row strips included.
 // Registers: no VGPR spill in the k-loop, the producers' transform or the epilogue (profiles/r05_experiments.md: the roles' prologues
 // are separate branches, per-lane addresses are rebuilt from the lane index, the accumulators are packed before the residual rows
@@ -679,7 +679,7 @@ bool conv_pk_fits(int C, int tiles_per_img, int nimg) {
     return true;
 }
 
-// a.w = conv_w4's slabs [n-block of 128 couts][kc16][tap][c8][128][8] (engine.cpp::make_conv d_w4), a.nkc = C / 16, a.nblocks = C / 128,
+// a.w = conv_w4's slabs [n-block of 128 couts][kc16][tap][c8][128][8] (weight_pack.hpp::pack_conv d_w4), a.nkc = C / 16, a.nblocks = C / 128,
 // a.ab required (fused activation), 16 x 32 tiles, a.stats = partials [img][tile][8][2].
 void conv_pk_launch(bool resid, const ConvArgs& a, hipStream_t stream) {
     const int C = a.cout;

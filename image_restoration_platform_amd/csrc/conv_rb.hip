@@ -324,7 +324,7 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
     // ---- epilogue building blocks ------------------------------------------------------------------------
     // ---- epilogue, straight from the accumulators -----------------------------------------------------------------
     // MFMA row rho of lane (r = pixel column, h) is accumulator i with rho = 8*(i>>2) + 4h + (i&3).  The weight slab is stored
-    // with its rows permuted (bits 2 and 3 of rho swapped, engine.cpp::make_conv), which makes accumulator i the cout
+    // with its rows permuted (bits 2 and 3 of rho swapped, weight_pack.hpp::pack_conv), which makes accumulator i the cout
     // j*32 + 16*(i>>3) + 8h + (i&7): for 16-cout group g = (j, p) a lane owns ONE whole 16-B chunk cc = j*4 + 2p + h of its
     // pixel in accumulators 8p..8p+7 -- packed and stored with no lane exchange (the natural row order needed one
     // v_permlane32_swap + two wait states per register).  GroupNorm partials are reduced over the 32 lanes of a half
@@ -405,7 +405,7 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
 #pragma unroll
         for (int pp = 0; pp < 2; ++pp) {
             const int g = j * 2 + pp;
-            // permuted slab rows (engine.cpp::make_conv): accumulators 8pp .. 8pp+7 of lane-half h are the 8 CONTIGUOUS couts
+            // permuted slab rows (weight_pack.hpp::pack_conv): accumulators 8pp .. 8pp+7 of lane-half h are the 8 CONTIGUOUS couts
             // j*32 + 16pp + 8h + (0..7) = 16-B chunk cc = j*4 + 2pp + h of the pixel: pack and store, no lane exchange
             float sA = 0.f, qA = 0.f, sB = 0.f, qB = 0.f;
 #pragma unroll

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(ST_THREADS) void conv_stem_kernel(ConvArgs a) {
     __shared__ float red[2][8][8][2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
 
-    // A fragments (weights): [ky][h][32 permuted rows][8] bf16, engine.cpp::make_conv (d_wstem)
+    // A fragments (weights): [ky][h][32 permuted rows][8] bf16, weight_pack.hpp::pack_conv (d_wstem)
     const u32x4_t* wf = reinterpret_cast<const u32x4_t*>(a.w);
     const bf16x8_t w0 = __builtin_bit_cast(bf16x8_t, wf[(0 * 2 + h) * 32 + r]);
     const bf16x8_t w1 = __builtin_bit_cast(bf16x8_t, wf[(1 * 2 + h) * 32 + r]);
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(ST_THREADS) void conv_stem_kernel(ConvArgs a) {
 }  // namespace
 
 // a.in0 = u8 [nimg][in_rows][Win][3] (rows iy_lo .. iy_lo + iy_span readable, the rest zero), a.out = bf16 [nimg][Hout][Wout][32],
-// a.w = A fragments [3][2][32][8] bf16 (engine.cpp::make_conv), a.bias[32], a.stats partials [img][tile][8][2]; 16x32 tiles
+// a.w = A fragments [3][2][32][8] bf16 (weight_pack.hpp::pack_conv), a.bias[32], a.stats partials [img][tile][8][2]; 16x32 tiles
 void conv_stem_launch(const ConvArgs& a, hipStream_t stream) {
     if (a.cout != 32 || a.Hout != a.Hin || a.Wout != a.Win || !a.stats) fail(IRE_ERR_INTERNAL, "internal: conv_stem shape");
     const int items = a.tiles_x * a.tiles_y * a.nimg;

@@ -5,7 +5,7 @@
 // low-resolution pixels: rows Y-1+a .. Y+a, columns X-1+b .. X+b.  The taps that fall on the same low-resolution pixel can be
 // summed ahead of time:   a = 0: row Y-1 <- ky 0,  row Y <- ky 1 + ky 2;     a = 1: row Y <- ky 0 + ky 1,  row Y+1 <- ky 2
 // (same for the columns), so each of the four output parities (a, b) is a 2x2 convolution with its own pre-summed weights
-// (engine.cpp::make_conv builds them; zero padding at the image border carries over exactly because a summed pair never
+// (weight_pack.hpp::pack_conv builds them; zero padding at the image border carries over exactly because a summed pair never
 // straddles the border).  K per output drops from 9*Cin to 4*Cin: 2.25x fewer MFMAs for the same result, the upsampled
 // tensor never exists, and one staged low-resolution tile serves 4x as many output pixels.
 //
@@ -18,7 +18,7 @@
 //
 // FUSED form (NKS > 0): RestoreNet-v0 follows every `up` with the 1x1 `fuse` over concat(up, skip) and nothing non-linear
 // sits between them, so   fuse(concat(up(x), skip)) = (Wf_up . Wup) * x_up  +  Wf_skip . skip  +  (Wf_up . b_up + b_f):
-// engine.cpp::make_up_fused composes the two weight tensors once per load (fp64, then the sub-pixel pre-sums, then bf16) and
+// weight_pack.hpp::pack_up_fused composes the two weight tensors once per load (fp64, then the sub-pixel pre-sums, then bf16) and
 // this kernel adds the skip term in its epilogue: the accumulator tile of a (parity, row) is D[cout][pixel], the skip pixels
 // come straight from HBM in the MFMA B layout (lane = pixel, 8 channels = 16 B) and the 32 x C skip weights of the item's
 // cout block wait in LDS (LDS-DMA one stage ahead).  The `up` tensor is never written or read (2 x 2 B x C per output pixel

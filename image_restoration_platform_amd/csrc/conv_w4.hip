@@ -77,7 +77,7 @@ template <int N> struct W4Regs { u32x4_t v[N]; unsigned ok; };   // native 128-b
 // FP8 (IRE_PRECISION_FP8, cfg 4): both MFMA operands are OCP e4m3 (v_mfma_f32_32x32x16_fp8_fp8): an 8-channel operand chunk
 // is 8 bytes instead of 16 in the LDS tile and in the weight slab (ds_read_b64 fragments, half the LDS bytes per MFMA).
 // Activations are quantised while staging -- after GroupNorm+FiLM+SiLU, scaled by kFp8ActScale so that small values stay
-// normal numbers, clamped to the e4m3 range -- weights offline with one scale per output channel (engine.cpp::make_conv);
+// normal numbers, clamped to the e4m3 range -- weights offline with one scale per output channel (weight_pack.hpp::pack_conv);
 // the epilogue multiplies each accumulator by its channel's (weight scale / kFp8ActScale).  HBM tensors stay bf16.
 constexpr float kFp8ActScale = 16.0f;
 template <int NT, int WAVES, bool FP8 = false>
@@ -487,7 +487,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
         stamp(2);
     };
     // ---- epilogue, straight from the accumulators (no LDS transpose, no workgroup barrier but the one for the GroupNorm
-    // partials).  The slab rows are permuted (bits 2 and 3 of the MFMA row swapped, engine.cpp::make_conv), so accumulator i
+    // partials).  The slab rows are permuted (bits 2 and 3 of the MFMA row swapped, weight_pack.hpp::pack_conv), so accumulator i
     // of lane (r = pixel column, h) is cout j*32 + 16*(i>>3) + 8h + (i&7): 8 contiguous couts per half tile = one 16-B
     // store per lane, a pixel's two lanes 32 contiguous bytes, no lane exchange.
     // It only READS acc: the item loop zeroes the accumulators unconditionally (a conditional redefinition of all 256
@@ -506,7 +506,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
             const int j = g >> 1, pp = g & 1;
             __builtin_amdgcn_sched_barrier(0);          // keep only one group's accumulator copies live
             if (g + RD - 1 < NTL * 2) load_resid(g + RD - 1, rv[(g + RD - 1) % RD]);
-            // permuted slab rows (engine.cpp::make_conv): accumulators 8pp .. 8pp+7 are the 8 contiguous couts j*32 + 16pp + 8h + (0..7)
+            // permuted slab rows (weight_pack.hpp::pack_conv): accumulators 8pp .. 8pp+7 are the 8 contiguous couts j*32 + 16pp + 8h + (0..7)
             float4 b0 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = b0;     // BIAS_INIT: the accumulators started at the bias
             if constexpr (!BIAS_INIT) {
                 b0 = *reinterpret_cast<const float4*>(bias_lds + cout0 + j * 32 + 16 * pp + 8 * h_e);

@@ -13,6 +13,7 @@
 
 #include "gn.hpp"
 #include "strips.hpp"
+#include "weight_pack.hpp"
 #include "grey_tables.inc"
 
 namespace ire {
@@ -25,34 +26,6 @@ const int kFilmDim = 960;
 
 inline double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-inline unsigned short f32_to_bf16(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    u = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;  // weights are finite: no NaN handling needed
-    return (unsigned short)u;
-}
-
-// fp32 -> OCP e4m3fn (1-4-3, bias 7, no infinities, max 448), round to nearest even, saturating.  Host-side, for weights.
-inline unsigned char f32_to_e4m3(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    const unsigned char sign = (u >> 31) ? 0x80 : 0;
-    float a = std::fabs(f);
-    if (!(a == a)) return sign | 0x7f;
-    if (a >= 448.0f) return sign | 0x7e;
-    if (a < 0.0009765625f) return sign;                         // < 2^-10 = half the smallest subnormal (2^-9): rounds to zero
-    int e;
-    std::frexp(a, &e);                                          // a = m * 2^e, m in [0.5, 1)
-    int E = e - 1;                                              // a = 1.xxx * 2^E
-    if (E < -6) E = -6;                                         // subnormal range: fixed exponent, step 2^-9
-    const float step = std::ldexp(1.0f, E - 3);
-    float q = std::nearbyint(a / step);                         // default rounding mode: to nearest even
-    if (E == -6 && q < 8.0f) return sign | (unsigned char)q;    // subnormal: mantissa only
-    if (q >= 16.0f) { q = 8.0f; E += 1; }
-    if (E > 8) return sign | 0x7e;
-    return sign | (unsigned char)(((E + 7) << 3) | ((int)q - 8));
 }
 
 }  // namespace
@@ -217,430 +190,77 @@ void Engine::load_weights_file(const char* path) {
     load_weights(blob.data(), blob.size());
 }
 
-ConvW Engine::make_conv(ConvKind kind, const std::string& wname, const std::string& bname, int cin, int cout) {
-    auto wi = host_w_.find(wname), bi = host_w_.find(bname);
-    if (wi == host_w_.end() || bi == host_w_.end()) fail(IRE_ERR_INVALID_INPUT, "invalid weight file: missing " + wname);
-    const auto& dims = wi->second.first;
-    const int taps = (kind == CONV_FUSE) ? 1 : 9, ks = (kind == CONV_FUSE) ? 1 : 3;
-    if (dims.size() != 4 || dims[0] != cout || dims[1] != cin || dims[2] != ks || dims[3] != ks ||
-        (int)bi->second.second.size() != cout)
-        fail(IRE_ERR_INVALID_INPUT, "invalid weight file: shape of " + wname);
-    const float* W = wi->second.second.data();
+// one packed array -> device (null for an array the packer did not produce: exec_conv picks kernels by that)
+template <class T>
+T* Engine::upload(const std::vector<T>& v) {
+    if (v.empty()) return nullptr;
+    T* d = (T*)dalloc(v.size() * sizeof(T));
+    net_.allocs.push_back(d);
+    IRE_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return d;
+}
+
+ConvW Engine::upload_conv(const PackedConv& p) {
     ConvW c;
-    c.kind = kind; c.cin = cin; c.cout = cout;
-    const int kc8 = (kind == CONV_STEM) ? 1 : 4;
-    const int cin_pad = (kind == CONV_STEM) ? 8 : cin;
-    const int cout_pad = (kind == CONV_HEAD) ? 32 : cout;
-    c.nt = conv_nt(kind, cout_pad);
-    if (cin_pad % (kc8 * 8) || cout_pad % c.nt) fail(IRE_ERR_INTERNAL, "internal: conv channel counts");
-    c.nkc = cin_pad / (kc8 * 8);
-    c.nblocks = cout_pad / c.nt;
-    if (kind == CONV_FUSE) { c.cin0 = cin / 2; c.cin1 = cin / 2; c.kc_split = c.nkc / 2; }
-    else { c.cin0 = cin_pad; c.cin1 = 0; c.kc_split = c.nkc; }
-    const int nsteps = conv_nsteps(kind), nkk = nsteps * 2;
-    // slab layout [nblock][kchunk][kk = tap*kc8 + c8][n][e]; element = W[cout][cin = kc*kc8*8 + c8*8 + e][tap]
-    std::vector<unsigned short> arr((size_t)c.nblocks * c.nkc * nkk * c.nt * 8, 0);
-    for (int nb = 0; nb < c.nblocks; ++nb)
-        for (int kc = 0; kc < c.nkc; ++kc)
-            for (int kk = 0; kk < taps * kc8; ++kk) {
-                const int tap = kk / kc8, c8 = kk % kc8;
-                for (int n = 0; n < c.nt; ++n) {
-                    const int co = nb * c.nt + n;
-                    if (co >= cout) continue;
-                    for (int e = 0; e < 8; ++e) {
-                        const int ci = kc * kc8 * 8 + c8 * 8 + e;
-                        if (ci >= cin) continue;
-                        const float v = W[((size_t)co * cin + ci) * taps + tap];
-                        arr[((((size_t)nb * c.nkc + kc) * nkk + kk) * c.nt + n) * 8 + e] = f32_to_bf16(v);
-                    }
-                }
-            }
-    c.d_w = (unsigned short*)dalloc(arr.size() * 2);
-    net_.allocs.push_back(c.d_w);
-    IRE_HIP(hipMemcpy(c.d_w, arr.data(), arr.size() * 2, hipMemcpyHostToDevice));
-    // conv_rb.hip / conv_w4.hip (direct epilogue): slab row n of a 32-row MFMA tile carries cout perm(n) = n with bits 2 and 3
-    // swapped, so that the 16 accumulators of a lane-half are two runs of 8 CONTIGUOUS couts (one 16-B store each, no
-    // v_permlane32_swap pairing).  The v1 kernel keeps the natural order (c.d_w).
-    auto perm = [](int n) { return (n & ~12) | ((n & 4) << 1) | ((n & 8) >> 1); };
-    if (kind == CONV_RB1 || kind == CONV_RB2 || kind == CONV_UP || kind == CONV_HEAD) {
-        std::vector<unsigned short> arrp(arr.size(), 0);
-        const size_t rows = arr.size() / ((size_t)c.nt * 8);
-        for (size_t rr = 0; rr < rows; ++rr)
-            for (int n = 0; n < c.nt; ++n)
-                std::memcpy(&arrp[(rr * c.nt + n) * 8], &arr[(rr * c.nt + perm(n)) * 8], 16);
-        c.d_wp = (unsigned short*)dalloc(arrp.size() * 2);
-        net_.allocs.push_back(c.d_wp);
-        IRE_HIP(hipMemcpy(c.d_wp, arrp.data(), arrp.size() * 2, hipMemcpyHostToDevice));
-    }
-    if (kind == CONV_STEM && cin == 3 && cout == 32) {
-        // conv_stem.hip: k-step ky is one tile row; lane (row rho, half h) holds W[perm(rho)] at k = 16 ky + 8 h + e, i.e. kx = 2 h + (e >> 2),
-        // c = e & 3 -- zero for the pad positions kx = 3 and c = 3 (the LDS tile holds a pixel as four bf16: R, G, B, 0)
-        std::vector<unsigned short> arrs(3 * 2 * 32 * 8, 0);
-        for (int ky = 0; ky < 3; ++ky)
-            for (int hh = 0; hh < 2; ++hh)
-                for (int rho = 0; rho < 32; ++rho)
-                    for (int e = 0; e < 8; ++e) {
-                        const int kx = 2 * hh + (e >> 2), ch = e & 3;
-                        if (kx >= 3 || ch >= 3) continue;
-                        arrs[(((size_t)ky * 2 + hh) * 32 + rho) * 8 + e] = f32_to_bf16(W[((size_t)perm(rho) * cin + ch) * 9 + ky * 3 + kx]);
-                    }
-        c.d_wstem = (unsigned short*)dalloc(arrs.size() * 2);
-        net_.allocs.push_back(c.d_wstem);
-        IRE_HIP(hipMemcpy(c.d_wstem, arrs.data(), arrs.size() * 2, hipMemcpyHostToDevice));
-    }
-    if (kind == CONV_DOWN && cin % 32 == 0 && cout % 64 == 0) {
-        // conv_down.hip: the stride-2 conv as a unit-stride conv over the four pixel phases P_ab[Y][X] = in[2Y+a][2X+b]:
-        // phase (a, b) carries the taps ky in (a ? {0, 2} : {1}) x kx in (b ? {0, 2} : {1}), in that order
-        const int nbd = cout / 64, nkd = cin / 32;
-        std::vector<unsigned short> arrd((size_t)nbd * nkd * 9 * 4 * 64 * 8, 0);
-        size_t pos = 0;
-        for (int nb = 0; nb < nbd; ++nb)
-            for (int kc = 0; kc < nkd; ++kc)
-                for (int ph = 0; ph < 4; ++ph) {
-                    const int pa = ph >> 1, pb = ph & 1, nty = pa ? 2 : 1, ntx = pb ? 2 : 1;
-                    for (int t = 0; t < nty * ntx; ++t) {
-                        const int ty = t / ntx, tx = t % ntx;
-                        const int ky = pa ? (ty ? 2 : 0) : 1, kx = pb ? (tx ? 2 : 0) : 1;
-                        for (int c8 = 0; c8 < 4; ++c8)
-                            for (int n = 0; n < 64; ++n)
-                                for (int e = 0; e < 8; ++e) {
-                                    const int co = nb * 64 + (n & 32) + perm(n & 31), ci = kc * 32 + c8 * 8 + e;
-                                    arrd[pos++] = f32_to_bf16(W[((size_t)co * cin + ci) * 9 + ky * 3 + kx]);
-                                }
-                    }
-                }
-        c.d_wd = (unsigned short*)dalloc(arrd.size() * 2);
-        net_.allocs.push_back(c.d_wd);
-        IRE_HIP(hipMemcpy(c.d_wd, arrd.data(), arrd.size() * 2, hipMemcpyHostToDevice));
-        if (cout % 128 == 0) {
-            // conv_dnq.hip: the same taps in the same phase order as 128-cout slabs: [n-block of 128][kc32][9 taps][c8][128 permuted rows][8]
-            std::vector<unsigned short> arrq((size_t)(cout / 128) * nkd * 9 * 4 * 128 * 8, 0);
-            size_t qpos = 0;
-            for (int nb = 0; nb < cout / 128; ++nb)
-                for (int kc = 0; kc < nkd; ++kc)
-                    for (int ph = 0; ph < 4; ++ph) {
-                        const int pa = ph >> 1, pb = ph & 1, nty = pa ? 2 : 1, ntx = pb ? 2 : 1;
-                        for (int t = 0; t < nty * ntx; ++t) {
-                            const int ty = t / ntx, tx = t % ntx;
-                            const int ky = pa ? (ty ? 2 : 0) : 1, kx = pb ? (tx ? 2 : 0) : 1;
-                            for (int c8 = 0; c8 < 4; ++c8)
-                                for (int n = 0; n < 128; ++n)
-                                    for (int e = 0; e < 8; ++e) {
-                                        const int co = nb * 128 + perm(n), ci = kc * 32 + c8 * 8 + e;
-                                        arrq[qpos++] = f32_to_bf16(W[((size_t)co * cin + ci) * 9 + ky * 3 + kx]);
-                                    }
-                        }
-                    }
-            if (!d_zero_) { d_zero_ = dalloc(256); IRE_HIP(hipMemset(d_zero_, 0, 256)); }
-            c.d_wdq = (unsigned short*)dalloc(arrq.size() * 2);
-            net_.allocs.push_back(c.d_wdq);
-            IRE_HIP(hipMemcpy(c.d_wdq, arrq.data(), arrq.size() * 2, hipMemcpyHostToDevice));
-        }
-    }
-    if (kind == CONV_UP && cin % 64 == 0 && cout % 32 == 0) {
-        // conv_up.hip: nearest x2 -> 3x3 == four 2x2 convolutions on the low-res grid, one per output parity (pa, pb); the taps that
-        // land on the same low-res pixel are summed here (fp32), then rounded to bf16:
-        //   pa = 0: window row 0 <- ky 0, row 1 <- ky 1 + ky 2;   pa = 1: row 0 <- ky 0 + ky 1, row 1 <- ky 2   (columns alike)
-        const int nbu = cout / 32, nku = cin / 32;
-        std::vector<unsigned short> arru((size_t)nbu * nku * 4 * 16 * 32 * 8, 0);
-        auto lo_of = [](int par, int d) { return par == 0 ? (d == 0 ? 0 : 1) : (d == 0 ? 0 : 2); };
-        auto hi_of = [](int par, int d) { return par == 0 ? (d == 0 ? 0 : 2) : (d == 0 ? 1 : 2); };
-        for (int nb = 0; nb < nbu; ++nb)
-            for (int kc = 0; kc < nku; ++kc)
-                for (int par = 0; par < 4; ++par)
-                    for (int kk = 0; kk < 16; ++kk) {
-                        const int pa = par >> 1, pb = par & 1, tap4 = kk >> 2, c8 = kk & 3, dy = tap4 >> 1, dx = tap4 & 1;
-                        for (int n = 0; n < 32; ++n)
-                            for (int e = 0; e < 8; ++e) {
-                                const int co = nb * 32 + perm(n), ci = kc * 32 + c8 * 8 + e;
-                                float sum = 0.f;
-                                for (int ky = lo_of(pa, dy); ky <= hi_of(pa, dy); ++ky)
-                                    for (int kx = lo_of(pb, dx); kx <= hi_of(pb, dx); ++kx) sum += W[((size_t)co * cin + ci) * 9 + ky * 3 + kx];
-                                arru[(((((size_t)nb * nku + kc) * 4 + par) * 16 + kk) * 32 + n) * 8 + e] = f32_to_bf16(sum);
-                            }
-                    }
-        c.d_wu = (unsigned short*)dalloc(arru.size() * 2);
-        net_.allocs.push_back(c.d_wu);
-        IRE_HIP(hipMemcpy(c.d_wu, arru.data(), arru.size() * 2, hipMemcpyHostToDevice));
-    }
-    if ((kind == CONV_RB1 || kind == CONV_RB2) && cout >= 128 && cin % 16 == 0 && cout % 128 == 0) {
-        // conv_w4.hip slabs: [nblock (128 couts)][kc16][kk = tap*2 + c8][128][8]
-        const int nb4 = cout / 128, nk4 = cin / 16;
-        std::vector<unsigned short> arr4((size_t)nb4 * nk4 * 18 * 128 * 8, 0);
-        for (int nb = 0; nb < nb4; ++nb)
-            for (int kc = 0; kc < nk4; ++kc)
-                for (int kk = 0; kk < 18; ++kk) {
-                    const int tap = kk >> 1, c8 = kk & 1;
-                    for (int n = 0; n < 128; ++n)
-                        for (int e = 0; e < 8; ++e) {
-                            const int co = nb * 128 + perm(n), ci = kc * 16 + c8 * 8 + e;       // permuted rows, as c.d_wp
-                            arr4[((((size_t)nb * nk4 + kc) * 18 + kk) * 128 + n) * 8 + e] = f32_to_bf16(W[((size_t)co * cin + ci) * 9 + tap]);
-                        }
-                }
-        c.d_w4 = (unsigned short*)dalloc(arr4.size() * 2);
-        net_.allocs.push_back(c.d_w4);
-        IRE_HIP(hipMemcpy(c.d_w4, arr4.data(), arr4.size() * 2, hipMemcpyHostToDevice));
-        {   // the same slabs in 64-cout blocks: [nblock (64 couts)][kc16][kk][64][8]
-            std::vector<unsigned short> arrh(arr4.size(), 0);
-            for (int nb = 0; nb < cout / 64; ++nb)
-                for (int kc = 0; kc < nk4; ++kc)
-                    for (int kk = 0; kk < 18; ++kk) {
-                        const int tap = kk >> 1, c8 = kk & 1;
-                        for (int n = 0; n < 64; ++n)
-                            for (int e = 0; e < 8; ++e) {
-                                const int co = nb * 64 + perm(n), ci = kc * 16 + c8 * 8 + e;
-                                arrh[((((size_t)nb * nk4 + kc) * 18 + kk) * 64 + n) * 8 + e] = f32_to_bf16(W[((size_t)co * cin + ci) * 9 + tap]);
-                            }
-                    }
-            c.d_w4h = (unsigned short*)dalloc(arrh.size() * 2);
-            net_.allocs.push_back(c.d_w4h);
-            IRE_HIP(hipMemcpy(c.d_w4h, arrh.data(), arrh.size() * 2, hipMemcpyHostToDevice));
-        }
-        if (precision_ == IRE_PRECISION_FP8) {
-            // the same slabs as OCP e4m3 with one scale per OUTPUT channel: w_q = e4m3(w / s_w[co]), s_w[co] = max|w[co]| / 448
-            // (the whole e4m3 range per channel); activations are scaled by kActScale = 16 while staging (conv_w4.hip), so the
-            // kernel's accumulator times oscale = s_w / 16 is the conv output and its accumulators start at bias / oscale
-            const float kActScale = 16.0f;
-            std::vector<float> sw(cout), osc(cout), b8(cout);
-            for (int co = 0; co < cout; ++co) {
-                float m = 0.f;
-                for (size_t k = 0; k < (size_t)cin * 9; ++k) m = std::max(m, std::fabs(W[(size_t)co * cin * 9 + k]));
-                sw[co] = m > 0.f ? m / 448.0f : 1.0f;
-                osc[co] = sw[co] / kActScale;
-                b8[co] = bi->second.second[co] / osc[co];
-            }
-            std::vector<unsigned char> arr8((size_t)nb4 * nk4 * 18 * 128 * 8, 0);
-            for (int nb = 0; nb < nb4; ++nb)
-                for (int kc = 0; kc < nk4; ++kc)
-                    for (int kk = 0; kk < 18; ++kk) {
-                        const int tap = kk >> 1, c8 = kk & 1;
-                        for (int n = 0; n < 128; ++n)
-                            for (int e = 0; e < 8; ++e) {
-                                const int co = nb * 128 + perm(n), ci = kc * 16 + c8 * 8 + e;
-                                arr8[((((size_t)nb * nk4 + kc) * 18 + kk) * 128 + n) * 8 + e] = f32_to_e4m3(W[((size_t)co * cin + ci) * 9 + tap] / sw[co]);
-                            }
-                    }
-            // the K = 64 form (conv_f8.hip): 32-channel stages, [tap][16-channel half][128 rows][16 bytes]
-            if (cin % 32 == 0) {
-                const int nk8 = cin / 32;
-                std::vector<unsigned char> arrx((size_t)nb4 * nk8 * 9 * 2 * 128 * 16, 0);
-                for (int nb = 0; nb < nb4; ++nb)
-                    for (int kc = 0; kc < nk8; ++kc)
-                        for (int tap = 0; tap < 9; ++tap)
-                            for (int hf = 0; hf < 2; ++hf)
-                                for (int n = 0; n < 128; ++n)
-                                    for (int e = 0; e < 16; ++e) {
-                                        const int co = nb * 128 + perm(n), ci = kc * 32 + hf * 16 + e;
-                                        arrx[(((((size_t)nb * nk8 + kc) * 9 + tap) * 2 + hf) * 128 + n) * 16 + e] = f32_to_e4m3(W[((size_t)co * cin + ci) * 9 + tap] / sw[co]);
-                                    }
-                c.d_w8x = (unsigned char*)dalloc(arrx.size());
-                net_.allocs.push_back(c.d_w8x);
-                IRE_HIP(hipMemcpy(c.d_w8x, arrx.data(), arrx.size(), hipMemcpyHostToDevice));
-            }
-            c.d_w8 = (unsigned char*)dalloc(arr8.size());
-            c.d_oscale = (float*)dalloc(cout * 4);
-            c.d_bias8 = (float*)dalloc(cout * 4);
-            net_.allocs.push_back(c.d_w8); net_.allocs.push_back(c.d_oscale); net_.allocs.push_back(c.d_bias8);
-            IRE_HIP(hipMemcpy(c.d_w8, arr8.data(), arr8.size(), hipMemcpyHostToDevice));
-            IRE_HIP(hipMemcpy(c.d_oscale, osc.data(), cout * 4, hipMemcpyHostToDevice));
-            IRE_HIP(hipMemcpy(c.d_bias8, b8.data(), cout * 4, hipMemcpyHostToDevice));
-        }
-    }
-    std::vector<float> bias(cout_pad, 0.f);
-    std::memcpy(bias.data(), bi->second.second.data(), sizeof(float) * cout);
-    c.d_bias = (float*)dalloc(bias.size() * 4);
-    net_.allocs.push_back(c.d_bias);
-    IRE_HIP(hipMemcpy(c.d_bias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
+    c.kind = p.kind; c.cin = p.cin; c.cout = p.cout; c.cin0 = p.cin0; c.cin1 = p.cin1;
+    c.nt = p.nt; c.nblocks = p.nblocks; c.nkc = p.nkc; c.kc_split = p.kc_split;
+    c.d_w = upload(p.w); c.d_wp = upload(p.wp); c.d_w4 = upload(p.w4); c.d_w4h = upload(p.w4h); c.d_wstem = upload(p.wstem);
+    c.d_wd = upload(p.wd); c.d_wu = upload(p.wu); c.d_wuf = upload(p.wuf); c.d_wdq = upload(p.wdq); c.d_wuq = upload(p.wuq);
+    c.d_wsq = upload(p.wsq); c.d_wsk = upload(p.wsk); c.d_bias_uf = upload(p.bias_uf); c.d_w8x = upload(p.w8x); c.d_w8 = upload(p.w8);
+    c.d_oscale = upload(p.oscale); c.d_bias8 = upload(p.bias8); c.d_bias = upload(p.bias);
     return c;
 }
 
-// `up` (nearest x2 -> 3x3, 2C -> C) followed by `fuse` (1x1 over concat(up, skip), 2C -> C) with nothing non-linear between
-// them is ONE convolution plus a 1x1 over the skip tensor:
-//   fuse(concat(up(x), skip)) = (Wf_up . Wup) * x_up  +  Wf_skip . skip  +  (Wf_up . b_up + b_f),   Wf = [Wf_up | Wf_skip].
-// The composition is done once here in double, then the sub-pixel pre-sums of conv_up.hip, then ONE rounding to bf16.
-void Engine::make_up_fused(ConvW& up, const std::string& sl) {
-    const int C = up.cout, cin = up.cin;
-    if (up.kind != CONV_UP || up.d_wu == nullptr || (C != 32 && C != 64 && C != 128)) return;
-    auto wu = host_w_.find("up" + sl + ".w"), bu = host_w_.find("up" + sl + ".b");
-    auto wf = host_w_.find("fuse" + sl + ".w"), bf = host_w_.find("fuse" + sl + ".b");
-    if (wu == host_w_.end() || bu == host_w_.end() || wf == host_w_.end() || bf == host_w_.end()) return;
-    const float* Wu = wu->second.second.data();        // [C][cin][3][3]
-    const float* Wf = wf->second.second.data();        // [C][2C]
-    if ((int)wf->second.second.size() != C * 2 * C) return;
-    std::vector<double> Wc((size_t)C * cin * 9, 0.0);
-    for (int co = 0; co < C; ++co)
-        for (int m = 0; m < C; ++m) {
-            const double f = Wf[(size_t)co * 2 * C + m];
-            const float* src = Wu + (size_t)m * cin * 9;
-            double* dst = Wc.data() + (size_t)co * cin * 9;
-            for (int k = 0; k < cin * 9; ++k) dst[k] += f * (double)src[k];
-        }
-    std::vector<float> bc(C);
-    for (int co = 0; co < C; ++co) {
-        double b = bf->second.second[co];
-        for (int m = 0; m < C; ++m) b += (double)Wf[(size_t)co * 2 * C + m] * (double)bu->second.second[m];
-        bc[co] = (float)b;
-    }
-    auto perm = [](int n) { return (n & ~12) | ((n & 4) << 1) | ((n & 8) >> 1); };
-    const int nbu = C / 32, nku = cin / 32;
-    std::vector<unsigned short> arru((size_t)nbu * nku * 4 * 16 * 32 * 8, 0);
-    auto lo_of = [](int par, int d) { return par == 0 ? (d == 0 ? 0 : 1) : (d == 0 ? 0 : 2); };
-    auto hi_of = [](int par, int d) { return par == 0 ? (d == 0 ? 0 : 2) : (d == 0 ? 1 : 2); };
-    for (int nb = 0; nb < nbu; ++nb)
-        for (int kc = 0; kc < nku; ++kc)
-            for (int par = 0; par < 4; ++par)
-                for (int kk = 0; kk < 16; ++kk) {
-                    const int pa = par >> 1, pb = par & 1, tap4 = kk >> 2, c8 = kk & 3, dy = tap4 >> 1, dx = tap4 & 1;
-                    for (int n = 0; n < 32; ++n)
-                        for (int e = 0; e < 8; ++e) {
-                            const int co = nb * 32 + perm(n), ci = kc * 32 + c8 * 8 + e;
-                            double sum = 0.0;
-                            for (int ky = lo_of(pa, dy); ky <= hi_of(pa, dy); ++ky)
-                                for (int kx = lo_of(pb, dx); kx <= hi_of(pb, dx); ++kx) sum += Wc[((size_t)co * cin + ci) * 9 + ky * 3 + kx];
-                            arru[(((((size_t)nb * nku + kc) * 4 + par) * 16 + kk) * 32 + n) * 8 + e] = f32_to_bf16((float)sum);
-                        }
-                }
-    const int nks = C / 16;
-    std::vector<unsigned short> arrs((size_t)nbu * nks * 2 * 32 * 8, 0);
-    for (int nb = 0; nb < nbu; ++nb)
-        for (int ks = 0; ks < nks; ++ks)
-            for (int hh = 0; hh < 2; ++hh)
-                for (int n = 0; n < 32; ++n)
-                    for (int e = 0; e < 8; ++e)
-                        arrs[((((size_t)nb * nks + ks) * 2 + hh) * 32 + n) * 8 + e] =
-                            f32_to_bf16(Wf[(size_t)(nb * 32 + perm(n)) * 2 * C + C + ks * 16 + hh * 8 + e]);
-    if (C == 128) {
-        // conv_upq.hip: the same composed, pre-summed weights (the same single rounding) as 128-cout slabs per output parity, and the
-        // skip half as four 32-channel stages
-        std::vector<unsigned short> arrq((size_t)4 * nku * 16 * 128 * 8, 0);
-        for (int par = 0; par < 4; ++par)
-            for (int kc = 0; kc < nku; ++kc)
-                for (int kk = 0; kk < 16; ++kk) {
-                    const int pa = par >> 1, pb = par & 1, tap4 = kk >> 2, c8 = kk & 3, dy = tap4 >> 1, dx = tap4 & 1;
-                    for (int n = 0; n < 128; ++n)
-                        for (int e = 0; e < 8; ++e) {
-                            const int co = perm(n), ci = kc * 32 + c8 * 8 + e;
-                            double sum = 0.0;
-                            for (int ky = lo_of(pa, dy); ky <= hi_of(pa, dy); ++ky)
-                                for (int kx = lo_of(pb, dx); kx <= hi_of(pb, dx); ++kx) sum += Wc[((size_t)co * cin + ci) * 9 + ky * 3 + kx];
-                            arrq[((((size_t)par * nku + kc) * 16 + kk) * 128 + n) * 8 + e] = f32_to_bf16((float)sum);
-                        }
-                }
-        std::vector<unsigned short> arrsq((size_t)(C / 32) * 4 * 128 * 8, 0);
-        for (int ks = 0; ks < C / 32; ++ks)
-            for (int c8 = 0; c8 < 4; ++c8)
-                for (int n = 0; n < 128; ++n)
-                    for (int e = 0; e < 8; ++e)
-                        arrsq[(((size_t)ks * 4 + c8) * 128 + n) * 8 + e] = f32_to_bf16(Wf[(size_t)perm(n) * 2 * C + C + ks * 32 + c8 * 8 + e]);
-        if (!d_zero_) { d_zero_ = dalloc(256); IRE_HIP(hipMemset(d_zero_, 0, 256)); }
-        up.d_wuq = (unsigned short*)dalloc(arrq.size() * 2);
-        up.d_wsq = (unsigned short*)dalloc(arrsq.size() * 2);
-        net_.allocs.push_back(up.d_wuq); net_.allocs.push_back(up.d_wsq);
-        IRE_HIP(hipMemcpy(up.d_wuq, arrq.data(), arrq.size() * 2, hipMemcpyHostToDevice));
-        IRE_HIP(hipMemcpy(up.d_wsq, arrsq.data(), arrsq.size() * 2, hipMemcpyHostToDevice));
-    }
-    up.d_wuf = (unsigned short*)dalloc(arru.size() * 2);
-    up.d_wsk = (unsigned short*)dalloc(arrs.size() * 2);
-    up.d_bias_uf = (float*)dalloc(C * 4);
-    net_.allocs.push_back(up.d_wuf); net_.allocs.push_back(up.d_wsk); net_.allocs.push_back(up.d_bias_uf);
-    IRE_HIP(hipMemcpy(up.d_wuf, arru.data(), arru.size() * 2, hipMemcpyHostToDevice));
-    IRE_HIP(hipMemcpy(up.d_wsk, arrs.data(), arrs.size() * 2, hipMemcpyHostToDevice));
-    IRE_HIP(hipMemcpy(up.d_bias_uf, bc.data(), C * 4, hipMemcpyHostToDevice));
-}
-
-GNW Engine::make_gn(const std::string& prefix, int C, int level) {
-    GNW g;
-    g.C = C; g.level = level;
-    for (int k = 0; k < 2; ++k) {
-        const std::string nm = prefix + (k == 0 ? ".g" : ".b");
-        auto it = host_w_.find(nm);
-        if (it == host_w_.end() || (int)it->second.second.size() != C)
-            fail(IRE_ERR_INVALID_INPUT, "invalid weight file: missing " + nm);
-        float* d = (float*)dalloc(sizeof(float) * C);
-        net_.allocs.push_back(d);
-        IRE_HIP(hipMemcpy(d, it->second.second.data(), sizeof(float) * C, hipMemcpyHostToDevice));
-        (k == 0 ? g.d_gamma : g.d_beta) = d;
-    }
-    return g;
-}
-
-RBW Engine::make_rb(const std::string& p, int C, int level) {
-    RBW r;
-    r.gn1 = make_gn(p + ".gn1", C, level);
-    r.conv1 = make_conv(CONV_RB1, p + ".conv1.w", p + ".conv1.b", C, C);
-    r.gn2 = make_gn(p + ".gn2", C, level);
-    r.conv2 = make_conv(CONV_RB2, p + ".conv2.w", p + ".conv2.b", C, C);
-    return r;
-}
-
+// the weights in weight_pack.hpp's layouts, layer by layer in the order of the schedule
 void Engine::load_weights(const void* blob, size_t bytes) {
-    const unsigned char* p = (const unsigned char*)blob;
-    auto need = [&](size_t off, size_t n) {
-        if (off + n > bytes) fail(IRE_ERR_INVALID_INPUT, "invalid weight file: truncated");
-    };
-    need(0, 12);
-    if (std::memcmp(p, "IREW", 4) != 0) fail(IRE_ERR_INVALID_INPUT, "invalid weight file: bad magic");
-    uint32_t ver, nt;
-    std::memcpy(&ver, p + 4, 4);
-    std::memcpy(&nt, p + 8, 4);
-    if (ver != 1 || nt > 4096) fail(IRE_ERR_INVALID_INPUT, "invalid weight file: version");
-    size_t off = 12;
-    host_w_.clear();
-    for (uint32_t i = 0; i < nt; ++i) {
-        uint32_t ln, nd;
-        need(off, 4); std::memcpy(&ln, p + off, 4); off += 4;
-        if (ln > 256) fail(IRE_ERR_INVALID_INPUT, "invalid weight file: name");
-        need(off, ln);
-        std::string name((const char*)p + off, ln); off += ln;
-        while (!name.empty() && name.back() == '\0') name.pop_back();
-        need(off, 4); std::memcpy(&nd, p + off, 4); off += 4;
-        if (nd > 4) fail(IRE_ERR_INVALID_INPUT, "invalid weight file: ndim");
-        std::vector<int> dims(nd);
-        size_t cnt = 1;
-        for (uint32_t d = 0; d < nd; ++d) {
-            uint32_t v; need(off, 4); std::memcpy(&v, p + off, 4); off += 4;
-            dims[d] = (int)v; cnt *= v;
-        }
-        need(off, cnt * 4);
-        std::vector<float> data(cnt);
-        std::memcpy(data.data(), p + off, cnt * 4); off += cnt * 4;
-        host_w_[name] = {dims, std::move(data)};
-    }
+    const TensorMap tm = parse_weights(blob, bytes);
     IRE_HIP(hipSetDevice(device_));
     IRE_HIP(hipDeviceSynchronize());
     delete tiled_; tiled_ = nullptr;
     for (void* q : net_.allocs) (void)hipFree(q);
     net_ = Net{};
-    net_.stem = make_conv(CONV_STEM, "stem.w", "stem.b", 3, 32);
+    if (!d_zero_) { d_zero_ = dalloc(256); IRE_HIP(hipMemset(d_zero_, 0, 256)); }
+    const bool fp8 = precision_ == IRE_PRECISION_FP8;
+    auto vec = [&](const std::string& nm, size_t n, const std::string& what) -> const std::vector<float>& {
+        auto it = tm.find(nm);
+        if (it == tm.end() || it->second.data.size() != n) fail(IRE_ERR_INVALID_INPUT, "invalid weight file: " + what);
+        return it->second.data;
+    };
+    auto conv = [&](ConvKind kind, const std::string& nm, int cin, int cout) { return upload_conv(pack_conv(tm, kind, nm + ".w", nm + ".b", cin, cout, fp8)); };
+    auto gn = [&](const std::string& nm, int C, int level) {
+        GNW g;
+        g.C = C; g.level = level;
+        g.d_gamma = upload(vec(nm + ".g", C, "missing " + nm + ".g"));
+        g.d_beta = upload(vec(nm + ".b", C, "missing " + nm + ".b"));
+        return g;
+    };
+    auto rb = [&](const std::string& p, int C, int level) {
+        RBW r;
+        r.gn1 = gn(p + ".gn1", C, level);
+        r.conv1 = conv(CONV_RB1, p + ".conv1", C, C);
+        r.gn2 = gn(p + ".gn2", C, level);
+        r.conv2 = conv(CONV_RB2, p + ".conv2", C, C);
+        return r;
+    };
+    net_.stem = conv(CONV_STEM, "stem", 3, 32);
     for (int l = 0; l < 4; ++l) {
-        for (int i = 0; i < 2; ++i)
-            net_.enc[l][i] = make_rb("enc" + std::to_string(l) + ".rb" + std::to_string(i), kWidths[l], l);
-        if (l < 3) net_.down[l] = make_conv(CONV_DOWN, "down" + std::to_string(l) + ".w", "down" + std::to_string(l) + ".b",
-                                           kWidths[l], kWidths[l + 1]);
+        const std::string s = std::to_string(l);
+        for (int i = 0; i < 2; ++i) net_.enc[l][i] = rb("enc" + s + ".rb" + std::to_string(i), kWidths[l], l);
+        if (l < 3) net_.down[l] = conv(CONV_DOWN, "down" + s, kWidths[l], kWidths[l + 1]);
     }
-    for (int i = 0; i < 2; ++i) net_.mid[i] = make_rb("mid.rb" + std::to_string(i), 256, 3);
+    for (int i = 0; i < 2; ++i) net_.mid[i] = rb("mid.rb" + std::to_string(i), 256, 3);
     for (int l = 2; l >= 0; --l) {
         const std::string s = std::to_string(l);
-        net_.up[l] = make_conv(CONV_UP, "up" + s + ".w", "up" + s + ".b", kWidths[l + 1], kWidths[l]);
-        net_.fuse[l] = make_conv(CONV_FUSE, "fuse" + s + ".w", "fuse" + s + ".b", 2 * kWidths[l], kWidths[l]);
-        make_up_fused(net_.up[l], s);
-        for (int i = 0; i < 2; ++i) net_.dec[l][i] = make_rb("dec" + s + ".rb" + std::to_string(i), kWidths[l], l);
+        PackedConv up = pack_conv(tm, CONV_UP, "up" + s + ".w", "up" + s + ".b", kWidths[l + 1], kWidths[l], fp8);
+        pack_up_fused(tm, up, s);
+        net_.up[l] = upload_conv(up);
+        net_.fuse[l] = conv(CONV_FUSE, "fuse" + s, 2 * kWidths[l], kWidths[l]);
+        for (int i = 0; i < 2; ++i) net_.dec[l][i] = rb("dec" + s + ".rb" + std::to_string(i), kWidths[l], l);
     }
-    net_.head_gn = make_gn("head.gn", 32, 0);
-    net_.head = make_conv(CONV_HEAD, "head.w", "head.b", 32, 3);
-    {
-        auto fw = host_w_.find("film.w"), fb = host_w_.find("film.b");
-        if (fw == host_w_.end() || fb == host_w_.end() || (int)fw->second.second.size() != kFilmDim * 7 ||
-            (int)fb->second.second.size() != kFilmDim)
-            fail(IRE_ERR_INVALID_INPUT, "invalid weight file: film");
-        net_.d_film_w = (float*)dalloc(sizeof(float) * kFilmDim * 7);
-        net_.d_film_b = (float*)dalloc(sizeof(float) * kFilmDim);
-        net_.allocs.push_back(net_.d_film_w);
-        net_.allocs.push_back(net_.d_film_b);
-        IRE_HIP(hipMemcpy(net_.d_film_w, fw->second.second.data(), sizeof(float) * kFilmDim * 7, hipMemcpyHostToDevice));
-        IRE_HIP(hipMemcpy(net_.d_film_b, fb->second.second.data(), sizeof(float) * kFilmDim, hipMemcpyHostToDevice));
-    }
-    host_w_.clear();
+    net_.head_gn = gn("head.gn", 32, 0);
+    net_.head = conv(CONV_HEAD, "head", 32, 3);
+    net_.d_film_w = upload(vec("film.w", (size_t)kFilmDim * 7, "film"));
+    net_.d_film_b = upload(vec("film.b", kFilmDim, "film"));
     net_.loaded = true;
     build_program();
 }

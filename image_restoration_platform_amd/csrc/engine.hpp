@@ -21,6 +21,7 @@ namespace ire {
 enum Family { FAM_CLASSIFIER = 0, FAM_CONV3 = 1, FAM_CONV1 = 2, FAM_STEM = 3, FAM_HEAD = 4, FAM_GN = 5,
               FAM_FUSION = 6, FAM_COUNT = 7 };
 
+struct PackedConv;   // weight_pack.hpp: the host side of ConvW
 struct ConvW {
     ConvKind kind = CONV_RB1;
     int cin = 0, cout = 0;       // logical channel counts (FLOP accounting)
@@ -33,7 +34,7 @@ struct ConvW {
     unsigned short* d_wstem = nullptr;  // CONV_STEM as MFMA A fragments (conv_stem.hip): [ky 3][h 2][32 permuted rows][8], k = 16 ky + 4 kx + c (kx = 3, c = 3: zero)
     unsigned short* d_wd = nullptr;  // CONV_DOWN by pixel phase (conv_down.hip): [nblock64][kc32][phase: 1+2+2+4 taps][tap*4 + c8][64][8]
     unsigned short* d_wu = nullptr;  // CONV_UP as a sub-pixel conv (conv_up.hip): [nblock32][kc32][parity][kk][32][8], taps pre-summed per parity
-    // CONV_UP composed with the level's 1x1 `fuse` (engine.cpp::make_up_fused; conv_up.hip fused form)
+    // CONV_UP composed with the level's 1x1 `fuse` (weight_pack.hpp::pack_up_fused; conv_up.hip fused form)
     unsigned short* d_wuf = nullptr; // sub-pixel slabs of (Wf_up . Wup), layout of d_wu
     unsigned short* d_wdq = nullptr; // conv_dnq.hip (stride-2 convs with cout % 128 == 0): d_wd's taps as 128-cout slabs
     unsigned short* d_wuq = nullptr; // conv_upq.hip (cout = 128): the same composed weights as [parity][kc32][tap4][c8][128 permuted rows][8]
@@ -237,10 +238,8 @@ private:
     void prof_end(hipStream_t s);
     void capture(const char* name, const unsigned short* d, size_t count, hipStream_t s);
     void capture_f32(const char* name, const float* d, size_t count, hipStream_t s);
-    ConvW make_conv(ConvKind kind, const std::string& wname, const std::string& bname, int cin, int cout);
-    void make_up_fused(ConvW& up, const std::string& level);
-    GNW make_gn(const std::string& prefix, int C, int level);
-    RBW make_rb(const std::string& prefix, int C, int level);
+    template <class T> T* upload(const std::vector<T>& v);     // allocate + register in net_.allocs + copy; null for an empty v
+    ConvW upload_conv(const PackedConv& p);                    // weight_pack.hpp's arrays of one convolution -> device
     void* dalloc(size_t bytes);
 
     int device_ = 0;
@@ -317,7 +316,6 @@ private:
     std::vector<Op> program_;
     class StripSession* tiled_ = nullptr;      // cached session of restore_tiled_device (one shape at a time)
     int tiled_h_ = 0, tiled_w_ = 0, tiled_n_ = 0;       // the layer schedule (build_program; rebuilt by load_weights)
-    std::map<std::string, std::pair<std::vector<int>, std::vector<float>>> host_w_;
     std::vector<Lane> lanes_;
     int ws_imgs_per_lane_ = 0, ws_imgs_cap_ = 0, ws_h_ = 0, ws_w_ = 0;
     size_t ws_bytes_ = 0;

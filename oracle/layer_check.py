@@ -231,7 +231,7 @@ def _wbf16(w):
 
 
 def fp8_weights(w):
-    """Per-output-channel e4m3 weights as engine.cpp (make_conv, IRE_PRECISION_FP8) states them: s_w = max|w[co]| / 448 (float),
+    """Per-output-channel e4m3 weights as weight_pack.hpp (pack_conv, fp8) states them: s_w = max|w[co]| / 448 (float),
     w_q = e4m3(w / s_w) (float division); -> (w_q * s_w in float64, K+4 roundings apply)."""
     w = np.asarray(w, dtype=np.float32)
     m = np.abs(w).reshape(w.shape[0], -1).max(axis=1)
@@ -468,7 +468,7 @@ class NetworkCheck:
             if self.up_mode != "fused":
                 cat = np.concatenate([self.get("up" + l), self.get(src2)], axis=1)
                 return _conv_layer(name, self.get(name), cat, None, _wbf16(wf)[:, :, None, None], self.w[name + ".b"], 0.0, pad=0)
-            # engine.cpp make_up_fused: fuse(concat(up(x), skip)) = (Wf_up . Wup) * x_up + Wf_skip . skip + (Wf_up . b_up + b_f);
+            # weight_pack.hpp pack_up_fused: fuse(concat(up(x), skip)) = (Wf_up . Wup) * x_up + Wf_skip . skip + (Wf_up . b_up + b_f);
             # composition in double, sub-pixel pre-sums, ONE rounding to bf16; the bias in double, rounded to float
             wu, bu = np.asarray(self.w["up" + l + ".w"], dtype=np.float64), np.asarray(self.w["up" + l + ".b"], dtype=np.float64)
             wc = np.einsum("om,mikl->oikl", wf[:, :c], wu)

@@ -1,5 +1,5 @@
 // conv_kind.hpp -- the seven convolution kinds and the integers of their v1 weight slabs; no HIP, no device code: shared by the
-// launch interface (conv_mfma.hpp) and by the host-only weight packer (weight_pack.hpp).
+// launch interface (conv_mfma.hpp), by the host-only weight packer (weight_pack.hpp) and by the launch rule book (conv_plan.hpp).
 #pragma once
 
 namespace ire {
@@ -28,5 +28,9 @@ inline int conv_nsteps(ConvKind kind) {
         default: return 18;         // 9 taps x 4 chunks
     }
 }
+// output rows per workgroup tile (columns: 32): the v1 template (conv_mfma.hip) ...
+inline int conv_tile_h(ConvKind kind) { return kind == CONV_DOWN ? 4 : 8; }
+// ... and the persistent pipelined kernels (conv_rb.hip and every kernel after it)
+constexpr int kRbTileH = 16;
 
 }  // namespace ire

@@ -345,7 +345,6 @@ void launch_one(const ConvArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-int conv_tile_h(ConvKind kind) { return kind == CONV_DOWN ? 4 : 8; }
 
 void conv_launch(ConvKind kind, const ConvArgs& a, hipStream_t stream) {
     const int nt = conv_nt(kind, a.cout);

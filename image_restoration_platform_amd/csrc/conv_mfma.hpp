@@ -87,13 +87,11 @@ struct ConvArgs {
     unsigned long long* stamps;  // diagnostic builds only (IRE_RB_ABLATE, DBG bit 16): s_memtime stamps, else null
 };
 
-int conv_tile_h(ConvKind kind);       // output rows per workgroup tile (columns: 32)
 void conv_launch(ConvKind kind, const ConvArgs& a, hipStream_t stream);
 
 // Persistent software-pipelined variant for CONV_RB1 / CONV_RB2 (conv_rb.hip): 16x32 tiles
 // (a.tiles_y must be ceil(Hout/16)), same ConvArgs; the weight slab rows are in permuted cout order (row n of a 32-row tile =
 // cout n with bits 2 and 3 swapped: weight_pack.hpp::pack_conv), so the epilogue stores straight from the accumulators.
-constexpr int kRbTileH = 16;
 // fused_act: apply y = silu(x*A+B) while staging (a.ab); otherwise the input is already activated.
 void conv_rb_launch(bool resid, bool fused_act, const ConvArgs& a, hipStream_t stream);
 // One-wave-per-SIMD variant for C >= 128 ResBlock convs on a pre-activated input (conv_w4.hip):
@@ -110,14 +108,12 @@ void conv_down_launch(const ConvArgs& a, hipStream_t stream);
 void conv_head_launch(const ConvArgs& a, hipStream_t stream);
 // C = 32 .. 256 ResBlock convs (fused activation) and the head as a producer / consumer workgroup, three waves per SIMD
 // (conv_pc.hip): a.w = permuted-row slabs [n-block of min(C, 64) couts][k-chunk][kk][rows][8] (d_wp), a.nkc = C/32, a.nblocks =
-// max(1, C/64), 16x32 tiles, partials layout of conv_rb_launch.  conv_pc_fits: every workgroup's images fit its coefficient table.
+// max(1, C/64), 16x32 tiles, partials layout of conv_rb_launch.  Every workgroup's images must fit its coefficient table (conv_plan.hpp::coef_table_fits).
 void conv_pc_launch(bool resid, bool head, const ConvArgs& a, hipStream_t stream);
-bool conv_pc_fits(int C, int tiles_per_img, int nimg);
 // C = 128 / 256 ResBlock convs (fused activation) as a producer / consumer workgroup with 128-cout items (conv_pk.hip): a.w =
 // conv_w4's slabs (d_w4), a.nkc = C / 16, a.nblocks = C / 128, 16x32 tiles; results bit-identical to conv_w4's 8-wave fused form.
-// conv_pk_fits: every workgroup's images fit its coefficient table (else conv_w4 takes the launch).
+// Every workgroup's images must fit its coefficient table (conv_plan.hpp::coef_table_fits; else conv_w4 takes the launch).
 void conv_pk_launch(bool resid, const ConvArgs& a, hipStream_t stream);
-bool conv_pk_fits(int C, int tiles_per_img, int nimg);
 // CONV_UP as a sub-pixel convolution on the low-resolution grid (conv_up.hip): 4 output parities x 2x2 pre-summed taps.
 // a.Hin/Win = low-res source, a.Hout/Wout = 2x; a.nkc = Cin/32 (even), a.nblocks = cout/32, tiles of 16x32 LOW-res pixels.
 void conv_up_subpixel_launch(const ConvArgs& a, hipStream_t stream);

@@ -16,6 +16,7 @@
 // conv_rb.hip's C = 32 variants: same results class (bf16 roundings identical, GroupNorm partials summed in the same order),
 // row strips included.  Roofline: HBM for the residual variant (1.5 GB per launch), VALU issue otherwise.
 #include "conv_mfma.hpp"
+#include "conv_plan.hpp"
 #include "gn_fold.hpp"
 #include "persist.hpp"
 
@@ -86,7 +87,7 @@ template <int C> struct PcCfg {
     static constexpr int NCC = NT / 8;                                          // 16-B chunks of an item's couts per pixel
     static constexpr int RED_OFF = BIAS_OFF + C * 4;                            // 2 x [8 waves][NCC chunks][sA, qA, sB, qB]
     static constexpr int RED_HALF = 8 * NCC * 4;                                // floats
-    static constexpr int COEF_IMGS = C == 32 ? 64 : 8;                          // images whose (A, B) the LDS table holds
+    static constexpr int COEF_IMGS = pc_coef_imgs(C);                          // images whose (A, B) the LDS table holds
     static constexpr int COEF_OFF = RED_OFF + 2 * RED_HALF * 4;
     static constexpr int HEAD_OFF = COEF_OFF + COEF_IMGS * C * 2 * 4;           // head: [8 waves][in | out][2 rows][96 B]
     static constexpr int PATCH_OFF = HEAD_OFF + (C == 32 ? 8 * 2 * 2 * 96 : 0);   // C = 32: [8 waves][32 pixels x 64 B] transpose patches of the line-coalesced epilogue
@@ -832,33 +833,17 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
 
 // C = 32 / 64 ResBlock convs with the activation applied while staging (a.ab required), and the head: a.w = permuted-row slabs
 // [k-chunk][kk = tap*4 + c8][C rows][8] (weight_pack.hpp::pack_conv d_wp), 16x32 tiles, a.stats = partials [img][tile][8][2] (not for the
-// head).  The producers' coefficient table holds 64 / 8 images (C = 32 / 64): conv_pc_fits() tells the engine whether every
-// workgroup of a launch stays within it.  (The C >= 128 form of this kernel -- 64-cout items, weight slabs streamed by the producers,
+// head).  The producers' coefficient table holds 64 / 8 images (C = 32 / 64): plan_conv (conv_plan.hpp) sends here only the
+// launches whose every workgroup stays within it.  (The C >= 128 form of this kernel -- 64-cout items, weight slabs streamed by the producers,
 // IRE_PC=7 -- lost to conv_w4 in round 2 and was superseded by conv_pk.hip in round 4: removed.)
-bool conv_pc_fits(int C, int tiles_per_img, int nimg) {
-    if (C != 32 && C != 64) return false;
-    const int imgs = C == 32 ? PcCfg<32>::COEF_IMGS : PcCfg<64>::COEF_IMGS;
-    if (nimg <= imgs) return true;
-    // the workgroups of XCD group x walk items [items x / X, items (x + 1) / X) (persist.hpp): images spanned by a range
-    const int nblk = 1;
-    const long long ipi = (long long)tiles_per_img * nblk, items = ipi * nimg;
-    const int cus = persistent_grid_cus();
-    const long long G = items < cus ? items : cus, X = G < 8 ? G : 8;
-    for (long long x = 0; x < X; ++x) {
-        const long long lo = items * x / X, hi = items * (x + 1) / X;
-        if (hi > lo && (hi - 1) / ipi - lo / ipi + 1 > imgs) return false;
-    }
-    return true;
-}
-
 void conv_pc_launch(bool resid, bool head, const ConvArgs& a, hipStream_t stream) {
     const int C = a.cout;
     if ((C != 32 && C != 64) || a.cin0 != C || a.nkc != C / 32 || a.nblocks != 1 || !a.ab)
         fail(IRE_ERR_INTERNAL, "internal: conv_pc arguments");
     if (head ? (C != 32 || !a.u8_in || !a.u8_out) : !a.stats) fail(IRE_ERR_INTERNAL, "internal: conv_pc arguments");
-    if (!conv_pc_fits(C, a.tiles_x * a.tiles_y, a.nimg)) fail(IRE_ERR_INTERNAL, "internal: conv_pc batch");
     const int items = a.tiles_x * a.tiles_y * a.nimg * a.nblocks;
     const int cus = persistent_grid_cus();
+    if (!coef_table_fits(pc_coef_imgs(C), (long long)a.tiles_x * a.tiles_y, a.nimg, cus)) fail(IRE_ERR_INTERNAL, "internal: conv_pc batch");
     const int grid = items < cus ? items : cus;
 #define PC_GO(CC, RS, HD) hipLaunchKernelGGL((conv_pc_kernel<CC, RS, HD>), dim3(grid), dim3(C3_CONS + pc_prod(CC, HD)), 0, stream, a)
     if (head) PC_GO(32, false, true);

@@ -29,6 +29,7 @@
 // the idle patches).
 // Roofline: MFMA.  `2*9*C*C` flop per output pixel, `4C` B (+ `2C` residual).
 #include "conv_mfma.hpp"
+#include "conv_plan.hpp"
 #include "gn_fold.hpp"
 #include "persist.hpp"
 
@@ -94,7 +95,7 @@ constexpr int PK_RED_BASE = PK_PATCH_BASE + 8 * PK_PATCH_BYTES;
 constexpr int PK_RED_BYTES = 2 * 8 * 16 * 2 * 4;                    // [item parity][8 waves][16 chunks of 8 couts][sum, sumsq]
 constexpr int PK_BIAS_BASE = PK_RED_BASE + PK_RED_BYTES;
 constexpr int PK_COEF_BASE = PK_BIAS_BASE + 256 * 4;
-constexpr int PK_IMGS = 4;                                          // images whose (A, B) the coefficient table holds
+// (PK_IMGS, the images whose (A, B) the coefficient table holds: conv_plan.hpp, next to the rule that keeps launches within it)
 template <int C> struct PkCfg {
     static constexpr int SINK = PK_COEF_BASE + PK_IMGS * C * 8;      // 256 B nobody reads: where the residual prefetch lands
     static constexpr int LDS = SINK + 256;
@@ -242,7 +243,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
         if (tid < C) reinterpret_cast<float*>(smem + PK_BIAS_BASE)[tid] = a.bias[tid];
         // the GroupNorm+FiLM coefficients of the images this workgroup's items belong to (gn_fold just wrote them, or
         // gn_finalize_kernel did): the producers read them from LDS -- their only vector-memory traffic is the input stream and the slabs
-        const int nim = cursor.last_img - cursor.first_img + 1;                // <= PK_IMGS (conv_pk_fits)
+        const int nim = cursor.last_img - cursor.first_img + 1;                // <= PK_IMGS (coef_table_fits)
         const float2* ab = a.ab + (size_t)cursor.first_img * C;
         float2* cd = reinterpret_cast<float2*>(smem + PK_COEF_BASE);
         if (!a.gn_stats) for (int i = tid; i < nim * C; i += PK_THREADS) cd[i] = ab[i];      // (gn_finalize_kernel ran: row strips, IRE_GN_FOLD=0)
@@ -664,30 +665,16 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
 
 }  // namespace
 
-// Every workgroup's items must stay within PK_IMGS images (the producers' coefficient table): the workgroups of XCD group x walk
-// items [items x / X, items (x + 1) / X) (persist.hpp).
-bool conv_pk_fits(int C, int tiles_per_img, int nimg) {
-    if (C != 128 && C != 256) return false;
-    if (nimg <= PK_IMGS) return true;
-    const long long ipi = (long long)tiles_per_img * (C / PK_NT), items = ipi * nimg;
-    const int cus = persistent_grid_cus();
-    const long long G = items < cus ? items : cus, X = G < 8 ? G : 8;
-    for (long long x = 0; x < X; ++x) {
-        const long long lo = items * x / X, hi = items * (x + 1) / X;
-        if (hi > lo && (hi - 1) / ipi - lo / ipi + 1 > PK_IMGS) return false;
-    }
-    return true;
-}
-
 // a.w = conv_w4's slabs [n-block of 128 couts][kc16][tap][c8][128][8] (weight_pack.hpp::pack_conv d_w4), a.nkc = C / 16, a.nblocks = C / 128,
 // a.ab required (fused activation), 16 x 32 tiles, a.stats = partials [img][tile][8][2].
 void conv_pk_launch(bool resid, const ConvArgs& a, hipStream_t stream) {
     const int C = a.cout;
     if ((C != 128 && C != 256) || a.cin0 != C || a.nkc != C / 16 || a.nblocks != C / PK_NT || !a.ab)
         fail(IRE_ERR_INTERNAL, "internal: conv_pk arguments");
-    if (!conv_pk_fits(C, a.tiles_x * a.tiles_y, a.nimg)) fail(IRE_ERR_INTERNAL, "internal: conv_pk batch");
     const int items = a.tiles_x * a.tiles_y * a.nimg * a.nblocks;
     const int cus = persistent_grid_cus();
+    // every workgroup's items must stay within PK_IMGS images, the producers' coefficient table (plan_conv sends the rest to conv_w4)
+    if (!coef_table_fits(PK_IMGS, (long long)a.tiles_x * a.tiles_y * a.nblocks, a.nimg, cus)) fail(IRE_ERR_INTERNAL, "internal: conv_pk batch");
     const int grid = items < cus ? items : cus;
 #define PK_GO(CC, RS) hipLaunchKernelGGL((conv_pk_kernel<CC, RS>), dim3(grid), dim3(PK_THREADS), 0, stream, a)
     if (C == 128) { if (resid) PK_GO(128, true); else PK_GO(128, false); }

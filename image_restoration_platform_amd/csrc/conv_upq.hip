@@ -22,7 +22,7 @@
 //     stores whole 256-B pixel runs); the DMA pieces of the stage after next are issued IN FRONT of the stores and the next barrier
 //     waits for "all but the 16 youngest" operations: the 128-KB-per-CU store burst drains behind the next stage's MFMAs.
 // One barrier per stage (8 per item).  GroupNorm partials: one (sum, sumsq) per group per ITEM, i.e. FOUR partial rows per low-res
-// tile (index tile * 4 + parity): the engine tells the finalize so (exec_conv: stat_parts).
+// tile (index tile * 4 + parity): the engine tells the finalize so (conv_plan.hpp: stat_parts).
 // Weights: a.w = [parity][kc32][tap4][c8][128 rows, permuted like conv_w4's][8] bf16 (weight_pack.hpp::pack_up_fused d_wuq),
 // a.w1 = skip weights [ks16][h][128 rows][8] (d_wsq; as bytes the same as [ks32][c8][128][8]), a.bias = composed bias.  Roofline: MFMA (executed 2*4*Cin*C + 2*C*C flop per pixel).
 #include "conv_mfma.hpp"

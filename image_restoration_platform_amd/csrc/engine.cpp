@@ -57,22 +57,8 @@ Engine::Engine(const ire_config& cfg) {
     if (num_lanes_ > 16) num_lanes_ = 16;
     if (cfg.flags & ~(uint32_t)IRE_FLAG_RESULT_PNG_BASE64) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
     flags_ = cfg.flags;
-    if (const char* v = std::getenv("IRE_CONV_V1")) rb_tile_h_ = (v[0] == '1') ? 8 : kRbTileH;
-    if (const char* v = std::getenv("IRE_RB_PRIO")) prio_young_ = std::atoi(v);
-    if (const char* v = std::getenv("IRE_W4")) use_w4_ = std::atoi(v);
-    if (const char* v = std::getenv("IRE_W4_SPLIT")) w4_split_ = std::atoi(v);
-    if (const char* v = std::getenv("IRE_UP_RB_MINC")) up_rb_min_c_ = std::atoi(v);
-    if (const char* v = std::getenv("IRE_UP_SUBPIX")) up_subpixel_ = std::atoi(v);
-    if (const char* v = std::getenv("IRE_UP_FUSE")) up_fuse_ = std::atoi(v);
-    if (const char* v = std::getenv("IRE_GN_FOLD")) gn_fold_ = std::atoi(v);
-    if (const char* v = std::getenv("IRE_PC")) pc_split_ = std::atoi(v);
-    if (const char* v = std::getenv("IRE_PK")) use_pk_ = std::atoi(v);
-    if (const char* v = std::getenv("IRE_UPQ")) use_upq_ = std::atoi(v);
-    if (const char* v = std::getenv("IRE_DNQ")) use_dnq_ = std::atoi(v);
-    if (const char* v = std::getenv("IRE_HEAD_RB")) head_rb_ = std::atoi(v);
-    if (const char* v = std::getenv("IRE_DOWN_RB")) down_rb_ = std::atoi(v);
-    if (const char* v = std::getenv("IRE_STEM_RB")) stem_rb_ = std::atoi(v);
-    if (const char* v = std::getenv("IRE_FP8_MX")) fp8_mx_ = std::atoi(v);
+    sw_ = ConvSwitches::from_env();
+    cus_ = persistent_grid_cus();
     if (const char* v = std::getenv("IRE_RB_STAMPS")) {   // diagnostic: "<cout>[r]" = stamp the first such ResBlock conv
         stamps_cout_ = std::atoi(v);
         stamps_resid_ = std::strchr(v, 'r') != nullptr;
@@ -190,7 +176,7 @@ void Engine::load_weights_file(const char* path) {
     load_weights(blob.data(), blob.size());
 }
 
-// one packed array -> device (null for an array the packer did not produce: exec_conv picks kernels by that)
+// one packed array -> device (null for an array the packer did not produce: conv_plan.hpp picks kernels by that)
 template <class T>
 T* Engine::upload(const std::vector<T>& v) {
     if (v.empty()) return nullptr;
@@ -202,8 +188,7 @@ T* Engine::upload(const std::vector<T>& v) {
 
 ConvW Engine::upload_conv(const PackedConv& p) {
     ConvW c;
-    c.kind = p.kind; c.cin = p.cin; c.cout = p.cout; c.cin0 = p.cin0; c.cin1 = p.cin1;
-    c.nt = p.nt; c.nblocks = p.nblocks; c.nkc = p.nkc; c.kc_split = p.kc_split;
+    c.desc = conv_desc(p);
     c.d_w = upload(p.w); c.d_wp = upload(p.wp); c.d_w4 = upload(p.w4); c.d_w4h = upload(p.w4h); c.d_wstem = upload(p.wstem);
     c.d_wd = upload(p.wd); c.d_wu = upload(p.wu); c.d_wuf = upload(p.wuf); c.d_wdq = upload(p.wdq); c.d_wuq = upload(p.wuq);
     c.d_wsq = upload(p.wsq); c.d_wsk = upload(p.wsk); c.d_bias_uf = upload(p.bias_uf); c.d_w8x = upload(p.w8x); c.d_w8 = upload(p.w8);
@@ -475,7 +460,7 @@ void Engine::prof_begin(int fam, hipStream_t s, double flops, double bytes) {
     r.e1 = get();
     prof_.push_back(r);
 }
-void Engine::prof_tag(const std::string& key, const char* kernel, int level, int cin, int cout, double flops_exec) {
+void Engine::prof_tag(const char* key, const char* kernel, int level, int cin, int cout, double flops_exec) {
     if (!prof_open_) return;
     int gi = -1;
     for (size_t i = 0; i < prof_groups_.size(); ++i) if (prof_groups_[i].key == key) { gi = (int)i; break; }
@@ -579,14 +564,12 @@ void Engine::debug_sums(int n, uint64_t* out) {
 // ------------------------------------------------------------------------------------------------
 void Engine::build_program() {
     program_.clear();
-    const bool v2 = rb_tile_h_ == kRbTileH;
     auto gn = [&](const GNW& g) { Op o; o.kind = Op::GN; o.gn = &g; program_.push_back(o); };
     auto conv = [&](const ConvW& cw, int in0, int in1, int resid, int out, int lin, int lout, bool use_ab, const std::string& name) {
         Op o; o.kind = Op::CONV; o.cw = &cw; o.in0 = in0; o.in1 = in1; o.resid = resid; o.out = out; o.lin = lin; o.lout = lout;
         o.use_ab = use_ab; o.name = name;
-        const bool upf = cw.kind == CONV_UP && in1 != BUF_NONE;           // `up` composed with `fuse`: its output is what fuse's was
-        o.halo_out = (cw.kind != CONV_UP || upf) && cw.kind != CONV_HEAD;   // a plain `up` feeds the 1x1 fuse only, the head writes pixels
-        o.stats_out = (cw.kind != CONV_UP || upf) && cw.kind != CONV_HEAD;
+        const bool upf = cw.desc.kind == CONV_UP && in1 != BUF_NONE;      // `up` composed with `fuse`: its output is what fuse's was
+        o.halo_out = o.stats_out = conv_feeds_gn(cw.desc.kind, upf);
         program_.push_back(o);
     };
     // ResBlock: out = x + conv2(silu(gn2(conv1(silu(gn1(x)))))); the partials of x were written by x's producer
@@ -614,8 +597,7 @@ void Engine::build_program() {
     int deep = buf_id(3, 2);
     for (int l = 2; l >= 0; --l) {
         const std::string sl = std::to_string(l);
-        const bool upf = v2 && up_fuse_ && up_subpixel_ && net_.up[l].d_wuf != nullptr && net_.up[l].cout >= up_rb_min_c_;
-        if (upf) {
+        if (up_is_composed(sw_, net_.up[l].desc)) {
             conv(net_.up[l], deep, buf_id(l, 4), BUF_NONE, buf_id(l, 2), l + 1, l, false, "fuse" + sl);     // one kernel, the `up` tensor never exists
         } else {
             conv(net_.up[l], deep, BUF_NONE, BUF_NONE, buf_id(l, 0), l + 1, l, false, "up" + sl);
@@ -641,9 +623,17 @@ Geo Engine::geo_of_lane(const Lane& L, int nimg, int h, int w, const uint8_t* d_
     return g;
 }
 
+// One convolution launch: conv_plan.hpp decides everything that can be decided without a device, this binds the pointers the plan
+// names and launches.
 void Engine::exec_conv(Run& R, const Op& op, const Geo& g) {
     const ConvW& cw = *op.cw;
-    const int Hin = g.h >> op.lin, Win = g.w >> op.lin, Hout = g.h >> op.lout, Wout = g.w >> op.lout;
+    const ConvDesc& d = cw.desc;
+    ConvSite site;
+    site.lin = op.lin; site.lout = op.lout; site.use_ab = op.use_ab; site.has_in1 = op.in1 != BUF_NONE; site.stats_out = op.stats_out;
+    site.nimg = g.nimg; site.h = g.h; site.w = g.w; site.H = g.H; site.halo = g.halo; site.has_up = g.has_up; site.has_down = g.has_down;
+    site.y0 = g.y0; site.cus = cus_;
+    const ConvPlan p = plan_conv(sw_, d, site, precision_ == IRE_PRECISION_FP8);
+
     // inputs are addressed from the buffer start (halo row included: in_row_off), outputs / residual from the first real row
     auto in_ptr = [&](int id) -> const unsigned short* { return id == BUF_NONE ? nullptr : g.buf[id >> 3][id & 7]; };
     auto out_ptr = [&](int id) -> unsigned short* {
@@ -651,77 +641,35 @@ void Engine::exec_conv(Run& R, const Op& op, const Geo& g) {
         const int l = id >> 3;
         return g.buf[l][id & 7] + (size_t)g.halo * (g.w >> l) * kWidths[l];
     };
+    const int Hout = g.h >> op.lout, Wout = g.w >> op.lout;
     ConvArgs a{};
-    a.in0 = (cw.kind == CONV_STEM) ? (const void*)g.img_in : (const void*)in_ptr(op.in0);
+    a.in0 = (d.kind == CONV_STEM) ? (const void*)g.img_in : (const void*)in_ptr(op.in0);
     a.in1 = in_ptr(op.in1);
-    a.cin0 = cw.cin0; a.cin1 = cw.cin1; a.kc_split = cw.kc_split; a.nkc = cw.nkc;
-    a.w = cw.d_w; a.bias = cw.d_bias; a.ab = op.use_ab ? R.ab : nullptr; a.resid = out_ptr(op.resid); a.out = out_ptr(op.out);
-    a.u8_in = cw.kind == CONV_HEAD ? g.img_in + (size_t)g.halo * g.w * 3 : nullptr;
-    a.u8_out = cw.kind == CONV_HEAD ? g.img_out : nullptr;
-    a.Hin = Hin; a.Win = Win; a.Hout = Hout; a.Wout = Wout;
-    a.in_rows = Hin + 2 * g.halo; a.in_row_off = g.halo;
-    {
-        const int HV = cw.kind == CONV_UP ? 2 * Hin : Hin;      // virtual input rows (nearest x2 folded into the staging)
-        a.iy_lo = (g.halo && g.has_up) ? -1 : 0;
-        a.iy_span = HV + ((g.halo && g.has_down) ? 1 : 0) - a.iy_lo;
-    }
-    a.cout = (cw.kind == CONV_HEAD) ? 32 : cw.cout;
-    a.tiles_x = ceil_div(Wout, 32);
-    const bool rb = (cw.kind == CONV_RB1 || cw.kind == CONV_RB2);
-    const bool up_rb = (cw.kind == CONV_UP) && rb_tile_h_ == kRbTileH && cw.cout >= up_rb_min_c_;
-    const bool up_sub = up_rb && up_subpixel_ && cw.d_wu != nullptr;       // sub-pixel form: tiles and halo rows on the LOW-res grid
-    const bool up_fused = up_sub && op.in1 != BUF_NONE;                     // composed with the 1x1 `fuse` (build_program)
-    // cout = 128: parity-major items with all 128 couts (conv_upq.hip); four partial rows per low-res tile (fp8 engines too: their `up` and
-    // `down` convs stay bf16).  The cout = 64 level stays on conv_up.hip: its row-parity form of this kernel measured 278 us against 241
-    // (profiles/r04_experiments.md).  A function of the layer only: batch / strip invariance holds.
-    const bool up_q = up_fused && use_upq_ && cw.d_wuq != nullptr && cw.cout == 128 && cw.cin % 32 == 0;
-    const int parts_mul = up_q ? 4 : 1;     // partial rows per low-res tile: one per item (parity)
-    const bool head_rb = cw.kind == CONV_HEAD && rb_tile_h_ == kRbTileH && head_rb_ && cw.d_wp != nullptr;    // the head on the pipelined kernel
-    const bool down_rb = cw.kind == CONV_DOWN && rb_tile_h_ == kRbTileH && down_rb_ && cw.d_wd != nullptr;    // stride-2 convs by pixel phase
-    const bool stem_rb = cw.kind == CONV_STEM && rb_tile_h_ == kRbTileH && stem_rb_ && cw.d_wstem != nullptr && op.stats_out;  // the stem on its own kernel
-    const int th = (rb || up_rb || head_rb || down_rb || stem_rb) ? rb_tile_h_ : conv_tile_h(cw.kind);
-    a.tiles_y = ceil_div(Hout, th);
-    if (up_sub) {
-        a.tiles_x = ceil_div(Win, 32); a.tiles_y = ceil_div(Hin, 16);
-        a.iy_lo = (g.halo && g.has_up) ? -1 : 0;
-        a.iy_span = Hin + ((g.halo && g.has_down) ? 1 : 0) - a.iy_lo;
-    }
-    a.stats = nullptr;
-    if (op.stats_out) {
-        // partials are indexed by the GLOBAL tile: a strip writes its tiles at its offset (strip starts are multiples of the
-        // tile height at every level: checked by the strip planner), so the finalize sees exactly the whole-image layout
-        // (the fused `up` writes one partial per LOW-res tile: its items are 32 x 64 output pixels)
-        const int sl = up_fused ? op.lin : op.lout;
-        const int ty0 = (g.y0 >> sl) / th;
-        float* dst = R.stats_alt ? R.stats_alt : R.stats;         // ping-pong: this conv may still be reading R.stats in its folded finalize
-        a.stats = dst + (size_t)ty0 * a.tiles_x * 16 * parts_mul;
-    }
-    a.nimg = g.nimg; a.nblocks = cw.nblocks;
-    a.group_size = std::max(1, a.cout / 8);
-    a.stamps = nullptr;
-    a.prio_young = prio_young_;
-    if (stamps_dev_ && rb && cw.cout == stamps_cout_ && (cw.kind == CONV_RB2) == stamps_resid_ && (!stamps_taken_ || !stamps_tl_.empty() || std::getenv("IRE_STAMPS_RAW"))) {
+    if (p.in1_first_row) a.in1 = in_ptr(op.in1) + (size_t)g.halo * Wout * d.cout;
+    a.cin0 = d.cin0; a.cin1 = p.cin1; a.kc_split = d.kc_split; a.nkc = p.nkc; a.nblocks = p.nblocks; a.w4_nt = p.w4_nt; a.fp8 = p.fp8;
+    const unsigned short* const slabs[] = {nullptr, cw.d_w, cw.d_wp, cw.d_w4, cw.d_w4h, cw.d_wstem, cw.d_wd, cw.d_wu, cw.d_wuf, cw.d_wdq, cw.d_wuq, cw.d_wsq,
+                                           cw.d_wsk, reinterpret_cast<const unsigned short*>(cw.d_w8x), reinterpret_cast<const unsigned short*>(cw.d_w8)};   // WeightArr
+    const float* const biases[] = {cw.d_bias, cw.d_bias_uf, cw.d_bias8};      // BiasArr
+    a.w = slabs[p.w]; a.w1 = slabs[p.w1]; a.bias = biases[p.bias];
+    if (p.fp8) a.oscale = cw.d_oscale;
+    if (p.zeros) a.zeros = d_zero_;
+    a.ab = op.use_ab ? R.ab : nullptr; a.resid = out_ptr(op.resid); a.out = out_ptr(op.out);
+    a.u8_in = d.kind == CONV_HEAD ? g.img_in + (size_t)g.halo * g.w * 3 : nullptr;
+    a.u8_out = d.kind == CONV_HEAD ? g.img_out : nullptr;
+    a.Hin = g.h >> op.lin; a.Win = g.w >> op.lin; a.Hout = Hout; a.Wout = Wout;
+    a.in_rows = p.in_rows; a.in_row_off = p.in_row_off; a.iy_lo = p.iy_lo; a.iy_span = p.iy_span;
+    a.cout = p.cout; a.group_size = p.group_size; a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.nimg = g.nimg;
+    // ping-pong: this conv may still be reading R.stats in its folded finalize
+    if (op.stats_out) a.stats = (R.stats_alt ? R.stats_alt : R.stats) + p.stats_offset();
+    a.prio_young = sw_.prio_young;
+    const bool rb = d.kind == CONV_RB1 || d.kind == CONV_RB2;
+    if (stamps_dev_ && rb && d.cout == stamps_cout_ && (d.kind == CONV_RB2) == stamps_resid_ && (!stamps_taken_ || !stamps_tl_.empty() || std::getenv("IRE_STAMPS_RAW"))) {
         a.stamps = stamps_dev_;
         stamps_taken_ = true;
     }
-    const int taps = (cw.kind == CONV_FUSE) ? 1 : 9;
-    const double px = (double)g.nimg * Hout * Wout;
-    double flops = 2.0 * taps * cw.cin * cw.cout * px;
-    const double in_px = (double)g.nimg * Hin * Win;
-    double bytes = in_px * cw.cin * (cw.kind == CONV_STEM ? 1 : 2) + px * cw.cout * (cw.kind == CONV_HEAD ? 1 : 2);
-    if (up_fused) { flops += 2.0 * 2 * cw.cout * cw.cout * px; bytes += px * cw.cout * 2; }   // the algorithmic work of `fuse` rides along: 1x1 over 2C channels, the skip tensor read
-    if (cw.kind == CONV_RB2) bytes += px * cw.cout * 2;
-    if (cw.kind == CONV_HEAD) bytes += px * 3;
-    int fam = FAM_CONV3;
-    if (cw.kind == CONV_FUSE) fam = FAM_CONV1;
-    else if (cw.kind == CONV_STEM) fam = FAM_STEM;
-    else if (cw.kind == CONV_HEAD) fam = FAM_HEAD;
-    // conv_w4: the C >= 128 ResBlock convs, activation fused into its staging
-    const bool w4 = rb && rb_tile_h_ == kRbTileH && use_w4_ && cw.d_w4 != nullptr && a.ab != nullptr && cw.cout >= 128;
     if (R.gn_pending) {
         // the deferred GroupNorm finalize of this conv's input: inside the kernel's prologue where it has one (gn_fold.hpp)
-        const bool folds = a.ab != nullptr && (w4 || head_rb || (rb && rb_tile_h_ == kRbTileH));
-        if (folds) {
+        if (p.folds_gn) {
             const GNW& gn = *R.gn_pending;
             a.gn_stats = R.gn_stats; a.gn_parts = R.gn_parts; a.gn_hw = (g.H >> gn.level) * (g.w >> gn.level);
             a.gn_gamma = gn.d_gamma; a.gn_beta = gn.d_beta; a.gn_film = R.film; a.gn_film_stride = kFilmDim; a.gn_film_off = kFilmOff[gn.level];
@@ -729,96 +677,35 @@ void Engine::exec_conv(Run& R, const Op& op, const Geo& g) {
             R.gn_pending = nullptr;
         } else flush_gn(R, g);
     }
-    prof_begin(fam, R.stream, flops, bytes);
-    const char* kname = "conv_mfma";       // which kernel takes this launch (the branches below)
-    if (w4 && fp8_mx_ && cw.d_w8x != nullptr && a.ab != nullptr) {   // IRE_PRECISION_FP8: the 2x-rate block-scaled fp8 MFMA
-        a.fp8 = 1; a.w = reinterpret_cast<const unsigned short*>(cw.d_w8x); a.bias = cw.d_bias8; a.oscale = cw.d_oscale;
-        a.nkc = cw.cin / 32; a.nblocks = cw.cout / 128;
-        conv_f8_launch(cw.kind == CONV_RB2, a, R.stream); kname = "conv_f8";
-    } else if (w4) {
-        a.w = cw.d_w4; a.nkc = cw.cin / 16; a.nblocks = cw.cout / 128;
-        {   // 64-cout items where 128-cout ones would leave CUs idle (512^2 at level 3): twice the items, each half the MFMAs.  The choice
-            // is a function of the IMAGE's shape at this level only -- not of the batch size, not of the strip -- because the two forms add
-            // the GroupNorm partials of a tile in different fp32 orders: a result must not depend on the batch around it or on the strip
-            // decomposition (tests: batch invariance, tiled == untiled).  Rule: a batch of 8 such images would not fill the CUs.
-            const int tiles_img = ceil_div(g.H >> op.lout, kRbTileH) * ceil_div(g.w >> op.lout, 32);
-            if (w4_split_ && cw.d_w4h && a.ab != nullptr && cw.d_w8 == nullptr && tiles_img * a.nblocks * 8 < 256) {
-                a.w = cw.d_w4h; a.nblocks = cw.cout / 64; a.w4_nt = 64;
-            }
-        }
-        if (cw.d_w8 != nullptr && a.ab != nullptr) {      // IRE_PRECISION_FP8: e4m3 operands for the C >= 128 ResBlock convs
-            a.fp8 = 1; a.w = reinterpret_cast<const unsigned short*>(cw.d_w8); a.bias = cw.d_bias8; a.oscale = cw.d_oscale;
-        }
-        // the producer / consumer form (conv_pk.hip) takes the 128-cout bf16 launches with a fused activation whose workgroups stay
-        // within its coefficient table, with and without the residual; same slabs, bit-identical results.  conv_w4 keeps fp8, the
-        // 64-cout items and the batches conv_pk_fits refuses
-        // (use_pk_ 2: all of them; 1: the convs without a residual -- the residual variant lost to conv_w4 while its epilogue spilled
-        //  and waited for its residual rows one pass at a time: profiles/r05_experiments.md)
-        if (use_pk_ && (use_pk_ >= 2 || cw.kind != CONV_RB2) && !a.fp8 && a.ab != nullptr && a.w4_nt != 64 && cw.cin == cw.cout &&
-            conv_pk_fits(cw.cout, a.tiles_x * a.tiles_y, g.nimg)) {
-            conv_pk_launch(cw.kind == CONV_RB2, a, R.stream); kname = "conv_pk";
-        } else {
-            conv_w4_launch(cw.kind == CONV_RB2, a, R.stream); kname = "conv_w4";
-        }
-    } else if (head_rb) { a.w = cw.d_wp; if (pc_split_ & 1) { conv_pc_launch(false, true, a, R.stream); kname = "conv_pc"; } else { conv_head_launch(a, R.stream); kname = "conv_rb"; } }
-    else if (down_rb && use_dnq_ && cw.d_wdq != nullptr) {
-        a.w = cw.d_wdq; a.nkc = cw.cin / 32; a.nblocks = cw.cout / 128; a.zeros = d_zero_;
-        conv_dnq_launch(a, R.stream); kname = "conv_dnq";
+    prof_begin(p.fam, R.stream, p.flops, p.bytes);
+    switch (p.kernel) {
+        case K_V1: conv_launch(d.kind, a, R.stream); break;
+        case K_F8: conv_f8_launch(p.resid, a, R.stream); break;
+        case K_PK: conv_pk_launch(p.resid, a, R.stream); break;
+        case K_W4: conv_w4_launch(p.resid, a, R.stream); break;
+        case K_PC: conv_pc_launch(p.resid, false, a, R.stream); break;
+        case K_RB: conv_rb_launch(p.resid, p.fused_act, a, R.stream); break;
+        case K_PC_HEAD: conv_pc_launch(false, true, a, R.stream); break;
+        case K_RB_HEAD: conv_head_launch(a, R.stream); break;
+        case K_DNQ: conv_dnq_launch(a, R.stream); break;
+        case K_DOWN: conv_down_launch(a, R.stream); break;
+        case K_STEM: conv_stem_launch(a, R.stream); break;
+        case K_UPQ: conv_upq_launch(a, R.stream); break;
+        case K_UP_FUSED:
+        case K_UP_SUB: conv_up_subpixel_launch(a, R.stream); break;
+        case K_UP_RB: conv_up_launch(a, R.stream); break;
     }
-    else if (down_rb) { a.w = cw.d_wd; a.nkc = cw.cin / 32; a.nblocks = cw.cout / 64; conv_down_launch(a, R.stream); kname = "conv_down"; }
-    else if (stem_rb) { a.w = cw.d_wstem; conv_stem_launch(a, R.stream); kname = "conv_stem"; }
-    else if (up_q) {
-        a.w = cw.d_wuq; a.w1 = cw.d_wsq; a.bias = cw.d_bias_uf; a.nkc = cw.cin / 32; a.nblocks = parts_mul;
-        a.in1 = in_ptr(op.in1) + (size_t)g.halo * Wout * cw.cout;
-        a.cin1 = cw.cout; a.zeros = d_zero_;
-        conv_upq_launch(a, R.stream); kname = "conv_upq";
-    }
-    else if (up_fused) {
-        a.w = cw.d_wuf; a.w1 = cw.d_wsk; a.bias = cw.d_bias_uf; a.nkc = cw.cin / 32; a.nblocks = cw.cout / 32;
-        a.in1 = in_ptr(op.in1) + (size_t)g.halo * Wout * cw.cout;      // the skip tensor is read at output pixels only: first real row
-        a.cin1 = cw.cout;
-        conv_up_subpixel_launch(a, R.stream); kname = "conv_up";
-    }
-    else if (up_sub) { a.in1 = nullptr; a.w = cw.d_wu; a.nkc = cw.cin / 32; a.nblocks = cw.cout / 32; conv_up_subpixel_launch(a, R.stream); kname = "conv_up"; }
-    else if (up_rb) { if (cw.d_wp) a.w = cw.d_wp; conv_up_launch(a, R.stream); kname = "conv_rb"; }
-    else if (rb && rb_tile_h_ == kRbTileH) {
-        if (cw.d_wp) a.w = cw.d_wp;
-        const bool pc = a.ab != nullptr && cw.d_wp && cw.cin == cw.cout &&
-                        ((cw.cout == 32 && (pc_split_ & 1)) || (cw.cout == 64 && (pc_split_ & 2))) && conv_pc_fits(cw.cout, a.tiles_x * a.tiles_y, g.nimg);
-        if (pc) { conv_pc_launch(cw.kind == CONV_RB2, false, a, R.stream); kname = "conv_pc"; }
-        else { conv_rb_launch(cw.kind == CONV_RB2, /*fused_act=*/a.ab != nullptr, a, R.stream); kname = "conv_rb"; }
-    }
-    else conv_launch(cw.kind, a, R.stream);
-    {
-        // layer group of this launch (bench.py roofline.per_level) and the flops the kernel really issues: the sub-pixel `up`
-        // form runs 4 of the 9 taps, its composed `fuse` only the skip half of the 1x1 (the up half is folded into the weights)
-        double fexec = flops;
-        if (up_fused) fexec = 2.0 * 4 * cw.cin * cw.cout * px + 2.0 * cw.cout * cw.cout * px;
-        else if (up_sub) fexec = 2.0 * 4 * cw.cin * cw.cout * px;
-        std::string key;
-        switch (cw.kind) {
-            case CONV_RB1: key = "L" + std::to_string(op.lout) + ".rb1"; break;
-            case CONV_RB2: key = "L" + std::to_string(op.lout) + ".rb2"; break;
-            case CONV_DOWN: key = "down" + std::to_string(op.lin); break;
-            case CONV_UP: key = "up" + std::to_string(op.lout); break;
-            case CONV_FUSE: key = "fuse" + std::to_string(op.lout); break;
-            case CONV_STEM: key = "stem"; break;
-            case CONV_HEAD: key = "head"; break;
-            default: key = "conv"; break;
-        }
-        prof_tag(key, kname, op.lout, cw.cin, cw.cout, fexec);
-    }
+    prof_tag(p.key, p.kname, op.lout, d.cin, d.cout, p.flops_exec);       // layer group of this launch (bench.py roofline.per_level)
     prof_end(R.stream);
     if (op.stats_out) {
-        const int sl = up_fused ? op.lin : op.lout;
-        R.stat_parts = a.tiles_x * ceil_div(g.H >> sl, th) * parts_mul;
+        R.stat_parts = p.stat_parts;
         if (R.stats_alt) std::swap(R.stats, R.stats_alt);          // R.stats = the partials produced last
     }
-    if (capture_ && !op.name.empty() && a.out && g.halo == 0) capture(op.name.c_str(), a.out, (size_t)g.nimg * Hout * Wout * cw.cout, R.stream);
+    if (capture_ && !op.name.empty() && a.out && g.halo == 0) capture(op.name.c_str(), a.out, (size_t)g.nimg * Hout * Wout * d.cout, R.stream);
     // the (A, B) of y = x A + B this conv applied while staging, [image][cin][2] floats, as "<layer>.ab" ("head.ab" for the head): what a
     // per-layer check needs to recompute the activated operand from the very coefficients the kernel used
     if (capture_ && a.ab != nullptr && g.halo == 0)
-        capture_f32(((op.name.empty() ? std::string("head") : op.name) + ".ab").c_str(), reinterpret_cast<const float*>(R.ab), (size_t)g.nimg * cw.cin * 2, R.stream);
+        capture_f32(((op.name.empty() ? std::string("head") : op.name) + ".ab").c_str(), reinterpret_cast<const float*>(R.ab), (size_t)g.nimg * d.cin * 2, R.stream);
 }
 
 void Engine::flush_gn(Run& R, const Geo& g) {
@@ -836,7 +723,7 @@ void Engine::exec_op(Run& R, const Op& op, const Geo& g) {
             // the partials of the tensor produced last; finalized by the consumer itself (exec_conv) unless that is switched off
             // or this is a row strip (one finalize over the gathered array serves all strips)
             R.gn_pending = op.gn; R.gn_stats = R.stats; R.gn_parts = R.stat_parts;
-            if (!gn_fold_ || g.halo) flush_gn(R, g);
+            if (!sw_.gn_fold || g.halo) flush_gn(R, g);
             break;
         }
         case Op::CONV: exec_conv(R, op, g); break;

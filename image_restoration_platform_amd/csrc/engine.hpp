@@ -15,18 +15,13 @@
 #include "classifier.hpp"
 #include "common.hpp"
 #include "conv_mfma.hpp"
+#include "conv_plan.hpp"
 
 namespace ire {
 
-enum Family { FAM_CLASSIFIER = 0, FAM_CONV3 = 1, FAM_CONV1 = 2, FAM_STEM = 3, FAM_HEAD = 4, FAM_GN = 5,
-              FAM_FUSION = 6, FAM_COUNT = 7 };
-
 struct PackedConv;   // weight_pack.hpp: the host side of ConvW
 struct ConvW {
-    ConvKind kind = CONV_RB1;
-    int cin = 0, cout = 0;       // logical channel counts (FLOP accounting)
-    int cin0 = 0, cin1 = 0;      // channels per pixel of the two sources
-    int nt = 0, nblocks = 0, nkc = 0, kc_split = 0;
+    ConvDesc desc;               // kind, channel counts and which of the arrays below exist (weight_pack.hpp::conv_desc)
     unsigned short* d_w = nullptr;
     unsigned short* d_wp = nullptr;   // slabs with permuted cout rows for conv_rb.hip's direct epilogue
     unsigned short* d_w4 = nullptr;  // second arrangement for conv_w4.hip (C >= 128 ResBlock convs): 16-channel stages, 128-cout blocks
@@ -234,7 +229,7 @@ private:
     void exec_conv(Run& R, const Op& op, const Geo& g);
     static Geo geo_of_lane(const Lane& L, int nimg, int h, int w, const uint8_t* d_in, uint8_t* d_out);
     void prof_begin(int fam, hipStream_t s, double flops, double bytes);
-    void prof_tag(const std::string& key, const char* kernel, int level, int cin, int cout, double flops_exec);   // after prof_begin: the open record's layer group
+    void prof_tag(const char* key, const char* kernel, int level, int cin, int cout, double flops_exec);   // after prof_begin: the open record's layer group
     void prof_end(hipStream_t s);
     void capture(const char* name, const unsigned short* d, size_t count, hipStream_t s);
     void capture_f32(const char* name, const float* d, size_t count, hipStream_t s);
@@ -247,22 +242,8 @@ private:
     int num_lanes_ = 1;
     uint32_t flags_ = 0;
     int precision_ = IRE_PRECISION_BF16;
-    int w4_split_ = 1;            // IRE_W4_SPLIT=0: never use the 64-cout items
-    int use_dnq_ = 1;             // the stride-2 convs with cout >= 128 as all-DMA 128-cout items on conv_dnq.hip (IRE_DNQ=0: conv_down.hip)
-    int use_upq_ = 1;             // the level-2 `up` + `fuse` (cout = 128) as parity-major 128-cout items on conv_upq.hip (IRE_UPQ=0: conv_up.hip)
-    int use_pk_ = 2;              // C >= 128 ResBlock convs (128-cout items, fused activation) on conv_pk.hip's producer / consumer workgroups: 2 = all, 1 = the convs without a residual (IRE_PK=0: conv_w4.hip)
-    int use_w4_ = 1;              // C >= 128 ResBlock convs on conv_w4.hip (IRE_W4=0: conv_rb.hip)
-    int fp8_mx_ = 1;              // fp8: the block-scaled K = 64 MFMA (conv_f8.hip); IRE_FP8_MX=0: the same-rate 32x32x16 fp8 form in conv_w4.hip
-    int down_rb_ = 1;             // stride-2 `down` convs on conv_down.hip's pipelined phase kernel (IRE_DOWN_RB=0: the v1 kernel)
-    int head_rb_ = 1;             // the 32 -> 3 head conv on conv_rb.hip's pipelined kernel (IRE_HEAD_RB=0: the v1 kernel)
-    int pc_split_ = 3;            // producer / consumer workgroups (conv_pc.hip): bit 0 = C = 32 ResBlock convs + head, bit 1 = C = 64; IRE_PC=0: conv_rb.hip
-    int gn_fold_ = 1;             // GroupNorm finalize inside the consuming conv's prologue (gn_fold.hpp); IRE_GN_FOLD=0: 33 gn_finalize launches per step
-    int stem_rb_ = 1;             // the stem on its own kernel (conv_stem.hip); IRE_STEM_RB=0: the v1 template
-    int up_fuse_ = 1;             // `up` + 1x1 `fuse` as ONE composed convolution with the skip term in conv_up.hip's epilogue (IRE_UP_FUSE=0: two kernels)
-    int up_subpixel_ = 1;         // `up` convs as sub-pixel convolutions on the low-res grid (IRE_UP_SUBPIX=0: nearest x2 + 3x3 on conv_rb.hip)
-    int up_rb_min_c_ = 32;        // `up` convs with cout >= this run on conv_rb.hip (IRE_UP_RB_MINC), the rest on the v1 kernel
-    int prio_young_ = 0;          // static s_setprio for waves 4-7 of conv_rb (A/B'd: it only swaps which half waits)
-    int rb_tile_h_ = kRbTileH;  // 16: persistent pipelined conv_rb.hip; 8: conv_mfma.hip (IRE_CONV_V1=1)
+    ConvSwitches sw_;             // the A/B schedule switches, read from the environment once (conv_plan.hpp)
+    int cus_ = 256;               // persistent_grid_cus(), read once
     std::mutex mu_;
     hipStream_t main_stream_ = nullptr;
     hipEvent_t ev_[4] = {};

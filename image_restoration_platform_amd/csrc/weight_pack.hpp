@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "conv_kind.hpp"
+#include "conv_plan.hpp"
 #include "errors.hpp"
 
 namespace ire {
@@ -188,7 +189,7 @@ inline std::vector<unsigned short> pack_stem(const float* W) {
     return a;
 }
 
-// The packed arrays of one convolution (an empty vector = the array does not exist: exec_conv picks kernels by that) and the
+// The packed arrays of one convolution (an empty vector = the array does not exist: conv_plan.hpp picks kernels by that) and the
 // scalars the launches need.  Field names and layouts: ConvW in engine.hpp.
 struct PackedConv {
     ConvKind kind = CONV_RB1;
@@ -266,6 +267,17 @@ inline PackedConv pack_conv(const TensorMap& tm, ConvKind kind, const std::strin
     c.bias.assign(cout_pad, 0.f);
     std::copy(B, B + cout, c.bias.begin());
     return c;
+}
+
+// what conv_plan.hpp needs to know of a packed convolution: its scalars and which arrays exist
+inline ConvDesc conv_desc(const PackedConv& p) {
+    ConvDesc d;
+    d.kind = p.kind; d.cin = p.cin; d.cout = p.cout; d.cin0 = p.cin0; d.cin1 = p.cin1; d.nkc = p.nkc; d.nblocks = p.nblocks; d.kc_split = p.kc_split;
+    d.w = !p.w.empty(); d.wp = !p.wp.empty(); d.w4 = !p.w4.empty(); d.w4h = !p.w4h.empty(); d.wstem = !p.wstem.empty(); d.wd = !p.wd.empty();
+    d.wu = !p.wu.empty(); d.wuf = !p.wuf.empty(); d.wdq = !p.wdq.empty(); d.wuq = !p.wuq.empty(); d.wsq = !p.wsq.empty(); d.wsk = !p.wsk.empty();
+    d.bias_uf = !p.bias_uf.empty(); d.w8x = !p.w8x.empty(); d.w8 = !p.w8.empty(); d.oscale = !p.oscale.empty(); d.bias8 = !p.bias8.empty();
+    d.bias = !p.bias.empty();
+    return d;
 }
 
 // `up` (nearest x2 -> 3x3, 2C -> C) followed by `fuse` (1x1 over concat(up, skip), 2C -> C) with nothing non-linear between

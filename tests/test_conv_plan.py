@@ -1,0 +1,170 @@
+"""The launch rule book (csrc/conv_plan.hpp) on the CPU box: tests/native/conv_plan_dump.cpp (test infrastructure; libire.so includes
+the same header) walks the network's convolutions in schedule order and prints every field of every launch plan, per case and layer
+group.  The expected lines (tests/golden/conv_plan_9e80c0a.txt) are a recording of commit 9e80c0a, not of the code under test: that
+commit's Engine::build_program and Engine::exec_conv text, and its conv_pc_fits / conv_pk_fits loops, were compiled unchanged into a
+scratch harness in which every conv_*_launch, prof_begin / prof_tag and the GroupNorm bookkeeping is a stub that prints what it
+received, the ConvW pointers are named sentinels wherever that commit's packer produces the array, a GroupNorm is always pending (so
+that the launch shows whether the kernel folds it) and 256 CUs stand for the device.  Four locals no stub sees (tile height,
+parts_mul, stats level, ty0) were printed by two lines added to the lifted text.  The recording is kept as it came out.
+
+Cases: default switches on twelve shapes (both sides of the 64-cout split at 512^2 and of both coefficient tables), every switch set
+of tests/test_layers_gpu.py and tests/test_restore_gpu.py plus IRE_PK=1 on two shapes, the fp8 engine with IRE_FP8_MX 1 and 0 on
+three, (64, 512, 512) for the launch conv_pk's table refuses, and first / middle / last row strips of three strip plans.  The comment-only invariants of the old exec_conv are asserted
+separately below, over a wider list (`props`)."""
+import glob
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "native", "conv_plan_dump.cpp")
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+SAN_MARKS = ("ERROR: AddressSanitizer", "runtime error", "LeakSanitizer")
+CUS = 256                                   # what the dump plans for (MI355X)
+COEF_IMGS = {"PK": 4, "PC": None, "PC_HEAD": 64}       # conv_pk.hip PK_IMGS; conv_pc.hip: 64 images at C = 32, 8 at C = 64
+
+
+def _build(tmp, name, flags):
+    exe = str(tmp / name)
+    r = subprocess.run(["g++", "-std=c++17", "-g", "-fno-omit-frame-pointer", "-ffp-contract=off", "-Wall"] + flags + [SRC, "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0 and "warning" not in r.stderr, r.stderr[-3000:]
+    return exe
+
+
+def _run(exe, mode):
+    r = subprocess.run([exe, mode], capture_output=True, text=True, timeout=600)
+    log = r.stdout[-2000:] + r.stderr[-4000:]
+    assert r.returncode == 0 and not r.stderr and not any(m in log for m in SAN_MARKS), log
+    return r.stdout
+
+
+@pytest.fixture(scope="module")
+def dumps(tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("conv_plan")
+    exe, exe_asan = _build(tmp, "cp", ["-O2"]), _build(tmp, "cp_asan", ["-O1", "-fsanitize=address,undefined"])
+    return {"fixture": _run(exe, "fixture"), "fixture_asan": _run(exe_asan, "fixture"), "props": _run(exe, "props")}
+
+
+FIXTURE = os.path.join(GOLDEN, "conv_plan_9e80c0a.txt")
+SCHEDULE = ["stem", "L0.rb1", "L0.rb2", "down0", "L1.rb1", "L1.rb2", "down1", "L2.rb1", "L2.rb2", "down2", "L3.rb1", "L3.rb2",
+            "up2", "fuse2", "up1", "fuse1", "up0", "fuse0", "head"]       # the order in which a case's groups first launch
+
+
+def golden_lines():
+    """Every recorded line as the dump prints it, header first.  The file holds a case whole (`case NAME`, then its lines) or as what
+    differs from an earlier, whole case (`case NAME like BASE`: the lines that differ, with `.` for a value that is the base's; new
+    groups whole; `-GROUP` for a group the case lacks)."""
+    text = open(FIXTURE).read().splitlines()
+    cases = {}
+    for ln in text[1:]:
+        if ln.startswith("case "):
+            w = ln.split(" ")
+            assert len(w) in (2, 4) and w[1] not in cases and (len(w) == 2 or (w[2] == "like" and " like " not in cases[w[3]][0])), ln
+            cur = cases[w[1]] = (ln, dict(cases[w[3]][1]) if len(w) == 4 else {})
+        elif ln.startswith("-"):
+            del cur[1][ln[1:]]
+        else:
+            g, rest = ln.split(" ", 1)
+            assert len(w) == 4 or g not in cur[1], ln
+            if "." in rest.split(" "):
+                rest = " ".join(b if v == "." else v for v, b in zip(rest.split(" "), cur[1][g].split(" ")))
+            cur[1][g] = rest
+    out = [text[0]]
+    for name, (_, groups) in cases.items():
+        assert set(groups) <= set(SCHEDULE), name
+        out += ["%s %s %s" % (name, g, groups[g]) for g in SCHEDULE if g in groups]
+    return out
+
+
+def parse(line, fields=open(FIXTURE).readline().split()[3:]):
+    case, group, rest = line.split(" ", 2)
+    values = rest.split(" ")
+    assert len(values) == len(fields), line
+    return case, group, dict(zip(fields, values))
+
+
+def test_every_plan_equals_the_recorded_parent(dumps):
+    want = golden_lines()
+    assert glob.glob(os.path.join(GOLDEN, "conv_plan_*.txt")) == [FIXTURE]
+    assert want[0].startswith("# case group kernel ") and len(want[0].split()) == 3 + 33
+    got = dumps["fixture"].splitlines()
+    assert got[0] == want[0]
+    want, got = want[1:], got[1:]
+    assert (len({ln.split(" ", 1)[0] for ln in want}), len(want)) == (63, 1028)          # the fixture is the whole recording
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert g == w
+    assert dumps["fixture_asan"] == dumps["fixture"]                                   # under ASan + UBSan: the same lines, no report
+    # no two ops of one group plan differently: one line per (case, group)
+    keys = [tuple(ln.split(" ", 2)[:2]) for ln in want]
+    assert len(set(keys)) == len(keys)
+    # the hand-checkable case: at 512^2 level 2 has 8 x 4 tiles x 1 block x 8 = 256 (not < 256: 128-cout items), level 3 has
+    # 4 x 2 x 2 x 8 = 128 (< 256: the 64-cout split)
+    by = {tuple(ln.split(" ", 2)[:2]): parse(ln)[2] for ln in want}
+    assert (by["default:bf16:1x512x512", "L2.rb1"]["w"], by["default:bf16:1x512x512", "L2.rb1"]["kernel"]) == ("w4", "PK")
+    assert (by["default:bf16:1x512x512", "L3.rb1"]["w"], by["default:bf16:1x512x512", "L3.rb1"]["w4_nt"]) == ("w4h", "64")
+    # both answers of coef_table_fits for conv_pk's table of 4 images: 128-cout items at 512^2 level 2 are 32 per image, an XCD range of a
+    # batch of 8 spans one image, of a batch of 64 eight.  (In the recorded parent no launch of the issue's twelve shapes is refused: 5 and
+    # 8 images of 1024^2 span 2 and 1 images per range, and small images take the 64-cout items; conv_pc's tables of 64 / 8 images hold
+    # every batch up to the engine's limit of 64 images, (12, 32, 48) and (64, 64, 64) included.)
+    assert by["default:bf16:8x512x512", "L2.rb1"]["kernel"] == "PK"
+    l2 = by["default:bf16:64x512x512", "L2.rb1"]
+    assert (l2["kernel"], l2["w"], l2["w4_nt"]) == ("W4", "w4", "0")
+    assert by["default:bf16:5x1024x1024", "L3.rb1"]["kernel"] == "PK" and by["default:bf16:8x1024x1024", "L3.rb1"]["kernel"] == "PK"
+    assert by["default:bf16:12x32x48", "L1.rb1"]["kernel"] == "PC" and by["default:bf16:64x64x64", "L1.rb1"]["kernel"] == "PC"
+
+
+def _case(name):
+    """(switch set, precision, n, h, w, strip, nstrips) of a case name"""
+    env, prec, rest = name.split(":", 2)
+    m = re.fullmatch(r"strip(\d+)of(\d+):(\d+)x(\d+)", rest)
+    if m:
+        s, ns, h, w = map(int, m.groups())
+        return env, prec, 1, h, w, s, ns
+    n, h, w = map(int, rest.split("x"))
+    return env, prec, n, h, w, None, 0
+
+
+def _fits(cap, items_per_img, nimg):
+    """the kernels' rule, restated: the workgroups of XCD group x walk items [items x / X, items (x + 1) / X); none may span more than cap images"""
+    items = items_per_img * nimg
+    X = min(min(items, CUS), 8)
+    return all((hi - 1) // items_per_img - lo // items_per_img + 1 <= cap
+               for lo, hi in ((items * x // X, items * (x + 1) // X) for x in range(X)) if hi > lo)
+
+
+def test_the_comment_only_invariants(dumps):
+    lines = [parse(ln) for ln in dumps["props"].splitlines()[1:]]
+    cases = {c for c, _, _ in lines}
+    assert (len(cases), len(lines)) == (9 * 8 + 1 + 2 + 8 + 4, 87 * 16)
+    plans = {}
+    for c, g, f in lines + [parse(ln) for ln in dumps["fixture"].splitlines()[1:]]:
+        plans.setdefault(_case(c), {})[g] = f
+    checked = {"split": 0, "fits": 0, "strips": 0}
+    for (env, prec, n, h, w, s, ns), groups in plans.items():
+        for g, f in groups.items():
+            # 1. 64- or 128-cout items (and the slabs that go with them): a function of the image's shape alone -- the same for every
+            #    batch size, and for a strip the same as for its whole image
+            if env == "default" and prec == "bf16" and (1, h, w, None, 0) in [k[2:] for k in plans if k[:2] == (env, prec)]:
+                one = plans[env, prec, 1, h, w, None, 0][g]
+                if s is not None or n <= 8:
+                    assert (f["w4_nt"], f["w"] in ("w4", "w4h") and f["w"]) == (one["w4_nt"], one["w"] in ("w4", "w4h") and one["w"]), (env, n, h, w, s, g)
+                    checked["split"] += 1
+            # 2. conv_pk / conv_pc get only what their coefficient table holds
+            if f["kernel"] in COEF_IMGS:
+                cap = COEF_IMGS[f["kernel"]] or (64 if f["cout"] == "32" else 8)
+                assert _fits(cap, int(f["tiles_x"]) * int(f["tiles_y"]) * int(f["nblocks"]), n), (env, n, h, w, g)
+                checked["fits"] += 1
+            # 3. a strip's tiles land at their global tile offset, and the finalize is told the whole image's count
+            if s is not None and f["stats_level"] != "-1":
+                whole = plans[env, prec, 1, h, w, None, 0][g]
+                y0 = s * (h // ns)
+                assert int(f["ty0"]) == (y0 >> int(f["stats_level"])) // int(f["tile_h"])
+                assert int(f["stats_off"]) == int(f["ty0"]) * int(f["tiles_x"]) * 16 * int(f["parts_mul"])
+                assert (f["stat_parts"], f["tile_h"], f["tiles_x"], f["parts_mul"]) == (whole["stat_parts"], whole["tile_h"], whole["tiles_x"], whole["parts_mul"])
+                assert int(f["tiles_y"]) * ns == int(whole["tiles_y"])
+                checked["strips"] += 1
+    assert min(checked.values()) > 100, checked

@@ -100,7 +100,7 @@ __global__ __launch_bounds__(DQ_THREADS) void conv_dnq_kernel(ConvArgs a) {
     const int NKC = a.nkc;                                   // 32-channel chunks of Cin; a stage = (chunk, phase)
     const int Cin = a.cin0;
     const int tiles_per_img = a.tiles_x * a.tiles_y;
-    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, C / NT, 4 * NKC);          // stage index within an item = phase * NKC + kc (PHASE-major: below)
+    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, C / NT, 4 * NKC, (int)gridDim.x, (int)blockIdx.x, a.walk_rev != 0);          // stage index within an item = phase * NKC + kc (PHASE-major: below)
     const int n_items = cursor.my_items, S = cursor.S;
     if (S == 0) return;
 

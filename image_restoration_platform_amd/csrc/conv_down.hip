@@ -87,7 +87,7 @@ __global__ __launch_bounds__(DN_THREADS) void conv_down_kernel(ConvArgs a) {
 
     const int tiles_per_img = a.tiles_x * a.tiles_y;
     const int nkc = a.nkc;                                // 32-channel chunks of Cin
-    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, a.nblocks, 4 * nkc);      // stage index within an item = kc*4 + phase
+    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, a.nblocks, 4 * nkc, (int)gridDim.x, (int)blockIdx.x, a.walk_rev != 0);      // stage index within an item = kc*4 + phase
     const int my_items = cursor.my_items;
     const int S = cursor.S;
     if (S == 0) return;

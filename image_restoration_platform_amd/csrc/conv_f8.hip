@@ -89,7 +89,7 @@ __global__ __launch_bounds__(F8_THREADS) void conv_f8_kernel(ConvArgs a) {
 
     const int tiles_per_img = a.tiles_x * a.tiles_y;
     const int nkc = a.nkc;                                // 32-channel stages per item (4 or 8: even)
-    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, a.nblocks, nkc);
+    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, a.nblocks, nkc, (int)gridDim.x, (int)blockIdx.x, a.walk_rev != 0);
     const int my_items = cursor.my_items;
     const int S = cursor.S;
     if (S == 0) return;

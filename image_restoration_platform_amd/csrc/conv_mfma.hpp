@@ -85,6 +85,7 @@ struct ConvArgs {
     int w4_nt;                   // conv_w4 cout block: 128 (default, 0) or 64 (launches whose 128-cout items would leave CUs idle; a.w = the 64-cout slabs)
     const void* zeros;           // conv_upq.hip: >= 16 bytes of zeros (what a DMA lane outside the image fetches)
     unsigned long long* stamps;  // diagnostic builds only (IRE_RB_ABLATE, DBG bit 16): s_memtime stamps, else null
+    int walk_rev;                // persist.hpp: 1 = the workgroups hand out their items last item first (set per launch by Engine::exec_conv)
 };
 
 void conv_launch(ConvKind kind, const ConvArgs& a, hipStream_t stream);

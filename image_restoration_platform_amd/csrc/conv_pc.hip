@@ -158,7 +158,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
 #endif
     };
     const int tiles_per_img = a.tiles_x * a.tiles_y;
-    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, K::NBLK, NKC);   // item = (tile, 64-cout block); a cursor step is one 32-channel stage
+    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, K::NBLK, NKC, (int)gridDim.x, (int)blockIdx.x, a.walk_rev != 0);   // item = (tile, 64-cout block); a cursor step is one 32-channel stage
     const int n_items = cursor.my_items;
     if (n_items == 0) return;
     const int n_stages = n_items * NKC;

@@ -148,7 +148,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
     const int r = lane & 31, h = lane >> 5;
 
     const int tiles_per_img = a.tiles_x * a.tiles_y;
-    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, NBLK, NKC);
+    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, NBLK, NKC, (int)gridDim.x, (int)blockIdx.x, a.walk_rev != 0);
     const int n_items = cursor.my_items, S = cursor.S;
     if (S == 0) return;
     // diagnostic build (-DPK_TICKS, tools/r04_pkstamps.sh): s_memtime stamps of consumer wave 0 (role 0) and producer wave 8 (role 1) of

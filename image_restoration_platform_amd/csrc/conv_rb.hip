@@ -139,7 +139,7 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
 
     // ---- persistent work assignment (persist.hpp: XCD-aware, advanced by additions instead of per-stage divisions) ----
     const int tiles_per_img = a.tiles_x * a.tiles_y;
-    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, a.nblocks, a.nkc);
+    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, a.nblocks, a.nkc, (int)gridDim.x, (int)blockIdx.x, a.walk_rev != 0);
     const int nkc = a.nkc;
     const int S = cursor.S;                                      // stages this workgroup runs
     if (S == 0) return;

@@ -16,6 +16,7 @@
 //   * epilogue as conv_pc's: accumulators start at the bias, bf16 stores straight from the accumulators, GroupNorm partial
 //     statistics (8 groups of 4 channels) of the stored values per tile
 #include "conv_mfma.hpp"
+#include "persist.hpp"
 
 #include <type_traits>
 
@@ -81,15 +82,13 @@ __global__ __launch_bounds__(ST_THREADS) void conv_stem_kernel(ConvArgs a) {
         srel[it] = (spy[it] * a.Win + spx[it]) * 3 + (sb[it] - spx[it] * 3);        // byte offset from the tile's first halo pixel
     }
 
-    const int tiles_per_img = a.tiles_x * a.tiles_y, total = tiles_per_img * a.nimg;
+    const int tiles_per_img = a.tiles_x * a.tiles_y;
     const unsigned char* in = reinterpret_cast<const unsigned char*>(a.in0);
     const bf16x2_t ones = __builtin_bit_cast(bf16x2_t, 0x3f803f80u);
     unsigned pv[ST_ITERS];
-    auto request = [&](int item) {                  // the tile's bytes -> pv (zero outside the image)
-        const int img = item / tiles_per_img, t = item - img * tiles_per_img;
-        const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
-        const int iy0 = ty * ST_TH - 1, ix0 = tx * ST_TW - 1;
-        const long long base = (((long long)img * a.in_rows + iy0 + a.in_row_off) * a.Win + ix0) * 3;      // (may point before the buffer: only used where ok)
+    auto request = [&](const PersistItem& ri) {     // the tile's bytes -> pv (zero outside the image)
+        const int iy0 = ri.ty * ST_TH - 1, ix0 = ri.tx * ST_TW - 1;
+        const long long base = (((long long)ri.img * a.in_rows + iy0 + a.in_row_off) * a.Win + ix0) * 3;      // (may point before the buffer: only used where ok)
 #pragma unroll
         for (int it = 0; it < ST_ITERS; ++it) {
             const bool ok = spy[it] < ST_IH && (unsigned)(iy0 + spy[it] - a.iy_lo) < (unsigned)a.iy_span && (unsigned)(ix0 + spx[it]) < (unsigned)a.Win;
@@ -98,15 +97,19 @@ __global__ __launch_bounds__(ST_THREADS) void conv_stem_kernel(ConvArgs a) {
         }
     };
     int par = 0;
-    if ((int)blockIdx.x < total) request(blockIdx.x);
-    for (int item = blockIdx.x; item < total; item += gridDim.x) {
-        const int img = item / tiles_per_img, t = item - img * tiles_per_img;
-        const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+    // items (tiles) are dealt and walked as in every persistent conv kernel (persist.hpp: an XCD group sweeps one eighth of the range,
+    // in the direction the launch asks for); one stage per item
+    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, 1, 1, (int)gridDim.x, (int)blockIdx.x, a.walk_rev != 0);
+    const int n_items = cursor.my_items;
+    PersistItem nx = cursor.cur.it;
+    if (n_items > 0) request(nx);
+    for (int k = 0; k < n_items; ++k) {
+        const int img = nx.img, t = nx.tile, ty = nx.ty, tx = nx.tx;
         unsigned short* tl = tile[par];
 #pragma unroll
         for (int it = 0; it < ST_ITERS; ++it)
             if (spy[it] < ST_IH) tl[spy[it] * ST_ROW + spx[it] * 4 + (sb[it] - spx[it] * 3)] = (unsigned short)(__builtin_bit_cast(unsigned, (float)pv[it]) >> 16);      // u8 -> bf16: exact
-        if (item + (int)gridDim.x < total) request(item + gridDim.x);      // in flight across this tile's arithmetic and stores
+        if (k + 1 < n_items) { nx = cursor.next().it; request(nx); }      // in flight across this tile's arithmetic and stores
         __syncthreads();                               // tile[par] is staged (its previous readers passed the barrier of the tile before last)
         // ---- per pixel row: two MFMAs, then stores + GroupNorm partials (groups of 4 channels: a lane's 8 contiguous couts are two groups) ----
         const int ox = tx * ST_TW + r;

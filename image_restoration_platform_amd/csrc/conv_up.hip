@@ -102,7 +102,7 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
     const int c8_fixed = tid & 3;
 
     // ---- persistent work assignment (persist.hpp) ---------------------------------------------------------------
-    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, a.nblocks, a.nkc);
+    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, a.nblocks, a.nkc, (int)gridDim.x, (int)blockIdx.x, a.walk_rev != 0);
     const int my_items = cursor.my_items;
     const int nkc = a.nkc;                               // 32-channel stages per item (>= 2, even)
     const int S = cursor.S;

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(UQ_THREADS) void conv_upq_kernel(ConvArgs a) {
     const int NST = NKC;                                     // (the skip term's k-steps ride at the end of the main stages: below)
     const int Cin = a.cin0;
     const int tiles_per_img = a.tiles_x * a.tiles_y;
-    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, 4, NST);          // it.nb = output parity pa * 2 + pb
+    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, 4, NST, (int)gridDim.x, (int)blockIdx.x, a.walk_rev != 0);          // it.nb = output parity pa * 2 + pb
     const int n_items = cursor.my_items, S = cursor.S;
     if (S == 0) return;
 

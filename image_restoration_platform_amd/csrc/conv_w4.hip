@@ -124,7 +124,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
 
     // ---- persistent work assignment (persist.hpp) ---------------------------------------------------------------
     const int tiles_per_img = a.tiles_x * a.tiles_y;
-    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, a.nblocks, a.nkc);
+    PersistCursor cursor(a.tiles_x, a.tiles_y, a.nimg, a.nblocks, a.nkc, (int)gridDim.x, (int)blockIdx.x, a.walk_rev != 0);
     const int my_items = cursor.my_items;
     const int nkc = a.nkc;                         // 16-channel stages per item
     const int S = cursor.S;

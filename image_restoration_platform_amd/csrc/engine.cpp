@@ -59,6 +59,7 @@ Engine::Engine(const ire_config& cfg) {
     flags_ = cfg.flags;
     sw_ = ConvSwitches::from_env();
     cus_ = persistent_grid_cus();
+    if (const char* v = std::getenv("IRE_SNAKE")) snake_ = std::atoi(v) != 0;
     if (const char* v = std::getenv("IRE_RB_STAMPS")) {   // diagnostic: "<cout>[r]" = stamp the first such ResBlock conv
         stamps_cout_ = std::atoi(v);
         stamps_resid_ = std::strchr(v, 'r') != nullptr;
@@ -662,6 +663,10 @@ void Engine::exec_conv(Run& R, const Op& op, const Geo& g) {
     // ping-pong: this conv may still be reading R.stats in its folded finalize
     if (op.stats_out) a.stats = (R.stats_alt ? R.stats_alt : R.stats) + p.stats_offset();
     a.prio_young = sw_.prio_young;
+    // walk order (persist.hpp): the first conv of a pass forward, every later one against the conv before it on this stream, so that it
+    // starts on the rows the Infinity Cache still holds.  The v1 template has no cursor: it walks forward whatever is asked.
+    a.walk_rev = R.snake && R.next_rev && p.kernel != K_V1;
+    R.next_rev = !a.walk_rev;
     const bool rb = d.kind == CONV_RB1 || d.kind == CONV_RB2;
     if (stamps_dev_ && rb && d.cout == stamps_cout_ && (d.kind == CONV_RB2) == stamps_resid_ && (!stamps_taken_ || !stamps_tl_.empty() || std::getenv("IRE_STAMPS_RAW"))) {
         a.stamps = stamps_dev_;
@@ -733,6 +738,7 @@ void Engine::exec_op(Run& R, const Op& op, const Geo& g) {
 void Engine::run_network(Lane& L, int nimg, int h, int w, const uint8_t* d_in, uint8_t* d_out, const float* d_film) {
     Run R;
     R.stream = L.stream; R.stats = L.stats; R.stats_alt = L.stats2; R.ab = L.ab; R.film = d_film;
+    R.snake = snake_;
     const Geo g = geo_of_lane(L, nimg, h, w, d_in, d_out);
     // inside one pass of the op list a profiled launch's end event is the next one's start (prof_begin): nothing but the
     // engine's own wrapped launches goes onto the stream here.  Everywhere else (copies, host syncs between calls) records

@@ -99,6 +99,8 @@ struct Run {
     const GNW* gn_pending = nullptr;  // a GroupNorm whose finalize was deferred to its consumer (exec_op GN -> exec_conv)
     const float* gn_stats = nullptr;  // its partials and their count per image
     int gn_parts = 0;
+    bool snake = false;               // whole-batch passes: consecutive convs walk their items in opposite directions (row strips: all forward)
+    bool next_rev = false;            // direction of the next cursor-driven conv on this stream
 };
 // where one executor instance's rows live: a whole batch (halo = 0) or one row strip of one image (halo = 1)
 struct Geo {
@@ -244,6 +246,7 @@ private:
     int precision_ = IRE_PRECISION_BF16;
     ConvSwitches sw_;             // the A/B schedule switches, read from the environment once (conv_plan.hpp)
     int cus_ = 256;               // persistent_grid_cus(), read once
+    bool snake_ = true;           // IRE_SNAKE (A/B switch, read once): 0 = every conv launch walks its items forward
     std::mutex mu_;
     hipStream_t main_stream_ = nullptr;
     hipEvent_t ev_[4] = {};

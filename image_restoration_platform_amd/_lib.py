@@ -7,6 +7,7 @@ LIB_PATH = os.environ.get("IRE_LIB") or os.path.join(HERE, "lib", "libire.so")  
 
 IRE_OK, IRE_ERR_INVALID_INPUT, IRE_ERR_TIMEOUT, IRE_ERR_UNAVAILABLE, IRE_ERR_INTERNAL = range(5)
 IRE_FLAG_RESULT_PNG_BASE64 = 1
+IRE_FLAG_RESULT_PNG_DEFLATE = 4
 IRE_ABI_VERSION = 3      # include/ire.h; load() refuses a library of another version (tests/test_abi.py cross-checks the three copies)
 
 
@@ -58,6 +59,9 @@ SYMBOLS = {
     "ire_png_base64_bytes_fit": (ctypes.c_size_t, [_i, _i]),
     "ire_encode_png_base64_fit_device": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     "ire_encode_png_base64_fit": (_i, [_vp, _u8p, _i, _i, _i, _u8p, ctypes.c_size_t]),
+    "ire_png_deflate_base64_bound": (ctypes.c_size_t, [_i, _i]),
+    "ire_encode_png_deflate_base64_fit_device": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp]),
+    "ire_encode_png_deflate_base64_fit": (_i, [_vp, _u8p, _i, _i, _i, _u8p, ctypes.c_size_t, _vp]),
     "ire_submit_fit": (_i, [_vp, _u8p, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
     "ire_submit": (_i, [_vp, _u8p, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
     "ire_restore_tiled_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -72,6 +76,7 @@ SYMBOLS = {
     "ire_strips_get_output": (_i, [_vp, _vp, _vp]),
     "ire_get_stats": (_i, [_vp, ctypes.POINTER(IreEngineStats)]),
     "ire_poll": (_i, [_vp, _vp, _i, _u8p, _vp, ctypes.POINTER(IreTimings)]),
+    "ire_poll_text": (_i, [_vp, _vp, _i, _u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), _vp, ctypes.POINTER(IreTimings)]),
     "ire_job_release": (_i, [_vp, _vp]),
     "ire_affinity_plan": (_i, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32),
                                ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),

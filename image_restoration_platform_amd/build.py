@@ -45,6 +45,7 @@ SOURCES = [
     ("fusion.hip", (["-DFUSE_FL=" + os.environ["FUSE_FL"]] if os.environ.get("FUSE_FL") else [])),
     ("preprocess.hip", []),
     ("encode.hip", []),
+    ("deflate.hip", []),
     ("engine.cpp", []),
     ("strips.cpp", []),
     ("api.cpp", []),

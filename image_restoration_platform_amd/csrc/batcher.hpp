@@ -39,6 +39,8 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "errors.hpp"
@@ -100,6 +102,17 @@ struct BatchSlot {
 //   void wait_compute(SlotBufs&) noexcept;                     blocks until it has
 //   void wait_done(SlotBufs&, ire_timings&);                   blocks until pin_out / pin_sc are complete; throws Error
 //   void drain() noexcept;                                     after a failed launch: nothing enqueued may still touch a slot
+// OPTIONAL (detected at compile time; a backend without it delivers out_bytes(h, w) bytes from the start of a result's place):
+//   const uint8_t* result_view(const uint8_t* place, int h, int w, size_t* len) const;
+//                                                              a result whose size depends on the data: where its payload starts inside
+//                                                              its out_bytes(h, w)-sized place and how long it really is
+template <class B, class = void>
+struct has_result_view : std::false_type {};
+template <class B>
+struct has_result_view<B, std::void_t<decltype(std::declval<const B&>().result_view((const uint8_t*)nullptr, 0, 0, (size_t*)nullptr))>> : std::true_type {};
+
+constexpr int kPollTooSmall = -2;     // Batcher::poll: the caller's buffer is shorter than the result; the job stays pending
+
 template <class Backend>
 class Batcher {
   public:
@@ -176,6 +189,12 @@ class Batcher {
     // Wait up to timeout_ms (< 0: forever).  Returns IRE_OK (outputs filled, job finished), IRE_ERR_TIMEOUT (job still pending:
     // poll again or release) or the job's failure status (*err_out = its message; job finished).
     int poll(const std::shared_ptr<Job>& j, int timeout_ms, uint8_t* out_rgb, double* scores_out, ire_timings* t, std::string* err_out) {
+        return poll(j, timeout_ms, out_rgb, (size_t)-1, nullptr, scores_out, t, err_out);
+    }
+
+    // The same with the size of the caller's buffer and the result's real length (*len_out, may be null).  A result longer than cap
+    // is not copied: kPollTooSmall, *len_out says what is needed, the job stays pending (nothing is lost to a short buffer).
+    int poll(const std::shared_ptr<Job>& j, int timeout_ms, uint8_t* out_rgb, size_t cap, size_t* len_out, double* scores_out, ire_timings* t, std::string* err_out) {
         BatchSlot* S = nullptr;
         {
             std::unique_lock<std::mutex> lk(mu_);
@@ -191,8 +210,16 @@ class Batcher {
         const int st = j->status;
         if (st == IRE_OK) {
             const size_t ob = be_.out_bytes(j->h, j->w);
-            // the ONE host copy of the output: pinned slot -> caller's buffer, in the caller's thread
-            if (out_rgb) std::memcpy(out_rgb, S ? S->b.pin_out + ob * j->idx : j->out.data(), ob);
+            const uint8_t* src = S ? S->b.pin_out + ob * j->idx : j->out.data();
+            size_t len = ob;
+            if constexpr (has_result_view<Backend>::value) src = be_.result_view(src, j->h, j->w, &len);
+            if (len_out) *len_out = len;
+            if (len > cap) {
+                if (S) { std::lock_guard<std::mutex> lk(mu_); S->reading -= 1; qcv_.notify_all(); }
+                return kPollTooSmall;
+            }
+            // the ONE host copy of the output: pinned slot -> caller's buffer, in the caller's thread; only the real length moves
+            if (out_rgb) std::memcpy(out_rgb, src, len);
             if (scores_out) std::memcpy(scores_out, j->scores, sizeof(double) * 7);
             if (t) *t = j->t;
         } else if (err_out) *err_out = j->err;

@@ -4,6 +4,7 @@
 // (server-node/src/clients/geminiClient.js:32-97).
 #include "engine.hpp"
 #include "encode.hpp"
+#include "deflate.hpp"
 
 #include <chrono>
 #include <cmath>
@@ -55,7 +56,9 @@ Engine::Engine(const ire_config& cfg) {
     if (max_batch_ > 64) fail(IRE_ERR_INVALID_INPUT, "invalid max_batch (1..64)");
     num_lanes_ = cfg.num_streams > 0 ? cfg.num_streams : 1;
     if (num_lanes_ > 16) num_lanes_ = 16;
-    if (cfg.flags & ~(uint32_t)IRE_FLAG_RESULT_PNG_BASE64) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
+    if (cfg.flags & ~(uint32_t)(IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
+    if ((cfg.flags & IRE_FLAG_RESULT_PNG_BASE64) && (cfg.flags & IRE_FLAG_RESULT_PNG_DEFLATE))
+        fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");
     flags_ = cfg.flags;
     sw_ = ConvSwitches::from_env();
     cus_ = persistent_grid_cus();
@@ -376,6 +379,64 @@ void Engine::encode_png_base64_fit_host(const uint8_t* rgb, int n, int h, int w,
     if (!rgb || !chars) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder: null buffer");
     if (n < 1 || n > max_batch_ || h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images, 1..8192 per side)");
     encode_host_impl(rgb, n, h, w, chars, stride);
+}
+
+// ---- the compressing encoder (deflate.hip): the same window, texts of data-dependent length and their counts -------------------------
+void Engine::ensure_enc_scratch(size_t need, size_t full) {
+    if (need <= enc_scratch_cap_) return;
+    IRE_HIP(hipDeviceSynchronize());
+    if (d_enc_scratch_) IRE_HIP(hipFree(d_enc_scratch_));
+    d_enc_scratch_ = nullptr; enc_scratch_cap_ = 0;
+    const size_t want = full <= ((size_t)256 << 20) ? full : need;       // a whole batch of this shape when that is small
+    d_enc_scratch_ = (uint8_t*)dalloc(want);
+    enc_scratch_cap_ = want;
+}
+
+void Engine::encode_deflate_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, uint8_t* d_lens,
+                                   size_t lens_pitch, hipStream_t s) {
+    if (stride < png_deflate_base64_bound(h, w)) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the PNG encoder: smaller than ire_png_deflate_base64_bound(h, w)");
+    if (row_pitch < (size_t)3 * w || (n > 1 && image_pitch < row_pitch * (size_t)(h - 1) + (size_t)3 * w))
+        fail(IRE_ERR_INVALID_INPUT, "invalid pitch for the PNG encoder: rows or images overlap");
+    ensure_enc_scratch(png_deflate_scratch_bytes(n, h, w), png_deflate_scratch_bytes(max_batch_, h, w));
+    encode_png_deflate_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_enc_scratch_, d_chars, stride, d_lens, lens_pitch, s);
+}
+
+void Engine::encode_png_deflate_base64_fit_device(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride,
+                                                  uint64_t* d_lens, hipStream_t s) {
+    if (!d_rgb || !d_chars || !d_lens || n < 1 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images)");
+    if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder: height and width must be in 1..8192");
+    encode_deflate_window(d_rgb, n, h, w, row_pitch, image_pitch, d_chars, stride, reinterpret_cast<uint8_t*>(d_lens), sizeof(uint64_t), s);
+}
+
+// pixels up, [count | text] per image down in ONE copy: the host learns the lengths from the D2H that carries the text
+void Engine::encode_png_deflate_base64_fit_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride, uint64_t* lens) {
+    if (!rgb || !chars || !lens) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder: null buffer");
+    if (n < 1 || n > max_batch_ || h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images, 1..8192 per side)");
+    const size_t ib = (size_t)h * w * 3, cb = png_deflate_base64_bound(h, w), cpad = (cb + 8 + 255) / 256 * 256;
+    if (stride < cb) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the PNG encoder: smaller than ire_png_deflate_base64_bound(h, w)");
+    const size_t in_pad = (ib * n + 255) / 256 * 256;
+    const size_t need = in_pad + cpad * (size_t)n;
+    if (need > enc_io_cap_) {
+        IRE_HIP(hipDeviceSynchronize());
+        if (d_enc_io_) IRE_HIP(hipFree(d_enc_io_));
+        d_enc_io_ = nullptr; enc_io_cap_ = 0;
+        d_enc_io_ = (uint8_t*)dalloc(need);
+        enc_io_cap_ = need;
+    }
+    hipStream_t s = main_stream_;
+    IRE_HIP(hipMemcpyAsync(d_enc_io_, rgb, ib * n, hipMemcpyHostToDevice, s));
+    uint8_t* d_txt = d_enc_io_ + in_pad;
+    encode_deflate_window(d_enc_io_, n, h, w, (size_t)3 * w, ib, d_txt + 8, cpad, d_txt, cpad, s);
+    std::vector<uint8_t> stage(cpad * (size_t)n);
+    IRE_HIP(hipMemcpyAsync(stage.data(), d_txt, cpad * (size_t)n, hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < n; ++i) {
+        uint64_t len = 0;
+        std::memcpy(&len, stage.data() + cpad * i, 8);
+        if (len > cb) fail(IRE_ERR_INTERNAL, "internal: the PNG encoder reported a length beyond its bound");
+        lens[i] = len;
+        std::memcpy(chars + stride * i, stage.data() + cpad * i + 8, (size_t)len);
+    }
 }
 
 void Engine::free_workspace() {
@@ -873,6 +934,12 @@ void Engine::restore_fit_device(const uint8_t* d_rgb, int n, int h, int w, const
     crop_window_launch(d_pad_out_, n, fit_dim(h), fit_dim(w), d_out, h, w, stream);
 }
 
+// the batcher's results as text: the stored PNG's characters, or with IRE_FLAG_RESULT_PNG_DEFLATE [uint64 count | characters] per result
+void Engine::encode_result(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_txt, size_t txt_stride, hipStream_t s) {
+    if (flags_ & IRE_FLAG_RESULT_PNG_DEFLATE) encode_deflate_window(d_rgb, n, h, w, row_pitch, image_pitch, d_txt + 8, txt_stride, d_txt, txt_stride, s);
+    else encode_window(d_rgb, n, h, w, row_pitch, image_pitch, d_txt, txt_stride, s);
+}
+
 void Engine::restore_fit_device_mixed(const uint8_t* d_rgb, int n, int h, int w, const double* host_scores, const uint8_t* has_scores,
                                       const uint8_t* d_is_jpeg, uint8_t* d_out, uint8_t* d_txt, size_t txt_stride, hipStream_t stream) {
     check_fit(n, h, w);
@@ -889,12 +956,12 @@ void Engine::restore_fit_device_mixed(const uint8_t* d_rgb, int n, int h, int w,
     }
     if (aligned) {
         restore_device(d_rgb, n, h, w, d_sc, d_is_jpeg, d_out, stream);
-        if (d_txt) encode_window(d_out, n, h, w, (size_t)3 * w, (size_t)3 * w * h, d_txt, txt_stride, stream);
+        if (d_txt) encode_result(d_out, n, h, w, (size_t)3 * w, (size_t)3 * w * h, d_txt, txt_stride, stream);
         return;
     }
     const int H = fit_dim(h), W = fit_dim(w);
     restore_padded(d_rgb, n, h, w, d_sc, d_is_jpeg, stream);
-    if (d_txt) encode_window(d_pad_out_, n, h, w, (size_t)3 * W, (size_t)3 * W * H, d_txt, txt_stride, stream);     // the crop costs no pass of its own
+    if (d_txt) encode_result(d_pad_out_, n, h, w, (size_t)3 * W, (size_t)3 * W * H, d_txt, txt_stride, stream);     // the crop costs no pass of its own
     else crop_window_launch(d_pad_out_, n, H, W, d_out, h, w, stream);
 }
 

@@ -40,6 +40,10 @@ export function bindIre(libPath) {
     ire_submit_fit: ['int', [P, P, 'int', 'int', 'int', P, PP]],
     ire_submit: ['int', [P, P, 'int', 'int', 'int', P, PP]],
     ire_poll: ['int', [P, P, 'int', P, P, P]],
+    ire_poll_text: ['int', [P, P, 'int', P, 'size_t', P, P, P]],
+    ire_png_deflate_base64_bound: ['size_t', ['int', 'int']],
+    ire_encode_png_deflate_base64_fit_device: ['int', [P, P, 'int', 'int', 'int', 'size_t', 'size_t', P, 'size_t', P, P]],
+    ire_encode_png_deflate_base64_fit: ['int', [P, P, 'int', 'int', 'int', P, 'size_t', P]],
     ire_job_release: ['int', [P, P]],
     ire_affinity_plan: ['int', ['string', 'string', P, 'size_t', IP, IP, IP]],
     ire_engine_affinity: ['int', [P, P, 'size_t', IP]],

@@ -69,6 +69,8 @@ def encode_jpeg_base64(rgb, quality=85):
 #   jpeg        host PIL JPEG q85 4:4:4 (the reference's own settings where it encodes: imagePreprocess.js:57-64): ~15 ms
 #   png-device  a PNG of stored deflate blocks + its base64 text written by the GPU (csrc/encode.hip): no host codec work at all;
 #               with an engine created with IRE_FLAG_RESULT_PNG_BASE64 the batcher hands the text back instead of pixels
+#   png-deflate-device  a COMPRESSED PNG (Paeth filter, Huffman-coded deflate blocks) + its base64 text written by the GPU
+#               (csrc/deflate.hip): no host codec work either, and a shorter string; the engine flag is IRE_FLAG_RESULT_PNG_DEFLATE
 RESULT_CODEC = os.environ.get("IRE_RESULT_CODEC", "png")
 
 
@@ -138,6 +140,8 @@ class EngineRestorer:
             return encode_jpeg_base64(result)
         if self.result_codec == "png-device":
             return self.engine.encode_png_base64_fit(result).decode("ascii")      # any width: the device encoder
+        if self.result_codec == "png-deflate-device":
+            return self.engine.encode_png_deflate_base64_fit(result).decode("ascii")
         return encode_png_base64(result)
 
     @staticmethod
@@ -156,7 +160,7 @@ class EngineRestorer:
         shapes = {d[0].shape for d in decoded}
         if len(shapes) != 1:
             raise ValueError("invalid images: fusion views must have identical dimensions")
-        text_engine = bool(getattr(self.engine, "_flags", 0) & _lib.IRE_FLAG_RESULT_PNG_BASE64)      # ire_poll returns the text
+        text_engine = bool(getattr(self.engine, "_flags", 0) & (_lib.IRE_FLAG_RESULT_PNG_BASE64 | _lib.IRE_FLAG_RESULT_PNG_DEFLATE))      # poll returns the text
         if len(decoded) == 1:
             # one image of any size is ONE job of the engine's batcher (ire_submit_fit): the engine pads on the device, classifies
             # the image's own pixels in the same batch when analyze() did not, and hands back the h x w window -- on a flagged
@@ -176,7 +180,7 @@ class EngineRestorer:
         restored = []
         for job, h, w in jobs:
             out, _, _ = self.engine.poll(job)
-            if text_engine:                                               # fusion needs the views' pixels: decode the stored PNG (a memcpy-speed inflate)
+            if text_engine:                                               # fusion needs the views' pixels: decode the device's PNG
                 out = decode_image(base64.b64decode(out))[0]
             restored.append(np.ascontiguousarray(out[:h, :w]))
         views = np.stack(restored, axis=0)

@@ -44,7 +44,8 @@ def get_service():
             try:
                 from ..restorator import RESULT_CODEC
                 # IRE_RESULT_CODEC=png-device: the batcher returns the base64 text of a device-encoded PNG (csrc/encode.hip)
-                eng = Engine(device_index=0, max_batch=8, flags=1 if RESULT_CODEC == "png-device" else 0)
+                # IRE_RESULT_CODEC=png-deflate-device: the text of a compressed PNG (csrc/deflate.hip), fetched with ire_poll_text
+                eng = Engine(device_index=0, max_batch=8, flags={"png-device": 1, "png-deflate-device": 4}.get(RESULT_CODEC, 0))
             except Exception as e:  # noqa: BLE001 -- EngineError or a missing library
                 _state["error"] = str(e)
                 raise
@@ -113,7 +114,7 @@ async def restore_batch(request: Request):
     import numpy as np
     import torch
     from ..prompt_enhancer import KEYS, PromptEnhancerService
-    from ..restorator import decode_image
+    from ..restorator import RESULT_CODEC, decode_image
     try:
         payload = await request.json()
         bufs = [base64.b64decode(b) for b in payload["images"]]
@@ -148,7 +149,13 @@ async def restore_batch(request: Request):
                 # one engine call per chunk: pad, network and crop on the device; then the result text on the device for every
                 # size (csrc/encode.hip through the extension): the D2H copy carries base64 characters, the host encodes nothing
                 restored = te.restore_fit(x, scores, None)
-                texts = te.encode_png_base64_fit(restored).cpu().numpy()
+                if RESULT_CODEC == "png-deflate-device":        # the compressed PNG (csrc/deflate.hip), through the C ABI's tensor form
+                    get_service()
+                    tx, ln = _state["engine"].encode_png_deflate_base64_fit_tensor(restored.contiguous())
+                    tx, ln = tx.cpu().numpy(), ln.cpu().numpy()
+                    texts = [tx[k, :int(ln[k])] for k in range(len(chunk))]
+                else:
+                    texts = te.encode_png_base64_fit(restored).cpu().numpy()
                 sc = scores.cpu().numpy()
                 t2 = time.time()
             except EngineError as e:

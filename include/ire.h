@@ -79,6 +79,11 @@ typedef struct ire_config {
  * ire_png_base64_bytes_fit(h, w) ASCII characters -- the string restorator.js:108 puts on the wire, with no codec or base64 work
  * left for the host. */
 #define IRE_FLAG_RESULT_PNG_BASE64 1u
+/* The batcher delivers every result as the base64 text of a COMPRESSED PNG file (Paeth-filtered scanlines, Huffman-coded deflate
+ * blocks: ire_encode_png_deflate_base64_fit_device below).  The text's length depends on the pixels: such results are fetched with
+ * ire_poll_text, into a buffer of ire_png_deflate_base64_bound(h, w) bytes.  Bit value 2 is not a flag; setting both result flags
+ * is invalid. */
+#define IRE_FLAG_RESULT_PNG_DEFLATE 4u
 
 
 
@@ -181,6 +186,23 @@ int ire_encode_png_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n,
                                      size_t image_pitch_bytes, uint8_t* d_chars, size_t stride_bytes, void* stream);
 int ire_encode_png_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes);
 
+/* ---- the same result as a COMPRESSED PNG, on the device ----
+ * The file: signature, IHDR, ONE IDAT, IEND.  The IDAT is a zlib stream of the Paeth-filtered scanlines (filter type 4 on every
+ * row): one dynamic-Huffman deflate block per 32 768 filtered bytes, literals only, canonical codes of at most 15 bits built on the
+ * device from the block's own histogram; every block but the last ends with an empty stored block (00 00 FF FF).  No LZ77 matching.
+ * Lossless; every PNG decoder reads it.  The text's length depends on the pixels:
+ * ire_png_deflate_base64_bound: the most characters any h x w image can give -- pure host arithmetic, 0 outside 1..8192; per block
+ * a 1887-bit header, 9 bits per symbol, the marker; sizes every buffer (stride_bytes >= it; nothing is written beyond it).
+ * The encoders read the window as ire_encode_png_base64_fit_device does and write, per image, the text at d_chars + i *
+ * stride_bytes and its character count to lens[i] (uint64).  The bytes are a pure function of the pixels: equal for any batch
+ * size, position, pitch and stream.  The number of stream operations per call does not depend on n; no host round trip. */
+size_t ire_png_deflate_base64_bound(int h, int w);
+int ire_encode_png_deflate_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes,
+                                             size_t image_pitch_bytes, uint8_t* d_chars, size_t stride_bytes,
+                                             uint64_t* d_lens /* n x uint64, device */, void* stream);
+int ire_encode_png_deflate_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes,
+                                      uint64_t* lens /* n x uint64, host */);
+
 /* ---- async batcher (restoreBatch's in-flight promises) ---------------------------------- */
 typedef struct ire_job ire_job;
 /* Queue one h x w image for restoration; jobs of equal shape are coalesced into batches of up
@@ -199,6 +221,14 @@ int ire_submit_fit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg,
  * poll again, or give the job up with ire_job_release.  One thread at a time per handle. */
 int ire_poll(ire_engine* e, ire_job* job, int timeout_ms, uint8_t* out_rgb, double* scores_out,
              ire_timings* t);
+/* ire_poll with a result length: works on every engine.  On IRE_OK `out` holds *len_out bytes: h*w*3 pixel bytes, the
+ * ire_png_base64_bytes_fit(h, w) characters of IRE_FLAG_RESULT_PNG_BASE64, or the real character count of
+ * IRE_FLAG_RESULT_PNG_DEFLATE (at most ire_png_deflate_base64_bound(h, w)).  cap_bytes is the size of `out`: when the result is
+ * longer the call returns IRE_ERR_INVALID_INPUT, sets *len_out to the size needed and leaves the job pending.  Otherwise as
+ * ire_poll.  On an engine with IRE_FLAG_RESULT_PNG_DEFLATE ire_poll itself has nowhere to report a length: it returns
+ * IRE_ERR_INVALID_INPUT ("invalid: use ire_poll_text") and -- the one exception to its rule -- leaves the job pending. */
+int ire_poll_text(ire_engine* e, ire_job* job, int timeout_ms, uint8_t* out, size_t cap_bytes, size_t* len_out,
+                  double* scores_out, ire_timings* t);
 /* Give up a job without fetching its result -- the caller's promise was rejected on a timeout and
  * the retry policy (server-node/src/utils/retry.js:12-47, 3 attempts) will submit the image anew:
  * frees the handle and whatever only it kept alive (its place among a finished batch's unread

@@ -44,13 +44,22 @@ struct DeviceGuard {       // staging is allocated on first use of a shape, poss
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-struct HipSlot {
-    uint8_t *d_in = nullptr, *d_out = nullptr, *d_jp = nullptr, *d_txt = nullptr;      // d_txt: IRE_FLAG_RESULT_PNG_BASE64, the results' text
-    hipEvent_t ev_in = nullptr, ev_c0 = nullptr, ev_c1 = nullptr, ev_cw = nullptr, ev_out = nullptr;
-    // ev_c1 and ev_cw mark the same point (the batch's compute is done): the launcher QUERIES ev_c1 under the batcher's lock while
-    // the completer SLEEPS on ev_cw -- hipEventSynchronize holds the event's own lock for as long as it waits, so a query of the
+// the five events of a slot: created together, destroyed together
+struct SlotEvents {
+    hipEvent_t in = nullptr, c0 = nullptr, c1 = nullptr, cw = nullptr, out = nullptr;
+    // c1 and cw mark the same point (the batch's compute is done): the launcher QUERIES c1 under the batcher's lock while
+    // the completer SLEEPS on cw -- hipEventSynchronize holds the event's own lock for as long as it waits, so a query of the
     // same event from another thread blocks until the batch is done (measured: with one event for both, every submitter stalled
     // behind the launcher for a whole batch and a 16-deep closed loop fell to batches of one, 464 img/s)
+    void create() {       // c0 .. c1 is timed
+        for (hipEvent_t* e : {&c0, &c1}) IRE_HIP(hipEventCreate(e));
+        for (hipEvent_t* e : {&in, &cw, &out}) IRE_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    ~SlotEvents() { for (hipEvent_t e : {in, c0, c1, cw, out}) if (e) (void)hipEventDestroy(e); }
+};
+// the backend's side of a slot: its staging (device_buf.hpp; SlotBufs holds views of the pinned half) and its events
+struct HipSlot : SlotMem<DeviceMem, PinnedMem> {
+    std::unique_ptr<SlotEvents> ev;
 };
 
 // CPU set of this engine's service threads (affinity.hpp): IRE_CPU_AFFINITY = "off" | a cpulist overrides the sysfs plan
@@ -119,109 +128,61 @@ struct HipBatchBackend {
         if (!os) IRE_HIP(hipStreamCreateWithFlags(&os, hipStreamNonBlocking));
     }
     void thread_enter(const char*) { (void)hipSetDevice(device); bind_this_thread(plan); }
-    // Everything new goes into locals first and is committed only when all of it exists: a failure half way (out of pinned
-    // memory at the fifth slot) frees the locals and leaves the slot exactly as it was -- usable at its old capacity, or empty.
+    // Everything new is complete before the slot is touched: a failure half way (out of pinned memory at the fifth slot) leaves the
+    // slot exactly as it was -- usable at its old capacity, or empty.
     void reserve(SlotBufs& b, size_t bytes, int mb) {
         if (b.fixed && bytes <= b.cap) return;
         DeviceGuard g(device);
-        HipSlot nh;
-        uint8_t *pj = nullptr, *pi = nullptr, *po = nullptr, *di = nullptr, *dout = nullptr, *dtxt = nullptr;
-        double *ps = nullptr, *psi = nullptr;
-        const bool want_fixed = !b.fixed, want_img = bytes > b.cap;
-        try {
-            if (want_fixed) {
-                IRE_HIP(hipEventCreateWithFlags(&nh.ev_in, hipEventDisableTiming));
-                IRE_HIP(hipEventCreate(&nh.ev_c0));
-                IRE_HIP(hipEventCreate(&nh.ev_c1));
-                IRE_HIP(hipEventCreateWithFlags(&nh.ev_cw, hipEventDisableTiming));
-                IRE_HIP(hipEventCreateWithFlags(&nh.ev_out, hipEventDisableTiming));
-                IRE_HIP(hipHostMalloc((void**)&pj, (size_t)mb));
-                IRE_HIP(hipHostMalloc((void**)&ps, sizeof(double) * 7 * (size_t)mb));
-                IRE_HIP(hipHostMalloc((void**)&psi, sizeof(double) * 7 * (size_t)mb));
-                IRE_HIP(hipMalloc((void**)&nh.d_jp, (size_t)mb));
-            }
-            if (want_img) {
-                IRE_HIP(hipHostMalloc((void**)&pi, bytes));
-                IRE_HIP(hipHostMalloc((void**)&po, bytes));
-                IRE_HIP(hipMalloc((void**)&di, bytes));
-                IRE_HIP(hipMalloc((void**)&dout, bytes));
-                if (text()) IRE_HIP(hipMalloc((void**)&dtxt, bytes + 256 * (size_t)mb));
-            }
-        } catch (...) {
-            if (nh.ev_in) (void)hipEventDestroy(nh.ev_in);
-            if (nh.ev_c0) (void)hipEventDestroy(nh.ev_c0);
-            if (nh.ev_c1) (void)hipEventDestroy(nh.ev_c1);
-            if (nh.ev_cw) (void)hipEventDestroy(nh.ev_cw);
-            if (nh.ev_out) (void)hipEventDestroy(nh.ev_out);
-            if (pj) (void)hipHostFree(pj);
-            if (ps) (void)hipHostFree(ps);
-            if (psi) (void)hipHostFree(psi);
-            if (nh.d_jp) (void)hipFree(nh.d_jp);
-            if (pi) (void)hipHostFree(pi);
-            if (po) (void)hipHostFree(po);
-            if (di) (void)hipFree(di);
-            if (dout) (void)hipFree(dout);
-            if (dtxt) (void)hipFree(dtxt);
-            throw;
-        }
-        HipSlot* hs = static_cast<HipSlot*>(b.impl);
-        if (!hs) { hs = new HipSlot(); b.impl = hs; }
-        if (want_fixed) {
-            hs->ev_in = nh.ev_in; hs->ev_c0 = nh.ev_c0; hs->ev_c1 = nh.ev_c1; hs->ev_cw = nh.ev_cw; hs->ev_out = nh.ev_out; hs->d_jp = nh.d_jp;
-            b.pin_jp = pj; b.pin_sc = ps; b.pin_sc_in = psi; b.fixed = true;
-        }
-        if (want_img) {
-            if (b.pin_in) { (void)hipHostFree(b.pin_in); (void)hipHostFree(b.pin_out); (void)hipFree(hs->d_in); (void)hipFree(hs->d_out); if (hs->d_txt) (void)hipFree(hs->d_txt); }
-            b.pin_in = pi; b.pin_out = po; hs->d_in = di; hs->d_out = dout; hs->d_txt = dtxt; b.cap = bytes;
-        }
+        std::unique_ptr<HipSlot> fresh(b.impl ? nullptr : new HipSlot());
+        HipSlot& hs = b.impl ? *static_cast<HipSlot*>(b.impl) : *fresh;
+        std::unique_ptr<SlotEvents> ev(b.fixed ? nullptr : new SlotEvents());
+        if (ev) ev->create();
+        hs.reserve(bytes, mb, text());        // the strong guarantee is SlotMem's
+        if (ev) hs.ev = std::move(ev);        // (nothing from here on throws)
+        if (fresh) b.impl = fresh.release();
+        b.pin_in = hs.pin_in.get<uint8_t>(); b.pin_out = hs.pin_out.get<uint8_t>(); b.pin_jp = hs.pin_jp.get<uint8_t>();
+        b.pin_sc = hs.pin_sc.get<double>(); b.pin_sc_in = hs.pin_sc_in.get<double>(); b.cap = hs.cap; b.fixed = hs.fixed;
     }
     void release(SlotBufs& b) noexcept {
         DeviceGuard g(device);
-        HipSlot* hs = static_cast<HipSlot*>(b.impl);
-        if (b.pin_in) { (void)hipHostFree(b.pin_in); (void)hipHostFree(b.pin_out); }
-        if (b.fixed) { (void)hipHostFree(b.pin_jp); (void)hipHostFree(b.pin_sc); (void)hipHostFree(b.pin_sc_in); }
-        if (hs) {
-            if (hs->d_in) { (void)hipFree(hs->d_in); (void)hipFree(hs->d_out); if (hs->d_txt) (void)hipFree(hs->d_txt); }
-            if (hs->ev_in) { (void)hipEventDestroy(hs->ev_in); (void)hipEventDestroy(hs->ev_c0); (void)hipEventDestroy(hs->ev_c1); (void)hipEventDestroy(hs->ev_cw); (void)hipEventDestroy(hs->ev_out); (void)hipFree(hs->d_jp); }
-            delete hs;
-        }
+        delete static_cast<HipSlot*>(b.impl);
         b = SlotBufs{};
     }
     void h2d(SlotBufs& b, size_t off, size_t bytes) {
         HipSlot& hs = *static_cast<HipSlot*>(b.impl);
-        IRE_HIP(hipMemcpyAsync(hs.d_in + off, b.pin_in + off, bytes, hipMemcpyHostToDevice, cs));
+        IRE_HIP(hipMemcpyAsync(hs.d_in.get<uint8_t>() + off, b.pin_in + off, bytes, hipMemcpyHostToDevice, cs));
     }
     void launch(SlotBufs& b, int n, int h, int w, const uint8_t* has_sc) {
         HipSlot& hs = *static_cast<HipSlot*>(b.impl);
         const size_t ib = (size_t)h * w * 3;
-        IRE_HIP(hipMemcpyAsync(hs.d_jp, b.pin_jp, (size_t)n, hipMemcpyHostToDevice, cs));
-        IRE_HIP(hipEventRecord(hs.ev_in, cs));
+        IRE_HIP(hipMemcpyAsync(hs.d_jp.get<uint8_t>(), b.pin_jp, (size_t)n, hipMemcpyHostToDevice, cs));
+        IRE_HIP(hipEventRecord(hs.ev->in, cs));
         hipStream_t ms = E.main_stream();
         on_stream(E, ms, [&] {
-            IRE_HIP(hipStreamWaitEvent(ms, hs.ev_in, 0));
-            IRE_HIP(hipEventRecord(hs.ev_c0, ms));
+            IRE_HIP(hipStreamWaitEvent(ms, hs.ev->in, 0));
+            IRE_HIP(hipEventRecord(hs.ev->c0, ms));
             // classifies the jobs that brought no scores; a shape the network cannot take as it is (ire_submit_fit) is padded into the
             // engine's staging and its window comes back; with text() the results leave the device as text
-            E.restore_fit_device_mixed(hs.d_in, n, h, w, b.pin_sc_in, has_sc, hs.d_jp, hs.d_out, text() ? hs.d_txt : nullptr, (out_bytes(h, w) + 255) / 256 * 256, ms);
+            E.restore_fit_device_mixed(hs.d_in.get<uint8_t>(), n, h, w, b.pin_sc_in, has_sc, hs.d_jp.get<uint8_t>(), hs.d_out.get<uint8_t>(), text() ? hs.d_txt.get<uint8_t>() : nullptr, (out_bytes(h, w) + 255) / 256 * 256, ms);
             IRE_HIP(hipMemcpyAsync(b.pin_sc, E.scores_device(), sizeof(double) * 7 * n, hipMemcpyDeviceToHost, ms));
-            IRE_HIP(hipEventRecord(hs.ev_c1, ms));
-            IRE_HIP(hipEventRecord(hs.ev_cw, ms));
+            IRE_HIP(hipEventRecord(hs.ev->c1, ms));
+            IRE_HIP(hipEventRecord(hs.ev->cw, ms));
         });
-        IRE_HIP(hipStreamWaitEvent(os, hs.ev_c1, 0));
+        IRE_HIP(hipStreamWaitEvent(os, hs.ev->c1, 0));
         if (text()) {
             const size_t ob = out_bytes(h, w), st = (ob + 255) / 256 * 256;
-            for (int i = 0; i < n; ++i) IRE_HIP(hipMemcpyAsync(b.pin_out + ob * i, hs.d_txt + st * i, ob, hipMemcpyDeviceToHost, os));
-        } else IRE_HIP(hipMemcpyAsync(b.pin_out, hs.d_out, ib * n, hipMemcpyDeviceToHost, os));
-        IRE_HIP(hipEventRecord(hs.ev_out, os));
+            for (int i = 0; i < n; ++i) IRE_HIP(hipMemcpyAsync(b.pin_out + ob * i, hs.d_txt.get<uint8_t>() + st * i, ob, hipMemcpyDeviceToHost, os));
+        } else IRE_HIP(hipMemcpyAsync(b.pin_out, hs.d_out.get<uint8_t>(), ib * n, hipMemcpyDeviceToHost, os));
+        IRE_HIP(hipEventRecord(hs.ev->out, os));
     }
-    bool computing(SlotBufs& b) noexcept { return hipEventQuery(static_cast<HipSlot*>(b.impl)->ev_c1) == hipErrorNotReady; }
-    void wait_compute(SlotBufs& b) noexcept { (void)hipEventSynchronize(static_cast<HipSlot*>(b.impl)->ev_cw); }
+    bool computing(SlotBufs& b) noexcept { return hipEventQuery(static_cast<HipSlot*>(b.impl)->ev->c1) == hipErrorNotReady; }
+    void wait_compute(SlotBufs& b) noexcept { (void)hipEventSynchronize(static_cast<HipSlot*>(b.impl)->ev->cw); }
     void wait_done(SlotBufs& b, ire_timings& t) {
         HipSlot& hs = *static_cast<HipSlot*>(b.impl);
-        const hipError_t rc = hipEventSynchronize(hs.ev_out);
+        const hipError_t rc = hipEventSynchronize(hs.ev->out);
         if (rc != hipSuccess) throw Error{IRE_ERR_INTERNAL, std::string("internal: ") + hipGetErrorString(rc)};
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, hs.ev_c0, hs.ev_c1) == hipSuccess) { t.restore_ms = ms; t.total_ms = ms; }
+        if (hipEventElapsedTime(&ms, hs.ev->c0, hs.ev->c1) == hipSuccess) { t.restore_ms = ms; t.total_ms = ms; }
     }
     void drain() noexcept {
         DeviceGuard g(device);

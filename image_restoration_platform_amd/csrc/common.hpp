@@ -29,6 +29,15 @@ inline void hip_check(hipError_t e, const char* what, const char* file, int line
 }
 #define IRE_HIP(expr) ::ire::hip_check((expr), #expr, __FILE__, __LINE__)
 
+struct DeviceMem {      // the two memory policies of device_buf.hpp: out of memory leaves here as the retryable 503 above
+    static void* alloc(size_t bytes) { void* p = nullptr; IRE_HIP(hipMalloc(&p, bytes)); return p; }
+    static void free(void* p) noexcept { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static void* alloc(size_t bytes) { void* p = nullptr; IRE_HIP(hipHostMalloc(&p, bytes)); return p; }
+    static void free(void* p) noexcept { (void)hipHostFree(p); }
+};
+
 template <typename T>
 inline T ceil_div(T a, T b) { return (a + b - 1) / b; }
 

@@ -1,8 +1,15 @@
-// conv_kind.hpp -- the seven convolution kinds and the integers of their v1 weight slabs; no HIP, no device code: shared by the
-// launch interface (conv_mfma.hpp), by the host-only weight packer (weight_pack.hpp) and by the launch rule book (conv_plan.hpp).
+// conv_kind.hpp -- the seven convolution kinds, the integers of their v1 weight slabs and the network's fixed sizes; no HIP, no device
+// code: shared by the launch interface (conv_mfma.hpp), by the host-only weight packer (weight_pack.hpp), by the launch rule book
+// (conv_plan.hpp) and by the buffer tables (device_buf.hpp).
 #pragma once
+#include <cstddef>
 
 namespace ire {
+
+// RestoreNet-v0's fixed sizes: channels per level, and the FiLM vector (a scale and a shift per channel of every level, level l at kFilmOff[l])
+constexpr int kWidths[4] = {32, 64, 128, 256}, kFilmOff[4] = {0, 64, 192, 448}, kFilmDim = 960;
+// floats of GroupNorm partials one h x w image needs at most: [8 groups][2] per 4 x 32-pixel tile of level 0, the smallest tile any producer uses
+inline size_t gn_partials(int h, int w) { return (size_t)((h + 3) / 4) * ((w + 31) / 32) * 16; }
 
 // The seven ways RestoreNet-v0 uses a convolution (DESIGN.md "RestoreNet-v0").
 enum ConvKind {

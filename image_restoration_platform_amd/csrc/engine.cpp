@@ -21,21 +21,11 @@ namespace ire {
 
 namespace {
 
-const int kWidths[4] = {32, 64, 128, 256};
-const int kFilmOff[4] = {0, 64, 192, 448};
-const int kFilmDim = 960;
-
 inline double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 }  // namespace
-
-void* Engine::dalloc(size_t bytes) {
-    void* p = nullptr;
-    IRE_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    return p;
-}
 
 Engine::Engine(const ire_config& cfg) {
     int ndev = 0;
@@ -80,18 +70,17 @@ Engine::Engine(const ire_config& cfg) {
     }
 
     // classifier tables
-    unsigned int* d_lin = (unsigned int*)dalloc(sizeof(kLin16));
-    unsigned int* d_thr = (unsigned int*)dalloc(sizeof(kGreyThr));
-    unsigned char* d_inv = (unsigned char*)dalloc(5008);          // 5001 buckets, padded to whole 16-byte chunks (classifier.hip loads it as uint4)
+    unsigned int* d_lin = tables_mem_.alloc<unsigned int>(sizeof(kLin16));
+    unsigned int* d_thr = tables_mem_.alloc<unsigned int>(sizeof(kGreyThr));
+    unsigned char* d_inv = tables_mem_.alloc<unsigned char>(5008);          // 5001 buckets, padded to whole 16-byte chunks (classifier.hip loads it as uint4)
     IRE_HIP(hipMemset(d_inv, 0, 5008));
-    table_allocs_ = {d_lin, d_thr, d_inv};
     IRE_HIP(hipMemcpy(d_lin, kLin16, sizeof(kLin16), hipMemcpyHostToDevice));
     IRE_HIP(hipMemcpy(d_thr, kGreyThr, sizeof(kGreyThr), hipMemcpyHostToDevice));
     IRE_HIP(hipMemcpy(d_inv, kGreyInv, sizeof(kGreyInv), hipMemcpyHostToDevice));
     tables_ = ClassifierTables{d_lin, d_thr, d_inv};
     if (stamps_cout_) {
-        stamps_dev_ = (unsigned long long*)dalloc(8 * 2 * 64 * 10 * 8);
-        IRE_HIP(hipMemset(stamps_dev_, 0, 8 * 2 * 64 * 10 * 8));
+        stamps_dev_.grow(8 * 2 * 64 * 10 * 8);
+        IRE_HIP(hipMemset(stamps_dev_.get<void>(), 0, 8 * 2 * 64 * 10 * 8));
     }
 
     if (cfg.weights_path && cfg.weights_path[0]) load_weights_file(cfg.weights_path);
@@ -102,17 +91,16 @@ Engine::~Engine() {
     (void)hipDeviceSynchronize();
     if (stamps_dev_ && std::getenv("IRE_STAMPS_RAW")) {     // diagnostic builds with their own stamp layout (conv_pk.hip PK_TICKS): the whole buffer, one value per line
         std::vector<unsigned long long> h(8 * 2 * 64 * 10);
-        (void)hipMemcpy(h.data(), stamps_dev_, h.size() * 8, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(h.data(), stamps_dev_.get<void>(), h.size() * 8, hipMemcpyDeviceToHost);
         if (FILE* f = std::fopen(std::getenv("IRE_STAMPS_RAW"), "w")) {
             for (size_t i = 0; i < h.size(); ++i) std::fprintf(f, "%llu\n", h[i]);
             std::fclose(f);
         }
-        (void)hipFree(stamps_dev_);
-        stamps_dev_ = nullptr;
+        stamps_dev_.reset();
     }
     if (stamps_dev_ && !stamps_tl_.empty()) {       // workgroup timeline (conv_w4.hip `tl`): raw stamps, one row per workgroup and slot
         std::vector<unsigned long long> h(8 * 2 * 64 * 10);
-        (void)hipMemcpy(h.data(), stamps_dev_, h.size() * 8, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(h.data(), stamps_dev_.get<void>(), h.size() * 8, hipMemcpyDeviceToHost);
         if (FILE* f = std::fopen(stamps_tl_.c_str(), "w")) {
             std::fprintf(f, "wg,slot,realtime_10ns,memtime\n");
             for (int wg = 0; wg < 256; ++wg)
@@ -120,12 +108,11 @@ Engine::~Engine() {
                     if (h[(size_t)wg * 32 + sl * 2] || h[(size_t)wg * 32 + sl * 2 + 1]) std::fprintf(f, "%d,%d,%llu,%llu\n", wg, sl, h[(size_t)wg * 32 + sl * 2], h[(size_t)wg * 32 + sl * 2 + 1]);
             std::fclose(f);
         }
-        (void)hipFree(stamps_dev_);
-        stamps_dev_ = nullptr;
+        stamps_dev_.reset();
     }
     if (stamps_dev_) {   // diagnostic dump: per-stage phase durations (s_memtime ticks = shader clocks / 100 MHz ref? printed raw)
         std::vector<unsigned long long> h(8 * 2 * 64 * 10);
-        (void)hipMemcpy(h.data(), stamps_dev_, h.size() * 8, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(h.data(), stamps_dev_.get<void>(), h.size() * 8, hipMemcpyDeviceToHost);
         const char* names[5] = {"top->mfma_loop_end", "->vmcnt0", "->epi_barrier1", "->epilogue_end", "->stage_barrier"};
         for (int wg = 0; wg < 2; ++wg)
             for (int wv = 0; wv < 2; ++wv) {
@@ -146,15 +133,7 @@ Engine::~Engine() {
                                  names[2], d23, names[3], d34, names[4], d45, (long long)(t[5] - t[0]));
                 }
             }
-        (void)hipFree(stamps_dev_);
     }
-    free_workspace();
-    delete tiled_;
-    for (void* p : net_.allocs) (void)hipFree(p);
-    for (void* p : table_allocs_) (void)hipFree(p);
-    for (void* p : {(void*)d_in_, (void*)d_out_, (void*)d_jpeg_, (void*)d_sums_, (void*)d_scores_, (void*)d_label_,
-                    (void*)d_cond_, (void*)d_film_, d_zero_, (void*)d_fL_, (void*)d_fQ_, (void*)d_fsad_, (void*)d_fmisc_, (void*)d_fwlut_, (void*)d_pp_tab_, (void*)d_pp_mid_, (void*)d_pp_in_, (void*)d_pp_out_, (void*)d_enc_scratch_, (void*)d_enc_io_, (void*)d_pad_in_, (void*)d_pad_out_})
-        if (p) (void)hipFree(p);
     for (auto& L : lanes_) {
         if (L.stream) (void)hipStreamDestroy(L.stream);
         if (L.done) (void)hipEventDestroy(L.done);
@@ -184,8 +163,7 @@ void Engine::load_weights_file(const char* path) {
 template <class T>
 T* Engine::upload(const std::vector<T>& v) {
     if (v.empty()) return nullptr;
-    T* d = (T*)dalloc(v.size() * sizeof(T));
-    net_.allocs.push_back(d);
+    T* d = net_.mem.alloc<T>(v.size() * sizeof(T));
     IRE_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return d;
 }
@@ -205,10 +183,9 @@ void Engine::load_weights(const void* blob, size_t bytes) {
     const TensorMap tm = parse_weights(blob, bytes);
     IRE_HIP(hipSetDevice(device_));
     IRE_HIP(hipDeviceSynchronize());
-    delete tiled_; tiled_ = nullptr;
-    for (void* q : net_.allocs) (void)hipFree(q);
+    tiled_.reset();
     net_ = Net{};
-    if (!d_zero_) { d_zero_ = dalloc(256); IRE_HIP(hipMemset(d_zero_, 0, 256)); }
+    if (d_zero_.grow(256)) IRE_HIP(hipMemset(d_zero_.get<void>(), 0, 256));
     const bool fp8 = precision_ == IRE_PRECISION_FP8;
     auto vec = [&](const std::string& nm, size_t n, const std::string& what) -> const std::vector<float>& {
         auto it = tm.find(nm);
@@ -267,26 +244,12 @@ void Engine::check_shape(int n, int h, int w, bool for_restore) const {
 void Engine::ensure_io(int n, int h, int w) {
     IRE_HIP(hipSetDevice(device_));
     const size_t px = (size_t)h * w;
-    if ((size_t)n <= io_cap_imgs_ && px <= io_cap_px_) return;
+    if ((size_t)n <= io_.cap_imgs && px <= io_.cap_px) return;
     IRE_HIP(hipDeviceSynchronize());
-    // small shapes: room for a whole batch at once (no regrowth per n); large ones: what was asked for
-    const size_t want = px * 3 * (size_t)max_batch_ <= ((size_t)256 << 20) ? (size_t)max_batch_ : (size_t)n;
-    const size_t imgs = std::max<size_t>(std::max<size_t>(io_cap_imgs_, want), (size_t)n);
-    const size_t cap_px = std::max(io_cap_px_, px);
-    for (void* p : {(void*)d_in_, (void*)d_out_, (void*)d_jpeg_, (void*)d_sums_, (void*)d_scores_, (void*)d_label_,
-                    (void*)d_cond_, (void*)d_film_})
-        if (p) (void)hipFree(p);
-    d_in_ = (uint8_t*)dalloc(imgs * cap_px * 3);
-    d_out_ = (uint8_t*)dalloc(imgs * cap_px * 3);
-    d_jpeg_ = (uint8_t*)dalloc(imgs);
-    d_sums_ = (unsigned long long*)dalloc(cls_sums_bytes());   // sums | tickets | workgroup partials (classifier.hpp)
-    IRE_HIP(hipMemset(d_sums_, 0, cls_sums_bytes()));
-    d_scores_ = (double*)dalloc(imgs * 7 * 8);
-    d_label_ = (int32_t*)dalloc(imgs * 4);
-    d_cond_ = (float*)dalloc(imgs * 8 * 4);
-    d_film_ = (float*)dalloc(imgs * kFilmDim * 4);
-    io_cap_imgs_ = imgs;
-    io_cap_px_ = cap_px;
+    // in images: a whole batch of the shape or what was asked for (batch_room), and never less than before on either axis
+    const size_t want = batch_room(px * 3 * (size_t)n, px * 3 * (size_t)max_batch_) / (px * 3);
+    io_.regrow(std::max({io_.cap_imgs, want, (size_t)n}), std::max(io_.cap_px, px), cls_sums_bytes());
+    IRE_HIP(hipMemset(io_.sums, 0, cls_sums_bytes()));
 }
 
 void Engine::enter(hipStream_t s) {
@@ -303,19 +266,25 @@ void Engine::check_fit(int n, int h, int w) const {
 }
 
 void Engine::ensure_pad(int n, int H, int W) {
-    const size_t need = (size_t)n * H * W * 3;
-    if (need <= pad_cap_) return;
+    const size_t per = (size_t)H * W * 3, need = per * (size_t)n;
+    if (need <= d_pad_out_.bytes()) return;      // (the pair has one size, and d_pad_out_ is the one allocated last)
     IRE_HIP(hipSetDevice(device_));
     IRE_HIP(hipDeviceSynchronize());
-    if (d_pad_in_) (void)hipFree(d_pad_in_);
-    if (d_pad_out_) (void)hipFree(d_pad_out_);
-    d_pad_in_ = d_pad_out_ = nullptr; pad_cap_ = 0;
-    // small shapes: room for a whole batch at once (the first batch of a shape allocates, the later ones never do)
-    const size_t per = (size_t)H * W * 3;
-    const size_t want = per * (size_t)max_batch_ <= ((size_t)256 << 20) ? per * (size_t)max_batch_ : need;
-    d_pad_in_ = (uint8_t*)dalloc(want);
-    d_pad_out_ = (uint8_t*)dalloc(want);
-    pad_cap_ = want;
+    d_pad_in_.reset(); d_pad_out_.reset();      // both go before either comes back
+    const size_t want = batch_room(need, per * (size_t)max_batch_);
+    d_pad_in_.grow(need, want);
+    d_pad_out_.grow(need, want);
+}
+
+// both encoders' per-batch scratch (`full`: what a whole batch of the shape needs) and the host entries' staging, pixels in | text out
+void Engine::ensure_enc_scratch(size_t need, size_t full) {
+    if (need > d_enc_scratch_.bytes()) IRE_HIP(hipDeviceSynchronize());
+    d_enc_scratch_.grow(need, batch_room(need, full));
+}
+uint8_t* Engine::ensure_enc_io(size_t need) {
+    if (need > d_enc_io_.bytes()) IRE_HIP(hipDeviceSynchronize());
+    d_enc_io_.grow(need);
+    return d_enc_io_.get<uint8_t>();
 }
 
 // the one encoder behind every entry: the window of n images -> n texts.  Three launches and one small memset per batch.
@@ -323,17 +292,8 @@ void Engine::encode_window(const uint8_t* d_rgb, int n, int h, int w, size_t row
     if (stride < png_base64_chars(h, w)) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the PNG encoder: smaller than ire_png_base64_bytes(h, w)");
     if (row_pitch < (size_t)3 * w || (n > 1 && image_pitch < row_pitch * (size_t)(h - 1) + (size_t)3 * w))
         fail(IRE_ERR_INVALID_INPUT, "invalid pitch for the PNG encoder: rows or images overlap");
-    const size_t need = png_scratch_bytes(n, h, w);
-    if (need > enc_scratch_cap_) {
-        IRE_HIP(hipDeviceSynchronize());
-        if (d_enc_scratch_) IRE_HIP(hipFree(d_enc_scratch_));
-        d_enc_scratch_ = nullptr; enc_scratch_cap_ = 0;
-        const size_t full = png_scratch_bytes(max_batch_, h, w);       // a whole batch of this shape when that is small
-        const size_t want = full <= ((size_t)256 << 20) ? full : need;
-        d_enc_scratch_ = (uint8_t*)dalloc(want);
-        enc_scratch_cap_ = want;
-    }
-    encode_png_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_enc_scratch_, d_chars, stride, s);
+    ensure_enc_scratch(png_scratch_bytes(n, h, w), png_scratch_bytes(max_batch_, h, w));
+    encode_png_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_enc_scratch_.get<uint8_t>(), d_chars, stride, s);
 }
 
 void Engine::encode_png_base64_device(const uint8_t* d_rgb, int n, int h, int w, uint8_t* d_chars, size_t stride, hipStream_t s) {
@@ -353,18 +313,11 @@ void Engine::encode_host_impl(const uint8_t* rgb, int n, int h, int w, uint8_t* 
     const size_t ib = (size_t)h * w * 3, cb = png_base64_chars(h, w), cpad = (cb + 255) / 256 * 256;
     if (stride < cb) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the PNG encoder: smaller than ire_png_base64_bytes(h, w)");
     const size_t in_pad = (ib * n + 255) / 256 * 256;
-    const size_t need = in_pad + cpad * (size_t)n;
-    if (need > enc_io_cap_) {
-        IRE_HIP(hipDeviceSynchronize());
-        if (d_enc_io_) IRE_HIP(hipFree(d_enc_io_));
-        d_enc_io_ = nullptr; enc_io_cap_ = 0;
-        d_enc_io_ = (uint8_t*)dalloc(need);
-        enc_io_cap_ = need;
-    }
+    uint8_t* d_px = ensure_enc_io(in_pad + cpad * (size_t)n);
     hipStream_t s = main_stream_;
-    IRE_HIP(hipMemcpyAsync(d_enc_io_, rgb, ib * n, hipMemcpyHostToDevice, s));
-    uint8_t* d_txt = d_enc_io_ + in_pad;
-    encode_window(d_enc_io_, n, h, w, (size_t)3 * w, ib, d_txt, cpad, s);
+    IRE_HIP(hipMemcpyAsync(d_px, rgb, ib * n, hipMemcpyHostToDevice, s));
+    uint8_t* d_txt = d_px + in_pad;
+    encode_window(d_px, n, h, w, (size_t)3 * w, ib, d_txt, cpad, s);
     for (int i = 0; i < n; ++i) IRE_HIP(hipMemcpyAsync(chars + stride * i, d_txt + cpad * i, cb, hipMemcpyDeviceToHost, s));
     IRE_HIP(hipStreamSynchronize(s));
 }
@@ -382,15 +335,6 @@ void Engine::encode_png_base64_fit_host(const uint8_t* rgb, int n, int h, int w,
 }
 
 // ---- the compressing encoder (deflate.hip): the same window, texts of data-dependent length and their counts -------------------------
-void Engine::ensure_enc_scratch(size_t need, size_t full) {
-    if (need <= enc_scratch_cap_) return;
-    IRE_HIP(hipDeviceSynchronize());
-    if (d_enc_scratch_) IRE_HIP(hipFree(d_enc_scratch_));
-    d_enc_scratch_ = nullptr; enc_scratch_cap_ = 0;
-    const size_t want = full <= ((size_t)256 << 20) ? full : need;       // a whole batch of this shape when that is small
-    d_enc_scratch_ = (uint8_t*)dalloc(want);
-    enc_scratch_cap_ = want;
-}
 
 void Engine::encode_deflate_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, uint8_t* d_lens,
                                    size_t lens_pitch, hipStream_t s) {
@@ -398,7 +342,7 @@ void Engine::encode_deflate_window(const uint8_t* d_rgb, int n, int h, int w, si
     if (row_pitch < (size_t)3 * w || (n > 1 && image_pitch < row_pitch * (size_t)(h - 1) + (size_t)3 * w))
         fail(IRE_ERR_INVALID_INPUT, "invalid pitch for the PNG encoder: rows or images overlap");
     ensure_enc_scratch(png_deflate_scratch_bytes(n, h, w), png_deflate_scratch_bytes(max_batch_, h, w));
-    encode_png_deflate_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_enc_scratch_, d_chars, stride, d_lens, lens_pitch, s);
+    encode_png_deflate_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_enc_scratch_.get<uint8_t>(), d_chars, stride, d_lens, lens_pitch, s);
 }
 
 void Engine::encode_png_deflate_base64_fit_device(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride,
@@ -415,18 +359,11 @@ void Engine::encode_png_deflate_base64_fit_host(const uint8_t* rgb, int n, int h
     const size_t ib = (size_t)h * w * 3, cb = png_deflate_base64_bound(h, w), cpad = (cb + 8 + 255) / 256 * 256;
     if (stride < cb) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the PNG encoder: smaller than ire_png_deflate_base64_bound(h, w)");
     const size_t in_pad = (ib * n + 255) / 256 * 256;
-    const size_t need = in_pad + cpad * (size_t)n;
-    if (need > enc_io_cap_) {
-        IRE_HIP(hipDeviceSynchronize());
-        if (d_enc_io_) IRE_HIP(hipFree(d_enc_io_));
-        d_enc_io_ = nullptr; enc_io_cap_ = 0;
-        d_enc_io_ = (uint8_t*)dalloc(need);
-        enc_io_cap_ = need;
-    }
+    uint8_t* d_px = ensure_enc_io(in_pad + cpad * (size_t)n);
     hipStream_t s = main_stream_;
-    IRE_HIP(hipMemcpyAsync(d_enc_io_, rgb, ib * n, hipMemcpyHostToDevice, s));
-    uint8_t* d_txt = d_enc_io_ + in_pad;
-    encode_deflate_window(d_enc_io_, n, h, w, (size_t)3 * w, ib, d_txt + 8, cpad, d_txt, cpad, s);
+    IRE_HIP(hipMemcpyAsync(d_px, rgb, ib * n, hipMemcpyHostToDevice, s));
+    uint8_t* d_txt = d_px + in_pad;
+    encode_deflate_window(d_px, n, h, w, (size_t)3 * w, ib, d_txt + 8, cpad, d_txt, cpad, s);
     std::vector<uint8_t> stage(cpad * (size_t)n);
     IRE_HIP(hipMemcpyAsync(stage.data(), d_txt, cpad * (size_t)n, hipMemcpyDeviceToHost, s));
     IRE_HIP(hipStreamSynchronize(s));
@@ -440,28 +377,9 @@ void Engine::encode_png_deflate_base64_fit_host(const uint8_t* rgb, int n, int h
 }
 
 void Engine::free_workspace() {
-    for (void* p : ws_allocs_) (void)hipFree(p);
-    ws_allocs_.clear();
-    for (auto& L : lanes_) {
-        std::memset(L.act, 0, sizeof(L.act));
-        std::memset(L.skip, 0, sizeof(L.skip));
-        L.stats = L.stats2 = nullptr;
-        L.ab = nullptr;
-    }
-    ws_imgs_per_lane_ = ws_imgs_cap_ = ws_h_ = ws_w_ = 0;
-    ws_bytes_ = 0;
-}
-
-// activation workspace (engine.cpp::ensure_workspace) + the staging of the host entry points (ensure_io) of ONE image
-size_t Engine::bytes_per_image(int h, int w) const {
-    size_t b = 0;
-    for (int l = 0; l < 4; ++l) {
-        const size_t t = (size_t)(h >> l) * (w >> l) * kWidths[l] * 2;
-        b += t * (4 + (l < 3 ? 1 : 0));
-    }
-    b += 2 * (size_t)ceil_div(h, 4) * ceil_div(w, 32) * 16 * 4 + 256 * sizeof(float2);
-    b += (size_t)h * w * 3 * 2;      // d_in_ / d_out_
-    return b;
+    ws_.clear();
+    for (Lane& L : lanes_) L.v = LaneBufs{};
+    ws_imgs_cap_ = ws_h_ = ws_w_ = 0;
 }
 
 int Engine::capacity_for(int h, int w) const {
@@ -469,7 +387,7 @@ int Engine::capacity_for(int h, int w) const {
     size_t free_b = 0, total_b = 0;
     if (hipSetDevice(device_) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 0;
     // what this engine already holds for activations would be released on a change of shape
-    const double avail = 0.92 * ((double)free_b + (double)ws_bytes_);
+    const double avail = 0.92 * ((double)free_b + (double)ws_.bytes());
     const double n = avail / (double)bytes_per_image(h, w);
     return n >= (double)max_batch_ ? max_batch_ : (int)n;
 }
@@ -481,24 +399,22 @@ void Engine::ensure_workspace(int n, int h, int w) {
     const int per = ceil_div(cap, num_lanes_);
     IRE_HIP(hipDeviceSynchronize());
     free_workspace();
-    auto alloc = [&](size_t bytes) { void* p = dalloc(bytes); ws_allocs_.push_back(p); ws_bytes_ += bytes; return p; };
-    try {
-        for (auto& L : lanes_) {
-            for (int l = 0; l < 4; ++l) {
-                const size_t bytes = (size_t)per * (h >> l) * (w >> l) * kWidths[l] * 2;
-                for (int b = 0; b < 4; ++b) L.act[l][b] = (unsigned short*)alloc(bytes);
-                if (l < 3) L.skip[l] = (unsigned short*)alloc(bytes);
-            }
-            const size_t tiles0 = (size_t)ceil_div(h, 4) * ceil_div(w, 32);
-            L.stats = (float*)alloc((size_t)per * tiles0 * 16 * 4);
-            L.stats2 = (float*)alloc((size_t)per * tiles0 * 16 * 4);
-            L.ab = (float2*)alloc((size_t)per * 256 * sizeof(float2));
+    // Memory and views are committed together: a throw half way frees `mem` (a partial allocation must not pin HBM: the caller gets
+    // "service unavailable" and may retry smaller) and leaves the engine with the empty workspace free_workspace made.
+    const std::vector<WsEntry> table = lane_workspace(per, h, w);
+    BufSet<DeviceMem> mem;
+    std::vector<LaneBufs> views(lanes_.size());
+    for (LaneBufs& v : views)
+        for (const WsEntry& e : table) {
+            void* p = mem.alloc<void>(e.bytes);
+            if (e.slot == WS_STATS) v.stats = (float*)p;
+            else if (e.slot == WS_STATS2) v.stats2 = (float*)p;
+            else if (e.slot == WS_AB) v.ab = (float2*)p;
+            else v.buf[e.slot >> 3][e.slot & 7] = (unsigned short*)p;
         }
-    } catch (...) {
-        free_workspace();     // a partial allocation must not pin HBM: the caller gets "service unavailable" and may retry smaller
-        throw;
-    }
-    ws_imgs_per_lane_ = per; ws_imgs_cap_ = per * num_lanes_; ws_h_ = h; ws_w_ = w;
+    ws_ = std::move(mem);
+    for (size_t i = 0; i < views.size(); ++i) lanes_[i].v = views[i];
+    ws_imgs_cap_ = per * num_lanes_; ws_h_ = h; ws_w_ = w;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -616,9 +532,9 @@ bool Engine::debug_activation(const std::string& name, float* out, size_t* count
     return true;
 }
 void Engine::debug_sums(int n, uint64_t* out) {
-    if (n <= 0 || (size_t)n > io_cap_imgs_ || !d_sums_) fail(IRE_ERR_INVALID_INPUT, "invalid n for debug sums");
+    if (n <= 0 || (size_t)n > io_.cap_imgs) fail(IRE_ERR_INVALID_INPUT, "invalid n for debug sums");
     IRE_HIP(hipDeviceSynchronize());
-    IRE_HIP(hipMemcpy(out, d_sums_, sizeof(uint64_t) * 14 * n, hipMemcpyDeviceToHost));
+    IRE_HIP(hipMemcpy(out, io_.sums, sizeof(uint64_t) * 14 * n, hipMemcpyDeviceToHost));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -676,11 +592,8 @@ void Engine::build_program() {
 Geo Engine::geo_of_lane(const Lane& L, int nimg, int h, int w, const uint8_t* d_in, uint8_t* d_out) {
     Geo g;
     g.nimg = nimg; g.h = h; g.w = w; g.H = h;
-    for (int l = 0; l < 4; ++l) {
-        for (int b = 0; b < 4; ++b) g.buf[l][b] = L.act[l][b];
-        g.buf[l][4] = l < 3 ? L.skip[l] : nullptr;
-        g.buf[l][5] = nullptr;
-    }
+    for (int l = 0; l < 4; ++l)
+        for (int b = 0; b < 5; ++b) g.buf[l][b] = L.v.buf[l][b];
     g.img_in = d_in; g.img_out = d_out;
     return g;
 }
@@ -714,7 +627,7 @@ void Engine::exec_conv(Run& R, const Op& op, const Geo& g) {
     const float* const biases[] = {cw.d_bias, cw.d_bias_uf, cw.d_bias8};      // BiasArr
     a.w = slabs[p.w]; a.w1 = slabs[p.w1]; a.bias = biases[p.bias];
     if (p.fp8) a.oscale = cw.d_oscale;
-    if (p.zeros) a.zeros = d_zero_;
+    if (p.zeros) a.zeros = d_zero_.get<void>();
     a.ab = op.use_ab ? R.ab : nullptr; a.resid = out_ptr(op.resid); a.out = out_ptr(op.out);
     a.u8_in = d.kind == CONV_HEAD ? g.img_in + (size_t)g.halo * g.w * 3 : nullptr;
     a.u8_out = d.kind == CONV_HEAD ? g.img_out : nullptr;
@@ -730,7 +643,7 @@ void Engine::exec_conv(Run& R, const Op& op, const Geo& g) {
     R.next_rev = !a.walk_rev;
     const bool rb = d.kind == CONV_RB1 || d.kind == CONV_RB2;
     if (stamps_dev_ && rb && d.cout == stamps_cout_ && (d.kind == CONV_RB2) == stamps_resid_ && (!stamps_taken_ || !stamps_tl_.empty() || std::getenv("IRE_STAMPS_RAW"))) {
-        a.stamps = stamps_dev_;
+        a.stamps = stamps_dev_.get<unsigned long long>();
         stamps_taken_ = true;
     }
     if (R.gn_pending) {
@@ -798,7 +711,7 @@ void Engine::exec_op(Run& R, const Op& op, const Geo& g) {
 
 void Engine::run_network(Lane& L, int nimg, int h, int w, const uint8_t* d_in, uint8_t* d_out, const float* d_film) {
     Run R;
-    R.stream = L.stream; R.stats = L.stats; R.stats_alt = L.stats2; R.ab = L.ab; R.film = d_film;
+    R.stream = L.stream; R.stats = L.v.stats; R.stats_alt = L.v.stats2; R.ab = L.v.ab; R.film = d_film;
     R.snake = snake_;
     const Geo g = geo_of_lane(L, nimg, h, w, d_in, d_out);
     // inside one pass of the op list a profiled launch's end event is the next one's start (prof_begin): nothing but the
@@ -822,10 +735,9 @@ void Engine::classify_device(const uint8_t* d_rgb, int n, int h, int w, const ui
     check_shape(n, h, w, false);
     if (!d_rgb) fail(IRE_ERR_INVALID_INPUT, "invalid input: null image pointer");
     ensure_io(n, 1, 1);
-    Lane tmp; tmp.stream = stream;
     prof_begin(FAM_CLASSIFIER, stream, 0, (double)n * h * w * 3);
-    classifier_launch(tables_, d_rgb, n, h, w, d_is_jpeg, d_sums_, d_scores ? d_scores : d_scores_, d_label ? d_label : d_label_,
-                      d_cond_, stream);
+    classifier_launch(tables_, d_rgb, n, h, w, d_is_jpeg, io_.sums, d_scores ? d_scores : io_.scores, d_label ? d_label : io_.label,
+                      io_.cond, stream);
     prof_end(stream);
     last_n_ = n;
 }
@@ -838,16 +750,16 @@ void Engine::restore_device(const uint8_t* d_rgb, int n, int h, int w, const dou
     ensure_io(n, 1, 1);
     ensure_workspace(n, h, w);
     if (d_scores) {
-        scores_to_cond_launch(d_scores, n, d_cond_, stream);
+        scores_to_cond_launch(d_scores, n, io_.cond, stream);
     } else {
         // classified inside: the scan's last workgroup per image writes the FiLM vector too (no film launch, no boundary behind the scan)
         prof_begin(FAM_CLASSIFIER, stream, 0, (double)n * h * w * 3);
-        classifier_launch(tables_, d_rgb, n, h, w, d_is_jpeg, d_sums_, d_scores_, d_label_, d_cond_, stream, net_.d_film_w, net_.d_film_b, kFilmDim, d_film_);
+        classifier_launch(tables_, d_rgb, n, h, w, d_is_jpeg, io_.sums, io_.scores, io_.label, io_.cond, stream, net_.d_film_w, net_.d_film_b, kFilmDim, io_.film);
         prof_end(stream);
     }
     if (d_scores) {
         prof_begin(FAM_GN, stream, 0, 0);
-        film_launch(d_cond_, n, net_.d_film_w, net_.d_film_b, kFilmDim, d_film_, stream);
+        film_launch(io_.cond, n, net_.d_film_w, net_.d_film_b, kFilmDim, io_.film, stream);
         prof_end(stream);
     }
     last_n_ = n;
@@ -863,7 +775,7 @@ void Engine::restore_device(const uint8_t* d_rgb, int n, int h, int w, const dou
     if (lanes_used == 1) {
         Lane L = lanes_[0];
         L.stream = stream;  // run inline on the caller's stream
-        run_network(L, n, h, w, d_rgb, d_out, d_film_);
+        run_network(L, n, h, w, d_rgb, d_out, io_.film);
         return;
     }
     const int per = ceil_div(n, lanes_used);
@@ -874,7 +786,7 @@ void Engine::restore_device(const uint8_t* d_rgb, int n, int h, int w, const dou
         Lane& L = lanes_[i];
         IRE_HIP(hipStreamWaitEvent(L.stream, fork_ev_, 0));
         run_network(L, cnt, h, w, d_rgb + (size_t)i0 * img_bytes, d_out + (size_t)i0 * img_bytes,
-                    d_film_ + (size_t)i0 * kFilmDim);
+                    io_.film + (size_t)i0 * kFilmDim);
         IRE_HIP(hipEventRecord(L.done, L.stream));
         IRE_HIP(hipStreamWaitEvent(stream, L.done, 0));
     }
@@ -885,16 +797,16 @@ void Engine::restore_tiled_device(const uint8_t* d_rgb, int h, int w, int nstrip
     if (!d_rgb || !d_out) fail(IRE_ERR_INVALID_INPUT, "invalid input: null image pointer");
     if (!tiled_ || tiled_h_ != h || tiled_w_ != w || tiled_n_ != nstrips) {
         IRE_HIP(hipDeviceSynchronize());
-        delete tiled_; tiled_ = nullptr;
-        tiled_ = new StripSession(*this, h, w, nstrips, 0, nstrips, nullptr);
+        tiled_.reset();
+        tiled_.reset(new StripSession(*this, h, w, nstrips, 0, nstrips, nullptr));
         tiled_h_ = h; tiled_w_ = w; tiled_n_ = nstrips;
     }
     ensure_io(1, 1, 1);
     if (!d_scores) {
         prof_begin(FAM_CLASSIFIER, stream, 0, (double)h * w * 3);
-        classifier_launch(tables_, d_rgb, 1, h, w, d_is_jpeg, d_sums_, d_scores_, d_label_, d_cond_, stream);
+        classifier_launch(tables_, d_rgb, 1, h, w, d_is_jpeg, io_.sums, io_.scores, io_.label, io_.cond, stream);
         prof_end(stream);
-        d_scores = d_scores_;
+        d_scores = io_.scores;
     }
     batches_run_ += 1; images_restored_ += 1; last_batch_ = 1;
     {
@@ -916,8 +828,8 @@ void Engine::restore_padded(const uint8_t* d_rgb, int n, int h, int w, const dou
     if (!net_.loaded) fail(IRE_ERR_UNAVAILABLE, "service unavailable: RestoreNet weights are not loaded");
     const int H = fit_dim(h), W = fit_dim(w);
     ensure_pad(n, H, W);
-    pad_edge_launch(d_rgb, n, h, w, d_pad_in_, H, W, stream);
-    restore_device(d_pad_in_, n, H, W, d_scores, d_is_jpeg, d_pad_out_, stream);
+    pad_edge_launch(d_rgb, n, h, w, d_pad_in_.get<uint8_t>(), H, W, stream);
+    restore_device(d_pad_in_.get<uint8_t>(), n, H, W, d_scores, d_is_jpeg, d_pad_out_.get<uint8_t>(), stream);
 }
 
 void Engine::restore_fit_device(const uint8_t* d_rgb, int n, int h, int w, const double* d_scores, const uint8_t* d_is_jpeg, uint8_t* d_out,
@@ -927,11 +839,11 @@ void Engine::restore_fit_device(const uint8_t* d_rgb, int n, int h, int w, const
     if (!d_rgb || !d_out) fail(IRE_ERR_INVALID_INPUT, "invalid input: null image pointer");
     ensure_io(n, 1, 1);
     if (!d_scores) {          // the classifier reads the ORIGINAL pixels, never the padded copy
-        classify_device(d_rgb, n, h, w, d_is_jpeg, d_scores_, d_label_, stream);
-        d_scores = d_scores_;
+        classify_device(d_rgb, n, h, w, d_is_jpeg, io_.scores, io_.label, stream);
+        d_scores = io_.scores;
     }
     restore_padded(d_rgb, n, h, w, d_scores, d_is_jpeg, stream);
-    crop_window_launch(d_pad_out_, n, fit_dim(h), fit_dim(w), d_out, h, w, stream);
+    crop_window_launch(d_pad_out_.get<uint8_t>(), n, fit_dim(h), fit_dim(w), d_out, h, w, stream);
 }
 
 // the batcher's results as text: the stored PNG's characters, or with IRE_FLAG_RESULT_PNG_DEFLATE [uint64 count | characters] per result
@@ -949,10 +861,10 @@ void Engine::restore_fit_device_mixed(const uint8_t* d_rgb, int n, int h, int w,
     for (int i = 0; i < n; ++i) { if (has_scores && has_scores[i]) any_given = true; else any_missing = true; }
     const double* d_sc = nullptr;       // null: restore_device classifies inside (its scan also writes the FiLM vector); only an aligned shape may
     if (any_given || !aligned) {
-        if (any_missing) classify_device(d_rgb, n, h, w, d_is_jpeg, d_scores_, d_label_, stream);      // the ORIGINAL pixels
+        if (any_missing) classify_device(d_rgb, n, h, w, d_is_jpeg, io_.scores, io_.label, stream);      // the ORIGINAL pixels
         for (int i = 0; i < n; ++i)
-            if (has_scores && has_scores[i]) IRE_HIP(hipMemcpyAsync(d_scores_ + 7 * i, host_scores + 7 * i, sizeof(double) * 7, hipMemcpyHostToDevice, stream));
-        d_sc = d_scores_;
+            if (has_scores && has_scores[i]) IRE_HIP(hipMemcpyAsync(io_.scores + 7 * i, host_scores + 7 * i, sizeof(double) * 7, hipMemcpyHostToDevice, stream));
+        d_sc = io_.scores;
     }
     if (aligned) {
         restore_device(d_rgb, n, h, w, d_sc, d_is_jpeg, d_out, stream);
@@ -961,8 +873,8 @@ void Engine::restore_fit_device_mixed(const uint8_t* d_rgb, int n, int h, int w,
     }
     const int H = fit_dim(h), W = fit_dim(w);
     restore_padded(d_rgb, n, h, w, d_sc, d_is_jpeg, stream);
-    if (d_txt) encode_result(d_pad_out_, n, h, w, (size_t)3 * W, (size_t)3 * W * H, d_txt, txt_stride, stream);     // the crop costs no pass of its own
-    else crop_window_launch(d_pad_out_, n, H, W, d_out, h, w, stream);
+    if (d_txt) encode_result(d_pad_out_.get<uint8_t>(), n, h, w, (size_t)3 * W, (size_t)3 * W * H, d_txt, txt_stride, stream);     // the crop costs no pass of its own
+    else crop_window_launch(d_pad_out_.get<uint8_t>(), n, H, W, d_out, h, w, stream);
 }
 
 void Engine::get_stats(ire_engine_stats* out) {
@@ -986,13 +898,13 @@ void Engine::classify_host(const uint8_t* rgb, int n, int h, int w, int row_stri
     if (row_stride < 3 * w) fail(IRE_ERR_INVALID_INPUT, "invalid row_stride (< 3*w)");
     ensure_io(n, h, w);
     hipStream_t s = main_stream_;
-    IRE_HIP(hipMemcpy2DAsync(d_in_, (size_t)3 * w, rgb, (size_t)row_stride, (size_t)3 * w, (size_t)n * h, hipMemcpyHostToDevice, s));
+    IRE_HIP(hipMemcpy2DAsync(io_.in, (size_t)3 * w, rgb, (size_t)row_stride, (size_t)3 * w, (size_t)n * h, hipMemcpyHostToDevice, s));
     std::vector<uint8_t> jp(n, 1);
     if (is_jpeg) std::memcpy(jp.data(), is_jpeg, n);
-    IRE_HIP(hipMemcpyAsync(d_jpeg_, jp.data(), n, hipMemcpyHostToDevice, s));
-    classify_device(d_in_, n, h, w, d_jpeg_, d_scores_, d_label_, s);
-    IRE_HIP(hipMemcpyAsync(scores, d_scores_, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, s));
-    if (label) IRE_HIP(hipMemcpyAsync(label, d_label_, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipMemcpyAsync(io_.jpeg, jp.data(), n, hipMemcpyHostToDevice, s));
+    classify_device(io_.in, n, h, w, io_.jpeg, io_.scores, io_.label, s);
+    IRE_HIP(hipMemcpyAsync(scores, io_.scores, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, s));
+    if (label) IRE_HIP(hipMemcpyAsync(label, io_.label, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
     IRE_HIP(hipStreamSynchronize(s));
 }
 
@@ -1004,26 +916,26 @@ void Engine::restore_host_impl(const uint8_t* rgb, int n, int h, int w, const do
     hipStream_t s = main_stream_;
     const size_t bytes = (size_t)n * h * w * 3;
     IRE_HIP(hipEventRecord(ev_[0], s));
-    IRE_HIP(hipMemcpyAsync(d_in_, rgb, bytes, hipMemcpyHostToDevice, s));
+    IRE_HIP(hipMemcpyAsync(io_.in, rgb, bytes, hipMemcpyHostToDevice, s));
     std::vector<uint8_t> jp(n, 1);
     if (is_jpeg) std::memcpy(jp.data(), is_jpeg, n);
-    IRE_HIP(hipMemcpyAsync(d_jpeg_, jp.data(), n, hipMemcpyHostToDevice, s));
+    IRE_HIP(hipMemcpyAsync(io_.jpeg, jp.data(), n, hipMemcpyHostToDevice, s));
     const double* d_sc = nullptr;
     IRE_HIP(hipEventRecord(ev_[1], s));
     if (scores) {
-        IRE_HIP(hipMemcpyAsync(d_scores_, scores, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
-        d_sc = d_scores_;
+        IRE_HIP(hipMemcpyAsync(io_.scores, scores, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
+        d_sc = io_.scores;
     } else {
         // classify as its own step so classify_ms / restore_ms mirror restorator.js:59-95 (the pixels as uploaded, never a padded copy)
         prof_begin(FAM_CLASSIFIER, s, 0, (double)n * h * w * 3);
-        classifier_launch(tables_, d_in_, n, h, w, d_jpeg_, d_sums_, d_scores_, d_label_, d_cond_, s);
+        classifier_launch(tables_, io_.in, n, h, w, io_.jpeg, io_.sums, io_.scores, io_.label, io_.cond, s);
         prof_end(s);
-        d_sc = d_scores_;
+        d_sc = io_.scores;
     }
     IRE_HIP(hipEventRecord(ev_[2], s));
-    restore_fit_device(d_in_, n, h, w, d_sc, d_jpeg_, d_out_, s);       // (an aligned shape: restore_device as it is)
+    restore_fit_device(io_.in, n, h, w, d_sc, io_.jpeg, io_.out, s);       // (an aligned shape: restore_device as it is)
     IRE_HIP(hipEventRecord(ev_[3], s));
-    IRE_HIP(hipMemcpyAsync(out, d_out_, bytes, hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipMemcpyAsync(out, io_.out, bytes, hipMemcpyDeviceToHost, s));
     IRE_HIP(hipStreamSynchronize(s));
     if (t) {
         float a = 0, b = 0, c = 0;

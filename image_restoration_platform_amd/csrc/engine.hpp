@@ -8,6 +8,7 @@
 #pragma once
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -16,6 +17,7 @@
 #include "common.hpp"
 #include "conv_mfma.hpp"
 #include "conv_plan.hpp"
+#include "device_buf.hpp"
 
 namespace ire {
 
@@ -59,17 +61,18 @@ struct Net {
     ConvW down[3], up[3], fuse[3];
     float* d_film_w = nullptr;
     float* d_film_b = nullptr;
-    std::vector<void*> allocs;
+    BufSet<DeviceMem> mem;            // every array the pointers above are views of
 };
 
+struct LaneBufs {                     // views into the engine's workspace (device_buf.hpp lane_workspace)
+    unsigned short* buf[4][5] = {};   // [level][0..3: activations | 4: the skip tensor (levels 0..2)]
+    float *stats = nullptr, *stats2 = nullptr;   // stats2: second partials array: a conv that finalizes its input's GroupNorm itself (gn_fold.hpp) reads one and writes the other
+    float2* ab = nullptr;
+};
 struct Lane {
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
-    unsigned short* act[4][4] = {};
-    unsigned short* skip[3] = {};
-    float* stats = nullptr;
-    float* stats2 = nullptr;          // second partials array: a conv that finalizes its input's GroupNorm itself (gn_fold.hpp) reads one and writes the other
-    float2* ab = nullptr;
+    LaneBufs v;
 };
 
 // ---- the layer schedule as a program (engine.cpp::build_program): one list of ops, executed op by op either over a whole
@@ -204,7 +207,7 @@ public:
     void enter(hipStream_t s);
     void leave(hipStream_t s);
     // device bytes one more image of this shape costs (activation workspace + staging), and how many fit right now
-    size_t bytes_per_image(int h, int w) const;
+    size_t bytes_per_image(int h, int w) const { return workspace_bytes_per_image(h, w); }
     int capacity_for(int h, int w) const;
     // cfg 4: the whole image on this GPU as nstrips "virtual ranks" (strips.cpp); d_scores null => classify inside
     void restore_tiled_device(const uint8_t* d_rgb, int h, int w, int nstrips, const double* d_scores, const uint8_t* d_is_jpeg,
@@ -215,7 +218,7 @@ public:
     void restore_device_mixed(const uint8_t* d_rgb, int n, int h, int w, const double* host_scores, const uint8_t* has_scores,
                               const uint8_t* d_is_jpeg, uint8_t* d_out, hipStream_t stream);
     hipStream_t main_stream() const { return main_stream_; }          // the stream of the host entry points and of the batcher's compute
-    const double* scores_device() const { return d_scores_; }       // [last n][7], valid after a classify on main_stream()
+    const double* scores_device() const { return io_.scores; }       // [last n][7], valid after a classify on main_stream()
     std::mutex& mutex() { return mu_; }
 
 private:
@@ -227,6 +230,7 @@ private:
     void encode_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, hipStream_t s);
     void encode_host_impl(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride);
     void ensure_enc_scratch(size_t need, size_t full);
+    uint8_t* ensure_enc_io(size_t need);      // d_enc_io_ with room for `need` bytes
     void encode_deflate_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, uint8_t* d_lens,
                                size_t lens_pitch, hipStream_t s);
     void encode_result(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_txt, size_t txt_stride, hipStream_t s);
@@ -244,9 +248,8 @@ private:
     void prof_end(hipStream_t s);
     void capture(const char* name, const unsigned short* d, size_t count, hipStream_t s);
     void capture_f32(const char* name, const float* d, size_t count, hipStream_t s);
-    template <class T> T* upload(const std::vector<T>& v);     // allocate + register in net_.allocs + copy; null for an empty v
+    template <class T> T* upload(const std::vector<T>& v);     // allocate in net_.mem + copy; null for an empty v
     ConvW upload_conv(const PackedConv& p);                    // weight_pack.hpp's arrays of one convolution -> device
-    void* dalloc(size_t bytes);
 
     int device_ = 0;
     int max_batch_ = 8;
@@ -268,55 +271,32 @@ private:
     double t0_ = 0.0;
 
     // classifier
+    // Every device buffer below is owned through device_buf.hpp: freed with the engine (members die after ~Engine's body: behind its
+    // hipDeviceSynchronize, the device still current), grow-only per shape, and empty after a failed grow.
     ClassifierTables tables_{};
-    std::vector<void*> table_allocs_;
+    BufSet<DeviceMem> tables_mem_;
 
-    // io / classifier buffers (sized by ensure_io)
-    size_t io_cap_imgs_ = 0, io_cap_px_ = 0;
-    uint8_t* d_in_ = nullptr;
-    uint8_t* d_out_ = nullptr;
-    uint8_t* d_jpeg_ = nullptr;
-    unsigned long long* d_sums_ = nullptr;
-    double* d_scores_ = nullptr;
-    int32_t* d_label_ = nullptr;
-    float* d_cond_ = nullptr;
-    float* d_film_ = nullptr;
+    IoBufs<DeviceMem> io_;                // io / classifier buffers (sized by ensure_io)
     int last_n_ = 0;
-    // fusion scratch
-    size_t fuse_cap_px_ = 0;
-    int fuse_cap_sets_ = 0;
-    unsigned* d_fwlut_ = nullptr;
-    uint8_t* d_fL_ = nullptr;
-    uint8_t* d_fQ_ = nullptr;
-    unsigned* d_fsad_ = nullptr;
-    int* d_fmisc_ = nullptr;
-    void* d_zero_ = nullptr;           // 256 bytes of zeros (conv_upq.hip's zero padding source)
-    // preprocess scratch (tap tables, intermediate of the horizontal pass, host-path staging)
-    size_t pp_tab_cap_ = 0, pp_mid_cap_ = 0, pp_in_cap_ = 0, pp_out_cap_ = 0;
-    int32_t* d_pp_tab_ = nullptr;
-    uint8_t* d_pp_mid_ = nullptr;
-    uint8_t* d_pp_in_ = nullptr;
-    uint8_t* d_pp_out_ = nullptr;
-    uint8_t* d_enc_scratch_ = nullptr;    // encode.hip: per batch: the PNG files + checksum state
-    uint8_t* d_pad_in_ = nullptr;         // any-size jobs: the edge-padded batch in front of the network ...
-    uint8_t* d_pad_out_ = nullptr;        // ... and the network's output on the padded shape
-    size_t pad_cap_ = 0;
-    uint8_t* d_enc_io_ = nullptr;         // host entry: pixels in | characters out
-    size_t enc_scratch_cap_ = 0, enc_io_cap_ = 0;
+    FuseBufs<DeviceMem> fuse_;            // fusion scratch
+    Buf<DeviceMem> d_zero_;               // 256 bytes of zeros (conv_upq.hip's zero padding source)
+    Buf<DeviceMem> d_pp_tab_, d_pp_mid_, d_pp_in_, d_pp_out_;   // preprocess scratch (tap tables, intermediate of the horizontal pass, host-path staging)
+    Buf<DeviceMem> d_enc_scratch_;        // encode.hip: per batch: the PNG files + checksum state
+    Buf<DeviceMem> d_pad_in_, d_pad_out_; // any-size jobs: the edge-padded batch in front of the network, and the network's output on the padded shape
+    Buf<DeviceMem> d_enc_io_;             // host entry: pixels in | characters out
 
     // network
     Net net_;
-    std::vector<Op> program_;
-    class StripSession* tiled_ = nullptr;      // cached session of restore_tiled_device (one shape at a time)
-    int tiled_h_ = 0, tiled_w_ = 0, tiled_n_ = 0;       // the layer schedule (build_program; rebuilt by load_weights)
+    std::vector<Op> program_;             // the layer schedule (build_program; rebuilt by load_weights)
+    std::unique_ptr<class StripSession> tiled_;   // cached session of restore_tiled_device (one shape at a time)
+    int tiled_h_ = 0, tiled_w_ = 0, tiled_n_ = 0;
     std::vector<Lane> lanes_;
-    int ws_imgs_per_lane_ = 0, ws_imgs_cap_ = 0, ws_h_ = 0, ws_w_ = 0;
-    size_t ws_bytes_ = 0;
-    std::vector<void*> ws_allocs_;
+    int ws_imgs_cap_ = 0, ws_h_ = 0, ws_w_ = 0;
+    BufSet<DeviceMem> ws_;                // what the lanes' LaneBufs point into
 
     // debug / profile
     // diagnostic stamps (IRE_RB_STAMPS, ablation builds)
-    unsigned long long* stamps_dev_ = nullptr;
+    Buf<DeviceMem> stamps_dev_;
     int stamps_cout_ = 0;
     bool stamps_resid_ = false, stamps_taken_ = false;
     std::string stamps_tl_;

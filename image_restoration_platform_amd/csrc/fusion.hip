@@ -457,25 +457,15 @@ void Engine::fuse_launch(const uint8_t* d_views, int nsets, int k, int h, int w,
                          int32_t* d_shifts, hipStream_t s) {
     const size_t px = (size_t)h * w;
     const int hq = h / 4, wq = w / 4, qp = (wq + 3) & ~3;
-    if (fuse_cap_px_ < px || fuse_cap_sets_ < nsets) {
+    if (fuse_.cap_px < px || fuse_.cap_sets < nsets) {
         IRE_HIP(hipDeviceSynchronize());
-        for (void* p : {(void*)d_fL_, (void*)d_fQ_, (void*)d_fsad_, (void*)d_fmisc_, (void*)d_fwlut_}) if (p) (void)hipFree(p);
-        const size_t cpx = std::max(px, fuse_cap_px_);
-        const int cs = std::max(nsets, fuse_cap_sets_);
-        // per view set: 3 luma planes, 3 quarter-res planes (pitch: a multiple of 4),
-        // per-workgroup SAD rows (coarse and fine take turns), coarse[3][2] + shifts[3][2], a ticket, a blend table
-        d_fL_ = (uint8_t*)dalloc((size_t)cs * 3 * cpx);
-        d_fQ_ = (uint8_t*)dalloc((size_t)cs * 3 * (cpx / 16 + cpx / 64 + 16) + 64);      // (w >= 64: the pitch adds at most 3 to a row of >= 16)
-        d_fsad_ = (unsigned*)dalloc(sizeof(unsigned) * (size_t)cs * 2 * FUSE_SAD_GRID * NC);
-        d_fmisc_ = (int*)dalloc(sizeof(int) * (size_t)cs * 16);
-        d_fwlut_ = (unsigned*)dalloc(sizeof(unsigned) * (size_t)cs * 256);
-        IRE_HIP(hipMemsetAsync(d_fmisc_, 0, sizeof(int) * (size_t)cs * 16, s));   // the tickets start at zero; the kernels reset them
-        fuse_cap_px_ = cpx; fuse_cap_sets_ = cs;
+        fuse_.regrow(std::max(nsets, fuse_.cap_sets), std::max(px, fuse_.cap_px), (size_t)2 * FUSE_SAD_GRID * NC);      // (device_buf.hpp FuseBufs)
+        IRE_HIP(hipMemsetAsync(fuse_.misc, 0, sizeof(int) * (size_t)fuse_.cap_sets * 16, s));   // the tickets start at zero; the kernels reset them
     }
-    // d_fmisc_: [sets][6] coarse | [sets][6] shifts | [sets] tickets
-    int* d_coarse = d_fmisc_;
-    int* d_sh = d_fmisc_ + 6 * fuse_cap_sets_;
-    unsigned* d_ticket = reinterpret_cast<unsigned*>(d_fmisc_ + 12 * fuse_cap_sets_);
+    // misc: [sets][6] coarse | [sets][6] shifts | [sets] tickets
+    int* d_coarse = fuse_.misc;
+    int* d_sh = fuse_.misc + 6 * fuse_.cap_sets;
+    unsigned* d_ticket = reinterpret_cast<unsigned*>(fuse_.misc + 12 * fuse_.cap_sets);
     FuseWlut lut;
     std::memcpy(lut.w, host_wluts, sizeof(lut.w));
     prof_begin(FAM_FUSION, s, 0, (double)nsets * (k + 1) * px * 3);
@@ -483,11 +473,11 @@ void Engine::fuse_launch(const uint8_t* d_views, int nsets, int k, int h, int w,
     if (nsets > 1) {      // one table per set (its own noise score); a single call carries its table in the kernel arguments
         // (copied on a stream of their own, beside the luma and SAD kernels, with the blend waiting on an event: measured, the chain is
         //  8 us LONGER -- the cross-stream wait costs more than the ~4 us copy in front: profiles/r03_experiments.md)
-        IRE_HIP(hipMemcpyAsync(d_fwlut_, host_wluts, sizeof(unsigned) * 256 * nsets, hipMemcpyHostToDevice, s));   // pageable source: staged before the call returns
-        d_wluts = d_fwlut_;
+        IRE_HIP(hipMemcpyAsync(fuse_.wlut, host_wluts, sizeof(unsigned) * 256 * nsets, hipMemcpyHostToDevice, s));   // pageable source: staged before the call returns
+        d_wluts = fuse_.wlut;
     }
     const int nq = k * hq * wq;
-    hipLaunchKernelGGL(fusion_luma_kernel, dim3(ceil_div(nq, 256), nsets), dim3(256), 0, s, d_views, k, h, w, qp, d_fL_, d_fQ_);
+    hipLaunchKernelGGL(fusion_luma_kernel, dim3(ceil_div(nq, 256), nsets), dim3(256), 0, s, d_views, k, h, w, qp, fuse_.L, fuse_.Q);
     auto tiles = [](int ph, int pw, int m, int step, int tw, int sr) {
         return ceil_div(pw - 2 * m, tw) * ceil_div(ceil_div(ph - 2 * m, step), sr);
     };
@@ -499,10 +489,10 @@ void Engine::fuse_launch(const uint8_t* d_views, int nsets, int k, int h, int w,
     const int gcap = gcap_env > 0 ? gcap_env : std::max(32, 512 / ((k - 1) * nsets));
     const int g0 = std::min(std::min(FUSE_SAD_GRID, gcap), tiles(hq, wq, CR, 1, SadCfg<0>::TW, SadCfg<0>::SR));
     const int g1 = std::min(std::min(FUSE_SAD_GRID, gcap), tiles(h, w, FM, 2, SadCfg<1>::TW, SadCfg<1>::SR));
-    hipLaunchKernelGGL(fusion_sad_kernel<0>, dim3(g0, k - 1, nsets), dim3(256), 0, s, d_fQ_, k, hq, wq, qp, d_coarse, d_sh, (int*)nullptr,
-                       d_fsad_, d_ticket);
-    hipLaunchKernelGGL(fusion_sad_kernel<1>, dim3(g1, k - 1, nsets), dim3(256), 0, s, d_fL_, k, h, w, w, d_coarse, d_sh, (int*)d_shifts,
-                       d_fsad_, d_ticket);
+    hipLaunchKernelGGL(fusion_sad_kernel<0>, dim3(g0, k - 1, nsets), dim3(256), 0, s, fuse_.Q, k, hq, wq, qp, d_coarse, d_sh, (int*)nullptr,
+                       fuse_.sad, d_ticket);
+    hipLaunchKernelGGL(fusion_sad_kernel<1>, dim3(g1, k - 1, nsets), dim3(256), 0, s, fuse_.L, k, h, w, w, d_coarse, d_sh, (int*)d_shifts,
+                       fuse_.sad, d_ticket);
     if (k == 3) hipLaunchKernelGGL(fusion_blend_kernel<3>, dim3(ceil_div((int)(px / 4), 256), nsets), dim3(256), 0, s, d_views, h, w, d_sh, lut, d_wluts, d_out);
     else hipLaunchKernelGGL(fusion_blend_kernel<2>, dim3(ceil_div((int)(px / 4), 256), nsets), dim3(256), 0, s, d_views, h, w, d_sh, lut, d_wluts, d_out);
     IRE_HIP(hipGetLastError());
@@ -511,9 +501,9 @@ void Engine::fuse_launch(const uint8_t* d_views, int nsets, int k, int h, int w,
 
 double Engine::noise_of_view0(const uint8_t* d_views, int h, int w, hipStream_t s) {
     ensure_io(1, 1, 1);
-    classifier_launch(tables_, d_views, 1, h, w, nullptr, d_sums_, d_scores_, d_label_, d_cond_, s);
+    classifier_launch(tables_, d_views, 1, h, w, nullptr, io_.sums, io_.scores, io_.label, io_.cond, s);
     double sc[7];
-    IRE_HIP(hipMemcpyAsync(sc, d_scores_, sizeof(sc), hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipMemcpyAsync(sc, io_.scores, sizeof(sc), hipMemcpyDeviceToHost, s));
     IRE_HIP(hipStreamSynchronize(s));   // the blend LUT is built on the host (exact double exp)
     return sc[IRE_SCORE_NOISE];
 }
@@ -550,19 +540,19 @@ void fuse_host(Engine& E, const uint8_t* rgb_views, int k, int h, int w, double 
 void Engine::fuse_host_impl(const uint8_t* rgb_views, int k, int h, int w, double noise_score, uint8_t* out_rgb,
                             int32_t* shifts_out, ire_timings* t) {
     const size_t px = (size_t)h * w;
-    ensure_io(3, h, w);   // views in d_in_, result in d_out_
+    ensure_io(3, h, w);   // views in io_.in, result in io_.out
     hipStream_t s = main_stream_;
     IRE_HIP(hipEventRecord(ev_[0], s));
-    IRE_HIP(hipMemcpyAsync(d_in_, rgb_views, (size_t)k * px * 3, hipMemcpyHostToDevice, s));
+    IRE_HIP(hipMemcpyAsync(io_.in, rgb_views, (size_t)k * px * 3, hipMemcpyHostToDevice, s));
     IRE_HIP(hipEventRecord(ev_[1], s));
-    if (noise_score < 0) noise_score = noise_of_view0(d_in_, h, w, s);
+    if (noise_score < 0) noise_score = noise_of_view0(io_.in, h, w, s);
     IRE_HIP(hipEventRecord(ev_[2], s));
     unsigned lut[256];
     make_wlut(noise_score, lut);
-    fuse_launch(d_in_, 1, k, h, w, lut, d_out_, nullptr, s);
+    fuse_launch(io_.in, 1, k, h, w, lut, io_.out, nullptr, s);
     IRE_HIP(hipEventRecord(ev_[3], s));
-    IRE_HIP(hipMemcpyAsync(out_rgb, d_out_, px * 3, hipMemcpyDeviceToHost, s));
-    if (shifts_out) IRE_HIP(hipMemcpyAsync(shifts_out, d_fmisc_ + 6 * fuse_cap_sets_, sizeof(int) * 2 * k, hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipMemcpyAsync(out_rgb, io_.out, px * 3, hipMemcpyDeviceToHost, s));
+    if (shifts_out) IRE_HIP(hipMemcpyAsync(shifts_out, fuse_.misc + 6 * fuse_.cap_sets, sizeof(int) * 2 * k, hipMemcpyDeviceToHost, s));
     IRE_HIP(hipStreamSynchronize(s));
     if (t) {
         float a = 0, b = 0, c = 0;

@@ -166,9 +166,9 @@ void Engine::preprocess_device(const uint8_t* d_rgb, int h, int w, int orientati
     const int kv = make_taps(uh, out_h, bv_, tv_);
     const size_t need_tab = (bh_.size() + th_.size() + bv_.size() + tv_.size()) * sizeof(int32_t);
     const size_t need_mid = (size_t)uh * out_w * 3;
-    if (need_tab > pp_tab_cap_) { if (d_pp_tab_) IRE_HIP(hipFree(d_pp_tab_)); d_pp_tab_ = (int32_t*)dalloc(need_tab); pp_tab_cap_ = need_tab; }
-    if (need_mid > pp_mid_cap_) { if (d_pp_mid_) IRE_HIP(hipFree(d_pp_mid_)); d_pp_mid_ = (uint8_t*)dalloc(need_mid); pp_mid_cap_ = need_mid; }
-    int32_t* d_bh = d_pp_tab_;
+    d_pp_tab_.grow(need_tab);
+    d_pp_mid_.grow(need_mid);
+    int32_t* d_bh = d_pp_tab_.get<int32_t>();
     int32_t* d_th = d_bh + bh_.size();
     int32_t* d_bv = d_th + th_.size();
     int32_t* d_tv = d_bv + bv_.size();
@@ -180,8 +180,8 @@ void Engine::preprocess_device(const uint8_t* d_rgb, int h, int w, int orientati
     IRE_HIP(hipMemcpyAsync(d_tv, tv_.data(), tv_.size() * 4, hipMemcpyHostToDevice, s));
     IRE_HIP(hipStreamSynchronize(s));      // the vectors die at return
     hipLaunchKernelGGL(resample_h_kernel, dim3((out_w + 255) / 256, uh), dim3(256), 0, s, d_rgb, h, w, orientation, uh, out_w, kh, d_bh,
-                       d_th, d_pp_mid_);
-    hipLaunchKernelGGL(resample_v_kernel, dim3((out_w * 3 + 255) / 256, out_h), dim3(256), 0, s, d_pp_mid_, out_w, out_h, kv, d_bv, d_tv,
+                       d_th, d_pp_mid_.get<uint8_t>());
+    hipLaunchKernelGGL(resample_v_kernel, dim3((out_w * 3 + 255) / 256, out_h), dim3(256), 0, s, d_pp_mid_.get<uint8_t>(), out_w, out_h, kv, d_bv, d_tv,
                        d_out);
     IRE_HIP(hipGetLastError());
 }
@@ -192,12 +192,13 @@ void Engine::preprocess_host(const uint8_t* rgb, int h, int w, int orientation, 
     if (pw != out_w || ph != out_h) fail(IRE_ERR_INVALID_INPUT, "invalid output size for preprocess: use ire_preprocess_plan");
     if (!rgb || !out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to preprocess: null buffer");
     const size_t in_bytes = (size_t)h * w * 3, out_bytes = (size_t)out_h * out_w * 3;
-    if (in_bytes > pp_in_cap_) { if (d_pp_in_) IRE_HIP(hipFree(d_pp_in_)); d_pp_in_ = (uint8_t*)dalloc(in_bytes); pp_in_cap_ = in_bytes; }
-    if (out_bytes > pp_out_cap_) { if (d_pp_out_) IRE_HIP(hipFree(d_pp_out_)); d_pp_out_ = (uint8_t*)dalloc(out_bytes); pp_out_cap_ = out_bytes; }
+    d_pp_in_.grow(in_bytes);
+    d_pp_out_.grow(out_bytes);
+    uint8_t *const d_in = d_pp_in_.get<uint8_t>(), *const d_res = d_pp_out_.get<uint8_t>();
     hipStream_t s = main_stream_;
-    IRE_HIP(hipMemcpyAsync(d_pp_in_, rgb, in_bytes, hipMemcpyHostToDevice, s));
-    preprocess_device(d_pp_in_, h, w, orientation, max_dim, d_pp_out_, out_h, out_w, s);
-    IRE_HIP(hipMemcpyAsync(out, d_pp_out_, out_bytes, hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipMemcpyAsync(d_in, rgb, in_bytes, hipMemcpyHostToDevice, s));
+    preprocess_device(d_in, h, w, orientation, max_dim, d_res, out_h, out_w, s);
+    IRE_HIP(hipMemcpyAsync(out, d_res, out_bytes, hipMemcpyDeviceToHost, s));
     IRE_HIP(hipStreamSynchronize(s));
 }
 

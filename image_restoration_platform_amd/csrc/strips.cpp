@@ -20,12 +20,7 @@
 
 namespace ire {
 
-namespace {
-const int kW[4] = {32, 64, 128, 256};
-const int kFilmDimS = 960;
-}  // namespace
-
-size_t StripSession::stats_floats(int H, int W) { return (size_t)ceil_div(H, 4) * ceil_div(W, 32) * 16; }
+size_t StripSession::stats_floats(int H, int W) { return gn_partials(H, W); }
 
 StripSession::StripSession(Engine& eng, int H, int W, int nstrips_total, int first_strip, int nlocal, float* d_stats_external)
     : E(eng), H_(H), W_(W), total_(nstrips_total), first_(first_strip), nlocal_(nlocal) {
@@ -40,42 +35,32 @@ StripSession::StripSession(Engine& eng, int H, int W, int nstrips_total, int fir
     if (nstrips_total == 1 && (H % 8 || H < 16)) fail(IRE_ERR_INVALID_INPUT, "invalid image size for restore: height and width must be multiples of 8, >= 16");
     if (first_strip < 0 || nlocal < 1 || first_strip + nlocal > nstrips_total) fail(IRE_ERR_INVALID_INPUT, "invalid strip range");
     IRE_HIP(hipSetDevice(E.device_));
-    auto alloc = [&](size_t bytes) { void* p = nullptr; IRE_HIP(hipMalloc(&p, bytes ? bytes : 16)); allocs_.push_back(p); return p; };
-    try {
-        strips_.resize(nlocal);
-        for (int s = 0; s < nlocal; ++s) {
-            Geo& g = strips_[s];
-            const int gs = first_strip + s;
-            g.nimg = 1; g.h = hr_; g.w = W; g.halo = 1; g.H = H; g.y0 = gs * hr_;
-            g.has_up = gs > 0; g.has_down = gs + 1 < nstrips_total;
-            for (int l = 0; l < 4; ++l) {
-                const size_t bytes = (size_t)((hr_ >> l) + 2) * (W >> l) * kW[l] * 2;
-                for (int b = 0; b < 5; ++b) {
-                    if (b == 4 && l == 3) continue;
-                    g.buf[l][b] = (unsigned short*)alloc(bytes);
-                }
+    strips_.resize(nlocal);       // (a throw below: mem_ frees what was allocated)
+    for (int s = 0; s < nlocal; ++s) {
+        Geo& g = strips_[s];
+        const int gs = first_strip + s;
+        g.nimg = 1; g.h = hr_; g.w = W; g.halo = 1; g.H = H; g.y0 = gs * hr_;
+        g.has_up = gs > 0; g.has_down = gs + 1 < nstrips_total;
+        for (int l = 0; l < 4; ++l) {
+            const size_t bytes = (size_t)((hr_ >> l) + 2) * (W >> l) * kWidths[l] * 2;
+            for (int b = 0; b < 5; ++b) {
+                if (b == 4 && l == 3) continue;
+                g.buf[l][b] = mem_.alloc<unsigned short>(bytes);
             }
-            uint8_t* img = (uint8_t*)alloc((size_t)(hr_ + 2) * W * 3);
-            g.img_in = img;
-            g.img_out = (uint8_t*)alloc((size_t)hr_ * W * 3);
         }
-        if (d_stats_external) stats_ = d_stats_external;
-        else stats_ = (float*)alloc(stats_floats(H, W) * 4);
-        ab_ = (float2*)alloc(256 * sizeof(float2));
-        d_cond_ = (float*)alloc(8 * 4);
-        d_film_ = (float*)alloc(kFilmDimS * 4);
-        d_scores_ = (double*)alloc(7 * 8);
-    } catch (...) {
-        for (void* p : allocs_) (void)hipFree(p);
-        allocs_.clear();
-        throw;
+        g.img_in = mem_.alloc<uint8_t>((size_t)(hr_ + 2) * W * 3);
+        g.img_out = mem_.alloc<uint8_t>((size_t)hr_ * W * 3);
     }
+    stats_ = d_stats_external ? d_stats_external : mem_.alloc<float>(stats_floats(H, W) * 4);
+    ab_ = mem_.alloc<float2>(256 * sizeof(float2));
+    d_cond_ = mem_.alloc<float>(8 * 4);
+    d_film_ = mem_.alloc<float>(kFilmDim * 4);
+    d_scores_ = mem_.alloc<double>(7 * 8);
 }
 
-StripSession::~StripSession() {
+StripSession::~StripSession() {       // (mem_ goes after this body)
     (void)hipSetDevice(E.device_);
     (void)hipDeviceSynchronize();
-    for (void* p : allocs_) (void)hipFree(p);
 }
 
 int StripSession::num_ops() const { return (int)E.program_.size(); }
@@ -90,7 +75,7 @@ void StripSession::set_input(const uint8_t* d_rows_with_halo, const double* d_sc
                                hipMemcpyDeviceToDevice, s));
     IRE_HIP(hipMemcpyAsync(d_scores_, d_scores, 7 * 8, hipMemcpyDeviceToDevice, s));
     scores_to_cond_launch(d_scores_, 1, d_cond_, s);
-    film_launch(d_cond_, 1, E.net_.d_film_w, E.net_.d_film_b, kFilmDimS, d_film_, s);
+    film_launch(d_cond_, 1, E.net_.d_film_w, E.net_.d_film_b, kFilmDim, d_film_, s);
     run_ = Run{};
     run_.stats = stats_; run_.ab = ab_; run_.film = d_film_;
 }
@@ -98,7 +83,7 @@ void StripSession::set_input(const uint8_t* d_rows_with_halo, const double* d_sc
 size_t StripSession::halo_row_bytes(int k) const {
     const Op& op = E.program_[k];
     if (op.kind != Op::CONV || !op.halo_out || total_ == 1) return 0;
-    return (size_t)(W_ >> op.lout) * kW[op.lout] * 2;
+    return (size_t)(W_ >> op.lout) * kWidths[op.lout] * 2;
 }
 
 void StripSession::run_op(int k, hipStream_t s, ire_strip_xchg* info) {
@@ -174,7 +159,7 @@ void StripSession::run_all(const uint8_t* d_rgb, const double* d_scores, uint8_t
     }
     IRE_HIP(hipMemcpyAsync(d_scores_, d_scores, 7 * 8, hipMemcpyDeviceToDevice, s));
     scores_to_cond_launch(d_scores_, 1, d_cond_, s);
-    film_launch(d_cond_, 1, E.net_.d_film_w, E.net_.d_film_b, kFilmDimS, d_film_, s);
+    film_launch(d_cond_, 1, E.net_.d_film_w, E.net_.d_film_b, kFilmDim, d_film_, s);
     run_ = Run{};
     run_.stats = stats_; run_.ab = ab_; run_.film = d_film_;
     for (int k = 0; k < num_ops(); ++k) run_op(k, s, nullptr);

@@ -29,7 +29,7 @@ private:
     Engine& E;
     int H_, W_, total_, first_, nlocal_, hr_ = 0;
     std::vector<Geo> strips_;
-    std::vector<void*> allocs_;
+    BufSet<DeviceMem> mem_;           // every buffer below and in strips_
     float* stats_ = nullptr;
     float2* ab_ = nullptr;
     float* d_cond_ = nullptr;

@@ -542,3 +542,35 @@ def stress_weights(w0):
         w["enc%d.rb0.conv1.b" % l][::4] = 4.0
     w["dec1.rb0.conv1.w"][:] = 0.0
     return w
+
+
+FP8_CLAMP_LAYERS = {"enc2.rb1": "enc2.rb1.gn2", "enc3.rb0.h": "enc3.rb0.gn1", "mid.rb0.h": "mid.rb0.gn1", "dec2.rb0": "dec2.rb0.gn2"}
+FP8_ZERO_ROW_CONV = "mid.rb1.conv1"
+
+
+def fp8_stress_weights(w0):
+    """stress_weights(w0) with the two edges of the fp8 operand rules on top, which neither the seeds nor the stress set reach (with
+    them the largest 16 silu(x A + B) at a C >= 128 layer is 325):
+    (a) the GroupNorm gains of channels 2::7 times 12 in front of the four convolutions of FP8_CLAMP_LAYERS (conv1 and conv2, with and
+        without the residual, C = 128 and C = 256): a share of 4e-3 .. 1e-2 of their activated operands has 16 silu >= 448, the largest
+        1024 .. 2337, so the clamp in front of the e4m3 conversion decides what the MFMA multiplies;
+    (b) the output rows ::9 of FP8_ZERO_ROW_CONV all zero: max|w| == 0, the scale 1.0 of fp8_weights and weight_pack.hpp::pack_conv;
+        those channels' output is their bias.
+    (b) was run on the CPU at 72 x 136 with the three stress images as written, and nothing had to be tamed: 29 of the 256 channels
+    of mid.rb1.h are constant per image, at most four of the 32 in a GroupNorm group, so no group's variance collapses (the constant
+    bias that stress_weights' docstring tames is the case of EVERY channel of a group); every layer of the intact fp8 oracle passes
+    and the caps hold (tests/test_layer_check.py asserts it, and prints the shares)."""
+    w = stress_weights(w0)
+    for gn in FP8_CLAMP_LAYERS.values():
+        w[gn + ".g"][2::7] *= 12.0
+    w[FP8_ZERO_ROW_CONV + ".w"][::9] = 0.0
+    return w
+
+
+def clamp_share(x, ab):
+    """Share of the activated fp8 operands of a convolution (stored input x [N,C,H,W], applied coefficients ab [N,C,2]) with
+    16 silu(x A + B) >= 448, and the largest 16 silu: what the clamp in front of the e4m3 conversion acts on."""
+    y = x * ab[:, :, 0][:, :, None, None] + ab[:, :, 1][:, :, None, None]
+    with np.errstate(over="ignore"):
+        v = FP8_ACT_SCALE * y / (1.0 + np.exp(-y))
+    return float((v >= 448.0).mean()), float(v.max())

@@ -2,7 +2,8 @@
 // network's convolutions in schedule order for a list of cases and prints, per case and layer group (the profiler key), one line with
 // every field of the launch plan, in the order of the header line; two ops of one group that plan differently print both lines.  The ConvDesc of a layer is what
 // weight_pack.hpp's packer produces for zero weights of the layer's shape: which arrays exist depends on shapes and precision only.
-// usage: conv_plan_dump fixture | props      (fixture: the recorded cases; props: the cases behind the separately asserted invariants)
+// usage: conv_plan_dump fixture | props | fp8      (fixture: the recorded cases; props: the cases behind the separately asserted invariants;
+// fp8: an fp8 engine under every combination of the switches that decide its C >= 128 ResBlock convolutions)
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -79,6 +80,17 @@ static std::vector<Case> property_cases() {
         if (p[0] != 1024) cs.push_back(whole({}, false, 1, p[0], p[1]));      // (1 x 1024 x 1024 is in the list above)
         for (int s = 0; s < p[2]; ++s) cs.push_back(strip_of(p[0], p[1], p[2], s));
     }
+    return cs;
+}
+
+// an fp8 engine under IRE_FP8_MX x IRE_W4 x IRE_PK, at the shapes tests/test_layers_gpu.py gives it
+static std::vector<Case> fp8_cases() {
+    std::vector<Case> cs;
+    for (const char* mx : {"1", "0"})
+        for (const char* w4 : {"1", "0"})
+            for (const char* pk : {"2", "0"})
+                for (auto& s : {std::vector<int>{1, 16, 16}, {2, 200, 328}, {12, 32, 48}, {3, 72, 136}})
+                    cs.push_back(whole({{"IRE_FP8_MX", mx}, {"IRE_W4", w4}, {"IRE_PK", pk}}, true, s[0], s[1], s[2]));
     return cs;
 }
 
@@ -174,9 +186,9 @@ static void run_case(const Case& c, const NetDesc& net) {
 int main(int argc, char** argv) {
     if (argc != 2) return 2;
     const std::string mode = argv[1];
-    if (mode != "fixture" && mode != "props") return 2;
+    if (mode != "fixture" && mode != "props" && mode != "fp8") return 2;
     const NetDesc bf16 = net_desc(false), fp8 = net_desc(true);
     std::printf("# case group kernel resid fused_act kname w w1 bias zeros cin1 nkc nblocks w4_nt fp8 cout group_size in1_off tile_h tiles_x tiles_y iy_lo iy_span in_rows in_row_off parts_mul stats_level ty0 stats_off stat_parts folds_gn fam flops flops_exec bytes\n");
-    for (const Case& c : mode == "props" ? property_cases() : fixture_cases()) run_case(c, c.fp8 ? fp8 : bf16);
+    for (const Case& c : mode == "props" ? property_cases() : mode == "fp8" ? fp8_cases() : fixture_cases()) run_case(c, c.fp8 ? fp8 : bf16);
     return 0;
 }

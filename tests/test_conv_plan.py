@@ -10,7 +10,8 @@ parts_mul, stats level, ty0) were printed by two lines added to the lifted text.
 Cases: default switches on twelve shapes (both sides of the 64-cout split at 512^2 and of both coefficient tables), every switch set
 of tests/test_layers_gpu.py and tests/test_restore_gpu.py plus IRE_PK=1 on two shapes, the fp8 engine with IRE_FP8_MX 1 and 0 on
 three, (64, 512, 512) for the launch conv_pk's table refuses, and first / middle / last row strips of three strip plans.  The comment-only invariants of the old exec_conv are asserted
-separately below, over a wider list (`props`)."""
+separately below, over a wider list (`props`).  A third list (`fp8`) is an fp8 engine under IRE_FP8_MX x IRE_W4 x IRE_PK: the table of
+which kernel, slab and bias its C >= 128 ResBlock convolutions really get is asserted at the end."""
 import glob
 import os
 import re
@@ -45,7 +46,7 @@ def _run(exe, mode):
 def dumps(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("conv_plan")
     exe, exe_asan = _build(tmp, "cp", ["-O2"]), _build(tmp, "cp_asan", ["-O1", "-fsanitize=address,undefined"])
-    return {"fixture": _run(exe, "fixture"), "fixture_asan": _run(exe_asan, "fixture"), "props": _run(exe, "props")}
+    return {"fixture": _run(exe, "fixture"), "fixture_asan": _run(exe_asan, "fixture"), "props": _run(exe, "props"), "fp8": _run(exe, "fp8")}
 
 
 FIXTURE = os.path.join(GOLDEN, "conv_plan_9e80c0a.txt")
@@ -168,3 +169,45 @@ def test_the_comment_only_invariants(dumps):
                 assert int(f["tiles_y"]) * ns == int(whole["tiles_y"])
                 checked["strips"] += 1
     assert min(checked.values()) > 100, checked
+
+
+def test_which_kernel_an_fp8_engine_really_runs(dumps):
+    """The C >= 128 ResBlock convolutions of an fp8 engine (precision="fp8") under IRE_FP8_MX x IRE_W4 x IRE_PK, read off plan_conv:
+
+      IRE_W4=1 (default)  IRE_FP8_MX=1 (default)  conv_f8.hip, slab w8x, bias8, fp8 = 1
+                          IRE_FP8_MX=0            conv_w4.hip on e4m3 operands, slab w8, bias8, fp8 = 1; 128-cout items only
+      IRE_W4=0            either                  conv_rb.hip on the bf16 slab wp with the float bias, fp8 = 0
+
+    IRE_PK changes nothing: conv_pk.hip takes no fp8 launch.  IRE_W4=0 makes an fp8 engine run a bf16 kernel SILENTLY -- the rule book
+    tests use_w4 before it looks at the precision -- so a per-layer check with fp8=True of such an engine would judge bf16 arithmetic by the
+    fp8 rules: that combination is kept out of the fp8 cases of tests/test_layers_gpu.py, and stated in DESIGN.md.  Everything else
+    of the network plans exactly as for a bf16 engine (fp8 = 0)."""
+    lines = [parse(ln) for ln in dumps["fp8"].splitlines()[1:]]
+    deep = ("L2.rb1", "L2.rb2", "L3.rb1", "L3.rb2")
+    want = {("1", "1"): ("F8", "conv_f8", "1", "w8x", "bias8"), ("0", "1"): ("W4", "conv_w4", "1", "w8", "bias8"),
+            ("1", "0"): ("RB", "conv_rb", "0", "wp", "bias"), ("0", "0"): ("RB", "conv_rb", "0", "wp", "bias")}
+    bf16 = {}
+    for c, g, f in (parse(ln) for ln in dumps["fixture"].splitlines()[1:]):
+        bf16[c, g] = f
+    seen = set()
+    for c, g, f in lines:
+        envs, prec, n, h, w, s, _ = _case(c)
+        env = dict(kv.split("=") for kv in envs.split(","))
+        assert prec == "fp8" and s is None and set(env) == {"IRE_FP8_MX", "IRE_W4", "IRE_PK"}
+        if g in deep:
+            assert (f["kernel"], f["kname"], f["fp8"], f["w"], f["bias"]) == want[env["IRE_FP8_MX"], env["IRE_W4"]], (c, g)
+            assert f["w4_nt"] == "0" and f["fused_act"] == "1" and f["w1"] == "none"
+            assert f["nkc"] == str(int(f["cout"]) // {"F8": 32, "W4": 16, "RB": 32}[f["kernel"]]), (c, g, f["nkc"])
+            seen.add((env["IRE_FP8_MX"], env["IRE_W4"], env["IRE_PK"], n, h, w, g))
+        else:
+            assert f["fp8"] == "0" and f["bias"] != "bias8" and f["w"] not in ("w8x", "w8"), (c, g)
+            # the bf16 engine's plan of the same launch, where the recording has the shape under default switches
+            same = bf16.get(("default:bf16:%dx%dx%d" % (n, h, w), g))
+            if same and (env["IRE_W4"], env["IRE_PK"]) == ("1", "2"):
+                assert f == same, (c, g)
+    assert len(seen) == 2 * 2 * 2 * 4 * len(deep)                        # every combination, every shape, all four groups
+    # IRE_PK is no input of an fp8 engine's plan: the two halves of the table are equal line by line
+    by = {(c, g): f for c, g, f in lines}
+    for (c, g), f in by.items():
+        if "IRE_PK=2" in c and g in deep:
+            assert by[c.replace("IRE_PK=2", "IRE_PK=0"), g] == f, (c, g)

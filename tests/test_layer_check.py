@@ -1,7 +1,10 @@
 """Self-test of the per-layer checker (oracle/layer_check.py) on the CPU: the emulating oracle's captures stand in for the engine's.
 (i) the intact oracle passes at every layer and the checker's own conditions hold; (ii) each of 21 defects injected into ONE layer of the
 ORACLE (never into a kernel) is reported at that layer, at no other, in the right pixel region; a one-ulp nudge of one element is
-reported.  This is what makes the assertions of tests/test_layers_gpu.py trustworthy."""
+reported; (iii) the same for the fp8 rules (activate(fp8=True), fp8_weights, K + 4 roundings) on the fp8-emulating oracle: the three
+defects at three C >= 128 convolutions, and two defects of the operand quantisation itself -- a clamp at 240 and one weight scale
+for the whole tensor -- which need lc.fp8_stress_weights to show.  This is what makes the assertions of tests/test_layers_gpu.py
+trustworthy."""
 import numpy as np
 import pytest
 import torch
@@ -15,6 +18,10 @@ from oracle import restorenet as onet
 H, W = 72, 136                       # ragged at every level (9 x 17 at 1/8 scale)
 DEFECT_LAYERS = ["enc0.rb1.conv1", "enc1.rb0.conv2", "enc2.rb0.conv1", "mid.rb0.conv1", "dec2.rb1.conv2", "dec1.rb0.conv1", "dec0.rb1.conv2"]
 DEFECTS = ["edge_replicated", "corner_takes_neighbour", "channels_swapped_last_columns"]
+FP8_DEFECT_LAYERS = ["enc2.rb0.conv1", "mid.rb0.conv1", "dec2.rb1.conv2"]
+# the defects only fp8 has, each at one convolution: (layer it is reported at, what the oracle does wrongly there)
+CLAMP_240_AT = "enc3.rb0.h"          # of lc.FP8_CLAMP_LAYERS; with plain stress weights nothing there reaches 240
+SHARED_SCALE_AT = "mid.rb1.h"        # lc.FP8_ZERO_ROW_CONV: the all-zero rows stay zero under any scale
 
 
 class _DefectiveNet(onet._Net):
@@ -28,6 +35,10 @@ class _DefectiveNet(onet._Net):
         if name != self.layer:
             return super().conv(x, name, stride, pad, fp8)
         w, b = self.w[name + ".w"], self.w[name + ".b"]
+        if fp8:                                              # the defect sits on the fp8 operands (restorenet.py _Net.conv)
+            sw = w.abs().amax(dim=(1, 2, 3), keepdim=True) / 448.0
+            sw = torch.where(sw > 0, sw, torch.ones_like(sw))
+            w = onet._e4m3(w / sw) * sw
         if self.defect == "edge_replicated":                 # (a) the right image edge replicated instead of zero-padded
             xp = F.pad(x, (1, 0, 1, 1))
             xp = torch.cat([xp, xp[:, :, :, -1:]], dim=3)
@@ -43,6 +54,33 @@ class _DefectiveNet(onet._Net):
             xs[:, 0], xs[:, 1] = x[:, 1], x[:, 0]
             y[:, :, :, -2:] = F.conv2d(xs, w, b, padding=1)[:, :, :, -2:]
         return self.q(y)
+
+
+class _MisquantisingNet(onet._Net):
+    """The fp8-emulating oracle with the operand quantisation of ONE convolution wrong; `at` is the name the checker reports it under."""
+
+    def __init__(self, weights_, capture, at, defect):
+        super().__init__(weights_, True, capture, True)
+        self.at, self.defect = at, defect
+        prefix, conv = (at[:-2], "conv1") if at.endswith(".h") else (at, "conv2")
+        self.conv_name = prefix + "." + conv
+
+    def gn_film_silu(self, x, prefix, level, film, keep=None):
+        a = super().gn_film_silu(x, prefix, level, film, keep)
+        if keep == self.at and self.defect == "clamp_at_240":
+            # saturation at 240, the largest e4m3fnuz value, instead of 448: 240 is an e4m3 value and the rounding is monotone, so
+            # min(e4m3(v), 240) IS e4m3(min(v, 240))
+            assert self.fp8 and x.shape[1] >= 128
+            a = torch.clamp(a, max=240.0 / onet.FP8_ACT_SCALE)
+        return a
+
+    def conv(self, x, name, stride=1, pad=1, fp8=False):
+        if name != self.conv_name or self.defect != "weight_scale_shared":
+            return super().conv(x, name, stride, pad, fp8)
+        assert fp8
+        w = self.w[name + ".w"]
+        sw = w.abs().amax() / 448.0                          # one scale for the whole tensor instead of one per output channel
+        return self.q(F.conv2d(x, onet._e4m3(w / sw) * sw, self.w[name + ".b"], stride=stride, padding=pad))
 
 
 def _scores(imgs):
@@ -99,11 +137,62 @@ def test_other_weight_sets_stay_finite_and_keep_the_conditions(case, seed):
         assert (1.0 + film[:, :32] < 0).any() and (w["enc0.rb0.gn1.g"] == 0).any() and (w["enc0.rb0.gn1.g"] < 0).any()
 
 
-@pytest.mark.parametrize("defect", DEFECTS)
-@pytest.mark.parametrize("layer", DEFECT_LAYERS)
-def test_defect_is_reported_at_its_layer_and_nowhere_else(case, layer, defect):
-    w, imgs, sc = case
-    reports, _, _ = _oracle_reports(w, imgs, sc, net=lambda cap: _DefectiveNet(w, cap, layer, defect))
+def _stress_images():
+    return np.stack([np.zeros((H, W, 3), np.uint8), np.full((H, W, 3), 255, np.uint8), synth.image(4, H, W)])
+
+
+def _weight_set(w0, name):
+    return lc.fp8_stress_weights(w0) if name == "fp8_stress" else lc.stress_weights(w0) if name == "stress" else weights.generate(name)
+
+
+_FP8_RUNS = {}
+
+
+def _fp8_run(w0, name):
+    """(weights, checker reports, captures, pixels) of the intact fp8 oracle on the three stress images: computed once per set."""
+    if name not in _FP8_RUNS:
+        w, imgs = _weight_set(w0, name), _stress_images()
+        _FP8_RUNS[name] = (w,) + _oracle_reports(w, imgs, _scores(imgs), fp8=True)
+    return _FP8_RUNS[name]
+
+
+def _clamp_shares(w, cap):
+    """{layer: (share of activated operands with 16 silu >= 448, largest 16 silu)} of every fp8 convolution, recomputed from the
+    captured inputs and the captured coefficients."""
+    out = {}
+    for nm in lc.layer_names("plain"):
+        if nm[:3] in ("enc", "dec", "mid") and lc.WIDTHS[lc._level(nm)] >= 128:
+            x = lc._nchw(cap[lc.layer_inputs(nm)[0]])
+            out[nm] = lc.clamp_share(x, np.asarray(cap[nm + ".ab"], dtype=np.float64))
+    return out
+
+
+@pytest.mark.parametrize("seed", [1, "stress", "fp8_stress"])
+def test_other_weight_sets_keep_the_conditions_on_the_fp8_oracle(case, seed):
+    """The fp8 form of the test above.  Only "fp8_stress" reaches the clamp in front of the e4m3 conversion and the zero weight scale:
+    the shares are recomputed here, the threshold of 1e-3 is a condition on the set (measured: 4.5e-3 .. 9.6e-3), not on an engine."""
+    w, reports, cap, out = _fp8_run(case[0], seed)
+    _assert_conditions(reports)
+    shares = _clamp_shares(w, cap)
+    assert len(shares) == 16
+    for nm, (share, top) in shares.items():
+        print("CLAMPSHARE %s | %s | share of 16 silu >= 448: %.2e | largest 16 silu %.0f" % (seed, nm, share, top))
+    if seed == "fp8_stress":
+        assert out.min() == 0 and out.max() == 255
+        for nm, (share, top) in shares.items():
+            assert (share >= 1e-3 and top > 448.0) if nm in lc.FP8_CLAMP_LAYERS else share == 0.0, (nm, share, top)
+        rows = np.abs(lc.fp8_weights(w[lc.FP8_ZERO_ROW_CONV + ".w"])).reshape(256, -1).max(axis=1)
+        assert (rows[::9] == 0).all() and (np.delete(rows, np.s_[::9]) > 0).all()
+        # those rows' output is the bias, on every pixel of every image
+        h = cap["mid.rb1.h"][..., ::9].astype(np.float64)
+        assert np.array_equal(h, np.broadcast_to(lc.bf16_round(w[lc.FP8_ZERO_ROW_CONV + ".b"].astype(np.float64))[::9], h.shape))
+    else:
+        assert all(share == 0.0 for share, _ in shares.values())           # why the new set exists
+    if seed == "stress":
+        assert shares[CLAMP_240_AT][1] < 240.0                              # (and a clamp at 240 is invisible there: asserted below)
+
+
+def _assert_reported_in_its_region(reports, layer, defect):
     prefix, conv = layer.rsplit(".", 1)
     target = prefix + ".h" if conv == "conv1" else prefix
     failing = sorted(nm for nm, r in reports.items() if not r.ok)
@@ -122,6 +211,46 @@ def test_defect_is_reported_at_its_layer_and_nowhere_else(case, layer, defect):
     assert not r.coeff_fail
 
 
+@pytest.mark.parametrize("defect", DEFECTS)
+@pytest.mark.parametrize("layer", DEFECT_LAYERS)
+def test_defect_is_reported_at_its_layer_and_nowhere_else(case, layer, defect):
+    w, imgs, sc = case
+    reports, _, _ = _oracle_reports(w, imgs, sc, net=lambda cap: _DefectiveNet(w, cap, layer, defect))
+    _assert_reported_in_its_region(reports, layer, defect)
+
+
+@pytest.mark.parametrize("defect", DEFECTS)
+@pytest.mark.parametrize("layer", FP8_DEFECT_LAYERS)
+def test_defect_on_fp8_operands_is_reported_at_its_layer_and_nowhere_else(case, layer, defect):
+    """The same three defects on the fp8-emulating oracle, judged by the checker's fp8 rules."""
+    w, imgs, sc = case
+    reports, _, _ = _oracle_reports(w, imgs, sc, net=lambda cap: _DefectiveNet(w, cap, layer, defect, emulate_fp8=True), fp8=True)
+    _assert_reported_in_its_region(reports, layer, defect)
+
+
+def _misquantised_reports(w, at, defect):
+    imgs = _stress_images()[2:]                       # the synthetic image alone reaches the clamp at all four layers (asserted)
+    reports, cap, _ = _oracle_reports(w, imgs, _scores(imgs), net=lambda cap: _MisquantisingNet(w, cap, at, defect), fp8=True)
+    return reports, _clamp_shares(w, cap)
+
+
+@pytest.mark.parametrize("at,defect", [(CLAMP_240_AT, "clamp_at_240"), (SHARED_SCALE_AT, "weight_scale_shared")])
+def test_fp8_quantisation_defect_is_reported_under_the_fp8_stress_weights(case, at, defect):
+    reports, shares = _misquantised_reports(lc.fp8_stress_weights(case[0]), at, defect)
+    assert all(shares[nm][0] >= 1e-3 for nm in lc.FP8_CLAMP_LAYERS), shares
+    failing = sorted(nm for nm, r in reports.items() if not r.ok)
+    assert failing == [at], (failing, at)
+    assert at in reports[at].message and "tile (" in reports[at].message and not reports[at].coeff_fail
+
+
+def test_clamp_at_240_passes_unreported_under_the_plain_stress_weights(case):
+    """The gap that lc.fp8_stress_weights closes: with the plain stress set (and with both seeds) no activated operand of the layer
+    reaches 240, so an engine that saturated there would pass every layer."""
+    reports, shares = _misquantised_reports(lc.stress_weights(case[0]), CLAMP_240_AT, "clamp_at_240")
+    assert shares[CLAMP_240_AT][1] < 240.0
+    _assert_conditions(reports)
+
+
 def test_wrong_groupnorm_coefficient_is_reported(case):
     """The captured (A, B) are checked against the float64 GroupNorm + FiLM on their own: one coefficient off by 1e-4 relative."""
     w, imgs, sc = case
@@ -136,10 +265,13 @@ def test_wrong_groupnorm_coefficient_is_reported(case):
 def test_one_ulp_nudge_of_one_element_is_reported(case, monkeypatch):
     w, imgs, sc = case
     monkeypatch.setattr(lc, "KEEP_ARRAYS", True)
-    cap = {}
-    out = onet.restore(imgs, sc, w, emulate_bf16=True, capture=cap)
-    for name in ("enc0.rb0.h", "enc2.rb1", "fuse1", "down0"):
-        clean = lc.NetworkCheck(w, imgs, sc, cap.__getitem__, out, up_mode="plain").check(name)
+    caps = {}
+    for fp8 in (False, True):
+        cap = {}
+        caps[fp8] = (cap, onet.restore(imgs, sc, w, emulate_bf16=True, capture=cap, emulate_fp8=fp8))
+    for name, fp8 in (("enc0.rb0.h", False), ("enc2.rb1", False), ("fuse1", False), ("down0", False), ("mid.rb0.h", True)):
+        cap, out = caps[fp8]
+        clean = lc.NetworkCheck(w, imgs, sc, cap.__getitem__, out, fp8=fp8, up_mode="plain").check(name)
         assert clean.ok
         below = np.argwhere(clean.bound_ulps < 1.0)                      # (n, c, y, x)
         n, c, y, x = (int(v) for v in below[len(below) // 2])
@@ -148,7 +280,7 @@ def test_one_ulp_nudge_of_one_element_is_reported(case, monkeypatch):
         away = 1.0 if a[n, y, x, c] >= clean.exact[n, c, y, x] else -1.0
         a[n, y, x, c] = np.float32(a[n, y, x, c] + away * lc.bf16_ulp(np.float64(a[n, y, x, c]) * (1.0 + away * np.sign(a[n, y, x, c]) * 2.0 ** -9)))
         nudged[name] = a
-        r = lc.NetworkCheck(w, imgs, sc, nudged.__getitem__, out, up_mode="plain").check(name)
+        r = lc.NetworkCheck(w, imgs, sc, nudged.__getitem__, out, fp8=fp8, up_mode="plain").check(name)
         assert not r.ok and r.nfail == 1 and tuple(r.fails[0]) == (n, y, x, c), (name, r.message)
 
 

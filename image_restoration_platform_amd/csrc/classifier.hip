@@ -24,7 +24,6 @@ namespace ire {
 
 namespace {
 
-constexpr int CT_H = 16, CT_W = 256;            // output tile: 16 rows x 64 four-pixel groups
 constexpr int CG = CT_W / 4;                    // groups per tile row
 constexpr int PL_ROWS = CT_H + 2;               // halo rows -1 .. 16
 constexpr int PL_WORDS = CG + 2;                // plane row = pixels x0-4 .. x0+259 as packed u8 words: pixel x0+dx is byte 4+dx
@@ -445,12 +444,10 @@ void classifier_launch(const ClassifierTables& tb, const uint8_t* d_rgb, int n, 
                        int32_t* d_label, float* d_cond, hipStream_t stream, const float* d_film_w, const float* d_film_b, int film_n, float* d_film) {
     // d_sums (engine.cpp::ensure_io): [cap][14] sums | [cap] tickets (zero at allocation, reset by the kernel) | [cap][CLS_MAX_WG][14]
     // workgroup partials -- no memset, no second launch
-    const int tiles_x = ceil_div(w, CT_W), tiles_y = ceil_div(h, CT_H);
+    const int tiles_x = cls_tiles(h, w).tiles_x, tiles_y = cls_tiles(h, w).tiles_y;
     const int ntiles = tiles_x * tiles_y;
-    // three workgroups per CU chip-wide, an equal number of tiles each where the counts allow; every workgroup amortises its
-    // 9 KB table load over its tiles
-    int per_img = std::max(1, std::min(ntiles, CLS_MAX_WG / std::max(1, n)));
-    per_img = ceil_div(ntiles, ceil_div(ntiles, per_img));
+    // three workgroups per CU chip-wide, an equal number of tiles each where the counts allow (classifier_grid.hpp)
+    const int per_img = cls_workgroups_per_image(n, ntiles);
     dim3 grid(per_img, n);
     hipLaunchKernelGGL(classifier_scan_kernel, grid, dim3(256), 0, stream, d_rgb, h, w, tiles_x, tiles_y,
                        tb.lin16, tb.thr, tb.inv, d_sums, cls_tickets(d_sums), cls_parts(d_sums), d_is_jpeg, d_scores, d_label, d_cond,

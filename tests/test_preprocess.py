@@ -65,7 +65,16 @@ def test_abi_plan_matches_oracle_without_gpu():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("h,w,o,max_dim", [(97, 131, 1, 64), (97, 131, 6, 64), (131, 97, 8, 50), (64, 200, 3, 100), (64, 200, 5, 100),
-                                            (200, 64, 7, 33), (50, 70, 2, 2048), (50, 70, 4, 2048), (50, 70, 1, 2048), (301, 777, 6, 256)])
+                                            (200, 64, 7, 33), (50, 70, 2, 2048), (50, 70, 4, 2048), (50, 70, 1, 2048), (301, 777, 6, 256),
+                                            # reductions far beyond 6x, outputs of one row / one pixel: 1 x 7 and 1 x 1 from 600 x 5000 (a
+                                            # vertical pass with ~3600 taps per output; rotated, 30001), 1 x 1 from 48 x 4096 either way up
+                                            (600, 5000, 1, 7), (600, 5000, 6, 7), (48, 4096, 1, 16), (4096, 48, 6, 16),
+                                            (8, 8192, 1, 2048),           # the widest legal row -> 2 x 2048
+                                            (3, 2500, 6, 2048),           # the box comes from the stored size, applied after the rotation -> 2 x 1
+                                            (2049, 1, 1, 2048), (1, 2049, 1, 2048),          # scale 2049 / 2048 on a one-pixel-wide image
+                                            # orientation only, more than one workgroup per row (600 and, swapped, 40 columns)
+                                            (40, 600, 2, 2048), (40, 600, 3, 2048), (40, 600, 4, 2048), (40, 600, 5, 2048), (40, 600, 6, 2048),
+                                            (40, 600, 7, 2048), (40, 600, 8, 2048)])
 def test_engine_preprocess_bit_exact_vs_oracle(engine, h, w, o, max_dim):
     a = _img(h, w, seed=o)
     exp, _ = opp.preprocess_pixels(a, o, max_dim)

@@ -169,6 +169,25 @@ def test_classify_inside_equals_given_scores_and_timings(engine):
     assert t["restore_ms"] > 0 and t["total_ms"] >= t["restore_ms"] and t["classify_ms"] > 0
 
 
+def test_benchmark_call_classifies_inside_as_the_oracle_does(engine):
+    """bench.py's call itself: restore_tensor of 8 x 1024 x 1024 with flags and no scores.  The classifier runs inside in its three-round
+    launch (86 workgroups per image, the last two of two tiles) and each image's last workgroup writes the FiLM vector; the same
+    call given the CPU oracle's scores must deliver equal bytes.  (Engine against engine on the network side: no network oracle.)"""
+    import sys
+    import torch
+    sys.path.insert(0, HERE)
+    import classifier_cases as cc
+    n, h, w, _, want = cc.LAUNCHES["benchmark"]
+    assert (n, h, w) == (8, 1024, 1024) and cc.classifier_grid(n, h, w) == want and want[3] == 3
+    imgs, jp, ref = cc.launch_batch("benchmark")
+    x = torch.from_numpy(imgs).cuda()
+    inside = engine.restore_tensor(x, is_jpeg_u8=torch.from_numpy(jp).cuda()).clone()
+    given = engine.restore_tensor(x, scores=torch.from_numpy(np.stack([r[0] for r in ref])).cuda())
+    torch.cuda.synchronize()
+    assert torch.equal(inside, given), [i for i in range(n) if not torch.equal(inside[i], given[i])]
+    assert (inside.int() - x.int()).abs().float().mean().item() > 1.0          # not the identity
+
+
 def test_conditioning_matters(engine):
     imgs = synth.batch(1, 64, 64)
     a = engine.restore(imgs, scores=np.zeros((1, 7)))

@@ -8,6 +8,7 @@ LIB_PATH = os.environ.get("IRE_LIB") or os.path.join(HERE, "lib", "libire.so")  
 IRE_OK, IRE_ERR_INVALID_INPUT, IRE_ERR_TIMEOUT, IRE_ERR_UNAVAILABLE, IRE_ERR_INTERNAL = range(5)
 IRE_FLAG_RESULT_PNG_BASE64 = 1
 IRE_FLAG_RESULT_PNG_DEFLATE = 4
+IRE_FLAG_RESULT_JPEG = 8
 IRE_ABI_VERSION = 3      # include/ire.h; load() refuses a library of another version (tests/test_abi.py cross-checks the three copies)
 
 
@@ -62,6 +63,9 @@ SYMBOLS = {
     "ire_png_deflate_base64_bound": (ctypes.c_size_t, [_i, _i]),
     "ire_encode_png_deflate_base64_fit_device": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp]),
     "ire_encode_png_deflate_base64_fit": (_i, [_vp, _u8p, _i, _i, _i, _u8p, ctypes.c_size_t, _vp]),
+    "ire_jpeg_base64_bound": (ctypes.c_size_t, [_i, _i]),
+    "ire_encode_jpeg_base64_fit_device": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp]),
+    "ire_encode_jpeg_base64_fit": (_i, [_vp, _u8p, _i, _i, _i, _u8p, ctypes.c_size_t, _vp]),
     "ire_submit_fit": (_i, [_vp, _u8p, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
     "ire_submit": (_i, [_vp, _u8p, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
     "ire_restore_tiled_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -46,6 +46,7 @@ SOURCES = [
     ("preprocess.hip", []),
     ("encode.hip", []),
     ("deflate.hip", []),
+    ("jpeg.hip", []),
     ("engine.cpp", []),
     ("strips.cpp", []),
     ("api.cpp", []),

@@ -15,6 +15,7 @@
 #include "affinity.hpp"
 #include "batcher.hpp"
 #include "deflate.hpp"
+#include "jpeg.hpp"
 #include "encode.hpp"
 #include "engine.hpp"
 #include "fusion.hpp"
@@ -111,15 +112,18 @@ struct HipBatchBackend {
     }
     int max_batch() const { return E.max_batch(); }
     bool deflate() const { return (E.flags() & IRE_FLAG_RESULT_PNG_DEFLATE) != 0; }
-    bool text() const { return (E.flags() & (IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE)) != 0; }
-    // a result's place in the staging: the pixels, the stored PNG's text, or [uint64 count | the compressed PNG's text, bound-sized]
-    size_t out_bytes(int h, int w) const { return deflate() ? 8 + png_deflate_base64_bound(h, w) : text() ? png_base64_chars(h, w) : (size_t)h * w * 3; }
-    // the batcher's optional hook: only the compressed text is shorter than its place
+    bool jpeg() const { return (E.flags() & IRE_FLAG_RESULT_JPEG) != 0; }
+    bool var_len() const { return deflate() || jpeg(); }      // the text's length depends on the pixels
+    bool text() const { return (E.flags() & (IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG)) != 0; }
+    size_t var_bound(int h, int w) const { return jpeg() ? jpeg_base64_bound(h, w) : png_deflate_base64_bound(h, w); }
+    // a result's place in the staging: the pixels, the stored PNG's text, or [uint64 count | the compressed PNG's or the JPEG's text, bound-sized]
+    size_t out_bytes(int h, int w) const { return var_len() ? 8 + var_bound(h, w) : text() ? png_base64_chars(h, w) : (size_t)h * w * 3; }
+    // the batcher's optional hook: only a text of data-dependent length is shorter than its place
     const uint8_t* result_view(const uint8_t* place, int h, int w, size_t* len) const {
-        if (!deflate()) { *len = out_bytes(h, w); return place; }
+        if (!var_len()) { *len = out_bytes(h, w); return place; }
         uint64_t n = 0;
         std::memcpy(&n, place, 8);
-        *len = (size_t)std::min<uint64_t>(n, png_deflate_base64_bound(h, w));
+        *len = (size_t)std::min<uint64_t>(n, var_bound(h, w));
         return place + 8;
     }
     void start() {
@@ -276,9 +280,9 @@ int ire_init(const ire_config* cfg, ire_engine** out) {
     return guarded([&] {
         if (!cfg || !out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_init");
         if (cfg->struct_size < sizeof(ire_config)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.struct_size");
-        if (cfg->flags & ~(uint32_t)(IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
-        if ((cfg->flags & IRE_FLAG_RESULT_PNG_BASE64) && (cfg->flags & IRE_FLAG_RESULT_PNG_DEFLATE))
-            fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");
+        if (cfg->flags & ~(uint32_t)(IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG))
+            fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
+        if ((cfg->flags & (cfg->flags - 1)) != 0) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");      // (every known bit is a result format)
         *out = nullptr;
         std::unique_ptr<ire_engine> E(new ire_engine());
         E->eng.reset(new Engine(*cfg));
@@ -441,6 +445,25 @@ int ire_encode_png_deflate_base64_fit(ire_engine* e, const uint8_t* rgb, int n, 
     });
 }
 
+size_t ire_jpeg_base64_bound(int h, int w) { return (h >= 1 && w >= 1 && h <= 8192 && w <= 8192) ? jpeg_base64_bound(h, w) : 0; }
+
+int ire_encode_jpeg_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes, size_t image_pitch_bytes, uint8_t* d_chars,
+                                      size_t stride_bytes, uint64_t* d_lens, void* stream) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, (hipStream_t)stream, [&] {
+            E.encode_jpeg_base64_fit_device(d_rgb, n, h, w, row_pitch_bytes, image_pitch_bytes, d_chars, stride_bytes, d_lens, (hipStream_t)stream);
+        });
+    });
+}
+
+int ire_encode_jpeg_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes, uint64_t* lens) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, E.main_stream(), [&] { E.encode_jpeg_base64_fit_host(rgb, n, h, w, chars, stride_bytes, lens); });
+    });
+}
+
 int ire_restore_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, const double* scores, const uint8_t* is_jpeg, uint8_t* out_rgb,
                     ire_timings* t) {
     return guarded([&] {
@@ -577,7 +600,7 @@ int ire_poll(ire_engine* e, ire_job* job, int timeout_ms, uint8_t* out_rgb, doub
         eng(e);
         if (!job || !job->j) fail(IRE_ERR_INVALID_INPUT, "invalid job handle");
         // a result of data-dependent length has no way out of this call: refuse it and keep the job (no result is lost to a wrong call)
-        if (e->backend->deflate()) fail(IRE_ERR_INVALID_INPUT, "invalid: use ire_poll_text (this engine's results have data-dependent lengths)");
+        if (e->backend->var_len()) fail(IRE_ERR_INVALID_INPUT, "invalid: use ire_poll_text (this engine's results have data-dependent lengths)");
         std::string err;
         const int st = e->batcher->poll(job->j, timeout_ms, out_rgb, scores_out, t, &err);
         if (st == IRE_ERR_TIMEOUT) fail(IRE_ERR_TIMEOUT, "timeout: job still pending");       // the handle stays valid: poll again or ire_job_release

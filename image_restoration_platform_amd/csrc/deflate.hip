@@ -495,10 +495,15 @@ void encode_png_deflate_base64_launch(const unsigned char* d_rgb, int n, int h, 
     for (int l = 0; l < 8; ++l) ops.lvl[l] = gf_x_pow_8n((unsigned long long)kSlice << l);
     ops.wg = gf_x_pow_8n((unsigned long long)kCrcWG * kSlice);
     hipLaunchKernelGGL(deflate_crc_kernel, dim3(L.nwg, n), dim3(kCrcWG), 0, s, files, (unsigned long long)L.file_pitch, flen, ops, parts, tickets);
-    const unsigned long long groups12 = (g.file_bound + 11) / 12;
-    hipLaunchKernelGGL(deflate_base64_kernel, dim3((unsigned)((groups12 + 255) / 256), n), dim3(256), 0, s, files, (unsigned long long)L.file_pitch, flen, d_chars,
-                       (unsigned long long)text_pitch);
+    base64_device_length_launch(files, L.file_pitch, flen, (size_t)g.file_bound, n, d_chars, text_pitch, s);
     IRE_HIP(hipGetLastError());
+}
+
+void base64_device_length_launch(const unsigned char* d_files, size_t file_pitch, const unsigned long long* d_flen, size_t file_bound, int n, unsigned char* d_chars,
+                                 size_t text_pitch, hipStream_t s) {
+    const unsigned long long groups12 = ((unsigned long long)file_bound + 11) / 12;
+    hipLaunchKernelGGL(deflate_base64_kernel, dim3((unsigned)((groups12 + 255) / 256), n), dim3(256), 0, s, d_files, (unsigned long long)file_pitch, d_flen, d_chars,
+                       (unsigned long long)text_pitch);
 }
 
 }  // namespace ire

@@ -5,6 +5,7 @@
 #include "engine.hpp"
 #include "encode.hpp"
 #include "deflate.hpp"
+#include "jpeg.hpp"
 
 #include <chrono>
 #include <cmath>
@@ -46,9 +47,9 @@ Engine::Engine(const ire_config& cfg) {
     if (max_batch_ > 64) fail(IRE_ERR_INVALID_INPUT, "invalid max_batch (1..64)");
     num_lanes_ = cfg.num_streams > 0 ? cfg.num_streams : 1;
     if (num_lanes_ > 16) num_lanes_ = 16;
-    if (cfg.flags & ~(uint32_t)(IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
-    if ((cfg.flags & IRE_FLAG_RESULT_PNG_BASE64) && (cfg.flags & IRE_FLAG_RESULT_PNG_DEFLATE))
-        fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");
+    if (cfg.flags & ~(uint32_t)(IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG))
+        fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
+    if ((cfg.flags & (cfg.flags - 1)) != 0) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");
     flags_ = cfg.flags;
     sw_ = ConvSwitches::from_env();
     cus_ = persistent_grid_cus();
@@ -374,6 +375,46 @@ void Engine::encode_png_deflate_base64_fit_host(const uint8_t* rgb, int n, int h
         lens[i] = len;
         std::memcpy(chars + stride * i, stage.data() + cpad * i + 8, (size_t)len);
     }
+}
+
+// ---- the JPEG encoder (jpeg.hip): the same window, texts of data-dependent length and their counts -----------------------------------
+
+void Engine::encode_jpeg_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, uint8_t* d_lens,
+                                size_t lens_pitch, hipStream_t s) {
+    if (stride < jpeg_base64_bound(h, w)) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the JPEG encoder: smaller than ire_jpeg_base64_bound(h, w)");
+    if (row_pitch < (size_t)3 * w || (n > 1 && image_pitch < row_pitch * (size_t)(h - 1) + (size_t)3 * w))
+        fail(IRE_ERR_INVALID_INPUT, "invalid pitch for the JPEG encoder: rows or images overlap");
+    ensure_enc_scratch(jpeg_scratch_bytes(n, h, w), jpeg_scratch_bytes(max_batch_, h, w));
+    encode_jpeg_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_enc_scratch_.get<uint8_t>(), d_chars, stride, d_lens, lens_pitch, s);
+}
+
+void Engine::encode_jpeg_base64_fit_device(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride,
+                                           uint64_t* d_lens, hipStream_t s) {
+    if (!d_rgb || !d_chars || !d_lens || n < 1 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the JPEG encoder (1..max_batch images)");
+    if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the JPEG encoder: height and width must be in 1..8192");
+    encode_jpeg_window(d_rgb, n, h, w, row_pitch, image_pitch, d_chars, stride, reinterpret_cast<uint8_t*>(d_lens), sizeof(uint64_t), s);
+}
+
+// pixels up, [count | text] per image down: the counts first (8 bytes each), then each text at its real length
+void Engine::encode_jpeg_base64_fit_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride, uint64_t* lens) {
+    if (!rgb || !chars || !lens) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the JPEG encoder: null buffer");
+    if (n < 1 || n > max_batch_ || h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the JPEG encoder (1..max_batch images, 1..8192 per side)");
+    const size_t ib = (size_t)h * w * 3, cb = jpeg_base64_bound(h, w), cpad = (cb + 8 + 255) / 256 * 256;
+    if (stride < cb) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the JPEG encoder: smaller than ire_jpeg_base64_bound(h, w)");
+    const size_t in_pad = (ib * n + 255) / 256 * 256;
+    uint8_t* d_px = ensure_enc_io(in_pad + cpad * (size_t)n);
+    hipStream_t s = main_stream_;
+    IRE_HIP(hipMemcpyAsync(d_px, rgb, ib * n, hipMemcpyHostToDevice, s));
+    uint8_t* d_txt = d_px + in_pad;
+    encode_jpeg_window(d_px, n, h, w, (size_t)3 * w, ib, d_txt + 8, cpad, d_txt, cpad, s);
+    // the bound is several times a real text (it doubles every byte for stuffing): fetch the counts, then only what they name
+    for (int i = 0; i < n; ++i) IRE_HIP(hipMemcpyAsync(&lens[i], d_txt + cpad * i, 8, hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < n; ++i) {
+        if (lens[i] > cb) fail(IRE_ERR_INTERNAL, "internal: the JPEG encoder reported a length beyond its bound");
+        IRE_HIP(hipMemcpyAsync(chars + stride * i, d_txt + cpad * i + 8, (size_t)lens[i], hipMemcpyDeviceToHost, s));
+    }
+    IRE_HIP(hipStreamSynchronize(s));
 }
 
 void Engine::free_workspace() {
@@ -846,9 +887,10 @@ void Engine::restore_fit_device(const uint8_t* d_rgb, int n, int h, int w, const
     crop_window_launch(d_pad_out_.get<uint8_t>(), n, fit_dim(h), fit_dim(w), d_out, h, w, stream);
 }
 
-// the batcher's results as text: the stored PNG's characters, or with IRE_FLAG_RESULT_PNG_DEFLATE [uint64 count | characters] per result
+// the batcher's results as text: the stored PNG's characters, or with IRE_FLAG_RESULT_PNG_DEFLATE / IRE_FLAG_RESULT_JPEG [uint64 count | characters] per result
 void Engine::encode_result(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_txt, size_t txt_stride, hipStream_t s) {
     if (flags_ & IRE_FLAG_RESULT_PNG_DEFLATE) encode_deflate_window(d_rgb, n, h, w, row_pitch, image_pitch, d_txt + 8, txt_stride, d_txt, txt_stride, s);
+    else if (flags_ & IRE_FLAG_RESULT_JPEG) encode_jpeg_window(d_rgb, n, h, w, row_pitch, image_pitch, d_txt + 8, txt_stride, d_txt, txt_stride, s);
     else encode_window(d_rgb, n, h, w, row_pitch, image_pitch, d_txt, txt_stride, s);
 }
 

@@ -175,6 +175,11 @@ public:
     void encode_png_deflate_base64_fit_device(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride,
                                               uint64_t* d_lens, hipStream_t s);
     void encode_png_deflate_base64_fit_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride, uint64_t* lens);
+    // jpeg.hip: the same window as a baseline JPEG (quality 85, 4:4:4): at most jpeg_base64_bound(h, w) characters per image, `stride`
+    // apart, and each text's real character count (n uint64)
+    void encode_jpeg_base64_fit_device(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride,
+                                       uint64_t* d_lens, hipStream_t s);
+    void encode_jpeg_base64_fit_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride, uint64_t* lens);
     // Any-size jobs (h, w in 1..8192): edge-replicate pad to (max(16, ceil8 h), max(16, ceil8 w)) into the engine's padded
     // staging, the network on the padded shape, the top-left h x w window as the result.  The classifier always sees the
     // ORIGINAL pixels.  A shape restore_device takes as it is skips the pad and runs exactly as restore_device does.
@@ -182,7 +187,7 @@ public:
                             hipStream_t stream);
     void restore_fit_host(const uint8_t* rgb, int n, int h, int w, const double* scores, const uint8_t* is_jpeg, uint8_t* out, ire_timings* t);
     // batcher form (restore_device_mixed for any size).  d_txt == null: d_out receives the n*h*w*3 result pixels.  d_txt != null:
-    // the results leave as text (png_base64_chars(h, w) characters each, txt_stride apart; with IRE_FLAG_RESULT_PNG_DEFLATE a uint64
+    // the results leave as text (png_base64_chars(h, w) characters each, txt_stride apart; with IRE_FLAG_RESULT_PNG_DEFLATE / IRE_FLAG_RESULT_JPEG a uint64
     // character count and then the characters), encoded where the network left them; d_out is then working space of n*h*w*3 bytes.
     void restore_fit_device_mixed(const uint8_t* d_rgb, int n, int h, int w, const double* host_scores, const uint8_t* has_scores,
                                   const uint8_t* d_is_jpeg, uint8_t* d_out, uint8_t* d_txt, size_t txt_stride, hipStream_t stream);
@@ -233,6 +238,8 @@ private:
     uint8_t* ensure_enc_io(size_t need);      // d_enc_io_ with room for `need` bytes
     void encode_deflate_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, uint8_t* d_lens,
                                size_t lens_pitch, hipStream_t s);
+    void encode_jpeg_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, uint8_t* d_lens,
+                            size_t lens_pitch, hipStream_t s);
     void encode_result(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_txt, size_t txt_stride, hipStream_t s);
     void ensure_io(int n, int h, int w);
     void ensure_workspace(int n, int h, int w);

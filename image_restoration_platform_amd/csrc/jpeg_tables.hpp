@@ -1,0 +1,179 @@
+// jpeg_tables.hpp -- everything about the device's JPEG file that needs no GPU: the two quantisation tables at quality 85, the
+// zig-zag order, the Annex K Huffman tables as (code, length) per symbol, the file's head for a given (h, w), and the size bound
+// with its derivation.  Host-only, header-only, plain C++17: jpeg.hip initialises its __constant__ tables from the constexpr
+// functions here, tests/native/jpeg_tables_dump.cpp prints all of it for comparison with tests/jpeg_model.py.
+//
+// The format (tests/jpeg_model.py states it in full): baseline sequential DCT, 8 bit, Y Cb Cr at 1 x 1 each (4:4:4), one interleaved
+// scan, a restart interval of kJpegR MCUs in raster order.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <initializer_list>
+
+namespace ire {
+namespace jpegtab {
+
+constexpr int kJpegR = 16;               // MCUs per restart interval
+constexpr int kJpegQuality = 85;
+constexpr int kHeaderBytes = 629;        // SOI 2 | APP0 18 | DQT 69 x 2 | SOF0 19 | DHT 33 + 183 + 33 + 183 | DRI 6 | SOS 14
+constexpr int kSofDims = 2 + 18 + 69 + 69 + 5;      // file offset of SOF0's height (2 bytes, then the width's 2)
+
+constexpr unsigned char kK1Luminance[64] = {
+    16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+    18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+constexpr unsigned char kK2Chrominance[64] = {
+    17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+    99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+// kZigzag[k]: the natural (row-major) index of the k-th coefficient in zig-zag order
+constexpr unsigned char kZigzag[64] = {
+    0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// IJG quality scaling, baseline: (q * scale + 50) / 100 clamped to 1..255, scale = 200 - 2 * quality above 50.  table 0: luminance,
+// 1: chrominance; natural order.
+constexpr int quant_at(int table, int natural) {
+    const int scale = kJpegQuality < 50 ? 5000 / kJpegQuality : 200 - 2 * kJpegQuality;
+    const int v = ((table ? kK2Chrominance[natural] : kK1Luminance[natural]) * scale + 50) / 100;
+    return v < 1 ? 1 : v > 255 ? 255 : v;
+}
+
+// ---- the quantiser's division as a multiplication --------------------------------------------------------------------------------
+// q(c) = sign(c) * floor((|c| + d / 2) / d), d = 8 * quant.  With M = ceil(2^32 / d), e = M d - 2^32 lies in [0, d) and
+// floor(x / d) = (x * M) >> 32 for every x with x * e < 2^32: x <= 8208 + 1020 < 2^14 here and e < d <= 2040 < 2^11.
+// tests/native/jpeg_tables_dump.cpp checks the identity for every divisor and every x < 2^16.
+constexpr unsigned quant_recip(int table, int natural) {
+    const unsigned long long d = 8ull * (unsigned)quant_at(table, natural);
+    return (unsigned)(((1ull << 32) + d - 1) / d);
+}
+
+// ---- Annex K Huffman tables -------------------------------------------------------------------------------------------------------
+constexpr unsigned char kDcLumBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+constexpr unsigned char kDcChrBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+constexpr unsigned char kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+constexpr unsigned char kAcLumBits[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
+constexpr unsigned char kAcLumVals[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1, 0x08,
+    0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28,
+    0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59,
+    0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89,
+    0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6,
+    0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
+    0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+constexpr unsigned char kAcChrBits[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
+constexpr unsigned char kAcChrVals[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91,
+    0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26,
+    0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58,
+    0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87,
+    0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4,
+    0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
+    0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+
+// Annex C: the symbols of a BITS / HUFFVAL list get consecutive codes, shortest first.  code[sym] = value | length << 16 (0: no code).
+struct HuffCodes { unsigned code[256]; };
+constexpr HuffCodes huff_codes(const unsigned char* bits, const unsigned char* vals) {
+    HuffCodes t{};
+    unsigned code = 0;
+    int k = 0;
+    for (int len = 1; len <= 16; ++len) {
+        for (int i = 0; i < bits[len - 1]; ++i) t.code[vals[k++]] = code++ | ((unsigned)len << 16);
+        code <<= 1;
+    }
+    return t;
+}
+constexpr HuffCodes dc_codes(int table) { return huff_codes(table ? kDcChrBits : kDcLumBits, kDcVals); }
+constexpr HuffCodes ac_codes(int table) { return huff_codes(table ? kAcChrBits : kAcLumBits, table ? kAcChrVals : kAcLumVals); }
+
+// ---- the file's head --------------------------------------------------------------------------------------------------------------
+struct JpegHeader { unsigned char b[kHeaderBytes]; };
+constexpr JpegHeader jpeg_header(int h, int w) {
+    JpegHeader o{};
+    int n = 0;
+    auto put = [&](int v) { o.b[n++] = (unsigned char)v; };
+    auto seg = [&](int marker, int payload) { put(0xff); put(marker); put((payload + 2) >> 8); put((payload + 2) & 0xff); };
+    put(0xff); put(0xd8);
+    seg(0xe0, 14);
+    for (int v : {(int)'J', (int)'F', (int)'I', (int)'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0}) put(v);      // version 1.01, density 1:1 without units, no thumbnail
+    for (int t = 0; t < 2; ++t) {
+        seg(0xdb, 65);
+        put(t);
+        for (int k = 0; k < 64; ++k) put(quant_at(t, kZigzag[k]));
+    }
+    seg(0xc0, 15);
+    put(8); put(h >> 8); put(h & 0xff); put(w >> 8); put(w & 0xff); put(3);
+    for (int v : {1, 0x11, 0, 2, 0x11, 1, 3, 0x11, 1}) put(v);
+    for (int t = 0; t < 2; ++t) {
+        seg(0xc4, 1 + 16 + 12);
+        put(t);
+        for (int k = 0; k < 16; ++k) put((t ? kDcChrBits : kDcLumBits)[k]);
+        for (int k = 0; k < 12; ++k) put(kDcVals[k]);
+        seg(0xc4, 1 + 16 + 162);
+        put(0x10 | t);
+        for (int k = 0; k < 16; ++k) put((t ? kAcChrBits : kAcLumBits)[k]);
+        for (int k = 0; k < 162; ++k) put((t ? kAcChrVals : kAcLumVals)[k]);
+    }
+    seg(0xdd, 2);
+    put(kJpegR >> 8); put(kJpegR & 0xff);
+    seg(0xda, 10);
+    for (int v : {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0}) put(v);
+    return o;      // n == kHeaderBytes (checked by the native test)
+}
+
+// ---- the size bound ---------------------------------------------------------------------------------------------------------------
+// 1. Amplitudes.  The forward DCT's output, scaled by 8 as the "islow" algorithm leaves it, of samples in -128..127 is in magnitude at
+//    most 8 * 128 * a(u) * a(v), a(u) = C(u) / 2 * sum_x |cos((2x + 1) u pi / 16)| (every sample at full scale with the sign of its
+//    basis value).  kCoefMax holds that product rounded, plus 16 for islow's own error: its 13-bit constants are off by at most
+//    2^-14 relative, and it rounds twice per pass, which comes to a few units of the output scale.  Natural order.
+constexpr unsigned short kCoefMax[64] = {
+    8208, 7439, 7584, 7439, 8208, 7439, 7584, 7439,
+    7439, 6742, 6874, 6742, 7439, 6742, 6874, 6742,
+    7584, 6874, 7008, 6874, 7584, 6874, 7008, 6874,
+    7439, 6742, 6874, 6742, 7439, 6742, 6874, 6742,
+    8208, 7439, 7584, 7439, 8208, 7439, 7584, 7439,
+    7439, 6742, 6874, 6742, 7439, 6742, 6874, 6742,
+    7584, 6874, 7008, 6874, 7584, 6874, 7008, 6874,
+    7439, 6742, 6874, 6742, 7439, 6742, 6874, 6742};
+constexpr int bit_length(unsigned v) { int n = 0; while (v) { ++n; v >>= 1; } return n; }
+// 2. Categories.  The largest magnitude category ("size") at zig-zag position k: of the quantised amplitude bound, and at k = 0 of
+//    twice that (the DC is sent as a difference).
+constexpr int size_max(int table, int k) {
+    const int nat = kZigzag[k], q = quant_at(table, nat);
+    const unsigned m = (kCoefMax[nat] + 4u * q) / (8u * q);
+    return bit_length(k == 0 ? 2 * m : m);
+}
+// 3. One block.  The exact maximum, over every sequence of (run, size) symbols whose sizes respect step 2, of the bits they take with
+//    the fixed tables: dynamic programming over the position p of the last non-zero coefficient so far.  best[p] = the most bits of
+//    the DC and positions 1..p when p is non-zero; a run of r zeros before p costs floor(r / 16) ZRL codes and the code of
+//    (r mod 16, size); a block whose last non-zero lies before 63 ends with EOB.
+constexpr unsigned block_bits_max(int table) {
+    const HuffCodes dc = dc_codes(table), ac = ac_codes(table);
+    int smax[64] = {};
+    for (int k = 0; k < 64; ++k) smax[k] = size_max(table, k);
+    unsigned best[64] = {};
+    for (int s = 0; s <= smax[0]; ++s) if ((dc.code[s] >> 16) + s > best[0]) best[0] = (dc.code[s] >> 16) + s;
+    for (int p = 1; p < 64; ++p)
+        for (int prev = 0; prev < p; ++prev) {
+            const int run = p - prev - 1;
+            unsigned sym = 0;
+            for (int s = 1; s <= smax[p]; ++s) { const unsigned v = (ac.code[((run & 15) << 4) | s] >> 16) + s; if (v > sym) sym = v; }
+            const unsigned v = best[prev] + (unsigned)(run >> 4) * (ac.code[0xf0] >> 16) + sym;
+            if (v > best[p]) best[p] = v;
+        }
+    unsigned out = best[63];
+    for (int p = 0; p < 63; ++p) if (best[p] + (ac.code[0x00] >> 16) > out) out = best[p] + (ac.code[0x00] >> 16);
+    return out;
+}
+constexpr unsigned kMcuBitsMax = block_bits_max(0) + 2 * block_bits_max(1);
+static_assert(kMcuBitsMax == 2343, "897 bits for a luminance block, 723 for a chrominance block");
+// 4. One interval of nmcu MCUs: its bits padded to a byte, every byte doubled by stuffing (a 0x00 behind each 0xFF), the marker.
+constexpr size_t interval_bound(unsigned nmcu) { return 2 * (((size_t)nmcu * kMcuBitsMax + 7) / 8) + 2; }
+// 5. The file: the head, the full intervals, the last one.
+constexpr size_t jpeg_file_bound(int h, int w) {
+    const size_t nmcu = (size_t)((h + 7) / 8) * (size_t)((w + 7) / 8);
+    const size_t full = nmcu / kJpegR, tail = nmcu % kJpegR;
+    return kHeaderBytes + full * interval_bound(kJpegR) + (tail ? interval_bound((unsigned)tail) : 0);
+}
+constexpr size_t jpeg_base64_bound(int h, int w) { return (jpeg_file_bound(h, w) + 2) / 3 * 4; }
+
+}  // namespace jpegtab
+}  // namespace ire

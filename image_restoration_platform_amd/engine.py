@@ -203,9 +203,11 @@ class Engine:
         return int(self._lib.ire_max_batch_for(self._h, int(h), int(w)))
 
     def poll(self, job, timeout_ms=-1):
-        """-> (restored [H,W,3] uint8 -- or, for an engine created with flags=IRE_FLAG_RESULT_PNG_BASE64 / IRE_FLAG_RESULT_PNG_DEFLATE,
-        the `bytes` of the base64 text of its PNG file --, scores[7], timings)"""
+        """-> (restored [H,W,3] uint8 -- or, for an engine created with flags=IRE_FLAG_RESULT_PNG_BASE64 / IRE_FLAG_RESULT_PNG_DEFLATE /
+        IRE_FLAG_RESULT_JPEG, the `bytes` of the base64 text of its PNG / JPEG file --, scores[7], timings)"""
         handle, h, w = job
+        if getattr(self, "_flags", 0) & _lib.IRE_FLAG_RESULT_JPEG:
+            return self._poll_text(handle, timeout_ms, self.jpeg_base64_bound(h, w))
         if getattr(self, "_flags", 0) & _lib.IRE_FLAG_RESULT_PNG_DEFLATE:
             return self._poll_text(handle, timeout_ms, self.png_deflate_base64_bound(h, w))
         text = bool(getattr(self, "_flags", 0) & _lib.IRE_FLAG_RESULT_PNG_BASE64)
@@ -218,7 +220,7 @@ class Engine:
         return out, scores, {"classify_ms": t.classify_ms, "restore_ms": t.restore_ms, "total_ms": t.total_ms}
 
     def _poll_text(self, handle, timeout_ms, cap):
-        """ire_poll_text: a result whose length depends on the data (IRE_FLAG_RESULT_PNG_DEFLATE) -> (`bytes` of its real length, ...)."""
+        """ire_poll_text: a result whose length depends on the data (IRE_FLAG_RESULT_PNG_DEFLATE, IRE_FLAG_RESULT_JPEG) -> (`bytes` of its real length, ...)."""
         out = np.empty(cap, np.uint8)
         n = ctypes.c_size_t(0)
         scores = np.zeros(7, np.float64)
@@ -267,6 +269,46 @@ class Engine:
         self._check(self._lib.ire_encode_png_deflate_base64_fit_device(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), n, h, w, sr, si if n > 1 else max(si, sr * h),
                                                                        ctypes.c_void_p(out.data_ptr()), stride, ctypes.c_void_p(lens.data_ptr()),
                                                                        self._stream_ptr(stream)))
+        return out[:, :cb], lens
+
+    def jpeg_base64_bound(self, h, w):
+        """The most characters the JPEG encoder can give for an h x w image (0 outside 1..8192): sizes every buffer."""
+        return int(self._lib.ire_jpeg_base64_bound(int(h), int(w)))
+
+    def encode_jpeg_base64_fit(self, rgb):
+        """[N,H,W,3] (or [H,W,3]) uint8, any size 1..8192 per side -> list of N `bytes` (one for a single image): the base64 text of a
+        baseline JPEG file of each image (quality 85, 4:4:4), encoded on the device; each of its real length."""
+        single = np.asarray(rgb).ndim == 3
+        x = self._as_batch(rgb)
+        n, h, w, _ = x.shape
+        cb = self.jpeg_base64_bound(h, w)
+        if cb == 0:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid image size for the JPEG encoder: height and width must be in 1..8192")
+        stride = (cb + 15) // 16 * 16
+        out = np.empty((n, stride), np.uint8)
+        lens = np.zeros(n, np.uint64)
+        self._check(self._lib.ire_encode_jpeg_base64_fit(self._h, _ptr(x), n, h, w, _ptr(out), stride, _ptr(lens)))
+        res = [out[i, :int(lens[i])].tobytes() for i in range(n)]
+        return res[0] if single else res
+
+    def encode_jpeg_base64_fit_tensor(self, rgb_u8, stream=None):
+        """cuda uint8 [N,h,w,3], possibly a window of a larger tensor -> (cuda uint8 [N, bound] ASCII, cuda int64 [N] character counts),
+        asynchronous on the stream: text i is out[i, :lens[i]]."""
+        import torch
+        assert rgb_u8.is_cuda and rgb_u8.dtype == torch.uint8 and rgb_u8.dim() == 4 and rgb_u8.shape[3] == 3
+        n, h, w, _ = rgb_u8.shape
+        si, sr, sp, sc = rgb_u8.stride()
+        if sc != 1 or sp != 3 or sr < 3 * w:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid tensor layout for the JPEG encoder: pixels must be dense RGB")
+        cb = self.jpeg_base64_bound(h, w)
+        if cb == 0:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid image size for the JPEG encoder: height and width must be in 1..8192")
+        stride = (cb + 3) // 4 * 4
+        out = torch.empty((n, stride), dtype=torch.uint8, device=rgb_u8.device)
+        lens = torch.zeros(n, dtype=torch.int64, device=rgb_u8.device)      # (the counts are uint64 and < 2^63)
+        self._check(self._lib.ire_encode_jpeg_base64_fit_device(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), n, h, w, sr, si if n > 1 else max(si, sr * h),
+                                                                ctypes.c_void_p(out.data_ptr()), stride, ctypes.c_void_p(lens.data_ptr()),
+                                                                self._stream_ptr(stream)))
         return out[:, :cb], lens
 
     def encode_png_base64(self, rgb):

@@ -71,6 +71,9 @@ def encode_jpeg_base64(rgb, quality=85):
 #               with an engine created with IRE_FLAG_RESULT_PNG_BASE64 the batcher hands the text back instead of pixels
 #   png-deflate-device  a COMPRESSED PNG (Paeth filter, Huffman-coded deflate blocks) + its base64 text written by the GPU
 #               (csrc/deflate.hip): no host codec work either, and a shorter string; the engine flag is IRE_FLAG_RESULT_PNG_DEFLATE
+#   jpeg-device  a baseline JPEG q85 4:4:4 (the reference's settings; byte for byte what libjpeg-turbo writes with a restart interval
+#               of 16 MCUs) + its base64 text written by the GPU (csrc/jpeg.hip): no host codec work, and the shortest string; the
+#               engine flag is IRE_FLAG_RESULT_JPEG
 RESULT_CODEC = os.environ.get("IRE_RESULT_CODEC", "png")
 
 
@@ -142,6 +145,8 @@ class EngineRestorer:
             return self.engine.encode_png_base64_fit(result).decode("ascii")      # any width: the device encoder
         if self.result_codec == "png-deflate-device":
             return self.engine.encode_png_deflate_base64_fit(result).decode("ascii")
+        if self.result_codec == "jpeg-device":
+            return self.engine.encode_jpeg_base64_fit(result).decode("ascii")
         return encode_png_base64(result)
 
     @staticmethod
@@ -160,7 +165,7 @@ class EngineRestorer:
         shapes = {d[0].shape for d in decoded}
         if len(shapes) != 1:
             raise ValueError("invalid images: fusion views must have identical dimensions")
-        text_engine = bool(getattr(self.engine, "_flags", 0) & (_lib.IRE_FLAG_RESULT_PNG_BASE64 | _lib.IRE_FLAG_RESULT_PNG_DEFLATE))      # poll returns the text
+        text_engine = bool(getattr(self.engine, "_flags", 0) & (_lib.IRE_FLAG_RESULT_PNG_BASE64 | _lib.IRE_FLAG_RESULT_PNG_DEFLATE | _lib.IRE_FLAG_RESULT_JPEG))      # poll returns the text
         if len(decoded) == 1:
             # one image of any size is ONE job of the engine's batcher (ire_submit_fit): the engine pads on the device, classifies
             # the image's own pixels in the same batch when analyze() did not, and hands back the h x w window -- on a flagged

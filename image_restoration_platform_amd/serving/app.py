@@ -45,7 +45,8 @@ def get_service():
                 from ..restorator import RESULT_CODEC
                 # IRE_RESULT_CODEC=png-device: the batcher returns the base64 text of a device-encoded PNG (csrc/encode.hip)
                 # IRE_RESULT_CODEC=png-deflate-device: the text of a compressed PNG (csrc/deflate.hip), fetched with ire_poll_text
-                eng = Engine(device_index=0, max_batch=8, flags={"png-device": 1, "png-deflate-device": 4}.get(RESULT_CODEC, 0))
+                # IRE_RESULT_CODEC=jpeg-device: the text of a baseline JPEG q85 4:4:4 (csrc/jpeg.hip), fetched with ire_poll_text
+                eng = Engine(device_index=0, max_batch=8, flags={"png-device": 1, "png-deflate-device": 4, "jpeg-device": 8}.get(RESULT_CODEC, 0))
             except Exception as e:  # noqa: BLE001 -- EngineError or a missing library
                 _state["error"] = str(e)
                 raise
@@ -154,6 +155,11 @@ async def restore_batch(request: Request):
                     tx, ln = _state["engine"].encode_png_deflate_base64_fit_tensor(restored.contiguous())
                     tx, ln = tx.cpu().numpy(), ln.cpu().numpy()
                     texts = [tx[k, :int(ln[k])] for k in range(len(chunk))]
+                elif RESULT_CODEC == "jpeg-device":             # the JPEG (csrc/jpeg.hip): the counts first, then each text at its real length
+                    get_service()
+                    tx, ln = _state["engine"].encode_jpeg_base64_fit_tensor(restored.contiguous())
+                    ln = ln.cpu().numpy()
+                    texts = [tx[k, :int(ln[k])].cpu().numpy() for k in range(len(chunk))]
                 else:
                     texts = te.encode_png_base64_fit(restored).cpu().numpy()
                 sc = scores.cpu().numpy()

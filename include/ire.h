@@ -84,6 +84,10 @@ typedef struct ire_config {
  * ire_poll_text, into a buffer of ire_png_deflate_base64_bound(h, w) bytes.  Bit value 2 is not a flag; setting both result flags
  * is invalid. */
 #define IRE_FLAG_RESULT_PNG_DEFLATE 4u
+/* The batcher delivers every result as the base64 text of a baseline JPEG file (quality 85, 4:4:4: the reference's own settings,
+ * imagePreprocess.js:57-64; ire_encode_jpeg_base64_fit_device below).  The text's length depends on the pixels: such results are
+ * fetched with ire_poll_text, into a buffer of ire_jpeg_base64_bound(h, w) bytes.  At most one result flag may be set. */
+#define IRE_FLAG_RESULT_JPEG 8u
 
 
 
@@ -203,6 +207,24 @@ int ire_encode_png_deflate_base64_fit_device(ire_engine* e, const uint8_t* d_rgb
 int ire_encode_png_deflate_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes,
                                       uint64_t* lens /* n x uint64, host */);
 
+/* ---- the same result as a baseline JPEG (quality 85, 4:4:4), on the device ----
+ * The file, in the order libjpeg writes it: SOI, JFIF APP0 (1.01, density 1:1), two DQT (the standard's Annex K tables at IJG quality
+ * 85), SOF0 (8 bit, Y Cb Cr, each sampled 1 x 1, the real h and w), four DHT (the Annex K tables, fixed), DRI, SOS (one interleaved
+ * scan), the entropy-coded data with a restart interval of 16 MCUs, EOI.  Every step is libjpeg's published integer algorithm (16-bit
+ * fixed-point colour transform, the "islow" DCT, round-half-up quantiser): the bytes equal libjpeg-turbo's for the same settings.
+ * Partial MCUs are completed by edge replication.  Every JPEG decoder reads it.  Lossy, unlike the two PNG forms.
+ * ire_jpeg_base64_bound: the most characters any h x w image can give -- pure host arithmetic, 0 outside 1..8192; per MCU 2343 bits
+ * (the exact maximum of the fixed Huffman tables over the amplitudes the quantiser can produce), doubled for byte stuffing, 2 bytes of
+ * marker per interval; sizes every buffer (stride_bytes >= it; nothing is written beyond it).  A real text is several times shorter.
+ * Arguments and guarantees as for ire_encode_png_deflate_base64_fit_device: the window, lens[i] (uint64) characters at d_chars + i *
+ * stride_bytes, bytes that are a pure function of the pixels, a number of stream operations independent of n, no host round trip. */
+size_t ire_jpeg_base64_bound(int h, int w);
+int ire_encode_jpeg_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes,
+                                      size_t image_pitch_bytes, uint8_t* d_chars, size_t stride_bytes,
+                                      uint64_t* d_lens /* n x uint64, device */, void* stream);
+int ire_encode_jpeg_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes,
+                               uint64_t* lens /* n x uint64, host */);
+
 /* ---- async batcher (restoreBatch's in-flight promises) ---------------------------------- */
 typedef struct ire_job ire_job;
 /* Queue one h x w image for restoration; jobs of equal shape are coalesced into batches of up
@@ -223,9 +245,10 @@ int ire_poll(ire_engine* e, ire_job* job, int timeout_ms, uint8_t* out_rgb, doub
              ire_timings* t);
 /* ire_poll with a result length: works on every engine.  On IRE_OK `out` holds *len_out bytes: h*w*3 pixel bytes, the
  * ire_png_base64_bytes_fit(h, w) characters of IRE_FLAG_RESULT_PNG_BASE64, or the real character count of
- * IRE_FLAG_RESULT_PNG_DEFLATE (at most ire_png_deflate_base64_bound(h, w)).  cap_bytes is the size of `out`: when the result is
+ * IRE_FLAG_RESULT_PNG_DEFLATE / IRE_FLAG_RESULT_JPEG (at most ire_png_deflate_base64_bound(h, w) / ire_jpeg_base64_bound(h, w)).
+ * cap_bytes is the size of `out`: when the result is
  * longer the call returns IRE_ERR_INVALID_INPUT, sets *len_out to the size needed and leaves the job pending.  Otherwise as
- * ire_poll.  On an engine with IRE_FLAG_RESULT_PNG_DEFLATE ire_poll itself has nowhere to report a length: it returns
+ * ire_poll.  On an engine with IRE_FLAG_RESULT_PNG_DEFLATE or IRE_FLAG_RESULT_JPEG ire_poll itself has nowhere to report a length: it returns
  * IRE_ERR_INVALID_INPUT ("invalid: use ire_poll_text") and -- the one exception to its rule -- leaves the job pending. */
 int ire_poll_text(ire_engine* e, ire_job* job, int timeout_ms, uint8_t* out, size_t cap_bytes, size_t* len_out,
                   double* scores_out, ire_timings* t);

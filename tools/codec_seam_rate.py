@@ -70,11 +70,11 @@ def one_codec(codec, size, requests, levels):
         assert all(ok)
         rows["service_%d_concurrent" % conc] = {"images_per_sec": requests / dt, "ms_per_request_wall": 1e3 * dt * conc / requests}
     t_enc = t_enc_host
-    if codec in ("png-device", "png-deflate-device"):
+    if codec in ("png-device", "png-deflate-device", "jpeg-device"):
         eng = appmod._state["engine"]
         t0 = time.perf_counter()
         for im in imgs[:4]:
-            (eng.encode_png_base64_fit if codec == "png-device" else eng.encode_png_deflate_base64_fit)(im)
+            {"png-device": eng.encode_png_base64_fit, "png-deflate-device": eng.encode_png_deflate_base64_fit, "jpeg-device": eng.encode_jpeg_base64_fit}[codec](im)
         t_enc = (time.perf_counter() - t0) / 4               # host pixels -> device -> text -> host (the flagged batcher skips even that)
     return {"codec": codec, "result_chars": out_chars, "decode_jpeg_ms": 1e3 * t_dec, "encode_ms": 1e3 * t_enc,
             "encode_host_equivalent_ms": 1e3 * t_enc_host, "rates": rows, "cores": len(os.sched_getaffinity(0))}
@@ -87,7 +87,7 @@ def main():
         print(json.dumps(one_codec(sys.argv[2], size, int(sys.argv[3]), [int(x) for x in sys.argv[4].split(",")])))
         return
     out = {}
-    for codec, requests in (("png", 16), ("jpeg", 48), ("png-device", 48), ("png-deflate-device", 48)):
+    for codec, requests in (("png", 16), ("jpeg", 48), ("png-device", 48), ("png-deflate-device", 48), ("jpeg-device", 48)):
         r = subprocess.run([sys.executable, os.path.abspath(__file__), arg, codec, str(requests), "1,4,8"], capture_output=True, text=True, timeout=900)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
         out[codec] = json.loads(line[-1]) if line else {"error": (r.stderr or r.stdout)[-600:]}

@@ -546,17 +546,22 @@ void Engine::profile_query(int fam, double* ms, int64_t* launches, double* flops
 // ------------------------------------------------------------------------------------------------
 // debug capture
 // ------------------------------------------------------------------------------------------------
-void Engine::capture(const char* name, const unsigned short* d, size_t count, hipStream_t s) {
+void Engine::capture(const char* name, const unsigned short* d, size_t count, hipStream_t s) { capture_rows(name, d, count, count, 0, s); }
+// `count` bf16 elements at `offset` of an entry of `total` floats (a whole batch: the entry itself; a row strip: its rows of the whole image).
+// An entry of the right size is kept and only these rows are replaced: a second strip run under one debug_capture(true) keeps the rows the
+// earlier run wrote and this one did not, so a comparison turns capture on (which clears) before every run.
+void Engine::capture_rows(const char* name, const unsigned short* d, size_t count, size_t total, size_t offset, hipStream_t s) {
     if (!capture_ || !name) return;
+    if (offset + count > total) fail(IRE_ERR_INTERNAL, std::string("internal: debug capture of rows beyond the tensor ") + name);
     IRE_HIP(hipStreamSynchronize(s));
     std::vector<unsigned short> hbuf(count);
     IRE_HIP(hipMemcpy(hbuf.data(), d, count * 2, hipMemcpyDeviceToHost));
-    std::vector<float> f(count);
+    std::vector<float>& f = captured_[name];
+    if (f.size() != total) f.assign(total, 0.f);
     for (size_t i = 0; i < count; ++i) {
         uint32_t u = (uint32_t)hbuf[i] << 16;
-        std::memcpy(&f[i], &u, 4);
+        std::memcpy(&f[offset + i], &u, 4);
     }
-    captured_[name] = std::move(f);
 }
 void Engine::capture_f32(const char* name, const float* d, size_t count, hipStream_t s) {
     if (!capture_ || !name) return;
@@ -722,6 +727,12 @@ void Engine::exec_conv(Run& R, const Op& op, const Geo& g) {
         if (R.stats_alt) std::swap(R.stats, R.stats_alt);          // R.stats = the partials produced last
     }
     if (capture_ && !op.name.empty() && a.out && g.halo == 0) capture(op.name.c_str(), a.out, (size_t)g.nimg * Hout * Wout * d.cout, R.stream);
+    // a row strip: its real rows (a.out is the first of them) at their place in an entry of the whole image's size, which the first strip
+    // to write it creates.  All sessions of one engine fill the same entry; a process that holds only some strips captures only its own
+    // rows (the others stay zero).  The (A, B) of a strip run is captured once per op by StripSession::run_op: one finalize serves all strips.
+    if (capture_ && !op.name.empty() && a.out && g.halo == 1)
+        capture_rows(op.name.c_str(), a.out, (size_t)Hout * Wout * d.cout, (size_t)(g.H >> op.lout) * Wout * d.cout,
+                     (size_t)(g.y0 >> op.lout) * Wout * d.cout, R.stream);
     // the (A, B) of y = x A + B this conv applied while staging, [image][cin][2] floats, as "<layer>.ab" ("head.ab" for the head): what a
     // per-layer check needs to recompute the activated operand from the very coefficients the kernel used
     if (capture_ && a.ab != nullptr && g.halo == 0)

@@ -254,6 +254,7 @@ private:
     void prof_tag(const char* key, const char* kernel, int level, int cin, int cout, double flops_exec);   // after prof_begin: the open record's layer group
     void prof_end(hipStream_t s);
     void capture(const char* name, const unsigned short* d, size_t count, hipStream_t s);
+    void capture_rows(const char* name, const unsigned short* d, size_t count, size_t total, size_t offset, hipStream_t s);   // a strip's rows into the whole image's entry
     void capture_f32(const char* name, const float* d, size_t count, hipStream_t s);
     template <class T> T* upload(const std::vector<T>& v);     // allocate in net_.mem + copy; null for an empty v
     ConvW upload_conv(const PackedConv& p);                    // weight_pack.hpp's arrays of one convolution -> device

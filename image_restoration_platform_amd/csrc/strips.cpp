@@ -26,7 +26,7 @@ StripSession::StripSession(Engine& eng, int H, int W, int nstrips_total, int fir
     : E(eng), H_(H), W_(W), total_(nstrips_total), first_(first_strip), nlocal_(nlocal) {
     if (!E.net_.loaded) fail(IRE_ERR_UNAVAILABLE, "service unavailable: RestoreNet weights are not loaded");
     if (E.sw_.rb_tile_h != kRbTileH)
-        fail(IRE_ERR_INVALID_INPUT, "invalid configuration for strip mode: the A/B schedule switches must be at their defaults");
+        fail(IRE_ERR_INVALID_INPUT, "invalid configuration for strip mode: IRE_CONV_V1=1 (the v1 schedule) does not run in strips; every other A/B switch does");
     if (H <= 0 || W <= 0 || H > 8192 || W > 8192 || W % 8) fail(IRE_ERR_INVALID_INPUT, "invalid image size for tiled restore");
     if (nstrips_total < 1 || nstrips_total > 64 || H % nstrips_total) fail(IRE_ERR_INVALID_INPUT, "invalid strip count: it must divide the image height");
     hr_ = H / nstrips_total;
@@ -93,6 +93,9 @@ void StripSession::run_op(int k, hipStream_t s, ire_strip_xchg* info) {
     if (info) std::memset(info, 0, sizeof(*info));
     if (op.kind == Op::GN) { E.exec_op(run_, op, strips_[0]); return; }       // one finalize over the complete partials array
     for (int i = 0; i < nlocal_; ++i) E.exec_op(run_, op, strips_[i]);
+    // debug capture: the (A, B) every strip of this op staged with, once ("<layer>.ab", "head.ab": the untiled capture's names)
+    if (E.capture_ && op.use_ab)
+        E.capture_f32(((op.name.empty() ? std::string("head") : op.name) + ".ab").c_str(), reinterpret_cast<const float*>(run_.ab), (size_t)op.cw->desc.cin * 2, s);
     const size_t rb = halo_row_bytes(k);
     if (rb) {
         // neighbours inside this session: the copy a rank pair would do over xGMI

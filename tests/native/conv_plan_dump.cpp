@@ -2,7 +2,7 @@
 // network's convolutions in schedule order for a list of cases and prints, per case and layer group (the profiler key), one line with
 // every field of the launch plan, in the order of the header line; two ops of one group that plan differently print both lines.  The ConvDesc of a layer is what
 // weight_pack.hpp's packer produces for zero weights of the layer's shape: which arrays exist depends on shapes and precision only.
-// usage: conv_plan_dump fixture | props | fp8      (fixture: the recorded cases; props: the cases behind the separately asserted invariants;
+// usage: conv_plan_dump fixture | props | fp8 | strips      (strips: the strips of tests/test_strips_layers_gpu.py's shapes; fixture: the recorded cases; props: the cases behind the separately asserted invariants;
 // fp8: an fp8 engine under every combination of the switches that decide its C >= 128 ResBlock convolutions)
 #include <cstdio>
 #include <cstdlib>
@@ -91,6 +91,26 @@ static std::vector<Case> fp8_cases() {
             for (const char* pk : {"2", "0"})
                 for (auto& s : {std::vector<int>{1, 16, 16}, {2, 200, 328}, {12, 32, 48}, {3, 72, 136}})
                     cs.push_back(whole({{"IRE_FP8_MX", mx}, {"IRE_W4", w4}, {"IRE_PK", pk}}, true, s[0], s[1], s[2]));
+    return cs;
+}
+
+// the shapes tests/test_strips_layers_gpu.py runs as strips (first, a middle and the last strip of each), under the switches that decide
+// which kernel and which item form the C >= 128 ResBlock convolutions get there
+static std::vector<Case> strip_layer_cases() {
+    std::vector<Case> cs;
+    auto add = [&](const std::vector<std::pair<const char*, const char*>>& env, bool fp8, int H, int W, int n) {
+        for (int s : {0, n / 2, n - 1}) {
+            if (!cs.empty() && cs.back().strip == s && cs.back().nstrips == n && cs.back().h == H && cs.back().fp8 == fp8 && env_name(cs.back().env) == env_name(env)) continue;      // (two strips: first and last)
+            Case c = strip_of(H, W, n, s);
+            c.env = env; c.fp8 = fp8;
+            c.name = env_name(env) + (fp8 ? ":fp8:" : ":bf16:") + c.name.substr(c.name.find("strip"));
+            cs.push_back(c);
+        }
+    };
+    for (auto& p : {std::vector<int>{384, 264, 3}, {1024, 264, 8}, {256, 72, 2}, {512, 264, 4}}) add({}, false, p[0], p[1], p[2]);
+    add({{"IRE_PK", "0"}}, false, 1024, 264, 8);
+    for (const char* mx : {"1", "0"})
+        for (auto& p : {std::vector<int>{384, 264, 3}, {1024, 264, 8}}) add({{"IRE_FP8_MX", mx}}, true, p[0], p[1], p[2]);
     return cs;
 }
 
@@ -186,9 +206,9 @@ static void run_case(const Case& c, const NetDesc& net) {
 int main(int argc, char** argv) {
     if (argc != 2) return 2;
     const std::string mode = argv[1];
-    if (mode != "fixture" && mode != "props" && mode != "fp8") return 2;
+    if (mode != "fixture" && mode != "props" && mode != "fp8" && mode != "strips") return 2;
     const NetDesc bf16 = net_desc(false), fp8 = net_desc(true);
     std::printf("# case group kernel resid fused_act kname w w1 bias zeros cin1 nkc nblocks w4_nt fp8 cout group_size in1_off tile_h tiles_x tiles_y iy_lo iy_span in_rows in_row_off parts_mul stats_level ty0 stats_off stat_parts folds_gn fam flops flops_exec bytes\n");
-    for (const Case& c : mode == "props" ? property_cases() : mode == "fp8" ? fp8_cases() : fixture_cases()) run_case(c, c.fp8 ? fp8 : bf16);
+    for (const Case& c : mode == "props" ? property_cases() : mode == "fp8" ? fp8_cases() : mode == "strips" ? strip_layer_cases() : fixture_cases()) run_case(c, c.fp8 ? fp8 : bf16);
     return 0;
 }

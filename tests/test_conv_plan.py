@@ -46,7 +46,7 @@ def _run(exe, mode):
 def dumps(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("conv_plan")
     exe, exe_asan = _build(tmp, "cp", ["-O2"]), _build(tmp, "cp_asan", ["-O1", "-fsanitize=address,undefined"])
-    return {"fixture": _run(exe, "fixture"), "fixture_asan": _run(exe_asan, "fixture"), "props": _run(exe, "props"), "fp8": _run(exe, "fp8")}
+    return {"fixture": _run(exe, "fixture"), "fixture_asan": _run(exe_asan, "fixture"), "props": _run(exe, "props"), "fp8": _run(exe, "fp8"), "strips": _run(exe, "strips")}
 
 
 FIXTURE = os.path.join(GOLDEN, "conv_plan_9e80c0a.txt")
@@ -211,3 +211,28 @@ def test_which_kernel_an_fp8_engine_really_runs(dumps):
     for (c, g), f in by.items():
         if "IRE_PK=2" in c and g in deep:
             assert by[c.replace("IRE_PK=2", "IRE_PK=0"), g] == f, (c, g)
+
+
+def test_the_strip_layer_test_shapes_get_the_kernels_and_items_their_cases_name(dumps):
+    """tests/test_strips_layers_gpu.py names a kernel family per shape and reads the kernel off the profile report, which does not carry
+    the item width of conv_w4; here the same strips are planned by plan_conv itself: 384x264 in 3 takes the 64-cout items at both deep
+    levels, 1024x264 in 8 conv_pk (IRE_PK=0: conv_w4's 128-cout items), an fp8 engine conv_f8 or conv_w4's fp8 form, in every strip."""
+    deep = ("L2.rb1", "L2.rb2", "L3.rb1", "L3.rb2")
+    want = {("default", "bf16", 384): ("W4", "conv_w4", "w4h", "64", "0"), ("default", "bf16", 1024): ("PK", "conv_pk", "w4", "0", "0"),
+            ("default", "bf16", 256): ("W4", "conv_w4", "w4h", "64", "0"), ("default", "bf16", 512): ("W4", "conv_w4", "w4h", "64", "0"),
+            ("IRE_PK=0", "bf16", 1024): ("W4", "conv_w4", "w4", "0", "0"),
+            ("IRE_FP8_MX=1", "fp8", 384): ("F8", "conv_f8", "w8x", "0", "1"), ("IRE_FP8_MX=1", "fp8", 1024): ("F8", "conv_f8", "w8x", "0", "1"),
+            ("IRE_FP8_MX=0", "fp8", 384): ("W4", "conv_w4", "w8", "0", "1"), ("IRE_FP8_MX=0", "fp8", 1024): ("W4", "conv_w4", "w8", "0", "1")}
+    seen = set()
+    for c, g, f in (parse(ln) for ln in dumps["strips"].splitlines()[1:]):
+        env, prec, n, h, w, s, ns = _case(c)
+        assert s is not None and (f["iy_lo"], f["in_row_off"]) == ("-1" if s else "0", "1"), (c, g)
+        if g in deep:
+            assert (f["kernel"], f["kname"], f["w"], f["w4_nt"], f["fp8"]) == want[env, prec, h], (c, g)
+            if f["w4_nt"] == "0":
+                assert f["nblocks"] == str(int(f["cout"]) // 128), (c, g)
+            seen.add((env, prec, h, s, g))
+        # ragged beside the boundary: the last tile column of these widths is partial at every level
+        if g.startswith("L"):
+            assert (w >> int(g[1])) % 32 != 0 and int(f["tiles_x"]) == -(-(w >> int(g[1])) // 32), (c, g)
+    assert len(seen) == (3 + 3 + 2 + 3 + 3 + 4 * 3) * len(deep), len(seen)      # (256x72 in 2 has two strips)

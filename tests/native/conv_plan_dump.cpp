@@ -2,7 +2,7 @@
 // network's convolutions in schedule order for a list of cases and prints, per case and layer group (the profiler key), one line with
 // every field of the launch plan, in the order of the header line; two ops of one group that plan differently print both lines.  The ConvDesc of a layer is what
 // weight_pack.hpp's packer produces for zero weights of the layer's shape: which arrays exist depends on shapes and precision only.
-// usage: conv_plan_dump fixture | props | fp8 | strips      (strips: the strips of tests/test_strips_layers_gpu.py's shapes; fixture: the recorded cases; props: the cases behind the separately asserted invariants;
+// usage: conv_plan_dump fixture | props | fp8 | strips | items      (items: the cases of tests/test_items_gpu.py at its two shapes, and the (3, 200, 328) batch under IRE_PK 0 / 1 / 2; strips: the strips of tests/test_strips_layers_gpu.py's shapes; fixture: the recorded cases; props: the cases behind the separately asserted invariants;
 // fp8: an fp8 engine under every combination of the switches that decide its C >= 128 ResBlock convolutions)
 #include <cstdio>
 #include <cstdlib>
@@ -114,6 +114,26 @@ static std::vector<Case> strip_layer_cases() {
     return cs;
 }
 
+// the cases of tests/test_items_gpu.py at its two shapes (default switches in bf16, the 128-cout items under IRE_W4_SPLIT=0 with IRE_PK 2 / 0 / 1,
+// the fp8 engine in both forms, every switch set of tests/test_layers_gpu.py SWITCHES), and the batch of
+// tests/test_restore_gpu.py::test_producer_consumer_c128_equals_conv_w4_bit_for_bit under IRE_PK 0 / 1 / 2 with and without IRE_W4_SPLIT=0
+static std::vector<Case> item_cases() {
+    std::vector<Case> cs;
+    const std::vector<std::vector<std::pair<const char*, const char*>>> sets = {
+        {}, {{"IRE_W4_SPLIT", "0"}}, {{"IRE_W4_SPLIT", "0"}, {"IRE_PK", "0"}}, {{"IRE_W4_SPLIT", "0"}, {"IRE_PK", "1"}},
+        {{"IRE_PK", "0"}}, {{"IRE_PC", "0"}}, {{"IRE_PC", "1"}}, {{"IRE_W4", "0"}}, {{"IRE_UPQ", "0"}}, {{"IRE_DNQ", "0"}}, {{"IRE_UP_FUSE", "0"}},
+        {{"IRE_UP_SUBPIX", "0"}}, {{"IRE_GN_FOLD", "0"}}, {{"IRE_DOWN_RB", "0"}, {"IRE_HEAD_RB", "0"}}, {{"IRE_STEM_RB", "0"}}};
+    for (auto& s : {std::vector<int>{3, 136, 136}, {3, 72, 264}}) {
+        for (auto& e : sets) cs.push_back(whole(e, false, s[0], s[1], s[2]));
+        for (const char* mx : {"1", "0"}) cs.push_back(whole({{"IRE_FP8_MX", mx}}, true, s[0], s[1], s[2]));
+    }
+    for (const char* pk : {"0", "1", "2"}) {
+        cs.push_back(whole({{"IRE_PK", pk}}, false, 3, 200, 328));
+        cs.push_back(whole({{"IRE_W4_SPLIT", "0"}, {"IRE_PK", pk}}, false, 3, 200, 328));
+    }
+    return cs;
+}
+
 // ---- the network's convolutions as weight_pack.hpp packs them (zero weights: existence of an array is a matter of shape) ----
 static const int kW[4] = {32, 64, 128, 256};
 struct NetDesc {
@@ -206,9 +226,9 @@ static void run_case(const Case& c, const NetDesc& net) {
 int main(int argc, char** argv) {
     if (argc != 2) return 2;
     const std::string mode = argv[1];
-    if (mode != "fixture" && mode != "props" && mode != "fp8" && mode != "strips") return 2;
+    if (mode != "fixture" && mode != "props" && mode != "fp8" && mode != "strips" && mode != "items") return 2;
     const NetDesc bf16 = net_desc(false), fp8 = net_desc(true);
     std::printf("# case group kernel resid fused_act kname w w1 bias zeros cin1 nkc nblocks w4_nt fp8 cout group_size in1_off tile_h tiles_x tiles_y iy_lo iy_span in_rows in_row_off parts_mul stats_level ty0 stats_off stat_parts folds_gn fam flops flops_exec bytes\n");
-    for (const Case& c : mode == "props" ? property_cases() : mode == "fp8" ? fp8_cases() : mode == "strips" ? strip_layer_cases() : fixture_cases()) run_case(c, c.fp8 ? fp8 : bf16);
+    for (const Case& c : mode == "props" ? property_cases() : mode == "fp8" ? fp8_cases() : mode == "strips" ? strip_layer_cases() : mode == "items" ? item_cases() : fixture_cases()) run_case(c, c.fp8 ? fp8 : bf16);
     return 0;
 }

@@ -11,13 +11,20 @@ Cases: default switches on twelve shapes (both sides of the 64-cout split at 512
 of tests/test_layers_gpu.py and tests/test_restore_gpu.py plus IRE_PK=1 on two shapes, the fp8 engine with IRE_FP8_MX 1 and 0 on
 three, (64, 512, 512) for the launch conv_pk's table refuses, and first / middle / last row strips of three strip plans.  The comment-only invariants of the old exec_conv are asserted
 separately below, over a wider list (`props`).  A third list (`fp8`) is an fp8 engine under IRE_FP8_MX x IRE_W4 x IRE_PK: the table of
-which kernel, slab and bias its C >= 128 ResBlock convolutions really get is asserted at the end."""
+which kernel, slab and bias its C >= 128 ResBlock convolutions really get is asserted at the end.  A fifth list (`items`) is every case
+of tests/test_items_gpu.py at its two shapes: kernel, slab, n-blocks and tile grid of every group are asserted against a table written
+out here, and the work cursor (tests/test_persist_walk.py's decode) shows that at grids of 8 and 16 workgroups every persistent launch
+gives some workgroup several items and that conv_pk, conv_w4 and conv_f8 see every kind of step from one item to the next."""
 import glob
 import os
 import re
 import subprocess
+import sys
 
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_persist_walk import decode      # noqa: E402    (held equal to csrc/persist.hpp's cursor by that file)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "conv_plan_dump.cpp")
@@ -46,7 +53,8 @@ def _run(exe, mode):
 def dumps(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("conv_plan")
     exe, exe_asan = _build(tmp, "cp", ["-O2"]), _build(tmp, "cp_asan", ["-O1", "-fsanitize=address,undefined"])
-    return {"fixture": _run(exe, "fixture"), "fixture_asan": _run(exe_asan, "fixture"), "props": _run(exe, "props"), "fp8": _run(exe, "fp8"), "strips": _run(exe, "strips")}
+    return {"fixture": _run(exe, "fixture"), "fixture_asan": _run(exe_asan, "fixture"), "props": _run(exe, "props"), "fp8": _run(exe, "fp8"), "strips": _run(exe, "strips"),
+            "items": _run(exe, "items")}
 
 
 FIXTURE = os.path.join(GOLDEN, "conv_plan_9e80c0a.txt")
@@ -236,3 +244,131 @@ def test_the_strip_layer_test_shapes_get_the_kernels_and_items_their_cases_name(
         if g.startswith("L"):
             assert (w >> int(g[1])) % 32 != 0 and int(f["tiles_x"]) == -(-(w >> int(g[1])) // 32), (c, g)
     assert len(seen) == (3 + 3 + 2 + 3 + 3 + 4 * 3) * len(deep), len(seen)      # (256x72 in 2 has two strips)
+
+
+# ---- tests/test_items_gpu.py: its cases at its two shapes ---------------------------------------------------------------------------------
+ITEM_SHAPES = [(3, 136, 136), (3, 72, 264)]
+ITEM_ENVS = ["default", "IRE_W4_SPLIT=0", "IRE_W4_SPLIT=0,IRE_PK=0", "IRE_W4_SPLIT=0,IRE_PK=1", "IRE_PK=0", "IRE_PC=0", "IRE_PC=1", "IRE_W4=0",
+             "IRE_UPQ=0", "IRE_DNQ=0", "IRE_UP_FUSE=0", "IRE_UP_SUBPIX=0", "IRE_GN_FOLD=0", "IRE_DOWN_RB=0,IRE_HEAD_RB=0", "IRE_STEM_RB=0"]
+ITEM_FP8 = ["IRE_FP8_MX=1", "IRE_FP8_MX=0"]
+DEEP = ("L2.rb1", "L2.rb2", "L3.rb1", "L3.rb2")
+WIDTHS = (32, 64, 128, 256)
+
+
+def items_expected(env, prec, h, w):
+    """{group: (kernel name, slab, nblocks, w4_nt, tiles_x, tiles_y)} of a case of tests/test_items_gpu.py, written out from the rule book's
+    prose (not computed by it): the default schedule first, then what the case's switches move."""
+    sw = dict(kv.split("=") for kv in env.split(",")) if env != "default" else {}
+    grid = lambda l, th=16: (-(-(w >> l) // 32), -(-(h >> l) // th))
+    e = {"stem": ("conv_stem", "wstem", 1, 0) + grid(0), "head": ("conv_pc", "wp", 1, 0) + grid(0),
+         "down0": ("conv_down", "wd", 1, 0) + grid(1), "down1": ("conv_dnq", "wdq", 1, 0) + grid(2), "down2": ("conv_dnq", "wdq", 2, 0) + grid(3),
+         "up2": ("conv_upq", "wuq", 4, 0) + grid(3), "up1": ("conv_up", "wuf", 2, 0) + grid(2), "up0": ("conv_up", "wuf", 1, 0) + grid(1)}
+    for l in range(4):
+        for g in ("L%d.rb1" % l, "L%d.rb2" % l):
+            # 6 tiles at level 2 and 2 at level 3 per image, at both shapes: tiles * (C / 128) * 8 < 256, the 64-cout items
+            e[g] = ("conv_pc", "wp", 1, 0) + grid(l) if l < 2 else ("conv_w4", "w4h", WIDTHS[l] // 64, 64) + grid(l)
+    for g in DEEP:
+        l, c = int(g[1]), WIDTHS[int(g[1])]
+        if prec == "fp8":
+            e[g] = (("conv_f8", "w8x") if sw["IRE_FP8_MX"] == "1" else ("conv_w4", "w8")) + (c // 128, 0) + grid(l)
+        elif sw.get("IRE_W4") == "0":
+            e[g] = ("conv_rb", "wp", c // 64, 0) + grid(l)
+        elif sw.get("IRE_W4_SPLIT") == "0":
+            pk = int(sw.get("IRE_PK", "2")) >= (2 if g.endswith("rb2") else 1)
+            e[g] = ("conv_pk" if pk else "conv_w4", "w4", c // 128, 0) + grid(l)
+    pc = int(sw.get("IRE_PC", "3"))
+    for l in (0, 1):
+        if not pc & (1 << l):
+            e["L%d.rb1" % l] = e["L%d.rb2" % l] = ("conv_rb", "wp", 1, 0) + grid(l)
+    if not pc & 1:
+        e["head"] = ("conv_rb", "wp", 1, 0) + grid(0)
+    if sw.get("IRE_UPQ") == "0":
+        e["up2"] = ("conv_up", "wuf", 4, 0) + grid(3)
+    if sw.get("IRE_DNQ") == "0":
+        e["down1"], e["down2"] = ("conv_down", "wd", 2, 0) + grid(2), ("conv_down", "wd", 4, 0) + grid(3)
+    if sw.get("IRE_UP_FUSE") == "0" or sw.get("IRE_UP_SUBPIX") == "0":
+        for l in range(3):
+            e["up%d" % l] = ("conv_up", "wu", WIDTHS[l] // 32, 0) + grid(l + 1) if "IRE_UP_FUSE" in sw else ("conv_rb", "wp", max(1, WIDTHS[l] // 64), 0) + grid(l)
+            e["fuse%d" % l] = ("conv_mfma", "w", max(1, WIDTHS[l] // 64), 0) + grid(l, 8)
+    if sw.get("IRE_DOWN_RB") == "0":
+        for l in range(3):
+            e["down%d" % l] = ("conv_mfma", "w", WIDTHS[l + 1] // 64, 0) + grid(l + 1, 4)
+    if sw.get("IRE_HEAD_RB") == "0":
+        e["head"] = ("conv_mfma", "w", 1, 0) + grid(0, 8)
+    if sw.get("IRE_STEM_RB") == "0":
+        e["stem"] = ("conv_mfma", "w", 1, 0) + grid(0, 8)
+    return e
+
+
+def _item_plans(dumps):
+    plans = {}
+    for c, g, f in (parse(ln) for ln in dumps["items"].splitlines()[1:]):
+        env, prec, n, h, w, s, _ = _case(c)
+        assert s is None and g not in plans.get((env, prec, n, h, w), {}), (c, g)
+        plans.setdefault((env, prec, n, h, w), {})[g] = f
+    return plans
+
+
+def test_the_item_test_cases_get_the_kernels_slabs_and_grids_their_table_names(dumps):
+    plans = _item_plans(dumps)
+    cases = [(e, "bf16") + s for s in ITEM_SHAPES for e in ITEM_ENVS] + [(e, "fp8") + s for s in ITEM_SHAPES for e in ITEM_FP8]
+    assert set(cases) <= set(plans) and len(cases) == 34
+    for env, prec, n, h, w in cases:
+        want = items_expected(env, prec, h, w)
+        got = {g: (f["kname"], f["w"], int(f["nblocks"]), int(f["w4_nt"]), int(f["tiles_x"]), int(f["tiles_y"])) for g, f in plans[env, prec, n, h, w].items()}
+        assert got == want, (env, prec, h, w, {g: (got.get(g), want.get(g)) for g in set(got) | set(want) if got.get(g) != want.get(g)})
+        # the plan of these batches does not depend on the grid size: three images fit every coefficient table outright
+        assert n <= min(COEF_IMGS["PK"], 8)
+    # the geometry classes the shapes were chosen for
+    assert items_expected("default", "bf16", 136, 136)["L2.rb1"][4:] == (2, 3) and items_expected("default", "bf16", 136, 136)["L3.rb1"][4:] == (1, 2)
+    assert items_expected("default", "bf16", 72, 264)["L2.rb1"][4:] == (3, 2) and items_expected("default", "bf16", 72, 264)["L3.rb1"][4:] == (2, 1)
+    assert ((264 >> 2) % 32, (264 >> 3) % 32, (136 >> 2) % 32, (136 >> 3) % 32) == (2, 1, 2, 17)      # the last tile columns: 2, 1, 2 and 17 pixels wide
+
+
+def _steps(items):
+    """the kinds of step from one item of a workgroup to its next: next n-block of the same tile, next tile column, next tile row, next image"""
+    kinds = set()
+    for (ia, ya, xa, _, ta), (ib, yb, xb, _, tb) in zip(items, items[1:]):
+        kinds.add("n-block" if (ia, ta) == (ib, tb) else "image" if ia != ib else "row" if ya != yb else "column")
+    return kinds
+
+
+@pytest.mark.parametrize("cus", [8, 16])
+def test_the_item_test_cases_give_workgroups_several_items_and_every_kind_of_step(dumps, cus):
+    """What tests/test_items_gpu.py runs with IRE_GRID_CUS = 8 and 16.  A launch's grid is min(items, cus) workgroups (conv_stem: 2 cus;
+    the v1 template conv_mfma is not persistent and has no walk)."""
+    plans = _item_plans(dumps)
+    steps = {}
+    launches = 0
+    for (env, prec, n, h, w), groups in plans.items():
+        if (n, h, w) not in ITEM_SHAPES:
+            continue
+        for g, f in groups.items():
+            if f["kname"] == "conv_mfma":
+                continue
+            geo = (int(f["tiles_x"]), int(f["tiles_y"]), n, int(f["nblocks"]), 1)
+            items = geo[0] * geo[1] * geo[2] * geo[3]
+            G = min(items, cus * (2 if f["kname"] == "conv_stem" else 1))
+            walks = [[it for _, it in decode(geo, G, b)] for b in range(G)]
+            assert sorted(len(wk) for wk in walks)[-1] >= 2, (env, prec, h, w, g, items, G)
+            assert sum(len(wk) for wk in walks) == items
+            for wk in walks:
+                steps.setdefault(f["kname"], set()).update(_steps(wk))
+            launches += 1
+    assert launches == 34 * 16 - 2 * (4 + 1)      # 16 persistent launches per case; IRE_DOWN_RB=0,IRE_HEAD_RB=0 and IRE_STEM_RB=0 move 4 and 1 to the v1 template
+    for k in ("conv_pk", "conv_w4", "conv_f8"):
+        assert steps[k] == {"n-block", "column", "row", "image"}, (k, cus, steps[k])
+
+
+def test_the_batch_of_the_bit_for_bit_test_plans_conv_w4_64_cout_items_unless_the_split_is_off(dumps):
+    """(3, 200, 328): 12 and 4 tiles per image at levels 2 and 3, 12 * 1 * 8 and 4 * 2 * 8 < 256 -- under default switches every value of IRE_PK
+    plans conv_w4 on the 64-cout items there, so comparing those engines compares conv_w4 with itself.  With IRE_W4_SPLIT=0 the switch decides:
+    that is what tests/test_restore_gpu.py::test_producer_consumer_c128_equals_conv_w4_bit_for_bit runs."""
+    plans = _item_plans(dumps)
+    want = {"0": ("conv_w4", "conv_w4"), "1": ("conv_pk", "conv_w4"), "2": ("conv_pk", "conv_pk")}
+    for pk in "012":
+        for g in DEEP:
+            f = plans["IRE_PK=" + pk, "bf16", 3, 200, 328][g]
+            assert (f["kname"], f["w"], f["w4_nt"]) == ("conv_w4", "w4h", "64"), (pk, g)
+            f = plans["IRE_W4_SPLIT=0,IRE_PK=" + pk, "bf16", 3, 200, 328][g]
+            assert (f["kname"], f["w"], f["w4_nt"], f["nblocks"]) == (want[pk][g.endswith("rb2")], "w4", "0", str(WIDTHS[int(g[1])] // 128)), (pk, g)

@@ -134,6 +134,30 @@ def test_producer_consumer_c128_equals_conv_w4_bit_for_bit(engine, weights0, mon
         finally:
             alt_engine.close()
         assert np.array_equal(alt, base), (pk, int(np.abs(alt.astype(np.int32) - base.astype(np.int32)).max()))
+    # At this shape plan_conv gives all three engines above conv_w4's 64-cout items (12 and 4 tiles per image at levels 2 and 3:
+    # tiles * n-blocks * 8 < 256; tests/test_conv_plan.py asserts it), so they hold conv_w4 to conv_w4.  IRE_W4_SPLIT=0 forces the 128-cout
+    # items, the ones conv_pk takes: conv_pk on every C >= 128 conv, on those without a residual, and conv_w4 on all of them.
+    monkeypatch.setenv("IRE_W4_SPLIT", "0")
+    ref = onet.restore(imgs, sc, weights0)
+    deep = ["L%d.rb%d" % (l, i) for l in (2, 3) for i in (1, 2)]
+    outs = {}
+    for pk in ("2", "1", "0"):
+        monkeypatch.setenv("IRE_PK", pk)
+        alt_engine = Engine(device_index=0, max_batch=8)
+        try:
+            alt_engine.profile_reset()
+            alt_engine.profile_enable(1)
+            outs[pk] = alt_engine.restore(imgs, scores=sc)
+            report = {r["group"]: r["kernel"] for r in alt_engine.profile_report()}
+            alt_engine.profile_enable(0)
+        finally:
+            alt_engine.close()
+        for g in deep:
+            want = "conv_pk" if int(pk) >= (2 if g.endswith("rb2") else 1) else "conv_w4"
+            assert report.get(g) == want, "IRE_W4_SPLIT=0 IRE_PK=%s: layer group %s ran on %r, not on %r (report: %r)" % (pk, g, report.get(g), want, report)
+        _assert_close(outs[pk], ref)
+    for pk in ("1", "0"):
+        assert np.array_equal(outs[pk], outs["2"]), (pk, int(np.abs(outs[pk].astype(np.int32) - outs["2"].astype(np.int32)).max()))
 
 
 @pytest.mark.parametrize("n,h,w", [(12, 32, 48), (20, 16, 32)])

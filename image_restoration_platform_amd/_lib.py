@@ -66,6 +66,9 @@ SYMBOLS = {
     "ire_jpeg_base64_bound": (ctypes.c_size_t, [_i, _i]),
     "ire_encode_jpeg_base64_fit_device": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp]),
     "ire_encode_jpeg_base64_fit": (_i, [_vp, _u8p, _i, _i, _i, _u8p, ctypes.c_size_t, _vp]),
+    "ire_decode_jpeg_plan": (_i, [_u8p, ctypes.c_size_t, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "ire_decode_jpeg": (_i, [_vp, _u8p, ctypes.c_size_t, _u8p, _i, _i]),
+    "ire_decode_jpeg_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp, _vp]),
     "ire_submit_fit": (_i, [_vp, _u8p, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
     "ire_submit": (_i, [_vp, _u8p, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
     "ire_restore_tiled_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -47,6 +47,7 @@ SOURCES = [
     ("encode.hip", []),
     ("deflate.hip", []),
     ("jpeg.hip", []),
+    ("jpeg_dec.hip", []),
     ("engine.cpp", []),
     ("strips.cpp", []),
     ("api.cpp", []),

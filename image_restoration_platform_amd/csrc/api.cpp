@@ -16,6 +16,7 @@
 #include "batcher.hpp"
 #include "deflate.hpp"
 #include "jpeg.hpp"
+#include "jpeg_parse.hpp"
 #include "encode.hpp"
 #include "engine.hpp"
 #include "fusion.hpp"
@@ -461,6 +462,33 @@ int ire_encode_jpeg_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, 
     return guarded([&] {
         Engine& E = eng(e);
         on_stream(E, E.main_stream(), [&] { E.encode_jpeg_base64_fit_host(rgb, n, h, w, chars, stride_bytes, lens); });
+    });
+}
+
+int ire_decode_jpeg_plan(const uint8_t* file, size_t bytes, int* out_h, int* out_w, int* out_sampling) {
+    return guarded([&] {
+        if (!file) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_decode_jpeg_plan: null file");
+        jpegparse::Header hd;
+        std::string why;
+        if (!jpegparse::plan(file, bytes, hd, why)) fail(IRE_ERR_INVALID_INPUT, why);
+        if (out_h) *out_h = hd.im.h;
+        if (out_w) *out_w = hd.im.w;
+        if (out_sampling) *out_sampling = hd.im.sampling;
+    });
+}
+
+int ire_decode_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, uint8_t* out_rgb, int h, int w) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, E.main_stream(), [&] { E.decode_jpeg_host(file, bytes, out_rgb, h, w); });
+    });
+}
+
+int ire_decode_jpeg_device(ire_engine* e, const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb, size_t image_pitch_bytes,
+                           int32_t* d_status, void* stream) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, (hipStream_t)stream, [&] { E.decode_jpeg_device(files, bytes, n, h, w, d_rgb, image_pitch_bytes, d_status, (hipStream_t)stream); });
     });
 }
 

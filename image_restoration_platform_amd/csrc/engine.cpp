@@ -6,6 +6,7 @@
 #include "encode.hpp"
 #include "deflate.hpp"
 #include "jpeg.hpp"
+#include "jpeg_dec.hpp"
 
 #include <chrono>
 #include <cmath>
@@ -54,6 +55,7 @@ Engine::Engine(const ire_config& cfg) {
     sw_ = ConvSwitches::from_env();
     cus_ = persistent_grid_cus();
     if (const char* v = std::getenv("IRE_SNAKE")) snake_ = std::atoi(v) != 0;
+    if (const char* v = std::getenv("IRE_JPEG_DEC_TIMES")) dec_times_ = std::atoi(v) != 0;
     if (const char* v = std::getenv("IRE_RB_STAMPS")) {   // diagnostic: "<cout>[r]" = stamp the first such ResBlock conv
         stamps_cout_ = std::atoi(v);
         stamps_resid_ = std::strchr(v, 'r') != nullptr;
@@ -90,6 +92,12 @@ Engine::Engine(const ire_config& cfg) {
 Engine::~Engine() {
     (void)hipSetDevice(device_);
     (void)hipDeviceSynchronize();
+    if (dec_times_) {
+        dec_times_collect();
+        std::fprintf(stderr, "{\"jpeg_dec_kernel_ms\": {\"memset\": %.4f, \"long\": %.4f, \"short\": %.4f, \"idct\": %.4f, \"colour\": %.4f, \"calls\": %lld}}\n", dec_ms_[0], dec_ms_[1],
+                     dec_ms_[2], dec_ms_[3], dec_ms_[4], (long long)dec_calls_);
+        for (hipEvent_t ev : dec_marks_) if (ev) (void)hipEventDestroy(ev);
+    }
     if (stamps_dev_ && std::getenv("IRE_STAMPS_RAW")) {     // diagnostic builds with their own stamp layout (conv_pk.hip PK_TICKS): the whole buffer, one value per line
         std::vector<unsigned long long> h(8 * 2 * 64 * 10);
         (void)hipMemcpy(h.data(), stamps_dev_.get<void>(), h.size() * 8, hipMemcpyDeviceToHost);
@@ -142,6 +150,7 @@ Engine::~Engine() {
     for (auto& ev : ev_) if (ev) (void)hipEventDestroy(ev);
     if (fork_ev_) (void)hipEventDestroy(fork_ev_);
     if (busy_ev_) (void)hipEventDestroy(busy_ev_);
+    for (hipEvent_t ev : dec_up_ev_) if (ev) (void)hipEventDestroy(ev);
     for (auto& r : prof_) { if (r.own_e0) (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
     for (auto ev : ev_pool_) (void)hipEventDestroy(ev);
     if (main_stream_) (void)hipStreamDestroy(main_stream_);
@@ -415,6 +424,73 @@ void Engine::encode_jpeg_base64_fit_host(const uint8_t* rgb, int n, int h, int w
         IRE_HIP(hipMemcpyAsync(chars + stride * i, d_txt + cpad * i + 8, (size_t)lens[i], hipMemcpyDeviceToHost, s));
     }
     IRE_HIP(hipStreamSynchronize(s));
+}
+
+// ---- the JPEG decoder (jpeg_parse.hpp on the host, jpeg_dec.hip on the device) -----------------------------------------------------------
+
+void Engine::decode_jpeg_device(const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status,
+                                hipStream_t s) {
+    if (!files || !bytes || !d_rgb || !d_status || n < 1 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the JPEG decoder (1..max_batch files)");
+    if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the JPEG decoder: height and width must be in 1..8192");
+    if (image_pitch < (size_t)3 * w * h) fail(IRE_ERR_INVALID_INPUT, "invalid pitch for the JPEG decoder: images overlap");
+    std::vector<jpegparse::Header> hd((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        std::string why;
+        if (!files[i] || !jpegparse::parse_header(files[i], bytes[i], hd[i], why)) fail(IRE_ERR_INVALID_INPUT, files[i] ? why : "invalid arguments to the JPEG decoder: null file");
+        if (hd[i].im.h != h || hd[i].im.w != w) fail(IRE_ERR_INVALID_INPUT, "invalid: the JPEG file's size is not the planned h x w");
+    }
+    const JpegDecLayout L0 = jpeg_dec_layout(hd.data(), bytes, n);
+    if (L0.total >= ((size_t)1 << 32)) fail(IRE_ERR_INVALID_INPUT, "invalid: the batch's JPEG files exceed 4 GB");
+    // two pinned blobs in turn: this one was last uploaded by the call before last, and that upload must have left it
+    const int turn = dec_turn_;
+    dec_turn_ ^= 1;
+    Buf<PinnedMem>& pin = dec_pin_[turn];
+    if (dec_up_recorded_[turn]) IRE_HIP(hipEventSynchronize(dec_up_ev_[turn]));
+    pin.grow(L0.total, L0.total + L0.total / 2);
+    JpegDecLayout L;
+    jpeg_dec_pack(files, bytes, hd.data(), n, L0, pin.get<uint8_t>(), L);
+    const size_t coef = jpeg_dec_coef_bytes(n, h, w), planes = jpeg_dec_plane_bytes(n, h, w);
+    if (L.total > d_dec_in_.bytes() || coef > d_dec_coef_.bytes() || planes > d_dec_planes_.bytes()) IRE_HIP(hipDeviceSynchronize());
+    d_dec_in_.grow(L.total, L.total + L.total / 2);
+    d_dec_coef_.grow(coef, batch_room(coef, jpeg_dec_coef_bytes(max_batch_, h, w)));
+    d_dec_planes_.grow(planes, batch_room(planes, jpeg_dec_plane_bytes(max_batch_, h, w)));
+    IRE_HIP(hipMemcpyAsync(d_dec_in_.get<uint8_t>(), pin.get<uint8_t>(), L.total, hipMemcpyHostToDevice, s));
+    if (!dec_up_ev_[turn]) IRE_HIP(hipEventCreateWithFlags(&dec_up_ev_[turn], hipEventDisableTiming));
+    IRE_HIP(hipEventRecord(dec_up_ev_[turn], s));
+    dec_up_recorded_[turn] = true;
+    if (dec_times_) {
+        dec_times_collect();
+        for (hipEvent_t& ev : dec_marks_) if (!ev) IRE_HIP(hipEventCreate(&ev));
+    }
+    jpeg_dec_launch(d_dec_in_.get<uint8_t>(), L, n, h, w, d_dec_coef_.get<uint8_t>(), d_dec_planes_.get<uint8_t>(), d_rgb, image_pitch, d_status, s,
+                    dec_times_ ? dec_marks_ : nullptr);
+    dec_marks_pending_ = dec_times_;
+}
+
+void Engine::dec_times_collect() {
+    if (!dec_marks_pending_) return;
+    dec_marks_pending_ = false;
+    if (hipEventSynchronize(dec_marks_[5]) != hipSuccess) return;
+    for (int k = 0; k < 5; ++k) { float ms = 0.f; if (hipEventElapsedTime(&ms, dec_marks_[k], dec_marks_[k + 1]) == hipSuccess) dec_ms_[k] += ms; }
+    ++dec_calls_;
+}
+
+void Engine::decode_jpeg_host(const uint8_t* file, size_t bytes, uint8_t* out_rgb, int h, int w) {
+    if (!file || !out_rgb) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the JPEG decoder: null buffer");
+    if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the JPEG decoder: height and width must be in 1..8192");
+    const size_t ib = (size_t)h * w * 3, ipad = (ib + 255) / 256 * 256;
+    if (ipad + 256 > d_dec_out_.bytes()) IRE_HIP(hipDeviceSynchronize());
+    d_dec_out_.grow(ipad + 256);
+    hipStream_t s = main_stream_;
+    uint8_t* d_px = d_dec_out_.get<uint8_t>();
+    int32_t* d_st = reinterpret_cast<int32_t*>(d_px + ipad);
+    decode_jpeg_device(&file, &bytes, 1, h, w, d_px, ib, d_st, s);
+    int32_t st = 0;
+    IRE_HIP(hipMemcpyAsync(out_rgb, d_px, ib, hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipMemcpyAsync(&st, d_st, sizeof(st), hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipStreamSynchronize(s));
+    // (bits: jpeg_dec_core.hpp kSt*; 16 = values no picture gives, where libjpeg-turbo's C and SIMD code differ)
+    if (st != 0) fail(IRE_ERR_INVALID_INPUT, "invalid: corrupt JPEG data (decoder status " + std::to_string(st) + ")");
 }
 
 void Engine::free_workspace() {

@@ -180,6 +180,13 @@ public:
     void encode_jpeg_base64_fit_device(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride,
                                        uint64_t* d_lens, hipStream_t s);
     void encode_jpeg_base64_fit_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride, uint64_t* lens);
+    // jpeg_dec.hip: n baseline JPEG files of one planned size (jpeg_parse.hpp decides which files) -> n images of h x w x 3 bytes on
+    // the device, image_pitch apart, and one status word per image (0: ok).  The host parse runs inside; one upload and a fixed
+    // number of launches per batch.  The only wait of the host: for the upload of the call BEFORE LAST, whose pinned staging this call
+    // reuses (that upload sits behind the kernels of the call before it, so a caller three calls ahead of the device waits for those).
+    void decode_jpeg_device(const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status,
+                            hipStream_t s);
+    void decode_jpeg_host(const uint8_t* file, size_t bytes, uint8_t* out_rgb, int h, int w);
     // Any-size jobs (h, w in 1..8192): edge-replicate pad to (max(16, ceil8 h), max(16, ceil8 w)) into the engine's padded
     // staging, the network on the padded shape, the top-left h x w window as the result.  The classifier always sees the
     // ORIGINAL pixels.  A shape restore_device takes as it is skips the pad and runs exactly as restore_device does.
@@ -292,6 +299,20 @@ private:
     Buf<DeviceMem> d_enc_scratch_;        // encode.hip: per batch: the PNG files + checksum state
     Buf<DeviceMem> d_pad_in_, d_pad_out_; // any-size jobs: the edge-padded batch in front of the network, and the network's output on the padded shape
     Buf<DeviceMem> d_enc_io_;             // host entry: pixels in | characters out
+    // the JPEG decoder: the batch's upload (records, tables, stream table, stream bytes) pinned and on the device, the coefficient
+    // scratch behind the status words, the sample planes, the host entry's pixels + status
+    Buf<PinnedMem> dec_pin_[2];           // two, used in turn: call k + 1 is parsed and staged while call k's upload may still run
+    Buf<DeviceMem> d_dec_in_, d_dec_coef_, d_dec_planes_, d_dec_out_;
+    hipEvent_t dec_up_ev_[2] = {};        // the last upload out of dec_pin_[i]
+    bool dec_up_recorded_[2] = {};
+    int dec_turn_ = 0;
+    // IRE_JPEG_DEC_TIMES=1 (read once; tools/jpeg_decode_measure.py): events between the decoder's launches, their times summed over
+    // the calls and printed to stderr as one JSON line when the engine closes.  Collecting waits for the previous call's kernels.
+    bool dec_times_ = false, dec_marks_pending_ = false;
+    hipEvent_t dec_marks_[6] = {};
+    double dec_ms_[5] = {};
+    int64_t dec_calls_ = 0;
+    void dec_times_collect();
 
     // network
     Net net_;

@@ -1,0 +1,361 @@
+// jpeg_dec.hip -- baseline JPEG files -> RGB pixels, on the device, byte for byte what libjpeg-turbo decodes.
+//
+// The host (jpeg_parse.hpp) reads the markers, refuses what is out of scope, cuts the scan at the restart markers into independent
+// streams with the byte stuffing removed, and builds the decode tables; ONE upload carries a whole batch: image records, tables,
+// stream table, stream bytes.  Then, per BATCH (image is a grid dimension; nothing below depends on n):
+//   memset                    the status words and the coefficient scratch (a block's zero coefficients are never written)
+//   K1 jpeg_dec_long_kernel   one workgroup per stream longer than kShortMaxBytes: the self-synchronising lane algorithm of
+//                             jpeg_dec_core.hpp, window by window (kLanes x kSubseqBits bits, staged into LDS as big-endian words,
+//                             one pad word per 32 so that lane i starts on bank i); the first lane of a window starts from the exact
+//                             end state of the window before.  No workgroup waits for another.
+//   K2 jpeg_dec_short_kernel  one LANE per short stream in a strided loop (our own encoder's 16-MCU intervals are ~80 bytes): the
+//                             same loop, start to end, straight from the stream's bytes
+//   K3 jpeg_dec_idct_kernel   dequantise + libjpeg's "islow" inverse DCT (jidctint.c) + range limit: 32 blocks per workgroup,
+//                             thread = (block, column) then (block, row) through LDS rows of 9 ints (conflict-free both ways, as
+//                             in jpeg.hip); samples to per-component planes on the block grid
+//   K4 jpeg_dec_colour_kernel per pixel: "fancy" h2v1 / h2v2 chroma upsampling on the planes' REAL sizes (the blocks' padding is
+//                             never read), YCbCr -> RGB in 16-bit fixed point; the image's status word to the caller's array
+// Safety: every loop of K1 / K2 is bounded by the stream's bit count and its block count; reads of stream bytes are clamped to
+// the stream's length (1-bits behind it, as libjpeg pads); a coefficient is written only to a block index below the image's block
+// count; a code no table holds, a zig-zag index above 63, a DC category above 11 or a stream that ends with blocks missing or bytes
+// left over sets the image's status word and stops that stream; so does (K3) a dequantised coefficient outside int16 or a sample
+// outside -512..511 before the range limit, where libjpeg-turbo's C and SIMD code give different bytes.  tests/native/jpeg_dec_sim.cpp runs the same code on the CPU.
+#include "jpeg_dec.hpp"
+
+#include <algorithm>
+#include <cstring>
+
+namespace ire {
+
+namespace {
+
+using namespace jpegdec;
+
+constexpr int kThreads = kLanes;
+constexpr int kWaves = kThreads / 64;
+
+struct DecBatch {
+    const DecImage* images;
+    const DecTable* tabs;          // 8 per image
+    const DecStream* streams;
+    const unsigned char* bytes;
+    int* stat;                     // one word per image
+    short* coef;                   // per image coef_stride int16
+    unsigned long long coef_stride;
+};
+
+__device__ __forceinline__ void load_image(const DecBatch& b, unsigned img, DecImage* s_im, DecTable* s_tabs, unsigned t) {
+    const unsigned* si = reinterpret_cast<const unsigned*>(b.images + img);
+    unsigned* di = reinterpret_cast<unsigned*>(s_im);
+    for (unsigned k = t; k < sizeof(DecImage) / 4; k += kThreads) di[k] = si[k];
+    const unsigned* st = reinterpret_cast<const unsigned*>(b.tabs + 8ull * img);
+    unsigned* dt = reinterpret_cast<unsigned*>(s_tabs);
+    for (unsigned k = t; k < 8 * sizeof(DecTable) / 4; k += kThreads) dt[k] = st[k];
+    __syncthreads();
+}
+static_assert(sizeof(DecImage) % 4 == 0 && sizeof(DecTable) % 4 == 0, "copied as dwords");
+
+// K1.  blockIdx.x: the image's long stream, blockIdx.y: the image.
+__global__ __launch_bounds__(kThreads) void jpeg_dec_long_kernel(DecBatch b) {
+    __shared__ unsigned s_words[kStagePadded];
+    __shared__ DecTable s_tabs[8];
+    __shared__ DecImage s_im;
+    __shared__ unsigned s_endp[2][kLanes], s_endbk[2][kLanes];
+    __shared__ unsigned s_scan[4][kWaves];
+    __shared__ unsigned s_final, s_err;
+    const unsigned t = threadIdx.x, img = blockIdx.y, lane = t & 63u, wv = t >> 6;
+    load_image(b, img, &s_im, s_tabs, t);
+    if (blockIdx.x >= s_im.nlong) return;
+    const DecStream sr = b.streams[s_im.first_long + blockIdx.x];
+    const unsigned char* bytes = b.bytes + sr.off;
+    short* coef = b.coef + (unsigned long long)img * b.coef_stride;
+    const unsigned total_bits = 8u * sr.len, total_blocks = sr.nmcu * s_im.bpm, gblk0 = sr.mcu0 * s_im.bpm;
+    if (t == 0) { s_final = kBadPos; s_err = 0; }
+    DecState carry{0, 0, 0};
+    unsigned done = 0, dcc[3] = {0, 0, 0};
+    for (unsigned win0 = 0; win0 < total_bits; win0 += kWindowBits) {
+        __syncthreads();                                            // the window before is read no more
+        for (unsigned k = t; k < kStageWords; k += kThreads) s_words[k + (k >> 5)] = stream_word(bytes, sr.len, win0 / 32 + k);
+        __syncthreads();
+        const WordReader rd{s_words, win0};
+        // the lanes whose subsequence begins inside the stream (a lane behind its end would only hand a state on, one lane per round)
+        const unsigned left = (total_bits - win0 + kSubseqBits - 1) / kSubseqBits, nl = left < (unsigned)kLanes ? left : (unsigned)kLanes;
+        const bool active = t < nl;
+        const unsigned e = win0 + (t + 1) * kSubseqBits, lim = e < total_bits ? e : total_bits;
+        DecState start = t == 0 ? carry : DecState{win0 + t * kSubseqBits, 0, 0};
+        DecState end = start;
+        LaneOut lo{0, {0, 0, 0}};
+        if (active) dec_subseq(rd, s_tabs, s_im, end, lim, 0xffffffffu, (short*)nullptr, 0, nullptr, lo);
+        s_endp[0][t] = end.p; s_endbk[0][t] = end.blk << 8 | end.k;
+        unsigned cur = 0;
+        __syncthreads();                                            // round 0's end states are written
+        for (int round = 1; round <= kLanes; ++round) {             // after round k the first k + 1 lanes are exact; ONE barrier per round:
+            int changed = 0;                                        // a round reads buffer `cur` and writes the other one
+            if (active && t > 0) {
+                const unsigned pp = s_endp[cur][t - 1], pbk = s_endbk[cur][t - 1];
+                if (pp != start.p || pbk != (start.blk << 8 | start.k)) {
+                    start = DecState{pp, pbk >> 8, pbk & 255u};
+                    end = start;
+                    dec_subseq(rd, s_tabs, s_im, end, lim, 0xffffffffu, (short*)nullptr, 0, nullptr, lo);
+                    changed = 1;
+                }
+            }
+            cur ^= 1u;
+            s_endp[cur][t] = end.p; s_endbk[cur][t] = end.blk << 8 | end.k;
+            if (!__syncthreads_or(changed)) break;
+        }
+        // prefix sums over the lanes: completed blocks, and the DC differences per component
+        unsigned v[4] = {lo.nblk, lo.dc[0], lo.dc[1], lo.dc[2]}, own[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            own[q] = v[q];
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) { const unsigned o = __shfl_up(v[q], off, 64); if ((int)lane >= off) v[q] += o; }
+            if (lane == 63) s_scan[q][wv] = v[q];
+        }
+        __syncthreads();
+        unsigned before[4], all[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            before[q] = v[q] - own[q]; all[q] = 0;
+#pragma unroll
+            for (unsigned k = 0; k < (unsigned)kWaves; ++k) { const unsigned x = s_scan[q][k]; if (k < wv) before[q] += x; all[q] += x; }
+        }
+        // the writing pass: every lane from its settled start state, its first block and its DC predictors now known
+        const unsigned first = done + before[0], room = total_blocks > first ? total_blocks - first : 0;
+        unsigned dcpred[4] = {dcc[0] + before[1], dcc[1] + before[2], dcc[2] + before[3], 0};
+        unsigned err = 0;
+        int fin = 0;
+        if (active) {
+            DecState st = start;
+            LaneOut w;
+            err = dec_subseq(rd, s_tabs, s_im, st, lim, room, coef, gblk0 + first, dcpred, w);
+            if (w.nblk && first + w.nblk == total_blocks) { s_final = st.p; fin = 1; }
+            if (err) atomicOr(&s_err, err);
+        }
+        done += all[0]; dcc[0] += all[1]; dcc[1] += all[2]; dcc[2] += all[3];
+        carry = DecState{s_endp[cur][nl - 1], s_endbk[cur][nl - 1] >> 8, s_endbk[cur][nl - 1] & 255u};
+        if (__syncthreads_or((int)err | fin)) break;
+    }
+    __syncthreads();
+    if (t == 0) {
+        unsigned err = s_err;
+        if (!err && !stream_end_ok(s_final, sr.len)) err = kStBadEnd;
+        if (err) atomicOr(&b.stat[img], (int)err);
+    }
+}
+
+// K2.  one lane per short stream of image blockIdx.y, in a strided loop
+__global__ __launch_bounds__(kThreads) void jpeg_dec_short_kernel(DecBatch b) {
+    __shared__ DecTable s_tabs[8];
+    __shared__ DecImage s_im;
+    const unsigned t = threadIdx.x, img = blockIdx.y;
+    load_image(b, img, &s_im, s_tabs, t);
+    short* coef = b.coef + (unsigned long long)img * b.coef_stride;
+    unsigned err = 0;
+    for (unsigned s = blockIdx.x * kThreads + t; s < s_im.nshort; s += gridDim.x * kThreads) {
+        const DecStream sr = b.streams[s_im.first_short + s];
+        const ByteReader rd{b.bytes + sr.off, sr.len};
+        DecState st{0, 0, 0};
+        unsigned dcpred[4] = {0, 0, 0, 0};
+        LaneOut o;
+        unsigned e = dec_subseq(rd, s_tabs, s_im, st, 8u * sr.len, sr.nmcu * s_im.bpm, coef, sr.mcu0 * s_im.bpm, dcpred, o);
+        if (!e && !(o.nblk == sr.nmcu * s_im.bpm && stream_end_ok(st.p, sr.len))) e = kStBadEnd;
+        err |= e;
+    }
+    if (err) atomicOr(&b.stat[img], (int)err);
+}
+
+// ---- libjpeg's "islow" inverse DCT (jidctint.c): 13-bit constants, 2 extra bits kept between the passes -----------------------------
+constexpr int F_0_298631336 = 2446, F_0_390180644 = 3196, F_0_541196100 = 4433, F_0_765366865 = 6270, F_0_899976223 = 7373, F_1_175875602 = 9633;
+constexpr int F_1_501321110 = 12299, F_1_847759065 = 15137, F_1_961570560 = 16069, F_2_053119869 = 16819, F_2_562915447 = 20995, F_3_072711026 = 25172;
+
+// In 64 bit, as jidctint.c's JLONG is: any int16 coefficient times any 8-bit table entry stays exact (< 2^47), so a well-formed
+// stream with absurd values has defined results; what passes between the passes fits 32 bits (< 2^29).
+template <int kShift>
+__device__ __forceinline__ void idct_1d(long long* d) {
+    long long z1 = (d[2] + d[6]) * F_0_541196100;
+    const long long e2 = z1 - d[6] * F_1_847759065, e3 = z1 + d[2] * F_0_765366865;
+    const long long e0 = (d[0] + d[4]) * (1 << 13), e1 = (d[0] - d[4]) * (1 << 13);
+    const long long t10 = e0 + e3, t13 = e0 - e3, t11 = e1 + e2, t12 = e1 - e2;
+    long long t0 = d[7], t1 = d[5], t2 = d[3], t3 = d[1];
+    z1 = t0 + t3;
+    long long z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
+    const long long z5 = (z3 + z4) * F_1_175875602;
+    t0 *= F_0_298631336; t1 *= F_2_053119869; t2 *= F_3_072711026; t3 *= F_1_501321110;
+    z1 *= -F_0_899976223; z2 *= -F_2_562915447;
+    z3 = z3 * -F_1_961570560 + z5; z4 = z4 * -F_0_390180644 + z5;
+    t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
+    constexpr long long r = 1ll << (kShift - 1);
+    d[0] = (t10 + t3 + r) >> kShift; d[7] = (t10 - t3 + r) >> kShift;
+    d[1] = (t11 + t2 + r) >> kShift; d[6] = (t11 - t2 + r) >> kShift;
+    d[2] = (t12 + t1 + r) >> kShift; d[5] = (t12 - t1 + r) >> kShift;
+    d[3] = (t13 + t0 + r) >> kShift; d[4] = (t13 - t0 + r) >> kShift;
+}
+
+constexpr int kIdctBlocks = kThreads / 8;     // blocks per workgroup
+constexpr int kPlane = 72;                    // ints per block in LDS: rows of 9
+
+// K3.  blockIdx.x: 32 blocks of the image's coefficient scratch (all components, in its order), blockIdx.y: the image.
+// A component's plane lies at 64 x its coef_off bytes, gridw * 8 samples per row.
+__global__ __launch_bounds__(kThreads) void jpeg_dec_idct_kernel(DecBatch b, unsigned char* __restrict__ planes, unsigned long long plane_stride) {
+    __shared__ int s_ws[kIdctBlocks * kPlane];
+    const unsigned t = threadIdx.x, img = blockIdx.y, lb = t >> 3, q = t & 7u;
+    const DecImage& im = b.images[img];
+    const unsigned nc = (unsigned)im.ncomp, nb = im.coef_off[nc - 1] + im.gridw[nc - 1] * im.gridh[nc - 1];
+    const unsigned g = blockIdx.x * kIdctBlocks + lb;
+    if (blockIdx.x * kIdctBlocks >= nb) return;
+    const bool valid = g < nb;
+    unsigned c = 0;
+    for (unsigned k = 1; k < nc; ++k) if (g >= im.coef_off[k]) c = k;
+    long long d[8];
+    bool odd = false;                                             // kStBadRange
+    if (valid) {                                                  // columns: coefficient x table entry, (x + 2^10) >> 11
+        const short* in = b.coef + (unsigned long long)img * b.coef_stride + (unsigned long long)g * 64 + q;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int v = (int)in[8 * r] * (int)im.quant[c][8 * r + q];
+            odd |= v < -32768 || v > 32767;
+            d[r] = v;
+        }
+        idct_1d<11>(d);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) s_ws[lb * kPlane + r * 9 + q] = (int)d[r];
+    }
+    __syncthreads();
+    if (!valid) return;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) d[k] = s_ws[lb * kPlane + q * 9 + k];
+    idct_1d<18>(d);                                               // rows: (x + 2^17) >> 18, then libjpeg's range limit
+    unsigned long long out = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        odd |= d[k] < -512 || d[k] > 511;
+        int v = (int)(d[k] & 1023);
+        if (v >= 512) v -= 1024;
+        v += 128;
+        v = v < 0 ? 0 : v > 255 ? 255 : v;
+        out |= (unsigned long long)v << (8 * k);
+    }
+    if (odd) atomicOr(&b.stat[img], kStBadRange);
+    const unsigned l = g - im.coef_off[c], brow = l / im.gridw[c], bcol = l - brow * im.gridw[c];
+    unsigned char* p = planes + (unsigned long long)img * plane_stride + 64ull * im.coef_off[c] + (unsigned long long)(brow * 8 + q) * (im.gridw[c] * 8) + bcol * 8;
+    *reinterpret_cast<unsigned long long*>(p) = out;              // (8-byte aligned: every term is a multiple of 8)
+}
+
+// K4.  one thread per pixel
+__global__ __launch_bounds__(kThreads) void jpeg_dec_colour_kernel(DecBatch b, const unsigned char* __restrict__ planes, unsigned long long plane_stride,
+                                                                   unsigned char* __restrict__ rgb, unsigned long long image_pitch, int h, int w, int* __restrict__ d_status) {
+    const unsigned img = blockIdx.y;
+    const unsigned long long idx = (unsigned long long)blockIdx.x * kThreads + threadIdx.x;
+    if (idx == 0) d_status[img] = b.stat[img];
+    if (idx >= (unsigned long long)h * w) return;
+    const DecImage& im = b.images[img];
+    const unsigned y = (unsigned)(idx / (unsigned)w), x = (unsigned)(idx - (unsigned long long)y * (unsigned)w);
+    const unsigned char* base = planes + (unsigned long long)img * plane_stride;
+    const int Y = base[(unsigned long long)y * (im.gridw[0] * 8) + x];
+    unsigned char* o = rgb + (unsigned long long)img * image_pitch + idx * 3;
+    if (im.sampling == 3) { o[0] = o[1] = o[2] = (unsigned char)Y; return; }
+    int cc[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const unsigned char* P = base + 64ull * im.coef_off[k + 1];
+        const unsigned pitch = im.gridw[k + 1] * 8, cw = im.pw[k + 1], ch = im.ph[k + 1];
+        if (im.sampling == 0) cc[k] = P[(unsigned long long)y * pitch + x];
+        else if (im.sampling == 1) {                              // jdsample.c h2v1_fancy_upsample
+            const unsigned char* row = P + (unsigned long long)y * pitch;
+            const unsigned i = x >> 1;
+            const int a = row[i];
+            if (x & 1u) cc[k] = i + 1 < cw ? (3 * a + row[i + 1] + 2) >> 2 : a;
+            else cc[k] = i > 0 ? (3 * a + row[i - 1] + 1) >> 2 : a;
+        } else {                                                  // h2v2_fancy_upsample
+            const unsigned r = y >> 1, nr = (y & 1u) ? (r + 1 < ch ? r + 1 : ch - 1) : (r > 0 ? r - 1 : 0);
+            const unsigned char *r0 = P + (unsigned long long)r * pitch, *r1 = P + (unsigned long long)nr * pitch;
+            const unsigned j = x >> 1, jn = (x & 1u) ? (j + 1 < cw ? j + 1 : j) : (j > 0 ? j - 1 : j);
+            const int cs = 3 * r0[j] + r1[j], cn = 3 * r0[jn] + r1[jn];
+            cc[k] = (3 * cs + cn + ((x & 1u) ? 7 : 8)) >> 4;
+        }
+    }
+    const int cb = cc[0] - 128, cr = cc[1] - 128;                 // jdcolor.c: F(x) = floor(x * 65536 + 0.5)
+    const int R = Y + ((91881 * cr + 32768) >> 16), B = Y + ((116130 * cb + 32768) >> 16), G = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
+    o[0] = (unsigned char)(R < 0 ? 0 : R > 255 ? 255 : R);
+    o[1] = (unsigned char)(G < 0 ? 0 : G > 255 ? 255 : G);
+    o[2] = (unsigned char)(B < 0 ? 0 : B > 255 ? 255 : B);
+}
+
+size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+
+}  // namespace
+
+// blocks of one image's coefficient scratch at most, whatever its sampling: three components on the 4:2:0 luma grid
+size_t jpeg_dec_blocks(int h, int w) { return (size_t)3 * (2 * (((size_t)w + 15) / 16)) * (2 * (((size_t)h + 15) / 16)); }
+size_t jpeg_dec_coef_bytes(int n, int h, int w) { return up256(4 * (size_t)n) + (size_t)n * jpeg_dec_blocks(h, w) * 128; }
+size_t jpeg_dec_plane_bytes(int n, int h, int w) { return (size_t)n * jpeg_dec_blocks(h, w) * 64; }
+
+JpegDecLayout jpeg_dec_layout(const jpegparse::Header* hd, const size_t* bytes, int n) {
+    JpegDecLayout L;
+    L.images = 0;
+    L.tabs = up256(sizeof(DecImage) * (size_t)n);
+    L.streams = up256(L.tabs + sizeof(DecTable) * 8 * (size_t)n);
+    size_t ns = 0;
+    for (int i = 0; i < n; ++i) ns += hd[i].nstreams;
+    L.bytes = up256(L.streams + sizeof(DecStream) * ns);
+    L.total = L.bytes;
+    for (int i = 0; i < n; ++i) L.total += up256(jpegparse::scan_room(hd[i], bytes[i]));
+    L.total += 256;                                               // (what an aligned dword load behind the last stream may touch)
+    return L;
+}
+
+// the batch's blob into `blob` (pinned): records, tables, the streams cut and unstuffed.  A file whose scan is refused: Error.
+void jpeg_dec_pack(const uint8_t* const* files, const size_t* bytes, jpegparse::Header* hd, int n, const JpegDecLayout& L, uint8_t* blob, JpegDecLayout& out) {
+    out = L;
+    out.max_long = out.max_short = 0;
+    DecImage* images = reinterpret_cast<DecImage*>(blob + L.images);
+    DecTable* tabs = reinterpret_cast<DecTable*>(blob + L.tabs);
+    DecStream* streams = reinterpret_cast<DecStream*>(blob + L.streams);
+    size_t s0 = 0, b0 = 0;
+    for (int i = 0; i < n; ++i) {
+        const size_t room = jpegparse::scan_room(hd[i], bytes[i]);
+        std::string why;
+        if (!jpegparse::split_scan(hd[i], files[i], bytes[i], blob + L.bytes + b0, room, streams + s0, why)) fail(IRE_ERR_INVALID_INPUT, why);
+        DecStream* first = streams + s0;
+        DecStream* mid = std::stable_partition(first, first + hd[i].nstreams, [](const DecStream& s) { return s.len > kShortMaxBytes; });
+        for (uint32_t k = 0; k < hd[i].nstreams; ++k) first[k].off += (uint32_t)b0;
+        DecImage& im = hd[i].im;
+        im.first_long = (uint32_t)s0; im.nlong = (uint32_t)(mid - first);
+        im.first_short = im.first_long + im.nlong; im.nshort = hd[i].nstreams - im.nlong;
+        out.max_long = std::max(out.max_long, im.nlong); out.max_short = std::max(out.max_short, im.nshort);
+        images[i] = im;
+        std::memcpy(tabs + 8 * (size_t)i, hd[i].tabs, sizeof(DecTable) * 8);
+        s0 += hd[i].nstreams; b0 += up256(room);
+    }
+}
+
+void jpeg_dec_launch(const uint8_t* d_blob, const JpegDecLayout& L, int n, int h, int w, uint8_t* d_coef, uint8_t* d_planes, uint8_t* d_rgb, size_t image_pitch,
+                     int32_t* d_status, hipStream_t s, hipEvent_t* marks) {
+    auto mark = [&](int k) { if (marks) IRE_HIP(hipEventRecord(marks[k], s)); };
+    DecBatch b;
+    b.images = reinterpret_cast<const DecImage*>(d_blob + L.images);
+    b.tabs = reinterpret_cast<const DecTable*>(d_blob + L.tabs);
+    b.streams = reinterpret_cast<const DecStream*>(d_blob + L.streams);
+    b.bytes = d_blob + L.bytes;
+    b.stat = reinterpret_cast<int*>(d_coef);
+    b.coef = reinterpret_cast<short*>(d_coef + up256(4 * (size_t)n));
+    const size_t blocks = jpeg_dec_blocks(h, w);
+    b.coef_stride = blocks * 64;
+    mark(0);
+    IRE_HIP(hipMemsetAsync(d_coef, 0, jpeg_dec_coef_bytes(n, h, w), s));
+    mark(1);
+    if (L.max_long) hipLaunchKernelGGL(jpeg_dec_long_kernel, dim3(L.max_long, n), dim3(kThreads), 0, s, b);
+    mark(2);
+    if (L.max_short) hipLaunchKernelGGL(jpeg_dec_short_kernel, dim3(std::min<uint32_t>((L.max_short + kThreads - 1) / kThreads, 1024u), n), dim3(kThreads), 0, s, b);
+    mark(3);
+    hipLaunchKernelGGL(jpeg_dec_idct_kernel, dim3((unsigned)((blocks + kIdctBlocks - 1) / kIdctBlocks), n), dim3(kThreads), 0, s, b, d_planes, (unsigned long long)(blocks * 64));
+    mark(4);
+    hipLaunchKernelGGL(jpeg_dec_colour_kernel, dim3((unsigned)(((size_t)h * w + kThreads - 1) / kThreads), n), dim3(kThreads), 0, s, b, d_planes, (unsigned long long)(blocks * 64),
+                       d_rgb, (unsigned long long)image_pitch, h, w, d_status);
+    mark(5);
+    IRE_HIP(hipGetLastError());
+}
+
+}  // namespace ire

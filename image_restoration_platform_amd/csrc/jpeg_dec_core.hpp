@@ -1,0 +1,211 @@
+// jpeg_dec_core.hpp -- the entropy decoder of a baseline JPEG scan, written once for the device and for the CPU: the records the
+// host parser (jpeg_parse.hpp) fills and the kernels (jpeg_dec.hip) read, the two bit readers, the per-symbol step and the
+// per-subsequence loop.  Plain C++17, no HIP header: every function is IRE_HD (__host__ __device__ under hipcc, nothing under g++),
+// so tests/native/jpeg_dec_sim.cpp runs the very code of the kernels with lanes as a loop, under ASan and UBSan.
+//
+// The algorithm (Klein & Wiseman 2003; Weissenberger & Schmidt 2018): a Huffman-coded stream re-synchronises by itself, so lanes
+// may start decoding at arbitrary bit positions.  A stream (the bytes between two restart markers, byte stuffing removed) is cut
+// into subsequences of kSubseqBits bits; kLanes consecutive subsequences are a window.  A lane's state is (bit position, block
+// within the MCU, zig-zag position).  In round 0 every lane starts at its own first bit in state (block 0, DC), decodes every
+// symbol that BEGINS before its end and records its end state; in every later round lane i restarts from lane i - 1's end state if
+// that differs from what it started from.  After round k the first k + 1 lanes are exact, so a loop bounded by kLanes is always
+// right and always ends; it stops early when no lane changed.  Then a prefix sum over the lanes' completed-block counts and DC
+// sums gives each lane its first block and its DC predictors, and a second pass writes the coefficients.
+#pragma once
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define IRE_HD __host__ __device__ __forceinline__
+#else
+#define IRE_HD inline
+#endif
+
+namespace ire {
+namespace jpegdec {
+
+constexpr int kLanes = 256;                            // lanes of a window = threads of the workgroup that owns a long stream
+constexpr int kSubseqBits = 1024;                      // S: bits per lane and round
+constexpr unsigned kWindowBits = (unsigned)kLanes * kSubseqBits;
+constexpr unsigned kStageWords = kWindowBits / 32 + 4; // big-endian words staged per window (+ what the last symbol may read ahead)
+constexpr unsigned kStagePadded = kStageWords + kStageWords / 32 + 1;      // one pad word per 32: lane i starts at word 33 i (no bank conflict)
+constexpr unsigned kShortMaxBytes = 2048;              // a stream of at most this many bytes is decoded by ONE lane, start to end
+constexpr unsigned kBadPos = 0xffffffffu;              // the bit position of a state that met an error
+
+// status bits of an image (0 = ok)
+constexpr int kStBadCode = 1;                          // a code that no table holds
+constexpr int kStBadIndex = 2;                         // a zig-zag index above 63
+constexpr int kStBadDc = 4;                            // a DC category above 11
+constexpr int kStBadEnd = 8;                           // the stream ended with blocks missing or bytes left over
+constexpr int kStBadRange = 16;                        // a dequantised coefficient outside int16, or a sample outside -512..511 before the range limit:
+                                                       // no picture gives these, and there libjpeg-turbo's SIMD code (saturating) and its C code (masking) part
+
+// One Huffman table as libjpeg's jdhuff.c decodes it: look[next 9 bits] = length << 8 | symbol for codes of up to 9 bits (0: the
+// code is longer), else the first l in 10..16 with code <= maxcode[l] and the symbol vals[valoff[l] + code].
+struct DecTable {
+    uint16_t look[512];
+    int32_t maxcode[18];                               // [l]: the largest code of length l, -1 when there is none
+    int32_t valoff[18];                                // [l]: index of the first symbol of length l minus its code
+    uint8_t vals[256];
+};
+// What the kernels know about one image.  Blocks are counted in SCAN order over the whole image: block g is block g % bpm of MCU
+// g / bpm.  Coefficients lie [component][block row][block column][64] (natural order, int16) from coef_off[c] (in blocks).
+struct DecImage {
+    int32_t h, w, ncomp, sampling;                     // sampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0, 3 = grey
+    uint32_t bpm, mcus_w, mcus_h, nblocks;             // blocks per MCU; MCUs per row / column; nblocks = mcus_w * mcus_h * bpm
+    uint8_t comp_of[8], bx[8], by[8];                  // per block of an MCU: its component and its place inside the MCU
+    uint8_t hs[4], vs[4], dc_tab[4], ac_tab[4];        // per component: blocks per MCU each way, Huffman table numbers
+    uint32_t gridw[4], gridh[4], coef_off[4];          // per component: blocks per row / column of its grid, first block
+    uint32_t pw[4], ph[4];                             // per component: the REAL size of its plane in samples
+    uint32_t first_long, nlong, first_short, nshort;   // its streams in the batch's stream table: the long ones, then the short ones
+    uint16_t quant[4][64];                             // per component, natural order
+};
+struct DecStream {
+    uint32_t off, len;                                 // its bytes (stuffing removed) in the batch's byte area; off is a multiple of 4
+    uint32_t mcu0, nmcu;                               // its first MCU and its MCU count
+};
+
+struct DecState { uint32_t p, blk, k; };               // bit position | block within the MCU | zig-zag position (0: a DC symbol is next)
+struct LaneOut { uint32_t nblk; uint32_t dc[3]; };     // blocks completed and, per component, the sum of the DC differences decoded
+
+IRE_HD uint32_t natural_of(uint32_t k) {               // zig-zag position -> natural (row-major) index
+    constexpr uint8_t t[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                               35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+    return t[k & 63u];
+}
+
+// ---- bit readers: peek(p) = the 32 bits from bit p on, MSB first; past the stream's end every bit is 1, as libjpeg pads ----------
+// big-endian word k of a stream (bytes 4 k .. 4 k + 3, clamped to the stream's length); `b` is 4-byte aligned
+IRE_HD uint32_t stream_word(const uint8_t* b, uint32_t len, uint32_t k) {
+    const uint64_t i = 4ull * k;
+    if (i + 4 <= len) return __builtin_bswap32(*reinterpret_cast<const uint32_t*>(b + i));
+    uint32_t v = 0;
+    for (uint32_t j = 0; j < 4; ++j) v = (v << 8) | (i + j < len ? b[i + j] : 0xffu);
+    return v;
+}
+// over a window staged by stream_word into padded words (kernel: LDS); bit0 = the first staged bit, a multiple of 32
+struct WordReader {
+    const uint32_t* w;
+    uint32_t bit0;
+    IRE_HD uint32_t peek(uint32_t p) const {
+        const uint32_t i = (p - bit0) >> 5, j = i + 1, s = p & 31u;
+        const uint32_t hi = w[i + (i >> 5)], lo = w[j + (j >> 5)];
+        return s ? (hi << s) | (lo >> (32u - s)) : hi;
+    }
+};
+// over the stream's bytes where they lie, every read clamped to its length
+struct ByteReader {
+    const uint8_t* b;
+    uint32_t len;
+    IRE_HD uint32_t peek(uint32_t p) const {
+        const uint32_t i = p >> 3;
+        uint64_t v = 0;
+        for (uint32_t j = 0; j < 5; ++j) v = (v << 8) | (i + j < len ? b[i + j] : 0xffu);
+        return (uint32_t)(v >> (8u - (p & 7u)));
+    }
+};
+
+// jdhuff's HUFF_EXTEND: the s (0..15) bits behind the first nb (<= 16) bits of w as a signed value.  nb + s <= 31: the peek that
+// gave the code gives the value too
+IRE_HD int extend_from(uint32_t w, uint32_t nb, uint32_t s) {
+    if (s == 0) return 0;
+    const int v = (int)((w << nb) >> (32u - s));
+    return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
+}
+
+// where block g (scan order) of the image lies in the coefficient scratch, in int16 units
+IRE_HD uint32_t block_base(const DecImage& im, uint32_t g) {
+    const uint32_t mcu = g / im.bpm, j = g - mcu * im.bpm, c = im.comp_of[j];
+    const uint32_t my = mcu / im.mcus_w, mx = mcu - my * im.mcus_w;
+    return (im.coef_off[c] + (my * im.vs[c] + im.by[j]) * im.gridw[c] + mx * im.hs[c] + im.bx[j]) * 64u;
+}
+
+// ---- the per-symbol step.  -> kind | kBlockDone; the value and its zig-zag position for kSymDc / kSymAc; st advanced.
+// soft: the synchronising rounds, where a lane that started at a wrong place reads nonsense.  There nothing is an error (an error
+// would stop the lane, and a stopped lane hands nothing on, so the lanes behind it could only settle one per round): an unknown code
+// costs one bit, a run past position 63 ends the block as it does in libjpeg.  A lane that started at the right place of a
+// well-formed stream never takes these branches, so its states are those of the strict step. -----------------------------------------
+constexpr int kSymNone = 0, kSymDc = 1, kSymAc = 2, kSymErr = 3, kBlockDone = 4;
+// t: the table of this symbol (the block's DC table when st.k == 0, else its AC table); bpm: blocks per MCU
+template <class R>
+IRE_HD int dec_step(const R& rd, const DecTable& t, uint32_t bpm, DecState& st, bool soft, int& val, uint32_t& pos, uint32_t& err) {
+    const uint32_t w = rd.peek(st.p);
+    const uint32_t e = t.look[w >> 23];
+    uint32_t nb, sym;
+    if (e) { nb = e >> 8; sym = e & 255u; }
+    else {
+        nb = 10;
+        while (nb <= 16 && (int32_t)(w >> (32u - nb)) > t.maxcode[nb]) ++nb;
+        if (nb > 16) {
+            if (soft) { st.p += 1; return kSymNone; }
+            err |= kStBadCode; return kSymErr;
+        }
+        sym = t.vals[(uint32_t)(t.valoff[nb] + (int32_t)(w >> (32u - nb))) & 255u];
+    }
+    int kind = kSymNone;
+    if (st.k == 0) {
+        if (sym > 11) {
+            if (!soft) { err |= kStBadDc; return kSymErr; }
+            sym &= 15u;
+        }
+        val = extend_from(w, nb, sym); pos = 0;
+        st.p += nb + sym; st.k = 1; kind = kSymDc;
+    } else {
+        const uint32_t r = sym >> 4, s = sym & 15u;
+        st.p += nb + s;
+        if (s == 0) {
+            if (r == 15) { st.k += 16; if (st.k > 63 && !soft) { err |= kStBadIndex; return kSymErr; } }      // ZRL: a coefficient must follow
+            else st.k = 64;                                                                          // end of block
+        } else {
+            st.k += r;
+            if (st.k > 63 && !soft) { err |= kStBadIndex; return kSymErr; }
+            val = extend_from(w, nb, s); pos = st.k & 63u;
+            st.k += 1; kind = kSymAc;
+        }
+    }
+    if (st.k >= 64) { st.k = 0; st.blk = st.blk + 1 >= bpm ? 0 : st.blk + 1; kind |= kBlockDone; }
+    return kind;
+}
+
+// ---- the per-subsequence loop: every symbol that begins before bit `lim`, at most max_blocks completed blocks.  coef == null:
+// count only, with the soft step (the synchronising rounds).  Else block `gblk` (scan order in the image) is the one open at st, dcpred
+// (4 words) holds the running DC per component, and the coefficients are written.  -> error bits; on an error st.p = kBadPos.  Ends
+// after at most lim - st.p steps: every step consumes at least one bit.  What a block needs of the image record (its component, its
+// two tables) is read once per block, and the DC sums are updated by selects, not by indexing: they stay in registers. ---------------
+template <class R>
+IRE_HD uint32_t dec_subseq(const R& rd, const DecTable* tabs, const DecImage& im, DecState& st, uint32_t lim, uint32_t max_blocks, int16_t* coef, uint32_t gblk,
+                           uint32_t* dcpred, LaneOut& o) {
+    o.nblk = 0; o.dc[0] = o.dc[1] = o.dc[2] = 0;
+    uint32_t err = 0;
+    const uint32_t bpm = im.bpm;
+    const bool soft = coef == nullptr;
+    uint32_t base = coef && max_blocks ? block_base(im, gblk) : 0;
+    uint32_t c = im.comp_of[st.blk & 7u] & 3u;
+    const DecTable *tdc = tabs + (im.dc_tab[c] & 3u), *tac = tabs + 4u + (im.ac_tab[c] & 3u);
+    while (st.p < lim && o.nblk < max_blocks) {
+        int val = 0;
+        uint32_t pos = 0;
+        const int r = dec_step(rd, st.k == 0 ? *tdc : *tac, bpm, st, soft, val, pos, err);
+        if ((r & 3) == kSymErr) { st.p = kBadPos; break; }
+        if ((r & 3) == kSymDc) {
+            const uint32_t v = (uint32_t)val;
+            o.dc[0] += c == 0 ? v : 0u; o.dc[1] += c == 1 ? v : 0u; o.dc[2] += c == 2 ? v : 0u;
+            if (coef) {
+                dcpred[0] += c == 0 ? v : 0u; dcpred[1] += c == 1 ? v : 0u; dcpred[2] += c == 2 ? v : 0u;
+                coef[base] = (int16_t)(c == 0 ? dcpred[0] : c == 1 ? dcpred[1] : dcpred[2]);
+            }
+        } else if ((r & 3) == kSymAc && coef) coef[base + natural_of(pos)] = (int16_t)val;
+        if (r & kBlockDone) {
+            ++o.nblk; ++gblk;
+            if (coef && o.nblk < max_blocks) base = block_base(im, gblk);
+            c = im.comp_of[st.blk & 7u] & 3u;
+            tdc = tabs + (im.dc_tab[c] & 3u); tac = tabs + 4u + (im.ac_tab[c] & 3u);
+        }
+    }
+    return err;
+}
+
+// what must hold when a stream's last block is done at bit p: its last byte has begun (the rest of it is padding)
+IRE_HD bool stream_end_ok(uint32_t p, uint32_t len) { return p != kBadPos && p <= 8u * len && 8u * len - p < 8u; }
+
+}  // namespace jpegdec
+}  // namespace ire

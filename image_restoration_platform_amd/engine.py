@@ -45,6 +45,7 @@ class Engine:
         cfg.weights_path = weights_path.encode() if weights_path else None
         cfg.flags = flags
         self._flags = flags
+        self.last_plan_reason = ""
         h = ctypes.c_void_p()
         self._h = None
         self._check(self._lib.ire_init(ctypes.byref(cfg), ctypes.byref(h)))
@@ -310,6 +311,57 @@ class Engine:
                                                                 ctypes.c_void_p(out.data_ptr()), stride, ctypes.c_void_p(lens.data_ptr()),
                                                                 self._stream_ptr(stream)))
         return out[:, :cb], lens
+
+    # ---- baseline JPEG uploads decoded on the device (csrc/jpeg_parse.hpp, csrc/jpeg_dec.hip) ----------------------------------
+    def decode_jpeg_plan_reason(self, data):
+        """bytes of a file -> ((h, w, sampling), None) when the device decodes it (sampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0,
+        3 = grey), else (None, reason) with the reason the C side gives ("invalid: progressive JPEG ...").  Pure host arithmetic;
+        nothing is kept on the engine, so any number of threads may ask (ire_last_error is per thread)."""
+        data = bytes(data)
+        h, w, s = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        if self._lib.ire_decode_jpeg_plan(data, len(data), ctypes.byref(h), ctypes.byref(w), ctypes.byref(s)) != 0:
+            return None, (self._lib.ire_last_error() or b"").decode()
+        return (h.value, w.value, s.value), None
+
+    def decode_jpeg_plan(self, data):
+        """decode_jpeg_plan_reason without the reason: (h, w, sampling) or None.  The reason of the LAST refusal on this engine is kept
+        in .last_plan_reason for interactive use; with several threads use decode_jpeg_plan_reason."""
+        plan, why = self.decode_jpeg_plan_reason(data)
+        if plan is None:
+            self.last_plan_reason = why
+        return plan
+
+    def decode_jpeg(self, data):
+        """bytes of a baseline JPEG file the plan accepts -> [h,w,3] uint8, equal to PIL.Image.open(f).convert("RGB"); raises
+        EngineError (invalid input) for a file out of scope or with corrupt data.  The plan runs here (the output's size comes from
+        it): a caller need not ask first."""
+        data = bytes(data)
+        plan, why = self.decode_jpeg_plan_reason(data)
+        if plan is None:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, why)
+        h, w, _ = plan
+        out = np.empty((h, w, 3), np.uint8)
+        self._check(self._lib.ire_decode_jpeg(self._h, data, len(data), _ptr(out), h, w))
+        return out
+
+    def decode_jpeg_device(self, files, out_u8=None, stream=None):
+        """list of N <= max_batch files (bytes) of one planned size -> (cuda uint8 [N,h,w,3], cuda int32 [N] status words, 0 = ok),
+        asynchronous on the stream.  out_u8: a cuda uint8 [N,h,w,3] tensor or a view of one whose images are dense (h*w*3 bytes)."""
+        import torch
+        files = [bytes(f) for f in files]
+        plans = [self.decode_jpeg_plan_reason(f)[0] for f in files]
+        if not files or any(p is None for p in plans) or len({p[:2] for p in plans}) != 1:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid input: decode_jpeg_device takes files of one planned size")
+        n, (h, w, _) = len(files), plans[0]
+        if out_u8 is None:
+            out_u8 = torch.empty((n, h, w, 3), dtype=torch.uint8, device="cuda")
+        assert out_u8.is_cuda and out_u8.dtype == torch.uint8 and tuple(out_u8.shape) == (n, h, w, 3) and out_u8[0].is_contiguous()
+        status = torch.empty(n, dtype=torch.int32, device=out_u8.device)
+        ptrs = (ctypes.c_char_p * n)(*files)
+        lens = (ctypes.c_size_t * n)(*[len(f) for f in files])
+        self._check(self._lib.ire_decode_jpeg_device(self._h, ptrs, lens, n, h, w, ctypes.c_void_p(out_u8.data_ptr()), out_u8.stride(0) if n > 1 else h * w * 3,
+                                                     ctypes.c_void_p(status.data_ptr()), self._stream_ptr(stream)))
+        return out_u8, status
 
     def encode_png_base64(self, rgb):
         """[N,H,W,3] (or [H,W,3]) uint8 -> list of N `bytes` (one for a single image): the base64 text of a PNG file of each image,

@@ -47,6 +47,9 @@ export function bindIre(libPath) {
     ire_jpeg_base64_bound: ['size_t', ['int', 'int']],
     ire_encode_jpeg_base64_fit_device: ['int', [P, P, 'int', 'int', 'int', 'size_t', 'size_t', P, 'size_t', P, P]],
     ire_encode_jpeg_base64_fit: ['int', [P, P, 'int', 'int', 'int', P, 'size_t', P]],
+    ire_decode_jpeg_plan: ['int', [P, 'size_t', P, P, P]],
+    ire_decode_jpeg: ['int', [P, P, 'size_t', P, 'int', 'int']],
+    ire_decode_jpeg_device: ['int', [P, P, P, 'int', 'int', 'int', P, 'size_t', P, P]],
     ire_job_release: ['int', [P, P]],
     ire_affinity_plan: ['int', ['string', 'string', P, 'size_t', IP, IP, IP]],
     ire_engine_affinity: ['int', [P, P, 'size_t', IP]],

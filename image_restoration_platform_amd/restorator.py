@@ -36,10 +36,28 @@ def _now_ms():
     return int(time.time() * 1000)  # Date.now()
 
 
-def decode_image(buffer):
+# How an upload becomes pixels (IRE_UPLOAD_CODEC, read at each call):
+#   unset        host PIL (libjpeg-turbo, libpng, ...): every format, ~5.6 ms of one core per 1024^2 JPEG -- the default
+#   jpeg-device  a baseline JPEG the engine's plan accepts (csrc/jpeg_parse.hpp) is decoded on the GPU (csrc/jpeg_dec.hip) to the
+#                very bytes PIL gives; every other file -- progressive, CMYK, PNG, WebP, one the device flags as corrupt -- goes
+#                to PIL exactly as above
+UPLOAD_DECODES = {"device": 0, "host": 0}      # which way the uploads of this process went
+
+
+def decode_image(buffer, engine=None):
     """encoded bytes -> (rgb uint8 [H,W,3], format str).  sharp(buf) decodes to 8-bit sRGB
     (Appendix A.1); no EXIF rotation inside the classifier (A.2)."""
     from PIL import Image
+    if engine is not None and os.environ.get("IRE_UPLOAD_CODEC") == "jpeg-device" and bytes(buffer[:2]) == b"\xff\xd8":
+        from .engine import EngineError
+        try:
+            rgb = engine.decode_jpeg(bytes(buffer))      # plans inside: a file out of scope or flagged on the device is "invalid input"
+            UPLOAD_DECODES["device"] += 1
+            return rgb, "jpeg"
+        except EngineError as e:
+            if e.status != _lib.IRE_ERR_INVALID_INPUT:   # only that is the host codec's to judge; unavailable / internal go up
+                raise
+    UPLOAD_DECODES["host"] += 1
     try:
         im = Image.open(io.BytesIO(bytes(buffer)))
         fmt = (im.format or "").lower()
@@ -124,7 +142,7 @@ class EngineClassifier:
         self.logger = logger
 
     def analyze(self, image_buffer):
-        rgb, fmt = decode_image(image_buffer)
+        rgb, fmt = decode_image(image_buffer, self.engine)
         scores, _ = self.engine.classify(rgb, is_jpeg=(fmt == "jpeg"))
         _seen_of(self.engine).put(image_buffer, rgb, fmt, scores[0].copy())
         return {k: float(scores[0, i]) for i, k in enumerate(KEYS)}
@@ -161,7 +179,7 @@ class EngineRestorer:
         decoded = []
         for b in images:             # analyze() already decoded and classified this buffer: reuse both
             hit = seen.take(b)
-            decoded.append(hit if hit is not None else (*decode_image(b), None))
+            decoded.append(hit if hit is not None else (*decode_image(b, self.engine), None))
         shapes = {d[0].shape for d in decoded}
         if len(shapes) != 1:
             raise ValueError("invalid images: fusion views must have identical dimensions")

@@ -16,6 +16,7 @@ engine's "service unavailable" message (there is no CPU fallback).
 Run: uvicorn image_restoration_platform_amd.serving.app:app
 """
 import base64
+import os
 import threading
 
 from fastapi import FastAPI, Request
@@ -130,9 +131,13 @@ async def restore_batch(request: Request):
     enhancer = PromptEnhancerService(None)
     results = [None] * len(bufs)
     decoded, groups = {}, {}
+    dec_engine = None
+    if os.environ.get("IRE_UPLOAD_CODEC") == "jpeg-device":     # baseline JPEG uploads are decoded by the ctypes engine (csrc/jpeg_dec.hip)
+        get_service()
+        dec_engine = _state["engine"]
     for i, b in enumerate(bufs):
         try:
-            rgb, fmt = decode_image(b)
+            rgb, fmt = decode_image(b, dec_engine)
             decoded[i] = (rgb, fmt)
             groups.setdefault(rgb.shape, []).append(i)          # by the image's own shape: the engine takes any size
         except Exception as e:  # noqa: BLE001 -- the reference's envelope for a failed image (restorator.js:141-167)

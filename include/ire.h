@@ -225,6 +225,31 @@ int ire_encode_jpeg_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n
 int ire_encode_jpeg_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes,
                                uint64_t* lens /* n x uint64, host */);
 
+/* ---- baseline JPEG uploads decoded on the device ----
+ * The RGB bytes equal libjpeg-turbo's (PIL.Image.open(f).convert("RGB")): the file's own Huffman tables, libjpeg's "islow" inverse
+ * DCT, its "fancy" chroma upsampling and its 16-bit fixed-point colour transform.
+ * ire_decode_jpeg_plan: pure host, no engine.  IRE_OK and the size (sampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0, 3 = grey; any
+ * output pointer may be NULL) if the device decodes this file: SOF0 / SOF1 with Huffman coding, 8-bit samples, one interleaved
+ * scan, 8-bit quantiser tables, up to 4 + 4 Huffman tables of any content, with or without restart markers, 1..8192 per side; Y Cb
+ * Cr with luma 1x1 / 2x1 / 2x2 over chroma 1x1 (width >= 5 when subsampled), or one grey component.  Everything else --
+ * progressive, arithmetic coding, 12 bit, CMYK, Adobe / RGB colour, several scans, other sampling factors, DNL, a truncated
+ * file -- is IRE_ERR_INVALID_INPUT with the reason in ire_last_error ("invalid: ..."): such a file stays with the host codec.
+ * ire_decode_jpeg: synchronous; out_rgb receives h*w*3 bytes (h, w as planned).  A stream whose entropy-coded data is corrupt
+ * (found on the device) is IRE_ERR_INVALID_INPUT "invalid: corrupt JPEG data"; the engine stays usable.  So is a well-formed stream
+ * whose values no picture gives (a dequantised coefficient outside int16, a sample outside -512..511 before the range limit): there
+ * libjpeg-turbo's own C and SIMD code give different bytes, and equality with it is promised for every image that is NOT flagged.
+ * ire_decode_jpeg_device: n <= max_batch files (host memory) of ONE planned size -> n images on the device, tightly packed rows,
+ * image i at d_rgb + i * image_pitch_bytes (>= h*w*3), ready for ire_classify_device / ire_preprocess_device /
+ * ire_restore_fit_device on the same stream; d_status: one int32 per image, 0 = ok (the pixels of a flagged image are
+ * unspecified, nothing outside them is written).  The host parse runs inside the call; the number of stream operations does not
+ * depend on n.  The host waits for one thing only: the upload of the call before last, whose pinned staging (one of two) this call
+ * reuses; uploads are ordered behind the kernels of the call before them, so a caller that runs three calls ahead of the device waits
+ * for those kernels -- never for the kernels of the call directly before it, nor for its own. */
+int ire_decode_jpeg_plan(const uint8_t* file, size_t bytes, int* out_h, int* out_w, int* out_sampling);
+int ire_decode_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, uint8_t* out_rgb /* h*w*3 */, int h, int w);
+int ire_decode_jpeg_device(ire_engine* e, const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb,
+                           size_t image_pitch_bytes, int32_t* d_status /* n x int32, device */, void* stream);
+
 /* ---- async batcher (restoreBatch's in-flight promises) ---------------------------------- */
 typedef struct ire_job ire_job;
 /* Queue one h x w image for restoration; jobs of equal shape are coalesced into batches of up

@@ -70,6 +70,7 @@ SYMBOLS = {
     "ire_decode_jpeg": (_i, [_vp, _u8p, ctypes.c_size_t, _u8p, _i, _i]),
     "ire_decode_jpeg_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp, _vp]),
     "ire_submit_fit": (_i, [_vp, _u8p, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
+    "ire_submit_jpeg": (_i, [_vp, _u8p, ctypes.c_size_t, _vp, ctypes.POINTER(_vp)]),
     "ire_submit": (_i, [_vp, _u8p, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
     "ire_restore_tiled_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ire_strips_stats_bytes": (ctypes.c_size_t, [_i, _i]),

@@ -62,6 +62,16 @@ struct SlotEvents {
 // the backend's side of a slot: its staging (device_buf.hpp; SlotBufs holds views of the pinned half) and its events
 struct HipSlot : SlotMem<DeviceMem, PinnedMem> {
     std::unique_ptr<SlotEvents> ev;
+    // file jobs: one status word per job from the device's JPEG decoder, and their way back with the batch
+    Buf<DeviceMem> d_fstat;
+    Buf<PinnedMem> pin_fstat;
+    int file_jobs = 0;         // jobs decoded into d_in since the slot opened; 0: a slot of pixel jobs
+};
+
+// what a file job keeps of its file between submit and its batch's decode: the head as parsed, the scan's streams as cut
+struct JpegFileHead {
+    jpegparse::Header hd;
+    std::vector<jpegdec::DecStream> streams;
 };
 
 // CPU set of this engine's service threads (affinity.hpp): IRE_CPU_AFFINITY = "off" | a cpulist overrides the sysfs plan
@@ -153,8 +163,54 @@ struct HipBatchBackend {
         delete static_cast<HipSlot*>(b.impl);
         b = SlotBufs{};
     }
+    // ---- file jobs (batcher.hpp: the optional hooks).  The parse and the cut run in the submitting thread; the launcher only packs
+    // the records of the jobs staged so far and enqueues the decode on the copy-in stream, under the previous batch's compute. ----
+    std::shared_ptr<void> file_plan(const uint8_t* file, size_t bytes, int* h, int* w, size_t* room) {
+        auto head = std::make_shared<JpegFileHead>();
+        std::string why;
+        if (!jpegparse::plan(file, bytes, head->hd, why)) fail(IRE_ERR_INVALID_INPUT, why);
+        *h = head->hd.im.h; *w = head->hd.im.w;
+        *room = jpegparse::scan_room(head->hd, bytes);
+        return head;
+    }
+    size_t file_stage(void* head, const uint8_t* file, size_t bytes, uint8_t* dst, size_t room) {
+        JpegFileHead& f = *static_cast<JpegFileHead*>(head);
+        f.streams.assign(f.hd.nstreams, jpegdec::DecStream{});
+        std::string why;
+        if (!jpegparse::split_scan(f.hd, file, bytes, dst, room, f.streams.data(), why)) fail(IRE_ERR_INVALID_INPUT, why);
+        const jpegdec::DecStream& last = f.streams.back();
+        return (size_t)last.off + last.len;
+    }
+    void decode(SlotBufs& b, int first, int count, int h, int w, void* const* heads, const size_t* used) {
+        HipSlot& hs = *static_cast<HipSlot*>(b.impl);
+        const size_t ib = (size_t)h * w * 3;
+        if (!hs.d_fstat) {                // zeroed once: the word of a job with nothing to decode is never written
+            hs.d_fstat = Buf<DeviceMem>(sizeof(int32_t) * kMaxBatch); hs.pin_fstat = Buf<PinnedMem>(sizeof(int32_t) * kMaxBatch);
+            IRE_HIP(hipMemsetAsync(hs.d_fstat.get<int32_t>(), 0, sizeof(int32_t) * kMaxBatch, cs));
+            std::memset(hs.pin_fstat.get<int32_t>(), 0, sizeof(int32_t) * kMaxBatch);
+        }
+        const jpegparse::Header* hd[kMaxBatch];
+        const jpegdec::DecStream* streams[kMaxBatch];
+        const uint8_t* bytes[kMaxBatch];
+        size_t room[kMaxBatch];
+        hs.file_jobs = first + count;
+        // a job whose staging failed (batcher.hpp) has nothing to decode: its place keeps whatever the slot held, its job fails alone;
+        // the runs of jobs between such ones are decoded one call each
+        for (int i = 0; i < count;) {
+            if (!used[i]) { ++i; continue; }
+            int n = 0;
+            const int i0 = i;
+            for (; i < count && used[i]; ++i, ++n) {
+                const JpegFileHead& f = *static_cast<const JpegFileHead*>(heads[i]);
+                hd[n] = &f.hd; streams[n] = f.streams.data(); bytes[n] = b.pin_in + ib * (size_t)(first + i); room[n] = used[i];
+            }
+            E.decode_jpeg_streams(hd, streams, bytes, room, n, h, w, hs.d_in.get<uint8_t>() + ib * (size_t)(first + i0), ib, hs.d_fstat.get<int32_t>() + first + i0, cs);
+        }
+    }
+    int file_status(SlotBufs& b, int i) { return static_cast<HipSlot*>(b.impl)->pin_fstat.get<int32_t>()[i]; }
     void h2d(SlotBufs& b, size_t off, size_t bytes) {
         HipSlot& hs = *static_cast<HipSlot*>(b.impl);
+        hs.file_jobs = 0;
         IRE_HIP(hipMemcpyAsync(hs.d_in.get<uint8_t>() + off, b.pin_in + off, bytes, hipMemcpyHostToDevice, cs));
     }
     void launch(SlotBufs& b, int n, int h, int w, const uint8_t* has_sc) {
@@ -170,6 +226,8 @@ struct HipBatchBackend {
             // engine's staging and its window comes back; with text() the results leave the device as text
             E.restore_fit_device_mixed(hs.d_in.get<uint8_t>(), n, h, w, b.pin_sc_in, has_sc, hs.d_jp.get<uint8_t>(), hs.d_out.get<uint8_t>(), text() ? hs.d_txt.get<uint8_t>() : nullptr, (out_bytes(h, w) + 255) / 256 * 256, ms);
             IRE_HIP(hipMemcpyAsync(b.pin_sc, E.scores_device(), sizeof(double) * 7 * n, hipMemcpyDeviceToHost, ms));
+            if (hs.file_jobs) IRE_HIP(hipMemcpyAsync(hs.pin_fstat.get<int32_t>(), hs.d_fstat.get<int32_t>(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ms));
+            hs.file_jobs = 0;
             IRE_HIP(hipEventRecord(hs.ev->c1, ms));
             IRE_HIP(hipEventRecord(hs.ev->cw, ms));
         });
@@ -620,6 +678,17 @@ int ire_submit_fit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg,
         if (!rgb || !job_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_fit");
         if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size: height and width must be in 1..8192");
         queue_job(e, rgb, h, w, is_jpeg, scores, job_out);
+    });
+}
+
+int ire_submit_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, const double* scores, ire_job** job_out) {
+    return guarded([&] {
+        eng(e);
+        if (!file || !job_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_jpeg");
+        *job_out = nullptr;
+        std::unique_ptr<ire_job> hnd(new ire_job{});
+        hnd->j = e->batcher->submit_file(file, bytes, scores);
+        *job_out = hnd.release();
     });
 }
 

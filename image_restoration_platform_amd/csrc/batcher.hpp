@@ -58,12 +58,15 @@ struct Job {
     bool has_scores = false;
     bool staged = false;              // input bytes are in the slot's pinned buffer (or in `in` on the overflow path)
     bool abandoned = false;           // released while pending: its result is dropped when the batch completes
+    std::shared_ptr<void> file;       // a file job (submit_file): what the backend's file_plan made of the file's head; its staged input is the scan, cut
+    size_t file_used = 0;             // bytes of that input
     BatchSlot* slot = nullptr;        // where the input was staged and the output will be; null: overflow (no free slot at submit) / evicted / fetched
     int idx = -1;
     std::vector<uint8_t> in, out;     // overflow input / evicted output only
     double scores[7] = {};
     ire_timings t{};
     int status = -1;                  // -1 pending, else ire_status
+    int stage_status = IRE_OK;        // a file job whose staging failed after it had got its place: the status it completes with
     std::string err;
 };
 
@@ -82,7 +85,8 @@ struct BatchSlot {
     uint8_t has_sc[kMaxBatch] = {};
     std::vector<std::shared_ptr<Job>> jobs;   // index order = position in the batch
     int h = 0, w = 0;
-    int h2d_issued = 0;                   // images whose H2D copy is already on the copy-in stream
+    bool files = false;                   // gathers file jobs (never mixed with pixel jobs: their input is decoded on the device, not copied)
+    int h2d_issued = 0;                   // images whose H2D copy (file jobs: whose decode) is already on the copy-in stream
     int unread = 0, reading = 0;          // DONE: jobs that have not fetched their output yet / polls copying right now
     std::chrono::steady_clock::time_point first_arrival, last_arrival;
     int status = IRE_OK;
@@ -106,6 +110,23 @@ struct BatchSlot {
 //   const uint8_t* result_view(const uint8_t* place, int h, int w, size_t* len) const;
 //                                                              a result whose size depends on the data: where its payload starts inside
 //                                                              its out_bytes(h, w)-sized place and how long it really is
+// OPTIONAL, all four or none (detected at compile time; without them submit_file does not compile): FILE JOBS, whose input is an
+// encoded file that the backend decodes on the device into the slot's device input, h * w * 3 bytes per job, in place of h2d
+//   std::shared_ptr<void> file_plan(const uint8_t* file, size_t bytes, int* h, int* w, size_t* room);
+//                                                              submitting thread, no lock: reads the file's head and checks all of it;
+//                                                              throws Error when the file is refused.  *room: bytes file_stage needs at most
+//   size_t file_stage(void* head, const uint8_t* file, size_t bytes, uint8_t* dst, size_t room);
+//                                                              submitting thread, no lock: what the device needs of the file into dst (the
+//                                                              job's place in pin_in, or the job's own vector); -> bytes written; throws Error
+//   void decode(SlotBufs&, int first, int count, int h, int w, void* const* heads, const size_t* used);
+//                                                              launcher, in place of h2d, WITHOUT the batcher's lock, copy-in stream: jobs first ..
+//                                                              first + count - 1 of the slot, their staged bytes at pin_in + h * w * 3 * index; throws Error
+//   int file_status(SlotBufs&, int index);                     after wait_done: 0, or what the device found wrong with that job's data
+template <class B, class = void>
+struct has_file_jobs : std::false_type {};
+template <class B>
+struct has_file_jobs<B, std::void_t<decltype(std::declval<B&>().file_status(std::declval<SlotBufs&>(), 0))>> : std::true_type {};
+
 template <class B, class = void>
 struct has_result_view : std::false_type {};
 template <class B>
@@ -158,16 +179,7 @@ class Batcher {
         uint8_t* dst = nullptr;
         {
             std::lock_guard<std::mutex> lk(mu_);
-            if (stop_) fail(IRE_ERR_UNAVAILABLE, "service unavailable: the engine is shutting down");
-            if (!started_) {
-                be_.start();
-                // staging for the three slots of a steady stream now, at this first shape (pinning 3 x 2 x max_batch images takes tens
-                // of ms): the first job pays it once, instead of later jobs paying it one slot at a time in the middle of a stream
-                for (int i = 0; i < kSlotsEager; ++i) be_.reserve(slots_[i].b, std::max(ib, be_.out_bytes(h, w)) * (size_t)be_.max_batch(), be_.max_batch());
-                launcher_ = std::thread([this] { launcher_loop(); });
-                completer_ = std::thread([this] { completer_loop(); });
-                started_ = true;
-            }
+            start_locked(h, w);
             const int si = overflow_.empty() ? slot_for(h, w) : -1;     // (jobs already overflowing keep their order)
             if (si >= 0) { slot_add(si, j); dst = slots_[si].b.pin_in + ib * j->idx; }
         }
@@ -181,6 +193,47 @@ class Batcher {
             j->staged = true;
             overflow_.push_back(j);
             cnt_.overflowed += 1;
+        }
+        qcv_.notify_all();
+        return j;
+    }
+
+    // Queue one encoded file (backends with file jobs).  The head is parsed and the scan is cut HERE, in the submitting thread,
+    // straight into the job's place in the slot's pinned input; the launcher only hands the staged jobs to the backend's decode.
+    // Throws Error when the backend refuses the file: no job exists then.
+    template <class BE = Backend>
+    std::shared_ptr<Job> submit_file(const uint8_t* file, size_t bytes, const double* scores) {
+        static_assert(has_file_jobs<BE>::value, "this backend has no file jobs");
+        auto j = std::make_shared<Job>();
+        size_t room = 0;
+        j->file = be_.file_plan(file, bytes, &j->h, &j->w, &room);
+        j->is_jpeg = 1;
+        if (scores) { std::memcpy(j->scores, scores, sizeof(double) * 7); j->has_scores = true; }
+        const int h = j->h, w = j->w;
+        const size_t ib = (size_t)h * w * 3;
+        if (room > ib) fail(IRE_ERR_INVALID_INPUT, "invalid: the file's entropy-coded data may be larger than its pixels (it stays with the host codec)");
+        uint8_t* dst = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            start_locked(h, w);
+            const int si = overflow_.empty() ? slot_for(h, w, true) : -1;
+            if (si >= 0) { slot_add(si, j); dst = slots_[si].b.pin_in + ib * j->idx; }
+        }
+        size_t used = 0;
+        int code = IRE_OK;
+        std::string why;
+        if (!dst) j->in.resize(room);
+        // (file_plan checked the whole file, so this cannot refuse it -- unless the caller changed the bytes meanwhile: the job then
+        // exists already, holds its place with nothing to decode and fails alone when its batch completes)
+        try { used = be_.file_stage(j->file.get(), file, bytes, dst ? dst : j->in.data(), room); }
+        catch (const Error& e) { code = e.code; why = e.msg; }
+        catch (const std::exception& e) { code = IRE_ERR_UNAVAILABLE; why = std::string("service unavailable: ") + e.what(); }      // (a bad_alloc: the job has its place, so it must become staged)
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            j->file_used = used;
+            if (code != IRE_OK) { j->stage_status = code; j->err = why; j->file_used = 0; }
+            if (!dst) { j->in.resize(j->file_used); overflow_.push_back(j); cnt_.overflowed += 1; }
+            j->staged = true;
         }
         qcv_.notify_all();
         return j;
@@ -258,6 +311,19 @@ class Batcher {
     }
 
   private:
+    // (mu_ held) at the top of every submit: refuses while shutting down; the first one starts the backend and the service threads
+    void start_locked(int h, int w) {
+        if (stop_) fail(IRE_ERR_UNAVAILABLE, "service unavailable: the engine is shutting down");
+        if (started_) return;
+        be_.start();
+        // staging for the three slots of a steady stream now, at this first shape (pinning 3 x 2 x max_batch images takes tens
+        // of ms): the first job pays it once, instead of later jobs paying it one slot at a time in the middle of a stream
+        for (int i = 0; i < kSlotsEager; ++i) be_.reserve(slots_[i].b, std::max((size_t)h * w * 3, be_.out_bytes(h, w)) * (size_t)be_.max_batch(), be_.max_batch());
+        launcher_ = std::thread([this] { launcher_loop(); });
+        completer_ = std::thread([this] { completer_loop(); });
+        started_ = true;
+    }
+
     // (mu_ held) a job's result has been fetched or given up: the slot is free once the last one has
     void drop_reader(BatchSlot& S, Job& j) {
         j.slot = nullptr;
@@ -269,11 +335,11 @@ class Batcher {
     // (mu_ held) an OPEN slot of this shape with room, else a FREE one opened for it, else -1.  May allocate staging (first use
     // of a shape: once).  A DONE slot nobody is reading is evicted when nothing else is left: its unfetched outputs move to
     // their jobs' own vectors (the extra copy only a caller that lets a slot's worth of batches pile up unpolled ever pays).
-    int slot_for(int h, int w) {
+    int slot_for(int h, int w, bool files = false) {
         const int mb = be_.max_batch();
         for (auto it = open_order_.rbegin(); it != open_order_.rend(); ++it) {
             BatchSlot& S = slots_[*it];
-            if (S.h == h && S.w == w && (int)S.jobs.size() < mb) return *it;
+            if (S.h == h && S.w == w && S.files == files && (int)S.jobs.size() < mb) return *it;
         }
         int pick = -1;
         const size_t need = std::max((size_t)h * w * 3, be_.out_bytes(h, w)) * (size_t)mb;
@@ -297,7 +363,7 @@ class Batcher {
         if (pick < 0) return -1;
         BatchSlot& S = slots_[pick];
         be_.reserve(S.b, need, mb);               // strong guarantee: a throw leaves the slot FREE with what it had
-        S.state = BatchSlot::OPEN; S.h = h; S.w = w; S.jobs.clear(); S.h2d_issued = 0; S.unread = S.reading = 0;
+        S.state = BatchSlot::OPEN; S.h = h; S.w = w; S.files = files; S.jobs.clear(); S.h2d_issued = 0; S.unread = S.reading = 0;
         S.status = IRE_OK; S.err.clear();
         S.first_arrival = S.last_arrival = clk::now();
         open_order_.push_back(pick);
@@ -318,14 +384,54 @@ class Batcher {
 
     // (launcher, mu_ held) H2D of every image staged so far, in index order, on the copy-in stream: rides under the previous
     // batch's compute.  A failure is recorded in the slot (the launch then fails the batch).
-    void slot_push_h2d(BatchSlot& S) {
+    // File jobs go to the backend's decode instead, and only once the batch is full or closing: a decode costs a fixed set of
+    // launches whatever the number of images (measured, profiles/jpeg_file_jobs.md: one 1024^2 file 2.5 ms, eight 4.7 ms), so pushing
+    // them one by one as they arrive would cap the slot at the one-file rate.  A full batch still goes at once and its decode runs on
+    // the copy-in stream under the previous batch's compute.  The decode is called with mu_ RELEASED (it packs records, may wait for
+    // an upload and enqueues a dozen operations; submitters and pollers must not queue behind that): the slot is full or CLOSED, so
+    // nobody adds to it meanwhile, and only this thread moves a slot out of OPEN / CLOSED.
+    void slot_push_h2d(BatchSlot& S, std::unique_lock<std::mutex>& lk, bool closing) {
         const size_t ib = (size_t)S.h * S.w * 3;
         int upto = S.h2d_issued;
         while (upto < (int)S.jobs.size() && S.jobs[upto]->staged) ++upto;
         if (upto == S.h2d_issued || S.status != IRE_OK) return;
-        try { be_.h2d(S.b, ib * S.h2d_issued, ib * (size_t)(upto - S.h2d_issued)); }
-        catch (const Error& e) { S.status = e.code; S.err = e.msg; }
+        if (S.files && !closing && upto < be_.max_batch()) return;
+        int code = IRE_OK;
+        std::string why;
+        try {
+            if (S.files) push_decode(S, upto, lk);
+            else be_.h2d(S.b, ib * S.h2d_issued, ib * (size_t)(upto - S.h2d_issued));
+        } catch (const Error& e) { code = e.code; why = e.msg; }
+        catch (const std::exception& e) { code = IRE_ERR_UNAVAILABLE; why = std::string("service unavailable: ") + e.what(); }      // (a decode's host allocations)
+        if (!lk.owns_lock()) lk.lock();
+        if (code != IRE_OK) { S.status = code; S.err = why; }
         S.h2d_issued = upto;
+    }
+
+    // (launcher) file jobs h2d_issued .. upto - 1 of the slot to the backend's decode; collects under mu_, calls without it
+    template <class BE = Backend>
+    void push_decode(BatchSlot& S, int upto, std::unique_lock<std::mutex>& lk) {
+        if constexpr (has_file_jobs<BE>::value) {
+            void* heads[kMaxBatch];
+            size_t used[kMaxBatch];
+            const int first = S.h2d_issued, count = upto - first, h = S.h, w = S.w;
+            for (int i = 0; i < count; ++i) { heads[i] = S.jobs[first + i]->file.get(); used[i] = S.jobs[first + i]->file_used; }
+            lk.unlock();
+            be_.decode(S.b, first, count, h, w, heads, used);
+            lk.lock();
+        } else fail(IRE_ERR_INTERNAL, "internal: a file slot on a backend without file jobs");
+    }
+
+    // (mu_ held) what fails job i of a completed batch ALONE: its staging failed at submit, or the device flagged its data
+    template <class BE = Backend>
+    bool job_failed_alone(BatchSlot& S, int i, Job& j) {
+        if (!S.files) return false;
+        if (j.stage_status != IRE_OK) { j.status = j.stage_status; return true; }       // (j.err holds the reason since submit)
+        if constexpr (has_file_jobs<BE>::value) {
+            const int st = be_.file_status(S.b, i);
+            if (st != 0) { j.status = IRE_ERR_INVALID_INPUT; j.err = "invalid: corrupt JPEG data (decoder status " + std::to_string(st) + ")"; return true; }
+        }
+        return false;
     }
 
     void complete_jobs(BatchSlot& S, const ire_timings& t) {     // mu_ held
@@ -333,6 +439,7 @@ class Batcher {
         int readers = 0;
         for (int i = 0; i < n; ++i) {
             Job& j = *S.jobs[i];
+            if (S.status == IRE_OK && !j.abandoned && job_failed_alone(S, i, j)) { j.slot = nullptr; continue; }
             if (S.status == IRE_OK && !j.abandoned) { std::memcpy(j.scores, S.b.pin_sc + 7 * i, sizeof(double) * 7); j.t = t; ++readers; }
             else j.slot = nullptr;
             j.err = S.err;
@@ -352,7 +459,7 @@ class Batcher {
             while (!overflow_.empty()) {
                 std::shared_ptr<Job> j = overflow_.front();
                 int si = -1;
-                try { si = slot_for(j->h, j->w); }
+                try { si = slot_for(j->h, j->w, j->file != nullptr); }
                 catch (const Error& e) { fail_job(*j, e.code, e.msg); overflow_.pop_front(); dcv_.notify_all(); continue; }
                 catch (const std::exception& e) {      // bad_alloc while evicting a DONE slot: this job fails, the service thread lives
                     fail_job(*j, IRE_ERR_UNAVAILABLE, std::string("service unavailable: ") + e.what()); overflow_.pop_front(); dcv_.notify_all(); continue;
@@ -361,7 +468,7 @@ class Batcher {
                 overflow_.pop_front();
                 slot_add(si, j);
                 BatchSlot& S = slots_[si];
-                std::memcpy(S.b.pin_in + (size_t)j->h * j->w * 3 * j->idx, j->in.data(), j->in.size());
+                if (!j->in.empty()) std::memcpy(S.b.pin_in + (size_t)j->h * j->w * 3 * j->idx, j->in.data(), j->in.size());
                 j->in.clear(); j->in.shrink_to_fit();
             }
             if (open_order_.empty()) {
@@ -373,7 +480,7 @@ class Batcher {
             }
             const int si = open_order_.front();
             BatchSlot& S = slots_[si];
-            slot_push_h2d(S);
+            slot_push_h2d(S, lk, false);
             const bool full = (int)S.jobs.size() >= be_.max_batch();
             if (!full && !stop_ && S.status == IRE_OK && open_order_.size() == 1) {
                 bool gpu_busy = false;
@@ -399,7 +506,7 @@ class Batcher {
             S.state = BatchSlot::CLOSED;
             open_order_.pop_front();
             qcv_.wait(lk, [&] { for (auto& j : S.jobs) if (!j->staged) return false; return true; });
-            slot_push_h2d(S);
+            slot_push_h2d(S, lk, true);
             const int n = (int)S.jobs.size();
             bool wanted = false;
             for (auto& j : S.jobs) wanted = wanted || !j->abandoned;

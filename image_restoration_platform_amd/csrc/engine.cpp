@@ -56,6 +56,7 @@ Engine::Engine(const ire_config& cfg) {
     cus_ = persistent_grid_cus();
     if (const char* v = std::getenv("IRE_SNAKE")) snake_ = std::atoi(v) != 0;
     if (const char* v = std::getenv("IRE_JPEG_DEC_TIMES")) dec_times_ = std::atoi(v) != 0;
+    if (const char* v = std::getenv("IRE_JPEG_DEC_WINDOWS")) dec_min_windows_ = (uint32_t)std::max(0, std::atoi(v));
     if (const char* v = std::getenv("IRE_RB_STAMPS")) {   // diagnostic: "<cout>[r]" = stamp the first such ResBlock conv
         stamps_cout_ = std::atoi(v);
         stamps_resid_ = std::strchr(v, 'r') != nullptr;
@@ -94,8 +95,10 @@ Engine::~Engine() {
     (void)hipDeviceSynchronize();
     if (dec_times_) {
         dec_times_collect();
-        std::fprintf(stderr, "{\"jpeg_dec_kernel_ms\": {\"memset\": %.4f, \"long\": %.4f, \"short\": %.4f, \"idct\": %.4f, \"colour\": %.4f, \"calls\": %lld}}\n", dec_ms_[0], dec_ms_[1],
-                     dec_ms_[2], dec_ms_[3], dec_ms_[4], (long long)dec_calls_);
+        std::fprintf(stderr,
+                     "{\"jpeg_dec_kernel_ms\": {\"memset\": %.4f, \"long\": %.4f, \"spec\": %.4f, \"chain\": %.4f, \"write\": %.4f, \"short\": %.4f, \"idct\": %.4f, "
+                     "\"colour\": %.4f, \"calls\": %lld}}\n",
+                     dec_ms_[0], dec_ms_[1], dec_ms_[2], dec_ms_[3], dec_ms_[4], dec_ms_[5], dec_ms_[6], dec_ms_[7], (long long)dec_calls_);
         for (hipEvent_t ev : dec_marks_) if (ev) (void)hipEventDestroy(ev);
     }
     if (stamps_dev_ && std::getenv("IRE_STAMPS_RAW")) {     // diagnostic builds with their own stamp layout (conv_pk.hip PK_TICKS): the whole buffer, one value per line
@@ -150,7 +153,6 @@ Engine::~Engine() {
     for (auto& ev : ev_) if (ev) (void)hipEventDestroy(ev);
     if (fork_ev_) (void)hipEventDestroy(fork_ev_);
     if (busy_ev_) (void)hipEventDestroy(busy_ev_);
-    for (hipEvent_t ev : dec_up_ev_) if (ev) (void)hipEventDestroy(ev);
     for (auto& r : prof_) { if (r.own_e0) (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
     for (auto ev : ev_pool_) (void)hipEventDestroy(ev);
     if (main_stream_) (void)hipStreamDestroy(main_stream_);
@@ -441,37 +443,79 @@ void Engine::decode_jpeg_device(const uint8_t* const* files, const size_t* bytes
     }
     const JpegDecLayout L0 = jpeg_dec_layout(hd.data(), bytes, n);
     if (L0.total >= ((size_t)1 << 32)) fail(IRE_ERR_INVALID_INPUT, "invalid: the batch's JPEG files exceed 4 GB");
-    // two pinned blobs in turn: this one was last uploaded by the call before last, and that upload must have left it
-    const int turn = dec_turn_;
-    dec_turn_ ^= 1;
-    Buf<PinnedMem>& pin = dec_pin_[turn];
-    if (dec_up_recorded_[turn]) IRE_HIP(hipEventSynchronize(dec_up_ev_[turn]));
-    pin.grow(L0.total, L0.total + L0.total / 2);
+    DecScratch& S = dec_;
+    Buf<PinnedMem>& pin = S.next_pin(L0.total);
+    const int turn = S.turn ^ 1;
     JpegDecLayout L;
-    jpeg_dec_pack(files, bytes, hd.data(), n, L0, pin.get<uint8_t>(), L);
-    const size_t coef = jpeg_dec_coef_bytes(n, h, w), planes = jpeg_dec_plane_bytes(n, h, w);
-    if (L.total > d_dec_in_.bytes() || coef > d_dec_coef_.bytes() || planes > d_dec_planes_.bytes()) IRE_HIP(hipDeviceSynchronize());
-    d_dec_in_.grow(L.total, L.total + L.total / 2);
-    d_dec_coef_.grow(coef, batch_room(coef, jpeg_dec_coef_bytes(max_batch_, h, w)));
-    d_dec_planes_.grow(planes, batch_room(planes, jpeg_dec_plane_bytes(max_batch_, h, w)));
-    IRE_HIP(hipMemcpyAsync(d_dec_in_.get<uint8_t>(), pin.get<uint8_t>(), L.total, hipMemcpyHostToDevice, s));
-    if (!dec_up_ev_[turn]) IRE_HIP(hipEventCreateWithFlags(&dec_up_ev_[turn], hipEventDisableTiming));
-    IRE_HIP(hipEventRecord(dec_up_ev_[turn], s));
-    dec_up_recorded_[turn] = true;
+    jpeg_dec_pack(files, bytes, hd.data(), n, L0, pin.get<uint8_t>(), L, dec_min_windows_);
+    const size_t lanes = jpeg_dec_lane_bytes(L.nwin);
+    S.grow(L.total, jpeg_dec_coef_bytes(n, h, w), jpeg_dec_coef_bytes(max_batch_, h, w), jpeg_dec_plane_bytes(n, h, w), jpeg_dec_plane_bytes(max_batch_, h, w), lanes, nullptr);
+    IRE_HIP(hipMemcpyAsync(S.d_in.get<uint8_t>(), pin.get<uint8_t>(), L.total, hipMemcpyHostToDevice, s));
+    S.uploaded(turn, s);
     if (dec_times_) {
         dec_times_collect();
         for (hipEvent_t& ev : dec_marks_) if (!ev) IRE_HIP(hipEventCreate(&ev));
     }
-    jpeg_dec_launch(d_dec_in_.get<uint8_t>(), L, n, h, w, d_dec_coef_.get<uint8_t>(), d_dec_planes_.get<uint8_t>(), d_rgb, image_pitch, d_status, s,
+    jpeg_dec_launch(S.d_in.get<uint8_t>(), L, n, h, w, S.d_coef.get<uint8_t>(), S.d_planes.get<uint8_t>(), lanes ? S.d_lanes.get<uint8_t>() : nullptr, d_rgb, image_pitch, d_status, s,
                     dec_times_ ? dec_marks_ : nullptr);
     dec_marks_pending_ = dec_times_;
+}
+
+// two pinned blobs in turn: the one handed out was last uploaded by the call before last, and that upload must have left it
+Buf<PinnedMem>& Engine::DecScratch::next_pin(size_t bytes) {
+    const int t = turn;
+    turn ^= 1;
+    if (up_recorded[t]) IRE_HIP(hipEventSynchronize(up_ev[t]));
+    pin[t].grow(bytes, bytes + bytes / 2);
+    return pin[t];
+}
+
+void Engine::DecScratch::uploaded(int which, hipStream_t s) {
+    if (!up_ev[which]) IRE_HIP(hipEventCreateWithFlags(&up_ev[which], hipEventDisableTiming));
+    IRE_HIP(hipEventRecord(up_ev[which], s));
+    up_recorded[which] = true;
+}
+
+// before a buffer goes, nothing enqueued may still use it: the whole device, or (only != null) the one stream that ever uses this scratch
+void Engine::DecScratch::grow(size_t blob, size_t coef, size_t coef_full, size_t planes, size_t planes_full, size_t lanes, hipStream_t only) {
+    if (blob > d_in.bytes() || coef > d_coef.bytes() || planes > d_planes.bytes() || lanes > d_lanes.bytes()) IRE_HIP(only ? hipStreamSynchronize(only) : hipDeviceSynchronize());
+    d_in.grow(blob, blob + blob / 2);
+    d_coef.grow(coef, batch_room(coef, coef_full));
+    d_planes.grow(planes, batch_room(planes, planes_full));
+    if (lanes) d_lanes.grow(lanes, lanes + lanes / 2);
+}
+
+void Engine::decode_jpeg_streams(const jpegparse::Header* const* hd, const jpegdec::DecStream* const* streams, const uint8_t* const* bytes, const size_t* used, int n, int h,
+                                 int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s) {
+    if (!hd || !streams || !bytes || !used || !d_rgb || !d_status || n < 1 || n > max_batch_) fail(IRE_ERR_INTERNAL, "internal: arguments of the batcher's JPEG decode");
+    std::vector<uint32_t> ns((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (hd[i]->im.h != h || hd[i]->im.w != w) fail(IRE_ERR_INTERNAL, "internal: a file job in a slot of another size");
+        ns[(size_t)i] = hd[i]->nstreams;
+    }
+    const JpegDecLayout L0 = jpeg_dec_layout_rooms(ns.data(), used, n);
+    if (L0.total >= ((size_t)1 << 32)) fail(IRE_ERR_INVALID_INPUT, "invalid: the batch's JPEG files exceed 4 GB");
+    DecScratch& S = dec_batch_;
+    Buf<PinnedMem>& pin = S.next_pin(L0.bytes);
+    const int turn = S.turn ^ 1;
+    JpegDecLayout L;
+    std::vector<size_t> off((size_t)n);
+    jpeg_dec_pack_streams(hd, streams, used, n, L0, pin.get<uint8_t>(), L, off.data(), dec_min_windows_);
+    const size_t lanes = jpeg_dec_lane_bytes(L.nwin);
+    S.grow(L.total, jpeg_dec_coef_bytes(n, h, w), jpeg_dec_coef_bytes(max_batch_, h, w), jpeg_dec_plane_bytes(n, h, w), jpeg_dec_plane_bytes(max_batch_, h, w), lanes, s);
+    IRE_HIP(hipMemcpyAsync(S.d_in.get<uint8_t>(), pin.get<uint8_t>(), L.bytes, hipMemcpyHostToDevice, s));
+    S.uploaded(turn, s);
+    // the streams go from where their submitters cut them (the slot's pinned input) straight to the blob on the device
+    for (int i = 0; i < n; ++i)
+        if (used[i]) IRE_HIP(hipMemcpyAsync(S.d_in.get<uint8_t>() + L.bytes + off[(size_t)i], bytes[i], used[i], hipMemcpyHostToDevice, s));
+    jpeg_dec_launch(S.d_in.get<uint8_t>(), L, n, h, w, S.d_coef.get<uint8_t>(), S.d_planes.get<uint8_t>(), lanes ? S.d_lanes.get<uint8_t>() : nullptr, d_rgb, image_pitch, d_status, s);
 }
 
 void Engine::dec_times_collect() {
     if (!dec_marks_pending_) return;
     dec_marks_pending_ = false;
-    if (hipEventSynchronize(dec_marks_[5]) != hipSuccess) return;
-    for (int k = 0; k < 5; ++k) { float ms = 0.f; if (hipEventElapsedTime(&ms, dec_marks_[k], dec_marks_[k + 1]) == hipSuccess) dec_ms_[k] += ms; }
+    if (hipEventSynchronize(dec_marks_[kJpegDecMarks - 1]) != hipSuccess) return;
+    for (int k = 0; k < kJpegDecMarks - 1; ++k) { float ms = 0.f; if (hipEventElapsedTime(&ms, dec_marks_[k], dec_marks_[k + 1]) == hipSuccess) dec_ms_[k] += ms; }
     ++dec_calls_;
 }
 

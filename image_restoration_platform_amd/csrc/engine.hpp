@@ -18,6 +18,7 @@
 #include "conv_mfma.hpp"
 #include "conv_plan.hpp"
 #include "device_buf.hpp"
+#include "jpeg_dec.hpp"
 
 namespace ire {
 
@@ -187,6 +188,11 @@ public:
     void decode_jpeg_device(const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status,
                             hipStream_t s);
     void decode_jpeg_host(const uint8_t* file, size_t bytes, uint8_t* out_rgb, int h, int w);
+    // The batcher's file jobs: n files of one planned size whose heads were parsed and whose scans were cut by their submitters
+    // (streams[i]: hd[i]->nstreams records with offsets inside bytes[i], pinned, used[i] bytes) -> the same as decode_jpeg_device.
+    // Works on a scratch of its own and takes no lock: ONE thread calls it (the batcher's launcher), always on the same stream.
+    void decode_jpeg_streams(const jpegparse::Header* const* hd, const jpegdec::DecStream* const* streams, const uint8_t* const* bytes, const size_t* used, int n, int h,
+                             int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s);
     // Any-size jobs (h, w in 1..8192): edge-replicate pad to (max(16, ceil8 h), max(16, ceil8 w)) into the engine's padded
     // staging, the network on the padded shape, the top-left h x w window as the result.  The classifier always sees the
     // ORIGINAL pixels.  A shape restore_device takes as it is skips the pad and runs exactly as restore_device does.
@@ -301,16 +307,33 @@ private:
     Buf<DeviceMem> d_enc_io_;             // host entry: pixels in | characters out
     // the JPEG decoder: the batch's upload (records, tables, stream table, stream bytes) pinned and on the device, the coefficient
     // scratch behind the status words, the sample planes, the host entry's pixels + status
-    Buf<PinnedMem> dec_pin_[2];           // two, used in turn: call k + 1 is parsed and staged while call k's upload may still run
-    Buf<DeviceMem> d_dec_in_, d_dec_coef_, d_dec_planes_, d_dec_out_;
-    hipEvent_t dec_up_ev_[2] = {};        // the last upload out of dec_pin_[i]
-    bool dec_up_recorded_[2] = {};
-    int dec_turn_ = 0;
+    // Two users that never share a buffer: dec_ serves the engine's own entries (under the engine's lock, on the caller's stream),
+    // dec_batch_ the batcher's file jobs (launcher thread, copy-in stream).
+    struct DecScratch {
+        Buf<PinnedMem> pin[2];            // two, used in turn: call k + 1 is parsed and staged while call k's upload may still run
+        Buf<DeviceMem> d_in, d_coef, d_planes;
+        Buf<DeviceMem> d_lanes;           // the lane records and window heads of the streams decoded window-parallel
+        hipEvent_t up_ev[2] = {};         // the last upload out of pin[i]
+        bool up_recorded[2] = {};
+        int turn = 0;
+        DecScratch() = default;
+        DecScratch(const DecScratch&) = delete;
+        DecScratch& operator=(const DecScratch&) = delete;
+        ~DecScratch() { for (hipEvent_t ev : up_ev) if (ev) (void)hipEventDestroy(ev); }
+        Buf<PinnedMem>& next_pin(size_t bytes);       // the blob this call fills, free of its last upload and `bytes` large at least
+        void uploaded(int which, hipStream_t s);
+        void grow(size_t blob, size_t coef, size_t coef_full, size_t planes, size_t planes_full, size_t lanes, hipStream_t only);
+    };
+    DecScratch dec_, dec_batch_;
+    Buf<DeviceMem> d_dec_out_;
+    // IRE_JPEG_DEC_WINDOWS (read once): a long stream of at least so many windows is decoded window-parallel; 0: none, the
+    // one-workgroup kernel walks them all (for measurement).  Default, and the least that counts: 2.
+    uint32_t dec_min_windows_ = 2;
     // IRE_JPEG_DEC_TIMES=1 (read once; tools/jpeg_decode_measure.py): events between the decoder's launches, their times summed over
     // the calls and printed to stderr as one JSON line when the engine closes.  Collecting waits for the previous call's kernels.
     bool dec_times_ = false, dec_marks_pending_ = false;
-    hipEvent_t dec_marks_[6] = {};
-    double dec_ms_[5] = {};
+    hipEvent_t dec_marks_[kJpegDecMarks] = {};
+    double dec_ms_[kJpegDecMarks - 1] = {};
     int64_t dec_calls_ = 0;
     void dec_times_collect();
 

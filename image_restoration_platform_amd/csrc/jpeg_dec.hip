@@ -7,7 +7,13 @@
 //   K1 jpeg_dec_long_kernel   one workgroup per stream longer than kShortMaxBytes: the self-synchronising lane algorithm of
 //                             jpeg_dec_core.hpp, window by window (kLanes x kSubseqBits bits, staged into LDS as big-endian words,
 //                             one pad word per 32 so that lane i starts on bank i); the first lane of a window starts from the exact
-//                             end state of the window before.  No workgroup waits for another.
+//                             end state of the window before.  No workgroup waits for another.  It keeps the long streams of ONE window.
+//   spec / chain / write      a long stream of two or more windows (the host lists them and their windows in the blob): every window
+//                             a workgroup.  jpeg_dec_spec_kernel settles each window from a guessed entry state and records its lanes;
+//                             jpeg_dec_chain_kernel, one workgroup per stream, carries the true state through its windows, decoding
+//                             again only the lanes up to the one whose recorded start it meets, and sums the windows' block counts and
+//                             DC sums; jpeg_dec_write_kernel writes every window's coefficients.  The three launches are the only
+//                             ordering between workgroups (jpeg_dec_core.hpp says why the result does not depend on the guess)
 //   K2 jpeg_dec_short_kernel  one LANE per short stream in a strided loop (our own encoder's 16-MCU intervals are ~80 bytes): the
 //                             same loop, start to end, straight from the stream's bytes
 //   K3 jpeg_dec_idct_kernel   dequantise + libjpeg's "islow" inverse DCT (jidctint.c) + range limit: 32 blocks per workgroup,
@@ -24,6 +30,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 namespace ire {
 
@@ -42,6 +49,12 @@ struct DecBatch {
     int* stat;                     // one word per image
     short* coef;                   // per image coef_stride int16
     unsigned long long coef_stride;
+    // the multi-window streams (window_count >= min_windows > 0), decoded by the spec / chain / write kernels and skipped by K1
+    const DecWindow* windows;
+    const DecChain* chains;
+    LaneRec* recs;                 // kLanes per window
+    WinHead* heads;                // one per window
+    unsigned min_windows;          // 0: K1 decodes every long stream
 };
 
 __device__ __forceinline__ void load_image(const DecBatch& b, unsigned img, DecImage* s_im, DecTable* s_tabs, unsigned t) {
@@ -67,6 +80,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_dec_long_kernel(DecBatch b) {
     load_image(b, img, &s_im, s_tabs, t);
     if (blockIdx.x >= s_im.nlong) return;
     const DecStream sr = b.streams[s_im.first_long + blockIdx.x];
+    if (b.min_windows && window_count(sr.len) >= b.min_windows) return;          // the window-parallel kernels' stream
     const unsigned char* bytes = b.bytes + sr.off;
     short* coef = b.coef + (unsigned long long)img * b.coef_stride;
     const unsigned total_bits = 8u * sr.len, total_blocks = sr.nmcu * s_im.bpm, gblk0 = sr.mcu0 * s_im.bpm;
@@ -142,6 +156,151 @@ __global__ __launch_bounds__(kThreads) void jpeg_dec_long_kernel(DecBatch b) {
         unsigned err = s_err;
         if (!err && !stream_end_ok(s_final, sr.len)) err = kStBadEnd;
         if (err) atomicOr(&b.stat[img], (int)err);
+    }
+}
+
+// ---- long streams of several windows: three launches, every window a workgroup (jpeg_dec_core.hpp says why this is exact) ----------
+
+// inclusive scans over the workgroup of four values per thread -> what lies before this thread (before) and the totals (all)
+__device__ __forceinline__ void block_scan4(const unsigned (&in)[4], unsigned (*s_scan)[kWaves], unsigned (&before)[4], unsigned (&all)[4]) {
+    const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    unsigned v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        v[q] = in[q];
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const unsigned o = __shfl_up(v[q], off, 64); if ((int)lane >= off) v[q] += o; }
+        if (lane == 63) s_scan[q][wv] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        before[q] = v[q] - in[q]; all[q] = 0;
+#pragma unroll
+        for (unsigned k = 0; k < (unsigned)kWaves; ++k) { const unsigned x = s_scan[q][k]; if (k < wv) before[q] += x; all[q] += x; }
+    }
+}
+
+// A.  blockIdx.x: the window.  K1's rounds on one window whose lane 0 starts from a guess; the settled lanes to the window's records.
+__global__ __launch_bounds__(kThreads) void jpeg_dec_spec_kernel(DecBatch b) {
+    __shared__ unsigned s_words[kStagePadded];
+    __shared__ DecTable s_tabs[8];
+    __shared__ DecImage s_im;
+    __shared__ unsigned s_endp[2][kLanes], s_endbk[2][kLanes];
+    const unsigned t = threadIdx.x;
+    const DecWindow wn = b.windows[blockIdx.x];
+    load_image(b, wn.image, &s_im, s_tabs, t);
+    const DecStream sr = b.streams[wn.stream];
+    const unsigned char* bytes = b.bytes + sr.off;
+    const unsigned total_bits = 8u * sr.len, win0 = wn.win0;
+    for (unsigned k = t; k < kStageWords; k += kThreads) s_words[k + (k >> 5)] = stream_word(bytes, sr.len, win0 / 32 + k);
+    __syncthreads();
+    const WordReader rd{s_words, win0};
+    const unsigned nl = window_lanes(total_bits, win0), lim = lane_lim(total_bits, win0, t);
+    const bool active = t < nl;
+    DecState start = spec_start(win0, t);
+    DecState end = start;
+    LaneOut lo{0, {0, 0, 0}};
+    if (active) dec_subseq(rd, s_tabs, s_im, end, lim, 0xffffffffu, (short*)nullptr, 0, nullptr, lo);
+    s_endp[0][t] = end.p; s_endbk[0][t] = state_bk(end);
+    unsigned cur = 0;
+    __syncthreads();
+    for (int round = 1; round <= kLanes; ++round) {                 // bounded by the lane count, as in K1
+        int changed = 0;
+        if (active && t > 0) {
+            const unsigned pp = s_endp[cur][t - 1], pbk = s_endbk[cur][t - 1];
+            if (pp != start.p || pbk != state_bk(start)) {
+                start = state_of(pp, pbk);
+                end = start;
+                dec_subseq(rd, s_tabs, s_im, end, lim, 0xffffffffu, (short*)nullptr, 0, nullptr, lo);
+                changed = 1;
+            }
+        }
+        cur ^= 1u;
+        s_endp[cur][t] = end.p; s_endbk[cur][t] = state_bk(end);
+        if (!__syncthreads_or(changed)) break;
+    }
+    if (active) b.recs[(unsigned long long)blockIdx.x * kLanes + t] = LaneRec{start.p, state_bk(start), end.p, state_bk(end), lo};
+}
+
+// B.  blockIdx.x: the multi-window stream.  Thread 0 carries the true state through the stream's windows (chain_lane, one lane's bits
+// staged into LDS by the workgroup); the workgroup sums each window's settled counts into the head of the next one.
+__global__ __launch_bounds__(kThreads) void jpeg_dec_chain_kernel(DecBatch b) {
+    __shared__ unsigned s_words[kChainStagePadded];
+    __shared__ DecTable s_tabs[8];
+    __shared__ DecImage s_im;
+    __shared__ unsigned s_scan[4][kWaves];
+    __shared__ unsigned s_go, s_bit0;
+    const unsigned t = threadIdx.x;
+    const DecChain ch = b.chains[blockIdx.x];
+    load_image(b, ch.image, &s_im, s_tabs, t);
+    const DecStream sr = b.streams[ch.stream];
+    const unsigned char* bytes = b.bytes + sr.off;
+    const unsigned total_bits = 8u * sr.len, total_blocks = sr.nmcu * s_im.bpm;
+    DecState carry{0, 0, 0};                                        // thread 0's: the true state in front of the next lane
+    unsigned done = 0, dcc[3] = {0, 0, 0};
+    for (unsigned wi = 0; wi < ch.nwin; ++wi) {                      // nwin = window_count(sr.len): the host built both from the same length
+        const unsigned win0 = wi * kWindowBits, nl = window_lanes(total_bits, win0);
+        LaneRec* recs = b.recs + (unsigned long long)(ch.first + wi) * kLanes;
+        if (t == 0) b.heads[ch.first + wi] = WinHead{done, {dcc[0], dcc[1], dcc[2]}};
+        for (unsigned l = 0; l < nl; ++l) {                         // until a lane's recorded start is the true one; all of them at the worst
+            if (t == 0) {
+                const bool same = recs[l].sp == carry.p && recs[l].sbk == state_bk(carry);
+                // (carry.p is never in front of lane l's first bit, where the staged words begin: the soft loop of the lane before
+                // ended at or behind its own last bit)
+                s_bit0 = win0 + l * kSubseqBits;
+                s_go = !same && carry.p >= s_bit0;
+                if (carry.p < s_bit0) atomicOr(&b.stat[ch.image], kStBadCode);          // never: flagged, not guessed
+            }
+            __syncthreads();
+            if (!s_go) break;
+            if (t < kChainStageWords) s_words[t + (t >> 5)] = stream_word(bytes, sr.len, s_bit0 / 32 + t);
+            __syncthreads();
+            if (t == 0) chain_lane(WordReader{s_words, s_bit0}, s_tabs, s_im, lane_lim(total_bits, win0, l), recs[l], carry);
+            __syncthreads();                                        // s_go, s_words and recs[l] are read no more / written
+        }
+        __syncthreads();                                            // thread 0's records are written
+        unsigned v[4] = {0, 0, 0, 0}, before[4], all[4];
+        if (t < nl) { const LaneOut o = recs[t].o; v[0] = o.nblk; v[1] = o.dc[0]; v[2] = o.dc[1]; v[3] = o.dc[2]; }
+        block_scan4(v, s_scan, before, all);
+        done += all[0]; dcc[0] += all[1]; dcc[1] += all[2]; dcc[2] += all[3];
+        if (t == 0) carry = state_of(recs[nl - 1].ep, recs[nl - 1].ebk);
+        __syncthreads();                                            // s_scan is read no more
+    }
+    if (t == 0 && done < total_blocks) atomicOr(&b.stat[ch.image], kStBadEnd);      // blocks missing
+}
+
+// C.  blockIdx.x: the window.  K1's writing pass from every lane's settled start.
+__global__ __launch_bounds__(kThreads) void jpeg_dec_write_kernel(DecBatch b) {
+    __shared__ unsigned s_words[kStagePadded];
+    __shared__ DecTable s_tabs[8];
+    __shared__ DecImage s_im;
+    __shared__ unsigned s_scan[4][kWaves];
+    const unsigned t = threadIdx.x;
+    const DecWindow wn = b.windows[blockIdx.x];
+    load_image(b, wn.image, &s_im, s_tabs, t);
+    const DecStream sr = b.streams[wn.stream];
+    const unsigned char* bytes = b.bytes + sr.off;
+    short* coef = b.coef + (unsigned long long)wn.image * b.coef_stride;
+    const unsigned total_bits = 8u * sr.len, total_blocks = sr.nmcu * s_im.bpm, gblk0 = sr.mcu0 * s_im.bpm, win0 = wn.win0;
+    for (unsigned k = t; k < kStageWords; k += kThreads) s_words[k + (k >> 5)] = stream_word(bytes, sr.len, win0 / 32 + k);
+    const unsigned nl = window_lanes(total_bits, win0), lim = lane_lim(total_bits, win0, t);
+    const bool active = t < nl;
+    LaneRec r{0, 0, 0, 0, {0, {0, 0, 0}}};
+    if (active) r = b.recs[(unsigned long long)blockIdx.x * kLanes + t];
+    const WinHead hd = b.heads[blockIdx.x];
+    const unsigned v[4] = {r.o.nblk, r.o.dc[0], r.o.dc[1], r.o.dc[2]};
+    unsigned before[4], all[4];
+    block_scan4(v, s_scan, before, all);                            // (its barrier also ends the staging)
+    const WordReader rd{s_words, win0};
+    const unsigned first = hd.done + before[0], room = total_blocks > first ? total_blocks - first : 0;
+    unsigned dcpred[4] = {hd.dc[0] + before[1], hd.dc[1] + before[2], hd.dc[2] + before[3], 0};
+    if (active) {
+        DecState st = state_of(r.sp, r.sbk);
+        LaneOut w;
+        unsigned err = dec_subseq(rd, s_tabs, s_im, st, lim, room, coef, gblk0 + first, dcpred, w);
+        if (!err && w.nblk && first + w.nblk == total_blocks && !stream_end_ok(st.p, sr.len)) err = kStBadEnd;     // bytes left over
+        if (err) atomicOr(&b.stat[wn.image], (int)err);
     }
 }
 
@@ -291,48 +450,101 @@ size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 size_t jpeg_dec_blocks(int h, int w) { return (size_t)3 * (2 * (((size_t)w + 15) / 16)) * (2 * (((size_t)h + 15) / 16)); }
 size_t jpeg_dec_coef_bytes(int n, int h, int w) { return up256(4 * (size_t)n) + (size_t)n * jpeg_dec_blocks(h, w) * 128; }
 size_t jpeg_dec_plane_bytes(int n, int h, int w) { return (size_t)n * jpeg_dec_blocks(h, w) * 64; }
+size_t jpeg_dec_lane_bytes(size_t nwin) { return nwin * (sizeof(LaneRec) * kLanes + sizeof(WinHead)); }
 
-JpegDecLayout jpeg_dec_layout(const jpegparse::Header* hd, const size_t* bytes, int n) {
+// rooms[i]: the bytes image i's streams take at most in the blob's byte area
+JpegDecLayout jpeg_dec_layout_rooms(const uint32_t* nstreams, const size_t* rooms, int n) {
     JpegDecLayout L;
     L.images = 0;
     L.tabs = up256(sizeof(DecImage) * (size_t)n);
     L.streams = up256(L.tabs + sizeof(DecTable) * 8 * (size_t)n);
     size_t ns = 0;
-    for (int i = 0; i < n; ++i) ns += hd[i].nstreams;
-    L.bytes = up256(L.streams + sizeof(DecStream) * ns);
+    for (int i = 0; i < n; ++i) ns += nstreams[i];
+    // multi-window streams are longer than a window, so a file has at most 8 * stream bytes / kWindowBits of them and twice as many windows
+    size_t nc = 0;
+    for (int i = 0; i < n; ++i) nc += 8 * rooms[i] / kWindowBits;
+    L.chains = up256(L.streams + sizeof(DecStream) * ns);
+    L.windows = up256(L.chains + sizeof(DecChain) * nc);
+    L.bytes = up256(L.windows + sizeof(DecWindow) * 2 * nc);
     L.total = L.bytes;
-    for (int i = 0; i < n; ++i) L.total += up256(jpegparse::scan_room(hd[i], bytes[i]));
+    for (int i = 0; i < n; ++i) L.total += up256(rooms[i]);
     L.total += 256;                                               // (what an aligned dword load behind the last stream may touch)
     return L;
 }
 
-// the batch's blob into `blob` (pinned): records, tables, the streams cut and unstuffed.  A file whose scan is refused: Error.
-void jpeg_dec_pack(const uint8_t* const* files, const size_t* bytes, jpegparse::Header* hd, int n, const JpegDecLayout& L, uint8_t* blob, JpegDecLayout& out) {
-    out = L;
-    out.max_long = out.max_short = 0;
+JpegDecLayout jpeg_dec_layout(const jpegparse::Header* hd, const size_t* bytes, int n) {
+    std::vector<size_t> rooms((size_t)n);
+    std::vector<uint32_t> ns((size_t)n);
+    for (int i = 0; i < n; ++i) { rooms[(size_t)i] = jpegparse::scan_room(hd[i], bytes[i]); ns[(size_t)i] = hd[i].nstreams; }
+    return jpeg_dec_layout_rooms(ns.data(), rooms.data(), n);
+}
+
+namespace {
+// image i's records into the blob: its streams (cut already: `first`, offsets inside the image's own bytes, which begin b0 bytes into
+// the byte area) ordered long ones first, its image record and tables, and the chains and windows of its multi-window streams
+void pack_image(int i, const jpegparse::Header& hd, DecStream* first, uint32_t s0, size_t b0, const JpegDecLayout& L, uint8_t* blob, JpegDecLayout& out) {
     DecImage* images = reinterpret_cast<DecImage*>(blob + L.images);
     DecTable* tabs = reinterpret_cast<DecTable*>(blob + L.tabs);
+    DecChain* chains = reinterpret_cast<DecChain*>(blob + L.chains);
+    DecWindow* windows = reinterpret_cast<DecWindow*>(blob + L.windows);
+    const size_t chain_room = (L.windows - L.chains) / sizeof(DecChain), window_room = (L.bytes - L.windows) / sizeof(DecWindow);
+    const uint32_t min_windows = out.min_windows;
+    DecStream* mid = std::stable_partition(first, first + hd.nstreams, [](const DecStream& s) { return s.len > kShortMaxBytes; });
+    for (uint32_t k = 0; k < hd.nstreams; ++k) first[k].off += (uint32_t)b0;
+    DecImage im = hd.im;
+    im.first_long = s0; im.nlong = (uint32_t)(mid - first);
+    im.first_short = im.first_long + im.nlong; im.nshort = hd.nstreams - im.nlong;
+    uint32_t k1 = 0;                                              // the last of its long streams that K1 keeps, + 1
+    for (uint32_t k = 0; k < im.nlong; ++k) {
+        const uint32_t nw = window_count(first[k].len);
+        if (!min_windows || nw < std::max(min_windows, 2u)) { k1 = k + 1; continue; }
+        if (out.nchain + 1 > chain_room || out.nwin + (size_t)nw > window_room) fail(IRE_ERR_INTERNAL, "internal: the JPEG decoder's window table overflows");
+        chains[out.nchain++] = DecChain{im.first_long + k, (uint32_t)i, out.nwin, nw};
+        for (uint32_t j = 0; j < nw; ++j) windows[out.nwin++] = DecWindow{im.first_long + k, (uint32_t)i, j * kWindowBits};
+    }
+    out.max_long = std::max(out.max_long, k1); out.max_short = std::max(out.max_short, im.nshort);
+    images[i] = im;
+    std::memcpy(tabs + 8 * (size_t)i, hd.tabs, sizeof(DecTable) * 8);
+}
+}  // namespace
+
+// the batch's blob into `blob` (pinned): records, tables, the streams cut and unstuffed.  A file whose scan is refused: Error.
+void jpeg_dec_pack(const uint8_t* const* files, const size_t* bytes, jpegparse::Header* hd, int n, const JpegDecLayout& L, uint8_t* blob, JpegDecLayout& out,
+                   uint32_t min_windows) {
+    out = L;
+    out.max_long = out.max_short = out.nwin = out.nchain = 0;
+    out.min_windows = min_windows;
     DecStream* streams = reinterpret_cast<DecStream*>(blob + L.streams);
     size_t s0 = 0, b0 = 0;
     for (int i = 0; i < n; ++i) {
         const size_t room = jpegparse::scan_room(hd[i], bytes[i]);
         std::string why;
         if (!jpegparse::split_scan(hd[i], files[i], bytes[i], blob + L.bytes + b0, room, streams + s0, why)) fail(IRE_ERR_INVALID_INPUT, why);
-        DecStream* first = streams + s0;
-        DecStream* mid = std::stable_partition(first, first + hd[i].nstreams, [](const DecStream& s) { return s.len > kShortMaxBytes; });
-        for (uint32_t k = 0; k < hd[i].nstreams; ++k) first[k].off += (uint32_t)b0;
-        DecImage& im = hd[i].im;
-        im.first_long = (uint32_t)s0; im.nlong = (uint32_t)(mid - first);
-        im.first_short = im.first_long + im.nlong; im.nshort = hd[i].nstreams - im.nlong;
-        out.max_long = std::max(out.max_long, im.nlong); out.max_short = std::max(out.max_short, im.nshort);
-        images[i] = im;
-        std::memcpy(tabs + 8 * (size_t)i, hd[i].tabs, sizeof(DecTable) * 8);
+        pack_image(i, hd[i], streams + s0, (uint32_t)s0, b0, L, blob, out);
+        hd[i].im = reinterpret_cast<DecImage*>(blob + L.images)[i];
         s0 += hd[i].nstreams; b0 += up256(room);
     }
 }
 
-void jpeg_dec_launch(const uint8_t* d_blob, const JpegDecLayout& L, int n, int h, int w, uint8_t* d_coef, uint8_t* d_planes, uint8_t* d_rgb, size_t image_pitch,
-                     int32_t* d_status, hipStream_t s, hipEvent_t* marks) {
+// the same for files whose scans were cut before (jpegparse::split_scan into the caller's own memory): only the records, up to
+// L.bytes; byte_off[i] says where image i's bytes belong in the byte area (the caller copies them there, rooms[i] at most)
+void jpeg_dec_pack_streams(const jpegparse::Header* const* hd, const DecStream* const* streams_in, const size_t* rooms, int n, const JpegDecLayout& L, uint8_t* blob,
+                           JpegDecLayout& out, size_t* byte_off, uint32_t min_windows) {
+    out = L;
+    out.max_long = out.max_short = out.nwin = out.nchain = 0;
+    out.min_windows = min_windows;
+    DecStream* streams = reinterpret_cast<DecStream*>(blob + L.streams);
+    size_t s0 = 0, b0 = 0;
+    for (int i = 0; i < n; ++i) {
+        std::copy(streams_in[i], streams_in[i] + hd[i]->nstreams, streams + s0);
+        pack_image(i, *hd[i], streams + s0, (uint32_t)s0, b0, L, blob, out);
+        byte_off[i] = b0;
+        s0 += hd[i]->nstreams; b0 += up256(rooms[i]);
+    }
+}
+
+void jpeg_dec_launch(const uint8_t* d_blob, const JpegDecLayout& L, int n, int h, int w, uint8_t* d_coef, uint8_t* d_planes, uint8_t* d_lanes, uint8_t* d_rgb,
+                     size_t image_pitch, int32_t* d_status, hipStream_t s, hipEvent_t* marks) {
     auto mark = [&](int k) { if (marks) IRE_HIP(hipEventRecord(marks[k], s)); };
     DecBatch b;
     b.images = reinterpret_cast<const DecImage*>(d_blob + L.images);
@@ -343,18 +555,32 @@ void jpeg_dec_launch(const uint8_t* d_blob, const JpegDecLayout& L, int n, int h
     b.coef = reinterpret_cast<short*>(d_coef + up256(4 * (size_t)n));
     const size_t blocks = jpeg_dec_blocks(h, w);
     b.coef_stride = blocks * 64;
+    b.chains = reinterpret_cast<const DecChain*>(d_blob + L.chains);
+    b.windows = reinterpret_cast<const DecWindow*>(d_blob + L.windows);
+    b.recs = reinterpret_cast<LaneRec*>(d_lanes);
+    b.heads = reinterpret_cast<WinHead*>(d_lanes + sizeof(LaneRec) * kLanes * (size_t)L.nwin);
+    b.min_windows = L.nwin ? std::max(L.min_windows, 2u) : 0;
+    if (L.nwin && !d_lanes) fail(IRE_ERR_INTERNAL, "internal: the JPEG decoder's lane records are missing");
     mark(0);
     IRE_HIP(hipMemsetAsync(d_coef, 0, jpeg_dec_coef_bytes(n, h, w), s));
     mark(1);
     if (L.max_long) hipLaunchKernelGGL(jpeg_dec_long_kernel, dim3(L.max_long, n), dim3(kThreads), 0, s, b);
     mark(2);
+    if (L.nwin) {
+        hipLaunchKernelGGL(jpeg_dec_spec_kernel, dim3(L.nwin), dim3(kThreads), 0, s, b);
+        mark(3);
+        hipLaunchKernelGGL(jpeg_dec_chain_kernel, dim3(L.nchain), dim3(kThreads), 0, s, b);
+        mark(4);
+        hipLaunchKernelGGL(jpeg_dec_write_kernel, dim3(L.nwin), dim3(kThreads), 0, s, b);
+    } else { mark(3); mark(4); }
+    mark(5);
     if (L.max_short) hipLaunchKernelGGL(jpeg_dec_short_kernel, dim3(std::min<uint32_t>((L.max_short + kThreads - 1) / kThreads, 1024u), n), dim3(kThreads), 0, s, b);
-    mark(3);
+    mark(6);
     hipLaunchKernelGGL(jpeg_dec_idct_kernel, dim3((unsigned)((blocks + kIdctBlocks - 1) / kIdctBlocks), n), dim3(kThreads), 0, s, b, d_planes, (unsigned long long)(blocks * 64));
-    mark(4);
+    mark(7);
     hipLaunchKernelGGL(jpeg_dec_colour_kernel, dim3((unsigned)(((size_t)h * w + kThreads - 1) / kThreads), n), dim3(kThreads), 0, s, b, d_planes, (unsigned long long)(blocks * 64),
                        d_rgb, (unsigned long long)image_pitch, h, w, d_status);
-    mark(5);
+    mark(8);
     IRE_HIP(hipGetLastError());
 }
 

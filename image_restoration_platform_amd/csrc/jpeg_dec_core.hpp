@@ -207,5 +207,51 @@ IRE_HD uint32_t dec_subseq(const R& rd, const DecTable* tabs, const DecImage& im
 // what must hold when a stream's last block is done at bit p: its last byte has begun (the rest of it is padding)
 IRE_HD bool stream_end_ok(uint32_t p, uint32_t len) { return p != kBadPos && p <= 8u * len && 8u * len - p < 8u; }
 
+// ---- long streams of several windows, decoded window-parallel in three passes (jpeg_dec.hip: spec / chain / write kernels) ------------
+// The only serial link between two windows of a stream is the state at which the second one is entered.  Pass A guesses it -- every
+// window's lane 0 starts like any other lane, at its own first bit in state (block 0, DC) -- and settles each window by itself, all
+// windows at once; it keeps every lane's start state, end state and counts in a LaneRec.  Pass B walks one stream's windows in order
+// with the TRUE entry state: from lane 0 on it decodes a lane again from the end of the lane before until an entry state equals the
+// start a lane was settled from -- from there on pass A's records are exact, because a lane's record is a function of its start state
+// alone.  A guess that never locks costs a window's kLanes decodes one after the other, never a wrong result.  B also gives every
+// window the block count and the DC sums in front of it (WinHead).  Pass C writes every window's coefficients, all windows at once.
+struct DecWindow { uint32_t stream, image, win0; };   // a window of a multi-window stream: its stream and image in the batch, its first bit
+struct DecChain { uint32_t stream, image, first, nwin; };      // a multi-window stream: its windows are first .. first + nwin - 1 of the window table
+struct LaneRec { uint32_t sp, sbk, ep, ebk; LaneOut o; };      // a lane's settled start and end state (bit position; block << 8 | zig-zag position), its counts
+struct WinHead { uint32_t done, dc[3]; };                      // in front of a window: completed blocks of its stream, DC sums per component
+static_assert(sizeof(LaneRec) == 32 && sizeof(WinHead) == 16 && sizeof(DecWindow) == 12 && sizeof(DecChain) == 16, "as the host lays them out");
+constexpr unsigned kChainStageWords = kSubseqBits / 32 + 2;    // what one lane's decode may read: its subsequence and the last symbol's read-ahead
+constexpr unsigned kChainStagePadded = kChainStageWords + kChainStageWords / 32 + 1;
+
+IRE_HD uint32_t state_bk(const DecState& s) { return s.blk << 8 | s.k; }
+IRE_HD DecState state_of(uint32_t p, uint32_t bk) { return DecState{p, bk >> 8, bk & 255u}; }
+// windows of a stream of `len` bytes (len < 2^28: jpeg_parse.hpp refuses larger files)
+IRE_HD uint32_t window_count(uint32_t len) { return (8u * len + kWindowBits - 1) / kWindowBits; }
+// the lanes of the window at bit win0 whose subsequence begins inside the stream, and the bit behind lane t's subsequence
+IRE_HD uint32_t window_lanes(uint32_t total_bits, uint32_t win0) {
+    const uint32_t left = (total_bits - win0 + kSubseqBits - 1) / kSubseqBits;
+    return left < (uint32_t)kLanes ? left : (uint32_t)kLanes;
+}
+IRE_HD uint32_t lane_lim(uint32_t total_bits, uint32_t win0, uint32_t t) {
+    const uint32_t e = win0 + (t + 1) * kSubseqBits;
+    return e < total_bits ? e : total_bits;
+}
+// pass A: where lane t of the window at bit win0 starts: only the stream's very first lane knows its state, every other start is a
+// guess that pass B checks (any state would do: the result does not depend on it)
+IRE_HD DecState spec_start(uint32_t win0, uint32_t t) { return DecState{win0 + t * kSubseqBits, 0, 0}; }
+// pass B, one lane: `in` is the true state in front of lane t.  true: the lane was settled from exactly that state, so its record and
+// all behind it in the window stand.  false: the lane was decoded again (soft, counting only) into its record, and `in` is its end.
+// rd must hold the bits from in.p up to `lim` and one symbol's read-ahead
+template <class R>
+IRE_HD bool chain_lane(const R& rd, const DecTable* tabs, const DecImage& im, uint32_t lim, LaneRec& r, DecState& in) {
+    if (r.sp == in.p && r.sbk == state_bk(in)) return true;
+    DecState end = in;
+    LaneOut lo;
+    dec_subseq(rd, tabs, im, end, lim, 0xffffffffu, (int16_t*)nullptr, 0, nullptr, lo);
+    r = LaneRec{in.p, state_bk(in), end.p, state_bk(end), lo};
+    in = end;
+    return false;
+}
+
 }  // namespace jpegdec
 }  // namespace ire

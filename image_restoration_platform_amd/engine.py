@@ -29,6 +29,19 @@ def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data) if a is not None else None
 
 
+def _jpeg_frame_size(data):
+    """(h, w) from the frame header of a JPEG file the engine has just accepted (ire_submit_jpeg parsed it: the segments are
+    well-formed and a baseline frame exists), without walking the file a second time: poll() sizes its buffer from them."""
+    i = 2
+    while True:
+        while data[i] == 0xFF:
+            i += 1
+        marker, n = data[i], int.from_bytes(data[i + 1:i + 3], "big")
+        if marker in (0xC0, 0xC1):
+            return int.from_bytes(data[i + 4:i + 6], "big"), int.from_bytes(data[i + 6:i + 8], "big")
+        i += 1 + n
+
+
 class Engine:
     def __init__(self, device_index=0, max_batch=8, num_streams=0, weights_path="default", seed=0, flags=0, precision="bf16"):
         self._lib = _lib.load()
@@ -190,6 +203,18 @@ class Engine:
         sc = None if scores is None else np.ascontiguousarray(np.asarray(scores, dtype=np.float64).reshape(7))
         job = ctypes.c_void_p()
         self._check(self._lib.ire_submit_fit(self._h, _ptr(rgb), h, w, int(bool(is_jpeg)), _ptr(sc), ctypes.byref(job)))
+        return (job, h, w)
+
+    def submit_jpeg(self, data, scores=None):
+        """submit_fit() for an encoded upload: the bytes of a baseline JPEG file that decode_jpeg_plan accepts.  The file is parsed in
+        this call and decoded on the device with its batch; the result is that of submit_fit(its pixels, is_jpeg=True, scores).
+        Raises EngineError (invalid input, the plan's reason) for a file out of scope: no job exists then.  A file with corrupt data
+        fails at its poll."""
+        data = bytes(data)
+        sc = None if scores is None else np.ascontiguousarray(np.asarray(scores, dtype=np.float64).reshape(7))
+        job = ctypes.c_void_p()
+        self._check(self._lib.ire_submit_jpeg(self._h, data, len(data), _ptr(sc), ctypes.byref(job)))      # the one parse of the file: refuses with the plan's reason
+        h, w = _jpeg_frame_size(data)
         return (job, h, w)
 
     def stats(self):

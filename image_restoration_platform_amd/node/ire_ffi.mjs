@@ -38,6 +38,7 @@ export function bindIre(libPath) {
     ire_encode_png_base64_fit_device: ['int', [P, P, 'int', 'int', 'int', 'size_t', 'size_t', P, 'size_t', P]],
     ire_encode_png_base64_fit: ['int', [P, P, 'int', 'int', 'int', P, 'size_t']],
     ire_submit_fit: ['int', [P, P, 'int', 'int', 'int', P, PP]],
+    ire_submit_jpeg: ['int', [P, P, 'size_t', P, PP]],
     ire_submit: ['int', [P, P, 'int', 'int', 'int', P, PP]],
     ire_poll: ['int', [P, P, 'int', P, P, P]],
     ire_poll_text: ['int', [P, P, 'int', P, 'size_t', P, P, P]],

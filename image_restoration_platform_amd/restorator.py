@@ -40,7 +40,8 @@ def _now_ms():
 #   unset        host PIL (libjpeg-turbo, libpng, ...): every format, ~5.6 ms of one core per 1024^2 JPEG -- the default
 #   jpeg-device  a baseline JPEG the engine's plan accepts (csrc/jpeg_parse.hpp) is decoded on the GPU (csrc/jpeg_dec.hip) to the
 #                very bytes PIL gives; every other file -- progressive, CMYK, PNG, WebP, one the device flags as corrupt -- goes
-#                to PIL exactly as above
+#                to PIL exactly as above.  A single upload that reaches restore_image undecoded becomes a file job of the engine's
+#                batcher (ire_submit_jpeg): decoded with its batch, eight uploads a time
 UPLOAD_DECODES = {"device": 0, "host": 0}      # which way the uploads of this process went
 
 
@@ -176,14 +177,32 @@ class EngineRestorer:
         if not images or len(images) > 3:
             raise ValueError("invalid images: expected 1..3 encoded images")  # provider limit: report.md:28
         seen = _seen_of(self.engine)
-        decoded = []
+        text_engine = bool(getattr(self.engine, "_flags", 0) & (_lib.IRE_FLAG_RESULT_PNG_BASE64 | _lib.IRE_FLAG_RESULT_PNG_DEFLATE | _lib.IRE_FLAG_RESULT_JPEG))      # poll returns the text
+        if len(images) == 1 and os.environ.get("IRE_UPLOAD_CODEC") == "jpeg-device" and bytes(images[0][:2]) == b"\xff\xd8":
+            # a single upload that analyze() has not decoded goes to the batcher as the FILE it is (ire_submit_jpeg): parsed here,
+            # decoded on the device with its batch.  A file the plan refuses (at submit) or the device flags (at poll) is "invalid
+            # input": the host codec then judges it, below, exactly as before
+            hit = seen.take(images[0])
+            if hit is None:
+                from .engine import EngineError
+                try:
+                    out, _, _ = self.engine.poll(self.engine.submit_jpeg(bytes(images[0])))
+                    UPLOAD_DECODES["device"] += 1
+                    return self._reply(out.decode("ascii") if text_engine else self._encode(out))
+                except EngineError as e:
+                    if e.status != _lib.IRE_ERR_INVALID_INPUT:
+                        raise
+                hit = (*decode_image(images[0]), None)          # (no engine: straight to the host codec, which is where the refusal sends it)
+            decoded = [hit]
+            images = []
+        else:
+            decoded = []
         for b in images:             # analyze() already decoded and classified this buffer: reuse both
             hit = seen.take(b)
             decoded.append(hit if hit is not None else (*decode_image(b, self.engine), None))
         shapes = {d[0].shape for d in decoded}
         if len(shapes) != 1:
             raise ValueError("invalid images: fusion views must have identical dimensions")
-        text_engine = bool(getattr(self.engine, "_flags", 0) & (_lib.IRE_FLAG_RESULT_PNG_BASE64 | _lib.IRE_FLAG_RESULT_PNG_DEFLATE | _lib.IRE_FLAG_RESULT_JPEG))      # poll returns the text
         if len(decoded) == 1:
             # one image of any size is ONE job of the engine's batcher (ire_submit_fit): the engine pads on the device, classifies
             # the image's own pixels in the same batch when analyze() did not, and hands back the h x w window -- on a flagged

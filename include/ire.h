@@ -260,6 +260,15 @@ int ire_submit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg, con
  * their exact (h, w), polled with ire_poll and released with ire_job_release.  With IRE_FLAG_RESULT_PNG_BASE64 ire_poll
  * delivers ire_png_base64_bytes_fit(h, w) characters: the PNG of the h x w result. */
 int ire_submit_fit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg, const double* scores, ire_job** job_out);
+/* ire_submit_fit for an ENCODED upload: `file` is a baseline JPEG file that ire_decode_jpeg_plan accepts; the job's result is that
+ * of ire_submit_fit(the file's decoded pixels, h, w, is_jpeg = 1, scores) with h, w as the plan reports them (the caller sizes its
+ * ire_poll / ire_poll_text buffer from the plan).  The file's head is parsed and its scan is cut in the calling thread, before
+ * return (the file may be freed then); the decode runs on the device with the job's batch.  File jobs are coalesced by their planned
+ * (h, w), whatever their sampling, and never share a batch with pixel jobs.  A file the plan refuses, or whose entropy-coded data
+ * may take more room than its h * w * 3 pixels, is IRE_ERR_INVALID_INPUT with the reason in ire_last_error ("invalid: ...") and
+ * creates no job: such a file stays with the host codec.  A file whose DATA the device finds corrupt fails only its own job, at
+ * its poll: IRE_ERR_INVALID_INPUT "invalid: corrupt JPEG data (decoder status N)"; the other jobs of its batch complete. */
+int ire_submit_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, const double* scores, ire_job** job_out);
 /* Wait up to timeout_ms (<0: forever) for the job; on IRE_OK out_rgb (h*w*3 pixel bytes, or with IRE_FLAG_RESULT_PNG_BASE64
  * ire_png_base64_bytes_fit(h, w) characters -- for an ire_submit job the same number as ire_png_base64_bytes(h, w), which is 0
  * for the ragged widths ire_submit_fit takes: size the buffer with the _fit form), scores_out (7, may

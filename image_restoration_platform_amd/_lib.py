@@ -9,6 +9,9 @@ IRE_OK, IRE_ERR_INVALID_INPUT, IRE_ERR_TIMEOUT, IRE_ERR_UNAVAILABLE, IRE_ERR_INT
 IRE_FLAG_RESULT_PNG_BASE64 = 1
 IRE_FLAG_RESULT_PNG_DEFLATE = 4
 IRE_FLAG_RESULT_JPEG = 8
+IRE_FLAG_DECODE_PROGRESSIVE = 32
+IRE_DECODE_ACCEPT_PROGRESSIVE = 1
+IRE_DECODE_MAX_SCANS = 64
 IRE_ABI_VERSION = 3      # include/ire.h; load() refuses a library of another version (tests/test_abi.py cross-checks the three copies)
 
 
@@ -67,6 +70,7 @@ SYMBOLS = {
     "ire_encode_jpeg_base64_fit_device": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp]),
     "ire_encode_jpeg_base64_fit": (_i, [_vp, _u8p, _i, _i, _i, _u8p, ctypes.c_size_t, _vp]),
     "ire_decode_jpeg_plan": (_i, [_u8p, ctypes.c_size_t, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "ire_decode_jpeg_plan_ex": (_i, [_u8p, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "ire_decode_jpeg": (_i, [_vp, _u8p, ctypes.c_size_t, _u8p, _i, _i]),
     "ire_decode_jpeg_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp, _vp]),
     "ire_submit_fit": (_i, [_vp, _u8p, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),

@@ -70,7 +70,7 @@ struct HipSlot : SlotMem<DeviceMem, PinnedMem> {
 
 // what a file job keeps of its file between submit and its batch's decode: the head as parsed, the scan's streams as cut
 struct JpegFileHead {
-    jpegparse::Header hd;
+    jpegparse::File hd;
     std::vector<jpegdec::DecStream> streams;
 };
 
@@ -168,18 +168,18 @@ struct HipBatchBackend {
     std::shared_ptr<void> file_plan(const uint8_t* file, size_t bytes, int* h, int* w, size_t* room) {
         auto head = std::make_shared<JpegFileHead>();
         std::string why;
-        if (!jpegparse::plan(file, bytes, head->hd, why)) fail(IRE_ERR_INVALID_INPUT, why);
-        *h = head->hd.im.h; *w = head->hd.im.w;
-        *room = jpegparse::scan_room(head->hd, bytes);
+        if (!jpegparse::plan_file(file, bytes, E.decode_accept(), head->hd, why)) fail(IRE_ERR_INVALID_INPUT, why);
+        *h = head->hd.hd.im.h; *w = head->hd.hd.im.w;
+        *room = jpegparse::file_room(head->hd, bytes);
         return head;
     }
     size_t file_stage(void* head, const uint8_t* file, size_t bytes, uint8_t* dst, size_t room) {
         JpegFileHead& f = *static_cast<JpegFileHead*>(head);
         f.streams.assign(f.hd.nstreams, jpegdec::DecStream{});
         std::string why;
-        if (!jpegparse::split_scan(f.hd, file, bytes, dst, room, f.streams.data(), why)) fail(IRE_ERR_INVALID_INPUT, why);
+        if (!jpegparse::split_file(f.hd, file, bytes, dst, room, f.streams.data(), why)) fail(IRE_ERR_INVALID_INPUT, why);
         const jpegdec::DecStream& last = f.streams.back();
-        return (size_t)last.off + last.len;
+        return std::max<size_t>((size_t)last.off + last.len, 1);      // (0 would say that nothing was staged: a last scan of no bytes)
     }
     void decode(SlotBufs& b, int first, int count, int h, int w, void* const* heads, const size_t* used) {
         HipSlot& hs = *static_cast<HipSlot*>(b.impl);
@@ -189,7 +189,7 @@ struct HipBatchBackend {
             IRE_HIP(hipMemsetAsync(hs.d_fstat.get<int32_t>(), 0, sizeof(int32_t) * kMaxBatch, cs));
             std::memset(hs.pin_fstat.get<int32_t>(), 0, sizeof(int32_t) * kMaxBatch);
         }
-        const jpegparse::Header* hd[kMaxBatch];
+        const jpegparse::File* hd[kMaxBatch];
         const jpegdec::DecStream* streams[kMaxBatch];
         const uint8_t* bytes[kMaxBatch];
         size_t room[kMaxBatch];
@@ -339,9 +339,9 @@ int ire_init(const ire_config* cfg, ire_engine** out) {
     return guarded([&] {
         if (!cfg || !out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_init");
         if (cfg->struct_size < sizeof(ire_config)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.struct_size");
-        if (cfg->flags & ~(uint32_t)(IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG))
-            fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
-        if ((cfg->flags & (cfg->flags - 1)) != 0) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");      // (every known bit is a result format)
+        constexpr uint32_t kResultBits = IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG;
+        if (cfg->flags & ~(kResultBits | IRE_FLAG_DECODE_PROGRESSIVE)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
+        if (((cfg->flags & kResultBits) & ((cfg->flags & kResultBits) - 1)) != 0) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");
         *out = nullptr;
         std::unique_ptr<ire_engine> E(new ire_engine());
         E->eng.reset(new Engine(*cfg));
@@ -532,6 +532,22 @@ int ire_decode_jpeg_plan(const uint8_t* file, size_t bytes, int* out_h, int* out
         if (out_h) *out_h = hd.im.h;
         if (out_w) *out_w = hd.im.w;
         if (out_sampling) *out_sampling = hd.im.sampling;
+    });
+}
+
+static_assert(IRE_DECODE_ACCEPT_PROGRESSIVE == jpegparse::kAcceptProgressive && IRE_DECODE_MAX_SCANS == jpegparse::kMaxScans, "ire.h and jpeg_parse.hpp");
+
+int ire_decode_jpeg_plan_ex(const uint8_t* file, size_t bytes, uint32_t accept, int* out_h, int* out_w, int* out_sampling, int* out_nscans) {
+    return guarded([&] {
+        if (!file) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_decode_jpeg_plan: null file");
+        if (accept & ~(uint32_t)IRE_DECODE_ACCEPT_PROGRESSIVE) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_decode_jpeg_plan_ex: unknown accept bits");
+        jpegparse::File f;
+        std::string why;
+        if (!jpegparse::plan_file(file, bytes, accept, f, why)) fail(IRE_ERR_INVALID_INPUT, why);
+        if (out_h) *out_h = f.hd.im.h;
+        if (out_w) *out_w = f.hd.im.w;
+        if (out_sampling) *out_sampling = f.hd.im.sampling;
+        if (out_nscans) *out_nscans = (int)f.nscans();
     });
 }
 

@@ -48,9 +48,9 @@ Engine::Engine(const ire_config& cfg) {
     if (max_batch_ > 64) fail(IRE_ERR_INVALID_INPUT, "invalid max_batch (1..64)");
     num_lanes_ = cfg.num_streams > 0 ? cfg.num_streams : 1;
     if (num_lanes_ > 16) num_lanes_ = 16;
-    if (cfg.flags & ~(uint32_t)(IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG))
-        fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
-    if ((cfg.flags & (cfg.flags - 1)) != 0) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");
+    constexpr uint32_t kResultBits = IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG;
+    if (cfg.flags & ~(kResultBits | IRE_FLAG_DECODE_PROGRESSIVE)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
+    if (((cfg.flags & kResultBits) & ((cfg.flags & kResultBits) - 1)) != 0) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");
     flags_ = cfg.flags;
     sw_ = ConvSwitches::from_env();
     cus_ = persistent_grid_cus();
@@ -97,8 +97,8 @@ Engine::~Engine() {
         dec_times_collect();
         std::fprintf(stderr,
                      "{\"jpeg_dec_kernel_ms\": {\"memset\": %.4f, \"long\": %.4f, \"spec\": %.4f, \"chain\": %.4f, \"write\": %.4f, \"short\": %.4f, \"idct\": %.4f, "
-                     "\"colour\": %.4f, \"calls\": %lld}}\n",
-                     dec_ms_[0], dec_ms_[1], dec_ms_[2], dec_ms_[3], dec_ms_[4], dec_ms_[5], dec_ms_[6], dec_ms_[7], (long long)dec_calls_);
+                     "\"colour\": %.4f, \"calls\": %lld, \"later_scans\": %.4f}}\n",
+                     dec_ms_[0], dec_ms_[1], dec_ms_[2], dec_ms_[3], dec_ms_[4], dec_ms_[5], dec_ms_[7], dec_ms_[8], (long long)dec_calls_, dec_ms_[6]);
         for (hipEvent_t ev : dec_marks_) if (ev) (void)hipEventDestroy(ev);
     }
     if (stamps_dev_ && std::getenv("IRE_STAMPS_RAW")) {     // diagnostic builds with their own stamp layout (conv_pk.hip PK_TICKS): the whole buffer, one value per line
@@ -435,11 +435,12 @@ void Engine::decode_jpeg_device(const uint8_t* const* files, const size_t* bytes
     if (!files || !bytes || !d_rgb || !d_status || n < 1 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the JPEG decoder (1..max_batch files)");
     if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the JPEG decoder: height and width must be in 1..8192");
     if (image_pitch < (size_t)3 * w * h) fail(IRE_ERR_INVALID_INPUT, "invalid pitch for the JPEG decoder: images overlap");
-    std::vector<jpegparse::Header> hd((size_t)n);
+    std::vector<jpegparse::File> hd((size_t)n);
     for (int i = 0; i < n; ++i) {
         std::string why;
-        if (!files[i] || !jpegparse::parse_header(files[i], bytes[i], hd[i], why)) fail(IRE_ERR_INVALID_INPUT, files[i] ? why : "invalid arguments to the JPEG decoder: null file");
-        if (hd[i].im.h != h || hd[i].im.w != w) fail(IRE_ERR_INVALID_INPUT, "invalid: the JPEG file's size is not the planned h x w");
+        if (!files[i] || !jpegparse::head_file(files[i], bytes[i], decode_accept(), hd[i], why))
+            fail(IRE_ERR_INVALID_INPUT, files[i] ? why : "invalid arguments to the JPEG decoder: null file");
+        if (hd[i].hd.im.h != h || hd[i].hd.im.w != w) fail(IRE_ERR_INVALID_INPUT, "invalid: the JPEG file's size is not the planned h x w");
     }
     const JpegDecLayout L0 = jpeg_dec_layout(hd.data(), bytes, n);
     if (L0.total >= ((size_t)1 << 32)) fail(IRE_ERR_INVALID_INPUT, "invalid: the batch's JPEG files exceed 4 GB");
@@ -448,16 +449,16 @@ void Engine::decode_jpeg_device(const uint8_t* const* files, const size_t* bytes
     const int turn = S.turn ^ 1;
     JpegDecLayout L;
     jpeg_dec_pack(files, bytes, hd.data(), n, L0, pin.get<uint8_t>(), L, dec_min_windows_);
-    const size_t lanes = jpeg_dec_lane_bytes(L.nwin);
-    S.grow(L.total, jpeg_dec_coef_bytes(n, h, w), jpeg_dec_coef_bytes(max_batch_, h, w), jpeg_dec_plane_bytes(n, h, w), jpeg_dec_plane_bytes(max_batch_, h, w), lanes, nullptr);
+    const size_t lanes = jpeg_dec_lane_bytes(L.nwin), walk = L.walk_blocks ? jpeg_dec_walk_bytes(L.walk_blocks) : 0;
+    S.grow(L.total, jpeg_dec_coef_bytes(n, h, w), jpeg_dec_coef_bytes(max_batch_, h, w), jpeg_dec_plane_bytes(n, h, w), jpeg_dec_plane_bytes(max_batch_, h, w), lanes, walk, nullptr);
     IRE_HIP(hipMemcpyAsync(S.d_in.get<uint8_t>(), pin.get<uint8_t>(), L.total, hipMemcpyHostToDevice, s));
     S.uploaded(turn, s);
     if (dec_times_) {
         dec_times_collect();
         for (hipEvent_t& ev : dec_marks_) if (!ev) IRE_HIP(hipEventCreate(&ev));
     }
-    jpeg_dec_launch(S.d_in.get<uint8_t>(), L, n, h, w, S.d_coef.get<uint8_t>(), S.d_planes.get<uint8_t>(), lanes ? S.d_lanes.get<uint8_t>() : nullptr, d_rgb, image_pitch, d_status, s,
-                    dec_times_ ? dec_marks_ : nullptr);
+    jpeg_dec_launch(S.d_in.get<uint8_t>(), L, n, h, w, S.d_coef.get<uint8_t>(), S.d_planes.get<uint8_t>(), lanes ? S.d_lanes.get<uint8_t>() : nullptr,
+                    walk ? S.d_walk.get<uint8_t>() : nullptr, d_rgb, image_pitch, d_status, s, dec_times_ ? dec_marks_ : nullptr);
     dec_marks_pending_ = dec_times_;
 }
 
@@ -477,23 +478,24 @@ void Engine::DecScratch::uploaded(int which, hipStream_t s) {
 }
 
 // before a buffer goes, nothing enqueued may still use it: the whole device, or (only != null) the one stream that ever uses this scratch
-void Engine::DecScratch::grow(size_t blob, size_t coef, size_t coef_full, size_t planes, size_t planes_full, size_t lanes, hipStream_t only) {
-    if (blob > d_in.bytes() || coef > d_coef.bytes() || planes > d_planes.bytes() || lanes > d_lanes.bytes()) IRE_HIP(only ? hipStreamSynchronize(only) : hipDeviceSynchronize());
+void Engine::DecScratch::grow(size_t blob, size_t coef, size_t coef_full, size_t planes, size_t planes_full, size_t lanes, size_t walk, hipStream_t only) {
+    if (blob > d_in.bytes() || coef > d_coef.bytes() || planes > d_planes.bytes() || lanes > d_lanes.bytes() || walk > d_walk.bytes()) IRE_HIP(only ? hipStreamSynchronize(only) : hipDeviceSynchronize());
     d_in.grow(blob, blob + blob / 2);
     d_coef.grow(coef, batch_room(coef, coef_full));
     d_planes.grow(planes, batch_room(planes, planes_full));
     if (lanes) d_lanes.grow(lanes, lanes + lanes / 2);
+    if (walk) d_walk.grow(walk, walk + walk / 2);
 }
 
-void Engine::decode_jpeg_streams(const jpegparse::Header* const* hd, const jpegdec::DecStream* const* streams, const uint8_t* const* bytes, const size_t* used, int n, int h,
+void Engine::decode_jpeg_streams(const jpegparse::File* const* hd, const jpegdec::DecStream* const* streams, const uint8_t* const* bytes, const size_t* used, int n, int h,
                                  int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s) {
     if (!hd || !streams || !bytes || !used || !d_rgb || !d_status || n < 1 || n > max_batch_) fail(IRE_ERR_INTERNAL, "internal: arguments of the batcher's JPEG decode");
-    std::vector<uint32_t> ns((size_t)n);
+    std::vector<uint32_t> ns((size_t)n), nu((size_t)n);
     for (int i = 0; i < n; ++i) {
-        if (hd[i]->im.h != h || hd[i]->im.w != w) fail(IRE_ERR_INTERNAL, "internal: a file job in a slot of another size");
-        ns[(size_t)i] = hd[i]->nstreams;
+        if (hd[i]->hd.im.h != h || hd[i]->hd.im.w != w) fail(IRE_ERR_INTERNAL, "internal: a file job in a slot of another size");
+        ns[(size_t)i] = hd[i]->nstreams; nu[(size_t)i] = hd[i]->nscans();
     }
-    const JpegDecLayout L0 = jpeg_dec_layout_rooms(ns.data(), used, n);
+    const JpegDecLayout L0 = jpeg_dec_layout_rooms(ns.data(), nu.data(), used, n);
     if (L0.total >= ((size_t)1 << 32)) fail(IRE_ERR_INVALID_INPUT, "invalid: the batch's JPEG files exceed 4 GB");
     DecScratch& S = dec_batch_;
     Buf<PinnedMem>& pin = S.next_pin(L0.bytes);
@@ -501,14 +503,15 @@ void Engine::decode_jpeg_streams(const jpegparse::Header* const* hd, const jpegd
     JpegDecLayout L;
     std::vector<size_t> off((size_t)n);
     jpeg_dec_pack_streams(hd, streams, used, n, L0, pin.get<uint8_t>(), L, off.data(), dec_min_windows_);
-    const size_t lanes = jpeg_dec_lane_bytes(L.nwin);
-    S.grow(L.total, jpeg_dec_coef_bytes(n, h, w), jpeg_dec_coef_bytes(max_batch_, h, w), jpeg_dec_plane_bytes(n, h, w), jpeg_dec_plane_bytes(max_batch_, h, w), lanes, s);
+    const size_t lanes = jpeg_dec_lane_bytes(L.nwin), walk = L.walk_blocks ? jpeg_dec_walk_bytes(L.walk_blocks) : 0;
+    S.grow(L.total, jpeg_dec_coef_bytes(n, h, w), jpeg_dec_coef_bytes(max_batch_, h, w), jpeg_dec_plane_bytes(n, h, w), jpeg_dec_plane_bytes(max_batch_, h, w), lanes, walk, s);
     IRE_HIP(hipMemcpyAsync(S.d_in.get<uint8_t>(), pin.get<uint8_t>(), L.bytes, hipMemcpyHostToDevice, s));
     S.uploaded(turn, s);
     // the streams go from where their submitters cut them (the slot's pinned input) straight to the blob on the device
     for (int i = 0; i < n; ++i)
         if (used[i]) IRE_HIP(hipMemcpyAsync(S.d_in.get<uint8_t>() + L.bytes + off[(size_t)i], bytes[i], used[i], hipMemcpyHostToDevice, s));
-    jpeg_dec_launch(S.d_in.get<uint8_t>(), L, n, h, w, S.d_coef.get<uint8_t>(), S.d_planes.get<uint8_t>(), lanes ? S.d_lanes.get<uint8_t>() : nullptr, d_rgb, image_pitch, d_status, s);
+    jpeg_dec_launch(S.d_in.get<uint8_t>(), L, n, h, w, S.d_coef.get<uint8_t>(), S.d_planes.get<uint8_t>(), lanes ? S.d_lanes.get<uint8_t>() : nullptr,
+                    walk ? S.d_walk.get<uint8_t>() : nullptr, d_rgb, image_pitch, d_status, s);
 }
 
 void Engine::dec_times_collect() {

@@ -191,7 +191,7 @@ public:
     // The batcher's file jobs: n files of one planned size whose heads were parsed and whose scans were cut by their submitters
     // (streams[i]: hd[i]->nstreams records with offsets inside bytes[i], pinned, used[i] bytes) -> the same as decode_jpeg_device.
     // Works on a scratch of its own and takes no lock: ONE thread calls it (the batcher's launcher), always on the same stream.
-    void decode_jpeg_streams(const jpegparse::Header* const* hd, const jpegdec::DecStream* const* streams, const uint8_t* const* bytes, const size_t* used, int n, int h,
+    void decode_jpeg_streams(const jpegparse::File* const* hd, const jpegdec::DecStream* const* streams, const uint8_t* const* bytes, const size_t* used, int n, int h,
                              int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s);
     // Any-size jobs (h, w in 1..8192): edge-replicate pad to (max(16, ceil8 h), max(16, ceil8 w)) into the engine's padded
     // staging, the network on the padded shape, the top-left h x w window as the result.  The classifier always sees the
@@ -207,6 +207,8 @@ public:
     static bool fit_is_aligned(int h, int w) { return h % 8 == 0 && w % 8 == 0 && h >= 16 && w >= 16; }
     static int fit_dim(int v) { return v <= 16 ? 16 : (v + 7) / 8 * 8; }
     uint32_t flags() const { return flags_; }
+    // what the JPEG decoder's parser is asked to accept (jpeg_parse.hpp)
+    uint32_t decode_accept() const { return (flags_ & IRE_FLAG_DECODE_PROGRESSIVE) ? jpegparse::kAcceptProgressive : 0u; }
 
     void debug_sums(int n, uint64_t* out);
     void debug_capture(bool on) { capture_ = on; captured_.clear(); }
@@ -313,6 +315,7 @@ private:
         Buf<PinnedMem> pin[2];            // two, used in turn: call k + 1 is parsed and staged while call k's upload may still run
         Buf<DeviceMem> d_in, d_coef, d_planes;
         Buf<DeviceMem> d_lanes;           // the lane records and window heads of the streams decoded window-parallel
+        Buf<DeviceMem> d_walk;            // the masks and walk records of a progressive file's AC refinement scans
         hipEvent_t up_ev[2] = {};         // the last upload out of pin[i]
         bool up_recorded[2] = {};
         int turn = 0;
@@ -322,7 +325,7 @@ private:
         ~DecScratch() { for (hipEvent_t ev : up_ev) if (ev) (void)hipEventDestroy(ev); }
         Buf<PinnedMem>& next_pin(size_t bytes);       // the blob this call fills, free of its last upload and `bytes` large at least
         void uploaded(int which, hipStream_t s);
-        void grow(size_t blob, size_t coef, size_t coef_full, size_t planes, size_t planes_full, size_t lanes, hipStream_t only);
+        void grow(size_t blob, size_t coef, size_t coef_full, size_t planes, size_t planes_full, size_t lanes, size_t walk, hipStream_t only);
     };
     DecScratch dec_, dec_batch_;
     Buf<DeviceMem> d_dec_out_;

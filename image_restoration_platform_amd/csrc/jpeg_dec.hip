@@ -1,4 +1,4 @@
-// jpeg_dec.hip -- baseline JPEG files -> RGB pixels, on the device, byte for byte what libjpeg-turbo decodes.
+// jpeg_dec.hip -- baseline and progressive JPEG files -> RGB pixels, on the device, byte for byte what libjpeg-turbo decodes.
 //
 // The host (jpeg_parse.hpp) reads the markers, refuses what is out of scope, cuts the scan at the restart markers into independent
 // streams with the byte stuffing removed, and builds the decode tables; ONE upload carries a whole batch: image records, tables,
@@ -21,6 +21,10 @@
 //                             in jpeg.hip); samples to per-component planes on the block grid
 //   K4 jpeg_dec_colour_kernel per pixel: "fancy" h2v1 / h2v2 chroma upsampling on the planes' REAL sizes (the blocks' padding is
 //                             never read), YCbCr -> RGB in 16-bit fixed point; the image's status word to the caller's array
+// A progressive file (jpeg_parse.hpp: parse_progressive) brings a record per SCAN: the frame's DecImage with the scan's own MCU, band and
+// bit position.  K1 .. K2 take such a record for an image (its first scans go through the very same lanes: jpeg_dec_core.hpp
+// dec_step_scan), once per dependency level; behind them run the level's refinement scans: jpeg_dec_dcref_kernel, and
+// jpeg_dec_mask_kernel / jpeg_dec_walk_kernel / jpeg_dec_apply_kernel.  K3 and K4 see the finished coefficients and know no difference.
 // Safety: every loop of K1 / K2 is bounded by the stream's bit count and its block count; reads of stream bytes are clamped to
 // the stream's length (1-bits behind it, as libjpeg pads); a coefficient is written only to a block index below the image's block
 // count; a code no table holds, a zig-zag index above 63, a DC category above 11 or a stream that ends with blocks missing or bytes
@@ -55,6 +59,10 @@ struct DecBatch {
     LaneRec* recs;                 // kLanes per window
     WinHead* heads;                // one per window
     unsigned min_windows;          // 0: K1 decodes every long stream
+    // a progressive file has a record per scan; a launch covers the records of ONE dependency level (they lie one behind the other)
+    unsigned unit0, win0, chain0;  // the level's first record / window / chain: added to the block index
+    uint64_t* masks;               // AC refinement scans: per block its non-zero mask (zig-zag order, the band only) ...
+    unsigned* wrecs;               // ... and its walk record, both from the record's walk0 on
 };
 
 __device__ __forceinline__ void load_image(const DecBatch& b, unsigned img, DecImage* s_im, DecTable* s_tabs, unsigned t) {
@@ -76,9 +84,10 @@ __global__ __launch_bounds__(kThreads) void jpeg_dec_long_kernel(DecBatch b) {
     __shared__ unsigned s_endp[2][kLanes], s_endbk[2][kLanes];
     __shared__ unsigned s_scan[4][kWaves];
     __shared__ unsigned s_final, s_err;
-    const unsigned t = threadIdx.x, img = blockIdx.y, lane = t & 63u, wv = t >> 6;
-    load_image(b, img, &s_im, s_tabs, t);
-    if (blockIdx.x >= s_im.nlong) return;
+    const unsigned t = threadIdx.x, unit = b.unit0 + blockIdx.y, lane = t & 63u, wv = t >> 6;
+    if (blockIdx.x >= b.images[unit].nlong) return;
+    load_image(b, unit, &s_im, s_tabs, t);
+    const unsigned img = s_im.slot;
     const DecStream sr = b.streams[s_im.first_long + blockIdx.x];
     if (b.min_windows && window_count(sr.len) >= b.min_windows) return;          // the window-parallel kernels' stream
     const unsigned char* bytes = b.bytes + sr.off;
@@ -187,8 +196,8 @@ __global__ __launch_bounds__(kThreads) void jpeg_dec_spec_kernel(DecBatch b) {
     __shared__ DecTable s_tabs[8];
     __shared__ DecImage s_im;
     __shared__ unsigned s_endp[2][kLanes], s_endbk[2][kLanes];
-    const unsigned t = threadIdx.x;
-    const DecWindow wn = b.windows[blockIdx.x];
+    const unsigned t = threadIdx.x, wi = b.win0 + blockIdx.x;
+    const DecWindow wn = b.windows[wi];
     load_image(b, wn.image, &s_im, s_tabs, t);
     const DecStream sr = b.streams[wn.stream];
     const unsigned char* bytes = b.bytes + sr.off;
@@ -220,7 +229,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_dec_spec_kernel(DecBatch b) {
         s_endp[cur][t] = end.p; s_endbk[cur][t] = state_bk(end);
         if (!__syncthreads_or(changed)) break;
     }
-    if (active) b.recs[(unsigned long long)blockIdx.x * kLanes + t] = LaneRec{start.p, state_bk(start), end.p, state_bk(end), lo};
+    if (active) b.recs[(unsigned long long)wi * kLanes + t] = LaneRec{start.p, state_bk(start), end.p, state_bk(end), lo};
 }
 
 // B.  blockIdx.x: the multi-window stream.  Thread 0 carries the true state through the stream's windows (chain_lane, one lane's bits
@@ -232,7 +241,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_dec_chain_kernel(DecBatch b) {
     __shared__ unsigned s_scan[4][kWaves];
     __shared__ unsigned s_go, s_bit0;
     const unsigned t = threadIdx.x;
-    const DecChain ch = b.chains[blockIdx.x];
+    const DecChain ch = b.chains[b.chain0 + blockIdx.x];
     load_image(b, ch.image, &s_im, s_tabs, t);
     const DecStream sr = b.streams[ch.stream];
     const unsigned char* bytes = b.bytes + sr.off;
@@ -250,7 +259,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_dec_chain_kernel(DecBatch b) {
                 // ended at or behind its own last bit)
                 s_bit0 = win0 + l * kSubseqBits;
                 s_go = !same && carry.p >= s_bit0;
-                if (carry.p < s_bit0) atomicOr(&b.stat[ch.image], kStBadCode);          // never: flagged, not guessed
+                if (carry.p < s_bit0) atomicOr(&b.stat[s_im.slot], kStBadCode);          // never: flagged, not guessed
             }
             __syncthreads();
             if (!s_go) break;
@@ -267,7 +276,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_dec_chain_kernel(DecBatch b) {
         if (t == 0) carry = state_of(recs[nl - 1].ep, recs[nl - 1].ebk);
         __syncthreads();                                            // s_scan is read no more
     }
-    if (t == 0 && done < total_blocks) atomicOr(&b.stat[ch.image], kStBadEnd);      // blocks missing
+    if (t == 0 && done < total_blocks) atomicOr(&b.stat[s_im.slot], kStBadEnd);      // blocks missing
 }
 
 // C.  blockIdx.x: the window.  K1's writing pass from every lane's settled start.
@@ -276,19 +285,19 @@ __global__ __launch_bounds__(kThreads) void jpeg_dec_write_kernel(DecBatch b) {
     __shared__ DecTable s_tabs[8];
     __shared__ DecImage s_im;
     __shared__ unsigned s_scan[4][kWaves];
-    const unsigned t = threadIdx.x;
-    const DecWindow wn = b.windows[blockIdx.x];
+    const unsigned t = threadIdx.x, wi = b.win0 + blockIdx.x;
+    const DecWindow wn = b.windows[wi];
     load_image(b, wn.image, &s_im, s_tabs, t);
     const DecStream sr = b.streams[wn.stream];
     const unsigned char* bytes = b.bytes + sr.off;
-    short* coef = b.coef + (unsigned long long)wn.image * b.coef_stride;
+    short* coef = b.coef + (unsigned long long)s_im.slot * b.coef_stride;
     const unsigned total_bits = 8u * sr.len, total_blocks = sr.nmcu * s_im.bpm, gblk0 = sr.mcu0 * s_im.bpm, win0 = wn.win0;
     for (unsigned k = t; k < kStageWords; k += kThreads) s_words[k + (k >> 5)] = stream_word(bytes, sr.len, win0 / 32 + k);
     const unsigned nl = window_lanes(total_bits, win0), lim = lane_lim(total_bits, win0, t);
     const bool active = t < nl;
     LaneRec r{0, 0, 0, 0, {0, {0, 0, 0}}};
-    if (active) r = b.recs[(unsigned long long)blockIdx.x * kLanes + t];
-    const WinHead hd = b.heads[blockIdx.x];
+    if (active) r = b.recs[(unsigned long long)wi * kLanes + t];
+    const WinHead hd = b.heads[wi];
     const unsigned v[4] = {r.o.nblk, r.o.dc[0], r.o.dc[1], r.o.dc[2]};
     unsigned before[4], all[4];
     block_scan4(v, s_scan, before, all);                            // (its barrier also ends the staging)
@@ -300,7 +309,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_dec_write_kernel(DecBatch b) {
         LaneOut w;
         unsigned err = dec_subseq(rd, s_tabs, s_im, st, lim, room, coef, gblk0 + first, dcpred, w);
         if (!err && w.nblk && first + w.nblk == total_blocks && !stream_end_ok(st.p, sr.len)) err = kStBadEnd;     // bytes left over
-        if (err) atomicOr(&b.stat[wn.image], (int)err);
+        if (err) atomicOr(&b.stat[s_im.slot], (int)err);
     }
 }
 
@@ -308,8 +317,10 @@ __global__ __launch_bounds__(kThreads) void jpeg_dec_write_kernel(DecBatch b) {
 __global__ __launch_bounds__(kThreads) void jpeg_dec_short_kernel(DecBatch b) {
     __shared__ DecTable s_tabs[8];
     __shared__ DecImage s_im;
-    const unsigned t = threadIdx.x, img = blockIdx.y;
-    load_image(b, img, &s_im, s_tabs, t);
+    const unsigned t = threadIdx.x, unit = b.unit0 + blockIdx.y;
+    if (b.images[unit].kind >= kScanDcRefine || blockIdx.x * kThreads >= b.images[unit].nshort) return;       // (a refinement scan's streams are no lanes' work)
+    load_image(b, unit, &s_im, s_tabs, t);
+    const unsigned img = s_im.slot;
     short* coef = b.coef + (unsigned long long)img * b.coef_stride;
     unsigned err = 0;
     for (unsigned s = blockIdx.x * kThreads + t; s < s_im.nshort; s += gridDim.x * kThreads) {
@@ -323,6 +334,125 @@ __global__ __launch_bounds__(kThreads) void jpeg_dec_short_kernel(DecBatch b) {
         err |= e;
     }
     if (err) atomicOr(&b.stat[img], (int)err);
+}
+
+// ---- the refinement scans of a progressive file (jpeg_dec_core.hpp says how an AC refinement scan is split) -------------------------
+// A refinement scan's streams lie in scan order from first_short on (none is "long"); restart intervals count the scan's own MCUs,
+// so block g of the scan belongs to stream g / (interval's blocks), and the interval is stream 0's own block count.
+
+// DC refinement: one thread per block of the scan; bit n of a stream is its block n.  blockIdx.y: the record within the level.
+__global__ __launch_bounds__(kThreads) void jpeg_dec_dcref_kernel(DecBatch b) {
+    const DecImage& im = b.images[b.unit0 + blockIdx.y];
+    if (im.kind != kScanDcRefine) return;
+    const unsigned g = blockIdx.x * kThreads + threadIdx.x;
+    if (g >= im.nblocks) return;
+    const unsigned per = b.streams[im.first_short].nmcu * im.bpm, si = g / per, n = g - si * per;
+    if (si >= im.nshort) return;
+    const DecStream sr = b.streams[im.first_short + si];
+    if (n >= sr.nmcu * im.bpm) return;
+    if (n == 0 && !stream_end_ok(sr.nmcu * im.bpm, sr.len)) atomicOr(&b.stat[im.slot], kStBadEnd);
+    const unsigned byte = n >> 3;
+    if (byte < sr.len && ((b.bytes[sr.off + byte] >> (7u - (n & 7u))) & 1u)) {
+        short* c = b.coef + (unsigned long long)im.slot * b.coef_stride + block_base(im, g);
+        *c = (short)(*c | (1 << im.al));
+    }
+}
+
+// AC refinement, the masks: one wave per block of the scan's plane, lane j looks at zig-zag position j.
+__global__ __launch_bounds__(kThreads) void jpeg_dec_mask_kernel(DecBatch b) {
+    const DecImage& im = b.images[b.unit0 + blockIdx.y];
+    if (im.kind != kScanAcRefine) return;
+    const unsigned lane = threadIdx.x & 63u, g = blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (g >= im.nblocks) return;                                    // (the whole wave)
+    const short* blk = b.coef + (unsigned long long)im.slot * b.coef_stride + block_base(im, g);
+    const bool nz = lane >= im.ss && lane <= im.se && blk[natural_of(lane)] != 0;
+    const uint64_t m = __ballot(nz);
+    if (lane == 0) b.masks[im.walk0 + g] = m;
+}
+
+// AC refinement, the walk of the short streams (at most kShortMaxBytes, as K2's): one lane per stream, over symbols and masks alone;
+// a record per block.
+__global__ __launch_bounds__(kThreads) void jpeg_dec_walk_kernel(DecBatch b) {
+    const DecImage& im = b.images[b.unit0 + blockIdx.y];
+    if (im.kind != kScanAcRefine) return;
+    const unsigned si = blockIdx.x * kThreads + threadIdx.x;
+    if (si >= im.nshort) return;
+    const DecStream sr = b.streams[im.first_short + si];
+    if (sr.len > kShortMaxBytes) return;                            // jpeg_dec_walk_long_kernel's
+    const unsigned c = im.comp_of[0] & 3u, g0 = sr.mcu0, nblk = sr.mcu0 < im.nblocks ? min(sr.nmcu, im.nblocks - sr.mcu0) : 0u;
+    const DecTable& tab = b.tabs[8ull * (b.unit0 + blockIdx.y) + 4u + (im.ac_tab[c] & 3u)];
+    const ByteReader rd{b.bytes + sr.off, sr.len};
+    const unsigned err = refine_walk_stream(rd, tab, im.ss, im.se, b.masks + im.walk0 + g0, b.wrecs + im.walk0 + g0, nblk, sr.len);
+    if (err) atomicOr(&b.stat[im.slot], (int)err);
+}
+
+// The walk of a longer stream: one WAVE (a workgroup of 64) per stream.  Lane 0 walks; in turns all 64 lanes stage the next
+// kWalkBlocks masks (lane i block i's: 512 bytes in one go) and the next kWalkWords stream words into LDS, so that the walking lane
+// never waits for a load of its own, and write the turn's records.  blockIdx.x: the stream of the scan, blockIdx.y: the record.
+__global__ __launch_bounds__(64) void jpeg_dec_walk_long_kernel(DecBatch b) {
+    __shared__ uint64_t s_mask[kWalkBlocks];
+    __shared__ unsigned s_rec[kWalkBlocks];
+    __shared__ unsigned s_words[kWalkStagePadded];
+    __shared__ DecTable s_tab;
+    __shared__ unsigned s_n, s_p, s_err;
+    const DecImage& im = b.images[b.unit0 + blockIdx.y];
+    if (im.kind != kScanAcRefine || blockIdx.x >= im.nshort) return;
+    const DecStream sr = b.streams[im.first_short + blockIdx.x];
+    if (sr.len <= kShortMaxBytes) return;
+    const unsigned lane = threadIdx.x, c = im.comp_of[0] & 3u, ss = im.ss, se = im.se;
+    const unsigned nblk = sr.mcu0 < im.nblocks ? min(sr.nmcu, im.nblocks - sr.mcu0) : 0u, total_bits = 8u * sr.len;
+    const uint64_t* masks = b.masks + im.walk0 + sr.mcu0;
+    unsigned* recs = b.wrecs + im.walk0 + sr.mcu0;
+    const unsigned char* bytes = b.bytes + sr.off;
+    {
+        const unsigned* st = reinterpret_cast<const unsigned*>(b.tabs + 8ull * (b.unit0 + blockIdx.y) + 4u + (im.ac_tab[c] & 3u));
+        unsigned* dt = reinterpret_cast<unsigned*>(&s_tab);
+        for (unsigned k = lane; k < sizeof(DecTable) / 4; k += 64) dt[k] = st[k];
+    }
+    RefState st{0, 0, 0};                                           // lane 0's
+    unsigned n = 0, mb = 0, p = 0, err = 0;                         // the next block | the staged masks' first block | st.p and the error, known to all
+    while (n < nblk && !err) {                                      // (uniform: n, p and err come out of LDS)
+        const unsigned bit0 = p & ~31u, nend = min(mb + kWalkBlocks, nblk);
+        __syncthreads();                                            // the turn before is read no more
+        s_mask[lane] = mb + lane < nblk ? masks[mb + lane] : 0ull;
+        for (unsigned k = lane; k < kWalkStageWords; k += 64) s_words[k + (k >> 5)] = stream_word(bytes, sr.len, bit0 / 32 + k);
+        __syncthreads();
+        if (lane == 0) {
+            unsigned nn = n;
+            const unsigned e = refine_walk_some(WordReader{s_words, bit0}, s_tab, ss, se, s_mask, s_rec, mb, nend, bit0 + 32u * kWalkWords, total_bits, st, nn);
+            s_n = nn; s_p = st.p; s_err = e;
+        }
+        __syncthreads();
+        n = s_n; p = s_p; err = s_err;
+        // every record of this turn's blocks that has begun: up to block n, and block n itself when the walk stopped inside it (an
+        // error, or the staged words ran out: its record was written when it began, in this turn or in one before -- then again the same)
+        if (n == nend || err) {
+            if (mb + lane < n || (mb + lane == n && n < nblk && err)) recs[mb + lane] = s_rec[lane];
+            if (n == nend) mb = nend;
+        }
+    }
+    if (err) for (unsigned j = n + 1 + lane; j < nblk; j += 64) recs[j] = kBadPos;
+    if (lane == 0) {
+        if (!err) err = refine_walk_end(st, sr.len);
+        if (err) atomicOr(&b.stat[im.slot], (int)err);
+    }
+}
+
+// AC refinement, every block by itself from its record: one thread per block.
+__global__ __launch_bounds__(kThreads) void jpeg_dec_apply_kernel(DecBatch b) {
+    const DecImage& im = b.images[b.unit0 + blockIdx.y];
+    if (im.kind != kScanAcRefine) return;
+    const unsigned g = blockIdx.x * kThreads + threadIdx.x;
+    if (g >= im.nblocks) return;
+    const unsigned per = b.streams[im.first_short].nmcu, si = g / per;
+    if (si >= im.nshort) return;
+    const DecStream sr = b.streams[im.first_short + si];
+    if (g < sr.mcu0 || g - sr.mcu0 >= sr.nmcu) return;
+    const unsigned c = im.comp_of[0] & 3u;
+    const DecTable& tab = b.tabs[8ull * (b.unit0 + blockIdx.y) + 4u + (im.ac_tab[c] & 3u)];
+    const ByteReader rd{b.bytes + sr.off, sr.len};
+    short* blk = b.coef + (unsigned long long)im.slot * b.coef_stride + block_base(im, g);
+    refine_apply_block(rd, tab, im.ss, im.se, im.al, b.masks[im.walk0 + g], b.wrecs[im.walk0 + g], blk);
 }
 
 // ---- libjpeg's "islow" inverse DCT (jidctint.c): 13-bit constants, 2 extra bits kept between the passes -----------------------------
@@ -452,14 +582,16 @@ size_t jpeg_dec_coef_bytes(int n, int h, int w) { return up256(4 * (size_t)n) + 
 size_t jpeg_dec_plane_bytes(int n, int h, int w) { return (size_t)n * jpeg_dec_blocks(h, w) * 64; }
 size_t jpeg_dec_lane_bytes(size_t nwin) { return nwin * (sizeof(LaneRec) * kLanes + sizeof(WinHead)); }
 
-// rooms[i]: the bytes image i's streams take at most in the blob's byte area
-JpegDecLayout jpeg_dec_layout_rooms(const uint32_t* nstreams, const size_t* rooms, int n) {
+size_t jpeg_dec_walk_bytes(size_t blocks) { return up256(8 * blocks) + 4 * blocks; }
+
+// rooms[i]: the bytes image i's streams take at most in the blob's byte area; nstreams[i], nscans[i]: over all its scans
+JpegDecLayout jpeg_dec_layout_rooms(const uint32_t* nstreams, const uint32_t* nscans, const size_t* rooms, int n) {
     JpegDecLayout L;
+    size_t ns = 0, nu = 0;
+    for (int i = 0; i < n; ++i) { ns += nstreams[i]; nu += nscans[i]; }
     L.images = 0;
-    L.tabs = up256(sizeof(DecImage) * (size_t)n);
-    L.streams = up256(L.tabs + sizeof(DecTable) * 8 * (size_t)n);
-    size_t ns = 0;
-    for (int i = 0; i < n; ++i) ns += nstreams[i];
+    L.tabs = up256(sizeof(DecImage) * nu);
+    L.streams = up256(L.tabs + sizeof(DecTable) * 8 * nu);
     // multi-window streams are longer than a window, so a file has at most 8 * stream bytes / kWindowBits of them and twice as many windows
     size_t nc = 0;
     for (int i = 0; i < n; ++i) nc += 8 * rooms[i] / kWindowBits;
@@ -472,78 +604,140 @@ JpegDecLayout jpeg_dec_layout_rooms(const uint32_t* nstreams, const size_t* room
     return L;
 }
 
-JpegDecLayout jpeg_dec_layout(const jpegparse::Header* hd, const size_t* bytes, int n) {
+JpegDecLayout jpeg_dec_layout(const jpegparse::File* f, const size_t* bytes, int n) {
     std::vector<size_t> rooms((size_t)n);
-    std::vector<uint32_t> ns((size_t)n);
-    for (int i = 0; i < n; ++i) { rooms[(size_t)i] = jpegparse::scan_room(hd[i], bytes[i]); ns[(size_t)i] = hd[i].nstreams; }
-    return jpeg_dec_layout_rooms(ns.data(), rooms.data(), n);
+    std::vector<uint32_t> ns((size_t)n), nu((size_t)n);
+    for (int i = 0; i < n; ++i) { rooms[(size_t)i] = jpegparse::file_room(f[i], bytes[i]); ns[(size_t)i] = f[i].nstreams; nu[(size_t)i] = f[i].nscans(); }
+    return jpeg_dec_layout_rooms(ns.data(), nu.data(), rooms.data(), n);
 }
 
 namespace {
-// image i's records into the blob: its streams (cut already: `first`, offsets inside the image's own bytes, which begin b0 bytes into
-// the byte area) ordered long ones first, its image record and tables, and the chains and windows of its multi-window streams
-void pack_image(int i, const jpegparse::Header& hd, DecStream* first, uint32_t s0, size_t b0, const JpegDecLayout& L, uint8_t* blob, JpegDecLayout& out) {
+// One record ("unit": a baseline file, or one scan of a progressive one) into the blob as record u: its streams (cut already: `first`,
+// stream s0 of the batch's table, their offsets moved into the batch's byte area before) with the long ones in front where lanes
+// decode them, its image record and tables, the chains and windows of its multi-window streams, and its share of its level's grids.
+void pack_unit(uint32_t u, uint32_t slot, DecImage im, const DecTable* const* tabs8, DecStream* first, uint32_t nstreams, uint32_t s0, const JpegDecLayout& L, uint8_t* blob,
+               JpegDecLayout& out, JpegDecLevel& lv) {
     DecImage* images = reinterpret_cast<DecImage*>(blob + L.images);
     DecTable* tabs = reinterpret_cast<DecTable*>(blob + L.tabs);
     DecChain* chains = reinterpret_cast<DecChain*>(blob + L.chains);
     DecWindow* windows = reinterpret_cast<DecWindow*>(blob + L.windows);
     const size_t chain_room = (L.windows - L.chains) / sizeof(DecChain), window_room = (L.bytes - L.windows) / sizeof(DecWindow);
     const uint32_t min_windows = out.min_windows;
-    DecStream* mid = std::stable_partition(first, first + hd.nstreams, [](const DecStream& s) { return s.len > kShortMaxBytes; });
-    for (uint32_t k = 0; k < hd.nstreams; ++k) first[k].off += (uint32_t)b0;
-    DecImage im = hd.im;
-    im.first_long = s0; im.nlong = (uint32_t)(mid - first);
-    im.first_short = im.first_long + im.nlong; im.nshort = hd.nstreams - im.nlong;
+    im.slot = slot;
+    im.first_long = s0;
+    if (im.kind >= kScanDcRefine) {                               // no lanes: the streams stay in scan order
+        im.nlong = 0;
+        if (im.kind == kScanDcRefine) lv.dcref_blocks = std::max(lv.dcref_blocks, im.nblocks);
+        else {
+            im.walk0 = lv.walk_blocks; lv.walk_blocks += im.nblocks;
+            lv.ac_blocks = std::max(lv.ac_blocks, im.nblocks); lv.ac_streams = std::max(lv.ac_streams, nstreams);
+            for (uint32_t k = 0; k < nstreams; ++k) (first[k].len > kShortMaxBytes ? lv.ac_long : lv.ac_short) = 1;
+        }
+    } else {
+        DecStream* mid = std::stable_partition(first, first + nstreams, [](const DecStream& s) { return s.len > kShortMaxBytes; });
+        im.nlong = (uint32_t)(mid - first);
+    }
+    im.first_short = im.first_long + im.nlong; im.nshort = nstreams - im.nlong;
     uint32_t k1 = 0;                                              // the last of its long streams that K1 keeps, + 1
     for (uint32_t k = 0; k < im.nlong; ++k) {
         const uint32_t nw = window_count(first[k].len);
         if (!min_windows || nw < std::max(min_windows, 2u)) { k1 = k + 1; continue; }
         if (out.nchain + 1 > chain_room || out.nwin + (size_t)nw > window_room) fail(IRE_ERR_INTERNAL, "internal: the JPEG decoder's window table overflows");
-        chains[out.nchain++] = DecChain{im.first_long + k, (uint32_t)i, out.nwin, nw};
-        for (uint32_t j = 0; j < nw; ++j) windows[out.nwin++] = DecWindow{im.first_long + k, (uint32_t)i, j * kWindowBits};
+        chains[out.nchain++] = DecChain{im.first_long + k, u, out.nwin, nw};
+        for (uint32_t j = 0; j < nw; ++j) windows[out.nwin++] = DecWindow{im.first_long + k, u, j * kWindowBits};
     }
-    out.max_long = std::max(out.max_long, k1); out.max_short = std::max(out.max_short, im.nshort);
-    images[i] = im;
-    std::memcpy(tabs + 8 * (size_t)i, hd.tabs, sizeof(DecTable) * 8);
+    lv.max_long = std::max(lv.max_long, k1);
+    if (im.kind < kScanDcRefine) lv.max_short = std::max(lv.max_short, im.nshort);
+    images[u] = im;
+    for (int k = 0; k < 8; ++k) std::memcpy(tabs + 8 * (size_t)u + k, tabs8[k], sizeof(DecTable));
+}
+
+// the records of n files whose streams lie in the blob's table in file order (image i's from s_img[i] on, their offsets inside the image's
+// own bytes, which begin b_img[i] bytes into the byte area): the first scan of every file in front (records 0 .. n - 1 are the images'
+// own: K3 and K4 read the geometry there), then the other scans by dependency level
+void pack_units(const jpegparse::File* const* f, int n, const uint32_t* s_img, const size_t* b_img, const JpegDecLayout& L, uint8_t* blob, JpegDecLayout& out) {
+    DecStream* streams = reinterpret_cast<DecStream*>(blob + L.streams);
+    struct Ref { uint32_t level, img, scan, s0; };
+    std::vector<Ref> order;
+    uint32_t nlevels = 1;
+    for (int i = 0; i < n; ++i) {
+        order.push_back(Ref{0, (uint32_t)i, 0, s_img[i]});
+        for (uint32_t k = 0; k < f[i]->nstreams; ++k) streams[s_img[i] + k].off += (uint32_t)b_img[i];
+    }
+    for (int i = 0; i < n; ++i) {
+        uint32_t s0 = s_img[i];
+        for (uint32_t k = 0; k < f[i]->nscans(); ++k) {
+            if (k) order.push_back(Ref{f[i]->scans[k].level, (uint32_t)i, k, s0});
+            if (f[i]->progressive) { s0 += f[i]->scans[k].nstreams; nlevels = std::max(nlevels, f[i]->scans[k].level + 1); }
+        }
+    }
+    std::stable_sort(order.begin() + n, order.end(), [](const Ref& a, const Ref& b) { return a.level < b.level; });
+    out.levels.assign(nlevels, JpegDecLevel{});
+    out.nunits = (uint32_t)order.size();
+    out.walk_blocks = 0;
+    if ((size_t)out.nunits * sizeof(DecImage) > L.tabs) fail(IRE_ERR_INTERNAL, "internal: the JPEG decoder's record table overflows");
+    for (uint32_t u = 0; u < out.nunits; ++u) {
+        const Ref& r = order[u];
+        const jpegparse::File& fi = *f[r.img];
+        JpegDecLevel& lv = out.levels[r.level];
+        if (!lv.nunits) { lv.unit0 = u; lv.win0 = out.nwin; lv.chain0 = out.nchain; }
+        ++lv.nunits;
+        const DecTable* t8[8];
+        if (fi.progressive) {
+            const jpegparse::Scan& sc = fi.scans[r.scan];
+            if (fi.pool.empty()) fail(IRE_ERR_INTERNAL, "internal: a progressive file without Huffman tables");
+            for (int k = 0; k < 8; ++k) t8[k] = &fi.pool[std::min<size_t>(sc.tab[k], fi.pool.size() - 1)];
+            pack_unit(u, r.img, sc.im, t8, streams + r.s0, sc.nstreams, r.s0, L, blob, out, lv);
+        } else {
+            for (int k = 0; k < 8; ++k) t8[k] = &fi.hd.tabs[k];
+            pack_unit(u, r.img, fi.hd.im, t8, streams + r.s0, fi.hd.nstreams, r.s0, L, blob, out, lv);
+        }
+        lv.nwin = out.nwin - lv.win0; lv.nchain = out.nchain - lv.chain0;
+        out.walk_blocks = std::max<size_t>(out.walk_blocks, lv.walk_blocks);
+    }
 }
 }  // namespace
 
 // the batch's blob into `blob` (pinned): records, tables, the streams cut and unstuffed.  A file whose scan is refused: Error.
-void jpeg_dec_pack(const uint8_t* const* files, const size_t* bytes, jpegparse::Header* hd, int n, const JpegDecLayout& L, uint8_t* blob, JpegDecLayout& out,
+void jpeg_dec_pack(const uint8_t* const* files, const size_t* bytes, const jpegparse::File* f, int n, const JpegDecLayout& L, uint8_t* blob, JpegDecLayout& out,
                    uint32_t min_windows) {
     out = L;
-    out.max_long = out.max_short = out.nwin = out.nchain = 0;
+    out.nwin = out.nchain = 0;
     out.min_windows = min_windows;
     DecStream* streams = reinterpret_cast<DecStream*>(blob + L.streams);
+    std::vector<uint32_t> s_img((size_t)n);
+    std::vector<size_t> b_img((size_t)n);
+    std::vector<const jpegparse::File*> fp((size_t)n);
     size_t s0 = 0, b0 = 0;
     for (int i = 0; i < n; ++i) {
-        const size_t room = jpegparse::scan_room(hd[i], bytes[i]);
+        const size_t room = jpegparse::file_room(f[i], bytes[i]);
         std::string why;
-        if (!jpegparse::split_scan(hd[i], files[i], bytes[i], blob + L.bytes + b0, room, streams + s0, why)) fail(IRE_ERR_INVALID_INPUT, why);
-        pack_image(i, hd[i], streams + s0, (uint32_t)s0, b0, L, blob, out);
-        hd[i].im = reinterpret_cast<DecImage*>(blob + L.images)[i];
-        s0 += hd[i].nstreams; b0 += up256(room);
+        if (!jpegparse::split_file(f[i], files[i], bytes[i], blob + L.bytes + b0, room, streams + s0, why)) fail(IRE_ERR_INVALID_INPUT, why);
+        s_img[(size_t)i] = (uint32_t)s0; b_img[(size_t)i] = b0; fp[(size_t)i] = f + i;
+        s0 += f[i].nstreams; b0 += up256(room);
     }
+    pack_units(fp.data(), n, s_img.data(), b_img.data(), L, blob, out);
 }
 
-// the same for files whose scans were cut before (jpegparse::split_scan into the caller's own memory): only the records, up to
+// the same for files whose scans were cut before (jpegparse::split_file into the caller's own memory): only the records, up to
 // L.bytes; byte_off[i] says where image i's bytes belong in the byte area (the caller copies them there, rooms[i] at most)
-void jpeg_dec_pack_streams(const jpegparse::Header* const* hd, const DecStream* const* streams_in, const size_t* rooms, int n, const JpegDecLayout& L, uint8_t* blob,
+void jpeg_dec_pack_streams(const jpegparse::File* const* f, const DecStream* const* streams_in, const size_t* rooms, int n, const JpegDecLayout& L, uint8_t* blob,
                            JpegDecLayout& out, size_t* byte_off, uint32_t min_windows) {
     out = L;
-    out.max_long = out.max_short = out.nwin = out.nchain = 0;
+    out.nwin = out.nchain = 0;
     out.min_windows = min_windows;
     DecStream* streams = reinterpret_cast<DecStream*>(blob + L.streams);
+    std::vector<uint32_t> s_img((size_t)n);
     size_t s0 = 0, b0 = 0;
     for (int i = 0; i < n; ++i) {
-        std::copy(streams_in[i], streams_in[i] + hd[i]->nstreams, streams + s0);
-        pack_image(i, *hd[i], streams + s0, (uint32_t)s0, b0, L, blob, out);
-        byte_off[i] = b0;
-        s0 += hd[i]->nstreams; b0 += up256(rooms[i]);
+        std::copy(streams_in[i], streams_in[i] + f[i]->nstreams, streams + s0);
+        s_img[(size_t)i] = (uint32_t)s0; byte_off[i] = b0;
+        s0 += f[i]->nstreams; b0 += up256(rooms[i]);
     }
+    pack_units(f, n, s_img.data(), byte_off, L, blob, out);
 }
 
-void jpeg_dec_launch(const uint8_t* d_blob, const JpegDecLayout& L, int n, int h, int w, uint8_t* d_coef, uint8_t* d_planes, uint8_t* d_lanes, uint8_t* d_rgb,
+void jpeg_dec_launch(const uint8_t* d_blob, const JpegDecLayout& L, int n, int h, int w, uint8_t* d_coef, uint8_t* d_planes, uint8_t* d_lanes, uint8_t* d_walk, uint8_t* d_rgb,
                      size_t image_pitch, int32_t* d_status, hipStream_t s, hipEvent_t* marks) {
     auto mark = [&](int k) { if (marks) IRE_HIP(hipEventRecord(marks[k], s)); };
     DecBatch b;
@@ -560,27 +754,46 @@ void jpeg_dec_launch(const uint8_t* d_blob, const JpegDecLayout& L, int n, int h
     b.recs = reinterpret_cast<LaneRec*>(d_lanes);
     b.heads = reinterpret_cast<WinHead*>(d_lanes + sizeof(LaneRec) * kLanes * (size_t)L.nwin);
     b.min_windows = L.nwin ? std::max(L.min_windows, 2u) : 0;
+    b.masks = reinterpret_cast<uint64_t*>(d_walk);
+    b.wrecs = reinterpret_cast<unsigned*>(d_walk + up256(8 * L.walk_blocks));
     if (L.nwin && !d_lanes) fail(IRE_ERR_INTERNAL, "internal: the JPEG decoder's lane records are missing");
+    if (L.walk_blocks && !d_walk) fail(IRE_ERR_INTERNAL, "internal: the JPEG decoder's walk records are missing");
+    if (L.levels.empty() || L.levels[0].unit0 != 0 || L.levels[0].nunits < (uint32_t)n) fail(IRE_ERR_INTERNAL, "internal: the JPEG decoder's records are out of order");
     mark(0);
     IRE_HIP(hipMemsetAsync(d_coef, 0, jpeg_dec_coef_bytes(n, h, w), s));
     mark(1);
-    if (L.max_long) hipLaunchKernelGGL(jpeg_dec_long_kernel, dim3(L.max_long, n), dim3(kThreads), 0, s, b);
-    mark(2);
-    if (L.nwin) {
-        hipLaunchKernelGGL(jpeg_dec_spec_kernel, dim3(L.nwin), dim3(kThreads), 0, s, b);
-        mark(3);
-        hipLaunchKernelGGL(jpeg_dec_chain_kernel, dim3(L.nchain), dim3(kThreads), 0, s, b);
-        mark(4);
-        hipLaunchKernelGGL(jpeg_dec_write_kernel, dim3(L.nwin), dim3(kThreads), 0, s, b);
-    } else { mark(3); mark(4); }
-    mark(5);
-    if (L.max_short) hipLaunchKernelGGL(jpeg_dec_short_kernel, dim3(std::min<uint32_t>((L.max_short + kThreads - 1) / kThreads, 1024u), n), dim3(kThreads), 0, s, b);
-    mark(6);
+    // One round of launches per dependency level: the scans of a level touch disjoint coefficients.  A batch of baseline files has
+    // one level and in it what lanes decode; the marks between the lanes' launches are those of level 0.
+    for (size_t li = 0; li < L.levels.size(); ++li) {
+        const JpegDecLevel& lv = L.levels[li];
+        if (!lv.nunits) continue;
+        b.unit0 = lv.unit0; b.win0 = lv.win0; b.chain0 = lv.chain0;
+        if (lv.max_long) hipLaunchKernelGGL(jpeg_dec_long_kernel, dim3(lv.max_long, lv.nunits), dim3(kThreads), 0, s, b);
+        if (!li) mark(2);
+        if (lv.nwin) {
+            hipLaunchKernelGGL(jpeg_dec_spec_kernel, dim3(lv.nwin), dim3(kThreads), 0, s, b);
+            if (!li) mark(3);
+            hipLaunchKernelGGL(jpeg_dec_chain_kernel, dim3(lv.nchain), dim3(kThreads), 0, s, b);
+            if (!li) mark(4);
+            hipLaunchKernelGGL(jpeg_dec_write_kernel, dim3(lv.nwin), dim3(kThreads), 0, s, b);
+        } else if (!li) { mark(3); mark(4); }
+        if (!li) mark(5);
+        if (lv.max_short) hipLaunchKernelGGL(jpeg_dec_short_kernel, dim3(std::min<uint32_t>((lv.max_short + kThreads - 1) / kThreads, 1024u), lv.nunits), dim3(kThreads), 0, s, b);
+        if (!li) mark(6);
+        if (lv.dcref_blocks) hipLaunchKernelGGL(jpeg_dec_dcref_kernel, dim3((lv.dcref_blocks + kThreads - 1) / kThreads, lv.nunits), dim3(kThreads), 0, s, b);
+        if (lv.ac_blocks) {
+            hipLaunchKernelGGL(jpeg_dec_mask_kernel, dim3((lv.ac_blocks + kWaves - 1) / kWaves, lv.nunits), dim3(kThreads), 0, s, b);
+            if (lv.ac_short) hipLaunchKernelGGL(jpeg_dec_walk_kernel, dim3((lv.ac_streams + kThreads - 1) / kThreads, lv.nunits), dim3(kThreads), 0, s, b);
+            if (lv.ac_long) hipLaunchKernelGGL(jpeg_dec_walk_long_kernel, dim3(lv.ac_streams, lv.nunits), dim3(64), 0, s, b);
+            hipLaunchKernelGGL(jpeg_dec_apply_kernel, dim3((lv.ac_blocks + kThreads - 1) / kThreads, lv.nunits), dim3(kThreads), 0, s, b);
+        }
+    }
+    mark(7);                                                       // (6 .. 7: every level behind the first, all of a progressive file's refinement)
     hipLaunchKernelGGL(jpeg_dec_idct_kernel, dim3((unsigned)((blocks + kIdctBlocks - 1) / kIdctBlocks), n), dim3(kThreads), 0, s, b, d_planes, (unsigned long long)(blocks * 64));
-    mark(7);
+    mark(8);
     hipLaunchKernelGGL(jpeg_dec_colour_kernel, dim3((unsigned)(((size_t)h * w + kThreads - 1) / kThreads), n), dim3(kThreads), 0, s, b, d_planes, (unsigned long long)(blocks * 64),
                        d_rgb, (unsigned long long)image_pitch, h, w, d_status);
-    mark(8);
+    mark(9);
     IRE_HIP(hipGetLastError());
 }
 

@@ -1,4 +1,5 @@
-// jpeg_dec_core.hpp -- the entropy decoder of a baseline JPEG scan, written once for the device and for the CPU: the records the
+// jpeg_dec_core.hpp -- the entropy decoder of a JPEG scan (baseline, and the four scan kinds of a progressive file), written once
+// for the device and for the CPU: the records the
 // host parser (jpeg_parse.hpp) fills and the kernels (jpeg_dec.hip) read, the two bit readers, the per-symbol step and the
 // per-subsequence loop.  Plain C++17, no HIP header: every function is IRE_HD (__host__ __device__ under hipcc, nothing under g++),
 // so tests/native/jpeg_dec_sim.cpp runs the very code of the kernels with lanes as a loop, under ASan and UBSan.
@@ -58,7 +59,14 @@ struct DecImage {
     uint32_t pw[4], ph[4];                             // per component: the REAL size of its plane in samples
     uint32_t first_long, nlong, first_short, nshort;   // its streams in the batch's stream table: the long ones, then the short ones
     uint16_t quant[4][64];                             // per component, natural order
+    // One scan of a progressive file is a record of its own (a "unit"): the frame's geometry, the scan's own MCU (bpm, comp_of, bx,
+    // by), its table numbers, and what follows.  A baseline file's one record has all of it 0.
+    uint8_t kind, ss, se, al;                          // kScan*; the band in zig-zag positions; the bit position the scan leaves
+    uint32_t slot;                                     // the image of the batch whose coefficients and status word this record writes
+    uint32_t raster, rw, rh;                           // 1: a scan of ONE component walks the rw x rh blocks of its REAL plane in raster order
+    uint32_t walk0;                                    // an AC refinement scan: its first block in the mask and walk-record scratch
 };
+constexpr int kScanBaseline = 0, kScanDcFirst = 1, kScanAcFirst = 2, kScanDcRefine = 3, kScanAcRefine = 4;
 struct DecStream {
     uint32_t off, len;                                 // its bytes (stuffing removed) in the batch's byte area; off is a multiple of 4
     uint32_t mcu0, nmcu;                               // its first MCU and its MCU count
@@ -114,6 +122,10 @@ IRE_HD int extend_from(uint32_t w, uint32_t nb, uint32_t s) {
 
 // where block g (scan order) of the image lies in the coefficient scratch, in int16 units
 IRE_HD uint32_t block_base(const DecImage& im, uint32_t g) {
+    if (im.raster) {
+        const uint32_t c = im.comp_of[0] & 3u, y = g / im.rw, x = g - y * im.rw;
+        return (im.coef_off[c] + y * im.gridw[c] + x) * 64u;
+    }
     const uint32_t mcu = g / im.bpm, j = g - mcu * im.bpm, c = im.comp_of[j];
     const uint32_t my = mcu / im.mcus_w, mx = mcu - my * im.mcus_w;
     return (im.coef_off[c] + (my * im.vs[c] + im.by[j]) * im.gridw[c] + mx * im.hs[c] + im.bx[j]) * 64u;
@@ -126,9 +138,15 @@ IRE_HD uint32_t block_base(const DecImage& im, uint32_t g) {
 // well-formed stream never takes these branches, so its states are those of the strict step. -----------------------------------------
 constexpr int kSymNone = 0, kSymDc = 1, kSymAc = 2, kSymErr = 3, kBlockDone = 4;
 // t: the table of this symbol (the block's DC table when st.k == 0, else its AC table); bpm: blocks per MCU
+// The first scans of a progressive file take the same step (T.81 G.1.2).  A DC first scan: the block ends behind its DC symbol.  An
+// AC first scan: positions ss..se (st.k == 0 stands for ss: every block begins so, in every kind); EOBn ends this block and the next
+// `run` - 1, all counted at the moment the symbol is read -- the bit position is never inside a run, so the streams synchronise as
+// baseline ones do.  run: blocks completed by this step when kBlockDone is set.
 template <class R>
-IRE_HD int dec_step(const R& rd, const DecTable& t, uint32_t bpm, DecState& st, bool soft, int& val, uint32_t& pos, uint32_t& err) {
+IRE_HD int dec_step_scan(const R& rd, const DecTable& t, uint32_t bpm, int skind, uint32_t ss, uint32_t se, DecState& st, bool soft, int& val, uint32_t& pos,
+                         uint32_t& err, uint32_t& run) {
     const uint32_t w = rd.peek(st.p);
+    run = 1;
     const uint32_t e = t.look[w >> 23];
     uint32_t nb, sym;
     if (e) { nb = e >> 8; sym = e & 255u; }
@@ -142,28 +160,38 @@ IRE_HD int dec_step(const R& rd, const DecTable& t, uint32_t bpm, DecState& st, 
         sym = t.vals[(uint32_t)(t.valoff[nb] + (int32_t)(w >> (32u - nb))) & 255u];
     }
     int kind = kSymNone;
-    if (st.k == 0) {
+    if (st.k == 0 && skind != kScanAcFirst) {
         if (sym > 11) {
             if (!soft) { err |= kStBadDc; return kSymErr; }
             sym &= 15u;
         }
         val = extend_from(w, nb, sym); pos = 0;
-        st.p += nb + sym; st.k = 1; kind = kSymDc;
+        st.p += nb + sym; st.k = skind == kScanDcFirst ? 64u : 1u; kind = kSymDc;
     } else {
         const uint32_t r = sym >> 4, s = sym & 15u;
+        if (st.k == 0) st.k = ss;
         st.p += nb + s;
         if (s == 0) {
-            if (r == 15) { st.k += 16; if (st.k > 63 && !soft) { err |= kStBadIndex; return kSymErr; } }      // ZRL: a coefficient must follow
-            else st.k = 64;                                                                          // end of block
+            if (r == 15) { st.k += 16; if (st.k > se && !soft) { err |= kStBadIndex; return kSymErr; } }      // ZRL: a coefficient must follow
+            else {                                                                                   // end of block, or of `run` blocks
+                if (skind == kScanAcFirst && r) { run = (1u << r) + ((w << nb) >> (32u - r)); st.p += r; }
+                st.k = 64;
+            }
         } else {
             st.k += r;
-            if (st.k > 63 && !soft) { err |= kStBadIndex; return kSymErr; }
+            if (st.k > se && !soft) { err |= kStBadIndex; return kSymErr; }
             val = extend_from(w, nb, s); pos = st.k & 63u;
             st.k += 1; kind = kSymAc;
         }
+        if (st.k > se) st.k = 64;
     }
     if (st.k >= 64) { st.k = 0; st.blk = st.blk + 1 >= bpm ? 0 : st.blk + 1; kind |= kBlockDone; }
     return kind;
+}
+template <class R>
+IRE_HD int dec_step(const R& rd, const DecTable& t, uint32_t bpm, DecState& st, bool soft, int& val, uint32_t& pos, uint32_t& err) {
+    uint32_t run;
+    return dec_step_scan(rd, t, bpm, kScanBaseline, 0u, 63u, st, soft, val, pos, err, run);
 }
 
 // ---- the per-subsequence loop: every symbol that begins before bit `lim`, at most max_blocks completed blocks.  coef == null:
@@ -176,7 +204,8 @@ IRE_HD uint32_t dec_subseq(const R& rd, const DecTable* tabs, const DecImage& im
                            uint32_t* dcpred, LaneOut& o) {
     o.nblk = 0; o.dc[0] = o.dc[1] = o.dc[2] = 0;
     uint32_t err = 0;
-    const uint32_t bpm = im.bpm;
+    const uint32_t bpm = im.bpm, ss = im.kind == kScanAcFirst ? im.ss : 1u, se = im.kind == kScanAcFirst ? im.se : 63u, al = im.al;
+    const int skind = im.kind;
     const bool soft = coef == nullptr;
     uint32_t base = coef && max_blocks ? block_base(im, gblk) : 0;
     uint32_t c = im.comp_of[st.blk & 7u] & 3u;
@@ -184,18 +213,20 @@ IRE_HD uint32_t dec_subseq(const R& rd, const DecTable* tabs, const DecImage& im
     while (st.p < lim && o.nblk < max_blocks) {
         int val = 0;
         uint32_t pos = 0;
-        const int r = dec_step(rd, st.k == 0 ? *tdc : *tac, bpm, st, soft, val, pos, err);
+        uint32_t run;
+        const int r = dec_step_scan(rd, st.k == 0 && skind != kScanAcFirst ? *tdc : *tac, bpm, skind, ss, se, st, soft, val, pos, err, run);
         if ((r & 3) == kSymErr) { st.p = kBadPos; break; }
+        if (run > max_blocks - o.nblk) { err |= kStBadEnd; st.p = kBadPos; break; }          // an EOB run that overshoots the stream's blocks
         if ((r & 3) == kSymDc) {
             const uint32_t v = (uint32_t)val;
             o.dc[0] += c == 0 ? v : 0u; o.dc[1] += c == 1 ? v : 0u; o.dc[2] += c == 2 ? v : 0u;
             if (coef) {
                 dcpred[0] += c == 0 ? v : 0u; dcpred[1] += c == 1 ? v : 0u; dcpred[2] += c == 2 ? v : 0u;
-                coef[base] = (int16_t)(c == 0 ? dcpred[0] : c == 1 ? dcpred[1] : dcpred[2]);
+                coef[base] = (int16_t)((c == 0 ? dcpred[0] : c == 1 ? dcpred[1] : dcpred[2]) << al);
             }
-        } else if ((r & 3) == kSymAc && coef) coef[base + natural_of(pos)] = (int16_t)val;
+        } else if ((r & 3) == kSymAc && coef) coef[base + natural_of(pos)] = (int16_t)((uint32_t)val << al);
         if (r & kBlockDone) {
-            ++o.nblk; ++gblk;
+            o.nblk += run; gblk += run;
             if (coef && o.nblk < max_blocks) base = block_base(im, gblk);
             c = im.comp_of[st.blk & 7u] & 3u;
             tdc = tabs + (im.dc_tab[c] & 3u); tac = tabs + 4u + (im.ac_tab[c] & 3u);
@@ -206,6 +237,146 @@ IRE_HD uint32_t dec_subseq(const R& rd, const DecTable* tabs, const DecImage& im
 
 // what must hold when a stream's last block is done at bit p: its last byte has begun (the rest of it is padding)
 IRE_HD bool stream_end_ok(uint32_t p, uint32_t len) { return p != kBadPos && p <= 8u * len && 8u * len - p < 8u; }
+
+// ---- the refinement scans of a progressive file (T.81 G.1.2.3; libjpeg's jdphuff.c) ----------------------------------------------------
+// A DC refinement scan has no code at all: bit n of a stream is block n of that stream, OR-ed into coefficient 0 at bit al.
+//
+// An AC refinement scan: behind every symbol the decoder walks the band and reads one correction bit for each coefficient that was
+// non-zero BEFORE this scan (one placed in this scan is never met again in it), so the bits a block takes depend on the blocks in
+// front of it and no lane can guess a position.  But they depend on the non-zero PATTERN alone.  So: a mask per block (64 bits in
+// zig-zag order, limited to the band: jpeg_dec_mask_kernel); a serial walk per stream over symbols and masks that touches no
+// coefficient and records where each block's bits begin (refine_walk_stream); then every block by itself (refine_apply_block).
+constexpr uint32_t kRecInRun = 0x80000000u;            // a walk record: the block lies inside an EOB run (bits 0..30: its first bit; kBadPos: none)
+struct RefState { uint32_t p, eobrun, k; };            // bit position | blocks the current EOB run still covers | zig-zag position (0: a block begins)
+
+IRE_HD uint64_t band_bits(uint32_t ss, uint32_t se) { return (~0ull << (ss & 63u)) & (~0ull >> (63u - (se & 63u))); }
+IRE_HD uint32_t popc64(uint64_t v) { return (uint32_t)__builtin_popcountll(v); }
+IRE_HD uint32_t ctz64(uint64_t v) { return (uint32_t)__builtin_ctzll(v); }
+
+// the code at the front of w -> its length and symbol; false: no table holds it
+IRE_HD bool huff_symbol(const DecTable& t, uint32_t w, uint32_t& nb, uint32_t& sym) {
+    const uint32_t e = t.look[w >> 23];
+    if (e) { nb = e >> 8; sym = e & 255u; return true; }
+    nb = 10;
+    while (nb <= 16 && (int32_t)(w >> (32u - nb)) > t.maxcode[nb]) ++nb;
+    if (nb > 16) return false;
+    sym = t.vals[(uint32_t)(t.valoff[nb] + (int32_t)(w >> (32u - nb))) & 255u];
+    return true;
+}
+// behind a symbol (r, s) read at position k: the (r + 1)-th coefficient at or behind k that is still zero -- where s is placed, or
+// the last of the 16 a ZRL skips.  64: the band ends first
+IRE_HD uint32_t refine_target(uint64_t mask, uint64_t band, uint32_t k, uint32_t r) {
+    uint64_t z = ~mask & band & (~0ull << k);
+    for (uint32_t i = 0; i < r; ++i) z &= z - 1;
+    return z ? ctz64(z) : 64u;
+}
+
+// One step of the walk: a whole block inside an EOB run, or one symbol and what follows it.  done: the block ended.  -> error bits.
+// Reads the 32 bits at st.p and no others (the correction bits are only counted).
+template <class R>
+IRE_HD uint32_t refine_walk_step(const R& rd, const DecTable& t, uint32_t ss, uint32_t se, uint64_t mask, RefState& st, bool& done) {
+    done = true;
+    if (st.k == 0 && st.eobrun) { st.p += popc64(mask); --st.eobrun; return 0; }
+    const uint32_t k = st.k ? st.k : ss;
+    const uint32_t w = rd.peek(st.p);
+    uint32_t nb, sym;
+    if (!huff_symbol(t, w, nb, sym)) return kStBadCode;
+    const uint32_t r = sym >> 4, s = sym & 15u;
+    st.p += nb;
+    st.k = 0;
+    if (s) {
+        if (s != 1) return kStBadCode;                              // (libjpeg warns and goes on; here the image is flagged)
+        st.p += 1;                                                  // the sign
+    } else if (r != 15) {                                           // EOBr: the rest of this block, and run - 1 blocks behind it
+        uint32_t run = 1u << r;
+        if (r) { run += (w << nb) >> (32u - r); st.p += r; }
+        st.eobrun = run - 1;
+        st.p += popc64(mask & (~0ull << k));
+        return 0;
+    }
+    const uint32_t k2 = refine_target(mask, band_bits(ss, se), k, r);
+    if (k2 > se) return kStBadIndex;                                // the run leaves the band
+    st.p += popc64(mask & (~0ull << k) & ~(~0ull << k2));
+    if (k2 < se) { st.k = k2 + 1; done = false; }
+    return 0;
+}
+
+// The walk over blocks n .. nend - 1 of a stream while the 32 bits at st.p lie below bit `lim` (what the caller staged; 0xffffffff:
+// all of it): masks[j] and recs[j] belong to block first + j.  A block's record is written when it begins.  -> error bits; n, st
+// advanced.  total_bits < 2^31: a position beyond the stream's end is an error, so a record never reaches kBadPos.
+template <class R>
+IRE_HD uint32_t refine_walk_some(const R& rd, const DecTable& t, uint32_t ss, uint32_t se, const uint64_t* masks, uint32_t* recs, uint32_t first, uint32_t nend,
+                                 uint32_t lim, uint32_t total_bits, RefState& st, uint32_t& n) {
+    while (n < nend && (lim == 0xffffffffu || st.p + 32u <= lim)) {
+        if (st.k == 0) recs[n - first] = st.p | (st.eobrun ? kRecInRun : 0u);
+        bool done;
+        const uint32_t err = refine_walk_step(rd, t, ss, se, masks[n - first], st, done);
+        if (err) return err;
+        if (st.p > total_bits) return kStBadEnd;
+        if (done) ++n;
+    }
+    return 0;
+}
+// what must hold behind a stream's last block
+IRE_HD uint32_t refine_walk_end(const RefState& st, uint32_t len) { return st.eobrun || !stream_end_ok(st.p, len) ? (uint32_t)kStBadEnd : 0u; }      // (an EOB run that overshoots the stream's blocks)
+
+// a whole stream of nblk blocks by one lane: masks[n] -> recs[n].  -> error bits; behind an error every record is kBadPos.
+template <class R>
+IRE_HD uint32_t refine_walk_stream(const R& rd, const DecTable& t, uint32_t ss, uint32_t se, const uint64_t* masks, uint32_t* recs, uint32_t nblk, uint32_t len) {
+    RefState st{0, 0, 0};
+    uint32_t n = 0;
+    uint32_t err = refine_walk_some(rd, t, ss, se, masks, recs, 0, nblk, 0xffffffffu, 8u * len, st, n);
+    if (err) for (uint32_t j = n + 1; j < nblk; ++j) recs[j] = kBadPos;
+    return err ? err : refine_walk_end(st, len);
+}
+// The same by a wave (jpeg_dec_walk_long_kernel; tests/native/jpeg_prog_sim.cpp as a loop): the walking lane must not wait for a load
+// per block or per symbol, so the other lanes stage kWalkBlocks masks and kWalkWords stream words (WordReader's layout) in front of it,
+// and the records leave kWalkBlocks at a time.
+constexpr unsigned kWalkBlocks = 64;
+constexpr unsigned kWalkWords = 256;                   // staged per turn: the walk stops when fewer than 32 bits of them are left
+constexpr unsigned kWalkStageWords = kWalkWords + 1;   // (+ WordReader's second word)
+constexpr unsigned kWalkStagePadded = kWalkStageWords + kWalkStageWords / 32 + 1;
+
+// the correction bits from bit p on for the coefficients of m (zig-zag bits, all non-zero before this scan) -> the bit behind them
+template <class R>
+IRE_HD uint32_t refine_correct(const R& rd, uint64_t m, uint32_t p, int p1, int16_t* blk) {
+    while (m) {
+        const uint32_t k = ctz64(m);
+        m &= m - 1;
+        if (rd.peek(p) >> 31) {
+            int16_t& c = blk[natural_of(k)];
+            if (!(c & p1)) c = (int16_t)(c >= 0 ? c + p1 : c - p1);
+        }
+        ++p;
+    }
+    return p;
+}
+// one block from its walk record: its symbols again, the corrections applied, the new coefficients placed.  blk: its 64 coefficients.
+// The walk met every error this could meet and turned the record into kBadPos, so a code it cannot read only ends the block.
+template <class R>
+IRE_HD void refine_apply_block(const R& rd, const DecTable& t, uint32_t ss, uint32_t se, uint32_t al, uint64_t mask, uint32_t rec, int16_t* blk) {
+    if (rec == kBadPos) return;
+    const int p1 = 1 << al;
+    uint32_t p = rec & ~kRecInRun;
+    if (rec & kRecInRun) { refine_correct(rd, mask, p, p1, blk); return; }
+    const uint64_t band = band_bits(ss, se);
+    uint32_t k = ss;
+    while (k <= se) {
+        const uint32_t w = rd.peek(p);
+        uint32_t nb, sym;
+        if (!huff_symbol(t, w, nb, sym)) return;
+        const uint32_t r = sym >> 4, s = sym & 15u;
+        p += nb;
+        int v = 0;
+        if (s) { v = (rd.peek(p) >> 31) ? p1 : -p1; p += 1; }
+        else if (r != 15) { refine_correct(rd, mask & (~0ull << k), p + r, p1, blk); return; }
+        const uint32_t k2 = refine_target(mask, band, k, r);
+        if (k2 > se) return;
+        p = refine_correct(rd, mask & (~0ull << k) & ~(~0ull << k2), p, p1, blk);
+        if (s) blk[natural_of(k2)] = (int16_t)v;
+        k = k2 + 1;
+    }
+}
 
 // ---- long streams of several windows, decoded window-parallel in three passes (jpeg_dec.hip: spec / chain / write kernels) ------------
 // The only serial link between two windows of a stream is the state at which the second one is entered.  Pass A guesses it -- every

@@ -31,13 +31,13 @@ def _ptr(a):
 
 def _jpeg_frame_size(data):
     """(h, w) from the frame header of a JPEG file the engine has just accepted (ire_submit_jpeg parsed it: the segments are
-    well-formed and a baseline frame exists), without walking the file a second time: poll() sizes its buffer from them."""
+    well-formed and a baseline or progressive frame exists), without walking the file a second time: poll() sizes its buffer from them."""
     i = 2
     while True:
         while data[i] == 0xFF:
             i += 1
         marker, n = data[i], int.from_bytes(data[i + 1:i + 3], "big")
-        if marker in (0xC0, 0xC1):
+        if marker in (0xC0, 0xC1, 0xC2):
             return int.from_bytes(data[i + 4:i + 6], "big"), int.from_bytes(data[i + 6:i + 8], "big")
         i += 1 + n
 
@@ -206,7 +206,8 @@ class Engine:
         return (job, h, w)
 
     def submit_jpeg(self, data, scores=None):
-        """submit_fit() for an encoded upload: the bytes of a baseline JPEG file that decode_jpeg_plan accepts.  The file is parsed in
+        """submit_fit() for an encoded upload: the bytes of a JPEG file that decode_jpeg_plan accepts (baseline; on an engine created with
+        IRE_FLAG_DECODE_PROGRESSIVE progressive too).  The file is parsed in
         this call and decoded on the device with its batch; the result is that of submit_fit(its pixels, is_jpeg=True, scores).
         Raises EngineError (invalid input, the plan's reason) for a file out of scope: no job exists then.  A file with corrupt data
         fails at its poll."""
@@ -337,14 +338,20 @@ class Engine:
                                                                 self._stream_ptr(stream)))
         return out[:, :cb], lens
 
-    # ---- baseline JPEG uploads decoded on the device (csrc/jpeg_parse.hpp, csrc/jpeg_dec.hip) ----------------------------------
+    # ---- JPEG uploads decoded on the device (csrc/jpeg_parse.hpp, csrc/jpeg_dec.hip) -------------------------------------------
+    @property
+    def decode_accept(self):
+        """what this engine's decoder takes beside baseline files: IRE_DECODE_ACCEPT_PROGRESSIVE when it was created with
+        IRE_FLAG_DECODE_PROGRESSIVE, else 0"""
+        return _lib.IRE_DECODE_ACCEPT_PROGRESSIVE if getattr(self, "_flags", 0) & _lib.IRE_FLAG_DECODE_PROGRESSIVE else 0
+
     def decode_jpeg_plan_reason(self, data):
-        """bytes of a file -> ((h, w, sampling), None) when the device decodes it (sampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0,
+        """bytes of a file -> ((h, w, sampling), None) when THIS engine's device decodes it (sampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0,
         3 = grey), else (None, reason) with the reason the C side gives ("invalid: progressive JPEG ...").  Pure host arithmetic;
         nothing is kept on the engine, so any number of threads may ask (ire_last_error is per thread)."""
         data = bytes(data)
-        h, w, s = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        if self._lib.ire_decode_jpeg_plan(data, len(data), ctypes.byref(h), ctypes.byref(w), ctypes.byref(s)) != 0:
+        h, w, s, k = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        if self._lib.ire_decode_jpeg_plan_ex(data, len(data), self.decode_accept, ctypes.byref(h), ctypes.byref(w), ctypes.byref(s), ctypes.byref(k)) != 0:
             return None, (self._lib.ire_last_error() or b"").decode()
         return (h.value, w.value, s.value), None
 
@@ -357,7 +364,7 @@ class Engine:
         return plan
 
     def decode_jpeg(self, data):
-        """bytes of a baseline JPEG file the plan accepts -> [h,w,3] uint8, equal to PIL.Image.open(f).convert("RGB"); raises
+        """bytes of a JPEG file the plan accepts -> [h,w,3] uint8, equal to PIL.Image.open(f).convert("RGB"); raises
         EngineError (invalid input) for a file out of scope or with corrupt data.  The plan runs here (the output's size comes from
         it): a caller need not ask first."""
         data = bytes(data)

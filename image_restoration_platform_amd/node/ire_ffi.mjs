@@ -49,6 +49,8 @@ export function bindIre(libPath) {
     ire_encode_jpeg_base64_fit_device: ['int', [P, P, 'int', 'int', 'int', 'size_t', 'size_t', P, 'size_t', P, P]],
     ire_encode_jpeg_base64_fit: ['int', [P, P, 'int', 'int', 'int', P, 'size_t', P]],
     ire_decode_jpeg_plan: ['int', [P, 'size_t', P, P, P]],
+    // (accept is a uint32_t of flag bits, 0 or 1 today: passed as an int)
+    ire_decode_jpeg_plan_ex: ['int', [P, 'size_t', 'int', P, P, P, P]],
     ire_decode_jpeg: ['int', [P, P, 'size_t', P, 'int', 'int']],
     ire_decode_jpeg_device: ['int', [P, P, P, 'int', 'int', 'int', P, 'size_t', P, P]],
     ire_job_release: ['int', [P, P]],

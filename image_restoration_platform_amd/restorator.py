@@ -38,9 +38,10 @@ def _now_ms():
 
 # How an upload becomes pixels (IRE_UPLOAD_CODEC, read at each call):
 #   unset        host PIL (libjpeg-turbo, libpng, ...): every format, ~5.6 ms of one core per 1024^2 JPEG -- the default
-#   jpeg-device  a baseline JPEG the engine's plan accepts (csrc/jpeg_parse.hpp) is decoded on the GPU (csrc/jpeg_dec.hip) to the
-#                very bytes PIL gives; every other file -- progressive, CMYK, PNG, WebP, one the device flags as corrupt -- goes
-#                to PIL exactly as above.  A single upload that reaches restore_image undecoded becomes a file job of the engine's
+#   jpeg-device  a JPEG the engine's plan accepts (csrc/jpeg_parse.hpp: baseline; progressive too on an engine created with
+#                IRE_FLAG_DECODE_PROGRESSIVE) is decoded on the GPU (csrc/jpeg_dec.hip) to the very bytes PIL gives; every other
+#                file -- progressive on an engine without that flag, CMYK, PNG, WebP, one the device flags as corrupt -- goes to
+#                PIL exactly as above.  A single upload that reaches restore_image undecoded becomes a file job of the engine's
 #                batcher (ire_submit_jpeg): decoded with its batch, eight uploads a time
 UPLOAD_DECODES = {"device": 0, "host": 0}      # which way the uploads of this process went
 

@@ -88,6 +88,11 @@ typedef struct ire_config {
  * imagePreprocess.js:57-64; ire_encode_jpeg_base64_fit_device below).  The text's length depends on the pixels: such results are
  * fetched with ire_poll_text, into a buffer of ire_jpeg_base64_bound(h, w) bytes.  At most one result flag may be set. */
 #define IRE_FLAG_RESULT_JPEG 8u
+/* Not a result format, and free to combine with one: ire_decode_jpeg, ire_decode_jpeg_device and ire_submit_jpeg accept PROGRESSIVE
+ * JPEG files (ire_decode_jpeg_plan_ex with IRE_DECODE_ACCEPT_PROGRESSIVE) beside baseline ones, in one batch where their planned
+ * sizes are equal.  Without it such a file is refused as before and stays with the host codec.  (Bit value 16 stays unknown, as 2
+ * does: tests/test_jpeg_model.py holds it to that.) */
+#define IRE_FLAG_DECODE_PROGRESSIVE 32u
 
 
 
@@ -246,6 +251,20 @@ int ire_encode_jpeg_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, 
  * reuses; uploads are ordered behind the kernels of the call before them, so a caller that runs three calls ahead of the device waits
  * for those kernels -- never for the kernels of the call directly before it, nor for its own. */
 int ire_decode_jpeg_plan(const uint8_t* file, size_t bytes, int* out_h, int* out_w, int* out_sampling);
+/* ire_decode_jpeg_plan with a choice of what is accepted (pure host, no engine).  accept == 0: ire_decode_jpeg_plan itself, status
+ * and reason.  IRE_DECODE_ACCEPT_PROGRESSIVE: beside those files a progressive one (SOF2, Huffman-coded, 8-bit; the colour, sampling
+ * and size rules above unchanged) with any scan script that T.81 Annex G allows -- DC scans with Ss = Se = 0, interleaved or not; AC
+ * scans of one component with 1 <= Ss <= Se <= 63; Ah = 0 in a coefficient's first scan, else Ah = the Al its last scan left and
+ * Al = Ah - 1; no AC scan of a component before its first DC scan -- and that is COMPLETE: every coefficient of every component ends
+ * at Al = 0 (libjpeg smooths the blocks of an incomplete file; the device does not, so such a file stays with the host codec).
+ * Huffman tables and restart intervals may change between scans; a DQT behind the first scan, more than IRE_DECODE_MAX_SCANS scans and
+ * everything ire_decode_jpeg_plan refuses are refused ("invalid: progressive JPEG ...").  *out_nscans: the file's scans, 1 for a
+ * baseline file.  An engine created with IRE_FLAG_DECODE_PROGRESSIVE decodes what this accepts; in corrupt entropy-coded data it may
+ * flag what libjpeg only warns about (a refinement symbol of size > 1, a run that leaves its band, an end-of-band run longer than
+ * its stream). */
+#define IRE_DECODE_ACCEPT_PROGRESSIVE 1u
+#define IRE_DECODE_MAX_SCANS 64
+int ire_decode_jpeg_plan_ex(const uint8_t* file, size_t bytes, uint32_t accept, int* out_h, int* out_w, int* out_sampling, int* out_nscans);
 int ire_decode_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, uint8_t* out_rgb /* h*w*3 */, int h, int w);
 int ire_decode_jpeg_device(ire_engine* e, const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb,
                            size_t image_pitch_bytes, int32_t* d_status /* n x int32, device */, void* stream);
@@ -260,7 +279,9 @@ int ire_submit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg, con
  * their exact (h, w), polled with ire_poll and released with ire_job_release.  With IRE_FLAG_RESULT_PNG_BASE64 ire_poll
  * delivers ire_png_base64_bytes_fit(h, w) characters: the PNG of the h x w result. */
 int ire_submit_fit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg, const double* scores, ire_job** job_out);
-/* ire_submit_fit for an ENCODED upload: `file` is a baseline JPEG file that ire_decode_jpeg_plan accepts; the job's result is that
+/* ire_submit_fit for an ENCODED upload: `file` is a JPEG file that ire_decode_jpeg_plan accepts (on an engine with
+ * IRE_FLAG_DECODE_PROGRESSIVE: that ire_decode_jpeg_plan_ex accepts with IRE_DECODE_ACCEPT_PROGRESSIVE; the room rule below then counts
+ * the data of all its scans); the job's result is that
  * of ire_submit_fit(the file's decoded pixels, h, w, is_jpeg = 1, scores) with h, w as the plan reports them (the caller sizes its
  * ire_poll / ire_poll_text buffer from the plan).  The file's head is parsed and its scan is cut in the calling thread, before
  * return (the file may be freed then); the decode runs on the device with the job's batch.  File jobs are coalesced by their planned

@@ -13,7 +13,11 @@ one with IRE_JPEG_DEC_WINDOWS=0 (every long stream walked by one workgroup: the 
 ones) and one with the default, their batches of 8 and their one-file calls ALTERNATED rep by rep; per-launch times of both; the
 chain pass's re-decodes per window (tests/native/jpeg_dec_win_sim.cpp); host PIL in the same run.
 `jpeg_decode_measure.py rate`: 64 jobs in flight of 1024^2 Pillow q85 4:4:4 files, submit_jpeg img/s against submit_fit fed by PIL
-decodes on 1 and on 8 threads, alternated, 5 rounds of 192 jobs each."""
+decodes on 1 and on 8 threads, alternated, 5 rounds of 192 jobs each.
+`jpeg_decode_measure.py progressive`: the eight images as Pillow's PROGRESSIVE q85 files (4:4:4 and 4:2:0; libjpeg's simple progression,
+10 scans -- Pillow writes no mozjpeg script) beside the baseline files of the same coefficients, on one engine created with
+IRE_FLAG_DECODE_PROGRESSIVE: batches of 8 and one-file calls, the per-launch times (the `later_scans` key holds everything behind the
+first level's lanes), host PIL on the same files."""
 import base64, io, json, os, statistics, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -83,15 +87,15 @@ def single_entry(eng, files):
     return spread(per)
 
 
-def kernel_times(files):
+def kernel_times(files, flags=0):
     """a child process with IRE_JPEG_DEC_TIMES=1: the engine prints its per-launch sums when it closes"""
     code = ("import sys, pickle; sys.path.insert(0, %r)\n"
             "from image_restoration_platform_amd.engine import Engine\n"
             "import torch\n"
             "files = pickle.load(open(sys.argv[1], 'rb'))\n"
-            "e = Engine(max_batch=8, weights_path=None)\n"
+            "e = Engine(max_batch=8, weights_path=None, flags=%d)\n"
             "for _ in range(%d): e.decode_jpeg_device(files)\n"
-            "torch.cuda.synchronize(); e.close()\n") % (ROOT, WARM + REPS)
+            "torch.cuda.synchronize(); e.close()\n") % (ROOT, flags, WARM + REPS)
     import pickle
     with tempfile.NamedTemporaryFile(suffix=".pkl", delete=False) as f:
         pickle.dump(files, f)
@@ -263,6 +267,34 @@ def run_rate():
     print(json.dumps(out))
 
 
+def run_progressive():
+    from PIL import ImageFile
+    from image_restoration_platform_amd import _lib
+    flag = _lib.IRE_FLAG_DECODE_PROGRESSIVE
+    eng = Engine(max_batch=8, weights_path=None, flags=flag)
+    px = np.ascontiguousarray(synth.batch(8, 1024, 1024))
+
+    def prog(p, sub):
+        bio = io.BytesIO()
+        old, ImageFile.MAXBLOCK = ImageFile.MAXBLOCK, 1 << 24          # (large scans: "Suspension not allowed here" otherwise)
+        try:
+            Image.fromarray(p, "RGB").save(bio, format="JPEG", quality=85, subsampling=sub, progressive=True)
+        finally:
+            ImageFile.MAXBLOCK = old
+        return bio.getvalue()
+    sets = {"progressive_q85_444": [prog(p, 0) for p in px], "baseline_q85_444": [pillow(p, 0) for p in px],
+            "progressive_q85_420": [prog(p, 2) for p in px], "baseline_q85_420": [pillow(p, 2) for p in px]}
+    out = {"device": torch.cuda.get_device_name(0), "reps": REPS, "warmup": WARM}
+    for name, files in sets.items():
+        out[name] = {"host_pil_per_image": host_decode(files), "device": device_decode(eng, files), "device_single_entry_per_image": single_entry(eng, files),
+                     "kernels": kernel_times(files, flag)}
+    eng.close()
+    print(json.dumps(out))
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "progressive":
+    run_progressive()
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "windows":
     run_windows()
     sys.exit(0)

@@ -76,6 +76,8 @@ SYMBOLS = {
     "ire_submit_fit": (_i, [_vp, _u8p, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
     "ire_submit_jpeg": (_i, [_vp, _u8p, ctypes.c_size_t, _vp, ctypes.POINTER(_vp)]),
     "ire_submit": (_i, [_vp, _u8p, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
+    "ire_submit_fuse_fit": (_i, [_vp, _vp, _i, _i, _i, _u8p, _u8p, _vp, ctypes.POINTER(_vp)]),
+    "ire_restore_fuse_fit_device": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ire_restore_tiled_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ire_strips_stats_bytes": (ctypes.c_size_t, [_i, _i]),
     "ire_strips_open": (_i, [_vp, _i, _i, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
@@ -94,6 +96,7 @@ SYMBOLS = {
                                ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "ire_engine_affinity": (_i, [_vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]),
     "ire_debug_classifier_sums": (_i, [_vp, _i, _vp]),
+    "ire_debug_fusion_wlut": (_i, [_vp, _vp, _i, _vp]),
     "ire_debug_capture": (_i, [_vp, _i]),
     "ire_debug_activation": (_i, [_vp, ctypes.c_char_p, _vp, ctypes.POINTER(ctypes.c_size_t)]),
     "ire_profile_enable": (_i, [_vp, _i]),

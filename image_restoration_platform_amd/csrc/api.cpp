@@ -110,6 +110,7 @@ static void bind_this_thread(const CpuPlan& p) {
     (void)pthread_setaffinity_np(pthread_self(), sizeof(set), &set);      // (a cpuset that excludes them all: EINVAL, the thread stays where it was)
 }
 
+static_assert(kGroupMaxJobs == kFuseMaxSets, "a full fusion slot must be one fused launch");
 struct HipBatchBackend {
     Engine& E;
     int device;
@@ -213,10 +214,14 @@ struct HipBatchBackend {
         hs.file_jobs = 0;
         IRE_HIP(hipMemcpyAsync(hs.d_in.get<uint8_t>() + off, b.pin_in + off, bytes, hipMemcpyHostToDevice, cs));
     }
-    void launch(SlotBufs& b, int n, int h, int w, const uint8_t* has_sc) {
+    void launch(SlotBufs& b, int n, int h, int w, const uint8_t* has_sc) { launch_jobs(b, n, 0, h, w, has_sc); }
+    // the batcher's optional hook: n fusion jobs of k views each, one fused result per job
+    void launch_group(SlotBufs& b, int n, int k, int h, int w, const uint8_t* has_sc) { launch_jobs(b, n, k, h, w, has_sc); }
+    // n jobs of one image (k == 0) or of k views: n results, n rows of scores (a fusion job's: its view 0's)
+    void launch_jobs(SlotBufs& b, int n, int k, int h, int w, const uint8_t* has_sc) {
         HipSlot& hs = *static_cast<HipSlot*>(b.impl);
         const size_t ib = (size_t)h * w * 3;
-        IRE_HIP(hipMemcpyAsync(hs.d_jp.get<uint8_t>(), b.pin_jp, (size_t)n, hipMemcpyHostToDevice, cs));
+        IRE_HIP(hipMemcpyAsync(hs.d_jp.get<uint8_t>(), b.pin_jp, (size_t)n * (size_t)std::max(1, k), hipMemcpyHostToDevice, cs));
         IRE_HIP(hipEventRecord(hs.ev->in, cs));
         hipStream_t ms = E.main_stream();
         on_stream(E, ms, [&] {
@@ -224,8 +229,13 @@ struct HipBatchBackend {
             IRE_HIP(hipEventRecord(hs.ev->c0, ms));
             // classifies the jobs that brought no scores; a shape the network cannot take as it is (ire_submit_fit) is padded into the
             // engine's staging and its window comes back; with text() the results leave the device as text
-            E.restore_fit_device_mixed(hs.d_in.get<uint8_t>(), n, h, w, b.pin_sc_in, has_sc, hs.d_jp.get<uint8_t>(), hs.d_out.get<uint8_t>(), text() ? hs.d_txt.get<uint8_t>() : nullptr, (out_bytes(h, w) + 255) / 256 * 256, ms);
-            IRE_HIP(hipMemcpyAsync(b.pin_sc, E.scores_device(), sizeof(double) * 7 * n, hipMemcpyDeviceToHost, ms));
+            if (k) {
+                E.restore_fuse_fit_device_mixed(hs.d_in.get<uint8_t>(), n, k, h, w, b.pin_sc_in, has_sc, hs.d_jp.get<uint8_t>(), hs.d_out.get<uint8_t>(), text() ? hs.d_txt.get<uint8_t>() : nullptr, (out_bytes(h, w) + 255) / 256 * 256, ms);
+                IRE_HIP(hipMemcpy2DAsync(b.pin_sc, sizeof(double) * 7, E.scores_device(), sizeof(double) * 7 * k, sizeof(double) * 7, (size_t)n, hipMemcpyDeviceToHost, ms));      // view 0 of every job
+            } else {
+                E.restore_fit_device_mixed(hs.d_in.get<uint8_t>(), n, h, w, b.pin_sc_in, has_sc, hs.d_jp.get<uint8_t>(), hs.d_out.get<uint8_t>(), text() ? hs.d_txt.get<uint8_t>() : nullptr, (out_bytes(h, w) + 255) / 256 * 256, ms);
+                IRE_HIP(hipMemcpyAsync(b.pin_sc, E.scores_device(), sizeof(double) * 7 * n, hipMemcpyDeviceToHost, ms));
+            }
             if (hs.file_jobs) IRE_HIP(hipMemcpyAsync(hs.pin_fstat.get<int32_t>(), hs.d_fstat.get<int32_t>(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ms));
             hs.file_jobs = 0;
             IRE_HIP(hipEventRecord(hs.ev->c1, ms));
@@ -705,6 +715,37 @@ int ire_submit_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, const doub
         std::unique_ptr<ire_job> hnd(new ire_job{});
         hnd->j = e->batcher->submit_file(file, bytes, scores);
         *job_out = hnd.release();
+    });
+}
+
+int ire_submit_fuse_fit(ire_engine* e, const uint8_t* const* views, int k, int h, int w, const uint8_t* is_jpeg, const uint8_t* has_scores, const double* scores,
+                        ire_job** job_out) {
+    return guarded([&] {
+        eng(e);
+        if (!views || !job_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_fuse_fit");
+        *job_out = nullptr;
+        if (k < 2 || k > 3) fail(IRE_ERR_INVALID_INPUT, "invalid view count for fusion: expected 2..3");
+        for (int v = 0; v < k; ++v) if (!views[v]) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_fuse_fit: null view");
+        if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size: height and width must be in 1..8192");
+        if (has_scores && !scores) for (int v = 0; v < k; ++v) if (has_scores[v]) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_fuse_fit: has_scores without scores");
+        std::unique_ptr<ire_job> hnd(new ire_job{});
+        hnd->j = e->batcher->submit_group(views, k, h, w, is_jpeg, has_scores, scores);       // (refuses k views on an engine with max_batch < k)
+        *job_out = hnd.release();
+    });
+}
+
+int ire_restore_fuse_fit_device(ire_engine* e, const uint8_t* d_views, int nsets, int k, int h, int w, const double* d_scores, const uint8_t* d_is_jpeg,
+                                uint8_t* d_out_rgb, void* stream) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, (hipStream_t)stream, [&] { E.restore_fuse_fit_device(d_views, nsets, k, h, w, d_scores, d_is_jpeg, d_out_rgb, (hipStream_t)stream); });
+    });
+}
+
+int ire_debug_fusion_wlut(ire_engine* e, const double* noise, int n, uint32_t* out) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, E.main_stream(), [&] { E.debug_fusion_wlut(noise, n, out); });
     });
 }
 

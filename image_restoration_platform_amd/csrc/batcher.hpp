@@ -22,6 +22,10 @@
 // per restoreBatch, 5 per worker -- is about to resubmit), and when the GPU is idle after a short bounded linger: kLingerQuietUs
 // after the last arrival, at most kLingerMaxUs after the first.
 //
+// A slot gathers ONE kind of job: pixel jobs, file jobs, or fusion jobs (submit_group) of one k -- a fusion job's k views take k
+// consecutive image places, so such a slot holds max_batch / k jobs (at most kGroupMaxJobs: a full slot is ONE fused launch) and
+// closes by the same full / linger rules.
+//
 // A job handle is used by ONE thread at a time (poll it, or release it).  A timed-out poll leaves the job pending; the caller
 // polls again or RELEASES it (the reference retries 3x on exactly this path: utils/retry.js:12-47): an abandoned job's slot
 // position is still computed with its batch, but nobody is counted as waiting for it.
@@ -51,19 +55,22 @@ constexpr int kSlots = 8;             // gathering | computing | up to six waiti
 constexpr int kSlotsEager = 3;        // staging allocated at the first job of a shape; the other slots get theirs when first needed
 constexpr int kLingerQuietUs = 250, kLingerMaxUs = 1500;
 constexpr int kMaxBatch = 64;
+constexpr int kGroupMaxJobs = 16;     // fusion jobs of one batch at most: what one fused launch takes (fusion.hpp kFuseMaxSets; api.cpp asserts that they agree)
 
 struct BatchSlot;
 struct Job {
-    int h = 0, w = 0, is_jpeg = 0;
-    bool has_scores = false;
+    int h = 0, w = 0;
     bool staged = false;              // input bytes are in the slot's pinned buffer (or in `in` on the overflow path)
     bool abandoned = false;           // released while pending: its result is dropped when the batch completes
+    int views = 0;                    // a fusion job (submit_group): its k = 2..3 views of h x w, staged one behind the other; 0: one image
+    uint8_t v_jpeg[3] = {}, v_has[3] = {};      // per image of the job (a pixel or file job: entry 0 alone): is_jpeg, scores supplied
+    double v_scores[3][7] = {};                 // ... and those scores
     std::shared_ptr<void> file;       // a file job (submit_file): what the backend's file_plan made of the file's head; its staged input is the scan, cut
     size_t file_used = 0;             // bytes of that input
     BatchSlot* slot = nullptr;        // where the input was staged and the output will be; null: overflow (no free slot at submit) / evicted / fetched
     int idx = -1;
     std::vector<uint8_t> in, out;     // overflow input / evicted output only
-    double scores[7] = {};
+    double scores[7] = {};            // the result's (a fusion job's: its view 0's), from the batch
     ire_timings t{};
     int status = -1;                  // -1 pending, else ire_status
     int stage_status = IRE_OK;        // a file job whose staging failed after it had got its place: the status it completes with
@@ -86,6 +93,7 @@ struct BatchSlot {
     std::vector<std::shared_ptr<Job>> jobs;   // index order = position in the batch
     int h = 0, w = 0;
     bool files = false;                   // gathers file jobs (never mixed with pixel jobs: their input is decoded on the device, not copied)
+    int k = 0;                            // gathers fusion jobs of k views each (never mixed with another kind or another k); 0: one image per job
     int h2d_issued = 0;                   // images whose H2D copy (file jobs: whose decode) is already on the copy-in stream
     int unread = 0, reading = 0;          // DONE: jobs that have not fetched their output yet / polls copying right now
     std::chrono::steady_clock::time_point first_arrival, last_arrival;
@@ -126,6 +134,16 @@ template <class B, class = void>
 struct has_file_jobs : std::false_type {};
 template <class B>
 struct has_file_jobs<B, std::void_t<decltype(std::declval<B&>().file_status(std::declval<SlotBufs&>(), 0))>> : std::true_type {};
+
+// OPTIONAL (detected at compile time; without it submit_group does not compile): FUSION JOBS, k = 2..3 views of one size per job.
+// Job i of such a slot owns images [i * k, i * k + k) of the slot's input and of pin_jp / has_sc / pin_sc_in, and result place i.
+//   void launch_group(SlotBufs&, int njobs, int k, int h, int w, const uint8_t* has_sc);
+//                                                              in place of launch: njobs results of out_bytes(h, w) bytes each, and
+//                                                              pin_sc[7 * i ..] = the scores of job i's view 0
+template <class B, class = void>
+struct has_group_launch : std::false_type {};
+template <class B>
+struct has_group_launch<B, std::void_t<decltype(std::declval<B&>().launch_group(std::declval<SlotBufs&>(), 0, 0, 0, 0, (const uint8_t*)nullptr))>> : std::true_type {};
 
 template <class B, class = void>
 struct has_result_view : std::false_type {};
@@ -173,8 +191,8 @@ class Batcher {
     // Queue one image.  Throws Error (invalid size is the caller's check); the returned job is pending.
     std::shared_ptr<Job> submit(const uint8_t* rgb, int h, int w, int is_jpeg, const double* scores) {
         auto j = std::make_shared<Job>();
-        j->h = h; j->w = w; j->is_jpeg = is_jpeg ? 1 : 0;
-        if (scores) { std::memcpy(j->scores, scores, sizeof(double) * 7); j->has_scores = true; }
+        j->h = h; j->w = w; j->v_jpeg[0] = is_jpeg ? 1 : 0;
+        if (scores) { std::memcpy(j->v_scores[0], scores, sizeof(double) * 7); j->v_has[0] = 1; }
         const size_t ib = (size_t)h * w * 3;
         uint8_t* dst = nullptr;
         {
@@ -207,8 +225,8 @@ class Batcher {
         auto j = std::make_shared<Job>();
         size_t room = 0;
         j->file = be_.file_plan(file, bytes, &j->h, &j->w, &room);
-        j->is_jpeg = 1;
-        if (scores) { std::memcpy(j->scores, scores, sizeof(double) * 7); j->has_scores = true; }
+        j->v_jpeg[0] = 1;
+        if (scores) { std::memcpy(j->v_scores[0], scores, sizeof(double) * 7); j->v_has[0] = 1; }
         const int h = j->h, w = j->w;
         const size_t ib = (size_t)h * w * 3;
         if (room > ib) fail(IRE_ERR_INVALID_INPUT, "invalid: the file's entropy-coded data may be larger than its pixels (it stays with the host codec)");
@@ -234,6 +252,40 @@ class Batcher {
             if (code != IRE_OK) { j->stage_status = code; j->err = why; j->file_used = 0; }
             if (!dst) { j->in.resize(j->file_used); overflow_.push_back(j); cnt_.overflowed += 1; }
             j->staged = true;
+        }
+        qcv_.notify_all();
+        return j;
+    }
+
+    // Queue one fusion job (backends with the group launch): k = 2..3 views of h x w.  All k views are staged HERE, in the submitting
+    // thread: one copy each into the job's k consecutive places of the pinned slot (or into the job's own vector on the overflow
+    // path).  is_jpeg / has_scores: [k] or null (all JPEG / none supplied); scores: [k][7], read where has_scores says so.
+    template <class BE = Backend>
+    std::shared_ptr<Job> submit_group(const uint8_t* const* views, int k, int h, int w, const uint8_t* is_jpeg, const uint8_t* has_scores, const double* scores) {
+        static_assert(has_group_launch<BE>::value, "this backend has no group launch");
+        if (k < 2 || k > 3) fail(IRE_ERR_INVALID_INPUT, "invalid view count for fusion: expected 2..3");
+        if (be_.max_batch() < k) fail(IRE_ERR_INVALID_INPUT, "invalid view count for fusion: the engine's max_batch is smaller than the number of views");
+        auto j = std::make_shared<Job>();
+        j->h = h; j->w = w; j->views = k;
+        for (int v = 0; v < k; ++v) {
+            j->v_jpeg[v] = is_jpeg ? (is_jpeg[v] ? 1 : 0) : 1;
+            j->v_has[v] = has_scores && has_scores[v] ? 1 : 0;
+            if (j->v_has[v]) std::memcpy(j->v_scores[v], scores + 7 * v, sizeof(double) * 7);
+        }
+        const size_t ib = (size_t)h * w * 3;
+        uint8_t* dst = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            start_locked(h, w);
+            const int si = overflow_.empty() ? slot_for(h, w, false, k) : -1;
+            if (si >= 0) { slot_add(si, j); dst = slots_[si].b.pin_in + ib * k * j->idx; }
+        }
+        if (!dst) { j->in.resize(ib * k); dst = j->in.data(); }
+        for (int v = 0; v < k; ++v) std::memcpy(dst + ib * v, views[v], ib);       // the ONE host copy of each view, in the caller's thread
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            j->staged = true;
+            if (!j->slot) { overflow_.push_back(j); cnt_.overflowed += 1; }
         }
         qcv_.notify_all();
         return j;
@@ -335,11 +387,11 @@ class Batcher {
     // (mu_ held) an OPEN slot of this shape with room, else a FREE one opened for it, else -1.  May allocate staging (first use
     // of a shape: once).  A DONE slot nobody is reading is evicted when nothing else is left: its unfetched outputs move to
     // their jobs' own vectors (the extra copy only a caller that lets a slot's worth of batches pile up unpolled ever pays).
-    int slot_for(int h, int w, bool files = false) {
+    int slot_for(int h, int w, bool files = false, int k = 0) {
         const int mb = be_.max_batch();
         for (auto it = open_order_.rbegin(); it != open_order_.rend(); ++it) {
             BatchSlot& S = slots_[*it];
-            if (S.h == h && S.w == w && S.files == files && (int)S.jobs.size() < mb) return *it;
+            if (S.h == h && S.w == w && S.files == files && S.k == k && (int)S.jobs.size() < capacity(S)) return *it;
         }
         int pick = -1;
         const size_t need = std::max((size_t)h * w * 3, be_.out_bytes(h, w)) * (size_t)mb;
@@ -363,20 +415,27 @@ class Batcher {
         if (pick < 0) return -1;
         BatchSlot& S = slots_[pick];
         be_.reserve(S.b, need, mb);               // strong guarantee: a throw leaves the slot FREE with what it had
-        S.state = BatchSlot::OPEN; S.h = h; S.w = w; S.files = files; S.jobs.clear(); S.h2d_issued = 0; S.unread = S.reading = 0;
+        S.state = BatchSlot::OPEN; S.h = h; S.w = w; S.files = files; S.k = k; S.jobs.clear(); S.h2d_issued = 0; S.unread = S.reading = 0;
         S.status = IRE_OK; S.err.clear();
         S.first_arrival = S.last_arrival = clk::now();
         open_order_.push_back(pick);
         return pick;
     }
 
+    // jobs a slot holds: max_batch images, so max_batch / k fusion jobs of k views, and never more than one fused launch takes
+    int capacity(const BatchSlot& S) const { return S.k ? std::min(be_.max_batch() / S.k, kGroupMaxJobs) : be_.max_batch(); }
+
     // (mu_ held) reserve the next index of slot si for job j
     void slot_add(int si, const std::shared_ptr<Job>& j) {
         BatchSlot& S = slots_[si];
         j->slot = &S; j->idx = (int)S.jobs.size();
-        S.b.pin_jp[j->idx] = (uint8_t)j->is_jpeg;
-        S.has_sc[j->idx] = j->has_scores ? 1 : 0;
-        if (j->has_scores) std::memcpy(S.b.pin_sc_in + 7 * j->idx, j->scores, sizeof(double) * 7);
+        const int per = std::max(1, j->views);     // images of the job: they take places idx * per .. of the slot
+        for (int v = 0; v < per; ++v) {
+            const int at = j->idx * per + v;
+            S.b.pin_jp[at] = j->v_jpeg[v];
+            S.has_sc[at] = j->v_has[v];
+            if (j->v_has[v]) std::memcpy(S.b.pin_sc_in + 7 * at, j->v_scores[v], sizeof(double) * 7);
+        }
         S.jobs.push_back(j);
         S.last_arrival = clk::now();
         if (j->idx == 0) S.first_arrival = S.last_arrival;
@@ -391,7 +450,7 @@ class Batcher {
     // an upload and enqueues a dozen operations; submitters and pollers must not queue behind that): the slot is full or CLOSED, so
     // nobody adds to it meanwhile, and only this thread moves a slot out of OPEN / CLOSED.
     void slot_push_h2d(BatchSlot& S, std::unique_lock<std::mutex>& lk, bool closing) {
-        const size_t ib = (size_t)S.h * S.w * 3;
+        const size_t ib = (size_t)S.h * S.w * 3 * (size_t)std::max(1, S.k);      // a job's staged input: one image, or a fusion job's k views
         int upto = S.h2d_issued;
         while (upto < (int)S.jobs.size() && S.jobs[upto]->staged) ++upto;
         if (upto == S.h2d_issued || S.status != IRE_OK) return;
@@ -420,6 +479,14 @@ class Batcher {
             be_.decode(S.b, first, count, h, w, heads, used);
             lk.lock();
         } else fail(IRE_ERR_INTERNAL, "internal: a file slot on a backend without file jobs");
+    }
+
+    // (launcher, no lock) the closed slot's batch to the backend: n images, or n fusion jobs of S.k views
+    template <class BE = Backend>
+    void launch_slot(BatchSlot& S, int n) {
+        if (!S.k) { be_.launch(S.b, n, S.h, S.w, S.has_sc); return; }
+        if constexpr (has_group_launch<BE>::value) be_.launch_group(S.b, n, S.k, S.h, S.w, S.has_sc);
+        else fail(IRE_ERR_INTERNAL, "internal: a fusion slot on a backend without the group launch");
     }
 
     // (mu_ held) what fails job i of a completed batch ALONE: its staging failed at submit, or the device flagged its data
@@ -459,7 +526,7 @@ class Batcher {
             while (!overflow_.empty()) {
                 std::shared_ptr<Job> j = overflow_.front();
                 int si = -1;
-                try { si = slot_for(j->h, j->w, j->file != nullptr); }
+                try { si = slot_for(j->h, j->w, j->file != nullptr, j->views); }
                 catch (const Error& e) { fail_job(*j, e.code, e.msg); overflow_.pop_front(); dcv_.notify_all(); continue; }
                 catch (const std::exception& e) {      // bad_alloc while evicting a DONE slot: this job fails, the service thread lives
                     fail_job(*j, IRE_ERR_UNAVAILABLE, std::string("service unavailable: ") + e.what()); overflow_.pop_front(); dcv_.notify_all(); continue;
@@ -468,7 +535,7 @@ class Batcher {
                 overflow_.pop_front();
                 slot_add(si, j);
                 BatchSlot& S = slots_[si];
-                if (!j->in.empty()) std::memcpy(S.b.pin_in + (size_t)j->h * j->w * 3 * j->idx, j->in.data(), j->in.size());
+                if (!j->in.empty()) std::memcpy(S.b.pin_in + (size_t)j->h * j->w * 3 * (size_t)std::max(1, j->views) * j->idx, j->in.data(), j->in.size());
                 j->in.clear(); j->in.shrink_to_fit();
             }
             if (open_order_.empty()) {
@@ -481,7 +548,7 @@ class Batcher {
             const int si = open_order_.front();
             BatchSlot& S = slots_[si];
             slot_push_h2d(S, lk, false);
-            const bool full = (int)S.jobs.size() >= be_.max_batch();
+            const bool full = (int)S.jobs.size() >= capacity(S);
             if (!full && !stop_ && S.status == IRE_OK && open_order_.size() == 1) {
                 bool gpu_busy = false;
                 if (last_launched_ >= 0) {
@@ -517,7 +584,7 @@ class Batcher {
             lk.unlock();
             try {
                 if (S.status != IRE_OK) throw Error{S.status, S.err};
-                be_.launch(S.b, n, S.h, S.w, S.has_sc);
+                launch_slot(S, n);
             } catch (const Error& e) { S.status = e.code; S.err = e.msg; }
             catch (const std::exception& e) { S.status = IRE_ERR_INTERNAL; S.err = std::string("internal: ") + e.what(); }
             if (S.status != IRE_OK) be_.drain();   // whatever was enqueued before the failure may still touch the slot's buffers

@@ -99,13 +99,14 @@ __global__ __launch_bounds__(256) void classifier_scan_kernel(const uint8_t* __r
                                                               const uint8_t* __restrict__ is_jpeg,
                                                               double* __restrict__ scores, int32_t* __restrict__ label,
                                                               float* __restrict__ cond,
-                                                              const float* __restrict__ film_w, const float* __restrict__ film_b, int film_n, float* __restrict__ film) {
+                                                              const float* __restrict__ film_w, const float* __restrict__ film_b, int film_n, float* __restrict__ film,
+                                                              size_t img_pitch) {
     __shared__ ClsLds L;
     __shared__ unsigned long long red[4][CLS_NSUMS];
     __shared__ int s_last;
     const int tid = threadIdx.x;
     const int img = blockIdx.y;
-    const uint8_t* base = rgb + (size_t)img * H * W * 3;
+    const uint8_t* base = rgb + (size_t)img * img_pitch;      // (rows are dense; only the images may lie apart)
 
 
     unsigned long long acc[CLS_NSUMS];
@@ -441,7 +442,7 @@ __global__ void scores_to_cond_kernel(const double* __restrict__ scores, int n, 
 
 void classifier_launch(const ClassifierTables& tb, const uint8_t* d_rgb, int n, int h, int w,
                        const uint8_t* d_is_jpeg, unsigned long long* d_sums, double* d_scores,
-                       int32_t* d_label, float* d_cond, hipStream_t stream, const float* d_film_w, const float* d_film_b, int film_n, float* d_film) {
+                       int32_t* d_label, float* d_cond, hipStream_t stream, const float* d_film_w, const float* d_film_b, int film_n, float* d_film, size_t img_pitch) {
     // d_sums (engine.cpp::ensure_io): [cap][14] sums | [cap] tickets (zero at allocation, reset by the kernel) | [cap][CLS_MAX_WG][14]
     // workgroup partials -- no memset, no second launch
     const int tiles_x = cls_tiles(h, w).tiles_x, tiles_y = cls_tiles(h, w).tiles_y;
@@ -451,7 +452,7 @@ void classifier_launch(const ClassifierTables& tb, const uint8_t* d_rgb, int n, 
     dim3 grid(per_img, n);
     hipLaunchKernelGGL(classifier_scan_kernel, grid, dim3(256), 0, stream, d_rgb, h, w, tiles_x, tiles_y,
                        tb.lin16, tb.thr, tb.inv, d_sums, cls_tickets(d_sums), cls_parts(d_sums), d_is_jpeg, d_scores, d_label, d_cond,
-                       d_film_w, d_film_b, film_n, d_film);
+                       d_film_w, d_film_b, film_n, d_film, img_pitch ? img_pitch : (size_t)h * w * 3);
     IRE_HIP(hipGetLastError());
 }
 

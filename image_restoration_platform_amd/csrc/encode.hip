@@ -304,6 +304,26 @@ __global__ __launch_bounds__(256) void pad_edge_kernel(const unsigned char* __re
     reinterpret_cast<unsigned*>(dst + ((size_t)img * H + y) * (size_t)W * 3)[xd] = out;
 }
 
+// The same pad with a PITCHED source: the h x w window at the top left of images whose rows lie row_pitch and whose first pixels lie
+// image_pitch bytes apart (a restored window inside the network's padded output) -> dense [n][H][W][3].  One dword per thread.
+__global__ __launch_bounds__(256) void pad_edge_pitched_kernel(const unsigned char* __restrict__ src, unsigned long long row_pitch, unsigned long long image_pitch,
+                                                               int h, int w, unsigned char* __restrict__ dst, int H, int W) {
+    const unsigned dw_row = 3u * (unsigned)W / 4u;
+    const unsigned xd = blockIdx.x * 256 + threadIdx.x;
+    if (xd >= dw_row) return;
+    const unsigned y = blockIdx.y, img = blockIdx.z;
+    const unsigned sy = y < (unsigned)h ? y : (unsigned)h - 1;
+    const unsigned char* __restrict__ srow = src + img * image_pitch + sy * row_pitch;
+    unsigned out = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned b = xd * 4 + k, x = b / 3, c = b - x * 3;
+        const unsigned sx = x < (unsigned)w ? x : (unsigned)w - 1;
+        out |= (unsigned)srow[sx * 3 + c] << (8 * k);
+    }
+    reinterpret_cast<unsigned*>(dst + ((size_t)img * H + y) * (size_t)W * 3)[xd] = out;
+}
+
 // the top-left h x w window of [n][H][W][3] -> [n][h][w][3] tightly packed.  The packed result is one run of n*h*w*3 bytes; a thread
 // moves the 4 of them that share a dword of the destination (`mis` = the destination's address mod 4), so every thread but the
 // first and the last of the run stores one aligned dword whatever h*w*3 and the caller's pointer are.
@@ -395,6 +415,16 @@ void pad_edge_launch(const unsigned char* d_src, int n, int h, int w, unsigned c
     if (n < 1 || h < 1 || w < 1 || H < h || W < w || W % 8 || H > 65535 || n > 65535) fail(IRE_ERR_INVALID_INPUT, "invalid sizes for the edge pad");
     const unsigned dw_row = 3u * (unsigned)W / 4u;
     hipLaunchKernelGGL(pad_edge_kernel, dim3((dw_row + 255) / 256, H, n), dim3(256), 0, s, d_src, h, w, d_dst, H, W);
+    IRE_HIP(hipGetLastError());
+}
+
+// the h x w windows of n pitched images -> d_dst [n][H][W][3], edge-replicated (H >= h, W >= w, W % 8 == 0, d_dst 4-byte aligned).  One launch.
+void pad_edge_pitched_launch(const unsigned char* d_src, int n, int h, int w, size_t row_pitch, size_t image_pitch, unsigned char* d_dst, int H, int W, hipStream_t s) {
+    if (n < 1 || h < 1 || w < 1 || H < h || W < w || W % 8 || H > 65535 || n > 65535) fail(IRE_ERR_INVALID_INPUT, "invalid sizes for the edge pad");
+    if (row_pitch < (size_t)3 * w || (n > 1 && image_pitch < row_pitch * (size_t)(h - 1) + (size_t)3 * w)) fail(IRE_ERR_INVALID_INPUT, "invalid pitch for the edge pad: rows or images overlap");
+    const unsigned dw_row = 3u * (unsigned)W / 4u;
+    hipLaunchKernelGGL(pad_edge_pitched_kernel, dim3((dw_row + 255) / 256, H, n), dim3(256), 0, s, d_src, (unsigned long long)row_pitch, (unsigned long long)image_pitch, h, w,
+                       d_dst, H, W);
     IRE_HIP(hipGetLastError());
 }
 

@@ -4,6 +4,7 @@
 // (server-node/src/clients/geminiClient.js:32-97).
 #include "engine.hpp"
 #include "encode.hpp"
+#include "fusion.hpp"
 #include "deflate.hpp"
 #include "jpeg.hpp"
 #include "jpeg_dec.hpp"
@@ -1051,6 +1052,93 @@ void Engine::restore_fit_device_mixed(const uint8_t* d_rgb, int n, int h, int w,
     restore_padded(d_rgb, n, h, w, d_sc, d_is_jpeg, stream);
     if (d_txt) encode_result(d_pad_out_.get<uint8_t>(), n, h, w, (size_t)3 * W, (size_t)3 * W * H, d_txt, txt_stride, stream);     // the crop costs no pass of its own
     else crop_window_launch(d_pad_out_.get<uint8_t>(), n, H, W, d_out, h, w, stream);
+}
+
+// ---- fusion jobs: restore every view, pad the windows to the fusion shape, fuse, crop / encode -- all on the stream ----------------
+void Engine::check_fuse_fit(int nsets, int k, int h, int w) const {
+    if (k < 2 || k > 3) fail(IRE_ERR_INVALID_INPUT, "invalid view count for fusion: expected 2..3");
+    if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size: height and width must be in 1..8192");
+    if (nsets < 1 || nsets > kFuseMaxSets || nsets * k > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid batch size for fusion: expected 1..16 view sets of at most max_batch images");
+}
+
+// Everything a fusion batch of this shape needs beyond the network's own buffers, sized by the grow rule for the largest batch of
+// the shape that the batcher can gather WHATEVER its k (a slot of k = 2 holds the most sets, a slot of either k at most max_batch
+// views), so that only the FIRST job of a shape allocates and a later job of the other k does not (FuseBufs::regrow synchronises
+// the device).
+void Engine::ensure_fuse_io(int nsets, int k, int HF, int WF, hipStream_t s) {
+    IRE_HIP(hipSetDevice(device_));
+    const size_t px = (size_t)HF * WF, per = px * 3;
+    const size_t full_sets = (size_t)std::max(nsets, std::min(kFuseMaxSets, max_batch_ / 2));
+    const size_t full_views = (size_t)std::max(nsets * k, std::min(kFuseMaxSets * 3, max_batch_));
+    const size_t need_in = per * (size_t)nsets * k, need_out = per * (size_t)nsets;
+    if (need_in > d_fuse_in_.bytes() || need_out > d_fuse_out_.bytes()) {
+        IRE_HIP(hipDeviceSynchronize());
+        d_fuse_in_.grow(need_in, batch_room(need_in, per * full_views));
+        d_fuse_out_.grow(need_out, batch_room(need_out, per * full_sets));
+    }
+    if (!d_fuse_sc_) d_fuse_sc_ = Buf<DeviceMem>(sizeof(double) * 7 * kFuseMaxSets);
+    // the chain's scratch, about 3.4 bytes per pixel and set (device_buf.hpp FuseBufs), in sets: a whole batch or what was asked for
+    const size_t want_sets = batch_room(px * 4 * (size_t)nsets, px * 4 * full_sets) / (px * 4);
+    fuse_reserve((int)want_sets, px, s);
+}
+
+void Engine::fuse_fit_core(const uint8_t* d_views, int nsets, int k, int h, int w, const double* d_sc, const uint8_t* d_is_jpeg, uint8_t* d_out, uint8_t* d_txt,
+                           size_t txt_stride, hipStream_t stream) {
+    if (!d_views || !d_out) fail(IRE_ERR_INVALID_INPUT, "invalid input: null image pointer");
+    if (!net_.loaded) fail(IRE_ERR_UNAVAILABLE, "service unavailable: RestoreNet weights are not loaded");
+    const int n = nsets * k, H = fit_dim(h), W = fit_dim(w), HF = fuse_dim(h), WF = fuse_dim(w);
+    const bool aligned = fit_is_aligned(h, w), direct = aligned && h >= 64 && w >= 64;      // direct: the network's output IS the fusion input
+    ensure_fuse_io(nsets, k, HF, WF, stream);
+    uint8_t* f_in = d_fuse_in_.get<uint8_t>();
+    if (direct) restore_device(d_views, n, h, w, d_sc, d_is_jpeg, f_in, stream);
+    else {
+        if (aligned) { ensure_pad(n, h, w); restore_device(d_views, n, h, w, d_sc, d_is_jpeg, d_pad_out_.get<uint8_t>(), stream); }
+        else restore_padded(d_views, n, h, w, d_sc, d_is_jpeg, stream);
+        // the restored h x w windows where the network left them -> the fusion input, edge-replicated (never the network's own padding)
+        pad_edge_pitched_launch(d_pad_out_.get<uint8_t>(), n, h, w, (size_t)3 * W, (size_t)3 * W * H, f_in, HF, WF, stream);
+    }
+    // the noise score of view 0 of every PADDED set, into a buffer of its own: io_.scores holds the jobs' scores
+    double* f_sc = d_fuse_sc_.get<double>();
+    // (ONE launch for all sets: the view 0s lie k images apart; the scan's sums are integers, so its grid does not change a score)
+    prof_begin(FAM_CLASSIFIER, stream, 0, (double)nsets * HF * WF * 3);
+    classifier_launch(tables_, f_in, nsets, HF, WF, nullptr, io_.sums, f_sc, nullptr, nullptr, stream, nullptr, nullptr, 0, nullptr, (size_t)k * HF * WF * 3);
+    prof_end(stream);
+    uint8_t* fused = (!d_txt && direct) ? d_out : d_fuse_out_.get<uint8_t>();
+    fuse_launch_device_tables(f_in, nsets, k, HF, WF, f_sc + IRE_SCORE_NOISE, 7, fused, nullptr, stream);
+    if (d_txt) encode_result(fused, nsets, h, w, (size_t)3 * WF, (size_t)3 * WF * HF, d_txt, txt_stride, stream);     // the crop costs no pass of its own
+    else if (!direct) crop_window_launch(fused, nsets, HF, WF, d_out, h, w, stream);
+}
+
+void Engine::restore_fuse_fit_device_mixed(const uint8_t* d_views, int nsets, int k, int h, int w, const double* host_scores, const uint8_t* has_scores,
+                                           const uint8_t* d_is_jpeg, uint8_t* d_out, uint8_t* d_txt, size_t txt_stride, hipStream_t stream) {
+    check_fuse_fit(nsets, k, h, w);
+    const int n = nsets * k;
+    ensure_io(n, 1, 1);
+    // the views' scores exactly as restore_fit_device_mixed settles them for n single jobs
+    const bool aligned = fit_is_aligned(h, w);
+    bool any_missing = false, any_given = false;
+    for (int i = 0; i < n; ++i) { if (has_scores && has_scores[i]) any_given = true; else any_missing = true; }
+    const double* d_sc = nullptr;
+    if (any_given || !aligned) {
+        if (any_missing) classify_device(d_views, n, h, w, d_is_jpeg, io_.scores, io_.label, stream);      // the ORIGINAL pixels
+        for (int i = 0; i < n; ++i)
+            if (has_scores && has_scores[i]) IRE_HIP(hipMemcpyAsync(io_.scores + 7 * i, host_scores + 7 * i, sizeof(double) * 7, hipMemcpyHostToDevice, stream));
+        d_sc = io_.scores;
+    }
+    fuse_fit_core(d_views, nsets, k, h, w, d_sc, d_is_jpeg, d_out, d_txt, txt_stride, stream);
+}
+
+void Engine::restore_fuse_fit_device(const uint8_t* d_views, int nsets, int k, int h, int w, const double* d_scores, const uint8_t* d_is_jpeg, uint8_t* d_out,
+                                     hipStream_t stream) {
+    check_fuse_fit(nsets, k, h, w);
+    const int n = nsets * k;
+    ensure_io(n, 1, 1);
+    if (!d_scores && !fit_is_aligned(h, w)) {      // the classifier reads the ORIGINAL pixels, never the padded copy
+        if (!d_views) fail(IRE_ERR_INVALID_INPUT, "invalid input: null image pointer");
+        classify_device(d_views, n, h, w, d_is_jpeg, io_.scores, io_.label, stream);
+        d_scores = io_.scores;
+    }
+    fuse_fit_core(d_views, nsets, k, h, w, d_scores, d_is_jpeg, d_out, nullptr, 0, stream);
 }
 
 void Engine::get_stats(ire_engine_stats* out) {

@@ -156,6 +156,22 @@ public:
     void fuse_launch(const uint8_t* d_views, int nsets, int k, int h, int w, const unsigned* host_wluts, uint8_t* d_out,
                      int32_t* d_shifts, hipStream_t s);
     double noise_of_view0(const uint8_t* d_views, int h, int w, hipStream_t s);
+    // the chain with its blend tables built on the device from d_noise[i * noise_stride] (fusion_wlut_kernel): no host round trip
+    void fuse_launch_device_tables(const uint8_t* d_views, int nsets, int k, int h, int w, const double* d_noise, int noise_stride, uint8_t* d_out,
+                                   int32_t* d_shifts, hipStream_t s);
+    void debug_fusion_wlut(const double* noise, int n, uint32_t* out);
+    // Fusion jobs (k = 2..3 views of one size, h, w in 1..8192), nsets sets laid out [nsets][k][h][w][3]: every view restored as
+    // restore_fit_device_mixed restores it, its h x w window edge-replicated to HF x WF = fuse_dim(h) x fuse_dim(w), the sets fused with
+    // the noise score of view 0 of the PADDED set (what noise_score < 0 means to ire_fuse), the fused image cropped to h x w.
+    // d_txt == null: d_out receives the nsets*h*w*3 fused pixels; else the results leave as text, encoded where the fused padded
+    // image lies (txt_stride apart, as restore_fit_device_mixed lays them out).  nsets <= kFuseMaxSets, nsets*k <= max_batch.
+    // The view's scores are in scores_device() afterwards, [nsets*k][7].  Nothing in it waits for the stream.
+    void restore_fuse_fit_device_mixed(const uint8_t* d_views, int nsets, int k, int h, int w, const double* host_scores, const uint8_t* has_scores,
+                                       const uint8_t* d_is_jpeg, uint8_t* d_out, uint8_t* d_txt, size_t txt_stride, hipStream_t stream);
+    // the same for a caller on the device: d_scores [nsets*k][7] for every view, or null: classified inside
+    void restore_fuse_fit_device(const uint8_t* d_views, int nsets, int k, int h, int w, const double* d_scores, const uint8_t* d_is_jpeg, uint8_t* d_out,
+                                 hipStream_t stream);
+    static int fuse_dim(int v) { return v <= 64 ? 64 : (v + 7) / 8 * 8; }
     void fuse_host_impl(const uint8_t* rgb_views, int k, int h, int w, double noise_score, uint8_t* out_rgb,
                         int32_t* shifts_out, ire_timings* t);
 
@@ -245,6 +261,12 @@ private:
     void check_shape(int n, int h, int w, bool for_restore) const;
     void check_fit(int n, int h, int w) const;
     void ensure_pad(int n, int H, int W);      // d_pad_in_ / d_pad_out_, grow-only
+    void ensure_fuse_io(int nsets, int k, int HF, int WF, hipStream_t s);      // d_fuse_in_ / d_fuse_out_ / d_fuse_sc_ and the fusion scratch, grow-only
+    void check_fuse_fit(int nsets, int k, int h, int w) const;
+    void fuse_fit_core(const uint8_t* d_views, int nsets, int k, int h, int w, const double* d_sc, const uint8_t* d_is_jpeg, uint8_t* d_out, uint8_t* d_txt,
+                       size_t txt_stride, hipStream_t stream);
+    void fuse_reserve(int nsets, size_t px, hipStream_t s);
+    void fuse_chain(const uint8_t* d_views, int nsets, int k, int h, int w, const unsigned* host_wluts, uint8_t* d_out, int32_t* d_shifts, hipStream_t s);
     void restore_padded(const uint8_t* d_rgb, int n, int h, int w, const double* d_scores, const uint8_t* d_is_jpeg, hipStream_t stream);
     void restore_host_impl(const uint8_t* rgb, int n, int h, int w, const double* scores, const uint8_t* is_jpeg, uint8_t* out, ire_timings* t);
     void encode_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, hipStream_t s);
@@ -306,6 +328,8 @@ private:
     Buf<DeviceMem> d_pp_tab_, d_pp_mid_, d_pp_in_, d_pp_out_;   // preprocess scratch (tap tables, intermediate of the horizontal pass, host-path staging)
     Buf<DeviceMem> d_enc_scratch_;        // encode.hip: per batch: the PNG files + checksum state
     Buf<DeviceMem> d_pad_in_, d_pad_out_; // any-size jobs: the edge-padded batch in front of the network, and the network's output on the padded shape
+    Buf<DeviceMem> d_fuse_in_, d_fuse_out_;   // fusion jobs: the restored windows padded to the fusion shape [n][HF][WF][3], the fused images [sets][HF][WF][3]
+    Buf<DeviceMem> d_fuse_sc_;            // ... and the classifier's scores of view 0 of every padded set, [kFuseMaxSets][7] (never io_.scores: those are the jobs')
     Buf<DeviceMem> d_enc_io_;             // host entry: pixels in | characters out
     // the JPEG decoder: the batch's upload (records, tables, stream table, stream bytes) pinned and on the device, the coefficient
     // scratch behind the status words, the sample planes, the host entry's pixels + status

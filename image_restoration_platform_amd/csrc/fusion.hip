@@ -435,6 +435,19 @@ __global__ __launch_bounds__(256) void fusion_blend_kernel(const uint8_t* __rest
     }
 }
 
+// make_wlut (below) on the device: one 256-thread workgroup per table, entry d by thread d.  The noise score of table i is
+// noise[i * stride]: a row of classifier scores, or a plain array.  Double exp and the same clamp, floor and minimum of 1 as the host
+// form, so a batch's tables need no host round trip (the batcher's launch must not wait for the stream).
+__global__ __launch_bounds__(256) void fusion_wlut_kernel(const double* __restrict__ noise, int stride, unsigned* __restrict__ wluts) {
+    double ns = noise[(size_t)blockIdx.x * stride];
+    if (!(ns >= 0.0)) ns = 0.0;
+    if (ns > 1.0) ns = 1.0;
+    const double sigma = 4.0 + 40.0 * ns;
+    const int d = threadIdx.x;
+    const double w = floor(1024.0 * exp(-(double)(d * d) / (2.0 * sigma * sigma)) + 0.5);
+    wluts[(size_t)blockIdx.x * 256 + d] = w < 1.0 ? 1u : (unsigned)w;
+}
+
 void make_wlut(double noise, unsigned* lut) {
     if (!(noise >= 0.0)) noise = 0.0;
     if (noise > 1.0) noise = 1.0;
@@ -453,24 +466,59 @@ void check_fuse_args(int k, int h, int w) {
 
 }  // namespace
 
+// the fusion scratch for `nsets` sets of `px` pixels (grow-only; a growth synchronises the device)
+void Engine::fuse_reserve(int nsets, size_t px, hipStream_t s) {
+    if (fuse_.cap_px >= px && fuse_.cap_sets >= nsets) return;
+    IRE_HIP(hipDeviceSynchronize());
+    fuse_.regrow(std::max(nsets, fuse_.cap_sets), std::max(px, fuse_.cap_px), (size_t)2 * FUSE_SAD_GRID * NC);      // (device_buf.hpp FuseBufs)
+    IRE_HIP(hipMemsetAsync(fuse_.misc, 0, sizeof(int) * (size_t)fuse_.cap_sets * 16, s));   // the tickets start at zero; the kernels reset them
+}
+
 void Engine::fuse_launch(const uint8_t* d_views, int nsets, int k, int h, int w, const unsigned* host_wluts, uint8_t* d_out,
                          int32_t* d_shifts, hipStream_t s) {
+    fuse_reserve(nsets, (size_t)h * w, s);
+    fuse_chain(d_views, nsets, k, h, w, host_wluts, d_out, d_shifts, s);
+}
+
+// The tables built on the device (fusion_wlut_kernel) from d_noise[i * noise_stride], for any nsets, 1 included: nothing here waits
+// for the stream.  The caller has reserved the scratch for its shape (fuse_reserve), so a steady stream of one shape never grows it.
+void Engine::fuse_launch_device_tables(const uint8_t* d_views, int nsets, int k, int h, int w, const double* d_noise, int noise_stride, uint8_t* d_out,
+                                       int32_t* d_shifts, hipStream_t s) {
+    check_fuse_args(k, h, w);
+    if (nsets < 1 || nsets > kFuseMaxSets) fail(IRE_ERR_INVALID_INPUT, "invalid batch size for fusion: expected 1..16 view sets");
+    fuse_reserve(nsets, (size_t)h * w, s);
+    hipLaunchKernelGGL(fusion_wlut_kernel, dim3(nsets), dim3(256), 0, s, d_noise, noise_stride, fuse_.wlut);
+    IRE_HIP(hipGetLastError());
+    fuse_chain(d_views, nsets, k, h, w, nullptr, d_out, d_shifts, s);
+}
+
+// ire_debug_fusion_wlut: n tables from n host noise scores through fusion_wlut_kernel, copied back (synchronous; tests only)
+void Engine::debug_fusion_wlut(const double* noise, int n, uint32_t* out) {
+    if (!noise || !out || n < 1 || n > 65535) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_debug_fusion_wlut (1..65535 scores)");
+    IRE_HIP(hipSetDevice(device_));
+    Buf<DeviceMem> d_noise(sizeof(double) * (size_t)n), d_lut(sizeof(unsigned) * 256 * (size_t)n);
+    hipStream_t s = main_stream_;
+    IRE_HIP(hipMemcpyAsync(d_noise.get<double>(), noise, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(fusion_wlut_kernel, dim3(n), dim3(256), 0, s, d_noise.get<double>(), 1, d_lut.get<unsigned>());
+    IRE_HIP(hipGetLastError());
+    IRE_HIP(hipMemcpyAsync(out, d_lut.get<unsigned>(), sizeof(unsigned) * 256 * (size_t)n, hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipStreamSynchronize(s));
+}
+
+// host_wluts == null: the nsets tables are in fuse_.wlut already
+void Engine::fuse_chain(const uint8_t* d_views, int nsets, int k, int h, int w, const unsigned* host_wluts, uint8_t* d_out,
+                        int32_t* d_shifts, hipStream_t s) {
     const size_t px = (size_t)h * w;
     const int hq = h / 4, wq = w / 4, qp = (wq + 3) & ~3;
-    if (fuse_.cap_px < px || fuse_.cap_sets < nsets) {
-        IRE_HIP(hipDeviceSynchronize());
-        fuse_.regrow(std::max(nsets, fuse_.cap_sets), std::max(px, fuse_.cap_px), (size_t)2 * FUSE_SAD_GRID * NC);      // (device_buf.hpp FuseBufs)
-        IRE_HIP(hipMemsetAsync(fuse_.misc, 0, sizeof(int) * (size_t)fuse_.cap_sets * 16, s));   // the tickets start at zero; the kernels reset them
-    }
     // misc: [sets][6] coarse | [sets][6] shifts | [sets] tickets
     int* d_coarse = fuse_.misc;
     int* d_sh = fuse_.misc + 6 * fuse_.cap_sets;
     unsigned* d_ticket = reinterpret_cast<unsigned*>(fuse_.misc + 12 * fuse_.cap_sets);
-    FuseWlut lut;
-    std::memcpy(lut.w, host_wluts, sizeof(lut.w));
+    FuseWlut lut{};
+    if (host_wluts) std::memcpy(lut.w, host_wluts, sizeof(lut.w));
     prof_begin(FAM_FUSION, s, 0, (double)nsets * (k + 1) * px * 3);
-    const unsigned* d_wluts = nullptr;
-    if (nsets > 1) {      // one table per set (its own noise score); a single call carries its table in the kernel arguments
+    const unsigned* d_wluts = host_wluts ? nullptr : fuse_.wlut;
+    if (host_wluts && nsets > 1) {      // one table per set (its own noise score); a single call carries its table in the kernel arguments
         // (copied on a stream of their own, beside the luma and SAD kernels, with the blend waiting on an event: measured, the chain is
         //  8 us LONGER -- the cross-stream wait costs more than the ~4 us copy in front: profiles/r03_experiments.md)
         IRE_HIP(hipMemcpyAsync(fuse_.wlut, host_wluts, sizeof(unsigned) * 256 * nsets, hipMemcpyHostToDevice, s));   // pageable source: staged before the call returns

@@ -218,6 +218,53 @@ class Engine:
         h, w = _jpeg_frame_size(data)
         return (job, h, w)
 
+    def submit_fuse_fit(self, views, is_jpeg=True, scores=None):
+        """Queue ONE fusion job: views [k,H,W,3] uint8 (or a list of k [H,W,3] arrays), k in 2..3, any size 1..8192 per side.  Every
+        view is restored as submit_fit() restores it, the restored views are fused on the device (noise score of view 0, as
+        fuse(noise_score=-1) takes it) and poll() returns the fused [H,W,3] image -- on a text engine its text.  is_jpeg: one bool or
+        k of them; scores: None, or k entries each None or the 7 scores classify() gave for that view.  poll() / release() take the
+        job as they take submit()'s; the polled scores are view 0's."""
+        vs = [np.ascontiguousarray(v, dtype=np.uint8) for v in views]
+        k = len(vs)
+        if k and any(v.ndim != 3 or v.shape[2] != 3 or v.shape != vs[0].shape for v in vs):
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid input: fusion views must be [H,W,3] uint8 of identical dimensions")
+        h, w = (vs[0].shape[0], vs[0].shape[1]) if k else (0, 0)
+        jp = np.ascontiguousarray(np.broadcast_to(np.asarray(is_jpeg, dtype=np.uint8), (k,)))
+        has = np.zeros(max(k, 1), np.uint8)
+        sc = np.zeros((max(k, 1), 7), np.float64)
+        if scores is not None and len(scores) != k:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid input: scores must have one entry (7 scores or None) for each fusion view")
+        for i, row in enumerate(scores if scores is not None else []):
+            if row is not None:
+                has[i] = 1
+                sc[i] = np.asarray(row, dtype=np.float64).reshape(7)
+        ptrs = (ctypes.c_void_p * max(k, 1))(*[v.ctypes.data for v in vs])
+        job = ctypes.c_void_p()
+        self._check(self._lib.ire_submit_fuse_fit(self._h, ptrs, k, h, w, _ptr(jp), _ptr(has), _ptr(sc), ctypes.byref(job)))
+        return (job, h, w)
+
+    def restore_fuse_fit_tensor(self, views_u8, out_u8=None, scores=None, is_jpeg_u8=None, stream=None):
+        """The fusion job's computation for tensors, asynchronous on the torch stream: views cuda uint8 [B,k,H,W,3] (B view sets of
+        k in 2..3 views, any size 1..8192 per side, B*k <= max_batch) -> fused cuda uint8 [B,H,W,3].  scores: cuda float64 [B*k,7]
+        for every view, or None: classified inside."""
+        import torch
+        assert views_u8.is_cuda and views_u8.dtype == torch.uint8 and views_u8.is_contiguous() and views_u8.dim() == 5
+        b, k, h, w, _ = views_u8.shape
+        if out_u8 is None:
+            out_u8 = torch.empty((b, h, w, 3), dtype=torch.uint8, device=views_u8.device)
+        sc = ctypes.c_void_p(scores.data_ptr()) if scores is not None else None
+        jp = ctypes.c_void_p(is_jpeg_u8.data_ptr()) if is_jpeg_u8 is not None else None
+        self._check(self._lib.ire_restore_fuse_fit_device(self._h, ctypes.c_void_p(views_u8.data_ptr()), b, k, h, w, sc, jp,
+                                                          ctypes.c_void_p(out_u8.data_ptr()), self._stream_ptr(stream)))
+        return out_u8
+
+    def fusion_wlut(self, noise):
+        """noise scores [n] -> blend tables [n,256] uint32, built on the device by the kernel the fusion jobs use (ire_debug_fusion_wlut)."""
+        ns = np.ascontiguousarray(np.asarray(noise, dtype=np.float64).reshape(-1))
+        out = np.zeros((ns.size, 256), np.uint32)
+        self._check(self._lib.ire_debug_fusion_wlut(self._h, _ptr(ns), ns.size, _ptr(out)))
+        return out
+
     def stats(self):
         """Service gauges (f4: getHealthStatus / the /health/ready dependency entry)."""
         st = _lib.IreEngineStats()

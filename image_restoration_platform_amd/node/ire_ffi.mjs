@@ -39,6 +39,8 @@ export function bindIre(libPath) {
     ire_encode_png_base64_fit: ['int', [P, P, 'int', 'int', 'int', P, 'size_t']],
     ire_submit_fit: ['int', [P, P, 'int', 'int', 'int', P, PP]],
     ire_submit_jpeg: ['int', [P, P, 'size_t', P, PP]],
+    ire_submit_fuse_fit: ['int', [P, P, 'int', 'int', 'int', P, P, P, PP]],
+    ire_restore_fuse_fit_device: ['int', [P, P, 'int', 'int', 'int', 'int', P, P, P, P]],
     ire_submit: ['int', [P, P, 'int', 'int', 'int', P, PP]],
     ire_poll: ['int', [P, P, 'int', P, P, P]],
     ire_poll_text: ['int', [P, P, 'int', P, 'size_t', P, P, P]],
@@ -68,6 +70,7 @@ export function bindIre(libPath) {
     ire_strips_get_output: ['int', [P, P, P]],
     ire_get_stats: ['int', [P, P]],
     ire_debug_classifier_sums: ['int', [P, 'int', P]],
+    ire_debug_fusion_wlut: ['int', [P, P, 'int', P]],
     ire_debug_capture: ['int', [P, 'int']],
     ire_debug_activation: ['int', [P, 'string', P, P]],
     ire_profile_enable: ['int', [P, 'int']],

@@ -97,16 +97,6 @@ def encode_jpeg_base64(rgb, quality=85):
 RESULT_CODEC = os.environ.get("IRE_RESULT_CODEC", "png")
 
 
-def pad_to_multiple(rgb, m=8, min_size=16):
-    """edge-replicate pad so H, W are multiples of m (RestoreNet has three stride-2 levels)."""
-    h, w, _ = rgb.shape
-    H = max(min_size, (h + m - 1) // m * m)
-    W = max(min_size, (w + m - 1) // m * m)
-    if (H, W) == (h, w):
-        return rgb, (h, w)
-    return np.ascontiguousarray(np.pad(rgb, ((0, H - h), (0, W - w), (0, 0)), mode="edge")), (h, w)
-
-
 class _Seen:
     """What analyze() learnt about a buffer, for the restoreImage() that follows on the SAME object
     (restorator.js:59-94 hands one Buffer to both seams): decoded pixels + the 7 scores, so a job is
@@ -211,25 +201,12 @@ class EngineRestorer:
             rgb, fmt, scores = decoded[0]
             out, _, _ = self.engine.poll(self.engine.submit_fit(rgb, is_jpeg=(fmt == "jpeg"), scores=scores))
             return self._reply(out.decode("ascii") if text_engine else self._encode(out))
-        # every view goes to the engine's batcher (ire_submit) before the first ire_poll: the views of this call and the
-        # single-image jobs of the other in-flight calls (restore_batch keeps 3 in flight) coalesce into engine batches
-        jobs = []
-        for rgb, fmt, scores in decoded:
-            padded, (h, w) = pad_to_multiple(rgb)
-            if scores is None and padded.shape != rgb.shape:
-                # condition on the image's own scores (what analyze() reports), never on its replicate-padded copy's
-                scores = self.engine.classify(rgb, is_jpeg=(fmt == "jpeg"))[0][0]
-            jobs.append((self.engine.submit(padded, is_jpeg=(fmt == "jpeg"), scores=scores), h, w))
-        restored = []
-        for job, h, w in jobs:
-            out, _, _ = self.engine.poll(job)
-            if text_engine:                                               # fusion needs the views' pixels: decode the device's PNG
-                out = decode_image(base64.b64decode(out))[0]
-            restored.append(np.ascontiguousarray(out[:h, :w]))
-        views = np.stack(restored, axis=0)
-        padded = np.stack([pad_to_multiple(v)[0] for v in views], axis=0)
-        fused, _ = self.engine.fuse(padded, noise_score=-1.0)
-        return self._reply(self._encode(np.ascontiguousarray(fused[:views.shape[1], :views.shape[2]])))
+        # 2..3 views are ONE fusion job of the engine's batcher (ire_submit_fuse_fit): every view restored as a single job would be (its
+        # own scores from analyze() where it ran, else classified in the batch), the views fused on the device, the h x w result
+        # polled -- on a flagged engine as its text, which IS the reply.  No host pad, decode, crop or second encode.
+        job = self.engine.submit_fuse_fit([d[0] for d in decoded], is_jpeg=[d[1] == "jpeg" for d in decoded], scores=[d[2] for d in decoded])
+        out, _, _ = self.engine.poll(job)
+        return self._reply(out.decode("ascii") if text_engine else self._encode(out))
 
 
 class RestoratorService:

@@ -290,6 +290,24 @@ int ire_submit_fit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg,
  * creates no job: such a file stays with the host codec.  A file whose DATA the device finds corrupt fails only its own job, at
  * its poll: IRE_ERR_INVALID_INPUT "invalid: corrupt JPEG data (decoder status N)"; the other jobs of its batch complete. */
 int ire_submit_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, const double* scores, ire_job** job_out);
+/* A FUSION job: k = 2 or 3 views of one scene, all h x w with h, w in 1..8192 (views[v]: h*w*3 bytes, copied before return),
+ * submitted once, computed on the device with its batch, polled and released like every other job; its result is the fused h x w
+ * image -- pixels, or on a text engine the engine's result text.  Every view is restored as ire_submit_fit restores it (scores of
+ * the view's own pixels unless has_scores[v] says that scores + 7*v holds them; is_jpeg NULL: all 1); each restored window is
+ * edge-replicated to HF x WF, HF = max(64, ceil8(h)) and WF likewise; the padded set is fused as ire_fuse fuses it with
+ * noise_score < 0 (view 0 of the padded set classified, its noise score the blend table's); the fused image is cropped to h x w.
+ * For h, w >= 64 on a pixel engine: the bytes of ire_submit_fit per view, edge pad, ire_fuse(noise_score = -1), crop.  scores_out
+ * of the poll: view 0's.  Fusion jobs are coalesced by (h, w, k), min(max_batch / k, 16) jobs a batch, never with another kind of job.
+ * k outside 2..3, a null view, a size outside 1..8192 or an engine with max_batch < k: IRE_ERR_INVALID_INPUT, no job. */
+int ire_submit_fuse_fit(ire_engine* e, const uint8_t* const* views, int k, int h, int w,
+                        const uint8_t* is_jpeg /* [k] or NULL */, const uint8_t* has_scores /* [k] or NULL */,
+                        const double* scores /* [k][7] */, ire_job** job_out);
+/* The same computation for a caller on the device, asynchronous on `stream`: d_views [nsets][k][h][w][3] -> d_out_rgb
+ * [nsets][h][w][3]; d_scores [nsets*k][7] (device) for every view, or NULL: classified inside.  nsets <= 16, nsets*k <= max_batch.
+ * No host round trip: the blend tables are built on the device. */
+int ire_restore_fuse_fit_device(ire_engine* e, const uint8_t* d_views, int nsets, int k, int h, int w,
+                                const double* d_scores /* [nsets*k][7] or NULL */, const uint8_t* d_is_jpeg,
+                                uint8_t* d_out_rgb, void* stream);
 /* Wait up to timeout_ms (<0: forever) for the job; on IRE_OK out_rgb (h*w*3 pixel bytes, or with IRE_FLAG_RESULT_PNG_BASE64
  * ire_png_base64_bytes_fit(h, w) characters -- for an ire_submit job the same number as ire_png_base64_bytes(h, w), which is 0
  * for the ragged widths ire_submit_fit takes: size the buffer with the _fit form), scores_out (7, may
@@ -375,6 +393,8 @@ int ire_get_stats(ire_engine* e, ire_engine_stats* out);
 /* Raw integer accumulators of the classifier scan for n images (14 u64 each, order documented in
  * csrc/classifier_finalize.hpp) of the last classify / restore call, copied to host. */
 int ire_debug_classifier_sums(ire_engine* e, int n, uint64_t* sums_out);
+/* The blend tables of n noise scores (host), built on the device by the kernel the fusion jobs use, copied to out (tests only). */
+int ire_debug_fusion_wlut(ire_engine* e, const double* noise, int n, uint32_t* out /* [n][256] */);
 /* Turn per-layer capture on/off (slow: synchronises after every layer; tests only). */
 int ire_debug_capture(ire_engine* e, int on);
 /* Copy one named intermediate activation of the last ire_restore* call to host as float32 NHWC.

@@ -14,10 +14,6 @@
 
 #include "affinity.hpp"
 #include "batcher.hpp"
-#include "deflate.hpp"
-#include "jpeg.hpp"
-#include "jpeg_parse.hpp"
-#include "encode.hpp"
 #include "engine.hpp"
 #include "fusion.hpp"
 #include "strips.hpp"
@@ -116,26 +112,22 @@ struct HipBatchBackend {
     int device;
     CpuPlan plan;
     hipStream_t cs = nullptr, os = nullptr;      // copy-in | copy-out
-    HipBatchBackend(Engine& e, int dev) : E(e), device(dev), plan(plan_for_device(dev)) {}
+    const TextFormat* const fmt;                 // the results' format (codec.hpp); null: pixels
+    HipBatchBackend(Engine& e, int dev) : E(e), device(dev), plan(plan_for_device(dev)), fmt(e.result_format()) {}
     ~HipBatchBackend() {
         DeviceGuard g(device);
         if (cs) { (void)hipStreamSynchronize(cs); (void)hipStreamDestroy(cs); }
         if (os) { (void)hipStreamSynchronize(os); (void)hipStreamDestroy(os); }
     }
     int max_batch() const { return E.max_batch(); }
-    bool deflate() const { return (E.flags() & IRE_FLAG_RESULT_PNG_DEFLATE) != 0; }
-    bool jpeg() const { return (E.flags() & IRE_FLAG_RESULT_JPEG) != 0; }
-    bool var_len() const { return deflate() || jpeg(); }      // the text's length depends on the pixels
-    bool text() const { return (E.flags() & (IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG)) != 0; }
-    size_t var_bound(int h, int w) const { return jpeg() ? jpeg_base64_bound(h, w) : png_deflate_base64_bound(h, w); }
     // a result's place in the staging: the pixels, the stored PNG's text, or [uint64 count | the compressed PNG's or the JPEG's text, bound-sized]
-    size_t out_bytes(int h, int w) const { return var_len() ? 8 + var_bound(h, w) : text() ? png_base64_chars(h, w) : (size_t)h * w * 3; }
+    size_t out_bytes(int h, int w) const { return fmt ? fmt->place_bytes(h, w) : (size_t)h * w * 3; }
     // the batcher's optional hook: only a text of data-dependent length is shorter than its place
     const uint8_t* result_view(const uint8_t* place, int h, int w, size_t* len) const {
-        if (!var_len()) { *len = out_bytes(h, w); return place; }
+        if (!fmt || !fmt->counted) { *len = out_bytes(h, w); return place; }
         uint64_t n = 0;
         std::memcpy(&n, place, 8);
-        *len = (size_t)std::min<uint64_t>(n, var_bound(h, w));
+        *len = (size_t)std::min<uint64_t>(n, fmt->bound(h, w));
         return place + 8;
     }
     void start() {
@@ -153,7 +145,7 @@ struct HipBatchBackend {
         HipSlot& hs = b.impl ? *static_cast<HipSlot*>(b.impl) : *fresh;
         std::unique_ptr<SlotEvents> ev(b.fixed ? nullptr : new SlotEvents());
         if (ev) ev->create();
-        hs.reserve(bytes, mb, text());        // the strong guarantee is SlotMem's
+        hs.reserve(bytes, mb, fmt != nullptr);        // the strong guarantee is SlotMem's
         if (ev) hs.ev = std::move(ev);        // (nothing from here on throws)
         if (fresh) b.impl = fresh.release();
         b.pin_in = hs.pin_in.get<uint8_t>(); b.pin_out = hs.pin_out.get<uint8_t>(); b.pin_jp = hs.pin_jp.get<uint8_t>();
@@ -169,7 +161,7 @@ struct HipBatchBackend {
     std::shared_ptr<void> file_plan(const uint8_t* file, size_t bytes, int* h, int* w, size_t* room) {
         auto head = std::make_shared<JpegFileHead>();
         std::string why;
-        if (!jpegparse::plan_file(file, bytes, E.decode_accept(), head->hd, why)) fail(IRE_ERR_INVALID_INPUT, why);
+        if (!jpegparse::plan_file(file, bytes, E.jpeg_decoder().accept(), head->hd, why)) fail(IRE_ERR_INVALID_INPUT, why);
         *h = head->hd.hd.im.h; *w = head->hd.hd.im.w;
         *room = jpegparse::file_room(head->hd, bytes);
         return head;
@@ -205,7 +197,7 @@ struct HipBatchBackend {
                 const JpegFileHead& f = *static_cast<const JpegFileHead*>(heads[i]);
                 hd[n] = &f.hd; streams[n] = f.streams.data(); bytes[n] = b.pin_in + ib * (size_t)(first + i); room[n] = used[i];
             }
-            E.decode_jpeg_streams(hd, streams, bytes, room, n, h, w, hs.d_in.get<uint8_t>() + ib * (size_t)(first + i0), ib, hs.d_fstat.get<int32_t>() + first + i0, cs);
+            E.jpeg_decoder().decode_streams(hd, streams, bytes, room, n, h, w, hs.d_in.get<uint8_t>() + ib * (size_t)(first + i0), ib, hs.d_fstat.get<int32_t>() + first + i0, cs);
         }
     }
     int file_status(SlotBufs& b, int i) { return static_cast<HipSlot*>(b.impl)->pin_fstat.get<int32_t>()[i]; }
@@ -228,12 +220,12 @@ struct HipBatchBackend {
             IRE_HIP(hipStreamWaitEvent(ms, hs.ev->in, 0));
             IRE_HIP(hipEventRecord(hs.ev->c0, ms));
             // classifies the jobs that brought no scores; a shape the network cannot take as it is (ire_submit_fit) is padded into the
-            // engine's staging and its window comes back; with text() the results leave the device as text
+            // engine's staging and its window comes back; with a text format the results leave the device as text
             if (k) {
-                E.restore_fuse_fit_device_mixed(hs.d_in.get<uint8_t>(), n, k, h, w, b.pin_sc_in, has_sc, hs.d_jp.get<uint8_t>(), hs.d_out.get<uint8_t>(), text() ? hs.d_txt.get<uint8_t>() : nullptr, (out_bytes(h, w) + 255) / 256 * 256, ms);
+                E.restore_fuse_fit_device_mixed(hs.d_in.get<uint8_t>(), n, k, h, w, b.pin_sc_in, has_sc, hs.d_jp.get<uint8_t>(), hs.d_out.get<uint8_t>(), fmt ? hs.d_txt.get<uint8_t>() : nullptr, (out_bytes(h, w) + 255) / 256 * 256, ms);
                 IRE_HIP(hipMemcpy2DAsync(b.pin_sc, sizeof(double) * 7, E.scores_device(), sizeof(double) * 7 * k, sizeof(double) * 7, (size_t)n, hipMemcpyDeviceToHost, ms));      // view 0 of every job
             } else {
-                E.restore_fit_device_mixed(hs.d_in.get<uint8_t>(), n, h, w, b.pin_sc_in, has_sc, hs.d_jp.get<uint8_t>(), hs.d_out.get<uint8_t>(), text() ? hs.d_txt.get<uint8_t>() : nullptr, (out_bytes(h, w) + 255) / 256 * 256, ms);
+                E.restore_fit_device_mixed(hs.d_in.get<uint8_t>(), n, h, w, b.pin_sc_in, has_sc, hs.d_jp.get<uint8_t>(), hs.d_out.get<uint8_t>(), fmt ? hs.d_txt.get<uint8_t>() : nullptr, (out_bytes(h, w) + 255) / 256 * 256, ms);
                 IRE_HIP(hipMemcpyAsync(b.pin_sc, E.scores_device(), sizeof(double) * 7 * n, hipMemcpyDeviceToHost, ms));
             }
             if (hs.file_jobs) IRE_HIP(hipMemcpyAsync(hs.pin_fstat.get<int32_t>(), hs.d_fstat.get<int32_t>(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ms));
@@ -242,7 +234,7 @@ struct HipBatchBackend {
             IRE_HIP(hipEventRecord(hs.ev->cw, ms));
         });
         IRE_HIP(hipStreamWaitEvent(os, hs.ev->c1, 0));
-        if (text()) {
+        if (fmt) {
             const size_t ob = out_bytes(h, w), st = (ob + 255) / 256 * 256;
             for (int i = 0; i < n; ++i) IRE_HIP(hipMemcpyAsync(b.pin_out + ob * i, hs.d_txt.get<uint8_t>() + st * i, ob, hipMemcpyDeviceToHost, os));
         } else IRE_HIP(hipMemcpyAsync(b.pin_out, hs.d_out.get<uint8_t>(), ib * n, hipMemcpyDeviceToHost, os));
@@ -349,9 +341,7 @@ int ire_init(const ire_config* cfg, ire_engine** out) {
     return guarded([&] {
         if (!cfg || !out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_init");
         if (cfg->struct_size < sizeof(ire_config)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.struct_size");
-        constexpr uint32_t kResultBits = IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG;
-        if (cfg->flags & ~(kResultBits | IRE_FLAG_DECODE_PROGRESSIVE)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
-        if (((cfg->flags & kResultBits) & ((cfg->flags & kResultBits) - 1)) != 0) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");
+        check_config_flags(cfg->flags);       // (before any device is touched)
         *out = nullptr;
         std::unique_ptr<ire_engine> E(new ire_engine());
         E->eng.reset(new Engine(*cfg));
@@ -462,74 +452,70 @@ int ire_preprocess_device(ire_engine* e, const uint8_t* d_rgb, int h, int w, int
     });
 }
 
-size_t ire_png_base64_bytes(int h, int w) { return (h >= 1 && w >= 8 && w % 8 == 0 && h <= 16384 && w <= 16384) ? png_base64_chars(h, w) : 0; }
+size_t ire_png_base64_bytes(int h, int w) { return (h >= 1 && w >= 8 && w % 8 == 0 && h <= 16384 && w <= 16384) ? kStoredPng.bound(h, w) : 0; }
 
 int ire_encode_png_base64_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, uint8_t* d_chars, size_t stride_bytes, void* stream) {
     return guarded([&] {
         Engine& E = eng(e);
-        on_stream(E, (hipStream_t)stream, [&] { E.encode_png_base64_device(d_rgb, n, h, w, d_chars, stride_bytes, (hipStream_t)stream); });
+        on_stream(E, (hipStream_t)stream, [&] { E.text_encoder().encode_png_aligned_device(d_rgb, n, h, w, d_chars, stride_bytes, (hipStream_t)stream); });
     });
 }
 
 int ire_encode_png_base64(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes) {
     return guarded([&] {
         Engine& E = eng(e);
-        on_stream(E, E.main_stream(), [&] { E.encode_png_base64_host(rgb, n, h, w, chars, stride_bytes); });
+        on_stream(E, E.main_stream(), [&] { E.text_encoder().encode_png_aligned_host(rgb, n, h, w, chars, stride_bytes); });
     });
 }
 
-size_t ire_png_base64_bytes_fit(int h, int w) { return (h >= 1 && w >= 1 && h <= 8192 && w <= 8192) ? png_base64_chars(h, w) : 0; }
+size_t ire_png_base64_bytes_fit(int h, int w) { return (h >= 1 && w >= 1 && h <= 8192 && w <= 8192) ? kStoredPng.bound(h, w) : 0; }
 
 int ire_encode_png_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes, size_t image_pitch_bytes,
                                      uint8_t* d_chars, size_t stride_bytes, void* stream) {
     return guarded([&] {
         Engine& E = eng(e);
-        on_stream(E, (hipStream_t)stream, [&] { E.encode_png_base64_fit_device(d_rgb, n, h, w, row_pitch_bytes, image_pitch_bytes, d_chars, stride_bytes, (hipStream_t)stream); });
+        on_stream(E, (hipStream_t)stream, [&] { E.text_encoder().encode_device(kStoredPng, d_rgb, n, h, w, row_pitch_bytes, image_pitch_bytes, d_chars, stride_bytes, nullptr, (hipStream_t)stream); });
     });
 }
 
 int ire_encode_png_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes) {
     return guarded([&] {
         Engine& E = eng(e);
-        on_stream(E, E.main_stream(), [&] { E.encode_png_base64_fit_host(rgb, n, h, w, chars, stride_bytes); });
+        on_stream(E, E.main_stream(), [&] { E.text_encoder().encode_host(kStoredPng, rgb, n, h, w, chars, stride_bytes, nullptr); });
     });
 }
 
-size_t ire_png_deflate_base64_bound(int h, int w) { return (h >= 1 && w >= 1 && h <= 8192 && w <= 8192) ? png_deflate_base64_bound(h, w) : 0; }
+size_t ire_png_deflate_base64_bound(int h, int w) { return (h >= 1 && w >= 1 && h <= 8192 && w <= 8192) ? kDeflatePng.bound(h, w) : 0; }
 
 int ire_encode_png_deflate_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes, size_t image_pitch_bytes,
                                              uint8_t* d_chars, size_t stride_bytes, uint64_t* d_lens, void* stream) {
     return guarded([&] {
         Engine& E = eng(e);
-        on_stream(E, (hipStream_t)stream, [&] {
-            E.encode_png_deflate_base64_fit_device(d_rgb, n, h, w, row_pitch_bytes, image_pitch_bytes, d_chars, stride_bytes, d_lens, (hipStream_t)stream);
-        });
+        on_stream(E, (hipStream_t)stream, [&] { E.text_encoder().encode_device(kDeflatePng, d_rgb, n, h, w, row_pitch_bytes, image_pitch_bytes, d_chars, stride_bytes, d_lens, (hipStream_t)stream); });
     });
 }
 
 int ire_encode_png_deflate_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes, uint64_t* lens) {
     return guarded([&] {
         Engine& E = eng(e);
-        on_stream(E, E.main_stream(), [&] { E.encode_png_deflate_base64_fit_host(rgb, n, h, w, chars, stride_bytes, lens); });
+        on_stream(E, E.main_stream(), [&] { E.text_encoder().encode_host(kDeflatePng, rgb, n, h, w, chars, stride_bytes, lens); });
     });
 }
 
-size_t ire_jpeg_base64_bound(int h, int w) { return (h >= 1 && w >= 1 && h <= 8192 && w <= 8192) ? jpeg_base64_bound(h, w) : 0; }
+size_t ire_jpeg_base64_bound(int h, int w) { return (h >= 1 && w >= 1 && h <= 8192 && w <= 8192) ? kJpeg.bound(h, w) : 0; }
 
 int ire_encode_jpeg_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes, size_t image_pitch_bytes, uint8_t* d_chars,
                                       size_t stride_bytes, uint64_t* d_lens, void* stream) {
     return guarded([&] {
         Engine& E = eng(e);
-        on_stream(E, (hipStream_t)stream, [&] {
-            E.encode_jpeg_base64_fit_device(d_rgb, n, h, w, row_pitch_bytes, image_pitch_bytes, d_chars, stride_bytes, d_lens, (hipStream_t)stream);
-        });
+        on_stream(E, (hipStream_t)stream, [&] { E.text_encoder().encode_device(kJpeg, d_rgb, n, h, w, row_pitch_bytes, image_pitch_bytes, d_chars, stride_bytes, d_lens, (hipStream_t)stream); });
     });
 }
 
 int ire_encode_jpeg_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes, uint64_t* lens) {
     return guarded([&] {
         Engine& E = eng(e);
-        on_stream(E, E.main_stream(), [&] { E.encode_jpeg_base64_fit_host(rgb, n, h, w, chars, stride_bytes, lens); });
+        on_stream(E, E.main_stream(), [&] { E.text_encoder().encode_host(kJpeg, rgb, n, h, w, chars, stride_bytes, lens); });
     });
 }
 
@@ -564,7 +550,7 @@ int ire_decode_jpeg_plan_ex(const uint8_t* file, size_t bytes, uint32_t accept, 
 int ire_decode_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, uint8_t* out_rgb, int h, int w) {
     return guarded([&] {
         Engine& E = eng(e);
-        on_stream(E, E.main_stream(), [&] { E.decode_jpeg_host(file, bytes, out_rgb, h, w); });
+        on_stream(E, E.main_stream(), [&] { E.jpeg_decoder().decode_host(file, bytes, out_rgb, h, w); });
     });
 }
 
@@ -572,7 +558,7 @@ int ire_decode_jpeg_device(ire_engine* e, const uint8_t* const* files, const siz
                            int32_t* d_status, void* stream) {
     return guarded([&] {
         Engine& E = eng(e);
-        on_stream(E, (hipStream_t)stream, [&] { E.decode_jpeg_device(files, bytes, n, h, w, d_rgb, image_pitch_bytes, d_status, (hipStream_t)stream); });
+        on_stream(E, (hipStream_t)stream, [&] { E.jpeg_decoder().decode_files(files, bytes, n, h, w, d_rgb, image_pitch_bytes, d_status, (hipStream_t)stream); });
     });
 }
 
@@ -754,7 +740,7 @@ int ire_poll(ire_engine* e, ire_job* job, int timeout_ms, uint8_t* out_rgb, doub
         eng(e);
         if (!job || !job->j) fail(IRE_ERR_INVALID_INPUT, "invalid job handle");
         // a result of data-dependent length has no way out of this call: refuse it and keep the job (no result is lost to a wrong call)
-        if (e->backend->var_len()) fail(IRE_ERR_INVALID_INPUT, "invalid: use ire_poll_text (this engine's results have data-dependent lengths)");
+        if (e->backend->fmt && e->backend->fmt->counted) fail(IRE_ERR_INVALID_INPUT, "invalid: use ire_poll_text (this engine's results have data-dependent lengths)");
         std::string err;
         const int st = e->batcher->poll(job->j, timeout_ms, out_rgb, scores_out, t, &err);
         if (st == IRE_ERR_TIMEOUT) fail(IRE_ERR_TIMEOUT, "timeout: job still pending");       // the handle stays valid: poll again or ire_job_release

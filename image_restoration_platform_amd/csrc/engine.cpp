@@ -5,9 +5,6 @@
 #include "engine.hpp"
 #include "encode.hpp"
 #include "fusion.hpp"
-#include "deflate.hpp"
-#include "jpeg.hpp"
-#include "jpeg_dec.hpp"
 
 #include <chrono>
 #include <cmath>
@@ -49,15 +46,11 @@ Engine::Engine(const ire_config& cfg) {
     if (max_batch_ > 64) fail(IRE_ERR_INVALID_INPUT, "invalid max_batch (1..64)");
     num_lanes_ = cfg.num_streams > 0 ? cfg.num_streams : 1;
     if (num_lanes_ > 16) num_lanes_ = 16;
-    constexpr uint32_t kResultBits = IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG;
-    if (cfg.flags & ~(kResultBits | IRE_FLAG_DECODE_PROGRESSIVE)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
-    if (((cfg.flags & kResultBits) & ((cfg.flags & kResultBits) - 1)) != 0) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");
-    flags_ = cfg.flags;
+    check_config_flags(cfg.flags);
+    result_format_ = result_format_of(cfg.flags);
     sw_ = ConvSwitches::from_env();
     cus_ = persistent_grid_cus();
     if (const char* v = std::getenv("IRE_SNAKE")) snake_ = std::atoi(v) != 0;
-    if (const char* v = std::getenv("IRE_JPEG_DEC_TIMES")) dec_times_ = std::atoi(v) != 0;
-    if (const char* v = std::getenv("IRE_JPEG_DEC_WINDOWS")) dec_min_windows_ = (uint32_t)std::max(0, std::atoi(v));
     if (const char* v = std::getenv("IRE_RB_STAMPS")) {   // diagnostic: "<cout>[r]" = stamp the first such ResBlock conv
         stamps_cout_ = std::atoi(v);
         stamps_resid_ = std::strchr(v, 'r') != nullptr;
@@ -65,6 +58,8 @@ Engine::Engine(const ire_config& cfg) {
     if (const char* v = std::getenv("IRE_W4_TL")) stamps_tl_ = v;     // diagnostic (-DIRE_W4_TL builds): CSV path of the workgroup timeline of the LAST stamped launch
 
     IRE_HIP(hipStreamCreateWithFlags(&main_stream_, hipStreamNonBlocking));
+    enc_.setup(max_batch_, main_stream_);
+    dec_.setup(max_batch_, (cfg.flags & IRE_FLAG_DECODE_PROGRESSIVE) ? jpegparse::kAcceptProgressive : 0u, main_stream_);
     for (auto& ev : ev_) IRE_HIP(hipEventCreate(&ev));
     IRE_HIP(hipEventCreateWithFlags(&fork_ev_, hipEventDisableTiming));
     IRE_HIP(hipEventCreateWithFlags(&busy_ev_, hipEventDisableTiming));
@@ -94,14 +89,7 @@ Engine::Engine(const ire_config& cfg) {
 Engine::~Engine() {
     (void)hipSetDevice(device_);
     (void)hipDeviceSynchronize();
-    if (dec_times_) {
-        dec_times_collect();
-        std::fprintf(stderr,
-                     "{\"jpeg_dec_kernel_ms\": {\"memset\": %.4f, \"long\": %.4f, \"spec\": %.4f, \"chain\": %.4f, \"write\": %.4f, \"short\": %.4f, \"idct\": %.4f, "
-                     "\"colour\": %.4f, \"calls\": %lld, \"later_scans\": %.4f}}\n",
-                     dec_ms_[0], dec_ms_[1], dec_ms_[2], dec_ms_[3], dec_ms_[4], dec_ms_[5], dec_ms_[7], dec_ms_[8], (long long)dec_calls_, dec_ms_[6]);
-        for (hipEvent_t ev : dec_marks_) if (ev) (void)hipEventDestroy(ev);
-    }
+    dec_.report_times();
     if (stamps_dev_ && std::getenv("IRE_STAMPS_RAW")) {     // diagnostic builds with their own stamp layout (conv_pk.hip PK_TICKS): the whole buffer, one value per line
         std::vector<unsigned long long> h(8 * 2 * 64 * 10);
         (void)hipMemcpy(h.data(), stamps_dev_.get<void>(), h.size() * 8, hipMemcpyDeviceToHost);
@@ -287,258 +275,6 @@ void Engine::ensure_pad(int n, int H, int W) {
     const size_t want = batch_room(need, per * (size_t)max_batch_);
     d_pad_in_.grow(need, want);
     d_pad_out_.grow(need, want);
-}
-
-// both encoders' per-batch scratch (`full`: what a whole batch of the shape needs) and the host entries' staging, pixels in | text out
-void Engine::ensure_enc_scratch(size_t need, size_t full) {
-    if (need > d_enc_scratch_.bytes()) IRE_HIP(hipDeviceSynchronize());
-    d_enc_scratch_.grow(need, batch_room(need, full));
-}
-uint8_t* Engine::ensure_enc_io(size_t need) {
-    if (need > d_enc_io_.bytes()) IRE_HIP(hipDeviceSynchronize());
-    d_enc_io_.grow(need);
-    return d_enc_io_.get<uint8_t>();
-}
-
-// the one encoder behind every entry: the window of n images -> n texts.  Three launches and one small memset per batch.
-void Engine::encode_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, hipStream_t s) {
-    if (stride < png_base64_chars(h, w)) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the PNG encoder: smaller than ire_png_base64_bytes(h, w)");
-    if (row_pitch < (size_t)3 * w || (n > 1 && image_pitch < row_pitch * (size_t)(h - 1) + (size_t)3 * w))
-        fail(IRE_ERR_INVALID_INPUT, "invalid pitch for the PNG encoder: rows or images overlap");
-    ensure_enc_scratch(png_scratch_bytes(n, h, w), png_scratch_bytes(max_batch_, h, w));
-    encode_png_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_enc_scratch_.get<uint8_t>(), d_chars, stride, s);
-}
-
-void Engine::encode_png_base64_device(const uint8_t* d_rgb, int n, int h, int w, uint8_t* d_chars, size_t stride, hipStream_t s) {
-    if (!d_rgb || !d_chars || n < 1 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images)");
-    if (h < 1 || w < 8 || w % 8 || h > 16384 || w > 16384) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder: width must be a multiple of 8");
-    encode_window(d_rgb, n, h, w, (size_t)3 * w, (size_t)3 * w * h, d_chars, stride, s);
-}
-
-void Engine::encode_png_base64_fit_device(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride,
-                                          hipStream_t s) {
-    if (!d_rgb || !d_chars || n < 1 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images)");
-    if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder: height and width must be in 1..8192");
-    encode_window(d_rgb, n, h, w, row_pitch, image_pitch, d_chars, stride, s);
-}
-
-void Engine::encode_host_impl(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride) {
-    const size_t ib = (size_t)h * w * 3, cb = png_base64_chars(h, w), cpad = (cb + 255) / 256 * 256;
-    if (stride < cb) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the PNG encoder: smaller than ire_png_base64_bytes(h, w)");
-    const size_t in_pad = (ib * n + 255) / 256 * 256;
-    uint8_t* d_px = ensure_enc_io(in_pad + cpad * (size_t)n);
-    hipStream_t s = main_stream_;
-    IRE_HIP(hipMemcpyAsync(d_px, rgb, ib * n, hipMemcpyHostToDevice, s));
-    uint8_t* d_txt = d_px + in_pad;
-    encode_window(d_px, n, h, w, (size_t)3 * w, ib, d_txt, cpad, s);
-    for (int i = 0; i < n; ++i) IRE_HIP(hipMemcpyAsync(chars + stride * i, d_txt + cpad * i, cb, hipMemcpyDeviceToHost, s));
-    IRE_HIP(hipStreamSynchronize(s));
-}
-
-void Engine::encode_png_base64_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride) {
-    if (!rgb || !chars) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder: null buffer");
-    if (n < 1 || n > max_batch_ || h < 1 || w < 8 || w % 8 || h > 16384 || w > 16384) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images, width a multiple of 8)");
-    encode_host_impl(rgb, n, h, w, chars, stride);
-}
-
-void Engine::encode_png_base64_fit_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride) {
-    if (!rgb || !chars) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder: null buffer");
-    if (n < 1 || n > max_batch_ || h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images, 1..8192 per side)");
-    encode_host_impl(rgb, n, h, w, chars, stride);
-}
-
-// ---- the compressing encoder (deflate.hip): the same window, texts of data-dependent length and their counts -------------------------
-
-void Engine::encode_deflate_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, uint8_t* d_lens,
-                                   size_t lens_pitch, hipStream_t s) {
-    if (stride < png_deflate_base64_bound(h, w)) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the PNG encoder: smaller than ire_png_deflate_base64_bound(h, w)");
-    if (row_pitch < (size_t)3 * w || (n > 1 && image_pitch < row_pitch * (size_t)(h - 1) + (size_t)3 * w))
-        fail(IRE_ERR_INVALID_INPUT, "invalid pitch for the PNG encoder: rows or images overlap");
-    ensure_enc_scratch(png_deflate_scratch_bytes(n, h, w), png_deflate_scratch_bytes(max_batch_, h, w));
-    encode_png_deflate_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_enc_scratch_.get<uint8_t>(), d_chars, stride, d_lens, lens_pitch, s);
-}
-
-void Engine::encode_png_deflate_base64_fit_device(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride,
-                                                  uint64_t* d_lens, hipStream_t s) {
-    if (!d_rgb || !d_chars || !d_lens || n < 1 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images)");
-    if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder: height and width must be in 1..8192");
-    encode_deflate_window(d_rgb, n, h, w, row_pitch, image_pitch, d_chars, stride, reinterpret_cast<uint8_t*>(d_lens), sizeof(uint64_t), s);
-}
-
-// pixels up, [count | text] per image down in ONE copy: the host learns the lengths from the D2H that carries the text
-void Engine::encode_png_deflate_base64_fit_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride, uint64_t* lens) {
-    if (!rgb || !chars || !lens) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder: null buffer");
-    if (n < 1 || n > max_batch_ || h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG encoder (1..max_batch images, 1..8192 per side)");
-    const size_t ib = (size_t)h * w * 3, cb = png_deflate_base64_bound(h, w), cpad = (cb + 8 + 255) / 256 * 256;
-    if (stride < cb) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the PNG encoder: smaller than ire_png_deflate_base64_bound(h, w)");
-    const size_t in_pad = (ib * n + 255) / 256 * 256;
-    uint8_t* d_px = ensure_enc_io(in_pad + cpad * (size_t)n);
-    hipStream_t s = main_stream_;
-    IRE_HIP(hipMemcpyAsync(d_px, rgb, ib * n, hipMemcpyHostToDevice, s));
-    uint8_t* d_txt = d_px + in_pad;
-    encode_deflate_window(d_px, n, h, w, (size_t)3 * w, ib, d_txt + 8, cpad, d_txt, cpad, s);
-    std::vector<uint8_t> stage(cpad * (size_t)n);
-    IRE_HIP(hipMemcpyAsync(stage.data(), d_txt, cpad * (size_t)n, hipMemcpyDeviceToHost, s));
-    IRE_HIP(hipStreamSynchronize(s));
-    for (int i = 0; i < n; ++i) {
-        uint64_t len = 0;
-        std::memcpy(&len, stage.data() + cpad * i, 8);
-        if (len > cb) fail(IRE_ERR_INTERNAL, "internal: the PNG encoder reported a length beyond its bound");
-        lens[i] = len;
-        std::memcpy(chars + stride * i, stage.data() + cpad * i + 8, (size_t)len);
-    }
-}
-
-// ---- the JPEG encoder (jpeg.hip): the same window, texts of data-dependent length and their counts -----------------------------------
-
-void Engine::encode_jpeg_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, uint8_t* d_lens,
-                                size_t lens_pitch, hipStream_t s) {
-    if (stride < jpeg_base64_bound(h, w)) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the JPEG encoder: smaller than ire_jpeg_base64_bound(h, w)");
-    if (row_pitch < (size_t)3 * w || (n > 1 && image_pitch < row_pitch * (size_t)(h - 1) + (size_t)3 * w))
-        fail(IRE_ERR_INVALID_INPUT, "invalid pitch for the JPEG encoder: rows or images overlap");
-    ensure_enc_scratch(jpeg_scratch_bytes(n, h, w), jpeg_scratch_bytes(max_batch_, h, w));
-    encode_jpeg_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_enc_scratch_.get<uint8_t>(), d_chars, stride, d_lens, lens_pitch, s);
-}
-
-void Engine::encode_jpeg_base64_fit_device(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride,
-                                           uint64_t* d_lens, hipStream_t s) {
-    if (!d_rgb || !d_chars || !d_lens || n < 1 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the JPEG encoder (1..max_batch images)");
-    if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the JPEG encoder: height and width must be in 1..8192");
-    encode_jpeg_window(d_rgb, n, h, w, row_pitch, image_pitch, d_chars, stride, reinterpret_cast<uint8_t*>(d_lens), sizeof(uint64_t), s);
-}
-
-// pixels up, [count | text] per image down: the counts first (8 bytes each), then each text at its real length
-void Engine::encode_jpeg_base64_fit_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride, uint64_t* lens) {
-    if (!rgb || !chars || !lens) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the JPEG encoder: null buffer");
-    if (n < 1 || n > max_batch_ || h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the JPEG encoder (1..max_batch images, 1..8192 per side)");
-    const size_t ib = (size_t)h * w * 3, cb = jpeg_base64_bound(h, w), cpad = (cb + 8 + 255) / 256 * 256;
-    if (stride < cb) fail(IRE_ERR_INVALID_INPUT, "invalid stride for the JPEG encoder: smaller than ire_jpeg_base64_bound(h, w)");
-    const size_t in_pad = (ib * n + 255) / 256 * 256;
-    uint8_t* d_px = ensure_enc_io(in_pad + cpad * (size_t)n);
-    hipStream_t s = main_stream_;
-    IRE_HIP(hipMemcpyAsync(d_px, rgb, ib * n, hipMemcpyHostToDevice, s));
-    uint8_t* d_txt = d_px + in_pad;
-    encode_jpeg_window(d_px, n, h, w, (size_t)3 * w, ib, d_txt + 8, cpad, d_txt, cpad, s);
-    // the bound is several times a real text (it doubles every byte for stuffing): fetch the counts, then only what they name
-    for (int i = 0; i < n; ++i) IRE_HIP(hipMemcpyAsync(&lens[i], d_txt + cpad * i, 8, hipMemcpyDeviceToHost, s));
-    IRE_HIP(hipStreamSynchronize(s));
-    for (int i = 0; i < n; ++i) {
-        if (lens[i] > cb) fail(IRE_ERR_INTERNAL, "internal: the JPEG encoder reported a length beyond its bound");
-        IRE_HIP(hipMemcpyAsync(chars + stride * i, d_txt + cpad * i + 8, (size_t)lens[i], hipMemcpyDeviceToHost, s));
-    }
-    IRE_HIP(hipStreamSynchronize(s));
-}
-
-// ---- the JPEG decoder (jpeg_parse.hpp on the host, jpeg_dec.hip on the device) -----------------------------------------------------------
-
-void Engine::decode_jpeg_device(const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status,
-                                hipStream_t s) {
-    if (!files || !bytes || !d_rgb || !d_status || n < 1 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the JPEG decoder (1..max_batch files)");
-    if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the JPEG decoder: height and width must be in 1..8192");
-    if (image_pitch < (size_t)3 * w * h) fail(IRE_ERR_INVALID_INPUT, "invalid pitch for the JPEG decoder: images overlap");
-    std::vector<jpegparse::File> hd((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        std::string why;
-        if (!files[i] || !jpegparse::head_file(files[i], bytes[i], decode_accept(), hd[i], why))
-            fail(IRE_ERR_INVALID_INPUT, files[i] ? why : "invalid arguments to the JPEG decoder: null file");
-        if (hd[i].hd.im.h != h || hd[i].hd.im.w != w) fail(IRE_ERR_INVALID_INPUT, "invalid: the JPEG file's size is not the planned h x w");
-    }
-    const JpegDecLayout L0 = jpeg_dec_layout(hd.data(), bytes, n);
-    if (L0.total >= ((size_t)1 << 32)) fail(IRE_ERR_INVALID_INPUT, "invalid: the batch's JPEG files exceed 4 GB");
-    DecScratch& S = dec_;
-    Buf<PinnedMem>& pin = S.next_pin(L0.total);
-    const int turn = S.turn ^ 1;
-    JpegDecLayout L;
-    jpeg_dec_pack(files, bytes, hd.data(), n, L0, pin.get<uint8_t>(), L, dec_min_windows_);
-    const size_t lanes = jpeg_dec_lane_bytes(L.nwin), walk = L.walk_blocks ? jpeg_dec_walk_bytes(L.walk_blocks) : 0;
-    S.grow(L.total, jpeg_dec_coef_bytes(n, h, w), jpeg_dec_coef_bytes(max_batch_, h, w), jpeg_dec_plane_bytes(n, h, w), jpeg_dec_plane_bytes(max_batch_, h, w), lanes, walk, nullptr);
-    IRE_HIP(hipMemcpyAsync(S.d_in.get<uint8_t>(), pin.get<uint8_t>(), L.total, hipMemcpyHostToDevice, s));
-    S.uploaded(turn, s);
-    if (dec_times_) {
-        dec_times_collect();
-        for (hipEvent_t& ev : dec_marks_) if (!ev) IRE_HIP(hipEventCreate(&ev));
-    }
-    jpeg_dec_launch(S.d_in.get<uint8_t>(), L, n, h, w, S.d_coef.get<uint8_t>(), S.d_planes.get<uint8_t>(), lanes ? S.d_lanes.get<uint8_t>() : nullptr,
-                    walk ? S.d_walk.get<uint8_t>() : nullptr, d_rgb, image_pitch, d_status, s, dec_times_ ? dec_marks_ : nullptr);
-    dec_marks_pending_ = dec_times_;
-}
-
-// two pinned blobs in turn: the one handed out was last uploaded by the call before last, and that upload must have left it
-Buf<PinnedMem>& Engine::DecScratch::next_pin(size_t bytes) {
-    const int t = turn;
-    turn ^= 1;
-    if (up_recorded[t]) IRE_HIP(hipEventSynchronize(up_ev[t]));
-    pin[t].grow(bytes, bytes + bytes / 2);
-    return pin[t];
-}
-
-void Engine::DecScratch::uploaded(int which, hipStream_t s) {
-    if (!up_ev[which]) IRE_HIP(hipEventCreateWithFlags(&up_ev[which], hipEventDisableTiming));
-    IRE_HIP(hipEventRecord(up_ev[which], s));
-    up_recorded[which] = true;
-}
-
-// before a buffer goes, nothing enqueued may still use it: the whole device, or (only != null) the one stream that ever uses this scratch
-void Engine::DecScratch::grow(size_t blob, size_t coef, size_t coef_full, size_t planes, size_t planes_full, size_t lanes, size_t walk, hipStream_t only) {
-    if (blob > d_in.bytes() || coef > d_coef.bytes() || planes > d_planes.bytes() || lanes > d_lanes.bytes() || walk > d_walk.bytes()) IRE_HIP(only ? hipStreamSynchronize(only) : hipDeviceSynchronize());
-    d_in.grow(blob, blob + blob / 2);
-    d_coef.grow(coef, batch_room(coef, coef_full));
-    d_planes.grow(planes, batch_room(planes, planes_full));
-    if (lanes) d_lanes.grow(lanes, lanes + lanes / 2);
-    if (walk) d_walk.grow(walk, walk + walk / 2);
-}
-
-void Engine::decode_jpeg_streams(const jpegparse::File* const* hd, const jpegdec::DecStream* const* streams, const uint8_t* const* bytes, const size_t* used, int n, int h,
-                                 int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s) {
-    if (!hd || !streams || !bytes || !used || !d_rgb || !d_status || n < 1 || n > max_batch_) fail(IRE_ERR_INTERNAL, "internal: arguments of the batcher's JPEG decode");
-    std::vector<uint32_t> ns((size_t)n), nu((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        if (hd[i]->hd.im.h != h || hd[i]->hd.im.w != w) fail(IRE_ERR_INTERNAL, "internal: a file job in a slot of another size");
-        ns[(size_t)i] = hd[i]->nstreams; nu[(size_t)i] = hd[i]->nscans();
-    }
-    const JpegDecLayout L0 = jpeg_dec_layout_rooms(ns.data(), nu.data(), used, n);
-    if (L0.total >= ((size_t)1 << 32)) fail(IRE_ERR_INVALID_INPUT, "invalid: the batch's JPEG files exceed 4 GB");
-    DecScratch& S = dec_batch_;
-    Buf<PinnedMem>& pin = S.next_pin(L0.bytes);
-    const int turn = S.turn ^ 1;
-    JpegDecLayout L;
-    std::vector<size_t> off((size_t)n);
-    jpeg_dec_pack_streams(hd, streams, used, n, L0, pin.get<uint8_t>(), L, off.data(), dec_min_windows_);
-    const size_t lanes = jpeg_dec_lane_bytes(L.nwin), walk = L.walk_blocks ? jpeg_dec_walk_bytes(L.walk_blocks) : 0;
-    S.grow(L.total, jpeg_dec_coef_bytes(n, h, w), jpeg_dec_coef_bytes(max_batch_, h, w), jpeg_dec_plane_bytes(n, h, w), jpeg_dec_plane_bytes(max_batch_, h, w), lanes, walk, s);
-    IRE_HIP(hipMemcpyAsync(S.d_in.get<uint8_t>(), pin.get<uint8_t>(), L.bytes, hipMemcpyHostToDevice, s));
-    S.uploaded(turn, s);
-    // the streams go from where their submitters cut them (the slot's pinned input) straight to the blob on the device
-    for (int i = 0; i < n; ++i)
-        if (used[i]) IRE_HIP(hipMemcpyAsync(S.d_in.get<uint8_t>() + L.bytes + off[(size_t)i], bytes[i], used[i], hipMemcpyHostToDevice, s));
-    jpeg_dec_launch(S.d_in.get<uint8_t>(), L, n, h, w, S.d_coef.get<uint8_t>(), S.d_planes.get<uint8_t>(), lanes ? S.d_lanes.get<uint8_t>() : nullptr,
-                    walk ? S.d_walk.get<uint8_t>() : nullptr, d_rgb, image_pitch, d_status, s);
-}
-
-void Engine::dec_times_collect() {
-    if (!dec_marks_pending_) return;
-    dec_marks_pending_ = false;
-    if (hipEventSynchronize(dec_marks_[kJpegDecMarks - 1]) != hipSuccess) return;
-    for (int k = 0; k < kJpegDecMarks - 1; ++k) { float ms = 0.f; if (hipEventElapsedTime(&ms, dec_marks_[k], dec_marks_[k + 1]) == hipSuccess) dec_ms_[k] += ms; }
-    ++dec_calls_;
-}
-
-void Engine::decode_jpeg_host(const uint8_t* file, size_t bytes, uint8_t* out_rgb, int h, int w) {
-    if (!file || !out_rgb) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the JPEG decoder: null buffer");
-    if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the JPEG decoder: height and width must be in 1..8192");
-    const size_t ib = (size_t)h * w * 3, ipad = (ib + 255) / 256 * 256;
-    if (ipad + 256 > d_dec_out_.bytes()) IRE_HIP(hipDeviceSynchronize());
-    d_dec_out_.grow(ipad + 256);
-    hipStream_t s = main_stream_;
-    uint8_t* d_px = d_dec_out_.get<uint8_t>();
-    int32_t* d_st = reinterpret_cast<int32_t*>(d_px + ipad);
-    decode_jpeg_device(&file, &bytes, 1, h, w, d_px, ib, d_st, s);
-    int32_t st = 0;
-    IRE_HIP(hipMemcpyAsync(out_rgb, d_px, ib, hipMemcpyDeviceToHost, s));
-    IRE_HIP(hipMemcpyAsync(&st, d_st, sizeof(st), hipMemcpyDeviceToHost, s));
-    IRE_HIP(hipStreamSynchronize(s));
-    // (bits: jpeg_dec_core.hpp kSt*; 16 = values no picture gives, where libjpeg-turbo's C and SIMD code differ)
-    if (st != 0) fail(IRE_ERR_INVALID_INPUT, "invalid: corrupt JPEG data (decoder status " + std::to_string(st) + ")");
 }
 
 void Engine::free_workspace() {
@@ -939,12 +675,7 @@ void Engine::restore_device(const uint8_t* d_rgb, int n, int h, int w, const dou
         prof_end(stream);
     }
     last_n_ = n;
-    batches_run_ += 1; images_restored_ += n; last_batch_ = n;
-    {
-        const double t = now_s();
-        recent_.emplace_back(t, n);
-        while (!recent_.empty() && recent_.front().first < t - 10.0) recent_.pop_front();
-    }
+    note_restored(n);
 
     const int lanes_used = std::min(num_lanes_, n);
     const size_t img_bytes = (size_t)h * w * 3;
@@ -984,12 +715,7 @@ void Engine::restore_tiled_device(const uint8_t* d_rgb, int h, int w, int nstrip
         prof_end(stream);
         d_scores = io_.scores;
     }
-    batches_run_ += 1; images_restored_ += 1; last_batch_ = 1;
-    {
-        const double t = now_s();          // tiled jobs count in the images/sec gauge like whole-batch calls
-        recent_.emplace_back(t, 1);
-        while (!recent_.empty() && recent_.front().first < t - 10.0) recent_.pop_front();
-    }
+    note_restored(1);          // tiled jobs count in the images/sec gauge like whole-batch calls
     tiled_->run_all(d_rgb, d_scores, d_out, stream);
 }
 
@@ -1014,19 +740,31 @@ void Engine::restore_fit_device(const uint8_t* d_rgb, int n, int h, int w, const
     if (fit_is_aligned(h, w)) { restore_device(d_rgb, n, h, w, d_scores, d_is_jpeg, d_out, stream); return; }
     if (!d_rgb || !d_out) fail(IRE_ERR_INVALID_INPUT, "invalid input: null image pointer");
     ensure_io(n, 1, 1);
-    if (!d_scores) {          // the classifier reads the ORIGINAL pixels, never the padded copy
-        classify_device(d_rgb, n, h, w, d_is_jpeg, io_.scores, io_.label, stream);
-        d_scores = io_.scores;
-    }
-    restore_padded(d_rgb, n, h, w, d_scores, d_is_jpeg, stream);
+    restore_padded(d_rgb, n, h, w, scores_of_original(d_rgb, n, h, w, d_scores, d_is_jpeg, stream), d_is_jpeg, stream);
     crop_window_launch(d_pad_out_.get<uint8_t>(), n, fit_dim(h), fit_dim(w), d_out, h, w, stream);
 }
 
 // the batcher's results as text: the stored PNG's characters, or with IRE_FLAG_RESULT_PNG_DEFLATE / IRE_FLAG_RESULT_JPEG [uint64 count | characters] per result
 void Engine::encode_result(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_txt, size_t txt_stride, hipStream_t s) {
-    if (flags_ & IRE_FLAG_RESULT_PNG_DEFLATE) encode_deflate_window(d_rgb, n, h, w, row_pitch, image_pitch, d_txt + 8, txt_stride, d_txt, txt_stride, s);
-    else if (flags_ & IRE_FLAG_RESULT_JPEG) encode_jpeg_window(d_rgb, n, h, w, row_pitch, image_pitch, d_txt + 8, txt_stride, d_txt, txt_stride, s);
-    else encode_window(d_rgb, n, h, w, row_pitch, image_pitch, d_txt, txt_stride, s);
+    enc_.places(result_format_ ? *result_format_ : kStoredPng, d_rgb, n, h, w, row_pitch, image_pitch, d_txt, txt_stride, s);
+}
+
+const double* Engine::scores_of_original(const uint8_t* d_rgb, int n, int h, int w, const double* d_scores, const uint8_t* d_is_jpeg, hipStream_t stream) {
+    if (d_scores || fit_is_aligned(h, w)) return d_scores;
+    classify_device(d_rgb, n, h, w, d_is_jpeg, io_.scores, io_.label, stream);
+    return io_.scores;
+}
+
+const double* Engine::settle_scores(const uint8_t* d_rgb, int n, int h, int w, const double* host_scores, const uint8_t* has_scores, const uint8_t* d_is_jpeg,
+                                    hipStream_t stream) {
+    bool any_missing = false, any_given = false;
+    for (int i = 0; i < n; ++i) { if (has_scores && has_scores[i]) any_given = true; else any_missing = true; }
+    // null: restore_device classifies inside (its scan also writes the FiLM vector); only an aligned shape may
+    if (!any_given && fit_is_aligned(h, w)) return nullptr;
+    if (any_missing) classify_device(d_rgb, n, h, w, d_is_jpeg, io_.scores, io_.label, stream);      // the ORIGINAL pixels
+    for (int i = 0; i < n; ++i)
+        if (has_scores && has_scores[i]) IRE_HIP(hipMemcpyAsync(io_.scores + 7 * i, host_scores + 7 * i, sizeof(double) * 7, hipMemcpyHostToDevice, stream));
+    return io_.scores;
 }
 
 void Engine::restore_fit_device_mixed(const uint8_t* d_rgb, int n, int h, int w, const double* host_scores, const uint8_t* has_scores,
@@ -1034,15 +772,7 @@ void Engine::restore_fit_device_mixed(const uint8_t* d_rgb, int n, int h, int w,
     check_fit(n, h, w);
     ensure_io(n, 1, 1);
     const bool aligned = fit_is_aligned(h, w);
-    bool any_missing = false, any_given = false;
-    for (int i = 0; i < n; ++i) { if (has_scores && has_scores[i]) any_given = true; else any_missing = true; }
-    const double* d_sc = nullptr;       // null: restore_device classifies inside (its scan also writes the FiLM vector); only an aligned shape may
-    if (any_given || !aligned) {
-        if (any_missing) classify_device(d_rgb, n, h, w, d_is_jpeg, io_.scores, io_.label, stream);      // the ORIGINAL pixels
-        for (int i = 0; i < n; ++i)
-            if (has_scores && has_scores[i]) IRE_HIP(hipMemcpyAsync(io_.scores + 7 * i, host_scores + 7 * i, sizeof(double) * 7, hipMemcpyHostToDevice, stream));
-        d_sc = io_.scores;
-    }
+    const double* d_sc = settle_scores(d_rgb, n, h, w, host_scores, has_scores, d_is_jpeg, stream);
     if (aligned) {
         restore_device(d_rgb, n, h, w, d_sc, d_is_jpeg, d_out, stream);
         if (d_txt) encode_result(d_out, n, h, w, (size_t)3 * w, (size_t)3 * w * h, d_txt, txt_stride, stream);
@@ -1115,17 +845,7 @@ void Engine::restore_fuse_fit_device_mixed(const uint8_t* d_views, int nsets, in
     const int n = nsets * k;
     ensure_io(n, 1, 1);
     // the views' scores exactly as restore_fit_device_mixed settles them for n single jobs
-    const bool aligned = fit_is_aligned(h, w);
-    bool any_missing = false, any_given = false;
-    for (int i = 0; i < n; ++i) { if (has_scores && has_scores[i]) any_given = true; else any_missing = true; }
-    const double* d_sc = nullptr;
-    if (any_given || !aligned) {
-        if (any_missing) classify_device(d_views, n, h, w, d_is_jpeg, io_.scores, io_.label, stream);      // the ORIGINAL pixels
-        for (int i = 0; i < n; ++i)
-            if (has_scores && has_scores[i]) IRE_HIP(hipMemcpyAsync(io_.scores + 7 * i, host_scores + 7 * i, sizeof(double) * 7, hipMemcpyHostToDevice, stream));
-        d_sc = io_.scores;
-    }
-    fuse_fit_core(d_views, nsets, k, h, w, d_sc, d_is_jpeg, d_out, d_txt, txt_stride, stream);
+    fuse_fit_core(d_views, nsets, k, h, w, settle_scores(d_views, n, h, w, host_scores, has_scores, d_is_jpeg, stream), d_is_jpeg, d_out, d_txt, txt_stride, stream);
 }
 
 void Engine::restore_fuse_fit_device(const uint8_t* d_views, int nsets, int k, int h, int w, const double* d_scores, const uint8_t* d_is_jpeg, uint8_t* d_out,
@@ -1133,12 +853,17 @@ void Engine::restore_fuse_fit_device(const uint8_t* d_views, int nsets, int k, i
     check_fuse_fit(nsets, k, h, w);
     const int n = nsets * k;
     ensure_io(n, 1, 1);
-    if (!d_scores && !fit_is_aligned(h, w)) {      // the classifier reads the ORIGINAL pixels, never the padded copy
-        if (!d_views) fail(IRE_ERR_INVALID_INPUT, "invalid input: null image pointer");
-        classify_device(d_views, n, h, w, d_is_jpeg, io_.scores, io_.label, stream);
-        d_scores = io_.scores;
+    fuse_fit_core(d_views, nsets, k, h, w, scores_of_original(d_views, n, h, w, d_scores, d_is_jpeg, stream), d_is_jpeg, d_out, nullptr, 0, stream);
+}
+
+double Engine::note_restored(int n) {
+    const double t = now_s();
+    if (n > 0) {
+        batches_run_ += 1; images_restored_ += n; last_batch_ = n;
+        recent_.emplace_back(t, n);
     }
-    fuse_fit_core(d_views, nsets, k, h, w, d_scores, d_is_jpeg, d_out, nullptr, 0, stream);
+    while (!recent_.empty() && recent_.front().first < t - 10.0) recent_.pop_front();
+    return t;
 }
 
 void Engine::get_stats(ire_engine_stats* out) {
@@ -1146,8 +871,7 @@ void Engine::get_stats(ire_engine_stats* out) {
     out->images = images_restored_;
     out->last_batch = last_batch_;
     out->max_batch = max_batch_;
-    const double t = now_s();
-    while (!recent_.empty() && recent_.front().first < t - 10.0) recent_.pop_front();
+    const double t = note_restored(0);
     double imgs = 0;
     for (auto& r : recent_) imgs += r.second;
     // span from the first call of the window to now; one lone call reports over >= 1 s so the gauge decays instead of spiking

@@ -4,7 +4,10 @@
 // weights re-laid-out for conv_mfma.hip, per-"lane" activation workspaces (a lane = one HIP
 // stream restoring a contiguous slice of the batch, so several images are in flight and the
 // per-image working set of the full-resolution levels stays inside the 256 MiB Infinity Cache),
-// staging buffers for the host-pointer entry points, and an event-based per-kernel profiler.
+// staging buffers for the host-pointer entry points, the pad and fusion staging of any-size jobs,
+// and an event-based per-kernel profiler.  The codecs in front of and behind the network (JPEG
+// uploads in, PNG / JPEG text out) are objects of their own (codec.hpp): the engine holds one of
+// each, hands them out, and only asks the encoder for the batcher's results as text.
 #pragma once
 #include <deque>
 #include <map>
@@ -14,11 +17,11 @@
 #include <vector>
 
 #include "classifier.hpp"
+#include "codec.hpp"
 #include "common.hpp"
 #include "conv_mfma.hpp"
 #include "conv_plan.hpp"
 #include "device_buf.hpp"
-#include "jpeg_dec.hpp"
 
 namespace ire {
 
@@ -179,36 +182,6 @@ public:
     void preprocess_device(const uint8_t* d_rgb, int h, int w, int orientation, int max_dim, uint8_t* d_out, int out_h, int out_w,
                            hipStream_t s);
     void preprocess_host(const uint8_t* rgb, int h, int w, int orientation, int max_dim, uint8_t* out, int out_h, int out_w);
-    // encode.hip: n images [h][w][3] -> n x png_base64_chars(h, w) characters, `stride` bytes apart (device buffers, asynchronous on s)
-    void encode_png_base64_device(const uint8_t* d_rgb, int n, int h, int w, uint8_t* d_chars, size_t stride, hipStream_t s);
-    void encode_png_base64_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride);
-    // the same encoder without the multiple-of-8 rule (h, w in 1..8192), reading the top-left h x w window of images that lie
-    // row_pitch / image_pitch bytes apart; the two entries above are their own argument checks in front of encode_window
-    void encode_png_base64_fit_device(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride,
-                                      hipStream_t s);
-    void encode_png_base64_fit_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride);
-    // deflate.hip: the compressing encoder on the same window: at most png_deflate_base64_bound(h, w) characters per image, `stride`
-    // apart, and each text's real character count (n uint64)
-    void encode_png_deflate_base64_fit_device(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride,
-                                              uint64_t* d_lens, hipStream_t s);
-    void encode_png_deflate_base64_fit_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride, uint64_t* lens);
-    // jpeg.hip: the same window as a baseline JPEG (quality 85, 4:4:4): at most jpeg_base64_bound(h, w) characters per image, `stride`
-    // apart, and each text's real character count (n uint64)
-    void encode_jpeg_base64_fit_device(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride,
-                                       uint64_t* d_lens, hipStream_t s);
-    void encode_jpeg_base64_fit_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride, uint64_t* lens);
-    // jpeg_dec.hip: n baseline JPEG files of one planned size (jpeg_parse.hpp decides which files) -> n images of h x w x 3 bytes on
-    // the device, image_pitch apart, and one status word per image (0: ok).  The host parse runs inside; one upload and a fixed
-    // number of launches per batch.  The only wait of the host: for the upload of the call BEFORE LAST, whose pinned staging this call
-    // reuses (that upload sits behind the kernels of the call before it, so a caller three calls ahead of the device waits for those).
-    void decode_jpeg_device(const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status,
-                            hipStream_t s);
-    void decode_jpeg_host(const uint8_t* file, size_t bytes, uint8_t* out_rgb, int h, int w);
-    // The batcher's file jobs: n files of one planned size whose heads were parsed and whose scans were cut by their submitters
-    // (streams[i]: hd[i]->nstreams records with offsets inside bytes[i], pinned, used[i] bytes) -> the same as decode_jpeg_device.
-    // Works on a scratch of its own and takes no lock: ONE thread calls it (the batcher's launcher), always on the same stream.
-    void decode_jpeg_streams(const jpegparse::File* const* hd, const jpegdec::DecStream* const* streams, const uint8_t* const* bytes, const size_t* used, int n, int h,
-                             int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s);
     // Any-size jobs (h, w in 1..8192): edge-replicate pad to (max(16, ceil8 h), max(16, ceil8 w)) into the engine's padded
     // staging, the network on the padded shape, the top-left h x w window as the result.  The classifier always sees the
     // ORIGINAL pixels.  A shape restore_device takes as it is skips the pad and runs exactly as restore_device does.
@@ -222,9 +195,10 @@ public:
                                   const uint8_t* d_is_jpeg, uint8_t* d_out, uint8_t* d_txt, size_t txt_stride, hipStream_t stream);
     static bool fit_is_aligned(int h, int w) { return h % 8 == 0 && w % 8 == 0 && h >= 16 && w >= 16; }
     static int fit_dim(int v) { return v <= 16 ? 16 : (v + 7) / 8 * 8; }
-    uint32_t flags() const { return flags_; }
-    // what the JPEG decoder's parser is asked to accept (jpeg_parse.hpp)
-    uint32_t decode_accept() const { return (flags_ & IRE_FLAG_DECODE_PROGRESSIVE) ? jpegparse::kAcceptProgressive : 0u; }
+    // the codecs (codec.hpp): used inside the same enter / leave bracket as every other call
+    TextEncoder& text_encoder() { return enc_; }
+    JpegDecoder& jpeg_decoder() { return dec_; }
+    const TextFormat* result_format() const { return result_format_; }      // of the batcher's results; null: pixels
 
     void debug_sums(int n, uint64_t* out);
     void debug_capture(bool on) { capture_ = on; captured_.clear(); }
@@ -267,16 +241,13 @@ private:
                        size_t txt_stride, hipStream_t stream);
     void fuse_reserve(int nsets, size_t px, hipStream_t s);
     void fuse_chain(const uint8_t* d_views, int nsets, int k, int h, int w, const unsigned* host_wluts, uint8_t* d_out, int32_t* d_shifts, hipStream_t s);
+    // the scores a batch of jobs runs with: rows flagged in has_scores as given (pinned, n*7), the rest classified; null: restore_device classifies inside
+    const double* settle_scores(const uint8_t* d_rgb, int n, int h, int w, const double* host_scores, const uint8_t* has_scores, const uint8_t* d_is_jpeg, hipStream_t stream);
+    // d_scores, or for an unaligned shape without them the classifier's of the ORIGINAL pixels (never of the padded copy)
+    const double* scores_of_original(const uint8_t* d_rgb, int n, int h, int w, const double* d_scores, const uint8_t* d_is_jpeg, hipStream_t stream);
+    double note_restored(int n);               // counters + the 10 s window of the images/sec gauge (n = 0: only prunes it); -> now
     void restore_padded(const uint8_t* d_rgb, int n, int h, int w, const double* d_scores, const uint8_t* d_is_jpeg, hipStream_t stream);
     void restore_host_impl(const uint8_t* rgb, int n, int h, int w, const double* scores, const uint8_t* is_jpeg, uint8_t* out, ire_timings* t);
-    void encode_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, hipStream_t s);
-    void encode_host_impl(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride);
-    void ensure_enc_scratch(size_t need, size_t full);
-    uint8_t* ensure_enc_io(size_t need);      // d_enc_io_ with room for `need` bytes
-    void encode_deflate_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, uint8_t* d_lens,
-                               size_t lens_pitch, hipStream_t s);
-    void encode_jpeg_window(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_chars, size_t stride, uint8_t* d_lens,
-                            size_t lens_pitch, hipStream_t s);
     void encode_result(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_txt, size_t txt_stride, hipStream_t s);
     void ensure_io(int n, int h, int w);
     void ensure_workspace(int n, int h, int w);
@@ -299,7 +270,7 @@ private:
     int device_ = 0;
     int max_batch_ = 8;
     int num_lanes_ = 1;
-    uint32_t flags_ = 0;
+    const TextFormat* result_format_ = nullptr;
     int precision_ = IRE_PRECISION_BF16;
     ConvSwitches sw_;             // the A/B schedule switches, read from the environment once (conv_plan.hpp)
     int cus_ = 256;               // persistent_grid_cus(), read once
@@ -326,43 +297,11 @@ private:
     FuseBufs<DeviceMem> fuse_;            // fusion scratch
     Buf<DeviceMem> d_zero_;               // 256 bytes of zeros (conv_upq.hip's zero padding source)
     Buf<DeviceMem> d_pp_tab_, d_pp_mid_, d_pp_in_, d_pp_out_;   // preprocess scratch (tap tables, intermediate of the horizontal pass, host-path staging)
-    Buf<DeviceMem> d_enc_scratch_;        // encode.hip: per batch: the PNG files + checksum state
     Buf<DeviceMem> d_pad_in_, d_pad_out_; // any-size jobs: the edge-padded batch in front of the network, and the network's output on the padded shape
     Buf<DeviceMem> d_fuse_in_, d_fuse_out_;   // fusion jobs: the restored windows padded to the fusion shape [n][HF][WF][3], the fused images [sets][HF][WF][3]
     Buf<DeviceMem> d_fuse_sc_;            // ... and the classifier's scores of view 0 of every padded set, [kFuseMaxSets][7] (never io_.scores: those are the jobs')
-    Buf<DeviceMem> d_enc_io_;             // host entry: pixels in | characters out
-    // the JPEG decoder: the batch's upload (records, tables, stream table, stream bytes) pinned and on the device, the coefficient
-    // scratch behind the status words, the sample planes, the host entry's pixels + status
-    // Two users that never share a buffer: dec_ serves the engine's own entries (under the engine's lock, on the caller's stream),
-    // dec_batch_ the batcher's file jobs (launcher thread, copy-in stream).
-    struct DecScratch {
-        Buf<PinnedMem> pin[2];            // two, used in turn: call k + 1 is parsed and staged while call k's upload may still run
-        Buf<DeviceMem> d_in, d_coef, d_planes;
-        Buf<DeviceMem> d_lanes;           // the lane records and window heads of the streams decoded window-parallel
-        Buf<DeviceMem> d_walk;            // the masks and walk records of a progressive file's AC refinement scans
-        hipEvent_t up_ev[2] = {};         // the last upload out of pin[i]
-        bool up_recorded[2] = {};
-        int turn = 0;
-        DecScratch() = default;
-        DecScratch(const DecScratch&) = delete;
-        DecScratch& operator=(const DecScratch&) = delete;
-        ~DecScratch() { for (hipEvent_t ev : up_ev) if (ev) (void)hipEventDestroy(ev); }
-        Buf<PinnedMem>& next_pin(size_t bytes);       // the blob this call fills, free of its last upload and `bytes` large at least
-        void uploaded(int which, hipStream_t s);
-        void grow(size_t blob, size_t coef, size_t coef_full, size_t planes, size_t planes_full, size_t lanes, size_t walk, hipStream_t only);
-    };
-    DecScratch dec_, dec_batch_;
-    Buf<DeviceMem> d_dec_out_;
-    // IRE_JPEG_DEC_WINDOWS (read once): a long stream of at least so many windows is decoded window-parallel; 0: none, the
-    // one-workgroup kernel walks them all (for measurement).  Default, and the least that counts: 2.
-    uint32_t dec_min_windows_ = 2;
-    // IRE_JPEG_DEC_TIMES=1 (read once; tools/jpeg_decode_measure.py): events between the decoder's launches, their times summed over
-    // the calls and printed to stderr as one JSON line when the engine closes.  Collecting waits for the previous call's kernels.
-    bool dec_times_ = false, dec_marks_pending_ = false;
-    hipEvent_t dec_marks_[kJpegDecMarks] = {};
-    double dec_ms_[kJpegDecMarks - 1] = {};
-    int64_t dec_calls_ = 0;
-    void dec_times_collect();
+    TextEncoder enc_;                     // codec.hpp: they own their buffers
+    JpegDecoder dec_;
 
     // network
     Net net_;

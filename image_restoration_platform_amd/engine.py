@@ -4,6 +4,7 @@ This is the "PyTorch-ROCm extension" side of BASELINE.json's north_star: torch s
 memory and streams (tensor.data_ptr(), torch.cuda.current_stream()), the engine does the work.
 Nothing here computes pixels on the CPU; if libire.so or the GPU is missing every call raises.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -12,6 +13,22 @@ from . import _lib, weights as _weights
 
 KEYS = ["blur", "noise", "lowLight", "compression", "scratch", "fade", "colorShift"]  # classifier.js:62-70
 FAMILIES = ["classifier", "conv3x3", "conv1x1", "stem", "head", "gn_finalize", "fusion", "all"]
+
+
+# One row per text format (csrc/codec.hpp TextFormat): the engine flag that selects it for the batcher's results, the ABI's host and
+# device entry, the Engine method that gives its bound, the noun of its messages, and whether a uint64 count goes with every text.
+TextFormat = collections.namedtuple("TextFormat", "flag host device bound noun counted")
+TEXT_FORMATS = {
+    "png": TextFormat(_lib.IRE_FLAG_RESULT_PNG_BASE64, "ire_encode_png_base64_fit", "ire_encode_png_base64_fit_device", "png_base64_bytes_fit", "PNG", False),
+    "png_deflate": TextFormat(_lib.IRE_FLAG_RESULT_PNG_DEFLATE, "ire_encode_png_deflate_base64_fit", "ire_encode_png_deflate_base64_fit_device",
+                              "png_deflate_base64_bound", "PNG", True),
+    "jpeg": TextFormat(_lib.IRE_FLAG_RESULT_JPEG, "ire_encode_jpeg_base64_fit", "ire_encode_jpeg_base64_fit_device", "jpeg_base64_bound", "JPEG", True),
+}
+
+
+def result_format(flags):
+    """The TextFormat of the results of an engine created with `flags`, or None: pixels."""
+    return next((f for f in TEXT_FORMATS.values() if flags & f.flag), None)
 
 
 class EngineError(RuntimeError):
@@ -280,12 +297,11 @@ class Engine:
         """-> (restored [H,W,3] uint8 -- or, for an engine created with flags=IRE_FLAG_RESULT_PNG_BASE64 / IRE_FLAG_RESULT_PNG_DEFLATE /
         IRE_FLAG_RESULT_JPEG, the `bytes` of the base64 text of its PNG / JPEG file --, scores[7], timings)"""
         handle, h, w = job
-        if getattr(self, "_flags", 0) & _lib.IRE_FLAG_RESULT_JPEG:
-            return self._poll_text(handle, timeout_ms, self.jpeg_base64_bound(h, w))
-        if getattr(self, "_flags", 0) & _lib.IRE_FLAG_RESULT_PNG_DEFLATE:
-            return self._poll_text(handle, timeout_ms, self.png_deflate_base64_bound(h, w))
-        text = bool(getattr(self, "_flags", 0) & _lib.IRE_FLAG_RESULT_PNG_BASE64)
-        out = np.empty(self.png_base64_bytes_fit(h, w), np.uint8) if text else np.empty((h, w, 3), np.uint8)     # (the job's own h, w)
+        fmt = result_format(getattr(self, "_flags", 0))
+        text = fmt is not None
+        if text and fmt.counted:
+            return self._poll_text(handle, timeout_ms, getattr(self, fmt.bound)(h, w))
+        out = np.empty(getattr(self, fmt.bound)(h, w), np.uint8) if text else np.empty((h, w, 3), np.uint8)     # (the job's own h, w)
         scores = np.zeros(7, np.float64)
         t = _lib.IreTimings()
         self._check(self._lib.ire_poll(self._h, handle, timeout_ms, _ptr(out), _ptr(scores), ctypes.byref(t)))
@@ -302,6 +318,43 @@ class Engine:
         self._check(self._lib.ire_poll_text(self._h, handle, timeout_ms, _ptr(out), cap, ctypes.byref(n), _ptr(scores), ctypes.byref(t)))
         return out[:n.value].tobytes(), scores, {"classify_ms": t.classify_ms, "restore_ms": t.restore_ms, "total_ms": t.total_ms}
 
+    def _encode_fit(self, fmt, rgb):
+        """The host encoder of TEXT_FORMATS[fmt]: [N,H,W,3] (or [H,W,3]) uint8 -> list of N `bytes` (one for a single image)."""
+        f = TEXT_FORMATS[fmt]
+        single = np.asarray(rgb).ndim == 3
+        x = self._as_batch(rgb)
+        n, h, w, _ = x.shape
+        cb = getattr(self, f.bound)(h, w)
+        if cb == 0:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, f"invalid image size for the {f.noun} encoder: height and width must be in 1..8192")
+        stride = (cb + 15) // 16 * 16
+        out = np.empty((n, stride), np.uint8)
+        lens = np.zeros(n, np.uint64) if f.counted else None
+        self._check(getattr(self._lib, f.host)(self._h, _ptr(x), n, h, w, _ptr(out), stride, *([_ptr(lens)] if f.counted else [])))
+        res = [out[i, :int(lens[i]) if f.counted else cb].tobytes() for i in range(n)]
+        return res[0] if single else res
+
+    def _encode_fit_tensor(self, fmt, rgb_u8, stream):
+        """The device encoder of TEXT_FORMATS[fmt]: -> cuda uint8 [N, bound] ASCII, and for a counted format (that, cuda int64 [N] counts).
+        The window is encoded where it lies, its strides go to the engine as pitches."""
+        import torch
+        f = TEXT_FORMATS[fmt]
+        assert rgb_u8.is_cuda and rgb_u8.dtype == torch.uint8 and rgb_u8.dim() == 4 and rgb_u8.shape[3] == 3
+        n, h, w, _ = rgb_u8.shape
+        si, sr, sp, sc = rgb_u8.stride()
+        if sc != 1 or sp != 3 or sr < 3 * w:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, f"invalid tensor layout for the {f.noun} encoder: pixels must be dense RGB")
+        cb = getattr(self, f.bound)(h, w)
+        if cb == 0:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, f"invalid image size for the {f.noun} encoder: height and width must be in 1..8192")
+        stride = (cb + 3) // 4 * 4
+        out = torch.empty((n, stride), dtype=torch.uint8, device=rgb_u8.device)
+        lens = torch.zeros(n, dtype=torch.int64, device=rgb_u8.device) if f.counted else None      # (the counts are uint64 and < 2^63)
+        self._check(getattr(self._lib, f.device)(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), n, h, w, sr, si if n > 1 else max(si, sr * h),
+                                                 ctypes.c_void_p(out.data_ptr()), stride, *([ctypes.c_void_p(lens.data_ptr())] if f.counted else []),
+                                                 self._stream_ptr(stream)))
+        return (out[:, :cb], lens) if f.counted else out[:, :cb]
+
     def png_base64_bytes(self, h, w):
         return int(self._lib.ire_png_base64_bytes(int(h), int(w)))
 
@@ -312,38 +365,12 @@ class Engine:
     def encode_png_deflate_base64_fit(self, rgb):
         """[N,H,W,3] (or [H,W,3]) uint8, any size 1..8192 per side -> list of N `bytes` (one for a single image): the base64 text of a
         COMPRESSED PNG file of each image (Paeth filter, Huffman-coded deflate blocks), encoded on the device; each of its real length."""
-        single = np.asarray(rgb).ndim == 3
-        x = self._as_batch(rgb)
-        n, h, w, _ = x.shape
-        cb = self.png_deflate_base64_bound(h, w)
-        if cb == 0:
-            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder: height and width must be in 1..8192")
-        stride = (cb + 15) // 16 * 16
-        out = np.empty((n, stride), np.uint8)
-        lens = np.zeros(n, np.uint64)
-        self._check(self._lib.ire_encode_png_deflate_base64_fit(self._h, _ptr(x), n, h, w, _ptr(out), stride, _ptr(lens)))
-        res = [out[i, :int(lens[i])].tobytes() for i in range(n)]
-        return res[0] if single else res
+        return self._encode_fit("png_deflate", rgb)
 
     def encode_png_deflate_base64_fit_tensor(self, rgb_u8, stream=None):
         """cuda uint8 [N,h,w,3], possibly a window of a larger tensor -> (cuda uint8 [N, bound] ASCII, cuda int64 [N] character counts),
         asynchronous on the stream: text i is out[i, :lens[i]]."""
-        import torch
-        assert rgb_u8.is_cuda and rgb_u8.dtype == torch.uint8 and rgb_u8.dim() == 4 and rgb_u8.shape[3] == 3
-        n, h, w, _ = rgb_u8.shape
-        si, sr, sp, sc = rgb_u8.stride()
-        if sc != 1 or sp != 3 or sr < 3 * w:
-            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid tensor layout for the PNG encoder: pixels must be dense RGB")
-        cb = self.png_deflate_base64_bound(h, w)
-        if cb == 0:
-            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder: height and width must be in 1..8192")
-        stride = (cb + 3) // 4 * 4
-        out = torch.empty((n, stride), dtype=torch.uint8, device=rgb_u8.device)
-        lens = torch.zeros(n, dtype=torch.int64, device=rgb_u8.device)      # (the counts are uint64 and < 2^63)
-        self._check(self._lib.ire_encode_png_deflate_base64_fit_device(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), n, h, w, sr, si if n > 1 else max(si, sr * h),
-                                                                       ctypes.c_void_p(out.data_ptr()), stride, ctypes.c_void_p(lens.data_ptr()),
-                                                                       self._stream_ptr(stream)))
-        return out[:, :cb], lens
+        return self._encode_fit_tensor("png_deflate", rgb_u8, stream)
 
     def jpeg_base64_bound(self, h, w):
         """The most characters the JPEG encoder can give for an h x w image (0 outside 1..8192): sizes every buffer."""
@@ -352,38 +379,12 @@ class Engine:
     def encode_jpeg_base64_fit(self, rgb):
         """[N,H,W,3] (or [H,W,3]) uint8, any size 1..8192 per side -> list of N `bytes` (one for a single image): the base64 text of a
         baseline JPEG file of each image (quality 85, 4:4:4), encoded on the device; each of its real length."""
-        single = np.asarray(rgb).ndim == 3
-        x = self._as_batch(rgb)
-        n, h, w, _ = x.shape
-        cb = self.jpeg_base64_bound(h, w)
-        if cb == 0:
-            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid image size for the JPEG encoder: height and width must be in 1..8192")
-        stride = (cb + 15) // 16 * 16
-        out = np.empty((n, stride), np.uint8)
-        lens = np.zeros(n, np.uint64)
-        self._check(self._lib.ire_encode_jpeg_base64_fit(self._h, _ptr(x), n, h, w, _ptr(out), stride, _ptr(lens)))
-        res = [out[i, :int(lens[i])].tobytes() for i in range(n)]
-        return res[0] if single else res
+        return self._encode_fit("jpeg", rgb)
 
     def encode_jpeg_base64_fit_tensor(self, rgb_u8, stream=None):
         """cuda uint8 [N,h,w,3], possibly a window of a larger tensor -> (cuda uint8 [N, bound] ASCII, cuda int64 [N] character counts),
         asynchronous on the stream: text i is out[i, :lens[i]]."""
-        import torch
-        assert rgb_u8.is_cuda and rgb_u8.dtype == torch.uint8 and rgb_u8.dim() == 4 and rgb_u8.shape[3] == 3
-        n, h, w, _ = rgb_u8.shape
-        si, sr, sp, sc = rgb_u8.stride()
-        if sc != 1 or sp != 3 or sr < 3 * w:
-            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid tensor layout for the JPEG encoder: pixels must be dense RGB")
-        cb = self.jpeg_base64_bound(h, w)
-        if cb == 0:
-            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid image size for the JPEG encoder: height and width must be in 1..8192")
-        stride = (cb + 3) // 4 * 4
-        out = torch.empty((n, stride), dtype=torch.uint8, device=rgb_u8.device)
-        lens = torch.zeros(n, dtype=torch.int64, device=rgb_u8.device)      # (the counts are uint64 and < 2^63)
-        self._check(self._lib.ire_encode_jpeg_base64_fit_device(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), n, h, w, sr, si if n > 1 else max(si, sr * h),
-                                                                ctypes.c_void_p(out.data_ptr()), stride, ctypes.c_void_p(lens.data_ptr()),
-                                                                self._stream_ptr(stream)))
-        return out[:, :cb], lens
+        return self._encode_fit_tensor("jpeg", rgb_u8, stream)
 
     # ---- JPEG uploads decoded on the device (csrc/jpeg_parse.hpp, csrc/jpeg_dec.hip) -------------------------------------------
     @property
@@ -472,35 +473,12 @@ class Engine:
 
     def encode_png_base64_fit(self, rgb):
         """encode_png_base64() for any size (1..8192 per side)."""
-        single = np.asarray(rgb).ndim == 3
-        x = self._as_batch(rgb)
-        n, h, w, _ = x.shape
-        cb = self.png_base64_bytes_fit(h, w)
-        if cb == 0:
-            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder: height and width must be in 1..8192")
-        stride = (cb + 15) // 16 * 16
-        out = np.empty((n, stride), np.uint8)
-        self._check(self._lib.ire_encode_png_base64_fit(self._h, _ptr(x), n, h, w, _ptr(out), stride))
-        res = [out[i, :cb].tobytes() for i in range(n)]
-        return res[0] if single else res
+        return self._encode_fit("png", rgb)
 
     def encode_png_base64_fit_tensor(self, rgb_u8, stream=None):
         """cuda uint8 [N,h,w,3], possibly a window `t[:, :h, :w]` of a larger tensor (only the pixel and channel axes have to be
         dense) -> cuda uint8 [N, chars] ASCII; the window is encoded where it lies, its strides go to the engine as pitches."""
-        import torch
-        assert rgb_u8.is_cuda and rgb_u8.dtype == torch.uint8 and rgb_u8.dim() == 4 and rgb_u8.shape[3] == 3
-        n, h, w, _ = rgb_u8.shape
-        si, sr, sp, sc = rgb_u8.stride()
-        if sc != 1 or sp != 3 or sr < 3 * w:
-            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid tensor layout for the PNG encoder: pixels must be dense RGB")
-        cb = self.png_base64_bytes_fit(h, w)
-        if cb == 0:
-            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid image size for the PNG encoder: height and width must be in 1..8192")
-        stride = (cb + 3) // 4 * 4
-        out = torch.empty((n, stride), dtype=torch.uint8, device=rgb_u8.device)
-        self._check(self._lib.ire_encode_png_base64_fit_device(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), n, h, w, sr, si if n > 1 else max(si, sr * h),
-                                                               ctypes.c_void_p(out.data_ptr()), stride, self._stream_ptr(stream)))
-        return out[:, :cb]
+        return self._encode_fit_tensor("png", rgb_u8, stream)
 
     def restore_fit_tensor(self, rgb_u8, out_u8=None, scores=None, is_jpeg_u8=None, stream=None):
         """restore_tensor() for any size (1..8192 per side), asynchronous on the torch stream."""

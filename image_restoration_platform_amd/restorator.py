@@ -26,6 +26,7 @@ from datetime import datetime, timezone
 import numpy as np
 
 from . import _lib
+from .engine import result_format
 from .prompt_enhancer import KEYS, PromptEnhancerService
 
 BATCH_REQUEST_DELAY_MS = float(os.environ.get("RESTORATION_BATCH_DELAY_MS", "0") or 0)  # restorator.js:13
@@ -168,7 +169,7 @@ class EngineRestorer:
         if not images or len(images) > 3:
             raise ValueError("invalid images: expected 1..3 encoded images")  # provider limit: report.md:28
         seen = _seen_of(self.engine)
-        text_engine = bool(getattr(self.engine, "_flags", 0) & (_lib.IRE_FLAG_RESULT_PNG_BASE64 | _lib.IRE_FLAG_RESULT_PNG_DEFLATE | _lib.IRE_FLAG_RESULT_JPEG))      # poll returns the text
+        text_engine = result_format(getattr(self.engine, "_flags", 0)) is not None      # poll returns the text
         if len(images) == 1 and os.environ.get("IRE_UPLOAD_CODEC") == "jpeg-device" and bytes(images[0][:2]) == b"\xff\xd8":
             # a single upload that analyze() has not decoded goes to the batcher as the FILE it is (ire_submit_jpeg): parsed here,
             # decoded on the device with its batch.  A file the plan refuses (at submit) or the device flags (at poll) is "invalid

@@ -680,6 +680,7 @@ int ire_submit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg, con
         if (!rgb || !job_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit");
         if (h <= 0 || w <= 0 || h % 8 || w % 8 || h < 16 || w < 16 || h > 8192 || w > 8192)
             fail(IRE_ERR_INVALID_INPUT, "invalid image size for restore: height and width must be multiples of 8, >= 16");
+        if (!piece_addressable(h, w, 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(h, w));      // no job is queued for the shape restore refuses
         queue_job(e, rgb, h, w, is_jpeg, scores, job_out);
     });
 }
@@ -689,6 +690,7 @@ int ire_submit_fit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg,
         eng(e);
         if (!rgb || !job_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_fit");
         if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size: height and width must be in 1..8192");
+        if (!piece_addressable(Engine::fit_dim(h), Engine::fit_dim(w), 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(Engine::fit_dim(h), Engine::fit_dim(w)));
         queue_job(e, rgb, h, w, is_jpeg, scores, job_out);
     });
 }
@@ -713,6 +715,7 @@ int ire_submit_fuse_fit(ire_engine* e, const uint8_t* const* views, int k, int h
         if (k < 2 || k > 3) fail(IRE_ERR_INVALID_INPUT, "invalid view count for fusion: expected 2..3");
         for (int v = 0; v < k; ++v) if (!views[v]) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_fuse_fit: null view");
         if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size: height and width must be in 1..8192");
+        if (!piece_addressable(Engine::fit_dim(h), Engine::fit_dim(w), 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(Engine::fit_dim(h), Engine::fit_dim(w)));
         if (has_scores && !scores) for (int v = 0; v < k; ++v) if (has_scores[v]) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_fuse_fit: has_scores without scores");
         std::unique_ptr<ire_job> hnd(new ire_job{});
         hnd->j = e->batcher->submit_group(views, k, h, w, is_jpeg, has_scores, scores);       // (refuses k views on an engine with max_batch < k)

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(DN_THREADS) void conv_down_kernel(ConvArgs a) {
         // the requests are inline asm (hipcc then neither tracks nor waits for them: every wait in the stage loop is a counted
         // s_waitcnt placed by hand, see `stage`); the resource descriptor by hand for the same reason
         const unsigned long long ba = (unsigned long long)base;
-        u32x4_t irsrc = {(unsigned)ba, (unsigned)(ba >> 32) & 0xffffu, (unsigned)(a.in_rows * a.Win * Cin * 2 - kc * 64), 0x00020000u};
+        u32x4_t irsrc = {(unsigned)ba, (unsigned)(ba >> 32) & 0xffffu, tensor_bytes(a.in_rows, a.Win, Cin * 2) - (unsigned)(kc * 64), 0x00020000u};
         irsrc.x = __builtin_amdgcn_readfirstlane(irsrc.x); irsrc.y = __builtin_amdgcn_readfirstlane(irsrc.y); irsrc.z = __builtin_amdgcn_readfirstlane(irsrc.z);
         const unsigned delta = (unsigned)((ph >> 1) * a.Win + (ph & 1)) << (cin_shift + 1);        // phase (a, b): a rows down, b pixels right
         const unsigned okp = cokb >> (ph * DN_IN_ITERS);
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(DN_THREADS) void conv_down_kernel(ConvArgs a) {
         int r_e = r, h_e = h, w_e = wave;
         asm volatile("" : "+v"(r_e), "+v"(h_e), "+v"(w_e));
         char* obase = reinterpret_cast<char*>(a.out) + (size_t)it.img * a.Hout * a.Wout * a.cout * 2;
-        const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, a.Hout * a.Wout * a.cout * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, tensor_bytes(a.Hout, a.Wout, a.cout * 2), 0x00020000);
         const bf16x2_t ones = __builtin_bit_cast(bf16x2_t, 0x3f803f80u);
         float* redw = red_base + red_par * (DN_RED_HALF / 4);
         const int ox = it.tx * DN_TW + r_e;

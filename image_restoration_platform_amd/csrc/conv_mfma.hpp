@@ -43,6 +43,15 @@ inline int persistent_grid_cus() {
     return forced > 0 && forced < cus ? forced : cus;
 }
 
+// Bytes of one image's tensor (rows x cols pixels of px_bytes each): the record count of a buffer resource, and the range of the 32-bit
+// byte offsets into it.  Formed in unsigned arithmetic: the product passes 2^31 from 4096 x 8192 level-0 pixels (64 bytes each) upward and
+// stays below 2^32 for every piece the engine admits (conv_plan.hpp::piece_addressable) -- an `int` product would only be right as long as
+// the compiler kept the wrap.  Per-lane offsets follow the same rule: pixel indices in `int` (they may be negative before a displacement
+// brings them back), the multiplication by the pixel's bytes in `unsigned`.
+__host__ __device__ __forceinline__ unsigned tensor_bytes(int rows, int cols, int px_bytes) {
+    return (unsigned)rows * (unsigned)cols * (unsigned)px_bytes;
+}
+
 enum { PRO_NONE = 0, PRO_GN = 1, PRO_U8 = 2 };
 
 struct ConvArgs {

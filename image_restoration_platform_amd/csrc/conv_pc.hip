@@ -220,14 +220,14 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
             const PersistItem& lit = ls.it;
             const int oy1 = lit.ty * C3_TH - 1, ox1 = lit.tx * C3_TW - 1;
             const char* base = reinterpret_cast<const char*>(a.in0) + (size_t)lit.img * a.in_rows * a.Win * (2 * C) + ls.kc * 64;
-            const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, a.in_rows * a.Win * (2 * C) - ls.kc * 64, 0x00020000);
-            const int base_off = ((oy1 + a.in_row_off) * a.Win + ox1) * (2 * C);
+            const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, tensor_bytes(a.in_rows, a.Win, 2 * C) - (unsigned)(ls.kc * 64), 0x00020000);
+            const unsigned base_off = (unsigned)((oy1 + a.in_row_off) * a.Win + ox1) * (unsigned)(2 * C);      // (a pixel index below zero wraps; rel brings a readable chunk back)
             // tile-local bounds (wave-uniform): halo row py is readable iff y_lo <= py < y_hi, column px iff x_lo <= px < x_hi
             const int y_lo = max(a.iy_lo - oy1, 0), y_hi = min(a.iy_lo + a.iy_span - oy1, C3_IH);
             const int x_lo = max(-ox1, 0), x_hi = min(a.Win - ox1, C3_IW);
             const int py = (int)(pyx[i] >> 8), px = (int)(pyx[i] & 0xffu);
             const bool ok = (unsigned)(py - y_lo) < (unsigned)(y_hi - y_lo) && (unsigned)(px - x_lo) < (unsigned)(x_hi - x_lo);
-            const unsigned off = ok ? (unsigned)(base_off + rel[i]) : 0xffffffffu;       // out of range: reads as zero
+            const unsigned off = ok ? base_off + rel[i] : 0xffffffffu;       // out of range: reads as zero
             if constexpr (C3_ABL & 8) { R[i] = make_uint4(off, 0x3f803f80u, i, 0x3f803f80u); }
             else {
                 const u32x4_t lv = __builtin_amdgcn_raw_buffer_load_b128(irsrc, off, 0, IRE_LD_IN);
@@ -465,7 +465,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
             if constexpr (RESID && TEPI64 && !(C3_ABL & 64)) {
                 // the residual rows in the read-back layout (1 KB = 8 pixels per request): RES_PRE of the 4 quarter-rows per row before the MFMAs
                 char* rbase = const_cast<char*>(reinterpret_cast<const char*>(a.resid)) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
-                const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(rbase, 0, a.Hout * a.Wout * (2 * C), 0x00020000);
+                const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(rbase, 0, tensor_bytes(a.Hout, a.Wout, 2 * C), 0x00020000);
 #pragma unroll
                 for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -478,7 +478,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
             if constexpr (RESID && TEPI && !(C3_ABL & 64)) {
                 // the residual rows in the read-back layout: two 1-KB requests per row, before the MFMAs
                 char* rbase = const_cast<char*>(reinterpret_cast<const char*>(a.resid)) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
-                const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(rbase, 0, a.Hout * a.Wout * (2 * C), 0x00020000);
+                const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(rbase, 0, tensor_bytes(a.Hout, a.Wout, 2 * C), 0x00020000);
 #pragma unroll
                 for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -569,7 +569,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
         }
         if constexpr (RESID && TEPI64 && RES_PRE < 2 * NTL) {
             char* rbase = const_cast<char*>(reinterpret_cast<const char*>(a.resid)) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
-            const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(rbase, 0, a.Hout * a.Wout * (2 * C), 0x00020000);
+            const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(rbase, 0, tensor_bytes(a.Hout, a.Wout, 2 * C), 0x00020000);
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -617,7 +617,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                 for (int j = 0; j < NTL; ++j) asm volatile("" :: "v"(acc[m][j]));       // every accumulator stays live: no MFMA may be optimised away
         } else if constexpr (TEPI64) {
             char* obase = reinterpret_cast<char*>(a.out) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
-            const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, a.Hout * a.Wout * (2 * C), 0x00020000);
+            const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, tensor_bytes(a.Hout, a.Wout, 2 * C), 0x00020000);
             const bf16x2_t ones = __builtin_bit_cast(bf16x2_t, 0x3f803f80u);
             float* redw = red_base + red_par * K::RED_HALF;
             {   // consumers' rendezvous: the item's last tile (an item ends on an odd stage: tile 1) is free once all 8 waves are here
@@ -686,7 +686,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
             st_img = it.img; st_tile = it.tile; st_nb = it.nb; st_par = red_par; red_par ^= 1;
         } else if constexpr (TEPI) {
             char* obase = reinterpret_cast<char*>(a.out) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
-            const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, a.Hout * a.Wout * (2 * C), 0x00020000);
+            const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, tensor_bytes(a.Hout, a.Wout, 2 * C), 0x00020000);
             const bf16x2_t ones = __builtin_bit_cast(bf16x2_t, 0x3f803f80u);
             float* redw = red_base + red_par * K::RED_HALF;
             unsigned char* patch = smem + K::PATCH_OFF + wave * 2048;
@@ -746,7 +746,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
             st_img = it.img; st_tile = it.tile; st_nb = it.nb; st_par = red_par; red_par ^= 1;
         } else {
             char* obase = reinterpret_cast<char*>(a.out) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
-            const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, a.Hout * a.Wout * (2 * C), 0x00020000);
+            const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, tensor_bytes(a.Hout, a.Wout, 2 * C), 0x00020000);
             const bf16x2_t ones = __builtin_bit_cast(bf16x2_t, 0x3f803f80u);
             float* redw = red_base + red_par * K::RED_HALF;
             const float mf[2] = {einb[0] ? 1.f : 0.f, einb[1] ? 1.f : 0.f};      // a pixel outside the image counts for nothing

@@ -10,7 +10,9 @@
 //   * a strip's tiles land at their GLOBAL tile offset (ty0), so the finalize sees exactly the whole-image partials layout.
 #pragma once
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
+#include <string>
 
 #include "conv_kind.hpp"
 
@@ -127,6 +129,26 @@ inline bool coef_table_fits(int imgs_cap, long long items_per_img, int nimg, int
         if (hi > lo && (hi - 1) / ipi - lo / ipi + 1 > imgs_cap) return false;
     }
     return true;
+}
+
+// ---- the address rule: what 32-bit byte offsets reach (DESIGN.md "Address arithmetic at the largest shapes") ----
+// A convolution addresses ONE image's tensor -- of a row strip: the strip's rows and its two halo rows -- with a 64-bit base and an unsigned
+// 32-bit byte offset per lane, and range-checks the offset against a buffer resource whose size is 32 bits too; the offset 0xffffffff is how
+// a chunk outside the image asks for its zero padding.  Images of a batch lie a 64-bit stride apart: the batch size is no part of the rule.
+// So a piece runs iff every tensor of it is smaller than 2^32 bytes.  The largest is level 0 (32 channels of bf16: 64 bytes a pixel): among
+// whole images of at most 8192 a side the rule refuses 8192 x 8192 alone (2^26 pixels = 2^32 bytes exactly), which still runs in row strips.
+constexpr unsigned long long kTensorBytesEnd = 1ull << 32;
+inline unsigned long long piece_tensor_bytes(int rows, int w, int halo, int level) {      // rows, w: of the piece at level 0, halo rows excluded
+    return (unsigned long long)((rows >> level) + 2 * halo) * (unsigned long long)(w >> level) * (unsigned long long)(kWidths[level] * 2);
+}
+// (level 0 decides: the bytes halve from level to level, the halo rows do not make up for it)
+inline bool piece_addressable(int rows, int w, int halo) { return piece_tensor_bytes(rows, w, halo, 0) < kTensorBytesEnd; }
+// h x w: the image as it runs -- for the any-size entries the size padded to multiples of 8, which is what the message names
+inline std::string not_addressable(int h, int w) {
+    char m[256];
+    std::snprintf(m, sizeof m, "invalid image size: a level-0 tensor of the image (height x width x 64 bytes, sides padded to multiples of 8) must stay "
+                  "below 2^32 bytes, which %d x %d (%llu bytes) is not; restore it in row strips", h, w, piece_tensor_bytes(h, w, 0, 0));
+    return m;
 }
 
 // `up` composed with the level's 1x1 `fuse` into one convolution (weight_pack.hpp::pack_up_fused): the schedule then has no `fuse`
@@ -293,6 +315,28 @@ inline ConvPlan plan_conv(const ConvSwitches& sw, const ConvDesc& d, const ConvS
     if (fused) p.flops_exec = 2.0 * 4 * d.cin * d.cout * px + 2.0 * d.cout * d.cout * px;
     else if (p.kernel == K_UP_SUB) p.flops_exec = 2.0 * 4 * d.cin * d.cout * px;
     return p;
+}
+
+// What one planned launch asks of the kernels' index types, in 64 bits (tests/test_conv_plan.py holds every field against the type the
+// kernels form it in): the bytes of one image of each tensor (32-bit resource sizes and byte offsets), of the whole batch (64-bit bases),
+// and the counts persist.hpp's cursor and the partials layout keep in `int`.
+struct ConvExtents {
+    unsigned long long in0_bytes = 0, in1_bytes = 0, out_bytes = 0;      // one image; in0 with the piece's halo rows
+    unsigned long long batch_bytes = 0;                                  // the largest tensor of the launch, all images
+    long long items = 0, stages = 0, stat_floats = 0;
+};
+inline ConvExtents conv_extents(const ConvPlan& p, const ConvDesc& d, const ConvSite& s) {
+    typedef unsigned long long u64;
+    ConvExtents e;
+    const u64 Win = (u64)(s.w >> s.lin), Hout = (u64)(s.h >> s.lout), Wout = (u64)(s.w >> s.lout);
+    e.in0_bytes = (u64)p.in_rows * Win * (d.kind == CONV_STEM ? 3u : (u64)d.cin0 * 2);
+    e.in1_bytes = s.has_in1 ? (Hout + 2 * (u64)s.halo) * Wout * (u64)p.cin1 * 2 : 0;
+    e.out_bytes = Hout * Wout * (d.kind == CONV_HEAD ? 3u : (u64)d.cout * 2);
+    e.batch_bytes = (u64)s.nimg * std::max({e.in0_bytes, e.in1_bytes, e.out_bytes});
+    e.items = (long long)p.tiles_x * p.tiles_y * s.nimg * std::max(1, p.nblocks);
+    e.stages = e.items * std::max(1, p.nkc);
+    e.stat_floats = s.stats_out ? (long long)s.nimg * p.stat_parts * 16 : 0;
+    return e;
 }
 
 }  // namespace ire

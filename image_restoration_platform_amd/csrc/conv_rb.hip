@@ -174,7 +174,7 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
         const char* base = reinterpret_cast<const char*>(src) + (size_t)it.img * a.in_rows * a.Win * Cin * 2 + kc * 64;
         // range-checked buffer loads: a halo pixel outside the image gets an offset past num_records and reads as zero --
         // no coordinate clamping (4 min/max per chunk); the `ok` bit still gates the value AFTER the activation
-        const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, a.in_rows * a.Win * Cin * 2 - kc * 64, 0x00020000);
+        const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, tensor_bytes(a.in_rows, a.Win, Cin * 2) - (unsigned)(kc * 64), 0x00020000);
         R.ok = 0;
         int t2 = tid;
         asm volatile("" : "+v"(t2));   // recompute the halo coordinates per stage: cheaper than 5 live registers
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
         const int cout0 = it.nb * NT;
         epi_fetch_rest(it);
         char* obase = reinterpret_cast<char*>(a.out) + (size_t)it.img * a.Hout * a.Wout * a.cout * 2;
-        const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, a.Hout * a.Wout * a.cout * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, tensor_bytes(a.Hout, a.Wout, a.cout * 2), 0x00020000);
         (void)obase;
         const float* bias_lds = reinterpret_cast<const float*>(smem + C::MAIN_BYTES + C::RED_BYTES + C::COEF_BYTES);
         const bf16x2_t ones = __builtin_bit_cast(bf16x2_t, 0x3f803f80u);

@@ -130,7 +130,7 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
         const UpItem& it = si.it;
         const int oy1 = it.ty * UP_TH - 1, ox1 = it.tx * UP_TW - 1;
         const char* base = reinterpret_cast<const char*>(a.in0) + (size_t)it.img * a.in_rows * a.Win * Cin * 2 + si.kc * 64;
-        const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, a.in_rows * a.Win * Cin * 2 - si.kc * 64, 0x00020000);
+        const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, tensor_bytes(a.in_rows, a.Win, Cin * 2) - (unsigned)(si.kc * 64), 0x00020000);
         int t2 = tid;
         asm volatile("" : "+v"(t2));
         const int p = (t2 + i * UP_THREADS) >> 2;
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
         int r_e = r, h_e = h, w_e = wave;
         asm volatile("" : "+v"(r_e), "+v"(h_e), "+v"(w_e));
         char* obase = reinterpret_cast<char*>(a.out) + (size_t)it.img * a.Hout * a.Wout * a.cout * 2;
-        const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, a.Hout * a.Wout * a.cout * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, tensor_bytes(a.Hout, a.Wout, a.cout * 2), 0x00020000);
         const int ly = it.ty * UP_TH + w_e * 2, lx = it.tx * UP_TW + r_e;       // low-res coordinates of row m = 0
         if constexpr (NKS > 0) {
             // ---- fused form: skip term by MFMA, bf16 stores, GroupNorm partials ------------------------------------------------
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
             const char* sbase = reinterpret_cast<const char*>(a.in1) + (size_t)it.img * a.Hout * a.Wout * C * 2;
             // loads past the image's last byte return zero; a pixel past the right edge reads a neighbour's bytes: either way the
             // MFMA column (= that pixel) is never stored nor counted
-            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(sbase), 0, a.Hout * a.Wout * C * 2, 0x00020000);
+            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(sbase), 0, tensor_bytes(a.Hout, a.Wout, C * 2), 0x00020000);
             const unsigned rowB = (unsigned)(a.Wout * C * 2), pxB = (unsigned)(C * 2);
             const unsigned s_off = (unsigned)((2 * ly) * a.Wout + 2 * lx) * pxB + (unsigned)(h_e * 16);
             const bool inb[2] = {ly < a.Hin && lx < a.Win, ly + 1 < a.Hin && lx < a.Win};
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
         int l_e = lane, w_e = wave;
         asm volatile("" : "+v"(l_e), "+v"(w_e));
         const char* sbase = reinterpret_cast<const char*>(a.in1) + (size_t)it.img * a.Hout * a.Wout * C * 2;
-        const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(sbase), 0, a.Hout * a.Wout * C * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(sbase), 0, tensor_bytes(a.Hout, a.Wout, C * 2), 0x00020000);
         const int ly = it.ty * UP_TH + w_e * 2, ox0 = 2 * it.tx * UP_TW;
         const int lc = l_e & 3, lp0 = l_e >> 2;
         const bool rowok = ly < a.Hin;
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
         for (int i = 0; i < 4; ++i) {
             const int p = lp0 + i * 16;
             const bool ok = rowok && ox0 + p < a.Wout;
-            skpre[i] = __builtin_amdgcn_raw_buffer_load_b128(srsrc, ok ? (unsigned)((((2 * ly) * a.Wout + ox0 + p) * C + lc * 8) * 2) : 0xffffffffu, 0, C == 32 ? IRE_LD_ONCE : 0);
+            skpre[i] = __builtin_amdgcn_raw_buffer_load_b128(srsrc, ok ? (unsigned)(((2 * ly) * a.Wout + ox0 + p) * C + lc * 8) * 2u : 0xffffffffu, 0, C == 32 ? IRE_LD_ONCE : 0);
         }
     };
     auto epilogue_t = [&](const UpItem& it) __attribute__((always_inline)) {
@@ -345,9 +345,9 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
         const int r_e = l_e & 31, h_e = l_e >> 5;
         unsigned char* patch = smem + UP_BUF + w_e * UP_PATCH;          // an item ends on an odd stage: buffer 1
         char* obase = reinterpret_cast<char*>(a.out) + (size_t)it.img * a.Hout * a.Wout * C * 2;
-        const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, a.Hout * a.Wout * C * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, tensor_bytes(a.Hout, a.Wout, C * 2), 0x00020000);
         const char* sbase = reinterpret_cast<const char*>(a.in1) + (size_t)it.img * a.Hout * a.Wout * C * 2;
-        const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(sbase), 0, a.Hout * a.Wout * C * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(sbase), 0, tensor_bytes(a.Hout, a.Wout, C * 2), 0x00020000);
         const int ly = it.ty * UP_TH + w_e * 2, ox0 = 2 * it.tx * UP_TW;
         const unsigned char* skw = smem + UP_SKW_OFF + (h_e * 32 + r_e) * 16;      // + ks * 1024
         const bf16x2_t ones = __builtin_bit_cast(bf16x2_t, 0x3f803f80u);
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
             for (int i = 0; i < CPP; ++i) {
                 const int p = lp0 + i * PSTEP;
                 const bool ok = rowok && ox0 + p < a.Wout;
-                sk[i] = __builtin_amdgcn_raw_buffer_load_b128(srsrc, ok ? (unsigned)(((oy * a.Wout + ox0 + p) * C + pc * PCH + lc * 8) * 2) : 0xffffffffu, 0, C == 32 ? IRE_LD_ONCE : 0);
+                sk[i] = __builtin_amdgcn_raw_buffer_load_b128(srsrc, ok ? (unsigned)((oy * a.Wout + ox0 + p) * C + pc * PCH + lc * 8) * 2u : 0xffffffffu, 0, C == 32 ? IRE_LD_ONCE : 0);
             }
         };
         if constexpr (!(IRE_UP_ABL & 1)) {
@@ -417,7 +417,7 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
                     ssum[d >> 1] = __builtin_amdgcn_fdot2_f32_bf16(bv, ones, ssum[d >> 1], false);
                     qsum[d >> 1] = __builtin_amdgcn_fdot2_f32_bf16(bv, bv, qsum[d >> 1], false);
                 }
-                if constexpr (!(IRE_UP_ABL & 4)) __builtin_amdgcn_raw_buffer_store_b128(v, orsrc, ok ? (unsigned)(((oy * a.Wout + ox0 + p) * C + it.nb * UP_NT + scq * 8) * 2) : 0xffffffffu, 0, (C == 32 ? IRE_ST_LINE : IRE_ST_PART));
+                if constexpr (!(IRE_UP_ABL & 4)) __builtin_amdgcn_raw_buffer_store_b128(v, orsrc, ok ? (unsigned)((oy * a.Wout + ox0 + p) * C + it.nb * UP_NT + scq * 8) * 2u : 0xffffffffu, 0, (C == 32 ? IRE_ST_LINE : IRE_ST_PART));
                 else asm volatile("" :: "v"(v));
             }
         }
@@ -525,7 +525,7 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
             const int C = a.cout;
             pf_base = reinterpret_cast<const char*>(a.in1) + (size_t)sq0.it.img * a.Hout * a.Wout * C * 2;
             pf_off = (unsigned)((2 * (sq0.it.ty * UP_TH + wave * 2)) * a.Wout + 2 * (sq0.it.tx * UP_TW + r)) * (unsigned)(C * 2) + (unsigned)(h * 32);
-            pf_lim = (unsigned)(a.Hout * a.Wout * C * 2 - 4);
+            pf_lim = tensor_bytes(a.Hout, a.Wout, C * 2) - 4u;
         }
         auto group = [&](auto g_tag) __attribute__((always_inline)) {
             constexpr int g = decltype(g_tag)::value;

@@ -240,6 +240,7 @@ void Engine::check_shape(int n, int h, int w, bool for_restore) const {
     if (h <= 0 || w <= 0 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size");
     if (for_restore && (h % 8 || w % 8 || h < 16 || w < 16))
         fail(IRE_ERR_INVALID_INPUT, "invalid image size for restore: height and width must be multiples of 8, >= 16");
+    if (for_restore && !piece_addressable(h, w, 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(h, w));
 }
 
 void Engine::ensure_io(int n, int h, int w) {
@@ -264,6 +265,7 @@ void Engine::leave(hipStream_t s) {
 void Engine::check_fit(int n, int h, int w) const {
     if (n <= 0 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid batch size n (1..max_batch)");
     if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size: height and width must be in 1..8192");
+    if (!piece_addressable(fit_dim(h), fit_dim(w), 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(fit_dim(h), fit_dim(w)));      // the padded image is what runs
 }
 
 void Engine::ensure_pad(int n, int H, int W) {
@@ -285,6 +287,7 @@ void Engine::free_workspace() {
 
 int Engine::capacity_for(int h, int w) const {
     if (h <= 0 || w <= 0 || h > 8192 || w > 8192 || h % 8 || w % 8 || h < 16 || w < 16) return 0;
+    if (!piece_addressable(h, w, 0)) return 0;       // the shape restore refuses (8192 x 8192: conv_plan.hpp)
     size_t free_b = 0, total_b = 0;
     if (hipSetDevice(device_) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 0;
     // what this engine already holds for activations would be released on a change of shape
@@ -788,6 +791,7 @@ void Engine::restore_fit_device_mixed(const uint8_t* d_rgb, int n, int h, int w,
 void Engine::check_fuse_fit(int nsets, int k, int h, int w) const {
     if (k < 2 || k > 3) fail(IRE_ERR_INVALID_INPUT, "invalid view count for fusion: expected 2..3");
     if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size: height and width must be in 1..8192");
+    if (!piece_addressable(fit_dim(h), fit_dim(w), 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(fit_dim(h), fit_dim(w)));      // before anything is allocated for it
     if (nsets < 1 || nsets > kFuseMaxSets || nsets * k > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid batch size for fusion: expected 1..16 view sets of at most max_batch images");
 }
 

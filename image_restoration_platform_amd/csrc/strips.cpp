@@ -33,6 +33,9 @@ StripSession::StripSession(Engine& eng, int H, int W, int nstrips_total, int fir
     // a strip must start on a tile boundary of every producing kernel at every level (16 rows at 1/8 scale => 128 rows)
     if (nstrips_total > 1 && hr_ % 128) fail(IRE_ERR_INVALID_INPUT, "invalid strip height: rows per strip must be a multiple of 128");
     if (nstrips_total == 1 && (H % 8 || H < 16)) fail(IRE_ERR_INVALID_INPUT, "invalid image size for restore: height and width must be multiples of 8, >= 16");
+    // a strip's tensors carry two halo rows: 8192 x 8192 as ONE strip is 8194 rows, past 2^32 bytes at level 0 (conv_plan.hpp)
+    if (!piece_addressable(hr_, W, 1))
+        fail(IRE_ERR_INVALID_INPUT, "invalid strip height: a level-0 tensor of a strip ((rows + 2) x width x 64 bytes) must stay below 2^32 bytes; use more strips");
     if (first_strip < 0 || nlocal < 1 || first_strip + nlocal > nstrips_total) fail(IRE_ERR_INVALID_INPUT, "invalid strip range");
     IRE_HIP(hipSetDevice(E.device_));
     strips_.resize(nlocal);       // (a throw below: mem_ frees what was allocated)

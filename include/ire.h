@@ -112,7 +112,8 @@ const char* ire_last_error(void);
 /* Load RestoreNet-v0 weights from memory (same bytes as the weight file). */
 int ire_load_weights(ire_engine* e, const void* blob, size_t bytes);
 /* Images of this shape one restore call can take right now: min(max_batch, what the free HBM (hipMemGetInfo) holds
- * at the engine's real per-image footprint: activation workspace + staging); 0 if the shape is unsupported or not
+ * at the engine's real per-image footprint: activation workspace + staging); 0 if the shape is unsupported (ire_restore's
+ * rules, 8192 x 8192 included) or not
  * even one image fits (a restore call would then fail with IRE_ERR_UNAVAILABLE "out of device memory"). */
 int ire_max_batch_for(ire_engine* e, int h, int w);
 
@@ -124,7 +125,10 @@ int ire_classify(ire_engine* e, const uint8_t* rgb, int n, int h, int w, int row
                  const uint8_t* is_jpeg, double* scores_out, int32_t* label_out);
 /* restoreImage() with one image per job: out_rgb is n*h*w*3 (tightly packed).  scores==NULL
  * => classify inside (is_jpeg then required); else n*7 doubles used as conditioning.
- * h and w must be multiples of 8 (three stride-2 levels), >= 16. */
+ * h and w must be multiples of 8 (three stride-2 levels), >= 16, at most 8192, and h * w * 64 < 2^32: the network's widest tensor of
+ * one image (32 channels of bf16 per pixel) is addressed with 32-bit byte offsets.  Of the sizes up to 8192 a side that excludes
+ * 8192 x 8192 alone (IRE_ERR_INVALID_INPUT; ire_max_batch_for answers 0); ire_restore_tiled_device restores it in 2..64 row strips.
+ * The batch size is no part of the rule: images lie a 64-bit stride apart. */
 int ire_restore(ire_engine* e, const uint8_t* rgb, int n, int h, int w, const double* scores,
                 const uint8_t* is_jpeg, uint8_t* out_rgb, ire_timings* t);
 /* restoreImage() with k = 2..3 views of one scene: align to view 0 and blend.  out: h*w*3.
@@ -178,6 +182,7 @@ int ire_encode_png_base64(ire_engine* e, const uint8_t* rgb, int n, int h, int w
  * (pixel (y, x) = source (min(y, h-1), min(x, w-1))), restores that and returns the top-left h x w window:
  * result == crop(ire_restore(edge_pad(x), scores), h, w).  scores == NULL => the classifier runs on the ORIGINAL h x w pixels
  * (never the padded copy) inside the same call.  A shape ire_restore takes is not padded and gives ire_restore's bytes.
+ * ire_restore's size rule holds for the padded image: H * W * 64 < 2^32, i.e. not both h and w above 8184.
  * Device staging: the first batch of a ragged shape allocates the padded staging (and, for text results, the encoder's scratch)
  * for max_batch images of it, so later batches never allocate -- as long as that is <= 256 MB (max_batch * H * W * 3; at
  * max_batch 8 up to about 3300 x 3300).  Above it the staging is sized for the batch at hand, and a later LARGER batch of the
@@ -337,7 +342,8 @@ int ire_job_release(ire_engine* e, ire_job* job);
  * The image is cut into nstrips equal row strips; every layer runs strip by strip, the boundary rows of every tensor a 3x3
  * convolution reads are exchanged between neighbouring strips after the layer that produced it (per-level halo exchange),
  * and the GroupNorm partial statistics of all strips are combined before each GroupNorm.  The result is bit-identical to
- * ire_restore_device on the whole image.  H must be a multiple of nstrips, rows per strip a multiple of 128, W of 8. */
+ * ire_restore_device on the whole image.  H must be a multiple of nstrips, rows per strip a multiple of 128, W of 8, and a strip
+ * with its two halo rows obeys ire_restore's size rule: (H / nstrips + 2) * W * 64 < 2^32 (8192 x 8192 needs two strips or more). */
 /* All strips on this GPU ("virtual ranks": the exchange steps are in-device copies).  d_scores NULL => classify inside. */
 int ire_restore_tiled_device(ire_engine* e, const uint8_t* d_rgb, int h, int w, int nstrips, const double* d_scores,
                              const uint8_t* d_is_jpeg, uint8_t* d_out_rgb, void* stream);

@@ -2,8 +2,14 @@
 // network's convolutions in schedule order for a list of cases and prints, per case and layer group (the profiler key), one line with
 // every field of the launch plan, in the order of the header line; two ops of one group that plan differently print both lines.  The ConvDesc of a layer is what
 // weight_pack.hpp's packer produces for zero weights of the layer's shape: which arrays exist depends on shapes and precision only.
-// usage: conv_plan_dump fixture | props | fp8 | strips | items      (items: the cases of tests/test_items_gpu.py at its two shapes, and the (3, 200, 328) batch under IRE_PK 0 / 1 / 2; strips: the strips of tests/test_strips_layers_gpu.py's shapes; fixture: the recorded cases; props: the cases behind the separately asserted invariants;
-// fp8: an fp8 engine under every combination of the switches that decide its C >= 128 ResBlock convolutions)
+// usage: conv_plan_dump fixture | props | fp8 | strips | items | large | rule
+//   fixture: the recorded cases
+//   props:   the cases behind the separately asserted invariants
+//   fp8:     an fp8 engine under every combination of the switches that decide its C >= 128 ResBlock convolutions
+//   strips:  the strips of tests/test_strips_layers_gpu.py's shapes
+//   items:   the cases of tests/test_items_gpu.py at its two shapes, and the (3, 200, 328) batch under IRE_PK 0 / 1 / 2
+//   large:   conv_extents -- bytes, items, stages, partials -- of every launch of tests/test_large_shapes_gpu.py's shapes and strip plans
+//   rule:    piece_addressable on both sides of its boundary
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -134,6 +140,21 @@ static std::vector<Case> item_cases() {
     return cs;
 }
 
+// the shapes of tests/test_large_shapes_gpu.py, whole and in the strip plans it runs (every strip), plus the shapes the issue named that
+// the strip planner refuses (4224 in 8, 8128 in 8: rows per strip no multiple of 128) as whole images, and 8192 x 8192 whole: the one
+// image the address rule refuses, printed so that the test sees WHY
+static const int kLargeWhole[8][3] = {{1, 4224, 8192}, {1, 8064, 8192}, {1, 8128, 8192}, {1, 8184, 8192}, {1, 8192, 8184}, {1, 8192, 8192}, {1, 8192, 4224}, {64, 1024, 1024}};
+static const int kLargeStrips[6][3] = {{4224, 8192, 11}, {8064, 8192, 7}, {8192, 8184, 8}, {8192, 8184, 16}, {8192, 8192, 16}, {8192, 4224, 8}};
+static std::vector<Case> large_cases() {
+    std::vector<Case> cs;
+    for (auto& s : kLargeWhole) cs.push_back(whole({}, false, s[0], s[1], s[2]));
+    cs.push_back(whole({}, true, 1, 4224, 8192));
+    cs.push_back(whole({}, true, 1, 8192, 8184));
+    for (auto& p : kLargeStrips)
+        for (int s = 0; s < p[2]; ++s) cs.push_back(strip_of(p[0], p[1], p[2], s));
+    return cs;
+}
+
 // ---- the network's convolutions as weight_pack.hpp packs them (zero weights: existence of an array is a matter of shape) ----
 static const int kW[4] = {32, 64, 128, 256};
 struct NetDesc {
@@ -177,6 +198,8 @@ static const char* kKernel[] = {"V1", "F8", "PK", "W4", "PC", "RB", "PC_HEAD", "
 static const char* kSlab[] = {"none", "w", "wp", "w4", "w4h", "wstem", "wd", "wu", "wuf", "wdq", "wuq", "wsq", "wsk", "w8x", "w8"};
 static const char* kBias[] = {"bias", "bias_uf", "bias8"};
 
+static bool g_extents = false;      // mode `large`: conv_extents of every launch instead of the plan's fields
+
 static void run_case(const Case& c, const NetDesc& net) {
     static const char* vars[] = {"IRE_CONV_V1", "IRE_RB_PRIO", "IRE_W4", "IRE_W4_SPLIT", "IRE_UP_RB_MINC", "IRE_UP_SUBPIX", "IRE_UP_FUSE", "IRE_GN_FOLD", "IRE_PC",
                                  "IRE_PK", "IRE_UPQ", "IRE_DNQ", "IRE_HEAD_RB", "IRE_DOWN_RB", "IRE_STEM_RB", "IRE_FP8_MX"};
@@ -198,6 +221,14 @@ static void run_case(const Case& c, const NetDesc& net) {
         const ConvPlan p = plan_conv(sw, d, s, c.fp8);
         const long long in1_off = !has_in1 ? -1 : p.in1_first_row ? (long long)s.halo * (s.w >> lout) * d.cout : 0;
         char buf[1024];
+        if (g_extents) {
+            const ConvExtents e = conv_extents(p, d, s);
+            std::snprintf(buf, sizeof buf, "%s %s %llu %llu %llu %llu %lld %lld %lld %d %d %d %d", kKernel[p.kernel], p.kname, e.in0_bytes, e.in1_bytes, e.out_bytes,
+                          e.batch_bytes, e.items, e.stages, e.stat_floats, p.tiles_x, p.tiles_y, p.nblocks, p.nkc);
+            for (auto& gl : lines) if (gl.first == p.key && gl.second == buf) return;
+            lines.emplace_back(p.key, buf);
+            return;
+        }
         std::snprintf(buf, sizeof buf, "%s %d %d %s %s %s %s %d %d %d %d %d %d %d %d %lld %d %d %d %d %d %d %d %d %d %d %lld %d %d %d %.0f %.0f %.0f",
                       kKernel[p.kernel], (int)p.resid, (int)p.fused_act, p.kname, kSlab[p.w], kSlab[p.w1], kBias[p.bias], p.zeros ? 1 : 0, p.cin1, p.nkc,
                       p.nblocks, p.w4_nt, p.fp8, p.cout, p.group_size, in1_off, p.tile_h, p.tiles_x, p.tiles_y, p.iy_lo, p.iy_span, p.in_rows,
@@ -226,8 +257,23 @@ static void run_case(const Case& c, const NetDesc& net) {
 int main(int argc, char** argv) {
     if (argc != 2) return 2;
     const std::string mode = argv[1];
-    if (mode != "fixture" && mode != "props" && mode != "fp8" && mode != "strips" && mode != "items") return 2;
+    if (mode == "rule") {
+        // the address rule (piece_addressable) on both sides of its boundary: `rule ROWS W HALO answer level-0-bytes`
+        static const int q[][3] = {{8192, 8192, 0}, {8184, 8192, 0}, {8192, 8184, 0}, {8128, 8192, 0}, {8064, 8192, 0}, {4224, 8192, 0}, {4096, 8192, 0},
+                                   {8192, 4224, 0}, {1024, 1024, 0}, {16, 16, 0}, {8192, 8192, 1}, {8190, 8192, 1}, {8189, 8192, 1}, {8184, 8192, 1},
+                                   {4096, 8192, 1}, {1152, 8192, 1}, {512, 8192, 1}, {384, 8192, 1}, {1024, 4224, 1}};
+        for (auto& r : q) std::printf("rule %d %d %d %d %llu\n", r[0], r[1], r[2], piece_addressable(r[0], r[1], r[2]) ? 1 : 0, piece_tensor_bytes(r[0], r[1], r[2], 0));
+        std::printf("end %llu\n", kTensorBytesEnd);
+        return 0;
+    }
+    if (mode != "fixture" && mode != "props" && mode != "fp8" && mode != "strips" && mode != "items" && mode != "large") return 2;
     const NetDesc bf16 = net_desc(false), fp8 = net_desc(true);
+    if (mode == "large") {
+        g_extents = true;
+        std::printf("# case group kernel kname in0_bytes in1_bytes out_bytes batch_bytes items stages stat_floats tiles_x tiles_y nblocks nkc\n");
+        for (const Case& c : large_cases()) run_case(c, c.fp8 ? fp8 : bf16);
+        return 0;
+    }
     std::printf("# case group kernel resid fused_act kname w w1 bias zeros cin1 nkc nblocks w4_nt fp8 cout group_size in1_off tile_h tiles_x tiles_y iy_lo iy_span in_rows in_row_off parts_mul stats_level ty0 stats_off stat_parts folds_gn fam flops flops_exec bytes\n");
     for (const Case& c : mode == "props" ? property_cases() : mode == "fp8" ? fp8_cases() : mode == "strips" ? strip_layer_cases() : mode == "items" ? item_cases() : fixture_cases()) run_case(c, c.fp8 ? fp8 : bf16);
     return 0;

@@ -54,7 +54,7 @@ def dumps(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("conv_plan")
     exe, exe_asan = _build(tmp, "cp", ["-O2"]), _build(tmp, "cp_asan", ["-O1", "-fsanitize=address,undefined"])
     return {"fixture": _run(exe, "fixture"), "fixture_asan": _run(exe_asan, "fixture"), "props": _run(exe, "props"), "fp8": _run(exe, "fp8"), "strips": _run(exe, "strips"),
-            "items": _run(exe, "items")}
+            "items": _run(exe, "items"), "large": _run(exe, "large"), "large_asan": _run(exe_asan, "large"), "rule": _run(exe_asan, "rule")}
 
 
 FIXTURE = os.path.join(GOLDEN, "conv_plan_9e80c0a.txt")
@@ -372,3 +372,78 @@ def test_the_batch_of_the_bit_for_bit_test_plans_conv_w4_64_cout_items_unless_th
             assert (f["kname"], f["w"], f["w4_nt"]) == ("conv_w4", "w4h", "64"), (pk, g)
             f = plans["IRE_W4_SPLIT=0,IRE_PK=" + pk, "bf16", 3, 200, 328][g]
             assert (f["kname"], f["w"], f["w4_nt"], f["nblocks"]) == (want[pk][g.endswith("rb2")], "w4", "0", str(WIDTHS[int(g[1])] // 128)), (pk, g)
+
+
+# ---- the largest shapes: csrc/conv_plan.hpp's address rule and conv_extents (DESIGN.md "Address arithmetic at the largest shapes") ----------
+U32_END = 1 << 32            # resource sizes and per-lane byte offsets are unsigned 32-bit; 0xffffffff asks for the zero padding
+INT_MAX = (1 << 31) - 1      # persist.hpp's cursor and the partials layout count in `int`
+LARGE_WHOLE = [(1, 4224, 8192), (1, 8064, 8192), (1, 8128, 8192), (1, 8184, 8192), (1, 8192, 8184), (1, 8192, 8192), (1, 8192, 4224), (64, 1024, 1024)]
+LARGE_STRIPS = [(4224, 8192, 11), (8064, 8192, 7), (8192, 8184, 8), (8192, 8184, 16), (8192, 8192, 16), (8192, 4224, 8)]      # tests/test_large_shapes_gpu.py's plans
+
+
+def test_the_address_rule_has_its_boundary_where_a_level_0_tensor_reaches_2_to_the_32(dumps):
+    """piece_addressable(rows, w, halo): every tensor of the piece below 2^32 bytes; level 0 (64 bytes a pixel) is the largest.  Among whole
+    images the engine admits otherwise (multiples of 8, 16..8192 a side) that refuses 8192 x 8192 alone, where the byte count is 2^32 exactly
+    and wraps to a resource of no bytes; among strips (two halo rows) it refuses from 8190 rows of 8192 pixels."""
+    rows = [ln.split() for ln in dumps["rule"].splitlines()]
+    assert rows[-1] == ["end", str(U32_END)] and len(rows) == 20
+    got = {(int(r), int(w), int(halo)): (int(ok), int(b)) for _, r, w, halo, ok, b in rows[:-1]}
+    for (r, w, halo), (ok, b) in got.items():
+        assert b == (r + 2 * halo) * w * 64 and ok == (b < U32_END), (r, w, halo, ok, b)
+    assert [k for k, v in got.items() if not v[0]] == [(8192, 8192, 0), (8192, 8192, 1), (8190, 8192, 1)]
+    assert got[8192, 8192, 0][1] == U32_END and got[8190, 8192, 1][1] == U32_END            # exactly the wrap to zero
+    assert got[8184, 8192, 0] == (1, U32_END - 8 * 8192 * 64) and got[8192, 8184, 0][0] == 1 and got[8189, 8192, 1][0] == 1
+    assert got[4096, 8192, 0] == (1, 1 << 31) and got[4224, 8192, 0][1] > 1 << 31           # admitted, and past what `int` holds
+    # the rule as arithmetic over every admitted whole-image shape: one refusal
+    sides = range(16, 8193, 8)
+    assert [(h, w) for h in sides[-40:] for w in sides[-40:] if h * w * 64 >= U32_END] == [(8192, 8192)]
+    assert all(h * w * 64 < U32_END for h in sides for w in sides if (h, w) != (8192, 8192))
+
+
+def test_every_launch_of_the_largest_shapes_fits_the_types_the_kernels_index_with(dumps):
+    """conv_extents of every launch planned for the large-shape tests: one image's tensors (resource sizes, byte offsets: unsigned 32-bit),
+    item, stage and partial counts (`int`).  8192 x 8192 whole is printed too and is the only case with a tensor of 2^32 bytes: what the
+    rule refuses.  Strips stay below 2^30 bytes, and the batch of 64 ends at byte 2^32 of its level-0 tensors with image 32 at 2^31."""
+    assert dumps["large_asan"] == dumps["large"]
+    head, *lines = dumps["large"].splitlines()
+    fields = head.split()[3:]
+    assert fields == "kernel kname in0_bytes in1_bytes out_bytes batch_bytes items stages stat_floats tiles_x tiles_y nblocks nkc".split()
+    cases = {}
+    for ln in lines:
+        c, g, *v = ln.split(" ")
+        assert len(v) == len(fields) and g not in cases.get(c, {}), ln          # one plan per (case, group)
+        cases.setdefault(c, {})[g] = dict(zip(fields, v))
+    want = ["default:bf16:%dx%dx%d" % s for s in LARGE_WHOLE] + ["default:fp8:1x4224x8192", "default:fp8:1x8192x8184"] + \
+           ["default:bf16:strip%dof%d:%dx%d" % (s, n, h, w) for h, w, n in LARGE_STRIPS for s in range(n)]
+    assert sorted(cases) == sorted(want)
+    over = {}
+    for c, groups in cases.items():
+        _, _, n, h, w, s, ns = _case(c)
+        assert set(groups) == set(SCHEDULE) - {"fuse0", "fuse1", "fuse2"}, c     # default switches: `fuse` rides in `up`
+        for g, f in groups.items():
+            assert f["kernel"] != "V1", (c, g)                                   # every launch is a persistent kernel: grid = min(items, CUs)
+            one = max(int(f["in0_bytes"]), int(f["in1_bytes"]), int(f["out_bytes"]))
+            assert int(f["items"]) == int(f["tiles_x"]) * int(f["tiles_y"]) * n * int(f["nblocks"]) > 0
+            assert int(f["items"]) <= int(f["stages"]) <= INT_MAX and int(f["stat_floats"]) <= INT_MAX, (c, g)
+            assert int(f["batch_bytes"]) == n * one < 1 << 40, (c, g)            # 64-bit bases: far from their type's end
+            if one >= U32_END:
+                over.setdefault(c, []).append(g)
+            if s is not None:
+                assert one < 1 << 30, (c, g)
+    # the one refused shape, and where it breaks: the level-0 tensors are 2^32 bytes -- a 32-bit resource of NO bytes
+    l0 = ["stem", "L0.rb1", "L0.rb2", "down0", "up0", "head"]
+    assert over == {"default:bf16:1x8192x8192": l0}
+    big = cases["default:bf16:1x8192x8192"]
+    assert int(big["stem"]["out_bytes"]) == int(big["L0.rb1"]["in0_bytes"]) == int(big["head"]["in0_bytes"]) == U32_END
+    assert int(big["L1.rb1"]["out_bytes"]) == 1 << 31
+    # the marks the GPU tests cross
+    lv0 = lambda c: int(cases[c]["L0.rb2"]["out_bytes"])
+    assert 1 << 31 < lv0("default:bf16:1x4224x8192") == lv0("default:bf16:1x8192x4224") == lv0("default:fp8:1x4224x8192") < U32_END
+    assert lv0("default:bf16:1x8064x8192") == U32_END - 128 * 8192 * 64 and lv0("default:bf16:1x8184x8192") == U32_END - 8 * 8192 * 64
+    assert lv0("default:bf16:1x8192x8184") == lv0("default:fp8:1x8192x8184") == U32_END - (1 << 22)        # the most the rule admits, strippable
+    top = cases["default:bf16:1x8192x8184"]                    # a ragged last tile column at every level: 8184, 4092, 2046, 1023 columns
+    assert [int(top[g]["tiles_x"]) for g in ("L0.rb1", "L1.rb1", "L2.rb1", "L3.rb1")] == [256, 128, 64, 32]
+    b64 = cases["default:bf16:64x1024x1024"]["L0.rb2"]
+    assert int(b64["batch_bytes"]) == U32_END and 32 * int(b64["out_bytes"]) == 1 << 31
+    # the 64-image batch stays on the producer / consumer kernel at level 0: its coefficient table holds 64 images
+    assert cases["default:bf16:64x1024x1024"]["L0.rb1"]["kname"] == "conv_pc"

@@ -316,8 +316,12 @@ def test_capacity_query_and_gauges(engine):
     """ire_max_batch_for computes from the free HBM and the real per-image footprint; ire_get_stats counts batches/images."""
     assert engine.max_batch_for(1024, 1024) == 8 and engine.max_batch_for(64, 64) == 8
     assert engine.max_batch_for(60, 64) == 0 and engine.max_batch_for(8, 8) == 0 and engine.max_batch_for(16384, 64) == 0
-    big = engine.max_batch_for(8192, 8192)             # ~38 GiB of activations per image: fewer than max_batch fit in 288 GB
-    assert 1 <= big < 8, big
+    # 8192 x 8192 is the one shape restore refuses (a level-0 tensor of 2^32 bytes: csrc/conv_plan.hpp::piece_addressable); the largest it
+    # takes, on either side of it, needs ~38 GiB of activations per image: fewer than max_batch fit in 288 GB
+    assert engine.max_batch_for(8192, 8192) == 0
+    for h, w in ((8184, 8192), (8192, 8184)):
+        big = engine.max_batch_for(h, w)
+        assert 1 <= big < 8, (h, w, big)
     s0 = engine.stats()
     imgs = synth.batch(3, 64, 64, start=50)
     engine.restore(imgs)

@@ -17,6 +17,7 @@
 // Weights: a.w = [n-block of 128][kc32][the 9 taps in phase order][c8][128 rows, permuted like conv_w4's][8] bf16
 // (weight_pack.hpp::pack_conv d_wdq).  Roofline: input staging (every output pixel reads four input pixels), then MFMA.
 #include "conv_mfma.hpp"
+#include "conv_prims.hpp"
 #include "persist.hpp"
 
 #include <type_traits>
@@ -24,12 +25,6 @@
 namespace ire {
 
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 #ifndef DQ_ST
 #define DQ_ST IRE_ST_LINE   // cache policy of the output stores (conv_mfma.hpp): build-time A/B
@@ -54,37 +49,12 @@ constexpr int DQ_PATCH_BYTES = 8 * DQ_NT * 2;                   // 2 048: 8 pixe
 constexpr int DQ_LDS = DQ_PATCH_BASE + 8 * DQ_PATCH_BYTES;
 static_assert(DQ_LDS <= 160 * 1024, "LDS");
 
-__host__ __device__ constexpr int dq_ntaps(int ph) { return ((ph >> 1) ? 2 : 1) * ((ph & 1) ? 2 : 1); }
 __host__ __device__ constexpr int dq_tap_base(int ph) { return ph == 0 ? 0 : ph == 1 ? 1 : ph == 2 ? 3 : 5; }     // first tap of the phase in the group's 9
 // tap t of phase (a, b) reads window pixel (row + oy, column + ox): oy = a ? t / ntx : 1, ox = b ? t % ntx : 1 (offsets -1 / 0 from the output pixel)
 __host__ __device__ constexpr int dq_tap_win(int ph, int t) {
     const int a = ph >> 1, b = ph & 1, ntx = b ? 2 : 1;
     const int oy = a ? t / ntx : 1, ox = b ? t % ntx : 1;
     return oy * 2 + ox;
-}
-
-__device__ __forceinline__ unsigned dq_pack(float a, float b) {
-    f32x2_t f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
-__device__ __forceinline__ void dq_glds16(const void* gsrc, unsigned lds_dst_uniform) {   // LDS-DMA, 1 KB per wave-instruction (conv_rb.hip::rb_glds16)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
-__device__ __forceinline__ float dq_swap16_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
-__device__ __forceinline__ float dq_swap32_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
-// conv_upq.hip::uq_stage_barrier
-template <int KEEP> __device__ __forceinline__ void dq_stage_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(KEEP) : "memory");
 }
 
 template <int COUT>
@@ -140,7 +110,7 @@ __global__ __launch_bounds__(DQ_THREADS) void conv_dnq_kernel(ConvArgs a) {
     // phase: 1 / 2 / 2 / 4 x 8 KB = 8 .. 32 pieces over the eight waves), tile piece 32 + w (waves 0..3)
     auto plan_stage = [&](auto ph_tag, const PersistStage& st, int b, Plan& P) __attribute__((always_inline)) {
         constexpr int PH = decltype(ph_tag)::value;              // == st.kc / NKC
-        constexpr int NSL = dq_ntaps(PH);                        // slab pieces per wave: the phase's taps x 8 KB over eight waves
+        constexpr int NSL = phase_ntaps(PH);                        // slab pieces per wave: the phase's taps x 8 KB over eight waves
         const unsigned tdst = smem_lds + b * DQ_TILE_BYTES, sdst = smem_lds + DQ_W_BASE + b * DQ_SLAB_BYTES;
         const int kc = st.kc - PH * NKC;
         const char* base = reinterpret_cast<const char*>(a.in0) + (size_t)st.it.img * a.in_rows * a.Win * (2 * Cin) + kc * 64;
@@ -196,10 +166,10 @@ __global__ __launch_bounds__(DQ_THREADS) void conv_dnq_kernel(ConvArgs a) {
         item_offsets(cs.it);
         plan_stage(std::integral_constant<int, 0>{}, cs, 0, P);
 #pragma unroll
-        for (int i = 0; i < 10; ++i) if (i < P.n) dq_glds16(P.src[i], P.dst[i]);
+        for (int i = 0; i < 10; ++i) if (i < P.n) glds16(P.src[i], P.dst[i]);
     }
     if (tid < C) reinterpret_cast<float*>(smem + DQ_BIAS_BASE)[tid] = a.bias[tid];
-    dq_stage_barrier<0>();
+    stage_barrier<0>();
     int stage_no = 0;
     bool pre_issued = false;              // the next stage's pieces are already on their way (issued by the previous item's epilogue)
 
@@ -223,7 +193,7 @@ __global__ __launch_bounds__(DQ_THREADS) void conv_dnq_kernel(ConvArgs a) {
         // pieces of the same 128-byte lines, and back to back the second piece is an L2 hit -- chunk-major (the phases of a chunk, then the
         // next chunk, 8 us later) fetched every line of `down1`'s input from HBM twice (2.1 x its tensor; DMA-only time 102 us).
         auto stage = [&](auto ph_tag, auto buf_tag, bool last_chunk) __attribute__((always_inline)) {
-            constexpr int PH = decltype(ph_tag)::value, BUF = decltype(buf_tag)::value, NTAPS = dq_ntaps(PH);
+            constexpr int PH = decltype(ph_tag)::value, BUF = decltype(buf_tag)::value, NTAPS = phase_ntaps(PH);
             Plan P;
             P.n = 0;
             if (stage_no + 1 < S && !pre_issued) {
@@ -252,7 +222,7 @@ __global__ __launch_bounds__(DQ_THREADS) void conv_dnq_kernel(ConvArgs a) {
                         // the next stage's DMA pieces, spread over the k-loop: piece i rides in front of MFMA pair (i NG) / 10
 #pragma unroll
                         for (int i = 0; i < 10; ++i)
-                            if ((i * NG) / 10 == g && i < P.n) dq_glds16(P.src[i], P.dst[i]);
+                            if ((i * NG) / 10 == g && i < P.n) glds16(P.src[i], P.dst[i]);
                         if (g + 1 < NG) bq[(g + 1) & 1] = rd_b((g + 1) / NTL, (g + 1) % NTL);
                         if (st + 1 < NS && j == 1) aq[(st + 1) & 1][0] = rd_a(st + 1, 0);
                         if (st + 1 < NS && j == 2) aq[(st + 1) & 1][1] = rd_a(st + 1, 1);
@@ -263,12 +233,12 @@ __global__ __launch_bounds__(DQ_THREADS) void conv_dnq_kernel(ConvArgs a) {
                     }
             } else {
 #pragma unroll
-                for (int i = 0; i < 10; ++i) if (i < P.n) dq_glds16(P.src[i], P.dst[i]);
+                for (int i = 0; i < 10; ++i) if (i < P.n) glds16(P.src[i], P.dst[i]);
             }
             ++stage_no;
             cs = cn; cn = cursor.next();
             // the next stage is staged; nobody reads this stage's pair any more
-            if (pre_issued) dq_stage_barrier<16>(); else dq_stage_barrier<0>();
+            if (pre_issued) stage_barrier<16>(); else stage_barrier<0>();
             pre_issued = false;
             flush_stats();
         };
@@ -290,7 +260,7 @@ __global__ __launch_bounds__(DQ_THREADS) void conv_dnq_kernel(ConvArgs a) {
             Plan P;
             plan_stage(std::integral_constant<int, 0>{}, cn, 1, P);       // the next item's stage 1 = phase 0, chunk 1
 #pragma unroll
-            for (int i = 0; i < 10; ++i) if (i < P.n) dq_glds16(P.src[i], P.dst[i]);
+            for (int i = 0; i < 10; ++i) if (i < P.n) glds16(P.src[i], P.dst[i]);
             pre_issued = true;
         }
         if constexpr (DQ_ABL & 2) {
@@ -328,8 +298,8 @@ __global__ __launch_bounds__(DQ_THREADS) void conv_dnq_kernel(ConvArgs a) {
                 for (int g = 0; g < NTL * 2; ++g) {
                     const f32x16_t& c = acc[m][g >> 1];
                     const int pp = g & 1;
-                    pkd[m][g] = u32x4_t{dq_pack(c[8 * pp + 0], c[8 * pp + 1]), dq_pack(c[8 * pp + 2], c[8 * pp + 3]),
-                                        dq_pack(c[8 * pp + 4], c[8 * pp + 5]), dq_pack(c[8 * pp + 6], c[8 * pp + 7])};
+                    pkd[m][g] = u32x4_t{pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
+                                        pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
                 }
             __builtin_amdgcn_sched_barrier(0);
             float ssum = 0.f, qsum = 0.f;
@@ -366,8 +336,8 @@ __global__ __launch_bounds__(DQ_THREADS) void conv_dnq_kernel(ConvArgs a) {
                     }
                 }
             // this lane's chunk cc_r over its read-backs; the other lanes with the same chunk sit 16 apart
-            ssum = dq_swap16_add(ssum); qsum = dq_swap16_add(qsum);
-            ssum = dq_swap32_add(ssum); qsum = dq_swap32_add(qsum);
+            ssum = swap16_add(ssum); qsum = swap16_add(qsum);
+            ssum = swap32_add(ssum); qsum = swap32_add(qsum);
             if (l_e < 16) *reinterpret_cast<float2*>(red + red_par * (8 * 32) + (wave * 16 + cc_r) * 2) = make_float2(ssum, qsum);
             st_img = it.img; st_tile = it.tile; st_cout0 = cout0; st_par = red_par; red_par ^= 1;
             if constexpr (DQ_ABL & 8) { if (pre_issued) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }      // (no stores behind the pieces: the counted wait would let them pass)
@@ -385,8 +355,7 @@ void conv_dnq_launch(const ConvArgs& a, hipStream_t stream) {
     if ((a.cout != 128 && a.cout != 256) || a.cin0 % 64 || a.nkc != a.cin0 / 32 || a.nblocks != a.cout / DQ_NT || !a.w || !a.zeros)
         fail(IRE_ERR_INTERNAL, "internal: conv_dnq arguments");
     const int items = a.tiles_x * a.tiles_y * a.nimg * a.nblocks;
-    const int cus = persistent_grid_cus();
-    const int grid = items < cus ? items : cus;
+    const int grid = persistent_grid(items);
     if (a.cout == 128) hipLaunchKernelGGL(conv_dnq_kernel<128>, dim3(grid), dim3(DQ_THREADS), 0, stream, a);
     else hipLaunchKernelGGL(conv_dnq_kernel<256>, dim3(grid), dim3(DQ_THREADS), 0, stream, a);
     IRE_HIP(hipGetLastError());

@@ -16,17 +16,12 @@
 // stores straight from the accumulators (permuted slab rows), GroupNorm partial statistics per tile.
 // Roofline: input staging (the layer reads the full-resolution tensor: 4 staged pixels per output pixel), then MFMA.
 #include "conv_mfma.hpp"
+#include "conv_prims.hpp"
 #include "persist.hpp"
 
 namespace ire {
 
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 #ifndef DN_LD_NT
 #define DN_LD_NT 0     // 1: the input rows non-temporal (build-time A/B)
@@ -45,32 +40,12 @@ constexpr int DN_RED_HALF = 8 * (DN_NT / 8) * 4 * 4;
 constexpr int DN_LDS = DN_MAIN + 2 * DN_RED_HALF + 256 * 4;
 static_assert(DN_LDS <= 160 * 1024, "LDS");
 
-__device__ __forceinline__ unsigned dn_pack(float a, float b) {
-    f32x2_t f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
-__device__ __forceinline__ void dn_glds16(const void* gsrc, unsigned lds_dst_uniform) {   // see conv_rb.hip::rb_glds16
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
-template <int N> __device__ __forceinline__ float dn_ror_add(float v) {
-    const int r = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false);
-    return v + __builtin_bit_cast(float, r);
-}
-__device__ __forceinline__ float dn_swap16_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
-
-// taps of phase p = a*2 + b, in slab order: tap index t = (dy index)*ntx + (dx index); offsets dy, dx in {-1, 0}
-__host__ __device__ constexpr int dn_ntaps(int p) { return ((p >> 1) ? 2 : 1) * ((p & 1) ? 2 : 1); }
+// taps of phase p = a*2 + b (phase_ntaps of them), in slab order: tap index t = (dy index)*ntx + (dx index); offsets dy, dx in {-1, 0}
 __host__ __device__ constexpr int dn_slab_off(int p) { return p == 0 ? 0 : p == 1 ? 4096 : p == 2 ? 12288 : 20480; }   // bytes within a (nb, kc) group
 constexpr int DN_GROUP_BYTES = 9 * 4 * DN_NT * 16;      // 36 KB per (n-block, k-chunk): 9 taps
 
 struct DnRegs { u32x4_t v[DN_IN_ITERS]; };
-__host__ __device__ constexpr int dn_dma_iters(int p) { return (dn_ntaps(p) * 4 * DN_NT + DN_THREADS - 1) / DN_THREADS; }   // LDS-DMA issues per wave for a phase's slab: 1, 1, 1, 2
+__host__ __device__ constexpr int dn_dma_iters(int p) { return (phase_ntaps(p) * 4 * DN_NT + DN_THREADS - 1) / DN_THREADS; }   // LDS-DMA issues per wave for a phase's slab: 1, 1, 1, 2
 template <int N> __device__ __forceinline__ void dn_wait_vm(bool counted) {
     // counted: at most N newer VMEM operations outstanding => everything issued before them is done (VMEM completes in order)
     if (counted) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
@@ -228,8 +203,8 @@ __global__ __launch_bounds__(DN_THREADS) void conv_down_kernel(ConvArgs a) {
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
                     const f32x16_t& c = acc[m][j];
-                    const unsigned w[4] = {dn_pack(c[8 * pp + 0], c[8 * pp + 1]), dn_pack(c[8 * pp + 2], c[8 * pp + 3]),
-                                           dn_pack(c[8 * pp + 4], c[8 * pp + 5]), dn_pack(c[8 * pp + 6], c[8 * pp + 7])};
+                    const unsigned w[4] = {pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
+                                           pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
                     float ts = 0.f, tq = 0.f;
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
@@ -242,11 +217,11 @@ __global__ __launch_bounds__(DN_THREADS) void conv_down_kernel(ConvArgs a) {
                     __builtin_amdgcn_raw_buffer_store_b128(wv4, orsrc, inb[m] ? offs[m] + (unsigned)(j * 64 + pp * 32) : 0xffffffffu, 0, IRE_ST_PART);
                 }
                 // sum over the 32 lanes of each half (one 16-B chunk each): cout >= 64 => a chunk never splits into two groups
-                sA = dn_ror_add<1>(sA); qA = dn_ror_add<1>(qA);
-                sA = dn_ror_add<2>(sA); qA = dn_ror_add<2>(qA);
-                sA = dn_ror_add<4>(sA); qA = dn_ror_add<4>(qA);
-                sA = dn_ror_add<8>(sA); qA = dn_ror_add<8>(qA);
-                sA = dn_swap16_add(sA); qA = dn_swap16_add(qA);
+                sA = ror_add<1>(sA); qA = ror_add<1>(qA);
+                sA = ror_add<2>(sA); qA = ror_add<2>(qA);
+                sA = ror_add<4>(sA); qA = ror_add<4>(qA);
+                sA = ror_add<8>(sA); qA = ror_add<8>(qA);
+                sA = swap16_add(sA); qA = swap16_add(qA);
                 if ((lane & 31) == 0) {
                     float* d = redw + (wave * 8 + j * 4 + 2 * pp + h_e) * 4;
                     d[0] = sA; d[1] = qA; d[2] = 0.f; d[3] = 0.f;
@@ -283,7 +258,7 @@ __global__ __launch_bounds__(DN_THREADS) void conv_down_kernel(ConvArgs a) {
         {   // weight slab of stage s+2 (phase (PHASE+2)&3: 4, 8, 8 or 16 KB) by LDS-DMA; branch-free: a wave past the slab's end
             // re-fetches a 64-piece group another wave also fetches (same bytes, same destination)
             constexpr int NPH = (PHASE + 2) & 3;
-            constexpr int pieces = dn_ntaps(NPH) * 4 * DN_NT;           // 16-B pieces: 256, 512, 512, 1024
+            constexpr int pieces = phase_ntaps(NPH) * 4 * DN_NT;           // 16-B pieces: 256, 512, 512, 1024
             const unsigned char* ws = wslab(sq2);
             const int wave_u = __builtin_amdgcn_readfirstlane(wave);
             const unsigned w_dst_lds = smem_lds + (unsigned)(DN_W_BASE + w2 * DN_W_BYTES_MAX);
@@ -291,7 +266,7 @@ __global__ __launch_bounds__(DN_THREADS) void conv_down_kernel(ConvArgs a) {
             for (int i = 0; i < D2; ++i) {
                 int cbase = i * DN_THREADS + wave_u * 64;
                 if ((i + 1) * DN_THREADS > pieces) cbase = cbase % pieces;
-                dn_glds16(ws + (size_t)(cbase + lane) * 16, w_dst_lds + cbase * 16);
+                glds16(ws + (size_t)(cbase + lane) * 16, w_dst_lds + cbase * 16);
             }
         }
         // the rows of stage s+1: requested at the start of stage s-1; since then: that stage's slab pieces, this stage's requests
@@ -348,8 +323,8 @@ __global__ __launch_bounds__(DN_THREADS) void conv_down_kernel(ConvArgs a) {
         const uint4* ws0 = reinterpret_cast<const uint4*>(wslab(sq0));
         const uint4* ws1 = reinterpret_cast<const uint4*>(wslab(sq1));
         uint4* wd = reinterpret_cast<uint4*>(smem + DN_W_BASE);
-        for (int i = tid; i < dn_ntaps(0) * 4 * DN_NT; i += DN_THREADS) wd[i] = ws0[i];                            // slab of stage 0 -> slot 0
-        for (int i = tid; i < dn_ntaps(1) * 4 * DN_NT; i += DN_THREADS) wd[DN_W_BYTES_MAX / 16 + i] = ws1[i];      // stage 1 -> slot 1
+        for (int i = tid; i < phase_ntaps(0) * 4 * DN_NT; i += DN_THREADS) wd[i] = ws0[i];                            // slab of stage 0 -> slot 0
+        for (int i = tid; i < phase_ntaps(1) * 4 * DN_NT; i += DN_THREADS) wd[DN_W_BYTES_MAX / 16 + i] = ws1[i];      // stage 1 -> slot 1
         uint4* in0 = reinterpret_cast<uint4*>(smem);
 #pragma unroll
         for (int i = 0; i < DN_IN_ITERS; ++i) store_chunk(i, R0, in0);
@@ -377,8 +352,7 @@ __global__ __launch_bounds__(DN_THREADS) void conv_down_kernel(ConvArgs a) {
 void conv_down_launch(const ConvArgs& a, hipStream_t stream) {
     if (a.cout % 64 || a.cout > 256 || a.nkc < 1 || a.stats == nullptr) fail(IRE_ERR_INTERNAL, "internal: conv_down shape");
     const int items = a.tiles_x * a.tiles_y * a.nimg * a.nblocks;
-    const int cus = persistent_grid_cus();
-    const int grid = items < cus ? items : cus;
+    const int grid = persistent_grid(items);
     hipLaunchKernelGGL(conv_down_kernel, dim3(grid), dim3(DN_THREADS), 0, stream, a);
     IRE_HIP(hipGetLastError());
 }

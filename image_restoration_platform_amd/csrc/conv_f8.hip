@@ -15,6 +15,7 @@
 // (accumulators start at bias / scale; dequantise, residual, bf16 stores, GroupNorm partials).  LDS tiles are two 16-channel
 // planes per pixel / per cout row, so every fragment is two conflict-free ds_read_b128.
 #include "conv_mfma.hpp"
+#include "conv_prims.hpp"
 #include "persist.hpp"
 #include "gn_fold.hpp"
 
@@ -22,10 +23,6 @@ namespace ire {
 
 namespace {
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 typedef int i32x8_t __attribute__((ext_vector_type(8)));
 
 constexpr float kF8ActScale = 16.0f;
@@ -49,32 +46,6 @@ constexpr int F8_COEF_OFF = F8_SCALE_OFF + 1024;         // [2 slots][A 32 | B 3
 constexpr int F8_LDS = F8_COEF_OFF + 2 * 256;
 static_assert((F8_PLANE / 4) % 32 == 16, "plane offset must be half a bank row");
 static_assert(F8_LDS <= 160 * 1024, "LDS");
-
-__device__ __forceinline__ unsigned f8_pack(float a, float b) {
-    f32x2_t f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
-__device__ __forceinline__ float f8_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float f8_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-__device__ __forceinline__ void f8_glds16(const void* gsrc, unsigned lds_dst_uniform) {   // see conv_rb.hip::rb_glds16
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
-template <int N> __device__ __forceinline__ float f8_ror_add(float v) {
-    const int r = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false);
-    return v + __builtin_bit_cast(float, r);
-}
-__device__ __forceinline__ float f8_swap16_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
-__device__ __forceinline__ float f8_swap32_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
 
 struct F8Regs { uint4 v[F8_IN_ITERS]; unsigned ok; };
 
@@ -168,7 +139,7 @@ __global__ __launch_bounds__(F8_THREADS) void conv_f8_kernel(ConvArgs a) {
         for (int d = 0; d < 4; ++d) {
             // plain f32 instructions (built with -fno-slp-vectorize): packed f32 is slower beside MFMAs, see conv_w4.hip
             constexpr float K = -1.4426950408889634f / kF8ActScale;
-            const float y0 = __builtin_fmaf(f8_lo(wds[d]), cA[2 * d], cB[2 * d]), y1 = __builtin_fmaf(f8_hi(wds[d]), cA[2 * d + 1], cB[2 * d + 1]);
+            const float y0 = __builtin_fmaf(bf16_lo(wds[d]), cA[2 * d], cB[2 * d]), y1 = __builtin_fmaf(bf16_hi(wds[d]), cA[2 * d + 1], cB[2 * d + 1]);
             const float e0 = __builtin_amdgcn_exp2f(y0 * K) + 1.0f, e1 = __builtin_amdgcn_exp2f(y1 * K) + 1.0f;
             const f32x2_t sv = {y0 * __builtin_amdgcn_rcpf(e0), y1 * __builtin_amdgcn_rcpf(e1)};
             const float f0 = __builtin_fminf(sv.x, 448.0f), f1 = __builtin_fminf(sv.y, 448.0f);
@@ -238,13 +209,13 @@ __global__ __launch_bounds__(F8_THREADS) void conv_f8_kernel(ConvArgs a) {
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
                 const f32x16_t& c = acc[m][j];
-                unsigned w[4] = {f8_pack(c[8 * pp + 0] * s0.x, c[8 * pp + 1] * s0.y), f8_pack(c[8 * pp + 2] * s0.z, c[8 * pp + 3] * s0.w),
-                                 f8_pack(c[8 * pp + 4] * s1.x, c[8 * pp + 5] * s1.y), f8_pack(c[8 * pp + 6] * s1.z, c[8 * pp + 7] * s1.w)};
+                unsigned w[4] = {pack_bf16(c[8 * pp + 0] * s0.x, c[8 * pp + 1] * s0.y), pack_bf16(c[8 * pp + 2] * s0.z, c[8 * pp + 3] * s0.w),
+                                 pack_bf16(c[8 * pp + 4] * s1.x, c[8 * pp + 5] * s1.y), pack_bf16(c[8 * pp + 6] * s1.z, c[8 * pp + 7] * s1.w)};
                 if constexpr (RESID) {
                     const uint4 rr = rv[g & 1][m];
                     const unsigned rw[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
-                    for (int d = 0; d < 4; ++d) w[d] = f8_pack(f8_lo(w[d]) + f8_lo(rw[d]), f8_hi(w[d]) + f8_hi(rw[d]));
+                    for (int d = 0; d < 4; ++d) w[d] = pack_bf16(bf16_lo(w[d]) + bf16_lo(rw[d]), bf16_hi(w[d]) + bf16_hi(rw[d]));
                 }
                 float s1v = 0.f, q1v = 0.f;
 #pragma unroll
@@ -264,17 +235,17 @@ __global__ __launch_bounds__(F8_THREADS) void conv_f8_kernel(ConvArgs a) {
 #pragma unroll
         for (int g = 0; g < F8_NTL * 2; ++g) { rv16[2 * g] = ssum[g >> 1][g & 1]; rv16[2 * g + 1] = qsum[g >> 1][g & 1]; }
 #pragma unroll
-        for (int i = 0; i < F8_NTL * 4; ++i) rv16[i] = f8_ror_add<1>(rv16[i]);
+        for (int i = 0; i < F8_NTL * 4; ++i) rv16[i] = ror_add<1>(rv16[i]);
 #pragma unroll
-        for (int i = 0; i < F8_NTL * 4; ++i) rv16[i] = f8_ror_add<2>(rv16[i]);
+        for (int i = 0; i < F8_NTL * 4; ++i) rv16[i] = ror_add<2>(rv16[i]);
 #pragma unroll
-        for (int i = 0; i < F8_NTL * 4; ++i) rv16[i] = f8_ror_add<4>(rv16[i]);
+        for (int i = 0; i < F8_NTL * 4; ++i) rv16[i] = ror_add<4>(rv16[i]);
 #pragma unroll
-        for (int i = 0; i < F8_NTL * 4; ++i) rv16[i] = f8_ror_add<8>(rv16[i]);
+        for (int i = 0; i < F8_NTL * 4; ++i) rv16[i] = ror_add<8>(rv16[i]);
 #pragma unroll
-        for (int i = 0; i < F8_NTL * 4; ++i) rv16[i] = f8_swap16_add(rv16[i]);
+        for (int i = 0; i < F8_NTL * 4; ++i) rv16[i] = swap16_add(rv16[i]);
 #pragma unroll
-        for (int i = 0; i < F8_NTL * 4; ++i) rv16[i] = f8_swap32_add(rv16[i]);
+        for (int i = 0; i < F8_NTL * 4; ++i) rv16[i] = swap32_add(rv16[i]);
         if (lane == 0) {
 #pragma unroll
             for (int g = 0; g < F8_NTL * 2; ++g) *reinterpret_cast<float2*>(red + (wave * 8 + g) * 2) = make_float2(rv16[2 * g], rv16[2 * g + 1]);
@@ -315,7 +286,7 @@ __global__ __launch_bounds__(F8_THREADS) void conv_f8_kernel(ConvArgs a) {
             for (int i = 0; i < F8_W_ITERS; ++i) {
                 int cbase = i * F8_THREADS + wave_u * 64;
                 if ((i + 1) * F8_THREADS > F8_W_CHUNKS) cbase = cbase >= F8_W_CHUNKS ? cbase - F8_W_CHUNKS : cbase;
-                f8_glds16(ws + (size_t)(cbase + lane) * 16, w_nxt_lds + cbase * 16);
+                glds16(ws + (size_t)(cbase + lane) * 16, w_nxt_lds + cbase * 16);
             }
         }
 #pragma unroll
@@ -408,8 +379,7 @@ __global__ __launch_bounds__(F8_THREADS) void conv_f8_kernel(ConvArgs a) {
 void conv_f8_launch(bool resid, const ConvArgs& a, hipStream_t stream) {
     if (a.cout % 128 || a.cout > 256 || a.nkc < 2 || (a.nkc & 1) || !a.ab || !a.oscale || !a.stats) fail(IRE_ERR_INTERNAL, "internal: conv_f8 arguments");
     const int items = a.tiles_x * a.tiles_y * a.nimg * a.nblocks;
-    const int cus = persistent_grid_cus();
-    const int grid = items < cus ? items : cus;
+    const int grid = persistent_grid(items);
     if (resid) hipLaunchKernelGGL(conv_f8_kernel<true>, dim3(grid), dim3(F8_THREADS), 0, stream, a);
     else hipLaunchKernelGGL(conv_f8_kernel<false>, dim3(grid), dim3(F8_THREADS), 0, stream, a);
     IRE_HIP(hipGetLastError());

@@ -22,34 +22,17 @@
 // Roofline: MFMA (2*9*Cin*Cout flop per output pixel) for C >= 128, HBM for C = 32/64
 // ((Cin+Cout)*2 B per pixel; DESIGN.md "kernels").
 #include "conv_mfma.hpp"
+#include "conv_prims.hpp"
 
 namespace ire {
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-
 constexpr int TW = 32;
 constexpr int NTHREADS = 256;
 
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
-    f32x2_t f = {a, b};
-    bf16x2_t v = __builtin_convertvector(f, bf16x2_t);
-    return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 __device__ __forceinline__ float bf16_round(float x) {  // value after a bf16 round trip
-    return bf16_lo(pack_bf16x2(x, 0.f));
-}
-
-__device__ __forceinline__ float silu_f(float y) {
-    // y * sigmoid(y); exp2/rcp hardware approximations (rel. err ~1e-6, far below bf16)
-    float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * y);
-    return y * __builtin_amdgcn_rcpf(1.0f + e);
+    return bf16_lo(pack_bf16(x, 0.f));
 }
 
 template <int KC8>
@@ -165,8 +148,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_mfma_kernel(ConvArgs a) {
                     if constexpr (PRO == PRO_U8) {
                         const unsigned char* pb = reinterpret_cast<const unsigned char*>(a.in0) + pix * 3;
                         // u8 -> bf16 is exact (integers <= 255); channels 3..7 are zero padding
-                        v[it].x = pack_bf16x2((float)pb[0], (float)pb[1]);
-                        v[it].y = pack_bf16x2((float)pb[2], 0.f);
+                        v[it].x = pack_bf16((float)pb[0], (float)pb[1]);
+                        v[it].y = pack_bf16((float)pb[2], 0.f);
                     } else {
                         v[it] = *reinterpret_cast<const uint4*>(src + pix * csrc + cbase + c8_fixed * 8);
                     }
@@ -184,7 +167,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_mfma_kernel(ConvArgs a) {
                             for (int d = 0; d < 4; ++d) {
                                 float y0 = __builtin_fmaf(bf16_lo(wds[d]), cA[2 * d], cB[2 * d]);
                                 float y1 = __builtin_fmaf(bf16_hi(wds[d]), cA[2 * d + 1], cB[2 * d + 1]);
-                                wds[d] = pack_bf16x2(silu_f(y0), silu_f(y1));
+                                wds[d] = pack_bf16(silu(y0), silu(y1));
                             }
                             o = make_uint4(wds[0], wds[1], wds[2], wds[3]);
                         }
@@ -260,7 +243,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_mfma_kernel(ConvArgs a) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     const int x = (i & 3) + 8 * (i >> 2) + 4 * h;
-                    const unsigned u = pack_bf16x2(acc[m][j][i] + bias, 0.f);
+                    const unsigned u = pack_bf16(acc[m][j][i] + bias, 0.f);
                     lds_o[((wave * MT + m) * TW + x) * NT + j * 32 + r] = (unsigned short)(u & 0xffffu);
                 }
         }
@@ -283,7 +266,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_mfma_kernel(ConvArgs a) {
                     const unsigned rw[4] = {rv.x, rv.y, rv.z, rv.w};
 #pragma unroll
                     for (int d = 0; d < 4; ++d)
-                        wds[d] = pack_bf16x2(bf16_lo(wds[d]) + bf16_lo(rw[d]), bf16_hi(wds[d]) + bf16_hi(rw[d]));
+                        wds[d] = pack_bf16(bf16_lo(wds[d]) + bf16_lo(rw[d]), bf16_hi(wds[d]) + bf16_hi(rw[d]));
                 }
                 if constexpr (STATS) {
 #pragma unroll

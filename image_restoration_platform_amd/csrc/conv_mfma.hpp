@@ -42,6 +42,9 @@ inline int persistent_grid_cus() {
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     return forced > 0 && forced < cus ? forced : cus;
 }
+// Grid of a persistent launch: one workgroup per work item, at most `slots` of them (the CUs, times the workgroups that share a CU
+// where a kernel runs more than one).
+inline int persistent_grid(int items, int slots = persistent_grid_cus()) { return items < slots ? items : slots; }
 
 // Bytes of one image's tensor (rows x cols pixels of px_bytes each): the record count of a buffer resource, and the range of the 32-bit
 // byte offsets into it.  Formed in unsigned arithmetic: the product passes 2^31 from 4096 x 8192 level-0 pixels (64 bytes each) upward and

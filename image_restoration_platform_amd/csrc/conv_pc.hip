@@ -17,6 +17,7 @@
 // row strips included.  Roofline: HBM for the residual variant (1.5 GB per launch), VALU issue otherwise.
 #include "conv_mfma.hpp"
 #include "conv_plan.hpp"
+#include "conv_prims.hpp"
 #include "gn_fold.hpp"
 #include "persist.hpp"
 
@@ -25,12 +26,6 @@
 namespace ire {
 
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 #ifndef C3_RES_PRE
 #define C3_RES_PRE -1     // residual groups requested before the MFMAs: -1 = per width (C = 32: 2, C = 64: 1); >= 0 forces one value (build-time A/B)
@@ -96,32 +91,6 @@ template <int C> struct PcCfg {
     static_assert(LDS <= 160 * 1024, "LDS");
 };
 
-__device__ __forceinline__ unsigned c3_pack(float a, float b) {
-    f32x2_t f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
-__device__ __forceinline__ float c3_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float c3_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-template <int N> __device__ __forceinline__ float c3_ror_add(float v) {
-    const int r = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false);
-    return v + __builtin_bit_cast(float, r);
-}
-__device__ __forceinline__ float c3_swap16_add(float v) {       // see conv_rb.hip::rb_swap16_add
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
-
-// The per-stage barrier, spelled out: only LDS traffic has to be ordered (the tile a producer just wrote, the partials a consumer
-// just wrote); global loads and stores stay in flight across it.  (hipcc's __syncthreads() is the same two instructions on
-// gfx950 -- its workgroup-scope fence waits for lgkmcnt only -- measured equal; the asm form states the requirement.)
-__device__ __forceinline__ void c3_glds16(const void* gsrc, unsigned lds_dst_uniform) {   // LDS-DMA, 1 KB per wave-instruction (conv_rb.hip)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
-__device__ __forceinline__ void c3_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 template <int C, bool RESID, bool HEAD>
 __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(ConvArgs a) {
     using K = PcCfg<C>;
@@ -170,7 +139,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
         constexpr int PIECES = NKC * K::W_STAGE_CHUNKS / 64;                 // 1-KB pieces: 18 (C = 32), 72 (C = 64)
         static_assert((NKC * K::W_STAGE_CHUNKS) % 64 == 0, "whole wave-instructions");
         const int wv = __builtin_amdgcn_readfirstlane(wave);
-        for (int p = wv; p < PIECES; p += THREADS / 64) c3_glds16(ws + ((size_t)p * 64 + lane) * 16, wl + p * 1024);
+        for (int p = wv; p < PIECES; p += THREADS / 64) glds16(ws + ((size_t)p * 64 + lane) * 16, wl + p * 1024);
     }
     // the folded GroupNorm finalize writes this workgroup's coefficient table straight into LDS (and to global memory for nobody's benefit here)
     if (a.gn_stats) gn_fold(a, smem, cursor.first_img, cursor.last_img, 512, reinterpret_cast<float2*>(smem + K::COEF_OFF));
@@ -266,8 +235,8 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
 #pragma unroll
                     for (int w = 0; w < NW; ++w) {
                         const int d = w & 3;
-                        y[2 * w] = __builtin_fmaf(c3_lo(wds[w]), cA[2 * d], cB[2 * d]);
-                        y[2 * w + 1] = __builtin_fmaf(c3_hi(wds[w]), cA[2 * d + 1], cB[2 * d + 1]);
+                        y[2 * w] = __builtin_fmaf(bf16_lo(wds[w]), cA[2 * d], cB[2 * d]);
+                        y[2 * w + 1] = __builtin_fmaf(bf16_hi(wds[w]), cA[2 * d + 1], cB[2 * d + 1]);
                     }
 #pragma unroll
                     for (int k = 0; k < NV; ++k) e[k] = y[k] * (-1.4426950408889634f);
@@ -282,7 +251,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                     for (int k = 0; k < NV; ++k) e[k] = __builtin_amdgcn_rcpf(e[k]);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int w = 0; w < NW; ++w) o[w] = c3_pack(y[2 * w] * e[2 * w], y[2 * w + 1] * e[2 * w + 1]);
+                    for (int w = 0; w < NW; ++w) o[w] = pack_bf16(y[2 * w] * e[2 * w], y[2 * w + 1] * e[2 * w + 1]);
 #else
                     static_assert(NCH == 2, "the packed-f32 form handles whole pairs");
                     f32x2_t y[8], e[8];
@@ -290,7 +259,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                     for (int w = 0; w < 8; ++w) {
                         // two channels at a time in packed f32: y = x A + B; silu(y) = y / (1 + 2^(-y log2 e))
                         const int d = w & 3;
-                        const f32x2_t x = {c3_lo(wds[w]), c3_hi(wds[w])};
+                        const f32x2_t x = {bf16_lo(wds[w]), bf16_hi(wds[w])};
                         const f32x2_t A = {cA[2 * d], cA[2 * d + 1]}, B = {cB[2 * d], cB[2 * d + 1]};
                         y[w] = __builtin_elementwise_fma(x, A, B);
                         e[w] = y[w] * (-1.4426950408889634f);
@@ -306,7 +275,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                     for (int w = 0; w < 8; ++w) e[w] = f32x2_t{__builtin_amdgcn_rcpf(e[w].x), __builtin_amdgcn_rcpf(e[w].y)};
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int w = 0; w < 8; ++w) { const f32x2_t sv = y[w] * e[w]; o[w] = c3_pack(sv.x, sv.y); }
+                    for (int w = 0; w < 8; ++w) { const f32x2_t sv = y[w] * e[w]; o[w] = pack_bf16(sv.x, sv.y); }
 #endif
                 }
 #pragma unroll
@@ -344,7 +313,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
         load_coeffs(ls);
         ls = cursor.next();
         transform_stage(smem);
-        c3_barrier();                                           // tile (and slab) of stage 0 are staged
+        lds_barrier();                                           // tile (and slab) of stage 0 are staged
         for (int t = 0; t < n_stages; ++t) {
             // tile / slab of stage t + 1 (for t + 1 == n_stages: the last stage again, into the slots nobody reads any more)
             stamp_item = t / NKC;
@@ -353,7 +322,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
             ls = cursor.next();
             transform_stage(smem + ((t + 1) & 1) * C3_IN_BYTES);   // the consumers finished reading this slot before the last barrier
             stamp(3 * (t % NKC) + 1);
-            c3_barrier();
+            lds_barrier();
             stamp(3 * (t % NKC) + 2);
         }
         return;
@@ -436,7 +405,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
     bool hok[2] = {false, false};
     PersistStage cs = cursor.cur;
     int stage_no = 0;
-    c3_barrier();                                               // tile of stage 0 is staged
+    lds_barrier();                                               // tile of stage 0 is staged
     for (int t = 0; t < n_items; ++t) {
         const PersistItem it = cs.it;
         stamp_item = t;
@@ -565,7 +534,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
             else stage_body(std::integral_constant<int, -1>{});
             ++stage_no;
             stamp(kc == 0 ? 1 : 3);
-            if (kc + 1 < NKC) { cs = cursor.next(); c3_barrier(); stamp(2); }      // the item's next stage: its tile is staged, this one is free
+            if (kc + 1 < NKC) { cs = cursor.next(); lds_barrier(); stamp(2); }      // the item's next stage: its tile is staged, this one is free
         }
         if constexpr (RESID && TEPI64 && RES_PRE < 2 * NTL) {
             char* rbase = const_cast<char*>(reinterpret_cast<const char*>(a.resid)) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
@@ -642,8 +611,8 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                 for (int g = 0; g < 2 * NTL; ++g) {
                     const f32x16_t& c = acc[m][g >> 1];
                     const int pp = g & 1;
-                    const u32x4_t wv = {c3_pack(c[8 * pp + 0], c[8 * pp + 1]), c3_pack(c[8 * pp + 2], c[8 * pp + 3]),
-                                        c3_pack(c[8 * pp + 4], c[8 * pp + 5]), c3_pack(c[8 * pp + 6], c[8 * pp + 7])};
+                    const u32x4_t wv = {pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
+                                        pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
                     *reinterpret_cast<u32x4_t*>(patch + r * 128 + (((2 * g + h) ^ wsw) << 4)) = wv;
                 }
 #pragma unroll
@@ -655,7 +624,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                         const uint4 rr = erv[k][m];
                         const unsigned rw[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
-                        for (int d = 0; d < 4; ++d) w[d] = c3_pack(c3_lo(w[d]) + c3_lo(rw[d]), c3_hi(w[d]) + c3_hi(rw[d]));
+                        for (int d = 0; d < 4; ++d) w[d] = pack_bf16(bf16_lo(w[d]) + bf16_lo(rw[d]), bf16_hi(w[d]) + bf16_hi(rw[d]));
                     }
                     const bool ok = trow[m] && tcol + 8 * k < a.Wout;
                     const float mf = ok ? 1.f : 0.f;
@@ -676,11 +645,11 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                 // the eight lanes that share a chunk sit 8 apart: one rotation within the row of 16, then the rows
                 float t2[2] = {sA, qA};
 #pragma unroll
-                for (int k = 0; k < 2; ++k) t2[k] = c3_ror_add<8>(t2[k]);
+                for (int k = 0; k < 2; ++k) t2[k] = ror_add<8>(t2[k]);
 #pragma unroll
-                for (int k = 0; k < 2; ++k) t2[k] = c3_swap16_add(t2[k]);
+                for (int k = 0; k < 2; ++k) t2[k] = swap16_add(t2[k]);
 #pragma unroll
-                for (int k = 0; k < 2; ++k) { float x = t2[k], y = t2[k]; asm volatile("v_nop\n\tv_nop\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y)); t2[k] = x + y; }
+                for (int k = 0; k < 2; ++k) t2[k] = swap32_add(t2[k]);
                 if (lane < 8) *reinterpret_cast<float4*>(redw + (wave * NCC + lane) * 4) = make_float4(t2[0], t2[1], 0.f, 0.f);
             }
             st_img = it.img; st_tile = it.tile; st_nb = it.nb; st_par = red_par; red_par ^= 1;
@@ -698,8 +667,8 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                 const f32x16_t& c = acc[m][0];
 #pragma unroll
                 for (int pp = 0; pp < 2; ++pp) {
-                    const u32x4_t wv = {c3_pack(c[8 * pp + 0], c[8 * pp + 1]), c3_pack(c[8 * pp + 2], c[8 * pp + 3]),
-                                        c3_pack(c[8 * pp + 4], c[8 * pp + 5]), c3_pack(c[8 * pp + 6], c[8 * pp + 7])};
+                    const u32x4_t wv = {pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
+                                        pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
                     *reinterpret_cast<u32x4_t*>(patch + r * 64 + (((2 * pp + h) ^ wsw) << 4)) = wv;
                 }
 #pragma unroll
@@ -711,7 +680,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                         const uint4 rr = erv[k][m];
                         const unsigned rw[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
-                        for (int d = 0; d < 4; ++d) w[d] = c3_pack(c3_lo(w[d]) + c3_lo(rw[d]), c3_hi(w[d]) + c3_hi(rw[d]));
+                        for (int d = 0; d < 4; ++d) w[d] = pack_bf16(bf16_lo(w[d]) + bf16_lo(rw[d]), bf16_hi(w[d]) + bf16_hi(rw[d]));
                     }
                     const bool ok = trow[m] && tcol + 16 * k < a.Wout;
                     const float mf = ok ? 1.f : 0.f;
@@ -734,13 +703,13 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                 // the sixteen lanes that share a chunk sit 4 apart: two rotations within the row of 16, then the rows
                 float t4[4] = {sA, qA, sB, qB};
 #pragma unroll
-                for (int k = 0; k < 4; ++k) t4[k] = c3_ror_add<4>(t4[k]);
+                for (int k = 0; k < 4; ++k) t4[k] = ror_add<4>(t4[k]);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) t4[k] = c3_ror_add<8>(t4[k]);
+                for (int k = 0; k < 4; ++k) t4[k] = ror_add<8>(t4[k]);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) t4[k] = c3_swap16_add(t4[k]);
+                for (int k = 0; k < 4; ++k) t4[k] = swap16_add(t4[k]);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) { float x = t4[k], y = t4[k]; asm volatile("v_nop\n\tv_nop\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y)); t4[k] = x + y; }
+                for (int k = 0; k < 4; ++k) t4[k] = swap32_add(t4[k]);
                 if (lane < 4) *reinterpret_cast<float4*>(redw + (wave * NCC + lane) * 4) = make_float4(t4[0], t4[1], t4[2], t4[3]);
             }
             st_img = it.img; st_tile = it.tile; st_nb = it.nb; st_par = red_par; red_par ^= 1;
@@ -763,13 +732,13 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
                     const f32x16_t& c = acc[m][j];
-                    unsigned w[4] = {c3_pack(c[8 * pp + 0], c[8 * pp + 1]), c3_pack(c[8 * pp + 2], c[8 * pp + 3]),
-                                     c3_pack(c[8 * pp + 4], c[8 * pp + 5]), c3_pack(c[8 * pp + 6], c[8 * pp + 7])};
+                    unsigned w[4] = {pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
+                                     pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
                     if constexpr (RESID) {
                         const uint4 rr = erv[g][m];
                         const unsigned rw[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
-                        for (int d = 0; d < 4; ++d) w[d] = c3_pack(c3_lo(w[d]) + c3_lo(rw[d]), c3_hi(w[d]) + c3_hi(rw[d]));
+                        for (int d = 0; d < 4; ++d) w[d] = pack_bf16(bf16_lo(w[d]) + bf16_lo(rw[d]), bf16_hi(w[d]) + bf16_hi(rw[d]));
                     }
                     float ts0 = 0.f, tq0 = 0.f, ts1 = 0.f, tq1 = 0.f;
                     if constexpr (!(C3_ABL & 32))
@@ -803,9 +772,9 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                 for (int k = 0; k < 4; ++k) u[k] = xch(b0 ? vq[k] : vs[k], b0 ? vs[k] : vq[k], std::integral_constant<int, 0xb1>{});     // quad_perm [1,0,3,2]: lane ^ 1
 #pragma unroll
                 for (int k = 0; k < 2; ++k) t2[k] = xch(b1 ? u[2 + k] : u[k], b1 ? u[k] : u[2 + k], std::integral_constant<int, 0x4e>{});   // quad_perm [2,3,0,1]: lane ^ 2
-                t2[0] = c3_ror_add<4>(t2[0]); t2[1] = c3_ror_add<4>(t2[1]);
-                t2[0] = c3_ror_add<8>(t2[0]); t2[1] = c3_ror_add<8>(t2[1]);
-                t2[0] = c3_swap16_add(t2[0]); t2[1] = c3_swap16_add(t2[1]);
+                t2[0] = ror_add<4>(t2[0]); t2[1] = ror_add<4>(t2[1]);
+                t2[0] = ror_add<8>(t2[0]); t2[1] = ror_add<8>(t2[1]);
+                t2[0] = swap16_add(t2[0]); t2[1] = swap16_add(t2[1]);
                 if ((lane & 28) == 0) {
                     if constexpr (C == 32) {      // values 2 b1 + e = (chunk pp = b1, half-chunk e): red[wave][cc = 2 pp + h][2 e + kind]
                         float* d = redw + (wave * NCC + (b1 ? 2 : 0) + h) * 4 + (b0 ? 1 : 0);
@@ -821,7 +790,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
         }
         stamp(NKC == 1 ? 3 : 4);
         cs = cursor.next();
-        c3_barrier();
+        lds_barrier();
         stamp(5);
         tl(3 + (t < 8 ? t : 8));
     }
@@ -844,7 +813,7 @@ void conv_pc_launch(bool resid, bool head, const ConvArgs& a, hipStream_t stream
     const int items = a.tiles_x * a.tiles_y * a.nimg * a.nblocks;
     const int cus = persistent_grid_cus();
     if (!coef_table_fits(pc_coef_imgs(C), (long long)a.tiles_x * a.tiles_y, a.nimg, cus)) fail(IRE_ERR_INTERNAL, "internal: conv_pc batch");
-    const int grid = items < cus ? items : cus;
+    const int grid = persistent_grid(items, cus);
 #define PC_GO(CC, RS, HD) hipLaunchKernelGGL((conv_pc_kernel<CC, RS, HD>), dim3(grid), dim3(C3_CONS + pc_prod(CC, HD)), 0, stream, a)
     if (head) PC_GO(32, false, true);
     else if (C == 32) { if (resid) PC_GO(32, true, false); else PC_GO(32, false, false); }

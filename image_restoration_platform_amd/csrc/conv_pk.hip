@@ -30,6 +30,7 @@
 // Roofline: MFMA.  `2*9*C*C` flop per output pixel, `4C` B (+ `2C` residual).
 #include "conv_mfma.hpp"
 #include "conv_plan.hpp"
+#include "conv_prims.hpp"
 #include "gn_fold.hpp"
 #include "persist.hpp"
 
@@ -38,12 +39,6 @@
 namespace ire {
 
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 #ifndef PK_PRIO
 #define PK_PRIO 1    // s_setprio of the producer waves (they are the youngest waves of their SIMD: at 0 they issue in the consumers' leftover slots)
@@ -103,39 +98,13 @@ template <int C> struct PkCfg {
 };
 static_assert((PK_PLANE / 4) % 32 == 16 && PK_W_CHUNKS == 9 * PK_PROD, "layout");
 
-__device__ __forceinline__ unsigned pk_pack(float a, float b) {
-    f32x2_t f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
-__device__ __forceinline__ float pk_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float pk_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-__device__ __forceinline__ void pk_glds16(const void* gsrc, unsigned lds_dst_uniform) {   // LDS-DMA, 1 KB per wave-instruction (conv_rb.hip)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
-// one dword per lane into a 256-B LDS sink: a load whose only purpose is to pull its 128-B line into the XCD's L2 (no register waits for it)
+// one dword per lane into a 256-B LDS sink: a load whose only purpose is to pull its 128-B line into the XCD's L2 (no register waits for it);
+// M0 as in conv_prims.hpp::glds16
 __device__ __forceinline__ void pk_touch(const void* gsrc, unsigned lds_sink_uniform) {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_sink_uniform) : "memory");
 }
-template <int N> __device__ __forceinline__ float pk_ror_add(float v) {
-    const int r = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false);
-    return v + __builtin_bit_cast(float, r);
-}
-__device__ __forceinline__ float pk_swap16_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
-__device__ __forceinline__ float pk_swap32_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
-// only LDS traffic is ordered by the stage barrier; global loads, stores and LDS-DMA stay in flight across it
-__device__ __forceinline__ void pk_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <int C, bool RESID>
 __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
@@ -229,7 +198,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
 #pragma unroll
         for (int d = d0; d < d1; ++d) {
             const int cbase = d * PK_PROD + wave_p * 64;
-            pk_glds16(ws + (size_t)(cbase + lane) * 16, dst + cbase * 16);
+            glds16(ws + (size_t)(cbase + lane) * 16, dst + cbase * 16);
         }
     };
     PersistStage q1 = cursor.cur, q2 = q1, q3 = q1;         // producers: the next stages to transform (q1) .. to request (q3)
@@ -297,8 +266,8 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
 #pragma unroll
                 for (int w = 0; w < NW; ++w) {
                     const int d = w & 3;
-                    y[2 * w] = __builtin_fmaf(pk_lo(wds[w]), cA[2 * d], cB[2 * d]);
-                    y[2 * w + 1] = __builtin_fmaf(pk_hi(wds[w]), cA[2 * d + 1], cB[2 * d + 1]);
+                    y[2 * w] = __builtin_fmaf(bf16_lo(wds[w]), cA[2 * d], cB[2 * d]);
+                    y[2 * w + 1] = __builtin_fmaf(bf16_hi(wds[w]), cA[2 * d + 1], cB[2 * d + 1]);
                 }
 #pragma unroll
                 for (int k = 0; k < NV; ++k) e[k] = y[k] * (-1.4426950408889634f);
@@ -313,7 +282,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
                 for (int k = 0; k < NV; ++k) e[k] = __builtin_amdgcn_rcpf(e[k]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int w = 0; w < NW; ++w) o[w] = pk_pack(y[2 * w] * e[2 * w], y[2 * w + 1] * e[2 * w + 1]);
+                for (int w = 0; w < NW; ++w) o[w] = pack_bf16(y[2 * w] * e[2 * w], y[2 * w + 1] * e[2 * w + 1]);
             }
 #pragma unroll
             for (int k = 0; k < NCH; ++k) {
@@ -358,7 +327,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (the slab of stage 0 among them)
         produce(RA, rokA, q1, smem, PK_DBUF ? q3 : q2, -1);
         q1 = q2; q2 = q3; q3 = cursor.next();
-        pk_barrier();                                              // tile 0 and slab 0 are staged
+        lds_barrier();                                              // tile 0 and slab 0 are staged
         // the consumers run stage t; this is stage t + 1 (for t + 1 == S: the last stage again, into slots nobody reads any more): set
         // (t + 1) & 1 -> tile (t + 1) & 1, the set then takes stage t + 3.  S is even (NKC is): the loop runs stage pairs.
         auto body = [&](int t, u32x4_t (&R)[PK_P_ITERS], unsigned& rok, int slot) __attribute__((always_inline)) {
@@ -386,7 +355,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
             if (!PK_CDMA) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PK_DMA_SPLIT ? 3 : PK_P_ITERS) : "memory");
             if (wv == 8) stamp(1, t, 3);
             wstamp(t, 0);
-            pk_barrier();
+            lds_barrier();
             wstamp(t, 1);
         };
         for (int t = 0; t < S; t += 2) {
@@ -442,10 +411,10 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
 #pragma unroll
         for (int d = 0; d < 5; ++d) {
             const int piece = cw + 8 * d;
-            if (piece < PK_W_CHUNKS / 64) pk_glds16(ws + (size_t)(piece * 64 + ln) * 16, dst + piece * 1024);
+            if (piece < PK_W_CHUNKS / 64) glds16(ws + (size_t)(piece * 64 + ln) * 16, dst + piece * 1024);
         }
     };
-    pk_barrier();                                                  // tile 0 and slab 0 are staged
+    lds_barrier();                                                  // tile 0 and slab 0 are staged
     tl(2);
     for (int t = 0; t < n_items; ++t) {
         const PersistItem it = cs.it;
@@ -478,7 +447,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {                                                    // read-back k: pixels 4 k + (lane >> 4), this lane's 8-cout chunk
                         const int ox = min(it.tx * PK_TW + 4 * k + (l_e >> 4), a.Wout - 1);         // (a column past the image: any valid address, the value is never used)
-                        pk_glds16(rbase + ((size_t)oy * a.Wout + ox) * (2 * C), smem_lds + PK_PATCH_BASE + cw * PK_PATCH_BYTES + k * 1024);
+                        glds16(rbase + ((size_t)oy * a.Wout + ox) * (2 * C), smem_lds + PK_PATCH_BASE + cw * PK_PATCH_BYTES + k * 1024);
                     }
                 }
             }
@@ -524,7 +493,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
             if (PK_CDMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's slab pieces (issued a whole k-loop ago) are in LDS
             if (cw == 0) stamp(0, stage_no, 1);
             ++stage_no;
-            if (kc + 1 < NKC) { cs = cn; cn = cursor.next(); wstamp(stage_no - 1, 0); pk_barrier(); wstamp(stage_no - 1, 1); }     // the item's next stage: its tile and slab are staged, these are free
+            if (kc + 1 < NKC) { cs = cn; cn = cursor.next(); wstamp(stage_no - 1, 0); lds_barrier(); wstamp(stage_no - 1, 1); }     // the item's next stage: its tile and slab are staged, these are free
         }
         // ---- epilogue: conv_w4's line-coalesced form -- a wave transposes 16 pixels x 128 couts at a time through its own 4-KB patch
         // (XOR-swizzled: conflict-free both ways) and reads / writes global memory in whole 256-B pixel runs, 1 KB per instruction
@@ -583,8 +552,8 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
                 for (int g = 0; g < NTL * 2; ++g) {
                     const f32x16_t& c = acc[m][g >> 1];
                     const int pp = g & 1;
-                    pkd[m][g] = u32x4_t{pk_pack(c[8 * pp + 0], c[8 * pp + 1]), pk_pack(c[8 * pp + 2], c[8 * pp + 3]),
-                                        pk_pack(c[8 * pp + 4], c[8 * pp + 5]), pk_pack(c[8 * pp + 6], c[8 * pp + 7])};
+                    pkd[m][g] = u32x4_t{pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
+                                        pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
                     asm volatile("" : "+v"(pkd[m][g]));                       // (packed HERE: left alone, hipcc sinks row 1's packing to
                 }                                                             //  pass 2 and keeps its 64 f32 accumulators live until then)
             __builtin_amdgcn_sched_barrier(0);
@@ -628,7 +597,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
                             const uint4 rr = rv[2 * m + q][k];
                             const unsigned rw[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
-                            for (int d = 0; d < 4; ++d) w[d] = pk_pack(pk_lo(w[d]) + pk_lo(rw[d]), pk_hi(w[d]) + pk_hi(rw[d]));
+                            for (int d = 0; d < 4; ++d) w[d] = pack_bf16(bf16_lo(w[d]) + bf16_lo(rw[d]), bf16_hi(w[d]) + bf16_hi(rw[d]));
                         }
                         float s1 = 0.f, q1 = 0.f;
 #pragma unroll
@@ -647,15 +616,15 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
                     if constexpr (RESID) { if (m == 0 && q == 0) load_resid_pass(3, rv[3]); }
                 }
             // this lane's chunk cc_r over its read-backs; the other lanes with the same chunk sit 16 apart
-            ssum = pk_swap16_add(ssum); qsum = pk_swap16_add(qsum);
-            ssum = pk_swap32_add(ssum); qsum = pk_swap32_add(qsum);
+            ssum = swap16_add(ssum); qsum = swap16_add(qsum);
+            ssum = swap32_add(ssum); qsum = swap32_add(qsum);
             if (l_e < 16) *reinterpret_cast<float2*>(red + red_par * (8 * 32) + (cw * 16 + cc_r) * 2) = make_float2(ssum, qsum);
             st_img = it.img; st_tile = it.tile; st_cout0 = cout0; st_par = red_par; red_par ^= 1;
         }
         if (cw == 0) stamp(0, stage_no - 1, 2);          // epilogue done
         cs = cn; cn = cursor.next();
         wstamp(stage_no - 1, 0);
-        pk_barrier();                          // stage barrier: the next item's first tile and slab are staged; every wave's chunk sums are in LDS
+        lds_barrier();                          // stage barrier: the next item's first tile and slab are staged; every wave's chunk sums are in LDS
         wstamp(stage_no - 1, 1);
         flush_stats();
         tl(3 + (t < 8 ? t : 8));
@@ -675,7 +644,7 @@ void conv_pk_launch(bool resid, const ConvArgs& a, hipStream_t stream) {
     const int cus = persistent_grid_cus();
     // every workgroup's items must stay within PK_IMGS images, the producers' coefficient table (plan_conv sends the rest to conv_w4)
     if (!coef_table_fits(PK_IMGS, (long long)a.tiles_x * a.tiles_y * a.nblocks, a.nimg, cus)) fail(IRE_ERR_INTERNAL, "internal: conv_pk batch");
-    const int grid = items < cus ? items : cus;
+    const int grid = persistent_grid(items, cus);
 #define PK_GO(CC, RS) hipLaunchKernelGGL((conv_pk_kernel<CC, RS>), dim3(grid), dim3(PK_THREADS), 0, stream, a)
     if (C == 128) { if (resid) PK_GO(128, true); else PK_GO(128, false); }
     else { if (resid) PK_GO(256, true); else PK_GO(256, false); }

@@ -16,6 +16,7 @@
 //   * C = 32: the whole 18 KB weight set stays resident in LDS for the life of the workgroup.
 // Roofline: MFMA for C >= 128 (2*9*C*C flop per pixel), HBM for C = 32/64 (4C..6C B per pixel).
 #include "conv_mfma.hpp"
+#include "conv_prims.hpp"
 #include "persist.hpp"
 #include "gn_fold.hpp"
 
@@ -25,12 +26,6 @@ namespace ire {
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
 constexpr int RB_TH = kRbTileH, RB_TW = 32;          // 16 (8 waves x 2 rows); IRE_RB_TH=8: 4 waves x 2 rows
 constexpr int RB_WAVES = RB_TH / 2;
 constexpr int RB_THREADS = RB_WAVES * 64;
@@ -39,51 +34,6 @@ constexpr int RB_IN_CHUNKS = RB_IH * RB_IW * 4;                                /
 constexpr int RB_IN_ITERS = (RB_IN_CHUNKS + RB_THREADS - 1) / RB_THREADS;       // 5
 constexpr int RB_IN_BYTES = RB_IN_ITERS * RB_THREADS * 16;                     // 40960: padded so all 5x512 chunk slots exist
 constexpr int RB_NSTEPS = 18;
-
-__device__ __forceinline__ unsigned rb_pack(float a, float b) {
-    f32x2_t f = {a, b};
-    bf16x2_t v = __builtin_convertvector(f, bf16x2_t);
-    return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float rb_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float rb_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-__device__ __forceinline__ float rb_silu(float y) {
-    float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * y);
-    return y * __builtin_amdgcn_rcpf(1.0f + e);
-}
-
-// LDS-DMA, 16 B per lane: LDS destination = wave-uniform byte address (through M0) + lane*16; the source is
-// per lane.  Not visible to the compiler's s_waitcnt bookkeeping: the caller waits (vmcnt) and barriers.
-__device__ __forceinline__ void rb_glds16(const void* gsrc, unsigned lds_dst_uniform) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
-
-// Sum over the lanes that share (lane % NCC), NCC in {4, 8}: row rotations (DPP) inside the 16-lane rows, then
-// the two permlane swaps across rows / wave halves.  Every lane ends with the total; fixed order => deterministic.
-// The swaps are inline asm on purpose: with the builtins hipcc (ROCm 7.2) folds the two results into one register
-// when both inputs are the same value (verified in the ISA); the two v_nop are the VALU-write -> permlane wait states.
-template <int N> __device__ __forceinline__ float rb_ror_add(float v) {
-    const int r = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false);
-    return v + __builtin_bit_cast(float, r);
-}
-__device__ __forceinline__ float rb_swap16_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
-__device__ __forceinline__ float rb_swap32_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
-template <int NCC> __device__ __forceinline__ float rb_group_sum(float v) {
-    if constexpr (NCC == 4) v = rb_ror_add<4>(v);
-    v = rb_ror_add<8>(v);
-    v = rb_swap16_add(v);
-    return rb_swap32_add(v);
-}
 
 using RbItem = PersistItem;   // img, ty, tx, nb, tile = ty*tiles_x + tx
 
@@ -239,7 +189,7 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
     auto transform_word = [&](unsigned w, int d, const float (&cA)[8], const float (&cB)[8]) -> unsigned {
         if constexpr (FUSED_ACT) {
             // two channels at a time in packed f32 (v_pk_fma/mul/add_f32): y = x*A + B ; silu(y) = y / (1 + 2^(-y log2 e))
-            const f32x2_t x = {rb_lo(w), rb_hi(w)};
+            const f32x2_t x = {bf16_lo(w), bf16_hi(w)};
             const f32x2_t A = {cA[2 * d], cA[2 * d + 1]}, B = {cB[2 * d], cB[2 * d + 1]};
             const f32x2_t y = __builtin_elementwise_fma(x, A, B);
             const f32x2_t t = y * (-1.4426950408889634f);
@@ -249,7 +199,7 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
             // (an inline-asm v_pk_mul_f32 here reads the v_rcp_f32 results before they are architecturally visible: hipcc pads
             // transcendental -> VALU dependencies for its own instructions only)
             const f32x2_t sv = y * rinv;
-            return rb_pack(sv.x, sv.y);
+            return pack_bf16(sv.x, sv.y);
         } else {
             return w;                                  // the input carries no GroupNorm (the `up` / `down` inputs of this family)
         }
@@ -413,14 +363,14 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
                 const f32x16_t& c = acc[m][j];
                 unsigned x0, x1, y0, y1;
                 // the bias is already in the accumulators (they start at it)
-                x0 = rb_pack(c[8 * pp + 0], c[8 * pp + 1]); x1 = rb_pack(c[8 * pp + 2], c[8 * pp + 3]);
-                y0 = rb_pack(c[8 * pp + 4], c[8 * pp + 5]); y1 = rb_pack(c[8 * pp + 6], c[8 * pp + 7]);
+                x0 = pack_bf16(c[8 * pp + 0], c[8 * pp + 1]); x1 = pack_bf16(c[8 * pp + 2], c[8 * pp + 3]);
+                y0 = pack_bf16(c[8 * pp + 4], c[8 * pp + 5]); y1 = pack_bf16(c[8 * pp + 6], c[8 * pp + 7]);
                 unsigned w[4] = {x0, x1, y0, y1};
                 if constexpr (RESID && !(DBG & 4)) {
                     const uint4 rr = erv[g][m];
                     const unsigned rw[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
-                    for (int d = 0; d < 4; ++d) w[d] = rb_pack(rb_lo(w[d]) + rb_lo(rw[d]), rb_hi(w[d]) + rb_hi(rw[d]));
+                    for (int d = 0; d < 4; ++d) w[d] = pack_bf16(bf16_lo(w[d]) + bf16_lo(rw[d]), bf16_hi(w[d]) + bf16_hi(rw[d]));
                 }
                 float ts0 = 0.f, tq0 = 0.f, ts1 = 0.f, tq1 = 0.f;
 #pragma unroll
@@ -444,17 +394,17 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
                 // instructions earlier and needs no s_nop padding (a chain reduced on its own gets one per step)
                 if constexpr (NT >= 64) {      // cout >= 64 => groups of >= 8 channels: a chunk never splits into two groups
                     sA += sB; qA += qB; sB = 0.f; qB = 0.f;
-                    sA = rb_ror_add<1>(sA); qA = rb_ror_add<1>(qA);
-                    sA = rb_ror_add<2>(sA); qA = rb_ror_add<2>(qA);
-                    sA = rb_ror_add<4>(sA); qA = rb_ror_add<4>(qA);
-                    sA = rb_ror_add<8>(sA); qA = rb_ror_add<8>(qA);
-                    sA = rb_swap16_add(sA); qA = rb_swap16_add(qA);
+                    sA = ror_add<1>(sA); qA = ror_add<1>(qA);
+                    sA = ror_add<2>(sA); qA = ror_add<2>(qA);
+                    sA = ror_add<4>(sA); qA = ror_add<4>(qA);
+                    sA = ror_add<8>(sA); qA = ror_add<8>(qA);
+                    sA = swap16_add(sA); qA = swap16_add(qA);
                 } else {
-                    sA = rb_ror_add<1>(sA); qA = rb_ror_add<1>(qA); sB = rb_ror_add<1>(sB); qB = rb_ror_add<1>(qB);
-                    sA = rb_ror_add<2>(sA); qA = rb_ror_add<2>(qA); sB = rb_ror_add<2>(sB); qB = rb_ror_add<2>(qB);
-                    sA = rb_ror_add<4>(sA); qA = rb_ror_add<4>(qA); sB = rb_ror_add<4>(sB); qB = rb_ror_add<4>(qB);
-                    sA = rb_ror_add<8>(sA); qA = rb_ror_add<8>(qA); sB = rb_ror_add<8>(sB); qB = rb_ror_add<8>(qB);
-                    sA = rb_swap16_add(sA); qA = rb_swap16_add(qA); sB = rb_swap16_add(sB); qB = rb_swap16_add(qB);
+                    sA = ror_add<1>(sA); qA = ror_add<1>(qA); sB = ror_add<1>(sB); qB = ror_add<1>(qB);
+                    sA = ror_add<2>(sA); qA = ror_add<2>(qA); sB = ror_add<2>(sB); qB = ror_add<2>(qB);
+                    sA = ror_add<4>(sA); qA = ror_add<4>(qA); sB = ror_add<4>(sB); qB = ror_add<4>(qB);
+                    sA = ror_add<8>(sA); qA = ror_add<8>(qA); sB = ror_add<8>(sB); qB = ror_add<8>(qB);
+                    sA = swap16_add(sA); qA = swap16_add(qA); sB = swap16_add(sB); qB = swap16_add(qB);
                 }
                 if ((lane & 31) == 0) {
                     float* d = redw + (wave * NCC + j * 4 + 2 * pp + h_e) * 4;
@@ -563,7 +513,7 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
                 if ((st & 3) == 3) store_words(st >> 2, Rn, tw, in_nxt);
             }
             if constexpr (!WRES) {
-                // (2) weight slab of stage s+1 by LDS-DMA (global_load_lds_dwordx4: 16 B per lane, no registers), a
+                // (2) weight slab of stage s+1 by LDS-DMA (glds16: 16 B per lane, no registers), a
                 // pure copy into the OTHER buffer, 17 k-steps ahead of the end-of-stage wait + barrier that publish
                 // it.  Inline asm on purpose: with the builtin hipcc orders every later ds_write after the DMA with
                 // a vmcnt(0) (same LDS array => may alias), which would also drain the s+2 input prefetch.
@@ -575,7 +525,7 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
                     for (int i = 0; i < C::W_ITERS; ++i) {
                         const int cbase = i * RB_THREADS + wave_u * 64;          // first chunk of this wave-instruction
                         if (cbase < C::W_CHUNKS)                                 // wave-uniform
-                            rb_glds16(ws + (size_t)(cbase + lane) * 16, w_nxt_lds + cbase * 16);
+                            glds16(ws + (size_t)(cbase + lane) * 16, w_nxt_lds + cbase * 16);
                     }
                 }
             }
@@ -658,7 +608,7 @@ void launch_rb(const ConvArgs& a, hipStream_t stream) {
     const int cus = persistent_grid_cus();
     // one workgroup per CU; with 8-row tiles (256 threads) two independent workgroups per CU where their LDS fits
     const int per_cu = (RB_TH == 8 && RbCfg<NT, RESID, WRES, FUSED_ACT>::LDS_BYTES <= 80 * 1024) ? 2 : 1;
-    const int grid = items < cus * per_cu ? items : cus * per_cu;
+    const int grid = persistent_grid(items, cus * per_cu);
     hipLaunchKernelGGL((conv_rb_kernel<NT, RESID, WRES, FUSED_ACT, DBG, UPS, HEAD>), dim3(grid), dim3(RB_THREADS), 0, stream, a);
     IRE_HIP(hipGetLastError());
 }

@@ -16,6 +16,7 @@
 //   * epilogue as conv_pc's: accumulators start at the bias, bf16 stores straight from the accumulators, GroupNorm partial
 //     statistics (8 groups of 4 channels) of the stored values per tile
 #include "conv_mfma.hpp"
+#include "conv_prims.hpp"
 #include "persist.hpp"
 
 #include <type_traits>
@@ -24,31 +25,11 @@ namespace ire {
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
 constexpr int ST_THREADS = 512, ST_TH = 16, ST_TW = 32, ST_IH = ST_TH + 2, ST_IW = ST_TW + 2;
 constexpr int ST_RB = ST_IW * 3;            // bytes of a tile row in the image: 102
 constexpr int ST_PW = ST_IW + 2;            // pixels per LDS row: the fragment of pixel r = 31, h = 1 reaches pixel 34 (zero weight) -- kept finite (zero)
 constexpr int ST_ROW = ST_PW * 4;           // LDS row pitch in bf16 elements (4 per pixel)
 constexpr int ST_ITERS = (ST_IH * ST_RB + ST_THREADS - 1) / ST_THREADS;     // 4 bytes per thread and tile
-
-__device__ __forceinline__ unsigned st_pack(float a, float b) {
-    f32x2_t f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
-template <int N> __device__ __forceinline__ float st_ror_add(float v) {
-    const int r = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false);
-    return v + __builtin_bit_cast(float, r);
-}
-__device__ __forceinline__ float st_swap16_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
 
 // two workgroups per CU (119 registers): they overlap one another's staging, arithmetic and stores; three would need <= 80
 // registers (36 spilled: 289 us against 150)
@@ -132,8 +113,8 @@ __global__ __launch_bounds__(ST_THREADS) void conv_stem_kernel(ConvArgs a) {
             const float mf = inb ? 1.f : 0.f;
 #pragma unroll
             for (int pp = 0; pp < 2; ++pp) {
-                const unsigned w[4] = {st_pack(c[8 * pp + 0], c[8 * pp + 1]), st_pack(c[8 * pp + 2], c[8 * pp + 3]),
-                                       st_pack(c[8 * pp + 4], c[8 * pp + 5]), st_pack(c[8 * pp + 6], c[8 * pp + 7])};
+                const unsigned w[4] = {pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
+                                       pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
 #pragma unroll
                 for (int d = 0; d < 4; ++d) {
                     const bf16x2_t wv = __builtin_bit_cast(bf16x2_t, w[d]);
@@ -164,9 +145,9 @@ __global__ __launch_bounds__(ST_THREADS) void conv_stem_kernel(ConvArgs a) {
             for (int k = 0; k < 4; ++k) u[k] = xch(b0 ? vq[k] : vs[k], b0 ? vs[k] : vq[k], std::integral_constant<int, 0xb1>{});     // quad_perm [1,0,3,2]: lane ^ 1
 #pragma unroll
             for (int k = 0; k < 2; ++k) t2[k] = xch(b1 ? u[2 + k] : u[k], b1 ? u[k] : u[2 + k], std::integral_constant<int, 0x4e>{});   // quad_perm [2,3,0,1]: lane ^ 2
-            t2[0] = st_ror_add<4>(t2[0]); t2[1] = st_ror_add<4>(t2[1]);
-            t2[0] = st_ror_add<8>(t2[0]); t2[1] = st_ror_add<8>(t2[1]);
-            t2[0] = st_swap16_add(t2[0]); t2[1] = st_swap16_add(t2[1]);
+            t2[0] = ror_add<4>(t2[0]); t2[1] = ror_add<4>(t2[1]);
+            t2[0] = ror_add<8>(t2[0]); t2[1] = ror_add<8>(t2[1]);
+            t2[0] = swap16_add(t2[0]); t2[1] = swap16_add(t2[1]);
             if ((lane & 28) == 0) {
                 const int g0 = 4 * (b1 ? 1 : 0) + 2 * h;      // hf = 0; hf = 1 is the next group
                 red[par][wave][g0][b0 ? 1 : 0] = t2[0];
@@ -192,8 +173,7 @@ __global__ __launch_bounds__(ST_THREADS) void conv_stem_kernel(ConvArgs a) {
 void conv_stem_launch(const ConvArgs& a, hipStream_t stream) {
     if (a.cout != 32 || a.Hout != a.Hin || a.Wout != a.Win || !a.stats) fail(IRE_ERR_INTERNAL, "internal: conv_stem shape");
     const int items = a.tiles_x * a.tiles_y * a.nimg;
-    const int cus = persistent_grid_cus();
-    const int grid = items < 2 * cus ? items : 2 * cus;
+    const int grid = persistent_grid(items, 2 * persistent_grid_cus());
     hipLaunchKernelGGL(conv_stem_kernel, dim3(grid), dim3(ST_THREADS), 0, stream, a);
     IRE_HIP(hipGetLastError());
 }

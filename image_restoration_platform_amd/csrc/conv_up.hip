@@ -25,6 +25,7 @@
 // less traffic, one launch less per level), `fuse`'s 2*C*C flop per pixel over the up half are gone, and the epilogue also
 // writes the GroupNorm partials `fuse` used to write: one (sum, sumsq) per group per ITEM (32 x 64 output pixels).
 #include "conv_mfma.hpp"
+#include "conv_prims.hpp"
 #include "persist.hpp"
 
 #include <type_traits>
@@ -32,12 +33,6 @@
 namespace ire {
 
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 #ifndef IRE_UP_TEPI
 #define IRE_UP_TEPI 1     // fused form: line-coalesced epilogue (skip rows and output rows through a wave-private LDS patch); 0: the direct epilogue (build-time A/B)
@@ -62,27 +57,6 @@ constexpr int UP_RED_OFF = UP_SKW_OFF + 8192;          // fused form: [8 waves][
 constexpr int UP_LDS = UP_RED_OFF + 8 * 8 * 2 * 4;
 static_assert(UP_LDS <= 160 * 1024, "LDS");
 constexpr int UP_PATCH = UP_BUF / 8;                   // line-coalesced epilogue: 9 KB per wave of the buffer the item's last stage has finished with
-
-__device__ __forceinline__ unsigned up_pack(float a, float b) {
-    f32x2_t f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
-// LDS-DMA (see conv_rb.hip::rb_glds16): invisible to the compiler's s_waitcnt bookkeeping, the caller waits and barriers
-__device__ __forceinline__ void up_glds16(const void* gsrc, unsigned lds_dst_uniform) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
-
-template <int N> __device__ __forceinline__ float up_ror_add(float v) {
-    const int r = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false);
-    return v + __builtin_bit_cast(float, r);
-}
-__device__ __forceinline__ float up_swap16_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
 
 template <int I, int N, class F> __device__ __forceinline__ void up_static_for(F& f) {
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); up_static_for<I + 1, N>(f); }
@@ -219,8 +193,8 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
                     const f32x16_t& c = acc[par][m];
 #pragma unroll
                     for (int pp = 0; pp < 2; ++pp) {
-                        unsigned w[4] = {up_pack(c[8 * pp + 0], c[8 * pp + 1]), up_pack(c[8 * pp + 2], c[8 * pp + 3]),
-                                         up_pack(c[8 * pp + 4], c[8 * pp + 5]), up_pack(c[8 * pp + 6], c[8 * pp + 7])};
+                        unsigned w[4] = {pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
+                                         pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
                         const u32x4_t wv4 = {w[0], w[1], w[2], w[3]};
                         if constexpr (!(IRE_UP_ABL & 4)) __builtin_amdgcn_raw_buffer_store_b128(wv4, orsrc, inb[m] ? off + (unsigned)(pp * 32) : 0xffffffffu, 0, IRE_ST_PART);
                         else asm volatile("" :: "v"(wv4));
@@ -248,15 +222,15 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
             // GroupNorm partials of the item: quad k of lane-half h is couts 16 (k >> 1) + 8 h + 4 (k & 1) .. + 3 of the block
             float rv[8] = {ssum[0], qsum[0], ssum[1], qsum[1], ssum[2], qsum[2], ssum[3], qsum[3]};
 #pragma unroll
-            for (int i = 0; i < 8; ++i) rv[i] = up_ror_add<1>(rv[i]);
+            for (int i = 0; i < 8; ++i) rv[i] = ror_add<1>(rv[i]);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) rv[i] = up_ror_add<2>(rv[i]);
+            for (int i = 0; i < 8; ++i) rv[i] = ror_add<2>(rv[i]);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) rv[i] = up_ror_add<4>(rv[i]);
+            for (int i = 0; i < 8; ++i) rv[i] = ror_add<4>(rv[i]);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) rv[i] = up_ror_add<8>(rv[i]);
+            for (int i = 0; i < 8; ++i) rv[i] = ror_add<8>(rv[i]);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) rv[i] = up_swap16_add(rv[i]);
+            for (int i = 0; i < 8; ++i) rv[i] = swap16_add(rv[i]);
             float* red = reinterpret_cast<float*>(smem + UP_RED_OFF);
             if (r_e == 0) {
 #pragma unroll
@@ -289,8 +263,8 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
                 const f32x16_t& c = acc[par][m];
 #pragma unroll
                 for (int pp = 0; pp < 2; ++pp) {
-                    const u32x4_t wv4 = {up_pack(c[8 * pp + 0], c[8 * pp + 1]), up_pack(c[8 * pp + 2], c[8 * pp + 3]),
-                                         up_pack(c[8 * pp + 4], c[8 * pp + 5]), up_pack(c[8 * pp + 6], c[8 * pp + 7])};
+                    const u32x4_t wv4 = {pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
+                                         pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
                     __builtin_amdgcn_raw_buffer_store_b128(wv4, orsrc, inb ? off + (unsigned)(pp * 32) : 0xffffffffu, 0, IRE_ST_PART);
                 }
             }
@@ -399,8 +373,8 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
                 const f32x16_t& c = acc[pa * 2 + pb][m];
 #pragma unroll
                 for (int pp = 0; pp < 2; ++pp) {
-                    const u32x4_t wv = {up_pack(c[8 * pp + 0], c[8 * pp + 1]), up_pack(c[8 * pp + 2], c[8 * pp + 3]),
-                                        up_pack(c[8 * pp + 4], c[8 * pp + 5]), up_pack(c[8 * pp + 6], c[8 * pp + 7])};
+                    const u32x4_t wv = {pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
+                                        pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
                     *reinterpret_cast<u32x4_t*>(patch + (2 * r_e + pb) * 64 + (((2 * pp + h_e) ^ (r_e & 3)) << 4)) = wv;
                 }
             }
@@ -425,13 +399,13 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
             // the 16 lanes that share a read-back chunk sit 4 apart: two rotations within the row of 16, then the rows and the halves
             float rv[4] = {ssum[0], qsum[0], ssum[1], qsum[1]};
 #pragma unroll
-            for (int i = 0; i < 4; ++i) rv[i] = up_ror_add<4>(rv[i]);
+            for (int i = 0; i < 4; ++i) rv[i] = ror_add<4>(rv[i]);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) rv[i] = up_ror_add<8>(rv[i]);
+            for (int i = 0; i < 4; ++i) rv[i] = ror_add<8>(rv[i]);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) rv[i] = up_swap16_add(rv[i]);
+            for (int i = 0; i < 4; ++i) rv[i] = swap16_add(rv[i]);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { float x = rv[i], y = rv[i]; asm volatile("v_nop\n\tv_nop\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y)); rv[i] = x + y; }
+            for (int i = 0; i < 4; ++i) rv[i] = swap32_add(rv[i]);
             float* red = reinterpret_cast<float*>(smem + UP_RED_OFF);
             if (l_e < 4) {          // chunk scq = lane: cout quads 2 scq, 2 scq + 1
                 *reinterpret_cast<float2*>(red + (w_e * 8 + 2 * l_e) * 2) = make_float2(rv[0], rv[1]);
@@ -549,7 +523,7 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
 #pragma unroll
                 for (int i = 0; i < UP_W_ITERS; ++i) {
                     const int cbase = i * UP_THREADS + wave_u * 64;
-                    up_glds16(ws + (size_t)(cbase + lane) * 16, w_nxt_lds + cbase * 16);
+                    glds16(ws + (size_t)(cbase + lane) * 16, w_nxt_lds + cbase * 16);
                 }
             }
             // fused form: the skip weights of this item's cout block (NKS KB) for the epilogue of the NEXT stage, one wave
@@ -557,7 +531,7 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
             if constexpr (NKS > 0 && PRELAST && g == 1) {
                 const int wave_u = __builtin_amdgcn_readfirstlane(wave);
                 if (wave_u < NKS)
-                    up_glds16(reinterpret_cast<const unsigned char*>(a.w1) + ((size_t)sq0.it.nb * NKS + wave_u) * 1024 + lane * 16,
+                    glds16(reinterpret_cast<const unsigned char*>(a.w1) + ((size_t)sq0.it.nb * NKS + wave_u) * 1024 + lane * 16,
                               smem_lds + UP_SKW_OFF + wave_u * 1024);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -622,8 +596,7 @@ void conv_up_subpixel_launch(const ConvArgs& a, hipStream_t stream) {
     if (a.nkc < 2 || (a.nkc & 1) || a.cout > 256) fail(IRE_ERR_INTERNAL, "internal: conv_up_subpixel shape");
     if (a.in1 && (!a.w1 || !a.stats || (a.cout != 32 && a.cout != 64 && a.cout != 128))) fail(IRE_ERR_INTERNAL, "internal: fused conv_up arguments");
     const int items = a.tiles_x * a.tiles_y * a.nimg * a.nblocks;
-    const int cus = persistent_grid_cus();
-    const int grid = items < cus ? items : cus;
+    const int grid = persistent_grid(items);
     if (!a.in1) hipLaunchKernelGGL(conv_up_kernel<0>, dim3(grid), dim3(UP_THREADS), 0, stream, a);
     else if (a.cout == 32) hipLaunchKernelGGL(conv_up_kernel<2>, dim3(grid), dim3(UP_THREADS), 0, stream, a);
     else if (a.cout == 64) hipLaunchKernelGGL(conv_up_kernel<4>, dim3(grid), dim3(UP_THREADS), 0, stream, a);

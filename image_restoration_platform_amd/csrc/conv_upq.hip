@@ -26,6 +26,7 @@
 // Weights: a.w = [parity][kc32][tap4][c8][128 rows, permuted like conv_w4's][8] bf16 (weight_pack.hpp::pack_up_fused d_wuq),
 // a.w1 = skip weights [ks16][h][128 rows][8] (d_wsq; as bytes the same as [ks32][c8][128][8]), a.bias = composed bias.  Roofline: MFMA (executed 2*4*Cin*C + 2*C*C flop per pixel).
 #include "conv_mfma.hpp"
+#include "conv_prims.hpp"
 #include "persist.hpp"
 
 #include <type_traits>
@@ -33,12 +34,6 @@
 namespace ire {
 
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 #ifndef UQ_ST
 #define UQ_ST IRE_ST_LINE   // cache policy of the output stores (conv_mfma.hpp): build-time A/B
@@ -63,33 +58,6 @@ constexpr int UQ_PATCH_BASE = UQ_BIAS_BASE + UQ_NT * 4;
 constexpr int UQ_PATCH_BYTES = 8 * UQ_NT * 2;                   // 2 048: a wave's transpose patch, 8 pixels x 128 couts (LDS of its own: see the epilogue)
 constexpr int UQ_LDS = UQ_PATCH_BASE + 8 * UQ_PATCH_BYTES;
 static_assert(UQ_LDS <= 160 * 1024, "LDS");
-
-__device__ __forceinline__ unsigned uq_pack(float a, float b) {
-    f32x2_t f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
-__device__ __forceinline__ void uq_glds16(const void* gsrc, unsigned lds_dst_uniform) {   // LDS-DMA, 1 KB per wave-instruction (conv_rb.hip::rb_glds16)
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
-__device__ __forceinline__ float uq_swap16_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
-__device__ __forceinline__ float uq_swap32_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
-// the stage barrier: this wave's DMA pieces of the next stage have landed, its LDS reads are done; behind the barrier everybody's are.
-// KEEP = 16: the stage that follows an epilogue -- its successor's pieces were issued IN FRONT of the epilogue's 16 output stores
-// (vector-memory operations retire in issue order: "all but the 16 youngest" = exactly those pieces), so the stores drain in the
-// background instead of in front of a barrier (all 256 workgroups store 128 KB at the same moment: 30 us per launch when waited for).
-template <int KEEP> __device__ __forceinline__ void uq_stage_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(KEEP) : "memory");
-}
 
 __global__ __launch_bounds__(UQ_THREADS) void conv_upq_kernel(ConvArgs a) {
     constexpr int NT = UQ_NT, NTL = UQ_NTL, C = UQ_NT;
@@ -207,10 +175,10 @@ __global__ __launch_bounds__(UQ_THREADS) void conv_upq_kernel(ConvArgs a) {
         item_offsets(cs.it);
         plan_stage(cs, 0, P);
 #pragma unroll
-        for (int i = 0; i < 10; ++i) if (i < P.n) uq_glds16(P.src[i], P.dst[i]);
+        for (int i = 0; i < 10; ++i) if (i < P.n) glds16(P.src[i], P.dst[i]);
     }
     if (tid < C) reinterpret_cast<float*>(smem + UQ_BIAS_BASE)[tid] = a.bias[tid];
-    uq_stage_barrier<0>();
+    stage_barrier<0>();
     int buf = 0, stage_no = 0;
     bool pre_issued = false;              // the next stage's pieces are already on their way (issued by the previous item's epilogue)
 
@@ -276,7 +244,7 @@ __global__ __launch_bounds__(UQ_THREADS) void conv_upq_kernel(ConvArgs a) {
                         // the next stage's DMA pieces, spread over the k-loop: piece i rides in front of MFMA pair (i NG) / 10
 #pragma unroll
                         for (int i = 0; i < 10; ++i)
-                            if ((i * (NG * UQ_DMA_SPAN / 32)) / 10 == g && i < P.n && !(((UQ_ABL & 8) && (i < 4 || i >= P.n - (wv < 4 ? 1 : 0))) || ((UQ_ABL & 16) && i >= 4 && i < P.n - (wv < 4 ? 1 : 0)))) uq_glds16(P.src[i], P.dst[i]);
+                            if ((i * (NG * UQ_DMA_SPAN / 32)) / 10 == g && i < P.n && !(((UQ_ABL & 8) && (i < 4 || i >= P.n - (wv < 4 ? 1 : 0))) || ((UQ_ABL & 16) && i >= 4 && i < P.n - (wv < 4 ? 1 : 0)))) glds16(P.src[i], P.dst[i]);
                         if (g + 1 < NG) bq[(g + 1) & 1] = rd_b((g + 1) / NTL, (g + 1) % NTL);
                         if (st + 1 < NS && j == 1) aq[(st + 1) & 1][0] = rd_a(st + 1, 0);
                         if (st + 1 < NS && j == 2) aq[(st + 1) & 1][1] = rd_a(st + 1, 1);
@@ -289,7 +257,7 @@ __global__ __launch_bounds__(UQ_THREADS) void conv_upq_kernel(ConvArgs a) {
             }
             if constexpr (UQ_ABL & 4) {
 #pragma unroll
-                for (int i = 0; i < 10; ++i) if (i < P.n) uq_glds16(P.src[i], P.dst[i]);
+                for (int i = 0; i < 10; ++i) if (i < P.n) glds16(P.src[i], P.dst[i]);
             }
             if constexpr (!(UQ_ABL & 1) && !(UQ_ABL & 4)) {
 #pragma unroll
@@ -309,7 +277,7 @@ __global__ __launch_bounds__(UQ_THREADS) void conv_upq_kernel(ConvArgs a) {
             ++stage_no;
             cs = cn; cn = cursor.next();
             // the next stage is staged; nobody reads this stage's pair any more
-            if (pre_issued) uq_stage_barrier<16>(); else uq_stage_barrier<0>();
+            if (pre_issued) stage_barrier<16>(); else stage_barrier<0>();
             pre_issued = false;
             flush_stats();
         };
@@ -321,7 +289,7 @@ __global__ __launch_bounds__(UQ_THREADS) void conv_upq_kernel(ConvArgs a) {
             Plan P;
             plan_stage(cn, buf ^ 1, P);
 #pragma unroll
-            for (int i = 0; i < 10; ++i) if (i < P.n) uq_glds16(P.src[i], P.dst[i]);
+            for (int i = 0; i < 10; ++i) if (i < P.n) glds16(P.src[i], P.dst[i]);
             pre_issued = true;
         }
         if constexpr (UQ_ABL & 2) {
@@ -362,8 +330,8 @@ __global__ __launch_bounds__(UQ_THREADS) void conv_upq_kernel(ConvArgs a) {
                 for (int g = 0; g < NTL * 2; ++g) {
                     const f32x16_t& c = acc[m][g >> 1];
                     const int pp = g & 1;
-                    pkd[m][g] = u32x4_t{uq_pack(c[8 * pp + 0], c[8 * pp + 1]), uq_pack(c[8 * pp + 2], c[8 * pp + 3]),
-                                        uq_pack(c[8 * pp + 4], c[8 * pp + 5]), uq_pack(c[8 * pp + 6], c[8 * pp + 7])};
+                    pkd[m][g] = u32x4_t{pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
+                                        pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
                 }
             __builtin_amdgcn_sched_barrier(0);
             float ssum = 0.f, qsum = 0.f;
@@ -398,8 +366,8 @@ __global__ __launch_bounds__(UQ_THREADS) void conv_upq_kernel(ConvArgs a) {
                     }
                 }
             // this lane's chunk cc_r over its read-backs; the other lanes with the same chunk sit 16 apart
-            ssum = uq_swap16_add(ssum); qsum = uq_swap16_add(qsum);
-            ssum = uq_swap32_add(ssum); qsum = uq_swap32_add(qsum);
+            ssum = swap16_add(ssum); qsum = swap16_add(qsum);
+            ssum = swap32_add(ssum); qsum = swap32_add(qsum);
             if (l_e < 16) *reinterpret_cast<float2*>(red + red_par * (8 * 32) + (wave * 16 + cc_r) * 2) = make_float2(ssum, qsum);
             st_img = it.img; st_slot = it.tile * 4 + it.nb; st_par = red_par; red_par ^= 1;
         }
@@ -418,8 +386,7 @@ void conv_upq_launch(const ConvArgs& a, hipStream_t stream) {
         a.Hout != 2 * a.Hin || a.Wout != 2 * a.Win)
         fail(IRE_ERR_INTERNAL, "internal: conv_upq arguments");
     const int items = a.tiles_x * a.tiles_y * a.nimg * 4;
-    const int cus = persistent_grid_cus();
-    const int grid = items < cus ? items : cus;
+    const int grid = persistent_grid(items);
     hipLaunchKernelGGL(conv_upq_kernel, dim3(grid), dim3(UQ_THREADS), 0, stream, a);
     IRE_HIP(hipGetLastError());
 }

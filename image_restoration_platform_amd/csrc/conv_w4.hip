@@ -16,6 +16,7 @@
 // 4-wave form are template branches no launch instantiates since round 4.  Epilogue: the 128-channel tile leaves in 4 passes of 32
 // channels through the current stage buffer (bias, residual, GroupNorm partials, full-line stores).
 #include "conv_mfma.hpp"
+#include "conv_prims.hpp"
 #include "persist.hpp"
 #include "gn_fold.hpp"
 
@@ -30,45 +31,12 @@ namespace ire {
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-
 constexpr int W4_TH = 16, W4_TW = 32, W4_IH = 18, W4_IW = 34;
 constexpr int W4_IN_CHUNKS = W4_IH * W4_IW * 2;                              // 1224 x 16 B (16 channels per pixel)
 constexpr int W4_IN_BYTES = (W4_IN_CHUNKS + 8) * 16;                          // + dummy slot (chunk slots past the tile)
 constexpr int W4_NSTEPS = 9;
 
-__device__ __forceinline__ unsigned w4_pack(float a, float b) {
-    f32x2_t f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
-__device__ __forceinline__ float w4_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float w4_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-
-__device__ __forceinline__ void w4_glds16(const void* gsrc, unsigned lds_dst_uniform) {   // see conv_rb.hip
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
-template <int N> __device__ __forceinline__ float w4_ror_add(float v) {
-    const int r = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false);
-    return v + __builtin_bit_cast(float, r);
-}
-__device__ __forceinline__ float w4_swap16_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
-__device__ __forceinline__ float w4_swap32_add(float v) {
-    float x = v, y = v;
-    asm volatile("v_nop\n\tv_nop\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
-
 using W4Item = PersistItem;
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 template <int N> struct W4Regs { u32x4_t v[N]; unsigned ok; };   // native 128-bit tuples: one register quad per load
 
 // WAVES = 4: one wave per SIMD, wave tile 4 rows x NT couts (all 256 AGPRs are accumulators at NT = 128)
@@ -208,14 +176,14 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
     // instruction costs several times two plain ones -- MI355X_MICROARCH.md per-instruction constants; profiles/r02_experiments.md)
     auto transform_pair = [&](unsigned w, int d) -> f32x2_t {        // (kFp8ActScale x) silu(x*A + B) of the word's two channels
         constexpr float K = FP8 ? -1.4426950408889634f / kFp8ActScale : -1.4426950408889634f;
-        const float y0 = __builtin_fmaf(w4_lo(w), cA[2 * d], cB[2 * d]), y1 = __builtin_fmaf(w4_hi(w), cA[2 * d + 1], cB[2 * d + 1]);
+        const float y0 = __builtin_fmaf(bf16_lo(w), cA[2 * d], cB[2 * d]), y1 = __builtin_fmaf(bf16_hi(w), cA[2 * d + 1], cB[2 * d + 1]);
         const float e0 = __builtin_amdgcn_exp2f(y0 * K) + 1.0f, e1 = __builtin_amdgcn_exp2f(y1 * K) + 1.0f;
         const f32x2_t sv = {y0 * __builtin_amdgcn_rcpf(e0), y1 * __builtin_amdgcn_rcpf(e1)};
         return sv;
     };
     auto transform_word = [&](unsigned w, int d) -> unsigned {
         const f32x2_t sv = transform_pair(w, d);
-        return w4_pack(sv.x, sv.y);
+        return pack_bf16(sv.x, sv.y);
     };
     auto store_chunk = [&](int i, const Regs& R, uint4* lds_in) {   // copy (or activate); zero padding outside the image
         int t2 = tid;
@@ -477,7 +445,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
                     for (int d = 5 * i; i < 2 && d < 5 * i + 5 && d < C::W_ITERS; ++d) {
                         int cbase = d * C::THREADS + wave_u * 64;
                         if ((d + 1) * C::THREADS > C::W_CHUNKS) cbase = cbase >= C::W_CHUNKS ? cbase - C::W_CHUNKS : cbase;   // wraps to a 64-aligned group
-                        w4_glds16(ws + (size_t)(cbase + lane) * 16, w_dst_lds + cbase * 16);
+                        glds16(ws + (size_t)(cbase + lane) * 16, w_dst_lds + cbase * 16);
                     }
                 }
             }
@@ -524,21 +492,21 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
                 const f32x16_t& c = acc[m][j];
                 unsigned x0, x1, y0, y1;
                 if constexpr (FP8) {
-                    x0 = w4_pack(c[8 * pp + 0] * s0.x, c[8 * pp + 1] * s0.y); x1 = w4_pack(c[8 * pp + 2] * s0.z, c[8 * pp + 3] * s0.w);
-                    y0 = w4_pack(c[8 * pp + 4] * s1.x, c[8 * pp + 5] * s1.y); y1 = w4_pack(c[8 * pp + 6] * s1.z, c[8 * pp + 7] * s1.w);
+                    x0 = pack_bf16(c[8 * pp + 0] * s0.x, c[8 * pp + 1] * s0.y); x1 = pack_bf16(c[8 * pp + 2] * s0.z, c[8 * pp + 3] * s0.w);
+                    y0 = pack_bf16(c[8 * pp + 4] * s1.x, c[8 * pp + 5] * s1.y); y1 = pack_bf16(c[8 * pp + 6] * s1.z, c[8 * pp + 7] * s1.w);
                 } else if constexpr (BIAS_INIT) {
-                    x0 = w4_pack(c[8 * pp + 0], c[8 * pp + 1]); x1 = w4_pack(c[8 * pp + 2], c[8 * pp + 3]);
-                    y0 = w4_pack(c[8 * pp + 4], c[8 * pp + 5]); y1 = w4_pack(c[8 * pp + 6], c[8 * pp + 7]);
+                    x0 = pack_bf16(c[8 * pp + 0], c[8 * pp + 1]); x1 = pack_bf16(c[8 * pp + 2], c[8 * pp + 3]);
+                    y0 = pack_bf16(c[8 * pp + 4], c[8 * pp + 5]); y1 = pack_bf16(c[8 * pp + 6], c[8 * pp + 7]);
                 } else {
-                    x0 = w4_pack(c[8 * pp + 0] + b0.x, c[8 * pp + 1] + b0.y); x1 = w4_pack(c[8 * pp + 2] + b0.z, c[8 * pp + 3] + b0.w);
-                    y0 = w4_pack(c[8 * pp + 4] + b1.x, c[8 * pp + 5] + b1.y); y1 = w4_pack(c[8 * pp + 6] + b1.z, c[8 * pp + 7] + b1.w);
+                    x0 = pack_bf16(c[8 * pp + 0] + b0.x, c[8 * pp + 1] + b0.y); x1 = pack_bf16(c[8 * pp + 2] + b0.z, c[8 * pp + 3] + b0.w);
+                    y0 = pack_bf16(c[8 * pp + 4] + b1.x, c[8 * pp + 5] + b1.y); y1 = pack_bf16(c[8 * pp + 6] + b1.z, c[8 * pp + 7] + b1.w);
                 }
                 unsigned w[4] = {x0, x1, y0, y1};
                 if constexpr (RESID) {
                     const uint4 rr = rv[g % RD][m];
                     const unsigned rw[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
-                    for (int d = 0; d < 4; ++d) w[d] = w4_pack(w4_lo(w[d]) + w4_lo(rw[d]), w4_hi(w[d]) + w4_hi(rw[d]));
+                    for (int d = 0; d < 4; ++d) w[d] = pack_bf16(bf16_lo(w[d]) + bf16_lo(rw[d]), bf16_hi(w[d]) + bf16_hi(rw[d]));
                 }
                 float s1 = 0.f, q1 = 0.f;
 #pragma unroll
@@ -582,13 +550,13 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) t4[k] = xch(b1 ? u[4 + k] : u[k], b1 ? u[k] : u[4 + k], std::integral_constant<int, 0x4e>{});   // quad_perm [2,3,0,1]: lane ^ 2
 #pragma unroll
-                for (int k = 0; k < 4; ++k) t4[k] = w4_ror_add<4>(t4[k]);
+                for (int k = 0; k < 4; ++k) t4[k] = ror_add<4>(t4[k]);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) t4[k] = w4_ror_add<8>(t4[k]);
+                for (int k = 0; k < 4; ++k) t4[k] = ror_add<8>(t4[k]);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) t4[k] = w4_swap16_add(t4[k]);
+                for (int k = 0; k < 4; ++k) t4[k] = swap16_add(t4[k]);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) t4[k] = w4_swap32_add(t4[k]);
+                for (int k = 0; k < 4; ++k) t4[k] = swap32_add(t4[k]);
                 if ((lane & 60) == 0) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) red[(wave * 8 + (b1 ? 4 : 0) + k) * 2 + (b0 ? 1 : 0)] = t4[k];
@@ -598,17 +566,17 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
     #pragma unroll
                 for (int g = 0; g < NTL * 2; ++g) { rv16[2 * g] = ssum[g >> 1][g & 1]; rv16[2 * g + 1] = qsum[g >> 1][g & 1]; }
     #pragma unroll
-                for (int i = 0; i < NTL * 4; ++i) rv16[i] = w4_ror_add<1>(rv16[i]);
+                for (int i = 0; i < NTL * 4; ++i) rv16[i] = ror_add<1>(rv16[i]);
     #pragma unroll
-                for (int i = 0; i < NTL * 4; ++i) rv16[i] = w4_ror_add<2>(rv16[i]);
+                for (int i = 0; i < NTL * 4; ++i) rv16[i] = ror_add<2>(rv16[i]);
     #pragma unroll
-                for (int i = 0; i < NTL * 4; ++i) rv16[i] = w4_ror_add<4>(rv16[i]);
+                for (int i = 0; i < NTL * 4; ++i) rv16[i] = ror_add<4>(rv16[i]);
     #pragma unroll
-                for (int i = 0; i < NTL * 4; ++i) rv16[i] = w4_ror_add<8>(rv16[i]);
+                for (int i = 0; i < NTL * 4; ++i) rv16[i] = ror_add<8>(rv16[i]);
     #pragma unroll
-                for (int i = 0; i < NTL * 4; ++i) rv16[i] = w4_swap16_add(rv16[i]);
+                for (int i = 0; i < NTL * 4; ++i) rv16[i] = swap16_add(rv16[i]);
     #pragma unroll
-                for (int i = 0; i < NTL * 4; ++i) rv16[i] = w4_swap32_add(rv16[i]);
+                for (int i = 0; i < NTL * 4; ++i) rv16[i] = swap32_add(rv16[i]);
                 if (lane == 0) {
     #pragma unroll
                     for (int g = 0; g < NTL * 2; ++g) *reinterpret_cast<float2*>(red + (wave * 8 + g) * 2) = make_float2(rv16[2 * g], rv16[2 * g + 1]);
@@ -680,11 +648,11 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
                             const float* sl = reinterpret_cast<const float*>(smem + C::MAIN_BYTES + C::RED_BYTES + C::BIAS_BYTES + C::COEF_BYTES);
                             const float4 s0 = *reinterpret_cast<const float4*>(sl + cout0 + j * 32 + 16 * pp + 8 * h_e);
                             const float4 s1 = *reinterpret_cast<const float4*>(sl + cout0 + j * 32 + 16 * pp + 8 * h_e + 4);
-                            wv = u32x4_t{w4_pack(c[8 * pp + 0] * s0.x, c[8 * pp + 1] * s0.y), w4_pack(c[8 * pp + 2] * s0.z, c[8 * pp + 3] * s0.w),
-                                         w4_pack(c[8 * pp + 4] * s1.x, c[8 * pp + 5] * s1.y), w4_pack(c[8 * pp + 6] * s1.z, c[8 * pp + 7] * s1.w)};
+                            wv = u32x4_t{pack_bf16(c[8 * pp + 0] * s0.x, c[8 * pp + 1] * s0.y), pack_bf16(c[8 * pp + 2] * s0.z, c[8 * pp + 3] * s0.w),
+                                         pack_bf16(c[8 * pp + 4] * s1.x, c[8 * pp + 5] * s1.y), pack_bf16(c[8 * pp + 6] * s1.z, c[8 * pp + 7] * s1.w)};
                         } else {
-                            wv = u32x4_t{w4_pack(c[8 * pp + 0], c[8 * pp + 1]), w4_pack(c[8 * pp + 2], c[8 * pp + 3]),
-                                         w4_pack(c[8 * pp + 4], c[8 * pp + 5]), w4_pack(c[8 * pp + 6], c[8 * pp + 7])};
+                            wv = u32x4_t{pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
+                                         pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
                         }
                         const int cc = 2 * g + h_e;                       // chunk of the pixel's 128-cout run: couts 8 cc .. 8 cc + 7
                         *reinterpret_cast<u32x4_t*>(patch + r16 * PITCH + ((cc ^ (r16 & (NCHK - 1))) << 4)) = wv;
@@ -700,7 +668,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
                         const uint4 rr = rvt[(2 * m + q) % 3][k];
                         const unsigned rw[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
-                        for (int d = 0; d < 4; ++d) w[d] = w4_pack(w4_lo(w[d]) + w4_lo(rw[d]), w4_hi(w[d]) + w4_hi(rw[d]));
+                        for (int d = 0; d < 4; ++d) w[d] = pack_bf16(bf16_lo(w[d]) + bf16_lo(rw[d]), bf16_hi(w[d]) + bf16_hi(rw[d]));
                     }
                     float s1 = 0.f, q1 = 0.f;
 #pragma unroll
@@ -718,9 +686,9 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
             }
         stamp(9);
         // this lane's chunk cc_r over its read-backs; the other lanes with the same chunk sit NCHK apart
-        if constexpr (NCHK == 8) { ssum = w4_ror_add<8>(ssum); qsum = w4_ror_add<8>(qsum); }
-        ssum = w4_swap16_add(ssum); qsum = w4_swap16_add(qsum);
-        ssum = w4_swap32_add(ssum); qsum = w4_swap32_add(qsum);
+        if constexpr (NCHK == 8) { ssum = ror_add<8>(ssum); qsum = ror_add<8>(qsum); }
+        ssum = swap16_add(ssum); qsum = swap16_add(qsum);
+        ssum = swap32_add(ssum); qsum = swap32_add(qsum);
         if (l_e < NCHK) *reinterpret_cast<float2*>(red + red_par * (WAVES * 32) + (wave * NCHK + cc_r) * 2) = make_float2(ssum, qsum);
         st_img = it.img; st_tile = it.tile; st_cout0 = cout0; st_par = red_par; red_par ^= 1;
     };
@@ -752,8 +720,8 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
             const unsigned char* ws1 = wslab(sq1);
             const int wave_u = __builtin_amdgcn_readfirstlane(wave);
             for (int p = wave_u; p < C::W_CHUNKS / 64; p += WAVES) {
-                w4_glds16(ws0 + ((size_t)p * 64 + lane) * 16, smem_lds + C::W_BASE + p * 1024);
-                w4_glds16(ws1 + ((size_t)p * 64 + lane) * 16, smem_lds + C::W_BASE + C::W_BYTES + p * 1024);
+                glds16(ws0 + ((size_t)p * 64 + lane) * 16, smem_lds + C::W_BASE + p * 1024);
+                glds16(ws1 + ((size_t)p * 64 + lane) * 16, smem_lds + C::W_BASE + C::W_BYTES + p * 1024);
             }
         }
         if (a.gn_stats) gn_fold(a, smem, cursor.first_img, cursor.last_img);     // GroupNorm finalize of the input tensor, folded in (gn_fold.hpp)
@@ -799,8 +767,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
 template <int NT, int WAVES, bool RESID, bool UPS, int DBG = 0, bool FUSED = false, bool FP8 = false>
 void launch_w4(const ConvArgs& a, hipStream_t stream) {
     const int items = a.tiles_x * a.tiles_y * a.nimg * a.nblocks;
-    const int cus = persistent_grid_cus();
-    const int grid = items < cus ? items : cus;
+    const int grid = persistent_grid(items);
     hipLaunchKernelGGL((conv_w4_kernel<NT, WAVES, RESID, UPS, DBG, FUSED, FP8>), dim3(grid), dim3(WAVES * 64), 0, stream, a);
     IRE_HIP(hipGetLastError());
 }

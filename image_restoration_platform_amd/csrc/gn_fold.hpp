@@ -33,7 +33,7 @@ __device__ __forceinline__ double gnf_xlane_add(double v, int ctrl_kind) {
         unsigned x = lo, y = lo, x2 = hi, y2 = hi;
         asm volatile("v_nop\n\tv_nop\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
         asm volatile("v_nop\n\tv_nop\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x2), "+v"(y2));
-        // after the swap x holds (own rows 0, 2 | partner rows ...): x and y are the two operands of the pairwise add, as in *_swap16_add
+        // after the swap x holds (own rows 0, 2 | partner rows ...): x and y are the two operands of the pairwise add, as in conv_prims.hpp::swap16_add
         const double a = __builtin_bit_cast(double, ((unsigned long long)x2 << 32) | x), c = __builtin_bit_cast(double, ((unsigned long long)y2 << 32) | y);
         return a + c;
     } else {

@@ -55,6 +55,10 @@ SYMBOLS = {
     "ire_preprocess_plan": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "ire_preprocess": (_i, [_vp, _u8p, _i, _i, _i, _i, _u8p, _i, _i]),
     "ire_preprocess_device": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "ire_preprocess_batch_device": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_size_t, _i, _i, _vp, _i, _i, ctypes.c_size_t, _vp]),
+    "ire_upload_plan": (_i, [_u8p, ctypes.c_size_t, ctypes.c_uint32, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i),
+                             ctypes.POINTER(_i)]),
+    "ire_submit_upload": (_i, [_vp, _u8p, ctypes.c_size_t, _i, _vp, ctypes.POINTER(_vp)]),
     "ire_png_base64_bytes": (ctypes.c_size_t, [_i, _i]),
     "ire_encode_png_base64_device": (_i, [_vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
     "ire_encode_png_base64": (_i, [_vp, _u8p, _i, _i, _i, _u8p, ctypes.c_size_t]),

@@ -177,6 +177,10 @@ struct HipBatchBackend {
     void decode(SlotBufs& b, int first, int count, int h, int w, void* const* heads, const size_t* used) {
         HipSlot& hs = *static_cast<HipSlot*>(b.impl);
         const size_t ib = (size_t)h * w * 3;
+        decode_runs(hs, b, first, count, ib, h, w, hs.d_in.get<uint8_t>(), ib, heads, used);
+    }
+    // jobs first .. first + count - 1 of the slot, their staged bytes `place` apart in pin_in, decoded to h x w images `pitch` apart in d_rgb
+    void decode_runs(HipSlot& hs, SlotBufs& b, int first, int count, size_t place, int h, int w, uint8_t* d_rgb, size_t pitch, void* const* heads, const size_t* used) {
         if (!hs.d_fstat) {                // zeroed once: the word of a job with nothing to decode is never written
             hs.d_fstat = Buf<DeviceMem>(sizeof(int32_t) * kMaxBatch); hs.pin_fstat = Buf<PinnedMem>(sizeof(int32_t) * kMaxBatch);
             IRE_HIP(hipMemsetAsync(hs.d_fstat.get<int32_t>(), 0, sizeof(int32_t) * kMaxBatch, cs));
@@ -195,10 +199,31 @@ struct HipBatchBackend {
             const int i0 = i;
             for (; i < count && used[i]; ++i, ++n) {
                 const JpegFileHead& f = *static_cast<const JpegFileHead*>(heads[i]);
-                hd[n] = &f.hd; streams[n] = f.streams.data(); bytes[n] = b.pin_in + ib * (size_t)(first + i); room[n] = used[i];
+                hd[n] = &f.hd; streams[n] = f.streams.data(); bytes[n] = b.pin_in + place * (size_t)(first + i); room[n] = used[i];
             }
-            E.jpeg_decoder().decode_streams(hd, streams, bytes, room, n, h, w, hs.d_in.get<uint8_t>() + ib * (size_t)(first + i0), ib, hs.d_fstat.get<int32_t>() + first + i0, cs);
+            E.jpeg_decoder().decode_streams(hd, streams, bytes, room, n, h, w, d_rgb + pitch * (size_t)(first + i0), pitch, hs.d_fstat.get<int32_t>() + first + i0, cs);
         }
+    }
+    // ---- upload jobs (batcher.hpp: the optional hooks): a file job decoded at its STORED size into the engine's scratch, then oriented
+    // and fitted into the slot's device input by one batched preprocess -- all on the copy-in stream, under the previous batch's compute ----
+    std::shared_ptr<void> upload_plan(const uint8_t* file, size_t bytes, int max_dim, int* h, int* w, size_t* room, int key[4]) {
+        int sh = 0, sw = 0;
+        auto head = file_plan(file, bytes, &sh, &sw, room);
+        key[0] = sh; key[1] = sw; key[2] = jpegparse::file_orientation(file, bytes); key[3] = max_dim;
+        preprocess_plan(sw, sh, key[2], max_dim, w, h, nullptr);
+        if (!piece_addressable(Engine::fit_dim(*h), Engine::fit_dim(*w), 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(Engine::fit_dim(*h), Engine::fit_dim(*w)));
+        return head;
+    }
+    void decode_upload(SlotBufs& b, int first, int count, int h, int w, const int key[4], void* const* heads, const size_t* used) {
+        HipSlot& hs = *static_cast<HipSlot*>(b.impl);
+        const int sh = key[0], sw = key[1];
+        const size_t ib = (size_t)h * w * 3, sb = (size_t)sh * sw * 3;
+        PreprocessScratch& P = E.preprocess_uploads();
+        // the any-size staging rule (ire.h): for max_batch images while that is <= 256 MB, else for the batch at hand
+        P.d_stored.grow(sb * (size_t)(first + count), batch_room(sb * (size_t)(first + count), sb * (size_t)E.max_batch()));
+        decode_runs(hs, b, first, count, ib, sh, sw, P.d_stored.get<uint8_t>(), sb, heads, used);
+        // (a job with nothing decoded is fitted from whatever the scratch held: it fails alone, its place is never read)
+        E.preprocess_batch_device(P, P.d_stored.get<uint8_t>() + sb * (size_t)first, count, sh, sw, sb, key[2], key[3], hs.d_in.get<uint8_t>() + ib * (size_t)first, h, w, ib, cs);
     }
     int file_status(SlotBufs& b, int i) { return static_cast<HipSlot*>(b.impl)->pin_fstat.get<int32_t>()[i]; }
     void h2d(SlotBufs& b, size_t off, size_t bytes) {
@@ -452,6 +477,36 @@ int ire_preprocess_device(ire_engine* e, const uint8_t* d_rgb, int h, int w, int
     });
 }
 
+int ire_preprocess_batch_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t image_pitch_bytes, int orientation, int max_dim, uint8_t* d_out_rgb,
+                                int out_h, int out_w, size_t out_image_pitch_bytes, void* stream) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, (hipStream_t)stream, [&] {
+            E.preprocess_batch_device(E.preprocess_own(), d_rgb, n, h, w, image_pitch_bytes, orientation, max_dim, d_out_rgb, out_h, out_w, out_image_pitch_bytes, (hipStream_t)stream);
+        });
+    });
+}
+
+int ire_upload_plan(const uint8_t* file, size_t bytes, uint32_t accept, int max_dim, int* stored_h, int* stored_w, int* orientation, int* out_h, int* out_w) {
+    return guarded([&] {
+        if (!file) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_upload_plan: null file");
+        if (accept & ~(uint32_t)IRE_DECODE_ACCEPT_PROGRESSIVE) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_upload_plan: unknown accept bits");
+        jpegparse::File f;
+        std::string why;
+        if (!jpegparse::plan_file(file, bytes, accept, f, why)) fail(IRE_ERR_INVALID_INPUT, why);
+        const int o = jpegparse::file_orientation(file, bytes);
+        int ow = 0, oh = 0;
+        preprocess_plan(f.hd.im.w, f.hd.im.h, o, max_dim, &ow, &oh, nullptr);
+        if (!piece_addressable(Engine::fit_dim(oh), Engine::fit_dim(ow), 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(Engine::fit_dim(oh), Engine::fit_dim(ow)));
+        if (jpegparse::file_room(f, bytes) > (size_t)oh * ow * 3) fail(IRE_ERR_INVALID_INPUT, kUploadRoomReason);
+        if (stored_h) *stored_h = f.hd.im.h;
+        if (stored_w) *stored_w = f.hd.im.w;
+        if (orientation) *orientation = o;
+        if (out_h) *out_h = oh;
+        if (out_w) *out_w = ow;
+    });
+}
+
 size_t ire_png_base64_bytes(int h, int w) { return (h >= 1 && w >= 8 && w % 8 == 0 && h <= 16384 && w <= 16384) ? kStoredPng.bound(h, w) : 0; }
 
 int ire_encode_png_base64_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, uint8_t* d_chars, size_t stride_bytes, void* stream) {
@@ -702,6 +757,17 @@ int ire_submit_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, const doub
         *job_out = nullptr;
         std::unique_ptr<ire_job> hnd(new ire_job{});
         hnd->j = e->batcher->submit_file(file, bytes, scores);
+        *job_out = hnd.release();
+    });
+}
+
+int ire_submit_upload(ire_engine* e, const uint8_t* file, size_t bytes, int max_dim, const double* scores, ire_job** job_out) {
+    return guarded([&] {
+        eng(e);
+        if (!file || !job_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_upload");
+        *job_out = nullptr;
+        std::unique_ptr<ire_job> hnd(new ire_job{});
+        hnd->j = e->batcher->submit_upload(file, bytes, max_dim, scores);
         *job_out = hnd.release();
     });
 }

@@ -22,9 +22,11 @@
 // per restoreBatch, 5 per worker -- is about to resubmit), and when the GPU is idle after a short bounded linger: kLingerQuietUs
 // after the last arrival, at most kLingerMaxUs after the first.
 //
-// A slot gathers ONE kind of job: pixel jobs, file jobs, or fusion jobs (submit_group) of one k -- a fusion job's k views take k
-// consecutive image places, so such a slot holds max_batch / k jobs (at most kGroupMaxJobs: a full slot is ONE fused launch) and
-// closes by the same full / linger rules.
+// A slot gathers ONE kind of job: pixel jobs, file jobs, upload jobs (submit_upload) of one key, or fusion jobs (submit_group) of one
+// k -- a fusion job's k views take k consecutive image places, so such a slot holds max_batch / k jobs (at most kGroupMaxJobs: a full
+// slot is ONE fused launch) and closes by the same full / linger rules.  An upload job is a file job whose decoded image is oriented
+// and fitted on the device before the network sees it: its h, w are the FITTED size, its key (stored h, stored w, orientation,
+// max_dim) says how the backend gets there, and two keys never share a slot even where they give one fitted size.
 //
 // A job handle is used by ONE thread at a time (poll it, or release it).  A timed-out poll leaves the job pending; the caller
 // polls again or RELEASES it (the reference retries 3x on exactly this path: utils/retry.js:12-47): an abandoned job's slot
@@ -67,6 +69,7 @@ struct Job {
     double v_scores[3][7] = {};                 // ... and those scores
     std::shared_ptr<void> file;       // a file job (submit_file): what the backend's file_plan made of the file's head; its staged input is the scan, cut
     size_t file_used = 0;             // bytes of that input
+    int up[4] = {};                   // an upload job (submit_upload): stored h, stored w, orientation, max_dim; up[0] == 0: none (h, w: the fitted size)
     BatchSlot* slot = nullptr;        // where the input was staged and the output will be; null: overflow (no free slot at submit) / evicted / fetched
     int idx = -1;
     std::vector<uint8_t> in, out;     // overflow input / evicted output only
@@ -93,6 +96,7 @@ struct BatchSlot {
     std::vector<std::shared_ptr<Job>> jobs;   // index order = position in the batch
     int h = 0, w = 0;
     bool files = false;                   // gathers file jobs (never mixed with pixel jobs: their input is decoded on the device, not copied)
+    int up[4] = {};                       // gathers upload jobs of this key (files is set too); up[0] == 0: not an upload slot
     int k = 0;                            // gathers fusion jobs of k views each (never mixed with another kind or another k); 0: one image per job
     int h2d_issued = 0;                   // images whose H2D copy (file jobs: whose decode) is already on the copy-in stream
     int unread = 0, reading = 0;          // DONE: jobs that have not fetched their output yet / polls copying right now
@@ -145,11 +149,27 @@ struct has_group_launch : std::false_type {};
 template <class B>
 struct has_group_launch<B, std::void_t<decltype(std::declval<B&>().launch_group(std::declval<SlotBufs&>(), 0, 0, 0, 0, (const uint8_t*)nullptr))>> : std::true_type {};
 
+// OPTIONAL, both or none, on a backend WITH file jobs (detected at compile time; without them submit_upload does not compile): UPLOAD
+// JOBS.  file_stage and file_status serve them as they serve file jobs.
+//   std::shared_ptr<void> upload_plan(const uint8_t* file, size_t bytes, int max_dim, int* h, int* w, size_t* room, int key[4]);
+//                                                              file_plan for an upload: *h, *w = the FITTED size, key = (stored h, stored w,
+//                                                              orientation, max_dim); throws Error when the file is refused
+//   void decode_upload(SlotBufs&, int first, int count, int h, int w, const int key[4], void* const* heads, const size_t* used);
+//                                                              in place of decode: the jobs' files decoded at their stored size, oriented and
+//                                                              fitted into the slot's device input, h * w * 3 bytes per job
+template <class B, class = void>
+struct has_upload_jobs : std::false_type {};
+template <class B>
+struct has_upload_jobs<B, std::void_t<decltype(std::declval<B&>().decode_upload(std::declval<SlotBufs&>(), 0, 0, 0, 0, (const int*)nullptr, (void* const*)nullptr,
+                                                                                  (const size_t*)nullptr))>> : std::true_type {};
+
 template <class B, class = void>
 struct has_result_view : std::false_type {};
 template <class B>
 struct has_result_view<B, std::void_t<decltype(std::declval<const B&>().result_view((const uint8_t*)nullptr, 0, 0, (size_t*)nullptr))>> : std::true_type {};
 
+// the room rule of upload jobs (submit_upload; ire_upload_plan says the same of the same file)
+constexpr const char* kUploadRoomReason = "invalid: the file's entropy-coded data may be larger than its fitted pixels (decode it with the host codec)";
 constexpr int kPollTooSmall = -2;     // Batcher::poll: the caller's buffer is shorter than the result; the job stays pending
 
 template <class Backend>
@@ -225,16 +245,38 @@ class Batcher {
         auto j = std::make_shared<Job>();
         size_t room = 0;
         j->file = be_.file_plan(file, bytes, &j->h, &j->w, &room);
+        if (room > (size_t)j->h * j->w * 3) fail(IRE_ERR_INVALID_INPUT, "invalid: the file's entropy-coded data may be larger than its pixels (it stays with the host codec)");
+        stage_file_job(j, file, bytes, room, scores);
+        return j;
+    }
+
+    // Queue one encoded upload (backends with upload jobs): a file job that the backend orients by the file's EXIF tag and fits inside
+    // max_dim on the device, after the decode and before the network.  The job's h, w are the fitted size; its place in the slot's
+    // input holds h * w * 3 bytes, and a file whose cut scan may need more is refused: no job exists then.
+    template <class BE = Backend>
+    std::shared_ptr<Job> submit_upload(const uint8_t* file, size_t bytes, int max_dim, const double* scores) {
+        static_assert(has_file_jobs<BE>::value && has_upload_jobs<BE>::value, "this backend has no upload jobs");
+        auto j = std::make_shared<Job>();
+        size_t room = 0;
+        j->file = be_.upload_plan(file, bytes, max_dim, &j->h, &j->w, &room, j->up);
+        if (room > (size_t)j->h * j->w * 3)
+            fail(IRE_ERR_INVALID_INPUT, kUploadRoomReason);
+        stage_file_job(j, file, bytes, room, scores);
+        return j;
+    }
+
+  private:
+    // the rest of submit_file / submit_upload: a place for the planned job, the scan cut into it in the submitting thread
+    void stage_file_job(const std::shared_ptr<Job>& j, const uint8_t* file, size_t bytes, size_t room, const double* scores) {
         j->v_jpeg[0] = 1;
         if (scores) { std::memcpy(j->v_scores[0], scores, sizeof(double) * 7); j->v_has[0] = 1; }
         const int h = j->h, w = j->w;
         const size_t ib = (size_t)h * w * 3;
-        if (room > ib) fail(IRE_ERR_INVALID_INPUT, "invalid: the file's entropy-coded data may be larger than its pixels (it stays with the host codec)");
         uint8_t* dst = nullptr;
         {
             std::lock_guard<std::mutex> lk(mu_);
             start_locked(h, w);
-            const int si = overflow_.empty() ? slot_for(h, w, true) : -1;
+            const int si = overflow_.empty() ? slot_for(h, w, true, 0, j->up) : -1;
             if (si >= 0) { slot_add(si, j); dst = slots_[si].b.pin_in + ib * j->idx; }
         }
         size_t used = 0;
@@ -254,9 +296,9 @@ class Batcher {
             j->staged = true;
         }
         qcv_.notify_all();
-        return j;
     }
 
+  public:
     // Queue one fusion job (backends with the group launch): k = 2..3 views of h x w.  All k views are staged HERE, in the submitting
     // thread: one copy each into the job's k consecutive places of the pinned slot (or into the job's own vector on the overflow
     // path).  is_jpeg / has_scores: [k] or null (all JPEG / none supplied); scores: [k][7], read where has_scores says so.
@@ -387,11 +429,13 @@ class Batcher {
     // (mu_ held) an OPEN slot of this shape with room, else a FREE one opened for it, else -1.  May allocate staging (first use
     // of a shape: once).  A DONE slot nobody is reading is evicted when nothing else is left: its unfetched outputs move to
     // their jobs' own vectors (the extra copy only a caller that lets a slot's worth of batches pile up unpolled ever pays).
-    int slot_for(int h, int w, bool files = false, int k = 0) {
+    int slot_for(int h, int w, bool files = false, int k = 0, const int* up = nullptr) {
+        static const int none[4] = {};
+        if (!up) up = none;
         const int mb = be_.max_batch();
         for (auto it = open_order_.rbegin(); it != open_order_.rend(); ++it) {
             BatchSlot& S = slots_[*it];
-            if (S.h == h && S.w == w && S.files == files && S.k == k && (int)S.jobs.size() < capacity(S)) return *it;
+            if (S.h == h && S.w == w && S.files == files && S.k == k && !std::memcmp(S.up, up, sizeof(S.up)) && (int)S.jobs.size() < capacity(S)) return *it;
         }
         int pick = -1;
         const size_t need = std::max((size_t)h * w * 3, be_.out_bytes(h, w)) * (size_t)mb;
@@ -415,7 +459,7 @@ class Batcher {
         if (pick < 0) return -1;
         BatchSlot& S = slots_[pick];
         be_.reserve(S.b, need, mb);               // strong guarantee: a throw leaves the slot FREE with what it had
-        S.state = BatchSlot::OPEN; S.h = h; S.w = w; S.files = files; S.k = k; S.jobs.clear(); S.h2d_issued = 0; S.unread = S.reading = 0;
+        S.state = BatchSlot::OPEN; S.h = h; S.w = w; S.files = files; S.k = k; std::memcpy(S.up, up, sizeof(S.up)); S.jobs.clear(); S.h2d_issued = 0; S.unread = S.reading = 0;
         S.status = IRE_OK; S.err.clear();
         S.first_arrival = S.last_arrival = clk::now();
         open_order_.push_back(pick);
@@ -475,8 +519,12 @@ class Batcher {
             size_t used[kMaxBatch];
             const int first = S.h2d_issued, count = upto - first, h = S.h, w = S.w;
             for (int i = 0; i < count; ++i) { heads[i] = S.jobs[first + i]->file.get(); used[i] = S.jobs[first + i]->file_used; }
+            int up[4];
+            std::memcpy(up, S.up, sizeof(up));
             lk.unlock();
-            be_.decode(S.b, first, count, h, w, heads, used);
+            if (!up[0]) be_.decode(S.b, first, count, h, w, heads, used);
+            else if constexpr (has_upload_jobs<BE>::value) be_.decode_upload(S.b, first, count, h, w, up, heads, used);
+            else fail(IRE_ERR_INTERNAL, "internal: an upload slot on a backend without upload jobs");
             lk.lock();
         } else fail(IRE_ERR_INTERNAL, "internal: a file slot on a backend without file jobs");
     }
@@ -526,7 +574,7 @@ class Batcher {
             while (!overflow_.empty()) {
                 std::shared_ptr<Job> j = overflow_.front();
                 int si = -1;
-                try { si = slot_for(j->h, j->w, j->file != nullptr, j->views); }
+                try { si = slot_for(j->h, j->w, j->file != nullptr, j->views, j->up); }
                 catch (const Error& e) { fail_job(*j, e.code, e.msg); overflow_.pop_front(); dcv_.notify_all(); continue; }
                 catch (const std::exception& e) {      // bad_alloc while evicting a DONE slot: this job fails, the service thread lives
                     fail_job(*j, IRE_ERR_UNAVAILABLE, std::string("service unavailable: ") + e.what()); overflow_.pop_front(); dcv_.notify_all(); continue;

@@ -120,6 +120,28 @@ struct Geo {
     uint8_t* img_out = nullptr;       // u8 output rows of the piece (no halo)
 };
 
+// ---- what the batched preprocess (preprocess.hip) keeps between calls ----
+// the tap table of one (in_size, out_size) pair on the device: bounds [out][2] (first, count) and behind them taps [out][ksize]
+struct TapTable {
+    int in = 0, out = 0, ksize = 0;
+    int span = 0;                     // the most input pixels the taps of 32 consecutive outputs cover (the tiled kernel's LDS rows)
+    uint64_t used = 0;                // LRU stamp; 0: empty
+    Buf<DeviceMem> d;
+    const int32_t* bounds() const { return d.get<int32_t>(); }
+    const int32_t* taps() const { return d.get<int32_t>() + 2 * (size_t)out; }
+};
+// One user at a time: the engine's own entry (under the engine's lock) and the batcher's upload jobs (its launcher thread, always on
+// the copy-in stream) each have their own, as the JPEG decoder's two users do.
+struct PreprocessScratch {
+    static constexpr int kTables = 16;
+    TapTable tab[kTables];
+    uint64_t clock = 0;
+    Buf<DeviceMem> d_mid;             // the horizontal pass's output, [n][upright h][pitch]
+    Buf<DeviceMem> d_stored;          // upload jobs: the decoded stored images of a batch, [n][sh][sw][3]
+    // the pair's table, built and uploaded on its first use (the host then waits for the upload on s); later uses touch no stream
+    const TapTable& table(int in_size, int out_size, hipStream_t s);
+};
+
 struct ProfRec {
     int fam;
     bool own_e0 = true;   // false: e0 is the previous record's e1 (back-to-back profiled launches share the event)
@@ -182,6 +204,12 @@ public:
     void preprocess_device(const uint8_t* d_rgb, int h, int w, int orientation, int max_dim, uint8_t* d_out, int out_h, int out_w,
                            hipStream_t s);
     void preprocess_host(const uint8_t* rgb, int h, int w, int orientation, int max_dim, uint8_t* out, int out_h, int out_w);
+    // n <= max_batch images of ONE stored size and orientation, image_pitch apart -> n upright fitted images out_pitch apart: image i
+    // is byte for byte preprocess_device's.  Two launches whatever n; no host wait once both tap tables are cached.  P: whose scratch.
+    void preprocess_batch_device(PreprocessScratch& P, const uint8_t* d_rgb, int n, int h, int w, size_t image_pitch, int orientation, int max_dim, uint8_t* d_out,
+                                 int out_h, int out_w, size_t out_pitch, hipStream_t s);
+    PreprocessScratch& preprocess_own() { return pp_own_; }         // the engine's own entries
+    PreprocessScratch& preprocess_uploads() { return pp_uploads_; } // the batcher's upload jobs
     // Any-size jobs (h, w in 1..8192): edge-replicate pad to (max(16, ceil8 h), max(16, ceil8 w)) into the engine's padded
     // staging, the network on the padded shape, the top-left h x w window as the result.  The classifier always sees the
     // ORIGINAL pixels.  A shape restore_device takes as it is skips the pad and runs exactly as restore_device does.
@@ -297,6 +325,7 @@ private:
     FuseBufs<DeviceMem> fuse_;            // fusion scratch
     Buf<DeviceMem> d_zero_;               // 256 bytes of zeros (conv_upq.hip's zero padding source)
     Buf<DeviceMem> d_pp_tab_, d_pp_mid_, d_pp_in_, d_pp_out_;   // preprocess scratch (tap tables, intermediate of the horizontal pass, host-path staging)
+    PreprocessScratch pp_own_, pp_uploads_;
     Buf<DeviceMem> d_pad_in_, d_pad_out_; // any-size jobs: the edge-padded batch in front of the network, and the network's output on the padded shape
     Buf<DeviceMem> d_fuse_in_, d_fuse_out_;   // fusion jobs: the restored windows padded to the fusion shape [n][HF][WF][3], the fused images [sets][HF][WF][3]
     Buf<DeviceMem> d_fuse_sc_;            // ... and the classifier's scores of view 0 of every padded set, [kFuseMaxSets][7] (never io_.scores: those are the jobs')

@@ -9,7 +9,7 @@
 // libjpeg reads as Y Cb Cr (a JFIF marker, or ids 1 2 3; no Adobe marker) with luma 1x1, 2x1 or 2x2 and chroma 1x1 (width >= 5 when
 // subsampled: below that libjpeg's fancy upsampler switches to replication), or one grey component.  Everything else is refused
 // with a reason; the caller then uses the host codec.  head_file / plan_file accept progressive files (SOF2) beside these when asked
-// to: see there.
+// to: see there.  exif_orientation / file_orientation read an upload's EXIF orientation (upload jobs); a broken block is orientation 1, never a refusal.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -473,6 +473,53 @@ inline bool head_file(const uint8_t* file, size_t bytes, uint32_t accept, File& 
 inline bool plan_file(const uint8_t* file, size_t bytes, uint32_t accept, File& f, std::string& why) {
     return head_file(file, bytes, accept, f, why) && (f.progressive || split_scan(f.hd, file, bytes, nullptr, 0, nullptr, why));
 }
+// ---- EXIF orientation ----------------------------------------------------------------------------------------------------------------
+// The payload of an APP1 segment (behind its length) -> the orientation its IFD0 names: tag 0x0112 of type SHORT, count 1, value 1..8.
+// 0: the payload is not an Exif block (the walk goes on to the next APP1).  Everything else that is not exactly that -- a TIFF header
+// that is none, an offset or an entry outside the payload, another type or count, a value outside 1..8 -- is 1: an upload with a broken
+// EXIF block is an upright upload, never a refused one.  No read leaves p[0 .. n).
+inline int exif_orientation(const uint8_t* p, size_t n) {
+    if (n < 6 || std::memcmp(p, "Exif\0\0", 6) != 0) return 0;
+    const uint8_t* t = p + 6;                                      // the TIFF header: offsets count from here
+    const size_t m = n - 6;
+    if (m < 8) return 1;
+    bool le;
+    if (t[0] == 'I' && t[1] == 'I') le = true; else if (t[0] == 'M' && t[1] == 'M') le = false; else return 1;
+    auto r16 = [&](size_t o) -> uint32_t { return le ? (uint32_t)t[o] | (uint32_t)t[o + 1] << 8 : (uint32_t)t[o] << 8 | t[o + 1]; };      // callers checked o + 2 <= m
+    auto r32 = [&](size_t o) -> uint32_t { return le ? r16(o) | r16(o + 2) << 16 : r16(o) << 16 | r16(o + 2); };
+    if (r16(2) != 42) return 1;
+    const size_t ifd = r32(4);
+    if (ifd > m || m - ifd < 2) return 1;
+    const uint32_t entries = r16(ifd);
+    for (uint32_t k = 0; k < entries; ++k) {
+        const size_t e = ifd + 2 + 12 * (size_t)k;
+        if (e > m || m - e < 12) return 1;
+        if (r16(e) != 0x0112) continue;
+        if (r16(e + 2) != 3 || r32(e + 4) != 1) return 1;
+        const uint32_t v = r16(e + 8);
+        return v >= 1 && v <= 8 ? (int)v : 1;
+    }
+    return 1;
+}
+// the orientation of a file: that of its first APP1 segment in front of the scan that is an Exif block; 1 when there is none or the
+// markers cannot be walked (the planner decides about such a file, not this)
+inline int file_orientation(const uint8_t* file, size_t bytes) {
+    if (!file || bytes < 4 || file[0] != 0xFF || file[1] != 0xD8) return 1;
+    size_t i = 2;
+    while (i + 4 <= bytes) {
+        if (file[i] != 0xFF) return 1;
+        while (i < bytes && file[i] == 0xFF) ++i;
+        if (i + 2 >= bytes) return 1;
+        const unsigned b = file[i++];
+        if (b == 0xDA || b == 0xD9 || b == 0xD8 || b == 0x00 || b == 0x01 || (b >= 0xD0 && b <= 0xD7)) return 1;
+        const size_t len = (size_t)file[i] << 8 | file[i + 1];
+        if (len < 2 || len > bytes - i) return 1;
+        if (b == 0xE1) { const int o = exif_orientation(file + i + 2, len - 2); if (o) return o; }
+        i += len;
+    }
+    return 1;
+}
+
 // bytes the streams of this file need at most in the staging area (each stream starts on a multiple of 4)
 inline size_t file_room(const File& f, size_t bytes) { return f.progressive ? f.data_bytes + 4 * (size_t)f.nstreams + 8 : scan_room(f.hd, bytes); }
 // every scan cut, in file order: the streams' bytes to dst (dst == null: only check), their records to streams[0 .. f.nstreams)

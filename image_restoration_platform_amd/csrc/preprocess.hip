@@ -9,9 +9,13 @@
 //
 // Both kernels are HBM-bound byte work (read each stored pixel once, write the intermediate once, read it once, write
 // the result): a thread produces one output pixel (3 bytes) from <= ksize taps; the orientation is folded into the
-// horizontal pass's reads, so there is no separate transpose pass.
+// horizontal pass's reads, so there is no separate transpose pass.  That is the single-image entry (preprocess_device), kept as it was.
+//
+// The batched entry (preprocess_batch_device, upload jobs) computes the same bytes from tiles staged in LDS -- stored pixels are read along
+// stored rows for every orientation -- with the image index as a grid dimension and the tap tables cached on the device: further down.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <vector>
@@ -123,6 +127,150 @@ __global__ __launch_bounds__(256) void orient_kernel(const uint8_t* __restrict__
     o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
 }
 
+// ---- the batched form (Engine::preprocess_batch_device): blockIdx.z = the image -------------------------------------------------------
+// Both tiled kernels work on a tile of the UPRIGHT image, kTY rows high, staged in LDS as lds[x][y][3] with a row pitch of kP bytes
+// (25 words, odd: the rows of consecutive x fall on different banks).  The loader is the only code that knows the orientation: it
+// always walks the STORED image along its rows -- orientations 1..4 (upright x = stored column) in runs of the tile's width,
+// orientations 5..8 (upright x = stored row) in runs of kTY pixels -- and writes LDS transposed where the upright image is.
+// flip_a: the stored coordinate that upright x becomes runs backwards; flip_b: the one upright y becomes.
+constexpr int kTX = 32, kTY = 32, kP = kTY * 3 + 4;
+constexpr size_t kTileLdsMax = 64 * 1024;      // the tiled horizontal pass's LDS per workgroup at most (the scale switch)
+
+template <bool SWAP>
+__device__ __forceinline__ void load_tile(uint8_t* lds, const uint8_t* __restrict__ img, int sh, int sw, int flip_a, int flip_b, int xb, int nx, int y0, int uh) {
+    const int tid = threadIdx.x;
+    if (SWAP) {
+        const int ny = min(kTY, uh - y0);
+        for (int i = tid; i < nx * (kTY * 3); i += 256) {
+            const int xr = i / (kTY * 3), j = i - xr * (kTY * 3), ty = j / 3, c = j - ty * 3;
+            if (ty >= ny) continue;
+            const int r = flip_a ? sh - 1 - (xb + xr) : xb + xr, col = flip_b ? sw - 1 - (y0 + ty) : y0 + ty;
+            lds[xr * kP + j] = img[((size_t)r * sw + col) * 3 + c];
+        }
+    } else {
+        const int wave = tid >> 6, lane = tid & 63;
+        for (int ty = wave; ty < kTY && y0 + ty < uh; ty += 4) {
+            const int r = flip_b ? sh - 1 - (y0 + ty) : y0 + ty;
+            const uint8_t* row = img + (size_t)r * sw * 3;
+            for (int j = lane; j < nx * 3; j += 64) {
+                const int xr = j / 3, c = j - xr * 3;
+                const int col = flip_a ? sw - 1 - (xb + xr) : xb + xr;
+                lds[xr * kP + ty * 3 + c] = row[col * 3 + c];
+            }
+        }
+    }
+}
+
+// horizontal pass, tiled: a workgroup makes kTY rows x kTX columns of the intermediate.  A thread makes one output column of four
+// consecutive rows: their 12 bytes lie side by side in a row of the tile (three word reads per tap, one tap load for all four pixels).
+// The results go back through LDS, where the tile was, and leave as whole words along the intermediate's rows (its row pitch mp is a
+// multiple of 4; a row's last word may reach into that padding).  span: the LDS rows the launch reserved.
+template <bool SWAP>
+__global__ __launch_bounds__(256) void resample_h_tiled_kernel(const uint8_t* __restrict__ src, size_t image_pitch, int sh, int sw, int flip_a, int flip_b, int uh,
+                                                               int ow, int ksize, const int32_t* __restrict__ bounds, const int32_t* __restrict__ taps,
+                                                               uint8_t* __restrict__ mid, int mp, int span) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int xx0 = blockIdx.x * kTX, y0 = blockIdx.y * kTY, xl = min(xx0 + kTX, ow) - 1;
+    const int xb = bounds[2 * xx0], nx = min(bounds[2 * xl] + bounds[2 * xl + 1] - xb, span);      // (first and count grow with the output index)
+    load_tile<SWAP>(lds, src + blockIdx.z * image_pitch, sh, sw, flip_a, flip_b, xb, nx, y0, uh);
+    __syncthreads();
+    const int xi = threadIdx.x & 31, xx = xx0 + xi, g = threadIdx.x >> 5;      // rows y0 + 4 g .. + 3 (rows past the image hold whatever LDS held: computed, never stored)
+    int acc[12];
+    for (int q = 0; q < 12; ++q) acc[q] = 1 << (kPrecisionBits - 1);
+    if (xx < ow) {
+        const int n = bounds[2 * xx + 1];
+        const uint32_t* v = reinterpret_cast<const uint32_t*>(lds + (bounds[2 * xx] - xb) * kP + 12 * g);
+        const int32_t* k = taps + (size_t)xx * ksize;
+        for (int t = 0; t < n; ++t, v += kP / 4) {
+            const int kv = k[t];
+            for (int q = 0; q < 3; ++q) {
+                const uint32_t w = v[q];
+                acc[4 * q] += (int)(w & 255u) * kv; acc[4 * q + 1] += (int)(w >> 8 & 255u) * kv; acc[4 * q + 2] += (int)(w >> 16 & 255u) * kv; acc[4 * q + 3] += (int)(w >> 24) * kv;
+            }
+        }
+    }
+    __syncthreads();      // every thread is done with the tile: its place takes the results, as kTY rows of kTX pixels
+    if (xx < ow)
+        for (int q = 0; q < 12; ++q) lds[(4 * g + q / 3) * (kTX * 3) + xi * 3 + q % 3] = (uint8_t)clip8(acc[q]);
+    __syncthreads();
+    const int nb = (xl + 1 - xx0) * 3, ny = min(kTY, uh - y0);
+    for (int i = threadIdx.x; i < ny * (kTX * 3 / 4); i += 256) {
+        const int ty = i / (kTX * 3 / 4), j = (i - ty * (kTX * 3 / 4)) * 4;
+        if (j < nb) *reinterpret_cast<uint32_t*>(mid + ((size_t)blockIdx.z * uh + y0 + ty) * mp + (size_t)xx0 * 3 + j) = *reinterpret_cast<const uint32_t*>(lds + ty * (kTX * 3) + j);
+    }
+}
+
+// horizontal pass for scales whose tile does not fit in LDS: resample_h_kernel per image (a thread gathers its own taps)
+__global__ __launch_bounds__(256) void resample_h_strip_kernel(const uint8_t* __restrict__ src, size_t image_pitch, int sh, int sw, int orientation, int uh, int ow,
+                                                               int ksize, const int32_t* __restrict__ bounds, const int32_t* __restrict__ taps,
+                                                               uint8_t* __restrict__ mid, int mp) {
+    const int xx = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (xx >= ow || y >= uh) return;
+    const uint8_t* img = src + blockIdx.z * image_pitch;
+    const int x0 = bounds[2 * xx], n = bounds[2 * xx + 1];
+    const int32_t* k = taps + (size_t)xx * ksize;
+    int r = 1 << (kPrecisionBits - 1), g = r, b = r;
+    for (int t = 0; t < n; ++t) {
+        const uint8_t* p = img + stored_index(orientation, y, x0 + t, sh, sw) * 3;
+        const int kv = k[t];
+        r += p[0] * kv; g += p[1] * kv; b += p[2] * kv;
+    }
+    uint8_t* o = mid + ((size_t)blockIdx.z * uh + y) * mp + (size_t)xx * 3;
+    o[0] = (uint8_t)clip8(r); o[1] = (uint8_t)clip8(g); o[2] = (uint8_t)clip8(b);
+}
+
+// vertical pass: a thread makes four consecutive bytes of an output row from one word per tap (the taps are the row's: uniform loads);
+// words: the output rows are word-aligned (3 * ow, the image pitch and the base are multiples of 4), so the four bytes leave as one word
+__global__ __launch_bounds__(256) void resample_v_batch_kernel(const uint8_t* __restrict__ mid, int uh, int mp, int ow3, int ksize,
+                                                               const int32_t* __restrict__ bounds, const int32_t* __restrict__ taps, uint8_t* __restrict__ dst,
+                                                               size_t out_pitch, int words) {
+    const int i = (blockIdx.x * blockDim.x + threadIdx.x) * 4, yy = blockIdx.y;
+    if (i >= ow3) return;
+    const int y0 = bounds[2 * yy], n = bounds[2 * yy + 1];
+    const int32_t* k = taps + (size_t)yy * ksize;
+    const uint8_t* col = mid + ((size_t)blockIdx.z * uh + y0) * mp + i;
+    int a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0, a3 = a0;
+    for (int t = 0; t < n; ++t, col += mp) {
+        const uint32_t v = *reinterpret_cast<const uint32_t*>(col);
+        const int kv = k[t];
+        a0 += (int)(v & 255u) * kv; a1 += (int)(v >> 8 & 255u) * kv; a2 += (int)(v >> 16 & 255u) * kv; a3 += (int)(v >> 24) * kv;
+    }
+    uint8_t* o = dst + blockIdx.z * out_pitch + (size_t)yy * ow3 + i;
+    const uint32_t b0 = (uint32_t)clip8(a0), b1 = (uint32_t)clip8(a1), b2 = (uint32_t)clip8(a2), b3 = (uint32_t)clip8(a3);
+    if (words) *reinterpret_cast<uint32_t*>(o) = b0 | b1 << 8 | b2 << 16 | b3 << 24;
+    else {
+        o[0] = (uint8_t)b0;
+        if (i + 1 < ow3) o[1] = (uint8_t)b1;
+        if (i + 2 < ow3) o[2] = (uint8_t)b2;
+        if (i + 3 < ow3) o[3] = (uint8_t)b3;
+    }
+}
+
+// orientation only: a kTY x kTX tile of the upright image through LDS -- stored rows in, upright rows out, whole words where `words`
+template <bool SWAP>
+__global__ __launch_bounds__(256) void orient_tiled_kernel(const uint8_t* __restrict__ src, size_t image_pitch, int sh, int sw, int flip_a, int flip_b, int uh, int uw,
+                                                           uint8_t* __restrict__ dst, size_t out_pitch, int words) {
+    __shared__ uint8_t lds[kTX * kP];
+    const int x0 = blockIdx.x * kTX, y0 = blockIdx.y * kTY, nx = min(kTX, uw - x0), ny = min(kTY, uh - y0);
+    load_tile<SWAP>(lds, src + blockIdx.z * image_pitch, sh, sw, flip_a, flip_b, x0, nx, y0, uh);
+    __syncthreads();
+    uint8_t* out = dst + blockIdx.z * out_pitch + ((size_t)y0 * uw + x0) * 3;
+    if (words) {          // 3 * uw is a multiple of 4, so is 3 * x0 = 96 * blockIdx.x, so is 3 * nx
+        for (int i = threadIdx.x; i < ny * (kTX * 3 / 4); i += 256) {
+            const int ty = i / (kTX * 3 / 4), j = (i - ty * (kTX * 3 / 4)) * 4;
+            if (j >= nx * 3) continue;
+            uint32_t v = 0;
+            for (int q = 0; q < 4; ++q) v |= (uint32_t)lds[(j + q) / 3 * kP + ty * 3 + (j + q) % 3] << (8 * q);
+            *reinterpret_cast<uint32_t*>(out + (size_t)ty * uw * 3 + j) = v;
+        }
+    } else {
+        for (int i = threadIdx.x; i < ny * (kTX * 3); i += 256) {
+            const int ty = i / (kTX * 3), j = i - ty * (kTX * 3);
+            if (j < nx * 3) out[(size_t)ty * uw * 3 + j] = lds[j / 3 * kP + ty * 3 + j % 3];
+        }
+    }
+}
+
 long js_round(double x) { return (long)std::floor(x + 0.5); }
 
 }  // namespace
@@ -183,6 +331,72 @@ void Engine::preprocess_device(const uint8_t* d_rgb, int h, int w, int orientati
                        d_th, d_pp_mid_.get<uint8_t>());
     hipLaunchKernelGGL(resample_v_kernel, dim3((out_w * 3 + 255) / 256, out_h), dim3(256), 0, s, d_pp_mid_.get<uint8_t>(), out_w, out_h, kv, d_bv, d_tv,
                        d_out);
+    IRE_HIP(hipGetLastError());
+}
+
+// The taps are built here, in double precision, by the same make_taps (the device's sin would not round the same).  A miss may
+// replace the pair used longest ago: kernels of earlier calls may still read that table, so the device is idle before it is freed.
+const TapTable& PreprocessScratch::table(int in_size, int out_size, hipStream_t s) {
+    TapTable* lru = &tab[0];
+    for (TapTable& t : tab) {
+        if (t.used && t.in == in_size && t.out == out_size) { t.used = ++clock; return t; }
+        if (t.used < lru->used) lru = &t;
+    }
+    std::vector<int32_t> bounds, taps;
+    const int ksize = make_taps(in_size, out_size, bounds, taps);
+    int span = 1;
+    for (int x0 = 0; x0 < out_size; x0 += kTX) {
+        int lo = in_size, hi = 0;
+        for (int x = x0; x < out_size && x < x0 + kTX; ++x) { lo = std::min(lo, bounds[2 * x]); hi = std::max(hi, bounds[2 * x] + bounds[2 * x + 1]); }
+        span = std::max(span, hi - lo);
+    }
+    if (lru->used) { IRE_HIP(hipDeviceSynchronize()); lru->used = 0; lru->d.reset(); }
+    lru->d = Buf<DeviceMem>((bounds.size() + taps.size()) * sizeof(int32_t));
+    IRE_HIP(hipMemcpyAsync(lru->d.get<int32_t>(), bounds.data(), bounds.size() * 4, hipMemcpyHostToDevice, s));
+    IRE_HIP(hipMemcpyAsync(lru->d.get<int32_t>() + bounds.size(), taps.data(), taps.size() * 4, hipMemcpyHostToDevice, s));
+    IRE_HIP(hipStreamSynchronize(s));      // the vectors die at return: the one wait of a pair's first use
+    lru->in = in_size; lru->out = out_size; lru->ksize = ksize; lru->span = span; lru->used = ++clock;
+    return *lru;
+}
+
+void Engine::preprocess_batch_device(PreprocessScratch& P, const uint8_t* d_rgb, int n, int h, int w, size_t image_pitch, int orientation, int max_dim,
+                                     uint8_t* d_out, int out_h, int out_w, size_t out_pitch, hipStream_t s) {
+    int pw = 0, ph = 0, resized = 0;
+    preprocess_plan(w, h, orientation, max_dim, &pw, &ph, &resized);
+    if (pw != out_w || ph != out_h) fail(IRE_ERR_INVALID_INPUT, "invalid output size for preprocess: use ire_preprocess_plan");
+    if (!d_rgb || !d_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to preprocess: null buffer");
+    if (n < 1 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid batch size for preprocess: expected 1..max_batch");
+    if (h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size: height and width must be in 1..8192");
+    const size_t in_bytes = (size_t)h * w * 3, out_bytes = (size_t)out_h * out_w * 3;
+    if (image_pitch < in_bytes || out_pitch < out_bytes) fail(IRE_ERR_INVALID_INPUT, "invalid image pitch for preprocess: smaller than an image");
+    const bool swap = orientation >= 5;
+    const int uw = swap ? h : w, uh = swap ? w : h;
+    const int flip_a = swap ? (orientation == 6 || orientation == 7) : (orientation == 2 || orientation == 3);
+    const int flip_b = swap ? (orientation == 7 || orientation == 8) : (orientation == 3 || orientation == 4);
+    const bool aligned = out_pitch % 4 == 0 && (uintptr_t)d_out % 4 == 0 && (size_t)out_w * 3 % 4 == 0;
+    if (!resized) {
+        if (orientation == 1) { IRE_HIP(hipMemcpy2DAsync(d_out, out_pitch, d_rgb, image_pitch, in_bytes, (size_t)n, hipMemcpyDeviceToDevice, s)); return; }
+        const dim3 grid((uw + kTX - 1) / kTX, (uh + kTY - 1) / kTY, n);
+        if (swap) hipLaunchKernelGGL(orient_tiled_kernel<true>, grid, dim3(256), 0, s, d_rgb, image_pitch, h, w, flip_a, flip_b, uh, uw, d_out, out_pitch, (int)aligned);
+        else hipLaunchKernelGGL(orient_tiled_kernel<false>, grid, dim3(256), 0, s, d_rgb, image_pitch, h, w, flip_a, flip_b, uh, uw, d_out, out_pitch, (int)aligned);
+        IRE_HIP(hipGetLastError());
+        return;
+    }
+    const TapTable& H = P.table(uw, out_w, s);
+    const TapTable& V = P.table(uh, out_h, s);      // (H was stamped just now: a miss here replaces another pair)
+    const int mp = (out_w * 3 + 3) & ~3;
+    const size_t per = (size_t)uh * mp;
+    P.d_mid.grow(per * n, batch_room(per * n, per * max_batch_));
+    uint8_t* mid = P.d_mid.get<uint8_t>();
+    const size_t tile = (size_t)H.span * kP, lds = std::max(tile, (size_t)kTY * kTX * 3);      // the tile; the results pass through the same place
+    if (tile <= kTileLdsMax) {
+        const dim3 grid((out_w + kTX - 1) / kTX, (uh + kTY - 1) / kTY, n);
+        if (swap) hipLaunchKernelGGL(resample_h_tiled_kernel<true>, grid, dim3(256), lds, s, d_rgb, image_pitch, h, w, flip_a, flip_b, uh, out_w, H.ksize, H.bounds(), H.taps(), mid, mp, H.span);
+        else hipLaunchKernelGGL(resample_h_tiled_kernel<false>, grid, dim3(256), lds, s, d_rgb, image_pitch, h, w, flip_a, flip_b, uh, out_w, H.ksize, H.bounds(), H.taps(), mid, mp, H.span);
+    } else
+        hipLaunchKernelGGL(resample_h_strip_kernel, dim3((out_w + 255) / 256, uh, n), dim3(256), 0, s, d_rgb, image_pitch, h, w, orientation, uh, out_w, H.ksize, H.bounds(), H.taps(), mid, mp);
+    hipLaunchKernelGGL(resample_v_batch_kernel, dim3((mp / 4 + 255) / 256, out_h, n), dim3(256), 0, s, mid, uh, mp, out_w * 3, V.ksize, V.bounds(), V.taps(), d_out, out_pitch,
+                       (int)aligned);
     IRE_HIP(hipGetLastError());
 }
 

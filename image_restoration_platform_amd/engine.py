@@ -59,6 +59,16 @@ def _jpeg_frame_size(data):
         i += 1 + n
 
 
+def upload_plan_reason(data, max_dim=2048, accept=0):
+    """bytes of a JPEG upload -> ((stored_h, stored_w, orientation, out_h, out_w), None): what submit_upload does with it on an engine
+    whose decoder accepts `accept` -- or (None, reason) when the file is refused.  ire_upload_plan: pure host, no engine, no GPU."""
+    data = bytes(data)
+    v = [ctypes.c_int() for _ in range(5)]
+    if _lib.load().ire_upload_plan(data, len(data), int(accept), int(max_dim), *[ctypes.byref(x) for x in v]) != 0:
+        return None, (_lib.load().ire_last_error() or b"").decode()
+    return tuple(x.value for x in v), None
+
+
 class Engine:
     def __init__(self, device_index=0, max_batch=8, num_streams=0, weights_path="default", seed=0, flags=0, precision="bf16"):
         self._lib = _lib.load()
@@ -200,6 +210,43 @@ class Engine:
         self._check(self._lib.ire_preprocess_device(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), h, w, int(orientation), int(max_dim),
                                                     ctypes.c_void_p(out.data_ptr()), oh, ow, self._stream_ptr(stream)))
         return out
+
+    def preprocess_batch(self, rgb_u8, orientation=1, max_dim=2048, out_u8=None, stream=None):
+        """cuda uint8 [N,h,w,3] stored images of one size and orientation (N <= max_batch; each image dense, the images any stride
+        apart: a view [:, :h*w*3] of a wider [N,pitch] buffer reshaped is fine) -> cuda uint8 [N,out_h,out_w,3] upright fitted images,
+        image i byte for byte preprocess_tensor's.  Asynchronous on the torch stream; two launches whatever N.  out_u8: where the
+        result goes (same rules: dense images, any stride between them; nothing between them is written)."""
+        import torch
+        assert rgb_u8.is_cuda and rgb_u8.dtype == torch.uint8 and rgb_u8.dim() == 4 and rgb_u8.shape[3] == 3 and rgb_u8[0].is_contiguous()
+        n, h, w, _ = rgb_u8.shape
+        ow, oh, _ = self.preprocess_plan(w, h, orientation, max_dim)
+        if out_u8 is None:
+            out_u8 = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=rgb_u8.device)
+        assert out_u8.is_cuda and out_u8.dtype == torch.uint8 and tuple(out_u8.shape) == (n, oh, ow, 3) and out_u8[0].is_contiguous()
+        self._check(self._lib.ire_preprocess_batch_device(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), n, h, w, rgb_u8.stride(0) if n > 1 else h * w * 3,
+                                                          int(orientation), int(max_dim), ctypes.c_void_p(out_u8.data_ptr()), oh, ow,
+                                                          out_u8.stride(0) if n > 1 else oh * ow * 3, self._stream_ptr(stream)))
+        return out_u8
+
+    def upload_plan(self, data, max_dim=2048):
+        """(stored_h, stored_w, orientation, out_h, out_w) of a JPEG upload as THIS engine's submit_upload takes it; raises EngineError
+        (invalid input, the plan's reason) for a file it refuses.  Pure host arithmetic."""
+        plan, why = upload_plan_reason(data, max_dim, self.decode_accept)
+        if plan is None:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, why)
+        return plan
+
+    def submit_upload(self, data, max_dim=2048, scores=None):
+        """Queue one JPEG upload as its bytes: decoded, turned upright by its EXIF orientation, fitted inside max_dim (Lanczos-3) and
+        restored, all on the device with its batch.  The result is that of submit_fit(preprocess(decode_jpeg(data), orientation,
+        max_dim), is_jpeg=True, scores), of the fitted size upload_plan reports.  Raises EngineError (invalid input) for a file the plan
+        refuses: no job exists then.  A file with corrupt data fails at its poll."""
+        data = bytes(data)
+        sc = None if scores is None else np.ascontiguousarray(np.asarray(scores, dtype=np.float64).reshape(7))
+        job = ctypes.c_void_p()
+        self._check(self._lib.ire_submit_upload(self._h, data, len(data), int(max_dim), _ptr(sc), ctypes.byref(job)))
+        _, _, _, oh, ow = upload_plan_reason(data, max_dim, self.decode_accept)[0]
+        return (job, oh, ow)
 
     def submit(self, rgb, is_jpeg=True, scores=None):
         """Queue one image with the engine's batcher (in-flight jobs of one shape coalesce into engine batches);

@@ -39,6 +39,9 @@ export function bindIre(libPath) {
     ire_encode_png_base64_fit: ['int', [P, P, 'int', 'int', 'int', P, 'size_t']],
     ire_submit_fit: ['int', [P, P, 'int', 'int', 'int', P, PP]],
     ire_submit_jpeg: ['int', [P, P, 'size_t', P, PP]],
+    ire_submit_upload: ['int', [P, P, 'size_t', 'int', P, PP]],
+    ire_upload_plan: ['int', [P, 'size_t', 'int', 'int', P, P, P, P, P]],
+    ire_preprocess_batch_device: ['int', [P, P, 'int', 'int', 'int', 'size_t', 'int', 'int', P, 'int', 'int', 'size_t', P]],
     ire_submit_fuse_fit: ['int', [P, P, 'int', 'int', 'int', P, P, P, PP]],
     ire_restore_fuse_fit_device: ['int', [P, P, 'int', 'int', 'int', 'int', P, P, P, P]],
     ire_submit: ['int', [P, P, 'int', 'int', 'int', P, PP]],

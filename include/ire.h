@@ -164,6 +164,18 @@ int ire_preprocess(ire_engine* e, const uint8_t* rgb, int h, int w, int orientat
                    uint8_t* out_rgb, int out_h, int out_w);
 int ire_preprocess_device(ire_engine* e, const uint8_t* d_rgb, int h, int w, int orientation, int max_dim,
                           uint8_t* d_out_rgb, int out_h, int out_w, void* stream);
+/* The batched, asynchronous form: n <= max_batch images of ONE stored size (h x w) and one orientation, image i at d_rgb + i *
+ * image_pitch_bytes (>= h*w*3, rows tightly packed), -> n upright fitted images at d_out_rgb + i * out_image_pitch_bytes (>=
+ * out_h*out_w*3, rows tightly packed); out_h, out_w as ire_preprocess_plan gives them.  Image i is byte for byte what
+ * ire_preprocess_device gives for it alone; nothing between the output images is written.  Two stream operations per call whatever n
+ * (one when nothing is resized).  The tap tables of an (input size, output size) pair are built on the host in double precision and
+ * kept on the device (the 16 pairs used last): the first call with a new pair uploads them and waits for that upload on `stream`;
+ * every later call returns without waiting for the device.  Stored pixels are read along stored rows for every orientation (5..8
+ * through a transposing tile in LDS); a resize by more than about 17 (the tile no longer fits in 64 KB of LDS) reads them tap by tap,
+ * as ire_preprocess_device does. */
+int ire_preprocess_batch_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t image_pitch_bytes,
+                                int orientation, int max_dim, uint8_t* d_out_rgb, int out_h, int out_w,
+                                size_t out_image_pitch_bytes, void* stream);
 
 /* ---- result side of the seam: restored pixels -> base64 text of a PNG file, on the device (restorator.js:108: `restoredImage` is
  * a base64 string of an ENCODED image; geminiClient.js:75-88) ----
@@ -295,6 +307,25 @@ int ire_submit_fit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg,
  * creates no job: such a file stays with the host codec.  A file whose DATA the device finds corrupt fails only its own job, at
  * its poll: IRE_ERR_INVALID_INPUT "invalid: corrupt JPEG data (decoder status N)"; the other jobs of its batch complete. */
 int ire_submit_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, const double* scores, ire_job** job_out);
+/* An UPLOAD job: ire_submit_jpeg with the preprocess step of imagePreprocess.js:40-55 between the decode and the network, all on the
+ * device -- no pixel of the upload is ever on the host.  The file is one ire_submit_jpeg takes.  Its orientation is read from the
+ * first APP1 segment that is an Exif block (IFD0 tag 0x0112, SHORT, count 1, value 1..8; anything else, a broken block included, is
+ * orientation 1 and never a refusal).  The job's result is exactly that of
+ *   ire_submit_fit(ire_preprocess(ire_decode_jpeg(file), that orientation, max_dim), is_jpeg = 1, scores)
+ * (scores == NULL: the classifier runs on the preprocessed, unpadded pixels); its size is the fitted out_h x out_w.  The reference's
+ * q85 re-encode between preprocess and restore (imagePreprocess.js:57-64) is NOT reproduced: it exists to hand an external API a file.
+ * ire_upload_plan: pure host, no engine -- what ire_submit_upload will do with this file on an engine whose decoder accepts
+ * `accept` (0, or IRE_DECODE_ACCEPT_PROGRESSIVE): the stored size, the orientation, the fitted size (any output pointer may be NULL;
+ * the caller sizes its poll buffer from out_h, out_w).  It refuses what ire_decode_jpeg_plan_ex refuses, with the same reason,
+ * a max_dim below 1, and a file that breaks the room rule below.
+ * Upload jobs are coalesced by (stored h, stored w, orientation, max_dim) and never share a batch with another kind of job.  Known
+ * limit, the room rule: the job's cut scan is staged in its input place of out_h * out_w * 3 bytes, so a file whose entropy-coded
+ * data may need more (a large file fitted into a small max_dim) is IRE_ERR_INVALID_INPUT ("invalid: ...") at submit and creates no
+ * job; the plan refuses it with the same reason.  Corrupt data fails the job alone at its poll, as for ire_submit_jpeg.  The decoded stored
+ * images of a batch lie in an engine scratch sized by the any-size staging rule above (max_batch images while that is <= 256 MB). */
+int ire_upload_plan(const uint8_t* file, size_t bytes, uint32_t accept, int max_dim, int* stored_h, int* stored_w,
+                    int* orientation, int* out_h, int* out_w);
+int ire_submit_upload(ire_engine* e, const uint8_t* file, size_t bytes, int max_dim, const double* scores, ire_job** job_out);
 /* A FUSION job: k = 2 or 3 views of one scene, all h x w with h, w in 1..8192 (views[v]: h*w*3 bytes, copied before return),
  * submitted once, computed on the device with its batch, polled and released like every other job; its result is the fused h x w
  * image -- pixels, or on a text engine the engine's result text.  Every view is restored as ire_submit_fit restores it (scores of

@@ -1,0 +1,34 @@
+"""The batcher's upload jobs (csrc/batcher.hpp: submit_upload and the optional backend hooks upload_plan / decode_upload) under
+ThreadSanitizer and AddressSanitizer + UBSan on the CPU, over a host-only stub backend (tests/native/batcher_uploads_stress.cpp -- test
+infrastructure, as tests/native/batcher_files_stress.cpp is for file jobs): uploads of two keys that share an output size land in
+different slots, no slot mixes kinds, a refused upload creates no job, releases while pending and while in flight, shutdown with jobs
+pending."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "native", "batcher_uploads_stress.cpp")
+
+
+def _build_and_run(tmp_path, name, flags):
+    exe = str(tmp_path / name)
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-Wall"] + flags + [SRC, "-o", exe, "-lpthread"], capture_output=True, text=True)
+    assert r.returncode == 0 and "warning" not in r.stderr, r.stderr[-3000:]
+    out = []
+    for _ in range(3):          # three runs: the interleavings differ
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+        out.append(r.stdout + r.stderr)
+        assert r.returncode == 0, out[-1][-4000:]
+        assert "batcher_uploads_stress ok" in r.stdout
+    return "\n".join(out)
+
+
+def test_upload_jobs_under_thread_sanitizer(tmp_path):
+    # IRE_BATCHER_SYSCLOCK_WAITS: gcc 11's libtsan does not intercept pthread_cond_clockwait (batcher.hpp::wait_deadline)
+    log = _build_and_run(tmp_path, "bus_tsan", ["-fsanitize=thread", "-DIRE_BATCHER_SYSCLOCK_WAITS"])
+    assert "WARNING: ThreadSanitizer" not in log, log[-4000:]
+
+
+def test_upload_jobs_under_address_sanitizer(tmp_path):
+    log = _build_and_run(tmp_path, "bus_asan", ["-fsanitize=address,undefined"])
+    assert "ERROR: AddressSanitizer" not in log and "runtime error" not in log and "LeakSanitizer" not in log, log[-4000:]

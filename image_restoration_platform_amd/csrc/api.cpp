@@ -122,7 +122,7 @@ struct HipBatchBackend {
     int max_batch() const { return E.max_batch(); }
     // a result's place in the staging: the pixels, the stored PNG's text, or [uint64 count | the compressed PNG's or the JPEG's text, bound-sized]
     size_t out_bytes(int h, int w) const { return fmt ? fmt->place_bytes(h, w) : (size_t)h * w * 3; }
-    // the batcher's optional hook: only a text of data-dependent length is shorter than its place
+    // only a text of data-dependent length is shorter than its place
     const uint8_t* result_view(const uint8_t* place, int h, int w, size_t* len) const {
         if (!fmt || !fmt->counted) { *len = out_bytes(h, w); return place; }
         uint64_t n = 0;
@@ -156,7 +156,7 @@ struct HipBatchBackend {
         delete static_cast<HipSlot*>(b.impl);
         b = SlotBufs{};
     }
-    // ---- file jobs (batcher.hpp: the optional hooks).  The parse and the cut run in the submitting thread; the launcher only packs
+    // ---- file jobs (batcher.hpp: the decoded kinds' hooks).  The parse and the cut run in the submitting thread; the launcher only packs
     // the records of the jobs staged so far and enqueues the decode on the copy-in stream, under the previous batch's compute. ----
     std::shared_ptr<void> file_plan(const uint8_t* file, size_t bytes, int* h, int* w, size_t* room) {
         auto head = std::make_shared<JpegFileHead>();
@@ -174,10 +174,22 @@ struct HipBatchBackend {
         const jpegdec::DecStream& last = f.streams.back();
         return std::max<size_t>((size_t)last.off + last.len, 1);      // (0 would say that nothing was staged: a last scan of no bytes)
     }
-    void decode(SlotBufs& b, int first, int count, int h, int w, void* const* heads, const size_t* used) {
+    // A file job is decoded straight into the slot's device input.  An upload job is decoded at its STORED size into the engine's scratch,
+    // then oriented and fitted into the slot's device input by one batched preprocess.  Either way all on the copy-in stream, under the
+    // previous batch's compute.
+    void decode(SlotBufs& b, int first, int count, const SlotKey& key, void* const* heads, const size_t* used) {
         HipSlot& hs = *static_cast<HipSlot*>(b.impl);
-        const size_t ib = (size_t)h * w * 3;
-        decode_runs(hs, b, first, count, ib, h, w, hs.d_in.get<uint8_t>(), ib, heads, used);
+        const int h = key.h, w = key.w;
+        const size_t ib = key.in_bytes();
+        if (key.kind != JobKind::Upload) { decode_runs(hs, b, first, count, ib, h, w, hs.d_in.get<uint8_t>(), ib, heads, used); return; }
+        const int sh = key.up[0], sw = key.up[1];
+        const size_t sb = (size_t)sh * sw * 3;
+        PreprocessScratch& P = E.preprocess_uploads();
+        // the any-size staging rule (ire.h): for max_batch images while that is <= 256 MB, else for the batch at hand
+        P.d_stored.grow(sb * (size_t)(first + count), batch_room(sb * (size_t)(first + count), sb * (size_t)E.max_batch()));
+        decode_runs(hs, b, first, count, ib, sh, sw, P.d_stored.get<uint8_t>(), sb, heads, used);
+        // (a job with nothing decoded is fitted from whatever the scratch held: it fails alone, its place is never read)
+        E.preprocess_batch_device(P, P.d_stored.get<uint8_t>() + sb * (size_t)first, count, sh, sw, sb, key.up[2], key.up[3], hs.d_in.get<uint8_t>() + ib * (size_t)first, h, w, ib, cs);
     }
     // jobs first .. first + count - 1 of the slot, their staged bytes `place` apart in pin_in, decoded to h x w images `pitch` apart in d_rgb
     void decode_runs(HipSlot& hs, SlotBufs& b, int first, int count, size_t place, int h, int w, uint8_t* d_rgb, size_t pitch, void* const* heads, const size_t* used) {
@@ -204,8 +216,7 @@ struct HipBatchBackend {
             E.jpeg_decoder().decode_streams(hd, streams, bytes, room, n, h, w, d_rgb + pitch * (size_t)(first + i0), pitch, hs.d_fstat.get<int32_t>() + first + i0, cs);
         }
     }
-    // ---- upload jobs (batcher.hpp: the optional hooks): a file job decoded at its STORED size into the engine's scratch, then oriented
-    // and fitted into the slot's device input by one batched preprocess -- all on the copy-in stream, under the previous batch's compute ----
+    // file_plan for an upload job: the FITTED size, and the key that says how decode gets there
     std::shared_ptr<void> upload_plan(const uint8_t* file, size_t bytes, int max_dim, int* h, int* w, size_t* room, int key[4]) {
         int sh = 0, sw = 0;
         auto head = file_plan(file, bytes, &sh, &sw, room);
@@ -214,31 +225,17 @@ struct HipBatchBackend {
         if (!piece_addressable(Engine::fit_dim(*h), Engine::fit_dim(*w), 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(Engine::fit_dim(*h), Engine::fit_dim(*w)));
         return head;
     }
-    void decode_upload(SlotBufs& b, int first, int count, int h, int w, const int key[4], void* const* heads, const size_t* used) {
-        HipSlot& hs = *static_cast<HipSlot*>(b.impl);
-        const int sh = key[0], sw = key[1];
-        const size_t ib = (size_t)h * w * 3, sb = (size_t)sh * sw * 3;
-        PreprocessScratch& P = E.preprocess_uploads();
-        // the any-size staging rule (ire.h): for max_batch images while that is <= 256 MB, else for the batch at hand
-        P.d_stored.grow(sb * (size_t)(first + count), batch_room(sb * (size_t)(first + count), sb * (size_t)E.max_batch()));
-        decode_runs(hs, b, first, count, ib, sh, sw, P.d_stored.get<uint8_t>(), sb, heads, used);
-        // (a job with nothing decoded is fitted from whatever the scratch held: it fails alone, its place is never read)
-        E.preprocess_batch_device(P, P.d_stored.get<uint8_t>() + sb * (size_t)first, count, sh, sw, sb, key[2], key[3], hs.d_in.get<uint8_t>() + ib * (size_t)first, h, w, ib, cs);
-    }
     int file_status(SlotBufs& b, int i) { return static_cast<HipSlot*>(b.impl)->pin_fstat.get<int32_t>()[i]; }
     void h2d(SlotBufs& b, size_t off, size_t bytes) {
         HipSlot& hs = *static_cast<HipSlot*>(b.impl);
         hs.file_jobs = 0;
         IRE_HIP(hipMemcpyAsync(hs.d_in.get<uint8_t>() + off, b.pin_in + off, bytes, hipMemcpyHostToDevice, cs));
     }
-    void launch(SlotBufs& b, int n, int h, int w, const uint8_t* has_sc) { launch_jobs(b, n, 0, h, w, has_sc); }
-    // the batcher's optional hook: n fusion jobs of k views each, one fused result per job
-    void launch_group(SlotBufs& b, int n, int k, int h, int w, const uint8_t* has_sc) { launch_jobs(b, n, k, h, w, has_sc); }
-    // n jobs of one image (k == 0) or of k views: n results, n rows of scores (a fusion job's: its view 0's)
-    void launch_jobs(SlotBufs& b, int n, int k, int h, int w, const uint8_t* has_sc) {
+    // n jobs of one image (key.k == 0) or of k views, one fused result per job: n results, n rows of scores (a fusion job's: its view 0's)
+    void launch(SlotBufs& b, int n, const SlotKey& key, const uint8_t* has_sc) {
         HipSlot& hs = *static_cast<HipSlot*>(b.impl);
-        const size_t ib = (size_t)h * w * 3;
-        IRE_HIP(hipMemcpyAsync(hs.d_jp.get<uint8_t>(), b.pin_jp, (size_t)n * (size_t)std::max(1, k), hipMemcpyHostToDevice, cs));
+        const int k = key.k, h = key.h, w = key.w;
+        IRE_HIP(hipMemcpyAsync(hs.d_jp.get<uint8_t>(), b.pin_jp, (size_t)n * (size_t)key.images_per_job(), hipMemcpyHostToDevice, cs));
         IRE_HIP(hipEventRecord(hs.ev->in, cs));
         hipStream_t ms = E.main_stream();
         on_stream(E, ms, [&] {
@@ -262,7 +259,7 @@ struct HipBatchBackend {
         if (fmt) {
             const size_t ob = out_bytes(h, w), st = (ob + 255) / 256 * 256;
             for (int i = 0; i < n; ++i) IRE_HIP(hipMemcpyAsync(b.pin_out + ob * i, hs.d_txt.get<uint8_t>() + st * i, ob, hipMemcpyDeviceToHost, os));
-        } else IRE_HIP(hipMemcpyAsync(b.pin_out, hs.d_out.get<uint8_t>(), ib * n, hipMemcpyDeviceToHost, os));
+        } else IRE_HIP(hipMemcpyAsync(b.pin_out, hs.d_out.get<uint8_t>(), out_bytes(h, w) * n, hipMemcpyDeviceToHost, os));
         IRE_HIP(hipEventRecord(hs.ev->out, os));
     }
     bool computing(SlotBufs& b) noexcept { return hipEventQuery(static_cast<HipSlot*>(b.impl)->ev->c1) == hipErrorNotReady; }
@@ -346,11 +343,12 @@ static int family_id(const char* f) {
 
 }  // namespace ire
 
-// behind ire_submit and ire_submit_fit, after their argument checks: one job into the batcher (keyed by its exact h, w)
-static void queue_job(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg, const double* scores, ire_job** job_out) {
+// behind every ire_submit*, after its argument checks: the job that `submit` queues in the batcher, wrapped in a handle
+template <typename F>
+static void job_handle(ire_job** job_out, F&& submit) {
     *job_out = nullptr;
     std::unique_ptr<ire_job> hnd(new ire_job{});
-    hnd->j = e->batcher->submit(rgb, h, w, is_jpeg, scores);
+    hnd->j = submit();
     *job_out = hnd.release();
 }
 
@@ -736,7 +734,7 @@ int ire_submit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg, con
         if (h <= 0 || w <= 0 || h % 8 || w % 8 || h < 16 || w < 16 || h > 8192 || w > 8192)
             fail(IRE_ERR_INVALID_INPUT, "invalid image size for restore: height and width must be multiples of 8, >= 16");
         if (!piece_addressable(h, w, 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(h, w));      // no job is queued for the shape restore refuses
-        queue_job(e, rgb, h, w, is_jpeg, scores, job_out);
+        job_handle(job_out, [&] { return e->batcher->submit(rgb, h, w, is_jpeg, scores); });
     });
 }
 
@@ -746,7 +744,7 @@ int ire_submit_fit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg,
         if (!rgb || !job_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_fit");
         if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size: height and width must be in 1..8192");
         if (!piece_addressable(Engine::fit_dim(h), Engine::fit_dim(w), 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(Engine::fit_dim(h), Engine::fit_dim(w)));
-        queue_job(e, rgb, h, w, is_jpeg, scores, job_out);
+        job_handle(job_out, [&] { return e->batcher->submit(rgb, h, w, is_jpeg, scores); });
     });
 }
 
@@ -754,10 +752,7 @@ int ire_submit_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, const doub
     return guarded([&] {
         eng(e);
         if (!file || !job_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_jpeg");
-        *job_out = nullptr;
-        std::unique_ptr<ire_job> hnd(new ire_job{});
-        hnd->j = e->batcher->submit_file(file, bytes, scores);
-        *job_out = hnd.release();
+        job_handle(job_out, [&] { return e->batcher->submit_file(file, bytes, scores); });
     });
 }
 
@@ -765,10 +760,7 @@ int ire_submit_upload(ire_engine* e, const uint8_t* file, size_t bytes, int max_
     return guarded([&] {
         eng(e);
         if (!file || !job_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_upload");
-        *job_out = nullptr;
-        std::unique_ptr<ire_job> hnd(new ire_job{});
-        hnd->j = e->batcher->submit_upload(file, bytes, max_dim, scores);
-        *job_out = hnd.release();
+        job_handle(job_out, [&] { return e->batcher->submit_upload(file, bytes, max_dim, scores); });
     });
 }
 
@@ -783,9 +775,7 @@ int ire_submit_fuse_fit(ire_engine* e, const uint8_t* const* views, int k, int h
         if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size: height and width must be in 1..8192");
         if (!piece_addressable(Engine::fit_dim(h), Engine::fit_dim(w), 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(Engine::fit_dim(h), Engine::fit_dim(w)));
         if (has_scores && !scores) for (int v = 0; v < k; ++v) if (has_scores[v]) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_fuse_fit: has_scores without scores");
-        std::unique_ptr<ire_job> hnd(new ire_job{});
-        hnd->j = e->batcher->submit_group(views, k, h, w, is_jpeg, has_scores, scores);       // (refuses k views on an engine with max_batch < k)
-        *job_out = hnd.release();
+        job_handle(job_out, [&] { return e->batcher->submit_group(views, k, h, w, is_jpeg, has_scores, scores); });       // (refuses k views on an engine with max_batch < k)
     });
 }
 

@@ -4,7 +4,7 @@
 //
 // The state machine is a template over its BACKEND -- everything that touches the device (pinned / device staging, copies, the
 // restore call, completion events) -- so that the same code is built twice: api.cpp instantiates it over HIP (HipBatchBackend),
-// tests/native/batcher_stress.cpp over a host-only stub and runs it under ThreadSanitizer and AddressSanitizer on the CPU box
+// tests/native/batcher_*_stress.cpp over a host-only stub (batcher_stub.hpp) and run it under ThreadSanitizer and AddressSanitizer on the CPU box
 // (sanitizers on the CPU build).  The stub is test infrastructure: libire.so never contains it.
 //
 // Data path, ONE host copy per direction: submit copies the caller's pixels straight into the pinned staging slot of the batch
@@ -22,11 +22,14 @@
 // per restoreBatch, 5 per worker -- is about to resubmit), and when the GPU is idle after a short bounded linger: kLingerQuietUs
 // after the last arrival, at most kLingerMaxUs after the first.
 //
-// A slot gathers ONE kind of job: pixel jobs, file jobs, upload jobs (submit_upload) of one key, or fusion jobs (submit_group) of one
-// k -- a fusion job's k views take k consecutive image places, so such a slot holds max_batch / k jobs (at most kGroupMaxJobs: a full
-// slot is ONE fused launch) and closes by the same full / linger rules.  An upload job is a file job whose decoded image is oriented
-// and fitted on the device before the network sees it: its h, w are the FITTED size, its key (stored h, stored w, orientation,
-// max_dim) says how the backend gets there, and two keys never share a slot even where they give one fitted size.
+// A slot gathers jobs of ONE SlotKey: the images' size, the kind of job (pixel, file, upload, fusion) and what tells two slots of that kind
+// apart -- a fusion job's number of views k, an upload's (stored h, stored w, orientation, max_dim).  The key also says how large a job's
+// place in the slot's input is (in_bytes) and how many image places it takes: a fusion job's k views take k consecutive ones, so such a
+// slot holds max_batch / k jobs (at most kGroupMaxJobs: a full slot is ONE fused launch) and closes by the same full / linger rules.  An
+// upload job is a file job whose decoded image is oriented and fitted on the device before the network sees it: its h, w are the FITTED
+// size, the rest of its key says how the backend gets there, and two keys never share a slot even where they give one fitted size.
+//
+// Every submit goes through ONE staging path (Batcher::stage): a place for the job, then its input written there in the caller's thread.
 //
 // A job handle is used by ONE thread at a time (poll it, or release it).  A timed-out poll leaves the job pending; the caller
 // polls again or RELEASES it (the reference retries 3x on exactly this path: utils/retry.js:12-47): an abandoned job's slot
@@ -45,7 +48,6 @@
 #include <new>
 #include <string>
 #include <thread>
-#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -59,24 +61,36 @@ constexpr int kLingerQuietUs = 250, kLingerMaxUs = 1500;
 constexpr int kMaxBatch = 64;
 constexpr int kGroupMaxJobs = 16;     // fusion jobs of one batch at most: what one fused launch takes (fusion.hpp kFuseMaxSets; api.cpp asserts that they agree)
 
+enum class JobKind { Pixels, File, Upload, Group };
+// What a slot gathers, and what a job is: jobs share a slot exactly when their keys are equal.
+struct SlotKey {
+    int h = 0, w = 0;                 // of every image of the job (an upload's: the FITTED size)
+    JobKind kind = JobKind::Pixels;
+    int k = 0;                        // Group: the job's views (2..3), staged one behind the other; else 0: one image
+    int up[4] = {};                   // Upload: stored h, stored w, orientation, max_dim; else zeros
+    bool operator==(const SlotKey& o) const { return h == o.h && w == o.w && kind == o.kind && k == o.k && !std::memcmp(up, o.up, sizeof(up)); }
+    int images_per_job() const { return std::max(1, k); }
+    size_t image_bytes() const { return (size_t)h * w * 3; }
+    size_t in_bytes() const { return image_bytes() * (size_t)images_per_job(); }      // one job's staged input: its place in pin_in
+    bool decoded() const { return kind == JobKind::File || kind == JobKind::Upload; }     // the input is a file's scan, decoded on the device
+};
+
 struct BatchSlot;
 struct Job {
-    int h = 0, w = 0;
+    SlotKey key;
     bool staged = false;              // input bytes are in the slot's pinned buffer (or in `in` on the overflow path)
     bool abandoned = false;           // released while pending: its result is dropped when the batch completes
-    int views = 0;                    // a fusion job (submit_group): its k = 2..3 views of h x w, staged one behind the other; 0: one image
-    uint8_t v_jpeg[3] = {}, v_has[3] = {};      // per image of the job (a pixel or file job: entry 0 alone): is_jpeg, scores supplied
+    uint8_t v_jpeg[3] = {}, v_has[3] = {};      // per image of the job (entry 0 alone unless it is a fusion job): is_jpeg, scores supplied
     double v_scores[3][7] = {};                 // ... and those scores
-    std::shared_ptr<void> file;       // a file job (submit_file): what the backend's file_plan made of the file's head; its staged input is the scan, cut
-    size_t file_used = 0;             // bytes of that input
-    int up[4] = {};                   // an upload job (submit_upload): stored h, stored w, orientation, max_dim; up[0] == 0: none (h, w: the fitted size)
+    std::shared_ptr<void> file;       // decoded kinds: what the backend's file_plan / upload_plan made of the file's head; the staged input is the scan, cut
+    size_t file_used = 0;             // bytes of the staged input (0: staging failed, nothing to decode)
     BatchSlot* slot = nullptr;        // where the input was staged and the output will be; null: overflow (no free slot at submit) / evicted / fetched
     int idx = -1;
     std::vector<uint8_t> in, out;     // overflow input / evicted output only
     double scores[7] = {};            // the result's (a fusion job's: its view 0's), from the batch
     ire_timings t{};
     int status = -1;                  // -1 pending, else ire_status
-    int stage_status = IRE_OK;        // a file job whose staging failed after it had got its place: the status it completes with
+    int stage_status = IRE_OK;        // a job whose staging failed after it had got its place: the status it completes with
     std::string err;
 };
 
@@ -94,79 +108,51 @@ struct BatchSlot {
     SlotBufs b;
     uint8_t has_sc[kMaxBatch] = {};
     std::vector<std::shared_ptr<Job>> jobs;   // index order = position in the batch
-    int h = 0, w = 0;
-    bool files = false;                   // gathers file jobs (never mixed with pixel jobs: their input is decoded on the device, not copied)
-    int up[4] = {};                       // gathers upload jobs of this key (files is set too); up[0] == 0: not an upload slot
-    int k = 0;                            // gathers fusion jobs of k views each (never mixed with another kind or another k); 0: one image per job
-    int h2d_issued = 0;                   // images whose H2D copy (file jobs: whose decode) is already on the copy-in stream
+    SlotKey key;                          // what it gathers: never two kinds, two k or two upload keys
+    int h2d_issued = 0;                   // jobs whose H2D copy (decoded kinds: whose decode) is already on the copy-in stream
     int unread = 0, reading = 0;          // DONE: jobs that have not fetched their output yet / polls copying right now
     std::chrono::steady_clock::time_point first_arrival, last_arrival;
     int status = IRE_OK;
     std::string err;
 };
 
-// Backend concept (HipBatchBackend in api.cpp; StubBackend in tests/native/batcher_stress.cpp):
+// Backend concept (HipBatchBackend in api.cpp; StubBackend in tests/native/batcher_stub.hpp).  Every hook is required: the product has one
+// backend and it serves every kind of job.
 //   int  max_batch() const;
-//   size_t out_bytes(int h, int w) const;                      bytes of one job's result (h * w * 3 pixels, or the text of an encoded image)
+//   size_t out_bytes(int h, int w) const;                      bytes of one job's result place (h * w * 3 pixels, or the text of an encoded image)
+//   const uint8_t* result_view(const uint8_t* place, int h, int w, size_t* len) const;
+//                                                              where a result's payload starts inside its place and how long it really is (a
+//                                                              result whose size does not depend on the data: place, out_bytes(h, w)).  Required,
+//                                                              not detected: the identity form is one line, a trait and its branch were more
 //   void start();                                              first submit, batcher lock held: streams
 //   void thread_enter(const char* role);                       at the top of a service thread: device, CPU affinity
 //   void reserve(SlotBufs&, size_t bytes, int max_batch);      grow to `bytes` per direction; STRONG guarantee: on a throw the SlotBufs is as before
 //   void release(SlotBufs&) noexcept;
 //   void h2d(SlotBufs&, size_t off, size_t bytes);             async copy pin_in -> device, copy-in stream; throws Error
-//   void launch(SlotBufs&, int n, int h, int w, const uint8_t* has_sc);   flags + restore + scores + D2H, all enqueued; throws Error
+//   void launch(SlotBufs&, int njobs, const SlotKey&, const uint8_t* has_sc);
+//                                                              flags + restore (Group: of all njobs * k views, then the fusion) + scores + D2H, all
+//                                                              enqueued; throws Error.  Job i owns images [i * images_per_job(), ...) of the slot's
+//                                                              input and of pin_jp / has_sc / pin_sc_in, and result place i; pin_sc[7 * i ..] = its
+//                                                              scores (a fusion job's: its view 0's)
 //   bool computing(SlotBufs&) noexcept;                        the launched batch's compute has not finished (non-blocking)
 //   void wait_compute(SlotBufs&) noexcept;                     blocks until it has
 //   void wait_done(SlotBufs&, ire_timings&);                   blocks until pin_out / pin_sc are complete; throws Error
 //   void drain() noexcept;                                     after a failed launch: nothing enqueued may still touch a slot
-// OPTIONAL (detected at compile time; a backend without it delivers out_bytes(h, w) bytes from the start of a result's place):
-//   const uint8_t* result_view(const uint8_t* place, int h, int w, size_t* len) const;
-//                                                              a result whose size depends on the data: where its payload starts inside
-//                                                              its out_bytes(h, w)-sized place and how long it really is
-// OPTIONAL, all four or none (detected at compile time; without them submit_file does not compile): FILE JOBS, whose input is an
-// encoded file that the backend decodes on the device into the slot's device input, h * w * 3 bytes per job, in place of h2d
+// DECODED KINDS (File, Upload), whose input is an encoded file that the backend decodes on the device into the slot's device input,
+// key.in_bytes() per job, in place of h2d:
 //   std::shared_ptr<void> file_plan(const uint8_t* file, size_t bytes, int* h, int* w, size_t* room);
 //                                                              submitting thread, no lock: reads the file's head and checks all of it;
 //                                                              throws Error when the file is refused.  *room: bytes file_stage needs at most
+//   std::shared_ptr<void> upload_plan(const uint8_t* file, size_t bytes, int max_dim, int* h, int* w, size_t* room, int up[4]);
+//                                                              file_plan for an upload: *h, *w = the FITTED size, up = the rest of its key
 //   size_t file_stage(void* head, const uint8_t* file, size_t bytes, uint8_t* dst, size_t room);
 //                                                              submitting thread, no lock: what the device needs of the file into dst (the
 //                                                              job's place in pin_in, or the job's own vector); -> bytes written; throws Error
-//   void decode(SlotBufs&, int first, int count, int h, int w, void* const* heads, const size_t* used);
+//   void decode(SlotBufs&, int first, int count, const SlotKey&, void* const* heads, const size_t* used);
 //                                                              launcher, in place of h2d, WITHOUT the batcher's lock, copy-in stream: jobs first ..
-//                                                              first + count - 1 of the slot, their staged bytes at pin_in + h * w * 3 * index; throws Error
+//                                                              first + count - 1 of the slot, their staged bytes at pin_in + key.in_bytes() * index;
+//                                                              an Upload's files decoded at their stored size, oriented and fitted; throws Error
 //   int file_status(SlotBufs&, int index);                     after wait_done: 0, or what the device found wrong with that job's data
-template <class B, class = void>
-struct has_file_jobs : std::false_type {};
-template <class B>
-struct has_file_jobs<B, std::void_t<decltype(std::declval<B&>().file_status(std::declval<SlotBufs&>(), 0))>> : std::true_type {};
-
-// OPTIONAL (detected at compile time; without it submit_group does not compile): FUSION JOBS, k = 2..3 views of one size per job.
-// Job i of such a slot owns images [i * k, i * k + k) of the slot's input and of pin_jp / has_sc / pin_sc_in, and result place i.
-//   void launch_group(SlotBufs&, int njobs, int k, int h, int w, const uint8_t* has_sc);
-//                                                              in place of launch: njobs results of out_bytes(h, w) bytes each, and
-//                                                              pin_sc[7 * i ..] = the scores of job i's view 0
-template <class B, class = void>
-struct has_group_launch : std::false_type {};
-template <class B>
-struct has_group_launch<B, std::void_t<decltype(std::declval<B&>().launch_group(std::declval<SlotBufs&>(), 0, 0, 0, 0, (const uint8_t*)nullptr))>> : std::true_type {};
-
-// OPTIONAL, both or none, on a backend WITH file jobs (detected at compile time; without them submit_upload does not compile): UPLOAD
-// JOBS.  file_stage and file_status serve them as they serve file jobs.
-//   std::shared_ptr<void> upload_plan(const uint8_t* file, size_t bytes, int max_dim, int* h, int* w, size_t* room, int key[4]);
-//                                                              file_plan for an upload: *h, *w = the FITTED size, key = (stored h, stored w,
-//                                                              orientation, max_dim); throws Error when the file is refused
-//   void decode_upload(SlotBufs&, int first, int count, int h, int w, const int key[4], void* const* heads, const size_t* used);
-//                                                              in place of decode: the jobs' files decoded at their stored size, oriented and
-//                                                              fitted into the slot's device input, h * w * 3 bytes per job
-template <class B, class = void>
-struct has_upload_jobs : std::false_type {};
-template <class B>
-struct has_upload_jobs<B, std::void_t<decltype(std::declval<B&>().decode_upload(std::declval<SlotBufs&>(), 0, 0, 0, 0, (const int*)nullptr, (void* const*)nullptr,
-                                                                                  (const size_t*)nullptr))>> : std::true_type {};
-
-template <class B, class = void>
-struct has_result_view : std::false_type {};
-template <class B>
-struct has_result_view<B, std::void_t<decltype(std::declval<const B&>().result_view((const uint8_t*)nullptr, 0, 0, (size_t*)nullptr))>> : std::true_type {};
 
 // the room rule of upload jobs (submit_upload; ire_upload_plan says the same of the same file)
 constexpr const char* kUploadRoomReason = "invalid: the file's entropy-coded data may be larger than its fitted pixels (decode it with the host codec)";
@@ -211,125 +197,55 @@ class Batcher {
     // Queue one image.  Throws Error (invalid size is the caller's check); the returned job is pending.
     std::shared_ptr<Job> submit(const uint8_t* rgb, int h, int w, int is_jpeg, const double* scores) {
         auto j = std::make_shared<Job>();
-        j->h = h; j->w = w; j->v_jpeg[0] = is_jpeg ? 1 : 0;
-        if (scores) { std::memcpy(j->v_scores[0], scores, sizeof(double) * 7); j->v_has[0] = 1; }
-        const size_t ib = (size_t)h * w * 3;
-        uint8_t* dst = nullptr;
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            start_locked(h, w);
-            const int si = overflow_.empty() ? slot_for(h, w) : -1;     // (jobs already overflowing keep their order)
-            if (si >= 0) { slot_add(si, j); dst = slots_[si].b.pin_in + ib * j->idx; }
-        }
-        if (dst) {
-            std::memcpy(dst, rgb, ib);                 // the ONE host copy of the input: caller's buffer -> pinned slot, in the caller's thread
-            std::lock_guard<std::mutex> lk(mu_);
-            j->staged = true;
-        } else {
-            j->in.assign(rgb, rgb + ib);               // every slot is busy: keep the pixels until the launcher finds one
-            std::lock_guard<std::mutex> lk(mu_);
-            j->staged = true;
-            overflow_.push_back(j);
-            cnt_.overflowed += 1;
-        }
-        qcv_.notify_all();
+        j->key.h = h; j->key.w = w;
+        set_image(*j, 0, is_jpeg != 0, scores);
+        // the ONE host copy of the input: caller's buffer -> pinned slot, in the caller's thread
+        stage(j, j->key.in_bytes(), [&](uint8_t* dst) { std::memcpy(dst, rgb, j->key.in_bytes()); return j->key.in_bytes(); });
         return j;
     }
 
-    // Queue one encoded file (backends with file jobs).  The head is parsed and the scan is cut HERE, in the submitting thread,
-    // straight into the job's place in the slot's pinned input; the launcher only hands the staged jobs to the backend's decode.
-    // Throws Error when the backend refuses the file: no job exists then.
-    template <class BE = Backend>
+    // Queue one encoded file.  The head is parsed and the scan is cut HERE, in the submitting thread, straight into the job's place in
+    // the slot's pinned input; the launcher only hands the staged jobs to the backend's decode.  Throws Error when the backend refuses
+    // the file: no job exists then.
     std::shared_ptr<Job> submit_file(const uint8_t* file, size_t bytes, const double* scores) {
-        static_assert(has_file_jobs<BE>::value, "this backend has no file jobs");
         auto j = std::make_shared<Job>();
         size_t room = 0;
-        j->file = be_.file_plan(file, bytes, &j->h, &j->w, &room);
-        if (room > (size_t)j->h * j->w * 3) fail(IRE_ERR_INVALID_INPUT, "invalid: the file's entropy-coded data may be larger than its pixels (it stays with the host codec)");
-        stage_file_job(j, file, bytes, room, scores);
+        j->key.kind = JobKind::File;
+        j->file = be_.file_plan(file, bytes, &j->key.h, &j->key.w, &room);
+        if (room > j->key.in_bytes()) fail(IRE_ERR_INVALID_INPUT, "invalid: the file's entropy-coded data may be larger than its pixels (it stays with the host codec)");
+        set_image(*j, 0, true, scores);
+        stage(j, room, [&](uint8_t* dst) { return be_.file_stage(j->file.get(), file, bytes, dst, room); });
         return j;
     }
 
-    // Queue one encoded upload (backends with upload jobs): a file job that the backend orients by the file's EXIF tag and fits inside
-    // max_dim on the device, after the decode and before the network.  The job's h, w are the fitted size; its place in the slot's
-    // input holds h * w * 3 bytes, and a file whose cut scan may need more is refused: no job exists then.
-    template <class BE = Backend>
+    // Queue one encoded upload: a file job that the backend orients by the file's EXIF tag and fits inside max_dim on the device, after
+    // the decode and before the network.  The job's h, w are the fitted size; its place in the slot's input holds that many pixels, and a
+    // file whose cut scan may need more is refused: no job exists then.
     std::shared_ptr<Job> submit_upload(const uint8_t* file, size_t bytes, int max_dim, const double* scores) {
-        static_assert(has_file_jobs<BE>::value && has_upload_jobs<BE>::value, "this backend has no upload jobs");
         auto j = std::make_shared<Job>();
         size_t room = 0;
-        j->file = be_.upload_plan(file, bytes, max_dim, &j->h, &j->w, &room, j->up);
-        if (room > (size_t)j->h * j->w * 3)
-            fail(IRE_ERR_INVALID_INPUT, kUploadRoomReason);
-        stage_file_job(j, file, bytes, room, scores);
+        j->key.kind = JobKind::Upload;
+        j->file = be_.upload_plan(file, bytes, max_dim, &j->key.h, &j->key.w, &room, j->key.up);
+        if (room > j->key.in_bytes()) fail(IRE_ERR_INVALID_INPUT, kUploadRoomReason);
+        set_image(*j, 0, true, scores);
+        stage(j, room, [&](uint8_t* dst) { return be_.file_stage(j->file.get(), file, bytes, dst, room); });
         return j;
     }
 
-  private:
-    // the rest of submit_file / submit_upload: a place for the planned job, the scan cut into it in the submitting thread
-    void stage_file_job(const std::shared_ptr<Job>& j, const uint8_t* file, size_t bytes, size_t room, const double* scores) {
-        j->v_jpeg[0] = 1;
-        if (scores) { std::memcpy(j->v_scores[0], scores, sizeof(double) * 7); j->v_has[0] = 1; }
-        const int h = j->h, w = j->w;
-        const size_t ib = (size_t)h * w * 3;
-        uint8_t* dst = nullptr;
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            start_locked(h, w);
-            const int si = overflow_.empty() ? slot_for(h, w, true, 0, j->up) : -1;
-            if (si >= 0) { slot_add(si, j); dst = slots_[si].b.pin_in + ib * j->idx; }
-        }
-        size_t used = 0;
-        int code = IRE_OK;
-        std::string why;
-        if (!dst) j->in.resize(room);
-        // (file_plan checked the whole file, so this cannot refuse it -- unless the caller changed the bytes meanwhile: the job then
-        // exists already, holds its place with nothing to decode and fails alone when its batch completes)
-        try { used = be_.file_stage(j->file.get(), file, bytes, dst ? dst : j->in.data(), room); }
-        catch (const Error& e) { code = e.code; why = e.msg; }
-        catch (const std::exception& e) { code = IRE_ERR_UNAVAILABLE; why = std::string("service unavailable: ") + e.what(); }      // (a bad_alloc: the job has its place, so it must become staged)
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            j->file_used = used;
-            if (code != IRE_OK) { j->stage_status = code; j->err = why; j->file_used = 0; }
-            if (!dst) { j->in.resize(j->file_used); overflow_.push_back(j); cnt_.overflowed += 1; }
-            j->staged = true;
-        }
-        qcv_.notify_all();
-    }
-
-  public:
-    // Queue one fusion job (backends with the group launch): k = 2..3 views of h x w.  All k views are staged HERE, in the submitting
-    // thread: one copy each into the job's k consecutive places of the pinned slot (or into the job's own vector on the overflow
-    // path).  is_jpeg / has_scores: [k] or null (all JPEG / none supplied); scores: [k][7], read where has_scores says so.
-    template <class BE = Backend>
+    // Queue one fusion job: k = 2..3 views of h x w.  All k views are staged HERE, in the submitting thread: one copy each into the
+    // job's k consecutive places of the pinned slot (or into the job's own vector on the overflow path).  is_jpeg / has_scores: [k] or
+    // null (all JPEG / none supplied); scores: [k][7], read where has_scores says so.
     std::shared_ptr<Job> submit_group(const uint8_t* const* views, int k, int h, int w, const uint8_t* is_jpeg, const uint8_t* has_scores, const double* scores) {
-        static_assert(has_group_launch<BE>::value, "this backend has no group launch");
         if (k < 2 || k > 3) fail(IRE_ERR_INVALID_INPUT, "invalid view count for fusion: expected 2..3");
         if (be_.max_batch() < k) fail(IRE_ERR_INVALID_INPUT, "invalid view count for fusion: the engine's max_batch is smaller than the number of views");
         auto j = std::make_shared<Job>();
-        j->h = h; j->w = w; j->views = k;
-        for (int v = 0; v < k; ++v) {
-            j->v_jpeg[v] = is_jpeg ? (is_jpeg[v] ? 1 : 0) : 1;
-            j->v_has[v] = has_scores && has_scores[v] ? 1 : 0;
-            if (j->v_has[v]) std::memcpy(j->v_scores[v], scores + 7 * v, sizeof(double) * 7);
-        }
-        const size_t ib = (size_t)h * w * 3;
-        uint8_t* dst = nullptr;
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            start_locked(h, w);
-            const int si = overflow_.empty() ? slot_for(h, w, false, k) : -1;
-            if (si >= 0) { slot_add(si, j); dst = slots_[si].b.pin_in + ib * k * j->idx; }
-        }
-        if (!dst) { j->in.resize(ib * k); dst = j->in.data(); }
-        for (int v = 0; v < k; ++v) std::memcpy(dst + ib * v, views[v], ib);       // the ONE host copy of each view, in the caller's thread
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            j->staged = true;
-            if (!j->slot) { overflow_.push_back(j); cnt_.overflowed += 1; }
-        }
-        qcv_.notify_all();
+        j->key.h = h; j->key.w = w; j->key.kind = JobKind::Group; j->key.k = k;
+        for (int v = 0; v < k; ++v) set_image(*j, v, !is_jpeg || is_jpeg[v], has_scores && has_scores[v] ? scores + 7 * v : nullptr);
+        const size_t ib = j->key.image_bytes();
+        stage(j, j->key.in_bytes(), [&](uint8_t* dst) {
+            for (int v = 0; v < k; ++v) std::memcpy(dst + ib * v, views[v], ib);       // the ONE host copy of each view, in the caller's thread
+            return j->key.in_bytes();
+        });
         return j;
     }
 
@@ -356,10 +272,9 @@ class Batcher {
         }
         const int st = j->status;
         if (st == IRE_OK) {
-            const size_t ob = be_.out_bytes(j->h, j->w);
-            const uint8_t* src = S ? S->b.pin_out + ob * j->idx : j->out.data();
+            const size_t ob = be_.out_bytes(j->key.h, j->key.w);
             size_t len = ob;
-            if constexpr (has_result_view<Backend>::value) src = be_.result_view(src, j->h, j->w, &len);
+            const uint8_t* src = be_.result_view(S ? S->b.pin_out + ob * j->idx : j->out.data(), j->key.h, j->key.w, &len);
             if (len_out) *len_out = len;
             if (len > cap) {
                 if (S) { std::lock_guard<std::mutex> lk(mu_); S->reading -= 1; qcv_.notify_all(); }
@@ -406,16 +321,62 @@ class Batcher {
 
   private:
     // (mu_ held) at the top of every submit: refuses while shutting down; the first one starts the backend and the service threads
-    void start_locked(int h, int w) {
+    void start_locked(const SlotKey& key) {
         if (stop_) fail(IRE_ERR_UNAVAILABLE, "service unavailable: the engine is shutting down");
         if (started_) return;
         be_.start();
         // staging for the three slots of a steady stream now, at this first shape (pinning 3 x 2 x max_batch images takes tens
         // of ms): the first job pays it once, instead of later jobs paying it one slot at a time in the middle of a stream
-        for (int i = 0; i < kSlotsEager; ++i) be_.reserve(slots_[i].b, std::max((size_t)h * w * 3, be_.out_bytes(h, w)) * (size_t)be_.max_batch(), be_.max_batch());
+        for (int i = 0; i < kSlotsEager; ++i) be_.reserve(slots_[i].b, staging_bytes(key), be_.max_batch());
         launcher_ = std::thread([this] { launcher_loop(); });
         completer_ = std::thread([this] { completer_loop(); });
         started_ = true;
+    }
+
+    // a slot's staging per direction: max_batch images of the key's size, or as many results
+    size_t staging_bytes(const SlotKey& key) const { return std::max(key.image_bytes(), be_.out_bytes(key.h, key.w)) * (size_t)be_.max_batch(); }
+
+    // image v of a job: its is_jpeg flag and, where the caller supplied them, its scores
+    static void set_image(Job& j, int v, bool is_jpeg, const double* scores) {
+        j.v_jpeg[v] = is_jpeg ? 1 : 0;
+        if (scores) { std::memcpy(j.v_scores[v], scores, sizeof(double) * 7); j.v_has[v] = 1; }
+    }
+
+    // The ONE staging path of every submit: a place for job j (whose key and per-image flags are set) -- the next index of a slot of its
+    // key, or, when every slot is busy or jobs are already overflowing (they keep their order), `room` bytes of its own that the
+    // launcher copies into a slot later -- then write(dst) -> bytes written puts the input there, in the caller's thread, without the
+    // lock.  `room`: what write needs at most (key.in_bytes(), or less for a file's scan).
+    //  * A throw before the job has its place (shutting down, no staging memory) reaches the submitter: no job exists.
+    //  * A throw from write comes after it -- the slot already counts on the job becoming staged -- so it is recorded: the job is staged
+    //    with nothing to decode (file_used = 0) and fails alone, with that status and reason, when its batch completes.  Only the decoded
+    //    kinds' writers can throw (file_plan checked the whole file, so file_stage cannot refuse it unless the caller changed the bytes
+    //    meanwhile; or a bad_alloc); the others are memcpys.
+    //  * On the overflow path the bytes stay in j->in, trimmed to what was written.
+    template <class Write>
+    void stage(const std::shared_ptr<Job>& j, size_t room, Write&& write) {
+        uint8_t* dst = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            start_locked(j->key);
+            const int si = overflow_.empty() ? slot_for(j->key) : -1;
+            if (si >= 0) { slot_add(si, j); dst = slots_[si].b.pin_in + j->key.in_bytes() * j->idx; }
+        }
+        const bool in_slot = dst != nullptr;
+        if (!in_slot) { j->in.resize(room); dst = j->in.data(); }
+        size_t used = 0;
+        int code = IRE_OK;
+        std::string why;
+        try { used = write(dst); }
+        catch (const Error& e) { code = e.code; why = e.msg; used = 0; }
+        catch (const std::exception& e) { code = IRE_ERR_UNAVAILABLE; why = std::string("service unavailable: ") + e.what(); used = 0; }
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            j->file_used = used;
+            if (code != IRE_OK) { j->stage_status = code; j->err = why; }
+            if (!in_slot) { j->in.resize(used); overflow_.push_back(j); cnt_.overflowed += 1; }
+            j->staged = true;
+        }
+        qcv_.notify_all();
     }
 
     // (mu_ held) a job's result has been fetched or given up: the slot is free once the last one has
@@ -426,25 +387,22 @@ class Batcher {
         qcv_.notify_all();                        // a FREE (or now evictable) slot: overflow jobs may be waiting for it
     }
 
-    // (mu_ held) an OPEN slot of this shape with room, else a FREE one opened for it, else -1.  May allocate staging (first use
+    // (mu_ held) an OPEN slot of this key with room, else a FREE one opened for it, else -1.  May allocate staging (first use
     // of a shape: once).  A DONE slot nobody is reading is evicted when nothing else is left: its unfetched outputs move to
     // their jobs' own vectors (the extra copy only a caller that lets a slot's worth of batches pile up unpolled ever pays).
-    int slot_for(int h, int w, bool files = false, int k = 0, const int* up = nullptr) {
-        static const int none[4] = {};
-        if (!up) up = none;
-        const int mb = be_.max_batch();
+    int slot_for(const SlotKey& key) {
         for (auto it = open_order_.rbegin(); it != open_order_.rend(); ++it) {
             BatchSlot& S = slots_[*it];
-            if (S.h == h && S.w == w && S.files == files && S.k == k && !std::memcmp(S.up, up, sizeof(S.up)) && (int)S.jobs.size() < capacity(S)) return *it;
+            if (S.key == key && (int)S.jobs.size() < capacity(S)) return *it;
         }
         int pick = -1;
-        const size_t need = std::max((size_t)h * w * 3, be_.out_bytes(h, w)) * (size_t)mb;
+        const size_t need = staging_bytes(key);
         for (int i = 0; i < kSlots && pick < 0; ++i) if (slots_[i].state == BatchSlot::FREE && slots_[i].b.cap >= need) pick = i;     // one whose staging exists
         for (int i = 0; i < kSlots && pick < 0; ++i) if (slots_[i].state == BatchSlot::FREE) pick = i;
         for (int i = 0; i < kSlots && pick < 0; ++i) {
             BatchSlot& S = slots_[i];
             if (S.state != BatchSlot::DONE || S.reading) continue;
-            const size_t ib = be_.out_bytes(S.h, S.w);
+            const size_t ib = be_.out_bytes(S.key.h, S.key.w);
             // job by job, each move complete before the slot forgets the job: a bad_alloc half way leaves a consistent DONE slot
             for (auto& j : S.jobs)
                 if (j->slot == &S) {
@@ -458,8 +416,8 @@ class Batcher {
         }
         if (pick < 0) return -1;
         BatchSlot& S = slots_[pick];
-        be_.reserve(S.b, need, mb);               // strong guarantee: a throw leaves the slot FREE with what it had
-        S.state = BatchSlot::OPEN; S.h = h; S.w = w; S.files = files; S.k = k; std::memcpy(S.up, up, sizeof(S.up)); S.jobs.clear(); S.h2d_issued = 0; S.unread = S.reading = 0;
+        be_.reserve(S.b, need, be_.max_batch());  // strong guarantee: a throw leaves the slot FREE with what it had
+        S.state = BatchSlot::OPEN; S.key = key; S.jobs.clear(); S.h2d_issued = 0; S.unread = S.reading = 0;
         S.status = IRE_OK; S.err.clear();
         S.first_arrival = S.last_arrival = clk::now();
         open_order_.push_back(pick);
@@ -467,13 +425,13 @@ class Batcher {
     }
 
     // jobs a slot holds: max_batch images, so max_batch / k fusion jobs of k views, and never more than one fused launch takes
-    int capacity(const BatchSlot& S) const { return S.k ? std::min(be_.max_batch() / S.k, kGroupMaxJobs) : be_.max_batch(); }
+    int capacity(const BatchSlot& S) const { return S.key.k ? std::min(be_.max_batch() / S.key.k, kGroupMaxJobs) : be_.max_batch(); }
 
     // (mu_ held) reserve the next index of slot si for job j
     void slot_add(int si, const std::shared_ptr<Job>& j) {
         BatchSlot& S = slots_[si];
         j->slot = &S; j->idx = (int)S.jobs.size();
-        const int per = std::max(1, j->views);     // images of the job: they take places idx * per .. of the slot
+        const int per = S.key.images_per_job();    // images of the job: they take places idx * per .. of the slot
         for (int v = 0; v < per; ++v) {
             const int at = j->idx * per + v;
             S.b.pin_jp[at] = j->v_jpeg[v];
@@ -494,16 +452,15 @@ class Batcher {
     // an upload and enqueues a dozen operations; submitters and pollers must not queue behind that): the slot is full or CLOSED, so
     // nobody adds to it meanwhile, and only this thread moves a slot out of OPEN / CLOSED.
     void slot_push_h2d(BatchSlot& S, std::unique_lock<std::mutex>& lk, bool closing) {
-        const size_t ib = (size_t)S.h * S.w * 3 * (size_t)std::max(1, S.k);      // a job's staged input: one image, or a fusion job's k views
         int upto = S.h2d_issued;
         while (upto < (int)S.jobs.size() && S.jobs[upto]->staged) ++upto;
         if (upto == S.h2d_issued || S.status != IRE_OK) return;
-        if (S.files && !closing && upto < be_.max_batch()) return;
+        if (S.key.decoded() && !closing && upto < be_.max_batch()) return;
         int code = IRE_OK;
         std::string why;
         try {
-            if (S.files) push_decode(S, upto, lk);
-            else be_.h2d(S.b, ib * S.h2d_issued, ib * (size_t)(upto - S.h2d_issued));
+            if (S.key.decoded()) push_decode(S, upto, lk);
+            else be_.h2d(S.b, S.key.in_bytes() * S.h2d_issued, S.key.in_bytes() * (size_t)(upto - S.h2d_issued));
         } catch (const Error& e) { code = e.code; why = e.msg; }
         catch (const std::exception& e) { code = IRE_ERR_UNAVAILABLE; why = std::string("service unavailable: ") + e.what(); }      // (a decode's host allocations)
         if (!lk.owns_lock()) lk.lock();
@@ -511,41 +468,24 @@ class Batcher {
         S.h2d_issued = upto;
     }
 
-    // (launcher) file jobs h2d_issued .. upto - 1 of the slot to the backend's decode; collects under mu_, calls without it
-    template <class BE = Backend>
+    // (launcher) jobs h2d_issued .. upto - 1 of a slot of a decoded kind to the backend's decode; collects under mu_, calls without it
     void push_decode(BatchSlot& S, int upto, std::unique_lock<std::mutex>& lk) {
-        if constexpr (has_file_jobs<BE>::value) {
-            void* heads[kMaxBatch];
-            size_t used[kMaxBatch];
-            const int first = S.h2d_issued, count = upto - first, h = S.h, w = S.w;
-            for (int i = 0; i < count; ++i) { heads[i] = S.jobs[first + i]->file.get(); used[i] = S.jobs[first + i]->file_used; }
-            int up[4];
-            std::memcpy(up, S.up, sizeof(up));
-            lk.unlock();
-            if (!up[0]) be_.decode(S.b, first, count, h, w, heads, used);
-            else if constexpr (has_upload_jobs<BE>::value) be_.decode_upload(S.b, first, count, h, w, up, heads, used);
-            else fail(IRE_ERR_INTERNAL, "internal: an upload slot on a backend without upload jobs");
-            lk.lock();
-        } else fail(IRE_ERR_INTERNAL, "internal: a file slot on a backend without file jobs");
-    }
-
-    // (launcher, no lock) the closed slot's batch to the backend: n images, or n fusion jobs of S.k views
-    template <class BE = Backend>
-    void launch_slot(BatchSlot& S, int n) {
-        if (!S.k) { be_.launch(S.b, n, S.h, S.w, S.has_sc); return; }
-        if constexpr (has_group_launch<BE>::value) be_.launch_group(S.b, n, S.k, S.h, S.w, S.has_sc);
-        else fail(IRE_ERR_INTERNAL, "internal: a fusion slot on a backend without the group launch");
+        void* heads[kMaxBatch];
+        size_t used[kMaxBatch];
+        const int first = S.h2d_issued, count = upto - first;
+        for (int i = 0; i < count; ++i) { heads[i] = S.jobs[first + i]->file.get(); used[i] = S.jobs[first + i]->file_used; }
+        const SlotKey key = S.key;
+        lk.unlock();
+        be_.decode(S.b, first, count, key, heads, used);
+        lk.lock();
     }
 
     // (mu_ held) what fails job i of a completed batch ALONE: its staging failed at submit, or the device flagged its data
-    template <class BE = Backend>
     bool job_failed_alone(BatchSlot& S, int i, Job& j) {
-        if (!S.files) return false;
         if (j.stage_status != IRE_OK) { j.status = j.stage_status; return true; }       // (j.err holds the reason since submit)
-        if constexpr (has_file_jobs<BE>::value) {
-            const int st = be_.file_status(S.b, i);
-            if (st != 0) { j.status = IRE_ERR_INVALID_INPUT; j.err = "invalid: corrupt JPEG data (decoder status " + std::to_string(st) + ")"; return true; }
-        }
+        if (!S.key.decoded()) return false;
+        const int st = be_.file_status(S.b, i);
+        if (st != 0) { j.status = IRE_ERR_INVALID_INPUT; j.err = "invalid: corrupt JPEG data (decoder status " + std::to_string(st) + ")"; return true; }
         return false;
     }
 
@@ -574,7 +514,7 @@ class Batcher {
             while (!overflow_.empty()) {
                 std::shared_ptr<Job> j = overflow_.front();
                 int si = -1;
-                try { si = slot_for(j->h, j->w, j->file != nullptr, j->views, j->up); }
+                try { si = slot_for(j->key); }
                 catch (const Error& e) { fail_job(*j, e.code, e.msg); overflow_.pop_front(); dcv_.notify_all(); continue; }
                 catch (const std::exception& e) {      // bad_alloc while evicting a DONE slot: this job fails, the service thread lives
                     fail_job(*j, IRE_ERR_UNAVAILABLE, std::string("service unavailable: ") + e.what()); overflow_.pop_front(); dcv_.notify_all(); continue;
@@ -583,7 +523,7 @@ class Batcher {
                 overflow_.pop_front();
                 slot_add(si, j);
                 BatchSlot& S = slots_[si];
-                if (!j->in.empty()) std::memcpy(S.b.pin_in + (size_t)j->h * j->w * 3 * (size_t)std::max(1, j->views) * j->idx, j->in.data(), j->in.size());
+                if (!j->in.empty()) std::memcpy(S.b.pin_in + S.key.in_bytes() * j->idx, j->in.data(), j->in.size());
                 j->in.clear(); j->in.shrink_to_fit();
             }
             if (open_order_.empty()) {
@@ -632,7 +572,7 @@ class Batcher {
             lk.unlock();
             try {
                 if (S.status != IRE_OK) throw Error{S.status, S.err};
-                launch_slot(S, n);
+                be_.launch(S.b, n, S.key, S.has_sc);       // (no lock: the slot is CLOSED, only this thread touches its key)
             } catch (const Error& e) { S.status = e.code; S.err = e.msg; }
             catch (const std::exception& e) { S.status = IRE_ERR_INTERNAL; S.err = std::string("internal: ") + e.what(); }
             if (S.status != IRE_OK) be_.drain();   // whatever was enqueued before the failure may still touch the slot's buffers

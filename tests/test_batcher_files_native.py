@@ -1,6 +1,6 @@
-"""The batcher's file jobs (csrc/batcher.hpp: submit_file and the optional backend hooks) under ThreadSanitizer and AddressSanitizer +
-UBSan on the CPU, over a host-only stub backend with the decode hook and a status word per job
-(tests/native/batcher_files_stress.cpp -- test infrastructure, as tests/native/batcher_stress.cpp is for pixel jobs): mixed file and
+"""The batcher's file jobs (csrc/batcher.hpp: submit_file and the backend's file hooks) under ThreadSanitizer and AddressSanitizer +
+UBSan on the CPU, over the host-only stub backend with its decode hook and a status word per job
+(tests/native/batcher_files_stress.cpp, batcher_stub.hpp -- test infrastructure): mixed file and
 pixel submitters never share a batch, a flagged file in the middle of a batch fails alone, refused and oversized files create no
 job, releases while gathering, and the overflow path."""
 import os

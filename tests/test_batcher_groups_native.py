@@ -1,5 +1,5 @@
-"""The batcher's fusion jobs (csrc/batcher.hpp: submit_group, slots of max_batch / k jobs, the backend's optional launch_group) under
-ThreadSanitizer and AddressSanitizer + UBSan on the CPU box, over a host-only stub backend (tests/native/batcher_groups_stress.cpp),
+"""The batcher's fusion jobs (csrc/batcher.hpp: submit_group, slots of max_batch / k jobs, the backend's launch under a Group key) under
+ThreadSanitizer and AddressSanitizer + UBSan on the CPU box, over the host-only stub backend (tests/native/batcher_groups_stress.cpp, batcher_stub.hpp),
 exactly as tests/test_batcher_native.py runs the pixel jobs' state machine."""
 import os
 import subprocess

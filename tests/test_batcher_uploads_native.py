@@ -1,6 +1,6 @@
-"""The batcher's upload jobs (csrc/batcher.hpp: submit_upload and the optional backend hooks upload_plan / decode_upload) under
-ThreadSanitizer and AddressSanitizer + UBSan on the CPU, over a host-only stub backend (tests/native/batcher_uploads_stress.cpp -- test
-infrastructure, as tests/native/batcher_files_stress.cpp is for file jobs): uploads of two keys that share an output size land in
+"""The batcher's upload jobs (csrc/batcher.hpp: submit_upload, the backend's upload_plan and its decode under an upload's key) under
+ThreadSanitizer and AddressSanitizer + UBSan on the CPU, over the host-only stub backend (tests/native/batcher_uploads_stress.cpp,
+batcher_stub.hpp -- test infrastructure): uploads of two keys that share an output size land in
 different slots, no slot mixes kinds, a refused upload creates no job, releases while pending and while in flight, shutdown with jobs
 pending."""
 import os

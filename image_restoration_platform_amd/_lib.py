@@ -18,7 +18,7 @@ IRE_ABI_VERSION = 3      # include/ire.h; load() refuses a library of another ve
 class IreConfig(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("device_index", ctypes.c_int32), ("precision", ctypes.c_int32),
                 ("max_batch", ctypes.c_int32), ("num_streams", ctypes.c_int32), ("weights_path", ctypes.c_char_p),
-                ("flags", ctypes.c_uint32)]
+                ("flags", ctypes.c_uint32), ("jpeg_quality", ctypes.c_int32), ("jpeg_sampling", ctypes.c_int32)]
 
 
 class IreTimings(ctypes.Structure):
@@ -73,6 +73,9 @@ SYMBOLS = {
     "ire_jpeg_base64_bound": (ctypes.c_size_t, [_i, _i]),
     "ire_encode_jpeg_base64_fit_device": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp]),
     "ire_encode_jpeg_base64_fit": (_i, [_vp, _u8p, _i, _i, _i, _u8p, ctypes.c_size_t, _vp]),
+    "ire_jpeg_base64_bound_ex": (ctypes.c_size_t, [_i, _i, _i, _i]),
+    "ire_encode_jpeg_base64_fit_device_ex": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _i, _i, _vp]),
+    "ire_encode_jpeg_base64_fit_ex": (_i, [_vp, _u8p, _i, _i, _i, _u8p, ctypes.c_size_t, _vp, _i, _i]),
     "ire_decode_jpeg_plan": (_i, [_u8p, ctypes.c_size_t, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "ire_decode_jpeg_plan_ex": (_i, [_u8p, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "ire_decode_jpeg": (_i, [_vp, _u8p, ctypes.c_size_t, _u8p, _i, _i]),

@@ -363,8 +363,17 @@ const char* ire_last_error(void) { return g_last_error.c_str(); }
 int ire_init(const ire_config* cfg, ire_engine** out) {
     return guarded([&] {
         if (!cfg || !out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_init");
-        if (cfg->struct_size < sizeof(ire_config)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.struct_size");
+        // the struct as it was before jpeg_quality and jpeg_sampling (flags was its last member; 4 bytes of padding behind it, which is
+        // where jpeg_quality now lies: the two fields are read only from a caller whose size covers both)
+        constexpr size_t kSizeBeforeJpeg = (offsetof(ire_config, flags) + sizeof(uint32_t) + alignof(ire_config) - 1) / alignof(ire_config) * alignof(ire_config);
+        static_assert(kSizeBeforeJpeg == 40 && sizeof(ire_config) == 48 && offsetof(ire_config, jpeg_quality) == 36, "ire_config's layout");
+        if (cfg->struct_size < kSizeBeforeJpeg) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.struct_size");
+        ire_config c{};
+        std::memcpy(&c, cfg, cfg->struct_size < sizeof(ire_config) ? kSizeBeforeJpeg : sizeof(ire_config));
+        if (cfg->struct_size < sizeof(ire_config)) c.jpeg_quality = c.jpeg_sampling = 0;
+        cfg = &c;
         check_config_flags(cfg->flags);       // (before any device is touched)
+        (void)check_config_jpeg(cfg->flags, cfg->jpeg_quality, cfg->jpeg_sampling);
         *out = nullptr;
         std::unique_ptr<ire_engine> E(new ire_engine());
         E->eng.reset(new Engine(*cfg));
@@ -555,21 +564,38 @@ int ire_encode_png_deflate_base64_fit(ire_engine* e, const uint8_t* rgb, int n, 
     });
 }
 
-size_t ire_jpeg_base64_bound(int h, int w) { return (h >= 1 && w >= 1 && h <= 8192 && w <= 8192) ? kJpeg.bound(h, w) : 0; }
+size_t ire_jpeg_base64_bound_ex(int h, int w, int quality, int sampling) {
+    if (h < 1 || w < 1 || h > 8192 || w > 8192 || quality < 0 || quality > 100 || (sampling != 0 && sampling != 2)) return 0;
+    return kJpeg.with(jpeg_settings_of(quality, sampling)).bound(h, w);
+}
 
-int ire_encode_jpeg_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes, size_t image_pitch_bytes, uint8_t* d_chars,
-                                      size_t stride_bytes, uint64_t* d_lens, void* stream) {
+int ire_encode_jpeg_base64_fit_device_ex(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes, size_t image_pitch_bytes, uint8_t* d_chars,
+                                         size_t stride_bytes, uint64_t* d_lens, int quality, int sampling, void* stream) {
     return guarded([&] {
         Engine& E = eng(e);
-        on_stream(E, (hipStream_t)stream, [&] { E.text_encoder().encode_device(kJpeg, d_rgb, n, h, w, row_pitch_bytes, image_pitch_bytes, d_chars, stride_bytes, d_lens, (hipStream_t)stream); });
+        const TextFormat f = kJpeg.with(jpeg_settings_of(quality, sampling));
+        on_stream(E, (hipStream_t)stream, [&] { E.text_encoder().encode_device(f, d_rgb, n, h, w, row_pitch_bytes, image_pitch_bytes, d_chars, stride_bytes, d_lens, (hipStream_t)stream); });
     });
 }
 
-int ire_encode_jpeg_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes, uint64_t* lens) {
+int ire_encode_jpeg_base64_fit_ex(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes, uint64_t* lens, int quality, int sampling) {
     return guarded([&] {
         Engine& E = eng(e);
-        on_stream(E, E.main_stream(), [&] { E.text_encoder().encode_host(kJpeg, rgb, n, h, w, chars, stride_bytes, lens); });
+        const TextFormat f = kJpeg.with(jpeg_settings_of(quality, sampling));
+        on_stream(E, E.main_stream(), [&] { E.text_encoder().encode_host(f, rgb, n, h, w, chars, stride_bytes, lens); });
     });
+}
+
+// the first three entries: the default settings of the three above
+size_t ire_jpeg_base64_bound(int h, int w) { return ire_jpeg_base64_bound_ex(h, w, 0, 0); }
+
+int ire_encode_jpeg_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes, size_t image_pitch_bytes, uint8_t* d_chars,
+                                      size_t stride_bytes, uint64_t* d_lens, void* stream) {
+    return ire_encode_jpeg_base64_fit_device_ex(e, d_rgb, n, h, w, row_pitch_bytes, image_pitch_bytes, d_chars, stride_bytes, d_lens, 0, 0, stream);
+}
+
+int ire_encode_jpeg_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes, uint64_t* lens) {
+    return ire_encode_jpeg_base64_fit_ex(e, rgb, n, h, w, chars, stride_bytes, lens, 0, 0);
 }
 
 int ire_decode_jpeg_plan(const uint8_t* file, size_t bytes, int* out_h, int* out_w, int* out_sampling) {

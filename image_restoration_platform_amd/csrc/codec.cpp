@@ -12,12 +12,25 @@
 
 namespace ire {
 
-const TextFormat kStoredPng = {"PNG", png_base64_chars, "ire_png_base64_bytes", png_scratch_bytes,
+const TextFormat kStoredPng = {"PNG", [](int h, int w, TextSettings) { return png_base64_chars(h, w); }, "ire_png_base64_bytes",
+                               [](int n, int h, int w, TextSettings) { return png_scratch_bytes(n, h, w); },
                                [](const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_scratch, uint8_t* d_chars, size_t stride,
-                                  uint8_t*, size_t, hipStream_t s) { encode_png_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_scratch, d_chars, stride, s); },
-                               false, false};
-const TextFormat kDeflatePng = {"PNG", png_deflate_base64_bound, "ire_png_deflate_base64_bound", png_deflate_scratch_bytes, encode_png_deflate_base64_launch, true, false};
-const TextFormat kJpeg = {"JPEG", jpeg_base64_bound, "ire_jpeg_base64_bound", jpeg_scratch_bytes, encode_jpeg_base64_launch, true, true};
+                                  uint8_t*, size_t, TextSettings, hipStream_t s) { encode_png_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_scratch, d_chars, stride, s); },
+                               false, false, {0, 0}};
+const TextFormat kDeflatePng = {"PNG", [](int h, int w, TextSettings) { return png_deflate_base64_bound(h, w); }, "ire_png_deflate_base64_bound",
+                                [](int n, int h, int w, TextSettings) { return png_deflate_scratch_bytes(n, h, w); },
+                                [](const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_scratch, uint8_t* d_chars, size_t stride,
+                                   uint8_t* d_lens, size_t lens_pitch, TextSettings, hipStream_t s) {
+                                    encode_png_deflate_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_scratch, d_chars, stride, d_lens, lens_pitch, s);
+                                },
+                                true, false, {0, 0}};
+const TextFormat kJpeg = {"JPEG", [](int h, int w, TextSettings o) { return jpeg_base64_bound(h, w, o.quality, o.sampling); }, "ire_jpeg_base64_bound",
+                          [](int n, int h, int w, TextSettings o) { return jpeg_scratch_bytes(n, h, w, o.quality, o.sampling); },
+                          [](const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_scratch, uint8_t* d_chars, size_t stride,
+                             uint8_t* d_lens, size_t lens_pitch, TextSettings o, hipStream_t s) {
+                              encode_jpeg_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_scratch, d_chars, stride, d_lens, lens_pitch, o.quality, o.sampling, s);
+                          },
+                          true, true, {kJpegDefaultQuality, kJpegDefaultSampling}};
 
 void check_config_flags(uint32_t flags) {
     constexpr uint32_t kResultBits = IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG;
@@ -27,6 +40,18 @@ void check_config_flags(uint32_t flags) {
 
 const TextFormat* result_format_of(uint32_t flags) {
     return (flags & IRE_FLAG_RESULT_PNG_DEFLATE) ? &kDeflatePng : (flags & IRE_FLAG_RESULT_JPEG) ? &kJpeg : (flags & IRE_FLAG_RESULT_PNG_BASE64) ? &kStoredPng : nullptr;
+}
+
+TextSettings jpeg_settings_of(int quality, int sampling) {
+    if (quality < 0 || quality > 100) fail(IRE_ERR_INVALID_INPUT, "invalid: JPEG quality must be in 1..100 (0: the default, 85)");
+    if (sampling != 0 && sampling != 2) fail(IRE_ERR_INVALID_INPUT, "invalid: JPEG sampling must be 0 (4:4:4) or 2 (4:2:0); 4:2:2 and grey results are not built");
+    return {quality ? quality : kJpegDefaultQuality, sampling};
+}
+
+TextSettings check_config_jpeg(uint32_t flags, int quality, int sampling) {
+    if ((quality || sampling) && !(flags & IRE_FLAG_RESULT_JPEG))
+        fail(IRE_ERR_INVALID_INPUT, "invalid ire_config: jpeg_quality or jpeg_sampling set without IRE_FLAG_RESULT_JPEG");
+    return jpeg_settings_of(quality, sampling);
 }
 
 namespace {

@@ -8,24 +8,40 @@
 
 namespace ire {
 
+// The format's settings, chosen per engine or per direct call: JPEG's quality (1..100) and sampling (0 = 4:4:4, 2 = 4:2:0).  The PNG
+// formats have none and ignore them.
+struct TextSettings { int quality, sampling; };
 struct TextFormat {
     const char* noun;                                   // the encoder as its messages name it: "PNG" | "JPEG"
-    size_t (*bound)(int h, int w);                      // the most characters an h x w image gives (stored PNG: exactly so many)
+    size_t (*bound_fn)(int h, int w, TextSettings o);   // the most characters an h x w image gives (stored PNG: exactly so many)
     const char* bound_name;                             // ... under its public name (include/ire.h)
-    size_t (*scratch_bytes)(int n, int h, int w);       // device scratch of a batch of n
+    size_t (*scratch_fn)(int n, int h, int w, TextSettings o);      // device scratch of a batch of n
     // the top-left h x w window of n images -> n texts `stride` apart and, for a counted format, their uint64 counts lens_pitch apart
-    void (*launch)(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_scratch, uint8_t* d_chars, size_t stride,
-                   uint8_t* d_lens, size_t lens_pitch, hipStream_t s);
+    void (*launch_fn)(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_scratch, uint8_t* d_chars, size_t stride,
+                      uint8_t* d_lens, size_t lens_pitch, TextSettings o, hipStream_t s);
     bool counted;                                       // the text's length depends on the pixels: a result is [uint64 count | text]
     // how the host entry fetches counted results.  false: [count | text] places whole, in ONE copy (the bound is tight: deflate);
     // true: the counts first, then only what they name (the bound is several times a real text: it doubles every byte for stuffing)
     bool counts_first;
+    TextSettings settings;                              // a row of the table holds the format's defaults; with() gives a copy with others
+    size_t bound(int h, int w) const { return bound_fn(h, w, settings); }
+    size_t scratch_bytes(int n, int h, int w) const { return scratch_fn(n, h, w, settings); }
+    void launch(const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_scratch, uint8_t* d_chars, size_t stride, uint8_t* d_lens,
+                size_t lens_pitch, hipStream_t s) const {
+        launch_fn(d_rgb, n, h, w, row_pitch, image_pitch, d_scratch, d_chars, stride, d_lens, lens_pitch, settings, s);
+    }
     size_t place_bytes(int h, int w) const { return (counted ? 8 : 0) + bound(h, w); }       // a result's place in a staging buffer
+    TextFormat with(TextSettings o) const { TextFormat f = *this; f.settings = o; return f; }
 };
-extern const TextFormat kStoredPng, kDeflatePng, kJpeg;
+extern const TextFormat kStoredPng, kDeflatePng, kJpeg;      // kJpeg: quality 85, 4:4:4
 // ire_config.flags: refuses unknown bits and two result formats | the format of the batcher's results, null: pixels
 void check_config_flags(uint32_t flags);
 const TextFormat* result_format_of(uint32_t flags);
+// JPEG settings as the ABI takes them: 0 means the default (85 | 4:4:4); refuses a quality outside 1..100 and a sampling other than 0
+// or 2 as "invalid: ..."
+TextSettings jpeg_settings_of(int quality, int sampling);
+// ire_config's two JPEG fields: jpeg_settings_of, and either field set without IRE_FLAG_RESULT_JPEG is refused
+TextSettings check_config_jpeg(uint32_t flags, int quality, int sampling);
 
 // Owns the scratch all formats share and the host entries' staging.  Every call runs under the engine's lock.
 class TextEncoder {

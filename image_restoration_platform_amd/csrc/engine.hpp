@@ -226,7 +226,7 @@ public:
     // the codecs (codec.hpp): used inside the same enter / leave bracket as every other call
     TextEncoder& text_encoder() { return enc_; }
     JpegDecoder& jpeg_decoder() { return dec_; }
-    const TextFormat* result_format() const { return result_format_; }      // of the batcher's results; null: pixels
+    const TextFormat* result_format() const { return result_format_; }      // of the batcher's results, with this engine's settings; null: pixels
 
     void debug_sums(int n, uint64_t* out);
     void debug_capture(bool on) { capture_ = on; captured_.clear(); }
@@ -299,6 +299,7 @@ private:
     int max_batch_ = 8;
     int num_lanes_ = 1;
     const TextFormat* result_format_ = nullptr;
+    TextFormat jpeg_format_ = kJpeg;      // kJpeg at ire_config's jpeg_quality and jpeg_sampling: what result_format_ points to on a JPEG engine
     int precision_ = IRE_PRECISION_BF16;
     ConvSwitches sw_;             // the A/B schedule switches, read from the environment once (conv_plan.hpp)
     int cus_ = 256;               // persistent_grid_cus(), read once

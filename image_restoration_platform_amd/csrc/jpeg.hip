@@ -1,24 +1,35 @@
 // jpeg.hip -- restored RGB pixels -> the base64 text of a baseline JPEG file, on the device.
 //
 // The two PNG results are large (4.2 MB of text per 1024^2 image stored, 0.5 - 0.93 of that Huffman-coded), and the hosts above the
-// engine are bound by exactly that payload (profiles/r04_codec_seam.json).  This file writes what the reference itself puts on the
-// wire (imagePreprocess.js:57-64: JPEG, quality 85, 4:4:4): baseline sequential DCT, Y Cb Cr at 1 x 1 each, one interleaved scan, the
-// standard's Annex K tables, and a restart interval of 16 MCUs -- which is what makes the entropy coder parallel: an interval's bits
-// depend on its own MCUs alone (DC predictors restart at 0, the interval ends on a byte).  Every step is libjpeg's published integer
-// algorithm; tests/jpeg_model.py restates them, equals libjpeg-turbo's file byte for byte (tests/test_jpeg_model.py), and the
-// device's bytes equal the model's (tests/test_jpeg_gpu.py).
+// engine are bound by exactly that payload (profiles/r04_codec_seam.json).  This file writes a baseline sequential DCT file: Y Cb Cr in
+// one interleaved scan, the standard's Annex K tables scaled to an IJG quality of 1..100, chroma at 4:4:4 or 4:2:0, and a restart
+// interval of 48 blocks (16 MCUs at 4:4:4, 8 at 4:2:0) -- which is what makes the entropy coder parallel: an interval's bits depend on
+// its own MCUs alone (DC predictors restart at 0, the interval ends on a byte).  The default, quality 85 at 4:4:4, is what the
+// reference itself puts on the wire (imagePreprocess.js:57-64).  Every step is libjpeg's published integer algorithm;
+// tests/jpeg_model.py and tests/jpeg_opt_model.py restate them, equal libjpeg-turbo's file byte for byte (tests/test_jpeg_model.py,
+// tests/test_jpeg_opt_model.py), and the device's bytes equal the models' (tests/test_jpeg_gpu.py, tests/test_jpeg_opt_gpu.py).
 //
 // Three launches per BATCH, none depending on n (image and interval are grid dimensions), no memset, no host round trip:
 //   K1 jpeg_interval_kernel   one workgroup per restart interval: pixels -> LDS (edge replication by clamped coordinates), colour
-//                             transform, the two DCT passes through LDS, quantiser + zig-zag, one WAVE per block for the symbols
-//                             (lane k = coefficient k: runs from a ballot, bit offsets from a wave scan), MSB-first bit packing into
-//                             LDS by atomic OR, byte stuffing, the interval's bytes with their RSTm / EOI marker and byte count to a
-//                             fixed-stride scratch
+//                             transform (at 4:2:0 with libjpeg's h2v2 downsample and its dummy blocks), the two DCT passes through
+//                             LDS, quantiser + zig-zag, one WAVE per block for the symbols (lane k = coefficient k: runs from a
+//                             ballot, bit offsets from a wave scan), MSB-first bit packing into LDS by atomic OR, byte stuffing, the
+//                             interval's bytes with their RSTm / EOI marker and byte count to a fixed-stride scratch
 //   K2 jpeg_gather_kernel     one workgroup per interval: prefix sum over the interval sizes, the interval's bytes to their place
 //                             behind the head; the first writes the head, the last the two lengths
 //   K3 deflate_base64_kernel  (deflate.hip) base64 over the device-side length
-// Everything is integer work, LDS integer atomics and fixed-order sums: the bytes are a pure function of the pixels.
+// Everything is integer work, LDS integer atomics and fixed-order sums: the bytes are a pure function of the pixels and the two
+// settings.  The quantiser's tables and the file's head are built on the host from jpeg_tables.hpp per launch and travel as kernel
+// arguments (768 and 629 bytes); K1 copies the tables to LDS, so one kernel body serves every quality.
+//
+// LDS.  The bit buffer and the stuffed bytes are sized by the worst interval, which grows with the quality (jpeg_tables.hpp: quality
+// 100 is the worst).  Two size classes, a template parameter: "small" holds every setting whose interval bound is at most that of
+// quality 85 at 4:2:0 (5034 bytes before stuffing; every quality up to 85 at either sampling), "big" holds quality 100.  Per
+// workgroup, of the CU's 160 KiB: small 4:4:4 31.1 KB (5 workgroups per CU, as before the settings existed: 30.0 KB), small 4:2:0
+// 34.2 KB (4), big 4:4:4 35.5 KB (4), big 4:2:0 38.7 KB (4).
 #include "jpeg.hpp"
+
+#include <atomic>
 
 #include "deflate.hpp"
 #include "jpeg_tables.hpp"
@@ -32,40 +43,87 @@ using namespace jpegtab;
 using pngbits::PngSrc;
 
 constexpr int kThreads = 256;
-constexpr int kR = kJpegR;                       // MCUs per interval
-constexpr int kBlocks = 3 * kR;                  // 8 x 8 blocks per interval, in scan order: block 3 m + c is component c of MCU m
+constexpr int kBlocks = 48;                      // 8 x 8 blocks per interval at either sampling, in scan order
 constexpr int kPlane = 72;                       // ints per block in LDS: rows of 9, so that neither DCT pass has a bank conflict
-constexpr unsigned kRawBytes = (kR * kMcuBitsMax + 7) / 8;                 // 4686: an interval's entropy-coded bytes before stuffing
-constexpr int kOutWords = (kRawBytes + 3) / 4 + 1;
-constexpr unsigned kIntBound = (unsigned)interval_bound(kR);               // 9374: stuffed, with the marker
-constexpr int kStuffWords = (kIntBound + 3) / 4 + 1;                       // (+ 1: the dword the gather may read behind the last byte)
-constexpr unsigned kIntStride = (kStuffWords * 4 + 63) / 64 * 64;          // scratch bytes per interval
-static_assert(kBlocks * kPlane >= kStuffWords, "the stuffed bytes reuse the DCT planes");
+static_assert(kJpegR * 3 == kBlocks && kJpegR420 * 6 == kBlocks, "an interval is 48 blocks");
+
+// an interval's entropy-coded bytes before stuffing, at most
+constexpr unsigned raw_bound_of(int sampling, unsigned mcu_bits) { return ((unsigned)restart_mcus(sampling) * mcu_bits + 7) / 8; }
+constexpr unsigned kBits85[2] = {mcu_bits_max(85, 0), mcu_bits_max(85, 2)}, kBits100[2] = {mcu_bits_max(100, 0), mcu_bits_max(100, 2)};
+constexpr unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
+constexpr unsigned kRawSmall = umax(raw_bound_of(0, kBits85[0]), raw_bound_of(2, kBits85[1]));       // 5034
+constexpr unsigned kRawBig = umax(raw_bound_of(0, kBits100[0]), raw_bound_of(2, kBits100[1]));       // 9448
+static_assert(kRawSmall == 5034 && kRawBig == 9448, "quality 85 and quality 100 at 4:2:0");
+static_assert(kBits100[0] < kNoCode && kBits100[1] < kNoCode, "no bound prices a symbol the tables do not have");
+
+// what depends on the sampling (kSamp: 0 | 2) and the size class
+template <int kSamp, bool kBig>
+struct Shape {
+    static constexpr int kR = restart_mcus(kSamp);                  // MCUs per interval
+    static constexpr int kP = mcu_pixels(kSamp);                    // an MCU's pixels per side
+    static constexpr int kPer = kSamp == 2 ? 6 : 3;                 // blocks per MCU
+    static constexpr int kRowDw = 3 * kP / 4;                       // dwords of one MCU's pixel row
+    static constexpr int kPxWords = kR * kP * kRowDw;               // the interval's pixels: MCU m, row r at dword (m * kP + r) * kRowDw
+    static constexpr unsigned kRawBytes = kBig ? kRawBig : kRawSmall;
+    static constexpr int kOutWords = (kRawBytes + 3) / 4 + 1;
+    static constexpr unsigned kIntBound = 2 * kRawBytes + 2;        // stuffed, with the marker
+    static constexpr int kStuffWords = (kIntBound + 3) / 4 + 1;     // (+ 1: the dword the gather may read behind the last byte)
+    static constexpr unsigned kIntStride = (kStuffWords * 4 + 63) / 64 * 64;      // scratch bytes per interval
+    static constexpr int kWorkWords = kPxWords + kBlocks * kPlane + kBlocks * 32; // pixels | DCT planes | quantised coefficients
+    static_assert(kRawBytes >= raw_bound_of(kSamp, kBig ? kBits100[kSamp / 2] : kBits85[kSamp / 2]), "the class holds its worst quality");
+    static_assert(kIntBound >= interval_bound_of(kR, kBig ? kBits100[kSamp / 2] : kBits85[kSamp / 2]), "and that interval stuffed");
+    static_assert(kWorkWords >= kStuffWords, "the stuffed bytes reuse the pixels, the DCT planes and the coefficients");
+};
+static_assert(Shape<0, false>::kIntBound >= interval_bound(kJpegR), "the default's bound");
 
 struct JpegGeom {
     int h, w;
     unsigned mcus_w;           // MCUs per row
     unsigned nmcu, nint;       // <= 2^20 MCUs, 2^16 intervals at 8192 x 8192
+    unsigned mcu_bits;         // jpegtab::mcu_bits_max of the settings
+    unsigned int_stride;       // scratch bytes per interval: Shape::kIntStride of the launch
+    int quality, sampling;
+    bool big;                  // the size class
     unsigned long long file_bound;
 };
-JpegGeom geom_of(int h, int w) {
+// the bound of an MCU runs a dynamic programme over the Huffman tables: once per setting and process
+unsigned mcu_bits_of(int quality, int sampling) {
+    if (quality == kJpegQuality) return kBits85[sampling / 2];
+    static std::atomic<unsigned> cache[101][2];
+    std::atomic<unsigned>& c = cache[quality][sampling / 2];
+    unsigned v = c.load(std::memory_order_relaxed);
+    if (!v) { v = mcu_bits_max(quality, sampling); c.store(v, std::memory_order_relaxed); }
+    return v;
+}
+JpegGeom geom_of(int h, int w, int quality, int sampling) {
+    if (!settings_ok(quality, sampling)) fail(IRE_ERR_INVALID_INPUT, "invalid settings for the JPEG encoder (quality 1..100; sampling 0 = 4:4:4 or 2 = 4:2:0)");
     JpegGeom g;
-    g.h = h; g.w = w;
-    g.mcus_w = (unsigned)(w + 7) / 8;
-    g.nmcu = g.mcus_w * ((unsigned)(h + 7) / 8);
-    g.nint = (g.nmcu + kR - 1) / kR;
-    g.file_bound = jpegtab::jpeg_file_bound(h, w);
+    const unsigned p = (unsigned)mcu_pixels(sampling), r = (unsigned)restart_mcus(sampling);
+    g.h = h; g.w = w; g.quality = quality; g.sampling = sampling;
+    g.mcus_w = ((unsigned)w + p - 1) / p;
+    g.nmcu = g.mcus_w * (((unsigned)h + p - 1) / p);
+    g.nint = (g.nmcu + r - 1) / r;
+    g.mcu_bits = mcu_bits_of(quality, sampling);
+    g.big = raw_bound_of(sampling, g.mcu_bits) > kRawSmall;
+    if (raw_bound_of(sampling, g.mcu_bits) > kRawBig) fail(IRE_ERR_INTERNAL, "internal: a JPEG interval bound beyond the largest size class");
+    g.int_stride = sampling == 2 ? (g.big ? Shape<2, true>::kIntStride : Shape<2, false>::kIntStride) : (g.big ? Shape<0, true>::kIntStride : Shape<0, false>::kIntStride);
+    g.file_bound = jpegtab::jpeg_file_bound_of(h, w, sampling, g.mcu_bits);
     return g;
 }
 
-// the quantiser per NATURAL index: the reciprocal of 8 q (jpeg_tables.hpp), half the divisor, the coefficient's zig-zag position
-struct QuantDev { unsigned recip[2][64]; unsigned short half[2][64]; unsigned char zzpos[64]; };
-constexpr QuantDev make_quant() {
-    QuantDev q{};
+// the quantiser per NATURAL index: the reciprocal of 8 q (jpeg_tables.hpp) and half the divisor; a kernel argument
+struct QuantArg { unsigned recip[2][64]; unsigned short half[2][64]; };
+QuantArg make_quant(int quality) {
+    QuantArg q{};
     for (int t = 0; t < 2; ++t)
-        for (int k = 0; k < 64; ++k) { q.recip[t][k] = quant_recip(t, k); q.half[t][k] = (unsigned short)(4 * quant_at(t, k)); }
-    for (int k = 0; k < 64; ++k) q.zzpos[kZigzag[k]] = (unsigned char)k;
+        for (int k = 0; k < 64; ++k) { q.recip[t][k] = quant_recip(t, k, quality); q.half[t][k] = (unsigned short)(4 * quant_at(t, k, quality)); }
     return q;
+}
+struct ZigzagDev { unsigned char zzpos[64]; };      // the coefficient's zig-zag position per natural index
+constexpr ZigzagDev make_zigzag() {
+    ZigzagDev z{};
+    for (int k = 0; k < 64; ++k) z.zzpos[kZigzag[k]] = (unsigned char)k;
+    return z;
 }
 struct HuffDev { unsigned ac[2][256]; unsigned dc[2][12]; };      // value | length << 16
 constexpr HuffDev make_huff() {
@@ -77,9 +135,8 @@ constexpr HuffDev make_huff() {
     }
     return h;
 }
-__constant__ QuantDev kQ = make_quant();
+__constant__ ZigzagDev kZ = make_zigzag();
 __constant__ HuffDev kH = make_huff();
-__constant__ JpegHeader kHead = jpeg_header(0, 0);      // the gather fills in SOF0's height and width
 
 // ---- libjpeg's "islow" forward DCT (jfdctint.c): 13-bit constants, 2 extra bits kept between the passes -----------------------------
 constexpr int kConstBits = 13, kPass1Bits = 2;
@@ -106,12 +163,12 @@ __device__ __forceinline__ void fdct_1d(int* d) {
     d[1] = descale(t7 * F_1_501321110 + y1 + y4, n);
 }
 
-// MSB-first bit packer into a zeroed LDS buffer of big-endian words: v (< 2^l, l in 1..32) at bit position pos, by atomic OR
-__device__ __forceinline__ void put_bits(unsigned* out, unsigned pos, unsigned v, unsigned l) {
+// MSB-first bit packer into a zeroed LDS buffer of nwords big-endian words: v (< 2^l, l in 1..32) at bit position pos, by atomic OR
+__device__ __forceinline__ void put_bits(unsigned* out, unsigned nwords, unsigned pos, unsigned v, unsigned l) {
     const unsigned wi = pos >> 5, off = pos & 31u;
     const unsigned long long x = (unsigned long long)v << (64u - off - l);
-    if (wi < (unsigned)kOutWords) atomicOr(&out[wi], (unsigned)(x >> 32));
-    if (off + l > 32u && wi + 1 < (unsigned)kOutWords) atomicOr(&out[wi + 1], (unsigned)x);
+    if (wi < nwords) atomicOr(&out[wi], (unsigned)(x >> 32));
+    if (off + l > 32u && wi + 1 < nwords) atomicOr(&out[wi + 1], (unsigned)x);
 }
 
 // What lane `lane` of a wave sends for coefficient c (zig-zag position `lane`; lane 0 holds the DC DIFFERENCE) of a block whose
@@ -138,35 +195,60 @@ __device__ __forceinline__ LaneSym lane_symbol(int c, unsigned lane, unsigned lo
     return o;
 }
 
+// The interval's blocks in scan order.  4:4:4: block 3 m + c is component c of MCU m.  4:2:0: block 6 m + j is Y00 Y01 Y10 Y11 Cb Cr
+// of MCU m.  table_of: 0 luminance, 1 chrominance.  pred_of: the block whose DC this block's is sent against, -1: none (0).  Three
+// chains; at 4:2:0 Y's runs through the four blocks of an MCU and on to the next MCU's first.
+template <int kSamp>
+__device__ __forceinline__ int table_of(unsigned blk) { return kSamp == 2 ? (blk % 6u >= 4u ? 1 : 0) : (blk % 3u ? 1 : 0); }
+template <int kSamp>
+__device__ __forceinline__ int pred_of(unsigned blk) {
+    if (kSamp != 2) return (int)blk - 3;
+    const unsigned j = blk % 6u;
+    if (j >= 1u && j < 4u) return (int)blk - 1;
+    return j == 0u ? (int)blk - 3 : (int)blk - 6;                  // (negative in the first MCU: none)
+}
+
 // K1.  blockIdx.x: the interval, blockIdx.y: the image.
-__global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, JpegGeom g, unsigned char* __restrict__ intbuf, unsigned* __restrict__ int_bytes) {
-    __shared__ unsigned s_px[kR * 8 * 6];                     // the interval's pixels: MCU m, row r at byte (m * 8 + r) * 24
-    __shared__ int s_plane[kBlocks * kPlane];                 // level-shifted samples, then coefficients; later the stuffed bytes
-    __shared__ short s_q[kBlocks * 64];                       // quantised coefficients, zig-zag order
+template <int kSamp, bool kBig>
+__global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, JpegGeom g, QuantArg qa, unsigned char* __restrict__ intbuf, unsigned* __restrict__ int_bytes) {
+    using S = Shape<kSamp, kBig>;
+    constexpr int kR = S::kR, kP = S::kP, kPer = S::kPer, kRowDw = S::kRowDw, kOutWords = S::kOutWords;
+    __shared__ unsigned s_work[S::kWorkWords];                // pixels | planes | coefficients; later the stuffed bytes over all three
     __shared__ unsigned s_out[kOutWords];                     // the entropy-coded bits, big-endian words
     __shared__ unsigned s_ac[2 * 256];
+    __shared__ unsigned s_recip[2 * 64];                      // the quantiser (QuantArg), natural order
+    __shared__ unsigned short s_half[2 * 64];
     __shared__ unsigned s_blkoff[kBlocks + 1];
     __shared__ unsigned s_scan[kThreads / 64];
+    __shared__ unsigned char s_dummy[kBlocks];                // 4:2:0: a Y block outside the image's own blocks (jpeg_opt_model.py)
+    unsigned* const s_px = s_work;                            // the interval's pixels: MCU m, row r at byte (m * kP + r) * 3 kP
+    int* const s_plane = reinterpret_cast<int*>(s_work + S::kPxWords);          // level-shifted samples, then coefficients
+    short* const s_q = reinterpret_cast<short*>(s_work + S::kPxWords + kBlocks * kPlane);      // quantised coefficients, zig-zag order
     const unsigned iv = blockIdx.x, img = blockIdx.y, t = threadIdx.x;
     const unsigned m0 = iv * (unsigned)kR;
     const unsigned nm = g.nmcu - m0 < (unsigned)kR ? g.nmcu - m0 : (unsigned)kR;
-    const unsigned nblk = 3 * nm;
+    const unsigned nblk = (unsigned)kPer * nm;
     const unsigned char* __restrict__ rgb = src.rgb + (unsigned long long)img * src.image_pitch;
 
     for (int k = t; k < kOutWords; k += kThreads) s_out[k] = 0;
     for (int k = t; k < 512; k += kThreads) s_ac[k] = kH.ac[k >> 8][k & 255];
+    if (t < 128) { s_recip[t] = qa.recip[t >> 6][t & 63u]; s_half[t] = qa.half[t >> 6][t & 63u]; }
+    if (kSamp == 2 && t < nblk) {
+        const unsigned m = t / 6u, j = t % 6u, mcu = m0 + m, my = mcu / g.mcus_w, mx = mcu - my * g.mcus_w;
+        s_dummy[t] = j < 4u && ((2 * mx + (j & 1u)) * 8 >= (unsigned)g.w || (2 * my + (j >> 1)) * 8 >= (unsigned)g.h) ? 1 : 0;
+    }
 
     // 1. pixels -> LDS.  Item = one dword of one MCU's pixel row; consecutive threads take consecutive dwords of a pixel row across
     //    the interval's MCUs.  A dword that is 4-aligned in memory and inside the row is loaded whole, any other byte by byte with
     //    the coordinates clamped (edge replication).
     const unsigned row_bytes = 3u * (unsigned)g.w;
-    for (unsigned idx = t; idx < (unsigned)(kR * 48); idx += kThreads) {
-        const unsigned r = idx / (kR * 6), rem = idx % (kR * 6), m = rem / 6, k = rem % 6;
+    for (unsigned idx = t; idx < (unsigned)S::kPxWords; idx += kThreads) {
+        const unsigned r = idx / (kR * kRowDw), rem = idx % (kR * kRowDw), m = rem / kRowDw, k = rem % kRowDw;
         if (m >= nm) continue;
         const unsigned mcu = m0 + m, my = mcu / g.mcus_w, mx = mcu - my * g.mcus_w;
-        const unsigned y = min(my * 8 + r, (unsigned)g.h - 1);
+        const unsigned y = min(my * kP + r, (unsigned)g.h - 1);
         const unsigned char* __restrict__ p = rgb + (unsigned long long)y * src.row_pitch;
-        const unsigned b0 = mx * 24 + 4 * k;
+        const unsigned b0 = mx * (3 * kP) + 4 * k;
         unsigned v;
         if (b0 + 4 <= row_bytes && ((reinterpret_cast<unsigned long long>(p) + b0) & 3u) == 0) v = *reinterpret_cast<const unsigned*>(p + b0);
         else {
@@ -177,20 +259,53 @@ __global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, Jpe
                 v |= (unsigned)p[3 * x + ch] << (8 * b);
             }
         }
-        s_px[(m * 8 + r) * 6 + k] = v;
+        s_px[(m * kP + r) * kRowDw + k] = v;
     }
     __syncthreads();
 
     // 2. RGB -> Y Cb Cr (jccolor.c: 16-bit fixed point, + 32768 to round, chroma offset 128), level shift by 128
     const unsigned char* s_pb = reinterpret_cast<const unsigned char*>(s_px);
-    for (unsigned pix = t; pix < nm * 64; pix += kThreads) {
-        const unsigned m = pix >> 6, r = (pix >> 3) & 7u, c = pix & 7u;
-        const unsigned char* q = s_pb + (m * 8 + r) * 24 + 3 * c;
-        const int R = q[0], G = q[1], B = q[2];
-        int* o = s_plane + 3 * m * kPlane + r * 9 + c;
-        o[0] = ((19595 * R + 38470 * G + 7471 * B + 32768) >> 16) - 128;
-        o[kPlane] = ((-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16) - 128;
-        o[2 * kPlane] = ((32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16) - 128;
+    if (kSamp != 2) {
+        for (unsigned pix = t; pix < nm * 64; pix += kThreads) {
+            const unsigned m = pix >> 6, r = (pix >> 3) & 7u, c = pix & 7u;
+            const unsigned char* q = s_pb + (m * 8 + r) * 24 + 3 * c;
+            const int R = q[0], G = q[1], B = q[2];
+            int* o = s_plane + 3 * m * kPlane + r * 9 + c;
+            o[0] = ((19595 * R + 38470 * G + 7471 * B + 32768) >> 16) - 128;
+            o[kPlane] = ((-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16) - 128;
+            o[2 * kPlane] = ((32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16) - 128;
+        }
+    } else {
+        // Y of every pixel of the 16 x 16 MCU into its four blocks (the clamped load is libjpeg's padding of Y; a dummy block's
+        // samples are never used)
+        for (unsigned pix = t; pix < nm * 256; pix += kThreads) {
+            const unsigned m = pix >> 8, r = (pix >> 4) & 15u, c = pix & 15u;
+            const unsigned char* q = s_pb + (m * 16 + r) * 48 + 3 * c;
+            const int R = q[0], G = q[1], B = q[2];
+            s_plane[(6 * m + 2 * (r >> 3) + (c >> 3)) * kPlane + (r & 7u) * 9 + (c & 7u)] = ((19595 * R + 38470 * G + 7471 * B + 32768) >> 16) - 128;
+        }
+        // Cb and Cr: jcsample.c's h2v2_downsample, (a + b + c + d + bias) >> 2 over the 2 x 2 cell, bias 1 in even output columns and
+        // 2 in odd ones.  To the right the cell's pixels are the clamped load's (the last column replicated).  Downwards libjpeg
+        // replicates the last DOWNSAMPLED row, which took rows 2 J and min(2 J + 1, h - 1), J = ceil(h / 2) - 1: so chroma row cy
+        // takes the cell of row min(cy, J), whose second row is again the clamped load's.
+        const unsigned last_cy = ((unsigned)g.h + 1) / 2 - 1;
+        for (unsigned idx = t; idx < nm * 64; idx += kThreads) {
+            const unsigned m = idx >> 6, cr = (idx >> 3) & 7u, cc = idx & 7u;
+            const unsigned my = (m0 + m) / g.mcus_w;
+            const unsigned la = 2 * (min(my * 8 + cr, last_cy) - my * 8);      // the cell's first row inside the MCU: 0..14
+            const unsigned char* q = s_pb + (m * 16 + la) * 48 + 6 * cc;
+            int cb = (int)(cc & 1u) + 1, crv = cb;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const unsigned char* e = q + (k >> 1) * 48 + (k & 1) * 3;
+                const int R = e[0], G = e[1], B = e[2];
+                cb += (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16;
+                crv += (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
+            }
+            int* o = s_plane + (6 * m + 4) * kPlane + cr * 9 + cc;
+            o[0] = (cb >> 2) - 128;
+            o[kPlane] = (crv >> 2) - 128;
+        }
     }
     __syncthreads();
 
@@ -207,7 +322,8 @@ __global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, Jpe
     __syncthreads();
     for (unsigned item = t; item < nblk * 8; item += kThreads) {
         const unsigned blk = item >> 3, col = item & 7u;
-        const int tb = blk % 3 ? 1 : 0;
+        const int tb = table_of<kSamp>(blk);
+        const bool dummy = kSamp == 2 && s_dummy[blk];
         const int* p = s_plane + blk * kPlane + col;
         int d[8];
 #pragma unroll
@@ -216,21 +332,30 @@ __global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, Jpe
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const unsigned nat = 8 * k + col;
-            const unsigned mag = (unsigned)(d[k] < 0 ? -d[k] : d[k]) + kQ.half[tb][nat];
-            const int qv = (int)__umulhi(mag, kQ.recip[tb][nat]);              // floor(mag / (8 q)): jpeg_tables.hpp
-            s_q[blk * 64 + kQ.zzpos[nat]] = (short)(d[k] < 0 ? -qv : qv);
+            const unsigned mag = (unsigned)(d[k] < 0 ? -d[k] : d[k]) + s_half[tb * 64 + nat];
+            const int qv = (int)__umulhi(mag, s_recip[tb * 64 + nat]);         // floor(mag / (8 q)): jpeg_tables.hpp
+            s_q[blk * 64 + kZ.zzpos[nat]] = dummy ? (short)0 : (short)(d[k] < 0 ? -qv : qv);
         }
     }
     __syncthreads();
+    if (kSamp == 2) {
+        // a dummy block's quantised DC is that of the block before it in the MCU (jccoefct.c): one thread per MCU walks its Y blocks
+        if (t < nm)
+            for (unsigned j = 1; j < 4; ++j)
+                if (s_dummy[6 * t + j]) s_q[(6 * t + j) * 64] = s_q[(6 * t + j - 1) * 64];
+        __syncthreads();
+    }
 
     // 5. bits per block: one wave per block, lane k = zig-zag position k.  The DC differences need no order: every DC is known.
     const unsigned wv = t >> 6, lane = t & 63u;
     for (unsigned blk = wv; blk < nblk; blk += kThreads / 64) {
         int c = s_q[blk * 64 + lane];
-        if (lane == 0 && blk >= 3) c -= s_q[(blk - 3) * 64];
+        const int pb = pred_of<kSamp>(blk);
+        if (lane == 0 && pb >= 0) c -= s_q[pb * 64];
         const unsigned long long mask = __ballot(c != 0) & ~1ull;
-        const LaneSym sy = lane_symbol(c, lane, mask, blk % 3 ? 1 : 0, s_ac);
-        unsigned bits = sy.nb + sy.nzrl * (s_ac[(blk % 3 ? 256 : 0) + 0xf0] >> 16);
+        const int tb = table_of<kSamp>(blk);
+        const LaneSym sy = lane_symbol(c, lane, mask, tb, s_ac);
+        unsigned bits = sy.nb + sy.nzrl * (s_ac[tb * 256 + 0xf0] >> 16);
         for (int off = 32; off >= 1; off >>= 1) bits += __shfl_down(bits, off, 64);
         if (lane == 0) s_blkoff[blk + 1] = bits;
     }
@@ -245,9 +370,10 @@ __global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, Jpe
     // 7. emit: a wave scan gives each lane its place in the block
     for (unsigned blk = wv; blk < nblk; blk += kThreads / 64) {
         int c = s_q[blk * 64 + lane];
-        if (lane == 0 && blk >= 3) c -= s_q[(blk - 3) * 64];
+        const int pb = pred_of<kSamp>(blk);
+        if (lane == 0 && pb >= 0) c -= s_q[pb * 64];
         const unsigned long long mask = __ballot(c != 0) & ~1ull;
-        const int tb = blk % 3 ? 1 : 0;
+        const int tb = table_of<kSamp>(blk);
         const LaneSym sy = lane_symbol(c, lane, mask, tb, s_ac);
         const unsigned zrl = s_ac[tb * 256 + 0xf0];
         const unsigned mine = sy.nb + sy.nzrl * (zrl >> 16);
@@ -255,13 +381,13 @@ __global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, Jpe
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) { const unsigned o = __shfl_up(inc, off, 64); if ((int)lane >= off) inc += o; }
         unsigned pos = s_blkoff[blk] + inc - mine;
-        for (unsigned k = 0; k < sy.nzrl; ++k) { put_bits(s_out, pos, zrl & 0xffffu, zrl >> 16); pos += zrl >> 16; }
-        if (sy.nb) put_bits(s_out, pos, sy.bits, sy.nb);
+        for (unsigned k = 0; k < sy.nzrl; ++k) { put_bits(s_out, kOutWords, pos, zrl & 0xffffu, zrl >> 16); pos += zrl >> 16; }
+        if (sy.nb) put_bits(s_out, kOutWords, pos, sy.bits, sy.nb);
     }
     const unsigned total_bits = s_blkoff[nblk];
     unsigned raw = (total_bits + 7) / 8;                         // bytes before stuffing; the last one is padded with 1-bits
-    if (raw > kRawBytes) raw = kRawBytes;                        // (cannot happen: jpeg_tables.hpp; nothing is ever written past the bound)
-    if (t == 0 && (total_bits & 7u)) put_bits(s_out, total_bits, (1u << (8 - (total_bits & 7u))) - 1u, 8 - (total_bits & 7u));
+    if (raw > S::kRawBytes) raw = S::kRawBytes;                  // (cannot happen: jpeg_tables.hpp; nothing is ever written past the bound)
+    if (t == 0 && (total_bits & 7u)) put_bits(s_out, kOutWords, total_bits, (1u << (8 - (total_bits & 7u))) - 1u, 8 - (total_bits & 7u));
     __syncthreads();
 
     // 8. stuffing: thread t takes bytes [per t, per t + per); a scan over the 0xFF counts gives each byte its place
@@ -277,16 +403,16 @@ __global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, Jpe
     unsigned before = inc - nff, all_ff = 0;
 #pragma unroll
     for (unsigned k = 0; k < kThreads / 64; ++k) { const unsigned x = s_scan[k]; if (k < wv) before += x; all_ff += x; }
-    unsigned char* s_st = reinterpret_cast<unsigned char*>(s_plane);           // (the planes were last read before two barriers)
+    unsigned char* s_st = reinterpret_cast<unsigned char*>(s_work);            // (pixels, planes and coefficients were last read before two barriers)
     unsigned o = i0 + before;
     for (unsigned i = i0; i < i1; ++i) {
         const unsigned b = (s_out[i >> 2] >> (24 - 8 * (i & 3u))) & 0xffu;
-        if (o < kIntBound) s_st[o] = (unsigned char)b;
+        if (o < S::kIntBound) s_st[o] = (unsigned char)b;
         ++o;
-        if (b == 0xffu) { if (o < kIntBound) s_st[o] = 0; ++o; }
+        if (b == 0xffu) { if (o < S::kIntBound) s_st[o] = 0; ++o; }
     }
     unsigned bytes = raw + all_ff + 2;
-    const unsigned bound = (unsigned)interval_bound(nm);
+    const unsigned bound = (unsigned)interval_bound_of(nm, g.mcu_bits);      // (<= S::kIntBound: geom_of chose the class by it)
     if (bytes > bound) bytes = bound;
     if (t == 0) {                                                // RST(m mod 8) behind every interval but the last, EOI behind the last
         s_st[bytes - 2] = 0xff;
@@ -295,20 +421,19 @@ __global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, Jpe
     __syncthreads();
     // 9. the interval's bytes and their count to the scratch
     const unsigned long long slot = (unsigned long long)img * g.nint + iv;
-    unsigned* dst = reinterpret_cast<unsigned*>(intbuf + slot * kIntStride);
-    const unsigned* s_sw = reinterpret_cast<const unsigned*>(s_plane);
-    for (unsigned k = t; k < (bytes + 3) / 4 + 1; k += kThreads) dst[k] = s_sw[k];      // (+ 1: the dword the gather may read behind the last byte)
+    unsigned* dst = reinterpret_cast<unsigned*>(intbuf + slot * g.int_stride);
+    for (unsigned k = t; k < (bytes + 3) / 4 + 1; k += kThreads) dst[k] = s_work[k];      // (+ 1: the dword the gather may read behind the last byte)
     if (t == 0) int_bytes[slot] = bytes;
 }
 
 // K2.  The interval's bytes to their place in the file; the head by interval 0, the lengths by the last interval.
-__global__ __launch_bounds__(kThreads) void jpeg_gather_kernel(JpegGeom g, const unsigned char* __restrict__ intbuf, const unsigned* __restrict__ int_bytes,
+__global__ __launch_bounds__(kThreads) void jpeg_gather_kernel(JpegGeom g, JpegHeader head, const unsigned char* __restrict__ intbuf, const unsigned* __restrict__ int_bytes,
                                                                 unsigned char* __restrict__ files, unsigned long long file_pitch, unsigned long long* __restrict__ flen,
                                                                 unsigned char* __restrict__ lens, unsigned long long lens_pitch) {
     __shared__ unsigned s_red[2][kThreads / 64];
     const unsigned iv = blockIdx.x, img = blockIdx.y, t = threadIdx.x;
     const unsigned* sizes = int_bytes + (unsigned long long)img * g.nint;
-    unsigned before = 0, all = 0;                                 // (integers: a sum in any order; < 2^16 * 9374 < 2^30)
+    unsigned before = 0, all = 0;                                 // (integers: a sum in any order; < 2^16 * 18898 < 2^31)
     for (unsigned k = t; k < g.nint; k += kThreads) { const unsigned s = sizes[k]; all += s; if (k < iv) before += s; }
     for (int off = 32; off >= 1; off >>= 1) { before += __shfl_down(before, off, 64); all += __shfl_down(all, off, 64); }
     if ((t & 63) == 0) { s_red[0][t >> 6] = before; s_red[1][t >> 6] = all; }
@@ -316,7 +441,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_gather_kernel(JpegGeom g, const
     before = all = 0;
     for (int k = 0; k < kThreads / 64; ++k) { before += s_red[0][k]; all += s_red[1][k]; }
     unsigned char* __restrict__ file = files + (unsigned long long)img * file_pitch;
-    const unsigned char* __restrict__ srcb = intbuf + ((unsigned long long)img * g.nint + iv) * kIntStride;
+    const unsigned char* __restrict__ srcb = intbuf + ((unsigned long long)img * g.nint + iv) * g.int_stride;
     const unsigned size = sizes[iv];
     const unsigned d0 = kHeaderBytes + before;                    // file offset of the interval's first byte (file_pitch is a multiple of 4)
     // [d0, d0 + size): bytes up to the first dword boundary, whole dwords, bytes again: no dword is shared with a neighbour's stores
@@ -334,10 +459,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_gather_kernel(JpegGeom g, const
     }
     if (t < ntail) file[d0 + nhead + 4 * ndw + t] = srcb[nhead + 4 * ndw + t];
     if (iv == 0)
-        for (unsigned k = t; k < (unsigned)kHeaderBytes; k += kThreads) {
-            const unsigned d = k - (unsigned)kSofDims;            // SOF0: height, width, two big-endian bytes each
-            file[k] = d < 4u ? (unsigned char)((d < 2u ? g.h : g.w) >> (d & 1u ? 0 : 8)) : kHead.b[k];
-        }
+        for (unsigned k = t; k < (unsigned)kHeaderBytes; k += kThreads) file[k] = head.b[k];      // (jpeg_header of the launch's h, w and settings)
     if (iv + 1 == g.nint) {
         const unsigned long long fl = (unsigned long long)kHeaderBytes + all;
         if (t < 48) { const unsigned long long o = fl + t; if (o < file_pitch) file[o] = 0; }      // what the last base64 thread reads behind the file
@@ -357,8 +479,8 @@ ScratchLayout layout_of(int n, const JpegGeom& g) {
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     L.flen = 0;                                                      // n x u64
     L.int_bytes = up((size_t)n * 8);                                 // n x nint u32
-    L.intbuf = up(L.int_bytes + (size_t)n * g.nint * 4);             // n x nint x kIntStride
-    L.files = up(L.intbuf + (size_t)n * g.nint * kIntStride);
+    L.intbuf = up(L.int_bytes + (size_t)n * g.nint * 4);             // n x nint x int_stride
+    L.files = up(L.intbuf + (size_t)n * g.nint * g.int_stride);
     L.file_pitch = up(((size_t)g.file_bound + 11) / 12 * 12 + 16);   // (the 12-byte groups of the last base64 threads stay inside)
     L.total = L.files + L.file_pitch * (size_t)n;
     return L;
@@ -366,24 +488,32 @@ ScratchLayout layout_of(int n, const JpegGeom& g) {
 
 }  // namespace
 
-size_t jpeg_file_bound(int h, int w) { return jpegtab::jpeg_file_bound(h, w); }
-size_t jpeg_base64_bound(int h, int w) { return jpegtab::jpeg_base64_bound(h, w); }
-size_t jpeg_scratch_bytes(int n, int h, int w) { return layout_of(n, geom_of(h, w)).total; }
+size_t jpeg_file_bound(int h, int w, int quality, int sampling) { return geom_of(h, w, quality, sampling).file_bound; }
+size_t jpeg_base64_bound(int h, int w, int quality, int sampling) { return ((size_t)geom_of(h, w, quality, sampling).file_bound + 2) / 3 * 4; }
+size_t jpeg_scratch_bytes(int n, int h, int w, int quality, int sampling) { return layout_of(n, geom_of(h, w, quality, sampling)).total; }
 
 void encode_jpeg_base64_launch(const unsigned char* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, unsigned char* d_scratch, unsigned char* d_chars,
-                               size_t text_pitch, unsigned char* d_lens, size_t lens_pitch, hipStream_t s) {
+                               size_t text_pitch, unsigned char* d_lens, size_t lens_pitch, int quality, int sampling, hipStream_t s) {
     if (n < 1 || n > 65535 || h <= 0 || w <= 0 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the JPEG encoder (1..8192 per side)");
     if (row_pitch < (size_t)3 * w) fail(IRE_ERR_INVALID_INPUT, "invalid row pitch for the JPEG encoder (< 3*w)");
-    const JpegGeom g = geom_of(h, w);
+    const JpegGeom g = geom_of(h, w, quality, sampling);
     const ScratchLayout L = layout_of(n, g);
     unsigned long long* flen = reinterpret_cast<unsigned long long*>(d_scratch + L.flen);
     unsigned* int_bytes = reinterpret_cast<unsigned*>(d_scratch + L.int_bytes);
     unsigned char* intbuf = d_scratch + L.intbuf;
     unsigned char* files = d_scratch + L.files;
     const PngSrc src{d_rgb, (unsigned long long)row_pitch, (unsigned long long)image_pitch};
-    hipLaunchKernelGGL(jpeg_interval_kernel, dim3(g.nint, n), dim3(kThreads), 0, s, src, g, intbuf, int_bytes);
-    hipLaunchKernelGGL(jpeg_gather_kernel, dim3(g.nint, n), dim3(kThreads), 0, s, g, intbuf, int_bytes, files, (unsigned long long)L.file_pitch, flen, d_lens,
-                       (unsigned long long)lens_pitch);
+    const QuantArg qa = make_quant(quality);
+    const dim3 grid(g.nint, n);
+    if (sampling == 2) {
+        if (g.big) hipLaunchKernelGGL((jpeg_interval_kernel<2, true>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes);
+        else hipLaunchKernelGGL((jpeg_interval_kernel<2, false>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes);
+    } else {
+        if (g.big) hipLaunchKernelGGL((jpeg_interval_kernel<0, true>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes);
+        else hipLaunchKernelGGL((jpeg_interval_kernel<0, false>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes);
+    }
+    hipLaunchKernelGGL(jpeg_gather_kernel, grid, dim3(kThreads), 0, s, g, jpeg_header(h, w, quality, sampling), intbuf, int_bytes, files, (unsigned long long)L.file_pitch, flen,
+                       d_lens, (unsigned long long)lens_pitch);
     base64_device_length_launch(files, L.file_pitch, flen, (size_t)g.file_bound, n, d_chars, text_pitch, s);
     IRE_HIP(hipGetLastError());
 }

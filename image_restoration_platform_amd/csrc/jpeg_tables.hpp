@@ -1,10 +1,13 @@
-// jpeg_tables.hpp -- everything about the device's JPEG file that needs no GPU: the two quantisation tables at quality 85, the
-// zig-zag order, the Annex K Huffman tables as (code, length) per symbol, the file's head for a given (h, w), and the size bound
-// with its derivation.  Host-only, header-only, plain C++17: jpeg.hip initialises its __constant__ tables from the constexpr
-// functions here, tests/native/jpeg_tables_dump.cpp prints all of it for comparison with tests/jpeg_model.py.
+// jpeg_tables.hpp -- everything about the device's JPEG file that needs no GPU: the two quantisation tables at any IJG quality, the
+// zig-zag order, the Annex K Huffman tables as (code, length) per symbol, the file's head for a given (h, w, quality, sampling), and
+// the size bound with its derivation.  Host-only, header-only, plain C++17: jpeg.hip builds the tables it passes to its kernels from
+// the constexpr functions here, tests/native/jpeg_tables_dump.cpp and jpeg_opt_tables_dump.cpp print all of it for comparison with
+// tests/jpeg_model.py and tests/jpeg_opt_model.py.
 //
-// The format (tests/jpeg_model.py states it in full): baseline sequential DCT, 8 bit, Y Cb Cr at 1 x 1 each (4:4:4), one interleaved
-// scan, a restart interval of kJpegR MCUs in raster order.
+// The format (the two models state it in full): baseline sequential DCT, 8 bit, one interleaved scan of Y Cb Cr, a restart interval
+// in raster order of MCUs.  Two settings: quality 1..100 and sampling, numbered as ire_decode_jpeg_plan numbers it: 0 = 4:4:4 (an MCU
+// is Y Cb Cr, 8 x 8 pixels, kJpegR = 16 MCUs per interval), 2 = 4:2:0 (an MCU is Y00 Y01 Y10 Y11 Cb Cr, 16 x 16 pixels, kJpegR420 = 8
+// MCUs per interval: 48 blocks and 128 pixels across either way).  Every name without the two settings is the (85, 0) instance.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -13,8 +16,12 @@
 namespace ire {
 namespace jpegtab {
 
-constexpr int kJpegR = 16;               // MCUs per restart interval
+constexpr int kJpegR = 16;               // MCUs per restart interval at 4:4:4
+constexpr int kJpegR420 = 8;             // ... at 4:2:0
 constexpr int kJpegQuality = 85;
+constexpr bool settings_ok(int quality, int sampling) { return quality >= 1 && quality <= 100 && (sampling == 0 || sampling == 2); }
+constexpr int restart_mcus(int sampling) { return sampling == 2 ? kJpegR420 : kJpegR; }
+constexpr int mcu_pixels(int sampling) { return sampling == 2 ? 16 : 8; }      // per side
 constexpr int kHeaderBytes = 629;        // SOI 2 | APP0 18 | DQT 69 x 2 | SOF0 19 | DHT 33 + 183 + 33 + 183 | DRI 6 | SOS 14
 constexpr int kSofDims = 2 + 18 + 69 + 69 + 5;      // file offset of SOF0's height (2 bytes, then the width's 2)
 
@@ -31,20 +38,21 @@ constexpr unsigned char kZigzag[64] = {
 
 // IJG quality scaling, baseline: (q * scale + 50) / 100 clamped to 1..255, scale = 200 - 2 * quality above 50.  table 0: luminance,
 // 1: chrominance; natural order.
-constexpr int quant_at(int table, int natural) {
-    const int scale = kJpegQuality < 50 ? 5000 / kJpegQuality : 200 - 2 * kJpegQuality;
+constexpr int quant_at(int table, int natural, int quality) {
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
     const int v = ((table ? kK2Chrominance[natural] : kK1Luminance[natural]) * scale + 50) / 100;
     return v < 1 ? 1 : v > 255 ? 255 : v;
 }
+constexpr int quant_at(int table, int natural) { return quant_at(table, natural, kJpegQuality); }
 
 // ---- the quantiser's division as a multiplication --------------------------------------------------------------------------------
 // q(c) = sign(c) * floor((|c| + d / 2) / d), d = 8 * quant.  With M = ceil(2^32 / d), e = M d - 2^32 lies in [0, d) and
-// floor(x / d) = (x * M) >> 32 for every x with x * e < 2^32: x <= 8208 + 1020 < 2^14 here and e < d <= 2040 < 2^11.
-// tests/native/jpeg_tables_dump.cpp checks the identity for every divisor and every x < 2^16.
-constexpr unsigned quant_recip(int table, int natural) {
-    const unsigned long long d = 8ull * (unsigned)quant_at(table, natural);
-    return (unsigned)(((1ull << 32) + d - 1) / d);
-}
+// floor(x / d) = (x * M) >> 32 for every x with x * e < 2^32: x <= 8208 + 1020 < 2^14 here and e < d <= 2040 < 2^11.  That holds
+// for every divisor the clamp 1..255 allows (d = 8 .. 2040), so for every quality.  tests/native/jpeg_tables_dump.cpp checks the
+// identity for the divisors of quality 85 and every x < 2^16, jpeg_opt_tables_dump.cpp for every d = 8 q, q in 1..255.
+constexpr unsigned recip_of(unsigned d) { return (unsigned)(((1ull << 32) + d - 1) / d); }
+constexpr unsigned quant_recip(int table, int natural, int quality) { return recip_of(8u * (unsigned)quant_at(table, natural, quality)); }
+constexpr unsigned quant_recip(int table, int natural) { return quant_recip(table, natural, kJpegQuality); }
 
 // ---- Annex K Huffman tables -------------------------------------------------------------------------------------------------------
 constexpr unsigned char kDcLumBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
@@ -86,7 +94,7 @@ constexpr HuffCodes ac_codes(int table) { return huff_codes(table ? kAcChrBits :
 
 // ---- the file's head --------------------------------------------------------------------------------------------------------------
 struct JpegHeader { unsigned char b[kHeaderBytes]; };
-constexpr JpegHeader jpeg_header(int h, int w) {
+constexpr JpegHeader jpeg_header(int h, int w, int quality, int sampling) {
     JpegHeader o{};
     int n = 0;
     auto put = [&](int v) { o.b[n++] = (unsigned char)v; };
@@ -97,11 +105,11 @@ constexpr JpegHeader jpeg_header(int h, int w) {
     for (int t = 0; t < 2; ++t) {
         seg(0xdb, 65);
         put(t);
-        for (int k = 0; k < 64; ++k) put(quant_at(t, kZigzag[k]));
+        for (int k = 0; k < 64; ++k) put(quant_at(t, kZigzag[k], quality));
     }
     seg(0xc0, 15);
     put(8); put(h >> 8); put(h & 0xff); put(w >> 8); put(w & 0xff); put(3);
-    for (int v : {1, 0x11, 0, 2, 0x11, 1, 3, 0x11, 1}) put(v);
+    for (int v : {1, sampling == 2 ? 0x22 : 0x11, 0, 2, 0x11, 1, 3, 0x11, 1}) put(v);      // Y at 2 x 2 for 4:2:0
     for (int t = 0; t < 2; ++t) {
         seg(0xc4, 1 + 16 + 12);
         put(t);
@@ -113,11 +121,12 @@ constexpr JpegHeader jpeg_header(int h, int w) {
         for (int k = 0; k < 162; ++k) put((t ? kAcChrVals : kAcLumVals)[k]);
     }
     seg(0xdd, 2);
-    put(kJpegR >> 8); put(kJpegR & 0xff);
+    put(restart_mcus(sampling) >> 8); put(restart_mcus(sampling) & 0xff);
     seg(0xda, 10);
     for (int v : {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0}) put(v);
     return o;      // n == kHeaderBytes (checked by the native test)
 }
+constexpr JpegHeader jpeg_header(int h, int w) { return jpeg_header(h, w, kJpegQuality, 0); }
 
 // ---- the size bound ---------------------------------------------------------------------------------------------------------------
 // 1. Amplitudes.  The forward DCT's output, scaled by 8 as the "islow" algorithm leaves it, of samples in -128..127 is in magnitude at
@@ -134,28 +143,42 @@ constexpr unsigned short kCoefMax[64] = {
     7584, 6874, 7008, 6874, 7584, 6874, 7008, 6874,
     7439, 6742, 6874, 6742, 7439, 6742, 6874, 6742};
 constexpr int bit_length(unsigned v) { int n = 0; while (v) { ++n; v >>= 1; } return n; }
-// 2. Categories.  The largest magnitude category ("size") at zig-zag position k: of the quantised amplitude bound, and at k = 0 of
-//    twice that (the DC is sent as a difference).
-constexpr int size_max(int table, int k) {
-    const int nat = kZigzag[k], q = quant_at(table, nat);
-    const unsigned m = (kCoefMax[nat] + 4u * q) / (8u * q);
-    return bit_length(k == 0 ? 2 * m : m);
+//    Four terms are EXACT in islow, formed by additions and shifts alone: those with both frequencies in {0, 4}.  The first pass
+//    leaves 4 * (a sum or difference of the row's samples), the second descales a sum or difference of eight of those by 2 bits.  So
+//    the DC is the sum of the 64 samples, in -8192 .. 8128, and each of the other three is a sum of 32 samples minus a sum of 32
+//    others, at most 32 * 128 + 32 * 127 = 8160 in magnitude.  At quality 100 (every divisor 8) the slack in kCoefMax would put
+//    them into categories the Huffman tables do not have; the exact values do not.
+constexpr unsigned kDcNegMax = 8192, kDcPosMax = 8128, kExactAcMax = 8160;
+constexpr unsigned coef_bound(int natural) { return (natural == 4 || natural == 32 || natural == 36) ? kExactAcMax : kCoefMax[natural]; }
+// 2. Categories.  The largest magnitude category ("size") at zig-zag position k of the quantised amplitude bound; at k = 0 of the
+//    largest DC DIFFERENCE, the most negative quantised DC against the most positive.  At the smallest divisor that is 1024 + 1016 =
+//    2040: category 11, the last the DC tables have.  An AC amplitude is at most (8160 + 4) / 8 = 1020: category 10, the last the AC
+//    tables have (libjpeg's own limit).
+constexpr int size_max(int table, int k, int quality) {
+    const int nat = kZigzag[k];
+    const unsigned q = (unsigned)quant_at(table, nat, quality);
+    if (k == 0) return bit_length((kDcNegMax + 4u * q) / (8u * q) + (kDcPosMax + 4u * q) / (8u * q));
+    return bit_length((coef_bound(nat) + 4u * q) / (8u * q));
 }
+constexpr int size_max(int table, int k) { return size_max(table, k, kJpegQuality); }
 // 3. One block.  The exact maximum, over every sequence of (run, size) symbols whose sizes respect step 2, of the bits they take with
 //    the fixed tables: dynamic programming over the position p of the last non-zero coefficient so far.  best[p] = the most bits of
 //    the DC and positions 1..p when p is non-zero; a run of r zeros before p costs floor(r / 16) ZRL codes and the code of
-//    (r mod 16, size); a block whose last non-zero lies before 63 ends with EOB.
-constexpr unsigned block_bits_max(int table) {
+//    (r mod 16, size); a block whose last non-zero lies before 63 ends with EOB.  A size without a code costs kNoCode bits, not none:
+//    were step 2 ever to allow one, every bound below would be absurd and jpeg.hip's static_asserts would refuse to compile.
+constexpr unsigned kNoCode = 1u << 20;
+constexpr unsigned symbol_bits(const HuffCodes& t, int sym, int size) { return (t.code[sym] >> 16) ? (t.code[sym] >> 16) + (unsigned)size : kNoCode; }
+constexpr unsigned block_bits_max(int table, int quality) {
     const HuffCodes dc = dc_codes(table), ac = ac_codes(table);
     int smax[64] = {};
-    for (int k = 0; k < 64; ++k) smax[k] = size_max(table, k);
+    for (int k = 0; k < 64; ++k) smax[k] = size_max(table, k, quality);
     unsigned best[64] = {};
-    for (int s = 0; s <= smax[0]; ++s) if ((dc.code[s] >> 16) + s > best[0]) best[0] = (dc.code[s] >> 16) + s;
+    for (int s = 0; s <= smax[0]; ++s) if (symbol_bits(dc, s, s) > best[0]) best[0] = symbol_bits(dc, s, s);
     for (int p = 1; p < 64; ++p)
         for (int prev = 0; prev < p; ++prev) {
             const int run = p - prev - 1;
             unsigned sym = 0;
-            for (int s = 1; s <= smax[p]; ++s) { const unsigned v = (ac.code[((run & 15) << 4) | s] >> 16) + s; if (v > sym) sym = v; }
+            for (int s = 1; s <= smax[p]; ++s) { const unsigned v = symbol_bits(ac, ((run & 15) << 4) | s, s); if (v > sym) sym = v; }
             const unsigned v = best[prev] + (unsigned)(run >> 4) * (ac.code[0xf0] >> 16) + sym;
             if (v > best[p]) best[p] = v;
         }
@@ -163,16 +186,28 @@ constexpr unsigned block_bits_max(int table) {
     for (int p = 0; p < 63; ++p) if (best[p] + (ac.code[0x00] >> 16) > out) out = best[p] + (ac.code[0x00] >> 16);
     return out;
 }
-constexpr unsigned kMcuBitsMax = block_bits_max(0) + 2 * block_bits_max(1);
+constexpr unsigned block_bits_max(int table) { return block_bits_max(table, kJpegQuality); }
+//    An MCU: one luminance block at 4:4:4, four at 4:2:0 (a dummy block of a partial MCU takes far less than the bound), and two
+//    chrominance blocks.  A smaller divisor never lowers a category, and the divisors fall as the quality rises, so the bound does
+//    not fall as the quality rises: quality 100 is the worst (jpeg_opt_tables_dump.cpp checks all hundred).
+constexpr unsigned mcu_bits_max(int quality, int sampling) { return (sampling == 2 ? 4u : 1u) * block_bits_max(0, quality) + 2 * block_bits_max(1, quality); }
+constexpr unsigned kMcuBitsMax = mcu_bits_max(kJpegQuality, 0);
 static_assert(kMcuBitsMax == 2343, "897 bits for a luminance block, 723 for a chrominance block");
-// 4. One interval of nmcu MCUs: its bits padded to a byte, every byte doubled by stuffing (a 0x00 behind each 0xFF), the marker.
-constexpr size_t interval_bound(unsigned nmcu) { return 2 * (((size_t)nmcu * kMcuBitsMax + 7) / 8) + 2; }
-// 5. The file: the head, the full intervals, the last one.
-constexpr size_t jpeg_file_bound(int h, int w) {
-    const size_t nmcu = (size_t)((h + 7) / 8) * (size_t)((w + 7) / 8);
-    const size_t full = nmcu / kJpegR, tail = nmcu % kJpegR;
-    return kHeaderBytes + full * interval_bound(kJpegR) + (tail ? interval_bound((unsigned)tail) : 0);
+// 4. One interval of nmcu MCUs of at most mcu_bits each: its bits padded to a byte, every byte doubled by stuffing (a 0x00 behind
+//    each 0xFF), the marker.
+constexpr size_t interval_bound_of(unsigned nmcu, unsigned mcu_bits) { return 2 * (((size_t)nmcu * mcu_bits + 7) / 8) + 2; }
+constexpr size_t interval_bound(unsigned nmcu, int quality, int sampling) { return interval_bound_of(nmcu, mcu_bits_max(quality, sampling)); }
+constexpr size_t interval_bound(unsigned nmcu) { return interval_bound_of(nmcu, kMcuBitsMax); }
+// 5. The file: the head, the full intervals, the last one.  (mcu_bits: mcu_bits_max(quality, sampling), for a caller that keeps it.)
+constexpr size_t jpeg_file_bound_of(int h, int w, int sampling, unsigned mcu_bits) {
+    const size_t p = (size_t)mcu_pixels(sampling), r = (size_t)restart_mcus(sampling);
+    const size_t nmcu = (((size_t)h + p - 1) / p) * (((size_t)w + p - 1) / p);
+    const size_t full = nmcu / r, tail = nmcu % r;
+    return kHeaderBytes + full * interval_bound_of((unsigned)r, mcu_bits) + (tail ? interval_bound_of((unsigned)tail, mcu_bits) : 0);
 }
+constexpr size_t jpeg_file_bound(int h, int w, int quality, int sampling) { return jpeg_file_bound_of(h, w, sampling, mcu_bits_max(quality, sampling)); }
+constexpr size_t jpeg_file_bound(int h, int w) { return jpeg_file_bound_of(h, w, 0, kMcuBitsMax); }
+constexpr size_t jpeg_base64_bound(int h, int w, int quality, int sampling) { return (jpeg_file_bound(h, w, quality, sampling) + 2) / 3 * 4; }
 constexpr size_t jpeg_base64_bound(int h, int w) { return (jpeg_file_bound(h, w) + 2) / 3 * 4; }
 
 }  // namespace jpegtab

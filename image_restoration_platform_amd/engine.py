@@ -70,7 +70,10 @@ def upload_plan_reason(data, max_dim=2048, accept=0):
 
 
 class Engine:
-    def __init__(self, device_index=0, max_batch=8, num_streams=0, weights_path="default", seed=0, flags=0, precision="bf16"):
+    def __init__(self, device_index=0, max_batch=8, num_streams=0, weights_path="default", seed=0, flags=0, precision="bf16", jpeg_quality=0,
+                 jpeg_sampling=0):
+        """jpeg_quality (1..100; 0: 85) and jpeg_sampling (0 = 4:4:4, 2 = 4:2:0): the settings of the results of an engine created with
+        flags=IRE_FLAG_RESULT_JPEG; invalid without that flag."""
         self._lib = _lib.load()
         if weights_path == "default":
             weights_path = _weights.ensure_default(seed)
@@ -84,7 +87,10 @@ class Engine:
         cfg.num_streams = num_streams
         cfg.weights_path = weights_path.encode() if weights_path else None
         cfg.flags = flags
+        cfg.jpeg_quality = jpeg_quality
+        cfg.jpeg_sampling = jpeg_sampling
         self._flags = flags
+        self._jpeg_settings = (int(jpeg_quality), int(jpeg_sampling))
         self.last_plan_reason = ""
         h = ctypes.c_void_p()
         self._h = None
@@ -365,41 +371,44 @@ class Engine:
         self._check(self._lib.ire_poll_text(self._h, handle, timeout_ms, _ptr(out), cap, ctypes.byref(n), _ptr(scores), ctypes.byref(t)))
         return out[:n.value].tobytes(), scores, {"classify_ms": t.classify_ms, "restore_ms": t.restore_ms, "total_ms": t.total_ms}
 
-    def _encode_fit(self, fmt, rgb):
-        """The host encoder of TEXT_FORMATS[fmt]: [N,H,W,3] (or [H,W,3]) uint8 -> list of N `bytes` (one for a single image)."""
+    def _encode_fit(self, fmt, rgb, settings=None):
+        """The host encoder of TEXT_FORMATS[fmt]: [N,H,W,3] (or [H,W,3]) uint8 -> list of N `bytes` (one for a single image).  settings:
+        None, or the format's own (JPEG: (quality, sampling)), which go to the entry's _ex form behind its other arguments."""
         f = TEXT_FORMATS[fmt]
         single = np.asarray(rgb).ndim == 3
         x = self._as_batch(rgb)
         n, h, w, _ = x.shape
-        cb = getattr(self, f.bound)(h, w)
+        ex = () if settings is None else tuple(int(v) for v in settings)
+        cb = getattr(self, f.bound)(h, w, *ex)
         if cb == 0:
-            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, f"invalid image size for the {f.noun} encoder: height and width must be in 1..8192")
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, f"invalid image size or settings for the {f.noun} encoder: height and width must be in 1..8192")
         stride = (cb + 15) // 16 * 16
         out = np.empty((n, stride), np.uint8)
         lens = np.zeros(n, np.uint64) if f.counted else None
-        self._check(getattr(self._lib, f.host)(self._h, _ptr(x), n, h, w, _ptr(out), stride, *([_ptr(lens)] if f.counted else [])))
+        self._check(getattr(self._lib, f.host + ("_ex" if ex else ""))(self._h, _ptr(x), n, h, w, _ptr(out), stride, *([_ptr(lens)] if f.counted else []), *ex))
         res = [out[i, :int(lens[i]) if f.counted else cb].tobytes() for i in range(n)]
         return res[0] if single else res
 
-    def _encode_fit_tensor(self, fmt, rgb_u8, stream):
+    def _encode_fit_tensor(self, fmt, rgb_u8, stream, settings=None):
         """The device encoder of TEXT_FORMATS[fmt]: -> cuda uint8 [N, bound] ASCII, and for a counted format (that, cuda int64 [N] counts).
-        The window is encoded where it lies, its strides go to the engine as pitches."""
+        The window is encoded where it lies, its strides go to the engine as pitches.  settings: as for _encode_fit."""
         import torch
         f = TEXT_FORMATS[fmt]
+        ex = () if settings is None else tuple(int(v) for v in settings)
         assert rgb_u8.is_cuda and rgb_u8.dtype == torch.uint8 and rgb_u8.dim() == 4 and rgb_u8.shape[3] == 3
         n, h, w, _ = rgb_u8.shape
         si, sr, sp, sc = rgb_u8.stride()
         if sc != 1 or sp != 3 or sr < 3 * w:
             raise EngineError(_lib.IRE_ERR_INVALID_INPUT, f"invalid tensor layout for the {f.noun} encoder: pixels must be dense RGB")
-        cb = getattr(self, f.bound)(h, w)
+        cb = getattr(self, f.bound)(h, w, *ex)
         if cb == 0:
-            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, f"invalid image size for the {f.noun} encoder: height and width must be in 1..8192")
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, f"invalid image size or settings for the {f.noun} encoder: height and width must be in 1..8192")
         stride = (cb + 3) // 4 * 4
         out = torch.empty((n, stride), dtype=torch.uint8, device=rgb_u8.device)
         lens = torch.zeros(n, dtype=torch.int64, device=rgb_u8.device) if f.counted else None      # (the counts are uint64 and < 2^63)
-        self._check(getattr(self._lib, f.device)(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), n, h, w, sr, si if n > 1 else max(si, sr * h),
-                                                 ctypes.c_void_p(out.data_ptr()), stride, *([ctypes.c_void_p(lens.data_ptr())] if f.counted else []),
-                                                 self._stream_ptr(stream)))
+        self._check(getattr(self._lib, f.device + ("_ex" if ex else ""))(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), n, h, w, sr, si if n > 1 else max(si, sr * h),
+                                                                         ctypes.c_void_p(out.data_ptr()), stride,
+                                                                         *([ctypes.c_void_p(lens.data_ptr())] if f.counted else []), *ex, self._stream_ptr(stream)))
         return (out[:, :cb], lens) if f.counted else out[:, :cb]
 
     def png_base64_bytes(self, h, w):
@@ -419,19 +428,26 @@ class Engine:
         asynchronous on the stream: text i is out[i, :lens[i]]."""
         return self._encode_fit_tensor("png_deflate", rgb_u8, stream)
 
-    def jpeg_base64_bound(self, h, w):
-        """The most characters the JPEG encoder can give for an h x w image (0 outside 1..8192): sizes every buffer."""
-        return int(self._lib.ire_jpeg_base64_bound(int(h), int(w)))
+    def _jpeg_ex(self, quality, sampling):
+        """the settings of a direct call: what the call names, else this engine's own (the batcher's results), else 85 and 4:4:4"""
+        q0, s0 = getattr(self, "_jpeg_settings", (0, 0))
+        return (q0 if quality is None else int(quality), s0 if sampling is None else int(sampling))
 
-    def encode_jpeg_base64_fit(self, rgb):
+    def jpeg_base64_bound(self, h, w, quality=None, sampling=None):
+        """The most characters the JPEG encoder can give for an h x w image at a quality (1..100) and sampling (0 = 4:4:4, 2 = 4:2:0);
+        left out: this engine's settings.  0 outside 1..8192 or for settings the encoder refuses.  Sizes every buffer."""
+        return int(self._lib.ire_jpeg_base64_bound_ex(int(h), int(w), *self._jpeg_ex(quality, sampling)))
+
+    def encode_jpeg_base64_fit(self, rgb, quality=None, sampling=None):
         """[N,H,W,3] (or [H,W,3]) uint8, any size 1..8192 per side -> list of N `bytes` (one for a single image): the base64 text of a
-        baseline JPEG file of each image (quality 85, 4:4:4), encoded on the device; each of its real length."""
-        return self._encode_fit("jpeg", rgb)
+        baseline JPEG file of each image, encoded on the device; each of its real length.  quality 1..100 and sampling 0 = 4:4:4 |
+        2 = 4:2:0; left out: this engine's settings (quality 85, 4:4:4 unless it was created with others)."""
+        return self._encode_fit("jpeg", rgb, self._jpeg_ex(quality, sampling))
 
-    def encode_jpeg_base64_fit_tensor(self, rgb_u8, stream=None):
+    def encode_jpeg_base64_fit_tensor(self, rgb_u8, stream=None, quality=None, sampling=None):
         """cuda uint8 [N,h,w,3], possibly a window of a larger tensor -> (cuda uint8 [N, bound] ASCII, cuda int64 [N] character counts),
-        asynchronous on the stream: text i is out[i, :lens[i]]."""
-        return self._encode_fit_tensor("jpeg", rgb_u8, stream)
+        asynchronous on the stream: text i is out[i, :lens[i]].  quality, sampling: as for encode_jpeg_base64_fit."""
+        return self._encode_fit_tensor("jpeg", rgb_u8, stream, self._jpeg_ex(quality, sampling))
 
     # ---- JPEG uploads decoded on the device (csrc/jpeg_parse.hpp, csrc/jpeg_dec.hip) -------------------------------------------
     @property

@@ -53,6 +53,10 @@ export function bindIre(libPath) {
     ire_jpeg_base64_bound: ['size_t', ['int', 'int']],
     ire_encode_jpeg_base64_fit_device: ['int', [P, P, 'int', 'int', 'int', 'size_t', 'size_t', P, 'size_t', P, P]],
     ire_encode_jpeg_base64_fit: ['int', [P, P, 'int', 'int', 'int', P, 'size_t', P]],
+    // (quality 1..100 | 0: 85; sampling 0 = 4:4:4, 2 = 4:2:0.  ire_config, passed to ire_init as a buffer, ends with the two as int32)
+    ire_jpeg_base64_bound_ex: ['size_t', ['int', 'int', 'int', 'int']],
+    ire_encode_jpeg_base64_fit_device_ex: ['int', [P, P, 'int', 'int', 'int', 'size_t', 'size_t', P, 'size_t', P, 'int', 'int', P]],
+    ire_encode_jpeg_base64_fit_ex: ['int', [P, P, 'int', 'int', 'int', P, 'size_t', P, 'int', 'int']],
     ire_decode_jpeg_plan: ['int', [P, 'size_t', P, P, P]],
     // (accept is a uint32_t of flag bits, 0 or 1 today: passed as an int)
     ire_decode_jpeg_plan_ex: ['int', [P, 'size_t', 'int', P, P, P, P]],

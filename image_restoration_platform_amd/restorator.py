@@ -92,10 +92,17 @@ def encode_jpeg_base64(rgb, quality=85):
 #               with an engine created with IRE_FLAG_RESULT_PNG_BASE64 the batcher hands the text back instead of pixels
 #   png-deflate-device  a COMPRESSED PNG (Paeth filter, Huffman-coded deflate blocks) + its base64 text written by the GPU
 #               (csrc/deflate.hip): no host codec work either, and a shorter string; the engine flag is IRE_FLAG_RESULT_PNG_DEFLATE
-#   jpeg-device  a baseline JPEG q85 4:4:4 (the reference's settings; byte for byte what libjpeg-turbo writes with a restart interval
-#               of 16 MCUs) + its base64 text written by the GPU (csrc/jpeg.hip): no host codec work, and the shortest string; the
-#               engine flag is IRE_FLAG_RESULT_JPEG
+#   jpeg-device  a baseline JPEG (byte for byte what libjpeg-turbo writes with a restart interval of 48 blocks) + its base64 text
+#               written by the GPU (csrc/jpeg.hip): no host codec work, and the shortest string; the engine flag is
+#               IRE_FLAG_RESULT_JPEG.  IRE_JPEG_QUALITY (1..100) and IRE_JPEG_SUBSAMPLING (0 = 4:4:4, 2 = 4:2:0) choose the file's
+#               settings; unset: quality 85 at 4:4:4, the reference's settings
 RESULT_CODEC = os.environ.get("IRE_RESULT_CODEC", "png")
+JPEG_SETTINGS = (int(os.environ.get("IRE_JPEG_QUALITY") or 0), int(os.environ.get("IRE_JPEG_SUBSAMPLING") or 0))      # (0: the default)
+
+
+def jpeg_engine_kwargs(result_codec=None):
+    """The Engine(...) arguments of the JPEG settings: given only with the codec value whose engine flag allows them."""
+    return {"jpeg_quality": JPEG_SETTINGS[0], "jpeg_sampling": JPEG_SETTINGS[1]} if (result_codec or RESULT_CODEC) == "jpeg-device" else {}
 
 
 class _Seen:
@@ -156,8 +163,9 @@ class EngineRestorer:
             return self.engine.encode_png_base64_fit(result).decode("ascii")      # any width: the device encoder
         if self.result_codec == "png-deflate-device":
             return self.engine.encode_png_deflate_base64_fit(result).decode("ascii")
-        if self.result_codec == "jpeg-device":
-            return self.engine.encode_jpeg_base64_fit(result).decode("ascii")
+        if self.result_codec == "jpeg-device":      # a JPEG engine's own settings; on any other engine the environment's
+            own = getattr(self.engine, "_flags", 0) & _lib.IRE_FLAG_RESULT_JPEG
+            return self.engine.encode_jpeg_base64_fit(result, *((None, None) if own else JPEG_SETTINGS)).decode("ascii")
         return encode_png_base64(result)
 
     @staticmethod

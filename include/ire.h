@@ -64,7 +64,9 @@ enum { IRE_SCORE_BLUR = 0, IRE_SCORE_NOISE, IRE_SCORE_LOWLIGHT, IRE_SCORE_COMPRE
 typedef struct ire_engine ire_engine;
 
 typedef struct ire_config {
-    uint32_t struct_size;     /* = sizeof(ire_config); lets the struct grow              */
+    uint32_t struct_size;     /* = sizeof(ire_config); lets the struct grow: a caller built
+                                 before the two JPEG fields passes its smaller size, and the
+                                 fields it does not have read as 0                        */
     int32_t device_index;     /* HIP device ordinal (one engine = one GPU = one process) */
     int32_t precision;        /* IRE_PRECISION_BF16 | IRE_PRECISION_FP8                  */
     int32_t max_batch;        /* images per call, 1..64 (default 8 when 0)               */
@@ -73,6 +75,11 @@ typedef struct ire_config {
     const char* weights_path; /* RestoreNet-v0 weight file (DESIGN.md "weight file");
                                  NULL: classify/fuse only until ire_load_weights         */
     uint32_t flags;           /* IRE_FLAG_* bits; unknown bits are rejected               */
+    int32_t jpeg_quality;     /* with IRE_FLAG_RESULT_JPEG: 1..100, IJG scaling of the Annex K
+                                 tables (what libjpeg and Pillow call quality); 0: 85     */
+    int32_t jpeg_sampling;    /* with IRE_FLAG_RESULT_JPEG: 0 = 4:4:4, 2 = 4:2:0, numbered as
+                                 ire_decode_jpeg_plan numbers it.  Anything else in either
+                                 field, or either set without the flag, is invalid        */
 } ire_config;
 /* The batcher (ire_submit / ire_poll) delivers every result as the base64 TEXT of a PNG file of the restored image, encoded
  * on the device (ire_encode_png_base64_device below), instead of raw pixels: ire_poll's out_rgb then receives
@@ -84,9 +91,11 @@ typedef struct ire_config {
  * ire_poll_text, into a buffer of ire_png_deflate_base64_bound(h, w) bytes.  Bit value 2 is not a flag; setting both result flags
  * is invalid. */
 #define IRE_FLAG_RESULT_PNG_DEFLATE 4u
-/* The batcher delivers every result as the base64 text of a baseline JPEG file (quality 85, 4:4:4: the reference's own settings,
- * imagePreprocess.js:57-64; ire_encode_jpeg_base64_fit_device below).  The text's length depends on the pixels: such results are
- * fetched with ire_poll_text, into a buffer of ire_jpeg_base64_bound(h, w) bytes.  At most one result flag may be set. */
+/* The batcher delivers every result as the base64 text of a baseline JPEG file (ire_encode_jpeg_base64_fit_device_ex below) at
+ * ire_config.jpeg_quality and jpeg_sampling; left 0 that is quality 85 at 4:4:4, the reference's own settings
+ * (imagePreprocess.js:57-64).  The text's length depends on the pixels: such results are fetched with ire_poll_text, into a buffer
+ * of ire_jpeg_base64_bound_ex(h, w, quality, sampling) bytes (ire_jpeg_base64_bound(h, w) for the default).  At most one result
+ * flag may be set. */
 #define IRE_FLAG_RESULT_JPEG 8u
 /* Not a result format, and free to combine with one: ire_decode_jpeg, ire_decode_jpeg_device and ire_submit_jpeg accept PROGRESSIVE
  * JPEG files (ire_decode_jpeg_plan_ex with IRE_DECODE_ACCEPT_PROGRESSIVE) beside baseline ones, in one batch where their planned
@@ -246,6 +255,20 @@ int ire_encode_jpeg_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n
                                       uint64_t* d_lens /* n x uint64, device */, void* stream);
 int ire_encode_jpeg_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes,
                                uint64_t* lens /* n x uint64, host */);
+/* The same with the two settings of the file; the three calls above are their (85, 0) case, byte for byte.
+ * quality: 1..100, the IJG scaling of the Annex K tables with the baseline clamp 1..255 (Pillow's quality=); 0: 85.
+ * sampling: 0 = 4:4:4 as above; 2 = 4:2:0: Y sampled 2 x 2 (SOF0 0x22), an MCU is 16 x 16 pixels in the order Y00 Y01 Y10 Y11 Cb Cr, a
+ * restart interval is 8 MCUs, chroma is libjpeg's h2v2 downsample ((a + b + c + d + bias) >> 2, bias 1 | 2 by output column), and
+ * the Y blocks of a partial MCU that lie outside the image are libjpeg's dummy blocks.  The bytes equal libjpeg-turbo's for
+ * quality=, subsampling=, optimize=False, restart_marker_blocks = 16 | 8 (tests/test_jpeg_opt_model.py).  4:2:2 and grey are refused
+ * ("invalid: ..."), as is a quality outside 0..100; the bound is then 0.  The bound grows with the quality: per MCU 1067 bits at
+ * quality 1, 4474 at 100 (4:4:4); 2006 and 9448 at 4:2:0, whose MCU covers four times the pixels. */
+size_t ire_jpeg_base64_bound_ex(int h, int w, int quality, int sampling);
+int ire_encode_jpeg_base64_fit_device_ex(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes,
+                                         size_t image_pitch_bytes, uint8_t* d_chars, size_t stride_bytes,
+                                         uint64_t* d_lens /* n x uint64, device */, int quality, int sampling, void* stream);
+int ire_encode_jpeg_base64_fit_ex(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes,
+                                  uint64_t* lens /* n x uint64, host */, int quality, int sampling);
 
 /* ---- baseline JPEG uploads decoded on the device ----
  * The RGB bytes equal libjpeg-turbo's (PIL.Image.open(f).convert("RGB")): the file's own Huffman tables, libjpeg's "islow" inverse

@@ -7,7 +7,9 @@
 // its own MCUs alone (DC predictors restart at 0, the interval ends on a byte).  The default, quality 85 at 4:4:4, is what the
 // reference itself puts on the wire (imagePreprocess.js:57-64).  Every step is libjpeg's published integer algorithm;
 // tests/jpeg_model.py and tests/jpeg_opt_model.py restate them, equal libjpeg-turbo's file byte for byte (tests/test_jpeg_model.py,
-// tests/test_jpeg_opt_model.py), and the device's bytes equal the models' (tests/test_jpeg_gpu.py, tests/test_jpeg_opt_gpu.py).
+// tests/test_jpeg_opt_model.py), and the device's bytes equal the models' (tests/test_jpeg_gpu.py, tests/test_jpeg_opt_gpu.py, and
+// tests/test_jpeg_opt_cases_gpu.py on the cases of tests/jpeg_opt_cases.py: the last category of either table, chains of ZRL codes,
+// dummy blocks behind a full DC swing, both sides of the size-class switch, every job kind).
 //
 // Three launches per BATCH, none depending on n (image and interval are grid dimensions), no memset, no host round trip:
 //   K1 jpeg_interval_kernel   one workgroup per restart interval: pixels -> LDS (edge replication by clamped coordinates), colour
@@ -24,7 +26,8 @@
 //
 // LDS.  The bit buffer and the stuffed bytes are sized by the worst interval, which grows with the quality (jpeg_tables.hpp: quality
 // 100 is the worst).  Two size classes, a template parameter: "small" holds every setting whose interval bound is at most that of
-// quality 85 at 4:2:0 (5034 bytes before stuffing; every quality up to 85 at either sampling), "big" holds quality 100.  Per
+// quality 85 at 4:2:0 (5034 bytes before stuffing; every quality up to 86 at 4:4:4 and up to 85 at 4:2:0), "big" holds quality 100;
+// the rule is jpeg_tables.hpp::big_class_of, held on the CPU for all two hundred settings (tests/test_jpeg_opt_cases.py).  Per
 // workgroup, of the CU's 160 KiB: small 4:4:4 31.1 KB (5 workgroups per CU, as before the settings existed: 30.0 KB), small 4:2:0
 // 34.2 KB (4), big 4:4:4 35.5 KB (4), big 4:2:0 38.7 KB (4).
 #include "jpeg.hpp"
@@ -47,16 +50,7 @@ constexpr int kBlocks = 48;                      // 8 x 8 blocks per interval at
 constexpr int kPlane = 72;                       // ints per block in LDS: rows of 9, so that neither DCT pass has a bank conflict
 static_assert(kJpegR * 3 == kBlocks && kJpegR420 * 6 == kBlocks, "an interval is 48 blocks");
 
-// an interval's entropy-coded bytes before stuffing, at most
-constexpr unsigned raw_bound_of(int sampling, unsigned mcu_bits) { return ((unsigned)restart_mcus(sampling) * mcu_bits + 7) / 8; }
-constexpr unsigned kBits85[2] = {mcu_bits_max(85, 0), mcu_bits_max(85, 2)}, kBits100[2] = {mcu_bits_max(100, 0), mcu_bits_max(100, 2)};
-constexpr unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
-constexpr unsigned kRawSmall = umax(raw_bound_of(0, kBits85[0]), raw_bound_of(2, kBits85[1]));       // 5034
-constexpr unsigned kRawBig = umax(raw_bound_of(0, kBits100[0]), raw_bound_of(2, kBits100[1]));       // 9448
-static_assert(kRawSmall == 5034 && kRawBig == 9448, "quality 85 and quality 100 at 4:2:0");
-static_assert(kBits100[0] < kNoCode && kBits100[1] < kNoCode, "no bound prices a symbol the tables do not have");
-
-// what depends on the sampling (kSamp: 0 | 2) and the size class
+// what depends on the sampling (kSamp: 0 | 2) and the size class (jpeg_tables.hpp: raw_bound_of, kRawSmall, kRawBig, big_class_of)
 template <int kSamp, bool kBig>
 struct Shape {
     static constexpr int kR = restart_mcus(kSamp);                  // MCUs per interval
@@ -104,8 +98,8 @@ JpegGeom geom_of(int h, int w, int quality, int sampling) {
     g.nmcu = g.mcus_w * (((unsigned)h + p - 1) / p);
     g.nint = (g.nmcu + r - 1) / r;
     g.mcu_bits = mcu_bits_of(quality, sampling);
-    g.big = raw_bound_of(sampling, g.mcu_bits) > kRawSmall;
-    if (raw_bound_of(sampling, g.mcu_bits) > kRawBig) fail(IRE_ERR_INTERNAL, "internal: a JPEG interval bound beyond the largest size class");
+    g.big = big_class_of(sampling, g.mcu_bits);
+    if (!fits_a_class(sampling, g.mcu_bits)) fail(IRE_ERR_INTERNAL, "internal: a JPEG interval bound beyond the largest size class");
     g.int_stride = sampling == 2 ? (g.big ? Shape<2, true>::kIntStride : Shape<2, false>::kIntStride) : (g.big ? Shape<0, true>::kIntStride : Shape<0, false>::kIntStride);
     g.file_bound = jpegtab::jpeg_file_bound_of(h, w, sampling, g.mcu_bits);
     return g;

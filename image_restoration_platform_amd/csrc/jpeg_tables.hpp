@@ -210,5 +210,21 @@ constexpr size_t jpeg_file_bound(int h, int w) { return jpeg_file_bound_of(h, w,
 constexpr size_t jpeg_base64_bound(int h, int w, int quality, int sampling) { return (jpeg_file_bound(h, w, quality, sampling) + 2) / 3 * 4; }
 constexpr size_t jpeg_base64_bound(int h, int w) { return (jpeg_file_bound(h, w) + 2) / 3 * 4; }
 
+// ---- the two size classes of jpeg.hip's interval kernel ---------------------------------------------------------------------------
+// The kernel's LDS is sized by an interval's entropy-coded bytes BEFORE stuffing, at most raw_bound_of.  "Small" holds every setting
+// whose bound is at most that of quality 85 at 4:2:0 (every quality up to 86 at 4:4:4 and up to 85 at 4:2:0), "big" holds quality 100
+// at either sampling.  The rule stands here, not in jpeg.hip, so that tests/native/jpeg_opt_tables_dump.cpp can print it for every
+// setting (tests/test_jpeg_opt_cases.py holds it against its restatement in Python).
+constexpr unsigned raw_bound_of(int sampling, unsigned mcu_bits) { return ((unsigned)restart_mcus(sampling) * mcu_bits + 7) / 8; }
+constexpr unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
+constexpr unsigned kBits85[2] = {mcu_bits_max(85, 0), mcu_bits_max(85, 2)}, kBits100[2] = {mcu_bits_max(100, 0), mcu_bits_max(100, 2)};
+constexpr unsigned kRawSmall = umax(raw_bound_of(0, kBits85[0]), raw_bound_of(2, kBits85[1]));       // 5034
+constexpr unsigned kRawBig = umax(raw_bound_of(0, kBits100[0]), raw_bound_of(2, kBits100[1]));       // 9448
+static_assert(kRawSmall == 5034 && kRawBig == 9448, "quality 85 and quality 100 at 4:2:0");
+static_assert(kBits100[0] < kNoCode && kBits100[1] < kNoCode, "no bound prices a symbol the tables do not have");
+constexpr bool big_class_of(int sampling, unsigned mcu_bits) { return raw_bound_of(sampling, mcu_bits) > kRawSmall; }
+constexpr bool fits_a_class(int sampling, unsigned mcu_bits) { return raw_bound_of(sampling, mcu_bits) <= kRawBig; }
+constexpr bool big_class(int quality, int sampling) { return big_class_of(sampling, mcu_bits_max(quality, sampling)); }
+
 }  // namespace jpegtab
 }  // namespace ire

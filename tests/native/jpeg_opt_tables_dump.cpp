@@ -76,5 +76,16 @@ int main(int argc, char** argv) {
         prev[0] = now[0]; prev[1] = now[1];
     }
     std::printf("largest_sizes: %d %d\nbound_monotone: %d\n", dc_size, ac_size, monotone);
+    // the size class jpeg.hip's interval kernel runs in, for all two hundred settings (tests/test_jpeg_opt_cases.py): 1 = big
+    std::printf("raw_classes: %u %u\n", kRawSmall, kRawBig);
+    for (int s : {0, 2}) {
+        std::printf("big_class s%d:", s);
+        for (int q = 1; q <= 100; ++q) std::printf(" %d", big_class(q, s) ? 1 : 0);
+        std::printf("\nraw_bound s%d:", s);
+        for (int q = 1; q <= 100; ++q) std::printf(" %u", raw_bound_of(s, mcu_bits_max(q, s)));
+        std::printf("\nfits_a_class s%d:", s);
+        for (int q = 1; q <= 100; ++q) std::printf(" %d", fits_a_class(s, mcu_bits_max(q, s)) ? 1 : 0);
+        std::printf("\n");
+    }
     return 0;
 }

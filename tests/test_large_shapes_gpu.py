@@ -295,3 +295,22 @@ def test_jpeg_text_at_8185x8191_equals_libjpeg_turbo(engine, big):
     text = texts[0, :n].tobytes()
     assert n == len(ref)
     assert text == ref, next(i for i in range(0, len(ref), 4096) if text[i:i + 4096] != ref[i:i + 4096])
+
+
+def test_jpeg_text_at_8177x8191_quality_100_420_equals_libjpeg_turbo(engine, big):
+    """The other end of the settings at the largest window: quality 100 runs the interval kernel's big size class (18944 bytes of scratch
+    per interval against 10112), 4:2:0 has half as many, larger intervals, and 8177 % 16 == 1 gives the last MCU row dummy Y blocks.
+    Pillow's file with the settings tests/test_jpeg_opt_model.py pins the model to; the model itself is too slow at this size."""
+    from test_jpeg_opt_gpu import _encode_tensor
+    from test_jpeg_opt_model import pillow_file
+    img, host = big
+    h, w, q, s = 8177, BW, 100, 2
+    bound = engine.jpeg_base64_bound(h, w, q, s)
+    texts, lens = _encode_tensor(engine, img[None, :h, :w], bound + 517, q, s, fill=0xA5)
+    n = int(lens[0])
+    assert 0 < n <= bound
+    assert (texts[0, bound:] == 0xA5).all() and (texts[0, n:bound] == 0xA5).all()
+    ref = base64.b64encode(pillow_file(np.ascontiguousarray(host[:h, :w]), q, s))
+    text = texts[0, :n].tobytes()
+    assert n == len(ref)
+    assert text == ref, next(i for i in range(0, len(ref), 4096) if text[i:i + 4096] != ref[i:i + 4096])

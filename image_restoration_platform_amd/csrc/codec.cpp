@@ -24,17 +24,17 @@ const TextFormat kDeflatePng = {"PNG", [](int h, int w, TextSettings) { return p
                                     encode_png_deflate_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_scratch, d_chars, stride, d_lens, lens_pitch, s);
                                 },
                                 true, false, {0, 0}};
-const TextFormat kJpeg = {"JPEG", [](int h, int w, TextSettings o) { return jpeg_base64_bound(h, w, o.quality, o.sampling); }, "ire_jpeg_base64_bound",
-                          [](int n, int h, int w, TextSettings o) { return jpeg_scratch_bytes(n, h, w, o.quality, o.sampling); },
+const TextFormat kJpeg = {"JPEG", [](int h, int w, TextSettings o) { return jpeg_base64_bound(h, w, o.quality, o.sampling, o.optimize != 0); }, "ire_jpeg_base64_bound",
+                          [](int n, int h, int w, TextSettings o) { return jpeg_scratch_bytes(n, h, w, o.quality, o.sampling, o.optimize != 0); },
                           [](const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_scratch, uint8_t* d_chars, size_t stride,
                              uint8_t* d_lens, size_t lens_pitch, TextSettings o, hipStream_t s) {
-                              encode_jpeg_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_scratch, d_chars, stride, d_lens, lens_pitch, o.quality, o.sampling, s);
+                              encode_jpeg_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_scratch, d_chars, stride, d_lens, lens_pitch, o.quality, o.sampling, o.optimize != 0, s);
                           },
-                          true, true, {kJpegDefaultQuality, kJpegDefaultSampling}};
+                          true, true, {kJpegDefaultQuality, kJpegDefaultSampling, 0}};
 
 void check_config_flags(uint32_t flags) {
     constexpr uint32_t kResultBits = IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG;
-    if (flags & ~(kResultBits | IRE_FLAG_DECODE_PROGRESSIVE)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
+    if (flags & ~(kResultBits | IRE_FLAG_DECODE_PROGRESSIVE | IRE_FLAG_JPEG_OPTIMIZE)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
     if (((flags & kResultBits) & ((flags & kResultBits) - 1)) != 0) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");
 }
 
@@ -42,16 +42,24 @@ const TextFormat* result_format_of(uint32_t flags) {
     return (flags & IRE_FLAG_RESULT_PNG_DEFLATE) ? &kDeflatePng : (flags & IRE_FLAG_RESULT_JPEG) ? &kJpeg : (flags & IRE_FLAG_RESULT_PNG_BASE64) ? &kStoredPng : nullptr;
 }
 
-TextSettings jpeg_settings_of(int quality, int sampling) {
+TextSettings jpeg_settings_of(int quality, int sampling, bool optimize) {
     if (quality < 0 || quality > 100) fail(IRE_ERR_INVALID_INPUT, "invalid: JPEG quality must be in 1..100 (0: the default, 85)");
     if (sampling != 0 && sampling != 2) fail(IRE_ERR_INVALID_INPUT, "invalid: JPEG sampling must be 0 (4:4:4) or 2 (4:2:0); 4:2:2 and grey results are not built");
-    return {quality ? quality : kJpegDefaultQuality, sampling};
+    return {quality ? quality : kJpegDefaultQuality, sampling, optimize ? 1 : 0};
 }
 
 TextSettings check_config_jpeg(uint32_t flags, int quality, int sampling) {
     if ((quality || sampling) && !(flags & IRE_FLAG_RESULT_JPEG))
         fail(IRE_ERR_INVALID_INPUT, "invalid ire_config: jpeg_quality or jpeg_sampling set without IRE_FLAG_RESULT_JPEG");
-    return jpeg_settings_of(quality, sampling);
+    if ((flags & IRE_FLAG_JPEG_OPTIMIZE) && !(flags & IRE_FLAG_RESULT_JPEG))
+        fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags: IRE_FLAG_JPEG_OPTIMIZE set without IRE_FLAG_RESULT_JPEG");
+    return jpeg_settings_of(quality, sampling, (flags & IRE_FLAG_JPEG_OPTIMIZE) != 0);
+}
+
+TextFormat jpeg_format_of(TextSettings o) {
+    TextFormat f = kJpeg.with(o);
+    if (o.optimize) f.bound_name = "ire_jpeg_optimized_base64_bound";
+    return f;
 }
 
 namespace {
@@ -134,6 +142,21 @@ void TextEncoder::run_host(const TextFormat& f, const uint8_t* rgb, int n, int h
         else std::memcpy(chars + stride * i, stage.data() + cpad * i + 8, (size_t)len);
     }
     if (f.counts_first) IRE_HIP(hipStreamSynchronize(s));
+}
+
+// the optimised JPEG path's table kernel alone, synchronous on the main stream: counts up, tables and symbol counts down
+void TextEncoder::debug_jpeg_huffman(const uint32_t* counts, int n, uint8_t* bits_vals_out, int32_t* nvals_out) {
+    if (!counts || !bits_vals_out || !nvals_out || n < 1 || n > 4096) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_debug_jpeg_huffman (1..4096 sets of four histograms)");
+    const size_t cb = (size_t)n * 4 * 256 * sizeof(uint32_t), tb = (size_t)n * 4 * (16 + 256), tpad = (tb + 255) / 256 * 256, nb = (size_t)n * 4 * sizeof(int32_t);
+    if (cb + tpad + nb > d_io_.bytes()) IRE_HIP(hipDeviceSynchronize());
+    d_io_.grow(cb + tpad + nb);
+    hipStream_t s = main_stream_;
+    uint8_t* d = d_io_.get<uint8_t>();
+    IRE_HIP(hipMemcpyAsync(d, counts, cb, hipMemcpyHostToDevice, s));
+    jpeg_huffman_tables_launch(reinterpret_cast<const unsigned*>(d), n, d + cb, reinterpret_cast<int*>(d + cb + tpad), s);
+    IRE_HIP(hipMemcpyAsync(bits_vals_out, d + cb, tb, hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipMemcpyAsync(nvals_out, d + cb + tpad, nb, hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipStreamSynchronize(s));
 }
 
 // ---- the JPEG decoder (jpeg_parse.hpp on the host, jpeg_dec.hip on the device) ------------------------------------------------------------

@@ -8,9 +8,9 @@
 
 namespace ire {
 
-// The format's settings, chosen per engine or per direct call: JPEG's quality (1..100) and sampling (0 = 4:4:4, 2 = 4:2:0).  The PNG
-// formats have none and ignore them.
-struct TextSettings { int quality, sampling; };
+// The format's settings, chosen per engine or per direct call: JPEG's quality (1..100), sampling (0 = 4:4:4, 2 = 4:2:0) and optimize
+// (0 | 1: the image's own Huffman tables).  The PNG formats have none and ignore them.
+struct TextSettings { int quality, sampling, optimize; };
 struct TextFormat {
     const char* noun;                                   // the encoder as its messages name it: "PNG" | "JPEG"
     size_t (*bound_fn)(int h, int w, TextSettings o);   // the most characters an h x w image gives (stored PNG: exactly so many)
@@ -39,9 +39,12 @@ void check_config_flags(uint32_t flags);
 const TextFormat* result_format_of(uint32_t flags);
 // JPEG settings as the ABI takes them: 0 means the default (85 | 4:4:4); refuses a quality outside 1..100 and a sampling other than 0
 // or 2 as "invalid: ..."
-TextSettings jpeg_settings_of(int quality, int sampling);
-// ire_config's two JPEG fields: jpeg_settings_of, and either field set without IRE_FLAG_RESULT_JPEG is refused
+TextSettings jpeg_settings_of(int quality, int sampling, bool optimize = false);
+// ire_config's two JPEG fields and IRE_FLAG_JPEG_OPTIMIZE: jpeg_settings_of, and any of the three set without IRE_FLAG_RESULT_JPEG is
+// refused
 TextSettings check_config_jpeg(uint32_t flags, int quality, int sampling);
+// kJpeg at the settings given; with optimize its messages name the optimised bound
+TextFormat jpeg_format_of(TextSettings o);
 
 // Owns the scratch all formats share and the host entries' staging.  Every call runs under the engine's lock.
 class TextEncoder {
@@ -61,6 +64,8 @@ public:
     // the first entries (stored PNG, w % 8 == 0, up to 16384 per side): their own argument checks in front of the same path
     void encode_png_aligned_device(const uint8_t* d_rgb, int n, int h, int w, uint8_t* d_chars, size_t stride, hipStream_t s);
     void encode_png_aligned_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride);
+    // ire_debug_jpeg_huffman: counts [n][4][256] -> bits_vals_out [n][4][16 + 256], nvals_out [n][4], by jpeg.hip's table kernel alone
+    void debug_jpeg_huffman(const uint32_t* counts, int n, uint8_t* bits_vals_out, int32_t* nvals_out);
 
 private:
     void run_host(const TextFormat& f, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride, uint64_t* lens);

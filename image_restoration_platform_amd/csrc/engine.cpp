@@ -48,7 +48,7 @@ Engine::Engine(const ire_config& cfg) {
     if (num_lanes_ > 16) num_lanes_ = 16;
     check_config_flags(cfg.flags);
     result_format_ = result_format_of(cfg.flags);
-    jpeg_format_ = kJpeg.with(check_config_jpeg(cfg.flags, cfg.jpeg_quality, cfg.jpeg_sampling));
+    jpeg_format_ = jpeg_format_of(check_config_jpeg(cfg.flags, cfg.jpeg_quality, cfg.jpeg_sampling));
     if (result_format_ == &kJpeg) result_format_ = &jpeg_format_;
     sw_ = ConvSwitches::from_env();
     cus_ = persistent_grid_cus();

@@ -30,6 +30,21 @@
 // the rule is jpeg_tables.hpp::big_class_of, held on the CPU for all two hundred settings (tests/test_jpeg_opt_cases.py).  Per
 // workgroup, of the CU's 160 KiB: small 4:4:4 31.1 KB (5 workgroups per CU, as before the settings existed: 30.0 KB), small 4:2:0
 // 34.2 KB (4), big 4:4:4 35.5 KB (4), big 4:2:0 38.7 KB (4).
+//
+// Optimised Huffman tables (optimize: libjpeg's optimize_coding; tests/jpeg_huffopt_model.py equals Pillow's optimize=True file, the
+// device equals the model: tests/test_jpeg_huffopt_gpu.py).  The file carries the image's own four tables.  A memset of the histograms
+// and five launches per BATCH, none depending on n, no host round trip:
+//   K1 in count mode          the same front end; the symbols of every block are counted into four LDS histograms (DC and AC, for Y and
+//                             for Cb and Cr together) and those added to the image's in global memory by integer atomics
+//   jpeg_table_kernel         one wave per (table, image): jpeg_huff_core.hpp turns a histogram into bits[16], vals[], the symbol count
+//                             and the code array, in device scratch
+//   K1 in emit mode           the front end again (the DCT is recomputed: storing the coefficients would write and read 6 bytes per
+//                             pixel, more than the 3 bytes per pixel the second read of the pixels costs) with the image's codes in LDS
+//   K2 with the head built from the fixed parts and the device's DHT segments, behind a per-image head length; K3 as it is
+// Under an arbitrary table a code can be 16 bits whatever the symbol, so an interval is bounded by jpeg_tables.hpp::mcu_bits_any (9990
+// bytes before stuffing at quality 100) and the emit pass has ONE size class of its own, kClassAny: 36.2 KB at 4:4:4, 39.3 KB at 4:2:0
+// (4 workgroups per CU).  The count pass packs no bits and runs in the small class's LDS less the code tables: 28.8 / 32.0 KB (5).
+// The fixed path's four instances are compiled from the same template and keep their LDS, registers and bytes.
 #include "jpeg.hpp"
 
 #include <atomic>
@@ -50,34 +65,39 @@ constexpr int kBlocks = 48;                      // 8 x 8 blocks per interval at
 constexpr int kPlane = 72;                       // ints per block in LDS: rows of 9, so that neither DCT pass has a bank conflict
 static_assert(kJpegR * 3 == kBlocks && kJpegR420 * 6 == kBlocks, "an interval is 48 blocks");
 
-// what depends on the sampling (kSamp: 0 | 2) and the size class (jpeg_tables.hpp: raw_bound_of, kRawSmall, kRawBig, big_class_of)
-template <int kSamp, bool kBig>
+// what depends on the sampling (kSamp: 0 | 2) and the size class (jpeg_tables.hpp: raw_bound_of, kRawSmall, kRawBig, big_class_of; kRawAny:
+// the one class of the optimised path, any table at quality 100)
+constexpr int kClassSmall = 0, kClassBig = 1, kClassAny = 2;
+template <int kSamp, int kClass>
 struct Shape {
+    static constexpr unsigned kWorstBits = kClass == kClassAny ? kBitsAny100[kSamp / 2] : kClass == kClassBig ? kBits100[kSamp / 2] : kBits85[kSamp / 2];
     static constexpr int kR = restart_mcus(kSamp);                  // MCUs per interval
     static constexpr int kP = mcu_pixels(kSamp);                    // an MCU's pixels per side
     static constexpr int kPer = kSamp == 2 ? 6 : 3;                 // blocks per MCU
     static constexpr int kRowDw = 3 * kP / 4;                       // dwords of one MCU's pixel row
     static constexpr int kPxWords = kR * kP * kRowDw;               // the interval's pixels: MCU m, row r at dword (m * kP + r) * kRowDw
-    static constexpr unsigned kRawBytes = kBig ? kRawBig : kRawSmall;
+    static constexpr unsigned kRawBytes = kClass == kClassAny ? kRawAny : kClass == kClassBig ? kRawBig : kRawSmall;
     static constexpr int kOutWords = (kRawBytes + 3) / 4 + 1;
     static constexpr unsigned kIntBound = 2 * kRawBytes + 2;        // stuffed, with the marker
     static constexpr int kStuffWords = (kIntBound + 3) / 4 + 1;     // (+ 1: the dword the gather may read behind the last byte)
     static constexpr unsigned kIntStride = (kStuffWords * 4 + 63) / 64 * 64;      // scratch bytes per interval
     static constexpr int kWorkWords = kPxWords + kBlocks * kPlane + kBlocks * 32; // pixels | DCT planes | quantised coefficients
-    static_assert(kRawBytes >= raw_bound_of(kSamp, kBig ? kBits100[kSamp / 2] : kBits85[kSamp / 2]), "the class holds its worst quality");
-    static_assert(kIntBound >= interval_bound_of(kR, kBig ? kBits100[kSamp / 2] : kBits85[kSamp / 2]), "and that interval stuffed");
+    static_assert(kRawBytes >= raw_bound_of(kSamp, kWorstBits), "the class holds its worst quality");
+    static_assert(kIntBound >= interval_bound_of(kR, kWorstBits), "and that interval stuffed");
+    static_assert(kOutWords >= 4 * 256, "the count pass keeps its four histograms where the emit pass keeps its bits");
     static_assert(kWorkWords >= kStuffWords, "the stuffed bytes reuse the pixels, the DCT planes and the coefficients");
 };
-static_assert(Shape<0, false>::kIntBound >= interval_bound(kJpegR), "the default's bound");
+static_assert(Shape<0, kClassSmall>::kIntBound >= interval_bound(kJpegR), "the default's bound");
 
 struct JpegGeom {
     int h, w;
     unsigned mcus_w;           // MCUs per row
     unsigned nmcu, nint;       // <= 2^20 MCUs, 2^16 intervals at 8192 x 8192
-    unsigned mcu_bits;         // jpegtab::mcu_bits_max of the settings
+    unsigned mcu_bits;         // jpegtab::mcu_bits_max of the settings (optimised tables: mcu_bits_any)
     unsigned int_stride;       // scratch bytes per interval: Shape::kIntStride of the launch
     int quality, sampling;
     bool big;                  // the size class
+    bool optimize;             // the image's own Huffman tables: the one class kClassAny
     unsigned long long file_bound;
 };
 // the bound of an MCU runs a dynamic programme over the Huffman tables: once per setting and process
@@ -89,7 +109,7 @@ unsigned mcu_bits_of(int quality, int sampling) {
     if (!v) { v = mcu_bits_max(quality, sampling); c.store(v, std::memory_order_relaxed); }
     return v;
 }
-JpegGeom geom_of(int h, int w, int quality, int sampling) {
+JpegGeom geom_of(int h, int w, int quality, int sampling, bool optimize) {
     if (!settings_ok(quality, sampling)) fail(IRE_ERR_INVALID_INPUT, "invalid settings for the JPEG encoder (quality 1..100; sampling 0 = 4:4:4 or 2 = 4:2:0)");
     JpegGeom g;
     const unsigned p = (unsigned)mcu_pixels(sampling), r = (unsigned)restart_mcus(sampling);
@@ -97,10 +117,11 @@ JpegGeom geom_of(int h, int w, int quality, int sampling) {
     g.mcus_w = ((unsigned)w + p - 1) / p;
     g.nmcu = g.mcus_w * (((unsigned)h + p - 1) / p);
     g.nint = (g.nmcu + r - 1) / r;
-    g.mcu_bits = mcu_bits_of(quality, sampling);
-    g.big = big_class_of(sampling, g.mcu_bits);
-    if (!fits_a_class(sampling, g.mcu_bits)) fail(IRE_ERR_INTERNAL, "internal: a JPEG interval bound beyond the largest size class");
-    g.int_stride = sampling == 2 ? (g.big ? Shape<2, true>::kIntStride : Shape<2, false>::kIntStride) : (g.big ? Shape<0, true>::kIntStride : Shape<0, false>::kIntStride);
+    g.optimize = optimize;
+    g.mcu_bits = optimize ? mcu_bits_any(quality, sampling) : mcu_bits_of(quality, sampling);
+    g.big = !optimize && big_class_of(sampling, g.mcu_bits);
+    if (!(optimize ? fits_any_class(sampling, g.mcu_bits) : fits_a_class(sampling, g.mcu_bits))) fail(IRE_ERR_INTERNAL, "internal: a JPEG interval bound beyond the largest size class");
+    g.int_stride = optimize ? (sampling == 2 ? Shape<2, kClassAny>::kIntStride : Shape<0, kClassAny>::kIntStride) : sampling == 2 ? (g.big ? Shape<2, kClassBig>::kIntStride : Shape<2, kClassSmall>::kIntStride) : (g.big ? Shape<0, kClassBig>::kIntStride : Shape<0, kClassSmall>::kIntStride);
     g.file_bound = jpegtab::jpeg_file_bound_of(h, w, sampling, g.mcu_bits);
     return g;
 }
@@ -167,14 +188,16 @@ __device__ __forceinline__ void put_bits(unsigned* out, unsigned nwords, unsigne
 
 // What lane `lane` of a wave sends for coefficient c (zig-zag position `lane`; lane 0 holds the DC DIFFERENCE) of a block whose
 // non-zero AC positions are the set bits of mask: nzrl ZRL codes, then `bits` (nb of them: the symbol's code and the value's bits).
+// kOwn: the DC codes are the image's own, in LDS (s_dc[2][16]); else the fixed ones in constant memory.
 struct LaneSym { unsigned bits, nb, nzrl; };
-__device__ __forceinline__ LaneSym lane_symbol(int c, unsigned lane, unsigned long long mask, int tb, const unsigned* s_ac) {
+template <bool kOwn>
+__device__ __forceinline__ LaneSym lane_symbol(int c, unsigned lane, unsigned long long mask, int tb, const unsigned* s_ac, const unsigned* s_dc) {
     LaneSym o{0u, 0u, 0u};
     const unsigned mag = (unsigned)(c < 0 ? -c : c);
     const unsigned s = 32u - (unsigned)__clz((int)mag);                         // the magnitude category (__clz(0) = 32)
     const unsigned vb = (unsigned)(c < 0 ? c - 1 : c) & ((1u << s) - 1u);      // a negative value is sent as v - 1
     if (lane == 0) {
-        const unsigned code = kH.dc[tb][s < 11u ? s : 11u];
+        const unsigned code = kOwn ? s_dc[tb * 16 + (s < 11u ? s : 11u)] : kH.dc[tb][s < 11u ? s : 11u];
         o.bits = ((code & 0xffffu) << s) | vb; o.nb = (code >> 16) + s;
     } else if (c != 0) {
         const unsigned long long below = mask & ((1ull << lane) - 1ull);
@@ -202,14 +225,22 @@ __device__ __forceinline__ int pred_of(unsigned blk) {
     return j == 0u ? (int)blk - 3 : (int)blk - 6;                  // (negative in the first MCU: none)
 }
 
-// K1.  blockIdx.x: the interval, blockIdx.y: the image.
-template <int kSamp, bool kBig>
-__global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, JpegGeom g, QuantArg qa, unsigned char* __restrict__ intbuf, unsigned* __restrict__ int_bytes) {
-    using S = Shape<kSamp, kBig>;
+// K1.  blockIdx.x: the interval, blockIdx.y: the image.  kMode: kEmitFixed, the fixed-table path; kCount, the optimised path's first
+// pass: the same front end, but the symbols are counted into four LDS histograms (DHT order: DC 0, AC 0, DC 1, AC 1) and those added
+// to the image's in `hist` -- integer sums, so their order does not matter; kEmitOwn, its second pass: the front end again
+// (recomputing costs less than 6 bytes per pixel of coefficients written and read back) and the bits under the image's own codes,
+// which the table kernel left in `codes` ([image][4][256], value | length << 16).
+constexpr int kEmitFixed = 0, kCount = 1, kEmitOwn = 2;
+template <int kSamp, int kClass, int kMode>
+__global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, JpegGeom g, QuantArg qa, unsigned char* __restrict__ intbuf, unsigned* __restrict__ int_bytes,
+                                                                  const unsigned* __restrict__ codes, unsigned* __restrict__ hist) {
+    using S = Shape<kSamp, kClass>;
+    constexpr bool kOwn = kMode == kEmitOwn;
     constexpr int kR = S::kR, kP = S::kP, kPer = S::kPer, kRowDw = S::kRowDw, kOutWords = S::kOutWords;
     __shared__ unsigned s_work[S::kWorkWords];                // pixels | planes | coefficients; later the stuffed bytes over all three
     __shared__ unsigned s_out[kOutWords];                     // the entropy-coded bits, big-endian words
-    __shared__ unsigned s_ac[2 * 256];
+    __shared__ unsigned s_ac[2 * 256 + (kOwn ? 2 * 16 : 0)];  // the AC codes; behind them the image's own DC codes (kEmitOwn)
+    const unsigned* const s_dc = s_ac + 2 * 256;
     __shared__ unsigned s_recip[2 * 64];                      // the quantiser (QuantArg), natural order
     __shared__ unsigned short s_half[2 * 64];
     __shared__ unsigned s_blkoff[kBlocks + 1];
@@ -225,7 +256,13 @@ __global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, Jpe
     const unsigned char* __restrict__ rgb = src.rgb + (unsigned long long)img * src.image_pitch;
 
     for (int k = t; k < kOutWords; k += kThreads) s_out[k] = 0;
-    for (int k = t; k < 512; k += kThreads) s_ac[k] = kH.ac[k >> 8][k & 255];
+    if (kOwn) {
+        const unsigned* own = codes + (unsigned long long)img * (4 * 256);
+        for (int k = t; k < 512; k += kThreads) s_ac[k] = own[(2 * (k >> 8) + 1) * 256 + (k & 255)];
+        if (t < 32) s_ac[512 + t] = own[2 * (t >> 4) * 256 + (t & 15u)];
+    } else if (kMode == kEmitFixed) {
+        for (int k = t; k < 512; k += kThreads) s_ac[k] = kH.ac[k >> 8][k & 255];
+    }
     if (t < 128) { s_recip[t] = qa.recip[t >> 6][t & 63u]; s_half[t] = qa.half[t >> 6][t & 63u]; }
     if (kSamp == 2 && t < nblk) {
         const unsigned m = t / 6u, j = t % 6u, mcu = m0 + m, my = mcu / g.mcus_w, mx = mcu - my * g.mcus_w;
@@ -340,15 +377,40 @@ __global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, Jpe
         __syncthreads();
     }
 
-    // 5. bits per block: one wave per block, lane k = zig-zag position k.  The DC differences need no order: every DC is known.
     const unsigned wv = t >> 6, lane = t & 63u;
+    if constexpr (kMode == kCount) {
+        // 5c. the symbols counted: one wave per block, lane k = zig-zag position k, as the emit pass finds them below
+        unsigned* const s_hist = s_out;                          // (zeroed above) [DC 0 | AC 0 | DC 1 | AC 1][256]
+        for (unsigned blk = wv; blk < nblk; blk += kThreads / 64) {
+            int c = s_q[blk * 64 + lane];
+            const int pb = pred_of<kSamp>(blk);
+            if (lane == 0 && pb >= 0) c -= s_q[pb * 64];
+            const unsigned long long mask = __ballot(c != 0) & ~1ull;
+            unsigned* const h = s_hist + table_of<kSamp>(blk) * 512;
+            const unsigned mag = (unsigned)(c < 0 ? -c : c);
+            const unsigned s = 32u - (unsigned)__clz((int)mag);
+            if (lane == 0) atomicAdd(&h[s < 11u ? s : 11u], 1u);
+            else if (c != 0) {
+                const unsigned long long below = mask & ((1ull << lane) - 1ull);
+                const unsigned prev = below ? 63u - (unsigned)__clzll((long long)below) : 0u;
+                const unsigned run = lane - prev - 1u;
+                atomicAdd(&h[256 + (((run & 15u) << 4) | (s & 15u))], 1u);
+                if (run >> 4) atomicAdd(&h[256 + 0xf0], run >> 4);
+            } else if (lane == 63) atomicAdd(&h[256], 1u);
+        }
+        __syncthreads();
+        unsigned* const dst = hist + (unsigned long long)img * (4 * 256);
+        for (unsigned k = t; k < 4 * 256; k += kThreads) { const unsigned v = s_hist[k]; if (v) atomicAdd(&dst[k], v); }
+        return;
+    }
+    // 5. bits per block: one wave per block, lane k = zig-zag position k.  The DC differences need no order: every DC is known.
     for (unsigned blk = wv; blk < nblk; blk += kThreads / 64) {
         int c = s_q[blk * 64 + lane];
         const int pb = pred_of<kSamp>(blk);
         if (lane == 0 && pb >= 0) c -= s_q[pb * 64];
         const unsigned long long mask = __ballot(c != 0) & ~1ull;
         const int tb = table_of<kSamp>(blk);
-        const LaneSym sy = lane_symbol(c, lane, mask, tb, s_ac);
+        const LaneSym sy = lane_symbol<kOwn>(c, lane, mask, tb, s_ac, s_dc);
         unsigned bits = sy.nb + sy.nzrl * (s_ac[tb * 256 + 0xf0] >> 16);
         for (int off = 32; off >= 1; off >>= 1) bits += __shfl_down(bits, off, 64);
         if (lane == 0) s_blkoff[blk + 1] = bits;
@@ -368,7 +430,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, Jpe
         if (lane == 0 && pb >= 0) c -= s_q[pb * 64];
         const unsigned long long mask = __ballot(c != 0) & ~1ull;
         const int tb = table_of<kSamp>(blk);
-        const LaneSym sy = lane_symbol(c, lane, mask, tb, s_ac);
+        const LaneSym sy = lane_symbol<kOwn>(c, lane, mask, tb, s_ac, s_dc);
         const unsigned zrl = s_ac[tb * 256 + 0xf0];
         const unsigned mine = sy.nb + sy.nzrl * (zrl >> 16);
         unsigned inc = mine;
@@ -420,10 +482,53 @@ __global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, Jpe
     if (t == 0) int_bytes[slot] = bytes;
 }
 
-// K2.  The interval's bytes to their place in the file; the head by interval 0, the lengths by the last interval.
+// The optimised path's table kernel, between its two passes: one wave per (table, image) turns a histogram into the table as its DHT
+// segment carries it (bits[16] | vals[256]), its symbol count and the code array the emit pass reads.  jpeg_huff_core.hpp holds the
+// algorithm (tests/native/jpeg_huffopt_dump.cpp runs it on the CPU); here the wave is a wave.
+// The wave-wide minimum is on the merge loop's critical path twice per merge, so it goes through DPP moves, not through LDS
+// permutes: shifts by 1, 2, 4 and 8 inside the rows of 16 lanes (a lane without a source keeps its own value), then lane 15 of a
+// row to the next row (rows 1 and 3), then lane 31 to rows 2 and 3; lane 63 holds the minimum, read into scalar registers.  All
+// 64 lanes are active wherever this is called.
+template <int kCtrl, int kRowMask>
+__device__ __forceinline__ unsigned long long dpp_min64(unsigned long long v) {
+    const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
+    const unsigned olo = (unsigned)__builtin_amdgcn_update_dpp(lo, lo, kCtrl, kRowMask, 0xf, false);
+    const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp(hi, hi, kCtrl, kRowMask, 0xf, false);
+    const unsigned long long o = ((unsigned long long)ohi << 32) | olo;
+    return o < v ? o : v;
+}
+struct DevWave {
+    struct Own { jpeghuff::Entries e; __device__ __forceinline__ jpeghuff::Entries& operator[](unsigned) { return e; } };
+    unsigned lane;
+    template <typename F> __device__ __forceinline__ void lanes(F f) { f(lane); }
+    template <typename F> __device__ __forceinline__ unsigned long long min64(F f) {
+        unsigned long long v = f(lane);
+        v = dpp_min64<0x111, 0xf>(v);      // row_shr:1
+        v = dpp_min64<0x112, 0xf>(v);      // row_shr:2
+        v = dpp_min64<0x114, 0xf>(v);      // row_shr:4
+        v = dpp_min64<0x118, 0xf>(v);      // row_shr:8
+        v = dpp_min64<0x142, 0xa>(v);      // row_bcast:15
+        v = dpp_min64<0x143, 0xc>(v);      // row_bcast:31
+        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+        return ((unsigned long long)hi << 32) | lo;
+    }
+    __device__ __forceinline__ void sync() { __syncthreads(); }
+    __device__ __forceinline__ void add1(int& x) { atomicAdd(&x, 1); }
+};
+__global__ __launch_bounds__(jpeghuff::kLanes) void jpeg_table_kernel(const unsigned* hist, unsigned char* bits_vals, int* nvals, unsigned* codes) {
+    __shared__ jpeghuff::Work s_work;
+    DevWave wv{threadIdx.x};
+    const unsigned long long slot = (unsigned long long)blockIdx.y * 4 + blockIdx.x;
+    jpeghuff::build_table(wv, s_work, hist + slot * 256, bits_vals + slot * jpeghuff::kBitsVals, nvals + slot, codes ? codes + slot * 256 : nullptr);
+}
+
+// K2.  The interval's bytes to their place in the file; the head by interval 0, the lengths by the last interval.  kOwn: the head
+// carries the image's own tables (bits_vals, nvals: the table kernel's), so its length is the image's own too.
+template <bool kOwn>
 __global__ __launch_bounds__(kThreads) void jpeg_gather_kernel(JpegGeom g, JpegHeader head, const unsigned char* __restrict__ intbuf, const unsigned* __restrict__ int_bytes,
                                                                 unsigned char* __restrict__ files, unsigned long long file_pitch, unsigned long long* __restrict__ flen,
-                                                                unsigned char* __restrict__ lens, unsigned long long lens_pitch) {
+                                                                unsigned char* __restrict__ lens, unsigned long long lens_pitch,
+                                                                const unsigned char* __restrict__ bits_vals, const int* __restrict__ nvals) {
     __shared__ unsigned s_red[2][kThreads / 64];
     const unsigned iv = blockIdx.x, img = blockIdx.y, t = threadIdx.x;
     const unsigned* sizes = int_bytes + (unsigned long long)img * g.nint;
@@ -437,7 +542,8 @@ __global__ __launch_bounds__(kThreads) void jpeg_gather_kernel(JpegGeom g, JpegH
     unsigned char* __restrict__ file = files + (unsigned long long)img * file_pitch;
     const unsigned char* __restrict__ srcb = intbuf + ((unsigned long long)img * g.nint + iv) * g.int_stride;
     const unsigned size = sizes[iv];
-    const unsigned d0 = kHeaderBytes + before;                    // file offset of the interval's first byte (file_pitch is a multiple of 4)
+    const unsigned head_len = kOwn ? jpeghuff::opt_head_bytes(nvals + 4ull * img) : (unsigned)kHeaderBytes;
+    const unsigned d0 = head_len + before;                        // file offset of the interval's first byte (file_pitch is a multiple of 4)
     // [d0, d0 + size): bytes up to the first dword boundary, whole dwords, bytes again: no dword is shared with a neighbour's stores
     const unsigned hd = (4u - (d0 & 3u)) & 3u;
     const unsigned nhead = hd < size ? hd : size;
@@ -452,10 +558,12 @@ __global__ __launch_bounds__(kThreads) void jpeg_gather_kernel(JpegGeom g, JpegH
         dstw[k] = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
     }
     if (t < ntail) file[d0 + nhead + 4 * ndw + t] = srcb[nhead + 4 * ndw + t];
-    if (iv == 0)
-        for (unsigned k = t; k < (unsigned)kHeaderBytes; k += kThreads) file[k] = head.b[k];      // (jpeg_header of the launch's h, w and settings)
+    if (iv == 0) {
+        if (kOwn) for (unsigned k = t; k < head_len; k += kThreads) file[k] = jpeghuff::opt_head_byte(k, head.b, bits_vals + 4ull * jpeghuff::kBitsVals * img, nvals + 4ull * img);
+        else for (unsigned k = t; k < (unsigned)kHeaderBytes; k += kThreads) file[k] = head.b[k];      // (jpeg_header of the launch's h, w and settings)
+    }
     if (iv + 1 == g.nint) {
-        const unsigned long long fl = (unsigned long long)kHeaderBytes + all;
+        const unsigned long long fl = (unsigned long long)head_len + all;
         if (t < 48) { const unsigned long long o = fl + t; if (o < file_pitch) file[o] = 0; }      // what the last base64 thread reads behind the file
         if (t == 64) {
             flen[img] = fl;
@@ -467,7 +575,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_gather_kernel(JpegGeom g, JpegH
     }
 }
 
-struct ScratchLayout { size_t flen, int_bytes, intbuf, files, file_pitch, total; };
+struct ScratchLayout { size_t flen, int_bytes, intbuf, files, file_pitch, hist, codes, bits_vals, nvals, total; };
 ScratchLayout layout_of(int n, const JpegGeom& g) {
     ScratchLayout L;
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
@@ -477,20 +585,28 @@ ScratchLayout layout_of(int n, const JpegGeom& g) {
     L.files = up(L.intbuf + (size_t)n * g.nint * g.int_stride);
     L.file_pitch = up(((size_t)g.file_bound + 11) / 12 * 12 + 16);   // (the 12-byte groups of the last base64 threads stay inside)
     L.total = L.files + L.file_pitch * (size_t)n;
+    L.hist = L.codes = L.bits_vals = L.nvals = 0;
+    if (g.optimize) {                                                // per image and table: 256 counts | 256 codes | bits and vals | the symbol count
+        L.hist = up(L.total);
+        L.codes = L.hist + (size_t)n * 4 * 256 * 4;
+        L.bits_vals = L.codes + (size_t)n * 4 * 256 * 4;
+        L.nvals = up(L.bits_vals + (size_t)n * 4 * jpeghuff::kBitsVals);
+        L.total = L.nvals + (size_t)n * 4 * 4;
+    }
     return L;
 }
 
 }  // namespace
 
-size_t jpeg_file_bound(int h, int w, int quality, int sampling) { return geom_of(h, w, quality, sampling).file_bound; }
-size_t jpeg_base64_bound(int h, int w, int quality, int sampling) { return ((size_t)geom_of(h, w, quality, sampling).file_bound + 2) / 3 * 4; }
-size_t jpeg_scratch_bytes(int n, int h, int w, int quality, int sampling) { return layout_of(n, geom_of(h, w, quality, sampling)).total; }
+size_t jpeg_file_bound(int h, int w, int quality, int sampling, bool optimize) { return geom_of(h, w, quality, sampling, optimize).file_bound; }
+size_t jpeg_base64_bound(int h, int w, int quality, int sampling, bool optimize) { return ((size_t)geom_of(h, w, quality, sampling, optimize).file_bound + 2) / 3 * 4; }
+size_t jpeg_scratch_bytes(int n, int h, int w, int quality, int sampling, bool optimize) { return layout_of(n, geom_of(h, w, quality, sampling, optimize)).total; }
 
 void encode_jpeg_base64_launch(const unsigned char* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, unsigned char* d_scratch, unsigned char* d_chars,
-                               size_t text_pitch, unsigned char* d_lens, size_t lens_pitch, int quality, int sampling, hipStream_t s) {
+                               size_t text_pitch, unsigned char* d_lens, size_t lens_pitch, int quality, int sampling, bool optimize, hipStream_t s) {
     if (n < 1 || n > 65535 || h <= 0 || w <= 0 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the JPEG encoder (1..8192 per side)");
     if (row_pitch < (size_t)3 * w) fail(IRE_ERR_INVALID_INPUT, "invalid row pitch for the JPEG encoder (< 3*w)");
-    const JpegGeom g = geom_of(h, w, quality, sampling);
+    const JpegGeom g = geom_of(h, w, quality, sampling, optimize);
     const ScratchLayout L = layout_of(n, g);
     unsigned long long* flen = reinterpret_cast<unsigned long long*>(d_scratch + L.flen);
     unsigned* int_bytes = reinterpret_cast<unsigned*>(d_scratch + L.int_bytes);
@@ -499,16 +615,45 @@ void encode_jpeg_base64_launch(const unsigned char* d_rgb, int n, int h, int w, 
     const PngSrc src{d_rgb, (unsigned long long)row_pitch, (unsigned long long)image_pitch};
     const QuantArg qa = make_quant(quality);
     const dim3 grid(g.nint, n);
-    if (sampling == 2) {
-        if (g.big) hipLaunchKernelGGL((jpeg_interval_kernel<2, true>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes);
-        else hipLaunchKernelGGL((jpeg_interval_kernel<2, false>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes);
-    } else {
-        if (g.big) hipLaunchKernelGGL((jpeg_interval_kernel<0, true>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes);
-        else hipLaunchKernelGGL((jpeg_interval_kernel<0, false>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes);
+    const unsigned* no_codes = nullptr;
+    unsigned* no_hist = nullptr;
+    if (optimize) {
+        // count pass | table kernel | emit pass: a memset and two launches more than the fixed path, none depending on n
+        unsigned* hist = reinterpret_cast<unsigned*>(d_scratch + L.hist);
+        unsigned* codes = reinterpret_cast<unsigned*>(d_scratch + L.codes);
+        unsigned char* bits_vals = d_scratch + L.bits_vals;
+        int* nvals = reinterpret_cast<int*>(d_scratch + L.nvals);
+        IRE_HIP(hipMemsetAsync(hist, 0, (size_t)n * 4 * 256 * 4, s));
+        if (sampling == 2) hipLaunchKernelGGL((jpeg_interval_kernel<2, kClassSmall, kCount>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes, no_codes, hist);
+        else hipLaunchKernelGGL((jpeg_interval_kernel<0, kClassSmall, kCount>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes, no_codes, hist);
+        hipLaunchKernelGGL(jpeg_table_kernel, dim3(4, n), dim3(jpeghuff::kLanes), 0, s, (const unsigned*)hist, bits_vals, nvals, codes);
+        if (sampling == 2) hipLaunchKernelGGL((jpeg_interval_kernel<2, kClassAny, kEmitOwn>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes, (const unsigned*)codes, no_hist);
+        else hipLaunchKernelGGL((jpeg_interval_kernel<0, kClassAny, kEmitOwn>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes, (const unsigned*)codes, no_hist);
+        hipLaunchKernelGGL(jpeg_gather_kernel<true>, grid, dim3(kThreads), 0, s, g, jpeg_header(h, w, quality, sampling), intbuf, int_bytes, files, (unsigned long long)L.file_pitch,
+                           flen, d_lens, (unsigned long long)lens_pitch, (const unsigned char*)bits_vals, (const int*)nvals);
+        base64_device_length_launch(files, L.file_pitch, flen, (size_t)g.file_bound, n, d_chars, text_pitch, s);
+        IRE_HIP(hipGetLastError());
+        return;
     }
-    hipLaunchKernelGGL(jpeg_gather_kernel, grid, dim3(kThreads), 0, s, g, jpeg_header(h, w, quality, sampling), intbuf, int_bytes, files, (unsigned long long)L.file_pitch, flen,
-                       d_lens, (unsigned long long)lens_pitch);
+    const unsigned char* no_tables = nullptr;
+    const int* no_nvals = nullptr;
+    if (sampling == 2) {
+        if (g.big) hipLaunchKernelGGL((jpeg_interval_kernel<2, kClassBig, kEmitFixed>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes, no_codes, no_hist);
+        else hipLaunchKernelGGL((jpeg_interval_kernel<2, kClassSmall, kEmitFixed>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes, no_codes, no_hist);
+    } else {
+        if (g.big) hipLaunchKernelGGL((jpeg_interval_kernel<0, kClassBig, kEmitFixed>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes, no_codes, no_hist);
+        else hipLaunchKernelGGL((jpeg_interval_kernel<0, kClassSmall, kEmitFixed>), grid, dim3(kThreads), 0, s, src, g, qa, intbuf, int_bytes, no_codes, no_hist);
+    }
+    hipLaunchKernelGGL(jpeg_gather_kernel<false>, grid, dim3(kThreads), 0, s, g, jpeg_header(h, w, quality, sampling), intbuf, int_bytes, files, (unsigned long long)L.file_pitch, flen,
+                       d_lens, (unsigned long long)lens_pitch, no_tables, no_nvals);
     base64_device_length_launch(files, L.file_pitch, flen, (size_t)g.file_bound, n, d_chars, text_pitch, s);
+    IRE_HIP(hipGetLastError());
+}
+
+// The table kernel alone (ire_debug_jpeg_huffman): n x 4 histograms of 256 counts on the device -> their tables and symbol counts
+void jpeg_huffman_tables_launch(const unsigned* d_counts, int n, unsigned char* d_bits_vals, int* d_nvals, hipStream_t s) {
+    unsigned* no_codes = nullptr;
+    hipLaunchKernelGGL(jpeg_table_kernel, dim3(4, n), dim3(jpeghuff::kLanes), 0, s, d_counts, d_bits_vals, d_nvals, no_codes);
     IRE_HIP(hipGetLastError());
 }
 

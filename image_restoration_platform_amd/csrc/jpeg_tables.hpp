@@ -13,6 +13,8 @@
 #include <cstdint>
 #include <initializer_list>
 
+#include "jpeg_huff_core.hpp"
+
 namespace ire {
 namespace jpegtab {
 
@@ -225,6 +227,38 @@ static_assert(kBits100[0] < kNoCode && kBits100[1] < kNoCode, "no bound prices a
 constexpr bool big_class_of(int sampling, unsigned mcu_bits) { return raw_bound_of(sampling, mcu_bits) > kRawSmall; }
 constexpr bool fits_a_class(int sampling, unsigned mcu_bits) { return raw_bound_of(sampling, mcu_bits) <= kRawBig; }
 constexpr bool big_class(int quality, int sampling) { return big_class_of(sampling, mcu_bits_max(quality, sampling)); }
+
+// ---- optimised Huffman tables: the bound under ANY table ---------------------------------------------------------------------------
+// With the image's own tables (jpeg_huff_core.hpp) a symbol's code can be 16 bits, whatever the symbol.  Price each of a block's 64
+// positions at 16 bits plus the largest category it can have (step 2): a coded coefficient costs at most that; a ZRL code (at most 16
+// bits) stands for 16 zero positions and the EOB (at most 16 bits) for at least one, each of them priced at 16 bits or more.  At
+// quality 100 that is 1665 bits per block (16 * 64 + 11 + 63 * 10) and 9990 bytes per interval of 48 blocks, above kRawBig (9448),
+// which was sized under the fixed tables.  ONE size class, sized for quality 100: the optimised path runs a count pass and a table
+// kernel beside the emit pass, so the emit pass's occupancy is a smaller share of its time than of the fixed path's, and the head's
+// length (at most the fixed head's: a DC table has at most 12 symbols, an AC table 162) already varies per image.
+constexpr unsigned block_bits_any(int table, int quality) {
+    unsigned b = 0;
+    for (int k = 0; k < 64; ++k) b += 16u + (unsigned)size_max(table, k, quality);
+    return b;
+}
+constexpr unsigned mcu_bits_any(int quality, int sampling) { return (sampling == 2 ? 4u : 1u) * block_bits_any(0, quality) + 2 * block_bits_any(1, quality); }
+constexpr unsigned kBitsAny100[2] = {mcu_bits_any(100, 0), mcu_bits_any(100, 2)};
+constexpr unsigned kRawAny = umax(raw_bound_of(0, kBitsAny100[0]), raw_bound_of(2, kBitsAny100[1]));
+static_assert(block_bits_any(0, 100) == 1665 && kRawAny == 9990, "48 blocks of 1665 bits");
+static_assert(kRawAny >= kRawBig, "no table is worse than every table");
+constexpr bool fits_any_class(int sampling, unsigned mcu_bits) { return raw_bound_of(sampling, mcu_bits) <= kRawAny; }      // (every setting: the dump checks all 200)
+constexpr size_t jpeg_opt_file_bound(int h, int w, int quality, int sampling) { return jpeg_file_bound_of(h, w, sampling, mcu_bits_any(quality, sampling)); }
+constexpr size_t jpeg_opt_base64_bound(int h, int w, int quality, int sampling) { return (jpeg_opt_file_bound(h, w, quality, sampling) + 2) / 3 * 4; }
+// The head of such a file: the fixed parts of jpeg_header and four tables (bits_vals[4][jpeghuff::kBitsVals] and nvals[4], in the
+// order of the DHT segments: 0x00, 0x10, 0x01, 0x11) -> out[<= kHeaderBytes]; returns its length.  Byte by byte through the function
+// jpeg.hip's gather kernel uses.
+inline size_t jpeg_header_opt(int h, int w, int quality, int sampling, const unsigned char* bits_vals, const int32_t* nvals, unsigned char* out) {
+    const JpegHeader fixed = jpeg_header(h, w, quality, sampling);
+    const unsigned n = jpeghuff::opt_head_bytes(nvals);
+    for (unsigned k = 0; k < n && k < (unsigned)kHeaderBytes; ++k) out[k] = jpeghuff::opt_head_byte(k, fixed.b, bits_vals, nvals);
+    return n;
+}
+static_assert(jpeghuff::kHeadFixedBytes == (unsigned)kHeaderBytes, "one head length");
 
 }  // namespace jpegtab
 }  // namespace ire

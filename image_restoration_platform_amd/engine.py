@@ -16,13 +16,16 @@ FAMILIES = ["classifier", "conv3x3", "conv1x1", "stem", "head", "gn_finalize", "
 
 
 # One row per text format (csrc/codec.hpp TextFormat): the engine flag that selects it for the batcher's results, the ABI's host and
-# device entry, the Engine method that gives its bound, the noun of its messages, and whether a uint64 count goes with every text.
-TextFormat = collections.namedtuple("TextFormat", "flag host device bound noun counted")
+# device entry, the Engine method that gives its bound, the noun of its messages, whether a uint64 count goes with every text, and what
+# the entries' names end in where they take the format's settings.  "jpeg_opt" is no result format of its own (flag 0): it is "jpeg"
+# with the image's own Huffman tables, chosen by IRE_FLAG_JPEG_OPTIMIZE beside IRE_FLAG_RESULT_JPEG or by optimize=True in a call.
+TextFormat = collections.namedtuple("TextFormat", "flag host device bound noun counted ex", defaults=("_ex",))
 TEXT_FORMATS = {
     "png": TextFormat(_lib.IRE_FLAG_RESULT_PNG_BASE64, "ire_encode_png_base64_fit", "ire_encode_png_base64_fit_device", "png_base64_bytes_fit", "PNG", False),
     "png_deflate": TextFormat(_lib.IRE_FLAG_RESULT_PNG_DEFLATE, "ire_encode_png_deflate_base64_fit", "ire_encode_png_deflate_base64_fit_device",
                               "png_deflate_base64_bound", "PNG", True),
     "jpeg": TextFormat(_lib.IRE_FLAG_RESULT_JPEG, "ire_encode_jpeg_base64_fit", "ire_encode_jpeg_base64_fit_device", "jpeg_base64_bound", "JPEG", True),
+    "jpeg_opt": TextFormat(0, "ire_encode_jpeg_optimized_base64_fit", "ire_encode_jpeg_optimized_base64_fit_device", "_jpeg_optimized_base64_bound", "JPEG", True, ""),
 }
 
 
@@ -73,7 +76,8 @@ class Engine:
     def __init__(self, device_index=0, max_batch=8, num_streams=0, weights_path="default", seed=0, flags=0, precision="bf16", jpeg_quality=0,
                  jpeg_sampling=0):
         """jpeg_quality (1..100; 0: 85) and jpeg_sampling (0 = 4:4:4, 2 = 4:2:0): the settings of the results of an engine created with
-        flags=IRE_FLAG_RESULT_JPEG; invalid without that flag."""
+        flags=IRE_FLAG_RESULT_JPEG; invalid without that flag.  flags=IRE_FLAG_RESULT_JPEG | IRE_FLAG_JPEG_OPTIMIZE: those results
+        carry their image's own, optimised Huffman tables (poll sizes its buffer by the larger bound of such a text)."""
         self._lib = _lib.load()
         if weights_path == "default":
             weights_path = _weights.ensure_default(seed)
@@ -385,7 +389,7 @@ class Engine:
         stride = (cb + 15) // 16 * 16
         out = np.empty((n, stride), np.uint8)
         lens = np.zeros(n, np.uint64) if f.counted else None
-        self._check(getattr(self._lib, f.host + ("_ex" if ex else ""))(self._h, _ptr(x), n, h, w, _ptr(out), stride, *([_ptr(lens)] if f.counted else []), *ex))
+        self._check(getattr(self._lib, f.host + (f.ex if ex else ""))(self._h, _ptr(x), n, h, w, _ptr(out), stride, *([_ptr(lens)] if f.counted else []), *ex))
         res = [out[i, :int(lens[i]) if f.counted else cb].tobytes() for i in range(n)]
         return res[0] if single else res
 
@@ -406,7 +410,7 @@ class Engine:
         stride = (cb + 3) // 4 * 4
         out = torch.empty((n, stride), dtype=torch.uint8, device=rgb_u8.device)
         lens = torch.zeros(n, dtype=torch.int64, device=rgb_u8.device) if f.counted else None      # (the counts are uint64 and < 2^63)
-        self._check(getattr(self._lib, f.device + ("_ex" if ex else ""))(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), n, h, w, sr, si if n > 1 else max(si, sr * h),
+        self._check(getattr(self._lib, f.device + (f.ex if ex else ""))(self._h, ctypes.c_void_p(rgb_u8.data_ptr()), n, h, w, sr, si if n > 1 else max(si, sr * h),
                                                                          ctypes.c_void_p(out.data_ptr()), stride,
                                                                          *([ctypes.c_void_p(lens.data_ptr())] if f.counted else []), *ex, self._stream_ptr(stream)))
         return (out[:, :cb], lens) if f.counted else out[:, :cb]
@@ -433,21 +437,43 @@ class Engine:
         q0, s0 = getattr(self, "_jpeg_settings", (0, 0))
         return (q0 if quality is None else int(quality), s0 if sampling is None else int(sampling))
 
-    def jpeg_base64_bound(self, h, w, quality=None, sampling=None):
-        """The most characters the JPEG encoder can give for an h x w image at a quality (1..100) and sampling (0 = 4:4:4, 2 = 4:2:0);
-        left out: this engine's settings.  0 outside 1..8192 or for settings the encoder refuses.  Sizes every buffer."""
+    def _jpeg_fmt(self, optimize):
+        """"jpeg_opt" | "jpeg": what the call names, else this engine's own setting (IRE_FLAG_JPEG_OPTIMIZE)"""
+        own = bool(getattr(self, "_flags", 0) & _lib.IRE_FLAG_JPEG_OPTIMIZE)
+        return "jpeg_opt" if (own if optimize is None else bool(optimize)) else "jpeg"
+
+    def _jpeg_optimized_base64_bound(self, h, w, quality, sampling):
+        return int(self._lib.ire_jpeg_optimized_base64_bound(int(h), int(w), int(quality), int(sampling)))
+
+    def jpeg_base64_bound(self, h, w, quality=None, sampling=None, optimize=None):
+        """The most characters the JPEG encoder can give for an h x w image at a quality (1..100) and sampling (0 = 4:4:4, 2 = 4:2:0),
+        with the fixed Huffman tables or (optimize=True: a larger bound) the image's own; left out: this engine's settings.  0 outside
+        1..8192 or for settings the encoder refuses.  Sizes every buffer."""
+        if self._jpeg_fmt(optimize) == "jpeg_opt":
+            return self._jpeg_optimized_base64_bound(h, w, *self._jpeg_ex(quality, sampling))
         return int(self._lib.ire_jpeg_base64_bound_ex(int(h), int(w), *self._jpeg_ex(quality, sampling)))
 
-    def encode_jpeg_base64_fit(self, rgb, quality=None, sampling=None):
+    def encode_jpeg_base64_fit(self, rgb, quality=None, sampling=None, optimize=None):
         """[N,H,W,3] (or [H,W,3]) uint8, any size 1..8192 per side -> list of N `bytes` (one for a single image): the base64 text of a
         baseline JPEG file of each image, encoded on the device; each of its real length.  quality 1..100 and sampling 0 = 4:4:4 |
-        2 = 4:2:0; left out: this engine's settings (quality 85, 4:4:4 unless it was created with others)."""
-        return self._encode_fit("jpeg", rgb, self._jpeg_ex(quality, sampling))
+        2 = 4:2:0; optimize: the file carries the image's own Huffman tables (smaller, the same pixels); left out: this engine's
+        settings (quality 85, 4:4:4, the fixed tables unless it was created with others)."""
+        return self._encode_fit(self._jpeg_fmt(optimize), rgb, self._jpeg_ex(quality, sampling))
 
-    def encode_jpeg_base64_fit_tensor(self, rgb_u8, stream=None, quality=None, sampling=None):
+    def encode_jpeg_base64_fit_tensor(self, rgb_u8, stream=None, quality=None, sampling=None, optimize=None):
         """cuda uint8 [N,h,w,3], possibly a window of a larger tensor -> (cuda uint8 [N, bound] ASCII, cuda int64 [N] character counts),
-        asynchronous on the stream: text i is out[i, :lens[i]].  quality, sampling: as for encode_jpeg_base64_fit."""
-        return self._encode_fit_tensor("jpeg", rgb_u8, stream, self._jpeg_ex(quality, sampling))
+        asynchronous on the stream: text i is out[i, :lens[i]].  quality, sampling, optimize: as for encode_jpeg_base64_fit."""
+        return self._encode_fit_tensor(self._jpeg_fmt(optimize), rgb_u8, stream, self._jpeg_ex(quality, sampling))
+
+    def debug_jpeg_huffman(self, counts):
+        """[n][4][256] symbol counts -> (bits_vals uint8 [n][4][272], nvals int32 [n][4]): the tables the optimised JPEG path's table
+        kernel builds (tests only)"""
+        c = np.ascontiguousarray(counts, np.uint32)
+        assert c.ndim == 3 and c.shape[1:] == (4, 256)
+        bv = np.zeros((c.shape[0], 4, 16 + 256), np.uint8)
+        nv = np.zeros((c.shape[0], 4), np.int32)
+        self._check(self._lib.ire_debug_jpeg_huffman(self._h, _ptr(c), c.shape[0], _ptr(bv), _ptr(nv)))
+        return bv, nv
 
     # ---- JPEG uploads decoded on the device (csrc/jpeg_parse.hpp, csrc/jpeg_dec.hip) -------------------------------------------
     @property

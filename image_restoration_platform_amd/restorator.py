@@ -95,9 +95,16 @@ def encode_jpeg_base64(rgb, quality=85):
 #   jpeg-device  a baseline JPEG (byte for byte what libjpeg-turbo writes with a restart interval of 48 blocks) + its base64 text
 #               written by the GPU (csrc/jpeg.hip): no host codec work, and the shortest string; the engine flag is
 #               IRE_FLAG_RESULT_JPEG.  IRE_JPEG_QUALITY (1..100) and IRE_JPEG_SUBSAMPLING (0 = 4:4:4, 2 = 4:2:0) choose the file's
-#               settings; unset: quality 85 at 4:4:4, the reference's settings
+#               settings; unset: quality 85 at 4:4:4, the reference's settings.  IRE_JPEG_OPTIMIZE=1: every file carries its image's
+#               own Huffman tables (IRE_FLAG_JPEG_OPTIMIZE), as the reference's mozjpeg encode does: a shorter string, the same pixels
 RESULT_CODEC = os.environ.get("IRE_RESULT_CODEC", "png")
 JPEG_SETTINGS = (int(os.environ.get("IRE_JPEG_QUALITY") or 0), int(os.environ.get("IRE_JPEG_SUBSAMPLING") or 0))      # (0: the default)
+JPEG_OPTIMIZE = (os.environ.get("IRE_JPEG_OPTIMIZE") or "0") not in ("0", "")
+
+
+def jpeg_engine_flags(result_codec=None):
+    """IRE_FLAG_JPEG_OPTIMIZE where IRE_JPEG_OPTIMIZE asks for it and the codec value's engine flag allows it, to be or-ed to that flag."""
+    return _lib.IRE_FLAG_JPEG_OPTIMIZE if JPEG_OPTIMIZE and (result_codec or RESULT_CODEC) == "jpeg-device" else 0
 
 
 def jpeg_engine_kwargs(result_codec=None):
@@ -165,7 +172,7 @@ class EngineRestorer:
             return self.engine.encode_png_deflate_base64_fit(result).decode("ascii")
         if self.result_codec == "jpeg-device":      # a JPEG engine's own settings; on any other engine the environment's
             own = getattr(self.engine, "_flags", 0) & _lib.IRE_FLAG_RESULT_JPEG
-            return self.engine.encode_jpeg_base64_fit(result, *((None, None) if own else JPEG_SETTINGS)).decode("ascii")
+            return self.engine.encode_jpeg_base64_fit(result, *((None, None, None) if own else JPEG_SETTINGS + (JPEG_OPTIMIZE,))).decode("ascii")
         return encode_png_base64(result)
 
     @staticmethod

@@ -102,6 +102,12 @@ typedef struct ire_config {
  * sizes are equal.  Without it such a file is refused as before and stays with the host codec.  (Bit value 16 stays unknown, as 2
  * does: tests/test_jpeg_model.py holds it to that.) */
 #define IRE_FLAG_DECODE_PROGRESSIVE 32u
+/* Not a result format: valid only together with IRE_FLAG_RESULT_JPEG (else ire_init fails, "invalid ... IRE_FLAG_RESULT_JPEG").
+ * Every JPEG result carries the image's own, optimised Huffman tables (ire_encode_jpeg_optimized_base64_fit_device below) in place
+ * of the Annex K ones: a smaller text that decodes to the same pixels.  Such a result is fetched with ire_poll_text into a buffer of
+ * ire_jpeg_optimized_base64_bound(h, w, quality, sampling) bytes, which is larger than ire_jpeg_base64_bound_ex's.  (Bit values 2,
+ * 16 and 64 stay unknown.) */
+#define IRE_FLAG_JPEG_OPTIMIZE 128u
 
 
 
@@ -269,6 +275,22 @@ int ire_encode_jpeg_base64_fit_device_ex(ire_engine* e, const uint8_t* d_rgb, in
                                          uint64_t* d_lens /* n x uint64, device */, int quality, int sampling, void* stream);
 int ire_encode_jpeg_base64_fit_ex(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes,
                                   uint64_t* lens /* n x uint64, host */, int quality, int sampling);
+/* The same three with OPTIMISED Huffman tables, libjpeg's optimize_coding: a first pass over the image counts its symbols (four
+ * histograms: DC and AC, for Y and for Cb and Cr together; the DC predictors restart at every restart interval in that pass too), a
+ * table per histogram is built as libjpeg's jpeg_gen_optimal_table builds it (code lengths limited to 16), and a second pass codes the
+ * image with them.  All on the device, two launches and one small memset more than the fixed-table call, none depending on n, no host
+ * round trip.  The file is the one above except that its four DHT segments (0x00, 0x10, 0x01, 0x11) carry the image's own tables, so
+ * the head's length varies (at most the fixed head's 629 bytes).  The bytes equal libjpeg-turbo's for quality=, subsampling=,
+ * optimize=True, restart_marker_blocks = 16 | 8 (tests/test_jpeg_huffopt_model.py), and decode to the pixels the fixed-table file
+ * decodes to.  Arguments, refusals and the asynchronous, windowed device form are those of the _ex entries.  The bound is larger than
+ * ire_jpeg_base64_bound_ex's: under an arbitrary table every code can be 16 bits, so a block is priced at 16 bits per position plus its
+ * largest categories -- 1665 bits per block at quality 100. */
+size_t ire_jpeg_optimized_base64_bound(int h, int w, int quality, int sampling);
+int ire_encode_jpeg_optimized_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes,
+                                                size_t image_pitch_bytes, uint8_t* d_chars, size_t stride_bytes,
+                                                uint64_t* d_lens /* n x uint64, device */, int quality, int sampling, void* stream);
+int ire_encode_jpeg_optimized_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes,
+                                         uint64_t* lens /* n x uint64, host */, int quality, int sampling);
 
 /* ---- baseline JPEG uploads decoded on the device ----
  * The RGB bytes equal libjpeg-turbo's (PIL.Image.open(f).convert("RGB")): the file's own Huffman tables, libjpeg's "islow" inverse
@@ -455,6 +477,11 @@ int ire_get_stats(ire_engine* e, ire_engine_stats* out);
 int ire_debug_classifier_sums(ire_engine* e, int n, uint64_t* sums_out);
 /* The blend tables of n noise scores (host), built on the device by the kernel the fusion jobs use, copied to out (tests only). */
 int ire_debug_fusion_wlut(ire_engine* e, const double* noise, int n, uint32_t* out /* [n][256] */);
+/* The Huffman tables of n x 4 histograms of 256 symbol counts (host; each count below 10^9, as libjpeg requires), built on the device
+ * by the kernel the optimised JPEG results use: per histogram bits[16] then vals[256] (zero behind the nvals symbols that have a
+ * code).  n in 1..4096 (tests only). */
+int ire_debug_jpeg_huffman(ire_engine* e, const uint32_t* counts /* [n][4][256] */, int n, uint8_t* bits_vals_out /* [n][4][16 + 256] */,
+                           int32_t* nvals_out /* [n][4] */);
 /* Turn per-layer capture on/off (slow: synchronises after every layer; tests only). */
 int ire_debug_capture(ire_engine* e, int on);
 /* Copy one named intermediate activation of the last ire_restore* call to host as float32 NHWC.

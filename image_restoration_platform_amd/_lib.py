@@ -11,7 +11,10 @@ IRE_FLAG_RESULT_PNG_DEFLATE = 4
 IRE_FLAG_RESULT_JPEG = 8
 IRE_FLAG_DECODE_PROGRESSIVE = 32
 IRE_FLAG_JPEG_OPTIMIZE = 128
+IRE_FLAG_UPLOAD_ICC = 256
 IRE_DECODE_ACCEPT_PROGRESSIVE = 1
+IRE_DECODE_ACCEPT_ICC = 4
+IRE_ICC_NONE, IRE_ICC_IDENTITY, IRE_ICC_MATRIX, IRE_ICC_GREY = range(4)
 IRE_DECODE_MAX_SCANS = 64
 IRE_ABI_VERSION = 3      # include/ire.h; load() refuses a library of another version (tests/test_abi.py cross-checks the three copies)
 
@@ -20,6 +23,10 @@ class IreConfig(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("device_index", ctypes.c_int32), ("precision", ctypes.c_int32),
                 ("max_batch", ctypes.c_int32), ("num_streams", ctypes.c_int32), ("weights_path", ctypes.c_char_p),
                 ("flags", ctypes.c_uint32), ("jpeg_quality", ctypes.c_int32), ("jpeg_sampling", ctypes.c_int32)]
+
+
+class IreIccTransform(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("m", ctypes.c_int32 * 9), ("lin", (ctypes.c_uint16 * 256) * 3)]
 
 
 class IreTimings(ctypes.Structure):
@@ -60,6 +67,10 @@ SYMBOLS = {
     "ire_upload_plan": (_i, [_u8p, ctypes.c_size_t, ctypes.c_uint32, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i),
                              ctypes.POINTER(_i)]),
     "ire_submit_upload": (_i, [_vp, _u8p, ctypes.c_size_t, _i, _vp, ctypes.POINTER(_vp)]),
+    "ire_icc_plan_profile": (_i, [_u8p, ctypes.c_size_t, _i, ctypes.POINTER(IreIccTransform)]),
+    "ire_icc_plan_file": (_i, [_u8p, ctypes.c_size_t, ctypes.POINTER(IreIccTransform)]),
+    "ire_icc_to_srgb_device": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_size_t, _vp, _vp]),
+    "ire_icc_to_srgb": (_i, [_vp, _u8p, _i, _i, _i, _vp]),
     "ire_png_base64_bytes": (ctypes.c_size_t, [_i, _i]),
     "ire_encode_png_base64_device": (_i, [_vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
     "ire_encode_png_base64": (_i, [_vp, _u8p, _i, _i, _i, _u8p, ctypes.c_size_t]),

@@ -68,6 +68,7 @@ struct HipSlot : SlotMem<DeviceMem, PinnedMem> {
 struct JpegFileHead {
     jpegparse::File hd;
     std::vector<jpegdec::DecStream> streams;
+    std::unique_ptr<icc::Transform> icc;      // an upload on an engine with IRE_FLAG_UPLOAD_ICC whose profile needs a transform; else null
 };
 
 // CPU set of this engine's service threads (affinity.hpp): IRE_CPU_AFFINITY = "off" | a cpulist overrides the sysfs plan
@@ -188,6 +189,13 @@ struct HipBatchBackend {
         // the any-size staging rule (ire.h): for max_batch images while that is <= 256 MB, else for the batch at hand
         P.d_stored.grow(sb * (size_t)(first + count), batch_room(sb * (size_t)(first + count), sb * (size_t)E.max_batch()));
         decode_runs(hs, b, first, count, ib, sh, sw, P.d_stored.get<uint8_t>(), sb, heads, used);
+        // the file's ICC profile, as sharp honours it: before the resize.  Every job brings its own tables (the profile is no part of the
+        // key); a push in which no job has any enqueues nothing.
+        if (E.upload_icc()) {
+            const icc::Transform* t[kMaxBatch];
+            for (int i = 0; i < count; ++i) t[i] = used[i] ? static_cast<const JpegFileHead*>(heads[i])->icc.get() : nullptr;
+            E.icc_converter().to_srgb_device(true, P.d_stored.get<uint8_t>() + sb * (size_t)first, count, sh, sw, sb, t, cs);
+        }
         // (a job with nothing decoded is fitted from whatever the scratch held: it fails alone, its place is never read)
         E.preprocess_batch_device(P, P.d_stored.get<uint8_t>() + sb * (size_t)first, count, sh, sw, sb, key.up[2], key.up[3], hs.d_in.get<uint8_t>() + ib * (size_t)first, h, w, ib, cs);
     }
@@ -220,6 +228,12 @@ struct HipBatchBackend {
     std::shared_ptr<void> upload_plan(const uint8_t* file, size_t bytes, int max_dim, int* h, int* w, size_t* room, int key[4]) {
         int sh = 0, sw = 0;
         auto head = file_plan(file, bytes, &sh, &sw, room);
+        if (E.upload_icc()) {
+            icc::Transform t;
+            std::string why;
+            if (!icc::plan_file(file, bytes, t, why)) fail(IRE_ERR_INVALID_INPUT, why);
+            if (t.kind == icc::kMatrix || t.kind == icc::kGrey) static_cast<JpegFileHead*>(head.get())->icc.reset(new icc::Transform(t));
+        }
         key[0] = sh; key[1] = sw; key[2] = jpegparse::file_orientation(file, bytes); key[3] = max_dim;
         preprocess_plan(sw, sh, key[2], max_dim, w, h, nullptr);
         if (!piece_addressable(Engine::fit_dim(*h), Engine::fit_dim(*w), 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(Engine::fit_dim(*h), Engine::fit_dim(*w)));
@@ -497,10 +511,14 @@ int ire_preprocess_batch_device(ire_engine* e, const uint8_t* d_rgb, int n, int 
 int ire_upload_plan(const uint8_t* file, size_t bytes, uint32_t accept, int max_dim, int* stored_h, int* stored_w, int* orientation, int* out_h, int* out_w) {
     return guarded([&] {
         if (!file) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_upload_plan: null file");
-        if (accept & ~(uint32_t)IRE_DECODE_ACCEPT_PROGRESSIVE) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_upload_plan: unknown accept bits");
+        if (accept & ~(uint32_t)(IRE_DECODE_ACCEPT_PROGRESSIVE | IRE_DECODE_ACCEPT_ICC)) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_upload_plan: unknown accept bits");
         jpegparse::File f;
         std::string why;
-        if (!jpegparse::plan_file(file, bytes, accept, f, why)) fail(IRE_ERR_INVALID_INPUT, why);
+        if (!jpegparse::plan_file(file, bytes, accept & IRE_DECODE_ACCEPT_PROGRESSIVE, f, why)) fail(IRE_ERR_INVALID_INPUT, why);
+        if (accept & IRE_DECODE_ACCEPT_ICC) {
+            icc::Transform t;
+            if (!icc::plan_file(file, bytes, t, why)) fail(IRE_ERR_INVALID_INPUT, why);
+        }
         const int o = jpegparse::file_orientation(file, bytes);
         int ow = 0, oh = 0;
         preprocess_plan(f.hd.im.w, f.hd.im.h, o, max_dim, &ow, &oh, nullptr);
@@ -511,6 +529,41 @@ int ire_upload_plan(const uint8_t* file, size_t bytes, uint32_t accept, int max_
         if (orientation) *orientation = o;
         if (out_h) *out_h = oh;
         if (out_w) *out_w = ow;
+    });
+}
+
+static_assert(sizeof(ire_icc_transform) == sizeof(icc::Transform) && offsetof(ire_icc_transform, lin) == offsetof(icc::Transform, lin) &&
+              IRE_ICC_NONE == icc::kNone && IRE_ICC_IDENTITY == icc::kIdentity && IRE_ICC_MATRIX == icc::kMatrix && IRE_ICC_GREY == icc::kGrey, "ire.h and icc_parse.hpp");
+
+int ire_icc_plan_profile(const uint8_t* profile, size_t bytes, int components, ire_icc_transform* out) {
+    return guarded([&] {
+        if (!profile || !out || (components != 1 && components != 3)) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_icc_plan_profile");
+        std::string why;
+        if (!icc::plan_profile(profile, bytes, components, *reinterpret_cast<icc::Transform*>(out), why)) fail(IRE_ERR_INVALID_INPUT, why);
+    });
+}
+
+int ire_icc_plan_file(const uint8_t* file, size_t bytes, ire_icc_transform* out) {
+    return guarded([&] {
+        if (!file || !out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_icc_plan_file");
+        std::string why;
+        if (!icc::plan_file(file, bytes, *reinterpret_cast<icc::Transform*>(out), why)) fail(IRE_ERR_INVALID_INPUT, why);
+    });
+}
+
+int ire_icc_to_srgb_device(ire_engine* e, uint8_t* d_rgb, int n, int h, int w, size_t image_pitch_bytes, const ire_icc_transform* const* t, void* stream) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, (hipStream_t)stream, [&] {
+            E.icc_converter().to_srgb_device(false, d_rgb, n, h, w, image_pitch_bytes, reinterpret_cast<const icc::Transform* const*>(t), (hipStream_t)stream);
+        });
+    });
+}
+
+int ire_icc_to_srgb(ire_engine* e, uint8_t* rgb, int n, int h, int w, const ire_icc_transform* const* t) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, E.main_stream(), [&] { E.icc_converter().to_srgb_host(rgb, n, h, w, reinterpret_cast<const icc::Transform* const*>(t), E.main_stream()); });
     });
 }
 

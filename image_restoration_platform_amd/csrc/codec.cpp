@@ -34,7 +34,7 @@ const TextFormat kJpeg = {"JPEG", [](int h, int w, TextSettings o) { return jpeg
 
 void check_config_flags(uint32_t flags) {
     constexpr uint32_t kResultBits = IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG;
-    if (flags & ~(kResultBits | IRE_FLAG_DECODE_PROGRESSIVE | IRE_FLAG_JPEG_OPTIMIZE)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
+    if (flags & ~(kResultBits | IRE_FLAG_DECODE_PROGRESSIVE | IRE_FLAG_JPEG_OPTIMIZE | IRE_FLAG_UPLOAD_ICC)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
     if (((flags & kResultBits) & ((flags & kResultBits) - 1)) != 0) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");
 }
 

@@ -6,6 +6,7 @@ Nothing here computes pixels on the CPU; if libire.so or the GPU is missing ever
 """
 import collections
 import ctypes
+import os
 
 import numpy as np
 
@@ -72,12 +73,44 @@ def upload_plan_reason(data, max_dim=2048, accept=0):
     return tuple(x.value for x in v), None
 
 
+def _icc_result(rc, t):
+    if rc != 0:
+        return None, (_lib.load().ire_last_error() or b"").decode()
+    return t, None
+
+
+def icc_plan_file(data):
+    """bytes of a JPEG file -> (IreIccTransform, None): what an engine created with upload_icc=True does with the file's ICC profile
+    (.kind: IRE_ICC_NONE / IDENTITY / MATRIX / GREY) -- or (None, reason) for a profile it refuses.  Pure host, no engine, no GPU."""
+    data = bytes(data)
+    t = _lib.IreIccTransform()
+    return _icc_result(_lib.load().ire_icc_plan_file(data, len(data), ctypes.byref(t)), t)
+
+
+def icc_plan_profile(profile, components=3):
+    """icc_plan_file for the raw bytes of a profile that came with an image of 1 or 3 components (a PNG's iCCP, decoded on the host)."""
+    profile = bytes(profile)
+    t = _lib.IreIccTransform()
+    return _icc_result(_lib.load().ire_icc_plan_profile(profile, len(profile), int(components), ctypes.byref(t)), t)
+
+
+def upload_icc_flags(flags, upload_icc=None, environ=None):
+    """the flags of an engine: IRE_FLAG_UPLOAD_ICC is added for upload_icc=True and, when upload_icc is None, for IRE_UPLOAD_ICC=1 in
+    the environment (which then holds for EVERY engine of the process that does not say upload_icc=False); nothing is ever taken away"""
+    if upload_icc is None:
+        upload_icc = (os.environ if environ is None else environ).get("IRE_UPLOAD_ICC") == "1"
+    return flags | _lib.IRE_FLAG_UPLOAD_ICC if upload_icc else flags
+
+
 class Engine:
     def __init__(self, device_index=0, max_batch=8, num_streams=0, weights_path="default", seed=0, flags=0, precision="bf16", jpeg_quality=0,
-                 jpeg_sampling=0):
+                 jpeg_sampling=0, upload_icc=None):
         """jpeg_quality (1..100; 0: 85) and jpeg_sampling (0 = 4:4:4, 2 = 4:2:0): the settings of the results of an engine created with
         flags=IRE_FLAG_RESULT_JPEG; invalid without that flag.  flags=IRE_FLAG_RESULT_JPEG | IRE_FLAG_JPEG_OPTIMIZE: those results
-        carry their image's own, optimised Huffman tables (poll sizes its buffer by the larger bound of such a text)."""
+        carry their image's own, optimised Huffman tables (poll sizes its buffer by the larger bound of such a text).
+        upload_icc=True (or IRE_FLAG_UPLOAD_ICC in flags; None: the environment's IRE_UPLOAD_ICC=1): submit_upload converts the pixels
+        of a file that carries an ICC profile to sRGB on the device, before the resize."""
+        flags = upload_icc_flags(flags, upload_icc)
         self._lib = _lib.load()
         if weights_path == "default":
             weights_path = _weights.ensure_default(seed)
@@ -241,7 +274,7 @@ class Engine:
     def upload_plan(self, data, max_dim=2048):
         """(stored_h, stored_w, orientation, out_h, out_w) of a JPEG upload as THIS engine's submit_upload takes it; raises EngineError
         (invalid input, the plan's reason) for a file it refuses.  Pure host arithmetic."""
-        plan, why = upload_plan_reason(data, max_dim, self.decode_accept)
+        plan, why = upload_plan_reason(data, max_dim, self.upload_accept)
         if plan is None:
             raise EngineError(_lib.IRE_ERR_INVALID_INPUT, why)
         return plan
@@ -249,13 +282,14 @@ class Engine:
     def submit_upload(self, data, max_dim=2048, scores=None):
         """Queue one JPEG upload as its bytes: decoded, turned upright by its EXIF orientation, fitted inside max_dim (Lanczos-3) and
         restored, all on the device with its batch.  The result is that of submit_fit(preprocess(decode_jpeg(data), orientation,
-        max_dim), is_jpeg=True, scores), of the fitted size upload_plan reports.  Raises EngineError (invalid input) for a file the plan
+        max_dim), is_jpeg=True, scores), of the fitted size upload_plan reports; on an engine created with upload_icc=True the decoded
+        pixels first go through icc_to_srgb with the file's own transform (icc_plan_file).  Raises EngineError (invalid input) for a file the plan
         refuses: no job exists then.  A file with corrupt data fails at its poll."""
         data = bytes(data)
         sc = None if scores is None else np.ascontiguousarray(np.asarray(scores, dtype=np.float64).reshape(7))
         job = ctypes.c_void_p()
         self._check(self._lib.ire_submit_upload(self._h, data, len(data), int(max_dim), _ptr(sc), ctypes.byref(job)))
-        _, _, _, oh, ow = upload_plan_reason(data, max_dim, self.decode_accept)[0]
+        _, _, _, oh, ow = upload_plan_reason(data, max_dim, self.upload_accept)[0]
         return (job, oh, ow)
 
     def submit(self, rgb, is_jpeg=True, scores=None):
@@ -481,6 +515,29 @@ class Engine:
         """what this engine's decoder takes beside baseline files: IRE_DECODE_ACCEPT_PROGRESSIVE when it was created with
         IRE_FLAG_DECODE_PROGRESSIVE, else 0"""
         return _lib.IRE_DECODE_ACCEPT_PROGRESSIVE if getattr(self, "_flags", 0) & _lib.IRE_FLAG_DECODE_PROGRESSIVE else 0
+
+    @property
+    def upload_accept(self):
+        """decode_accept, and IRE_DECODE_ACCEPT_ICC when the engine was created with IRE_FLAG_UPLOAD_ICC: what upload_plan_reason is asked"""
+        return self.decode_accept | (_lib.IRE_DECODE_ACCEPT_ICC if getattr(self, "_flags", 0) & _lib.IRE_FLAG_UPLOAD_ICC else 0)
+
+    def icc_to_srgb(self, rgb, transforms):
+        """[n,h,w,3] uint8 (or one [h,w,3]) and n IreIccTransform (None: leave the image) -> the converted copy: ire_icc_to_srgb."""
+        a = np.array(rgb, dtype=np.uint8, order="C")
+        one = a.ndim == 3
+        b = a[None] if one else a
+        n, h, w, _ = b.shape
+        assert len(transforms) == n
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.addressof(t) if t is not None else None for t in transforms])
+        self._check(self._lib.ire_icc_to_srgb(self._h, _ptr(b), n, h, w, ptrs))
+        return b[0] if one else b
+
+    def icc_to_srgb_device(self, buf_u8, n, h, w, pitch, transforms, stream=None):
+        """in place over a cuda uint8 tensor that holds n images of h x w x 3 bytes, `pitch` bytes apart: ire_icc_to_srgb_device"""
+        assert buf_u8.is_cuda and buf_u8.is_contiguous() and buf_u8.numel() >= pitch * (n - 1) + h * w * 3 and len(transforms) == n
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.addressof(t) if t is not None else None for t in transforms])
+        self._check(self._lib.ire_icc_to_srgb_device(self._h, ctypes.c_void_p(buf_u8.data_ptr()), n, h, w, int(pitch), ptrs, self._stream_ptr(stream)))
+        return buf_u8
 
     def decode_jpeg_plan_reason(self, data):
         """bytes of a file -> ((h, w, sampling), None) when THIS engine's device decodes it (sampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0,

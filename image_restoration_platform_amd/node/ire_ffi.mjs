@@ -41,6 +41,10 @@ export function bindIre(libPath) {
     ire_submit_jpeg: ['int', [P, P, 'size_t', P, PP]],
     ire_submit_upload: ['int', [P, P, 'size_t', 'int', P, PP]],
     ire_upload_plan: ['int', [P, 'size_t', 'int', 'int', P, P, P, P, P]],
+    ire_icc_plan_profile: ['int', [P, 'size_t', 'int', P]],
+    ire_icc_plan_file: ['int', [P, 'size_t', P]],
+    ire_icc_to_srgb_device: ['int', [P, P, 'int', 'int', 'int', 'size_t', P, P]],
+    ire_icc_to_srgb: ['int', [P, P, 'int', 'int', 'int', P]],
     ire_preprocess_batch_device: ['int', [P, P, 'int', 'int', 'int', 'size_t', 'int', 'int', P, 'int', 'int', 'size_t', P]],
     ire_submit_fuse_fit: ['int', [P, P, 'int', 'int', 'int', P, P, P, PP]],
     ire_restore_fuse_fit_device: ['int', [P, P, 'int', 'int', 'int', 'int', P, P, P, P]],

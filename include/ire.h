@@ -108,6 +108,12 @@ typedef struct ire_config {
  * ire_jpeg_optimized_base64_bound(h, w, quality, sampling) bytes, which is larger than ire_jpeg_base64_bound_ex's.  (Bit values 2,
  * 16 and 64 stay unknown.) */
 #define IRE_FLAG_JPEG_OPTIMIZE 128u
+/* Not a result format, and free to combine with every other flag: UPLOAD jobs (ire_submit_upload) convert the pixels of a file that
+ * carries an ICC profile (Display P3, Adobe RGB, ...) to sRGB on the device, between the decode and the preprocess step -- the third
+ * operation of the reference's preprocess, .withMetadata({ icc: 'sRGB' }) (imagePreprocess.js:57-66).  See ire_icc_plan_file below for
+ * what is converted and what is refused.  Without the flag every upload is treated as sRGB, tagged or not, as before.  File jobs
+ * (ire_submit_jpeg) and every other entry are not changed by it. */
+#define IRE_FLAG_UPLOAD_ICC 256u
 
 
 
@@ -326,6 +332,7 @@ int ire_decode_jpeg_plan(const uint8_t* file, size_t bytes, int* out_h, int* out
  * its stream). */
 #define IRE_DECODE_ACCEPT_PROGRESSIVE 1u
 #define IRE_DECODE_MAX_SCANS 64
+#define IRE_DECODE_ACCEPT_ICC 4u          /* ire_upload_plan only: see there.  (Bit value 2 stays unknown.) */
 int ire_decode_jpeg_plan_ex(const uint8_t* file, size_t bytes, uint32_t accept, int* out_h, int* out_w, int* out_sampling, int* out_nscans);
 int ire_decode_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, uint8_t* out_rgb /* h*w*3 */, int h, int w);
 int ire_decode_jpeg_device(ire_engine* e, const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb,
@@ -350,17 +357,23 @@ int ire_submit_fit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg,
  * (h, w), whatever their sampling, and never share a batch with pixel jobs.  A file the plan refuses, or whose entropy-coded data
  * may take more room than its h * w * 3 pixels, is IRE_ERR_INVALID_INPUT with the reason in ire_last_error ("invalid: ...") and
  * creates no job: such a file stays with the host codec.  A file whose DATA the device finds corrupt fails only its own job, at
- * its poll: IRE_ERR_INVALID_INPUT "invalid: corrupt JPEG data (decoder status N)"; the other jobs of its batch complete. */
+ * its poll: IRE_ERR_INVALID_INPUT "invalid: corrupt JPEG data (decoder status N)"; the other jobs of its batch complete.  A file job
+ * has no preprocess semantics: IRE_FLAG_UPLOAD_ICC does not change it, its pixels are taken as they are decoded. */
 int ire_submit_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, const double* scores, ire_job** job_out);
 /* An UPLOAD job: ire_submit_jpeg with the preprocess step of imagePreprocess.js:40-55 between the decode and the network, all on the
  * device -- no pixel of the upload is ever on the host.  The file is one ire_submit_jpeg takes.  Its orientation is read from the
  * first APP1 segment that is an Exif block (IFD0 tag 0x0112, SHORT, count 1, value 1..8; anything else, a broken block included, is
  * orientation 1 and never a refusal).  The job's result is exactly that of
  *   ire_submit_fit(ire_preprocess(ire_decode_jpeg(file), that orientation, max_dim), is_jpeg = 1, scores)
- * (scores == NULL: the classifier runs on the preprocessed, unpadded pixels); its size is the fitted out_h x out_w.  The reference's
+ * (scores == NULL: the classifier runs on the preprocessed, unpadded pixels); its size is the fitted out_h x out_w.  On an engine created
+ * with IRE_FLAG_UPLOAD_ICC the file's ICC profile is honoured, as sharp honours it before it resizes: the result is exactly that of
+ *   ire_submit_fit(ire_preprocess(ire_icc_to_srgb(ire_decode_jpeg(file), ire_icc_plan_file(file)), that orientation, max_dim), is_jpeg = 1, scores)
+ * and a file whose profile ire_icc_plan_file refuses is refused at submit with that reason and creates no job.  The profile is no part
+ * of the batch key: uploads with different profiles, or none, share a batch.  Without the flag nothing changes, for tagged files too.  The reference's
  * q85 re-encode between preprocess and restore (imagePreprocess.js:57-64) is NOT reproduced: it exists to hand an external API a file.
  * ire_upload_plan: pure host, no engine -- what ire_submit_upload will do with this file on an engine whose decoder accepts
- * `accept` (0, or IRE_DECODE_ACCEPT_PROGRESSIVE): the stored size, the orientation, the fitted size (any output pointer may be NULL;
+ * `accept` (0, or IRE_DECODE_ACCEPT_PROGRESSIVE, IRE_DECODE_ACCEPT_ICC for an engine with IRE_FLAG_UPLOAD_ICC -- the plan then also refuses
+ * what ire_icc_plan_file refuses, with the same reason; without the bit the profile is not looked at): the stored size, the orientation, the fitted size (any output pointer may be NULL;
  * the caller sizes its poll buffer from out_h, out_w).  It refuses what ire_decode_jpeg_plan_ex refuses, with the same reason,
  * a max_dim below 1, and a file that breaks the room rule below.
  * Upload jobs are coalesced by (stored h, stored w, orientation, max_dim) and never share a batch with another kind of job.  Known
@@ -371,6 +384,48 @@ int ire_submit_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, const doub
 int ire_upload_plan(const uint8_t* file, size_t bytes, uint32_t accept, int max_dim, int* stored_h, int* stored_w,
                     int* orientation, int* out_h, int* out_w);
 int ire_submit_upload(ire_engine* e, const uint8_t* file, size_t bytes, int max_dim, const double* scores, ire_job** job_out);
+
+/* ---- ICC profiles of uploads: convert to sRGB on the device (icc_parse.hpp, icc.hip) ------------------------------------------------
+ * The transform is all-integer and is stated once.  Tables, built on the host in double precision:
+ *   lin[c][v] = rint(65535 * TRC_c(v / 255))              u16, clamped (grey: row 0 only)
+ *   m         = rint(16384 * inv(M_sRGB) * M_profile)     Q14; M_profile's columns are the profile's rXYZ gXYZ bXYZ, M_sRGB's the D50
+ *               sRGB colorants (0.43607, 0.22249, 0.01392), (0.38515, 0.71687, 0.09708), (0.14307, 0.06061, 0.71410) as s15Fixed16
+ * Per pixel:
+ *   y_c   = clamp((sum_k m[3 c + k] * lin[k][v_k] + 8192) >> 14, 0, 65535)     (arithmetic shift, 64-bit sum)
+ *   out_c = enc8(y_c),  enc8(x) = rint(255 * sRGB_OETF(x / 65535)), exact for all 65536 x
+ *   IRE_ICC_GREY: out = enc8(lin[0][v]) on all three bytes (v: the pixel's first byte; a decoded grey file has three equal ones)
+ * Within one level of littlecms (what sharp runs) on every sample: profiles/upload_icc.md.
+ * kind: IRE_ICC_NONE -- nothing to apply: no profile, structurally broken bytes (a size field beyond the bytes, no 'acsp', a tag
+ * outside the profile, a missing or truncated rXYZ gXYZ bXYZ rTRC gTRC bTRC / kTRC), or a profile whose colour space is not the
+ * image's (RGB for 3 components, GRAY for 1); IRE_ICC_IDENTITY -- the transform above changes no byte (rounded matrix = 16384 I and
+ * enc8(lin[c][v]) == v for all v: the common sRGB profiles); IRE_ICC_MATRIX / IRE_ICC_GREY -- a transform to apply.  Accepted: v2 and
+ * v4 headers, data colour space RGB or GRAY, PCS XYZ, curves `curv` of count 0 (identity), 1 (a u8Fixed8 gamma), 2..4096 (a u16 table,
+ * linearly interpolated) and `para` function types 0..4; `chad` is ignored (the colorants are D50 already).  REFUSED, as
+ * IRE_ERR_INVALID_INPUT with the reason in ire_last_error ("invalid: ICC profile ..."): a well-formed profile with an A2B0 / A2B1 /
+ * A2B2 tag (littlecms would use the lookup table, not the matrix), any other data colour space (CMYK ...), any other PCS (Lab), a
+ * curve of another type or a longer table, a matrix coefficient outside (-4, 4).  Such an upload stays with the host codec.
+ * Rendering intents and black-point compensation do not exist here: a matrix profile has one colorimetric transform. */
+enum { IRE_ICC_NONE = 0, IRE_ICC_IDENTITY = 1, IRE_ICC_MATRIX = 2, IRE_ICC_GREY = 3 };
+typedef struct ire_icc_transform {
+    int32_t kind;             /* IRE_ICC_* */
+    int32_t m[9];             /* row-major Q14; zeros unless IRE_ICC_MATRIX or an RGB profile's IRE_ICC_IDENTITY */
+    uint16_t lin[3][256];
+} ire_icc_transform;
+/* Pure host, no engine.  ire_icc_plan_profile: the raw bytes of a profile (for callers who decode a PNG's iCCP on the host) that came
+ * with an image of `components` (1 or 3) components.  ire_icc_plan_file: the profile of a JPEG file -- the APP2 segments in front of
+ * its first scan whose payload starts "ICC_PROFILE\0", a 1-based sequence number and a count, in any order; every chunk must state the
+ * same count, every number 1..count must occur exactly once and the assembled profile is at most 1 MiB, else the file has NO profile
+ * (IRE_ICC_NONE; never a refusal, like a broken EXIF block) -- and the component count of its frame header. */
+int ire_icc_plan_profile(const uint8_t* profile, size_t bytes, int components, ire_icc_transform* out);
+int ire_icc_plan_file(const uint8_t* file, size_t bytes, ire_icc_transform* out);
+/* The conversion by itself, for pixel callers (PNG / WebP uploads decoded on the host) and for the tests: n <= max_batch tightly
+ * packed h x w RGB images (1..8192 per side), converted IN PLACE, image i by t[i] (NULL, IRE_ICC_NONE and IRE_ICC_IDENTITY: left as
+ * it is).  One launch whatever n; none when no image needs a transform.  Only pixels are written: with image_pitch_bytes > h*w*3 the
+ * bytes between images stay untouched.  ire_icc_to_srgb_device: asynchronous on `stream`, the tables are copied before return.
+ * ire_icc_to_srgb: synchronous, host pointers, images h*w*3 apart. */
+int ire_icc_to_srgb_device(ire_engine* e, uint8_t* d_rgb, int n, int h, int w, size_t image_pitch_bytes,
+                           const ire_icc_transform* const* t /* n entries, NULL = leave */, void* stream);
+int ire_icc_to_srgb(ire_engine* e, uint8_t* rgb, int n, int h, int w, const ire_icc_transform* const* t);
 /* A FUSION job: k = 2 or 3 views of one scene, all h x w with h, w in 1..8192 (views[v]: h*w*3 bytes, copied before return),
  * submitted once, computed on the device with its batch, polled and released like every other job; its result is the fused h x w
  * image -- pixels, or on a text engine the engine's result text.  Every view is restored as ire_submit_fit restores it (scores of

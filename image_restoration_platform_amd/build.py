@@ -48,6 +48,7 @@ SOURCES = [
     ("deflate.hip", []),
     ("jpeg.hip", []),
     ("jpeg_dec.hip", []),
+    ("png_dec.hip", []),
     ("icc.hip", []),
     ("codec.cpp", ["--offload-host-only"]),      # no device code: its constant tables hold host function pointers
     ("engine.cpp", []),

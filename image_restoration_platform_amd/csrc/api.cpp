@@ -65,11 +65,19 @@ struct HipSlot : SlotMem<DeviceMem, PinnedMem> {
 };
 
 // what a file job keeps of its file between submit and its batch's decode: the head as parsed, the scan's streams as cut
-struct JpegFileHead {
+struct FileHead { bool png = false; };
+struct JpegFileHead : FileHead {
     jpegparse::File hd;
     std::vector<jpegdec::DecStream> streams;
     std::unique_ptr<icc::Transform> icc;      // an upload on an engine with IRE_FLAG_UPLOAD_ICC whose profile needs a transform; else null
 };
+
+// a PNG job's: the plan; the staged input is the IDAT payloads back to back, one zlib stream
+struct PngFileHead : FileHead {
+    pngparse::File f;
+    PngFileHead() { png = true; }
+};
+static const FileHead& head_of(const void* head) { return *static_cast<const FileHead*>(head); }
 
 // CPU set of this engine's service threads (affinity.hpp): IRE_CPU_AFFINITY = "off" | a cpulist overrides the sysfs plan
 static CpuPlan plan_for_device(int device) {
@@ -159,18 +167,32 @@ struct HipBatchBackend {
     }
     // ---- file jobs (batcher.hpp: the decoded kinds' hooks).  The parse and the cut run in the submitting thread; the launcher only packs
     // the records of the jobs staged so far and enqueues the decode on the copy-in stream, under the previous batch's compute. ----
-    std::shared_ptr<void> file_plan(const uint8_t* file, size_t bytes, int* h, int* w, size_t* room) {
-        auto head = std::make_shared<JpegFileHead>();
+    // (every head leaves as a shared_ptr<FileHead>, so the void* the batcher hands back points at the FileHead)
+    std::shared_ptr<void> file_plan(const uint8_t* file, size_t bytes, int* h, int* w, size_t* room) { return plan_head(file, bytes, 0, h, w, room); }
+    std::shared_ptr<FileHead> plan_head(const uint8_t* file, size_t bytes, uint32_t png_flags, int* h, int* w, size_t* room) {
         std::string why;
+        if (E.png_decoder().enabled() && pngparse::is_png(file, bytes)) {      // (an engine without the flag goes on and refuses it as a JPEG parser does)
+            auto head = std::make_shared<PngFileHead>();
+            if (!pngparse::plan_file(file, bytes, png_flags, head->f, why)) fail(IRE_ERR_INVALID_INPUT, why);
+            *h = head->f.h; *w = head->f.w;
+            *room = head->f.idat_bytes;
+            return head;
+        }
+        auto head = std::make_shared<JpegFileHead>();
         if (!jpegparse::plan_file(file, bytes, E.jpeg_decoder().accept(), head->hd, why)) fail(IRE_ERR_INVALID_INPUT, why);
         *h = head->hd.hd.im.h; *w = head->hd.hd.im.w;
         *room = jpegparse::file_room(head->hd, bytes);
         return head;
     }
     size_t file_stage(void* head, const uint8_t* file, size_t bytes, uint8_t* dst, size_t room) {
-        JpegFileHead& f = *static_cast<JpegFileHead*>(head);
-        f.streams.assign(f.hd.nstreams, jpegdec::DecStream{});
         std::string why;
+        if (head_of(head).png) {
+            const size_t used = pngparse::stage(static_cast<PngFileHead*>(static_cast<FileHead*>(head))->f, file, bytes, dst, room, why);
+            if (!used) fail(IRE_ERR_INVALID_INPUT, why);
+            return used;
+        }
+        JpegFileHead& f = *static_cast<JpegFileHead*>(static_cast<FileHead*>(head));
+        f.streams.assign(f.hd.nstreams, jpegdec::DecStream{});
         if (!jpegparse::split_file(f.hd, file, bytes, dst, room, f.streams.data(), why)) fail(IRE_ERR_INVALID_INPUT, why);
         const jpegdec::DecStream& last = f.streams.back();
         return std::max<size_t>((size_t)last.off + last.len, 1);      // (0 would say that nothing was staged: a last scan of no bytes)
@@ -193,7 +215,7 @@ struct HipBatchBackend {
         // key); a push in which no job has any enqueues nothing.
         if (E.upload_icc()) {
             const icc::Transform* t[kMaxBatch];
-            for (int i = 0; i < count; ++i) t[i] = used[i] ? static_cast<const JpegFileHead*>(heads[i])->icc.get() : nullptr;
+            for (int i = 0; i < count; ++i) t[i] = used[i] && !head_of(heads[i]).png ? static_cast<const JpegFileHead*>(&head_of(heads[i]))->icc.get() : nullptr;
             E.icc_converter().to_srgb_device(true, P.d_stored.get<uint8_t>() + sb * (size_t)first, count, sh, sw, sb, t, cs);
         }
         // (a job with nothing decoded is fitted from whatever the scratch held: it fails alone, its place is never read)
@@ -211,23 +233,41 @@ struct HipBatchBackend {
         const uint8_t* bytes[kMaxBatch];
         size_t room[kMaxBatch];
         hs.file_jobs = first + count;
-        // a job whose staging failed (batcher.hpp) has nothing to decode: its place keeps whatever the slot held, its job fails alone;
-        // the runs of jobs between such ones are decoded one call each
-        for (int i = 0; i < count;) {
-            if (!used[i]) { ++i; continue; }
-            int n = 0;
-            const int i0 = i;
-            for (; i < count && used[i]; ++i, ++n) {
-                const JpegFileHead& f = *static_cast<const JpegFileHead*>(heads[i]);
-                hd[n] = &f.hd; streams[n] = f.streams.data(); bytes[n] = b.pin_in + place * (size_t)(first + i); room[n] = used[i];
-            }
-            E.jpeg_decoder().decode_streams(hd, streams, bytes, room, n, h, w, d_rgb + pitch * (size_t)(first + i0), pitch, hs.d_fstat.get<int32_t>() + first + i0, cs);
+        // the PNG jobs of the push, wherever they stand among the others: ONE call, every file to its own image and status word
+        {
+            const pngparse::File* pf[kMaxBatch];
+            int dst[kMaxBatch], n = 0;
+            for (int i = 0; i < count; ++i)
+                if (used[i] && head_of(heads[i]).png) {
+                    pf[n] = &static_cast<const PngFileHead*>(&head_of(heads[i]))->f; bytes[n] = b.pin_in + place * (size_t)(first + i); room[n] = used[i]; dst[n] = first + i;
+                    ++n;
+                }
+            if (n) E.png_decoder().decode_staged(pf, bytes, room, dst, n, h, w, d_rgb, pitch, hs.d_fstat.get<int32_t>(), cs);
+        }
+        // and the JPEG jobs likewise: one call per kind, whatever the number of jobs and however the kinds interleave.  A job whose staging
+        // failed (batcher.hpp) has nothing to decode: its place keeps whatever the slot held, its job fails alone.
+        {
+            int dst[kMaxBatch], n = 0;
+            for (int i = 0; i < count; ++i)
+                if (used[i] && !head_of(heads[i]).png) {
+                    const JpegFileHead& f = *static_cast<const JpegFileHead*>(&head_of(heads[i]));
+                    hd[n] = &f.hd; streams[n] = f.streams.data(); bytes[n] = b.pin_in + place * (size_t)(first + i); room[n] = used[i]; dst[n] = first + i;
+                    ++n;
+                }
+            if (n) E.jpeg_decoder().decode_streams(hd, streams, bytes, room, n, h, w, d_rgb, pitch, hs.d_fstat.get<int32_t>(), cs, dst);
         }
     }
     // file_plan for an upload job: the FITTED size, and the key that says how decode gets there
     std::shared_ptr<void> upload_plan(const uint8_t* file, size_t bytes, int max_dim, int* h, int* w, size_t* room, int key[4]) {
         int sh = 0, sw = 0;
-        auto head = file_plan(file, bytes, &sh, &sw, room);
+        // (a PNG's iCCP on an engine that honours profiles: refused, reading the chunk is a later change)
+        auto head = plan_head(file, bytes, E.upload_icc() ? pngparse::kRefuseIccp : 0u, &sh, &sw, room);
+        if (head->png) {
+            key[0] = sh; key[1] = sw; key[2] = static_cast<PngFileHead*>(head.get())->f.orientation; key[3] = max_dim;
+            preprocess_plan(sw, sh, key[2], max_dim, w, h, nullptr);
+            if (!piece_addressable(Engine::fit_dim(*h), Engine::fit_dim(*w), 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(Engine::fit_dim(*h), Engine::fit_dim(*w)));
+            return head;
+        }
         if (E.upload_icc()) {
             icc::Transform t;
             std::string why;
@@ -511,9 +551,23 @@ int ire_preprocess_batch_device(ire_engine* e, const uint8_t* d_rgb, int n, int 
 int ire_upload_plan(const uint8_t* file, size_t bytes, uint32_t accept, int max_dim, int* stored_h, int* stored_w, int* orientation, int* out_h, int* out_w) {
     return guarded([&] {
         if (!file) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_upload_plan: null file");
-        if (accept & ~(uint32_t)(IRE_DECODE_ACCEPT_PROGRESSIVE | IRE_DECODE_ACCEPT_ICC)) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_upload_plan: unknown accept bits");
+        if (accept & ~(uint32_t)(IRE_DECODE_ACCEPT_PROGRESSIVE | IRE_DECODE_ACCEPT_ICC | IRE_DECODE_ACCEPT_PNG)) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_upload_plan: unknown accept bits");
         jpegparse::File f;
         std::string why;
+        if ((accept & IRE_DECODE_ACCEPT_PNG) && pngparse::is_png(file, bytes)) {
+            pngparse::File p;
+            if (!pngparse::plan_file(file, bytes, (accept & IRE_DECODE_ACCEPT_ICC) ? pngparse::kRefuseIccp : 0u, p, why)) fail(IRE_ERR_INVALID_INPUT, why);
+            int ow = 0, oh = 0;
+            preprocess_plan(p.w, p.h, p.orientation, max_dim, &ow, &oh, nullptr);
+            if (!piece_addressable(Engine::fit_dim(oh), Engine::fit_dim(ow), 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(Engine::fit_dim(oh), Engine::fit_dim(ow)));
+            if (p.idat_bytes > (size_t)oh * ow * 3) fail(IRE_ERR_INVALID_INPUT, kUploadRoomReason);
+            if (stored_h) *stored_h = p.h;
+            if (stored_w) *stored_w = p.w;
+            if (orientation) *orientation = p.orientation;
+            if (out_h) *out_h = oh;
+            if (out_w) *out_w = ow;
+            return;
+        }
         if (!jpegparse::plan_file(file, bytes, accept & IRE_DECODE_ACCEPT_PROGRESSIVE, f, why)) fail(IRE_ERR_INVALID_INPUT, why);
         if (accept & IRE_DECODE_ACCEPT_ICC) {
             icc::Transform t;
@@ -724,6 +778,35 @@ int ire_decode_jpeg_device(ire_engine* e, const uint8_t* const* files, const siz
     });
 }
 
+static_assert(IRE_DECODE_ACCEPT_ICC == pngparse::kRefuseIccp, "ire.h and png_parse.hpp");
+
+int ire_decode_png_plan(const uint8_t* file, size_t bytes, int* out_h, int* out_w, int* out_colour_type) {
+    return guarded([&] {
+        if (!file) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_decode_png_plan: null file");
+        pngparse::File f;
+        std::string why;
+        if (!pngparse::plan_file(file, bytes, 0, f, why)) fail(IRE_ERR_INVALID_INPUT, why);
+        if (out_h) *out_h = f.h;
+        if (out_w) *out_w = f.w;
+        if (out_colour_type) *out_colour_type = f.ctype;
+    });
+}
+
+int ire_decode_png(ire_engine* e, const uint8_t* file, size_t bytes, uint8_t* out_rgb, int h, int w) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, E.main_stream(), [&] { E.png_decoder().decode_host(file, bytes, out_rgb, h, w); });
+    });
+}
+
+int ire_decode_png_device(ire_engine* e, const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb, size_t image_pitch_bytes,
+                          int32_t* d_status, void* stream) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, (hipStream_t)stream, [&] { E.png_decoder().decode_files(files, bytes, n, h, w, d_rgb, image_pitch_bytes, d_status, (hipStream_t)stream); });
+    });
+}
+
 int ire_restore_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, const double* scores, const uint8_t* is_jpeg, uint8_t* out_rgb,
                     ire_timings* t) {
     return guarded([&] {
@@ -861,15 +944,20 @@ int ire_submit_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, const doub
     return guarded([&] {
         eng(e);
         if (!file || !job_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_jpeg");
-        job_handle(job_out, [&] { return e->batcher->submit_file(file, bytes, scores); });
+        // (is_jpeg = 0 for a PNG on an engine that decodes it: what ire_submit_fit of its pixels would be told)
+        const bool png = eng(e).png_decoder().enabled() && pngparse::is_png(file, bytes);
+        job_handle(job_out, [&] { return e->batcher->submit_file(file, bytes, scores, !png); });
     });
 }
+
+int ire_submit_file(ire_engine* e, const uint8_t* file, size_t bytes, const double* scores, ire_job** job_out) { return ire_submit_jpeg(e, file, bytes, scores, job_out); }
 
 int ire_submit_upload(ire_engine* e, const uint8_t* file, size_t bytes, int max_dim, const double* scores, ire_job** job_out) {
     return guarded([&] {
         eng(e);
         if (!file || !job_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_submit_upload");
-        job_handle(job_out, [&] { return e->batcher->submit_upload(file, bytes, max_dim, scores); });
+        const bool png = eng(e).png_decoder().enabled() && pngparse::is_png(file, bytes);
+        job_handle(job_out, [&] { return e->batcher->submit_upload(file, bytes, max_dim, scores, !png); });
     });
 }
 

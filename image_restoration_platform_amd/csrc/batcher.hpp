@@ -204,16 +204,17 @@ class Batcher {
         return j;
     }
 
-    // Queue one encoded file.  The head is parsed and the scan is cut HERE, in the submitting thread, straight into the job's place in
+    // Queue one encoded file (is_jpeg: what the ABI entry found it to be; the backend's hooks dispatch on the head they made).
+    // The head is parsed and the scan is cut HERE, in the submitting thread, straight into the job's place in
     // the slot's pinned input; the launcher only hands the staged jobs to the backend's decode.  Throws Error when the backend refuses
     // the file: no job exists then.
-    std::shared_ptr<Job> submit_file(const uint8_t* file, size_t bytes, const double* scores) {
+    std::shared_ptr<Job> submit_file(const uint8_t* file, size_t bytes, const double* scores, bool is_jpeg = true) {
         auto j = std::make_shared<Job>();
         size_t room = 0;
         j->key.kind = JobKind::File;
         j->file = be_.file_plan(file, bytes, &j->key.h, &j->key.w, &room);
         if (room > j->key.in_bytes()) fail(IRE_ERR_INVALID_INPUT, "invalid: the file's entropy-coded data may be larger than its pixels (it stays with the host codec)");
-        set_image(*j, 0, true, scores);
+        set_image(*j, 0, is_jpeg, scores);
         stage(j, room, [&](uint8_t* dst) { return be_.file_stage(j->file.get(), file, bytes, dst, room); });
         return j;
     }
@@ -221,13 +222,13 @@ class Batcher {
     // Queue one encoded upload: a file job that the backend orients by the file's EXIF tag and fits inside max_dim on the device, after
     // the decode and before the network.  The job's h, w are the fitted size; its place in the slot's input holds that many pixels, and a
     // file whose cut scan may need more is refused: no job exists then.
-    std::shared_ptr<Job> submit_upload(const uint8_t* file, size_t bytes, int max_dim, const double* scores) {
+    std::shared_ptr<Job> submit_upload(const uint8_t* file, size_t bytes, int max_dim, const double* scores, bool is_jpeg = true) {
         auto j = std::make_shared<Job>();
         size_t room = 0;
         j->key.kind = JobKind::Upload;
         j->file = be_.upload_plan(file, bytes, max_dim, &j->key.h, &j->key.w, &room, j->key.up);
         if (room > j->key.in_bytes()) fail(IRE_ERR_INVALID_INPUT, kUploadRoomReason);
-        set_image(*j, 0, true, scores);
+        set_image(*j, 0, is_jpeg, scores);
         stage(j, room, [&](uint8_t* dst) { return be_.file_stage(j->file.get(), file, bytes, dst, room); });
         return j;
     }
@@ -485,7 +486,11 @@ class Batcher {
         if (j.stage_status != IRE_OK) { j.status = j.stage_status; return true; }       // (j.err holds the reason since submit)
         if (!S.key.decoded()) return false;
         const int st = be_.file_status(S.b, i);
-        if (st != 0) { j.status = IRE_ERR_INVALID_INPUT; j.err = "invalid: corrupt JPEG data (decoder status " + std::to_string(st) + ")"; return true; }
+        if (st != 0) {        // (is_jpeg = false on a decoded kind: the ABI entry found a PNG)
+            j.status = IRE_ERR_INVALID_INPUT;
+            j.err = std::string("invalid: corrupt ") + (j.v_jpeg[0] ? "JPEG" : "PNG") + " data (decoder status " + std::to_string(st) + ")";
+            return true;
+        }
         return false;
     }
 

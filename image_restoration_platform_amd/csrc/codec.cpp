@@ -34,7 +34,7 @@ const TextFormat kJpeg = {"JPEG", [](int h, int w, TextSettings o) { return jpeg
 
 void check_config_flags(uint32_t flags) {
     constexpr uint32_t kResultBits = IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG;
-    if (flags & ~(kResultBits | IRE_FLAG_DECODE_PROGRESSIVE | IRE_FLAG_JPEG_OPTIMIZE | IRE_FLAG_UPLOAD_ICC)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
+    if (flags & ~(kResultBits | IRE_FLAG_DECODE_PROGRESSIVE | IRE_FLAG_JPEG_OPTIMIZE | IRE_FLAG_UPLOAD_ICC | IRE_FLAG_DECODE_PNG)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
     if (((flags & kResultBits) & ((flags & kResultBits) - 1)) != 0) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");
 }
 
@@ -180,7 +180,7 @@ int JpegDecoder::Scratch::next_pin(size_t bytes) {
 }
 
 void JpegDecoder::run(Scratch& S, int turn, const JpegDecLayout& L, size_t pin_bytes, const uint8_t* const* tails, const size_t* tail_bytes, const size_t* tail_off, int n, int h,
-                      int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s) {
+                      int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s, const int* dst) {
     const bool own = &S == &own_, timed = own && times_;
     const size_t coef = jpeg_dec_coef_bytes(n, h, w), planes = jpeg_dec_plane_bytes(n, h, w);
     const size_t lanes = jpeg_dec_lane_bytes(L.nwin), walk = L.walk_blocks ? jpeg_dec_walk_bytes(L.walk_blocks) : 0;
@@ -204,7 +204,7 @@ void JpegDecoder::run(Scratch& S, int turn, const JpegDecLayout& L, size_t pin_b
         for (hipEvent_t& ev : marks_) if (!ev) IRE_HIP(hipEventCreate(&ev));
     }
     jpeg_dec_launch(d_in, L, n, h, w, S.d_coef.get<uint8_t>(), S.d_planes.get<uint8_t>(), lanes ? S.d_lanes.get<uint8_t>() : nullptr, walk ? S.d_walk.get<uint8_t>() : nullptr,
-                    d_rgb, image_pitch, d_status, s, timed ? marks_ : nullptr);
+                    d_rgb, image_pitch, d_status, s, timed ? marks_ : nullptr, dst);
     if (own) marks_pending_ = times_;
 }
 
@@ -228,7 +228,7 @@ void JpegDecoder::decode_files(const uint8_t* const* files, const size_t* bytes,
 }
 
 void JpegDecoder::decode_streams(const jpegparse::File* const* hd, const jpegdec::DecStream* const* streams, const uint8_t* const* bytes, const size_t* used, int n, int h,
-                                 int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s) {
+                                 int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s, const int* dst) {
     if (!hd || !streams || !bytes || !used || !d_rgb || !d_status || n < 1 || n > max_batch_) fail(IRE_ERR_INTERNAL, "internal: arguments of the batcher's JPEG decode");
     std::vector<uint32_t> ns((size_t)n), nu((size_t)n);
     for (int i = 0; i < n; ++i) {
@@ -242,7 +242,7 @@ void JpegDecoder::decode_streams(const jpegparse::File* const* hd, const jpegdec
     std::vector<size_t> off((size_t)n);
     jpeg_dec_pack_streams(hd, streams, used, n, L0, batch_.pin[turn].get<uint8_t>(), L, off.data(), min_windows_);
     // the streams go from where their submitters cut them (the slot's pinned input) straight to the blob on the device
-    run(batch_, turn, L, L.bytes, bytes, used, off.data(), n, h, w, d_rgb, image_pitch, d_status, s);
+    run(batch_, turn, L, L.bytes, bytes, used, off.data(), n, h, w, d_rgb, image_pitch, d_status, s, dst);
 }
 
 void JpegDecoder::times_collect() {
@@ -278,6 +278,131 @@ void JpegDecoder::decode_host(const uint8_t* file, size_t bytes, uint8_t* out_rg
     IRE_HIP(hipStreamSynchronize(s));
     // (bits: jpeg_dec_core.hpp kSt*; 16 = values no picture gives, where libjpeg-turbo's C and SIMD code differ)
     if (st != 0) fail(IRE_ERR_INVALID_INPUT, "invalid: corrupt JPEG data (decoder status " + std::to_string(st) + ")");
+}
+
+// ---- the PNG decoder (png_parse.hpp on the host, png_dec.hip on the device) ---------------------------------------------------------------
+
+void PngDecoder::setup(int max_batch, bool enabled, hipStream_t main_stream) {
+    max_batch_ = max_batch; enabled_ = enabled; main_stream_ = main_stream;
+    if (const char* v = std::getenv("IRE_PNG_DEC_TIMES")) times_ = std::atoi(v) != 0;
+}
+
+PngDecoder::~PngDecoder() {
+    if (times_) {
+        times_collect();
+        std::fprintf(stderr, "{\"png_dec_kernel_ms\": {\"inflate\": %.4f, \"unfilter\": %.4f, \"calls\": %lld, \"walk_share\": %.4f, \"place_share\": %.4f}}\n", ms_[0], ms_[1],
+                     (long long)calls_, ticks_[2] > 0 ? ticks_[0] / ticks_[2] : 0.0, ticks_[2] > 0 ? ticks_[1] / ticks_[2] : 0.0);
+    }
+    for (hipEvent_t ev : marks_) if (ev) (void)hipEventDestroy(ev);
+}
+
+void PngDecoder::check_enabled() const {
+    if (!enabled_) fail(IRE_ERR_INVALID_INPUT, "invalid: this engine does not decode PNG files (create it with IRE_FLAG_DECODE_PNG)");
+}
+
+int PngDecoder::Scratch::next_pin(size_t bytes) {
+    const int t = turn;
+    turn ^= 1;
+    if (up_recorded[t]) IRE_HIP(hipEventSynchronize(up_ev[t]));
+    pin[t].grow(bytes, bytes + bytes / 2);
+    return t;
+}
+
+void PngDecoder::times_collect() {
+    if (!marks_pending_) return;
+    marks_pending_ = false;
+    if (hipEventSynchronize(marks_[2]) != hipSuccess) return;
+    for (int k = 0; k < 2; ++k) { float ms = 0.f; if (hipEventElapsedTime(&ms, marks_[k], marks_[k + 1]) == hipSuccess) ms_[k] += ms; }
+    ++calls_;
+    std::vector<unsigned long long> t(3 * (size_t)ticks_n_);
+    if (ticks_n_ && hipMemcpy(t.data(), d_ticks_.get<void>(), t.size() * 8, hipMemcpyDeviceToHost) == hipSuccess)
+        for (size_t i = 0; i < t.size(); ++i) ticks_[i % 3] += (double)t[i];
+}
+
+void PngDecoder::run(Scratch& S, int turn, const PngDecLayout& L, size_t pin_bytes, const uint8_t* const* tails, const size_t* tail_bytes, const pngdec::Record* rec, int n, int h,
+                     int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s) {
+    const bool own = &S == &own_, timed = own && times_;
+    // the scanlines of a whole batch of four-byte pixels: the first batch of a shape allocates, later ones of any colour types do not
+    const size_t scan_full = (((size_t)h * (1 + (size_t)w * 4) + 15) & ~(size_t)15) * (size_t)max_batch_;
+    if (L.total > S.d_in.bytes() || L.scan_bytes > S.d_scan.bytes()) IRE_HIP(own ? hipDeviceSynchronize() : hipStreamSynchronize(s));
+    S.d_in.grow(L.total, L.total + L.total / 2);
+    S.d_scan.grow(L.scan_bytes, batch_room(L.scan_bytes, scan_full));
+    uint8_t* d_in = S.d_in.get<uint8_t>();
+    IRE_HIP(hipMemcpyAsync(d_in, S.pin[turn].get<uint8_t>(), pin_bytes, hipMemcpyHostToDevice, s));
+    if (!S.up_ev[turn]) IRE_HIP(hipEventCreateWithFlags(&S.up_ev[turn], hipEventDisableTiming));
+    IRE_HIP(hipEventRecord(S.up_ev[turn], s));
+    S.up_recorded[turn] = true;
+    for (int i = 0; tails && i < n; ++i)
+        if (tail_bytes[i]) IRE_HIP(hipMemcpyAsync(d_in + L.bytes + rec[i].in_off, tails[i], tail_bytes[i], hipMemcpyHostToDevice, s));
+    if (timed) {
+        times_collect();
+        for (hipEvent_t& ev : marks_) if (!ev) IRE_HIP(hipEventCreate(&ev));
+        d_ticks_.grow(sizeof(unsigned long long) * 3 * (size_t)max_batch_);
+        ticks_n_ = n;
+    }
+    png_dec_launch(d_in, L, n, h, w, S.d_scan.get<uint8_t>(), d_rgb, image_pitch, d_status, s, timed ? marks_ : nullptr, timed ? d_ticks_.get<unsigned long long>() : nullptr);
+    if (own) marks_pending_ = timed;
+}
+
+void PngDecoder::decode_files(const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s) {
+    check_enabled();
+    if (!files || !bytes || !d_rgb || !d_status || n < 1 || n > max_batch_) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG decoder (1..max_batch files)");
+    if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the PNG decoder: height and width must be in 1..8192");
+    if (image_pitch < (size_t)3 * w * h) fail(IRE_ERR_INVALID_INPUT, "invalid pitch for the PNG decoder: images overlap");
+    std::vector<pngparse::File> hd((size_t)n);
+    std::vector<const pngparse::File*> hp((size_t)n);
+    std::vector<size_t> rooms((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        std::string why;
+        if (!files[i] || !pngparse::plan_file(files[i], bytes[i], 0, hd[(size_t)i], why)) fail(IRE_ERR_INVALID_INPUT, files[i] ? why : "invalid arguments to the PNG decoder: null file");
+        if (hd[(size_t)i].h != h || hd[(size_t)i].w != w) fail(IRE_ERR_INVALID_INPUT, "invalid: the PNG file's size is not the planned h x w");
+        hp[(size_t)i] = &hd[(size_t)i]; rooms[(size_t)i] = hd[(size_t)i].idat_bytes;
+    }
+    const PngDecLayout L = png_dec_layout(hp.data(), rooms.data(), nullptr, n, nullptr);
+    if (L.total >= ((size_t)1 << 32)) fail(IRE_ERR_INVALID_INPUT, "invalid: the batch's PNG files exceed 4 GB");
+    const int turn = own_.next_pin(L.total);
+    uint8_t* blob = own_.pin[turn].get<uint8_t>();
+    pngdec::Record* rec = reinterpret_cast<pngdec::Record*>(blob);
+    (void)png_dec_layout(hp.data(), rooms.data(), nullptr, n, rec);
+    for (int i = 0; i < n; ++i) {
+        std::string why;
+        if (pngparse::stage(hd[(size_t)i], files[i], bytes[i], blob + L.bytes + rec[i].in_off, rooms[(size_t)i], why) != rooms[(size_t)i]) fail(IRE_ERR_INVALID_INPUT, why);
+    }
+    run(own_, turn, L, L.total, nullptr, nullptr, rec, n, h, w, d_rgb, image_pitch, d_status, s);
+}
+
+void PngDecoder::decode_staged(const pngparse::File* const* f, const uint8_t* const* bytes, const size_t* used, const int* dst, int n, int h, int w, uint8_t* d_rgb,
+                               size_t image_pitch, int32_t* d_status, hipStream_t s) {
+    if (!enabled_ || !f || !bytes || !used || !dst || !d_rgb || !d_status || n < 1 || n > max_batch_) fail(IRE_ERR_INTERNAL, "internal: arguments of the batcher's PNG decode");
+    for (int i = 0; i < n; ++i)
+        if (f[i]->h != h || f[i]->w != w || used[i] != f[i]->idat_bytes) fail(IRE_ERR_INTERNAL, "internal: a PNG job in a slot of another size");
+    const PngDecLayout L = png_dec_layout(f, used, dst, n, nullptr);
+    if (L.total >= ((size_t)1 << 32)) fail(IRE_ERR_INVALID_INPUT, "invalid: the batch's PNG files exceed 4 GB");
+    const int turn = batch_.next_pin(L.bytes);
+    pngdec::Record* rec = reinterpret_cast<pngdec::Record*>(batch_.pin[turn].get<uint8_t>());
+    (void)png_dec_layout(f, used, dst, n, rec);
+    // the streams go from where their submitters staged them (the slot's pinned input) straight to the blob on the device
+    run(batch_, turn, L, L.bytes, bytes, used, rec, n, h, w, d_rgb, image_pitch, d_status, s);
+}
+
+void PngDecoder::decode_host(const uint8_t* file, size_t bytes, uint8_t* out_rgb, int h, int w) {
+    check_enabled();
+    if (!file || !out_rgb) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to the PNG decoder: null buffer");
+    if (h < 1 || w < 1 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the PNG decoder: height and width must be in 1..8192");
+    const size_t ib = (size_t)h * w * 3, ipad = (ib + 255) / 256 * 256;
+    if (ipad + 256 > d_out_.bytes()) IRE_HIP(hipDeviceSynchronize());
+    d_out_.grow(ipad + 256);
+    hipStream_t s = main_stream_;
+    uint8_t* d_px = d_out_.get<uint8_t>();
+    int32_t* d_st = reinterpret_cast<int32_t*>(d_px + ipad);
+    decode_files(&file, &bytes, 1, h, w, d_px, ib, d_st, s);
+    int32_t st = 0;
+    IRE_HIP(hipMemcpyAsync(out_rgb, d_px, ib, hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipMemcpyAsync(&st, d_st, sizeof(st), hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipStreamSynchronize(s));
+    // (png_inflate_core.hpp Status.  Flagged: whatever zlib would not decompress to exactly h * (1 + w * bpp) bytes with filter bytes 0..4.
+    // Pillow zero-fills a short stream and ignores a long one; the device flags both, and the host codec then decides.)
+    if (st != 0) fail(IRE_ERR_INVALID_INPUT, "invalid: corrupt PNG data (decoder status " + std::to_string(st) + ")");
 }
 
 }  // namespace ire

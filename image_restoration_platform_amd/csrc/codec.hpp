@@ -5,6 +5,7 @@
 #include "common.hpp"
 #include "device_buf.hpp"
 #include "jpeg_dec.hpp"
+#include "png_dec.hpp"
 
 namespace ire {
 
@@ -92,7 +93,8 @@ public:
     // the same for files whose heads were parsed and whose scans were cut by their submitters (streams[i]: hd[i]->nstreams records
     // with offsets inside bytes[i], pinned, used[i] bytes)
     void decode_streams(const jpegparse::File* const* hd, const jpegdec::DecStream* const* streams, const uint8_t* const* bytes, const size_t* used, int n, int h, int w,
-                        uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s);
+                        uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s, const int* dst = nullptr);
+    // dst: null, or which image of d_rgb and which status word file i becomes (a slot that holds other kinds of files between these)
     void decode_host(const uint8_t* file, size_t bytes, uint8_t* out_rgb, int h, int w);      // one file, synchronous on the main stream
     void report_times();      // IRE_JPEG_DEC_TIMES: the summed times as one JSON line on stderr (the engine closes; the device is idle)
 
@@ -116,7 +118,7 @@ private:
     // what both entries do once pin[turn] holds the packed batch: grow, upload its first pin_bytes (the batcher's stream bytes follow
     // from where their submitters cut them), record the turn, launch
     void run(Scratch& S, int turn, const JpegDecLayout& L, size_t pin_bytes, const uint8_t* const* tails, const size_t* tail_bytes, const size_t* tail_off, int n, int h, int w,
-             uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s);
+             uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s, const int* dst = nullptr);
     void times_collect();
 
     int max_batch_ = 8;
@@ -133,6 +135,53 @@ private:
     hipEvent_t marks_[kJpegDecMarks] = {};
     double ms_[kJpegDecMarks - 1] = {};
     int64_t calls_ = 0;
+};
+
+// The PNG decoder's buffers (png_parse.hpp on the host, png_dec.hip on the device), with the JPEG decoder's two users and its rule for
+// the host's one wait.  An engine without IRE_FLAG_DECODE_PNG has the object and refuses every call.
+class PngDecoder {
+public:
+    ~PngDecoder();        // IRE_PNG_DEC_TIMES=1: the two kernels' summed times as one JSON line on stderr (tools/png_decode_measure.py)
+    void setup(int max_batch, bool enabled, hipStream_t main_stream);
+    bool enabled() const { return enabled_; }
+    // n files of one planned size, of any colour types -> n images of h x w x 3 bytes on the device, image_pitch apart, one status word per
+    // image (0: ok, else pngdec::Status).  One upload and two launches per batch.
+    void decode_files(const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s);
+    // the same for files whose submitters planned them and staged their IDAT payloads (bytes[i]: pinned, used[i] bytes); file i becomes image
+    // dst[i] and sets status word dst[i]
+    void decode_staged(const pngparse::File* const* f, const uint8_t* const* bytes, const size_t* used, const int* dst, int n, int h, int w, uint8_t* d_rgb,
+                       size_t image_pitch, int32_t* d_status, hipStream_t s);
+    void decode_host(const uint8_t* file, size_t bytes, uint8_t* out_rgb, int h, int w);      // one file, synchronous on the main stream
+
+private:
+    struct Scratch {
+        Buf<PinnedMem> pin[2];            // two, used in turn (JpegDecoder::Scratch)
+        Buf<DeviceMem> d_in, d_scan;      // the batch's upload | the filtered scanlines, n * h * (1 + w * bpp) bytes
+        hipEvent_t up_ev[2] = {};
+        bool up_recorded[2] = {};
+        int turn = 0;
+        Scratch() = default;
+        Scratch(const Scratch&) = delete;
+        Scratch& operator=(const Scratch&) = delete;
+        ~Scratch() { for (hipEvent_t ev : up_ev) if (ev) (void)hipEventDestroy(ev); }
+        int next_pin(size_t bytes);
+    };
+    void run(Scratch& S, int turn, const PngDecLayout& L, size_t pin_bytes, const uint8_t* const* tails, const size_t* tail_bytes, const pngdec::Record* rec, int n, int h, int w,
+             uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s);
+    void times_collect();
+    void check_enabled() const;
+    int max_batch_ = 8;
+    bool enabled_ = false;
+    hipStream_t main_stream_ = nullptr;
+    Scratch own_, batch_;
+    Buf<DeviceMem> d_out_;                // decode_host: the pixels and the status word
+    bool times_ = false, marks_pending_ = false;
+    hipEvent_t marks_[3] = {};
+    double ms_[2] = {};
+    int64_t calls_ = 0;
+    Buf<DeviceMem> d_ticks_;              // with times_: lane 0's clock in the inflate kernel's walk | placement | whole, per image
+    double ticks_[3] = {};
+    int ticks_n_ = 0;
 };
 
 }  // namespace ire

@@ -227,6 +227,7 @@ public:
     // the codecs (codec.hpp): used inside the same enter / leave bracket as every other call
     TextEncoder& text_encoder() { return enc_; }
     JpegDecoder& jpeg_decoder() { return dec_; }
+    PngDecoder& png_decoder() { return pdec_; }             // IRE_FLAG_DECODE_PNG; without the flag it refuses every call
     IccConverter& icc_converter() { return icc_; }          // icc.hpp: ICC-tagged pixels to sRGB
     bool upload_icc() const { return upload_icc_; }         // IRE_FLAG_UPLOAD_ICC: upload jobs honour their file's ICC profile
     const TextFormat* result_format() const { return result_format_; }      // of the batcher's results, with this engine's settings; null: pixels
@@ -335,6 +336,7 @@ private:
     Buf<DeviceMem> d_fuse_sc_;            // ... and the classifier's scores of view 0 of every padded set, [kFuseMaxSets][7] (never io_.scores: those are the jobs')
     TextEncoder enc_;                     // codec.hpp: they own their buffers
     JpegDecoder dec_;
+    PngDecoder pdec_;
     IccConverter icc_;
     bool upload_icc_ = false;
 

@@ -532,18 +532,21 @@ __global__ __launch_bounds__(kThreads) void jpeg_dec_idct_kernel(DecBatch b, uns
     *reinterpret_cast<unsigned long long*>(p) = out;              // (8-byte aligned: every term is a multiple of 8)
 }
 
+// which image of the output, and which status word, file i of the batch becomes (the batcher's slots: a file's place in its slot)
+struct DecDst { unsigned char at[64]; };
 // K4.  one thread per pixel
 __global__ __launch_bounds__(kThreads) void jpeg_dec_colour_kernel(DecBatch b, const unsigned char* __restrict__ planes, unsigned long long plane_stride,
-                                                                   unsigned char* __restrict__ rgb, unsigned long long image_pitch, int h, int w, int* __restrict__ d_status) {
-    const unsigned img = blockIdx.y;
+                                                                   unsigned char* __restrict__ rgb, unsigned long long image_pitch, int h, int w, int* __restrict__ d_status,
+                                                                   DecDst dst) {
+    const unsigned img = blockIdx.y, out = dst.at[img];
     const unsigned long long idx = (unsigned long long)blockIdx.x * kThreads + threadIdx.x;
-    if (idx == 0) d_status[img] = b.stat[img];
+    if (idx == 0) d_status[out] = b.stat[img];
     if (idx >= (unsigned long long)h * w) return;
     const DecImage& im = b.images[img];
     const unsigned y = (unsigned)(idx / (unsigned)w), x = (unsigned)(idx - (unsigned long long)y * (unsigned)w);
     const unsigned char* base = planes + (unsigned long long)img * plane_stride;
     const int Y = base[(unsigned long long)y * (im.gridw[0] * 8) + x];
-    unsigned char* o = rgb + (unsigned long long)img * image_pitch + idx * 3;
+    unsigned char* o = rgb + (unsigned long long)out * image_pitch + idx * 3;
     if (im.sampling == 3) { o[0] = o[1] = o[2] = (unsigned char)Y; return; }
     int cc[2];
 #pragma unroll
@@ -738,7 +741,11 @@ void jpeg_dec_pack_streams(const jpegparse::File* const* f, const DecStream* con
 }
 
 void jpeg_dec_launch(const uint8_t* d_blob, const JpegDecLayout& L, int n, int h, int w, uint8_t* d_coef, uint8_t* d_planes, uint8_t* d_lanes, uint8_t* d_walk, uint8_t* d_rgb,
-                     size_t image_pitch, int32_t* d_status, hipStream_t s, hipEvent_t* marks) {
+                     size_t image_pitch, int32_t* d_status, hipStream_t s, hipEvent_t* marks, const int* dst) {
+    if (n < 1 || n > 64) fail(IRE_ERR_INTERNAL, "internal: the JPEG decoder's batch is outside 1..64");
+    DecDst where;
+    for (int i = 0; i < 64; ++i) where.at[i] = (unsigned char)(i < n && dst ? dst[i] : i);
+    for (int i = 0; dst && i < n; ++i) if (dst[i] < 0 || dst[i] > 63) fail(IRE_ERR_INTERNAL, "internal: the JPEG decoder's output index is outside 0..63");
     auto mark = [&](int k) { if (marks) IRE_HIP(hipEventRecord(marks[k], s)); };
     DecBatch b;
     b.images = reinterpret_cast<const DecImage*>(d_blob + L.images);
@@ -792,7 +799,7 @@ void jpeg_dec_launch(const uint8_t* d_blob, const JpegDecLayout& L, int n, int h
     hipLaunchKernelGGL(jpeg_dec_idct_kernel, dim3((unsigned)((blocks + kIdctBlocks - 1) / kIdctBlocks), n), dim3(kThreads), 0, s, b, d_planes, (unsigned long long)(blocks * 64));
     mark(8);
     hipLaunchKernelGGL(jpeg_dec_colour_kernel, dim3((unsigned)(((size_t)h * w + kThreads - 1) / kThreads), n), dim3(kThreads), 0, s, b, d_planes, (unsigned long long)(blocks * 64),
-                       d_rgb, (unsigned long long)image_pitch, h, w, d_status);
+                       d_rgb, (unsigned long long)image_pitch, h, w, d_status, where);
     mark(9);
     IRE_HIP(hipGetLastError());
 }

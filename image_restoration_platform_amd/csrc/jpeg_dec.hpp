@@ -42,7 +42,8 @@ void jpeg_dec_pack_streams(const jpegparse::File* const* f, const jpegdec::DecSt
 // the blob on the device -> n images of h x w x 3 bytes, image_pitch apart, and one status word per image (0: ok)
 // d_lanes: jpeg_dec_lane_bytes(L.nwin) bytes, d_walk: jpeg_dec_walk_bytes(L.walk_blocks) bytes (each may be null when it has none)
 void jpeg_dec_launch(const uint8_t* d_blob, const JpegDecLayout& L, int n, int h, int w, uint8_t* d_coef, uint8_t* d_planes, uint8_t* d_lanes, uint8_t* d_walk, uint8_t* d_rgb,
-                     size_t image_pitch, int32_t* d_status, hipStream_t s, hipEvent_t* marks = nullptr);
+                     size_t image_pitch, int32_t* d_status, hipStream_t s, hipEvent_t* marks = nullptr, const int* dst = nullptr);
+// dst: null, or n indices 0..63: file i becomes image dst[i] of d_rgb and sets status word dst[i] (null: image i)
 // marks: null, or kJpegDecMarks timing events recorded before the memset and behind the memset, level 0's K1, spec, chain and write
 // kernels and K2, everything a progressive file runs behind those (later levels, refinement scans), K3, K4 (tools/jpeg_decode_measure.py)
 }  // namespace ire

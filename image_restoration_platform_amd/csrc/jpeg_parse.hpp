@@ -478,10 +478,9 @@ inline bool plan_file(const uint8_t* file, size_t bytes, uint32_t accept, File& 
 // 0: the payload is not an Exif block (the walk goes on to the next APP1).  Everything else that is not exactly that -- a TIFF header
 // that is none, an offset or an entry outside the payload, another type or count, a value outside 1..8 -- is 1: an upload with a broken
 // EXIF block is an upright upload, never a refused one.  No read leaves p[0 .. n).
-inline int exif_orientation(const uint8_t* p, size_t n) {
-    if (n < 6 || std::memcmp(p, "Exif\0\0", 6) != 0) return 0;
-    const uint8_t* t = p + 6;                                      // the TIFF header: offsets count from here
-    const size_t m = n - 6;
+// The TIFF walk behind that prefix, shared with a PNG's eXIf chunk (png_parse.hpp), whose payload starts with the TIFF header: t[0 .. m)
+// -> 1..8 by the rules above, 1 for everything else.
+inline int tiff_orientation(const uint8_t* t, size_t m) {
     if (m < 8) return 1;
     bool le;
     if (t[0] == 'I' && t[1] == 'I') le = true; else if (t[0] == 'M' && t[1] == 'M') le = false; else return 1;
@@ -500,6 +499,10 @@ inline int exif_orientation(const uint8_t* p, size_t n) {
         return v >= 1 && v <= 8 ? (int)v : 1;
     }
     return 1;
+}
+inline int exif_orientation(const uint8_t* p, size_t n) {
+    if (n < 6 || std::memcmp(p, "Exif\0\0", 6) != 0) return 0;
+    return tiff_orientation(p + 6, n - 6);                         // the TIFF header: offsets count from there
 }
 // the orientation of a file: that of its first APP1 segment in front of the scan that is an Exif block; 1 when there is none or the
 // markers cannot be walked (the planner decides about such a file, not this)

@@ -94,6 +94,27 @@ def icc_plan_profile(profile, components=3):
     return _icc_result(_lib.load().ire_icc_plan_profile(profile, len(profile), int(components), ctypes.byref(t)), t)
 
 
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+
+def decode_png_plan_reason(data):
+    """bytes of a file -> ((h, w, colour_type), None) when an engine created with decode_png=True decodes it on the device, else (None,
+    reason) with the reason the C side gives ("invalid: PNG ...").  ire_decode_png_plan: pure host, no engine, no GPU."""
+    data = bytes(data)
+    h, w, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    if _lib.load().ire_decode_png_plan(data, len(data), ctypes.byref(h), ctypes.byref(w), ctypes.byref(c)) != 0:
+        return None, (_lib.load().ire_last_error() or b"").decode()
+    return (h.value, w.value, c.value), None
+
+
+def decode_png_flags(flags, decode_png=None, environ=None):
+    """the flags of an engine: IRE_FLAG_DECODE_PNG is added for decode_png=True and, when decode_png is None, for IRE_DECODE_PNG=1 in
+    the environment; nothing is ever taken away"""
+    if decode_png is None:
+        decode_png = (os.environ if environ is None else environ).get("IRE_DECODE_PNG") == "1"
+    return flags | _lib.IRE_FLAG_DECODE_PNG if decode_png else flags
+
+
 def upload_icc_flags(flags, upload_icc=None, environ=None):
     """the flags of an engine: IRE_FLAG_UPLOAD_ICC is added for upload_icc=True and, when upload_icc is None, for IRE_UPLOAD_ICC=1 in
     the environment (which then holds for EVERY engine of the process that does not say upload_icc=False); nothing is ever taken away"""
@@ -104,13 +125,15 @@ def upload_icc_flags(flags, upload_icc=None, environ=None):
 
 class Engine:
     def __init__(self, device_index=0, max_batch=8, num_streams=0, weights_path="default", seed=0, flags=0, precision="bf16", jpeg_quality=0,
-                 jpeg_sampling=0, upload_icc=None):
+                 jpeg_sampling=0, upload_icc=None, decode_png=None):
         """jpeg_quality (1..100; 0: 85) and jpeg_sampling (0 = 4:4:4, 2 = 4:2:0): the settings of the results of an engine created with
         flags=IRE_FLAG_RESULT_JPEG; invalid without that flag.  flags=IRE_FLAG_RESULT_JPEG | IRE_FLAG_JPEG_OPTIMIZE: those results
         carry their image's own, optimised Huffman tables (poll sizes its buffer by the larger bound of such a text).
         upload_icc=True (or IRE_FLAG_UPLOAD_ICC in flags; None: the environment's IRE_UPLOAD_ICC=1): submit_upload converts the pixels
-        of a file that carries an ICC profile to sRGB on the device, before the resize."""
-        flags = upload_icc_flags(flags, upload_icc)
+        of a file that carries an ICC profile to sRGB on the device, before the resize.
+        decode_png=True (or IRE_FLAG_DECODE_PNG in flags; None: the environment's IRE_DECODE_PNG=1): decode_png, and submit_jpeg /
+        submit_file / submit_upload take a PNG file beside a JPEG one."""
+        flags = decode_png_flags(upload_icc_flags(flags, upload_icc), decode_png)
         self._lib = _lib.load()
         if weights_path == "default":
             weights_path = _weights.ensure_default(seed)
@@ -272,7 +295,7 @@ class Engine:
         return out_u8
 
     def upload_plan(self, data, max_dim=2048):
-        """(stored_h, stored_w, orientation, out_h, out_w) of a JPEG upload as THIS engine's submit_upload takes it; raises EngineError
+        """(stored_h, stored_w, orientation, out_h, out_w) of a JPEG (with decode_png=True: or PNG) upload as THIS engine's submit_upload takes it; raises EngineError
         (invalid input, the plan's reason) for a file it refuses.  Pure host arithmetic."""
         plan, why = upload_plan_reason(data, max_dim, self.upload_accept)
         if plan is None:
@@ -280,7 +303,8 @@ class Engine:
         return plan
 
     def submit_upload(self, data, max_dim=2048, scores=None):
-        """Queue one JPEG upload as its bytes: decoded, turned upright by its EXIF orientation, fitted inside max_dim (Lanczos-3) and
+        """Queue one upload as its bytes -- a JPEG file, or on an engine created with decode_png=True a PNG file (orientation from its eXIf
+        chunk; the result is then that of submit_fit(..., is_jpeg=False, ...) of decode_png's pixels): decoded, turned upright by its EXIF orientation, fitted inside max_dim (Lanczos-3) and
         restored, all on the device with its batch.  The result is that of submit_fit(preprocess(decode_jpeg(data), orientation,
         max_dim), is_jpeg=True, scores), of the fitted size upload_plan reports; on an engine created with upload_icc=True the decoded
         pixels first go through icc_to_srgb with the file's own transform (icc_plan_file).  Raises EngineError (invalid input) for a file the plan
@@ -315,7 +339,8 @@ class Engine:
 
     def submit_jpeg(self, data, scores=None):
         """submit_fit() for an encoded upload: the bytes of a JPEG file that decode_jpeg_plan accepts (baseline; on an engine created with
-        IRE_FLAG_DECODE_PROGRESSIVE progressive too).  The file is parsed in
+        IRE_FLAG_DECODE_PROGRESSIVE progressive too), or on an engine created with decode_png=True of a PNG file that decode_png_plan
+        accepts (its result is that of submit_fit(decode_png(data), is_jpeg=False, scores)).  The file is parsed in
         this call and decoded on the device with its batch; the result is that of submit_fit(its pixels, is_jpeg=True, scores).
         Raises EngineError (invalid input, the plan's reason) for a file out of scope: no job exists then.  A file with corrupt data
         fails at its poll."""
@@ -323,8 +348,13 @@ class Engine:
         sc = None if scores is None else np.ascontiguousarray(np.asarray(scores, dtype=np.float64).reshape(7))
         job = ctypes.c_void_p()
         self._check(self._lib.ire_submit_jpeg(self._h, data, len(data), _ptr(sc), ctypes.byref(job)))      # the one parse of the file: refuses with the plan's reason
-        h, w = _jpeg_frame_size(data)
+        if data[:8] == PNG_SIGNATURE:          # (accepted, so the engine decodes PNG and IHDR follows the signature)
+            w, h = int.from_bytes(data[16:20], "big"), int.from_bytes(data[20:24], "big")
+        else:
+            h, w = _jpeg_frame_size(data)
         return (job, h, w)
+
+    submit_file = submit_jpeg          # the neutral name: a JPEG file, or on an engine created with decode_png=True a PNG file
 
     def submit_fuse_fit(self, views, is_jpeg=True, scores=None):
         """Queue ONE fusion job: views [k,H,W,3] uint8 (or a list of k [H,W,3] arrays), k in 2..3, any size 1..8192 per side.  Every
@@ -519,7 +549,9 @@ class Engine:
     @property
     def upload_accept(self):
         """decode_accept, and IRE_DECODE_ACCEPT_ICC when the engine was created with IRE_FLAG_UPLOAD_ICC: what upload_plan_reason is asked"""
-        return self.decode_accept | (_lib.IRE_DECODE_ACCEPT_ICC if getattr(self, "_flags", 0) & _lib.IRE_FLAG_UPLOAD_ICC else 0)
+        f = getattr(self, "_flags", 0)
+        return (self.decode_accept | (_lib.IRE_DECODE_ACCEPT_ICC if f & _lib.IRE_FLAG_UPLOAD_ICC else 0) |
+                (_lib.IRE_DECODE_ACCEPT_PNG if f & _lib.IRE_FLAG_DECODE_PNG else 0))
 
     def icc_to_srgb(self, rgb, transforms):
         """[n,h,w,3] uint8 (or one [h,w,3]) and n IreIccTransform (None: leave the image) -> the converted copy: ire_icc_to_srgb."""
@@ -569,6 +601,44 @@ class Engine:
         out = np.empty((h, w, 3), np.uint8)
         self._check(self._lib.ire_decode_jpeg(self._h, data, len(data), _ptr(out), h, w))
         return out
+
+    # ---- PNG uploads decoded on the device (csrc/png_parse.hpp, csrc/png_dec.hip): an engine created with decode_png=True ----------
+    def decode_png_plan(self, data):
+        """(h, w, colour_type) or None; the reason of the last refusal is kept in .last_plan_reason (decode_png_plan_reason: no engine)"""
+        plan, why = decode_png_plan_reason(data)
+        if plan is None:
+            self.last_plan_reason = why
+        return plan
+
+    def decode_png(self, data):
+        """bytes of a PNG file the plan accepts -> [h,w,3] uint8, equal to PIL.Image.open(f).convert("RGB"); raises EngineError (invalid
+        input) for a file out of scope, for data the device flags, and on an engine created without decode_png=True."""
+        data = bytes(data)
+        plan, why = decode_png_plan_reason(data)
+        if plan is None:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, why)
+        h, w, _ = plan
+        out = np.empty((h, w, 3), np.uint8)
+        self._check(self._lib.ire_decode_png(self._h, data, len(data), _ptr(out), h, w))
+        return out
+
+    def decode_png_device(self, files, out_u8=None, stream=None):
+        """decode_jpeg_device for PNG files of one planned size, of any colour types"""
+        import torch
+        files = [bytes(f) for f in files]
+        plans = [decode_png_plan_reason(f)[0] for f in files]
+        if not files or any(p is None for p in plans) or len({p[:2] for p in plans}) != 1:
+            raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid input: decode_png_device takes files of one planned size")
+        n, (h, w, _) = len(files), plans[0]
+        if out_u8 is None:
+            out_u8 = torch.empty((n, h, w, 3), dtype=torch.uint8, device="cuda")
+        assert out_u8.is_cuda and out_u8.dtype == torch.uint8 and tuple(out_u8.shape) == (n, h, w, 3) and out_u8[0].is_contiguous()
+        status = torch.empty(n, dtype=torch.int32, device=out_u8.device)
+        ptrs = (ctypes.c_char_p * n)(*files)
+        lens = (ctypes.c_size_t * n)(*[len(f) for f in files])
+        self._check(self._lib.ire_decode_png_device(self._h, ptrs, lens, n, h, w, ctypes.c_void_p(out_u8.data_ptr()), out_u8.stride(0) if n > 1 else h * w * 3,
+                                                    ctypes.c_void_p(status.data_ptr()), self._stream_ptr(stream)))
+        return out_u8, status
 
     def decode_jpeg_device(self, files, out_u8=None, stream=None):
         """list of N <= max_batch files (bytes) of one planned size -> (cuda uint8 [N,h,w,3], cuda int32 [N] status words, 0 = ok),

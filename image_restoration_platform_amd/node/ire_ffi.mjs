@@ -39,6 +39,7 @@ export function bindIre(libPath) {
     ire_encode_png_base64_fit: ['int', [P, P, 'int', 'int', 'int', P, 'size_t']],
     ire_submit_fit: ['int', [P, P, 'int', 'int', 'int', P, PP]],
     ire_submit_jpeg: ['int', [P, P, 'size_t', P, PP]],
+    ire_submit_file: ['int', [P, P, 'size_t', P, PP]],
     ire_submit_upload: ['int', [P, P, 'size_t', 'int', P, PP]],
     ire_upload_plan: ['int', [P, 'size_t', 'int', 'int', P, P, P, P, P]],
     ire_icc_plan_profile: ['int', [P, 'size_t', 'int', P]],
@@ -70,6 +71,9 @@ export function bindIre(libPath) {
     ire_decode_jpeg_plan_ex: ['int', [P, 'size_t', 'int', P, P, P, P]],
     ire_decode_jpeg: ['int', [P, P, 'size_t', P, 'int', 'int']],
     ire_decode_jpeg_device: ['int', [P, P, P, 'int', 'int', 'int', P, 'size_t', P, P]],
+    ire_decode_png_plan: ['int', [P, 'size_t', P, P, P]],
+    ire_decode_png: ['int', [P, P, 'size_t', P, 'int', 'int']],
+    ire_decode_png_device: ['int', [P, P, P, 'int', 'int', 'int', P, 'size_t', P, P]],
     ire_job_release: ['int', [P, P]],
     ire_affinity_plan: ['int', ['string', 'string', P, 'size_t', IP, IP, IP]],
     ire_engine_affinity: ['int', [P, P, 'size_t', IP]],

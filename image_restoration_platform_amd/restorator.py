@@ -51,12 +51,17 @@ def decode_image(buffer, engine=None):
     """encoded bytes -> (rgb uint8 [H,W,3], format str).  sharp(buf) decodes to 8-bit sRGB
     (Appendix A.1); no EXIF rotation inside the classifier (A.2)."""
     from PIL import Image
-    if engine is not None and os.environ.get("IRE_UPLOAD_CODEC") == "jpeg-device" and bytes(buffer[:2]) == b"\xff\xd8":
+    # IRE_UPLOAD_CODEC: jpeg-device | png-device (an engine created with decode_png=True) | device (both)
+    codec = os.environ.get("IRE_UPLOAD_CODEC")
+    is_jpeg = bytes(buffer[:2]) == b"\xff\xd8" and codec in ("jpeg-device", "device")
+    is_png = bytes(buffer[:8]) == b"\x89PNG\r\n\x1a\n" and codec in ("png-device", "device")
+    if engine is not None and (is_jpeg or is_png):
         from .engine import EngineError
         try:
-            rgb = engine.decode_jpeg(bytes(buffer))      # plans inside: a file out of scope or flagged on the device is "invalid input"
+            # plans inside: a file out of scope or flagged on the device is "invalid input"
+            rgb = engine.decode_jpeg(bytes(buffer)) if is_jpeg else engine.decode_png(bytes(buffer))
             UPLOAD_DECODES["device"] += 1
-            return rgb, "jpeg"
+            return rgb, "jpeg" if is_jpeg else "png"
         except EngineError as e:
             if e.status != _lib.IRE_ERR_INVALID_INPUT:   # only that is the host codec's to judge; unavailable / internal go up
                 raise

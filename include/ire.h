@@ -114,6 +114,12 @@ typedef struct ire_config {
  * what is converted and what is refused.  Without the flag every upload is treated as sRGB, tagged or not, as before.  File jobs
  * (ire_submit_jpeg) and every other entry are not changed by it. */
 #define IRE_FLAG_UPLOAD_ICC 256u
+/* Not a result format, and free to combine with every other flag: the engine decodes PNG uploads on the device -- ire_decode_png,
+ * ire_decode_png_device, and ire_submit_jpeg / ire_submit_file / ire_submit_upload take a PNG file (they sniff the eight signature
+ * bytes) beside a JPEG one.  See ire_decode_png_plan below for what is decoded and what is refused.  Without the flag every entry
+ * refuses a PNG with the reason it gave before the flag existed, and nothing else changes.  (Bit value 512 stays unknown, as 2, 16 and
+ * 64 do: tests/test_icc_plan.py holds it to that.) */
+#define IRE_FLAG_DECODE_PNG 1024u
 
 
 
@@ -333,10 +339,40 @@ int ire_decode_jpeg_plan(const uint8_t* file, size_t bytes, int* out_h, int* out
 #define IRE_DECODE_ACCEPT_PROGRESSIVE 1u
 #define IRE_DECODE_MAX_SCANS 64
 #define IRE_DECODE_ACCEPT_ICC 4u          /* ire_upload_plan only: see there.  (Bit value 2 stays unknown.) */
+#define IRE_DECODE_ACCEPT_PNG 16u         /* ire_upload_plan only: the plan of an engine with IRE_FLAG_DECODE_PNG.  (Bit value 8 stays unknown beside 2:
+                                             tests/test_icc_plan.py holds both to that.) */
 int ire_decode_jpeg_plan_ex(const uint8_t* file, size_t bytes, uint32_t accept, int* out_h, int* out_w, int* out_sampling, int* out_nscans);
 int ire_decode_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, uint8_t* out_rgb /* h*w*3 */, int h, int w);
 int ire_decode_jpeg_device(ire_engine* e, const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb,
                            size_t image_pitch_bytes, int32_t* d_status /* n x int32, device */, void* stream);
+
+/* ---- PNG uploads decoded on the device (png_parse.hpp, png_inflate_core.hpp, png_dec.hip) ----
+ * The RGB bytes equal PIL.Image.open(f).convert("RGB"): the stream inflated, the scanlines unfiltered, grey replicated, the palette
+ * looked up, alpha of any kind dropped.
+ * ire_decode_png_plan: pure host, no engine.  IRE_OK and the size and colour type (any output pointer may be NULL) if the device decodes
+ * this file: the signature, IHDR first; bit depth 8; colour type 0, 2, 3, 4 or 6; compression 0, filter method 0, no interlace; 1..8192
+ * per side; PLTE of 1..256 entries (required for type 3); one or more CONSECUTIVE IDAT chunks, empty ones among them; IEND, or the end
+ * of the file, behind the last IDAT; tRNS is read past; gAMA, cHRM, sRGB, pHYs, iCCP, text and every other ancillary chunk are skipped.
+ * Everything else -- 16-bit and sub-8-bit depths, Adam7, APNG (acTL in front of IDAT), type 3 without PLTE, an IHDR or PLTE chunk whose
+ * CRC-32 is wrong, any other chunk in front of IDAT whose CRC-32 is wrong, a chunk that overruns the file (behind the last IDAT only an
+ * empty IEND may lack its CRC, and the file may end inside a chunk's eight header bytes: what Pillow still reads), IDAT chunks that are
+ * not consecutive, no IDAT, a zlib header that is not deflate
+ * with a window of at most 32 KiB and no preset dictionary -- is IRE_ERR_INVALID_INPUT with the reason in ire_last_error ("invalid: PNG
+ * ..."): such a file stays with the host codec.  IDAT CRCs are NOT checked: Pillow does not check them either, and the stream's
+ * Adler-32, which the device compares, covers the data.
+ * ire_decode_png (engine with IRE_FLAG_DECODE_PNG; else IRE_ERR_INVALID_INPUT): synchronous; out_rgb receives h*w*3 bytes (h, w as
+ * planned).  A file whose DATA is FLAGGED on the device is IRE_ERR_INVALID_INPUT "invalid: corrupt PNG data (decoder status N)"; the
+ * engine stays usable.  Flagged is everything but this: zlib decompresses the stream without error, it yields exactly
+ * h * (1 + w * bytes per pixel) bytes, and every scanline's filter byte is 0..4.  Pillow zero-fills a short stream and ignores a long
+ * one; the device flags both, and the host codec then decides.  Equality with Pillow is promised for every image that is NOT flagged.
+ * ire_decode_png_device: ire_decode_jpeg_device's contract -- n <= max_batch files (host memory) of ONE planned size, of any colour
+ * types, -> n images on the device, image i at d_rgb + i * image_pitch_bytes (>= h*w*3), nothing between them written; d_status: one
+ * int32 per image, 0 = ok (the pixels of a flagged image are unspecified); the host parse runs inside the call; two launches whatever
+ * n; the host's one wait is for the upload of the call before last. */
+int ire_decode_png_plan(const uint8_t* file, size_t bytes, int* out_h, int* out_w, int* out_colour_type);
+int ire_decode_png(ire_engine* e, const uint8_t* file, size_t bytes, uint8_t* out_rgb /* h*w*3 */, int h, int w);
+int ire_decode_png_device(ire_engine* e, const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb,
+                          size_t image_pitch_bytes, int32_t* d_status /* n x int32, device */, void* stream);
 
 /* ---- async batcher (restoreBatch's in-flight promises) ---------------------------------- */
 typedef struct ire_job ire_job;
@@ -360,6 +396,17 @@ int ire_submit_fit(ire_engine* e, const uint8_t* rgb, int h, int w, int is_jpeg,
  * its poll: IRE_ERR_INVALID_INPUT "invalid: corrupt JPEG data (decoder status N)"; the other jobs of its batch complete.  A file job
  * has no preprocess semantics: IRE_FLAG_UPLOAD_ICC does not change it, its pixels are taken as they are decoded. */
 int ire_submit_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, const double* scores, ire_job** job_out);
+/* The same entry under its neutral name.  On an engine with IRE_FLAG_DECODE_PNG both take a PNG file that ire_decode_png_plan accepts
+ * (they sniff the eight signature bytes): the job's result is that of ire_submit_fit(ire_decode_png(file), h, w, is_jpeg = 0, scores).
+ * The room rule is the same: a file whose IDAT payload is larger than its h * w * 3 pixels is refused at submit (a noise image
+ * compresses to slightly more than its pixels).  PNG and JPEG jobs of one size share a batch, decoded with one call per kind however they interleave.  Corrupt data fails its own job at its
+ * poll, "invalid: corrupt PNG data (decoder status N)"; the rest of the batch completes.  ire_submit_upload likewise: its result is
+ *   ire_submit_fit(ire_preprocess(ire_decode_png(file), its orientation, max_dim), is_jpeg = 0, scores)
+ * with the orientation of an eXIf chunk in front of IDAT (the TIFF walk of a JPEG's Exif block; a broken chunk is orientation 1), and
+ * ire_upload_plan says the same with IRE_DECODE_ACCEPT_PNG.  On an engine with IRE_FLAG_UPLOAD_ICC (the plan: IRE_DECODE_ACCEPT_ICC)
+ * a PNG that carries iCCP is refused with a reason: reading the chunk is a later change; without that flag the profile is ignored, as
+ * a JPEG's is.  Without IRE_FLAG_DECODE_PNG both entries refuse a PNG as they always did ("invalid: not a JPEG file (no SOI)"). */
+int ire_submit_file(ire_engine* e, const uint8_t* file, size_t bytes, const double* scores, ire_job** job_out);
 /* An UPLOAD job: ire_submit_jpeg with the preprocess step of imagePreprocess.js:40-55 between the decode and the network, all on the
  * device -- no pixel of the upload is ever on the host.  The file is one ire_submit_jpeg takes.  Its orientation is read from the
  * first APP1 segment that is an Exif block (IFD0 tag 0x0112, SHORT, count 1, value 1..8; anything else, a broken block included, is

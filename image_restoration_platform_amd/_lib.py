@@ -11,6 +11,7 @@ IRE_FLAG_RESULT_PNG_DEFLATE = 4
 IRE_FLAG_RESULT_JPEG = 8
 IRE_FLAG_DECODE_PROGRESSIVE = 32
 IRE_FLAG_JPEG_OPTIMIZE = 128
+IRE_FLAG_JPEG_PROGRESSIVE = 2048
 IRE_FLAG_UPLOAD_ICC = 256
 IRE_FLAG_DECODE_PNG = 1024
 IRE_DECODE_ACCEPT_PROGRESSIVE = 1
@@ -93,6 +94,9 @@ SYMBOLS = {
     "ire_jpeg_optimized_base64_bound": (ctypes.c_size_t, [_i, _i, _i, _i]),
     "ire_encode_jpeg_optimized_base64_fit_device": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _i, _i, _vp]),
     "ire_encode_jpeg_optimized_base64_fit": (_i, [_vp, _u8p, _i, _i, _i, _u8p, ctypes.c_size_t, _vp, _i, _i]),
+    "ire_jpeg_progressive_base64_bound": (ctypes.c_size_t, [_i, _i, _i, _i]),
+    "ire_encode_jpeg_progressive_base64_fit_device": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_size_t, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _i, _i, _vp]),
+    "ire_encode_jpeg_progressive_base64_fit": (_i, [_vp, _u8p, _i, _i, _i, _u8p, ctypes.c_size_t, _vp, _i, _i]),
     "ire_decode_jpeg_plan": (_i, [_u8p, ctypes.c_size_t, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "ire_decode_jpeg_plan_ex": (_i, [_u8p, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "ire_decode_jpeg": (_i, [_vp, _u8p, ctypes.c_size_t, _u8p, _i, _i]),
@@ -126,6 +130,7 @@ SYMBOLS = {
     "ire_debug_classifier_sums": (_i, [_vp, _i, _vp]),
     "ire_debug_fusion_wlut": (_i, [_vp, _vp, _i, _vp]),
     "ire_debug_jpeg_huffman": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "ire_debug_jpeg_progressive_from_coefs": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
     "ire_debug_capture": (_i, [_vp, _i]),
     "ire_debug_activation": (_i, [_vp, ctypes.c_char_p, _vp, ctypes.POINTER(ctypes.c_size_t)]),
     "ire_profile_enable": (_i, [_vp, _i]),

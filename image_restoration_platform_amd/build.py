@@ -47,6 +47,7 @@ SOURCES = [
     ("encode.hip", []),
     ("deflate.hip", []),
     ("jpeg.hip", []),
+    ("jpeg_progenc.hip", []),
     ("jpeg_dec.hip", []),
     ("png_dec.hip", []),
     ("icc.hip", []),

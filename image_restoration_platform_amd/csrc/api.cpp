@@ -716,6 +716,36 @@ int ire_encode_jpeg_optimized_base64_fit(ire_engine* e, const uint8_t* rgb, int 
     });
 }
 
+// the same three as a progressive file
+size_t ire_jpeg_progressive_base64_bound(int h, int w, int quality, int sampling) {
+    if (h < 1 || w < 1 || h > 8192 || w > 8192 || quality < 0 || quality > 100 || (sampling != 0 && sampling != 2)) return 0;
+    return jpeg_format_of(jpeg_settings_of(quality, sampling, false, true)).bound(h, w);
+}
+
+int ire_encode_jpeg_progressive_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes, size_t image_pitch_bytes, uint8_t* d_chars,
+                                                  size_t stride_bytes, uint64_t* d_lens, int quality, int sampling, void* stream) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        const TextFormat f = jpeg_format_of(jpeg_settings_of(quality, sampling, false, true));
+        on_stream(E, (hipStream_t)stream, [&] { E.text_encoder().encode_device(f, d_rgb, n, h, w, row_pitch_bytes, image_pitch_bytes, d_chars, stride_bytes, d_lens, (hipStream_t)stream); });
+    });
+}
+
+int ire_encode_jpeg_progressive_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes, uint64_t* lens, int quality, int sampling) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        const TextFormat f = jpeg_format_of(jpeg_settings_of(quality, sampling, false, true));
+        on_stream(E, E.main_stream(), [&] { E.text_encoder().encode_host(f, rgb, n, h, w, chars, stride_bytes, lens); });
+    });
+}
+
+int ire_debug_jpeg_progressive_from_coefs(ire_engine* e, const int16_t* coefs, int n, int h, int w, int quality, int sampling, uint8_t* out_files, size_t stride, uint64_t* lens) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, E.main_stream(), [&] { E.text_encoder().debug_jpeg_progressive(coefs, n, h, w, quality, sampling, out_files, stride, lens); });
+    });
+}
+
 int ire_debug_jpeg_huffman(ire_engine* e, const uint32_t* counts, int n, uint8_t* bits_vals_out, int32_t* nvals_out) {
     return guarded([&] {
         Engine& E = eng(e);

@@ -16,25 +16,32 @@ const TextFormat kStoredPng = {"PNG", [](int h, int w, TextSettings) { return pn
                                [](int n, int h, int w, TextSettings) { return png_scratch_bytes(n, h, w); },
                                [](const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_scratch, uint8_t* d_chars, size_t stride,
                                   uint8_t*, size_t, TextSettings, hipStream_t s) { encode_png_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_scratch, d_chars, stride, s); },
-                               false, false, {0, 0}};
+                               false, false, {0, 0, 0, 0}};
 const TextFormat kDeflatePng = {"PNG", [](int h, int w, TextSettings) { return png_deflate_base64_bound(h, w); }, "ire_png_deflate_base64_bound",
                                 [](int n, int h, int w, TextSettings) { return png_deflate_scratch_bytes(n, h, w); },
                                 [](const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_scratch, uint8_t* d_chars, size_t stride,
                                    uint8_t* d_lens, size_t lens_pitch, TextSettings, hipStream_t s) {
                                     encode_png_deflate_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_scratch, d_chars, stride, d_lens, lens_pitch, s);
                                 },
-                                true, false, {0, 0}};
-const TextFormat kJpeg = {"JPEG", [](int h, int w, TextSettings o) { return jpeg_base64_bound(h, w, o.quality, o.sampling, o.optimize != 0); }, "ire_jpeg_base64_bound",
-                          [](int n, int h, int w, TextSettings o) { return jpeg_scratch_bytes(n, h, w, o.quality, o.sampling, o.optimize != 0); },
+                                true, false, {0, 0, 0, 0}};
+const TextFormat kJpeg = {"JPEG",
+                          [](int h, int w, TextSettings o) {
+                              return o.progressive ? jpeg_progressive_base64_bound(h, w, o.quality, o.sampling) : jpeg_base64_bound(h, w, o.quality, o.sampling, o.optimize != 0);
+                          },
+                          "ire_jpeg_base64_bound",
+                          [](int n, int h, int w, TextSettings o) {
+                              return o.progressive ? jpeg_progressive_scratch_bytes(n, h, w, o.quality, o.sampling) : jpeg_scratch_bytes(n, h, w, o.quality, o.sampling, o.optimize != 0);
+                          },
                           [](const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, uint8_t* d_scratch, uint8_t* d_chars, size_t stride,
                              uint8_t* d_lens, size_t lens_pitch, TextSettings o, hipStream_t s) {
+                              if (o.progressive) return encode_jpeg_progressive_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_scratch, d_chars, stride, d_lens, lens_pitch, o.quality, o.sampling, s);
                               encode_jpeg_base64_launch(d_rgb, n, h, w, row_pitch, image_pitch, d_scratch, d_chars, stride, d_lens, lens_pitch, o.quality, o.sampling, o.optimize != 0, s);
                           },
-                          true, true, {kJpegDefaultQuality, kJpegDefaultSampling, 0}};
+                          true, true, {kJpegDefaultQuality, kJpegDefaultSampling, 0, 0}};
 
 void check_config_flags(uint32_t flags) {
     constexpr uint32_t kResultBits = IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG;
-    if (flags & ~(kResultBits | IRE_FLAG_DECODE_PROGRESSIVE | IRE_FLAG_JPEG_OPTIMIZE | IRE_FLAG_UPLOAD_ICC | IRE_FLAG_DECODE_PNG)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
+    if (flags & ~(kResultBits | IRE_FLAG_DECODE_PROGRESSIVE | IRE_FLAG_JPEG_OPTIMIZE | IRE_FLAG_UPLOAD_ICC | IRE_FLAG_DECODE_PNG | IRE_FLAG_JPEG_PROGRESSIVE)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
     if (((flags & kResultBits) & ((flags & kResultBits) - 1)) != 0) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");
 }
 
@@ -42,10 +49,10 @@ const TextFormat* result_format_of(uint32_t flags) {
     return (flags & IRE_FLAG_RESULT_PNG_DEFLATE) ? &kDeflatePng : (flags & IRE_FLAG_RESULT_JPEG) ? &kJpeg : (flags & IRE_FLAG_RESULT_PNG_BASE64) ? &kStoredPng : nullptr;
 }
 
-TextSettings jpeg_settings_of(int quality, int sampling, bool optimize) {
+TextSettings jpeg_settings_of(int quality, int sampling, bool optimize, bool progressive) {
     if (quality < 0 || quality > 100) fail(IRE_ERR_INVALID_INPUT, "invalid: JPEG quality must be in 1..100 (0: the default, 85)");
     if (sampling != 0 && sampling != 2) fail(IRE_ERR_INVALID_INPUT, "invalid: JPEG sampling must be 0 (4:4:4) or 2 (4:2:0); 4:2:2 and grey results are not built");
-    return {quality ? quality : kJpegDefaultQuality, sampling, optimize ? 1 : 0};
+    return {quality ? quality : kJpegDefaultQuality, sampling, optimize ? 1 : 0, progressive ? 1 : 0};
 }
 
 TextSettings check_config_jpeg(uint32_t flags, int quality, int sampling) {
@@ -53,12 +60,15 @@ TextSettings check_config_jpeg(uint32_t flags, int quality, int sampling) {
         fail(IRE_ERR_INVALID_INPUT, "invalid ire_config: jpeg_quality or jpeg_sampling set without IRE_FLAG_RESULT_JPEG");
     if ((flags & IRE_FLAG_JPEG_OPTIMIZE) && !(flags & IRE_FLAG_RESULT_JPEG))
         fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags: IRE_FLAG_JPEG_OPTIMIZE set without IRE_FLAG_RESULT_JPEG");
-    return jpeg_settings_of(quality, sampling, (flags & IRE_FLAG_JPEG_OPTIMIZE) != 0);
+    if ((flags & IRE_FLAG_JPEG_PROGRESSIVE) && !(flags & IRE_FLAG_RESULT_JPEG))
+        fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags: IRE_FLAG_JPEG_PROGRESSIVE set without IRE_FLAG_RESULT_JPEG");
+    return jpeg_settings_of(quality, sampling, (flags & IRE_FLAG_JPEG_OPTIMIZE) != 0, (flags & IRE_FLAG_JPEG_PROGRESSIVE) != 0);
 }
 
 TextFormat jpeg_format_of(TextSettings o) {
     TextFormat f = kJpeg.with(o);
     if (o.optimize) f.bound_name = "ire_jpeg_optimized_base64_bound";
+    if (o.progressive) f.bound_name = "ire_jpeg_progressive_base64_bound";
     return f;
 }
 
@@ -156,6 +166,32 @@ void TextEncoder::debug_jpeg_huffman(const uint32_t* counts, int n, uint8_t* bit
     jpeg_huffman_tables_launch(reinterpret_cast<const unsigned*>(d), n, d + cb, reinterpret_cast<int*>(d + cb + tpad), s);
     IRE_HIP(hipMemcpyAsync(bits_vals_out, d + cb, tb, hipMemcpyDeviceToHost, s));
     IRE_HIP(hipMemcpyAsync(nvals_out, d + cb + tpad, nb, hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipStreamSynchronize(s));
+}
+
+// the progressive JPEG path behind its coefficient pass, synchronous on the main stream: coefficients up, files and lengths down
+void TextEncoder::debug_jpeg_progressive(const int16_t* coefs, int n, int h, int w, int quality, int sampling, uint8_t* files_out, size_t stride, uint64_t* lens_out) {
+    if (!coefs || !files_out || !lens_out || n < 1 || n > max_batch_ || h < 1 || w < 1 || h > 8192 || w > 8192)
+        fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_debug_jpeg_progressive_from_coefs (1..max_batch images, 1..8192 per side)");
+    const TextSettings o = jpeg_settings_of(quality, sampling, false, true);
+    const size_t bound = jpeg_progressive_file_bound(h, w, o.quality, o.sampling);
+    if (stride < bound) fail(IRE_ERR_INVALID_INPUT, "invalid stride for ire_debug_jpeg_progressive_from_coefs: smaller than the file bound");
+    const size_t cb = (size_t)n * jpeg_progressive_coef_count(h, w, o.sampling) * sizeof(int16_t), need = jpeg_progressive_scratch_bytes(n, h, w, o.quality, o.sampling);
+    if (cb > d_io_.bytes() || need > d_scratch_.bytes()) IRE_HIP(hipDeviceSynchronize());
+    d_io_.grow(cb);
+    d_scratch_.grow(need);
+    hipStream_t s = main_stream_;
+    uint8_t* d = d_io_.get<uint8_t>();
+    uint8_t* sc = d_scratch_.get<uint8_t>();
+    IRE_HIP(hipMemcpyAsync(d, coefs, cb, hipMemcpyHostToDevice, s));
+    size_t files_off = 0, file_pitch = 0, flen_off = 0;
+    jpeg_progressive_from_coefs_launch(reinterpret_cast<const short*>(d), n, h, w, o.quality, o.sampling, sc, &files_off, &file_pitch, &flen_off, s);
+    IRE_HIP(hipMemcpyAsync(lens_out, sc + flen_off, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < n; ++i) {
+        if (lens_out[i] > bound) fail(IRE_ERR_INTERNAL, "internal: the JPEG encoder reported a length beyond its bound");
+        IRE_HIP(hipMemcpyAsync(files_out + stride * i, sc + files_off + file_pitch * i, (size_t)lens_out[i], hipMemcpyDeviceToHost, s));
+    }
     IRE_HIP(hipStreamSynchronize(s));
 }
 

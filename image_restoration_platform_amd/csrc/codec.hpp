@@ -9,9 +9,10 @@
 
 namespace ire {
 
-// The format's settings, chosen per engine or per direct call: JPEG's quality (1..100), sampling (0 = 4:4:4, 2 = 4:2:0) and optimize
-// (0 | 1: the image's own Huffman tables).  The PNG formats have none and ignore them.
-struct TextSettings { int quality, sampling, optimize; };
+// The format's settings, chosen per engine or per direct call: JPEG's quality (1..100), sampling (0 = 4:4:4, 2 = 4:2:0), optimize
+// (0 | 1: the image's own Huffman tables) and progressive (0 | 1: the ten-scan progressive file of jpeg_progenc.hip, whose tables are
+// always its own: optimize beside it changes nothing).  The PNG formats have none and ignore them.
+struct TextSettings { int quality, sampling, optimize, progressive; };
 struct TextFormat {
     const char* noun;                                   // the encoder as its messages name it: "PNG" | "JPEG"
     size_t (*bound_fn)(int h, int w, TextSettings o);   // the most characters an h x w image gives (stored PNG: exactly so many)
@@ -40,11 +41,11 @@ void check_config_flags(uint32_t flags);
 const TextFormat* result_format_of(uint32_t flags);
 // JPEG settings as the ABI takes them: 0 means the default (85 | 4:4:4); refuses a quality outside 1..100 and a sampling other than 0
 // or 2 as "invalid: ..."
-TextSettings jpeg_settings_of(int quality, int sampling, bool optimize = false);
-// ire_config's two JPEG fields and IRE_FLAG_JPEG_OPTIMIZE: jpeg_settings_of, and any of the three set without IRE_FLAG_RESULT_JPEG is
-// refused
+TextSettings jpeg_settings_of(int quality, int sampling, bool optimize = false, bool progressive = false);
+// ire_config's two JPEG fields, IRE_FLAG_JPEG_OPTIMIZE and IRE_FLAG_JPEG_PROGRESSIVE: jpeg_settings_of, and any of the four set without
+// IRE_FLAG_RESULT_JPEG is refused
 TextSettings check_config_jpeg(uint32_t flags, int quality, int sampling);
-// kJpeg at the settings given; with optimize its messages name the optimised bound
+// kJpeg at the settings given; with optimize or progressive its messages name that bound
 TextFormat jpeg_format_of(TextSettings o);
 
 // Owns the scratch all formats share and the host entries' staging.  Every call runs under the engine's lock.
@@ -67,6 +68,9 @@ public:
     void encode_png_aligned_host(const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride);
     // ire_debug_jpeg_huffman: counts [n][4][256] -> bits_vals_out [n][4][16 + 256], nvals_out [n][4], by jpeg.hip's table kernel alone
     void debug_jpeg_huffman(const uint32_t* counts, int n, uint8_t* bits_vals_out, int32_t* nvals_out);
+    // ire_debug_jpeg_progressive_from_coefs: the progressive path behind its coefficient pass on coefficients given (host) -> n files
+    // `stride` apart (host) and their lengths
+    void debug_jpeg_progressive(const int16_t* coefs, int n, int h, int w, int quality, int sampling, uint8_t* files_out, size_t stride, uint64_t* lens_out);
 
 private:
     void run_host(const TextFormat& f, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride, uint64_t* lens);

@@ -230,7 +230,10 @@ __device__ __forceinline__ int pred_of(unsigned blk) {
 // to the image's in `hist` -- integer sums, so their order does not matter; kEmitOwn, its second pass: the front end again
 // (recomputing costs less than 6 bytes per pixel of coefficients written and read back) and the bits under the image's own codes,
 // which the table kernel left in `codes` ([image][4][256], value | length << 16).
-constexpr int kEmitFixed = 0, kCount = 1, kEmitOwn = 2;
+// kCoefs, the progressive path's coefficient pass (jpeg_progenc.hip): the same front end once per image, the quantised coefficients
+// as int16 to the image's planes behind `intbuf` (jpeg_progenc_core.hpp: Geom), nothing else -- ten scans in two passes each would
+// otherwise run the DCT twenty times, so there "store" beats "recompute".
+constexpr int kEmitFixed = 0, kCount = 1, kEmitOwn = 2, kCoefs = 3;
 template <int kSamp, int kClass, int kMode>
 __global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, JpegGeom g, QuantArg qa, unsigned char* __restrict__ intbuf, unsigned* __restrict__ int_bytes,
                                                                   const unsigned* __restrict__ codes, unsigned* __restrict__ hist) {
@@ -377,6 +380,20 @@ __global__ __launch_bounds__(kThreads) void jpeg_interval_kernel(PngSrc src, Jpe
         __syncthreads();
     }
 
+    if constexpr (kMode == kCoefs) {
+        // the interval's blocks to their places in the component planes, a dword (two coefficients) per thread and step
+        const jpegprog::Geom pg = jpegprog::geom_of(g.h, g.w, kSamp);
+        unsigned* const planes = reinterpret_cast<unsigned*>(intbuf) + (unsigned long long)img * pg.nblocks * 32ull;
+        const unsigned* const s_qw = s_work + S::kPxWords + kBlocks * kPlane;
+        for (unsigned idx = t; idx < nblk * 32u; idx += kThreads) {
+            const unsigned blk = idx >> 5, m = blk / (unsigned)kPer, j = blk % (unsigned)kPer, mcu = m0 + m, my = mcu / g.mcus_w, mx = mcu - my * g.mcus_w;
+            unsigned comp, by, bx;
+            if (kSamp == 2 && j < 4u) { comp = 0; by = 2 * my + (j >> 1); bx = 2 * mx + (j & 1u); }
+            else { comp = kSamp == 2 ? j - 3u : j; by = my; bx = mx; }
+            planes[((unsigned long long)jpegprog::comp_off(pg, (int)comp) + (unsigned long long)by * jpegprog::y_or_c(pg.cols[0], pg.cols[1], (int)comp) + bx) * 32ull + (idx & 31u)] = s_qw[idx];
+        }
+        return;
+    }
     const unsigned wv = t >> 6, lane = t & 63u;
     if constexpr (kMode == kCount) {
         // 5c. the symbols counted: one wave per block, lane k = zig-zag position k, as the emit pass finds them below
@@ -518,7 +535,7 @@ struct DevWave {
 __global__ __launch_bounds__(jpeghuff::kLanes) void jpeg_table_kernel(const unsigned* hist, unsigned char* bits_vals, int* nvals, unsigned* codes) {
     __shared__ jpeghuff::Work s_work;
     DevWave wv{threadIdx.x};
-    const unsigned long long slot = (unsigned long long)blockIdx.y * 4 + blockIdx.x;
+    const unsigned long long slot = (unsigned long long)blockIdx.y * gridDim.x + blockIdx.x;      // (4 tables per image, or the progressive path's 10)
     jpeghuff::build_table(wv, s_work, hist + slot * 256, bits_vals + slot * jpeghuff::kBitsVals, nvals + slot, codes ? codes + slot * 256 : nullptr);
 }
 
@@ -647,6 +664,27 @@ void encode_jpeg_base64_launch(const unsigned char* d_rgb, int n, int h, int w, 
     hipLaunchKernelGGL(jpeg_gather_kernel<false>, grid, dim3(kThreads), 0, s, g, jpeg_header(h, w, quality, sampling), intbuf, int_bytes, files, (unsigned long long)L.file_pitch, flen,
                        d_lens, (unsigned long long)lens_pitch, no_tables, no_nvals);
     base64_device_length_launch(files, L.file_pitch, flen, (size_t)g.file_bound, n, d_chars, text_pitch, s);
+    IRE_HIP(hipGetLastError());
+}
+
+// The progressive path's coefficient pass (jpeg_progenc.hip): the front end of K1 alone, one workgroup per 48 blocks in MCU order
+void jpeg_coefs_launch(const unsigned char* d_rgb, int n, int h, int w, size_t row_pitch, size_t image_pitch, int quality, int sampling, short* d_coefs, hipStream_t s) {
+    if (n < 1 || n > 65535 || h <= 0 || w <= 0 || h > 8192 || w > 8192) fail(IRE_ERR_INVALID_INPUT, "invalid image size for the JPEG encoder (1..8192 per side)");
+    if (row_pitch < (size_t)3 * w) fail(IRE_ERR_INVALID_INPUT, "invalid row pitch for the JPEG encoder (< 3*w)");
+    const JpegGeom g = geom_of(h, w, quality, sampling, false);
+    const PngSrc src{d_rgb, (unsigned long long)row_pitch, (unsigned long long)image_pitch};
+    const QuantArg qa = make_quant(quality);
+    unsigned* no_u = nullptr;
+    const unsigned* no_codes = nullptr;
+    unsigned char* planes = reinterpret_cast<unsigned char*>(d_coefs);
+    if (sampling == 2) hipLaunchKernelGGL((jpeg_interval_kernel<2, kClassSmall, kCoefs>), dim3(g.nint, n), dim3(kThreads), 0, s, src, g, qa, planes, no_u, no_codes, no_u);
+    else hipLaunchKernelGGL((jpeg_interval_kernel<0, kClassSmall, kCoefs>), dim3(g.nint, n), dim3(kThreads), 0, s, src, g, qa, planes, no_u, no_codes, no_u);
+    IRE_HIP(hipGetLastError());
+}
+
+// The table kernel on ntab histograms per image, with the code arrays (the progressive path: ntab = 10)
+void jpeg_tables_launch(const unsigned* d_counts, int ntab, int n, unsigned char* d_bits_vals, int* d_nvals, unsigned* d_codes, hipStream_t s) {
+    hipLaunchKernelGGL(jpeg_table_kernel, dim3(ntab, n), dim3(jpeghuff::kLanes), 0, s, d_counts, d_bits_vals, d_nvals, d_codes);
     IRE_HIP(hipGetLastError());
 }
 

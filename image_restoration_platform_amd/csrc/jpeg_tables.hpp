@@ -14,6 +14,7 @@
 #include <initializer_list>
 
 #include "jpeg_huff_core.hpp"
+#include "jpeg_progenc_core.hpp"
 
 namespace ire {
 namespace jpegtab {
@@ -259,6 +260,50 @@ inline size_t jpeg_header_opt(int h, int w, int quality, int sampling, const uns
     return n;
 }
 static_assert(jpeghuff::kHeadFixedBytes == (unsigned)kHeaderBytes, "one head length");
+
+// ---- progressive files (jpeg_progenc_core.hpp): the bound ---------------------------------------------------------------------------
+// Ten scans, each under a table of its own, so a code has at most 16 bits.  Per scan and block:
+//   DC first        16 + the largest category of a difference of two SHIFTED DCs: the quantised DC lies in -A..B (step 2), the
+//                   shifted one in -ceil(A / 2^Al)..floor(B / 2^Al)
+//   DC refinement   1 bit
+//   AC first        every position of the band at 16 + the largest category of its magnitude after the shift (a ZRL stands for 16 zero
+//                   positions, each priced at 16 or more), and one EOBn symbol with 14 extra bits
+//   AC refinement   every position at 16 + 1 (the sign) + 1 (a correction bit), and one EOBn symbol with 14 extra bits
+// An interval -- one block row of the scan -- is its blocks' bits rounded up to bytes, doubled for the stuffing, and 2 bytes of
+// marker.  A scan's head is at most two DHT segments of 16 + 256 entries, a DRI and a three-component SOS.  The bound sizes the
+// interval stride, the file's place and the public bound; ByteSink writes nothing beyond it.
+constexpr unsigned kProgScanHeadMax = 2 * (5 + 16 + 256) + 6 + 14, kProgEobnBits = 16 + 14;
+inline unsigned prog_block_bits(int scan, int comp, int quality) {
+    const jpegprog::Scan sc = jpegprog::scan_of(scan);
+    const int table = comp ? 1 : 0;
+    if (sc.ss == 0) {
+        if (sc.ah) return 1;
+        const unsigned q = (unsigned)quant_at(table, 0, quality);
+        const unsigned a = (kDcNegMax + 4u * q) / (8u * q), b = (kDcPosMax + 4u * q) / (8u * q), r = (1u << sc.al) - 1u;
+        return 16u + (unsigned)bit_length((b >> sc.al) + ((a + r) >> sc.al));
+    }
+    if (sc.ah) return (unsigned)(sc.se - sc.ss + 1) * 18u + kProgEobnBits;
+    unsigned bits = kProgEobnBits;
+    for (int k = sc.ss; k <= sc.se; ++k) {
+        const int nat = kZigzag[k];
+        const unsigned q = (unsigned)quant_at(table, nat, quality);
+        bits += 16u + (unsigned)bit_length(((coef_bound(nat) + 4u * q) / (8u * q)) >> sc.al);
+    }
+    return bits;
+}
+inline size_t prog_interval_bound(const jpegprog::Geom& g, int quality, int scan) {
+    const jpegprog::Scan sc = jpegprog::scan_of(scan);
+    const size_t bits = sc.ncomp == 3 ? (size_t)g.mw * ((g.sampling == 2 ? 4u : 1u) * prog_block_bits(scan, 0, quality) + 2u * prog_block_bits(scan, 1, quality))
+                                      : (size_t)g.ocols[sc.comp] * prog_block_bits(scan, sc.comp, quality);
+    return 2 * ((bits + 7) / 8) + 2;
+}
+inline size_t jpeg_prog_file_bound(int h, int w, int quality, int sampling) {
+    const jpegprog::Geom g = jpegprog::geom_of(h, w, sampling);
+    size_t n = jpegprog::kFixedHead + 2;
+    for (int s = 0; s < jpegprog::kScans; ++s) n += kProgScanHeadMax + (size_t)jpegprog::scan_rows(g, s) * prog_interval_bound(g, quality, s);
+    return n;
+}
+inline size_t jpeg_prog_base64_bound(int h, int w, int quality, int sampling) { return (jpeg_prog_file_bound(h, w, quality, sampling) + 2) / 3 * 4; }
 
 }  // namespace jpegtab
 }  // namespace ire

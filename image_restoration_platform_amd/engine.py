@@ -19,7 +19,8 @@ FAMILIES = ["classifier", "conv3x3", "conv1x1", "stem", "head", "gn_finalize", "
 # One row per text format (csrc/codec.hpp TextFormat): the engine flag that selects it for the batcher's results, the ABI's host and
 # device entry, the Engine method that gives its bound, the noun of its messages, whether a uint64 count goes with every text, and what
 # the entries' names end in where they take the format's settings.  "jpeg_opt" is no result format of its own (flag 0): it is "jpeg"
-# with the image's own Huffman tables, chosen by IRE_FLAG_JPEG_OPTIMIZE beside IRE_FLAG_RESULT_JPEG or by optimize=True in a call.
+# with the image's own Huffman tables, chosen by IRE_FLAG_JPEG_OPTIMIZE beside IRE_FLAG_RESULT_JPEG or by optimize=True in a call;
+# "jpeg_prog" likewise: "jpeg" as a progressive file, chosen by IRE_FLAG_JPEG_PROGRESSIVE or by progressive=True in a call.
 TextFormat = collections.namedtuple("TextFormat", "flag host device bound noun counted ex", defaults=("_ex",))
 TEXT_FORMATS = {
     "png": TextFormat(_lib.IRE_FLAG_RESULT_PNG_BASE64, "ire_encode_png_base64_fit", "ire_encode_png_base64_fit_device", "png_base64_bytes_fit", "PNG", False),
@@ -27,6 +28,7 @@ TEXT_FORMATS = {
                               "png_deflate_base64_bound", "PNG", True),
     "jpeg": TextFormat(_lib.IRE_FLAG_RESULT_JPEG, "ire_encode_jpeg_base64_fit", "ire_encode_jpeg_base64_fit_device", "jpeg_base64_bound", "JPEG", True),
     "jpeg_opt": TextFormat(0, "ire_encode_jpeg_optimized_base64_fit", "ire_encode_jpeg_optimized_base64_fit_device", "_jpeg_optimized_base64_bound", "JPEG", True, ""),
+    "jpeg_prog": TextFormat(0, "ire_encode_jpeg_progressive_base64_fit", "ire_encode_jpeg_progressive_base64_fit_device", "_jpeg_progressive_base64_bound", "JPEG", True, ""),
 }
 
 
@@ -501,33 +503,44 @@ class Engine:
         q0, s0 = getattr(self, "_jpeg_settings", (0, 0))
         return (q0 if quality is None else int(quality), s0 if sampling is None else int(sampling))
 
-    def _jpeg_fmt(self, optimize):
-        """"jpeg_opt" | "jpeg": what the call names, else this engine's own setting (IRE_FLAG_JPEG_OPTIMIZE)"""
-        own = bool(getattr(self, "_flags", 0) & _lib.IRE_FLAG_JPEG_OPTIMIZE)
+    def _jpeg_fmt(self, optimize, progressive=None):
+        """"jpeg_prog" | "jpeg_opt" | "jpeg": what the call names, else this engine's own setting (IRE_FLAG_JPEG_PROGRESSIVE,
+        IRE_FLAG_JPEG_OPTIMIZE); progressive wins: such a file's tables are always its own"""
+        flags = getattr(self, "_flags", 0)
+        if bool(flags & _lib.IRE_FLAG_JPEG_PROGRESSIVE) if progressive is None else bool(progressive):
+            return "jpeg_prog"
+        own = bool(flags & _lib.IRE_FLAG_JPEG_OPTIMIZE)
         return "jpeg_opt" if (own if optimize is None else bool(optimize)) else "jpeg"
+
+    def _jpeg_progressive_base64_bound(self, h, w, quality, sampling):
+        return int(self._lib.ire_jpeg_progressive_base64_bound(int(h), int(w), int(quality), int(sampling)))
 
     def _jpeg_optimized_base64_bound(self, h, w, quality, sampling):
         return int(self._lib.ire_jpeg_optimized_base64_bound(int(h), int(w), int(quality), int(sampling)))
 
-    def jpeg_base64_bound(self, h, w, quality=None, sampling=None, optimize=None):
+    def jpeg_base64_bound(self, h, w, quality=None, sampling=None, optimize=None, progressive=None):
         """The most characters the JPEG encoder can give for an h x w image at a quality (1..100) and sampling (0 = 4:4:4, 2 = 4:2:0),
-        with the fixed Huffman tables or (optimize=True: a larger bound) the image's own; left out: this engine's settings.  0 outside
-        1..8192 or for settings the encoder refuses.  Sizes every buffer."""
-        if self._jpeg_fmt(optimize) == "jpeg_opt":
+        with the fixed Huffman tables, (optimize=True: a larger bound) the image's own, or (progressive=True: larger again) as a
+        progressive file; left out: this engine's settings.  0 outside 1..8192 or for settings the encoder refuses.  Sizes every buffer."""
+        fmt = self._jpeg_fmt(optimize, progressive)
+        if fmt == "jpeg_prog":
+            return self._jpeg_progressive_base64_bound(h, w, *self._jpeg_ex(quality, sampling))
+        if fmt == "jpeg_opt":
             return self._jpeg_optimized_base64_bound(h, w, *self._jpeg_ex(quality, sampling))
         return int(self._lib.ire_jpeg_base64_bound_ex(int(h), int(w), *self._jpeg_ex(quality, sampling)))
 
-    def encode_jpeg_base64_fit(self, rgb, quality=None, sampling=None, optimize=None):
+    def encode_jpeg_base64_fit(self, rgb, quality=None, sampling=None, optimize=None, progressive=None):
         """[N,H,W,3] (or [H,W,3]) uint8, any size 1..8192 per side -> list of N `bytes` (one for a single image): the base64 text of a
         baseline JPEG file of each image, encoded on the device; each of its real length.  quality 1..100 and sampling 0 = 4:4:4 |
-        2 = 4:2:0; optimize: the file carries the image's own Huffman tables (smaller, the same pixels); left out: this engine's
-        settings (quality 85, 4:4:4, the fixed tables unless it was created with others)."""
-        return self._encode_fit(self._jpeg_fmt(optimize), rgb, self._jpeg_ex(quality, sampling))
+        2 = 4:2:0; optimize: the file carries the image's own Huffman tables (smaller, the same pixels); progressive: the file is a
+        progressive one, ten scans each under its own table (smaller again, the same pixels); left out: this engine's settings
+        (quality 85, 4:4:4, the fixed tables unless it was created with others)."""
+        return self._encode_fit(self._jpeg_fmt(optimize, progressive), rgb, self._jpeg_ex(quality, sampling))
 
-    def encode_jpeg_base64_fit_tensor(self, rgb_u8, stream=None, quality=None, sampling=None, optimize=None):
+    def encode_jpeg_base64_fit_tensor(self, rgb_u8, stream=None, quality=None, sampling=None, optimize=None, progressive=None):
         """cuda uint8 [N,h,w,3], possibly a window of a larger tensor -> (cuda uint8 [N, bound] ASCII, cuda int64 [N] character counts),
-        asynchronous on the stream: text i is out[i, :lens[i]].  quality, sampling, optimize: as for encode_jpeg_base64_fit."""
-        return self._encode_fit_tensor(self._jpeg_fmt(optimize), rgb_u8, stream, self._jpeg_ex(quality, sampling))
+        asynchronous on the stream: text i is out[i, :lens[i]].  quality, sampling, optimize, progressive: as for encode_jpeg_base64_fit."""
+        return self._encode_fit_tensor(self._jpeg_fmt(optimize, progressive), rgb_u8, stream, self._jpeg_ex(quality, sampling))
 
     def debug_jpeg_huffman(self, counts):
         """[n][4][256] symbol counts -> (bits_vals uint8 [n][4][272], nvals int32 [n][4]): the tables the optimised JPEG path's table
@@ -538,6 +551,18 @@ class Engine:
         nv = np.zeros((c.shape[0], 4), np.int32)
         self._check(self._lib.ire_debug_jpeg_huffman(self._h, _ptr(c), c.shape[0], _ptr(bv), _ptr(nv)))
         return bv, nv
+
+    def debug_jpeg_progressive_from_coefs(self, coefs, h, w, quality, sampling):
+        """[n][blocks][64] int16 coefficients (the layout ire.h gives) -> list of n `bytes`: the progressive files the device makes of
+        them, without its coefficient pass (tests only)"""
+        c = np.ascontiguousarray(coefs, np.int16)
+        assert c.ndim == 3 and c.shape[2] == 64
+        n = c.shape[0]
+        stride = (self._jpeg_progressive_base64_bound(h, w, quality, sampling) // 4 * 3 + 15) // 16 * 16
+        out = np.empty((n, stride), np.uint8)
+        lens = np.zeros(n, np.uint64)
+        self._check(self._lib.ire_debug_jpeg_progressive_from_coefs(self._h, _ptr(c), n, int(h), int(w), int(quality), int(sampling), _ptr(out), stride, _ptr(lens)))
+        return [out[i, :int(lens[i])].tobytes() for i in range(n)]
 
     # ---- JPEG uploads decoded on the device (csrc/jpeg_parse.hpp, csrc/jpeg_dec.hip) -------------------------------------------
     @property

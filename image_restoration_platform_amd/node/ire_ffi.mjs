@@ -66,6 +66,10 @@ export function bindIre(libPath) {
     ire_jpeg_optimized_base64_bound: ['size_t', ['int', 'int', 'int', 'int']],
     ire_encode_jpeg_optimized_base64_fit_device: ['int', [P, P, 'int', 'int', 'int', 'size_t', 'size_t', P, 'size_t', P, 'int', 'int', P]],
     ire_encode_jpeg_optimized_base64_fit: ['int', [P, P, 'int', 'int', 'int', P, 'size_t', P, 'int', 'int']],
+    // (the same as a progressive file: ten scans, each under its own optimal table)
+    ire_jpeg_progressive_base64_bound: ['size_t', ['int', 'int', 'int', 'int']],
+    ire_encode_jpeg_progressive_base64_fit_device: ['int', [P, P, 'int', 'int', 'int', 'size_t', 'size_t', P, 'size_t', P, 'int', 'int', P]],
+    ire_encode_jpeg_progressive_base64_fit: ['int', [P, P, 'int', 'int', 'int', P, 'size_t', P, 'int', 'int']],
     ire_decode_jpeg_plan: ['int', [P, 'size_t', P, P, P]],
     // (accept is a uint32_t of flag bits, 0 or 1 today: passed as an int)
     ire_decode_jpeg_plan_ex: ['int', [P, 'size_t', 'int', P, P, P, P]],
@@ -91,6 +95,7 @@ export function bindIre(libPath) {
     ire_debug_classifier_sums: ['int', [P, 'int', P]],
     ire_debug_fusion_wlut: ['int', [P, P, 'int', P]],
     ire_debug_jpeg_huffman: ['int', [P, P, 'int', P, P]],
+    ire_debug_jpeg_progressive_from_coefs: ['int', [P, P, 'int', 'int', 'int', 'int', 'int', P, 'size_t', P]],
     ire_debug_capture: ['int', [P, 'int']],
     ire_debug_activation: ['int', [P, 'string', P, P]],
     ire_profile_enable: ['int', [P, 'int']],

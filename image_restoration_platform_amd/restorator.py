@@ -101,15 +101,21 @@ def encode_jpeg_base64(rgb, quality=85):
 #               written by the GPU (csrc/jpeg.hip): no host codec work, and the shortest string; the engine flag is
 #               IRE_FLAG_RESULT_JPEG.  IRE_JPEG_QUALITY (1..100) and IRE_JPEG_SUBSAMPLING (0 = 4:4:4, 2 = 4:2:0) choose the file's
 #               settings; unset: quality 85 at 4:4:4, the reference's settings.  IRE_JPEG_OPTIMIZE=1: every file carries its image's
-#               own Huffman tables (IRE_FLAG_JPEG_OPTIMIZE), as the reference's mozjpeg encode does: a shorter string, the same pixels
+#               own Huffman tables (IRE_FLAG_JPEG_OPTIMIZE), as the reference's mozjpeg encode does: a shorter string, the same pixels.
+#               IRE_JPEG_PROGRESSIVE=1: every file is a progressive one (IRE_FLAG_JPEG_PROGRESSIVE), the form mozjpeg writes: ten scans,
+#               each under its own table -- shorter again, the same pixels
 RESULT_CODEC = os.environ.get("IRE_RESULT_CODEC", "png")
 JPEG_SETTINGS = (int(os.environ.get("IRE_JPEG_QUALITY") or 0), int(os.environ.get("IRE_JPEG_SUBSAMPLING") or 0))      # (0: the default)
 JPEG_OPTIMIZE = (os.environ.get("IRE_JPEG_OPTIMIZE") or "0") not in ("0", "")
+JPEG_PROGRESSIVE = (os.environ.get("IRE_JPEG_PROGRESSIVE") or "0") not in ("0", "")
 
 
 def jpeg_engine_flags(result_codec=None):
-    """IRE_FLAG_JPEG_OPTIMIZE where IRE_JPEG_OPTIMIZE asks for it and the codec value's engine flag allows it, to be or-ed to that flag."""
-    return _lib.IRE_FLAG_JPEG_OPTIMIZE if JPEG_OPTIMIZE and (result_codec or RESULT_CODEC) == "jpeg-device" else 0
+    """IRE_FLAG_JPEG_OPTIMIZE and IRE_FLAG_JPEG_PROGRESSIVE where IRE_JPEG_OPTIMIZE / IRE_JPEG_PROGRESSIVE ask for them and the codec
+    value's engine flag allows them, to be or-ed to that flag."""
+    if (result_codec or RESULT_CODEC) != "jpeg-device":
+        return 0
+    return (_lib.IRE_FLAG_JPEG_OPTIMIZE if JPEG_OPTIMIZE else 0) | (_lib.IRE_FLAG_JPEG_PROGRESSIVE if JPEG_PROGRESSIVE else 0)
 
 
 def jpeg_engine_kwargs(result_codec=None):
@@ -177,7 +183,7 @@ class EngineRestorer:
             return self.engine.encode_png_deflate_base64_fit(result).decode("ascii")
         if self.result_codec == "jpeg-device":      # a JPEG engine's own settings; on any other engine the environment's
             own = getattr(self.engine, "_flags", 0) & _lib.IRE_FLAG_RESULT_JPEG
-            return self.engine.encode_jpeg_base64_fit(result, *((None, None, None) if own else JPEG_SETTINGS + (JPEG_OPTIMIZE,))).decode("ascii")
+            return self.engine.encode_jpeg_base64_fit(result, *((None, None, None, None) if own else JPEG_SETTINGS + (JPEG_OPTIMIZE, JPEG_PROGRESSIVE))).decode("ascii")
         return encode_png_base64(result)
 
     @staticmethod

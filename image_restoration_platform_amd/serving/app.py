@@ -47,7 +47,7 @@ def get_service():
                 # IRE_RESULT_CODEC=png-device: the batcher returns the base64 text of a device-encoded PNG (csrc/encode.hip)
                 # IRE_RESULT_CODEC=png-deflate-device: the text of a compressed PNG (csrc/deflate.hip), fetched with ire_poll_text
                 # IRE_RESULT_CODEC=jpeg-device: the text of a baseline JPEG (csrc/jpeg.hip) at IRE_JPEG_QUALITY and IRE_JPEG_SUBSAMPLING
-                # (unset: quality 85 at 4:4:4), with optimised Huffman tables where IRE_JPEG_OPTIMIZE=1, fetched with ire_poll_text
+                # (unset: quality 85 at 4:4:4), with optimised Huffman tables where IRE_JPEG_OPTIMIZE=1, as progressive files where IRE_JPEG_PROGRESSIVE=1, fetched with ire_poll_text
                 eng = Engine(device_index=0, max_batch=8, flags={"png-device": 1, "png-deflate-device": 4, "jpeg-device": 8}.get(RESULT_CODEC, 0) | jpeg_engine_flags(),
                              **jpeg_engine_kwargs())
             except Exception as e:  # noqa: BLE001 -- EngineError or a missing library

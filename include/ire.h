@@ -108,6 +108,13 @@ typedef struct ire_config {
  * ire_jpeg_optimized_base64_bound(h, w, quality, sampling) bytes, which is larger than ire_jpeg_base64_bound_ex's.  (Bit values 2,
  * 16 and 64 stay unknown.) */
 #define IRE_FLAG_JPEG_OPTIMIZE 128u
+/* Not a result format: valid only together with IRE_FLAG_RESULT_JPEG (else ire_init fails, "invalid ... IRE_FLAG_RESULT_JPEG").
+ * Every JPEG result is a PROGRESSIVE file (ire_encode_jpeg_progressive_base64_fit_device below): the same quantised coefficients as
+ * libjpeg's ten jpeg_simple_progression scans, each under its own optimal Huffman table -- a text some 4 - 8 % shorter than the
+ * optimised baseline one, decoding to the same pixels.  Such a result is fetched with ire_poll_text into a buffer of
+ * ire_jpeg_progressive_base64_bound(h, w, quality, sampling) bytes.  IRE_FLAG_JPEG_OPTIMIZE beside it is allowed and changes nothing
+ * (a progressive file's tables are always its own).  (Bit values 2, 16, 64 and 512 stay unknown.) */
+#define IRE_FLAG_JPEG_PROGRESSIVE 2048u
 /* Not a result format, and free to combine with every other flag: UPLOAD jobs (ire_submit_upload) convert the pixels of a file that
  * carries an ICC profile (Display P3, Adobe RGB, ...) to sRGB on the device, between the decode and the preprocess step -- the third
  * operation of the reference's preprocess, .withMetadata({ icc: 'sRGB' }) (imagePreprocess.js:57-66).  See ire_icc_plan_file below for
@@ -303,6 +310,26 @@ int ire_encode_jpeg_optimized_base64_fit_device(ire_engine* e, const uint8_t* d_
                                                 uint64_t* d_lens /* n x uint64, device */, int quality, int sampling, void* stream);
 int ire_encode_jpeg_optimized_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes,
                                          uint64_t* lens /* n x uint64, host */, int quality, int sampling);
+/* The same three as a PROGRESSIVE file (SOF2): the image's quantised coefficients -- those of the entries above, from the same front
+ * end, computed once and kept in device scratch (128 bytes per 8 x 8 block) -- sent as the ten scans of libjpeg's
+ * jpeg_simple_progression for Y Cb Cr: DC of all three components interleaved at Al = 1; Y 1-5 at Al = 2; Cr 1-63 and Cb 1-63 at
+ * Al = 1; Y 6-63 at Al = 2; Y 1-63 refined to Al = 1; the DC refinement to Al = 0; Cr, Cb and Y 1-63 refined to Al = 0.  Every scan
+ * that uses Huffman codes is preceded by a DHT with its own optimal table (ten tables per image, built on the device as the optimised
+ * entries build theirs), and the restart interval is one MCU row of the scan (a DRI wherever it changes), which is the unit the device
+ * codes in parallel: end-of-band runs and buffered correction bits cross blocks but never a restart.  The bytes equal libjpeg-turbo's
+ * for Pillow's save(quality=, subsampling=, progressive=True, restart_marker_rows=1) (tests/test_jpeg_progenc_model.py) and decode to
+ * the pixels the baseline file decodes to; the engine's own decoder reads them back under IRE_FLAG_DECODE_PROGRESSIVE.  Integer
+ * work and fixed-order sums throughout: the text is a pure function of the pixels and the two settings.  Arguments, refusals and the
+ * asynchronous, windowed device form are those of the _optimized_ entries.  The bound prices, per scan and block, every code at 16
+ * bits, the largest category the quantiser can yield after the scan's shift, one EOBn symbol with 14 extra bits and one correction
+ * bit per refined coefficient, doubles that for byte stuffing and adds 2 marker bytes per interval and the largest head per scan
+ * (csrc/jpeg_tables.hpp: jpeg_prog_file_bound); nothing is ever written beyond it. */
+size_t ire_jpeg_progressive_base64_bound(int h, int w, int quality, int sampling);
+int ire_encode_jpeg_progressive_base64_fit_device(ire_engine* e, const uint8_t* d_rgb, int n, int h, int w, size_t row_pitch_bytes,
+                                                  size_t image_pitch_bytes, uint8_t* d_chars, size_t stride_bytes,
+                                                  uint64_t* d_lens /* n x uint64, device */, int quality, int sampling, void* stream);
+int ire_encode_jpeg_progressive_base64_fit(ire_engine* e, const uint8_t* rgb, int n, int h, int w, uint8_t* chars, size_t stride_bytes,
+                                           uint64_t* lens /* n x uint64, host */, int quality, int sampling);
 
 /* ---- baseline JPEG uploads decoded on the device ----
  * The RGB bytes equal libjpeg-turbo's (PIL.Image.open(f).convert("RGB")): the file's own Huffman tables, libjpeg's "islow" inverse
@@ -584,6 +611,13 @@ int ire_debug_fusion_wlut(ire_engine* e, const double* noise, int n, uint32_t* o
  * code).  n in 1..4096 (tests only). */
 int ire_debug_jpeg_huffman(ire_engine* e, const uint32_t* counts /* [n][4][256] */, int n, uint8_t* bits_vals_out /* [n][4][16 + 256] */,
                            int32_t* nvals_out /* [n][4] */);
+/* The progressive JPEG path behind its coefficient pass (count pass, table kernel, emit pass, gather) on coefficients given: per
+ * image [blocks][64] int16 in zig-zag order, component after component, a component's blocks in raster order -- at 4:4:4 ceil(h/8) x
+ * ceil(w/8) blocks per component; at 4:2:0 Y on the MCU grid (2 ceil(h/16) x 2 ceil(w/16), dummy blocks included) and Cb, Cr
+ * ceil(h/16) x ceil(w/16).  out_files receives n FILES (not base64) `stride` bytes apart, stride at least
+ * ire_jpeg_progressive_base64_bound(h, w, quality, sampling) / 4 * 3, and lens their lengths.  n in 1..max_batch (tests only). */
+int ire_debug_jpeg_progressive_from_coefs(ire_engine* e, const int16_t* coefs, int n, int h, int w, int quality, int sampling,
+                                          uint8_t* out_files, size_t stride, uint64_t* lens /* n x uint64, host */);
 /* Turn per-layer capture on/off (slow: synchronises after every layer; tests only). */
 int ire_debug_capture(ire_engine* e, int on);
 /* Copy one named intermediate activation of the last ire_restore* call to host as float32 NHWC.

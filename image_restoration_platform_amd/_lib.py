@@ -14,9 +14,11 @@ IRE_FLAG_JPEG_OPTIMIZE = 128
 IRE_FLAG_JPEG_PROGRESSIVE = 2048
 IRE_FLAG_UPLOAD_ICC = 256
 IRE_FLAG_DECODE_PNG = 1024
+IRE_FLAG_DECODE_PNG_ALL = 8192
 IRE_DECODE_ACCEPT_PROGRESSIVE = 1
 IRE_DECODE_ACCEPT_ICC = 4
 IRE_DECODE_ACCEPT_PNG = 16
+IRE_DECODE_ACCEPT_PNG_ALL = 32
 IRE_ICC_NONE, IRE_ICC_IDENTITY, IRE_ICC_MATRIX, IRE_ICC_GREY = range(4)
 IRE_DECODE_MAX_SCANS = 64
 IRE_ABI_VERSION = 3      # include/ire.h; load() refuses a library of another version (tests/test_abi.py cross-checks the three copies)
@@ -102,6 +104,7 @@ SYMBOLS = {
     "ire_decode_jpeg": (_i, [_vp, _u8p, ctypes.c_size_t, _u8p, _i, _i]),
     "ire_decode_jpeg_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp, _vp]),
     "ire_decode_png_plan": (_i, [_u8p, ctypes.c_size_t, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "ire_decode_png_plan_ex": (_i, [_u8p, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "ire_decode_png": (_i, [_vp, _u8p, ctypes.c_size_t, _u8p, _i, _i]),
     "ire_decode_png_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, ctypes.c_size_t, _vp, _vp]),
     "ire_submit_fit": (_i, [_vp, _u8p, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),

@@ -173,7 +173,7 @@ struct HipBatchBackend {
         std::string why;
         if (E.png_decoder().enabled() && pngparse::is_png(file, bytes)) {      // (an engine without the flag goes on and refuses it as a JPEG parser does)
             auto head = std::make_shared<PngFileHead>();
-            if (!pngparse::plan_file(file, bytes, png_flags, head->f, why)) fail(IRE_ERR_INVALID_INPUT, why);
+            if (!pngparse::plan_file(file, bytes, png_flags | E.png_decoder().accept(), head->f, why)) fail(IRE_ERR_INVALID_INPUT, why);
             *h = head->f.h; *w = head->f.w;
             *room = head->f.idat_bytes;
             return head;
@@ -551,12 +551,13 @@ int ire_preprocess_batch_device(ire_engine* e, const uint8_t* d_rgb, int n, int 
 int ire_upload_plan(const uint8_t* file, size_t bytes, uint32_t accept, int max_dim, int* stored_h, int* stored_w, int* orientation, int* out_h, int* out_w) {
     return guarded([&] {
         if (!file) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_upload_plan: null file");
-        if (accept & ~(uint32_t)(IRE_DECODE_ACCEPT_PROGRESSIVE | IRE_DECODE_ACCEPT_ICC | IRE_DECODE_ACCEPT_PNG)) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_upload_plan: unknown accept bits");
+        if (accept & ~(uint32_t)(IRE_DECODE_ACCEPT_PROGRESSIVE | IRE_DECODE_ACCEPT_ICC | IRE_DECODE_ACCEPT_PNG | IRE_DECODE_ACCEPT_PNG_ALL)) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_upload_plan: unknown accept bits");
+        if ((accept & IRE_DECODE_ACCEPT_PNG_ALL) && !(accept & IRE_DECODE_ACCEPT_PNG)) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_upload_plan: IRE_DECODE_ACCEPT_PNG_ALL set without IRE_DECODE_ACCEPT_PNG");
         jpegparse::File f;
         std::string why;
         if ((accept & IRE_DECODE_ACCEPT_PNG) && pngparse::is_png(file, bytes)) {
             pngparse::File p;
-            if (!pngparse::plan_file(file, bytes, (accept & IRE_DECODE_ACCEPT_ICC) ? pngparse::kRefuseIccp : 0u, p, why)) fail(IRE_ERR_INVALID_INPUT, why);
+            if (!pngparse::plan_file(file, bytes, ((accept & IRE_DECODE_ACCEPT_ICC) ? pngparse::kRefuseIccp : 0u) | (accept & IRE_DECODE_ACCEPT_PNG_ALL), p, why)) fail(IRE_ERR_INVALID_INPUT, why);
             int ow = 0, oh = 0;
             preprocess_plan(p.w, p.h, p.orientation, max_dim, &ow, &oh, nullptr);
             if (!piece_addressable(Engine::fit_dim(oh), Engine::fit_dim(ow), 0)) fail(IRE_ERR_INVALID_INPUT, not_addressable(Engine::fit_dim(oh), Engine::fit_dim(ow)));
@@ -809,6 +810,7 @@ int ire_decode_jpeg_device(ire_engine* e, const uint8_t* const* files, const siz
 }
 
 static_assert(IRE_DECODE_ACCEPT_ICC == pngparse::kRefuseIccp, "ire.h and png_parse.hpp");
+static_assert(IRE_DECODE_ACCEPT_PNG_ALL == pngparse::kAcceptAll, "ire.h and png_parse.hpp");
 
 int ire_decode_png_plan(const uint8_t* file, size_t bytes, int* out_h, int* out_w, int* out_colour_type) {
     return guarded([&] {
@@ -819,6 +821,21 @@ int ire_decode_png_plan(const uint8_t* file, size_t bytes, int* out_h, int* out_
         if (out_h) *out_h = f.h;
         if (out_w) *out_w = f.w;
         if (out_colour_type) *out_colour_type = f.ctype;
+    });
+}
+
+int ire_decode_png_plan_ex(const uint8_t* file, size_t bytes, uint32_t accept, int* out_h, int* out_w, int* out_colour_type, int* out_depth, int* out_interlace) {
+    return guarded([&] {
+        if (!file) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_decode_png_plan_ex: null file");
+        if (accept & ~(uint32_t)IRE_DECODE_ACCEPT_PNG_ALL) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_decode_png_plan_ex: unknown accept bits");
+        pngparse::File f;
+        std::string why;
+        if (!pngparse::plan_file(file, bytes, accept, f, why)) fail(IRE_ERR_INVALID_INPUT, why);
+        if (out_h) *out_h = f.h;
+        if (out_w) *out_w = f.w;
+        if (out_colour_type) *out_colour_type = f.ctype;
+        if (out_depth) *out_depth = f.depth;
+        if (out_interlace) *out_interlace = f.interlace;
     });
 }
 

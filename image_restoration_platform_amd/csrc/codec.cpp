@@ -41,8 +41,10 @@ const TextFormat kJpeg = {"JPEG",
 
 void check_config_flags(uint32_t flags) {
     constexpr uint32_t kResultBits = IRE_FLAG_RESULT_PNG_BASE64 | IRE_FLAG_RESULT_PNG_DEFLATE | IRE_FLAG_RESULT_JPEG;
-    if (flags & ~(kResultBits | IRE_FLAG_DECODE_PROGRESSIVE | IRE_FLAG_JPEG_OPTIMIZE | IRE_FLAG_UPLOAD_ICC | IRE_FLAG_DECODE_PNG | IRE_FLAG_JPEG_PROGRESSIVE)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
+    if (flags & ~(kResultBits | IRE_FLAG_DECODE_PROGRESSIVE | IRE_FLAG_JPEG_OPTIMIZE | IRE_FLAG_UPLOAD_ICC | IRE_FLAG_DECODE_PNG | IRE_FLAG_JPEG_PROGRESSIVE | IRE_FLAG_DECODE_PNG_ALL)) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (unknown bits set)");
     if (((flags & kResultBits) & ((flags & kResultBits) - 1)) != 0) fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags (two result formats set)");
+    if ((flags & IRE_FLAG_DECODE_PNG_ALL) && !(flags & IRE_FLAG_DECODE_PNG))
+        fail(IRE_ERR_INVALID_INPUT, "invalid ire_config.flags: IRE_FLAG_DECODE_PNG_ALL set without IRE_FLAG_DECODE_PNG");
 }
 
 const TextFormat* result_format_of(uint32_t flags) {
@@ -318,8 +320,8 @@ void JpegDecoder::decode_host(const uint8_t* file, size_t bytes, uint8_t* out_rg
 
 // ---- the PNG decoder (png_parse.hpp on the host, png_dec.hip on the device) ---------------------------------------------------------------
 
-void PngDecoder::setup(int max_batch, bool enabled, hipStream_t main_stream) {
-    max_batch_ = max_batch; enabled_ = enabled; main_stream_ = main_stream;
+void PngDecoder::setup(int max_batch, bool enabled, bool accept_all, hipStream_t main_stream) {
+    max_batch_ = max_batch; enabled_ = enabled; accept_ = accept_all ? pngparse::kAcceptAll : 0u; main_stream_ = main_stream;
     if (const char* v = std::getenv("IRE_PNG_DEC_TIMES")) times_ = std::atoi(v) != 0;
 }
 
@@ -359,7 +361,9 @@ void PngDecoder::run(Scratch& S, int turn, const PngDecLayout& L, size_t pin_byt
                      int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s) {
     const bool own = &S == &own_, timed = own && times_;
     // the scanlines of a whole batch of four-byte pixels: the first batch of a shape allocates, later ones of any colour types do not
-    const size_t scan_full = (((size_t)h * (1 + (size_t)w * 4) + 15) & ~(size_t)15) * (size_t)max_batch_;
+    // (with kAcceptAll the largest form is interlaced 16-bit RGBA: eight-byte pixels and seven passes' filter bytes)
+    const size_t scan_one = accept_ ? (size_t)pngdec::scan_total((uint32_t)h, (uint32_t)w, 6, 16, 1) : (size_t)h * (1 + (size_t)w * 4);
+    const size_t scan_full = ((scan_one + 15) & ~(size_t)15) * (size_t)max_batch_;
     if (L.total > S.d_in.bytes() || L.scan_bytes > S.d_scan.bytes()) IRE_HIP(own ? hipDeviceSynchronize() : hipStreamSynchronize(s));
     S.d_in.grow(L.total, L.total + L.total / 2);
     S.d_scan.grow(L.scan_bytes, batch_room(L.scan_bytes, scan_full));
@@ -390,7 +394,7 @@ void PngDecoder::decode_files(const uint8_t* const* files, const size_t* bytes, 
     std::vector<size_t> rooms((size_t)n);
     for (int i = 0; i < n; ++i) {
         std::string why;
-        if (!files[i] || !pngparse::plan_file(files[i], bytes[i], 0, hd[(size_t)i], why)) fail(IRE_ERR_INVALID_INPUT, files[i] ? why : "invalid arguments to the PNG decoder: null file");
+        if (!files[i] || !pngparse::plan_file(files[i], bytes[i], accept_, hd[(size_t)i], why)) fail(IRE_ERR_INVALID_INPUT, files[i] ? why : "invalid arguments to the PNG decoder: null file");
         if (hd[(size_t)i].h != h || hd[(size_t)i].w != w) fail(IRE_ERR_INVALID_INPUT, "invalid: the PNG file's size is not the planned h x w");
         hp[(size_t)i] = &hd[(size_t)i]; rooms[(size_t)i] = hd[(size_t)i].idat_bytes;
     }
@@ -436,7 +440,7 @@ void PngDecoder::decode_host(const uint8_t* file, size_t bytes, uint8_t* out_rgb
     IRE_HIP(hipMemcpyAsync(out_rgb, d_px, ib, hipMemcpyDeviceToHost, s));
     IRE_HIP(hipMemcpyAsync(&st, d_st, sizeof(st), hipMemcpyDeviceToHost, s));
     IRE_HIP(hipStreamSynchronize(s));
-    // (png_inflate_core.hpp Status.  Flagged: whatever zlib would not decompress to exactly h * (1 + w * bpp) bytes with filter bytes 0..4.
+    // (png_inflate_core.hpp Status.  Flagged: whatever zlib would not decompress to exactly the scanlines' bytes (File::scan_bytes) with filter bytes 0..4.
     // Pillow zero-fills a short stream and ignores a long one; the device flags both, and the host codec then decides.)
     if (st != 0) fail(IRE_ERR_INVALID_INPUT, "invalid: corrupt PNG data (decoder status " + std::to_string(st) + ")");
 }

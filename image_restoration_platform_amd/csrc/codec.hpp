@@ -146,8 +146,10 @@ private:
 class PngDecoder {
 public:
     ~PngDecoder();        // IRE_PNG_DEC_TIMES=1: the two kernels' summed times as one JSON line on stderr (tools/png_decode_measure.py)
-    void setup(int max_batch, bool enabled, hipStream_t main_stream);
+    void setup(int max_batch, bool enabled, bool accept_all, hipStream_t main_stream);
     bool enabled() const { return enabled_; }
+    // what every plan_file of this engine is asked: pngparse::kAcceptAll on an engine with IRE_FLAG_DECODE_PNG_ALL, else 0
+    uint32_t accept() const { return accept_; }
     // n files of one planned size, of any colour types -> n images of h x w x 3 bytes on the device, image_pitch apart, one status word per
     // image (0: ok, else pngdec::Status).  One upload and two launches per batch.
     void decode_files(const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb, size_t image_pitch, int32_t* d_status, hipStream_t s);
@@ -176,6 +178,7 @@ private:
     void check_enabled() const;
     int max_batch_ = 8;
     bool enabled_ = false;
+    uint32_t accept_ = 0;
     hipStream_t main_stream_ = nullptr;
     Scratch own_, batch_;
     Buf<DeviceMem> d_out_;                // decode_host: the pixels and the status word

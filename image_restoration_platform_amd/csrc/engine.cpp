@@ -62,7 +62,7 @@ Engine::Engine(const ire_config& cfg) {
     IRE_HIP(hipStreamCreateWithFlags(&main_stream_, hipStreamNonBlocking));
     enc_.setup(max_batch_, main_stream_);
     dec_.setup(max_batch_, (cfg.flags & IRE_FLAG_DECODE_PROGRESSIVE) ? jpegparse::kAcceptProgressive : 0u, main_stream_);
-    pdec_.setup(max_batch_, (cfg.flags & IRE_FLAG_DECODE_PNG) != 0, main_stream_);
+    pdec_.setup(max_batch_, (cfg.flags & IRE_FLAG_DECODE_PNG) != 0, (cfg.flags & IRE_FLAG_DECODE_PNG_ALL) != 0, main_stream_);
     icc_.setup(max_batch_);
     upload_icc_ = (cfg.flags & IRE_FLAG_UPLOAD_ICC) != 0;
     for (auto& ev : ev_) IRE_HIP(hipEventCreate(&ev));

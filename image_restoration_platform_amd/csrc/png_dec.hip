@@ -14,6 +14,8 @@
 //   which lane 63 left in LDS.  The store does the colour work: palette lookup, grey replication, alpha drop.
 //   Access: each lane reads its own row front to back (1..4 bytes a step, the next step's pixel loaded a step ahead) and writes 3
 //   bytes a step; neighbouring lanes are a scanline apart.  Nobody has tuned either kernel: profiles/png_decode.md has the times.
+// K2' png_unfilter_any_kernel: takes K2's place for a batch that holds a file of depth 1, 2, 4 or 16 or an Adam7 one (see there);
+//   still two launches whatever n.  K1 is the same for every form: only the stream's expected length differs (Record::scan_total).
 #include "png_dec.hpp"
 
 namespace ire {
@@ -29,7 +31,7 @@ __global__ __launch_bounds__(kLanes) void png_inflate_kernel(const uint8_t* __re
     const unsigned long long t_begin = timed ? wall_clock64() : 0;
     const Record& R = reinterpret_cast<const Record*>(blob)[blockIdx.x];
     const int lane = (int)threadIdx.x;
-    if (lane == 0) begin(S, blob + bytes_off + R.in_off, R.in_len, scan + R.scan_off, R.h * (1u + R.w * R.bpp));
+    if (lane == 0) begin(S, blob + bytes_off + R.in_off, R.in_len, scan + R.scan_off, R.scan_total);
     __syncthreads();
     for (;;) {
         window_load(S, lane);
@@ -63,15 +65,11 @@ __device__ __forceinline__ uint32_t load_px(const uint8_t* p, uint32_t bpp) {
     return v;
 }
 
-__global__ __launch_bounds__(kLanes) void png_unfilter_kernel(const uint8_t* __restrict__ blob, const uint8_t* __restrict__ scan_all, uint8_t* __restrict__ rgb_all, size_t image_pitch,
-                                                              int32_t* __restrict__ status) {
-    __shared__ uint32_t hand[8192];          // the raw pixels of the band's last row, for lane 0 of the next band
-    const Record& R = reinterpret_cast<const Record*>(blob)[blockIdx.x];
-    if (status[R.dst] != 0) return;      // (the whole workgroup: K1 flagged the stream, its scanlines are not all there)
+// one image of the form "8 bits, not interlaced": the whole workgroup (one wave).  hand: 8192 words of LDS
+__device__ __forceinline__ void unfilter_rows8(const Record& R, const uint8_t* __restrict__ scan_all, uint8_t* __restrict__ rgb, uint32_t* hand, int32_t* __restrict__ status) {
     const uint32_t lane = threadIdx.x, h = R.h, w = R.w, bpp = R.bpp, ctype = R.ctype;
     const size_t stride = 1 + (size_t)w * bpp;
     const uint8_t* scan = scan_all + R.scan_off;
-    uint8_t* rgb = rgb_all + image_pitch * R.dst;
     bool bad = false;
     for (uint32_t r0 = 0; r0 < h; r0 += kLanes) {
         const uint32_t r = r0 + lane;
@@ -103,6 +101,84 @@ __global__ __launch_bounds__(kLanes) void png_unfilter_kernel(const uint8_t* __r
     if (bad) status[R.dst] = kStFilter;
 }
 
+__global__ __launch_bounds__(kLanes) void png_unfilter_kernel(const uint8_t* __restrict__ blob, const uint8_t* __restrict__ scan_all, uint8_t* __restrict__ rgb_all, size_t image_pitch,
+                                                              int32_t* __restrict__ status) {
+    __shared__ uint32_t hand[8192];          // the raw pixels of the band's last row, for lane 0 of the next band
+    const Record& R = reinterpret_cast<const Record*>(blob)[blockIdx.x];
+    if (status[R.dst] != 0) return;      // (the whole workgroup: K1 flagged the stream, its scanlines are not all there)
+    unfilter_rows8(R, scan_all, rgb_all + image_pitch * R.dst, hand, status);
+}
+
+// ---- every other form: 1, 2, 4 and 16 bits, Adam7 (png_adam7_core.hpp) ------------------------------------------------------------------
+__device__ __forceinline__ uint64_t load_unit(const uint8_t* p, uint32_t unit) {
+    uint64_t v = 0;
+    for (uint32_t k = 0; k < 8; ++k) if (k < unit) v |= (uint64_t)p[k] << (8 * k);
+    return v;
+}
+__device__ __forceinline__ uint64_t shfl_up1(uint64_t v) {
+    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, 1), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), 1);
+    return (uint64_t)hi << 32 | lo;
+}
+
+// One workgroup (one wave) per (image, pass): grid (n, 7) when the batch holds an interlaced file, else (n, 1).  The passes of an image
+// share nothing but the output, where each writes its own pixels, so they run side by side; within a pass the scheme is K2's: a skewed
+// wavefront over bands of 64 pass rows, lane i on unit t - i of pass row 64 b + i, the band's last row handed on in LDS.  A unit is
+// 1..8 bytes in one uint64; the store expands it to its 1..8 pixels and scatters them to (y0 + r dy, x0 + c dx).  A record of the old
+// form takes unfilter_rows8 in its workgroup of pass 0, so a mixed batch gives each file the bytes its own form's code gives.
+__global__ __launch_bounds__(kLanes) void png_unfilter_any_kernel(const uint8_t* __restrict__ blob, const uint8_t* __restrict__ scan_all, uint8_t* __restrict__ rgb_all,
+                                                                  size_t image_pitch, int32_t* __restrict__ status) {
+    __shared__ uint64_t hand[8192];          // at most 8192 units a pass row: pw <= 8192, and a sub-8-bit row has <= 4096 bytes
+    const Record& R = reinterpret_cast<const Record*>(blob)[blockIdx.x];
+    if (status[R.dst] != 0) return;      // (K1's word, or kStFilter from another pass of this image: either way the image is flagged)
+    uint8_t* rgb = rgb_all + image_pitch * R.dst;
+    const uint32_t p = blockIdx.y;
+    if (R.depth == 8 && R.interlace == 0) {
+        if (p == 0) unfilter_rows8(R, scan_all, rgb, reinterpret_cast<uint32_t*>(hand), status);
+        return;
+    }
+    if (p >= pass_count(R.interlace)) return;
+    const Pass P = pass_of(R.h, R.w, R.ctype, R.depth, R.interlace, p);
+    if (P.pw == 0 || P.ph == 0) return;      // (uniform: no barrier is left waiting)
+    const uint32_t lane = threadIdx.x, w = R.w, ctype = R.ctype, depth = R.depth;
+    const uint32_t unit = filter_unit(ctype, depth), per = unit_pixels(ctype, depth), nu = P.row_bytes / unit;      // row_bytes = nu * unit: whole pixels from 8 bits on
+    const size_t stride = 1 + (size_t)P.row_bytes;
+    const uint8_t* scan = scan_all + R.scan_off + P.off;
+    bool bad = false;
+    for (uint32_t r0 = 0; r0 < P.ph; r0 += kLanes) {
+        const uint32_t r = r0 + lane;
+        const bool row = r < P.ph;
+        const uint8_t* line = scan + stride * (row ? r : 0);
+        uint32_t ft = row ? line[0] : 0;
+        if (ft > 4) { bad = true; ft = 0; }
+        uint64_t cur = 0, prev = 0;
+        uint64_t next = (row && lane == 0) ? load_unit(line + 1, unit) : 0;
+        uint8_t* orow = rgb + ((size_t)(P.y0 + (row ? r : 0) * P.dy) * w + P.x0) * 3;      // y0 + r dy < h where r < ph
+        for (uint32_t t = 0; t < nu + kLanes - 1; ++t) {
+            uint64_t up = shfl_up1(cur), upleft = shfl_up1(prev);
+            const uint32_t x = t - lane;
+            const bool on = row && t >= lane && x < nu;
+            const uint64_t px = next;
+            if (row && t + 1 >= lane && x + 1 < nu) next = load_unit(line + 1 + (size_t)(x + 1) * unit, unit);      // x + 1 in 0 .. nu - 1
+            if (on) {
+                if (lane == 0) { up = hand[x]; upleft = x ? hand[x - 1] : 0; }
+                const uint64_t a = x ? cur : 0, b = r ? up : 0, c = (r && x) ? upleft : 0;      // r: the PASS's row, so its first has no row above
+                const uint64_t raw = unfilter_unit(ft, unit, px, a, b, c);
+                prev = cur; cur = raw;
+                for (uint32_t k = 0; k < per; ++k) {
+                    const uint32_t q = x * per + k;                 // the pass's column
+                    if (q >= P.pw) break;                           // the row's last byte may hold fewer pixels
+                    const uint32_t v = rgb_of_unit(ctype, depth, raw, k, R.pal);
+                    uint8_t* o = orow + (size_t)q * P.dx * 3;       // x0 + q dx < w where q < pw
+                    o[0] = (uint8_t)v; o[1] = (uint8_t)(v >> 8); o[2] = (uint8_t)(v >> 16);
+                }
+                if (lane == kLanes - 1) hand[x] = raw;
+            }
+        }
+        __syncthreads();
+    }
+    if (bad) status[R.dst] = kStFilter;
+}
+
 PngDecLayout png_dec_layout(const pngparse::File* const* f, const size_t* rooms, const int* dst, int n, pngdec::Record* rec) {
     PngDecLayout L;
     L.bytes = (sizeof(Record) * (size_t)n + 255) / 256 * 256;
@@ -113,8 +189,11 @@ PngDecLayout png_dec_layout(const pngparse::File* const* f, const size_t* rooms,
             r.scan_off = scan; r.in_off = (uint32_t)off; r.in_len = (uint32_t)rooms[i];
             r.dst = (uint32_t)(dst ? dst[i] : i); r.reserved = 0;
             r.h = (uint32_t)f[i]->h; r.w = (uint32_t)f[i]->w; r.ctype = (uint32_t)f[i]->ctype; r.bpp = (uint32_t)f[i]->bpp;
+            r.depth = (uint32_t)f[i]->depth; r.interlace = (uint32_t)f[i]->interlace; r.scan_total = (uint32_t)f[i]->scan_bytes(); r.pad = 0;
             std::memcpy(r.pal, f[i]->pal, sizeof(r.pal));
         }
+        if (f[i]->depth != 8 || f[i]->interlace) L.any_form = true;
+        if (f[i]->interlace) L.passes = (int)kMaxPasses;
         off += (rooms[i] + 3) & ~(size_t)3;
         scan += (f[i]->scan_bytes() + 15) & ~(size_t)15;
     }
@@ -130,7 +209,9 @@ void png_dec_launch(const uint8_t* d_blob, const PngDecLayout& L, int n, int h, 
     hipLaunchKernelGGL(png_inflate_kernel, dim3((unsigned)n), dim3(kLanes), 0, s, d_blob, L.bytes, d_scan, d_status, d_ticks);
     IRE_HIP(hipGetLastError());
     if (marks) IRE_HIP(hipEventRecord(marks[1], s));
-    hipLaunchKernelGGL(png_unfilter_kernel, dim3((unsigned)n), dim3(kLanes), 0, s, d_blob, d_scan, d_rgb, image_pitch, d_status);
+    // a batch of the old form alone: the kernel it always had; else the one that branches per record, a workgroup per (image, pass)
+    if (!L.any_form) hipLaunchKernelGGL(png_unfilter_kernel, dim3((unsigned)n), dim3(kLanes), 0, s, d_blob, d_scan, d_rgb, image_pitch, d_status);
+    else hipLaunchKernelGGL(png_unfilter_any_kernel, dim3((unsigned)n, (unsigned)L.passes), dim3(kLanes), 0, s, d_blob, d_scan, d_rgb, image_pitch, d_status);
     IRE_HIP(hipGetLastError());
     if (marks) IRE_HIP(hipEventRecord(marks[2], s));
 }

@@ -9,6 +9,8 @@ namespace ire {
 struct PngDecLayout {
     size_t bytes = 0, total = 0;       // the records' bytes (a multiple of 256) | records and streams
     size_t scan_bytes = 0;             // device scratch: the filtered scanlines of all n images
+    bool any_form = false;             // a file of another form than "8 bits, not interlaced" is among them: the second kernel is the per-pass one
+    int passes = 1;                    // that kernel's workgroups per image: 7 when a file is interlaced
 };
 // rooms[i]: the bytes of file i's stream; dst[i]: which image of the output it becomes (null: image i).  Fills rec[i] when rec is not null.
 PngDecLayout png_dec_layout(const pngparse::File* const* f, const size_t* rooms, const int* dst, int n, pngdec::Record* rec);

@@ -75,6 +75,8 @@ struct Record {
     uint32_t h, w, ctype, bpp;
     uint32_t dst, reserved;       // which image of the output, and which status word, is its
     uint8_t pal[768];       // colour type 3: the palette, zeros behind its last entry
+    uint32_t depth, interlace;    // 8 and 0: the form the fields above describe alone; else png_adam7_core.hpp's (bpp: the filter unit)
+    uint32_t scan_total, pad;     // the stream's expected length: h * (1 + w * bpp) for depth 8 without interlace, else the passes' sum
 };
 
 // a prefix code in canonical form: count[l] codes of l bits, their symbols in order

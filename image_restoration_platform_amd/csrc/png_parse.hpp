@@ -14,6 +14,8 @@
 // with a window of at most 32 KiB and no preset dictionary; with kRefuseIccp a file that carries iCCP.
 // IDAT CRCs are NOT checked: Pillow does not check them either, and the stream's Adler-32, which the device compares, covers the data.
 // A refused file stays with the host codec, so being stricter than Pillow is safe; being laxer is not.
+// With kAcceptAll (below) the depth and interlace rules widen to every standard form but 16-bit grey; a PLTE longer than 2^depth entries
+// is taken as Pillow takes it (the entries no index reaches are never read), one shorter gives black past its end, as at depth 8.
 // The FIRST eXIf chunk in front of IDAT gives the orientation by jpeg_parse.hpp's TIFF walk; a broken chunk is orientation 1, never a refusal.
 #pragma once
 #include <cstddef>
@@ -23,22 +25,30 @@
 #include <vector>
 
 #include "jpeg_parse.hpp"
+#include "png_adam7_core.hpp"
 
 namespace ire {
 namespace pngparse {
 
 constexpr uint32_t kRefuseIccp = 4u;       // ire.h: IRE_DECODE_ACCEPT_ICC -- the caller would have to read the profile; that is a later change
+// ire.h: IRE_DECODE_ACCEPT_PNG_ALL -- beside the 8-bit, non-interlaced files: depth 1, 2 and 4 for colour types 0 and 3, depth 16 for colour
+// types 2, 4 and 6, and Adam7 for all of them (png_adam7_core.hpp).  Without the bit every answer and every reason is what it was.
+// Still refused with it: the (type, depth) pairs the PNG specification forbids (Pillow refuses them too), and 16-bit GREY: Pillow opens
+// it as I;16 and convert("RGB") clips (0x0100 -> 255), sharp takes the high byte, so no device result could equal both host codecs.
+constexpr uint32_t kAcceptAll = 32u;
 
 struct Span { size_t off, len; };          // an IDAT chunk's payload in the file
 struct File {
-    int h = 0, w = 0, ctype = 0, bpp = 0;
+    int h = 0, w = 0, ctype = 0, bpp = 0;  // bpp: the filter unit's bytes, 1..4 for an 8-bit file, up to 8 for a 16-bit one, 1 below 8 bits
+    int depth = 8, interlace = 0;
     uint32_t npal = 0;
     uint8_t pal[768] = {};                 // zeros behind the last entry
     size_t idat_bytes = 0;                 // the zlib stream: what stage() copies, and the job's room
     std::vector<Span> spans;               // the non-empty IDAT payloads, in file order
     int orientation = 1;
     bool iccp = false;
-    size_t scan_bytes() const { return (size_t)h * (1 + (size_t)w * (size_t)bpp); }       // the filtered scanlines
+    // the filtered scanlines: the sum over the passes of rows * (1 + row bytes); h * (1 + w * bpp) for an 8-bit file without interlace
+    size_t scan_bytes() const { return (size_t)pngdec::scan_total((uint32_t)h, (uint32_t)w, (uint32_t)ctype, (uint32_t)depth, (uint32_t)interlace); }
 };
 
 struct Cursor {
@@ -92,13 +102,20 @@ inline bool plan_file(const uint8_t* file, size_t bytes, uint32_t flags, File& f
             const uint32_t w = s.u32(), h = s.u32();
             const unsigned depth = s.u8(), ctype = s.u8(), comp = s.u8(), filt = s.u8(), lace = s.u8();
             if (s.u32() != crc32(file + pay - 4, 17)) return refuse(why, "IHDR with a wrong CRC");
-            if (depth != 8) return refuse(why, "bit depth other than 8");
+            const bool all = (flags & kAcceptAll) != 0;
+            if (!all && depth != 8) return refuse(why, "bit depth other than 8");
             if (ctype != 0 && ctype != 2 && ctype != 3 && ctype != 4 && ctype != 6) return refuse(why, "unknown colour type");
+            if (all) {
+                if (depth != 1 && depth != 2 && depth != 4 && depth != 8 && depth != 16) return refuse(why, "bit depth that is none of 1, 2, 4, 8 and 16");
+                if (depth == 16 && ctype == 0) return refuse(why, "16-bit grey: the host codecs disagree on its conversion");
+                if (depth == 16 && ctype == 3) return refuse(why, "16-bit palette image: no such form");
+                if (depth < 8 && ctype != 0 && ctype != 3) return refuse(why, "bit depth below 8 in a colour type that has none");
+            }
             if (comp != 0 || filt != 0) return refuse(why, "unknown compression or filter method");
-            if (lace != 0) return refuse(why, "Adam7 interlacing");
+            if (all ? lace > 1 : lace != 0) return refuse(why, all ? "unknown interlace method" : "Adam7 interlacing");
             if (w < 1 || h < 1 || w > 8192 || h > 8192) return refuse(why, "size outside 1..8192");
-            f.h = (int)h; f.w = (int)w; f.ctype = (int)ctype;
-            f.bpp = ctype == 0 ? 1 : ctype == 2 ? 3 : ctype == 3 ? 1 : ctype == 4 ? 2 : 4;
+            f.h = (int)h; f.w = (int)w; f.ctype = (int)ctype; f.depth = (int)depth; f.interlace = (int)lace;
+            f.bpp = (int)pngdec::filter_unit(ctype, depth);
             have_ihdr = true;
             continue;
         }

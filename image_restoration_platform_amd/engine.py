@@ -109,6 +109,17 @@ def decode_png_plan_reason(data):
     return (h.value, w.value, c.value), None
 
 
+def decode_png_plan_ex_reason(data, accept=0):
+    """decode_png_plan_reason with a choice of what is accepted: accept = 0, or IRE_DECODE_ACCEPT_PNG_ALL for the plan of an engine
+    created with IRE_FLAG_DECODE_PNG | IRE_FLAG_DECODE_PNG_ALL.  -> ((h, w, colour_type, depth, interlace), None) or (None, reason).
+    ire_decode_png_plan_ex: pure host, no engine, no GPU."""
+    data = bytes(data)
+    h, w, c, d, lace = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    if _lib.load().ire_decode_png_plan_ex(data, len(data), int(accept), ctypes.byref(h), ctypes.byref(w), ctypes.byref(c), ctypes.byref(d), ctypes.byref(lace)) != 0:
+        return None, (_lib.load().ire_last_error() or b"").decode()
+    return (h.value, w.value, c.value, d.value, lace.value), None
+
+
 def decode_png_flags(flags, decode_png=None, environ=None):
     """the flags of an engine: IRE_FLAG_DECODE_PNG is added for decode_png=True and, when decode_png is None, for IRE_DECODE_PNG=1 in
     the environment; nothing is ever taken away"""
@@ -134,7 +145,8 @@ class Engine:
         upload_icc=True (or IRE_FLAG_UPLOAD_ICC in flags; None: the environment's IRE_UPLOAD_ICC=1): submit_upload converts the pixels
         of a file that carries an ICC profile to sRGB on the device, before the resize.
         decode_png=True (or IRE_FLAG_DECODE_PNG in flags; None: the environment's IRE_DECODE_PNG=1): decode_png, and submit_jpeg /
-        submit_file / submit_upload take a PNG file beside a JPEG one."""
+        submit_file / submit_upload take a PNG file beside a JPEG one.  IRE_FLAG_DECODE_PNG_ALL in flags beside it: also 1-, 2-, 4- and
+        16-bit files and Adam7 ones (decode_png_plan_ex_reason says which)."""
         flags = decode_png_flags(upload_icc_flags(flags, upload_icc), decode_png)
         self._lib = _lib.load()
         if weights_path == "default":
@@ -576,7 +588,17 @@ class Engine:
         """decode_accept, and IRE_DECODE_ACCEPT_ICC when the engine was created with IRE_FLAG_UPLOAD_ICC: what upload_plan_reason is asked"""
         f = getattr(self, "_flags", 0)
         return (self.decode_accept | (_lib.IRE_DECODE_ACCEPT_ICC if f & _lib.IRE_FLAG_UPLOAD_ICC else 0) |
-                (_lib.IRE_DECODE_ACCEPT_PNG if f & _lib.IRE_FLAG_DECODE_PNG else 0))
+                (_lib.IRE_DECODE_ACCEPT_PNG if f & _lib.IRE_FLAG_DECODE_PNG else 0) | self.png_accept)
+
+    @property
+    def png_accept(self):
+        """IRE_DECODE_ACCEPT_PNG_ALL when the engine was created with IRE_FLAG_DECODE_PNG_ALL, else 0: what this engine's PNG plan is asked"""
+        return _lib.IRE_DECODE_ACCEPT_PNG_ALL if getattr(self, "_flags", 0) & _lib.IRE_FLAG_DECODE_PNG_ALL else 0
+
+    def _png_plan(self, data):
+        """((h, w, colour_type), None) or (None, reason), as THIS engine's decoder plans the file"""
+        plan, why = decode_png_plan_ex_reason(data, self.png_accept)
+        return (plan[:3] if plan else None), why
 
     def icc_to_srgb(self, rgb, transforms):
         """[n,h,w,3] uint8 (or one [h,w,3]) and n IreIccTransform (None: leave the image) -> the converted copy: ire_icc_to_srgb."""
@@ -630,7 +652,7 @@ class Engine:
     # ---- PNG uploads decoded on the device (csrc/png_parse.hpp, csrc/png_dec.hip): an engine created with decode_png=True ----------
     def decode_png_plan(self, data):
         """(h, w, colour_type) or None; the reason of the last refusal is kept in .last_plan_reason (decode_png_plan_reason: no engine)"""
-        plan, why = decode_png_plan_reason(data)
+        plan, why = self._png_plan(data)
         if plan is None:
             self.last_plan_reason = why
         return plan
@@ -639,7 +661,7 @@ class Engine:
         """bytes of a PNG file the plan accepts -> [h,w,3] uint8, equal to PIL.Image.open(f).convert("RGB"); raises EngineError (invalid
         input) for a file out of scope, for data the device flags, and on an engine created without decode_png=True."""
         data = bytes(data)
-        plan, why = decode_png_plan_reason(data)
+        plan, why = self._png_plan(data)
         if plan is None:
             raise EngineError(_lib.IRE_ERR_INVALID_INPUT, why)
         h, w, _ = plan
@@ -651,7 +673,7 @@ class Engine:
         """decode_jpeg_device for PNG files of one planned size, of any colour types"""
         import torch
         files = [bytes(f) for f in files]
-        plans = [decode_png_plan_reason(f)[0] for f in files]
+        plans = [self._png_plan(f)[0] for f in files]
         if not files or any(p is None for p in plans) or len({p[:2] for p in plans}) != 1:
             raise EngineError(_lib.IRE_ERR_INVALID_INPUT, "invalid input: decode_png_device takes files of one planned size")
         n, (h, w, _) = len(files), plans[0]

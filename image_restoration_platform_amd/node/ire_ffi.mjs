@@ -76,6 +76,8 @@ export function bindIre(libPath) {
     ire_decode_jpeg: ['int', [P, P, 'size_t', P, 'int', 'int']],
     ire_decode_jpeg_device: ['int', [P, P, P, 'int', 'int', 'int', P, 'size_t', P, P]],
     ire_decode_png_plan: ['int', [P, 'size_t', P, P, P]],
+    // (accept: 0 or IRE_DECODE_ACCEPT_PNG_ALL = 32, passed as an int)
+    ire_decode_png_plan_ex: ['int', [P, 'size_t', 'int', P, P, P, P, P]],
     ire_decode_png: ['int', [P, P, 'size_t', P, 'int', 'int']],
     ire_decode_png_device: ['int', [P, P, P, 'int', 'int', 'int', P, 'size_t', P, P]],
     ire_job_release: ['int', [P, P]],

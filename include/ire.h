@@ -127,6 +127,12 @@ typedef struct ire_config {
  * refuses a PNG with the reason it gave before the flag existed, and nothing else changes.  (Bit value 512 stays unknown, as 2, 16 and
  * 64 do: tests/test_icc_plan.py holds it to that.) */
 #define IRE_FLAG_DECODE_PNG 1024u
+/* Valid only together with IRE_FLAG_DECODE_PNG (else ire_init fails, "invalid ... IRE_FLAG_DECODE_PNG"): the same entries also take the
+ * PNG forms ire_decode_png_plan_ex accepts with IRE_DECODE_ACCEPT_PNG_ALL -- 1, 2 and 4 bits per sample (grey and palette), 16 bits per
+ * sample (RGB, grey + alpha, RGB + alpha) and Adam7 interlacing.  16-bit GREY stays with the host codec: Pillow clips it, sharp takes
+ * its high byte, so the two hosts disagree.  A batch may mix old and new forms of one size.  Without this bit every entry gives the
+ * status, the reason and the bytes it gave before the bit existed.  (Bit values 2, 16, 64, 512 and 4096 stay unknown.) */
+#define IRE_FLAG_DECODE_PNG_ALL 8192u
 
 
 
@@ -368,6 +374,8 @@ int ire_decode_jpeg_plan(const uint8_t* file, size_t bytes, int* out_h, int* out
 #define IRE_DECODE_ACCEPT_ICC 4u          /* ire_upload_plan only: see there.  (Bit value 2 stays unknown.) */
 #define IRE_DECODE_ACCEPT_PNG 16u         /* ire_upload_plan only: the plan of an engine with IRE_FLAG_DECODE_PNG.  (Bit value 8 stays unknown beside 2:
                                              tests/test_icc_plan.py holds both to that.) */
+#define IRE_DECODE_ACCEPT_PNG_ALL 32u     /* ire_decode_png_plan_ex, and ire_upload_plan beside IRE_DECODE_ACCEPT_PNG: the plan of an engine with
+                                             IRE_FLAG_DECODE_PNG_ALL.  (Bit values 2 and 8 stay unknown.) */
 int ire_decode_jpeg_plan_ex(const uint8_t* file, size_t bytes, uint32_t accept, int* out_h, int* out_w, int* out_sampling, int* out_nscans);
 int ire_decode_jpeg(ire_engine* e, const uint8_t* file, size_t bytes, uint8_t* out_rgb /* h*w*3 */, int h, int w);
 int ire_decode_jpeg_device(ire_engine* e, const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb,
@@ -380,7 +388,7 @@ int ire_decode_jpeg_device(ire_engine* e, const uint8_t* const* files, const siz
  * this file: the signature, IHDR first; bit depth 8; colour type 0, 2, 3, 4 or 6; compression 0, filter method 0, no interlace; 1..8192
  * per side; PLTE of 1..256 entries (required for type 3); one or more CONSECUTIVE IDAT chunks, empty ones among them; IEND, or the end
  * of the file, behind the last IDAT; tRNS is read past; gAMA, cHRM, sRGB, pHYs, iCCP, text and every other ancillary chunk are skipped.
- * Everything else -- 16-bit and sub-8-bit depths, Adam7, APNG (acTL in front of IDAT), type 3 without PLTE, an IHDR or PLTE chunk whose
+ * Everything else -- 16-bit and sub-8-bit depths and Adam7 (but see ire_decode_png_plan_ex and IRE_FLAG_DECODE_PNG_ALL), APNG (acTL in front of IDAT), type 3 without PLTE, an IHDR or PLTE chunk whose
  * CRC-32 is wrong, any other chunk in front of IDAT whose CRC-32 is wrong, a chunk that overruns the file (behind the last IDAT only an
  * empty IEND may lack its CRC, and the file may end inside a chunk's eight header bytes: what Pillow still reads), IDAT chunks that are
  * not consecutive, no IDAT, a zlib header that is not deflate
@@ -395,7 +403,22 @@ int ire_decode_jpeg_device(ire_engine* e, const uint8_t* const* files, const siz
  * ire_decode_png_device: ire_decode_jpeg_device's contract -- n <= max_batch files (host memory) of ONE planned size, of any colour
  * types, -> n images on the device, image i at d_rgb + i * image_pitch_bytes (>= h*w*3), nothing between them written; d_status: one
  * int32 per image, 0 = ok (the pixels of a flagged image are unspecified); the host parse runs inside the call; two launches whatever
- * n; the host's one wait is for the upload of the call before last. */
+ * n; the host's one wait is for the upload of the call before last.
+ * ire_decode_png_plan_ex: ire_decode_png_plan with a choice of what is accepted, and the file's bit depth and interlace method beside
+ * its colour type.  accept == 0: ire_decode_png_plan itself, status and reason; any bit but IRE_DECODE_ACCEPT_PNG_ALL is
+ * IRE_ERR_INVALID_INPUT "unknown accept bits".  IRE_DECODE_ACCEPT_PNG_ALL: beside those files, bit depth 1, 2 or 4 for colour types 0
+ * and 3, bit depth 16 for colour types 2, 4 and 6, and interlace method 1 (Adam7) for every accepted (type, depth) pair; the other
+ * rules above are unchanged.  The pixels are still PIL's convert("RGB"): a grey sample of 1, 2 or 4 bits times 255, 85 or 17; a palette
+ * index looked up, black where it lies past the last PLTE entry (a PLTE longer than 2^depth entries is read as Pillow reads it);
+ * of a 16-bit sample its HIGH byte (0x00ff -> 0, 0x80ff -> 128); tRNS read past, alpha dropped.  Still refused, each with its own
+ * reason: the (type, depth) pairs the PNG specification forbids, and 16-bit GREY (colour type 0) -- Pillow opens it as I;16 and
+ * convert("RGB") CLIPS (0x0100 -> 255) where sharp takes the high byte, so a device result could equal only one of the two host codecs:
+ * "invalid: PNG 16-bit grey: the host codecs disagree on its conversion".  An engine with IRE_FLAG_DECODE_PNG_ALL decodes what this
+ * accepts, in ire_decode_png, ire_decode_png_device (old and new forms may share a batch; still two launches) and the submit entries;
+ * "flagged" then reads: the stream yields exactly the passes' scanlines -- per pass that has a pixel, rows * (1 + ceil(width * bits per
+ * pixel / 8)) bytes -- and every filter byte is 0..4.  The device path is still slower than the host codec (profiles/png_depths.md). */
+int ire_decode_png_plan_ex(const uint8_t* file, size_t bytes, uint32_t accept, int* out_h, int* out_w, int* out_colour_type, int* out_depth,
+                           int* out_interlace);
 int ire_decode_png_plan(const uint8_t* file, size_t bytes, int* out_h, int* out_w, int* out_colour_type);
 int ire_decode_png(ire_engine* e, const uint8_t* file, size_t bytes, uint8_t* out_rgb /* h*w*3 */, int h, int w);
 int ire_decode_png_device(ire_engine* e, const uint8_t* const* files, const size_t* bytes, int n, int h, int w, uint8_t* d_rgb,

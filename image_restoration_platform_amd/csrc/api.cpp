@@ -224,7 +224,7 @@ struct HipBatchBackend {
     // jobs first .. first + count - 1 of the slot, their staged bytes `place` apart in pin_in, decoded to h x w images `pitch` apart in d_rgb
     void decode_runs(HipSlot& hs, SlotBufs& b, int first, int count, size_t place, int h, int w, uint8_t* d_rgb, size_t pitch, void* const* heads, const size_t* used) {
         if (!hs.d_fstat) {                // zeroed once: the word of a job with nothing to decode is never written
-            hs.d_fstat = Buf<DeviceMem>(sizeof(int32_t) * kMaxBatch); hs.pin_fstat = Buf<PinnedMem>(sizeof(int32_t) * kMaxBatch);
+            hs.d_fstat = Buf<DeviceMem>(sizeof(int32_t) * kMaxBatch, BufUse::Persistent); hs.pin_fstat = Buf<PinnedMem>(sizeof(int32_t) * kMaxBatch, BufUse::Persistent);
             IRE_HIP(hipMemsetAsync(hs.d_fstat.get<int32_t>(), 0, sizeof(int32_t) * kMaxBatch, cs));
             std::memset(hs.pin_fstat.get<int32_t>(), 0, sizeof(int32_t) * kMaxBatch);
         }
@@ -1106,6 +1106,21 @@ int ire_debug_classifier_sums(ire_engine* e, int n, uint64_t* sums_out) {
         if (!sums_out) fail(IRE_ERR_INVALID_INPUT, "invalid output pointer");
         std::lock_guard<std::mutex> lk(E.mutex());
         E.debug_sums(n, sums_out);
+    });
+}
+
+int ire_debug_poison_scratch(ire_engine* e, int byte, uint64_t* bytes_filled) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        if (!BufRegistry::on()) fail(IRE_ERR_INVALID_INPUT, "invalid call: ire_debug_poison_scratch needs IRE_DEBUG_POISON=<0..255> in the environment of the process");
+        // The check and the fill under the engine's lock (the batcher's own lock is only ever taken inside it, never the other way round).
+        // A queued job's input is already in its slot's staging, a delivered one's result still is: neither survives a fill.  A submit
+        // takes the batcher's lock alone, so one that arrives between the check and the fill is not excluded: the caller submits nothing
+        // while it poisons (ire.h).
+        std::lock_guard<std::mutex> lk(E.mutex());
+        if (e->batcher && !e->batcher->idle()) fail(IRE_ERR_INVALID_INPUT, "invalid call: ire_debug_poison_scratch while a job is queued, in flight or not yet polled");
+        const uint64_t filled = E.debug_poison_scratch(byte);
+        if (bytes_filled) *bytes_filled = filled;
     });
 }
 

@@ -313,6 +313,14 @@ class Batcher {
     struct Counters { long batches = 0, overflowed = 0, evicted = 0, abandoned = 0, failed_batches = 0; };
     Counters counters() { std::lock_guard<std::mutex> lk(mu_); return cnt_; }
 
+    // no job queued, in flight or delivered but not yet polled: every slot is FREE and nothing overflows
+    bool idle() {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (!overflow_.empty()) return false;
+        for (const BatchSlot& S : slots_) if (S.state != BatchSlot::FREE) return false;
+        return true;
+    }
+
     int queue_depth() {
         std::lock_guard<std::mutex> lk(mu_);
         int depth = (int)overflow_.size();

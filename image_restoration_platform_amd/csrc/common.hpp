@@ -4,8 +4,10 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <string>
 
+#include "buf_registry.hpp"
 #include "errors.hpp"
 
 namespace ire {
@@ -29,12 +31,30 @@ inline void hip_check(hipError_t e, const char* what, const char* file, int line
 }
 #define IRE_HIP(expr) ::ire::hip_check((expr), #expr, __FILE__, __LINE__)
 
-struct DeviceMem {      // the two memory policies of device_buf.hpp: out of memory leaves here as the retryable 503 above
-    static void* alloc(size_t bytes) { void* p = nullptr; IRE_HIP(hipMalloc(&p, bytes)); return p; }
+// The two memory policies of device_buf.hpp: out of memory leaves here as the retryable 503 above.  Under IRE_DEBUG_POISON
+// (buf_registry.hpp) what they hand out is filled with the byte first, and the fill is complete before the caller has the pointer.
+struct DeviceMem {
+    static constexpr bool kPinned = false;
+    static void* alloc(size_t bytes) {
+        void* p = nullptr;
+        IRE_HIP(hipMalloc(&p, bytes));
+        if (const int b = debug_poison_byte(); b >= 0) {
+            hipError_t e = hipMemset(p, b, bytes);
+            if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+            if (e != hipSuccess) { (void)hipFree(p); IRE_HIP(e); }
+        }
+        return p;
+    }
     static void free(void* p) noexcept { (void)hipFree(p); }
 };
 struct PinnedMem {
-    static void* alloc(size_t bytes) { void* p = nullptr; IRE_HIP(hipHostMalloc(&p, bytes)); return p; }
+    static constexpr bool kPinned = true;
+    static void* alloc(size_t bytes) {
+        void* p = nullptr;
+        IRE_HIP(hipHostMalloc(&p, bytes));
+        if (const int b = debug_poison_byte(); b >= 0) std::memset(p, b, bytes);
+        return p;
+    }
     static void free(void* p) noexcept { (void)hipHostFree(p); }
 };
 

@@ -1,51 +1,72 @@
 // device_buf.hpp -- who owns device and pinned memory, and how it grows; no HIP, no device code.  libire.so instantiates it over the two
 // policies of common.hpp (DeviceMem, PinnedMem), tests/native/device_buf_test.cpp over a counting policy on the CPU.  A policy `Mem` has
-// static void* alloc(size_t) (throws on failure) and static void free(void*) noexcept.  Two guarantees (DESIGN.md "Buffer ownership"):
+// static void* alloc(size_t) (throws on failure) and static void free(void*) noexcept; one of pinned memory also says
+// static constexpr bool kPinned = true (a policy without the member counts as device memory).  Under
+// IRE_DEBUG_POISON every live allocation of a Buf is entered in buf_registry.hpp's registry, as scratch unless its site says
+// BufUse::Persistent; a Buf keeps that use through reset and grow.  Two guarantees (DESIGN.md "Buffer ownership"):
 // an engine scratch buffer or group is EMPTY after a failed grow, never dangling (the caller is told "service unavailable", calls again,
 // and the capacity check sends it back into the grow); a batcher slot is UNCHANGED after a failed reserve.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
+#include "buf_registry.hpp"
 #include "conv_kind.hpp"
 
 namespace ire {
+
+// whether a policy's memory is pinned host memory: its kPinned, false where it has none
+template <class Mem, class = void> struct mem_pinned : std::false_type {};
+template <class Mem> struct mem_pinned<Mem, std::void_t<decltype(Mem::kPinned)>> : std::bool_constant<Mem::kPinned> {};
 
 // move-only owner of one allocation (a zero-byte request allocates 16 bytes)
 template <class Mem>
 class Buf {
 public:
     Buf() = default;
-    explicit Buf(size_t bytes) : bytes_(bytes ? bytes : 16) { p_ = Mem::alloc(bytes_); }
-    Buf(Buf&& o) noexcept : p_(std::exchange(o.p_, nullptr)), bytes_(std::exchange(o.bytes_, 0)) {}
+    explicit Buf(BufUse use) : use_(use) {}      // empty, for a later grow
+    explicit Buf(size_t bytes, BufUse use = BufUse::Scratch) : bytes_(bytes ? bytes : 16), use_(use) {
+        p_ = Mem::alloc(bytes_);                 // (a throw: nothing allocated, nothing entered)
+        if (BufRegistry::on()) BufRegistry::get().add(p_, bytes_, mem_pinned<Mem>::value, use_);
+    }
+    Buf(Buf&& o) noexcept : p_(std::exchange(o.p_, nullptr)), bytes_(std::exchange(o.bytes_, 0)), use_(o.use_) {}
     Buf& operator=(Buf&& o) noexcept {
-        if (this != &o) { reset(); p_ = std::exchange(o.p_, nullptr); bytes_ = std::exchange(o.bytes_, 0); }
+        if (this != &o) { reset(); p_ = std::exchange(o.p_, nullptr); bytes_ = std::exchange(o.bytes_, 0); use_ = o.use_; }
         return *this;
     }
     ~Buf() { reset(); }
     template <class T> T* get() const { return static_cast<T*>(p_); }
     size_t bytes() const { return bytes_; }
+    BufUse use() const { return use_; }
     explicit operator bool() const { return p_ != nullptr; }
-    void reset() noexcept { if (p_) Mem::free(p_); p_ = nullptr; bytes_ = 0; }
+    void reset() noexcept {
+        if (p_) {
+            if (BufRegistry::on()) BufRegistry::get().remove(p_);      // before the free: the address may be handed out again at once
+            Mem::free(p_);
+        }
+        p_ = nullptr; bytes_ = 0;
+    }
     // Room for `need` bytes: nothing when there is, else `want` (>= need) bytes in place of the old ones; true = reallocated.  The old
     // memory goes FIRST (allocating before freeing would double the peak of the largest shapes) and the buffer is empty while the
     // allocation runs, so a throw leaves it empty.
-    bool grow(size_t need, size_t want) { if (need <= bytes_) return false; reset(); *this = Buf(want); return true; }
+    bool grow(size_t need, size_t want) { if (need <= bytes_) return false; reset(); *this = Buf(want, use_); return true; }
     bool grow(size_t need) { return grow(need, need); }
 private:
     void* p_ = nullptr;
     size_t bytes_ = 0;
+    BufUse use_ = BufUse::Scratch;
 };
 
 // move-only owner of any number of allocations (what it hands out are views)
 template <class Mem>
 class BufSet {
 public:
-    template <class T> T* alloc(size_t bytes) {
+    template <class T> T* alloc(size_t bytes, BufUse use = BufUse::Scratch) {
         v_.emplace_back();                  // the place first: a throw below leaves an empty entry, not an unowned allocation
-        v_.back() = Buf<Mem>(bytes);
+        v_.back() = Buf<Mem>(bytes, use);
         return v_.back().template get<T>();
     }
     size_t bytes() const { size_t b = 0; for (const Buf<Mem>& x : v_) b += x.bytes(); return b; }
@@ -76,7 +97,7 @@ struct IoBufs {
         g.in = g.mem.template alloc<uint8_t>(imgs * px * 3);
         g.out = g.mem.template alloc<uint8_t>(imgs * px * 3);
         g.jpeg = g.mem.template alloc<uint8_t>(imgs);
-        g.sums = g.mem.template alloc<unsigned long long>(sums_bytes);
+        g.sums = g.mem.template alloc<unsigned long long>(sums_bytes, BufUse::Persistent);      // cleared once by ensure_io: the tickets clean themselves
         g.scores = g.mem.template alloc<double>(imgs * 7 * 8);
         g.label = g.mem.template alloc<int32_t>(imgs * 4);
         g.cond = g.mem.template alloc<float>(imgs * 8 * 4);
@@ -102,7 +123,7 @@ struct FuseBufs {
         g.L = g.mem.template alloc<uint8_t>(cs * 3 * px);
         g.Q = g.mem.template alloc<uint8_t>(cs * 3 * (px / 16 + px / 64 + 16) + 64);      // (w >= 64: the pitch adds at most 3 to a row of >= 16)
         g.sad = g.mem.template alloc<unsigned>(sizeof(unsigned) * cs * sad_words);
-        g.misc = g.mem.template alloc<int>(sizeof(int) * cs * 16);
+        g.misc = g.mem.template alloc<int>(sizeof(int) * cs * 16, BufUse::Persistent);      // cleared once by fuse_reserve: the tickets clean themselves
         g.wlut = g.mem.template alloc<unsigned>(sizeof(unsigned) * cs * 256);
         g.cap_px = px; g.cap_sets = sets;
         *this = std::move(g);

@@ -75,9 +75,9 @@ Engine::Engine(const ire_config& cfg) {
     }
 
     // classifier tables
-    unsigned int* d_lin = tables_mem_.alloc<unsigned int>(sizeof(kLin16));
-    unsigned int* d_thr = tables_mem_.alloc<unsigned int>(sizeof(kGreyThr));
-    unsigned char* d_inv = tables_mem_.alloc<unsigned char>(5008);          // 5001 buckets, padded to whole 16-byte chunks (classifier.hip loads it as uint4)
+    unsigned int* d_lin = tables_mem_.alloc<unsigned int>(sizeof(kLin16), BufUse::Persistent);
+    unsigned int* d_thr = tables_mem_.alloc<unsigned int>(sizeof(kGreyThr), BufUse::Persistent);
+    unsigned char* d_inv = tables_mem_.alloc<unsigned char>(5008, BufUse::Persistent);          // 5001 buckets, padded to whole 16-byte chunks (classifier.hip loads it as uint4)
     IRE_HIP(hipMemset(d_inv, 0, 5008));
     IRE_HIP(hipMemcpy(d_lin, kLin16, sizeof(kLin16), hipMemcpyHostToDevice));
     IRE_HIP(hipMemcpy(d_thr, kGreyThr, sizeof(kGreyThr), hipMemcpyHostToDevice));
@@ -169,7 +169,7 @@ void Engine::load_weights_file(const char* path) {
 template <class T>
 T* Engine::upload(const std::vector<T>& v) {
     if (v.empty()) return nullptr;
-    T* d = net_.mem.alloc<T>(v.size() * sizeof(T));
+    T* d = net_.mem.alloc<T>(v.size() * sizeof(T), BufUse::Persistent);
     IRE_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return d;
 }
@@ -449,6 +449,22 @@ void Engine::debug_sums(int n, uint64_t* out) {
     if (n <= 0 || (size_t)n > io_.cap_imgs) fail(IRE_ERR_INVALID_INPUT, "invalid n for debug sums");
     IRE_HIP(hipDeviceSynchronize());
     IRE_HIP(hipMemcpy(out, io_.sums, sizeof(uint64_t) * 14 * n, hipMemcpyDeviceToHost));
+}
+// ire_debug_poison_scratch: every scratch allocation of the registry (buf_registry.hpp: the PROCESS's, whichever engine owns it) over
+// its whole capacity, between two waits for the device.  Persistent entries were poisoned at birth and keep what their owners put there.
+uint64_t Engine::debug_poison_scratch(int byte) {
+    if (byte < 0 || byte > 255) fail(IRE_ERR_INVALID_INPUT, "invalid byte for ire_debug_poison_scratch: expected 0..255");
+    IRE_HIP(hipSetDevice(device_));
+    IRE_HIP(hipDeviceSynchronize());
+    uint64_t filled = 0;
+    for (const BufRegistry::Entry& e : BufRegistry::get().snapshot()) {
+        if (e.persistent) continue;
+        if (e.pinned) std::memset(e.p, byte, e.bytes);
+        else IRE_HIP(hipMemset(e.p, byte, e.bytes));
+        filled += e.bytes;
+    }
+    IRE_HIP(hipDeviceSynchronize());
+    return filled;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -233,6 +233,7 @@ public:
     const TextFormat* result_format() const { return result_format_; }      // of the batcher's results, with this engine's settings; null: pixels
 
     void debug_sums(int n, uint64_t* out);
+    uint64_t debug_poison_scratch(int byte);      // -> bytes filled
     void debug_capture(bool on) { capture_ = on; captured_.clear(); }
     bool debug_activation(const std::string& name, float* out, size_t* count);
 
@@ -328,7 +329,7 @@ private:
     IoBufs<DeviceMem> io_;                // io / classifier buffers (sized by ensure_io)
     int last_n_ = 0;
     FuseBufs<DeviceMem> fuse_;            // fusion scratch
-    Buf<DeviceMem> d_zero_;               // 256 bytes of zeros (conv_upq.hip's zero padding source)
+    Buf<DeviceMem> d_zero_{BufUse::Persistent};             // 256 bytes of zeros (conv_upq.hip's zero padding source)
     Buf<DeviceMem> d_pp_tab_, d_pp_mid_, d_pp_in_, d_pp_out_;   // preprocess scratch (tap tables, intermediate of the horizontal pass, host-path staging)
     PreprocessScratch pp_own_, pp_uploads_;
     Buf<DeviceMem> d_pad_in_, d_pad_out_; // any-size jobs: the edge-padded batch in front of the network, and the network's output on the padded shape
@@ -351,7 +352,7 @@ private:
 
     // debug / profile
     // diagnostic stamps (IRE_RB_STAMPS, ablation builds)
-    Buf<DeviceMem> stamps_dev_;
+    Buf<DeviceMem> stamps_dev_{BufUse::Persistent};
     int stamps_cout_ = 0;
     bool stamps_resid_ = false, stamps_taken_ = false;
     std::string stamps_tl_;

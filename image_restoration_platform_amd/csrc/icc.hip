@@ -118,7 +118,7 @@ void IccConverter::setup(int max_batch) {
     uint8_t host[kIccEncBytes];
     std::memcpy(host, E.coarse, 4096);
     std::memcpy(host + 4096, E.last, 512);
-    d_enc_ = Buf<DeviceMem>(kIccEncBytes);
+    d_enc_ = Buf<DeviceMem>(kIccEncBytes, BufUse::Persistent);
     IRE_HIP(hipMemcpy(d_enc_.get<void>(), host, kIccEncBytes, hipMemcpyHostToDevice));
 }
 

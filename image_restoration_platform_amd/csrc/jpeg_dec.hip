@@ -580,7 +580,7 @@ size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 }  // namespace
 
 // blocks of one image's coefficient scratch at most, whatever its sampling: three components on the 4:2:0 luma grid
-size_t jpeg_dec_blocks(int h, int w) { return (size_t)3 * (2 * (((size_t)w + 15) / 16)) * (2 * (((size_t)h + 15) / 16)); }
+size_t jpeg_dec_blocks(int h, int w) { return jpegdec::coef_blocks(h, w); }
 size_t jpeg_dec_coef_bytes(int n, int h, int w) { return up256(4 * (size_t)n) + (size_t)n * jpeg_dec_blocks(h, w) * 128; }
 size_t jpeg_dec_plane_bytes(int n, int h, int w) { return (size_t)n * jpeg_dec_blocks(h, w) * 64; }
 size_t jpeg_dec_lane_bytes(size_t nwin) { return nwin * (sizeof(LaneRec) * kLanes + sizeof(WinHead)); }

@@ -13,6 +13,7 @@
 // right and always ends; it stops early when no lane changed.  Then a prefix sum over the lanes' completed-block counts and DC
 // sums gives each lane its first block and its DC predictors, and a second pass writes the coefficients.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #if defined(__HIPCC__)
@@ -397,6 +398,11 @@ constexpr unsigned kChainStagePadded = kChainStageWords + kChainStageWords / 32 
 IRE_HD uint32_t state_bk(const DecState& s) { return s.blk << 8 | s.k; }
 IRE_HD DecState state_of(uint32_t p, uint32_t bk) { return DecState{p, bk >> 8, bk & 255u}; }
 // windows of a stream of `len` bytes (len < 2^28: jpeg_parse.hpp refuses larger files)
+// Blocks of one image's coefficient scratch at most, whatever its sampling: three components on the 4:2:0 luma grid.  THE extent of
+// jpeg_dec.hip's scratch per image (jpeg_dec_blocks) and of what jpeg_dec_launch clears in front of every batch; tests/native's simulators
+// take it from here.
+inline size_t coef_blocks(int h, int w) { return (size_t)3 * (2 * (((size_t)w + 15) / 16)) * (2 * (((size_t)h + 15) / 16)); }
+
 IRE_HD uint32_t window_count(uint32_t len) { return (8u * len + kWindowBits - 1) / kWindowBits; }
 // the lanes of the window at bit win0 whose subsequence begins inside the stream, and the bit behind lane t's subsequence
 IRE_HD uint32_t window_lanes(uint32_t total_bits, uint32_t win0) {

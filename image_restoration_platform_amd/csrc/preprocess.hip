@@ -351,7 +351,7 @@ const TapTable& PreprocessScratch::table(int in_size, int out_size, hipStream_t 
         span = std::max(span, hi - lo);
     }
     if (lru->used) { IRE_HIP(hipDeviceSynchronize()); lru->used = 0; lru->d.reset(); }
-    lru->d = Buf<DeviceMem>((bounds.size() + taps.size()) * sizeof(int32_t));
+    lru->d = Buf<DeviceMem>((bounds.size() + taps.size()) * sizeof(int32_t), BufUse::Persistent);      // cached: later calls of the pair read it
     IRE_HIP(hipMemcpyAsync(lru->d.get<int32_t>(), bounds.data(), bounds.size() * 4, hipMemcpyHostToDevice, s));
     IRE_HIP(hipMemcpyAsync(lru->d.get<int32_t>() + bounds.size(), taps.data(), taps.size() * 4, hipMemcpyHostToDevice, s));
     IRE_HIP(hipStreamSynchronize(s));      // the vectors die at return: the one wait of a pair's first use

@@ -855,6 +855,12 @@ class Engine:
         self._check(self._lib.ire_debug_classifier_sums(self._h, n, _ptr(sums)))
         return sums
 
+    def debug_poison_scratch(self, byte):
+        """Fill every scratch allocation of the process with `byte` (ire_debug_poison_scratch; only under IRE_DEBUG_POISON) -> bytes filled."""
+        n = ctypes.c_uint64(0)
+        self._check(self._lib.ire_debug_poison_scratch(self._h, int(byte), ctypes.byref(n)))
+        return n.value
+
     def debug_capture(self, on=True):
         self._check(self._lib.ire_debug_capture(self._h, int(on)))
 

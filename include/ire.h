@@ -641,6 +641,13 @@ int ire_debug_jpeg_huffman(ire_engine* e, const uint32_t* counts /* [n][4][256] 
  * ire_jpeg_progressive_base64_bound(h, w, quality, sampling) / 4 * 3, and lens their lengths.  n in 1..max_batch (tests only). */
 int ire_debug_jpeg_progressive_from_coefs(ire_engine* e, const int16_t* coefs, int n, int h, int w, int quality, int sampling,
                                           uint8_t* out_files, size_t stride, uint64_t* lens /* n x uint64, host */);
+/* Fill every scratch allocation of the process (device and pinned, over its whole capacity, whichever engine owns it) with `byte`, between
+ * two waits for the device; *bytes_filled (may be null) = how many bytes that was.  Only in a process started with
+ * IRE_DEBUG_POISON=<0..255> (every allocation is then filled with that byte at birth and entered in a registry): IRE_ERR_INVALID_INPUT
+ * without it, and while this engine has a job queued, in flight or delivered but not yet polled.  Persistent allocations (weights,
+ * tables, tickets that clean themselves: DESIGN.md "Buffer ownership") are left alone.  The caller submits no job while the call runs and keeps
+ * every other engine of the process, and every strip session, idle meanwhile (tests only). */
+int ire_debug_poison_scratch(ire_engine* e, int byte, uint64_t* bytes_filled);
 /* Turn per-layer capture on/off (slow: synchronises after every layer; tests only). */
 int ire_debug_capture(ire_engine* e, int on);
 /* Copy one named intermediate activation of the last ire_restore* call to host as float32 NHWC.

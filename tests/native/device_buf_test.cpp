@@ -2,12 +2,15 @@
 // infrastructure: libire.so includes the same header over hipMalloc / hipHostMalloc; here the memory policy counts.
 //   (no argument)  every ownership check below; prints "ok"
 //   dump           the workspace table and bytes-per-image lines the Python driver compares with its own restatement of the parent
+//   registry       csrc/buf_registry.hpp under IRE_DEBUG_POISON (the driver sets it; also built under ThreadSanitizer): an entry per live
+//                  allocation, none after free, reset, a failed grow or for a moved-from buffer, the persistent flag, two threads; prints "ok"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <set>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../image_restoration_platform_amd/csrc/device_buf.hpp"
@@ -226,6 +229,138 @@ static void test_slot() {
     CHECK(Count::live.empty() && Count::bad_frees == 0);
 }
 
+// ---- the registry.  `Pin` is a second policy (pinned, thread-safe, no log) so that both kinds and two threads can be told apart. ----
+struct Pin {
+    static constexpr bool kPinned = true;
+    static void* alloc(size_t bytes) { return std::malloc(bytes); }
+    static void free(void* p) noexcept { std::free(p); }
+};
+static const BufRegistry::Entry* find(const std::vector<BufRegistry::Entry>& v, const void* p) {
+    for (const BufRegistry::Entry& e : v) if (e.p == p) return &e;
+    return nullptr;
+}
+// the registry holds exactly these buffers' allocations, with their sizes
+template <class... B>
+static bool holds(const B&... b) {
+    const std::vector<BufRegistry::Entry> v = BufRegistry::get().snapshot();
+    size_t n = 0;
+    bool ok = true;
+    auto one = [&](const void* p, size_t bytes) {
+        if (!p) return;
+        ++n;
+        const BufRegistry::Entry* e = find(v, p);
+        ok = ok && e && e->bytes == bytes;
+    };
+    (one(b.template get<void>(), b.bytes()), ...);
+    return ok && v.size() == n;
+}
+
+static void test_registry() {
+    BufRegistry& R = BufRegistry::get();
+    CHECK(BufRegistry::on() && debug_poison_byte() == 90 && R.size() == 0);
+    Count::restart();
+    {
+        Buf<Count> a(100), e;
+        Buf<Pin> p(7, BufUse::Persistent);
+        CHECK(holds(a, e, p));
+        const auto v = R.snapshot();
+        CHECK(!find(v, a.get<void>())->pinned && !find(v, a.get<void>())->persistent);           // scratch unless the site says otherwise
+        CHECK(find(v, p.get<void>())->pinned && find(v, p.get<void>())->persistent && find(v, p.get<void>())->bytes == 7);
+        // grow: the old entry goes, the new one has the new size and the buffer's use; below the capacity nothing changes
+        CHECK(p.grow(8, 64) && holds(a, p) && find(R.snapshot(), p.get<void>())->persistent && p.use() == BufUse::Persistent);
+        CHECK(!a.grow(50) && holds(a, p));
+        CHECK(a.grow(101, 300) && holds(a, p) && find(R.snapshot(), a.get<void>())->bytes == 300);
+        // an empty buffer declared persistent stays so through its first grow (Engine: d_zero_)
+        Buf<Count> z(BufUse::Persistent);
+        CHECK(holds(a, p, z) && z.grow(16) && holds(a, p, z) && find(R.snapshot(), z.get<void>())->persistent);
+        // a failed grow: no entry, and none after the retry's predecessor either
+        Count::fail(1);
+        CHECK(throws([&] { a.grow(301, 600); }));
+        CHECK(!a && holds(p, z));
+        CHECK(a.grow(301, 600) && holds(a, p, z));
+        // a throwing constructor enters nothing
+        Count::fail(1);
+        CHECK(throws([&] { Buf<Count> t(9); }));
+        CHECK(holds(a, p, z));
+        // a move: one entry, the same pointer; the moved-from buffer has none; the use travels with the allocation
+        void* was = z.get<void>();
+        Buf<Count> m(std::move(z));
+        CHECK(!z && m.get<void>() == was && holds(a, p, m) && find(R.snapshot(), was)->persistent);
+        Buf<Count> n(32);
+        n = std::move(m);                       // n's own 32 bytes leave the registry with the assignment
+        CHECK(!m && holds(a, p, n) && n.use() == BufUse::Persistent);
+        n.reset();
+        CHECK(holds(a, p));
+        n.reset();
+        CHECK(holds(a, p));
+    }
+    CHECK(R.size() == 0 && Count::live.empty() && Count::bad_frees == 0);
+    {
+        // sets and groups: an entry per allocation, the persistent ones where device_buf.hpp says
+        BufSet<Count> s;
+        int* x = s.alloc<int>(40);
+        char* y = s.alloc<char>(0, BufUse::Persistent);
+        auto v = R.snapshot();
+        CHECK(v.size() == 2 && !find(v, x)->persistent && find(v, y)->persistent && find(v, y)->bytes == 16);
+        Count::fail(1);
+        CHECK(throws([&] { s.alloc<char>(8); }));
+        CHECK(R.size() == 2);
+        BufSet<Count> t(std::move(s));
+        CHECK(R.size() == 2);
+        t.clear();
+        CHECK(R.size() == 0);
+        IoBufs<Count> g;
+        g.regrow(2, 64, kSums);
+        v = R.snapshot();
+        CHECK(v.size() == 8);
+        for (const BufRegistry::Entry& e : v) CHECK(e.persistent == (e.p == (void*)g.sums));
+        for (int k = 1; k <= 8; ++k) {
+            Count::fail(k);
+            CHECK(throws([&] { g.regrow(4, 256, kSums); }));
+            CHECK(R.size() == 0);
+            g.regrow(2, 64, kSums);
+            CHECK(R.size() == 8);
+        }
+        FuseBufs<Count> f;
+        f.regrow(1, 4096, 100);
+        v = R.snapshot();
+        CHECK(v.size() == 13);
+        for (const BufRegistry::Entry& e : v) if (e.p != (void*)g.sums) CHECK(e.persistent == (e.p == (void*)f.misc));
+        Slot sl;
+        sl.reserve(1000, 4, true);
+        CHECK(R.size() == 22);
+        for (int j = 1; j <= 5; ++j) {          // a failed reserve leaves the slot, and the registry, as they were
+            Count::fail(j);
+            CHECK(throws([&] { sl.reserve(5000, 4, true); }));
+            CHECK(R.size() == 22);
+        }
+        sl.reserve(5000, 4, true);
+        CHECK(R.size() == 22 && find(R.snapshot(), sl.d_txt.get<void>())->bytes == 6024);
+    }
+    CHECK(R.size() == 0 && Count::live.empty() && Count::bad_frees == 0);
+    {
+        // two threads allocating, growing, moving and freeing at once while a third reads: every entry accounted for at every join
+        std::vector<Buf<Pin>> kept[2];
+        auto work = [&](int t) {
+            for (int i = 0; i < 2000; ++i) {
+                Buf<Pin> b(8 + (size_t)i % 64, (i & 1) ? BufUse::Persistent : BufUse::Scratch);
+                b.grow(200);
+                Buf<Pin> c(std::move(b));
+                if (i % 100 == 0) kept[t].push_back(std::move(c));
+            }
+        };
+        std::thread t0(work, 0), t1(work, 1);
+        size_t seen = 0;
+        for (int i = 0; i < 200; ++i) seen += R.snapshot().size();
+        t0.join(); t1.join();
+        (void)seen;
+        CHECK(R.size() == 40);
+        for (const BufRegistry::Entry& e : R.snapshot()) CHECK(e.pinned && !e.persistent && e.bytes == 200);
+        kept[0].clear(); kept[1].clear();
+    }
+    CHECK(R.size() == 0);
+}
+
 static void dump() {
     const int shapes[4][3] = {{1, 16, 16}, {3, 64, 40}, {8, 1024, 1024}, {1, 8192, 8192}};
     for (const auto& s : shapes)
@@ -241,11 +376,14 @@ static void dump() {
 
 int main(int argc, char** argv) {
     if (argc > 1 && !std::strcmp(argv[1], "dump")) { dump(); return 0; }
+    if (argc > 1 && !std::strcmp(argv[1], "registry")) { test_registry(); std::printf("ok\n"); return 0; }
+    CHECK(!BufRegistry::on() && debug_poison_byte() == -1);       // the variable is unset: nothing below may enter the registry
     test_buf();
     test_bufset();
     test_groups();
     test_batch_room();
     test_slot();
+    CHECK(BufRegistry::get().size() == 0);
     std::printf("ok\n");
     return 0;
 }

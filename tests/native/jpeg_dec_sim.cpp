@@ -7,6 +7,8 @@
 //                                  OUT receives the coefficient scratch: int16 [component][block row][block column][64]
 //   jpeg_dec_sim batch PACK        PACK = { u32 length, bytes } ... ; one line per file: "refused <reason>" | "status S rounds R windows W"
 //   jpeg_dec_sim consts            the kernel's constants
+//   "--poison BYTE" in front of a mode (sim_poison.hpp): the staged words and their padding, the lanes' states and counts, and the staging
+//   behind every stream start as that byte; the coefficient scratch stays zero over the extent jpeg_dec_launch clears
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,6 +16,9 @@
 #include <vector>
 
 #include "../../image_restoration_platform_amd/csrc/jpeg_parse.hpp"
+#include "sim_poison.hpp"
+
+using simpoison::dirty;
 
 using namespace ire::jpegdec;
 using namespace ire::jpegparse;
@@ -23,9 +28,9 @@ struct Result { int status = 0; unsigned rounds = 0, windows = 0, longest = 0; }
 // one long stream: what one workgroup of jpeg_dec_long_kernel does
 static void decode_long(const DecImage& im, const DecTable* tabs, const DecStream& sr, const uint8_t* bytes, int16_t* coef, Result& res) {
     const uint32_t total_bits = 8u * sr.len, total_blocks = sr.nmcu * im.bpm, gblk0 = sr.mcu0 * im.bpm;
-    std::vector<uint32_t> words(kStagePadded);
-    std::vector<DecState> start(kLanes), end(kLanes), prev_end(kLanes);
-    std::vector<LaneOut> lo(kLanes);
+    std::vector<uint32_t> words = dirty<uint32_t>(kStagePadded);
+    std::vector<DecState> start = dirty<DecState>(kLanes), end = dirty<DecState>(kLanes), prev_end = dirty<DecState>(kLanes);
+    std::vector<LaneOut> lo = dirty<LaneOut>(kLanes);
     DecState carry{0, 0, 0};
     uint32_t done_blocks = 0, dc_carry[4] = {0, 0, 0, 0}, final_p = kBadPos;
     uint32_t err = 0;
@@ -65,6 +70,7 @@ static void decode_long(const DecImage& im, const DecTable* tabs, const DecStrea
             const uint32_t room = total_blocks > before ? total_blocks - before : 0;
             DecState st = start[t];
             LaneOut w;
+            simpoison::soil(&w, 1);
             err |= dec_subseq(rd, tabs, im, st, lim_of(t), room, coef, gblk0 + before, dcpred, w);
             if (w.nblk && before + w.nblk == total_blocks) { final_p = st.p; finished = true; }
             before += lo[t].nblk;
@@ -84,6 +90,7 @@ static void decode_short(const DecImage& im, const DecTable* tabs, const DecStre
     DecState st{0, 0, 0};
     uint32_t dcpred[4] = {0, 0, 0, 0};
     LaneOut o;
+    simpoison::soil(&o, 1);
     uint32_t err = dec_subseq(rd, tabs, im, st, 8u * sr.len, sr.nmcu * im.bpm, coef, sr.mcu0 * im.bpm, dcpred, o);
     if (!err && !(o.nblk == sr.nmcu * im.bpm && stream_end_ok(st.p, sr.len))) err |= kStBadEnd;
     res.status |= (int)err;
@@ -92,11 +99,16 @@ static void decode_short(const DecImage& im, const DecTable* tabs, const DecStre
 static bool decode_file(const uint8_t* file, size_t bytes, Header& hd, std::vector<int16_t>& coef, Result& res, std::string& why) {
     if (!parse_header(file, bytes, hd, why)) return false;
     const size_t room = scan_room(hd, bytes);
-    std::vector<uint8_t> stage(room);
+    std::vector<uint8_t> stage = dirty<uint8_t>(room);      // (a pinned blob used before: what lies behind a stream is not zero)
     std::vector<DecStream> streams(hd.nstreams);
     if (!split_scan(hd, file, bytes, stage.data(), room, streams.data(), why)) return false;
     uint32_t nblk = 0;
     for (int c = 0; c < hd.im.ncomp; ++c) nblk += hd.im.gridw[c] * hd.im.gridh[c];
+    // the one thing jpeg_dec_launch clears: the status words and, per image, coef_blocks(h, w) blocks of coefficients (jpeg_dec_core.hpp:
+    // the launch code's own extent).  The blocks a file really has lie inside that extent, so they start as zero under --poison too; the
+    // rest of the extent, and the dirty memory behind it, no block index of this file reaches (dec_subseq writes below the block count).
+    const size_t cleared = coef_blocks(hd.im.h, hd.im.w);
+    if (nblk > cleared) { why = "simulator: more blocks than jpeg_dec_launch clears"; return false; }
     coef.assign((size_t)nblk * 64, 0);
     for (const DecStream& s : streams) {
         if (s.len > kShortMaxBytes) decode_long(hd.im, hd.tabs, s, stage.data() + s.off, coef.data(), res);
@@ -117,6 +129,7 @@ static std::vector<uint8_t> slurp(const char* path) {
 }
 
 int main(int argc, char** argv) {
+    simpoison::take_poison(argc, argv);
     if (argc == 2 && !std::strcmp(argv[1], "consts")) {
         std::printf("lanes %d subseq_bits %d window_bits %u short_max_bytes %u\n", kLanes, kSubseqBits, kWindowBits, kShortMaxBytes);
         return 0;

@@ -13,6 +13,9 @@
 //   jpeg_dec_win_sim batch PACK               PACK = { u32 length, bytes } ... ; one line per file: "refused <reason>" | "status S"
 //   jpeg_dec_win_sim table LEN                a stream of LEN bytes: "windows W", then per window "win0 lanes last_lim"
 //   jpeg_dec_win_sim consts                   the kernels' constants
+//   "--poison BYTE" in front of a mode (sim_poison.hpp; not the `poison` word behind dump, which is about guesses): the lane records and
+//   window heads (device scratch that nothing clears), the staged words and their padding, the lanes' states and counts and the staging
+//   behind the streams start as that byte; the coefficient scratch stays zero over the extent jpeg_dec_launch clears
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,6 +23,9 @@
 #include <vector>
 
 #include "../../image_restoration_platform_amd/csrc/jpeg_parse.hpp"
+#include "sim_poison.hpp"
+
+using simpoison::dirty;
 
 using namespace ire::jpegdec;
 using namespace ire::jpegparse;
@@ -32,17 +38,17 @@ static void stage(std::vector<uint32_t>& words, unsigned n, const uint8_t* bytes
 
 static void decode_long(const DecImage& im, const DecTable* tabs, const DecStream& sr, const uint8_t* bytes, int16_t* coef, bool poison, Result& res) {
     const uint32_t total_bits = 8u * sr.len, total_blocks = sr.nmcu * im.bpm, gblk0 = sr.mcu0 * im.bpm, nwin = window_count(sr.len);
-    std::vector<LaneRec> recs((size_t)nwin * kLanes);
-    std::vector<WinHead> heads(nwin);
-    std::vector<uint32_t> words(kStagePadded), lane_words(kChainStagePadded);
+    std::vector<LaneRec> recs = dirty<LaneRec>((size_t)nwin * kLanes);
+    std::vector<WinHead> heads = dirty<WinHead>(nwin);
+    std::vector<uint32_t> words = dirty<uint32_t>(kStagePadded), lane_words = dirty<uint32_t>(kChainStagePadded);
     uint32_t err = 0;
     // A: every window by itself (jpeg_dec_spec_kernel)
     for (uint32_t wi = 0; wi < nwin; ++wi) {
         const uint32_t win0 = wi * kWindowBits, nl = window_lanes(total_bits, win0);
         stage(words, kStageWords, bytes, sr.len, win0);
         const WordReader rd{words.data(), win0};
-        std::vector<DecState> start(nl), end(nl), prev_end(nl);
-        std::vector<LaneOut> lo(nl);
+        std::vector<DecState> start = dirty<DecState>(nl), end = dirty<DecState>(nl), prev_end = dirty<DecState>(nl);
+        std::vector<LaneOut> lo = dirty<LaneOut>(nl);
         for (uint32_t t = 0; t < nl; ++t) {
             start[t] = spec_start(win0, t);
             // poison: every guess (all but the stream's very first lane, whose state is known) wrong on purpose
@@ -98,6 +104,7 @@ static void decode_long(const DecImage& im, const DecTable* tabs, const DecStrea
             const uint32_t room = total_blocks > first ? total_blocks - first : 0;
             DecState st = state_of(r.sp, r.sbk);
             LaneOut w;
+            simpoison::soil(&w, 1);
             uint32_t e = dec_subseq(rd, tabs, im, st, lane_lim(total_bits, win0, t), room, coef, gblk0 + first, dcpred, w);
             if (!e && w.nblk && first + w.nblk == total_blocks && !stream_end_ok(st.p, sr.len)) e = kStBadEnd;
             err |= e;
@@ -114,6 +121,7 @@ static void decode_short(const DecImage& im, const DecTable* tabs, const DecStre
     DecState st{0, 0, 0};
     uint32_t dcpred[4] = {0, 0, 0, 0};
     LaneOut o;
+    simpoison::soil(&o, 1);
     uint32_t err = dec_subseq(rd, tabs, im, st, 8u * sr.len, sr.nmcu * im.bpm, coef, sr.mcu0 * im.bpm, dcpred, o);
     if (!err && !(o.nblk == sr.nmcu * im.bpm && stream_end_ok(st.p, sr.len))) err |= kStBadEnd;
     res.status |= (int)err;
@@ -122,11 +130,16 @@ static void decode_short(const DecImage& im, const DecTable* tabs, const DecStre
 static bool decode_file(const uint8_t* file, size_t bytes, Header& hd, std::vector<int16_t>& coef, bool poison, Result& res, std::string& why) {
     if (!parse_header(file, bytes, hd, why)) return false;
     const size_t room = scan_room(hd, bytes);
-    std::vector<uint8_t> stage_bytes(room);
+    std::vector<uint8_t> stage_bytes = dirty<uint8_t>(room);
     std::vector<DecStream> streams(hd.nstreams);
     if (!split_scan(hd, file, bytes, stage_bytes.data(), room, streams.data(), why)) return false;
     uint32_t nblk = 0;
     for (int c = 0; c < hd.im.ncomp; ++c) nblk += hd.im.gridw[c] * hd.im.gridh[c];
+    // the one thing jpeg_dec_launch clears: the status words and, per image, coef_blocks(h, w) blocks of coefficients (jpeg_dec_core.hpp:
+    // the launch code's own extent).  The blocks a file really has lie inside that extent, so they start as zero under --poison too; the
+    // rest of the extent, and the dirty memory behind it, no block index of this file reaches (dec_subseq writes below the block count).
+    const size_t cleared = coef_blocks(hd.im.h, hd.im.w);
+    if (nblk > cleared) { why = "simulator: more blocks than jpeg_dec_launch clears"; return false; }
     coef.assign((size_t)nblk * 64, 0);
     for (const DecStream& s : streams) {
         // an exact-size copy of the stream on the heap: a read one byte past it is a sanitizer report
@@ -149,6 +162,7 @@ static std::vector<uint8_t> slurp(const char* path) {
 }
 
 int main(int argc, char** argv) {
+    simpoison::take_poison(argc, argv);
     if (argc == 2 && !std::strcmp(argv[1], "consts")) {
         std::printf("lanes %d subseq_bits %d window_bits %u short_max_bytes %u\n", kLanes, kSubseqBits, kWindowBits, kShortMaxBytes);
         return 0;

@@ -11,6 +11,10 @@
 //   jpeg_prog_sim plan FILE ACCEPT         "ok h w sampling nscans" | "refused <reason>"
 //   jpeg_prog_sim batch PACK               PACK = { u32 length, bytes } ... ; one line per file: "refused <reason>" | "status S"
 //   jpeg_prog_sim consts                   the kernels' constants
+//   "--poison BYTE" in front of a mode (sim_poison.hpp; not the `poison` word behind dump, which is about guesses): the lane records, window
+//   heads, masks and walk records (device scratch that nothing clears), the walk's LDS (masks, records, words), the staged words and their
+//   padding, the lanes' state and the staging behind the streams start as that byte; the coefficient scratch stays zero over the extent
+//   jpeg_dec_launch clears
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +23,9 @@
 #include <vector>
 
 #include "../../image_restoration_platform_amd/csrc/jpeg_parse.hpp"
+#include "sim_poison.hpp"
+
+using simpoison::dirty;
 
 using namespace ire::jpegdec;
 using namespace ire::jpegparse;
@@ -32,17 +39,17 @@ static void stage(std::vector<uint32_t>& words, unsigned n, const uint8_t* bytes
 // a long stream of a baseline or first scan: jpeg_dec_spec_kernel, jpeg_dec_chain_kernel, jpeg_dec_write_kernel
 static void decode_long(const DecImage& im, const DecTable* tabs, const DecStream& sr, const uint8_t* bytes, int16_t* coef, bool poison, Result& res) {
     const uint32_t total_bits = 8u * sr.len, total_blocks = sr.nmcu * im.bpm, gblk0 = sr.mcu0 * im.bpm, nwin = window_count(sr.len);
-    std::vector<LaneRec> recs((size_t)nwin * kLanes);
-    std::vector<WinHead> heads(nwin);
-    std::vector<uint32_t> words(kStagePadded), lane_words(kChainStagePadded);
+    std::vector<LaneRec> recs = dirty<LaneRec>((size_t)nwin * kLanes);
+    std::vector<WinHead> heads = dirty<WinHead>(nwin);
+    std::vector<uint32_t> words = dirty<uint32_t>(kStagePadded), lane_words = dirty<uint32_t>(kChainStagePadded);
     uint32_t err = 0;
     res.windows += nwin; res.maxwin = std::max(res.maxwin, nwin);
     for (uint32_t wi = 0; wi < nwin; ++wi) {
         const uint32_t win0 = wi * kWindowBits, nl = window_lanes(total_bits, win0);
         stage(words, kStageWords, bytes, sr.len, win0);
         const WordReader rd{words.data(), win0};
-        std::vector<DecState> start(nl), end(nl), prev_end(nl);
-        std::vector<LaneOut> lo(nl);
+        std::vector<DecState> start = dirty<DecState>(nl), end = dirty<DecState>(nl), prev_end = dirty<DecState>(nl);
+        std::vector<LaneOut> lo = dirty<LaneOut>(nl);
         for (uint32_t t = 0; t < nl; ++t) {
             start[t] = spec_start(win0, t);
             if (poison && start[t].p != 0) start[t] = DecState{start[t].p + 7, im.bpm > 1 ? 1u : 0u, 5};
@@ -92,6 +99,7 @@ static void decode_long(const DecImage& im, const DecTable* tabs, const DecStrea
             const uint32_t room = total_blocks > first ? total_blocks - first : 0;
             DecState st = state_of(r.sp, r.sbk);
             LaneOut w;
+            simpoison::soil(&w, 1);
             uint32_t e = dec_subseq(rd, tabs, im, st, lane_lim(total_bits, win0, t), room, coef, gblk0 + first, dcpred, w);
             if (!e && w.nblk && first + w.nblk == total_blocks && !stream_end_ok(st.p, sr.len)) e = kStBadEnd;
             err |= e;
@@ -108,6 +116,7 @@ static void decode_short(const DecImage& im, const DecTable* tabs, const DecStre
     DecState st{0, 0, 0};
     uint32_t dcpred[4] = {0, 0, 0, 0};
     LaneOut o;
+    simpoison::soil(&o, 1);
     uint32_t err = dec_subseq(rd, tabs, im, st, 8u * sr.len, sr.nmcu * im.bpm, coef, sr.mcu0 * im.bpm, dcpred, o);
     if (!err && !(o.nblk == sr.nmcu * im.bpm && stream_end_ok(st.p, sr.len))) err |= kStBadEnd;
     res.status |= (int)err;
@@ -132,8 +141,8 @@ static void dc_refine(const DecImage& im, const DecStream* streams, uint32_t nst
 
 // jpeg_dec_walk_long_kernel: lane 0's walk between the turns in which the wave stages masks and words and writes the records
 static uint32_t walk_long(const DecTable& tab, const DecImage& im, const DecStream& sr, const uint8_t* bytes, const uint64_t* masks, uint32_t* recs, uint32_t nblk, Result& res) {
-    std::vector<uint64_t> s_mask(kWalkBlocks);
-    std::vector<uint32_t> s_rec(kWalkBlocks), s_words(kWalkStagePadded);
+    std::vector<uint64_t> s_mask = dirty<uint64_t>(kWalkBlocks);
+    std::vector<uint32_t> s_rec = dirty<uint32_t>(kWalkBlocks), s_words = dirty<uint32_t>(kWalkStagePadded);
     RefState st{0, 0, 0};
     uint32_t n = 0, mb = 0, err = 0;
     const uint32_t total_bits = 8u * sr.len;
@@ -155,8 +164,9 @@ static uint32_t walk_long(const DecTable& tab, const DecImage& im, const DecStre
 
 // jpeg_dec_mask_kernel, jpeg_dec_walk_kernel / jpeg_dec_walk_long_kernel, jpeg_dec_apply_kernel
 static void ac_refine(const DecImage& im, const DecTable* tabs, const DecStream* streams, uint32_t nstreams, const uint8_t* stage_bytes, int16_t* coef, Result& res) {
-    std::vector<uint64_t> masks(im.nblocks);
+    std::vector<uint64_t> masks = dirty<uint64_t>(im.nblocks);
     std::vector<uint32_t> recs(im.nblocks, 0x5a5a5a5au);
+    simpoison::soil(recs.data(), recs.size());
     for (uint32_t g = 0; g < im.nblocks; ++g) {
         const int16_t* blk = coef + block_base(im, g);
         uint64_t m = 0;
@@ -186,12 +196,17 @@ static void ac_refine(const DecImage& im, const DecTable* tabs, const DecStream*
 static bool decode_file(const uint8_t* file, size_t bytes, File& f, std::vector<int16_t>& coef, bool poison, Result& res, std::string& why) {
     if (!plan_file(file, bytes, kAcceptProgressive, f, why)) return false;
     const size_t room = file_room(f, bytes);
-    std::vector<uint8_t> stage_bytes(room);
+    std::vector<uint8_t> stage_bytes = dirty<uint8_t>(room);
     std::vector<DecStream> streams(f.nstreams);
     if (!split_file(f, file, bytes, stage_bytes.data(), room, streams.data(), why)) return false;
     const DecImage& fr = f.hd.im;
     uint32_t nblk = 0;
     for (int c = 0; c < fr.ncomp; ++c) nblk += fr.gridw[c] * fr.gridh[c];
+    // the one thing jpeg_dec_launch clears: the status words and, per image, coef_blocks(h, w) blocks of coefficients (jpeg_dec_core.hpp:
+    // the launch code's own extent).  The blocks a file really has lie inside that extent, so they start as zero under --poison too; the
+    // rest of the extent, and the dirty memory behind it, no block index of this file reaches (dec_subseq writes below the block count).
+    const size_t cleared = coef_blocks(fr.h, fr.w);
+    if (nblk > cleared) { why = "simulator: more blocks than jpeg_dec_launch clears"; return false; }
     coef.assign((size_t)nblk * 64, 0);
     if (!f.progressive) {
         for (const DecStream& s : streams) {
@@ -233,6 +248,7 @@ static std::vector<uint8_t> slurp(const char* path) {
 }
 
 int main(int argc, char** argv) {
+    simpoison::take_poison(argc, argv);
     if (argc == 2 && !std::strcmp(argv[1], "consts")) {
         std::printf("lanes %d subseq_bits %d window_bits %u short_max_bytes %u walk_blocks %u walk_words %u max_scans %u\n", kLanes, kSubseqBits, kWindowBits, kShortMaxBytes,
                     kWalkBlocks, kWalkWords, kMaxScans);

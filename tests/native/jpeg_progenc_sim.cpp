@@ -7,6 +7,9 @@
 //                      "C name: length hex | the seven event counts"
 // Every interval is emitted into a heap buffer of exactly its bound (rounded up to the sink's 8-byte words), so ASan sees a store
 // beyond it.
+//   "--poison BYTE" as the program's arguments (sim_poison.hpp): the correction words and the table builder's work area (LDS), the codes,
+//   tables and symbol counts (device scratch the table kernel writes) and every interval's buffer start as that byte; the histograms
+//   stay zero: jpeg_progenc.hip clears exactly n * kTables * 256 words of them in front of the count pass.
 #include <cstdio>
 #include <iostream>
 #include <sstream>
@@ -14,6 +17,9 @@
 #include <vector>
 
 #include "../../image_restoration_platform_amd/csrc/jpeg_tables.hpp"
+#include "sim_poison.hpp"
+
+using simpoison::dirty;
 
 using namespace ire;
 using namespace ire::jpegprog;
@@ -24,7 +30,8 @@ struct CountSink {
     void bits(uint32_t, unsigned) {}
 };
 
-int main() {
+int main(int argc, char** argv) {
+    simpoison::take_poison(argc, argv);
     std::string line;
     while (std::getline(std::cin, line)) {
         std::istringstream in(line);
@@ -46,16 +53,17 @@ int main() {
             for (auto& c : coefs) { int v; din >> v; c = (int16_t)v; }
             if (!din) { std::fprintf(stderr, "bad coefficient line\n"); return 2; }
             Events ev{};
-            std::vector<uint32_t> corr(kCorrWords);
-            std::vector<uint32_t> hist(kTables * 256, 0u), codes(kTables * 256, 0u);
+            std::vector<uint32_t> corr = dirty<uint32_t>(kCorrWords);
+            std::vector<uint32_t> hist(kTables * 256, 0u), codes = dirty<uint32_t>(kTables * 256);
             CountSink cs{hist.data()};
             for (int sc = 0; sc < kScans; ++sc)
                 for (unsigned r = 0; r < scan_rows(g, sc); ++r) walk_interval(g, sc, r, coefs.data(), cs, corr.data(), 1u, &ev);
-            std::vector<unsigned char> bv(kTables * jpeghuff::kBitsVals);
-            std::vector<int32_t> nv(kTables);
+            std::vector<unsigned char> bv = dirty<unsigned char>(kTables * jpeghuff::kBitsVals);
+            std::vector<int32_t> nv = dirty<int32_t>(kTables);
             for (int t = 0; t < kTables; ++t) {
                 jpeghuff::HostWave wv;
-                jpeghuff::Work* work = new jpeghuff::Work;
+                jpeghuff::Work* work = new jpeghuff::Work();
+                simpoison::soil(work, 1);
                 jpeghuff::build_table(wv, *work, hist.data() + t * 256, bv.data() + t * jpeghuff::kBitsVals, &nv[t], codes.data() + t * 256);
                 delete work;
             }
@@ -69,7 +77,7 @@ int main() {
                 for (unsigned k = 0; k < hb; ++k) file.push_back(scan_head_byte(g, sc, k, bv.data(), nv.data()));
                 const size_t ibound = jpegtab::prog_interval_bound(g, q, sc), cap = (ibound + 7) / 8 * 8;      // (the sink stores words of 8 bytes)
                 for (unsigned r = 0; r < scan_rows(g, sc); ++r) {
-                    std::vector<unsigned char>* buf = new std::vector<unsigned char>(cap);
+                    std::vector<unsigned char>* buf = new std::vector<unsigned char>(dirty<unsigned char>(cap));
                     ByteSink bs{buf->data(), 0u, (unsigned)cap, codes.data(), 0, 0ull, 0u, 0ull};
                     walk_interval(g, sc, r, coefs.data(), bs, corr.data(), 1u, nullptr);
                     bs.finish(r + 1 == scan_rows(g, sc) ? 0 : 0xd0 + (int)(r & 7u));

@@ -3,6 +3,7 @@
 // shifts as array reads of the step before.  Every buffer has exactly the size the device is promised (the scanlines, the pixels, a
 // hand-off row of the pass's own units), so ASan sees what the device would not forgive.  Stand-alone, built plain and under
 // ASan + UBSan by tests/test_png_depths_native.py.
+//   [--poison BYTE] in front of either mode: png_sim.hpp
 //   dump <in.png> <rgb.bin> <scan.bin> <flags>   "refused <reason>" | "head h w ctype bpp orientation idat_bytes spans depth interlace" and
 //                                                "status N"; the RGB pixels and the filtered scanlines to the two files
 //   fuzz <in.png> <seed> <count> <flags>         png_fuzz.cpp's lines for a file of any form: the file cut at every tenth byte, then
@@ -25,7 +26,7 @@ static bool unfilter_pass(const pngparse::File& f, uint32_t p, const std::vector
     const size_t stride = 1 + (size_t)P.row_bytes;
     // the pass's scanlines as their own allocation: a read past them is a report, not a read of the next pass
     const std::vector<uint8_t> scan(scan_all.begin() + (long)P.off, scan_all.begin() + (long)(P.off + (uint64_t)P.ph * stride));
-    std::vector<uint64_t> hand(nu, 0);
+    std::vector<uint64_t> hand = pngsim::dirty<uint64_t>(nu);
     bool ok = true;
     for (uint32_t r0 = 0; r0 < P.ph; r0 += kLanes) {
         uint64_t cur[kLanes] = {}, prev[kLanes] = {};
@@ -63,8 +64,8 @@ static pngsim::Result decode(const uint8_t* file, size_t bytes, uint32_t flags) 
     if (!pngparse::plan_file(file, bytes, flags, R.f, R.why)) { R.refused = true; return R; }
     std::vector<uint8_t> in(R.f.idat_bytes);
     if (pngparse::stage(R.f, file, bytes, in.data(), in.size(), R.why) != in.size()) { R.refused = true; return R; }
-    R.scan.assign(R.f.scan_bytes(), 0);
-    R.rgb.assign((size_t)R.f.h * R.f.w * 3, 0);
+    R.scan = pngsim::dirty<uint8_t>(R.f.scan_bytes());
+    R.rgb = pngsim::dirty<uint8_t>((size_t)R.f.h * R.f.w * 3);
     R.status = pngsim::inflate(in.data(), (uint32_t)in.size(), R.scan.data(), (uint32_t)R.scan.size(), &R.rounds);
     if (R.status != 0) return R;
     if (R.f.depth == 8 && R.f.interlace == 0) { R.status = pngsim::unfilter(R.f, R.scan.data(), R.rgb.data()); return R; }      // the branch the kernel takes per record
@@ -83,6 +84,7 @@ static void put(const char* path, const std::vector<uint8_t>& v) {
 }
 
 int main(int argc, char** argv) {
+    pngsim::take_poison(argc, argv);
     if (argc == 6 && !std::strcmp(argv[1], "dump")) {
         const std::vector<uint8_t> file = pngsim::read_file(argv[2]);
         const pngsim::Result R = anysim::decode(file.data(), file.size(), (uint32_t)std::atoi(argv[5]));

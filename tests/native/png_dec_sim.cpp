@@ -1,5 +1,6 @@
 // png_dec_sim.cpp -- the device's PNG decoder on the CPU (png_sim.hpp): stand-alone, built plain and under ASan + UBSan by
 // tests/test_png_native.py.
+//   [--poison BYTE] in front of either mode: png_sim.hpp
 //   dump <in.png> <rgb.bin> <scan.bin> [flags]   "refused <reason>" | "head h w ctype bpp orientation idat_bytes spans" and "status N rounds R";
 //                                                the RGB pixels and the filtered scanlines to the two files
 //   batch <pack>                                 a pack of [u32 length | file] records: one line each, "refused <reason>" | "status N"
@@ -13,6 +14,7 @@ static void put(const char* path, const std::vector<uint8_t>& v) {
 }
 
 int main(int argc, char** argv) {
+    pngsim::take_poison(argc, argv);
     if (argc >= 5 && !std::strcmp(argv[1], "dump")) {
         const std::vector<uint8_t> file = pngsim::read_file(argv[2]);
         const pngsim::Result R = pngsim::decode(file.data(), file.size(), argc > 5 ? (uint32_t)std::atoi(argv[5]) : 0u);

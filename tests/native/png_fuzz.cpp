@@ -1,6 +1,6 @@
 // png_fuzz.cpp -- malformed PNG files through csrc/png_parse.hpp and the decoder's CPU form (png_sim.hpp): stand-alone, built plain and
 // under ASan + UBSan by tests/test_png_native.py.
-//   png_fuzz <in.png> <seed> <count>
+//   png_fuzz [--poison BYTE] <in.png> <seed> <count>
 // First the file cut at every tenth byte: "cut <bytes> refused|status N".  Then <count> single-byte mutations of the IDAT payload,
 // positions and values from a 64-bit LCG started at <seed>: "mut <offset in the payload> <new value> refused|status N".  The test
 // repeats every mutation from the printed numbers and asks zlib about the same bytes.
@@ -13,6 +13,7 @@ static void report(const pngsim::Result& R) {
 }
 
 int main(int argc, char** argv) {
+    pngsim::take_poison(argc, argv);
     if (argc != 4) { std::fprintf(stderr, "usage: png_fuzz <in.png> <seed> <count>\n"); return 2; }
     const std::vector<uint8_t> good = pngsim::read_file(argv[1]);
     uint64_t x = std::strtoull(argv[2], nullptr, 10);

@@ -1,6 +1,8 @@
 // png_sim.hpp -- csrc/png_dec.hip's two kernels on the CPU, with the lanes as a loop: the phases of csrc/png_inflate_core.hpp in the
 // kernel's order, a barrier where a lane loop ends, and the unfilter's skewed wavefront with the cross-lane shifts as array reads of
 // the step before.  Every buffer has exactly the size the device is promised, so ASan sees what the device would not forgive.
+// "--poison BYTE" in front of a program's mode (sim_poison.hpp): the inflate state before begin, the scanlines, the hand-off row and
+// the pixels -- LDS, and device scratch that png_dec_launch never clears -- start as that byte, not as zero.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -9,14 +11,18 @@
 
 #include "../../image_restoration_platform_amd/csrc/png_inflate_core.hpp"
 #include "../../image_restoration_platform_amd/csrc/png_parse.hpp"
+#include "sim_poison.hpp"
 
 namespace pngsim {
 using namespace ire;
 using pngdec::kLanes;
 
+using simpoison::dirty;
+using simpoison::take_poison;
+
 // the inflate kernel: in[0 .. in_len) -> out[0 .. total); the status
 inline int inflate(const uint8_t* in, uint32_t in_len, uint8_t* out, uint32_t total, long* rounds = nullptr) {
-    std::vector<pngdec::Inflate> mem(1);
+    std::vector<pngdec::Inflate> mem = dirty<pngdec::Inflate>(1);          // __shared__ Inflate S: LDS is never cleared
     pngdec::Inflate& S = mem[0];
     pngdec::begin(S, in, in_len, out, total);
     for (;;) {
@@ -43,7 +49,7 @@ inline int inflate(const uint8_t* in, uint32_t in_len, uint8_t* out, uint32_t to
 inline int unfilter(const pngparse::File& f, const uint8_t* scan, uint8_t* rgb) {
     const uint32_t h = (uint32_t)f.h, w = (uint32_t)f.w, bpp = (uint32_t)f.bpp;
     const size_t stride = 1 + (size_t)w * bpp;
-    std::vector<uint32_t> hand(w, 0);
+    std::vector<uint32_t> hand = dirty<uint32_t>(w);
     int status = 0;
     for (uint32_t r0 = 0; r0 < h; r0 += kLanes) {
         uint32_t cur[kLanes] = {}, prev[kLanes] = {}, ft[kLanes] = {};
@@ -79,8 +85,8 @@ inline Result decode(const uint8_t* file, size_t bytes, uint32_t flags = 0) {
     if (!pngparse::plan_file(file, bytes, flags, R.f, R.why)) { R.refused = true; return R; }
     std::vector<uint8_t> in(R.f.idat_bytes);
     if (pngparse::stage(R.f, file, bytes, in.data(), in.size(), R.why) != in.size()) { R.refused = true; return R; }
-    R.scan.assign(R.f.scan_bytes(), 0);
-    R.rgb.assign((size_t)R.f.h * R.f.w * 3, 0);
+    R.scan = dirty<uint8_t>(R.f.scan_bytes());
+    R.rgb = dirty<uint8_t>((size_t)R.f.h * R.f.w * 3);
     R.status = inflate(in.data(), (uint32_t)in.size(), R.scan.data(), (uint32_t)R.scan.size(), &R.rounds);
     if (R.status == 0) R.status = unfilter(R.f, R.scan.data(), R.rgb.data());
     return R;

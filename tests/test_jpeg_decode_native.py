@@ -1,7 +1,9 @@
 """csrc/jpeg_parse.hpp and csrc/jpeg_dec_core.hpp on the CPU (tests/native/jpeg_dec_sim.cpp: the lane algorithm of csrc/jpeg_dec.hip
 with lanes as a loop, the kernels' own step and loop compiled for the host), built plain and under ASan + UBSan: its coefficients
 equal the model's on every case, some case needs more than one round and some stream more than one window, and malformed input
-ends in a refusal or a non-zero status with no sanitizer report -- before any of it reaches a GPU."""
+ends in a refusal or a non-zero status with no sanitizer report -- before any of it reaches a GPU.  With "--poison BYTE"
+(tests/native/sim_poison.hpp: dirty LDS, lane state and staging; the coefficients cleared as jpeg_dec_launch clears them) every line,
+and the coefficients of every file with status 0, equal the plain run's."""
 import os
 import struct
 import subprocess
@@ -43,12 +45,12 @@ def consts(exe):
     return dict(zip(f[0::2], (int(v) for v in f[1::2])))
 
 
-def _dump(tmp, exe, data):
+def _dump(tmp, exe, data, poison=None):
     """-> (head fields, {status, rounds, windows, longest}, coefficients int16 flat) or the refusal's reason"""
     src, out = str(tmp / "in.jpg"), str(tmp / "out.bin")
     with open(src, "wb") as f:
         f.write(data)
-    lines = _run(exe, "dump", src, out)
+    lines = _run(exe, *(() if poison is None else ("--poison", str(poison))), "dump", src, out)
     if lines[0].startswith("refused "):
         return lines[0][len("refused "):]
     f = lines[1].split()
@@ -105,6 +107,44 @@ def test_long_streams_rounds_and_windows(exes):
         head, st, got = _dump(tmp, exe, data)
         print(name, st)
         assert st["status"] == 0 and st["windows"] >= 1 and np.array_equal(got.astype(np.int64), want), name
+
+
+def _long_files(c):
+    side = 16
+    while True:
+        data = cases.encode(cases.noise(side, side, 41), 95, 0)
+        if 8 * len(model.plan(data).streams[0][0]) >= 1.25 * c["window_bits"]:
+            break
+        side += 16
+    return {"long_noise": data, "long_420": cases.encode(cases.noise(96, 96, 42), 95, 2), "long_flat": cases.encode(np.full((512, 512, 3), 77, np.uint8), 85, 0),
+            "long_smooth422": cases.encode(cases.smooth(160, 200, 43), 95, 1, optimize=True)}
+
+
+@pytest.mark.parametrize("byte", [0x00, 0xFF, 0x5A])
+def test_nothing_depends_on_what_lds_and_scratch_held(exes, byte):
+    """the grid, the encoder's files, the long streams, the refused files and the malformed pack under the sanitizers with dirty LDS and
+    scratch, against the plain program's unpoisoned run: the same lines, and at status 0 the same coefficients"""
+    tmp, exe, exe_san = exes
+    files = dict(cases.grid_cases())
+    files.update(cases.encoder_cases())
+    files.update(cases.sweep_cases())
+    files.update(_long_files(consts(exe)))
+    files.update({"refused_" + k: v[0] for k, v in cases.refused_cases().items()})
+    for name, data in files.items():
+        a, b = _dump(tmp, exe_san, data, poison=byte), _dump(tmp, exe, data)
+        if isinstance(a, str) or isinstance(b, str):
+            assert a == b, name
+            continue
+        assert a[0] == b[0] and a[1] == b[1], (name, a[:2], b[:2])
+        if a[1]["status"] == 0:
+            assert np.array_equal(a[2], b[2]), name
+    _, variants = cases.malformed_pack()
+    pack = str(tmp / "pack_poison.bin")
+    with open(pack, "wb") as f:
+        for _, data in variants:
+            f.write(struct.pack("<I", len(data)) + data)
+    lines = _run(exe_san, "--poison", str(byte), "batch", pack)
+    assert len(lines) == len(variants) and lines == _run(exe, "batch", pack)
 
 
 def test_plan_reasons_equal_the_models(exes):

@@ -2,7 +2,9 @@
 spec, chain and write kernels with windows and lanes as loops, over csrc/jpeg_dec_core.hpp's own code), built plain and under
 ASan + UBSan: its coefficients equal the model's with honest and with deliberately wrong guesses, every window of the test files
 synchronises, the window arithmetic holds at the window's byte boundaries, a stream whose last subsequence is exactly full decodes,
-and corrupt multi-window files end in a non-zero status with no sanitizer report."""
+and corrupt multi-window files end in a non-zero status with no sanitizer report.  With "--poison BYTE" (tests/native/sim_poison.hpp:
+the lane records and window heads, which nothing on the device clears, the staged words and the lanes' state start as that byte) every
+line, and the coefficients of every file with status 0, equal the plain run's."""
 import os
 import struct
 import subprocess
@@ -45,12 +47,12 @@ def _consts(exe):
     return dict(zip(f[0::2], (int(v) for v in f[1::2])))
 
 
-def _dump(tmp, exe, data, poison=False):
-    """-> (head fields, status, chain re-decodes per window, coefficients int16 flat)"""
+def _dump(tmp, exe, data, poison=False, dirty=None):
+    """-> (head fields, status, chain re-decodes per window, coefficients int16 flat); poison: wrong guesses; dirty: --poison BYTE"""
     src, out = str(tmp / "in.jpg"), str(tmp / "out.bin")
     with open(src, "wb") as f:
         f.write(data)
-    lines = _run(exe, "dump", src, out, *(["poison"] if poison else []))
+    lines = _run(exe, *(() if dirty is None else ("--poison", str(dirty))), "dump", src, out, *(["poison"] if poison else []))
     assert lines[0].startswith("ok "), lines[0]
     f = lines[1].split()
     again = [] if f[5] == "-" else [int(v) for v in f[5].split(",")]
@@ -97,6 +99,33 @@ def test_multi_window_files_equal_the_model_and_every_window_synchronises(exes, 
             assert status == 0 and len(again) == windows and again[0] == 0, (name, again)
             assert all(a < c["lanes"] for a in again), (name, again)
             assert np.array_equal(got.astype(np.int64), want), (name, poison)
+
+
+@pytest.mark.parametrize("byte", [0x00, 0xFF, 0x5A])
+def test_nothing_depends_on_what_lds_and_scratch_held(exes, byte):
+    """the grid's sanitizer subset, the encoder's files, the multi-window files (honest and wrong guesses), the full-last-subsequence file
+    and the 200 corruptions of the two-window file, under the sanitizers with dirty records, heads, LDS and lane state, against the plain
+    program's unpoisoned run"""
+    tmp, exe, exe_san = exes
+    c = _consts(exe)
+    files = {k: v for k, v in cases.grid_cases().items() if k.startswith(("33x47", "grey_17x13", "5x3", "64x48", "40x88"))}
+    files.update(cases.encoder_cases())
+    files.update({k: v[0] for k, v in wcases.multi_window_files().items()})
+    full, _ = wcases.full_last_subsequence_file(c["subseq_bits"] // 8, c["short_max_bytes"])
+    files["full_last_subsequence"] = full
+    for name, data in files.items():
+        for guesses in (False, True):
+            a, b = _dump(tmp, exe_san, data, guesses, dirty=byte), _dump(tmp, exe, data, guesses)
+            assert a[:3] == b[:3], (name, guesses, a[:3], b[:3])
+            if a[1] == 0:
+                assert np.array_equal(a[3], b[3]), (name, guesses)
+    _, variants = wcases.corrupted_two_window_files()
+    pack = str(tmp / "pack_poison.bin")
+    with open(pack, "wb") as f:
+        for _, data in variants:
+            f.write(struct.pack("<I", len(data)) + data)
+    lines = _run(exe_san, "--poison", str(byte), "batch", pack)
+    assert len(lines) == 200 and lines == _run(exe, "batch", pack)
 
 
 def test_the_window_table_at_the_windows_byte_boundaries(exes):

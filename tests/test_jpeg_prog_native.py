@@ -2,7 +2,9 @@
 decoded the way csrc/jpeg_dec.hip decodes it, with lanes, windows, waves and launches as loops, the steps the kernels' own compiled
 for the host), built plain and under ASan + UBSan as a stand-alone program: its coefficients equal the model's on every case, its
 refusals carry the model's reasons, and malformed input ends in a refusal or a non-zero status with no sanitizer report -- before
-any of it reaches a GPU."""
+any of it reaches a GPU.  With "--poison BYTE" (tests/native/sim_poison.hpp: the lane records, window heads, masks and walk records,
+the walk's LDS, the staged words and the lanes' state dirty; the coefficients cleared as jpeg_dec_launch clears them) every line, and
+the coefficients of every file with status 0, equal the plain run's."""
 import os
 import struct
 import subprocess
@@ -46,12 +48,12 @@ def consts(exe):
     return dict(zip(f[0::2], (int(v) for v in f[1::2])))
 
 
-def _dump(tmp, exe, data, poison=False):
-    """-> (head fields, the status line's fields, coefficients int16 flat) or the refusal's reason"""
+def _dump(tmp, exe, data, poison=False, dirty=None):
+    """-> (head fields, the status line's fields, coefficients int16 flat) or the refusal's reason; poison: wrong guesses; dirty: --poison BYTE"""
     src, out = str(tmp / "in.jpg"), str(tmp / "out.bin")
     with open(src, "wb") as f:
         f.write(data)
-    lines = _run(exe, "dump", src, out, *(["poison"] if poison else []))
+    lines = _run(exe, *(() if dirty is None else ("--poison", str(dirty))), "dump", src, out, *(["poison"] if poison else []))
     if lines[0].startswith("refused "):
         return lines[0][len("refused "):]
     f = lines[1].split()
@@ -85,6 +87,38 @@ def test_coefficients_equal_the_model(exes):
     san = dict(written)
     san.update({k: v for k, v in grid.items() if k.startswith(("33x47", "grey_17x13", "5x3"))})
     assert _compare(tmp, exe_san, san) >= 72 + 15
+
+
+@pytest.mark.parametrize("byte", [0x00, 0xFF, 0x5A])
+def test_nothing_depends_on_what_lds_and_scratch_held(exes, byte):
+    """every file of the writer, the Pillow grid, the 64-scan file, a baseline file, the multi-window files (wrong guesses too), the flat
+    file, the long-refinement file, the refused files, the malformed pack and the corrupt refinement scans, under the sanitizers with
+    dirty scratch and LDS, against the plain program's unpoisoned run"""
+    tmp, exe, exe_san = exes
+    files = {k: v[0] for k, v in prog.writer_cases().items()}
+    files.update(prog.pillow_grid_cases())
+    files["cap"] = prog.cap_scans_file()[0]
+    files["baseline"] = cases.encode(cases.noise(47, 33, 3), 85, 2)
+    files["flat"] = prog.flat_file()
+    files["long_refinement"] = prog.long_refinement_file()
+    files.update({"refused_" + k: v[0] for k, v in prog.refused_cases().items()})
+    many = prog.multi_window_files(consts(exe)["window_bits"])
+    for name, data in list(files.items()) + [(k + "_guesses", v) for k, v in many.items()] + list(many.items()):
+        guesses = name.endswith("_guesses")
+        a, b = _dump(tmp, exe_san, data, guesses, dirty=byte), _dump(tmp, exe, data, guesses)
+        if isinstance(a, str) or isinstance(b, str):
+            assert a == b, name
+            continue
+        assert a[0] == b[0] and a[1] == b[1], (name, a[:2], b[:2])
+        if a[1]["status"] == 0:
+            assert np.array_equal(a[2], b[2]), name
+    for which, variants in (("malformed", prog.malformed_pack()[1]), ("refine", prog.corrupt_refinement_candidates()[1])):
+        pack = str(tmp / ("poison_%s.bin" % which))
+        with open(pack, "wb") as f:
+            for _, data in variants:
+                f.write(struct.pack("<I", len(data)) + data)
+        lines = _run(exe_san, "--poison", str(byte), "batch", pack)
+        assert len(lines) == len(variants) and lines == _run(exe, "batch", pack), which
 
 
 def test_a_baseline_file_takes_the_same_way(exes):

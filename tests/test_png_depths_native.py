@@ -3,7 +3,8 @@ The plan through the C ABI (every accepted form with its depth and interlace, ev
 files refused with the old reasons without the accept bit, the flag rules); tests/native/png_any_sim.cpp -- csrc/png_adam7_core.hpp
 with the lanes of csrc/png_dec.hip's png_unfilter_any_kernel as a loop -- built plain and under ASan + UBSan and run directly: its
 RGB equals Pillow's and its scanlines equal zlib.decompress on every case of tests/png_depth_cases.py; truncations and mutations end
-in a refusal or a status, status 0 exactly where zlib yields the passes' scanlines with filter bytes 0..4."""
+in a refusal or a status, status 0 exactly where zlib yields the passes' scanlines with filter bytes 0..4.  With "--poison BYTE"
+(tests/native/png_sim.hpp: dirty LDS and scratch) every line, and the pixels and scanlines of every file with status 0, stay the same."""
 import ctypes
 import os
 import subprocess
@@ -151,12 +152,12 @@ def exes(tmp_path_factory):
     return {"tmp": tmp, "sim": _build(tmp, "sim", ["-O2"]), "sim_san": _build(tmp, "sim_san", ["-O1", "-fsanitize=address,undefined"])}
 
 
-def _dump(ex, exe, data, flags=ALL):
+def _dump(ex, exe, data, flags=ALL, poison=None):
     tmp = ex["tmp"]
     src, rgb, scan = str(tmp / "in.png"), str(tmp / "rgb.bin"), str(tmp / "scan.bin")
     with open(src, "wb") as f:
         f.write(data)
-    lines = _run(ex[exe], "dump", src, rgb, scan, str(flags))
+    lines = _run(ex[exe], *(() if poison is None else ("--poison", str(poison))), "dump", src, rgb, scan, str(flags))
     if lines[0].startswith("refused "):
         return lines[0][len("refused "):]
     return [int(v) for v in lines[0].split()[1:]], int(lines[1].split()[1]), np.fromfile(rgb, np.uint8), np.fromfile(scan, np.uint8)
@@ -195,6 +196,31 @@ def test_a_filter_byte_of_5_on_a_pass_first_row_is_status_16(exes):
     bad, good = cases.bad_filter_adam7()
     assert _dump(exes, "sim_san", bad)[1] == 16 and _dump(exes, "sim_san", good)[1] == 0
     assert not cases.zlib_says_ok(cases.idat_stream(bad), cases.head_of(bad))[0]
+
+
+@pytest.mark.filterwarnings("ignore:Palette images with Transparency")
+@pytest.mark.parametrize("byte", [0x00, 0xFF, 0x5A])
+def test_nothing_depends_on_what_lds_and_scratch_held(exes, byte):
+    """every accepted case, the old form, the filter-byte-5 file, the refused files and both fuzz files' cuts and mutations, under the
+    sanitizers with dirty LDS and scratch, against the plain program's unpoisoned run"""
+    files = dict(cases.accept_cases())
+    files.update({"old_" + k: v for k, v in old_cases.shape_cases().items()})
+    files.update({"refused_" + k: v[0] for k, v in cases.refused_cases().items()})
+    files["bad_filter"], files["good_filter"] = cases.bad_filter_adam7()
+    for name, data in files.items():
+        a, b = _dump(exes, "sim_san", data, poison=byte), _dump(exes, "sim", data)
+        if isinstance(a, str) or isinstance(b, str):
+            assert a == b, name
+            continue
+        assert a[0] == b[0] and a[1] == b[1], (name, a[:2], b[:2])
+        if a[1] == 0:              # (what a flagged file leaves in its pixels is nobody's result)
+            assert np.array_equal(a[2], b[2]) and np.array_equal(a[3], b[3]), name
+    for which, good in cases.fuzz_files().items():
+        src = str(exes["tmp"] / ("fuzz_poison_%s.png" % which))
+        with open(src, "wb") as f:
+            f.write(good)
+        lines = _run(exes["sim_san"], "--poison", str(byte), "fuzz", src, str(cases.FUZZ_SEED), "200", str(ALL))
+        assert len(lines) > 200 and lines == _run(exes["sim"], "fuzz", src, str(cases.FUZZ_SEED), "200", str(ALL)), which
 
 
 @pytest.mark.parametrize("which", ["adam7_plte4", "rgb16"])

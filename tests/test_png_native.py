@@ -2,7 +2,11 @@
 csrc/png_dec.hip with lanes as a loop), stand-alone programs built plain and under ASan + UBSan and run directly: the RGB equals
 Pillow's and the filtered scanlines equal zlib.decompress on every case; truncations and mutations end in a refusal or a status with
 no sanitizer report, and the status is 0 exactly where zlib decompresses the stream to exactly h * (1 + w * bpp) bytes whose filter
-bytes are 0..4 -- before any PNG reaches a GPU."""
+bytes are 0..4 -- before any PNG reaches a GPU.
+
+With "--poison BYTE" the simulator's stand-ins for LDS and for device scratch that no launch clears (the inflate state, the scanlines,
+the hand-off row, the pixels) start as that byte: every line printed, and the pixels and scanlines of every file with status 0, must
+equal the unpoisoned run's, under the sanitizers."""
 import os
 import struct
 import subprocess
@@ -56,12 +60,12 @@ def zlib_says_ok(z, head):
     return len(d) == h * stride and all(d[y * stride] <= 4 for y in range(h)), False
 
 
-def _dump(ex, exe, data, flags=0):
+def _dump(ex, exe, data, flags=0, poison=None):
     tmp = ex["tmp"]
     src, rgb, scan = str(tmp / "in.png"), str(tmp / "rgb.bin"), str(tmp / "scan.bin")
     with open(src, "wb") as f:
         f.write(data)
-    lines = _run(ex[exe], "dump", src, rgb, scan, str(flags))
+    lines = _run(ex[exe], *(() if poison is None else ("--poison", str(poison))), "dump", src, rgb, scan, str(flags))
     if lines[0].startswith("refused "):
         return lines[0][len("refused "):]
     head = [int(v) for v in lines[0].split()[1:]]
@@ -153,6 +157,33 @@ def test_corrupt_data_gets_ten_distinct_statuses(exes):
         statuses[name] = got[1]
     print(statuses)
     assert len(set(statuses.values())) == 10
+
+
+def _same(a, b, name):
+    """two _dump results: the same refusal, or the same head and status and, at status 0, the same pixels and scanlines (what a flagged
+    file leaves in its pixels is nobody's result: the caller is told to ignore them)"""
+    if isinstance(a, str) or isinstance(b, str):
+        assert a == b, name
+        return
+    assert a[0] == b[0] and a[1] == b[1] and a[2] == b[2], (name, a[:3], b[:3])
+    if a[1] == 0:
+        assert np.array_equal(a[3], b[3]) and np.array_equal(a[4], b[4]), name
+
+
+@pytest.mark.filterwarnings("ignore:Palette images with Transparency")
+@pytest.mark.parametrize("byte", [0x00, 0xFF, 0x5A])
+def test_nothing_depends_on_what_lds_and_scratch_held(exes, byte):
+    """this file's good cases, its refused and corrupt ones, and the cuts and mutations of the fuzz file, with dirty LDS and scratch"""
+    files = dict(cases.accept_cases())
+    files.update({"refused_" + k: v[0] for k, v in cases.refused_cases().items()})
+    files.update({"corrupt_" + k: v for k, v in cases.corrupt_cases().items()})
+    for name, data in files.items():
+        _same(_dump(exes, "sim_san", data, poison=byte), _dump(exes, "sim", data), name)
+    src = str(exes["tmp"] / "fuzz_poison.png")
+    with open(src, "wb") as f:
+        f.write(cases.fuzz_file())
+    lines = _run(exes["fuzz_san"], "--poison", str(byte), src, str(cases.FUZZ_SEED), "200")
+    assert len(lines) > 200 and lines == _run(exes["fuzz"], src, str(cases.FUZZ_SEED), "200")
 
 
 def _pillow_reads(data, want):

@@ -14,35 +14,24 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib", "libire.so")
 
 # (source, extra flags).  classifier.hip carries the IEEE-exact double finalize: no FMA contraction.
+# IRE_W4_TL=1 builds the workgroup-timeline diagnostic into conv_w4 / conv_pc / conv_pk (tools/r04_tl.sh); PK_TICKS and PK_DEFS reach the
+# two build-time arms conv_pk.hip still carries (see its header).
+_TL = ["-DIRE_W4_TL"] if os.environ.get("IRE_W4_TL") else []
 SOURCES = [
-    ("classifier.hip", ["-ffp-contract=off"] + (["-DCLS_ABL=" + os.environ["CLS_ABL"]] if os.environ.get("CLS_ABL") else [])),
+    ("classifier.hip", ["-ffp-contract=off"]),
     ("conv_mfma.hip", []),
-    ("conv_rb.hip", (["-DIRE_RB_ABLATE"] if os.environ.get("IRE_RB_ABLATE") else []) +
-     (["-DIRE_RB_NGP64=" + os.environ["IRE_RB_NGP64"]] if os.environ.get("IRE_RB_NGP64") else [])),
-    ("conv_w4.hip", (["-DIRE_W4_STAMPS"] if os.environ.get("IRE_RB_ABLATE") else []) +
-     (["-DIRE_W4_TICKS"] if os.environ.get("IRE_RB_ABLATE") == "2" else []) +
-     (["-DW4_TEPI=" + os.environ["IRE_W4_TEPI"]] if os.environ.get("IRE_W4_TEPI") else []) +
-     (["-DIRE_W4_TL"] if os.environ.get("IRE_W4_TL") else [])),
-    ("conv_up.hip", (["-DIRE_UP_ABL=" + os.environ["IRE_UP_ABL"]] if os.environ.get("IRE_UP_ABL") else []) +
-     (["-DIRE_UP_D=" + os.environ["IRE_UP_D"]] if os.environ.get("IRE_UP_D") else []) +
-     (["-DIRE_UP_TEPI=" + os.environ["IRE_UP_TEPI"]] if os.environ.get("IRE_UP_TEPI") else [])),
-    ("conv_upq.hip", os.environ.get("UQ_DEFS", "").split()),
-    ("conv_dnq.hip", os.environ.get("DQ_DEFS", "").split()),
-    ("conv_down.hip", (["-DDN_LD_NT=" + os.environ["DN_LD_NT"]] if os.environ.get("DN_LD_NT") else [])),
+    ("conv_rb.hip", []),
+    ("conv_w4.hip", _TL),
+    ("conv_up.hip", []),
+    ("conv_upq.hip", []),
+    ("conv_dnq.hip", []),
+    ("conv_down.hip", []),
     ("conv_stem.hip", []),
     ("conv_f8.hip", []),
-    ("conv_pc.hip", (["-DC3_ABL=" + os.environ["C3_ABL"]] if os.environ.get("C3_ABL") else []) +
-     (["-DC3_PRIO=" + os.environ["C3_PRIO"]] if os.environ.get("C3_PRIO") else []) +
-     (["-DC3_RES_PRE=" + os.environ["C3_RES_PRE"]] if os.environ.get("C3_RES_PRE") else []) +
-     (["-DC3_TEPI=" + os.environ["C3_TEPI"]] if os.environ.get("C3_TEPI") else []) +
-     (["-DC3_TEPI64=" + os.environ["C3_TEPI64"]] if os.environ.get("C3_TEPI64") else []) +
-     (["-DIRE_LD_ONCE32=" + os.environ["IRE_LD_ONCE32"]] if os.environ.get("IRE_LD_ONCE32") else []) +
-     (["-DC3_PROD8=" + os.environ["C3_PROD8"]] if os.environ.get("C3_PROD8") else []) +
-     (["-DIRE_PC_TICKS"] if os.environ.get("IRE_RB_ABLATE") == "2" else []) + (["-DIRE_W4_TL"] if os.environ.get("IRE_W4_TL") else [])),
-    ("conv_pk.hip", (["-DPK_ABL=" + os.environ["PK_ABL"]] if os.environ.get("PK_ABL") else []) +
-     (["-DPK_TICKS"] if os.environ.get("PK_TICKS") else []) + (["-DIRE_W4_TL"] if os.environ.get("IRE_W4_TL") else []) + os.environ.get("PK_DEFS", "").split()),
+    ("conv_pc.hip", _TL),
+    ("conv_pk.hip", _TL + (["-DPK_TICKS"] if os.environ.get("PK_TICKS") else []) + os.environ.get("PK_DEFS", "").split()),
     ("gn.hip", []),
-    ("fusion.hip", (["-DFUSE_FL=" + os.environ["FUSE_FL"]] if os.environ.get("FUSE_FL") else [])),
+    ("fusion.hip", []),
     ("preprocess.hip", []),
     ("encode.hip", []),
     ("deflate.hip", []),
@@ -61,10 +50,6 @@ SOURCES = [
 # IRE_SLP=1 builds with the vectorizer on (A/B).
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-D__HIP_PLATFORM_AMD__"] + ([] if os.environ.get("IRE_SLP") == "1" else ["-fno-slp-vectorize"]) + \
-         (["-DIRE_ST_LINE=" + os.environ["IRE_ST_LINE"]] if os.environ.get("IRE_ST_LINE") else []) + \
-         (["-DIRE_ST_PART=" + os.environ["IRE_ST_PART"]] if os.environ.get("IRE_ST_PART") else []) + \
-         (["-DIRE_LD_ONCE=" + os.environ["IRE_LD_ONCE"]] if os.environ.get("IRE_LD_ONCE") else []) + \
-         (["-DIRE_LD_IN=" + os.environ["IRE_LD_IN"]] if os.environ.get("IRE_LD_IN") else []) + \
          os.environ.get("IRE_XFLAGS", "").split()          # extra compiler flags for build-time A/B (tools/s2_xflags.sh)
 
 def _hipcc():

@@ -28,9 +28,6 @@ constexpr int CG = CT_W / 4;                    // groups per tile row
 constexpr int PL_ROWS = CT_H + 2;               // halo rows -1 .. 16
 constexpr int PL_WORDS = CG + 2;                // plane row = pixels x0-4 .. x0+259 as packed u8 words: pixel x0+dx is byte 4+dx
 constexpr int NBUCKETS = 5001;
-#ifndef CLS_ABL
-#define CLS_ABL 0     // timing ablations (results wrong by design): 1 no grey tables, 2 no phase B, 4 no phase C, 8 no atomics / finalize
-#endif
 constexpr unsigned DIV44_M = 11916u;            // floor(n / 44) == (n * 11916) >> 19 for every n < 32768 (11916 * 44 = 2^19 + 16)
 
 struct ClsLds {
@@ -114,7 +111,6 @@ __global__ __launch_bounds__(256) void classifier_scan_kernel(const uint8_t* __r
     for (int i = 0; i < CLS_NSUMS; ++i) acc[i] = 0;
 
     auto grey_of = [&](unsigned r, unsigned g, unsigned b) -> unsigned {
-        if constexpr (CLS_ABL & 1) return g;
         const unsigned y = L.wR[r] + L.wG[g] + L.wB[b];
         unsigned gv = L.inv[y >> 17];
         gv += (y >= L.thr[gv + 1]) ? 1u : 0u;
@@ -203,7 +199,6 @@ __global__ __launch_bounds__(256) void classifier_scan_kernel(const uint8_t* __r
         if (tile + (int)gridDim.x < ntiles) load_tile(tile + gridDim.x);      // in flight across phases B and C
 
         // phase B: horizontal {12,20,12}/44 pass, rounded to u8; rows 4 rb .. 4 rb + 3, and plane rows 16 + rb for rb < 2
-        if constexpr (!(CLS_ABL & 2))
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
             const int py = k < 4 ? rb * 4 + k : CT_H + rb;
@@ -218,7 +213,7 @@ __global__ __launch_bounds__(256) void classifier_scan_kernel(const uint8_t* __r
         __syncthreads();
 
         // phase C: this thread's 4 x 4 pixels
-        if constexpr (!(CLS_ABL & 4)) {
+        {
             const int gx = x0 + 4 * g;
             unsigned xm = 0;                                   // 0xff per pixel of the group that is inside the image
 #pragma unroll
@@ -290,7 +285,6 @@ __global__ __launch_bounds__(256) void classifier_scan_kernel(const uint8_t* __r
         __syncthreads();  // planes are rewritten by the next tile
     }
 
-    if constexpr (CLS_ABL & 8) { if (acc[0] + acc[5] + acc[9] + acc[13] == 0x123456789ull) sums[0] = 1; return; }
     // workgroup reduction -> 14 u64 atomics per workgroup
     const int wave = tid >> 6, lane = tid & 63;
 #pragma unroll

@@ -26,12 +26,6 @@ namespace ire {
 
 namespace {
 
-#ifndef DQ_ST
-#define DQ_ST IRE_ST_LINE   // cache policy of the output stores (conv_mfma.hpp): build-time A/B
-#endif
-#ifndef DQ_ABL
-#define DQ_ABL 0      // timing ablations (results wrong by design): 2 no epilogue, 4 no MFMA loop, 8 epilogue without its stores, 16 without its statistics, 32 without the pre-issued DMA
-#endif
 
 constexpr int DQ_THREADS = 512;
 constexpr int DQ_TH = 16, DQ_TW = 32, DQ_IH = 17, DQ_IW = 33, DQ_NT = 128, DQ_NTL = 4;
@@ -203,38 +197,33 @@ __global__ __launch_bounds__(DQ_THREADS) void conv_dnq_kernel(ConvArgs a) {
             }
             const unsigned char* ib = smem + BUF * DQ_TILE_BYTES;
             const unsigned char* wb = smem + DQ_W_BASE + BUF * DQ_SLAB_BYTES + b_off;
-            if constexpr (!(DQ_ABL & 4)) {
-                constexpr int NS = 2 * NTAPS, NG = NS * NTL;
-                auto rd_b = [&](int st, int j) __attribute__((always_inline)) -> bf16x8_t {
-                    return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(wb + (((st >> 1) * 4 + 2 * (st & 1)) * NT + j * 32) * 16));
-                };
-                auto rd_a = [&](int st, int m) __attribute__((always_inline)) -> bf16x8_t {
-                    return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ib + (a_off[m][dq_tap_win(PH, st >> 1)] ^ ((st & 1) << 5))));
-                };
-                bf16x8_t bq[2], aq[2][2];
-                bq[0] = rd_b(0, 0);
-                aq[0][0] = rd_a(0, 0); aq[0][1] = rd_a(0, 1);
+            constexpr int NS = 2 * NTAPS, NG = NS * NTL;
+            auto rd_b = [&](int st, int j) __attribute__((always_inline)) -> bf16x8_t {
+                return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(wb + (((st >> 1) * 4 + 2 * (st & 1)) * NT + j * 32) * 16));
+            };
+            auto rd_a = [&](int st, int m) __attribute__((always_inline)) -> bf16x8_t {
+                return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ib + (a_off[m][dq_tap_win(PH, st >> 1)] ^ ((st & 1) << 5))));
+            };
+            bf16x8_t bq[2], aq[2][2];
+            bq[0] = rd_b(0, 0);
+            aq[0][0] = rd_a(0, 0); aq[0][1] = rd_a(0, 1);
 #pragma unroll
-                for (int st = 0; st < NS; ++st)
+            for (int st = 0; st < NS; ++st)
 #pragma unroll
-                    for (int j = 0; j < NTL; ++j) {
-                        const int g = st * NTL + j;
-                        // the next stage's DMA pieces, spread over the k-loop: piece i rides in front of MFMA pair (i NG) / 10
+                for (int j = 0; j < NTL; ++j) {
+                    const int g = st * NTL + j;
+                    // the next stage's DMA pieces, spread over the k-loop: piece i rides in front of MFMA pair (i NG) / 10
 #pragma unroll
-                        for (int i = 0; i < 10; ++i)
-                            if ((i * NG) / 10 == g && i < P.n) glds16(P.src[i], P.dst[i]);
-                        if (g + 1 < NG) bq[(g + 1) & 1] = rd_b((g + 1) / NTL, (g + 1) % NTL);
-                        if (st + 1 < NS && j == 1) aq[(st + 1) & 1][0] = rd_a(st + 1, 0);
-                        if (st + 1 < NS && j == 2) aq[(st + 1) & 1][1] = rd_a(st + 1, 1);
-                        __builtin_amdgcn_sched_barrier(0);
+                    for (int i = 0; i < 10; ++i)
+                        if ((i * NG) / 10 == g && i < P.n) glds16(P.src[i], P.dst[i]);
+                    if (g + 1 < NG) bq[(g + 1) & 1] = rd_b((g + 1) / NTL, (g + 1) % NTL);
+                    if (st + 1 < NS && j == 1) aq[(st + 1) & 1][0] = rd_a(st + 1, 0);
+                    if (st + 1 < NS && j == 2) aq[(st + 1) & 1][1] = rd_a(st + 1, 1);
+                    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                        for (int m = 0; m < 2; ++m) acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq[g & 1], aq[st & 1][m], acc[m][j], 0, 0, 0);   // D[cout][pixel]
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 10; ++i) if (i < P.n) glds16(P.src[i], P.dst[i]);
-            }
+                    for (int m = 0; m < 2; ++m) acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq[g & 1], aq[st & 1][m], acc[m][j], 0, 0, 0);   // D[cout][pixel]
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             ++stage_no;
             cs = cn; cn = cursor.next();
             // the next stage is staged; nobody reads this stage's pair any more
@@ -256,20 +245,14 @@ __global__ __launch_bounds__(DQ_THREADS) void conv_dnq_kernel(ConvArgs a) {
         phase(std::integral_constant<int, 3>{});
         // ---- epilogue (conv_upq.hip): the pieces of the stage after next (the next item's stage 1: pair 1) first, then 8 passes of 8
         // pixels x 128 couts through the wave's patch, 16 stores of whole 256-B pixel runs
-        if (stage_no + 1 < S && !(DQ_ABL & 32)) {
+        if (stage_no + 1 < S) {
             Plan P;
             plan_stage(std::integral_constant<int, 0>{}, cn, 1, P);       // the next item's stage 1 = phase 0, chunk 1
 #pragma unroll
             for (int i = 0; i < 10; ++i) if (i < P.n) glds16(P.src[i], P.dst[i]);
             pre_issued = true;
         }
-        if constexpr (DQ_ABL & 2) {
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int j = 0; j < NTL; ++j) asm volatile("" :: "v"(acc[m][j]));
-            if (pre_issued) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
+        {
             unsigned char* patch = smem + DQ_PATCH_BASE + wave * DQ_PATCH_BYTES;
             int l_e = lane, w_e = wave;
             asm volatile("" : "+v"(l_e), "+v"(w_e));
@@ -322,7 +305,6 @@ __global__ __launch_bounds__(DQ_THREADS) void conv_dnq_kernel(ConvArgs a) {
                         const u32x4_t v = *reinterpret_cast<const u32x4_t*>(patch + p * PITCH + ((cc_r ^ p) << 4));
                         const unsigned w[4] = {v.x, v.y, v.z, v.w};
                         float s1 = 0.f, q1 = 0.f;
-                        if constexpr (!(DQ_ABL & 16))
 #pragma unroll
                         for (int d = 0; d < 4; ++d) {
                             const bf16x2_t bv = __builtin_bit_cast(bf16x2_t, w[d]);
@@ -331,8 +313,7 @@ __global__ __launch_bounds__(DQ_THREADS) void conv_dnq_kernel(ConvArgs a) {
                         }
                         const bool ok = trow[m] && tcol0 + 8 * e + 4 * k < a.Wout;
                         ssum += ok ? s1 : 0.f; qsum += ok ? q1 : 0.f;
-                        if constexpr (DQ_ABL & 8) asm volatile("" :: "v"(v));
-                        else __builtin_amdgcn_raw_buffer_store_b128(v, orsrc, ok ? toffs[m] + (unsigned)(2 * e + k) * cstep : 0xffffffffu, 0, DQ_ST);
+                        __builtin_amdgcn_raw_buffer_store_b128(v, orsrc, ok ? toffs[m] + (unsigned)(2 * e + k) * cstep : 0xffffffffu, 0, IRE_ST_LINE);
                     }
                 }
             // this lane's chunk cc_r over its read-backs; the other lanes with the same chunk sit 16 apart
@@ -340,7 +321,6 @@ __global__ __launch_bounds__(DQ_THREADS) void conv_dnq_kernel(ConvArgs a) {
             ssum = swap32_add(ssum); qsum = swap32_add(qsum);
             if (l_e < 16) *reinterpret_cast<float2*>(red + red_par * (8 * 32) + (wave * 16 + cc_r) * 2) = make_float2(ssum, qsum);
             st_img = it.img; st_tile = it.tile; st_cout0 = cout0; st_par = red_par; red_par ^= 1;
-            if constexpr (DQ_ABL & 8) { if (pre_issued) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }      // (no stores behind the pieces: the counted wait would let them pass)
         }
     }
     __syncthreads();                     // the last item's chunk sums

@@ -23,9 +23,6 @@ namespace ire {
 
 namespace {
 
-#ifndef DN_LD_NT
-#define DN_LD_NT 0     // 1: the input rows non-temporal (build-time A/B)
-#endif
 constexpr int DN_THREADS = 512;
 constexpr int DN_TH = 16, DN_TW = 32;                  // output tile
 constexpr int DN_IH = DN_TH + 1, DN_IW = DN_TW + 1;    // phase-image halo tile: offsets -1 .. 0
@@ -122,11 +119,7 @@ __global__ __launch_bounds__(DN_THREADS) void conv_down_kernel(ConvArgs a) {
 #pragma unroll
         for (int i = 0; i < DN_IN_ITERS; ++i) {
             const unsigned off = ((okp >> i) & 1u) ? coff[i] + delta : 0xffffffffu;
-#if DN_LD_NT
-            asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen nt" : "+v"(R.v[i]) : "v"(off), "s"(irsrc) : "memory");
-#else
             asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "+v"(R.v[i]) : "v"(off), "s"(irsrc) : "memory");      // out of range reads as zero: the padding
-#endif
         }
     };
     auto store_chunk = [&](int i, const DnRegs& R, uint4* lds_in) {

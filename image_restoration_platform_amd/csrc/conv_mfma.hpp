@@ -9,23 +9,15 @@
 // RB2 211.8 / 216.8 -> 196.8 / 196.3 us, RB1 172 -> 164 / 165.5, conv_w4 168.2 / 155.0 -> 165.6 / 152.0.  IRE_ST_PART: epilogues
 // whose store instruction covers PARTS of lines (32 B per lane from the accumulator layout, 64 B of a 128-B pixel row) stay
 // write-back -- written through, every part is its own memory write: conv_pc<32> 311 -> 449 us, conv_down 157 -> 201
-// (profiles/r03_experiments.md).  Build-time A/B: IRE_ST_LINE=..., IRE_ST_PART=...
-#ifndef IRE_ST_LINE
-#define IRE_ST_LINE 16
-#endif
+// (profiles/r03_experiments.md).
+constexpr int IRE_ST_LINE = 16;
+constexpr int IRE_ST_PART = 0;
 // IRE_LD_ONCE: loads of bytes a kernel reads exactly once AS WHOLE LINES (conv_pc<64>'s residual rows, conv_up's level-0 skip rows)
 // are non-temporal (nt): same box, conv_up<2> 299.4 / 296.1 -> 286.4 / 289.4 us, conv_pc<64> RB2 195.4 / 195.9 -> 191.9 / 191.9.
 // Not where a line is read in two halves at different times (conv_up<4>, <8>: 64-B pieces of 128-B rows: 246 -> 267 us, 219 -> 234),
 // and no effect on conv_w4's and conv_pc<32>'s residual loads.
-#ifndef IRE_LD_ONCE
-#define IRE_LD_ONCE 2
-#endif
-#ifndef IRE_LD_IN
-#define IRE_LD_IN 0        // cache policy of conv_pc's input tile loads (build-time A/B)
-#endif
-#ifndef IRE_ST_PART
-#define IRE_ST_PART 0
-#endif
+constexpr int IRE_LD_ONCE = 2;
+constexpr int IRE_LD_IN = 0;         // cache policy of conv_pc's input tile loads
 
 #include <cstdlib>
 
@@ -96,7 +88,7 @@ struct ConvArgs {
     const float* oscale;         // fp8: [cout] accumulator -> output scale (weight scale of the channel / activation scale)
     int w4_nt;                   // conv_w4 cout block: 128 (default, 0) or 64 (launches whose 128-cout items would leave CUs idle; a.w = the 64-cout slabs)
     const void* zeros;           // conv_upq.hip: >= 16 bytes of zeros (what a DMA lane outside the image fetches)
-    unsigned long long* stamps;  // diagnostic builds only (IRE_RB_ABLATE, DBG bit 16): s_memtime stamps, else null
+    unsigned long long* stamps;  // diagnostic builds only (-DIRE_W4_TL, conv_pk's -DPK_TICKS): clock stamps, else null
     int walk_rev;                // persist.hpp: 1 = the workgroups hand out their items last item first (set per launch by Engine::exec_conv)
 };
 

@@ -27,44 +27,18 @@ namespace ire {
 
 namespace {
 
-#ifndef C3_RES_PRE
-#define C3_RES_PRE -1     // residual groups requested before the MFMAs: -1 = per width (C = 32: 2, C = 64: 1); >= 0 forces one value (build-time A/B)
-#endif
-#ifndef C3_SCALAR
-#define C3_SCALAR 1
-#endif
-#ifndef C3_PRIO
-#define C3_PRIO 1     // measured: priority 1 for the producer waves +0.5 % (911 -> 916 img/s); 3 the same
-#endif
-#ifndef C3_TEPI
-#define C3_TEPI 1    // C = 32 line-coalesced epilogue through a wave-private LDS transpose patch (0: the direct epilogue; build-time A/B).  With plain
-                     // (write-back) stores it measured NEUTRAL (RB2 314.3 / 318.8 vs 314.8 / 315.3 us): the addresser's busy cycles fall, the kernel's time
-                     // does not.  With its whole-line stores written THROUGH (IRE_ST_LINE) it pays on the residual kernel: same box, three times
-                     // each, RB2 314.0 / 317.6 / 317.3 -> 302.3 / 302.0 / 302.5 us, RB1 unchanged, step 1014.8 / 1018.2 / 1016.8 -> 1023.9 / 1022.3 / 1022.0 img/s
-#endif
-#ifndef IRE_LD_ONCE32
-#define IRE_LD_ONCE32 2      // the C = 32 line-coalesced residual loads are non-temporal (build-time A/B: RB2 304.5 / 303.4 -> 299.0 / 301.7 us, step +0.3 %)
-#endif
-#ifndef C3_TEPI64
-#define C3_TEPI64 1  // C = 64: line-coalesced epilogue through the item's released input tile (0: the direct epilogue; build-time A/B)
-#endif
-#ifndef C3_PROD8
-#define C3_PROD8 0   // 1: C = 32 ResBlock convs with EIGHT producer waves (16 waves per CU = four per SIMD, 128 registers each) instead of four
-                     // (build-time A/B).  Stamps: at C = 32 the four producers need 6 300-8 700 ticks for an item's tile while the consumers'
-                     // k-loop takes 2 300 and their epilogue ~3 000: the item waits for its producers.  Twice the producer waves: RB1 257.1 / 255.6
-                     // vs 260.5 / 259.8 us, RB2 313.9 / 317.2 vs 319.9 / 315.0 (same box): nothing -- the SIMD's vector issue is what the producers'
-                     // transform and the epilogues fill (85 % busy: profiles/r02_experiments.md), not a wave's own speed.  Off.
-#endif
-#ifndef C3_INTERIOR
-#define C3_INTERIOR 0   // producers: tiles that touch no image border skip the zero-padding masks (two copies of the stage under a wave-uniform branch;
-                        // as a select hipcc if-converts it and the count goes up): 4 of ~70 vector instructions per chunk
-#endif
-#ifndef C3_ABL
-#define C3_ABL 0     // timing ablations (results wrong by design): 1 no transform, 2 no epilogue, 4 no MFMA loop, 8 no input loads, 16 no output stores, 32 no statistics, 64 no residual loads
-#endif
+// Decided by measurement (the losing arms are in the history; profiles/r02_experiments.md, profiles/r03_experiments.md):
+//  * line-coalesced epilogues: C = 32 through a wave-private LDS transpose patch, C = 64 through the item's released input tile.  At C = 32,
+//    with plain (write-back) stores it measured NEUTRAL (RB2 314.3 / 318.8 vs 314.8 / 315.3 us): the addresser's busy cycles fall, the
+//    kernel's time does not.  With its whole-line stores written THROUGH (IRE_ST_LINE) it pays on the residual kernel: same box, three times
+//    each, RB2 314.0 / 317.6 / 317.3 -> 302.3 / 302.0 / 302.5 us, RB1 unchanged, step 1014.8 / 1018.2 / 1016.8 -> 1023.9 / 1022.3 / 1022.0 img/s
+//  * the line-coalesced residual loads are non-temporal (IRE_LD_ONCE; at C = 32: RB2 304.5 / 303.4 -> 299.0 / 301.7 us, step +0.3 %)
+//  * FOUR producer waves.  EIGHT for the C = 32 ResBlock convs (16 waves per CU = four per SIMD, 128 registers each) -- stamps: at C = 32
+//    the four producers need 6 300-8 700 ticks for an item's tile while the consumers' k-loop takes 2 300 and their epilogue ~3 000: the
+//    item waits for its producers -- measured RB1 257.1 / 255.6 vs 260.5 / 259.8 us, RB2 313.9 / 317.2 vs 319.9 / 315.0 (same box):
+//    nothing -- the SIMD's vector issue is what the producers' transform and the epilogues fill (85 % busy), not a wave's own speed
+//  * the producers' transform runs in plain f32 instructions, one channel each (packed f32 lost: see `pair` below)
 constexpr int C3_CONS = 512, C3_PROD = 256, C3_THREADS = C3_CONS + C3_PROD;
-// producer threads of an instantiation: 512 for the C = 32 ResBlock convs (C3_PROD8), 256 otherwise
-constexpr int pc_prod(int C, bool head) { return (C3_PROD8 && C == 32 && !head) ? 512 : 256; }
 constexpr int C3_TH = 16, C3_TW = 32, C3_IH = C3_TH + 2, C3_IW = C3_TW + 2;
 constexpr int C3_IN_CHUNKS = C3_IH * C3_IW * 4;                                 // 2448 x 16 B (32 channels per pixel and stage)
 constexpr int C3_P_ITERS = (C3_IN_CHUNKS + C3_PROD - 1) / C3_PROD;               // 10 chunks per producer thread and stage
@@ -92,29 +66,15 @@ template <int C> struct PcCfg {
 };
 
 template <int C, bool RESID, bool HEAD>
-__global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(ConvArgs a) {
+__global__ __launch_bounds__(C3_THREADS) void conv_pc_kernel(ConvArgs a) {
     using K = PcCfg<C>;
-    constexpr int PROD = pc_prod(C, HEAD), THREADS = C3_CONS + PROD;
-    constexpr int P_ITERS = (C3_IN_CHUNKS + PROD - 1) / PROD;        // chunks per producer thread and stage: 10 or 5 (P_ITERS * PROD * 16 == C3_IN_BYTES either way)
-    static_assert(P_ITERS * PROD * 16 == C3_IN_BYTES, "tile slots");
+    constexpr int PROD = C3_PROD, THREADS = C3_THREADS, P_ITERS = C3_P_ITERS;
     constexpr int NKC = K::NKC, NTL = K::NTL, NCC = K::NCC, NT = K::NT;
     static_assert(!HEAD || C == 32, "the head is a C = 32 layer");
     __shared__ __attribute__((aligned(16))) unsigned char smem[K::LDS];
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
-    // diagnostic build (IRE_RB_ABLATE=2, IRE_RB_STAMPS=<C>[r]): s_memtime stamps of consumer wave 0 and producer wave 8, per item
-    int stamp_item = 0;
-    auto stamp = [&](int k) {
-#ifdef IRE_PC_TICKS
-        const unsigned long long t = __builtin_amdgcn_s_memtime();
-        if (a.stamps && lane == 0 && (wave == 0 || wave == 8) && blockIdx.x < 8 && stamp_item < 64)
-            a.stamps[(((size_t)blockIdx.x * 2 + (wave ? 1 : 0)) * 64 + stamp_item) * 10 + k] = t;
-#else
-        (void)k;
-#endif
-    };
-
     // workgroup TIMELINE (diagnostic build -DIRE_W4_TL, tools/r04_tl.sh; layout as conv_w4.hip): entry (0), fold done (1), prologue done (2), exit (12)
     auto tl = [&](int slot) {
 #ifdef IRE_W4_TL
@@ -162,10 +122,10 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
 
     if (__builtin_amdgcn_readfirstlane(wave) >= 8) {
         // =============================== producers: waves 8..11 ===============================================================
-#if C3_PRIO
-        // (C = 32 ResBlock convs: the producers at the consumers' priority is faster -- RB1 278 -> 267 us; the head and C = 64 want them above)
-        if (C3_PRIO != 1 || C != 32 || HEAD) asm volatile("s_setprio %0" :: "n"(C3_PRIO));            // the producers are the youngest waves of their SIMD: without this they issue in the consumers' leftover slots
-#endif
+        // the producers are the youngest waves of their SIMD: without this they issue in the consumers' leftover slots.  Measured: priority 1 for
+        // the producer waves +0.5 % (911 -> 916 img/s), 3 the same.  (C = 32 ResBlock convs: the producers at the consumers' priority is
+        // faster -- RB1 278 -> 267 us; the head and C = 64 want them above)
+        if (C != 32 || HEAD) asm volatile("s_setprio 1");
         const int tp = tid - C3_CONS;
         const int c8 = tp & 3;                                   // this thread always stages the same 8-channel slice of a pixel
         // chunk i of this thread: halo-tile pixel p = (tp + PROD i) >> 2 -- constant for the whole kernel
@@ -197,11 +157,8 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
             const int py = (int)(pyx[i] >> 8), px = (int)(pyx[i] & 0xffu);
             const bool ok = (unsigned)(py - y_lo) < (unsigned)(y_hi - y_lo) && (unsigned)(px - x_lo) < (unsigned)(x_hi - x_lo);
             const unsigned off = ok ? base_off + rel[i] : 0xffffffffu;       // out of range: reads as zero
-            if constexpr (C3_ABL & 8) { R[i] = make_uint4(off, 0x3f803f80u, i, 0x3f803f80u); }
-            else {
-                const u32x4_t lv = __builtin_amdgcn_raw_buffer_load_b128(irsrc, off, 0, IRE_LD_IN);
-                R[i] = make_uint4(lv.x, lv.y, lv.z, lv.w);
-            }
+            const u32x4_t lv = __builtin_amdgcn_raw_buffer_load_b128(irsrc, off, 0, IRE_LD_IN);
+            R[i] = make_uint4(lv.x, lv.y, lv.z, lv.w);
             okbits = (okbits & ~(1u << i)) | (ok ? (1u << i) : 0u);
         };
         auto load_coeffs = [&](const PersistStage& st) __attribute__((always_inline)) {      // (A, B) of this thread's 8 channels
@@ -214,8 +171,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
         // as soon as a pair has been transformed the same registers are reloaded with the NEXT stage's pair, so every load has
         // most of a stage's time to land and the first pair of the next transform is the oldest request.  Straight-line code on
         // purpose: with the reloads under a branch hipcc loses the order of the pending loads at the join and waits for all.
-        auto transform_stage_v = [&](unsigned char* tile, auto interior_tag) __attribute__((always_inline)) {
-            constexpr bool INTERIOR = decltype(interior_tag)::value;
+        auto transform_pairs = [&](unsigned char* tile) __attribute__((always_inline)) {
             auto pair = [&](auto pp_tag) __attribute__((always_inline)) {
                 constexpr int pp_ = decltype(pp_tag)::value, i = 2 * pp_;
                 constexpr int NCH = i + 1 < P_ITERS ? 2 : 1;              // chunks in this group (the last group of an odd P_ITERS is a single chunk)
@@ -223,68 +179,36 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                 constexpr int i1 = NCH == 2 ? i + 1 : i;
                 const unsigned wds[8] = {R[i].x, R[i].y, R[i].z, R[i].w, R[i1].x, R[i1].y, R[i1].z, R[i1].w};
                 unsigned o[8];
-                if constexpr (C3_ABL & 1) {
+                // plain f32 instructions, one channel each (build flag -fno-slp-vectorize keeps them so): beside the consumers'
+                // MFMAs a packed f32 instruction costs several times two plain ones (MI355X_MICROARCH.md, per-instruction
+                // constants; measured here: profiles/r02_experiments.md)
+                float y[16], e[16];
 #pragma unroll
-                    for (int w = 0; w < NW; ++w) o[w] = wds[w];
-                } else {
-#if C3_SCALAR
-                    // plain f32 instructions, one channel each (build flag -fno-slp-vectorize keeps them so): beside the consumers'
-                    // MFMAs a packed f32 instruction costs several times two plain ones (MI355X_MICROARCH.md, per-instruction
-                    // constants; measured here: profiles/r02_experiments.md)
-                    float y[16], e[16];
-#pragma unroll
-                    for (int w = 0; w < NW; ++w) {
-                        const int d = w & 3;
-                        y[2 * w] = __builtin_fmaf(bf16_lo(wds[w]), cA[2 * d], cB[2 * d]);
-                        y[2 * w + 1] = __builtin_fmaf(bf16_hi(wds[w]), cA[2 * d + 1], cB[2 * d + 1]);
-                    }
-#pragma unroll
-                    for (int k = 0; k < NV; ++k) e[k] = y[k] * (-1.4426950408889634f);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int k = 0; k < NV; ++k) e[k] = __builtin_amdgcn_exp2f(e[k]);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int k = 0; k < NV; ++k) e[k] = e[k] + 1.0f;
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int k = 0; k < NV; ++k) e[k] = __builtin_amdgcn_rcpf(e[k]);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int w = 0; w < NW; ++w) o[w] = pack_bf16(y[2 * w] * e[2 * w], y[2 * w + 1] * e[2 * w + 1]);
-#else
-                    static_assert(NCH == 2, "the packed-f32 form handles whole pairs");
-                    f32x2_t y[8], e[8];
-#pragma unroll
-                    for (int w = 0; w < 8; ++w) {
-                        // two channels at a time in packed f32: y = x A + B; silu(y) = y / (1 + 2^(-y log2 e))
-                        const int d = w & 3;
-                        const f32x2_t x = {bf16_lo(wds[w]), bf16_hi(wds[w])};
-                        const f32x2_t A = {cA[2 * d], cA[2 * d + 1]}, B = {cB[2 * d], cB[2 * d + 1]};
-                        y[w] = __builtin_elementwise_fma(x, A, B);
-                        e[w] = y[w] * (-1.4426950408889634f);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int w = 0; w < 8; ++w) e[w] = f32x2_t{__builtin_amdgcn_exp2f(e[w].x), __builtin_amdgcn_exp2f(e[w].y)};
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int w = 0; w < 8; ++w) e[w] = e[w] + 1.0f;
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int w = 0; w < 8; ++w) e[w] = f32x2_t{__builtin_amdgcn_rcpf(e[w].x), __builtin_amdgcn_rcpf(e[w].y)};
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int w = 0; w < 8; ++w) { const f32x2_t sv = y[w] * e[w]; o[w] = pack_bf16(sv.x, sv.y); }
-#endif
+                for (int w = 0; w < NW; ++w) {
+                    const int d = w & 3;
+                    y[2 * w] = __builtin_fmaf(bf16_lo(wds[w]), cA[2 * d], cB[2 * d]);
+                    y[2 * w + 1] = __builtin_fmaf(bf16_hi(wds[w]), cA[2 * d + 1], cB[2 * d + 1]);
                 }
 #pragma unroll
+                for (int k = 0; k < NV; ++k) e[k] = y[k] * (-1.4426950408889634f);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int k = 0; k < NV; ++k) e[k] = __builtin_amdgcn_exp2f(e[k]);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int k = 0; k < NV; ++k) e[k] = e[k] + 1.0f;
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int k = 0; k < NV; ++k) e[k] = __builtin_amdgcn_rcpf(e[k]);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int w = 0; w < NW; ++w) o[w] = pack_bf16(y[2 * w] * e[2 * w], y[2 * w + 1] * e[2 * w + 1]);
+#pragma unroll
                 for (int k = 0; k < NCH; ++k) {
-                    uint4 ov = make_uint4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
-                    if constexpr (!INTERIOR) {
-                        const unsigned m = (okbits >> (i + k)) & 1u ? 0xffffffffu : 0u;   // zero padding applies AFTER the activation
-                        ov = make_uint4(o[4 * k] & m, o[4 * k + 1] & m, o[4 * k + 2] & m, o[4 * k + 3] & m);
-                    }
+                    // (skipping the masks for tiles that touch no image border -- two copies of the stage under a wave-uniform branch; as a select
+                    // hipcc if-converts it and the count goes up -- would save 4 of ~70 vector instructions per chunk)
+                    const unsigned m = (okbits >> (i + k)) & 1u ? 0xffffffffu : 0u;       // zero padding applies AFTER the activation
+                    const uint4 ov = make_uint4(o[4 * k] & m, o[4 * k + 1] & m, o[4 * k + 2] & m, o[4 * k + 3] & m);
                     *reinterpret_cast<uint4*>(tile + lds_off[i + k]) = ov;
                 }
                 load_chunk(i);
@@ -294,17 +218,8 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
             pair(std::integral_constant<int, 0>{}); pair(std::integral_constant<int, 1>{}); pair(std::integral_constant<int, 2>{});
             if constexpr (P_ITERS > 6) { pair(std::integral_constant<int, 3>{}); pair(std::integral_constant<int, 4>{}); }
         };
-        // chunk slots past the tile (halo-tile row 18: only the last chunk of the upper threads) are never read: they do not count against "interior"
-        unsigned past_last = 0u;
-        {
-            const int q = tp + (P_ITERS - 1) * PROD;
-            past_last = (q >> 2) >= C3_IH * C3_IW ? (1u << (P_ITERS - 1)) : 0u;
-        }
         auto transform_stage = [&](unsigned char* tile) __attribute__((always_inline)) {
-            if constexpr (C3_INTERIOR) {
-                if (__builtin_amdgcn_ballot_w64((okbits | past_last) != (1u << P_ITERS) - 1u) == 0) { transform_stage_v(tile, std::true_type{}); return; }
-            }
-            transform_stage_v(tile, std::false_type{});
+            transform_pairs(tile);
         };
         // stage 0 -> R; then every transform reloads R with the stage after (past the last stage the cursor stays on it: a
         // redundant reload of rows that are never used).  `ps` = the stage whose rows are in R = the stage being produced.
@@ -316,14 +231,10 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
         lds_barrier();                                           // tile (and slab) of stage 0 are staged
         for (int t = 0; t < n_stages; ++t) {
             // tile / slab of stage t + 1 (for t + 1 == n_stages: the last stage again, into the slots nobody reads any more)
-            stamp_item = t / NKC;
-            stamp(3 * (t % NKC) + 0);
             load_coeffs(ls);
             ls = cursor.next();
             transform_stage(smem + ((t + 1) & 1) * C3_IN_BYTES);   // the consumers finished reading this slot before the last barrier
-            stamp(3 * (t % NKC) + 1);
             lds_barrier();
-            stamp(3 * (t % NKC) + 2);
         }
         return;
     }
@@ -378,25 +289,24 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
     uint4 erv[2 * NTL][2];
     // residual groups requested before the MFMAs, the rest after the k-loop.  Same box, C = 64 with the line-coalesced epilogue: 0 / 1 / 2 / 3 / 4
     // = 218.4 / 216.9 / 223.5 / 294.8 / 299.6 us (from 3 on the consumer spills into its k-loop); C = 32: 326.8 / 329.4 / 320.3
-    constexpr int RES_WANT = C3_RES_PRE >= 0 ? C3_RES_PRE : (C == 64 ? 1 : 2);
+    constexpr int RES_WANT = C == 64 ? 1 : 2;
     constexpr int RES_PRE = RES_WANT < 2 * NTL ? RES_WANT : 2 * NTL;
     unsigned eoffs[2];
     bool einb[2];
-    // C = 32 line-coalesced epilogue (TEPI, off by default -- see C3_TEPI): the accumulator layout (lane = pixel) makes every lane
+    // C = 32 line-coalesced epilogue (TEPI): the accumulator layout (lane = pixel) makes every lane
     // of a quad address a different pixel, and the texture addresser coalesces only within a quad: a 16-B-per-lane store of 32
     // pixels x 32 B costs ~66 of its cycles, a residual load of that shape ~115, against 16 for quad-contiguous addresses (PMC: TA
     // busy 72 % of the C = 32 residual kernel, profiles/r03_experiments.md).  With TEPI a wave transposes a pixel row through its
     // own 2-KB LDS patch (XOR-swizzled: conflict-free both ways) so that four consecutive lanes hold one pixel's 64 B and every
-    // global instruction of the epilogue is 1 KB contiguous.  Correct (same tests), and neutral in time: the addresser was busy,
-    // not limiting.
-    constexpr bool TEPI = C3_TEPI && C == 32 && !HEAD;
+    // global instruction of the epilogue is 1 KB contiguous (what it measured: the note at the top of the file).
+    constexpr bool TEPI = C == 32 && !HEAD;
     // C = 64 (TEPI64): the same transposition, with the patches in the input tile the item's LAST stage has just finished with (the
     // kernel has no other 32 KB of LDS).  That tile belongs to the consumers until the stage barrier -- the producers are writing the
     // other one -- but every consumer wave must be past its last fragment read first: the consumers meet on an LDS counter (no
     // workgroup barrier: the producers must not wait here).  Why it pays at C = 64 and not at C = 32: here the item's stores sit on
     // the critical path -- stamps (profiles/r03_experiments.md): the eight consumer waves issue their 64 partial-line stores
     // together, ~66 addresser cycles each = 4 200 of the epilogue's 5 000 ticks, and the producers wait 4 000 ticks at the barrier.
-    constexpr bool TEPI64 = C3_TEPI64 && C == 64 && !HEAD;
+    constexpr bool TEPI64 = C == 64 && !HEAD;
     unsigned toffs[2];            // byte offset of (read-back pixel lane >> 2 of row m, chunk lane & 3) in the output image
     bool trow[2];
     int tcol = 0;
@@ -408,8 +318,6 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
     lds_barrier();                                               // tile of stage 0 is staged
     for (int t = 0; t < n_items; ++t) {
         const PersistItem it = cs.it;
-        stamp_item = t;
-        stamp(0);
         flush_stats();
         {   // output / residual offsets of this lane's two pixels; the residual rows are requested before the MFMAs
             const int oyb = it.ty * C3_TH + wave * 2, ox = it.tx * C3_TW + r;
@@ -431,7 +339,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                     toffs[m] = ((unsigned)((min(oy, a.Hout - 1) * a.Wout + tcol) * C + 8 * (lane % LPP)) << 1);
                 }
             }
-            if constexpr (RESID && TEPI64 && !(C3_ABL & 64)) {
+            if constexpr (RESID && TEPI64) {
                 // the residual rows in the read-back layout (1 KB = 8 pixels per request): RES_PRE of the 4 quarter-rows per row before the MFMAs
                 char* rbase = const_cast<char*>(reinterpret_cast<const char*>(a.resid)) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
                 const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(rbase, 0, tensor_bytes(a.Hout, a.Wout, 2 * C), 0x00020000);
@@ -440,11 +348,11 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
 #pragma unroll
                     for (int k = 0; k < RES_PRE; ++k) {
                         const bool ok = trow[m] && tcol + 8 * k < a.Wout;
-                        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, ok ? toffs[m] + (unsigned)(8 * k * 2 * C) : 0xffffffffu, 0, IRE_LD_ONCE32);
+                        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, ok ? toffs[m] + (unsigned)(8 * k * 2 * C) : 0xffffffffu, 0, IRE_LD_ONCE);
                         erv[k][m] = make_uint4(v.x, v.y, v.z, v.w);
                     }
             } else
-            if constexpr (RESID && TEPI && !(C3_ABL & 64)) {
+            if constexpr (RESID && TEPI) {
                 // the residual rows in the read-back layout: two 1-KB requests per row, before the MFMAs
                 char* rbase = const_cast<char*>(reinterpret_cast<const char*>(a.resid)) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
                 const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(rbase, 0, tensor_bytes(a.Hout, a.Wout, 2 * C), 0x00020000);
@@ -456,11 +364,6 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                         const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, ok ? toffs[m] + (unsigned)(16 * k * 2 * C) : 0xffffffffu, 0, IRE_LD_ONCE);
                         erv[k][m] = make_uint4(v.x, v.y, v.z, v.w);
                     }
-            } else if constexpr (RESID && (C3_ABL & 64)) {
-#pragma unroll
-                for (int g = 0; g < 2 * NTL; ++g)
-#pragma unroll
-                    for (int m = 0; m < 2; ++m) erv[g][m] = make_uint4(eoffs[m], g, 0x3f803f80u, m);
             } else if constexpr (RESID) {
                 const char* rbase = reinterpret_cast<const char*>(a.resid) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
                 // row by row, a pixel's 16-B pieces back to back: the requests for the two halves of a 64-B sector (and the
@@ -514,7 +417,6 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                 for (int j = 0; j < NTL; ++j) pw[j] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(wk + ((tap * 4 + 2 * cp) * NT + j * 32) * 16));
             };
             read_k(0, af[0], bf[0]);
-            if constexpr (!(C3_ABL & 4))
 #pragma unroll
             for (int g = 0; g < 18; ++g) {
                 if (g + 1 < 18) read_k(g + 1, af[(g + 1) & 1], bf[(g + 1) & 1]);
@@ -533,8 +435,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
             else if constexpr (NKC == 2) { if (kc & 1) stage_body(std::integral_constant<int, 1>{}); else stage_body(std::integral_constant<int, 0>{}); }   // (an item starts on an even stage)
             else stage_body(std::integral_constant<int, -1>{});
             ++stage_no;
-            stamp(kc == 0 ? 1 : 3);
-            if (kc + 1 < NKC) { cs = cursor.next(); lds_barrier(); stamp(2); }      // the item's next stage: its tile is staged, this one is free
+            if (kc + 1 < NKC) { cs = cursor.next(); lds_barrier(); }      // the item's next stage: its tile is staged, this one is free
         }
         if constexpr (RESID && TEPI64 && RES_PRE < 2 * NTL) {
             char* rbase = const_cast<char*>(reinterpret_cast<const char*>(a.resid)) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
@@ -579,11 +480,6 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
 #pragma unroll
             for (int m = 0; m < 2; ++m)
                 if (hok[m]) *reinterpret_cast<unsigned*>(a.u8_out + hoff[m]) = *reinterpret_cast<const unsigned*>(hp + 192 + m * 96 + 4 * min(lane, 23));
-        } else if constexpr (C3_ABL & 2) {
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int j = 0; j < NTL; ++j) asm volatile("" :: "v"(acc[m][j]));       // every accumulator stays live: no MFMA may be optimised away
         } else if constexpr (TEPI64) {
             char* obase = reinterpret_cast<char*>(a.out) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
             const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, tensor_bytes(a.Hout, a.Wout, 2 * C), 0x00020000);
@@ -629,7 +525,6 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                     const bool ok = trow[m] && tcol + 8 * k < a.Wout;
                     const float mf = ok ? 1.f : 0.f;
                     float ts0 = 0.f, tq0 = 0.f;
-                    if constexpr (!(C3_ABL & 32))
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
                         const bf16x2_t bv = __builtin_bit_cast(bf16x2_t, w[d]);
@@ -637,11 +532,10 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                     }
                     sA = __builtin_fmaf(ts0, mf, sA); qA = __builtin_fmaf(tq0, mf, qA);
                     const u32x4_t o4 = {w[0], w[1], w[2], w[3]};
-                    if constexpr (C3_ABL & 16) asm volatile("" :: "v"(o4));
-                    else __builtin_amdgcn_raw_buffer_store_b128(o4, orsrc, ok ? toffs[m] + (unsigned)(8 * k * 2 * C) : 0xffffffffu, 0, IRE_ST_LINE);
+                    __builtin_amdgcn_raw_buffer_store_b128(o4, orsrc, ok ? toffs[m] + (unsigned)(8 * k * 2 * C) : 0xffffffffu, 0, IRE_ST_LINE);
                 }
             }
-            if constexpr (!(C3_ABL & 32)) {
+            {
                 // the eight lanes that share a chunk sit 8 apart: one rotation within the row of 16, then the rows
                 float t2[2] = {sA, qA};
 #pragma unroll
@@ -685,7 +579,6 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                     const bool ok = trow[m] && tcol + 16 * k < a.Wout;
                     const float mf = ok ? 1.f : 0.f;
                     float ts0 = 0.f, tq0 = 0.f, ts1 = 0.f, tq1 = 0.f;
-                    if constexpr (!(C3_ABL & 32))
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
                         const bf16x2_t bv = __builtin_bit_cast(bf16x2_t, w[d]);
@@ -695,11 +588,10 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                     sA = __builtin_fmaf(ts0, mf, sA); qA = __builtin_fmaf(tq0, mf, qA);
                     sB = __builtin_fmaf(ts1, mf, sB); qB = __builtin_fmaf(tq1, mf, qB);
                     const u32x4_t o4 = {w[0], w[1], w[2], w[3]};
-                    if constexpr (C3_ABL & 16) asm volatile("" :: "v"(o4));
-                    else __builtin_amdgcn_raw_buffer_store_b128(o4, orsrc, ok ? toffs[m] + (unsigned)(16 * k * 2 * C) : 0xffffffffu, 0, IRE_ST_LINE);
+                    __builtin_amdgcn_raw_buffer_store_b128(o4, orsrc, ok ? toffs[m] + (unsigned)(16 * k * 2 * C) : 0xffffffffu, 0, IRE_ST_LINE);
                 }
             }
-            if constexpr (!(C3_ABL & 32)) {
+            {
                 // the sixteen lanes that share a chunk sit 4 apart: two rotations within the row of 16, then the rows
                 float t4[4] = {sA, qA, sB, qB};
 #pragma unroll
@@ -741,7 +633,6 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                         for (int d = 0; d < 4; ++d) w[d] = pack_bf16(bf16_lo(w[d]) + bf16_lo(rw[d]), bf16_hi(w[d]) + bf16_hi(rw[d]));
                     }
                     float ts0 = 0.f, tq0 = 0.f, ts1 = 0.f, tq1 = 0.f;
-                    if constexpr (!(C3_ABL & 32))
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
                         const bf16x2_t wv = __builtin_bit_cast(bf16x2_t, w[d]);
@@ -751,8 +642,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
                     sA = __builtin_fmaf(ts0, mf[m], sA); qA = __builtin_fmaf(tq0, mf[m], qA);
                     if constexpr (C == 32) { sB = __builtin_fmaf(ts1, mf[m], sB); qB = __builtin_fmaf(tq1, mf[m], qB); }
                     const u32x4_t wv4 = {w[0], w[1], w[2], w[3]};
-                    if constexpr (C3_ABL & 16) asm volatile("" :: "v"(wv4));
-                    else __builtin_amdgcn_raw_buffer_store_b128(wv4, orsrc, einb[m] ? eoffs[m] + (unsigned)(g * 32) : 0xffffffffu, 0, IRE_ST_PART);
+                    __builtin_amdgcn_raw_buffer_store_b128(wv4, orsrc, einb[m] ? eoffs[m] + (unsigned)(g * 32) : 0xffffffffu, 0, IRE_ST_PART);
                 }
                 if constexpr (C == 32) { vs[2 * pp] = sA; vq[2 * pp] = qA; vs[2 * pp + 1] = sB; vq[2 * pp + 1] = qB; }
                 else { vs[g] = sA; vq[g] = qA; }
@@ -761,7 +651,7 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
             // its values and hands the other half to its partner (lane ^ 1, then lane ^ 2), so 8 -> 4 -> 2 values per lane; those two
             // take the plain steps over lane bits 2, 3 and 4.  28 instead of 56 cross-lane instructions; fixed order.  Lane l of a
             // half ends with (kind = b0: sum / sum of squares) of the values 2 b1 and 2 b1 + 1.
-            if constexpr (!(C3_ABL & 32)) {
+            {
                 const bool b0 = lane & 1, b1 = lane & 2;
                 auto xch = [&](float keep, float give, auto ctrl_tag) __attribute__((always_inline)) -> float {
                     const int gg = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, give), decltype(ctrl_tag)::value, 0xf, 0xf, false);
@@ -788,10 +678,8 @@ __global__ __launch_bounds__(C3_CONS + pc_prod(C, HEAD)) void conv_pc_kernel(Con
             }
             st_img = it.img; st_tile = it.tile; st_nb = it.nb; st_par = red_par; red_par ^= 1;
         }
-        stamp(NKC == 1 ? 3 : 4);
         cs = cursor.next();
         lds_barrier();
-        stamp(5);
         tl(3 + (t < 8 ? t : 8));
     }
     flush_stats();
@@ -814,7 +702,7 @@ void conv_pc_launch(bool resid, bool head, const ConvArgs& a, hipStream_t stream
     const int cus = persistent_grid_cus();
     if (!coef_table_fits(pc_coef_imgs(C), (long long)a.tiles_x * a.tiles_y, a.nimg, cus)) fail(IRE_ERR_INTERNAL, "internal: conv_pc batch");
     const int grid = persistent_grid(items, cus);
-#define PC_GO(CC, RS, HD) hipLaunchKernelGGL((conv_pc_kernel<CC, RS, HD>), dim3(grid), dim3(C3_CONS + pc_prod(CC, HD)), 0, stream, a)
+#define PC_GO(CC, RS, HD) hipLaunchKernelGGL((conv_pc_kernel<CC, RS, HD>), dim3(grid), dim3(C3_THREADS), 0, stream, a)
     if (head) PC_GO(32, false, true);
     else if (C == 32) { if (resid) PC_GO(32, true, false); else PC_GO(32, false, false); }
     else { if (resid) PC_GO(64, true, false); else PC_GO(64, false, false); }

@@ -25,7 +25,7 @@
 // Registers: no VGPR spill in the k-loop, the producers' transform or the epilogue (profiles/r05_experiments.md: the roles' prologues
 // are separate branches, per-lane addresses are rebuilt from the lane index, the accumulators are packed before the residual rows
 // are requested).  LDS (bytes): tiles 2 x 19 712 + slabs 2 x 36 864 + patches 8 x 4 096 + partials 2 048 + bias 1 024 + coefficients
-// 4 C x 8 + sink 256 = 151 808 (C = 128) / 155 904 (C = 256) of 163 840; the residual rows take no LDS of their own (pass 0 lands in
+// 4 C x 8 + 256 spare = 151 808 (C = 128) / 155 904 (C = 256) of 163 840; the residual rows take no LDS of their own (pass 0 lands in
 // the idle patches).
 // Roofline: MFMA.  `2*9*C*C` flop per output pixel, `4C` B (+ `2C` residual).
 #include "conv_mfma.hpp"
@@ -40,39 +40,25 @@ namespace ire {
 
 namespace {
 
-#ifndef PK_PRIO
-#define PK_PRIO 1    // s_setprio of the producer waves (they are the youngest waves of their SIMD: at 0 they issue in the consumers' leftover slots)
-#endif
-#ifndef PK_DMA_SPLIT
-#define PK_DMA_SPLIT 1   // 1: three slab DMA pieces in front of the first transform group, six behind it; 0: all nine at the top of the stage
-#endif
-#ifndef PK_BDEPTH
-#define PK_BDEPTH 2  // weight-fragment registers of the consumers' rotation: 2 = the next fragment is read one MFMA pair ahead, 3 = two pairs ahead
-#endif
-#ifndef PK_CPRIO
-#define PK_CPRIO 0   // 1: consumers raise their priority early in a stage (k-steps 0..3: 3, 4..6: 2, 7..8: 1 -- conv_w4's progress feedback: the wave that is behind outranks its partner)
-#endif
+// Decided by measurement (profiles/r04_experiments.md, profiles/r05_experiments.md; the losing arms are in the history):
+//  * the producer waves run at s_setprio 1 (they are the youngest waves of their SIMD: at 0 they issue in the consumers' leftover
+//    slots); the consumers stay at 0 (conv_w4's progress feedback 3 / 2 / 1 over the k-steps did not pay here)
+//  * the slab DMA goes out as three pieces in front of the first transform group and six behind it (all nine at the top lost)
+//  * the consumers' weight fragments rotate through two registers: the next one is read one MFMA pair ahead (two pairs ahead lost)
+//  * tiles that touch no image border skip the zero-padding masks (a wave-uniform branch per stage)
+//  * residual variant: the FIRST pass's residual rows (16 pixels x 256 B per wave) travel by LDS-DMA into the wave's own -- still
+//    idle -- transpose patch at the top of the item's last stage: no register waits for them through the k-loop, and the epilogue
+//    starts with its first residual rows in LDS; passes 1 and 2 are requested as soon as the accumulators are packed, pass 3
+//    behind pass 0.  Pulling the rows into L2 from the producers ahead of the epilogue lost at every distance (three stages
+//    ahead measured slower -- 32 CUs x 128 KB is the XCD's whole L2)
+// Two build-time arms and the phase-tick stamps remain, because the compiler's register allocation of this 168-register kernel
+// changes when their (dead) code is taken out -- tools/isa_same.py shows it:
 #ifndef PK_DBUF
 #define PK_DBUF 0    // 1: two producer register sets, a stage's rows requested two stages ahead; 0: one set, one stage ahead (vmcnt(0) at the top of a stage)
-#endif
-#ifndef PK_INTERIOR
-#define PK_INTERIOR 1   // tiles that touch no image border skip the zero-padding masks (a wave-uniform branch per stage)
 #endif
 #ifndef PK_CDMA
 #define PK_CDMA 0    // 1: the CONSUMER waves issue the slab DMA (4-5 one-KB pieces each, at the top of their stage, where they would otherwise wait
                      // for the producers); 0: the producers do (9 pieces each: ~900 of their ~5 000 ticks per stage)
-#endif
-#ifndef PK_TOUCH
-#define PK_TOUCH 0   // residual variant: the producers pull the item's residual rows into L2 PK_TOUCH stages before the epilogue (0: off)
-#endif
-#ifndef PK_RDMA
-#define PK_RDMA 1    // residual variant: the FIRST pass's residual rows (16 pixels x 256 B per wave) travel by LDS-DMA into the wave's own -- still
-                     // idle -- transpose patch at the top of the item's last stage: no register waits for them through the k-loop, and the
-                     // epilogue starts with its first residual rows in LDS; passes 1 and 2 are requested as soon as the accumulators are
-                     // packed, pass 3 behind pass 0
-#endif
-#ifndef PK_ABL
-#define PK_ABL 0     // timing ablations (results wrong by design): 1 no transform, 2 no epilogue, 4 no MFMA loop, 8 no slab DMA, 16 epilogue without its global stores
 #endif
 
 constexpr int PK_CONS = 512, PK_PROD = 256, PK_THREADS = PK_CONS + PK_PROD;
@@ -92,19 +78,10 @@ constexpr int PK_BIAS_BASE = PK_RED_BASE + PK_RED_BYTES;
 constexpr int PK_COEF_BASE = PK_BIAS_BASE + 256 * 4;
 // (PK_IMGS, the images whose (A, B) the coefficient table holds: conv_plan.hpp, next to the rule that keeps launches within it)
 template <int C> struct PkCfg {
-    static constexpr int SINK = PK_COEF_BASE + PK_IMGS * C * 8;      // 256 B nobody reads: where the residual prefetch lands
-    static constexpr int LDS = SINK + 256;
+    static constexpr int LDS = PK_COEF_BASE + PK_IMGS * C * 8 + 256;      // (+ 256 B spare)
     static_assert(LDS <= 160 * 1024, "LDS");
 };
 static_assert((PK_PLANE / 4) % 32 == 16 && PK_W_CHUNKS == 9 * PK_PROD, "layout");
-
-// one dword per lane into a 256-B LDS sink: a load whose only purpose is to pull its 128-B line into the XCD's L2 (no register waits for it);
-// M0 as in conv_prims.hpp::glds16
-__device__ __forceinline__ void pk_touch(const void* gsrc, unsigned lds_sink_uniform) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_sink_uniform) : "memory");
-}
 
 template <int C, bool RESID>
 __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
@@ -179,8 +156,9 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
             cok |= ok ? (1u << i) : 0u;
         }
     };
-    // TWO register sets: stage s waits in set s & 1, requested TWO stages before it is transformed -- the transform never waits for
-    // its own stage's loads (one set, requested a stage ahead: ~340 ticks of vmcnt(0) at the top of every producer stage)
+    // As built (PK_DBUF = 0): ONE register set, RA -- a stage's rows are requested one stage before they are transformed, into the registers
+    // the transform has just freed (~340 ticks of vmcnt(0) at the top of every producer stage).  RB / rokB / q3 serve the PK_DBUF = 1 arm only:
+    // two sets, stage s in set s & 1, requested TWO stages ahead.
     u32x4_t RA[PK_P_ITERS], RB[PK_P_ITERS];
     unsigned rokA = 0, rokB = 0;                            // bit i: the chunk in R[i] lies inside the image (travels with the data)
     auto load_chunk = [&](u32x4_t (&R)[PK_P_ITERS], const PersistStage& st, int i) __attribute__((always_inline)) {
@@ -191,7 +169,6 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
         return reinterpret_cast<const unsigned char*>(a.w) + ((size_t)st.it.nb * NKC + st.kc) * PK_W_BYTES;
     };
     auto dma_slab = [&](const PersistStage& st, int slot, int d0 = 0, int d1 = 9) __attribute__((always_inline)) {     // pieces d0 .. d1 - 1 of the 9 x 1 KB per producer wave
-        if constexpr (PK_ABL & 8) return;
         const unsigned char* ws = wslab(st);
         const int wave_p = __builtin_amdgcn_readfirstlane(wave) - 8;
         const unsigned dst = smem_lds + PK_W_BASE + slot * PK_W_BYTES;
@@ -239,7 +216,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
         setup();
         tp = (wv - 8) * 64 + lane_now();
         c8_fixed = tp & 1;
-        if (PK_PRIO) asm volatile("s_setprio %0" :: "n"(PK_PRIO));
+        asm volatile("s_setprio 1");
         unsigned pastbits = 0;                                   // bit i: this thread's chunk i is a slot past the tile (idx >= 1224): its value is never read
 #pragma unroll
         for (int i = 0; i < PK_P_ITERS; ++i) pastbits |= (tp + i * PK_PROD >= PK_IN_CHUNKS) ? (1u << i) : 0u;
@@ -258,32 +235,27 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
             unsigned wds[NW], o[NW];
 #pragma unroll
             for (int k = 0; k < NCH; ++k) { wds[4 * k] = R[i0 + k].x; wds[4 * k + 1] = R[i0 + k].y; wds[4 * k + 2] = R[i0 + k].z; wds[4 * k + 3] = R[i0 + k].w; }
-            if constexpr (PK_ABL & 1) {
+            float y[NV], e[NV];
 #pragma unroll
-                for (int w = 0; w < NW; ++w) o[w] = wds[w];
-            } else {
-                float y[NV], e[NV];
-#pragma unroll
-                for (int w = 0; w < NW; ++w) {
-                    const int d = w & 3;
-                    y[2 * w] = __builtin_fmaf(bf16_lo(wds[w]), cA[2 * d], cB[2 * d]);
-                    y[2 * w + 1] = __builtin_fmaf(bf16_hi(wds[w]), cA[2 * d + 1], cB[2 * d + 1]);
-                }
-#pragma unroll
-                for (int k = 0; k < NV; ++k) e[k] = y[k] * (-1.4426950408889634f);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int k = 0; k < NV; ++k) e[k] = __builtin_amdgcn_exp2f(e[k]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int k = 0; k < NV; ++k) e[k] = e[k] + 1.0f;
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int k = 0; k < NV; ++k) e[k] = __builtin_amdgcn_rcpf(e[k]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int w = 0; w < NW; ++w) o[w] = pack_bf16(y[2 * w] * e[2 * w], y[2 * w + 1] * e[2 * w + 1]);
+            for (int w = 0; w < NW; ++w) {
+                const int d = w & 3;
+                y[2 * w] = __builtin_fmaf(bf16_lo(wds[w]), cA[2 * d], cB[2 * d]);
+                y[2 * w + 1] = __builtin_fmaf(bf16_hi(wds[w]), cA[2 * d + 1], cB[2 * d + 1]);
             }
+#pragma unroll
+            for (int k = 0; k < NV; ++k) e[k] = y[k] * (-1.4426950408889634f);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < NV; ++k) e[k] = __builtin_amdgcn_exp2f(e[k]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < NV; ++k) e[k] = e[k] + 1.0f;
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < NV; ++k) e[k] = __builtin_amdgcn_rcpf(e[k]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int w = 0; w < NW; ++w) o[w] = pack_bf16(y[2 * w] * e[2 * w], y[2 * w + 1] * e[2 * w + 1]);
 #pragma unroll
             for (int k = 0; k < NCH; ++k) {
                 int t2 = tp;
@@ -300,30 +272,29 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
             }
             __builtin_amdgcn_sched_barrier(0);
         };
-        // one producer stage: register set R (stage `ps`, landed) -> tile; R <- stage `nxt` (two stages on)
-        // slab_slot >= 0 (PK_CDMA = 0): the DMA of ps's weight slab rides along (PK_DMA_SPLIT: three pieces in front, six behind the first group)
+        // one producer stage: register set R (stage `ps`) -> tile; R <- stage `nxt` (the next stage; PK_DBUF = 1: two stages on)
+        // slab_slot >= 0 (PK_CDMA = 0): the DMA of ps's weight slab rides along (three pieces in front, six behind the first group)
         auto produce = [&](u32x4_t (&R)[PK_P_ITERS], unsigned& rok, const PersistStage& ps, unsigned char* tile, const PersistStage& nxt, int slab_slot) __attribute__((always_inline)) {
-            // this set's loads are older than the 5 requests of the stage in between: everything but the 5 youngest operations has landed
+            // R's rows have landed (PK_DBUF = 1: this set's loads are older than the 5 requests of the stage in between: all but the 5 youngest operations)
             asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PK_DBUF ? PK_P_ITERS : 0) : "memory");
 #pragma unroll
             for (int i = 0; i < PK_P_ITERS; ++i) asm volatile("" : "+v"(R[i]));
-            if (!PK_CDMA && slab_slot >= 0) dma_slab(ps, slab_slot, 0, PK_DMA_SPLIT ? 3 : 9);
+            if (!PK_CDMA && slab_slot >= 0) dma_slab(ps, slab_slot, 0, 3);
             load_coeffs(ps);
             const unsigned okbits = rok;
             if (nxt.kc == 0) item_offsets(nxt.it);       // (past the queue's end the cursor stays on the last stage: kc != 0)
             // every real chunk of every lane of this wave inside the image: one scalar test per stage (the slots past the tile are never read)
-            const bool interior = PK_INTERIOR && __builtin_amdgcn_ballot_w64((okbits | pastbits) != 0x1fu) == 0;
+            const bool interior = __builtin_amdgcn_ballot_w64((okbits | pastbits) != 0x1fu) == 0;
             auto groups = [&](auto interior_tag) __attribute__((always_inline)) {
                 transform_group(R, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{}, interior_tag, tile, nxt, okbits);
-                if (!PK_CDMA && PK_DMA_SPLIT && slab_slot >= 0) dma_slab(ps, slab_slot, 3, 9);
+                if (!PK_CDMA && slab_slot >= 0) dma_slab(ps, slab_slot, 3, 9);
                 transform_group(R, std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, interior_tag, tile, nxt, okbits);
                 transform_group(R, std::integral_constant<int, 4>{}, std::integral_constant<int, 1>{}, interior_tag, tile, nxt, okbits);
             };
             if (interior) groups(std::true_type{}); else groups(std::false_type{});
             rok = cok;
         };
-        // stage 0 (set A) -> tile 0 (its slab is in slot 0 already), set A <- stage 2
-        PersistStage cc = q1;                                       // the stage the consumers are in
+        // stage 0 (set A) -> tile 0 (its slab is in slot 0 already), set A <- stage 1 (PK_DBUF = 1: stage 2)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (the slab of stage 0 among them)
         produce(RA, rokA, q1, smem, PK_DBUF ? q3 : q2, -1);
         q1 = q2; q2 = q3; q3 = cursor.next();
@@ -332,27 +303,12 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
         // (t + 1) & 1 -> tile (t + 1) & 1, the set then takes stage t + 3.  S is even (NKC is): the loop runs stage pairs.
         auto body = [&](int t, u32x4_t (&R)[PK_P_ITERS], unsigned& rok, int slot) __attribute__((always_inline)) {
             if (wv == 8) stamp(1, t, 0);
-            if constexpr (RESID) {
-                // the residual rows of the item the consumers are in, touched (one dword per 128-B line, 1 024 lines) PK_TOUCH stages
-                // before its epilogue (three stages ahead measured slower -- 32 CUs x 128 KB is the XCD's whole L2)
-                if (PK_TOUCH && cc.kc == NKC - PK_TOUCH) {
-                    const char* rbase = reinterpret_cast<const char*>(a.resid) + (size_t)cc.it.img * a.Hout * a.Wout * (2 * C) + (size_t)cc.it.nb * NT * 2;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int k = tp + j * PK_PROD;                      // line k: tile row k >> 6, 128-B segment k & 63 of the row's 32 x 256 B
-                        const int oy = min(cc.it.ty * PK_TH + (k >> 6), a.Hout - 1), ox = min(cc.it.tx * PK_TW + ((k & 63) >> 1), a.Wout - 1);
-                        pk_touch(rbase + ((size_t)oy * a.Wout + ox) * (2 * C) + (k & 1) * 128, smem_lds + K::SINK);
-                    }
-                }
-            }
-            if (wv == 8) stamp(1, t, 1);
             // (PK_CDMA = 0: slot (t + 1) & 1 held slab t - 1: free since the last barrier)
             produce(R, rok, q1, smem + slot * PK_IN_BYTES, PK_DBUF ? q3 : q2, slot);
-            cc = q1;
             q1 = q2; q2 = q3; q3 = cursor.next();
             if (wv == 8) stamp(1, t, 2);
             // PK_CDMA = 0: the slab must have landed before the barrier; the requests that follow its last DMA piece may stay in flight
-            if (!PK_CDMA) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PK_DMA_SPLIT ? 3 : PK_P_ITERS) : "memory");
+            if (!PK_CDMA) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
             if (wv == 8) stamp(1, t, 3);
             wstamp(t, 0);
             lds_barrier();
@@ -404,7 +360,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
     // just passed): 36 one-KB pieces, wave w takes pieces w, w + 8, w + 16, w + 24 (and w + 32 for w < 4).  LDS-DMA needs no destination
     // registers; the pieces land during the k-loop and the wait behind it is free.
     auto consumer_dma = [&](const PersistStage& st, int slot) __attribute__((always_inline)) {
-        if constexpr (!PK_CDMA || (PK_ABL & 8)) return;
+        if constexpr (!PK_CDMA) return;
         const unsigned char* ws = wslab(st);
         const unsigned dst = smem_lds + PK_W_BASE + slot * PK_W_BYTES;
         const int ln = lane_now();
@@ -439,7 +395,7 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
             const unsigned char* wb = smem + PK_W_BASE + par * PK_W_BYTES + (h_k * NT + r_k) * 16;
             if (cw == 0) stamp(0, stage_no, 0);
             if (stage_no + 1 < S) consumer_dma(cn, par ^ 1);
-            if constexpr (RESID && PK_RDMA) {
+            if constexpr (RESID) {
                 if (kc == NKC - 1) {
                     const int l_e = lane_now(), w_e = cw;
                     const int oy = min(it.ty * PK_TH + w_e * 2, a.Hout - 1);                       // pass 0 = the wave's first row, its first 16 pixels
@@ -451,44 +407,39 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
                     }
                 }
             }
-            if constexpr (!(PK_ABL & 4)) {
-                // 9 k-steps (taps) x 4 weight fragments x 2 pixel rows.  Fragments rotate through TWO weight registers and two PAIRS of
-                // pixel registers (24 of the 40 registers the accumulators leave): the read of the next weight fragment is issued in
-                // front of the two MFMAs of the current one, the next k-step's pixel fragments during this k-step's second and third
-                // pair -- every ds_read_b128 has at least one MFMA pair (64 matrix-pipe cycles, plus whatever the SIMD's other consumer
-                // wave issues in between) to land.  The sched_barriers pin that order (left alone, hipcc reads each weight fragment
-                // right before its MFMAs and waits lgkmcnt(0): ~100 exposed cycles per pair).
-                auto rd_b = [&](int st, int j) __attribute__((always_inline)) -> bf16x8_t {
-                    return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(wb + (2 * st * NT + j * 32) * 16));
-                };
-                auto rd_a = [&](int st, int m) __attribute__((always_inline)) -> bf16x8_t {
-                    const int ky = st / 3, kx = st - ky * 3;
-                    return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ib + ((m + ky) * PK_IW + kx) * 16));
-                };
-                constexpr int BD = PK_BDEPTH;                      // weight-fragment registers in rotation
-                constexpr int NG = 9 * NTL;                        // weight fragments (= MFMA pairs) of a stage
-                auto rd_bg = [&](int g) __attribute__((always_inline)) -> bf16x8_t { return rd_b(g / NTL, g % NTL); };
-                bf16x8_t bq[BD], aq[2][2];
+            // 9 k-steps (taps) x 4 weight fragments x 2 pixel rows.  Fragments rotate through TWO weight registers and two PAIRS of
+            // pixel registers (24 of the 40 registers the accumulators leave): the read of the next weight fragment is issued in
+            // front of the two MFMAs of the current one, the next k-step's pixel fragments during this k-step's second and third
+            // pair -- every ds_read_b128 has at least one MFMA pair (64 matrix-pipe cycles, plus whatever the SIMD's other consumer
+            // wave issues in between) to land.  The sched_barriers pin that order (left alone, hipcc reads each weight fragment
+            // right before its MFMAs and waits lgkmcnt(0): ~100 exposed cycles per pair).
+            auto rd_b = [&](int st, int j) __attribute__((always_inline)) -> bf16x8_t {
+                return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(wb + (2 * st * NT + j * 32) * 16));
+            };
+            auto rd_a = [&](int st, int m) __attribute__((always_inline)) -> bf16x8_t {
+                const int ky = st / 3, kx = st - ky * 3;
+                return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ib + ((m + ky) * PK_IW + kx) * 16));
+            };
+            constexpr int BD = 2;                              // weight-fragment registers in rotation
+            constexpr int NG = 9 * NTL;                        // weight fragments (= MFMA pairs) of a stage
+            auto rd_bg = [&](int g) __attribute__((always_inline)) -> bf16x8_t { return rd_b(g / NTL, g % NTL); };
+            bf16x8_t bq[BD], aq[2][2];
 #pragma unroll
-                for (int d = 0; d + 1 < BD; ++d) bq[d] = rd_bg(d);
-                aq[0][0] = rd_a(0, 0); aq[0][1] = rd_a(0, 1);
+            for (int d = 0; d + 1 < BD; ++d) bq[d] = rd_bg(d);
+            aq[0][0] = rd_a(0, 0); aq[0][1] = rd_a(0, 1);
 #pragma unroll
-                for (int st = 0; st < 9; ++st)
+            for (int st = 0; st < 9; ++st)
 #pragma unroll
-                    for (int j = 0; j < NTL; ++j) {
-                        const int g = st * NTL + j;
-                        if (PK_CPRIO && j == 0 && st == 0) __builtin_amdgcn_s_setprio(3);
-                        if (PK_CPRIO && j == 0 && st == 4) __builtin_amdgcn_s_setprio(2);
-                        if (PK_CPRIO && j == 0 && st == 7) __builtin_amdgcn_s_setprio(1);
-                        if (g + BD - 1 < NG) bq[(g + BD - 1) % BD] = rd_bg(g + BD - 1);
-                        if (st + 1 < 9 && j == 1) aq[(st + 1) & 1][0] = rd_a(st + 1, 0);
-                        if (st + 1 < 9 && j == 2) aq[(st + 1) & 1][1] = rd_a(st + 1, 1);
-                        __builtin_amdgcn_sched_barrier(0);
+                for (int j = 0; j < NTL; ++j) {
+                    const int g = st * NTL + j;
+                    if (g + BD - 1 < NG) bq[(g + BD - 1) % BD] = rd_bg(g + BD - 1);
+                    if (st + 1 < 9 && j == 1) aq[(st + 1) & 1][0] = rd_a(st + 1, 0);
+                    if (st + 1 < 9 && j == 2) aq[(st + 1) & 1][1] = rd_a(st + 1, 1);
+                    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                        for (int m = 0; m < 2; ++m) acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq[g % BD], aq[st & 1][m], acc[m][j], 0, 0, 0);   // D[cout][pixel]
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-            }
+                    for (int m = 0; m < 2; ++m) acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq[g % BD], aq[st & 1][m], acc[m][j], 0, 0, 0);   // D[cout][pixel]
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             par ^= 1;
             if (PK_CDMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's slab pieces (issued a whole k-loop ago) are in LDS
             if (cw == 0) stamp(0, stage_no, 1);
@@ -497,129 +448,119 @@ __global__ __launch_bounds__(PK_THREADS) void conv_pk_kernel(ConvArgs a) {
         }
         // ---- epilogue: conv_w4's line-coalesced form -- a wave transposes 16 pixels x 128 couts at a time through its own 4-KB patch
         // (XOR-swizzled: conflict-free both ways) and reads / writes global memory in whole 256-B pixel runs, 1 KB per instruction
-        if constexpr (PK_ABL & 2) {
+        {
+        const int l_e = lane_now(), w_e = cw;
+        const int oyb = it.ty * PK_TH + w_e * 2;
+        const int tcol0 = it.tx * PK_TW + (l_e >> 4);
+        unsigned toffs[2];
+        bool trow[2];
 #pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int j = 0; j < NTL; ++j) asm volatile("" :: "v"(acc[m][j]));
-        } else {
-            const int l_e = lane_now(), w_e = cw;
-            const int oyb = it.ty * PK_TH + w_e * 2;
-            const int tcol0 = it.tx * PK_TW + (l_e >> 4);
-            unsigned toffs[2];
-            bool trow[2];
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const int oy = oyb + m;
-                trow[m] = oy < a.Hout;
-                toffs[m] = ((unsigned)((min(oy, a.Hout - 1) * a.Wout + tcol0) * C + cout0 + 8 * (l_e & 15)) << 1);
-            }
-            char* obase = reinterpret_cast<char*>(a.out) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
-            const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, a.Hout * a.Wout * (2 * C), 0x00020000);
-            const unsigned cstep = (unsigned)(2 * C) * 4u;                    // bytes per read-back's 4 pixels
-            // the global offset of read-back (m, q, k), or 0xffffffff (buffer range check: nothing loaded or stored) for a pixel past
-            // the image.  Recomputed at every use from values the compiler cannot see through: left alone, it keeps all 16 offsets of
-            // the residual loads live until the stores that share them -- and spills them, each reload a vmcnt(0) on the residual rows
-            auto eoff = [&](int m, int q, int k) __attribute__((always_inline)) -> unsigned {
-                unsigned o = toffs[m];
-                int c = tcol0;
-                asm volatile("" : "+v"(o), "+v"(c));
-                return trow[m] && c + 16 * q + 4 * k < a.Wout ? o + (unsigned)(4 * q + k) * cstep : 0xffffffffu;
-            };
-            auto load_resid_pass = [&](int pass, uint4 (&dst)[4]) __attribute__((always_inline)) {
-                if constexpr (RESID) {
-                    char* rbase = const_cast<char*>(reinterpret_cast<const char*>(a.resid)) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
-                    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(rbase, 0, a.Hout * a.Wout * (2 * C), 0x00020000);
-                    const int m = pass >> 1, q = pass & 1;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, eoff(m, q, k), 0, 0);
-                        dst[k] = make_uint4(v.x, v.y, v.z, v.w);
-                    }
-                }
-            };
-            const bf16x2_t ones = __builtin_bit_cast(bf16x2_t, 0x3f803f80u);
-            const int r16 = l_e & 15, qh = (l_e >> 4) & 1;                    // writer: pixel r = 16 qh + r16 of the row, half h
-            const int h_e = l_e >> 5;
-            const int pq = l_e >> 4, cc_r = l_e & 15;                         // reader: pixel 4 k + pq of the half-row, chunk cc_r (8 couts)
-            constexpr int PITCH = NT * 2;
-            // all 128 accumulators to packed bf16 FIRST (the same 64 conversions the passes would do one by one): 64 registers come
-            // free at once -- the residual rows of the next passes wait in them instead of in scratch
-            u32x4_t pkd[2][NTL * 2];
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int g = 0; g < NTL * 2; ++g) {
-                    const f32x16_t& c = acc[m][g >> 1];
-                    const int pp = g & 1;
-                    pkd[m][g] = u32x4_t{pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
-                                        pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
-                    asm volatile("" : "+v"(pkd[m][g]));                       // (packed HERE: left alone, hipcc sinks row 1's packing to
-                }                                                             //  pass 2 and keeps its 64 f32 accumulators live until then)
-            __builtin_amdgcn_sched_barrier(0);
-            // the residual rows of the four passes: pass 0 from the patch (PK_RDMA: it landed during the k-loop), passes 1 and 2 requested
-            // together, pass 3 behind pass 0 (into pass 0's registers: 48 of them at the peak, beside the 64 of pkd) -- the epilogue waits
-            // for about one round trip, not one per pass, and nothing waits in scratch
-            uint4 rv[4][4];
+        for (int m = 0; m < 2; ++m) {
+            const int oy = oyb + m;
+            trow[m] = oy < a.Hout;
+            toffs[m] = ((unsigned)((min(oy, a.Hout - 1) * a.Wout + tcol0) * C + cout0 + 8 * (l_e & 15)) << 1);
+        }
+        char* obase = reinterpret_cast<char*>(a.out) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
+        const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, a.Hout * a.Wout * (2 * C), 0x00020000);
+        const unsigned cstep = (unsigned)(2 * C) * 4u;                    // bytes per read-back's 4 pixels
+        // the global offset of read-back (m, q, k), or 0xffffffff (buffer range check: nothing loaded or stored) for a pixel past
+        // the image.  Recomputed at every use from values the compiler cannot see through: left alone, it keeps all 16 offsets of
+        // the residual loads live until the stores that share them -- and spills them, each reload a vmcnt(0) on the residual rows
+        auto eoff = [&](int m, int q, int k) __attribute__((always_inline)) -> unsigned {
+            unsigned o = toffs[m];
+            int c = tcol0;
+            asm volatile("" : "+v"(o), "+v"(c));
+            return trow[m] && c + 16 * q + 4 * k < a.Wout ? o + (unsigned)(4 * q + k) * cstep : 0xffffffffu;
+        };
+        auto load_resid_pass = [&](int pass, uint4 (&dst)[4]) __attribute__((always_inline)) {
             if constexpr (RESID) {
-                if constexpr (PK_RDMA) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the DMA of the last stage's top: landed a k-loop ago
+                char* rbase = const_cast<char*>(reinterpret_cast<const char*>(a.resid)) + (size_t)it.img * a.Hout * a.Wout * (2 * C);
+                const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(rbase, 0, a.Hout * a.Wout * (2 * C), 0x00020000);
+                const int m = pass >> 1, q = pass & 1;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) rv[0][k] = *reinterpret_cast<const uint4*>(patch + k * 1024 + l_e * 16);
-                } else {
-                    load_resid_pass(0, rv[0]);
+                for (int k = 0; k < 4; ++k) {
+                    const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, eoff(m, q, k), 0, 0);
+                    dst[k] = make_uint4(v.x, v.y, v.z, v.w);
                 }
-#pragma unroll
-                for (int p1 = 1; p1 < 3; ++p1) load_resid_pass(p1, rv[p1]);
             }
-            float ssum = 0.f, qsum = 0.f;
+        };
+        const bf16x2_t ones = __builtin_bit_cast(bf16x2_t, 0x3f803f80u);
+        const int r16 = l_e & 15, qh = (l_e >> 4) & 1;                    // writer: pixel r = 16 qh + r16 of the row, half h
+        const int h_e = l_e >> 5;
+        const int pq = l_e >> 4, cc_r = l_e & 15;                         // reader: pixel 4 k + pq of the half-row, chunk cc_r (8 couts)
+        constexpr int PITCH = NT * 2;
+        // all 128 accumulators to packed bf16 FIRST (the same 64 conversions the passes would do one by one): 64 registers come
+        // free at once -- the residual rows of the next passes wait in them instead of in scratch
+        u32x4_t pkd[2][NTL * 2];
 #pragma unroll
-            for (int m = 0; m < 2; ++m)
+        for (int m = 0; m < 2; ++m)
 #pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    int r16_p = r16, h_p = h_e, pq_p = pq, cc_p = cc_r;       // (recomputed patch addresses per pass: no 8 + 4 of them live throughout)
-                    asm volatile("" : "+v"(r16_p), "+v"(h_p), "+v"(pq_p), "+v"(cc_p));
-                    if (qh == q) {
+            for (int g = 0; g < NTL * 2; ++g) {
+                const f32x16_t& c = acc[m][g >> 1];
+                const int pp = g & 1;
+                pkd[m][g] = u32x4_t{pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
+                                    pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
+                asm volatile("" : "+v"(pkd[m][g]));                       // (packed HERE: left alone, hipcc sinks row 1's packing to
+            }                                                             //  pass 2 and keeps its 64 f32 accumulators live until then)
+        __builtin_amdgcn_sched_barrier(0);
+        // the residual rows of the four passes: pass 0 from the patch (it landed by LDS-DMA during the k-loop), passes 1 and 2 requested
+        // together, pass 3 behind pass 0 (into pass 0's registers: 48 of them at the peak, beside the 64 of pkd) -- the epilogue waits
+        // for about one round trip, not one per pass, and nothing waits in scratch
+        uint4 rv[4][4];
+        if constexpr (RESID) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // the DMA of the last stage's top: landed a k-loop ago
 #pragma unroll
-                        for (int g = 0; g < NTL * 2; ++g) {
-                            const int cc = 2 * g + h_p;                       // chunk of the pixel's 128-cout run: couts 8 cc .. 8 cc + 7
-                            *reinterpret_cast<u32x4_t*>(patch + r16_p * PITCH + ((cc ^ r16_p) << 4)) = pkd[m][g];
-                        }
+            for (int k = 0; k < 4; ++k) rv[0][k] = *reinterpret_cast<const uint4*>(patch + k * 1024 + l_e * 16);
+#pragma unroll
+            for (int p1 = 1; p1 < 3; ++p1) load_resid_pass(p1, rv[p1]);
+        }
+        float ssum = 0.f, qsum = 0.f;
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                __builtin_amdgcn_sched_barrier(0);
+                int r16_p = r16, h_p = h_e, pq_p = pq, cc_p = cc_r;       // (recomputed patch addresses per pass: no 8 + 4 of them live throughout)
+                asm volatile("" : "+v"(r16_p), "+v"(h_p), "+v"(pq_p), "+v"(cc_p));
+                if (qh == q) {
+#pragma unroll
+                    for (int g = 0; g < NTL * 2; ++g) {
+                        const int cc = 2 * g + h_p;                       // chunk of the pixel's 128-cout run: couts 8 cc .. 8 cc + 7
+                        *reinterpret_cast<u32x4_t*>(patch + r16_p * PITCH + ((cc ^ r16_p) << 4)) = pkd[m][g];
                     }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int p = 4 * k + pq_p;
-                        const u32x4_t v = *reinterpret_cast<const u32x4_t*>(patch + p * PITCH + ((cc_p ^ p) << 4));
-                        unsigned w[4] = {v.x, v.y, v.z, v.w};
-                        if constexpr (RESID) {
-                            const uint4 rr = rv[2 * m + q][k];
-                            const unsigned rw[4] = {rr.x, rr.y, rr.z, rr.w};
-#pragma unroll
-                            for (int d = 0; d < 4; ++d) w[d] = pack_bf16(bf16_lo(w[d]) + bf16_lo(rw[d]), bf16_hi(w[d]) + bf16_hi(rw[d]));
-                        }
-                        float s1 = 0.f, q1 = 0.f;
-#pragma unroll
-                        for (int d = 0; d < 4; ++d) {
-                            const bf16x2_t bv = __builtin_bit_cast(bf16x2_t, w[d]);
-                            s1 = __builtin_amdgcn_fdot2_f32_bf16(bv, ones, s1, false);
-                            q1 = __builtin_amdgcn_fdot2_f32_bf16(bv, bv, q1, false);
-                        }
-                        const unsigned off = eoff(m, q, k);
-                        const bool ok = off != 0xffffffffu;
-                        ssum += ok ? s1 : 0.f; qsum += ok ? q1 : 0.f;
-                        const u32x4_t o4 = {w[0], w[1], w[2], w[3]};
-                        if constexpr (PK_ABL & 16) asm volatile("" :: "v"(o4));
-                        else __builtin_amdgcn_raw_buffer_store_b128(o4, orsrc, off, 0, IRE_ST_LINE);
-                    }
-                    if constexpr (RESID) { if (m == 0 && q == 0) load_resid_pass(3, rv[3]); }
                 }
-            // this lane's chunk cc_r over its read-backs; the other lanes with the same chunk sit 16 apart
-            ssum = swap16_add(ssum); qsum = swap16_add(qsum);
-            ssum = swap32_add(ssum); qsum = swap32_add(qsum);
-            if (l_e < 16) *reinterpret_cast<float2*>(red + red_par * (8 * 32) + (cw * 16 + cc_r) * 2) = make_float2(ssum, qsum);
-            st_img = it.img; st_tile = it.tile; st_cout0 = cout0; st_par = red_par; red_par ^= 1;
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int p = 4 * k + pq_p;
+                    const u32x4_t v = *reinterpret_cast<const u32x4_t*>(patch + p * PITCH + ((cc_p ^ p) << 4));
+                    unsigned w[4] = {v.x, v.y, v.z, v.w};
+                    if constexpr (RESID) {
+                        const uint4 rr = rv[2 * m + q][k];
+                        const unsigned rw[4] = {rr.x, rr.y, rr.z, rr.w};
+#pragma unroll
+                        for (int d = 0; d < 4; ++d) w[d] = pack_bf16(bf16_lo(w[d]) + bf16_lo(rw[d]), bf16_hi(w[d]) + bf16_hi(rw[d]));
+                    }
+                    float s1 = 0.f, q1 = 0.f;
+#pragma unroll
+                    for (int d = 0; d < 4; ++d) {
+                        const bf16x2_t bv = __builtin_bit_cast(bf16x2_t, w[d]);
+                        s1 = __builtin_amdgcn_fdot2_f32_bf16(bv, ones, s1, false);
+                        q1 = __builtin_amdgcn_fdot2_f32_bf16(bv, bv, q1, false);
+                    }
+                    const unsigned off = eoff(m, q, k);
+                    const bool ok = off != 0xffffffffu;
+                    ssum += ok ? s1 : 0.f; qsum += ok ? q1 : 0.f;
+                    const u32x4_t o4 = {w[0], w[1], w[2], w[3]};
+                    __builtin_amdgcn_raw_buffer_store_b128(o4, orsrc, off, 0, IRE_ST_LINE);
+                }
+                if constexpr (RESID) { if (m == 0 && q == 0) load_resid_pass(3, rv[3]); }
+            }
+        // this lane's chunk cc_r over its read-backs; the other lanes with the same chunk sit 16 apart
+        ssum = swap16_add(ssum); qsum = swap16_add(qsum);
+        ssum = swap32_add(ssum); qsum = swap32_add(qsum);
+        if (l_e < 16) *reinterpret_cast<float2*>(red + red_par * (8 * 32) + (cw * 16 + cc_r) * 2) = make_float2(ssum, qsum);
+        st_img = it.img; st_tile = it.tile; st_cout0 = cout0; st_par = red_par; red_par ^= 1;
         }
         if (cw == 0) stamp(0, stage_no - 1, 2);          // epilogue done
         cs = cn; cn = cursor.next();

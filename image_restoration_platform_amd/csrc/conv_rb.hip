@@ -60,12 +60,10 @@ struct RbCfg {
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
-// DBG (timing ablations only, results are wrong): 1 = no MFMA, 2 = no fragment reads + no MFMA,
-// 4 = no epilogue global traffic, 8 = no input global loads.
 // HEAD (NT = 32, weights resident, fused GroupNorm+SiLU): RestoreNet's last layer, 32 -> 3 channels (slab padded to 32 rows):
 // the epilogue is out = clamp(round(input + y)) as u8 RGB -- couts 0..2 are accumulators 0..2 of the lanes with h = 0 -- no
 // bf16 tensor, no statistics.  Same pipeline as every other C = 32 convolution instead of the single-buffered v1 kernel.
-template <int NT, bool RESID, bool WRES, bool FUSED_ACT, int DBG = 0, bool UPS = false, bool HEAD = false>
+template <int NT, bool RESID, bool WRES, bool FUSED_ACT, bool UPS = false, bool HEAD = false>
 __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
     static_assert(!HEAD || (NT == 32 && WRES && FUSED_ACT && !RESID && !UPS), "HEAD: the C = 32 resident-weight fused variant");
     using C = RbCfg<NT, RESID, WRES, FUSED_ACT>;
@@ -78,14 +76,6 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
     const int lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int c8_fixed = tid & 3;  // this thread always stages the same 8-channel slice of a pixel
-    // diagnostic stamps (DBG & 16): lane 0 of waves 0 and 4 of the first 8 workgroups, 6 stamps x 64 stages
-    auto stamp = [&](int s, int k) {
-        if constexpr (DBG & 16) {
-            const unsigned long long t = __builtin_amdgcn_s_memtime();
-            if (a.stamps && lane == 0 && (wave == 0 || wave == 4) && blockIdx.x < 8 && s < 64)
-                a.stamps[(((size_t)blockIdx.x * 2 + (wave >> 2)) * 64 + s) * 10 + k] = t;
-        }
-    };
 
     // ---- persistent work assignment (persist.hpp: XCD-aware, advanced by additions instead of per-stage divisions) ----
     const int tiles_per_img = a.tiles_x * a.tiles_y;
@@ -138,11 +128,8 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
             const bool ok = (unsigned)(iy - a.iy_lo) < (unsigned)a.iy_span && (unsigned)ix < (unsigned)WV;   // slots past the tile (py >= 18) land in the LDS padding
             const int sy = (UPS ? (iy >> 1) : iy) + a.in_row_off, sx = UPS ? (ix >> 1) : ix;
             const unsigned off = ok ? ((unsigned)(sy * a.Win + sx) << (cin_shift + 1)) + (unsigned)(c8_fixed * 16) : 0xffffffffu;
-            if constexpr (DBG & 8) R.v[i] = make_uint4(off, 0x3f803f80u, i, 0x3f803f80u);
-            else {
-                const u32x4_t lv = __builtin_amdgcn_raw_buffer_load_b128(irsrc, off, 0, 0);
-                R.v[i] = make_uint4(lv.x, lv.y, lv.z, lv.w);
-            }
+            const u32x4_t lv = __builtin_amdgcn_raw_buffer_load_b128(irsrc, off, 0, 0);
+            R.v[i] = make_uint4(lv.x, lv.y, lv.z, lv.w);
             R.ok |= ok ? (1u << i) : 0u;
         }
     };
@@ -280,10 +267,7 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
     // v_permlane32_swap + two wait states per register).  GroupNorm partials are reduced over the 32 lanes of a half
     // (same chunk) and land in red[wave][cc].
     constexpr int NG = NTL * 2;
-#ifndef IRE_RB_NGP64
-#define IRE_RB_NGP64 4
-#endif
-    constexpr int NGP = (NT == 64 && FUSED_ACT) ? IRE_RB_NGP64 : NG;      // residual groups requested a stage ahead
+    constexpr int NGP = (NT == 64 && FUSED_ACT) ? 4 : NG;      // residual groups requested a stage ahead
     uint4 erv[NG][2];
     unsigned eoffs[2];
     bool einb[2];
@@ -300,7 +284,7 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
             einb[m] = colok && oy < a.Hout;
             eoffs[m] = ((unsigned)((min(oy, a.Hout - 1) * a.Wout + oxc) * a.cout + it.nb * NT) << 1) + (unsigned)(h_e * 16);
         }
-        if constexpr (RESID && !(DBG & 4)) {
+        if constexpr (RESID) {
             const char* rbase = reinterpret_cast<const char*>(a.resid) + (size_t)it.img * a.Hout * a.Wout * a.cout * 2;
 #pragma unroll
             for (int g = 0; g < NGP; ++g)
@@ -310,7 +294,7 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
     };
     // the groups not requested a stage ahead (register budget of the fused NT = 64 variant): requested when the epilogue starts
     auto epi_fetch_rest = [&](const RbItem& it) __attribute__((always_inline)) {
-        if constexpr (RESID && !(DBG & 4) && NGP < NG) {
+        if constexpr (RESID && NGP < NG) {
             const char* rbase = reinterpret_cast<const char*>(a.resid) + (size_t)it.img * a.Hout * a.Wout * a.cout * 2;
 #pragma unroll
             for (int g = NGP; g < NG; ++g)
@@ -366,7 +350,7 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
                 x0 = pack_bf16(c[8 * pp + 0], c[8 * pp + 1]); x1 = pack_bf16(c[8 * pp + 2], c[8 * pp + 3]);
                 y0 = pack_bf16(c[8 * pp + 4], c[8 * pp + 5]); y1 = pack_bf16(c[8 * pp + 6], c[8 * pp + 7]);
                 unsigned w[4] = {x0, x1, y0, y1};
-                if constexpr (RESID && !(DBG & 4)) {
+                if constexpr (RESID) {
                     const uint4 rr = erv[g][m];
                     const unsigned rw[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
@@ -380,13 +364,10 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
                     else { ts1 = __builtin_amdgcn_fdot2_f32_bf16(wv, ones, ts1, false); tq1 = __builtin_amdgcn_fdot2_f32_bf16(wv, wv, tq1, false); }
                 }
                 sA += einb[m] ? ts0 : 0.f; qA += einb[m] ? tq0 : 0.f; sB += einb[m] ? ts1 : 0.f; qB += einb[m] ? tq1 : 0.f;
-                if constexpr (DBG & 4) { if (einb[m] && w[0] == 0x12345678u) obase[eoffs[m]] = 1; }
-                else {
-                    // range-checked buffer store: lanes outside the image get an offset past num_records and the hardware
-                    // drops them -- no exec-mask branch per store
-                    const u32x4_t wv4 = {w[0], w[1], w[2], w[3]};
-                    __builtin_amdgcn_raw_buffer_store_b128(wv4, orsrc, einb[m] ? eoffs[m] + (unsigned)(g * 32) : 0xffffffffu, 0, 0);
-                }
+                // range-checked buffer store: lanes outside the image get an offset past num_records and the hardware
+                // drops them -- no exec-mask branch per store
+                const u32x4_t wv4 = {w[0], w[1], w[2], w[3]};
+                __builtin_amdgcn_raw_buffer_store_b128(wv4, orsrc, einb[m] ? eoffs[m] + (unsigned)(g * 32) : 0xffffffffu, 0, 0);
             }
             if (!UPS) {        // ResBlock convs always feed a GroupNorm (a.stats != nullptr), `up` convs never do: no run-time branch
                                       // sum over the 32 lanes of each half (= one chunk each), not across halves
@@ -436,7 +417,6 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
 
         // (1) coefficients of stage s+1 first, then (3) the input prefetch of stage s+2, so that waiting
         // for (1) never waits for (3) (VMEM returns in issue order)
-        stamp(s, 0);
         // Rn was retired at the end of the previous stage (or of the prologue); say so on every path into the
         // stage, so no wait on it is placed after the weight DMA below (where it would be a vmcnt(0)).
 #pragma unroll
@@ -476,37 +456,27 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
         // register budget: without it the scheduler hoists far ahead and spills).
         bf16x8_t bfr[2][NTL], afr[2][2];
         auto read_frags = [&](int st, bf16x8_t (&bf)[NTL], bf16x8_t (&af)[2]) {
-            if constexpr (!(DBG & 2)) {
-                const int tap = st >> 1;
+            const int tap = st >> 1;
 #pragma unroll
-                for (int j = 0; j < NTL; ++j)
-                    bf[j] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(wb + (2 * st * NT + j * 32) * 16));
+            for (int j = 0; j < NTL; ++j)
+                bf[j] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(wb + (2 * st * NT + j * 32) * 16));
 #pragma unroll
-                for (int m = 0; m < 2; ++m)
-                    af[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ib + (a_off[m][tap] ^ ((st & 1) << 5))));
-            }
+            for (int m = 0; m < 2; ++m)
+                af[m] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ib + (a_off[m][tap] ^ ((st & 1) << 5))));
         };
         read_frags(0, bfr[0], afr[0]);
 #pragma unroll
         for (int st = 0; st < RB_NSTEPS; ++st) {
             if (st + 1 < RB_NSTEPS) read_frags(st + 1, bfr[(st + 1) & 1], afr[(st + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);   // keep the reads AHEAD of this step's MFMAs (hipcc sinks them otherwise)
-            if constexpr (!(DBG & 3)) {
 #pragma unroll
-                for (int m = 0; m < 2; ++m)
+            for (int m = 0; m < 2; ++m)
 #pragma unroll
-                    for (int j = 0; j < NTL; ++j)
-                    {
-                        f32x16_t cin = acc[m][j];
-                        if constexpr (WRES) { if (st == 0) cin = bias_acc; }
-                        acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[st & 1][j], afr[st & 1][m], cin, 0, 0, 0);  // D[cout][pixel]
-                    }
-            } else if constexpr (!(DBG & 2)) {
-#pragma unroll
-                for (int j = 0; j < NTL; ++j) asm volatile("" :: "v"(bfr[st & 1][j]));   // keep the reads alive
-#pragma unroll
-                for (int m = 0; m < 2; ++m) asm volatile("" :: "v"(afr[st & 1][m]));
-            }
+                for (int j = 0; j < NTL; ++j) {
+                    f32x16_t cin = acc[m][j];
+                    if constexpr (WRES) { if (st == 0) cin = bias_acc; }
+                    acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[st & 1][j], afr[st & 1][m], cin, 0, 0, 0);  // D[cout][pixel]
+                }
             {   // piece st of the s+1 transform (chunk st>>2, word st&3); two pieces per even k-step (interleaved dependency chains) measured
                 // no better (profiles/r02_experiments.md)
                 tw[st & 3] = transform_word(word_of(Rn.v[st >> 2], st & 3), st & 3, cA, cB);
@@ -531,7 +501,6 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        stamp(s, 1);
 #pragma unroll
         for (int pc = RB_NSTEPS; pc < RB_IN_ITERS * 4; ++pc) {         // pieces 18, 19 (and 20..23 with 6 chunks per thread)
             tw[pc & 3] = transform_word(word_of(Rn.v[pc >> 2], pc & 3), pc & 3, cA, cB);
@@ -546,15 +515,12 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
         put_coeffs((s + 1) & 1, cnext);
         // (5) the DMA'd weight slab must have landed before the stage barrier publishes it
         if constexpr (!WRES) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        stamp(s, 2);
         // (6) last k-chunk of the item: epilogue
         const int kc = sq0.kc;
         if constexpr (WRES) direct_epilogue(sq0.it);
         else if constexpr (PAR == 1) { if (kc == nkc - 1) direct_epilogue(sq0.it); }
-        stamp(s, 4);
         // (7) stage barrier: buf[nxt] complete, buf[cur] (and red[]) free
         __syncthreads();
-        stamp(s, 5);
         flush_stats();                                          // red[st_par] is complete; its next writer is two items away
         sq0 = sq1; sq1 = sq2; sq2 = cursor.next();
     };
@@ -602,25 +568,24 @@ __global__ __launch_bounds__(RB_THREADS) void conv_rb_kernel(ConvArgs a) {
     flush_stats();
 }
 
-template <int NT, bool RESID, bool WRES, bool FUSED_ACT, int DBG = 0, bool UPS = false, bool HEAD = false>
+template <int NT, bool RESID, bool WRES, bool FUSED_ACT, bool UPS = false, bool HEAD = false>
 void launch_rb(const ConvArgs& a, hipStream_t stream) {
     const int items = a.tiles_x * a.tiles_y * a.nimg * a.nblocks;
     const int cus = persistent_grid_cus();
     // one workgroup per CU; with 8-row tiles (256 threads) two independent workgroups per CU where their LDS fits
     const int per_cu = (RB_TH == 8 && RbCfg<NT, RESID, WRES, FUSED_ACT>::LDS_BYTES <= 80 * 1024) ? 2 : 1;
     const int grid = persistent_grid(items, cus * per_cu);
-    hipLaunchKernelGGL((conv_rb_kernel<NT, RESID, WRES, FUSED_ACT, DBG, UPS, HEAD>), dim3(grid), dim3(RB_THREADS), 0, stream, a);
+    hipLaunchKernelGGL((conv_rb_kernel<NT, RESID, WRES, FUSED_ACT, UPS, HEAD>), dim3(grid), dim3(RB_THREADS), 0, stream, a);
     IRE_HIP(hipGetLastError());
 }
 
-template <int DBG>
 void rb_dispatch(bool resid, bool fused_act, const ConvArgs& a, hipStream_t stream) {
     if (a.cout == 32) {
-        if (resid) launch_rb<32, true, true, true, DBG>(a, stream); else launch_rb<32, false, true, true, DBG>(a, stream);
+        if (resid) launch_rb<32, true, true, true>(a, stream); else launch_rb<32, false, true, true>(a, stream);
     } else if (fused_act) {
-        if (resid) launch_rb<64, true, false, true, DBG>(a, stream); else launch_rb<64, false, false, true, DBG>(a, stream);
+        if (resid) launch_rb<64, true, false, true>(a, stream); else launch_rb<64, false, false, true>(a, stream);
     } else {
-        if (resid) launch_rb<64, true, false, false, DBG>(a, stream); else launch_rb<64, false, false, false, DBG>(a, stream);
+        if (resid) launch_rb<64, true, false, false>(a, stream); else launch_rb<64, false, false, false>(a, stream);
     }
 }
 
@@ -628,31 +593,18 @@ void rb_dispatch(bool resid, bool fused_act, const ConvArgs& a, hipStream_t stre
 
 void conv_up_launch(const ConvArgs& a, hipStream_t stream) {
     // nearest x2 -> conv3x3 (2C -> C): weights streamed (nkc >= 2), no prologue, no residual, no statistics
-    if (a.cout == 32) launch_rb<32, false, false, false, 0, true>(a, stream);
-    else launch_rb<64, false, false, false, 0, true>(a, stream);
+    if (a.cout == 32) launch_rb<32, false, false, false, true>(a, stream);
+    else launch_rb<64, false, false, false, true>(a, stream);
 }
 
 void conv_head_launch(const ConvArgs& a, hipStream_t stream) {
     if (a.cout != 32 || a.nkc != 1 || a.nblocks != 1 || !a.ab || !a.u8_in || !a.u8_out) fail(IRE_ERR_INTERNAL, "internal: conv_head_launch arguments");
-    launch_rb<32, false, true, true, 0, false, true>(a, stream);
+    launch_rb<32, false, true, true, false, true>(a, stream);
 }
 
 void conv_rb_launch(bool resid, bool fused_act, const ConvArgs& a, hipStream_t stream) {
     if (a.stats == nullptr) fail(IRE_ERR_INTERNAL, "internal: conv_rb_launch needs a GroupNorm partials buffer (ResBlock convs always feed a GroupNorm)");
-#ifdef IRE_RB_ABLATE
-    static const int dbg = std::getenv("IRE_RB_DEBUG") ? std::atoi(std::getenv("IRE_RB_DEBUG")) : 0;
-    switch (dbg) {
-        case 1: return rb_dispatch<1>(resid, fused_act, a, stream);
-        case 2: return rb_dispatch<2>(resid, fused_act, a, stream);
-        case 4: return rb_dispatch<4>(resid, fused_act, a, stream);
-        case 8: return rb_dispatch<8>(resid, fused_act, a, stream);
-        case 6: return rb_dispatch<6>(resid, fused_act, a, stream);
-        case 14: return rb_dispatch<14>(resid, fused_act, a, stream);
-        case 16: return rb_dispatch<16>(resid, fused_act, a, stream);
-        default: break;
-    }
-#endif
-    rb_dispatch<0>(resid, fused_act, a, stream);
+    rb_dispatch(resid, fused_act, a, stream);
 }
 
 }  // namespace ire

@@ -34,12 +34,7 @@ namespace ire {
 
 namespace {
 
-#ifndef IRE_UP_TEPI
-#define IRE_UP_TEPI 1     // fused form: line-coalesced epilogue (skip rows and output rows through a wave-private LDS patch); 0: the direct epilogue (build-time A/B)
-#endif
-#ifndef IRE_UP_ABL
-#define IRE_UP_ABL 0      // timing ablations of the fused epilogue (results wrong by design): 1 no skip term, 2 no statistics, 4 no stores, 8 L2 touches in the last stage
-#endif
+constexpr bool UP_L2_TOUCH = false;     // fused form: touch the item's skip pixels during the last stage (measured slower: see `PREFETCH`)
 constexpr int UP_THREADS = 512;
 constexpr int UP_TH = 16, UP_TW = 32;                 // low-resolution tile
 constexpr int UP_IH = UP_TH + 2, UP_IW = UP_TW + 2;
@@ -143,114 +138,6 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
         char* obase = reinterpret_cast<char*>(a.out) + (size_t)it.img * a.Hout * a.Wout * a.cout * 2;
         const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase, 0, tensor_bytes(a.Hout, a.Wout, a.cout * 2), 0x00020000);
         const int ly = it.ty * UP_TH + w_e * 2, lx = it.tx * UP_TW + r_e;       // low-res coordinates of row m = 0
-        if constexpr (NKS > 0) {
-            // ---- fused form: skip term by MFMA, bf16 stores, GroupNorm partials ------------------------------------------------
-            constexpr int NKG = NKS / 2;              // units (two k-steps = 32 skip channels) per (parity, row)
-            constexpr int U = 8 * NKG;                // unit u = (par * 2 + m) * NKG + kg
-            // units in flight (2 x 16 B per lane each): as many as fit WITHOUT a spill -- a scratch reload in this epilogue queues
-            // behind the skip loads in flight (VMEM completes in order) and drains the ring.  Same-box A/B (IRE_UP_D = 4 / 3 / 2 for
-            // all): NKS 2: 337 / 362 / 342 us, NKS 4 (2 spills at 4): 259 / 253 / 270, NKS 8 (13 spills at 4, 5 at 3): 236 / 233 / 226
-#ifdef IRE_UP_D
-            constexpr int D = IRE_UP_D;
-#else
-            constexpr int D = NKS <= 2 ? 4 : NKS == 4 ? 3 : 2;
-#endif
-            const int C = a.cout;
-            const char* sbase = reinterpret_cast<const char*>(a.in1) + (size_t)it.img * a.Hout * a.Wout * C * 2;
-            // loads past the image's last byte return zero; a pixel past the right edge reads a neighbour's bytes: either way the
-            // MFMA column (= that pixel) is never stored nor counted
-            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(sbase), 0, tensor_bytes(a.Hout, a.Wout, C * 2), 0x00020000);
-            const unsigned rowB = (unsigned)(a.Wout * C * 2), pxB = (unsigned)(C * 2);
-            const unsigned s_off = (unsigned)((2 * ly) * a.Wout + 2 * lx) * pxB + (unsigned)(h_e * 16);
-            const bool inb[2] = {ly < a.Hin && lx < a.Win, ly + 1 < a.Hin && lx < a.Win};
-            const unsigned char* skw = smem + UP_SKW_OFF + (h_e * 32 + r_e) * 16;      // + ks * 1024
-            const bf16x2_t ones = __builtin_bit_cast(bf16x2_t, 0x3f803f80u);
-            u32x4_t ring[D][2];
-            float ssum[4] = {0.f, 0.f, 0.f, 0.f}, qsum[4] = {0.f, 0.f, 0.f, 0.f};   // per cout quad of this lane-half: i = 4k .. 4k + 3
-            auto issue = [&](auto u_tag) __attribute__((always_inline)) {
-                constexpr int u = decltype(u_tag)::value;
-                constexpr int pm = u / NKG, kg = u % NKG, par = pm >> 1, m = pm & 1, pa = par >> 1, pb = par & 1;
-                const unsigned off = s_off + (unsigned)(2 * m + pa) * rowB + (unsigned)pb * pxB + (unsigned)(kg * 64);
-                ring[u % D][0] = __builtin_amdgcn_raw_buffer_load_b128(srsrc, off, 0, 0);
-                ring[u % D][1] = __builtin_amdgcn_raw_buffer_load_b128(srsrc, off + 32u, 0, 0);
-            };
-            auto consume = [&](auto u_tag) __attribute__((always_inline)) {
-                constexpr int u = decltype(u_tag)::value;
-                constexpr int pm = u / NKG, kg = u % NKG, par = pm >> 1, m = pm & 1;
-                const bf16x8_t w0 = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(skw + (2 * kg) * 1024));
-                const bf16x8_t w1 = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(skw + (2 * kg + 1) * 1024));
-                acc[par][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, __builtin_bit_cast(bf16x8_t, ring[u % D][0]), acc[par][m], 0, 0, 0);
-                acc[par][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, __builtin_bit_cast(bf16x8_t, ring[u % D][1]), acc[par][m], 0, 0, 0);
-            };
-            auto finish = [&](auto par_tag) __attribute__((always_inline)) {
-                constexpr int par = decltype(par_tag)::value;
-                constexpr int pa = par >> 1, pb = par & 1;
-                const int ox = 2 * lx + pb;
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    const int oy = 2 * (ly + m) + pa;
-                    const unsigned off = ((unsigned)((oy * a.Wout + ox) * a.cout + it.nb * UP_NT) << 1) + (unsigned)(h_e * 16);
-                    const f32x16_t& c = acc[par][m];
-#pragma unroll
-                    for (int pp = 0; pp < 2; ++pp) {
-                        unsigned w[4] = {pack_bf16(c[8 * pp + 0], c[8 * pp + 1]), pack_bf16(c[8 * pp + 2], c[8 * pp + 3]),
-                                         pack_bf16(c[8 * pp + 4], c[8 * pp + 5]), pack_bf16(c[8 * pp + 6], c[8 * pp + 7])};
-                        const u32x4_t wv4 = {w[0], w[1], w[2], w[3]};
-                        if constexpr (!(IRE_UP_ABL & 4)) __builtin_amdgcn_raw_buffer_store_b128(wv4, orsrc, inb[m] ? off + (unsigned)(pp * 32) : 0xffffffffu, 0, IRE_ST_PART);
-                        else asm volatile("" :: "v"(wv4));
-                        if constexpr (!(IRE_UP_ABL & 2))
-#pragma unroll
-                        for (int d = 0; d < 4; ++d) {
-                            const bf16x2_t wv = __builtin_bit_cast(bf16x2_t, inb[m] ? w[d] : 0u);     // the statistics are those of the STORED values
-                            ssum[2 * pp + (d >> 1)] = __builtin_amdgcn_fdot2_f32_bf16(wv, ones, ssum[2 * pp + (d >> 1)], false);
-                            qsum[2 * pp + (d >> 1)] = __builtin_amdgcn_fdot2_f32_bf16(wv, wv, qsum[2 * pp + (d >> 1)], false);
-                        }
-                    }
-                }
-            };
-            auto unit = [&](auto u_tag) __attribute__((always_inline)) {
-                constexpr int u = decltype(u_tag)::value;
-                if constexpr (!(IRE_UP_ABL & 1)) {
-                consume(u_tag);
-                if constexpr (u + D < U) issue(std::integral_constant<int, u + D>{});
-                }
-                if constexpr ((u + 1) % (2 * NKG) == 0) finish(std::integral_constant<int, u / (2 * NKG)>{});
-            };
-            if constexpr (!(IRE_UP_ABL & 1)) up_static_for<0, D>(issue);
-            up_static_for<0, U>(unit);
-            if constexpr (!(IRE_UP_ABL & 2)) {
-            // GroupNorm partials of the item: quad k of lane-half h is couts 16 (k >> 1) + 8 h + 4 (k & 1) .. + 3 of the block
-            float rv[8] = {ssum[0], qsum[0], ssum[1], qsum[1], ssum[2], qsum[2], ssum[3], qsum[3]};
-#pragma unroll
-            for (int i = 0; i < 8; ++i) rv[i] = ror_add<1>(rv[i]);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) rv[i] = ror_add<2>(rv[i]);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) rv[i] = ror_add<4>(rv[i]);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) rv[i] = ror_add<8>(rv[i]);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) rv[i] = swap16_add(rv[i]);
-            float* red = reinterpret_cast<float*>(smem + UP_RED_OFF);
-            if (r_e == 0) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    *reinterpret_cast<float2*>(red + (w_e * 8 + (k >> 1) * 4 + 2 * h_e + (k & 1)) * 2) = make_float2(rv[2 * k], rv[2 * k + 1]);
-            }
-            __syncthreads();
-            const int G = a.group_size, qpg = G >> 2, ngl = UP_NT / G;       // quads per group (1, 2 or 4), groups in the item's 32 couts
-            if (tid < ngl) {
-                float sv = 0.f, qv = 0.f;
-#pragma unroll
-                for (int w = 0; w < 8; ++w)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (k < qpg) { sv += red[(w * 8 + tid * qpg + k) * 2 + 0]; qv += red[(w * 8 + tid * qpg + k) * 2 + 1]; }
-                float* st = a.stats + (((size_t)it.img * tiles_per_img + it.tile) * 8 + (it.nb * UP_NT) / G + tid) * 2;
-                st[0] = sv; st[1] = qv;
-            }
-            }
-        } else {
 #pragma unroll
         for (int par = 0; par < 4; ++par) {
             const int pa = par >> 1, pb = par & 1;
@@ -269,15 +156,14 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
                 }
             }
         }
-        }
 #pragma unroll
         for (int par = 0; par < 4; ++par)
 #pragma unroll
             for (int m = 0; m < 2; ++m) asm volatile("" : "=v"(acc[par][m]));     // dead until the next item
     };
 
-    // ---- fused form, line-coalesced epilogue (IRE_UP_TEPI).  The direct epilogue below fetches the skip pixels in the MFMA B layout
-    // and stores from the accumulator layout: lane = pixel, so the four lanes of a quad address four different pixels and the
+    // ---- fused form, line-coalesced epilogue.  A direct epilogue (the plain form's, above, plus skip pixels fetched in the MFMA B layout)
+    // loads and stores in the accumulator layout: lane = pixel, so the four lanes of a quad address four different pixels and the
     // texture addresser -- which coalesces within a quad -- spends ~100 cycles on such a load and ~66 on such a store instead of
     // ~16-20 (profiles/r03_experiments.md): 21 000 / 34 000 / 60 000 addresser cycles per item at levels 0 / 1 / 2, half of the
     // kernel, all in a phase where nothing else runs.  Here a wave works through its four output rows (m, pa); per row
@@ -343,14 +229,11 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
                 sk[i] = __builtin_amdgcn_raw_buffer_load_b128(srsrc, ok ? (unsigned)((oy * a.Wout + ox0 + p) * C + pc * PCH + lc * 8) * 2u : 0xffffffffu, 0, C == 32 ? IRE_LD_ONCE : 0);
             }
         };
-        if constexpr (!(IRE_UP_ABL & 1)) {
 #pragma unroll
-            for (int i = 0; i < CPP; ++i) sk[i] = skpre[i];        // piece (row 0, channels 0..31): requested by epi_prefetch before the stage barrier
-        }
+        for (int i = 0; i < CPP; ++i) sk[i] = skpre[i];            // piece (row 0, channels 0..31): requested by epi_prefetch before the stage barrier
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             const int m = rr >> 1, pa = rr & 1;
-            if constexpr (!(IRE_UP_ABL & 1))
 #pragma unroll
             for (int pc = 0; pc < NPIECE; ++pc) {
 #pragma unroll
@@ -384,46 +267,42 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
                 const u32x4_t v = *reinterpret_cast<const u32x4_t*>(patch + p * 64 + ((scq ^ ((p >> 1) & 3)) << 4));
                 const bool ok = rowok && ox0 + p < a.Wout;
                 const unsigned w[4] = {v.x, v.y, v.z, v.w};
-                if constexpr (!(IRE_UP_ABL & 2))
 #pragma unroll
                 for (int d = 0; d < 4; ++d) {
                     const bf16x2_t bv = __builtin_bit_cast(bf16x2_t, ok ? w[d] : 0u);      // the statistics are those of the STORED values
                     ssum[d >> 1] = __builtin_amdgcn_fdot2_f32_bf16(bv, ones, ssum[d >> 1], false);
                     qsum[d >> 1] = __builtin_amdgcn_fdot2_f32_bf16(bv, bv, qsum[d >> 1], false);
                 }
-                if constexpr (!(IRE_UP_ABL & 4)) __builtin_amdgcn_raw_buffer_store_b128(v, orsrc, ok ? (unsigned)((oy * a.Wout + ox0 + p) * C + it.nb * UP_NT + scq * 8) * 2u : 0xffffffffu, 0, (C == 32 ? IRE_ST_LINE : IRE_ST_PART));
-                else asm volatile("" :: "v"(v));
+                __builtin_amdgcn_raw_buffer_store_b128(v, orsrc, ok ? (unsigned)((oy * a.Wout + ox0 + p) * C + it.nb * UP_NT + scq * 8) * 2u : 0xffffffffu, 0, (C == 32 ? IRE_ST_LINE : IRE_ST_PART));
             }
         }
-        if constexpr (!(IRE_UP_ABL & 2)) {
-            // the 16 lanes that share a read-back chunk sit 4 apart: two rotations within the row of 16, then the rows and the halves
-            float rv[4] = {ssum[0], qsum[0], ssum[1], qsum[1]};
+        // the 16 lanes that share a read-back chunk sit 4 apart: two rotations within the row of 16, then the rows and the halves
+        float rv[4] = {ssum[0], qsum[0], ssum[1], qsum[1]};
 #pragma unroll
-            for (int i = 0; i < 4; ++i) rv[i] = ror_add<4>(rv[i]);
+        for (int i = 0; i < 4; ++i) rv[i] = ror_add<4>(rv[i]);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) rv[i] = ror_add<8>(rv[i]);
+        for (int i = 0; i < 4; ++i) rv[i] = ror_add<8>(rv[i]);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) rv[i] = swap16_add(rv[i]);
+        for (int i = 0; i < 4; ++i) rv[i] = swap16_add(rv[i]);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) rv[i] = swap32_add(rv[i]);
-            float* red = reinterpret_cast<float*>(smem + UP_RED_OFF);
-            if (l_e < 4) {          // chunk scq = lane: cout quads 2 scq, 2 scq + 1
-                *reinterpret_cast<float2*>(red + (w_e * 8 + 2 * l_e) * 2) = make_float2(rv[0], rv[1]);
-                *reinterpret_cast<float2*>(red + (w_e * 8 + 2 * l_e + 1) * 2) = make_float2(rv[2], rv[3]);
-            }
-            __syncthreads();
-            const int G = a.group_size, qpg = G >> 2, ngl = UP_NT / G;       // quads per group (1, 2 or 4), groups in the item's 32 couts
-            if (tid < ngl) {
-                float sv = 0.f, qv = 0.f;
+        for (int i = 0; i < 4; ++i) rv[i] = swap32_add(rv[i]);
+        float* red = reinterpret_cast<float*>(smem + UP_RED_OFF);
+        if (l_e < 4) {          // chunk scq = lane: cout quads 2 scq, 2 scq + 1
+            *reinterpret_cast<float2*>(red + (w_e * 8 + 2 * l_e) * 2) = make_float2(rv[0], rv[1]);
+            *reinterpret_cast<float2*>(red + (w_e * 8 + 2 * l_e + 1) * 2) = make_float2(rv[2], rv[3]);
+        }
+        __syncthreads();
+        const int G = a.group_size, qpg = G >> 2, ngl = UP_NT / G;       // quads per group (1, 2 or 4), groups in the item's 32 couts
+        if (tid < ngl) {
+            float sv = 0.f, qv = 0.f;
 #pragma unroll
-                for (int w = 0; w < 8; ++w)
+            for (int w = 0; w < 8; ++w)
 #pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (k < qpg) { sv += red[(w * 8 + tid * qpg + k) * 2 + 0]; qv += red[(w * 8 + tid * qpg + k) * 2 + 1]; }
-                float* st = a.stats + (((size_t)it.img * tiles_per_img + it.tile) * 8 + (it.nb * UP_NT) / G + tid) * 2;
-                st[0] = sv; st[1] = qv;
-            }
-        } else __syncthreads();
+                for (int k = 0; k < 4; ++k)
+                    if (k < qpg) { sv += red[(w * 8 + tid * qpg + k) * 2 + 0]; qv += red[(w * 8 + tid * qpg + k) * 2 + 1]; }
+            float* st = a.stats + (((size_t)it.img * tiles_per_img + it.tile) * 8 + (it.nb * UP_NT) / G + tid) * 2;
+            st[0] = sv; st[1] = qv;
+        }
 #pragma unroll
         for (int par = 0; par < 4; ++par)
 #pragma unroll
@@ -492,7 +371,9 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
         // fused form, levels whose skip tensor comes from HBM (C <= 64): the item's skip pixels are touched one dword per 32 B
         // during the last stage, so that the epilogue's 16-B fragment loads find them in L2 (the epilogue is a pure
         // load -> MFMA -> store phase: what it waits for is exactly these loads)
-        constexpr bool PREFETCH = NKS > 0 && NKS <= 4 && LAST && (IRE_UP_ABL & 8);   // measured: 325 -> 376 us at level 0 (the touches' 64 sectors per instruction cost more than they hide): off
+        // measured: 325 -> 376 us at level 0 (the touches' 64 sectors per instruction cost more than they hide): off.  The arm itself stays:
+        // without its (dead) code the compiler allocates the kernel's scalar registers differently (tools/isa_same.py)
+        constexpr bool PREFETCH = NKS > 0 && NKS <= 4 && LAST && UP_L2_TOUCH;
         unsigned pf_off = 0, pf_lim = 0, pf_dummy = 0;
         const char* pf_base = nullptr;
         if constexpr (PREFETCH) {
@@ -546,8 +427,8 @@ __global__ __launch_bounds__(UP_THREADS) void conv_up_kernel(ConvArgs a) {
         // the stage's one wait: the s+2 reloads and the DMA'd slab of s+1 (and the previous item's output stores)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if constexpr (PREFETCH) asm volatile("" :: "v"(pf_dummy));      // the touches' destination register stayed reserved until here
-        if constexpr (LAST && NKS > 0 && IRE_UP_TEPI) {
-            if constexpr (!(IRE_UP_ABL & 1)) epi_prefetch(sq0.it);
+        if constexpr (LAST && NKS > 0) {
+            epi_prefetch(sq0.it);
             __syncthreads();              // the stage barrier first: the finished buffer becomes the waves' patches
             epilogue_t(sq0.it);           // ends with the barrier that publishes the partials: nobody restages that buffer before it
         } else {

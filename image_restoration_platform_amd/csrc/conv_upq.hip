@@ -35,16 +35,6 @@ namespace ire {
 
 namespace {
 
-#ifndef UQ_ST
-#define UQ_ST IRE_ST_LINE   // cache policy of the output stores (conv_mfma.hpp): build-time A/B
-#endif
-#ifndef UQ_DMA_SPAN
-#define UQ_DMA_SPAN 32   // the next stage's DMA pieces are issued within the first UQ_DMA_SPAN / 32 of the k-loop's MFMA pairs
-#endif
-#ifndef UQ_ABL
-#define UQ_ABL 0      // timing ablations (results wrong by design): 1 no skip term, 2 no epilogue, 4 no MFMA loop, 8 no tile DMA, 16 no slab DMA, 64 the k-loop twice
-#endif
-
 constexpr int UQ_THREADS = 512;
 constexpr int UQ_TH = 16, UQ_TW = 32, UQ_IH = 17, UQ_IW = 33, UQ_NT = 128, UQ_NTL = 4;
 constexpr int UQ_TILE_PIECES = 36;                              // 17 x 33 pixels x 64 B = 35 904 B as 1-KB DMA pieces (the last 960 B: dummy slots)
@@ -203,16 +193,14 @@ __global__ __launch_bounds__(UQ_THREADS) void conv_upq_kernel(ConvArgs a) {
             // rows 32 j + r of [ks][h][128][8]: 1 KB contiguous per load) come STRAIGHT FROM GLOBAL MEMORY into registers at the top of the
             // stage and are used behind its k-loop -- the separate skip stages (a DMA round trip for 16 MFMAs each) are gone
             u32x4_t skp[2], skw[NTL];
-            if constexpr (!(UQ_ABL & 1)) {
-                const int ks = cs.kc;
-                char* sbase = const_cast<char*>(reinterpret_cast<const char*>(a.in1)) + (size_t)cs.it.img * a.Hout * a.Wout * (2 * C) + ks * 32;
-                const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, a.Hout * a.Wout * (2 * C) - ks * 32, 0x00020000);
+            const int ks = cs.kc;
+            char* sbase = const_cast<char*>(reinterpret_cast<const char*>(a.in1)) + (size_t)cs.it.img * a.Hout * a.Wout * (2 * C) + ks * 32;
+            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, a.Hout * a.Wout * (2 * C) - ks * 32, 0x00020000);
 #pragma unroll
-                for (int m = 0; m < 2; ++m) skp[m] = __builtin_amdgcn_raw_buffer_load_b128(srsrc, skoff[m], 0, 0);      // ~0u: out of range reads as zero
-                const char* wsk = reinterpret_cast<const char*>(a.w1) + ((size_t)(ks * 2 + h) * NT + r) * 16;
+            for (int m = 0; m < 2; ++m) skp[m] = __builtin_amdgcn_raw_buffer_load_b128(srsrc, skoff[m], 0, 0);      // ~0u: out of range reads as zero
+            const char* wsk = reinterpret_cast<const char*>(a.w1) + ((size_t)(ks * 2 + h) * NT + r) * 16;
 #pragma unroll
-                for (int j = 0; j < NTL; ++j) skw[j] = *reinterpret_cast<const u32x4_t*>(wsk + j * 512);
-            }
+            for (int j = 0; j < NTL; ++j) skw[j] = *reinterpret_cast<const u32x4_t*>(wsk + j * 512);
             Plan P;
             P.n = 0;
             if (stage_no + 1 < S && !pre_issued) {
@@ -223,49 +211,38 @@ __global__ __launch_bounds__(UQ_THREADS) void conv_upq_kernel(ConvArgs a) {
             const unsigned char* wb = smem + UQ_W_BASE + buf * UQ_SLAB_BYTES + b_off;
             // NS k-steps (tap, k) x 4 weight fragments x 2 pixel rows; fragments rotate through two weight registers and two pairs of pixel
             // registers, every ds_read_b128 issued one MFMA pair ahead (conv_pk.hip's k-loop)
-            if constexpr (!(UQ_ABL & 4)) {
-                constexpr int NS = 2 * decltype(ntaps_tag)::value, NG = NS * NTL;
-                auto rd_b = [&](int st, int j) __attribute__((always_inline)) -> bf16x8_t {
-                    return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(wb + (((st >> 1) * 4 + 2 * (st & 1)) * NT + j * 32) * 16));
-                };
-                auto rd_a = [&](int st, int m) __attribute__((always_inline)) -> bf16x8_t {
-                    return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ib + (a_off[m][st >> 1] ^ ((st & 1) << 5))));
-                };
-#pragma unroll 1
-                for (int rep = 0; rep < ((UQ_ABL & 64) ? 2 : 1); ++rep) {       // (ablation 64: the k-loop twice per stage -- what does a k-loop cost by itself?)
-                bf16x8_t bq[2], aq[2][2];
-                bq[0] = rd_b(0, 0);
-                aq[0][0] = rd_a(0, 0); aq[0][1] = rd_a(0, 1);
+            constexpr int NS = 2 * decltype(ntaps_tag)::value, NG = NS * NTL;
+            auto rd_b = [&](int st, int j) __attribute__((always_inline)) -> bf16x8_t {
+                return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(wb + (((st >> 1) * 4 + 2 * (st & 1)) * NT + j * 32) * 16));
+            };
+            auto rd_a = [&](int st, int m) __attribute__((always_inline)) -> bf16x8_t {
+                return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ib + (a_off[m][st >> 1] ^ ((st & 1) << 5))));
+            };
+            bf16x8_t bq[2], aq[2][2];
+            bq[0] = rd_b(0, 0);
+            aq[0][0] = rd_a(0, 0); aq[0][1] = rd_a(0, 1);
 #pragma unroll
-                for (int st = 0; st < NS; ++st)
+            for (int st = 0; st < NS; ++st)
 #pragma unroll
-                    for (int j = 0; j < NTL; ++j) {
-                        const int g = st * NTL + j;
-                        // the next stage's DMA pieces, spread over the k-loop: piece i rides in front of MFMA pair (i NG) / 10
+                for (int j = 0; j < NTL; ++j) {
+                    const int g = st * NTL + j;
+                    // the next stage's DMA pieces, spread over the k-loop: piece i rides in front of MFMA pair (i NG) / 10
 #pragma unroll
-                        for (int i = 0; i < 10; ++i)
-                            if ((i * (NG * UQ_DMA_SPAN / 32)) / 10 == g && i < P.n && !(((UQ_ABL & 8) && (i < 4 || i >= P.n - (wv < 4 ? 1 : 0))) || ((UQ_ABL & 16) && i >= 4 && i < P.n - (wv < 4 ? 1 : 0)))) glds16(P.src[i], P.dst[i]);
-                        if (g + 1 < NG) bq[(g + 1) & 1] = rd_b((g + 1) / NTL, (g + 1) % NTL);
-                        if (st + 1 < NS && j == 1) aq[(st + 1) & 1][0] = rd_a(st + 1, 0);
-                        if (st + 1 < NS && j == 2) aq[(st + 1) & 1][1] = rd_a(st + 1, 1);
-                        __builtin_amdgcn_sched_barrier(0);
+                    for (int i = 0; i < 10; ++i)
+                        if ((i * NG) / 10 == g && i < P.n) glds16(P.src[i], P.dst[i]);
+                    if (g + 1 < NG) bq[(g + 1) & 1] = rd_b((g + 1) / NTL, (g + 1) % NTL);
+                    if (st + 1 < NS && j == 1) aq[(st + 1) & 1][0] = rd_a(st + 1, 0);
+                    if (st + 1 < NS && j == 2) aq[(st + 1) & 1][1] = rd_a(st + 1, 1);
+                    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                        for (int m = 0; m < 2; ++m) acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq[g & 1], aq[st & 1][m], acc[m][j], 0, 0, 0);   // D[cout][pixel]
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
+                    for (int m = 0; m < 2; ++m) acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq[g & 1], aq[st & 1][m], acc[m][j], 0, 0, 0);   // D[cout][pixel]
+                    __builtin_amdgcn_sched_barrier(0);
                 }
-            }
-            if constexpr (UQ_ABL & 4) {
 #pragma unroll
-                for (int i = 0; i < 10; ++i) if (i < P.n) glds16(P.src[i], P.dst[i]);
-            }
-            if constexpr (!(UQ_ABL & 1) && !(UQ_ABL & 4)) {
+            for (int j = 0; j < NTL; ++j)
 #pragma unroll
-                for (int j = 0; j < NTL; ++j)
-#pragma unroll
-                    for (int m = 0; m < 2; ++m)
-                        acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, skw[j]), __builtin_bit_cast(bf16x8_t, skp[m]), acc[m][j], 0, 0, 0);
-            }
+                for (int m = 0; m < 2; ++m)
+                    acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, skw[j]), __builtin_bit_cast(bf16x8_t, skp[m]), acc[m][j], 0, 0, 0);
             {   // the fragment addresses move to the other tile
                 const int step = buf ? -UQ_TILE_BYTES : UQ_TILE_BYTES;
 #pragma unroll
@@ -292,15 +269,7 @@ __global__ __launch_bounds__(UQ_THREADS) void conv_upq_kernel(ConvArgs a) {
             for (int i = 0; i < 10; ++i) if (i < P.n) glds16(P.src[i], P.dst[i]);
             pre_issued = true;
         }
-        if constexpr (UQ_ABL & 2) {
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int j = 0; j < NTL; ++j) asm volatile("" :: "v"(acc[m][j]));
-            if (pre_issued) {       // keep the counted wait honest: 16 dummy-free -- no stores were issued, so wait for everything
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-        } else {
+        {
             unsigned char* patch = smem + UQ_PATCH_BASE + wave * UQ_PATCH_BYTES;
             const int pa = it.nb >> 1, pb = it.nb & 1;
             int l_e = lane, w_e = wave;
@@ -362,7 +331,7 @@ __global__ __launch_bounds__(UQ_THREADS) void conv_upq_kernel(ConvArgs a) {
                         }
                         const bool ok = trow[m] && lcol0 + 8 * e + 4 * k < a.Win;
                         ssum += ok ? s1 : 0.f; qsum += ok ? q1 : 0.f;
-                        __builtin_amdgcn_raw_buffer_store_b128(v, orsrc, ok ? toffs[m] + (unsigned)(2 * e + k) * cstep : 0xffffffffu, 0, UQ_ST);
+                        __builtin_amdgcn_raw_buffer_store_b128(v, orsrc, ok ? toffs[m] + (unsigned)(2 * e + k) * cstep : 0xffffffffu, 0, IRE_ST_LINE);
                     }
                 }
             // this lane's chunk cc_r over its read-backs; the other lanes with the same chunk sit 16 apart

@@ -11,10 +11,11 @@
 //
 // Stage = 16 input channels (pixel = 2 x 16-B chunks in the LDS tile): 9 k-steps (one per tap) x 16 MFMAs = 144
 // MFMAs per wave = 4608 pipe cycles.  LDS: 2 x (19.6 KB input tile + 36.9 KB weight slab [tap][c8][128][8]).
-// Pipeline, VMEM ordering rules, LDS-DMA weights, stage queue: as conv_rb.hip.  The engine launches the
-// fused-activation 8-wave form (GroupNorm+FiLM+SiLU while staging); the plain-copy staging of a pre-activated input and the
-// 4-wave form are template branches no launch instantiates since round 4.  Epilogue: the 128-channel tile leaves in 4 passes of 32
-// channels through the current stage buffer (bias, residual, GroupNorm partials, full-line stores).
+// Pipeline, VMEM ordering rules, LDS-DMA weights, stage queue: as conv_rb.hip.  Eight waves (two per SIMD, wave tile 2 rows x NT
+// couts, 128 accumulators: a partner wave's MFMAs cover this wave's VMEM / LDS-DMA / epilogue issue slots); GroupNorm+FiLM+SiLU is
+// applied while staging.  (A 4-wave form with a 4-row wave tile and a plain-copy staging of a pre-activated input lost every A/B
+// from round 1 to round 3.)  Epilogue: line-coalesced through wave-private LDS patches; the fp8 form stores straight from the
+// accumulators.
 #include "conv_mfma.hpp"
 #include "conv_prims.hpp"
 #include "persist.hpp"
@@ -22,10 +23,6 @@
 
 #include <cstdlib>
 #include <type_traits>
-
-#ifndef W4_TEPI
-#define W4_TEPI 1      // 0: the direct epilogue of round 2 (build-time A/B: IRE_W4_TEPI=0)
-#endif
 
 namespace ire {
 
@@ -35,22 +32,20 @@ constexpr int W4_TH = 16, W4_TW = 32, W4_IH = 18, W4_IW = 34;
 constexpr int W4_IN_CHUNKS = W4_IH * W4_IW * 2;                              // 1224 x 16 B (16 channels per pixel)
 constexpr int W4_IN_BYTES = (W4_IN_CHUNKS + 8) * 16;                          // + dummy slot (chunk slots past the tile)
 constexpr int W4_NSTEPS = 9;
+constexpr int W4_WAVES = 8, W4_THREADS = W4_WAVES * 64;                      // two waves per SIMD
 
 using W4Item = PersistItem;
 template <int N> struct W4Regs { u32x4_t v[N]; unsigned ok; };   // native 128-bit tuples: one register quad per load
 
-// WAVES = 4: one wave per SIMD, wave tile 4 rows x NT couts (all 256 AGPRs are accumulators at NT = 128)
-// WAVES = 8: two waves per SIMD, wave tile 2 rows x NT couts (128 accumulators): a partner wave's MFMAs cover this wave's
-//            VMEM / LDS-DMA / epilogue issue slots, which a single wave per SIMD can only serialise
 // FP8 (IRE_PRECISION_FP8, cfg 4): both MFMA operands are OCP e4m3 (v_mfma_f32_32x32x16_fp8_fp8): an 8-channel operand chunk
 // is 8 bytes instead of 16 in the LDS tile and in the weight slab (ds_read_b64 fragments, half the LDS bytes per MFMA).
 // Activations are quantised while staging -- after GroupNorm+FiLM+SiLU, scaled by kFp8ActScale so that small values stay
 // normal numbers, clamped to the e4m3 range -- weights offline with one scale per output channel (weight_pack.hpp::pack_conv);
 // the epilogue multiplies each accumulator by its channel's (weight scale / kFp8ActScale).  HBM tensors stay bf16.
 constexpr float kFp8ActScale = 16.0f;
-template <int NT, int WAVES, bool FP8 = false>
+template <int NT, bool FP8 = false>
 struct W4Cfg {
-    static constexpr int THREADS = WAVES * 64;
+    static constexpr int WAVES = W4_WAVES, THREADS = W4_THREADS;
     static constexpr int MT = W4_TH / WAVES;
     static constexpr int IN_ITERS = (W4_IN_CHUNKS + THREADS - 1) / THREADS;
     static constexpr int NTL = NT / 32;
@@ -63,11 +58,11 @@ struct W4Cfg {
     static constexpr int W_ITERS = (W_CHUNKS + THREADS - 1) / THREADS;
     static constexpr int W_BASE = 2 * IN_BYTES;                // in[2] | w[3]
     static constexpr int MAIN_BYTES = W_BASE + 3 * W_BYTES;
-    static constexpr int RED_BYTES = 2 * WAVES * 16 * 2 * 4;   // [item parity][waves][16 chunks of 8 couts][sum, sumsq]  (old epilogue: [waves][8 slots of 16 couts][2])
+    static constexpr int RED_BYTES = 2 * WAVES * 16 * 2 * 4;   // [item parity][waves][16 chunks of 8 couts][sum, sumsq]  (direct epilogue: [waves][8 slots of 16 couts][2])
     static constexpr int PATCH_BYTES = 16 * NT * 2;            // line-coalesced epilogue: a wave's transpose patch (16 pixels x NT couts) inside the stage's dead weight slab
     static_assert(FP8 || WAVES * PATCH_BYTES <= W4_NSTEPS * 2 * NT * EB, "the patches live in one weight slab");
     static constexpr int BIAS_BYTES = 256 * 4;
-    static constexpr int COEF_BYTES = WAVES * 128;             // FUSED: per wave, 16 channels x (A, B) of the stage being staged
+    static constexpr int COEF_BYTES = WAVES * 128;             // per wave, 16 channels x (A, B) of the stage being staged
     static constexpr int SCALE_BYTES = FP8 ? 256 * 4 : 0;      // FP8: per-cout output scale
     static constexpr int LDS_BYTES = MAIN_BYTES + RED_BYTES + BIAS_BYTES + COEF_BYTES + SCALE_BYTES;
     static_assert((PLANE / 4) % 32 == 16, "plane offset must be half a bank row");
@@ -75,10 +70,10 @@ struct W4Cfg {
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
-template <int NT, int WAVES, bool RESID, bool UPS, int DBG = 0, bool FUSED = false, bool FP8 = false>
-__global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
-    static_assert(!FP8 || (FUSED && WAVES == 8), "fp8 operands: fused-activation 8-wave form only");
-    using C = W4Cfg<NT, WAVES, FP8>;
+template <int NT, bool RESID, bool FP8 = false>
+__global__ __launch_bounds__(W4_THREADS) void conv_w4_kernel(ConvArgs a) {
+    using C = W4Cfg<NT, FP8>;
+    constexpr int WAVES = C::WAVES;
     constexpr int EB = C::EB;
     using Regs = W4Regs<C::IN_ITERS>;
     constexpr int NTL = C::NTL;
@@ -129,10 +124,9 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
             const int p = (t2 + i * C::THREADS) >> 1;
             const int py = p / W4_IW, px = p - py * W4_IW;
             const int iy = oy1 + py, ix = ox1 + px;
-            const int WV = UPS ? a.Wout : a.Win;
-            const int cy = min(max(iy, a.iy_lo), a.iy_lo + a.iy_span - 1), cx = min(max(ix, 0), WV - 1);
+            const int cy = min(max(iy, a.iy_lo), a.iy_lo + a.iy_span - 1), cx = min(max(ix, 0), a.Win - 1);
             const bool ok = iy == cy && ix == cx;
-            const int sy = (UPS ? (cy >> 1) : cy) + a.in_row_off, sx = UPS ? (cx >> 1) : cx;
+            const int sy = cy + a.in_row_off, sx = cx;
             coff[i] = ((unsigned)(sy * a.Win + sx) << (cin_shift + 1)) + (unsigned)(c8_fixed * 16);
             cok |= ok ? (1u << i) : 0u;
         }
@@ -147,29 +141,25 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
 #pragma unroll
         for (int i = 0; i < C::IN_ITERS; ++i) load_chunk(si, i, R);
     };
-    // FUSED: y = silu(x*A + B) with (A, B) = GroupNorm+FiLM coefficients of the channel (gn_finalize), applied while staging, two
+    // y = silu(x*A + B) with (A, B) = GroupNorm+FiLM coefficients of the channel (gn_finalize), applied while staging, two
     // channels at a time in packed f32 (as conv_rb.hip::transform_word); zero padding applies AFTER the activation.
     // The coefficients of a stage's 16 channels travel global -> 8 lanes' float4 (fetched with the stage's input, a stage
     // ahead) -> this wave's own 128-B LDS slot -> every lane's 8 (A, B) pairs: wave-local ordering, no barrier.
     float* coef_lds = reinterpret_cast<float*>(smem + C::MAIN_BYTES + C::RED_BYTES + C::BIAS_BYTES) + wave * 32;
     auto fetch_coeffs = [&](const StageInfo& si) -> float4 {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (FUSED) v = reinterpret_cast<const float4*>(a.ab + (size_t)si.it.img * Cin + si.kc * 16)[lane & 7];
-        return v;
+        return reinterpret_cast<const float4*>(a.ab + (size_t)si.it.img * Cin + si.kc * 16)[lane & 7];
     };
     float cA[8], cB[8];
     auto stage_coeffs = [&](const float4& v) {          // publish to the wave's slot, read back this lane's half (c8)
-        if constexpr (FUSED) {
-            // published as (A, A', B, B') per channel pair: a lane's float4 read is then the two register pairs the packed
-            // FMA takes (as (A, B, A', B') every use cost four moves to pair them up)
-            if (lane < 8) reinterpret_cast<float4*>(coef_lds)[lane] = make_float4(v.x, v.z, v.y, v.w);
-            const float4* ab = reinterpret_cast<const float4*>(coef_lds + c8_fixed * 16);
+        // published as (A, A', B, B') per channel pair: a lane's float4 read is then the two register pairs the packed
+        // FMA takes (as (A, B, A', B') every use cost four moves to pair them up)
+        if (lane < 8) reinterpret_cast<float4*>(coef_lds)[lane] = make_float4(v.x, v.z, v.y, v.w);
+        const float4* ab = reinterpret_cast<const float4*>(coef_lds + c8_fixed * 16);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { const float4 t = ab[e]; cA[2 * e] = t.x; cA[2 * e + 1] = t.y; cB[2 * e] = t.z; cB[2 * e + 1] = t.w; }
-            if constexpr (FP8) {       // y' = kFp8ActScale * y: silu comes out pre-scaled for the e4m3 conversion at no per-element cost
+        for (int e = 0; e < 4; ++e) { const float4 t = ab[e]; cA[2 * e] = t.x; cA[2 * e + 1] = t.y; cB[2 * e] = t.z; cB[2 * e + 1] = t.w; }
+        if constexpr (FP8) {       // y' = kFp8ActScale * y: silu comes out pre-scaled for the e4m3 conversion at no per-element cost
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { cA[e] *= kFp8ActScale; cB[e] *= kFp8ActScale; }
-            }
+            for (int e = 0; e < 8; ++e) { cA[e] *= kFp8ActScale; cB[e] *= kFp8ActScale; }
         }
     };
     // (plain f32 instructions, one channel each, and the file is built with -fno-slp-vectorize: beside MFMAs a packed f32
@@ -185,7 +175,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
         const f32x2_t sv = transform_pair(w, d);
         return pack_bf16(sv.x, sv.y);
     };
-    auto store_chunk = [&](int i, const Regs& R, uint4* lds_in) {   // copy (or activate); zero padding outside the image
+    auto store_chunk = [&](int i, const Regs& R, uint4* lds_in) {   // activate; zero padding outside the image
         int t2 = tid;
         asm volatile("" : "+v"(t2));
         const int idx = t2 + i * C::THREADS;
@@ -208,7 +198,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
             *reinterpret_cast<uint2*>(idx < W4_IN_CHUNKS ? lb + c8_fixed * PLANE + (idx >> 1) * 8 : lb + 2 * PLANE) = o8;
             return;
         }
-        if constexpr (FUSED) { v.x = transform_word(v.x, 0); v.y = transform_word(v.y, 1); v.z = transform_word(v.z, 2); v.w = transform_word(v.w, 3); }
+        v.x = transform_word(v.x, 0); v.y = transform_word(v.y, 1); v.z = transform_word(v.z, 2); v.w = transform_word(v.w, 3);
         const u32x4_t o = ok ? v : zero;
         const int slot = c8_fixed * (W4_IN_CHUNKS / 2) + (idx >> 1);
         reinterpret_cast<u32x4_t*>(lds_in)[idx < W4_IN_CHUNKS ? slot : W4_IN_CHUNKS] = o;
@@ -220,17 +210,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
     f32x16_t acc[C::MT][NTL];
     // accumulators start at the bias (permuted slab rows: accumulator i of lane-half h is cout nb*NT + j*32 + 16(i>>3) + 8h + (i&7)):
     // 4*NTL LDS reads per item instead of 16*NTL*MT adds in the epilogue; the moves take the place of the zeroing
-    constexpr bool BIAS_INIT = WAVES == 8;     // (the 512-register form keeps zeroing: a non-constant fill of 256 AGPRs spills)
     auto zero_acc = [&](int nb) {
-        if constexpr (!BIAS_INIT) {
-#pragma unroll
-            for (int m = 0; m < C::MT; ++m)
-#pragma unroll
-                for (int j = 0; j < NTL; ++j)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) acc[m][j][i] = 0.f;
-            return;
-        }
         const float* bl = reinterpret_cast<const float*>(smem + C::MAIN_BYTES + C::RED_BYTES) + nb * NT + 8 * h;
 #pragma unroll
         for (int j = 0; j < NTL; ++j)
@@ -242,19 +222,8 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
             }
     };
 
-    float* red = reinterpret_cast<float*>(smem + C::MAIN_BYTES);                       // [4 waves][4 cc][4]
-    const float* bias_lds = reinterpret_cast<const float*>(smem + C::MAIN_BYTES + C::RED_BYTES);
+    float* red = reinterpret_cast<float*>(smem + C::MAIN_BYTES);                       // GroupNorm partials (W4Cfg::RED_BYTES)
 
-    int s = 0;
-    auto stamp = [&](int k) {
-#ifdef IRE_W4_TICKS
-        const unsigned long long t = __builtin_amdgcn_s_memtime();
-        if (a.stamps && lane == 0 && (wave == 0 || wave == WAVES - 1) && blockIdx.x < 8 && s < 64)
-            a.stamps[(((size_t)blockIdx.x * 2 + (wave ? 1 : 0)) * 64 + s) * 10 + k] = t;
-#else
-        (void)k;
-#endif
-    };
     // workgroup TIMELINE (diagnostic build -DIRE_W4_TL, tools/r04_tl.sh): wave 0 of every workgroup stamps the constant 100 MHz
     // counter (comparable across CUs and XCDs) and its own shader clock at kernel entry (0), after the folded GroupNorm finalize (1),
     // after the prologue (2: the first MFMA follows), at the end of each item (3 + k) and at exit (12); slot 13 = (XCC id, items)
@@ -270,7 +239,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
     };
     // residual prefetch state lives across the item's last stage: the first RD-1 groups are requested BEFORE that stage's
     // MFMAs (k-steps 0..3 carry no other VMEM), so the epilogue finds them landed
-    constexpr int RD = FUSED ? 2 : 4;                // residual groups in flight (the fused variant has 16 registers of coefficients live)
+    constexpr int RD = 2;                            // residual groups in flight (16 registers of coefficients are live beside them)
     uint4 rv[RD][C::MT];
     unsigned offs[C::MT];
     bool inb[C::MT];
@@ -280,7 +249,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
     // profiles/r03_experiments.md: the RB2 epilogue was 23 800 ticks per item, 3.2 stages' worth, RB1's 11 000).  Here a wave
     // transposes 16 pixels x 128 couts at a time through a 4-KB patch of the stage's dead weight slab (XOR-swizzled: conflict-free
     // both ways) and reads / writes global memory in whole 256-B pixel runs: 1 KB contiguous per instruction.
-    constexpr bool TEPI = W4_TEPI && WAVES == 8 && !FP8 && !(DBG & 64);        // (the same-rate fp8 fallback has half-size slabs: direct epilogue)
+    constexpr bool TEPI = !FP8;        // (the same-rate fp8 fallback has half-size slabs: direct epilogue)
     unsigned toffs[C::MT];        // byte offset of (this lane's read-back pixel at q = 0, k = 0; its chunk c = lane & 15) in the output image
     bool trow[C::MT];
     int tcol0 = 0;
@@ -350,7 +319,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
     //   * k-steps 0..3 issue no VMEM at all; the single wait (vmcnt(0) at k-step 4) therefore only sees operations issued
     //     at least four k-steps earlier, and nothing is waited for at the stage end but the barrier.
     Regs R;
-    float4 cnext = make_float4(0.f, 0.f, 0.f, 0.f);   // FUSED: coefficients of the stage whose input R holds
+    float4 cnext = make_float4(0.f, 0.f, 0.f, 0.f);   // coefficients of the stage whose input R holds
     int widx = 0;                                   // weight slab of the current stage (s % 3)
     int par = 0;                                    // input tile of the current stage (s & 1)
     // ONE stage body in the loop (tile parity and slab index are run-time offsets): unrolling stage pairs made the
@@ -362,7 +331,6 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
         const unsigned char* wb = smem + C::W_BASE + widx * C::W_BYTES + b_off;
         const int w2 = widx == 0 ? 2 : widx - 1;    // (s + 2) % 3
         const unsigned w_dst_lds = smem_lds + C::W_BASE + w2 * C::W_BYTES;
-        stamp(0);
         using frag_t = typename std::conditional<FP8, long, bf16x8_t>::type;     // 8 k-values per lane: 8 e4m3 bytes or 8 bf16
         frag_t bfr[2][NTL], afr[2][C::MT];
         auto read_frags = [&](int st, frag_t (&bf)[NTL], frag_t (&af)[C::MT]) {
@@ -386,24 +354,20 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
         for (int st = 0; st < W4_NSTEPS; ++st) {
             // progress feedback: a wave early in its stage outranks one that is further along.  (The SIMD's arbitration otherwise
             // favours the older of its two waves: it runs ahead, idles ~a quarter of every stage at the barrier, and the younger
-            // one then runs without a partner to fill its stalls -- tools/s2_stamps.sh.  A static priority only swaps the roles.)
+            // one then runs without a partner to fill its stalls -- phase stamps, profiles/r02_experiments.md.  A static priority only swaps the roles.)
             // (boundaries 0 / 4 / 7 -- the MFMA-only k-steps, the first three staging k-steps, the last two -- measured against 0 / 3 / 6:
             //  RB1 / RB2 168.2 / 191.1 -> 165.0 / 187.2 us; 0 / 5 / 7 and 0 / 4 / 8 the same as 0 / 4 / 7)
-            if (WAVES == 8 && st == 0) __builtin_amdgcn_s_setprio(3);
-            if (WAVES == 8 && st == 4) __builtin_amdgcn_s_setprio(2);
-            if (WAVES == 8 && st == 7) __builtin_amdgcn_s_setprio(1);
-            if (st + 1 < W4_NSTEPS && !(DBG & 2)) read_frags(st + 1, bfr[(st + 1) & 1], afr[(st + 1) & 1]);
+            if (st == 0) __builtin_amdgcn_s_setprio(3);
+            if (st == 4) __builtin_amdgcn_s_setprio(2);
+            if (st == 7) __builtin_amdgcn_s_setprio(1);
+            if (st + 1 < W4_NSTEPS) read_frags(st + 1, bfr[(st + 1) & 1], afr[(st + 1) & 1]);
             if (st == 4) {
                 // everything issued during the previous stage (R loads, slab s+1, epilogue stores) has had >= 4 k-steps
-                stamp(6);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                stamp(7);
 #pragma unroll
                 for (int i = 0; i < C::IN_ITERS; ++i) asm volatile("" : "+v"(R.v[i]));
-                if constexpr (FUSED) {            // coefficients of the data now in R (fetched with it, one stage ago)
-                    asm volatile("" : "+v"(cnext.x), "+v"(cnext.y), "+v"(cnext.z), "+v"(cnext.w));
-                    stage_coeffs(cnext);
-                }
+                asm volatile("" : "+v"(cnext.x), "+v"(cnext.y), "+v"(cnext.z), "+v"(cnext.w));
+                stage_coeffs(cnext);              // coefficients of the data now in R (fetched with it, one stage ago)
                 if constexpr (LAST && RESID && TEPI) {
 #pragma unroll
                     for (int k = 0; k < NRD; ++k) asm volatile("" : "+v"(rvt[0][k].x), "+v"(rvt[0][k].y), "+v"(rvt[0][k].z), "+v"(rvt[0][k].w));
@@ -420,10 +384,10 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
 #pragma unroll
                 for (int j = 0; j < NTL; ++j)
                     if constexpr (FP8) acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(bfr[st & 1][j], afr[st & 1][m], acc[m][j], 0, 0, 0);
-                    else if constexpr (!(DBG & 1)) acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[(DBG & 2) ? 0 : (st & 1)][j], afr[(DBG & 2) ? 0 : (st & 1)][m], acc[m][j], 0, 0, 0);  // D[cout][pixel]
+                    else acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[st & 1][j], afr[st & 1][m], acc[m][j], 0, 0, 0);  // D[cout][pixel]
             if (st >= 4) {
                 const int i = st - 4;
-                if (!(DBG & 8) && i < C::IN_ITERS) {
+                if (i < C::IN_ITERS) {
                     // (the last chunk index only exists for the first threads: waves all of whose lanes are past the tile skip it)
                     const bool live = (i + 1) * C::THREADS <= W4_IN_CHUNKS || __builtin_amdgcn_readfirstlane(wave) * 64 + i * C::THREADS < W4_IN_CHUNKS;
                     if (live) {
@@ -431,28 +395,24 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
                         load_chunk(sq2, i, R);                          // stage s+2 input -> R.v[i]
                     }
                 }
-                if (FUSED && i == 0) cnext = fetch_coeffs(sq2);   // after the last use of the old coefficients (stage_coeffs at k-step 4)
+                if (i == 0) cnext = fetch_coeffs(sq2);   // after the last use of the old coefficients (stage_coeffs at k-step 4)
                 // slab s+2: all DMA issues in k-steps 4 and 5, so that the stage's LAST VMEM operation is the third input chunk at
                 // k-step 6 -- seven k-steps of flight before the next stage's vmcnt(0); spread over k-steps 4..8 the last issue had
                 // four MFMA-only k-steps (~1 us) and the wait stalled: RB1 / RB2 182 / 200 -> 176.5 / 196 us
-                if constexpr (!(DBG & 32)) {
-                    const unsigned char* ws = wslab(sq2);
-                    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-                    // branch-free issue (a CFG merge here makes hipcc drain vmcnt): waves past the slab's end re-fetch a
-                    // chunk group another wave also fetches (same bytes, same destination)
-                    static_assert(C::W_CHUNKS >= C::THREADS, "slab >= one workgroup-wide DMA issue");
+                const unsigned char* ws = wslab(sq2);
+                const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+                // branch-free issue (a CFG merge here makes hipcc drain vmcnt): waves past the slab's end re-fetch a
+                // chunk group another wave also fetches (same bytes, same destination)
+                static_assert(C::W_CHUNKS >= C::THREADS, "slab >= one workgroup-wide DMA issue");
 #pragma unroll
-                    for (int d = 5 * i; i < 2 && d < 5 * i + 5 && d < C::W_ITERS; ++d) {
-                        int cbase = d * C::THREADS + wave_u * 64;
-                        if ((d + 1) * C::THREADS > C::W_CHUNKS) cbase = cbase >= C::W_CHUNKS ? cbase - C::W_CHUNKS : cbase;   // wraps to a 64-aligned group
-                        glds16(ws + (size_t)(cbase + lane) * 16, w_dst_lds + cbase * 16);
-                    }
+                for (int d = 5 * i; i < 2 && d < 5 * i + 5 && d < C::W_ITERS; ++d) {
+                    int cbase = d * C::THREADS + wave_u * 64;
+                    if ((d + 1) * C::THREADS > C::W_CHUNKS) cbase = cbase >= C::W_CHUNKS ? cbase - C::W_CHUNKS : cbase;   // wraps to a 64-aligned group
+                    glds16(ws + (size_t)(cbase + lane) * 16, w_dst_lds + cbase * 16);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        stamp(1);
-        stamp(2);
     };
     // ---- epilogue, straight from the accumulators (no LDS transpose, no workgroup barrier but the one for the GroupNorm
     // partials).  The slab rows are permuted (bits 2 and 3 of the MFMA row swapped, weight_pack.hpp::pack_conv), so accumulator i
@@ -475,11 +435,6 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
             __builtin_amdgcn_sched_barrier(0);          // keep only one group's accumulator copies live
             if (g + RD - 1 < NTL * 2) load_resid(g + RD - 1, rv[(g + RD - 1) % RD]);
             // permuted slab rows (weight_pack.hpp::pack_conv): accumulators 8pp .. 8pp+7 are the 8 contiguous couts j*32 + 16pp + 8h + (0..7)
-            float4 b0 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = b0;     // BIAS_INIT: the accumulators started at the bias
-            if constexpr (!BIAS_INIT) {
-                b0 = *reinterpret_cast<const float4*>(bias_lds + cout0 + j * 32 + 16 * pp + 8 * h_e);
-                b1 = *reinterpret_cast<const float4*>(bias_lds + cout0 + j * 32 + 16 * pp + 8 * h_e + 4);
-            }
             float ts = 0.f, tq = 0.f;
             float4 s0 = make_float4(1.f, 1.f, 1.f, 1.f), s1 = s0;
             if constexpr (FP8) {        // per-cout dequantisation: weight scale / activation scale (the accumulators started at bias / scale)
@@ -494,12 +449,9 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
                 if constexpr (FP8) {
                     x0 = pack_bf16(c[8 * pp + 0] * s0.x, c[8 * pp + 1] * s0.y); x1 = pack_bf16(c[8 * pp + 2] * s0.z, c[8 * pp + 3] * s0.w);
                     y0 = pack_bf16(c[8 * pp + 4] * s1.x, c[8 * pp + 5] * s1.y); y1 = pack_bf16(c[8 * pp + 6] * s1.z, c[8 * pp + 7] * s1.w);
-                } else if constexpr (BIAS_INIT) {
+                } else {                  // (the accumulators started at the bias)
                     x0 = pack_bf16(c[8 * pp + 0], c[8 * pp + 1]); x1 = pack_bf16(c[8 * pp + 2], c[8 * pp + 3]);
                     y0 = pack_bf16(c[8 * pp + 4], c[8 * pp + 5]); y1 = pack_bf16(c[8 * pp + 6], c[8 * pp + 7]);
-                } else {
-                    x0 = pack_bf16(c[8 * pp + 0] + b0.x, c[8 * pp + 1] + b0.y); x1 = pack_bf16(c[8 * pp + 2] + b0.z, c[8 * pp + 3] + b0.w);
-                    y0 = pack_bf16(c[8 * pp + 4] + b1.x, c[8 * pp + 5] + b1.y); y1 = pack_bf16(c[8 * pp + 6] + b1.z, c[8 * pp + 7] + b1.w);
                 }
                 unsigned w[4] = {x0, x1, y0, y1};
                 if constexpr (RESID) {
@@ -516,14 +468,9 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
                     q1 = __builtin_amdgcn_fdot2_f32_bf16(wv, wv, q1, false);
                 }
                 ts += inb[m] ? s1 : 0.f; tq += inb[m] ? q1 : 0.f;
-                const bool st_ok = inb[m] && (!(DBG & 4) || w[0] == 0x12345678u);
-                if constexpr (WAVES == 8) {
-                    // range-checked buffer store: out-of-image lanes get an offset past num_records and are dropped by the hardware
-                    const u32x4_t wv4 = {w[0], w[1], w[2], w[3]};
-                    __builtin_amdgcn_raw_buffer_store_b128(wv4, orsrc, st_ok ? offs[m] + (unsigned)(j * 64 + pp * 32) : 0xffffffffu, 0, IRE_ST_PART);
-                } else {          // 512-register form: no room for the resource descriptor's live range
-                    if (st_ok) *reinterpret_cast<uint4*>(obase + offs[m] + (unsigned)(j * 64 + pp * 32)) = make_uint4(w[0], w[1], w[2], w[3]);
-                }
+                // range-checked buffer store: out-of-image lanes get an offset past num_records and are dropped by the hardware
+                const u32x4_t wv4 = {w[0], w[1], w[2], w[3]};
+                __builtin_amdgcn_raw_buffer_store_b128(wv4, orsrc, inb[m] ? offs[m] + (unsigned)(j * 64 + pp * 32) : 0xffffffffu, 0, IRE_ST_PART);
             }
             ssum[j][pp] = ts; qsum[j][pp] = tq;
         }
@@ -622,7 +569,6 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
         const int cout0 = cout0_e;
         // every wave is past its last fragment read of the stage: the slab becomes eight wave-private patches
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        stamp(8);
         if constexpr (RESID) { load_resid_pass(1, rvt[1]); load_resid_pass(2, rvt[2]); }      // into the registers the fragments just freed; pass p + 3 follows pass p
         unsigned char* patch = smem + C::W_BASE + widx * C::W_BYTES + wave * C::PATCH_BYTES;
         char* obase = reinterpret_cast<char*>(a.out) + (size_t)it.img * a.Hout * a.Wout * a.cout * 2;
@@ -677,14 +623,13 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
                         s1 = __builtin_amdgcn_fdot2_f32_bf16(bv, ones, s1, false);
                         q1 = __builtin_amdgcn_fdot2_f32_bf16(bv, bv, q1, false);
                     }
-                    const bool ok = trow[m] && tcol0 + 16 * q + PPR * k < a.Wout && (!(DBG & 4) || w[0] == 0x12345678u);
+                    const bool ok = trow[m] && tcol0 + 16 * q + PPR * k < a.Wout;
                     ssum += ok ? s1 : 0.f; qsum += ok ? q1 : 0.f;
                     const u32x4_t o4 = {w[0], w[1], w[2], w[3]};
                     __builtin_amdgcn_raw_buffer_store_b128(o4, orsrc, ok ? toffs[m] + (unsigned)(NRD * q + k) * cstep : 0xffffffffu, 0, IRE_ST_LINE);
                 }
                 if constexpr (RESID) { if (2 * m + q + 3 < 2 * C::MT) load_resid_pass(2 * m + q + 3, rvt[(2 * m + q) % 3]); }
             }
-        stamp(9);
         // this lane's chunk cc_r over its read-backs; the other lanes with the same chunk sit NCHK apart
         if constexpr (NCHK == 8) { ssum = ror_add<8>(ssum); qsum = ror_add<8>(qsum); }
         ssum = swap16_add(ssum); qsum = swap16_add(qsum);
@@ -692,10 +637,8 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
         if (l_e < NCHK) *reinterpret_cast<float2*>(red + red_par * (WAVES * 32) + (wave * NCHK + cc_r) * 2) = make_float2(ssum, qsum);
         st_img = it.img; st_tile = it.tile; st_cout0 = cout0; st_par = red_par; red_par ^= 1;
     };
-    auto finish = [&](int s) {
-        stamp(4);
+    auto finish = [&]() {
         __syncthreads();          // stage barrier: buf[nxt] complete, buf[cur] free
-        stamp(5);
         sq0 = sq1; sq1 = sq2; sq2 = cursor.next();
         if (sq2.kc == 0) item_offsets(sq2.it);       // (past the queue's end the cursor stays on the last stage: kc != 0)
         widx = widx == 2 ? 0 : widx + 1;
@@ -734,12 +677,12 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // R and this wave's slab pieces have landed
 #pragma unroll
         for (int i = 0; i < C::IN_ITERS; ++i) asm volatile("" : "+v"(R.v[i]));
-        if constexpr (FUSED) stage_coeffs(fetch_coeffs(sq0));
+        stage_coeffs(fetch_coeffs(sq0));
         uint4* in0 = reinterpret_cast<uint4*>(smem);
 #pragma unroll
         for (int i = 0; i < C::IN_ITERS; ++i) store_chunk(i, R, in0);
         load_stage(sq1, R);
-        if constexpr (FUSED) cnext = fetch_coeffs(sq1);
+        cnext = fetch_coeffs(sq1);
     }
     __syncthreads();
     tl(2);
@@ -750,13 +693,12 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
         // loop makes the allocator split live ranges of in-flight prefetch registers mid-stage (vmcnt(0) + v_mov)
         for (int kc = 0; kc + 1 < nkc; ++kc) {
             compute(std::false_type{});
-            finish(s); ++s;
+            finish();
         }
         epi_prefetch();
         compute(std::true_type{});
-        stamp(3);
         if constexpr (TEPI) epilogue_t(); else epilogue();
-        finish(s); ++s;
+        finish();
         if constexpr (TEPI) flush_stats();      // after the stage barrier: every wave's chunk sums are in LDS (parity red_par ^ 1)
         tl(3 + (k < 8 ? k : 8));
     }
@@ -764,11 +706,11 @@ __global__ __launch_bounds__(WAVES * 64) void conv_w4_kernel(ConvArgs a) {
     tl(12);
 }
 
-template <int NT, int WAVES, bool RESID, bool UPS, int DBG = 0, bool FUSED = false, bool FP8 = false>
+template <int NT, bool RESID, bool FP8 = false>
 void launch_w4(const ConvArgs& a, hipStream_t stream) {
     const int items = a.tiles_x * a.tiles_y * a.nimg * a.nblocks;
     const int grid = persistent_grid(items);
-    hipLaunchKernelGGL((conv_w4_kernel<NT, WAVES, RESID, UPS, DBG, FUSED, FP8>), dim3(grid), dim3(WAVES * 64), 0, stream, a);
+    hipLaunchKernelGGL((conv_w4_kernel<NT, RESID, FP8>), dim3(grid), dim3(W4_THREADS), 0, stream, a);
     IRE_HIP(hipGetLastError());
 }
 
@@ -776,16 +718,14 @@ void launch_w4(const ConvArgs& a, hipStream_t stream) {
 
 // a.nkc = Cin/16 stages, a.nblocks = cout/128, a.w = slabs [nblock][kc16][tap][c8][128][8], tiles of 16x32.
 void conv_w4_launch(bool resid, const ConvArgs& a, hipStream_t stream) {
-    // the engine launches the 8-wave form with the activation fused into the staging (the 4-wave form and the pre-activated input
-    // it needed lost every A/B from round 1 to round 3; their launches were removed in round 4)
     if (a.ab == nullptr) fail(IRE_ERR_INTERNAL, "internal: conv_w4 needs the GroupNorm coefficients of its input");
     if (a.fp8) {
         if (a.oscale == nullptr) fail(IRE_ERR_INTERNAL, "internal: fp8 conv_w4 needs the per-channel scales");
-        if (resid) launch_w4<128, 8, true, false, 0, true, true>(a, stream); else launch_w4<128, 8, false, false, 0, true, true>(a, stream);
+        if (resid) launch_w4<128, true, true>(a, stream); else launch_w4<128, false, true>(a, stream);
         return;
     }
-    if (a.w4_nt == 64) { if (resid) launch_w4<64, 8, true, false, 0, true>(a, stream); else launch_w4<64, 8, false, false, 0, true>(a, stream); }
-    else { if (resid) launch_w4<128, 8, true, false, 0, true>(a, stream); else launch_w4<128, 8, false, false, 0, true>(a, stream); }
+    if (a.w4_nt == 64) { if (resid) launch_w4<64, true>(a, stream); else launch_w4<64, false>(a, stream); }
+    else { if (resid) launch_w4<128, true>(a, stream); else launch_w4<128, false>(a, stream); }
 }
 
 }  // namespace ire

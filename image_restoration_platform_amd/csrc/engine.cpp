@@ -83,7 +83,7 @@ Engine::Engine(const ire_config& cfg) {
     IRE_HIP(hipMemcpy(d_thr, kGreyThr, sizeof(kGreyThr), hipMemcpyHostToDevice));
     IRE_HIP(hipMemcpy(d_inv, kGreyInv, sizeof(kGreyInv), hipMemcpyHostToDevice));
     tables_ = ClassifierTables{d_lin, d_thr, d_inv};
-    if (stamps_cout_) {
+    if (stamps_cout_ && (!stamps_tl_.empty() || std::getenv("IRE_STAMPS_RAW"))) {      // somebody will dump them
         stamps_dev_.grow(8 * 2 * 64 * 10 * 8);
         IRE_HIP(hipMemset(stamps_dev_.get<void>(), 0, 8 * 2 * 64 * 10 * 8));
     }
@@ -115,30 +115,6 @@ Engine::~Engine() {
             std::fclose(f);
         }
         stamps_dev_.reset();
-    }
-    if (stamps_dev_) {   // diagnostic dump: per-stage phase durations (s_memtime ticks = shader clocks / 100 MHz ref? printed raw)
-        std::vector<unsigned long long> h(8 * 2 * 64 * 10);
-        (void)hipMemcpy(h.data(), stamps_dev_.get<void>(), h.size() * 8, hipMemcpyDeviceToHost);
-        const char* names[5] = {"top->mfma_loop_end", "->vmcnt0", "->epi_barrier1", "->epilogue_end", "->stage_barrier"};
-        for (int wg = 0; wg < 2; ++wg)
-            for (int wv = 0; wv < 2; ++wv) {
-                std::fprintf(stderr, "[stamps] wg %d wave %d (ticks per segment; -1 = not taken)\n", wg, wv * 4);
-                for (int s = 0; s < 40; ++s) {
-                    const unsigned long long* t = &h[(((size_t)wg * 2 + wv) * 64 + s) * 10];
-                    if (!t[0]) continue;
-                    long long d01 = (long long)(t[1] - t[0]), d12 = (long long)(t[2] - t[1]);
-                    long long d23 = t[3] ? (long long)(t[3] - t[2]) : -1, d34 = t[3] ? (long long)(t[4] - t[3]) : (long long)(t[4] - t[2]);
-                    long long d45 = (long long)(t[5] - t[4]);
-                    if (t[6]) std::fprintf(stderr, "      k-steps 0..3=%lld  vmcnt wait=%lld  k-steps 4..8=%lld\n",
-                                           (long long)(t[6] - t[0]), (long long)(t[7] - t[6]), (long long)(t[1] - t[7]));
-                    std::fprintf(stderr, "      raw deltas t1-t0..t5-t4: %lld %lld %lld %lld %lld\n", (long long)(t[1] - t[0]), (long long)(t[2] - t[1]),
-                                 (long long)(t[3] - t[2]), (long long)(t[4] - t[3]), (long long)(t[5] - t[4]));
-                    if (t[3] && t[8]) std::fprintf(stderr, "      epilogue: barrier A=%lld  passes=%lld  reduce+red=%lld\n",
-                                                   (long long)(t[8] - t[3]), (long long)(t[9] - t[8]), (long long)(t[4] - t[9]));
-                    std::fprintf(stderr, "  s%02d %s=%lld %s=%lld %s=%lld %s=%lld %s=%lld | stage=%lld\n", s, names[0], d01, names[1], d12,
-                                 names[2], d23, names[3], d34, names[4], d45, (long long)(t[5] - t[0]));
-                }
-            }
     }
     for (auto& L : lanes_) {
         if (L.stream) (void)hipStreamDestroy(L.stream);
@@ -572,10 +548,7 @@ void Engine::exec_conv(Run& R, const Op& op, const Geo& g) {
     a.walk_rev = R.snake && R.next_rev && p.kernel != K_V1;
     R.next_rev = !a.walk_rev;
     const bool rb = d.kind == CONV_RB1 || d.kind == CONV_RB2;
-    if (stamps_dev_ && rb && d.cout == stamps_cout_ && (d.kind == CONV_RB2) == stamps_resid_ && (!stamps_taken_ || !stamps_tl_.empty() || std::getenv("IRE_STAMPS_RAW"))) {
-        a.stamps = stamps_dev_.get<unsigned long long>();
-        stamps_taken_ = true;
-    }
+    if (stamps_dev_ && rb && d.cout == stamps_cout_ && (d.kind == CONV_RB2) == stamps_resid_) a.stamps = stamps_dev_.get<unsigned long long>();
     if (R.gn_pending) {
         // the deferred GroupNorm finalize of this conv's input: inside the kernel's prologue where it has one (gn_fold.hpp)
         if (p.folds_gn) {

@@ -351,10 +351,10 @@ private:
     BufSet<DeviceMem> ws_;                // what the lanes' LaneBufs point into
 
     // debug / profile
-    // diagnostic stamps (IRE_RB_STAMPS, ablation builds)
+    // diagnostic stamps (IRE_RB_STAMPS selects the launches; dumped by ~Engine as the workgroup timeline IRE_W4_TL or raw, IRE_STAMPS_RAW)
     Buf<DeviceMem> stamps_dev_{BufUse::Persistent};
     int stamps_cout_ = 0;
-    bool stamps_resid_ = false, stamps_taken_ = false;
+    bool stamps_resid_ = false;
     std::string stamps_tl_;
     bool capture_ = false;
     std::map<std::string, std::vector<float>> captured_;

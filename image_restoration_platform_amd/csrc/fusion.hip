@@ -102,9 +102,7 @@ struct SadCfg {
     static_assert(SR * TWD % 256 == 0 && M % 4 == 0, "tile shape");
 };
 
-#ifndef FUSE_FL
-#define FUSE_FL 16      // loads in flight per thread in the last workgroup's row sum (build-time A/B)
-#endif
+#define FUSE_FL 16      // loads in flight per thread in the last workgroup's row sum (a #define: tests/test_fusion_cases.py reads it from this file)
 constexpr int FUSE_SAD_GRID = 512;   // workgroups per view at most (= rows of `part` per view)
 
 template <int MODE>

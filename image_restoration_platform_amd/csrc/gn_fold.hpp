@@ -47,10 +47,6 @@ __device__ __forceinline__ double gnf_xlane_add(double v, int ctrl_kind) {
 }
 
 __device__ __forceinline__ void gn_fold(const ConvArgs& a, unsigned char* smem, int img_lo, int img_hi, int nthr_used = 0, float2* lds_ab = nullptr) {
-#if defined(IRE_FOLD_ABL) && IRE_FOLD_ABL == 1      // timing ablation (results wrong by design): the consumers read stale coefficients
-    __syncthreads();
-    return;
-#endif
     const int tid = threadIdx.x, nthr = nthr_used ? nthr_used : (int)blockDim.x;
     const bool act = tid < nthr;
     double* red = reinterpret_cast<double*>(smem);                       // [waves][8 groups][2]

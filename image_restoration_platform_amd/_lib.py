@@ -135,6 +135,7 @@ SYMBOLS = {
     "ire_debug_jpeg_huffman": (_i, [_vp, _vp, _i, _vp, _vp]),
     "ire_debug_jpeg_progressive_from_coefs": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
     "ire_debug_poison_scratch": (_i, [_vp, _i, _vp]),
+    "ire_debug_gn_finalize": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "ire_debug_capture": (_i, [_vp, _i]),
     "ire_debug_activation": (_i, [_vp, ctypes.c_char_p, _vp, ctypes.POINTER(ctypes.c_size_t)]),
     "ire_profile_enable": (_i, [_vp, _i]),

@@ -1124,6 +1124,14 @@ int ire_debug_poison_scratch(ire_engine* e, int byte, uint64_t* bytes_filled) {
     });
 }
 
+int ire_debug_gn_finalize(ire_engine* e, const float* stats, int nimg, int parts, int C, int hw, const float* gamma, const float* beta,
+                          const float* film, int film_stride, int film_off, float* ab_out) {
+    return guarded([&] {
+        Engine& E = eng(e);
+        on_stream(E, E.main_stream(), [&] { E.debug_gn_finalize(stats, nimg, parts, C, hw, gamma, beta, film, film_stride, film_off, ab_out); });
+    });
+}
+
 int ire_debug_capture(ire_engine* e, int on) {
     return guarded([&] {
         Engine& E = eng(e);

@@ -442,6 +442,31 @@ uint64_t Engine::debug_poison_scratch(int byte) {
     IRE_HIP(hipDeviceSynchronize());
     return filled;
 }
+// ire_debug_gn_finalize: host partials through gn_finalize_kernel (gn.hip: gn_fold with 512 threads, one workgroup per image), the
+// coefficients copied back (synchronous; tests only)
+void Engine::debug_gn_finalize(const float* stats, int nimg, int parts, int C, int hw, const float* gamma, const float* beta, const float* film,
+                               int film_stride, int film_off, float* ab_out) {
+    if (!stats || !gamma || !beta || !ab_out) fail(IRE_ERR_INVALID_INPUT, "invalid arguments to ire_debug_gn_finalize: null pointer");
+    if (C != 32 && C != 64 && C != 128 && C != 256) fail(IRE_ERR_INVALID_INPUT, "invalid channels for ire_debug_gn_finalize: expected 32, 64, 128 or 256");
+    if (nimg < 1 || nimg > 65535) fail(IRE_ERR_INVALID_INPUT, "invalid images for ire_debug_gn_finalize: expected 1..65535");
+    if (parts < 1 || parts > (1 << 20)) fail(IRE_ERR_INVALID_INPUT, "invalid parts for ire_debug_gn_finalize: expected 1..2^20");
+    if (hw < 1) fail(IRE_ERR_INVALID_INPUT, "invalid hw for ire_debug_gn_finalize: expected >= 1");
+    if (film && (film_off < 0 || film_stride < 2 * C || film_off > film_stride - 2 * C))
+        fail(IRE_ERR_INVALID_INPUT, "invalid film window for ire_debug_gn_finalize: film_off + 2 C leaves the row of film_stride");
+    IRE_HIP(hipSetDevice(device_));
+    const size_t nstats = (size_t)nimg * parts * 16, nfilm = film ? (size_t)nimg * film_stride : 0;
+    Buf<DeviceMem> d_stats(sizeof(float) * nstats), d_gamma(sizeof(float) * C), d_beta(sizeof(float) * C), d_film(sizeof(float) * std::max<size_t>(nfilm, 1)),
+        d_ab(sizeof(float2) * (size_t)nimg * C);
+    hipStream_t s = main_stream_;
+    IRE_HIP(hipMemcpyAsync(d_stats.get<float>(), stats, sizeof(float) * nstats, hipMemcpyHostToDevice, s));
+    IRE_HIP(hipMemcpyAsync(d_gamma.get<float>(), gamma, sizeof(float) * C, hipMemcpyHostToDevice, s));
+    IRE_HIP(hipMemcpyAsync(d_beta.get<float>(), beta, sizeof(float) * C, hipMemcpyHostToDevice, s));
+    if (film) IRE_HIP(hipMemcpyAsync(d_film.get<float>(), film, sizeof(float) * nfilm, hipMemcpyHostToDevice, s));
+    gn_finalize_launch(d_stats.get<float>(), nimg, parts, C, hw, d_gamma.get<float>(), d_beta.get<float>(), film ? d_film.get<float>() : nullptr,
+                       film_stride, film_off, d_ab.get<float2>(), s);
+    IRE_HIP(hipMemcpyAsync(ab_out, d_ab.get<float2>(), sizeof(float2) * (size_t)nimg * C, hipMemcpyDeviceToHost, s));
+    IRE_HIP(hipStreamSynchronize(s));
+}
 
 // ------------------------------------------------------------------------------------------------
 // RestoreNet-v0 schedule: a program of ops (built once per weight load), executed op by op

@@ -234,6 +234,8 @@ public:
 
     void debug_sums(int n, uint64_t* out);
     uint64_t debug_poison_scratch(int byte);      // -> bytes filled
+    void debug_gn_finalize(const float* stats, int nimg, int parts, int C, int hw, const float* gamma, const float* beta, const float* film,
+                           int film_stride, int film_off, float* ab_out);
     void debug_capture(bool on) { capture_ = on; captured_.clear(); }
     bool debug_activation(const std::string& name, float* out, size_t* count);
 

@@ -861,6 +861,21 @@ class Engine:
         self._check(self._lib.ire_debug_poison_scratch(self._h, int(byte), ctypes.byref(n)))
         return n.value
 
+    def debug_gn_finalize(self, stats, hw, gamma, beta, film=None, film_off=0):
+        """GroupNorm partials [nimg, parts, 8, 2] (sum, sum of squares per tile and group) of tensors of `hw` pixels and C = len(gamma)
+        channels -> the (A, B) of y = x A + B as [nimg, C, 2] float32, from the standalone finalize kernel (ire_debug_gn_finalize).
+        film: [nimg, film_stride] or None; the scale at film_off + c, the shift at film_off + C + c."""
+        st = np.ascontiguousarray(stats, dtype=np.float32)
+        assert st.ndim == 4 and st.shape[2:] == (8, 2), st.shape
+        g, b = (np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in (gamma, beta))
+        assert g.size == b.size
+        fm = None if film is None else np.ascontiguousarray(film, dtype=np.float32)
+        assert fm is None or (fm.ndim == 2 and fm.shape[0] == st.shape[0]), "film: one row per image"
+        out = np.zeros((st.shape[0], g.size, 2), np.float32)
+        self._check(self._lib.ire_debug_gn_finalize(self._h, _ptr(st), st.shape[0], st.shape[1], g.size, int(hw), _ptr(g), _ptr(b), _ptr(fm),
+                                                    0 if fm is None else fm.shape[1], int(film_off), _ptr(out)))
+        return out
+
     def debug_capture(self, on=True):
         self._check(self._lib.ire_debug_capture(self._h, int(on)))
 

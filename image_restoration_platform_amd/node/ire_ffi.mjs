@@ -99,6 +99,7 @@ export function bindIre(libPath) {
     ire_debug_jpeg_huffman: ['int', [P, P, 'int', P, P]],
     ire_debug_jpeg_progressive_from_coefs: ['int', [P, P, 'int', 'int', 'int', 'int', 'int', P, 'size_t', P]],
     ire_debug_poison_scratch: ['int', [P, 'int', P]],
+    ire_debug_gn_finalize: ['int', [P, P, 'int', 'int', 'int', 'int', P, P, P, 'int', 'int', P]],
     ire_debug_capture: ['int', [P, 'int']],
     ire_debug_activation: ['int', [P, 'string', P, P]],
     ire_profile_enable: ['int', [P, 'int']],

@@ -648,6 +648,13 @@ int ire_debug_jpeg_progressive_from_coefs(ire_engine* e, const int16_t* coefs, i
  * tables, tickets that clean themselves: DESIGN.md "Buffer ownership") are left alone.  The caller submits no job while the call runs and keeps
  * every other engine of the process, and every strip session, idle meanwhile (tests only). */
 int ire_debug_poison_scratch(ire_engine* e, int byte, uint64_t* bytes_filled);
+/* The standalone GroupNorm finalize (csrc/gn.hip: one workgroup per image running csrc/gn_fold.hpp's gn_fold, the function every
+ * activated convolution runs in its prologue) on partials given: stats [nimg][parts][8][2] (sum, sum of squares) per tile and group,
+ * C in {32, 64, 128, 256} channels, hw pixels per image, gamma / beta [C]; film (may be null) [nimg][film_stride] with the scale at
+ * film_off + c and the shift at film_off + C + c.  ab_out receives (A, B) of y = x A + B as [nimg][C][2].  nimg in 1..65535, parts in
+ * 1..2^20.  All pointers are host memory; synchronous (tests only). */
+int ire_debug_gn_finalize(ire_engine* e, const float* stats, int nimg, int parts, int C, int hw, const float* gamma, const float* beta,
+                          const float* film, int film_stride, int film_off, float* ab_out);
 /* Turn per-layer capture on/off (slow: synchronises after every layer; tests only). */
 int ire_debug_capture(ire_engine* e, int on);
 /* Copy one named intermediate activation of the last ire_restore* call to host as float32 NHWC.

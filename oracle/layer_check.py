@@ -62,6 +62,21 @@ exceeds the variance) is an order of magnitude wider than the SiLU sequence's; i
 uncertain on the reference alone.  Taking (A, B) from the engine keeps the window at the SiLU sequence's own error and still checks
 the statistics, against the bound that belongs to them.
 
+The partials-level check (coeffs_from_partials; tests/gn_cases.py, tests/test_gn_fold_gpu.py): gn_fold.hpp's reduction takes three
+different paths per thread -- passes of its 8-chain unrolled loop, a tail loop, or no tile at all -- chosen by P, the partials per
+image, and the shapes run() can afford stay below the P = 449 at which the first lane enters the unrolled loop.  So the standalone
+finalize is also run on partials GIVEN to it (ire_debug_gn_finalize) at every pass structure, and judged against the same
+coefficient formulas with what then remains of the statistics' bound: the partials are the input, so D = 0; gn_fold adds P
+floats in double in a fixed order, in error by at most P 2^-53 sum|partial| / cnt on the mean and on the mean of squares (the bound of a
+chain of P additions; gn_fold's tree is at most P / 512 + 21 deep, and from P = 26 on what it leaves unused covers the four double
+operations between the sums and the variance -- two divisions, a square, a difference, 2^-53 relative each -- which have no term of
+their own: the cases below that P are built so that all four are exact); mean and rstd rounded to float
+and the float tail as above, one u per written operation (which covers a contracted fma: fewer roundings, not more).  An error of
+one partial in P shifts a moment by 1 / P of it, ~2^-17 at the largest accepted image against a bound of ~2^-23: the tests' coded
+partials are built so that no single dropped, repeated or misplaced partial stays inside it.  In the network, run_coeffs() applies
+check_coeffs alone, with the moments taken in chunks from the captured float32 tensors, at shapes whose levels reach the unrolled
+loop (1024 x 1024, 272 x 1000).
+
 Final pixels: floor(clamp(in + y, 0, 255) + 0.5) is monotone in y as well; the two fp32 additions add u (|in + y| + 256) to b, and
 the engine's pixel must lie in [pixel(exact - b), pixel(exact + b)]: equal to the reference except within b of a .5 boundary,
 and there within 1 LSB.
@@ -142,17 +157,23 @@ def film_vectors(weights, scores):
     return cond @ w.T + b[None, :], 8 * U * (np.abs(cond) @ np.abs(w).T + np.abs(b)[None, :])
 
 
-def _gn_coeffs(x, g, b, s, t, ds, dt):
-    """x [N,C,H,W] float64 (stored bf16 values); per-image, per-channel (A, B) of y = x A + B in float64 and their error bounds
-    (dA, dB) for the engine's float path (module docstring: statistics, coefficients)."""
-    n, c = x.shape[:2]
-    xg = x.reshape(n, 8, -1)
-    cnt = xg.shape[2]
-    mean, mabs, msq = xg.mean(axis=2), np.abs(xg).mean(axis=2), (xg * xg).mean(axis=2)
+def _gn_moments(x):
+    """x [N,C,H,W] float64 -> per image and group (mean, mean|x|, mean x^2), each [N, 8]."""
+    xg = x.reshape(x.shape[0], 8, -1)
+    return xg.mean(axis=2), np.abs(xg).mean(axis=2), (xg * xg).mean(axis=2)
+
+
+def _coeffs_from_moments(mean, mabs, msq, c, g, b, s, t, ds, dt, stat_depth=STAT_DEPTH, e_mean=None, e_msq=None):
+    """Per-group moments [N, 8] of a tensor of c channels -> per-image, per-channel (A, B) of y = x A + B in float64 and their error
+    bounds (dA, dB) for the engine's float path (module docstring: statistics, coefficients).  stat_depth: the depth of the fp32
+    summation behind the moments the engine used (0: its partials are the given ones).  e_mean, e_msq [N, 8] (optional): a further
+    absolute error of the engine's mean and mean x^2 (coeffs_from_partials: the double summation)."""
     var = np.maximum(msq - mean * mean, 0.0)
     rstd = 1.0 / np.sqrt(var + GN_EPS)
-    d_mean = STAT_DEPTH * U * mabs + U * np.abs(mean)
-    d_var = STAT_DEPTH * U * (msq + 2.0 * np.abs(mean) * mabs)
+    d_mean = stat_depth * U * mabs + U * np.abs(mean)
+    d_var = stat_depth * U * (msq + 2.0 * np.abs(mean) * mabs)
+    if e_mean is not None:
+        d_mean, d_var = d_mean + e_mean, d_var + e_msq + 2.0 * np.abs(mean) * e_mean
     e_rstd = 0.5 * d_var / (var + GN_EPS) + U                     # relative
     rep = c // 8
     mean, rstd, d_mean, e_rstd = (np.repeat(v, rep, axis=1) for v in (mean, rstd, d_mean, e_rstd))
@@ -174,6 +195,51 @@ def _gn_coeffs(x, g, b, s, t, ds, dt):
     return A, B, dA, dB
 
 
+def _gn_coeffs(x, g, b, s, t, ds, dt):
+    """x [N,C,H,W] float64 (stored bf16 values) -> (A, B, dA, dB) [N, C] of _coeffs_from_moments at the depth of the tile partials."""
+    return _coeffs_from_moments(*_gn_moments(x), x.shape[1], g, b, s, t, ds, dt)
+
+
+def partial_sums(stats, exact=False):
+    """stats [N, P, 8, 2] float32 -> (sum, sum of absolute values) over the P partials, each [N, 8, 2] float64.  Summed image by image
+    in float64 (exact for integer-valued partials below 2^53); exact=True: math.fsum, correctly rounded for any floats."""
+    st = np.asarray(stats, dtype=np.float32)
+    assert st.ndim == 4 and st.shape[2:] == (8, 2), st.shape
+    tot, mag = np.zeros((st.shape[0], 8, 2)), np.zeros((st.shape[0], 8, 2))
+    for i in range(st.shape[0]):
+        v = st[i].astype(np.float64)
+        if exact:
+            import math
+            for g in range(8):
+                for k in range(2):
+                    tot[i, g, k], mag[i, g, k] = math.fsum(v[:, g, k]), math.fsum(np.abs(v[:, g, k]))
+        else:
+            tot[i], mag[i] = v.sum(axis=0), np.abs(v).sum(axis=0)
+    return tot, mag
+
+
+def coeffs_from_sums(tot, mag, parts, hw, C, gamma, beta, s=None, t=None):
+    """coeffs_from_partials behind the summation: tot, mag [N, 8, 2] as partial_sums returns them, parts = P."""
+    n = tot.shape[0]
+    assert tot.shape == mag.shape == (n, 8, 2) and C % 8 == 0
+    cnt = float(hw) * (C // 8)
+    e = parts * 2.0 ** -53 * mag / cnt
+    zero = np.zeros((n, C))
+    s, t = (zero if v is None else np.asarray(v, dtype=np.float32).astype(np.float64).reshape(n, C) for v in (s, t))
+    return _coeffs_from_moments(tot[:, :, 0] / cnt, mag[:, :, 0] / cnt, tot[:, :, 1] / cnt, C, np.asarray(gamma), np.asarray(beta), s, t, zero, zero,
+                                stat_depth=0, e_mean=e[:, :, 0], e_msq=e[:, :, 1])
+
+
+def coeffs_from_partials(stats, hw, C, gamma, beta, s=None, t=None, exact=False):
+    """(A, B, dA, dB) [N, C] of gn_fold.hpp on GIVEN partials: stats [N, P, 8, 2] float32 (sum, sum of squares per tile and group) of
+    tensors of hw pixels and C channels, gamma / beta [C], the FiLM scale and shift s, t [N, C] as the floats the kernel reads (None: no
+    FiLM).  The partials are summed in float64 (exact=True: math.fsum).  Nothing in front of the partials is judged, so
+    stat_depth = 0 and no FiLM error; what remains of the statistics' bound is gn_fold's own summation, P terms in double in some
+    order: at most P 2^-53 sum|partial| / cnt on the mean and on the mean of squares (module docstring: the partials-level check)."""
+    tot, mag = partial_sums(stats, exact)
+    return coeffs_from_sums(tot, mag, np.shape(stats)[1], hw, C, gamma, beta, s, t)
+
+
 def reference_coeffs(x, weights, gn_prefix, level, film, d_film):
     """(A, B, dA, dB) [N, C] of the GroupNorm + FiLM in front of a convolution, from its stored input x."""
     c = x.shape[1]
@@ -193,6 +259,14 @@ def check_coeffs(name, ab, ref):
     return ("%s: GroupNorm+FiLM coefficients outside their bound for %d (image, channel) pairs; first: image %d channel %d (group %d): "
             "engine A %.9g B %.9g, exact A %.9g +- %.3g B %.9g +- %.3g"
             % (name, int(bad.sum()), n, c, c // (A.shape[1] // 8), ab[n, c, 0], ab[n, c, 1], A[n, c], dA[n, c], B[n, c], dB[n, c]))
+
+
+def coeff_share(ab, ref):
+    """Largest |engine - exact| / bound over all (image, channel) pairs and both coefficients (0 / 0 counts as 0): information."""
+    A, B, dA, dB = ref
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.concatenate([(np.abs(ab[:, :, 0] - A) / dA).ravel(), (np.abs(ab[:, :, 1] - B) / dB).ravel()])
+    return float(np.nan_to_num(r, nan=0.0, posinf=np.inf).max())
 
 
 def activate(x, ab, fp8=False):
@@ -389,6 +463,11 @@ def layer_names(up_mode="fused"):
     return names + ["pixels"]
 
 
+def gn_layer_names(up_mode="fused"):
+    """The layers whose convolution applies a GroupNorm (their coefficients are captured as '<layer>.ab'; the head's as 'head.ab')."""
+    return [nm for nm in layer_names(up_mode) if ".rb" in nm or nm == "pixels"]
+
+
 def _level(name):
     if name in ("stem", "pixels"):
         return 0
@@ -413,6 +492,8 @@ class NetworkCheck:
         self.get_raw, self.pixels, self.fp8, self.up_mode = get, np.asarray(pixels), fp8, up_mode
         assert up_mode in ("fused", "subpix", "plain")
         self._cache = {}
+        self.chunk = 1 << 18                      # run_coeffs: elements per chunk of the float64 moments
+        self.coeff_share = {}                     # run_coeffs: per layer the largest share of the coefficients' bound in use
 
     def get(self, name):
         if name == "image":
@@ -512,6 +593,48 @@ class NetworkCheck:
     def run(self, names=None):
         """-> {name: LayerReport} for the listed layers (default: all of this up_mode)."""
         return {nm: self.check(nm) for nm in (names or layer_names(self.up_mode))}
+
+    def _chunked_moments(self, src, level, chunk=None):
+        """(mean, mean|x|, mean x^2) [N, 8] and C of the captured tensor `src`, straight from its float32 NHWC array in chunks of about
+        `chunk` elements (cache-sized: the walk is bound by memory) into float64 accumulators; no float64 copy of the tensor is made or kept.  The products of bf16 values are exact
+        in float64; a sum of N terms in any order is within N 2^-53 of sum|x| relative (N <= 2^22 per group here: 2^-31, against a
+        bound of STAT_DEPTH 2^-24)."""
+        n, h, w, _ = self.images.shape
+        h, w = h >> level, w >> level
+        a = np.asarray(self.get_raw(src), dtype=np.float32)
+        c = a.size // (n * h * w)
+        assert c % 8 == 0 and c * n * h * w == a.size, (src, a.size)
+        a = a.reshape(n, h * w, c)
+        acc = np.zeros((3, n, c))                                    # per channel; the channels of a group are added last
+        step = max(1, (chunk or self.chunk) // c)
+        for i in range(n):
+            for r in range(0, h * w, step):
+                v = a[i, r:r + step].astype(np.float64)
+                acc[0, i] += v.sum(axis=0)
+                acc[2, i] += np.einsum("pc,pc->c", v, v)
+                acc[1, i] += np.abs(v, out=v).sum(axis=0)
+        acc = acc.reshape(3, n, 8, c // 8).sum(axis=3)
+        return acc[0] / (h * w * (c // 8)), acc[1] / (h * w * (c // 8)), acc[2] / (h * w * (c // 8)), c
+
+    def run_coeffs(self, names=None):
+        """The coefficients alone: for every listed layer that applies a GroupNorm (default: all of them; `pixels` is the head, captured
+        as head.ab) the captured (A, B) against the float64 GroupNorm + FiLM of the captured input, within check_coeffs' bound ->
+        {name: '' or the message}.  No convolution is evaluated and no tensor is converted whole, so the walk is affordable at shapes
+        where run() is not (1024 x 1024: tens of thousands of tiles per image for gn_fold.hpp to add up)."""
+        out = {}
+        for nm in (names or gn_layer_names(self.up_mode)):
+            assert nm == "pixels" or ".rb" in nm, nm + ": no GroupNorm in front of this layer"
+            prefix = nm[:-2] if nm.endswith(".h") else nm
+            gn = "head.gn" if nm == "pixels" else prefix + (".gn1" if nm.endswith(".h") else ".gn2")
+            level = _level(nm)
+            mean, mabs, msq, c = self._chunked_moments(layer_inputs(nm)[0], level)
+            off = FILM_OFFSETS[level]
+            ref = _coeffs_from_moments(mean, mabs, msq, c, self.w[gn + ".g"], self.w[gn + ".b"], self.film[:, off:off + c], self.film[:, off + c:off + 2 * c],
+                                       self.d_film[:, off:off + c], self.d_film[:, off + c:off + 2 * c])
+            ab = np.asarray(self.get_raw(("head" if nm == "pixels" else nm) + ".ab"), dtype=np.float32).astype(np.float64).reshape(mean.shape[0], c, 2)
+            out[nm] = check_coeffs("head" if nm == "pixels" else nm, ab, ref)
+            self.coeff_share[nm] = coeff_share(ab, ref)
+        return out
 
 
 def assert_network(weights, images, scores, get, pixels, fp8=False, up_mode="fused", names=None, label=""):
